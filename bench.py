@@ -24,7 +24,7 @@ ROOT = pathlib.Path(__file__).resolve().parent
 sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tests"))
 
-from benchlegs import cpu, headline, line as bench_line, realtime, scaling, variants  # noqa: E402
+from benchlegs import cpu, dump, headline, line as bench_line, realtime, scaling, variants  # noqa: E402
 from benchlegs.common import HBM_PEAK_GBS, Job, build_strips, dist_backend, dist_device, gate_events, gate_open  # noqa: E402,F401  (re-exported: tests and tools import them from here)
 from benchlegs.fir import fir_leg  # noqa: E402
 from benchlegs.video import video_leg  # noqa: E402
@@ -61,6 +61,7 @@ def parse_args(argv=None):
                     help="N > 1: independent 8-layer streams per rank (weak scaling), or ONE stream cut into row bands over the ranks (strong scaling)")
     ap.add_argument("--full-out", default=str(ROOT / "bench_full.json"), help="where rank 0 writes everything the legs measured")
     ap.add_argument("--headline-only", action="store_true", help="every secondary leg off (profiler passes)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the Master / Cue buses of the last timed step to DIR/*.npy (benchlegs/dump.py)")
     for flag, what in (("cpu-baseline", "the CPU oracle timed on this host"), ("buses-leg", "the group-bus topology leg"), ("one-stream-leg", "the MX_OVERLAP_AUTO=0 leg"),
                        ("held-leg", "the held-gates comparison leg"), ("other-policy-leg", "N > 1: the second tick policy"), ("scaling-probe", "the one-GPU model of 2 / 4 / 8 ranks"),
                        ("profile", "per-kernel hipEvents in the timed region (roofline omitted)"), ("t-sweep", "the shorter-submission legs"), ("realtime", "the one-tick-per-submission leg"),
@@ -69,6 +70,8 @@ def parse_args(argv=None):
         ap.add_argument(f"--no-{flag}", action="store_true", help=f"skip {what}")
     ap.add_argument("--no-scaled-leg", dest="no_other_policy_leg", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.headline_only:
         for k in ("cpu_baseline", "buses_leg", "one_stream_leg", "held_leg", "other_policy_leg", "scaling_probe", "t_sweep", "realtime", "north_star", "contract_leg", "rate_leg",
                   "material_leg"):
@@ -181,6 +184,7 @@ def main(argv=None):
         dt = timed_region(args.warmup, args.steps)                      # THE timed region: exactly K steps
         nxt = args.warmup + args.steps
         n_run = nxt                                                    # submissions the graph has run so far (the oracle replay compares the LAST one)
+        dumped = dump.collect(job, ex, nxt - 1) if args.dump_outputs and rank == 0 else None    # (before the N > 1 path's extra steps reuse its slots)
         if use_dist and not args.no_profile:
             g.profile_enable(True)
             for i in range(3):
@@ -302,6 +306,8 @@ def main(argv=None):
                 out["fir_resample"]["cpu_baseline"] = dict(cpu.fir(), build=note)
             out["cpu_baseline"] = cpu.audio(Workspace, synth, abi, args.strips, SR, note)
             out["cpu_baseline_all_cores"] = dict(cpu.audio_all_cores(Workspace, synth, abi, shard, args.strips, SR), build=note)
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": str(args.dump_outputs), "shapes": dump.write(args.dump_outputs, dumped)}
         full_text = json.dumps(out, allow_nan=False)
         try:
             pathlib.Path(args.full_out).write_text(full_text + "\n")

@@ -51,3 +51,25 @@ def test_a_nan_or_an_oversized_line_is_refused():
 def test_bench_py_stays_a_thin_assembler():
     n = len((ROOT / "bench.py").read_text().splitlines())
     assert n <= 400, f"bench.py has {n} lines: legs belong in benchlegs/"
+
+
+def test_dump_outputs_keeps_a_fixed_seeded_tick_sample_under_the_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs (benchlegs/dump.py): written whole while it fits, above the cap the same seeded ticks of every bus, listed in ticks.npy."""
+    import numpy as np
+    from benchlegs import dump
+
+    rng = np.random.default_rng(5)
+    bufs = {"master": rng.standard_normal((40, 8, 2), dtype=np.float32), "cue": rng.standard_normal((40, 8, 2), dtype=np.float32)}
+    assert dump.write(tmp_path / "whole", bufs) == {"master": [40, 8, 2], "cue": [40, 8, 2]}
+    assert np.array_equal(np.load(tmp_path / "whole" / "master.npy"), bufs["master"]) and not (tmp_path / "whole" / "ticks.npy").exists()
+    monkeypatch.setattr(dump, "CAP_BYTES", 40 * 8 * 2 * 4)                  # room for half of the ticks
+    for run in ("a", "b"):
+        dump.write(tmp_path / run, bufs)
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["cue.npy", "master.npy", "ticks.npy"] and sum((tmp_path / "a" / f).stat().st_size for f in files) <= dump.CAP_BYTES + 3 * 128   # (+ .npy headers)
+    ticks = np.load(tmp_path / "a" / "ticks.npy")
+    assert ticks.dtype == np.float64 and ticks.size == (2560 - 8 * 40) // 128 and np.all(np.diff(ticks) > 0)
+    for name in ("master", "cue"):
+        got = np.load(tmp_path / "a" / f"{name}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, bufs[name][ticks.astype(int)])
+    assert all(np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)) for f in files)

@@ -2,6 +2,7 @@
 restatement of Engine::run_tick semantics, and that the C-ABI library loads and exports every
 symbol include/mixlab_gpu.h declares (no compute calls without a GPU)."""
 import ctypes
+import hashlib
 import pathlib
 import re
 
@@ -15,7 +16,6 @@ from mixlab_amd.workspace import Workspace
 
 ROOT = pathlib.Path(__file__).resolve().parent.parent
 GOLDEN = ROOT / "tests" / "golden"
-REF_FIXTURES = pathlib.Path("/root/reference/fixtures/module/eq_three")
 SPT = 735
 
 
@@ -66,16 +66,17 @@ def test_oracle_contract_mode_is_within_one_ulp_of_the_reference_golden_prefix_a
         assert synth.ulp_diff(a, b).max() <= 1
 
 
-@pytest.mark.skipif(not REF_FIXTURES.exists(), reason="full fixture only exists where /root/reference is mounted")
 def test_oracle_eq_three_matches_full_reference_fixture():
-    x = np.fromfile(REF_FIXTURES / "chronos.f32.raw", dtype="<f4")
-    y = np.fromfile(REF_FIXTURES / "chronos-eq.f32.raw", dtype="<f4")
+    # the reference's fixture files, committed as the prefix above + the samples after it (tests/golden/make_eq_three_prefix.py)
+    def whole(stem, sha256):
+        data = (GOLDEN / f"{stem}_prefix131072.f32.raw").read_bytes() + (GOLDEN / f"{stem}_from131072.f32.raw").read_bytes()
+        assert hashlib.sha256(data).hexdigest() == sha256, f"{stem}: prefix + rest is not the reference's file"
+        return np.frombuffer(data, dtype="<f4")
+    x = whole("eq_three_chronos", "55d75ec7ea2361d10abc1bb7c7a4201e183101bbb2400523319521ac440de292")
+    y = whole("eq_three_chronos-eq", "e35db948918dd8a2f6bd02810565298274ac6919104343fe5c8010fc36d8fb11")
     assert x.size == 355285
     st = oracle.eq_three_new(44100.0)
     assert np.array_equal(bits(oracle.eq_three_run(st, (4.0, 0.0, 4.0), x)), bits(y))
-    # and the committed prefix really is a prefix of the reference files
-    assert np.array_equal(np.fromfile(GOLDEN / "eq_three_chronos_prefix131072.f32.raw", dtype="<f4"), x[:131072])
-    assert np.array_equal(np.fromfile(GOLDEN / "eq_three_chronos-eq_prefix131072.f32.raw", dtype="<f4"), y[:131072])
 
 
 # ---------------- oracle module semantics (source text is the only spec for these) ----------------

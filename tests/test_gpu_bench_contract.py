@@ -114,8 +114,9 @@ def test_two_rank_rccl_job_is_bit_exact_when_two_gpus_are_visible(tmp_path):
     the fixed-T policy runs beside it."""
     sys.path.insert(0, str(ROOT))
     from mixlab_amd import abi
-    if abi.lib.mx_device_count() < 2:
-        pytest.skip("needs two GPUs")
+    n = abi.lib.mx_device_count()
+    if n < 2:
+        pytest.skip(f"needs 2 GPUs, found {n}")
     for k, mode in enumerate(("allgather", "slices")):
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(29571 + k),
                str(ROOT / "bench.py"), "--gpus", "2", "--exchange", mode, *SMALL]
@@ -146,7 +147,9 @@ def _multi_rank_on_one_gpu(world, extra, tmp_path, small=None):
     return _strict(lines[0]), _strict(full.read_text())
 
 
-@pytest.mark.parametrize("world,mode,vshard", [(2, "allgather", "replicas"), (4, "slices", "bands"), (8, "auto", "replicas")])
+# at most 4 ranks: with the launcher and this test's own process that is 6 processes holding the one GPU (the N = 8 exchange runs in-process in
+# test_gpu_config5_sharded.py)
+@pytest.mark.parametrize("world,mode,vshard", [(2, "allgather", "replicas"), (4, "slices", "bands"), (4, "auto", "replicas")])
 def test_the_drivers_multi_rank_launch_line_on_one_gpu_through_the_rccl_double(world, mode, vshard, tmp_path):
     """Times mean nothing here; what is checked is the N > 1 code of bench.py and of mx_exchange.cpp as the driver will run it: the T x N tick policy as the headline, the
     fixed-T policy beside it, both exchanges bit-exact on every rank against the host sum in rank order, the oracle replay of the last submission, the video leg."""
@@ -183,3 +186,20 @@ def test_flags_of_the_multi_rank_path_that_no_other_test_drives(world, extra, tm
         assert ex["parity_check"]["all_ranks"] == "bit-exact" and rec["other_policy"]["parity"]["verdict"] == "bit-exact"
     fixed = "--fixed-ticks" in extra
     assert line["config"]["ticks_per_step"] == (64 if fixed else 64 * world) and rec["other_policy"]["ticks_per_step"] == (64 * world if fixed else 64)
+
+
+def test_dump_outputs_are_the_last_timed_step_and_the_same_from_run_to_run(tmp_path):
+    """--dump-outputs DIR: the Master / Cue buses of the last timed step as float32 [ticks, samples_per_tick, 2]; the same arguments give the same files, and the
+    single-rank exchange path (--force-combine) hands its caller the same buses as the plain path."""
+    import numpy as np
+    dirs = {}
+    for run, extra in (("a", []), ("b", []), ("combined", ["--force-combine", "--exchange", "allgather"])):
+        dirs[run] = tmp_path / run
+        (tmp_path / f"full_{run}").mkdir()
+        line, full = _run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", *SMALL, *extra, "--dump-outputs", str(dirs[run])], tmp_path / f"full_{run}")
+        assert line["steps"] == 3 and line["ms_per_step"] > 0 and full["dump_outputs"]["shapes"] == {"master": [64, 800, 2], "cue": [64, 800, 2]}
+    for name in ("master", "cue"):
+        a = np.load(dirs["a"] / f"{name}.npy")
+        assert a.dtype == np.float32 and a.shape == (64, 800, 2) and np.any(a != 0) and np.all(np.isfinite(a))
+        for other in ("b", "combined"):
+            assert np.array_equal(a.view(np.uint32), np.load(dirs[other] / f"{name}.npy").view(np.uint32)), f"{name}: {other}"

@@ -275,7 +275,7 @@ def test_headline_shape_bank_released_behind_the_gate_equals_the_one_stream_bank
         buf = np.tile(synth.noise(j, 256 * SPT48), T // 256)
         g.write_source(s, buf, T)
         one.bind_source_device(s, g.output_device_ptr(s, 0)[0])
-    hip = C.CDLL("libamdhip64.so")
+    hip = C.CDLL(str(abi.LIB_PATH))    # the HIP runtime libmixlab_gpu.so is bound to (by name, "libamdhip64.so" is torch's copy once torch is imported)
     pm, fpt = g.output_device_ptr(mix, 0)
     pc, _ = g.output_device_ptr(mix, 1)
     n = fpt * T

@@ -139,7 +139,7 @@ def test_a_bank_released_by_the_next_runs_eq_three_launch_is_the_oracles():
     g = ws.build(max_ticks_per_run=batch, flags=abi.FLAG_OVERLAP_TAIL)   # (the flag, not the automatism: taking the buses' device pointers would end that)
     tail = g.tail_stream()
     assert tail is not None
-    hip = C.CDLL("libamdhip64.so")
+    hip = C.CDLL(str(abi.LIB_PATH))    # the HIP runtime libmixlab_gpu.so is bound to (by name, "libamdhip64.so" is torch's copy once torch is imported)
     pm, nm = g.output_device_ptr(mix, 0)
     pc, _ = g.output_device_ptr(mix, 1)
     assert nm == 2 * SPT                                   # floats per tick; the buffer holds the run's ticks back to back
@@ -261,7 +261,7 @@ def test_group_buses_the_tail_is_the_bank_and_the_master_above_it():
             for j, gm in enumerate(gms):
                 acc["g"][j].append(og.output(gm, 0).copy())
         want.append((np.concatenate(acc["m"]), np.concatenate(acc["c"]), [np.concatenate(x) for x in acc["g"]]))
-    hip = C.CDLL("libamdhip64.so")
+    hip = C.CDLL(str(abi.LIB_PATH))
     for flags in (abi.FLAG_OVERLAP_TAIL, 0):
         g = ws.build(max_ticks_per_run=batch, flags=flags)
         tail = g.tail_stream()
@@ -326,7 +326,7 @@ def test_taking_a_raw_pointer_ends_the_automatism_and_leaves_a_one_stream_graph(
         want.append((np.concatenate(m), np.concatenate(c))); want_amp.append(np.concatenate(a))
     g = ws.build(max_ticks_per_run=batch, flags=flags)
     assert g.tail_stream() is not None                            # automatic mode
-    hip = C.CDLL("libamdhip64.so")
+    hip = C.CDLL(str(abi.LIB_PATH))
     ptr = n_fl = None
 
     def peek():                                                   # what a stream-ordered consumer on the graph's stream sees behind the raw pointer

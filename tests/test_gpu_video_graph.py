@@ -438,7 +438,7 @@ def test_a_callers_stream_can_be_retired_and_its_handle_reused():
     import ctypes as C
     with pytest.raises(abi.MxError):
         video.stream_retired(None)
-    hip = C.CDLL("libamdhip64.so")                 # the runtime the library itself is linked against (importing torch here would bring a second one)
+    hip = C.CDLL(str(abi.LIB_PATH))                # dlsym through the library's handle: the runtime it is bound to ("libamdhip64.so" is torch's copy once torch is imported)
     handle = C.c_void_p()
     assert hip.hipStreamCreate(C.byref(handle)) == 0 and handle.value
 
