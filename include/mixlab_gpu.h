@@ -207,6 +207,19 @@ int mx_graph_debug_eq_records(mx_graph* g, void** device_records, size_t* bytes)
 /* DEBUG: how the Mixer banks of the second-stream mode (MX_FLAG_OVERLAP_TAIL / automatic) went out since the graph was built: behind the gate that the next run's EqThree
  * launch opens, or at once (a join released them, or the next run had no such launch).  Tests use it to know which path they exercised. */
 int mx_graph_debug_tail_releases(mx_graph* g, uint64_t* gated, uint64_t* at_once);
+/* DEBUG: which form the first EqThree launch group's last launch took (MX_EQ_LAUNCH_NONE before any).  out[0] the form, out[1] the super-block of a tiled
+ * form -- 16 (half lines, two tiles), 32 (whole lines, two tiles) or 321 (whole lines, one tile) -- else 0, out[2] chunks per instance, out[3] the chunk
+ * length in samples, out[4] the warm-up of a speculative chunk.  The scan form: out[2] the spans of its time split, out[3] the span length, out[4] the
+ * samples its pre-pass reads at the end of each span (the span itself: the full pre-pass).  The sequential form: 1 chunk of the whole stream, no warm-up.
+ * Tests use it to know which path a sample rate and tick length reached. */
+#define MX_EQ_LAUNCH_NONE 0u
+#define MX_EQ_LAUNCH_SEQUENTIAL 1u     /* one lane (or the two-lane split cascade) per instance, no speculation */
+#define MX_EQ_LAUNCH_DIRECT 2u         /* speculative chunks, k_eq_three_spec (no tile) */
+#define MX_EQ_LAUNCH_TILED 3u          /* speculative chunks, tiled kernel, chunks and ticks whole super-blocks */
+#define MX_EQ_LAUNCH_RAGGED_TICK 4u    /* speculative chunks, tiled kernel for an inline Envelope whose ticks are not whole 32-sample super-blocks */
+#define MX_EQ_LAUNCH_CONTROL_TILE 5u   /* speculative chunks, tiled kernel with a control tile (an Amplifier modulated by a buffer) */
+#define MX_EQ_LAUNCH_SCAN 6u           /* MX_FLAG_EQ_FAST: the time-parallel scan */
+int mx_graph_debug_eq_launch(mx_graph* g, uint32_t out[5]);
 
 /* Feed a SOURCE_* node: n_ticks consecutive tick buffers (SPT mono / 2*SPT interleaved stereo f32). */
 int mx_graph_write_source(mx_graph* g, uint32_t node, const float* host_samples, size_t n_ticks);

@@ -34,6 +34,8 @@ FLAG_NO_FUSE = 2
 FLAG_EQ_FAST = 4    # time-parallel EqThree: <= 1 ULP, not bit-exact
 FLAG_FP_CONTRACT = 16   # the contracted order (mul+add fused): <= 1 ULP of the exact order, equal to the oracle's contract mode
 FLAG_OVERLAP_TAIL = 8   # the last Mixer bank runs on a second stream beside the next run's earlier groups
+# MX_EQ_LAUNCH_* (mx_graph_debug_eq_launch): the form an EqThree launch took
+EQ_LAUNCH = {0: "none", 1: "sequential", 2: "direct", 3: "tiled", 4: "ragged_tick", 5: "control_tile", 6: "scan"}
 
 
 class MixerChannelParams(C.Structure):
@@ -115,6 +117,7 @@ _proto("mx_graph_schedule_params_batch", C.c_int, C.c_void_p, C.POINTER(ParamEve
 _proto("mx_graph_eq_spec_stats", C.c_int, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64))
 _proto("mx_graph_debug_eq_records", C.c_int, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t))
 _proto("mx_graph_debug_tail_releases", C.c_int, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64))
+_proto("mx_graph_debug_eq_launch", C.c_int, C.c_void_p, C.POINTER(C.c_uint32))
 _proto("mx_graph_eq_repair_stats", C.c_int, C.c_void_p, C.POINTER(C.c_uint64))
 _proto("mx_graph_write_source", C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t)
 _proto("mx_graph_bind_source_device", C.c_int, C.c_void_p, C.c_uint32, C.c_void_p)
@@ -241,6 +244,13 @@ class Graph:
         a, b = C.c_uint64(), C.c_uint64()
         check(lib.mx_graph_debug_tail_releases(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def debug_eq_launch(self) -> dict:
+        """mx_graph_debug_eq_launch: the form the first EqThree group's last launch took -> {form: one of EQ_LAUNCH, super_block, n_chunks, chunk, warm}
+        (the scan: n_chunks / chunk = the spans of its time split and their length, warm = what its pre-pass reads of each span)"""
+        v = (C.c_uint32 * 5)()
+        check(lib.mx_graph_debug_eq_launch(self._h, v))
+        return {"form": EQ_LAUNCH.get(v[0], str(v[0])), "super_block": int(v[1]), "n_chunks": int(v[2]), "chunk": int(v[3]), "warm": int(v[4])}
 
     def debug_eq_records(self):
         """-> (device pointer, bytes) of the first EqThree group's chunk records of the last speculative launch (mx_graph_debug_eq_records)"""

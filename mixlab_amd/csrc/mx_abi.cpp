@@ -135,6 +135,10 @@ int mx_graph_debug_tail_releases(mx_graph* g, uint64_t* gated, uint64_t* at_once
     return guard([&] { REQUIRE(g, "NULL argument"); g->g->tail_releases(gated, at_once); });
 }
 
+int mx_graph_debug_eq_launch(mx_graph* g, uint32_t out[5]) {
+    return guard([&] { REQUIRE(g && out, "NULL argument"); g->g->eq_launch(out); });
+}
+
 int mx_graph_eq_repair_stats(mx_graph* g, uint64_t out[8]) {
     return guard([&] {
         REQUIRE(g, "graph is NULL");

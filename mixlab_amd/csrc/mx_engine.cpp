@@ -1090,6 +1090,7 @@ void Graph::run_span(uint64_t t0, size_t fpc, uint32_t call_off, uint32_t n_call
     }
     std::vector<PlotJob> jobs;
     size_t gi = 0;
+    bool first_eq = true;
     for (Group& g : groups_) {
         const uint32_t n = (uint32_t)g.nodes.size();
         const size_t gf = frames * g.dom_num / g.dom_den;   // frames of this group's sample-rate domain
@@ -1105,6 +1106,7 @@ void Graph::run_span(uint64_t t0, size_t fpc, uint32_t call_off, uint32_t n_call
         }
         case MX_KIND_EQ_THREE: {
             EqRun r{gf, gfpc, n_calls, fp_contract() ? 1u : 0u, t0, sample_rate_, 1.0 / sample_rate_, lo_f_, hi_f_, nullptr};
+            uint32_t launch[5] = {MX_EQ_LAUNCH_SEQUENTIAL, 0u, 1u, (uint32_t)gf, 0u};   // what ran (mx_graph_debug_eq_launch)
             if (g.state2.p) {   // Envelopes folded into the epilogue: their state entering every tick of this span
                 const size_t need = (size_t)n * n_calls * sizeof(EnvTick);
                 if (g.env_ticks.bytes < need || !g.env_ticks.p) { sync(); g.env_ticks.alloc(need); }
@@ -1122,7 +1124,7 @@ void Graph::run_span(uint64_t t0, size_t fpc, uint32_t call_off, uint32_t n_call
                         if (!gate_flag_.p) { gate_flag_.alloc(64); hip_check(hipMemset(gate_flag_.p, 0, 64), "hipMemset"); }
                         r.started = (uint32_t*)gate_flag_.p; r.started_seq = ++gate_seq_; gate_armed_ = true;
                     }
-                    const bool opens_gate = launch_eq_three_spec((const EqDesc*)desc_of(g), (EqState*)g.state.p, n, r, plan, g.eq_mode, g.spec.p, (uint64_t*)eq_stats_.p, stream_);
+                    const bool opens_gate = launch_eq_three_spec((const EqDesc*)desc_of(g), (EqState*)g.state.p, n, r, plan, g.eq_mode, g.spec.p, (uint64_t*)eq_stats_.p, stream_, launch);
                     if (!opens_gate && !(getenv("MX_TAIL_GATE_TEST") && atoi(getenv("MX_TAIL_GATE_TEST")))) gate_armed_ = false;   // the direct form never stores the flag: a gate would spin to its time limit before the bank starts (MX_TAIL_GATE_TEST: tests of that bounded spin)
                     if (deferred_.pending) flush_deferred_tail(true);     // run k's Mixer bank: behind the gate this launch opens
                 } else {
@@ -1147,7 +1149,9 @@ void Graph::run_span(uint64_t t0, size_t fpc, uint32_t call_off, uint32_t n_call
                     toeplitz_pow((long double)hi_f_, sp.span, pp.hi);
                 }
                 launch_eq_three_scan((const EqDesc*)desc_of(g), (EqState*)g.state.p, n, r, (const EqScanTab*)eq_tabs_.p, sp, pp, stream_);
+                launch[0] = MX_EQ_LAUNCH_SCAN; launch[2] = sp.n_split; launch[3] = (uint32_t)sp.span; launch[4] = (uint32_t)sp.warm;
             }
+            if (first_eq) { std::copy(launch, launch + 5, eq_launch_); first_eq = false; }
             break;
         }
         case MX_KIND_FM_SINE: launch_fm_sine((const FmDesc*)desc_of(g), n, gf, t0, sample_rate_, stream_, sin_mode_); break;

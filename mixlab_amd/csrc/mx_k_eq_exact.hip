@@ -1341,17 +1341,21 @@ __global__ __launch_bounds__(64) void k_eq_three_repair(const EqDesc* __restrict
     }
 }
 
-// warm-up length: the 4-pole cascade's response to a unit difference k samples back is at most C(k+3,3) p^k (p = 1 - f); W is
+// warm-up length: the 4-pole cascade's response to a unit difference k samples back is at most g C(k+3,3) |p|^k (p = 1 - f; g = max(1, f)^4
+// bounds the gains f between sections, 1 at every positive pole); W is
 // the first multiple of 128 where that is below 2^-72 -- twenty bits under the f64 ulp of a full-scale state, so that two
 // trajectories are within rounding of each other and coalesce (measured: 0 mismatching boundaries from W = 1024 at 48 kHz
-// on every live signal tried, all of them at W = 768).  A longer W only costs time; a shorter one only costs repairs.
+// on every live signal tried, all of them at W = 768).  A longer W only costs time; a shorter one only costs repairs.  A negative pole (the high band
+// at rates up to ~16.2 kHz) forgets at the pace of |p|; |p| >= 1 never forgets (-1: no speculation, every boundary would need its repair).
 static size_t eq_warm_len(double f) {
-    const long double p = 1.0L - (long double)f;
-    if (!(p > 0.0L) || !(p < 1.0L)) return 128;
+    const long double p = fabsl(1.0L - (long double)f);
+    if (p == 0.0L) return 128;
+    if (!(p < 1.0L)) return (size_t)-1;
+    const long double g = f > 1.0 ? powl((long double)f, 4) : 1.0L;
     const long double lim = ldexpl(1.0L, -72);
     for (size_t K = 128; K <= ((size_t)1 << 22); K += 128) {
         const long double c = (long double)(K + 3) * (long double)(K + 2) * (long double)(K + 1) / 6.0L;
-        if (c * expl((long double)K * logl(p)) < lim) return K;
+        if (g * c * expl((long double)K * logl(p)) < lim) return K;
     }
     return (size_t)-1;
 }
@@ -1382,6 +1386,7 @@ bool eq_plan_spec(uint32_t n, size_t frames, size_t fpc, double lo_f, double hi_
     // state): short submissions get a wave of 64 chunks per strip where C >= W allowed 40.  Not below 256 samples.
     const size_t c_min = std::max<size_t>(unit, 256);
     const size_t nc_max = frames / c_min;
+    if (nc_max < 2) return false;                             // one chunk never speculates; none (a forced warm-up below 128 on a stream shorter than c_min) would divide by zero in chunk_of
     size_t best;
     if (force_c > 1) best = std::min<size_t>((size_t)force_c, nc_max);
     else {
@@ -1458,7 +1463,8 @@ int eq_epilogue_mode(uint32_t epi, uint32_t flags, bool has_ctl) {
     return mode * 2 + stereo;
 }
 
-bool launch_eq_three_spec(const EqDesc* d, EqState* st, uint32_t n, const EqRun& r_in, const EqSpecPlan& plan_in, int uniform_mode, void* scratch, uint64_t* stats, hipStream_t s) {
+bool launch_eq_three_spec(const EqDesc* d, EqState* st, uint32_t n, const EqRun& r_in, const EqSpecPlan& plan_in, int uniform_mode, void* scratch, uint64_t* stats, hipStream_t s,
+                          uint32_t* launch) {
     if (!n || !r_in.frames) return false;
     // A stream that is not whole pieces of four samples (735 t frames at 44.1 kHz with t not a multiple of 4): the tiled kernel runs the frames up to the last
     // multiple of four, and the proof / repair kernel -- which ends up holding the exact state there -- walks the one to three samples left (`tail`).
@@ -1539,6 +1545,11 @@ bool launch_eq_three_spec(const EqDesc* d, EqState* st, uint32_t n, const EqRun&
         default: MX_GO(-1, -1); break;
         }
 #undef MX_GO
+    }
+    if (launch) {   // the values of MX_EQ_LAUNCH_* (include/mixlab_gpu.h)
+        launch[0] = !tiled ? 2u : (um == 4 || um == 5) ? 5u : rt ? 4u : 3u;
+        launch[1] = !tiled ? 0u : (um == 4 || um == 5 || rt) ? 321u : (uint32_t)(sb == 321 ? 321 : r.fc ? 16 : sb);   // (MX_GT: the contracted order's two-tile form is the half-line one)
+        launch[2] = plan.n_chunks; launch[3] = plan.chunk; launch[4] = plan.warm;
     }
     // the proof (and, where a boundary fails, the repair) runs the same order the chunks ran
     plan_t.n_chunks = plan.n_chunks;

@@ -453,19 +453,22 @@ void launch_eq_three_scan(const EqDesc* d, EqState* st, uint32_t n, const EqRun&
 }
 
 // how many trailing samples of a span decide its zero-state end state: the 4-pole cascade's response to a sample k
-// steps back is at most C(k+3,3) p^k (p = 1 - f, the pole; all section gains f <= 1), so everything older than K adds
-// less than tail(K) = sum_{k>=K} C(k+3,3) p^k per unit of input.  K is the first multiple of 128 where tail(K) < 2^-280
-// (48 kHz: 3968, 44.1 kHz: 3584, 96 kHz: 8064, 192 kHz: 16384 samples).
+// steps back is at most g C(k+3,3) |p|^k (p = 1 - f, the pole; g = max(1, f)^4 bounds the four section gains f), so everything older
+// than K adds less than tail(K) = g sum_{k>=K} C(k+3,3) |p|^k per unit of input.  K is the first multiple of 128 where tail(K) < 2^-280
+// (48 kHz: 3968, 44.1 kHz: 3584, 96 kHz: 8064, 192 kHz: 16384 samples).  At rates up to ~16.2 kHz the high pole is negative (1 < f <= 2):
+// the response oscillates and forgets at the pace of |p| (6 kHz: p = -0.975, 9 088 samples); |p| >= 1 (5.4 kHz: p = -1) never forgets.
 static size_t eq_forget_len(double f) {
-    const long double p = 1.0L - (long double)f;
-    if (!(p > 0.0L) || !(p < 1.0L)) return p <= 0.0L ? 8 : (size_t)-1;
+    const long double p = fabsl(1.0L - (long double)f);
+    if (p == 0.0L) return 8;
+    if (!(p < 1.0L)) return (size_t)-1;
+    const long double g = f > 1.0 ? powl((long double)f, 4) : 1.0L;
     const long double lim = ldexpl(1.0L, -280);
     for (size_t K = 128; K <= ((size_t)1 << 22); K += 128) {
         // tail(K) <= C(K+3,3) p^K * sum_j ((K+4)/(K+1) p)^j : ratio of consecutive terms is (k+4)/(k+1) p, decreasing in k
         const long double r = (long double)(K + 4) / (long double)(K + 1) * p;
         if (r >= 1.0L) continue;
         const long double c = (long double)(K + 3) * (long double)(K + 2) * (long double)(K + 1) / 6.0L;
-        const long double t = c * expl((long double)K * logl(p)) / (1.0L - r);
+        const long double t = g * c * expl((long double)K * logl(p)) / (1.0L - r);
         if (t < lim) return K;
     }
     return (size_t)-1;

@@ -1,10 +1,12 @@
 """Host-side proof obligation of the envelope kernel's exact-division shortcut (see
 mixlab_amd/csrc/mx_audio_kernels.hip: seq_ms): checked exhaustively for every sample distance the
-fast path accepts (dt < 2^32, i.e. > 24 h of audio) at both supported rates."""
+fast path accepts (dt < 2^32, i.e. > 24 h of audio) at every sample rate of the tick-shape table (tests/tick_shapes.py)."""
 import pathlib
 import subprocess
 
 import pytest
+
+from tick_shapes import SHAPES
 
 HERE = pathlib.Path(__file__).resolve().parent / "helpers"
 
@@ -16,7 +18,7 @@ def checker(tmp_path_factory):
     return exe
 
 
-@pytest.mark.parametrize("rate", [44100, 48000])
+@pytest.mark.parametrize("rate", sorted({s.sample_rate for s in SHAPES}))
 def test_markstein_quotient_is_ieee_quotient_for_all_dt_below_2_32(checker, rate):
     out = subprocess.run([str(checker), str(rate), "0", str(1 << 32)], capture_output=True, text=True)
     assert out.returncode == 0 and out.stdout.strip() == "0", out.stdout + out.stderr

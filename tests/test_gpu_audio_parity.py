@@ -295,8 +295,8 @@ def test_type_mismatch_is_reported_not_crashed():
 # ------------------------------------------------------------------------------------------------
 # graphs (Engine::run_tick): SURVEY.md section 8d configs 1 and 2
 # ------------------------------------------------------------------------------------------------
-def config1():
-    ws = Workspace(SR, 60)
+def config1(sr=SR, tps=60):
+    ws = Workspace(sr, tps)
     oscs = [ws.oscillator(100.0, abi.WAVE_SINE), ws.oscillator(220.0, abi.WAVE_SAW),
             ws.oscillator(440.0, abi.WAVE_SQUARE), ws.oscillator(880.0, abi.WAVE_TRIANGLE)]
     mix = ws.mixer([(0.0, 1.0, False), (-6.0, 0.8, True), (3.0, 0.5, False), (-12.0, 0.25, True)])
@@ -338,9 +338,9 @@ def test_config1_four_osc_mixer_plotter(batch):
     assert n_fired == n_ticks // 6
 
 
-def strips(n_strips, sr=SR):
+def strips(n_strips, sr=SR, tps=60):
     """per strip Trigger->Envelope ; Source->EqThree->Panner(L=R)->Amplifier(ctl=Envelope) -> Mixer."""
-    ws = Workspace(sr, 60)
+    ws = Workspace(sr, tps)
     gains = synth.uniform(10, 3 * n_strips, -24.0, 6.0)
     mg = synth.uniform(11, n_strips, -24.0, 6.0)
     mf = synth.uniform(12, n_strips, 0.0, 1.0)

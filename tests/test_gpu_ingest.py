@@ -36,8 +36,8 @@ class FrameBook:
 
 
 class AbiMedia:
-    def __init__(self, book):
-        self.m, self.book = ingest.MediaSource(SR, 60), book
+    def __init__(self, book, sr=SR, tps=60):
+        self.m, self.book = ingest.MediaSource(sr, tps), book
 
     def set_media(self, present):
         self.m.set_media(present)

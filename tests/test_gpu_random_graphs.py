@@ -26,9 +26,9 @@ def bits(a):
     return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
-def random_graph(seed):
+def random_graph(seed, sr=SR, tps=60):
     rng = np.random.default_rng(seed)
-    ws = Workspace(SR, 60)
+    ws = Workspace(sr, tps)
     outs = {MONO: [], STEREO: []}      # (node, port) by line type
     ins = []                           # (node, port, type)
     sources = []

@@ -14,8 +14,8 @@ FADERS = [1.0, 0.75, 0.5, 0.5, 0.25, 0.9, 0.1]
 MATRIX = [3900, 150, 46, 4096, 60, 3980, 56, -2048, 20, 120, 3956, 0]   # Q12 3x4, mild cross-talk + offsets
 
 
-def cascade(sizes, matrix):
-    ws = Workspace(44100, 60)
+def cascade(sizes, matrix, sr=44100, tps=60):
+    ws = Workspace(sr, tps)
     srcs = [ws.source_video() for _ in sizes]
     prev, mixers = srcs[0], []
     for k in range(1, len(sizes)):
