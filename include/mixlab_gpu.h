@@ -26,7 +26,8 @@ extern "C" {
 #endif
 
 #define MX_ABI_VERSION 4u   /* 2: mx_exchange_*, mx_monitor_tick.dropped, mx_monitor_params_ex, packed RGB pixel formats; 3: MX_FLAG_FP_CONTRACT;
-                              * 4: mx_graph_read_output_window, per-pixel alpha (MX_PIXFMT_YUVA420P, mx_dframe_*_alpha; the A byte of packed RGBA honoured) */
+                              * 4: mx_graph_read_output_window, per-pixel alpha (MX_PIXFMT_YUVA420P, mx_dframe_*_alpha; the A byte of packed RGBA honoured);
+                              *    later, without a bump (only additions): MX_KIND_OUTPUT_DEVICE, mx_graph_read_audio_out, mx_graph_audio_out_lag */
 
 /* ---- status codes (0 ok, <0 error; cf. MIXLAB_IOCTX_ERROR / MIXLAB_IOCTX_PANIC) ---- */
 enum {
@@ -66,8 +67,14 @@ enum {
                                      their codec threads (monitor.rs:226-236; encode.rs:183-195 f32->i16, :287-295 DynamicScaler to the
                                      encoder's picture): keeps every tick's program frame, scaled, and serves the mix as i16
                                      in: Video, Stereo  out: --   params: mx_monitor_params */
-    MX_KIND_COUNT = 18
+    MX_KIND_OUTPUT_DEVICE = 18,   /* src/module/output_device.rs: the sound-card sink's tick-thread work -- routing into the device's interleaved frame, clip test,
+                                     Clip / Lag indication (run_tick :174-246); cpal and its ring stay on the host.  in: Stereo  out: --
+                                     params: mx_output_device_params; read with mx_graph_read_audio_out */
+    MX_KIND_COUNT = 19
 };
+/* mx_graph_profile_run / _collect write this many per-kind times (the kinds that have launch groups of their own; an OutputDevice's time shows in
+ * ms_total and in mx_graph_performance_info's module_us) */
+#define MX_PROFILE_KINDS 18
 
 /* protocol/src/lib.rs:233-241, bincode variant order */
 enum { MX_WAVE_ON = 0, MX_WAVE_OFF = 1, MX_WAVE_SINE = 2, MX_WAVE_SQUARE = 3, MX_WAVE_TRIANGLE = 4, MX_WAVE_SAW = 5 };
@@ -89,6 +96,12 @@ typedef struct { uint32_t width, height; } mx_monitor_params;   /* the encoder's
  * no picture is scaled or kept, mx_monitor_tick.dropped = 1 -- exactly what the codec thread would never see.  queue_depth = 0 (and the short
  * form): every tick of a submission is kept (one scaled frame per tick stays on the device until the next run: max_ticks_per_run x frame bytes). */
 typedef struct { uint32_t width, height, queue_depth, _pad; } mx_monitor_params_ex;
+/* OutputDeviceParams (protocol) as the adapter sees it once cpal has opened the stream: channels = the open stream's config.channels, 0 = no
+ * stream (no device, or not found: output_device.rs:95-150); left / right = the requested channel, -1 = None.  channels <= 256, left / right
+ * >= -1 (else MX_ERR_INVALID).  Creation applies them as the first update from the empty state; every update (output_device.rs:152-169) with
+ * a stream open zeroes the whole scratch when the STORED left / right (already filtered) differ from the requested ones, then stores
+ * left / right filtered by < channels; with channels = 0 the stored left / right are kept and nothing is zeroed. */
+typedef struct { uint32_t channels; int32_t left, right; uint32_t _pad; } mx_output_device_params;
 /* Build-specified audio extras (DESIGN.md "FIR and resampler").  Both are variable-length blobs: the header below
  * followed by the f64 coefficients.  Arithmetic: f32 widened to f64, accumulated in f64 in ascending tap index with
  * separate multiply and add, rounded once to f32 -- the reference's own convention (mixer.rs:62, amplifier.rs:56). */
@@ -246,18 +259,45 @@ int mx_graph_write_source_i16(mx_graph* g, uint32_t node, const int16_t* host_sa
 /* Device pointer + per-tick length (floats) of an output port (for zero-copy consumers / RCCL). */
 int mx_graph_output_device_ptr(mx_graph* g, uint32_t node, uint32_t port, void** device_ptr, size_t* floats_per_tick);
 
+/* MX_KIND_OUTPUT_DEVICE after a run: ticks [first_tick_in_run, first_tick_in_run + n_ticks) of the last mx_graph_run_ticks.
+ *   samples  what run_tick would have pushed into the cpal ring over those ticks (stream.tx.push_slice, output_device.rs:210), concatenated in
+ *            tick order: frames * channels floats per tick (frames = the input's samples per tick in its own rate domain), nothing for a tick
+ *            with no stream.  Positions of no assigned channel hold the scratch as it was: zeros after a reassignment, stale samples of an
+ *            earlier layout after a change of channel count.
+ *   ticks    one record per tick: clip (a written sample was < -1 or > 1), clip_status / lag_status (0 None, 1 Recent, 2 Active -- the
+ *            encoding of mx_performance_info.lag), changed (the reference's run_tick returned Some: a status differs from the previous
+ *            tick's), channels.
+ *   Clock: the graph's own -- tick k's `now` is its t in samples; Active when (now - last) * 10 < sample_rate (100 ms), Recent when now - last
+ *   < 5 * sample_rate (5 s).  At 44 100 / 60 and 48 000 / 60 a clip stays Active for 6 ticks (the 6th later tick is exactly 100 ms: not
+ *   Active) and Recent until 300 ticks later.  The node assumes the tick count only moves forward, as the reference's Instant does: after a
+ *   run whose first tick lies BEFORE a recorded clip or lag, now - last is negative and reads as Active (signed arithmetic) until the
+ *   clock has passed that time by 100 ms.
+ * samples or ticks may be NULL (not copied); *n_samples (may be NULL) receives the float count of the window, and with both NULL the call is
+ * a size query only.  samples_cap < that count, a window beyond the last run or a node of another kind: MX_ERR_INVALID.  Joins the graph's
+ * streams like mx_graph_read_output. */
+typedef struct { uint8_t clip, clip_status, lag_status, changed; uint32_t channels; } mx_audio_out_tick;
+int mx_graph_read_audio_out(mx_graph* g, uint32_t node, uint32_t first_tick_in_run, uint32_t n_ticks, float* samples, size_t samples_cap,
+                            mx_audio_out_tick* ticks, size_t* n_samples);
+/* The cpal data callback ran short (output_device.rs:117-129, the store at :126): sets the node's lag flag.  Safe to call from any thread, concurrently with
+ * mx_graph_run_ticks; the first tick of the next run consumes it (lag_flag.swap(false), :219). */
+int mx_graph_audio_out_lag(mx_graph* g, uint32_t node);
+/* mx_graph_adopt_state and an OutputDevice: the module persists across a topology edit, so the new node takes the old one's STATE as the
+ * reference's module keeps it -- channel count, stored (filtered) left / right, scratch, clip / lag times and statuses, a pending lag note --
+ * and the params it was built with are not applied.  A host that changed something at the same time (another device, another channel
+ * count or assignment) applies it afterwards with mx_graph_update_params, exactly as OutputDevice::update would have seen it. */
+
 /* Plotter indication (src/module/plotter.rs:37-56) for tick `tick_in_run` of the last run:
  * *fired = 1 and SPT floats in each of left/right when it fired (every 6th call, input connected). */
 int mx_graph_read_plotter(mx_graph* g, uint32_t node, uint32_t tick_in_run, float* left, float* right, int* fired);
 
 /* Per-kind device time of the last profiled run (the PerformanceInfo analogue,
  * src/engine/timing.rs:86-94): run once with hipEvents around every launch group. */
-int mx_graph_profile_run(mx_graph* g, uint64_t first_tick, uint32_t n_ticks, float* ms_by_kind /* MX_KIND_COUNT */, float* ms_total);
+int mx_graph_profile_run(mx_graph* g, uint64_t first_tick, uint32_t n_ticks, float* ms_by_kind /* MX_PROFILE_KINDS */, float* ms_total);
 /* Same, accumulated over many asynchronous runs: while enabled every mx_graph_run_ticks records a
  * hipEvent before/after each launch group on the graph's stream (no synchronisation);
  * collect synchronises and returns the sums (ms) and the number of runs they cover. */
 int mx_graph_profile_enable(mx_graph* g, int on);
-int mx_graph_profile_collect(mx_graph* g, float* ms_by_kind /* MX_KIND_COUNT */, float* ms_total, uint32_t* n_runs);
+int mx_graph_profile_collect(mx_graph* g, float* ms_by_kind /* MX_PROFILE_KINDS */, float* ms_total, uint32_t* n_runs);
 
 /* The reference's performance panel (PerformanceInfo, protocol/src/lib.rs:32-59, filled by EngineStat::report,
  * src/engine/timing.rs:46-60) from the most recent profiled run (mx_graph_profile_run, or profile_enable + collect):

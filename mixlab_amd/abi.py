@@ -25,9 +25,11 @@ MX_OK, MX_ERR_INVALID, MX_ERR_TYPE, MX_ERR_DEVICE, MX_ERR_NOMEM, MX_ERR_INTERNAL
 MX_DISCONNECTED, MX_MONO, MX_STEREO, MX_VIDEO = 0, 1, 2, 3
 (KIND_AMPLIFIER, KIND_ENVELOPE, KIND_EQ_THREE, KIND_FM_SINE, KIND_MIXER, KIND_OSCILLATOR, KIND_PLOTTER,
  KIND_STEREO_PANNER, KIND_STEREO_SPLITTER, KIND_TRIGGER, KIND_VIDEO_MIXER, KIND_SOURCE_MONO,
- KIND_SOURCE_STEREO, KIND_SOURCE_VIDEO, KIND_VIDEO_TO_RGBA, KIND_FIR, KIND_RESAMPLE, KIND_MONITOR, KIND_COUNT) = range(19)
+ KIND_SOURCE_STEREO, KIND_SOURCE_VIDEO, KIND_VIDEO_TO_RGBA, KIND_FIR, KIND_RESAMPLE, KIND_MONITOR, KIND_OUTPUT_DEVICE, KIND_COUNT) = range(20)
+PROFILE_KINDS = 18   # MX_PROFILE_KINDS: floats mx_graph_profile_run / _collect write (an OutputDevice's time is in ms_total)
 KIND_NAMES = ["amplifier", "envelope", "eq_three", "fm_sine", "mixer", "oscillator", "plotter", "stereo_panner",
-              "stereo_splitter", "trigger", "video_mixer", "source_mono", "source_stereo", "source_video", "video_to_rgba", "fir", "resample", "monitor"]
+              "stereo_splitter", "trigger", "video_mixer", "source_mono", "source_stereo", "source_video", "video_to_rgba", "fir", "resample", "monitor",
+              "output_device"]
 WAVE_ON, WAVE_OFF, WAVE_SINE, WAVE_SQUARE, WAVE_TRIANGLE, WAVE_SAW = range(6)
 FLAG_EQ_EXACT = 1   # the default (kept as a no-op name)
 FLAG_NO_FUSE = 2
@@ -131,6 +133,19 @@ _proto("mx_graph_output_device_ptr", C.c_int, C.c_void_p, C.c_uint32, C.c_uint32
 _proto("mx_graph_tail_stream", C.c_int, C.c_void_p, C.POINTER(C.c_void_p))
 _proto("mx_graph_stream", C.c_int, C.c_void_p, C.POINTER(C.c_void_p))
 _proto("mx_graph_read_plotter", C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int))
+class OutputDeviceParams(C.Structure):
+    """mx_output_device_params: channels of the open stream (0 = none), left / right (-1 = None)."""
+    _fields_ = [("channels", C.c_uint32), ("left", C.c_int32), ("right", C.c_int32), ("_pad", C.c_uint32)]
+
+
+class AudioOutTick(C.Structure):
+    """mx_audio_out_tick: one tick's clip bit, Clip / Lag statuses (0 None, 1 Recent, 2 Active), changed, channels."""
+    _fields_ = [("clip", C.c_uint8), ("clip_status", C.c_uint8), ("lag_status", C.c_uint8), ("changed", C.c_uint8), ("channels", C.c_uint32)]
+
+
+AUDIO_OUT_TICK_DTYPE = np.dtype([("clip", np.uint8), ("clip_status", np.uint8), ("lag_status", np.uint8), ("changed", np.uint8), ("channels", np.uint32)])
+_proto("mx_graph_read_audio_out", C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_size_t))
+_proto("mx_graph_audio_out_lag", C.c_int, C.c_void_p, C.c_uint32)
 _proto("mx_graph_profile_run", C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float))
 _proto("mx_graph_profile_enable", C.c_int, C.c_void_p, C.c_int)
 _proto("mx_graph_profile_collect", C.c_int, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32))
@@ -289,6 +304,21 @@ class Graph:
         check(lib.mx_graph_read_output_window(self._h, node, port, out.ctypes.data_as(C.c_void_p), first_tick, n_ticks))
         return out
 
+    def read_audio_out(self, node, first_tick: int, n_ticks: int):
+        """OutputDevice: (the floats pushed into the ring over ticks [first_tick, first_tick + n_ticks) of the last run, their per-tick records
+        as a structured array of AUDIO_OUT_TICK_DTYPE)"""
+        n = C.c_size_t(0)
+        check(lib.mx_graph_read_audio_out(self._h, node, first_tick, n_ticks, None, 0, None, C.byref(n)))
+        samples = np.empty(n.value, dtype=np.float32)
+        ticks = np.empty(n_ticks, dtype=AUDIO_OUT_TICK_DTYPE)
+        check(lib.mx_graph_read_audio_out(self._h, node, first_tick, n_ticks, samples.ctypes.data_as(C.c_void_p), n.value,
+                                          ticks.ctypes.data_as(C.c_void_p), C.byref(n)))
+        return samples, ticks
+
+    def audio_out_lag(self, node):
+        """the cpal callback ran short: the next run's first tick takes the note (any thread, also during a run)"""
+        check(lib.mx_graph_audio_out_lag(self._h, node))
+
     def read_output_i16(self, node, port, n_ticks: int, stereo: bool, rate=(1, 1)) -> np.ndarray:
         out = np.empty(n_ticks * (self.spt * rate[0] // rate[1]) * (2 if stereo else 1), dtype=np.int16)
         check(lib.mx_graph_read_output_i16(self._h, node, port, out.ctypes.data_as(C.c_void_p), n_ticks))
@@ -324,10 +354,10 @@ class Graph:
         return (l, r) if fired.value else None
 
     def profile_run(self, first_tick, n_ticks):
-        by_kind = (C.c_float * KIND_COUNT)()
+        by_kind = (C.c_float * PROFILE_KINDS)()
         total = C.c_float()
         check(lib.mx_graph_profile_run(self._h, first_tick, n_ticks, by_kind, C.byref(total)))
-        return {KIND_NAMES[k]: by_kind[k] for k in range(KIND_COUNT) if by_kind[k] > 0}, total.value
+        return {KIND_NAMES[k]: by_kind[k] for k in range(PROFILE_KINDS) if by_kind[k] > 0}, total.value
 
 
     def profile_enable(self, on: bool):
@@ -335,11 +365,11 @@ class Graph:
 
     def profile_collect(self):
         """-> ({kind_name: total ms}, total ms, n_runs) accumulated since profile_enable(True)."""
-        by_kind = (C.c_float * KIND_COUNT)()
+        by_kind = (C.c_float * PROFILE_KINDS)()
         total = C.c_float()
         n = C.c_uint32()
         check(lib.mx_graph_profile_collect(self._h, by_kind, C.byref(total), C.byref(n)))
-        return {KIND_NAMES[k]: by_kind[k] for k in range(KIND_COUNT) if by_kind[k] > 0}, total.value, n.value
+        return {KIND_NAMES[k]: by_kind[k] for k in range(PROFILE_KINDS) if by_kind[k] > 0}, total.value, n.value
 
 
     def performance_info(self, n_nodes: int):

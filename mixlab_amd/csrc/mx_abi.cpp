@@ -199,6 +199,19 @@ int mx_graph_output_device_ptr(mx_graph* g, uint32_t node, uint32_t port, void**
     });
 }
 
+int mx_graph_read_audio_out(mx_graph* g, uint32_t node, uint32_t first_tick_in_run, uint32_t n_ticks, float* samples, size_t samples_cap,
+                            mx_audio_out_tick* ticks, size_t* n_samples) {
+    static_assert(sizeof(mx_audio_out_tick) == sizeof(mx::OutTick), "mx_audio_out_tick is the device record");
+    return guard([&] {
+        REQUIRE(g, "graph is NULL");
+        g->g->read_audio_out(node, first_tick_in_run, n_ticks, samples, samples_cap, reinterpret_cast<mx::OutTick*>(ticks), n_samples);
+    });
+}
+
+int mx_graph_audio_out_lag(mx_graph* g, uint32_t node) {
+    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->audio_out_lag(node); });
+}
+
 int mx_graph_read_plotter(mx_graph* g, uint32_t node, uint32_t tick_in_run, float* left, float* right, int* fired) {
     return guard([&] {
         REQUIRE(g && left && right && fired, "NULL argument");

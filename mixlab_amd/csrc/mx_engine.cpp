@@ -57,6 +57,7 @@ static void kind_ports(uint32_t kind, size_t params_len, std::vector<uint8_t>& i
     case MX_KIND_MONITOR:   // monitor.rs:99-102
         if (params_len != sizeof(mx_monitor_params_ex)) need(sizeof(mx_monitor_params), "mx_monitor_params (or mx_monitor_params_ex)");
         in = {MX_VIDEO, MX_STEREO}; out = {}; break;
+    case MX_KIND_OUTPUT_DEVICE: need(sizeof(mx_output_device_params), "mx_output_device_params"); in = {MX_STEREO}; out = {}; break;   // output_device.rs:80-81
     default: throw Error(MX_ERR_INVALID, "unknown module kind");
     }
 }
@@ -85,6 +86,11 @@ static void toeplitz_pow(long double f, uint64_t n, double out[4]) {
 // y = T(a) v for the lower-triangular Toeplitz matrix with first column a
 static void toeplitz_apply_ld(const long double a[4], const long double v[4], long double y[4]) {
     for (int i = 0; i < 4; ++i) { y[i] = 0.0L; for (int k = 0; k <= i; ++k) y[i] += a[k] * v[i - k]; }
+}
+
+static void check_output_device_params(const void* params) {
+    mx_output_device_params p; std::memcpy(&p, params, sizeof p);
+    if (p.channels > 256 || p.left < -1 || p.right < -1) throw Error(MX_ERR_INVALID, "mx_output_device_params: channels <= 256, left / right >= -1 (-1 = None)");
 }
 
 static inline size_t floats_per_frame(uint8_t lt) { return lt == MX_MONO ? 1 : (lt == MX_STEREO ? 2 : 0); }
@@ -124,6 +130,7 @@ Graph::Graph(const mx_node* nodes, size_t n_nodes, const mx_edge* edges, size_t 
         n.in_src.assign(n.in_type.size(), PortRef{});
         n.out_off.assign(n.out_type.size(), 0);
         n.out_off2.assign(n.out_type.size(), SIZE_MAX);
+        if (n.kind == MX_KIND_OUTPUT_DEVICE) { check_output_device_params(n.params.data()); n.od_lag.reset(new std::atomic<bool>(false)); }
     }
     for (size_t e = 0; e < n_edges; ++e) {
         const mx_edge& ed = edges[e];
@@ -229,7 +236,8 @@ Graph::Graph(const mx_node* nodes, size_t n_nodes, const mx_edge* edges, size_t 
     };
     for (Node& n : nodes_) n.sub_key = eq_key(n);
     std::vector<uint32_t> sorted;
-    for (uint32_t id : order_) if (!nodes_[id].elided) sorted.push_back(id);
+    for (uint32_t id : order_) if (!nodes_[id].elided && nodes_[id].kind != MX_KIND_OUTPUT_DEVICE) sorted.push_back(id);
+    for (uint32_t id : order_) if (nodes_[id].kind == MX_KIND_OUTPUT_DEVICE) od_nodes_.push_back(id);
     std::stable_sort(sorted.begin(), sorted.end(), [&](uint32_t a, uint32_t b) {
         if (nodes_[a].level != nodes_[b].level) return nodes_[a].level < nodes_[b].level;
         if (nodes_[a].kind != nodes_[b].kind) return nodes_[a].kind < nodes_[b].kind;
@@ -368,6 +376,86 @@ Graph::Graph(const mx_node* nodes, size_t n_nodes, const mx_edge* edges, size_t 
     }
     layout_slab();
     build_descriptors();
+    // OutputDevice: created from the empty state, its params applied as the adapter's first update
+    for (Node& n : nodes_) {
+        if (n.kind != MX_KIND_OUTPUT_DEVICE) continue;
+        n.od_frames = (uint32_t)(spt_ * n.in_dom_num / n.in_dom_den);
+        const OutState st0{-1, -1, 0u, 0u};
+        n.od_state.alloc(sizeof(OutState));
+        hip_check(hipMemcpy(n.od_state.p, &st0, sizeof st0, hipMemcpyHostToDevice), "hipMemcpy(output device state)");
+        n.od_rec.alloc(std::max<size_t>(1, cap_frames_ / spt_) * sizeof(OutTick));
+        od_update(n);
+        hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
+    }
+}
+
+// A channel count above any seen before: the scratch grows (its samples kept, the new part zero: Vec::resize, output_device.rs:185) and the
+// per-run buffers are sized for a whole submission of it.  The stream is quiescent (construction, or behind sync()).
+void Graph::od_grow(Node& n, uint32_t channels) {
+    if (channels <= n.od_cmax) return;
+    const size_t F = n.od_frames, ticks = std::max<size_t>(1, cap_frames_ / spt_);
+    DevBuf sc; sc.alloc(F * channels * sizeof(float));
+    hip_check(hipMemsetAsync(sc.p, 0, F * channels * sizeof(float), stream_), "hipMemsetAsync(output device scratch)");
+    if (n.od_cmax) hip_check(hipMemcpyAsync(sc.p, n.od_scratch.p, F * n.od_cmax * sizeof(float), hipMemcpyDeviceToDevice, stream_), "hipMemcpyAsync(output device scratch)");
+    hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
+    n.od_scratch = std::move(sc);
+    n.od_out.alloc(ticks * F * channels * sizeof(float));
+    n.od_part.alloc(ticks * out_route_blocks(F, channels) * sizeof(uint32_t));
+    n.od_cmax = channels;
+}
+
+// OutputDevice::update (output_device.rs:152-169) for n.params; `device` has already been resolved by the adapter into `channels`
+void Graph::od_update(Node& n) {
+    mx_output_device_params p; std::memcpy(&p, n.params.data(), sizeof p);
+    n.od_channels = p.channels;
+    if (!p.channels) return;   // no stream: the stored left / right stay, nothing is zeroed
+    od_grow(n, p.channels);
+    // the STORED (filtered) assignment against the requested one: a repeated request for a channel the stream lacks zeroes again every time
+    if (n.od_left != p.left || n.od_right != p.right)
+        hip_check(hipMemsetAsync(n.od_scratch.p, 0, (size_t)n.od_frames * n.od_cmax * sizeof(float), stream_), "hipMemsetAsync(output device scratch)");
+    n.od_left = p.left >= 0 && (uint32_t)p.left < p.channels ? p.left : -1;
+    n.od_right = p.right >= 0 && (uint32_t)p.right < p.channels ? p.right : -1;
+}
+
+size_t Graph::od_offset(const Node& n, uint32_t tick) const {
+    size_t off = 0;
+    for (const Node::OdSpan& sp : n.od_spans)
+        if (tick > sp.first) off += (size_t)std::min(tick - sp.first, sp.n) * n.od_frames * sp.channels;
+    return off;
+}
+
+// The span's OutputDevice launches.  One that reads an output of the tail (MX_FLAG_OVERLAP_TAIL / automatic mode) goes behind it on the tail
+// stream -- held back with it when the tail is held -- and the events that join the tail cover it; any other runs on stream_ after the span's groups.
+void Graph::launch_outputs(uint64_t t0, uint32_t call_off, uint32_t n_calls, bool prof, std::vector<hipEvent_t>& ev) {
+    uint8_t where = 0;
+    for (uint32_t id : od_nodes_) {
+        Node& n = nodes_[id];
+        const PortRef src = n.in_src[0];
+        int32_t o = src.node;
+        while (o >= 0 && nodes_[o].elided && nodes_[o].owner >= 0) o = nodes_[o].owner;
+        const bool on_tail = overlap_this_run_ && o >= 0 && nodes_[o].group >= tail_gi_;
+        const uint32_t C = n.od_channels;
+        const size_t base = od_offset(n, call_off);
+        n.od_spans.push_back(Node::OdSpan{call_off, n_calls, C});
+        OutRun r{};
+        r.in = in_ptr(n, 0, false); r.dup = src.node >= 0 && nodes_[src.node].out_dup[src.port] ? 1u : 0u;
+        r.frames = n.od_frames; r.channels = C; r.left = n.od_left; r.right = n.od_right; r.n_ticks = n_calls;
+        r.scratch = (float*)n.od_scratch.p; r.out = (float*)n.od_out.p + base; r.partial = (uint32_t*)n.od_part.p;
+        r.state = (OutState*)n.od_state.p; r.rec = (OutTick*)n.od_rec.p + call_off;
+        r.t0 = t0; r.spt = (uint32_t)spt_; r.rate = (uint32_t)sample_rate_; r.lag = call_off == 0 && n.od_lag_run ? 1u : 0u;
+        if (on_tail && tail_gate_) { deferred_.outs.push_back(r); where |= 2; }
+        else if (on_tail) { launch_output_device(r, tail_stream_); where |= 2; }
+        else { launch_output_device(r, stream_); where |= 1; }
+    }
+    if (where & 2) {
+        if (tail_gate_) deferred_.outs_prof_ev = prof ? ev[groups_.size() + 4] : nullptr;
+        else {
+            if (prof) hip_check(hipEventRecord(ev[groups_.size() + 4], tail_stream_), "hipEventRecord");
+            hip_check(hipEventRecord(ev_tail_done_[parity_], tail_stream_), "hipEventRecord");   // joins of the tail cover what reads it
+        }
+    }
+    if (prof && (where & 1)) hip_check(hipEventRecord(ev[groups_.size() + 3], stream_), "hipEventRecord");
+    if (prof) prof_runs_od_.push_back(where);
 }
 
 void Graph::flush_deferred_tail(bool gated) {
@@ -381,6 +469,9 @@ void Graph::flush_deferred_tail(bool gated) {
         if (t.prof_ev) hip_check(hipEventRecord(t.prof_ev, tail_stream_), "hipEventRecord");
     }
     deferred_.items.clear();
+    for (const OutRun& r : deferred_.outs) launch_output_device(r, tail_stream_);   // OutputDevices that read the tail's outputs
+    if (!deferred_.outs.empty() && deferred_.outs_prof_ev) hip_check(hipEventRecord(deferred_.outs_prof_ev, tail_stream_), "hipEventRecord");
+    deferred_.outs.clear(); deferred_.outs_prof_ev = nullptr;
     if (tail_hook_) { auto hook = std::move(tail_hook_); tail_hook_ = nullptr; hook(tail_stream_); }   // (mx_exchange: pack + exchange of that run's buses, behind the bank)
     // recorded AFTER the hook: whoever waits for this tail (wait_tail) is then also ordered behind the hook's reads of the buses on the tail stream -- a later run's Mixer on
     // stream_ must not overwrite them under a pack that is still copying
@@ -512,7 +603,7 @@ void Graph::plan_fusion() {
         const uint32_t x = (uint32_t)(E.fuse_amp >= 0 ? E.fuse_amp : E.fuse_pan);
         const auto& xc = cons[x][0];
         bool only_mixers = !xc.empty();
-        for (const auto& c : xc) only_mixers = only_mixers && nodes_[c.first].kind == MX_KIND_MIXER;
+        for (const auto& c : xc) only_mixers = only_mixers && (nodes_[c.first].kind == MX_KIND_MIXER || nodes_[c.first].kind == MX_KIND_OUTPUT_DEVICE);   // (an OutputDevice expands it)
         if (only_mixers) nodes_[x].out_dup[0] = 1;
     }
 }
@@ -785,6 +876,7 @@ void Graph::update_params(uint32_t node, const void* params, size_t len) {
     if (node >= nodes_.size()) throw Error(MX_ERR_INVALID, "node out of range");
     if (len != nodes_[node].params.size()) throw Error(MX_ERR_INVALID, "params_len differs from the node's params (terminal count is frozen with the topology)");
     if (len && !params) throw Error(MX_ERR_INVALID, "params is NULL");
+    if (nodes_[node].kind == MX_KIND_OUTPUT_DEVICE) check_output_device_params(params);
     // a Trigger's params live in the GateBits rows the next run uploads: nothing on the device reads them, nothing has to be waited for (and a Mixer bank that is being
     // held back for the next run stays held)
     if (nodes_[node].kind != MX_KIND_TRIGGER) sync();
@@ -797,6 +889,7 @@ void Graph::apply_params(uint32_t node, const void* params, size_t len) {
     Node& n = nodes_[node];
     if (len) std::memcpy(n.params.data(), params, len);
     if (n.kind == MX_KIND_TRIGGER) { ++gates_version_; return; }
+    if (n.kind == MX_KIND_OUTPUT_DEVICE) { od_update(n); return; }
     if (n.kind == MX_KIND_VIDEO_MIXER && n.vmixer) {
         mx_video_mixer_params p; std::memcpy(&p, n.params.data(), sizeof p);
         n.vmixer->update(p);
@@ -812,6 +905,7 @@ void Graph::check_schedule(uint32_t node, const void* params, size_t len) const 
     const Node& n = nodes_[node];
     if (len != n.params.size()) throw Error(MX_ERR_INVALID, "params_len differs from the node's params (terminal count is frozen with the topology)");
     if (len && !params) throw Error(MX_ERR_INVALID, "params is NULL");
+    if (n.kind == MX_KIND_OUTPUT_DEVICE) check_output_device_params(params);
 }
 
 void Graph::drop_schedules() {
@@ -1003,6 +1097,15 @@ void Graph::run(uint64_t t0, size_t fpc, uint32_t n_calls, float* ms_by_kind, fl
         }
     };
     if (any_sched) apply_at(0);
+    for (uint32_t id : od_nodes_) {   // the lag flag is swapped by the run's first tick (output_device.rs:219); the spans of this run replace the last run's
+        Node& n = nodes_[id];
+        n.od_lag_run = n.od_lag->exchange(false);
+        n.od_spans.clear();
+        // a scheduled update to more channels than any before: the buffers grow now, not between two spans (the hand-off holds every span's ticks)
+        uint32_t cmax = 0;
+        for (const Node::SchedEv& ev : n.sched) { mx_output_device_params q; std::memcpy(&q, ev.params.data(), sizeof q); cmax = std::max(cmax, q.channels); }
+        if (cmax > n.od_cmax) { sync(); od_grow(n, cmax); }
+    }
     for (uint32_t id : video_order_) if (nodes_[id].kind == MX_KIND_MONITOR) nodes_[id].mon_ticks.clear();
 
     // Plotter bookkeeping is host logic (plotter.rs:37-40): count += 1 per call, fire on every 6th
@@ -1083,7 +1186,7 @@ void Graph::run_span(uint64_t t0, size_t fpc, uint32_t call_off, uint32_t n_call
     if (prof) {
         if (!prof_pool_.empty()) { ev = std::move(prof_pool_.back()); prof_pool_.pop_back(); }
         else {
-            ev.resize(groups_.size() + 3);   // one slot per launch group + the per-tick video section + the begin of a tail launch that was held back (its own stream)
+            ev.resize(groups_.size() + 5);   // one slot per launch group + the per-tick video section + the begin of a tail launch that was held back (its own stream) + OutputDevices on either stream
             for (auto& e : ev) hip_check(hipEventCreate(&e), "hipEventCreate");
         }
         hip_check(hipEventRecord(ev[0], stream_), "hipEventRecord");
@@ -1162,7 +1265,7 @@ void Graph::run_span(uint64_t t0, size_t fpc, uint32_t call_off, uint32_t n_call
                     if (deferred_.pending) flush_deferred_tail(false);   // (a run whose earlier groups had no speculative EqThree launch: nothing opened a gate)
                     hip_check(hipEventRecord(ev_head_done_, stream_), "hipEventRecord");
                     if (tail_gate_ < 0) { const char* e = getenv("MX_TAIL_GATE"); tail_gate_ = e && atoi(e) == 0 ? 0 : 1; }   // A/B: 0 = launched at once (round 4's form)
-                    if (tail_gate_) { deferred_.items.clear(); deferred_.parity = parity_; deferred_.prof_begin = prof ? ev[groups_.size() + 2] : nullptr; tail_held_this_span_ = true; }
+                    if (tail_gate_) { deferred_.items.clear(); deferred_.outs.clear(); deferred_.parity = parity_; deferred_.prof_begin = prof ? ev[groups_.size() + 2] : nullptr; tail_held_this_span_ = true; }
                     else hip_check(hipStreamWaitEvent(tail_stream_, ev_head_done_, 0), "hipStreamWaitEvent");
                 }
                 if (tail_gate_) {
@@ -1219,6 +1322,8 @@ void Graph::run_span(uint64_t t0, size_t fpc, uint32_t call_off, uint32_t n_call
         for (uint32_t id : video_order_) { Node& vn = nodes_[id]; if (!vn.rgba_pending.empty()) launch_pending_rgba(vn, vn.rgba_pending.size(), false); vn.rgba_calls = 0; }   // the last ticks' sinks
     }
     if (prof && has_video_) hip_check(hipEventRecord(ev[groups_.size() + 1], stream_), "hipEventRecord");
+    // after everything else of the span on stream_ (the video section included): its profile interval starts at the latest event recorded there
+    launch_outputs(t0, call_off, n_calls, prof, ev);
     if (prof) { prof_runs_.push_back(std::move(ev)); prof_runs_held_.push_back(tail_held_this_span_); }
     tail_held_this_span_ = false;
 }
@@ -1235,7 +1340,7 @@ void Graph::profile_enable(bool on) { prof_on_ = on; }
 
 uint32_t Graph::profile_collect(float* ms_by_kind, float* ms_total) {
     sync();
-    if (ms_by_kind) for (int k = 0; k < MX_KIND_COUNT; ++k) ms_by_kind[k] = 0.f;
+    if (ms_by_kind) for (int k = 0; k < MX_PROFILE_KINDS; ++k) ms_by_kind[k] = 0.f;
     if (ms_total) *ms_total = 0.f;
     const uint32_t n = prof_runs_count_;   // run() calls; a run cut into spans recorded one event list per span
     prof_runs_count_ = 0;
@@ -1261,13 +1366,20 @@ uint32_t Graph::profile_collect(float* ms_by_kind, float* ms_total) {
             perf_group_ms_[i] = ms;
             last = i + 1;
         }
-        { float ms = 0.f; hip_check(hipEventElapsedTime(&ms, ev.front(), ev[last]), "hipEventElapsedTime"); if (ms_total) *ms_total += ms; perf_total_ms_ = ms; }
+        // OutputDevice launches: on stream_ after the span's groups and video section (ev[last] is the latest event before them there; their end
+        // is the run's), or behind the tail on its stream (from the last tail group's event)
+        const uint8_t od = run_i - 1 < prof_runs_od_.size() ? prof_runs_od_[run_i - 1] : 0;
+        perf_od_ms_ = 0.f;
+        hipEvent_t end = ev[last];
+        if (od & 1) { float ms = 0.f; hip_check(hipEventElapsedTime(&ms, ev[last], ev[groups_.size() + 3]), "hipEventElapsedTime"); perf_od_ms_ += ms; end = ev[groups_.size() + 3]; }
+        if (od & 2) { float ms = 0.f; hip_check(hipEventElapsedTime(&ms, ev[groups_.size()], ev[groups_.size() + 4]), "hipEventElapsedTime"); perf_od_ms_ += ms; }
+        { float ms = 0.f; hip_check(hipEventElapsedTime(&ms, ev.front(), end), "hipEventElapsedTime"); if (ms_total) *ms_total += ms; perf_total_ms_ = ms; }
         perf_calls_ = last_calls_;
         if (perf_calls_ && perf_total_ms_ * 1000.0 / perf_calls_ > 1e6 / (double)tps_)   // timing.rs:37-40: the tick ran over its budget
             perf_last_lag_s_ = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
         prof_pool_.push_back(std::move(ev));
     }
-    prof_runs_.clear(); prof_runs_held_.clear();
+    prof_runs_.clear(); prof_runs_held_.clear(); prof_runs_od_.clear();
     return n;
 }
 
@@ -1346,6 +1458,16 @@ void Graph::adopt_state(Graph& old, const int32_t* old_of_new, size_t n) {
             nn.vmixer->rebind(stream_, nn.vlazy, tps_);   // the old graph's stream may be gone after this call; this graph's fusion plan and tick rate apply
             nn.vmixer->update(p);
         }
+        if (nn.kind == MX_KIND_OUTPUT_DEVICE) {   // the module persists: its stored assignment, scratch, clip / lag times and statuses, a pending lag note
+            od_grow(nn, on.od_cmax);
+            if (on.od_cmax) {
+                const size_t bytes = (size_t)std::min(nn.od_frames * nn.od_cmax, on.od_frames * on.od_cmax) * sizeof(float);
+                hip_check(hipMemcpyAsync(nn.od_scratch.p, on.od_scratch.p, bytes, hipMemcpyDeviceToDevice, stream_), "hipMemcpyAsync(output device scratch)");
+            }
+            hip_check(hipMemcpyAsync(nn.od_state.p, on.od_state.p, sizeof(OutState), hipMemcpyDeviceToDevice, stream_), "hipMemcpyAsync(output device state)");
+            nn.od_channels = on.od_channels; nn.od_left = on.od_left; nn.od_right = on.od_right; nn.params = on.params;   // (mixlab_gpu.h: the new build's params are not applied)
+            if (on.od_lag->exchange(false)) nn.od_lag->store(true);
+        }
         if (nn.kind == MX_KIND_SOURCE_VIDEO) { nn.vsrc_ring = on.vsrc_ring; nn.vsrc_ring_pos = on.vsrc_ring_pos; nn.vsrc_sched = on.vsrc_sched; nn.vband = on.vband; nn.vband_pool = on.vband_pool; nn.vsrc = on.vsrc; nn.vsrc_dur = on.vsrc_dur; nn.vsrc_off = on.vsrc_off; nn.vsrc_repeat = on.vsrc_repeat; nn.vsrc_pending = on.vsrc_pending; }
     }
     hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
@@ -1387,6 +1509,11 @@ Graph::Perf Graph::performance_info(uint64_t* module_us, size_t cap) {
         accounted += us;
         if (module_us) for (uint32_t id : members) module_us[id] += (uint64_t)(us / (double)members.size() + 0.5);
     }
+    if (!od_nodes_.empty()) {   // OutputDevice launches, split evenly over the nodes
+        const double us = perf_od_ms_ * 1000.0 / calls;
+        accounted += us;
+        if (module_us) for (uint32_t id : od_nodes_) module_us[id] += (uint64_t)(us / (double)od_nodes_.size() + 0.5);
+    }
     pf.engine_us = (uint64_t)std::max(0.0, tick_us - accounted + 0.5);             // PerformanceAccount::Engine = tick - modules (timing.rs:43)
     return pf;
 }
@@ -1411,6 +1538,26 @@ void Graph::read_output(uint32_t node, uint32_t port, float* host, size_t frames
     const size_t fpf = floats_per_frame(n.out_type[port]);
     hip_check(hipMemcpyAsync(host, out_ptr(n, port) + fpf * f0, fpf * frames * sizeof(float), hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(D2H)");
     sync();
+}
+
+void Graph::read_audio_out(uint32_t node, uint32_t first, uint32_t n, float* samples, size_t samples_cap, OutTick* ticks, size_t* n_samples) {
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    if (node >= nodes_.size() || nodes_[node].kind != MX_KIND_OUTPUT_DEVICE) throw Error(MX_ERR_INVALID, "node is not an OUTPUT_DEVICE");
+    if ((uint64_t)first + n > last_calls_) throw Error(MX_ERR_INVALID, "the window lies beyond the last run");
+    const Node& nd = nodes_[node];
+    const size_t a = od_offset(nd, first), b = od_offset(nd, first + n);
+    if (n_samples) *n_samples = b - a;
+    if (!samples && !ticks) return;
+    if (samples && samples_cap < b - a) throw Error(MX_ERR_INVALID, "samples_cap is smaller than the window's samples");
+    wait_tail(-1);
+    if (samples && b > a) hip_check(hipMemcpyAsync(samples, (const float*)nd.od_out.p + a, (b - a) * sizeof(float), hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(D2H)");
+    if (ticks && n) hip_check(hipMemcpyAsync(ticks, (const OutTick*)nd.od_rec.p + first, (size_t)n * sizeof(OutTick), hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(D2H)");
+    sync();
+}
+
+void Graph::audio_out_lag(uint32_t node) {
+    if (node >= nodes_.size() || nodes_[node].kind != MX_KIND_OUTPUT_DEVICE) throw Error(MX_ERR_INVALID, "node is not an OUTPUT_DEVICE");
+    nodes_[node].od_lag->store(true);   // AtomicBool::store (output_device.rs:126); nothing else of the graph is touched
 }
 
 void Graph::read_output_i16(uint32_t node, uint32_t port, int16_t* host, size_t frames) {

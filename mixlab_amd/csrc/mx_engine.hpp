@@ -6,6 +6,7 @@
 // dependency level into one launch, and runs n_ticks ticks per submission.
 #pragma once
 #include <algorithm>
+#include <atomic>
 #include <functional>
 #include <hip/hip_runtime.h>
 
@@ -75,6 +76,16 @@ struct Node {
     bool mon_has_epoch = false; Rational mon_epoch;
     std::shared_ptr<Scaler> mon_scaler;
     DevBuf mon_pack;                           // the packed read-back's device staging
+    // OUTPUT_DEVICE (output_device.rs): the open stream's channel count (0: none), the stored left / right (filtered; -1: None), the largest
+    // channel count seen (what the buffers are sized for) and the input's frames per tick
+    uint32_t od_channels = 0, od_cmax = 0; int32_t od_left = -1, od_right = -1; uint32_t od_frames = 0;
+    DevBuf od_scratch;                         // the persistent scratch: od_frames * od_cmax floats, only ever grows (:185)
+    DevBuf od_state;                           // OutState
+    DevBuf od_out, od_rec, od_part;            // the last run's hand-off, per-tick records (OutTick) and the route kernel's clip partials
+    std::unique_ptr<std::atomic<bool>> od_lag; // set by the cpal callback (mx_graph_audio_out_lag), swapped by the next run
+    bool od_lag_run = false;                   // ... taken by the current run
+    struct OdSpan { uint32_t first, n, channels; };
+    std::vector<OdSpan> od_spans;              // the last run's spans, in order (the hand-off is their ticks back to back)
 };
 
 struct Group {
@@ -141,6 +152,9 @@ public:
     void profile_enable(bool on);
     uint32_t profile_collect(float* ms_by_kind, float* ms_total);   // syncs; returns number of runs collected
     void read_output(uint32_t node, uint32_t port, float* host, size_t frames, size_t first_frame = 0);   // frames [first_frame, first_frame + frames) of the last run
+    // OUTPUT_DEVICE: ticks [first, first + n) of the last run (mx_graph_read_audio_out); samples / ticks may be null
+    void read_audio_out(uint32_t node, uint32_t first, uint32_t n, float* samples, size_t samples_cap, OutTick* ticks, size_t* n_samples);
+    void audio_out_lag(uint32_t node);
     void read_output_i16(uint32_t node, uint32_t port, int16_t* host, size_t frames);   // sink hand-off format
     void write_source_i16(uint32_t node, const int16_t* host, size_t frames);            // ingest format
     float* output_ptr(uint32_t node, uint32_t port, size_t* floats_per_tick, bool stream_ordered_consumer = true /* false: a caller inside the library that orders itself
@@ -196,6 +210,10 @@ private:
     // one launch sequence over ticks [call_off, call_off + n_calls) of the current run
     void run_span(uint64_t t0, size_t fpc, uint32_t call_off, uint32_t n_calls, uint32_t run_calls);
     void apply_params(uint32_t node, const void* params, size_t len);   // update_params without the synchronisation
+    void od_update(Node& n);                                             // OUTPUT_DEVICE: ModuleT::update with n.params (output_device.rs:152-169), on a quiescent stream
+    void od_grow(Node& n, uint32_t channels);                            // ... buffers for a channel count above any seen before
+    size_t od_offset(const Node& n, uint32_t tick) const;                // float offset of tick `tick` of the last run in the hand-off
+    void launch_outputs(uint64_t t0, uint32_t call_off, uint32_t n_calls, bool prof, std::vector<hipEvent_t>& ev);   // the span's OutputDevice launches
     void refresh_gates(Group& g, uint32_t run_calls);
     uint32_t trigger_of_row(const Group& g, uint32_t row) const;        // node id of the Trigger behind row `row` of a gated group, or ~0u
     void stage_upload(void* dst, const void* src, size_t bytes);         // H2D on the graph's stream through page-locked staging
@@ -233,7 +251,8 @@ private:
     // when the bank was nearly done: no overlap at all), the EqThree workgroups are placed on an empty chip, and the Mixer's waves fill what is left.  Every join
     // (mx_graph_sync, read-backs, mx_graph_tail_stream, an exchange's submit, a cut run) releases a held launch at once.  MX_TAIL_GATE=0: launched at once as in round 4.
     struct TailLaunch { const void* desc = nullptr; uint32_t n = 0, max_ch = 0; size_t frames = 0; int dup_mode = 0; hipEvent_t prof_ev = nullptr; };
-    struct DeferredTail { bool pending = false; std::vector<TailLaunch> items; uint32_t parity = 0; hipEvent_t prof_begin = nullptr; } deferred_;   // the tail: every Mixer group from tail_gi_ on (a bank, or a bank and the buses above it), in order
+    struct DeferredTail { bool pending = false; std::vector<TailLaunch> items; uint32_t parity = 0; hipEvent_t prof_begin = nullptr;
+                          std::vector<OutRun> outs; hipEvent_t outs_prof_ev = nullptr; } deferred_;   // outs: OutputDevices that read the tail's outputs, behind it   // the tail: every Mixer group from tail_gi_ on (a bank, or a bank and the buses above it), in order
     std::function<void(hipStream_t)> tail_hook_;
     std::vector<hipEvent_t> head_waits_;
     uint64_t n_gated_ = 0, n_at_once_ = 0;
@@ -255,6 +274,9 @@ private:
     std::vector<uint32_t> sched_nodes_;     // nodes with a pending schedule (a 60 000-node graph must not be walked per tick)
     std::vector<uint32_t> plotter_nodes_;   // launched Plotter nodes
     std::vector<uint32_t> video_order_;     // the video nodes of order_, in run order
+    std::vector<uint32_t> od_nodes_;        // OutputDevice nodes of order_ (never in a launch group: launched after the span's groups, behind their input's producer)
+    std::vector<uint8_t> prof_runs_od_;     // parallel to prof_runs_: 1 OutputDevice launches on stream_ (event groups + 3), 2 on the tail stream (event groups + 4)
+    float perf_od_ms_ = 0.f;                // OutputDevice launches of the last collected run
     bool prof_this_run_ = false;
     size_t plot_job_off_ = 0;
     size_t zero_off_ = 0;

@@ -140,6 +140,22 @@ struct CopyJob { void* dst; const void* src; size_t bytes; };
 void launch_copy_jobs(const CopyJob* device_jobs, uint32_t n, hipStream_t s);   // one block per job
 // bytes out of page-locked host memory into device memory BY A KERNEL (the device reads the host buffer): ordered by the queue's own barrier packets like any launch
 void launch_upload(void* dst_device, const void* src_pinned_host, size_t bytes, hipStream_t s);
+// OutputDevice (src/module/output_device.rs:174-246, mx_k_out.hip): the node's state on the device (times in samples at the graph rate, -1 = None;
+// statuses 0 None, 1 Recent, 2 Active) and one span's launch pair
+struct OutState { int64_t last_clip, last_lag; uint32_t clip_status, lag_status; };
+struct OutTick { uint8_t clip, clip_status, lag_status, changed; uint32_t channels; };   // = mx_audio_out_tick
+struct OutRun {
+    const float* in; uint32_t dup;          // the input port at the span's first tick; dup: stored as one float per frame (L == R)
+    uint32_t frames, channels;              // frames per tick of the input's rate domain; the stream's channel count (0: no stream)
+    int32_t left, right;                    // stored assignments (-1: None), already < channels
+    uint32_t n_ticks;
+    float* scratch; float* out;             // persistent scratch (frames * channels floats at least); the span's hand-off (n_ticks * frames * channels)
+    uint32_t* partial;                      // n_ticks * out_route_blocks(frames, channels) clip partials
+    OutState* state; OutTick* rec;          // device state; the span's per-tick records
+    uint64_t t0; uint32_t spt, rate, lag;   // the span's first t (samples), samples per tick and rate of the graph; lag: the flag was set
+};
+uint32_t out_route_blocks(size_t frames_per_tick, uint32_t channels);
+void launch_output_device(const OutRun& r, hipStream_t s);
 void launch_fir(const FirDesc* d, uint32_t n, uint32_t max_taps, size_t frames, hipStream_t s, bool fc = false);
 void launch_resample(const ResampleDesc* d, uint32_t n, uint32_t max_taps, uint32_t tab_doubles /* max up * taps_per_phase */,
                      uint32_t win_frames /* max 255 * down / up + 2 + taps_per_phase */, size_t in_frames, size_t out_frames,

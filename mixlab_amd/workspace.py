@@ -108,6 +108,11 @@ class Workspace:
             return self.add(abi.KIND_MONITOR, struct.pack("<II", width, height))
         return self.add(abi.KIND_MONITOR, struct.pack("<IIII", width, height, queue_depth, 0))
 
+    def output_device(self, channels, left=None, right=None) -> int:
+        """OutputDevice (output_device.rs) once the adapter has opened cpal: channels of the open stream (0 = no stream), the device
+        channel the stereo input's left / right go to (None = unassigned).  in: Stereo; read with Graph.read_audio_out"""
+        return self.add(abi.KIND_OUTPUT_DEVICE, abi.OutputDeviceParams(channels, -1 if left is None else left, -1 if right is None else right, 0))
+
     def video_to_rgba(self, matrix_q12=None) -> int:
         from .video import to_rgba_params
         return self.add(abi.KIND_VIDEO_TO_RGBA, to_rgba_params(matrix_q12))
