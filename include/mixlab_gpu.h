@@ -27,7 +27,8 @@ extern "C" {
 
 #define MX_ABI_VERSION 4u   /* 2: mx_exchange_*, mx_monitor_tick.dropped, mx_monitor_params_ex, packed RGB pixel formats; 3: MX_FLAG_FP_CONTRACT;
                               * 4: mx_graph_read_output_window, per-pixel alpha (MX_PIXFMT_YUVA420P, mx_dframe_*_alpha; the A byte of packed RGBA honoured);
-                              *    later, without a bump (only additions): MX_KIND_OUTPUT_DEVICE, mx_graph_read_audio_out, mx_graph_audio_out_lag */
+                              *    later, without a bump (only additions): MX_KIND_OUTPUT_DEVICE, mx_graph_read_audio_out, mx_graph_audio_out_lag;
+                              *    mx_port_ref, mx_meter_params, mx_meter_tick, mx_graph_set_meters, mx_graph_read_meters */
 
 /* ---- status codes (0 ok, <0 error; cf. MIXLAB_IOCTX_ERROR / MIXLAB_IOCTX_PANIC) ---- */
 enum {
@@ -285,6 +286,39 @@ int mx_graph_audio_out_lag(mx_graph* g, uint32_t node);
  * reference's module keeps it -- channel count, stored (filtered) left / right, scratch, clip / lag times and statuses, a pending lag note --
  * and the params it was built with are not applied.  A host that changed something at the same time (another device, another channel
  * count or assignment) applies it afterwards with mx_graph_update_params, exactly as OutputDevice::update would have seen it. */
+
+/* Level meters: taps on output ports of a built graph.  A tap observes a port: it is no module, adds no edge and changes
+ * neither the run order nor the fusion plan.  Every run measures each tap's every tick on the device, once per run after its last span:
+ *   peak      the largest |x| of the tick per channel: the integer maximum of bits(x) & 0x7fffffff, read as f32 (a NaN shows as the largest
+ *             NaN pattern of the tick, +Inf as +Inf)
+ *   sum_sq    sum of x*x in f64 in a fixed order: 64 partials, partial j adds (double)x * (double)x of the frames f = j (mod 64) in ascending f
+ *             from +0.0, then s[j] = s[j] + s[j ^ k] for k = 32, 16, 8, 4, 2, 1; the result is s[0].  mean square = sum_sq / frames
+ *   over      samples with x < -1 or x > 1 (OutputDevice's clip test; NaN and +-1.0 do not count)
+ *   hold      per channel h (f32) and age a (u32), both 0 when the tap is set; every tick in order: a = min(a + 1, UINT32_MAX); when
+ *             a > hold_ticks, h = isfinite(h) ? h * release : 0; when bits(peak) >= bits(h), h = peak and a = 0; record h.  Carried across runs.
+ *   frames    frames of the tick in the port's own rate domain (a Resample output has rate * up / down); channels: 1 mono, 2 stereo (for a mono
+ *             port every [1] field is 0).  A stereo port stored as one float per frame (the fused L == R strip result) meters both channels
+ *             from that float: the records equal MX_FLAG_NO_FUSE's bit for bit. */
+typedef struct { uint32_t node, port; } mx_port_ref;
+typedef struct { uint32_t hold_ticks; float release; } mx_meter_params;   /* release: finite, 0 < release <= 1 */
+typedef struct {
+    float    peak[2];
+    float    hold[2];
+    double   sum_sq[2];
+    uint32_t over[2];
+    uint32_t frames;
+    uint32_t channels;
+} mx_meter_tick;   /* 48 bytes: peak 0, hold 8, sum_sq 16, over 32, frames 40, channels 44 */
+/* Replaces the graph's taps with ports[0..n), params[i] for ports[i] (n = 0: none; the graph then launches nothing for meters).  Video port:
+ * MX_ERR_TYPE.  A node or port out of range, a duplicate (node, port), bad params, or a port the fusion did not materialise: MX_ERR_INVALID.
+ * Waits for outstanding work like a read-back but keeps the automatic second-stream mode on.  A tap whose (node, port) was in the previous
+ * set keeps its hold state; a new one starts from 0.  Device memory: max_ticks_per_run x n x 48 bytes of records + 8 bytes per channel.
+ * mx_graph_adopt_state does not carry taps: set them again on the new graph.  Meter launches count in the profile calls' ms_total only. */
+int mx_graph_set_meters(mx_graph* g, const mx_port_ref* ports, size_t n, const mx_meter_params* params);
+/* Ticks [first_tick_in_run, first_tick_in_run + n_ticks) of the last run, laid out [tick][tap] in set order; cap = records dst holds.
+ * A window beyond the last run (or a run made before the taps were set), cap < n_ticks x taps, or no taps: MX_ERR_INVALID.  Joins the
+ * graph's streams like mx_graph_read_output. */
+int mx_graph_read_meters(mx_graph* g, uint32_t first_tick_in_run, uint32_t n_ticks, mx_meter_tick* dst, size_t cap);
 
 /* Plotter indication (src/module/plotter.rs:37-56) for tick `tick_in_run` of the last run:
  * *fired = 1 and SPT floats in each of left/right when it fired (every 6th call, input connected). */

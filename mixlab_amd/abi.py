@@ -146,6 +146,21 @@ class AudioOutTick(C.Structure):
 AUDIO_OUT_TICK_DTYPE = np.dtype([("clip", np.uint8), ("clip_status", np.uint8), ("lag_status", np.uint8), ("changed", np.uint8), ("channels", np.uint32)])
 _proto("mx_graph_read_audio_out", C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_size_t))
 _proto("mx_graph_audio_out_lag", C.c_int, C.c_void_p, C.c_uint32)
+class PortRef(C.Structure):
+    """mx_port_ref: an output terminal (node, port) a meter taps."""
+    _fields_ = [("node", C.c_uint32), ("port", C.c_uint32)]
+
+
+class MeterParams(C.Structure):
+    """mx_meter_params: ticks a peak is held before it decays, and the per-tick decay factor (finite, 0 < release <= 1)."""
+    _fields_ = [("hold_ticks", C.c_uint32), ("release", C.c_float)]
+
+
+METER_TICK_DTYPE = np.dtype({"names": ["peak", "hold", "sum_sq", "over", "frames", "channels"],
+                             "formats": [(np.float32, 2), (np.float32, 2), (np.float64, 2), (np.uint32, 2), np.uint32, np.uint32],
+                             "offsets": [0, 8, 16, 32, 40, 44], "itemsize": 48})   # mx_meter_tick
+_proto("mx_graph_set_meters", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
+_proto("mx_graph_read_meters", C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t)
 _proto("mx_graph_profile_run", C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float))
 _proto("mx_graph_profile_enable", C.c_int, C.c_void_p, C.c_int)
 _proto("mx_graph_profile_collect", C.c_int, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32))
@@ -318,6 +333,24 @@ class Graph:
     def audio_out_lag(self, node):
         """the cpal callback ran short: the next run's first tick takes the note (any thread, also during a run)"""
         check(lib.mx_graph_audio_out_lag(self._h, node))
+
+    def set_meters(self, ports, params=MeterParams(0, 1.0)):
+        """level meters on output ports [(node, port), ...]; params: one MeterParams for every tap, or a list of one per tap.
+        A tap already set keeps its peak-hold state; [] removes them all."""
+        ports = list(ports)
+        if isinstance(params, MeterParams):
+            params = [params] * len(ports)
+        pa = (PortRef * max(1, len(ports)))(*[PortRef(int(n), int(p)) for (n, p) in ports])
+        pr = (MeterParams * max(1, len(ports)))(*[MeterParams(q.hold_ticks, q.release) for q in params])
+        check(lib.mx_graph_set_meters(self._h, pa, len(ports), pr))
+        self._n_meters = len(ports)
+
+    def read_meters(self, first_tick: int, n_ticks: int) -> np.ndarray:
+        """ticks [first_tick, first_tick + n_ticks) of the last run: a METER_TICK_DTYPE array shaped (n_ticks, taps) in set order"""
+        n = getattr(self, "_n_meters", 0)
+        out = np.zeros((n_ticks, n), dtype=METER_TICK_DTYPE)
+        check(lib.mx_graph_read_meters(self._h, first_tick, n_ticks, out.ctypes.data_as(C.c_void_p), out.size))
+        return out
 
     def read_output_i16(self, node, port, n_ticks: int, stereo: bool, rate=(1, 1)) -> np.ndarray:
         out = np.empty(n_ticks * (self.spt * rate[0] // rate[1]) * (2 if stereo else 1), dtype=np.int16)

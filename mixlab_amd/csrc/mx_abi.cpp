@@ -212,6 +212,17 @@ int mx_graph_audio_out_lag(mx_graph* g, uint32_t node) {
     return guard([&] { REQUIRE(g, "graph is NULL"); g->g->audio_out_lag(node); });
 }
 
+int mx_graph_set_meters(mx_graph* g, const mx_port_ref* ports, size_t n, const mx_meter_params* params) {
+    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->set_meters(ports, n, params); });
+}
+
+int mx_graph_read_meters(mx_graph* g, uint32_t first_tick_in_run, uint32_t n_ticks, mx_meter_tick* dst, size_t cap) {
+    static_assert(sizeof(mx_meter_tick) == 48 && sizeof(mx_meter_tick) == sizeof(mx::MeterTick), "mx_meter_tick is the device record");
+    static_assert(offsetof(mx_meter_tick, sum_sq) == offsetof(mx::MeterTick, sum_sq) && offsetof(mx_meter_tick, frames) == offsetof(mx::MeterTick, frames),
+                  "mx_meter_tick is the device record");
+    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->read_meters(first_tick_in_run, n_ticks, reinterpret_cast<mx::MeterTick*>(dst), cap); });
+}
+
 int mx_graph_read_plotter(mx_graph* g, uint32_t node, uint32_t tick_in_run, float* left, float* right, int* fired) {
     return guard([&] {
         REQUIRE(g && left && right && fired, "NULL argument");

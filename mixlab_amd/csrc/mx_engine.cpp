@@ -472,6 +472,9 @@ void Graph::flush_deferred_tail(bool gated) {
     for (const OutRun& r : deferred_.outs) launch_output_device(r, tail_stream_);   // OutputDevices that read the tail's outputs
     if (!deferred_.outs.empty() && deferred_.outs_prof_ev) hip_check(hipEventRecord(deferred_.outs_prof_ev, tail_stream_), "hipEventRecord");
     deferred_.outs.clear(); deferred_.outs_prof_ev = nullptr;
+    for (const MeterRun& r : deferred_.meters) launch_meters(r, tail_stream_);   // meters on the tail's outputs
+    if (!deferred_.meters.empty() && deferred_.meters_prof_ev) hip_check(hipEventRecord(deferred_.meters_prof_ev, tail_stream_), "hipEventRecord");
+    deferred_.meters.clear(); deferred_.meters_prof_ev = nullptr;
     if (tail_hook_) { auto hook = std::move(tail_hook_); tail_hook_ = nullptr; hook(tail_stream_); }   // (mx_exchange: pack + exchange of that run's buses, behind the bank)
     // recorded AFTER the hook: whoever waits for this tail (wait_tail) is then also ordered behind the hook's reads of the buses on the tail stream -- a later run's Mixer on
     // stream_ must not overwrite them under a pack that is still copying
@@ -509,6 +512,7 @@ void Graph::end_auto_tail() {
     overlap_this_run_ = false;
     for (Group& g : groups_) { g.desc_alt.free_(); g.extra_alt.free_(); }
     build_descriptors();
+    if (!meters_.empty()) upload_meters(meter_fpc_);   // every tap on stream_, the first buffers only
 }
 
 Graph::~Graph() {
@@ -1027,6 +1031,7 @@ void Graph::bind_source(uint32_t node, const void* dev) {
     sync();
     n.bound = (const float*)dev;
     build_descriptors();
+    if (!meters_.empty()) upload_meters(meter_fpc_);
 }
 
 void Graph::set_input_enabled(uint32_t node, uint32_t port, bool enabled) {
@@ -1054,6 +1059,7 @@ void Graph::ensure_capacity(size_t frames) {
     cap_frames_ = frames;
     layout_slab();
     build_descriptors();
+    if (!meters_.empty()) upload_meters(meter_fpc_);   // the ports moved; room for more ticks
 }
 
 static bool group_launches(const Group& g);
@@ -1062,8 +1068,9 @@ void Graph::run(uint64_t t0, size_t fpc, uint32_t n_calls, float* ms_by_kind, fl
     const size_t frames = fpc * (size_t)n_calls;
     auto drop_schedules = [&] { for (uint32_t id : sched_nodes_) { nodes_[id].sched.clear(); nodes_[id].gate_sched.clear(); } sched_nodes_.clear(); };
     if (frames > cap_frames_) { drop_schedules(); throw Error(MX_ERR_INVALID, "n_ticks exceeds max_ticks_per_run"); }
-    if (n_calls == 0 || fpc == 0) { drop_schedules(); last_calls_ = n_calls; last_frames_per_call_ = fpc; return; }
+    if (n_calls == 0 || fpc == 0) { drop_schedules(); last_calls_ = n_calls; last_frames_per_call_ = fpc; meter_run_ticks_ = 0; return; }
     hip_check(hipSetDevice(device_), "hipSetDevice");
+    if (!meters_.empty() && fpc != meter_fpc_) { sync(); upload_meters(fpc); }   // (the module compat path's call length): frames per tick and record room
 
     // ---- scheduled parameter updates (Engine::client_update between two ticks, src/engine.rs:192-214,277-398) ----
     // Trigger updates travel as one gate bit per tick and cost nothing.  Any other module's update cuts the run into spans:
@@ -1174,6 +1181,7 @@ void Graph::run(uint64_t t0, size_t fpc, uint32_t n_calls, float* ms_by_kind, fl
     hip_check(hipGetLastError(), "kernel launch");
     last_calls_ = n_calls;
     last_frames_per_call_ = fpc;
+    meter_run_ticks_ = meters_.empty() ? 0u : n_calls;
     if (prof) ++prof_runs_count_;
     if (ms_by_kind) (void)profile_collect(ms_by_kind, ms_total);
 }
@@ -1186,7 +1194,7 @@ void Graph::run_span(uint64_t t0, size_t fpc, uint32_t call_off, uint32_t n_call
     if (prof) {
         if (!prof_pool_.empty()) { ev = std::move(prof_pool_.back()); prof_pool_.pop_back(); }
         else {
-            ev.resize(groups_.size() + 5);   // one slot per launch group + the per-tick video section + the begin of a tail launch that was held back (its own stream) + OutputDevices on either stream
+            ev.resize(groups_.size() + 7);   // one slot per launch group + the per-tick video section + the begin of a tail launch that was held back (its own stream) + OutputDevices on either stream + meters on either stream
             for (auto& e : ev) hip_check(hipEventCreate(&e), "hipEventCreate");
         }
         hip_check(hipEventRecord(ev[0], stream_), "hipEventRecord");
@@ -1265,7 +1273,7 @@ void Graph::run_span(uint64_t t0, size_t fpc, uint32_t call_off, uint32_t n_call
                     if (deferred_.pending) flush_deferred_tail(false);   // (a run whose earlier groups had no speculative EqThree launch: nothing opened a gate)
                     hip_check(hipEventRecord(ev_head_done_, stream_), "hipEventRecord");
                     if (tail_gate_ < 0) { const char* e = getenv("MX_TAIL_GATE"); tail_gate_ = e && atoi(e) == 0 ? 0 : 1; }   // A/B: 0 = launched at once (round 4's form)
-                    if (tail_gate_) { deferred_.items.clear(); deferred_.outs.clear(); deferred_.parity = parity_; deferred_.prof_begin = prof ? ev[groups_.size() + 2] : nullptr; tail_held_this_span_ = true; }
+                    if (tail_gate_) { deferred_.items.clear(); deferred_.outs.clear(); deferred_.meters.clear(); deferred_.parity = parity_; deferred_.prof_begin = prof ? ev[groups_.size() + 2] : nullptr; tail_held_this_span_ = true; }
                     else hip_check(hipStreamWaitEvent(tail_stream_, ev_head_done_, 0), "hipStreamWaitEvent");
                 }
                 if (tail_gate_) {
@@ -1314,7 +1322,6 @@ void Graph::run_span(uint64_t t0, size_t fpc, uint32_t call_off, uint32_t n_call
         if (prof && group_launches(g)) hip_check(hipEventRecord(ev[gi + 1], stream_), "hipEventRecord");
         ++gi;
     }
-    (void)run_calls;
     // video sub-graph: tick by tick (frames arrive per tick; nothing to batch over time)
     if (has_video_) {
         for (uint32_t c = 0; c < n_calls; ++c) run_video_tick(t0 + (uint64_t)c * fpc);
@@ -1324,6 +1331,8 @@ void Graph::run_span(uint64_t t0, size_t fpc, uint32_t call_off, uint32_t n_call
     if (prof && has_video_) hip_check(hipEventRecord(ev[groups_.size() + 1], stream_), "hipEventRecord");
     // after everything else of the span on stream_ (the video section included): its profile interval starts at the latest event recorded there
     launch_outputs(t0, call_off, n_calls, prof, ev);
+    // the port buffers hold every tick of the run: the meters go once, after its last span
+    if (call_off + n_calls == run_calls) launch_meter_taps(run_calls, prof, ev);
     if (prof) { prof_runs_.push_back(std::move(ev)); prof_runs_held_.push_back(tail_held_this_span_); }
     tail_held_this_span_ = false;
 }
@@ -1373,7 +1382,16 @@ uint32_t Graph::profile_collect(float* ms_by_kind, float* ms_total) {
         hipEvent_t end = ev[last];
         if (od & 1) { float ms = 0.f; hip_check(hipEventElapsedTime(&ms, ev[last], ev[groups_.size() + 3]), "hipEventElapsedTime"); perf_od_ms_ += ms; end = ev[groups_.size() + 3]; }
         if (od & 2) { float ms = 0.f; hip_check(hipEventElapsedTime(&ms, ev[groups_.size()], ev[groups_.size() + 4]), "hipEventElapsedTime"); perf_od_ms_ += ms; }
+        // meter launches: no kind of their own, counted in the total (and so in engine_us): on stream_ last of all, or on the tail stream
+        // behind the tail (and its OutputDevices)
+        if (od & 4) end = ev[groups_.size() + 5];
         { float ms = 0.f; hip_check(hipEventElapsedTime(&ms, ev.front(), end), "hipEventElapsedTime"); if (ms_total) *ms_total += ms; perf_total_ms_ = ms; }
+        if (od & 8) {
+            float ms = 0.f;
+            hip_check(hipEventElapsedTime(&ms, ev[(od & 2) ? groups_.size() + 4 : groups_.size()], ev[groups_.size() + 6]), "hipEventElapsedTime");
+            if (ms_total) *ms_total += ms;
+            perf_total_ms_ += ms;
+        }
         perf_calls_ = last_calls_;
         if (perf_calls_ && perf_total_ms_ * 1000.0 / perf_calls_ > 1e6 / (double)tps_)   // timing.rs:37-40: the tick ran over its budget
             perf_last_lag_s_ = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -1558,6 +1576,130 @@ void Graph::read_audio_out(uint32_t node, uint32_t first, uint32_t n, float* sam
 void Graph::audio_out_lag(uint32_t node) {
     if (node >= nodes_.size() || nodes_[node].kind != MX_KIND_OUTPUT_DEVICE) throw Error(MX_ERR_INVALID, "node is not an OUTPUT_DEVICE");
     nodes_[node].od_lag->store(true);   // AtomicBool::store (output_device.rs:126); nothing else of the graph is touched
+}
+
+// ---- level meters (mixlab_gpu.h mx_graph_set_meters) ----
+
+void Graph::set_meters(const mx_port_ref* ports, size_t n, const mx_meter_params* params) {
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    if (n && (!ports || !params)) throw Error(MX_ERR_INVALID, "ports / params is NULL");
+    if (n > 0xffffffu) throw Error(MX_ERR_INVALID, "more than 2^24 meters");
+    std::vector<MeterTap> taps(n);
+    std::vector<uint64_t> keys(n);
+    for (size_t i = 0; i < n; ++i) {
+        const mx_port_ref pr = ports[i];
+        if (pr.node >= nodes_.size() || pr.port >= nodes_[pr.node].out_type.size()) throw Error(MX_ERR_INVALID, "meter: output terminal out of range");
+        const Node& nd = nodes_[pr.node];
+        if (nd.out_type[pr.port] == MX_VIDEO) throw Error(MX_ERR_TYPE, "meter: a video port has no level");
+        if (nd.out_elided[pr.port]) throw Error(MX_ERR_INVALID, "port is not materialised: it only feeds a fused consumer (build with MX_FLAG_NO_FUSE to observe it)");
+        const float rel = params[i].release;
+        if (!(std::isfinite(rel) && rel > 0.0f && rel <= 1.0f)) throw Error(MX_ERR_INVALID, "mx_meter_params: release must be finite, 0 < release <= 1");
+        taps[i] = MeterTap{pr.node, pr.port, params[i].hold_ticks, rel};
+        keys[i] = (uint64_t)pr.node << 32 | pr.port;
+    }
+    { std::vector<uint64_t> k = keys; std::sort(k.begin(), k.end()); if (std::adjacent_find(k.begin(), k.end()) != k.end()) throw Error(MX_ERR_INVALID, "meter: duplicate (node, port)"); }
+    // like a read-back: the last run's launches (held-back tail included) are done with the records and states.  The second-stream mode stays on:
+    // the meters read the ports through descriptors of both parities, in stream order with their producers (launch_meter_taps)
+    sync();
+    DevBuf st;
+    if (n) {
+        st.alloc(n * 2 * sizeof(MeterHold));
+        hip_check(hipMemsetAsync(st.p, 0, n * 2 * sizeof(MeterHold), stream_), "hipMemsetAsync(meter state)");
+        for (size_t i = 0; i < n; ++i)   // a surviving tap keeps its hold
+            for (size_t j = 0; j < meters_.size(); ++j)
+                if (meters_[j].node == taps[i].node && meters_[j].port == taps[i].port)
+                    hip_check(hipMemcpyAsync((MeterHold*)st.p + 2 * i, (const MeterHold*)meter_state_.p + 2 * j, 2 * sizeof(MeterHold), hipMemcpyDeviceToDevice, stream_),
+                              "hipMemcpyAsync(meter state)");
+        hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
+    }
+    meters_ = std::move(taps);
+    meter_state_ = std::move(st);
+    meter_run_ticks_ = 0;
+    meter_rec_.free_();
+    if (meters_.empty()) { meter_desc_.free_(); return; }
+    upload_meters(meter_fpc_ ? meter_fpc_ : spt_);
+}
+
+// The descriptors of every tap for both buffer parities (the second only differs for a port the tail reads, while the second-stream mode is on),
+// and room for a whole submission's records.  The stream is quiescent.
+void Graph::upload_meters(size_t fpc) {
+    meter_fpc_ = fpc;
+    const size_t n = meters_.size();
+    // launch order: the taps read on stream_, then those on the tail's outputs
+    std::vector<uint32_t> order, tail;
+    for (uint32_t i = 0; i < (uint32_t)n; ++i) {
+        int32_t o = (int32_t)meters_[i].node;
+        while (nodes_[o].elided && nodes_[o].owner >= 0) o = nodes_[o].owner;   // the node whose launch writes the port
+        (tail_gi_ >= 0 && nodes_[o].group >= tail_gi_ ? tail : order).push_back(i);
+    }
+    meter_n_head_ = (uint32_t)order.size();
+    order.insert(order.end(), tail.begin(), tail.end());
+    std::vector<MeterDesc> d(2 * n);
+    for (uint32_t par = 0; par < 2; ++par)
+        for (size_t k = 0; k < n; ++k) {
+            const MeterTap& tp = meters_[order[k]];
+            const Node& nd = nodes_[tp.node];
+            MeterDesc& m = d[par * n + k];
+            // the port at tick 0 of the run (out_ptr without a span's offset)
+            if (nd.bound && tp.port == 0) m.p = nd.bound;
+            else m.p = (const float*)slab_.p + (par && nd.out_off2[tp.port] != SIZE_MAX ? nd.out_off2[tp.port] : nd.out_off[tp.port]);
+            m.frames = (uint32_t)(fpc * nd.dom_num / nd.dom_den);
+            m.layout = nd.out_dup[tp.port] ? METER_DUP : (nd.out_type[tp.port] == MX_MONO ? METER_MONO : METER_STEREO);
+            m.slot = order[k]; m.hold_ticks = tp.hold_ticks; m.release = tp.release; m._pad = 0;
+        }
+    meter_desc_.alloc(d.size() * sizeof(MeterDesc));
+    hip_check(hipMemcpy(meter_desc_.p, d.data(), d.size() * sizeof(MeterDesc), hipMemcpyHostToDevice), "hipMemcpy(meter descriptors)");
+    const size_t need = std::max<size_t>(1, cap_frames_ / fpc) * n * sizeof(MeterTick);
+    if (!meter_rec_.p || meter_rec_.bytes < need) meter_rec_.alloc(need);
+}
+
+// The run's meter launches, after its last span.  Why no buffer a meter reads is overwritten before it has read it:
+//  - a tap read on stream_ (every tap when the run is on one stream: a cut run, a short one in the automatic mode, a graph without the mode)
+//    is queued there behind the run's producers and ahead of the next run's launches, which are the only ones that write that port again.  Its
+//    descriptor points at THIS run's buffer parity: the tail-read ports alternate per run, run k + 1 writes the other buffer, and run k + 2 --
+//    the next writer of this one -- comes after the meter on the same stream;
+//  - a tap on an output of the tail (the Mixer bank and the buses above it) goes on the tail stream behind the tail's last launch, held back
+//    with it (deferred_.meters) when the tail is held.  Those outputs are single buffers written only by the tail, whose next launch (run
+//    k + 1's) is queued behind this one on that same stream.  ev_tail_done_ is recorded after it, so every join -- read_meters, read_output,
+//    a run that reuses this parity -- covers the meter too.
+// The records and hold states of the two groups of taps are disjoint (slots); a later run's meters of a group follow on that group's stream.
+void Graph::launch_meter_taps(uint32_t n_calls, bool prof, std::vector<hipEvent_t>& ev) {
+    if (meters_.empty()) return;
+    const uint32_t n = (uint32_t)meters_.size();
+    const MeterDesc* d = (const MeterDesc*)meter_desc_.p + (size_t)(parity_ & 1u) * n;
+    MeterRun all{d, n, n_calls, n, (MeterTick*)meter_rec_.p, (MeterHold*)meter_state_.p};
+    uint8_t where = 0;
+    if (!overlap_this_run_ || meter_n_head_ == n) {
+        launch_meters(all, stream_); where |= 4;
+    } else {
+        if (meter_n_head_) { MeterRun h = all; h.n = meter_n_head_; launch_meters(h, stream_); where |= 4; }
+        MeterRun t = all; t.desc = d + meter_n_head_; t.n = n - meter_n_head_;
+        if (tail_gate_) {
+            deferred_.meters.push_back(t);
+            deferred_.meters_prof_ev = prof ? ev[groups_.size() + 6] : nullptr;
+        } else {
+            launch_meters(t, tail_stream_);
+            if (prof) hip_check(hipEventRecord(ev[groups_.size() + 6], tail_stream_), "hipEventRecord");
+            hip_check(hipEventRecord(ev_tail_done_[parity_], tail_stream_), "hipEventRecord");   // joins of the tail cover the meters
+        }
+        where |= 8;
+    }
+    if (prof && (where & 4)) hip_check(hipEventRecord(ev[groups_.size() + 5], stream_), "hipEventRecord");
+    if (prof && !prof_runs_od_.empty()) prof_runs_od_.back() |= where;
+}
+
+void Graph::read_meters(uint32_t first, uint32_t n, MeterTick* dst, size_t cap) {
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    if (meters_.empty()) throw Error(MX_ERR_INVALID, "no meters are set");
+    if ((uint64_t)first + n > meter_run_ticks_) throw Error(MX_ERR_INVALID, "the window lies beyond the last run (or no run since the meters were set)");
+    const size_t count = (size_t)n * meters_.size();
+    if (cap < count) throw Error(MX_ERR_INVALID, "cap is smaller than n_ticks x meters");
+    if (count && !dst) throw Error(MX_ERR_INVALID, "dst is NULL");
+    if (!count) return;
+    wait_tail(-1);
+    hip_check(hipMemcpyAsync(dst, (const MeterTick*)meter_rec_.p + (size_t)first * meters_.size(), count * sizeof(MeterTick), hipMemcpyDeviceToHost, stream_),
+              "hipMemcpyAsync(D2H)");
+    sync();
 }
 
 void Graph::read_output_i16(uint32_t node, uint32_t port, int16_t* host, size_t frames) {

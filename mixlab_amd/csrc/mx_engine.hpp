@@ -155,6 +155,9 @@ public:
     // OUTPUT_DEVICE: ticks [first, first + n) of the last run (mx_graph_read_audio_out); samples / ticks may be null
     void read_audio_out(uint32_t node, uint32_t first, uint32_t n, float* samples, size_t samples_cap, OutTick* ticks, size_t* n_samples);
     void audio_out_lag(uint32_t node);
+    // level meters (mx_graph_set_meters / mx_graph_read_meters): taps on output ports, measured once per run after its last span
+    void set_meters(const mx_port_ref* ports, size_t n, const mx_meter_params* params);
+    void read_meters(uint32_t first, uint32_t n, MeterTick* dst, size_t cap);
     void read_output_i16(uint32_t node, uint32_t port, int16_t* host, size_t frames);   // sink hand-off format
     void write_source_i16(uint32_t node, const int16_t* host, size_t frames);            // ingest format
     float* output_ptr(uint32_t node, uint32_t port, size_t* floats_per_tick, bool stream_ordered_consumer = true /* false: a caller inside the library that orders itself
@@ -214,6 +217,8 @@ private:
     void od_grow(Node& n, uint32_t channels);                            // ... buffers for a channel count above any seen before
     size_t od_offset(const Node& n, uint32_t tick) const;                // float offset of tick `tick` of the last run in the hand-off
     void launch_outputs(uint64_t t0, uint32_t call_off, uint32_t n_calls, bool prof, std::vector<hipEvent_t>& ev);   // the span's OutputDevice launches
+    void upload_meters(size_t fpc);                                      // the taps' descriptors (both parities) and record room, on a quiescent stream
+    void launch_meter_taps(uint32_t n_calls, bool prof, std::vector<hipEvent_t>& ev);   // the run's meter launches (after its last span)
     void refresh_gates(Group& g, uint32_t run_calls);
     uint32_t trigger_of_row(const Group& g, uint32_t row) const;        // node id of the Trigger behind row `row` of a gated group, or ~0u
     void stage_upload(void* dst, const void* src, size_t bytes);         // H2D on the graph's stream through page-locked staging
@@ -252,7 +257,8 @@ private:
     // (mx_graph_sync, read-backs, mx_graph_tail_stream, an exchange's submit, a cut run) releases a held launch at once.  MX_TAIL_GATE=0: launched at once as in round 4.
     struct TailLaunch { const void* desc = nullptr; uint32_t n = 0, max_ch = 0; size_t frames = 0; int dup_mode = 0; hipEvent_t prof_ev = nullptr; };
     struct DeferredTail { bool pending = false; std::vector<TailLaunch> items; uint32_t parity = 0; hipEvent_t prof_begin = nullptr;
-                          std::vector<OutRun> outs; hipEvent_t outs_prof_ev = nullptr; } deferred_;   // outs: OutputDevices that read the tail's outputs, behind it   // the tail: every Mixer group from tail_gi_ on (a bank, or a bank and the buses above it), in order
+                          std::vector<OutRun> outs; hipEvent_t outs_prof_ev = nullptr;
+                          std::vector<MeterRun> meters; hipEvent_t meters_prof_ev = nullptr; } deferred_;   // outs: OutputDevices that read the tail's outputs, behind it   // the tail: every Mixer group from tail_gi_ on (a bank, or a bank and the buses above it), in order
     std::function<void(hipStream_t)> tail_hook_;
     std::vector<hipEvent_t> head_waits_;
     uint64_t n_gated_ = 0, n_at_once_ = 0;
@@ -275,7 +281,17 @@ private:
     std::vector<uint32_t> plotter_nodes_;   // launched Plotter nodes
     std::vector<uint32_t> video_order_;     // the video nodes of order_, in run order
     std::vector<uint32_t> od_nodes_;        // OutputDevice nodes of order_ (never in a launch group: launched after the span's groups, behind their input's producer)
-    std::vector<uint8_t> prof_runs_od_;     // parallel to prof_runs_: 1 OutputDevice launches on stream_ (event groups + 3), 2 on the tail stream (event groups + 4)
+    std::vector<uint8_t> prof_runs_od_;     // parallel to prof_runs_: 1 OutputDevice launches on stream_ (event groups + 3), 2 on the tail stream (event groups + 4),
+                                            // 4 meter launches on stream_ (groups + 5), 8 on the tail stream (groups + 6)
+    // level meters: the taps in set order; launch order puts the taps read on stream_ first (meter_n_head_ of them), then the taps on outputs of
+    // the tail (behind the Mixer bank on its stream while the second-stream mode is on).  meter_desc_: MeterDesc[2][n] in launch order, one row
+    // per buffer parity; meter_rec_: MeterTick[max ticks][n]; meter_state_: MeterHold[n][2]
+    struct MeterTap { uint32_t node, port, hold_ticks; float release; };
+    std::vector<MeterTap> meters_;
+    uint32_t meter_n_head_ = 0;
+    DevBuf meter_desc_, meter_rec_, meter_state_;
+    size_t meter_fpc_ = 0;                  // frames per call the descriptors were built for
+    uint32_t meter_run_ticks_ = 0;          // ticks of the last run that measured the current taps (0: none since they were set)
     float perf_od_ms_ = 0.f;                // OutputDevice launches of the last collected run
     bool prof_this_run_ = false;
     size_t plot_job_off_ = 0;

@@ -156,6 +156,19 @@ struct OutRun {
 };
 uint32_t out_route_blocks(size_t frames_per_tick, uint32_t channels);
 void launch_output_device(const OutRun& r, hipStream_t s);
+// Level meters (mx_k_meter.hip, mixlab_gpu.h mx_graph_set_meters): one descriptor per tap and buffer parity, the per-tick record (=
+// mx_meter_tick) and each channel's peak-hold state
+enum : uint32_t { METER_MONO = 0, METER_STEREO = 1, METER_DUP = 2 };   // METER_DUP: stereo stored as one float per frame (L == R)
+struct MeterDesc { const float* p; uint32_t frames, layout, slot, hold_ticks; float release; uint32_t _pad; };   // p: the port at tick 0 of the run; slot: index in set order
+struct MeterTick { float peak[2], hold[2]; double sum_sq[2]; uint32_t over[2], frames, channels; };
+struct MeterHold { float h; uint32_t a; };
+struct MeterRun {
+    const MeterDesc* desc; uint32_t n;       // the launch's taps
+    uint32_t n_ticks, stride;                // ticks of the run; records per tick (every tap of the set)
+    MeterTick* rec; MeterHold* state;        // rec[tick * stride + slot]; state[2 * slot + channel]
+};
+void launch_meters(const MeterRun& r, hipStream_t s);   // k_meter_reduce, then k_meter_hold
+
 void launch_fir(const FirDesc* d, uint32_t n, uint32_t max_taps, size_t frames, hipStream_t s, bool fc = false);
 void launch_resample(const ResampleDesc* d, uint32_t n, uint32_t max_taps, uint32_t tab_doubles /* max up * taps_per_phase */,
                      uint32_t win_frames /* max 255 * down / up + 2 + taps_per_phase */, size_t in_frames, size_t out_frames,
