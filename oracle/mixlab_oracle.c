@@ -375,6 +375,7 @@ static int node_ports(onode* n) {
     case ORC_KIND_SOURCE_MONO: ni = 0; no = 1; ot[0] = LT_MONO; break;
     case ORC_KIND_SOURCE_STEREO: ni = 0; no = 1; ot[0] = LT_STEREO; break;
     case ORC_KIND_FIR: case ORC_KIND_RESAMPLE: ni = 1; it[0] = LT_STEREO; no = 1; ot[0] = LT_STEREO; break;
+    case ORC_KIND_OUTPUT_DEVICE: ni = 1; it[0] = LT_STEREO; no = 0; break;                              /* output_device.rs:80 */
     case ORC_KIND_MIXER: {
         uint32_t nch = n->params_len / (uint32_t)sizeof(orc_mixer_channel_params);              /* mixer.rs:22-28 */
         n->n_in = nch; n->n_out = 2;
@@ -444,12 +445,20 @@ orc_graph* orc_graph_build(const orc_node* nodes, size_t n_nodes, const orc_edge
     for (size_t e = 0; e < n_edges; e++) feeds[edges[e].src_node] = 1;
     for (size_t i = 0; i < n_nodes; i++) if (!feeds[i]) traverse(g, (uint32_t)i, seen);
     free(feeds); free(seen);
-    /* sample-rate domains (build-specified Resample nodes change them), then the port buffers */
+    /* sample-rate domains (build-specified Resample nodes change them), then the port buffers.  A back-edge reads Disconnected, so it
+     * carries no domain; the inputs that remain must share one (Graph::Graph, mx_engine.cpp). */
+    int64_t* pos = (int64_t*)malloc(sizeof(int64_t) * (n_nodes ? n_nodes : 1));
+    for (size_t i = 0; i < n_nodes; i++) pos[i] = -1;
+    for (size_t oi = 0; oi < g->n_order; oi++) pos[g->order[oi]] = (int64_t)oi;
     for (size_t oi = 0; oi < g->n_order; oi++) {
         onode* n = &g->nodes[g->order[oi]];
+        int have = 0;
         for (uint32_t k = 0; k < n->n_in; k++) if (n->in_src_node[k] >= 0) {
+            const int64_t p = pos[n->in_src_node[k]];
+            if (p < 0 || p >= (int64_t)oi) continue;   /* back-edge */
             const onode* sn = &g->nodes[n->in_src_node[k]];
-            n->in_dom_num = sn->dom_num; n->in_dom_den = sn->dom_den;
+            if (have && (sn->dom_num != n->in_dom_num || sn->dom_den != n->in_dom_den)) { free(pos); orc_graph_destroy(g); return NULL; }
+            n->in_dom_num = sn->dom_num; n->in_dom_den = sn->dom_den; have = 1;
         }
         n->dom_num = n->in_dom_num; n->dom_den = n->in_dom_den;
         if (n->kind == ORC_KIND_RESAMPLE) {
@@ -461,6 +470,7 @@ orc_graph* orc_graph_build(const orc_node* nodes, size_t n_nodes, const orc_edge
         }
         if (n->kind == ORC_KIND_FIR) n->hist = (float*)calloc(2 * (size_t)((const uint32_t*)n->params)[0], sizeof(float));
     }
+    free(pos);
     for (size_t i = 0; i < n_nodes; i++) {
         onode* n = &g->nodes[i];
         for (uint32_t k = 0; k < n->n_out; k++) n->out_buf[k] = (float*)calloc(node_len(g, n, n->out_type[k]) + 1, sizeof(float));
@@ -577,6 +587,8 @@ int orc_graph_run_tick(orc_graph* g, uint64_t tick) {
             break;
         case ORC_KIND_SOURCE_STEREO:
             if (n->source) memcpy(n->out_buf[0], n->source + (n->source_ring ? (tick % n->source_ring) * 2 * spt : 0), 2 * spt * sizeof(float));
+            break;
+        case ORC_KIND_OUTPUT_DEVICE:   /* a sink: what it hands off is tests/output_device_model.py's, fed this tick's input port */
             break;
         default: return -1;
         }

@@ -48,7 +48,10 @@ enum {
     ORC_KIND_SOURCE_VIDEO = 13, ORC_KIND_VIDEO_TO_RGBA = 14,   /* not handled by the audio graph runner */
     ORC_KIND_FIR = 15,           /* build-specified (no reference module) */
     ORC_KIND_RESAMPLE = 16,      /* build-specified (no reference module) */
-    ORC_KIND_COUNT = 17
+    ORC_KIND_MONITOR = 17,       /* not handled by the audio graph runner */
+    ORC_KIND_OUTPUT_DEVICE = 18, /* a sink: one stereo input, no outputs, nothing computed here (tests/output_device_model.py is its
+                                  * arithmetic); it takes its place in the run order and the domain pass */
+    ORC_KIND_COUNT = 19
 };
 
 /* protocol/src/lib.rs:233-241 (bincode variant order) */
@@ -130,7 +133,9 @@ typedef struct { uint32_t src_node, src_port, dst_node, dst_port; } orc_edge;
 typedef struct orc_graph orc_graph;
 
 /* sample_rate/ticks_per_second are compile-time 44100/60 in the reference (src/engine.rs:52-55);
- * they are parameters here only so the 48 kHz performance configuration has a CPU baseline. */
+ * they are parameters here only so the 48 kHz performance configuration has a CPU baseline.
+ * Sample-rate domains follow Graph::Graph (mx_engine.cpp): a back-edge (an input whose producer runs later in the tick, or never)
+ * does not give its node a domain, and a node whose other inputs live in two domains is refused (NULL). */
 orc_graph* orc_graph_build(const orc_node* nodes, size_t n_nodes, const orc_edge* edges, size_t n_edges,
                            uint32_t sample_rate, uint32_t ticks_per_second);
 void orc_graph_destroy(orc_graph* g);

@@ -8,7 +8,7 @@ from meter_model import MeterModel, records_equal
 from mixlab_amd import abi
 from mixlab_amd.workspace import Workspace
 from test_gpu_audio_parity import strips
-from tick_shapes import SHAPES
+from tick_shapes import SHAPES, by_id
 
 pytestmark = pytest.mark.gpu
 
@@ -133,31 +133,44 @@ def test_resample_output_and_bound_source():
         check_run(g2, taps2, n, f"bound run {r}")
 
 
-@pytest.mark.parametrize("n_taps", [1, 7, 1024, 1031])
-def test_many_taps(n_taps):
-    sr, n = 48000, 3
-    ws = Workspace(sr, 60)
-    nodes = [ws.source_mono() if k % 3 else ws.source_stereo() for k in range(n_taps)]
+@pytest.mark.parametrize("n_taps,shape_id,n", [pytest.param(k, "48k", 3, id=str(k)) for k in (1, 7, 1024, 1031)]
+                         # beyond 16 384 (tap, tick) pairs: k_meter_reduce's grid (4096 blocks of 4 waves) strides over the rest
+                         + [pytest.param(9, "8k_8000", 5000, id="9-8k_8000-5000"), pytest.param(1031, "48k", 20, id="1031-48k-20")])
+def test_many_taps(n_taps, shape_id, n):
+    shape = by_id(shape_id)
+    spt = shape.spt
+    ws, mix, strip_srcs, trigs = strips(2, shape.sample_rate, shape.ticks_per_second)
+    n_dup = 2 if n_taps >= 3 else 0   # the strips' Amplifiers, read by the Mixer alone: stored one float per frame
+    nodes = [ws.source_mono() if k % 3 else ws.source_stereo() for k in range(n_taps - n_dup)]
     g = ws.build(max_ticks_per_run=n)
     taps = [Tap(s, 0, 1 if k % 3 else 2, hold_ticks=k % 4, release=0.5 + (k % 5) / 10) for k, s in enumerate(nodes)]
+    taps += [Tap(mix + 6 * (k + 1), 0, 2, hold_ticks=k, release=0.9) for k in range(n_dup)]
     set_taps(g, taps)
     for r in range(2):
         for k, s in enumerate(nodes):
-            g.write_source(s, synth.noise(k + 7 * r, n * 800 * taps[k].channels) * np.float32(1 + k % 3), n)
+            g.write_source(s, synth.noise(k + 7 * r, n * spt * taps[k].channels) * np.float32(1 + k % 3), n)
+        for k, s in enumerate(strip_srcs):
+            g.write_source(s, synth.noise(5000 + k + 7 * r, n * spt) * np.float32(3.0), n)
         g.run_ticks(r * n, n)
         check_run(g, taps, n, f"{n_taps} taps run {r}")
 
 
-def test_long_runs_and_one_tick_runs():
-    sr, n = 48000, 2048
-    ws, ss, sm, amp, g = io_graph(sr, 60, n)
-    taps = [Tap(amp, 0, 2, hold_ticks=30, release=0.9), Tap(sm, 0, 1, hold_ticks=3, release=0.99)]
+@pytest.mark.parametrize("shape_id,n", [("48k", 2048), ("8k_8000", 5000)])   # 5000 ticks: more than two of k_meter_hold's 2048-tick chunks
+def test_long_runs_and_one_tick_runs(shape_id, n):
+    shape = by_id(shape_id)
+    spt = shape.spt
+    ws, ss, sm, amp, g = io_graph(shape.sample_rate, shape.ticks_per_second, n)
+    taps = [Tap(amp, 0, 2, hold_ticks=30, release=0.9), Tap(sm, 0, 1, hold_ticks=3, release=0.99),
+            Tap(ss, 0, 2, hold_ticks=1500, release=0.999)]   # holds that span the chunk boundaries
     set_taps(g, taps)
-    g.write_source(ss, spicy(1, n * 1600), n); g.write_source(sm, spicy(2, n * 800, 0.8), n)
+    g.write_source(ss, spicy(1, n * 2 * spt), n); g.write_source(sm, spicy(2, n * spt, 0.8), n)
     g.run_ticks(0, n)
-    check_run(g, taps, n, "2048 ticks")
+    got = check_run(g, taps, n, f"{n} ticks")
+    if n > 2048:   # a hold taken before a chunk boundary is still held after it
+        h = got["hold"][:, 2, 0].view(np.uint32)
+        assert any(h[b - 1] == h[b] and got["peak"][b, 2, 0] < got["hold"][b, 2, 0] for b in (2048, 4096))
     for r in range(4):   # one-tick runs on the same graph, the hold carried on
-        g.write_source(ss, spicy(30 + r, 1600), 1); g.write_source(sm, spicy(40 + r, 800), 1)
+        g.write_source(ss, spicy(30 + r, 2 * spt), 1); g.write_source(sm, spicy(40 + r, spt), 1)
         g.run_ticks(n + r, 1)
         check_run(g, taps, 1, f"one tick {r}")
 

@@ -64,16 +64,23 @@ def test_hand_off_and_records_at_every_tick_shape(shape, channels, n_ticks):
         check_run(g, od, model, g.read_output(amp, 0, n_ticks, True), r * n_ticks * spt, spt, n_ticks, f"run {r}")
 
 
-@pytest.mark.parametrize("sr", [44100, 48000])
-@pytest.mark.parametrize("channels,n_ticks", [(2, 64), (8, 64), (256, 64), (2, 2048)])
-def test_long_submissions(sr, channels, n_ticks):
-    spt = sr // 60
-    ws, src, amp, od, g = amp_graph(sr, 60, channels, 1, 0, n_ticks)
+@pytest.mark.parametrize("sr,tps,channels,n_ticks", [pytest.param(sr, 60, c, n, id=f"{c}-{n}-{sr}") for (c, n) in ((2, 64), (8, 64), (256, 64), (2, 2048))
+                                                      for sr in (44100, 48000)]
+                         + [pytest.param(8000, 8000, c, 5000, id=f"{c}-5000-8k_8000") for c in (2, 256)])
+def test_long_submissions(sr, tps, channels, n_ticks):
+    spt = sr // tps
+    ws, src, amp, od, g = amp_graph(sr, tps, channels, 1, 0, n_ticks)
     model = OutputDeviceModel(sr, channels, 1, 0)
     for r in range(2):
-        g.write_source(src, loud_noise(r, n_ticks, spt), n_ticks)
+        x = loud_noise(r, n_ticks, spt)
+        if n_ticks > 2048:   # quiet but for ticks [1000, 1200): at 8000 ticks/s Clip goes None -> Active -> Recent inside the run
+            x[:1000 * 2 * spt] *= np.float32(0.01)
+            x[1200 * 2 * spt:] *= np.float32(0.01)
+        g.write_source(src, x, n_ticks)
         g.run_ticks(r * n_ticks, n_ticks)
-        check_run(g, od, model, g.read_output(amp, 0, n_ticks, True), r * n_ticks * spt, spt, n_ticks, f"run {r}")
+        got, ticks = check_run(g, od, model, g.read_output(amp, 0, n_ticks, True), r * n_ticks * spt, spt, n_ticks, f"run {r}")
+        if n_ticks > 2048 and r == 0:
+            assert set(ticks["clip_status"].tolist()) == {0, 1, 2}
     # a window of the last run is the matching slice of the whole
     whole, wt = g.read_audio_out(od, 0, n_ticks)
     part, pt = g.read_audio_out(od, 5, 9)

@@ -3,18 +3,29 @@ cycles (back-edges read Disconnected, engine.rs:479-482), modules nobody listens
 device (fused and unfused, several ticks per submission and one) and on the CPU oracle's graph runner, every port
 compared bit for bit.
 
-Only modules whose device arithmetic is bit-exact are drawn (EqThree in exact-order mode; oscillators Saw / Triangle /
-On / Off -- Sine / Square / FmSine differ from the host libm by <= 1 ULP and would make everything downstream inexact;
-they have their own tests).  What is under test is the scheduler: run order, levels, launch groups, the fusion planner's
-conditions, slab layout, state carry.
+`random_graph(seed)` draws the round-1 module set (EqThree in exact-order mode; oscillators Saw / Triangle / On / Off); the
+64 seeds of the first test and tests/test_gpu_tick_shapes.py keep those graphs.  `random_graph(seed, full=True)` draws every
+kind the oracle runs: all six waveforms, FmSine, FIR, Resample (sample-rate domains that feed Mixers, Amplifiers, Splitters,
+Panners, with fan-out and cycles of their own), Mixers up to 24 inputs wide and OutputDevice sinks -- all bit-exact against the
+oracle (README).  The full tests add scheduled updates of every kind with params, updates and lag notes
+between runs, level meters on a random third of the ports (fed the ORACLE's samples of the port) and the OutputDevice hand-off
+(tests/output_device_model.py fed the oracle's input samples), plus the MX_FLAG_FP_CONTRACT order against the oracle's contract
+mode.  What is under test is the scheduler: run order, levels, sample-rate domains, launch groups, the fusion planner's
+conditions, slab layout, spans cut by scheduled updates, state carry.
 """
+import struct
+from fractions import Fraction
+
 import numpy as np
 import pytest
 
 import oracle
 import synth
+from meter_model import METER_TICK, MeterModel, records_equal
 from mixlab_amd import abi
 from mixlab_amd.workspace import Workspace
+from output_device_model import OutputDeviceModel
+from tick_shapes import by_id
 
 pytestmark = pytest.mark.gpu
 
@@ -26,7 +37,11 @@ def bits(a):
     return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
-def random_graph(seed, sr=SR, tps=60):
+def random_graph(seed, sr=SR, tps=60, full=False):
+    """-> (workspace, [(source node, MONO | STEREO)]).  full=False: the round-1 module set, the same graphs as ever; full=True: every
+    kind the oracle runs (_full_graph)"""
+    if full:
+        return _full_graph(seed, sr, tps)
     rng = np.random.default_rng(seed)
     ws = Workspace(sr, tps)
     outs = {MONO: [], STEREO: []}      # (node, port) by line type
@@ -78,13 +93,237 @@ def random_graph(seed, sr=SR, tps=60):
     return ws, sources
 
 
+RATIOS = [(160, 147), (2, 1), (1, 3), (4, 5), (3, 7), (8, 7), (1, 1), (147, 160)]   # tests/test_gpu_fir_resample.py's
+RATE_BOUND = {abi.KIND_EQ_THREE, abi.KIND_ENVELOPE, abi.KIND_OSCILLATOR, abi.KIND_FM_SINE, abi.KIND_PLOTTER}   # base domain only (Graph::Graph)
+OD_CHANNELS = [0, 1, 2, 6, 8]
+
+
+def n_inputs(kind, params):
+    if kind == abi.KIND_MIXER:
+        return len(params)
+    return {abi.KIND_AMPLIFIER: 2, abi.KIND_ENVELOPE: 1, abi.KIND_EQ_THREE: 1, abi.KIND_FM_SINE: 1, abi.KIND_PLOTTER: 1, abi.KIND_STEREO_PANNER: 2,
+            abi.KIND_STEREO_SPLITTER: 1, abi.KIND_FIR: 1, abi.KIND_RESAMPLE: 1, abi.KIND_OUTPUT_DEVICE: 1}.get(kind, 0)
+
+
+def resample_ratio(params):
+    up, down, _tpp, _pad = struct.unpack_from("<IIII", params)
+    return Fraction(up, down)
+
+
+def engine_domains(ws):
+    """Graph::Graph's run order and sample-rate domains (mx_engine.cpp): DFS through inputs from every module that feeds nothing, in
+    ascending id; an input whose producer runs later (or never) is a back-edge and carries no domain.  -> (order, {node: Fraction},
+    refusal) where refusal is None or (node, why) for the first module the engine would refuse"""
+    conn = ws._conn
+    feeds = {s for (s, _sp) in conn.values()}
+    order, seen = [], set()
+    for root in range(len(ws.nodes)):
+        if root in feeds or root in seen:
+            continue
+        seen.add(root)
+        stack = [[root, 0]]
+        while stack:
+            f = stack[-1]
+            kind, params = ws.nodes[f[0]]
+            if f[1] < n_inputs(kind, params):
+                src = conn.get((f[0], f[1]))
+                f[1] += 1
+                if src is not None and src[0] not in seen:
+                    seen.add(src[0]); stack.append([src[0], 0])
+            else:
+                order.append(f[0]); stack.pop()
+    pos = {n: i for i, n in enumerate(order)}
+    dom = {}
+    for n in order:
+        kind, params = ws.nodes[n]
+        ins = [conn.get((n, k)) for k in range(n_inputs(kind, params))]
+        doms = {dom[s] for s in (x[0] for x in ins if x is not None) if pos.get(s, len(order)) < pos[n]}
+        if len(doms) > 1:
+            return order, dom, (n, "mixed")
+        d = doms.pop() if doms else Fraction(1)
+        if kind == abi.KIND_RESAMPLE:
+            d *= resample_ratio(params)
+        dom[n] = d
+        if (ws.spt * d).denominator != 1:
+            return order, dom, (n, "ratio")
+        if kind in RATE_BOUND and d != 1:
+            return order, dom, (n, "rate")
+    return order, dom, None
+
+
+def _full_graph(seed, sr, tps):
+    """Every audio kind the oracle runs.  Each module is given a sample-rate domain when it is created -- the base one or the output
+    domain of an existing Resample -- and its inputs are drawn from ports of that domain (earlier or later modules: cycles happen
+    inside resampled domains too); a few inputs are drawn from any domain on purpose.  Where a cycle makes such an edge a forward
+    one, or leaves a module without the inputs that gave it its domain, the engine would refuse the graph: those edges are dropped
+    (engine_domains) until it builds.  A drawn edge from a resampled port into a base-domain module that the run order makes a
+    back-edge stays: it reads Disconnected."""
+    rng = np.random.default_rng(seed)
+    ws = Workspace(sr, tps)
+    spt = ws.spt
+    base = Fraction(1)
+    domains = [base]
+    outs = {}                          # (line type, domain) -> [(node, port)]
+    ins = []                           # (node, port, type, domain)
+    intended = {}
+    sources = []
+
+    def out(n, p, ty, d):
+        outs.setdefault((ty, d), []).append((n, p))
+
+    def pick_domain(kind=None):
+        if kind in RATE_BOUND or len(domains) == 1 or rng.random() < 0.45:
+            return base
+        return domains[int(rng.integers(1, len(domains)))]
+
+    for _ in range(int(rng.integers(10, 36))):
+        k = rng.choice(["src_m", "src_s", "osc", "trig", "eq", "env", "amp", "pan", "split", "mix", "plot", "fm", "fir", "rs", "rs",
+                        "amp", "pan", "split", "mix", "fir"])
+        if k == "src_m":
+            n = ws.source_mono(); sources.append((n, MONO)); out(n, 0, MONO, base)
+        elif k == "src_s":
+            n = ws.source_stereo(); sources.append((n, STEREO)); out(n, 0, STEREO, base)
+        elif k == "osc":
+            n = ws.oscillator(float(rng.uniform(50, 2000)), int(rng.integers(0, 6)))
+            out(n, 0, MONO, base); out(n, 1, STEREO, base)
+        elif k == "trig":
+            n = ws.trigger(bool(rng.integers(0, 2))); out(n, 0, MONO, base)
+        elif k == "eq":
+            n = ws.eq_three(*[float(v) for v in rng.uniform(-24, 6, 3)]); ins.append((n, 0, MONO, base)); out(n, 0, MONO, base)
+        elif k == "env":
+            n = ws.envelope(float(rng.uniform(1, 50)), float(rng.uniform(5, 600)), float(rng.uniform(0.1, 1.0)), float(rng.uniform(5, 300)))
+            ins.append((n, 0, MONO, base)); out(n, 0, MONO, base)
+        elif k == "fm":
+            lo = float(rng.uniform(50, 1000))
+            n = ws.fm_sine(lo, lo + float(rng.uniform(0, 3000))); ins.append((n, 0, MONO, base)); out(n, 0, STEREO, base)
+        elif k == "plot":
+            n = ws.plotter(); ins.append((n, 0, STEREO, base))
+        elif k == "rs":
+            d = pick_domain()
+            cand = [r for r in RATIOS if (spt * d * Fraction(*r)).denominator == 1 and (spt * Fraction(*r)).denominator == 1]
+            up, down = cand[int(rng.integers(0, len(cand)))]
+            n = ws.resample(up, down, rng.uniform(-0.5, 0.5, (up, int(rng.integers(1, 9)))))
+            feed = outs.get((STEREO, d), [])
+            if feed:                   # fed at once from its own domain, so its output domain is the one drawn
+                ws.connect(*feed[int(rng.integers(0, len(feed)))], n, 0)
+            else:
+                ins.append((n, 0, STEREO, d))
+            nd = d * Fraction(up, down)
+            if nd not in domains:
+                domains.append(nd)
+            out(n, 0, STEREO, nd)
+        else:
+            d = pick_domain()
+            if k == "amp":
+                n = ws.amplifier(float(rng.uniform(0.1, 2.0)), float(rng.uniform(0.0, 1.0)))
+                ins += [(n, 0, STEREO, d), (n, 1, MONO, d)]; out(n, 0, STEREO, d)
+            elif k == "pan":
+                n = ws.stereo_panner(); ins += [(n, 0, MONO, d), (n, 1, MONO, d)]; out(n, 0, STEREO, d)
+            elif k == "split":
+                n = ws.stereo_splitter(); ins.append((n, 0, STEREO, d)); out(n, 0, MONO, d); out(n, 1, MONO, d)
+            elif k == "fir":
+                n = ws.fir(rng.uniform(-0.5, 0.5, int(rng.integers(1, 71)))); ins.append((n, 0, STEREO, d)); out(n, 0, STEREO, d)
+            else:
+                w = int(rng.integers(0, 25))
+                n = ws.mixer([(float(rng.uniform(-24, 6)), float(rng.uniform(0, 1)), bool(rng.integers(0, 2))) for _ in range(w)])
+                ins += [(n, c, STEREO, d) for c in range(w)]
+                out(n, 0, STEREO, d); out(n, 1, STEREO, d)
+        intended[n] = d if k not in ("src_m", "src_s", "osc", "trig", "eq", "env", "fm", "plot") else base
+    # strips like the benchmark's; the first one is left whole and feeds a Mixer nobody reads, so it runs and the fused graph stores its
+    # Amplifier's output one float per frame (a dup-stored port); the others deviate at random
+    for i in range(int(rng.integers(1, 4))):
+        s = ws.source_mono(); sources.append((s, MONO)); e = ws.eq_three(*[float(v) for v in rng.uniform(-24, 6, 3)])
+        p = ws.stereo_panner(); a = ws.amplifier(1.0, 0.5); t = ws.trigger(bool(rng.integers(0, 2))); v = ws.envelope()
+        ws.connect(s, 0, e, 0); ws.connect(e, 0, p, 0); ws.connect(e, 0, p, 1); ws.connect(p, 0, a, 0); ws.connect(t, 0, v, 0); ws.connect(v, 0, a, 1)
+        if i == 0:
+            bus = ws.mixer([(float(rng.uniform(-12, 0)), 0.8, False)])
+            ws.connect(a, 0, bus, 0)
+            continue
+        out(e, 0, MONO, base); out(v, 0, MONO, base); out(t, 0, MONO, base); out(p, 0, STEREO, base); out(a, 0, STEREO, base)
+        ins += [(e, 0, MONO, base), (p, 0, MONO, base), (p, 1, MONO, base), (a, 0, STEREO, base), (a, 1, MONO, base), (v, 0, MONO, base)]
+    # 0-2 sinks; left / right None, inside the channel range or beyond it (the node filters those), sometimes the same channel
+    for _ in range(int(rng.integers(0, 3))):
+        od = ws.output_device(*random_od(rng))
+        d = pick_domain()
+        intended[od] = d
+        ins.append((od, 0, STEREO, d))
+    for (n, port, ty, d) in ins:
+        if rng.random() < 0.15:                      # any domain: kept where the run order makes it a back-edge
+            pool = [x for (t2, _d2), xs in outs.items() if t2 == ty for x in xs]
+        elif rng.random() < 0.85:
+            pool = outs.get((ty, d), [])
+        else:
+            continue
+        if pool:
+            ws.connect(*pool[int(rng.integers(0, len(pool)))], n, port)
+    while True:
+        _order, dom, bad = engine_domains(ws)
+        if bad is None:
+            return ws, sources
+        n, why = bad
+        kind, params = ws.nodes[n]
+        conn = [(k, ws._conn[(n, k)]) for k in range(n_inputs(kind, params)) if (n, k) in ws._conn]
+        fwd = [(k, src) for (k, src) in conn if src[0] in dom]
+        if why == "mixed":   # keep the inputs of the module's own domain where there are any
+            keep = intended.get(n, base) if any(dom[src[0]] == intended.get(n, base) for _k, src in fwd) else dom[fwd[0][1][0]]
+            drop = next(k for (k, src) in fwd if dom[src[0]] != keep)
+        else:
+            drop = next(k for (k, src) in fwd if why == "ratio" or dom[src[0]] != base)
+        del ws._conn[(n, drop)]
+
+
+def random_od(rng):
+    """OutputDevice (channels, left, right)"""
+    c = OD_CHANNELS[int(rng.integers(0, len(OD_CHANNELS)))]
+
+    def ch():
+        u = rng.random()
+        return None if u < 0.25 else (int(rng.integers(0, c)) if u < 0.8 and c else int(rng.integers(c, c + 3)))
+
+    left = ch()
+    right = left if rng.random() < 0.2 else ch()
+    return c, left, right
+
+
+def random_params(rng, ws, node):
+    """new params of the same shape for `node` (None: the kind has none)"""
+    kind, p = ws.nodes[node]
+    u = lambda lo, hi: float(rng.uniform(lo, hi))
+    if kind == abi.KIND_TRIGGER:
+        return abi.TriggerParams(int(rng.integers(0, 2)))
+    if kind == abi.KIND_EQ_THREE:
+        return abi.EqThreeParams(u(-24, 6), u(-24, 6), u(-24, 6))
+    if kind == abi.KIND_ENVELOPE:
+        return abi.EnvelopeParams(u(1, 50), u(5, 600), u(0.1, 1.0), u(5, 300))
+    if kind == abi.KIND_AMPLIFIER:
+        return abi.AmplifierParams(u(0.1, 2.0), u(0.0, 1.0))
+    if kind == abi.KIND_OSCILLATOR:
+        return abi.OscillatorParams(u(50, 2000), int(rng.integers(0, 6)), 0)
+    if kind == abi.KIND_FM_SINE:
+        lo = u(50, 1000)
+        return abi.FmSineParams(lo, lo + u(0, 3000))
+    if kind == abi.KIND_MIXER and p:
+        return [abi.MixerChannelParams(u(-24, 6), u(0, 1), int(rng.integers(0, 2))) for _ in p]
+    if kind == abi.KIND_FIR:
+        n_taps = struct.unpack_from("<I", p)[0]
+        return struct.pack("<II", n_taps, 0) + rng.uniform(-0.5, 0.5, n_taps).tobytes()
+    if kind == abi.KIND_RESAMPLE:
+        up, down, tpp, _pad = struct.unpack_from("<IIII", p)
+        return struct.pack("<IIII", up, down, tpp, 0) + rng.uniform(-0.5, 0.5, (up, tpp)).tobytes()
+    if kind == abi.KIND_OUTPUT_DEVICE:
+        c, left, right = random_od(rng)
+        return abi.OutputDeviceParams(c, -1 if left is None else left, -1 if right is None else right, 0)
+    return None
+
+
 def port_types(ws):
     res = []
     for kind, params in ws.nodes:
         res.append({abi.KIND_AMPLIFIER: [STEREO], abi.KIND_ENVELOPE: [MONO], abi.KIND_EQ_THREE: [MONO], abi.KIND_MIXER: [STEREO, STEREO],
                     abi.KIND_OSCILLATOR: [MONO, STEREO], abi.KIND_PLOTTER: [], abi.KIND_STEREO_PANNER: [STEREO],
                     abi.KIND_STEREO_SPLITTER: [MONO, MONO], abi.KIND_TRIGGER: [MONO], abi.KIND_SOURCE_MONO: [MONO],
-                    abi.KIND_SOURCE_STEREO: [STEREO]}[kind])
+                    abi.KIND_SOURCE_STEREO: [STEREO], abi.KIND_FM_SINE: [STEREO], abi.KIND_FIR: [STEREO], abi.KIND_RESAMPLE: [STEREO],
+                    abi.KIND_OUTPUT_DEVICE: []}[kind])
     return res
 
 
@@ -158,3 +397,178 @@ def test_random_graph_fusion_and_batching_are_invisible_with_the_time_parallel_e
                 assert "MX_FLAG_NO_FUSE" in str(e)
                 continue
             assert np.array_equal(bits(a), bits(gu.read_output(n, p, T, ty == STEREO))), f"seed {seed}: node {n} port {p}: fused != unfused"
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# every kind the oracle runs, scheduled updates, meters and OutputDevice sinks (random_graph(full=True))
+# ---------------------------------------------------------------------------------------------------------------------------
+FULL_SEEDS = ([("44k1", s) for s in range(200, 224)] + [("48k", s) for s in range(300, 324)] + [("44k1_100", s) for s in range(400, 403)]
+              + [("16k_1000", s) for s in range(500, 502)] + [("8k_8000", s) for s in range(600, 602)])
+MAX_RUN = 6
+PARAM_KINDS = {abi.KIND_TRIGGER, abi.KIND_EQ_THREE, abi.KIND_ENVELOPE, abi.KIND_AMPLIFIER, abi.KIND_OSCILLATOR, abi.KIND_FM_SINE, abi.KIND_MIXER,
+               abi.KIND_FIR, abi.KIND_RESAMPLE, abi.KIND_OUTPUT_DEVICE}
+
+
+def od_args(p):
+    return p.channels, (None if p.left < 0 else p.left), (None if p.right < 0 else p.right)
+
+
+def run_full_graph(shape_id, seed, builds, flags):
+    """random_graph(full=True) through 3-4 runs of 1-6 ticks on every build in `builds` against the oracle (in whatever mode it is in):
+    every materialised port, meter records and OutputDevice hand-offs, bit for bit"""
+    shape = by_id(shape_id)
+    ws, sources = random_graph(seed, shape.sample_rate, shape.ticks_per_second, full=True)
+    spt = ws.spt
+    rng = np.random.default_rng(7000 + seed)
+    og = oracle.OracleGraph(ws)
+    order = og.run_order()
+    graphs = {name: ws.build(max_ticks_per_run=1 if name == "ticked" else MAX_RUN,
+                             flags=flags | {"fused": 0, "unfused": abi.FLAG_NO_FUSE, "ticked": 0, "overlap": abi.FLAG_OVERLAP_TAIL}[name])
+              for name in builds}
+    for g in graphs.values():
+        assert g.run_order() == order
+    types = port_types(ws)
+    frames = {(n, p): og.output(n, p).size // ty for n in order for p, ty in enumerate(types[n])}   # per tick, the port's own domain
+    pos = {n: i for i, n in enumerate(order)}
+    ods = [n for n in order if ws.nodes[n][0] == abi.KIND_OUTPUT_DEVICE]
+    od_in = {}                          # OutputDevice -> its input port, None where it reads Disconnected (also a back-edge)
+    for od in ods:
+        src = ws._conn.get((od, 0))
+        od_in[od] = src if src is not None and pos.get(src[0], len(order)) < pos[od] else None
+
+    def readable(g, n, p):
+        try:
+            g.read_output(n, p, 1, types[n][p] == STEREO, rate=(frames[(n, p)], spt))
+            return True
+        except abi.MxError as e:
+            assert g is not graphs.get("unfused") and "MX_FLAG_NO_FUSE" in str(e)   # folded away by the graph compiler
+            return False
+
+    ports = {name: [pt for pt in frames if readable(g, *pt)] for name, g in graphs.items()}
+    common = [pt for pt in frames if all(pt in ps for ps in ports.values())]
+    # taps: a random third, every OutputDevice's input, a dup-stored fused strip port, a resampled port
+    dup = []
+    if "fused" in graphs:
+        for (n, p) in common:
+            if types[n][p] == STEREO:
+                try:
+                    graphs["fused"].output_device_ptr(n, p)
+                except abi.MxError:
+                    dup.append((n, p))
+        assert dup, f"seed {seed}: the first strip's Amplifier is not stored one float per frame"
+    resampled = [pt for pt in common if frames[pt] != spt or ws.nodes[pt[0]][0] == abi.KIND_RESAMPLE]   # (a 1/1 Resample is one too)
+    if any(ws.nodes[n][0] == abi.KIND_RESAMPLE for n in order):
+        assert resampled
+
+    def draw_taps():
+        t = {pt for pt in common if rng.random() < 1 / 3}
+        t |= {src for src in od_in.values() if src is not None}
+        for must in (dup, resampled):
+            if must:
+                t.add(must[int(rng.integers(0, len(must)))])
+        return sorted(t)
+
+    taps = draw_taps()
+    assert all(src in taps for src in od_in.values() if src is not None)
+    tap_params = {}
+    models = {}
+
+    def set_taps(new):
+        for pt in new:
+            if pt not in models:   # a new tap starts from 0; a surviving one keeps its hold
+                tap_params[pt] = abi.MeterParams(int(rng.integers(0, 9)), float(rng.uniform(0.5, 1.0)))
+                models[pt] = MeterModel(types[pt[0]][pt[1]], tap_params[pt].hold_ticks, tap_params[pt].release)
+        for pt in list(models):
+            if pt not in new:
+                del models[pt]
+        for g in graphs.values():
+            g.set_meters(new, [tap_params[pt] for pt in new])
+
+    set_taps(taps)
+    od_models = {od: OutputDeviceModel(shape.sample_rate, *od_args(ws.nodes[od][1])) for od in ods}
+    updatable = [n for n in order if ws.nodes[n][0] in PARAM_KINDS and ws.nodes[n][1]]   # (a Mixer of no channels has none)
+    tick = 0
+    n_runs = int(rng.integers(3, 5))
+    for run in range(n_runs):
+        L = int(rng.integers(1, MAX_RUN + 1))
+        if run == 2:
+            taps = sorted({pt for pt in taps if rng.random() < 0.5} | set(draw_taps()))
+            set_taps(taps)
+        if run and rng.random() < 0.5:   # updates between runs
+            for n in rng.choice(updatable, size=min(len(updatable), 3), replace=False):
+                p = random_params(rng, ws, int(n))
+                og.update_params(int(n), p)
+                for g in graphs.values():
+                    g.update_params(int(n), p)
+                if int(n) in od_models:
+                    od_models[int(n)].update(*od_args(p))
+        for od in ods:
+            if rng.random() < 0.3:       # the cpal callback ran short
+                od_models[od].note_lag()
+                for g in graphs.values():
+                    g.audio_out_lag(od)
+        events = {}                      # tick in run -> [(node, params)], one event per node and tick
+        for n in updatable:
+            if rng.random() < 0.3:
+                for k in sorted(set(rng.integers(0, L, size=int(rng.integers(1, 3))).tolist())):
+                    events.setdefault(k, []).append((n, random_params(rng, ws, n)))
+        data = {n: (synth.noise(9000 + 97 * seed + 13 * run + n, L * spt * ty) * np.float32(1.5)).astype(np.float32) for (n, ty) in sources}
+        # the oracle, tick by tick; the models take the oracle's samples
+        want, want_meters, want_od = {}, [], {od: ([], []) for od in ods}
+        for k in range(L):
+            for (n, p) in events.get(k, []):
+                og.update_params(n, p)
+                if n in od_models:
+                    od_models[n].update(*od_args(p))
+            for (n, ty) in sources:
+                og.set_source(n, data[n][k * spt * ty:(k + 1) * spt * ty])
+            og.run_tick(tick + k)
+            for pt in frames:
+                want.setdefault(pt, []).append(og.output(*pt))
+            want_meters.append([models[pt].tick(og.output(*pt)) for pt in taps])
+            for od in ods:
+                x = og.output(*od_in[od]) if od_in[od] is not None else np.zeros(2 * spt, np.float32)
+                pushed, rec = od_models[od].run_tick((tick + k) * spt, x)
+                want_od[od][0].append(pushed); want_od[od][1].append(rec)
+        want_meters = np.array(want_meters, dtype=METER_TICK)
+        for name, g in graphs.items():
+            step = 1 if name == "ticked" else L
+            got, got_meters, got_od = {}, [], {od: [[], []] for od in ods}
+            for k0 in range(0, L, step):
+                for (n, ty) in sources:
+                    g.write_source(n, data[n][k0 * spt * ty:(k0 + step) * spt * ty], step)
+                for k in range(k0, k0 + step):
+                    for (n, p) in events.get(k, []):
+                        g.schedule_params(n, k - k0, p)
+                g.run_ticks(tick + k0, step)
+                for pt in ports[name]:
+                    got.setdefault(pt, []).append(g.read_output(*pt, step, types[pt[0]][pt[1]] == STEREO, rate=(frames[pt], spt)))
+                got_meters.append(g.read_meters(0, step))
+                for od in ods:
+                    s, r = g.read_audio_out(od, 0, step)
+                    got_od[od][0].append(s); got_od[od][1] += [tuple(int(v) for v in q) for q in r.tolist()]
+            what = f"{shape_id} seed {seed} run {run} ({L} ticks from {tick}): {name} graph"
+            for pt, chunks in got.items():
+                a, b = np.concatenate(chunks), np.concatenate(want[pt])
+                assert np.array_equal(bits(a), bits(b)), f"{what}: node {pt[0]} (kind {ws.nodes[pt[0]][0]}) port {pt[1]} differs from the oracle"
+            ok = records_equal(np.concatenate(got_meters), want_meters)
+            if not ok.all():
+                k, i = (int(v[0]) for v in np.nonzero(~ok))
+                raise AssertionError(f"{what}: meter on {taps[i]} tick {k}: got {np.concatenate(got_meters)[k, i]}, want {want_meters[k, i]}")
+            for od in ods:
+                a, b = np.concatenate(got_od[od][0]), np.concatenate(want_od[od][0])
+                assert a.size == b.size and np.array_equal(bits(a), bits(b)), f"{what}: OutputDevice {od} hand-off differs"
+                assert got_od[od][1] == want_od[od][1], f"{what}: OutputDevice {od} records {got_od[od][1]} != {want_od[od][1]}"
+        tick += L
+
+
+@pytest.mark.parametrize("shape_id,seed", FULL_SEEDS, ids=[f"{s}-{n}" for s, n in FULL_SEEDS])
+def test_full_random_graph_matches_the_oracle(shape_id, seed):
+    run_full_graph(shape_id, seed, ("fused", "unfused", "ticked", "overlap"), abi.FLAG_EQ_EXACT)
+
+
+@pytest.mark.parametrize("shape_id,seed", FULL_SEEDS[:8] + FULL_SEEDS[24:32] + FULL_SEEDS[48:50],
+                         ids=[f"{s}-{n}" for s, n in FULL_SEEDS[:8] + FULL_SEEDS[24:32] + FULL_SEEDS[48:50]])
+def test_full_random_graph_contracted_matches_the_contract_oracle(shape_id, seed):
+    with oracle.fp_contract():
+        run_full_graph(shape_id, seed, ("fused", "unfused"), abi.FLAG_FP_CONTRACT)
