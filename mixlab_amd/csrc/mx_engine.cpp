@@ -326,9 +326,10 @@ Graph::Graph(const mx_node* nodes, size_t n_nodes, const mx_edge* edges, size_t 
     // AUTOMATIC (round 5) for graphs with at least 64 EqThree instances and submissions of at least 16 ticks, while the second buffers stay below MX_OVERLAP_AUTO_MAX_GB
     // (default 32) and a quarter of the free device memory: the bank's launch is held back until the next run's EqThree launch has been placed (flush_deferred_tail,
     // k_tail_gate) and then shares the SIMDs with it -- 1024 strips x 2048 ticks 5.42 -> 4.84 ms, x 256 ticks 0.915 -> 0.860, 128 strips x 2048 ticks 0.934 -> 0.875
-    // (tools/q_gate.sh).  Launched at once instead (round 4, MX_TAIL_GATE=0) the same mode LOST from 256 ticks up: the next run's k_env_ticks ran beside the bank (140 us
-    // instead of 9) with the EqThree launch waiting behind it.  MX_OVERLAP_AUTO=0 turns the automatism off; results are bit-identical either way.
+    // (profiles/r05/short_submission_regime.md).  Launched at once instead (round 4's form) the same mode LOST from 256 ticks up: the next run's k_env_ticks ran beside
+    // the bank (140 us instead of 9) with the EqThree launch waiting behind it.  MX_OVERLAP_AUTO=0 turns the automatism off; results are bit-identical either way.
     { const char* const sm = getenv("MX_SIN_MODE"); sin_mode_ = sm ? atoi(sm) : 0; }   // (A/B and tests: mx_k_stream.hip SIN_MODE)
+    { const char* const gt = getenv("MX_TAIL_GATE_TEST"); gate_test_ = gt && atoi(gt); }
     bool overlap_auto = false;
     {
         const char* const ae = getenv("MX_OVERLAP_AUTO");   // read per graph: tests build both kinds in one process
@@ -424,10 +425,10 @@ size_t Graph::od_offset(const Node& n, uint32_t tick) const {
     return off;
 }
 
-// The span's OutputDevice launches.  One that reads an output of the tail (MX_FLAG_OVERLAP_TAIL / automatic mode) goes behind it on the tail
-// stream -- held back with it when the tail is held -- and the events that join the tail cover it; any other runs on stream_ after the span's groups.
-void Graph::launch_outputs(uint64_t t0, uint32_t call_off, uint32_t n_calls, bool prof, std::vector<hipEvent_t>& ev) {
-    uint8_t where = 0;
+// The span's OutputDevice launches.  One that reads an output of the tail (MX_FLAG_OVERLAP_TAIL / automatic mode) is held back with it and goes
+// behind it on the tail stream, where the events that join the tail cover it; any other runs on stream_ after the span's groups.
+void Graph::launch_outputs(uint64_t t0, uint32_t call_off, uint32_t n_calls, ProfSpan* prof) {
+    bool here = false;
     for (uint32_t id : od_nodes_) {
         Node& n = nodes_[id];
         const PortRef src = n.in_src[0];
@@ -438,43 +439,38 @@ void Graph::launch_outputs(uint64_t t0, uint32_t call_off, uint32_t n_calls, boo
         const size_t base = od_offset(n, call_off);
         n.od_spans.push_back(Node::OdSpan{call_off, n_calls, C});
         OutRun r{};
-        r.in = in_ptr(n, 0, false); r.dup = src.node >= 0 && nodes_[src.node].out_dup[src.port] ? 1u : 0u;
+        r.in = in_ptr(n, 0, false, parity_); r.dup = src.node >= 0 && nodes_[src.node].out_dup[src.port] ? 1u : 0u;
         r.frames = n.od_frames; r.channels = C; r.left = n.od_left; r.right = n.od_right; r.n_ticks = n_calls;
         r.scratch = (float*)n.od_scratch.p; r.out = (float*)n.od_out.p + base; r.partial = (uint32_t*)n.od_part.p;
         r.state = (OutState*)n.od_state.p; r.rec = (OutTick*)n.od_rec.p + call_off;
         r.t0 = t0; r.spt = (uint32_t)spt_; r.rate = (uint32_t)sample_rate_; r.lag = call_off == 0 && n.od_lag_run ? 1u : 0u;
-        if (on_tail && tail_gate_) { deferred_.outs.push_back(r); where |= 2; }
-        else if (on_tail) { launch_output_device(r, tail_stream_); where |= 2; }
-        else { launch_output_device(r, stream_); where |= 1; }
+        if (on_tail) deferred_.outs.push_back(r);
+        else { launch_output_device(r, stream_); here = true; }
     }
-    if (where & 2) {
-        if (tail_gate_) deferred_.outs_prof_ev = prof ? ev[groups_.size() + 4] : nullptr;
-        else {
-            if (prof) hip_check(hipEventRecord(ev[groups_.size() + 4], tail_stream_), "hipEventRecord");
-            hip_check(hipEventRecord(ev_tail_done_[parity_], tail_stream_), "hipEventRecord");   // joins of the tail cover what reads it
-        }
-    }
-    if (prof && (where & 1)) hip_check(hipEventRecord(ev[groups_.size() + 3], stream_), "hipEventRecord");
-    if (prof) prof_runs_od_.push_back(where);
+    if (!prof) return;
+    if (here) { hip_check(hipEventRecord(prof->od_end, stream_), "hipEventRecord"); prof->od = true; }
+    prof->od_tail = !deferred_.outs.empty();
 }
 
 void Graph::flush_deferred_tail(bool gated) {
     if (!deferred_.pending) return;
     deferred_.pending = false;
+    ProfSpan* const prof = deferred_.prof;
+    deferred_.prof = nullptr;
     hip_check(hipStreamWaitEvent(tail_stream_, ev_head_done_, 0), "hipStreamWaitEvent");
     if (gated && gate_armed_) { launch_tail_gate((const uint32_t*)gate_flag_.p, gate_seq_, 300u, tail_stream_); ++n_gated_; } else ++n_at_once_;
-    if (deferred_.prof_begin) hip_check(hipEventRecord(deferred_.prof_begin, tail_stream_), "hipEventRecord");
+    if (prof) hip_check(hipEventRecord(prof->tail_begin, tail_stream_), "hipEventRecord");
     for (const TailLaunch& t : deferred_.items) {
         launch_mixer((const MixDesc*)t.desc, t.n, t.max_ch, t.frames, t.dup_mode, tail_stream_);
         if (t.prof_ev) hip_check(hipEventRecord(t.prof_ev, tail_stream_), "hipEventRecord");
     }
     deferred_.items.clear();
     for (const OutRun& r : deferred_.outs) launch_output_device(r, tail_stream_);   // OutputDevices that read the tail's outputs
-    if (!deferred_.outs.empty() && deferred_.outs_prof_ev) hip_check(hipEventRecord(deferred_.outs_prof_ev, tail_stream_), "hipEventRecord");
-    deferred_.outs.clear(); deferred_.outs_prof_ev = nullptr;
+    if (prof && !deferred_.outs.empty()) hip_check(hipEventRecord(prof->od_tail_end, tail_stream_), "hipEventRecord");
+    deferred_.outs.clear();
     for (const MeterRun& r : deferred_.meters) launch_meters(r, tail_stream_);   // meters on the tail's outputs
-    if (!deferred_.meters.empty() && deferred_.meters_prof_ev) hip_check(hipEventRecord(deferred_.meters_prof_ev, tail_stream_), "hipEventRecord");
-    deferred_.meters.clear(); deferred_.meters_prof_ev = nullptr;
+    if (prof && !deferred_.meters.empty()) hip_check(hipEventRecord(prof->meters_tail_end, tail_stream_), "hipEventRecord");
+    deferred_.meters.clear();
     if (tail_hook_) { auto hook = std::move(tail_hook_); tail_hook_ = nullptr; hook(tail_stream_); }   // (mx_exchange: pack + exchange of that run's buses, behind the bank)
     // recorded AFTER the hook: whoever waits for this tail (wait_tail) is then also ordered behind the hook's reads of the buses on the tail stream -- a later run's Mixer on
     // stream_ must not overwrite them under a pack that is still copying
@@ -522,8 +518,7 @@ Graph::~Graph() {
     if (stream_) (void)hipStreamSynchronize(stream_);
     if (tail_stream_) { (void)hipStreamDestroy(tail_stream_); (void)hipEventDestroy(ev_head_done_); for (auto& e : ev_tail_done_) (void)hipEventDestroy(e); }
     for (Node& n : nodes_) { n.vmixer.reset(); n.vout.clear(); n.vsrc = FrameRef(); n.vsrc_ring.clear(); n.vsrc_sched.clear(); }
-    for (auto& v : prof_runs_) for (auto& e : v) (void)hipEventDestroy(e);
-    for (auto& v : prof_pool_) for (auto& e : v) (void)hipEventDestroy(e);
+    prof_runs_.clear(); prof_pool_.clear();
     for (Stage& st : stage_) { if (st.done) (void)hipEventDestroy(st.done); if (st.host) (void)hipHostFree(st.host); }
     // the descriptor ring launch_video_batch keeps per stream goes with a stream this graph OWNS; a caller's stream may be shared with other
     // graphs / scalers that are launching on it right now (their ring must not be freed under them): its ring lives as long as the process
@@ -636,38 +631,39 @@ void Graph::layout_slab() {
     hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
 }
 
-float* Graph::out_ptr(const Node& n, uint32_t port) const {
+float* Graph::out_ptr(const Node& n, uint32_t port, uint32_t parity) const {
     // run_off_frames_: a run that is cut at scheduled parameter updates launches span by span; a span's buffers start that many
     // (base-rate) frames into the port
     const size_t fpf = n.out_dup[port] ? 1 : floats_per_frame(n.out_type[port]);
     const size_t off = fpf * (run_off_frames_ * n.dom_num / n.dom_den);
     if (n.bound && port == 0) return const_cast<float*>(n.bound) + off;
-    const bool alt = (building_alt_ || (parity_ && !building_main_)) && n.out_off2[port] != SIZE_MAX;
+    const bool alt = parity && n.out_off2[port] != SIZE_MAX;
     return (float*)slab_.p + (alt ? n.out_off2[port] : n.out_off[port]) + off;
 }
-const float* Graph::in_ptr(const Node& n, uint32_t port, bool null_if_disconnected) const {
+const float* Graph::in_ptr(const Node& n, uint32_t port, bool null_if_disconnected, uint32_t parity) const {
     const PortRef pr = n.in_src[port];
     if (pr.node < 0) return null_if_disconnected ? nullptr : (const float*)slab_.p + zero_off_;
-    return out_ptr(nodes_[pr.node], pr.port);
+    return out_ptr(nodes_[pr.node], pr.port, parity);
 }
 
 static double db_to_linear(double db) { return std::pow(10.0, db / 20.0); }   // protocol/src/lib.rs:469-471
 
-void Graph::upload_group_one(Group& g) {
+void Graph::upload_group_one(Group& g, uint32_t parity) {
     const size_t n = g.nodes.size();
     auto up = [&](DevBuf& b, const void* src, size_t bytes) {
         if (b.bytes < bytes || !b.p) b.alloc(bytes);
         if (bytes) hip_check(hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice), "hipMemcpy(desc)");
     };
+    DevBuf& desc = parity ? g.desc_alt : g.desc;
     switch (g.kind) {
     case MX_KIND_AMPLIFIER: {
         std::vector<AmpDesc> d(n);
         for (size_t i = 0; i < n; ++i) {
             const Node& nd = nodes_[g.nodes[i]];
             mx_amplifier_params p; std::memcpy(&p, nd.params.data(), sizeof p);
-            d[i] = AmpDesc{in_ptr(nd, 0, false), in_ptr(nd, 1, true), out_ptr(nd, 0), p.amplitude, p.mod_depth};
+            d[i] = AmpDesc{in_ptr(nd, 0, false, parity), in_ptr(nd, 1, true, parity), out_ptr(nd, 0, parity), p.amplitude, p.mod_depth};
         }
-        up(desc_buf(g), d.data(), n * sizeof(AmpDesc));
+        up(desc, d.data(), n * sizeof(AmpDesc));
         break;
     }
     case MX_KIND_ENVELOPE: {
@@ -680,11 +676,11 @@ void Graph::upload_group_one(Group& g) {
                 mx_trigger_params tp; std::memcpy(&tp, nodes_[nd.fuse_trigger].params.data(), sizeof tp);
                 gate_const = tp.gate_open ? 1.0f : 0.0f; use_const = 2; g.has_gates = true;
             }
-            d[i] = EnvDesc{use_const ? nullptr : in_ptr(nd, 0, false), out_ptr(nd, 0), gate_const, use_const,
+            d[i] = EnvDesc{use_const ? nullptr : in_ptr(nd, 0, false, parity), out_ptr(nd, 0, parity), gate_const, use_const,
                            EnvParams{p.attack_ms, 1.0 / p.attack_ms, 1.0 / p.decay_ms,
                                      p.sustain_amplitude, 1.0 - p.sustain_amplitude, 1.0 / p.release_ms}};
         }
-        up(desc_buf(g), d.data(), n * sizeof(EnvDesc));
+        up(desc, d.data(), n * sizeof(EnvDesc));
         if (!g.state.p) { g.state.alloc(n * sizeof(EnvState)); hip_check(hipMemset(g.state.p, 0, n * sizeof(EnvState)), "hipMemset"); }
         break;
     }
@@ -696,19 +692,19 @@ void Graph::upload_group_one(Group& g) {
             const Node& nd = nodes_[g.nodes[i]];
             mx_eq_three_params p; std::memcpy(&p, nd.params.data(), sizeof p);
             EqDesc e{};
-            e.in = in_ptr(nd, 0, false);
+            e.in = in_ptr(nd, 0, false, parity);
             e.gain_lo = db_to_linear(p.gain_lo_db); e.gain_mid = db_to_linear(p.gain_mid_db); e.gain_hi = db_to_linear(p.gain_hi_db);
             if (nd.fuse_amp >= 0) {          // EqThree -> StereoPanner(L = R) -> Amplifier in one kernel
                 const Node& amp = nodes_[nd.fuse_amp];
                 if (amp.out_dup[0]) e.flags |= MX_EQF_MONO_DUP;
                 mx_amplifier_params ap; std::memcpy(&ap, amp.params.data(), sizeof ap);
-                e.out = out_ptr(amp, 0); e.ctl = in_ptr(amp, 1, true);
+                e.out = out_ptr(amp, 0, parity); e.ctl = in_ptr(amp, 1, true, parity);
                 e.amp_one_minus = 1.0 - ap.mod_depth; e.amp_mod_depth = ap.mod_depth; e.amp_amplitude = ap.amplitude; e.epi = 2;
             } else if (nd.fuse_pan >= 0) {   // EqThree -> StereoPanner(L = R)
-                e.out = out_ptr(nodes_[nd.fuse_pan], 0); e.epi = 1;
+                e.out = out_ptr(nodes_[nd.fuse_pan], 0, parity); e.epi = 1;
                 if (nodes_[nd.fuse_pan].out_dup[0]) e.flags |= MX_EQF_MONO_DUP;
             } else {
-                e.out = out_ptr(nd, 0); e.epi = 0;
+                e.out = out_ptr(nd, 0, parity); e.epi = 0;
             }
             if (nd.fuse_env >= 0) {          // Envelope (constant gate) evaluated inline as the control
                 const Node& env = nodes_[nd.fuse_env];
@@ -731,7 +727,7 @@ void Graph::upload_group_one(Group& g) {
                         (unsigned)g.nodes[i], nd.sub_key - 1, em);
             }
         }
-        up(desc_buf(g), d.data(), n * sizeof(EqDesc));
+        up(desc, d.data(), n * sizeof(EqDesc));
         if (any_env) up(g.tick_desc, td.data(), n * sizeof(EnvTickDesc));
         if (!g.state.p) { g.state.alloc(n * sizeof(EqState)); hip_check(hipMemset(g.state.p, 0, n * sizeof(EqState)), "hipMemset"); }
         break;
@@ -743,16 +739,16 @@ void Graph::upload_group_one(Group& g) {
             mx_fm_sine_params p; std::memcpy(&p, nd.params.data(), sizeof p);
             const double freq_amp = (p.freq_hi - p.freq_lo) / 2.0;    // fm_sine.rs:42
             const double freq_mid = p.freq_lo + freq_amp;            // fm_sine.rs:43
-            d[i] = FmDesc{in_ptr(nd, 0, false), out_ptr(nd, 0), freq_mid, freq_amp};
+            d[i] = FmDesc{in_ptr(nd, 0, false, parity), out_ptr(nd, 0, parity), freq_mid, freq_amp};
         }
-        up(desc_buf(g), d.data(), n * sizeof(FmDesc));
+        up(desc, d.data(), n * sizeof(FmDesc));
         break;
     }
     case MX_KIND_MIXER: {
         size_t total = 0;
         for (uint32_t id : g.nodes) total += nodes_[id].in_type.size();
         std::vector<MixChan> ch(total ? total : 1);
-        DevBuf& xb = extra_buf(g);
+        DevBuf& xb = parity ? g.extra_alt : g.extra;
         if (xb.bytes < ch.size() * sizeof(MixChan) || !xb.p) xb.alloc(ch.size() * sizeof(MixChan));
         std::vector<MixDesc> d(n);
         size_t o = 0, n_dup = 0;
@@ -765,16 +761,16 @@ void Graph::upload_group_one(Group& g) {
                 const PortRef src = nd.in_src[c];
                 const uint32_t dup = (src.node >= 0 && nodes_[src.node].out_dup[src.port]) ? 1u : 0u;
                 n_dup += dup;
-                ch[o + c] = MixChan{in_ptr(nd, (uint32_t)c, false), cp.fader * db_to_linear(cp.gain_db), cp.cue ? 1u : 0u, dup};  // mixer.rs:59
+                ch[o + c] = MixChan{in_ptr(nd, (uint32_t)c, false, parity), cp.fader * db_to_linear(cp.gain_db), cp.cue ? 1u : 0u, dup};  // mixer.rs:59
             }
-            d[i] = MixDesc{(const MixChan*)xb.p + o, (uint32_t)nch, 0u, out_ptr(nd, 0), out_ptr(nd, 1)};
+            d[i] = MixDesc{(const MixChan*)xb.p + o, (uint32_t)nch, 0u, out_ptr(nd, 0, parity), out_ptr(nd, 1, parity)};
             o += nch;
         }
         g.dup_mode = n_dup == 0 ? 0 : (n_dup == total ? 1 : 2);
         g.max_taps = 0;
         for (uint32_t id : g.nodes) g.max_taps = std::max<uint32_t>(g.max_taps, (uint32_t)nodes_[id].in_type.size());   // Mixer: most channels
         hip_check(hipMemcpy(xb.p, ch.data(), ch.size() * sizeof(MixChan), hipMemcpyHostToDevice), "hipMemcpy(mixchan)");
-        up(desc_buf(g), d.data(), n * sizeof(MixDesc));
+        up(desc, d.data(), n * sizeof(MixDesc));
         break;
     }
     case MX_KIND_OSCILLATOR: {
@@ -782,21 +778,21 @@ void Graph::upload_group_one(Group& g) {
         for (size_t i = 0; i < n; ++i) {
             const Node& nd = nodes_[g.nodes[i]];
             mx_oscillator_params p; std::memcpy(&p, nd.params.data(), sizeof p);
-            d[i] = OscDesc{out_ptr(nd, 0), out_ptr(nd, 1), p.freq, p.waveform, 0u};
+            d[i] = OscDesc{out_ptr(nd, 0, parity), out_ptr(nd, 1, parity), p.freq, p.waveform, 0u};
         }
-        up(desc_buf(g), d.data(), n * sizeof(OscDesc));
+        up(desc, d.data(), n * sizeof(OscDesc));
         break;
     }
     case MX_KIND_STEREO_PANNER: {
         std::vector<PanDesc> d(n);
-        for (size_t i = 0; i < n; ++i) { const Node& nd = nodes_[g.nodes[i]]; d[i] = PanDesc{in_ptr(nd, 0, false), in_ptr(nd, 1, false), out_ptr(nd, 0)}; }
-        up(desc_buf(g), d.data(), n * sizeof(PanDesc));
+        for (size_t i = 0; i < n; ++i) { const Node& nd = nodes_[g.nodes[i]]; d[i] = PanDesc{in_ptr(nd, 0, false, parity), in_ptr(nd, 1, false, parity), out_ptr(nd, 0, parity)}; }
+        up(desc, d.data(), n * sizeof(PanDesc));
         break;
     }
     case MX_KIND_STEREO_SPLITTER: {
         std::vector<SplitDesc> d(n);
-        for (size_t i = 0; i < n; ++i) { const Node& nd = nodes_[g.nodes[i]]; d[i] = SplitDesc{in_ptr(nd, 0, false), out_ptr(nd, 0), out_ptr(nd, 1)}; }
-        up(desc_buf(g), d.data(), n * sizeof(SplitDesc));
+        for (size_t i = 0; i < n; ++i) { const Node& nd = nodes_[g.nodes[i]]; d[i] = SplitDesc{in_ptr(nd, 0, false, parity), out_ptr(nd, 0, parity), out_ptr(nd, 1, parity)}; }
+        up(desc, d.data(), n * sizeof(SplitDesc));
         break;
     }
     case MX_KIND_TRIGGER: {
@@ -804,10 +800,10 @@ void Graph::upload_group_one(Group& g) {
         for (size_t i = 0; i < n; ++i) {
             const Node& nd = nodes_[g.nodes[i]];
             mx_trigger_params p; std::memcpy(&p, nd.params.data(), sizeof p);
-            d[i] = TrigDesc{out_ptr(nd, 0), p.gate_open ? 1.0f : 0.0f, 0u};   // trigger.rs:38-41
+            d[i] = TrigDesc{out_ptr(nd, 0, parity), p.gate_open ? 1.0f : 0.0f, 0u};   // trigger.rs:38-41
         }
         g.has_gates = true;
-        up(desc_buf(g), d.data(), n * sizeof(TrigDesc));
+        up(desc, d.data(), n * sizeof(TrigDesc));
         break;
     }
     case MX_KIND_FIR: {
@@ -822,11 +818,11 @@ void Graph::upload_group_one(Group& g) {
             const Node& nd = nodes_[g.nodes[i]];
             mx_fir_params h; std::memcpy(&h, nd.params.data(), sizeof h);
             std::memcpy(&taps[o], nd.params.data() + sizeof h, (size_t)h.n_taps * sizeof(double));
-            d[i] = FirDesc{in_ptr(nd, 0, false), out_ptr(nd, 0), (const double*)g.extra.p + o, (float2*)g.state.p + o, h.n_taps, 0u};
+            d[i] = FirDesc{in_ptr(nd, 0, false, parity), out_ptr(nd, 0, parity), (const double*)g.extra.p + o, (float2*)g.state.p + o, h.n_taps, 0u};
             o += h.n_taps;
         }
         hip_check(hipMemcpy(g.extra.p, taps.data(), tt * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(fir taps)");
-        up(desc_buf(g), d.data(), n * sizeof(FirDesc));
+        up(desc, d.data(), n * sizeof(FirDesc));
         break;
     }
     case MX_KIND_RESAMPLE: {
@@ -850,11 +846,11 @@ void Graph::upload_group_one(Group& g) {
             mx_resample_params h; std::memcpy(&h, nd.params.data(), sizeof h);
             const size_t cnt = (size_t)h.up * h.taps_per_phase;
             std::memcpy(&taps[o], nd.params.data() + sizeof h, cnt * sizeof(double));
-            d[i] = ResampleDesc{in_ptr(nd, 0, false), out_ptr(nd, 0), (const double*)g.extra.p + o, (float2*)g.state.p + oh, h.up, h.down, h.taps_per_phase, 0u};
+            d[i] = ResampleDesc{in_ptr(nd, 0, false, parity), out_ptr(nd, 0, parity), (const double*)g.extra.p + o, (float2*)g.state.p + oh, h.up, h.down, h.taps_per_phase, 0u};
             o += cnt; oh += h.taps_per_phase;
         }
         hip_check(hipMemcpy(g.extra.p, taps.data(), tt * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(resample taps)");
-        up(desc_buf(g), d.data(), n * sizeof(ResampleDesc));
+        up(desc, d.data(), n * sizeof(ResampleDesc));
         break;
     }
     default: break;  // PLOTTER (jobs built per run), SOURCE_* (no launch)
@@ -862,14 +858,8 @@ void Graph::upload_group_one(Group& g) {
 }
 
 void Graph::upload_group(Group& g) {
-    building_main_ = true;
-    upload_group_one(g);
-    building_main_ = false;
-    if (tail_gi_ >= 0) {   // the same descriptors with the double-buffered ports at their second buffer
-        building_alt_ = true;
-        upload_group_one(g);
-        building_alt_ = false;
-    }
+    upload_group_one(g, 0);
+    if (tail_gi_ >= 0) upload_group_one(g, 1);   // the same descriptors with the double-buffered ports at their second buffer
 }
 
 void Graph::build_descriptors() {
@@ -1019,7 +1009,7 @@ void Graph::write_source(uint32_t node, const float* host, size_t frames) {
     if (frames > cap_frames_) throw Error(MX_ERR_INVALID, "more ticks than max_ticks_per_run");
     if (frames && !host) throw Error(MX_ERR_INVALID, "host_samples is NULL");
     const size_t fl = floats_per_frame(n.out_type[0]) * frames;
-    hip_check(hipMemcpyAsync(out_ptr(n, 0), host, fl * sizeof(float), hipMemcpyHostToDevice, stream_), "hipMemcpyAsync(H2D source)");
+    hip_check(hipMemcpyAsync(out_ptr(n, 0, parity_), host, fl * sizeof(float), hipMemcpyHostToDevice, stream_), "hipMemcpyAsync(H2D source)");
     hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");  // host buffer is the caller's again on return
 }
 
@@ -1189,15 +1179,12 @@ void Graph::run(uint64_t t0, size_t fpc, uint32_t n_calls, float* ms_by_kind, fl
 // ticks [call_off, call_off + n_calls) of the current run: one launch per (level, kind, domain) group, then the video section
 void Graph::run_span(uint64_t t0, size_t fpc, uint32_t call_off, uint32_t n_calls, uint32_t run_calls) {
     const size_t frames = fpc * (size_t)n_calls;
-    const bool prof = prof_this_run_;
-    std::vector<hipEvent_t> ev;
-    if (prof) {
-        if (!prof_pool_.empty()) { ev = std::move(prof_pool_.back()); prof_pool_.pop_back(); }
-        else {
-            ev.resize(groups_.size() + 7);   // one slot per launch group + the per-tick video section + the begin of a tail launch that was held back (its own stream) + OutputDevices on either stream + meters on either stream
-            for (auto& e : ev) hip_check(hipEventCreate(&e), "hipEventCreate");
-        }
-        hip_check(hipEventRecord(ev[0], stream_), "hipEventRecord");
+    ProfSpan* prof = nullptr;   // the pool's last record, moved to prof_runs_ once the span is queued (deferred_.prof may point at it before)
+    if (prof_this_run_) {
+        if (prof_pool_.empty()) prof_pool_.push_back(std::make_unique<ProfSpan>(groups_.size()));
+        prof = prof_pool_.back().get();
+        prof->tail_held = prof->od = prof->od_tail = prof->meters = prof->meters_tail = false;
+        hip_check(hipEventRecord(prof->begin, stream_), "hipEventRecord");
     }
     std::vector<PlotJob> jobs;
     size_t gi = 0;
@@ -1236,7 +1223,7 @@ void Graph::run_span(uint64_t t0, size_t fpc, uint32_t call_off, uint32_t n_call
                         r.started = (uint32_t*)gate_flag_.p; r.started_seq = ++gate_seq_; gate_armed_ = true;
                     }
                     const bool opens_gate = launch_eq_three_spec((const EqDesc*)desc_of(g), (EqState*)g.state.p, n, r, plan, g.eq_mode, g.spec.p, (uint64_t*)eq_stats_.p, stream_, launch);
-                    if (!opens_gate && !(getenv("MX_TAIL_GATE_TEST") && atoi(getenv("MX_TAIL_GATE_TEST")))) gate_armed_ = false;   // the direct form never stores the flag: a gate would spin to its time limit before the bank starts (MX_TAIL_GATE_TEST: tests of that bounded spin)
+                    if (!opens_gate && !gate_test_) gate_armed_ = false;   // the direct form never stores the flag: a gate would spin to its time limit before the bank starts (MX_TAIL_GATE_TEST: tests of that bounded spin)
                     if (deferred_.pending) flush_deferred_tail(true);     // run k's Mixer bank: behind the gate this launch opens
                 } else {
                     void* scratch = nullptr;
@@ -1267,23 +1254,15 @@ void Graph::run_span(uint64_t t0, size_t fpc, uint32_t call_off, uint32_t n_call
         }
         case MX_KIND_FM_SINE: launch_fm_sine((const FmDesc*)desc_of(g), n, gf, t0, sample_rate_, stream_, sin_mode_); break;
         case MX_KIND_MIXER:
-            if (overlap_this_run_ && (int)gi >= tail_gi_) {   // beside the next run's earlier groups (HBM-bound beside VALU-bound)
-                const bool first = (int)gi == tail_gi_, last = gi + 1 == groups_.size();
-                if (first) {
+            if (overlap_this_run_ && (int)gi >= tail_gi_) {   // held back for the next run's EqThree launch, then beside its earlier groups (HBM-bound beside VALU-bound)
+                if ((int)gi == tail_gi_) {
                     if (deferred_.pending) flush_deferred_tail(false);   // (a run whose earlier groups had no speculative EqThree launch: nothing opened a gate)
                     hip_check(hipEventRecord(ev_head_done_, stream_), "hipEventRecord");
-                    if (tail_gate_ < 0) { const char* e = getenv("MX_TAIL_GATE"); tail_gate_ = e && atoi(e) == 0 ? 0 : 1; }   // A/B: 0 = launched at once (round 4's form)
-                    if (tail_gate_) { deferred_.items.clear(); deferred_.outs.clear(); deferred_.meters.clear(); deferred_.parity = parity_; deferred_.prof_begin = prof ? ev[groups_.size() + 2] : nullptr; tail_held_this_span_ = true; }
-                    else hip_check(hipStreamWaitEvent(tail_stream_, ev_head_done_, 0), "hipStreamWaitEvent");
+                    deferred_.items.clear(); deferred_.outs.clear(); deferred_.meters.clear(); deferred_.parity = parity_; deferred_.prof = prof;
+                    if (prof) prof->tail_held = true;
                 }
-                if (tail_gate_) {
-                    deferred_.items.push_back(TailLaunch{desc_of(g), n, g.max_taps, gf, g.dup_mode, prof ? ev[gi + 1] : nullptr});
-                    if (last) deferred_.pending = true;
-                } else {
-                    launch_mixer((const MixDesc*)desc_of(g), n, g.max_taps, gf, g.dup_mode, tail_stream_);
-                    if (prof) hip_check(hipEventRecord(ev[gi + 1], tail_stream_), "hipEventRecord");
-                    if (last) { hip_check(hipEventRecord(ev_tail_done_[parity_], tail_stream_), "hipEventRecord"); tail_pending_[parity_] = true; }
-                }
+                deferred_.items.push_back(TailLaunch{desc_of(g), n, g.max_taps, gf, g.dup_mode, prof ? prof->group_end[gi] : nullptr});
+                if (gi + 1 == groups_.size()) deferred_.pending = true;
                 ++gi;
                 continue;
             }
@@ -1305,7 +1284,7 @@ void Graph::run_span(uint64_t t0, size_t fpc, uint32_t call_off, uint32_t n_call
                 for (uint32_t c = 0; c < n_calls; ++c) {
                     if (!nd.plot_fired[call_off + c]) continue;
                     float* stage = (float*)plot_stage_.p + (size_t)nd.plot_slot[call_off + c] * 2 * fpc;
-                    jobs.push_back(PlotJob{in_ptr(nd, 0, false) + (size_t)c * 2 * fpc, stage, stage + fpc});
+                    jobs.push_back(PlotJob{in_ptr(nd, 0, false, parity_) + (size_t)c * 2 * fpc, stage, stage + fpc});
                 }
             }
             if (!jobs.empty()) {
@@ -1319,7 +1298,7 @@ void Graph::run_span(uint64_t t0, size_t fpc, uint32_t call_off, uint32_t n_call
         default: break;
         }
         // an event costs ~5 us of stream time: none for groups that launch nothing (sources, video kinds)
-        if (prof && group_launches(g)) hip_check(hipEventRecord(ev[gi + 1], stream_), "hipEventRecord");
+        if (prof && group_launches(g)) hip_check(hipEventRecord(prof->group_end[gi], stream_), "hipEventRecord");
         ++gi;
     }
     // video sub-graph: tick by tick (frames arrive per tick; nothing to batch over time)
@@ -1328,13 +1307,12 @@ void Graph::run_span(uint64_t t0, size_t fpc, uint32_t call_off, uint32_t n_call
         flush_scales(stream_);
         for (uint32_t id : video_order_) { Node& vn = nodes_[id]; if (!vn.rgba_pending.empty()) launch_pending_rgba(vn, vn.rgba_pending.size(), false); vn.rgba_calls = 0; }   // the last ticks' sinks
     }
-    if (prof && has_video_) hip_check(hipEventRecord(ev[groups_.size() + 1], stream_), "hipEventRecord");
+    if (prof && has_video_) hip_check(hipEventRecord(prof->video_end, stream_), "hipEventRecord");
     // after everything else of the span on stream_ (the video section included): its profile interval starts at the latest event recorded there
-    launch_outputs(t0, call_off, n_calls, prof, ev);
+    launch_outputs(t0, call_off, n_calls, prof);
     // the port buffers hold every tick of the run: the meters go once, after its last span
-    if (call_off + n_calls == run_calls) launch_meter_taps(run_calls, prof, ev);
-    if (prof) { prof_runs_.push_back(std::move(ev)); prof_runs_held_.push_back(tail_held_this_span_); }
-    tail_held_this_span_ = false;
+    if (call_off + n_calls == run_calls) launch_meter_taps(run_calls, prof);
+    if (prof) { prof_runs_.push_back(std::move(prof_pool_.back())); prof_pool_.pop_back(); }
 }
 
 static bool group_launches(const Group& g) {
@@ -1347,57 +1325,69 @@ static bool group_launches(const Group& g) {
 
 void Graph::profile_enable(bool on) { prof_on_ = on; }
 
+Graph::ProfSpan::ProfSpan(size_t n_groups) : group_end(n_groups) {
+    for (hipEvent_t* e : {&begin, &video_end, &tail_begin, &od_end, &od_tail_end, &meters_end, &meters_tail_end}) hip_check(hipEventCreate(e), "hipEventCreate");
+    for (hipEvent_t& e : group_end) hip_check(hipEventCreate(&e), "hipEventCreate");
+}
+
+Graph::ProfSpan::~ProfSpan() {
+    for (hipEvent_t e : {begin, video_end, tail_begin, od_end, od_tail_end, meters_end, meters_tail_end}) (void)hipEventDestroy(e);
+    for (hipEvent_t e : group_end) (void)hipEventDestroy(e);
+}
+
 uint32_t Graph::profile_collect(float* ms_by_kind, float* ms_total) {
     sync();
     if (ms_by_kind) for (int k = 0; k < MX_PROFILE_KINDS; ++k) ms_by_kind[k] = 0.f;
     if (ms_total) *ms_total = 0.f;
-    const uint32_t n = prof_runs_count_;   // run() calls; a run cut into spans recorded one event list per span
+    const uint32_t n = prof_runs_count_;   // run() calls; a run cut into spans recorded one record per span
     prof_runs_count_ = 0;
-    size_t run_i = 0;
-    for (auto& ev : prof_runs_) {
-        const bool held = run_i < prof_runs_held_.size() && prof_runs_held_[run_i]; ++run_i;
+    auto elapsed = [](hipEvent_t from, hipEvent_t to) { float ms = 0.f; hip_check(hipEventElapsedTime(&ms, from, to), "hipEventElapsedTime"); return ms; };
+    for (auto& rec : prof_runs_) {
+        const ProfSpan& p = *rec;
         perf_group_ms_.assign(groups_.size() + 1, 0.f);
-        size_t last = 0;   // index of the latest event that was recorded in this run
-        for (size_t i = 0; i + 1 < ev.size() && i <= groups_.size(); ++i) {
-            const bool recorded = i < groups_.size() ? group_launches(groups_[i]) : has_video_;
-            if (!recorded) continue;
-            float ms = 0.f;
-            if (held && i < groups_.size() && (int)i >= tail_gi_) {
+        hipEvent_t last = p.begin;   // the latest event recorded on stream_
+        for (size_t i = 0; i < groups_.size(); ++i) {
+            if (!group_launches(groups_[i])) continue;
+            float ms;
+            if (p.tail_held && (int)i >= tail_gi_) {
                 // a tail launch that was held back ran on its own stream, inside the NEXT run's window: its own begin (the tail's, or the tail group's before it) and end;
                 // the run's total ends where its stream's work did
-                hip_check(hipEventElapsedTime(&ms, (int)i == tail_gi_ ? ev[groups_.size() + 2] : ev[i], ev[i + 1]), "hipEventElapsedTime");
-                if (ms_by_kind) ms_by_kind[groups_[i].kind] += ms;
-                perf_group_ms_[i] = ms;
-                continue;
+                ms = elapsed((int)i == tail_gi_ ? p.tail_begin : p.group_end[i - 1], p.group_end[i]);
+            } else {
+                ms = elapsed(last, p.group_end[i]);
+                last = p.group_end[i];
             }
-            hip_check(hipEventElapsedTime(&ms, ev[last], ev[i + 1]), "hipEventElapsedTime");
-            if (ms_by_kind) ms_by_kind[i < groups_.size() ? groups_[i].kind : (uint32_t)MX_KIND_VIDEO_MIXER] += ms;
+            if (ms_by_kind) ms_by_kind[groups_[i].kind] += ms;
             perf_group_ms_[i] = ms;
-            last = i + 1;
         }
-        // OutputDevice launches: on stream_ after the span's groups and video section (ev[last] is the latest event before them there; their end
+        if (has_video_) {
+            const float ms = elapsed(last, p.video_end);
+            if (ms_by_kind) ms_by_kind[MX_KIND_VIDEO_MIXER] += ms;
+            perf_group_ms_[groups_.size()] = ms;
+            last = p.video_end;
+        }
+        // OutputDevice launches: on stream_ after the span's groups and video section (`last` is the latest event before them there; their end
         // is the run's), or behind the tail on its stream (from the last tail group's event)
-        const uint8_t od = run_i - 1 < prof_runs_od_.size() ? prof_runs_od_[run_i - 1] : 0;
         perf_od_ms_ = 0.f;
-        hipEvent_t end = ev[last];
-        if (od & 1) { float ms = 0.f; hip_check(hipEventElapsedTime(&ms, ev[last], ev[groups_.size() + 3]), "hipEventElapsedTime"); perf_od_ms_ += ms; end = ev[groups_.size() + 3]; }
-        if (od & 2) { float ms = 0.f; hip_check(hipEventElapsedTime(&ms, ev[groups_.size()], ev[groups_.size() + 4]), "hipEventElapsedTime"); perf_od_ms_ += ms; }
+        hipEvent_t end = last;
+        if (p.od) { perf_od_ms_ += elapsed(last, p.od_end); end = p.od_end; }
+        if (p.od_tail) perf_od_ms_ += elapsed(p.group_end.back(), p.od_tail_end);
         // meter launches: no kind of their own, counted in the total (and so in engine_us): on stream_ last of all, or on the tail stream
         // behind the tail (and its OutputDevices)
-        if (od & 4) end = ev[groups_.size() + 5];
-        { float ms = 0.f; hip_check(hipEventElapsedTime(&ms, ev.front(), end), "hipEventElapsedTime"); if (ms_total) *ms_total += ms; perf_total_ms_ = ms; }
-        if (od & 8) {
-            float ms = 0.f;
-            hip_check(hipEventElapsedTime(&ms, ev[(od & 2) ? groups_.size() + 4 : groups_.size()], ev[groups_.size() + 6]), "hipEventElapsedTime");
+        if (p.meters) end = p.meters_end;
+        perf_total_ms_ = elapsed(p.begin, end);
+        if (ms_total) *ms_total += perf_total_ms_;
+        if (p.meters_tail) {
+            const float ms = elapsed(p.od_tail ? p.od_tail_end : p.group_end.back(), p.meters_tail_end);
             if (ms_total) *ms_total += ms;
             perf_total_ms_ += ms;
         }
         perf_calls_ = last_calls_;
         if (perf_calls_ && perf_total_ms_ * 1000.0 / perf_calls_ > 1e6 / (double)tps_)   // timing.rs:37-40: the tick ran over its budget
             perf_last_lag_s_ = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-        prof_pool_.push_back(std::move(ev));
+        prof_pool_.push_back(std::move(rec));
     }
-    prof_runs_.clear(); prof_runs_held_.clear(); prof_runs_od_.clear();
+    prof_runs_.clear();
     return n;
 }
 
@@ -1548,13 +1538,13 @@ void Graph::read_output(uint32_t node, uint32_t port, float* host, size_t frames
     const size_t f0 = first_frame * n.dom_num / n.dom_den;
     frames = (first_frame + frames) * n.dom_num / n.dom_den - f0;
     if (n.out_dup[port]) {   // stored as one float per frame (L == R): expand for the caller
-        hip_check(hipMemcpyAsync(host, out_ptr(n, port) + f0, frames * sizeof(float), hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(D2H)");
+        hip_check(hipMemcpyAsync(host, out_ptr(n, port, parity_) + f0, frames * sizeof(float), hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(D2H)");
         sync();
         for (size_t i = frames; i-- > 0;) { const float v = host[i]; host[2 * i] = v; host[2 * i + 1] = v; }
         return;
     }
     const size_t fpf = floats_per_frame(n.out_type[port]);
-    hip_check(hipMemcpyAsync(host, out_ptr(n, port) + fpf * f0, fpf * frames * sizeof(float), hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(D2H)");
+    hip_check(hipMemcpyAsync(host, out_ptr(n, port, parity_) + fpf * f0, fpf * frames * sizeof(float), hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(D2H)");
     sync();
 }
 
@@ -1658,34 +1648,23 @@ void Graph::upload_meters(size_t fpc) {
 //    is queued there behind the run's producers and ahead of the next run's launches, which are the only ones that write that port again.  Its
 //    descriptor points at THIS run's buffer parity: the tail-read ports alternate per run, run k + 1 writes the other buffer, and run k + 2 --
 //    the next writer of this one -- comes after the meter on the same stream;
-//  - a tap on an output of the tail (the Mixer bank and the buses above it) goes on the tail stream behind the tail's last launch, held back
-//    with it (deferred_.meters) when the tail is held.  Those outputs are single buffers written only by the tail, whose next launch (run
-//    k + 1's) is queued behind this one on that same stream.  ev_tail_done_ is recorded after it, so every join -- read_meters, read_output,
-//    a run that reuses this parity -- covers the meter too.
+//  - a tap on an output of the tail (the Mixer bank and the buses above it) is held back with it (deferred_.meters) and goes on the tail
+//    stream behind the tail's last launch.  Those outputs are single buffers written only by the tail, whose next launch (run k + 1's) is
+//    queued behind this one on that same stream.  ev_tail_done_ is recorded after it, so every join -- read_meters, read_output, a run that
+//    reuses this parity -- covers the meter too.
 // The records and hold states of the two groups of taps are disjoint (slots); a later run's meters of a group follow on that group's stream.
-void Graph::launch_meter_taps(uint32_t n_calls, bool prof, std::vector<hipEvent_t>& ev) {
+void Graph::launch_meter_taps(uint32_t n_calls, ProfSpan* prof) {
     if (meters_.empty()) return;
     const uint32_t n = (uint32_t)meters_.size();
     const MeterDesc* d = (const MeterDesc*)meter_desc_.p + (size_t)(parity_ & 1u) * n;
     MeterRun all{d, n, n_calls, n, (MeterTick*)meter_rec_.p, (MeterHold*)meter_state_.p};
-    uint8_t where = 0;
-    if (!overlap_this_run_ || meter_n_head_ == n) {
-        launch_meters(all, stream_); where |= 4;
-    } else {
-        if (meter_n_head_) { MeterRun h = all; h.n = meter_n_head_; launch_meters(h, stream_); where |= 4; }
-        MeterRun t = all; t.desc = d + meter_n_head_; t.n = n - meter_n_head_;
-        if (tail_gate_) {
-            deferred_.meters.push_back(t);
-            deferred_.meters_prof_ev = prof ? ev[groups_.size() + 6] : nullptr;
-        } else {
-            launch_meters(t, tail_stream_);
-            if (prof) hip_check(hipEventRecord(ev[groups_.size() + 6], tail_stream_), "hipEventRecord");
-            hip_check(hipEventRecord(ev_tail_done_[parity_], tail_stream_), "hipEventRecord");   // joins of the tail cover the meters
-        }
-        where |= 8;
-    }
-    if (prof && (where & 4)) hip_check(hipEventRecord(ev[groups_.size() + 5], stream_), "hipEventRecord");
-    if (prof && !prof_runs_od_.empty()) prof_runs_od_.back() |= where;
+    const uint32_t n_head = overlap_this_run_ ? meter_n_head_ : n;
+    if (n_head < n) { MeterRun t = all; t.desc = d + n_head; t.n = n - n_head; deferred_.meters.push_back(t); }
+    all.n = n_head;
+    if (n_head) launch_meters(all, stream_);
+    if (!prof) return;
+    if (n_head) { hip_check(hipEventRecord(prof->meters_end, stream_), "hipEventRecord"); prof->meters = true; }
+    prof->meters_tail = !deferred_.meters.empty();
 }
 
 void Graph::read_meters(uint32_t first, uint32_t n, MeterTick* dst, size_t cap) {
@@ -1713,7 +1692,7 @@ void Graph::read_output_i16(uint32_t node, uint32_t port, int16_t* host, size_t 
     const size_t cnt = floats_per_frame(n.out_type[port]) * (frames * n.dom_num / n.dom_den);
     if (!cnt) return;
     if (conv_stage_.bytes < cnt * sizeof(int16_t)) { sync(); conv_stage_.alloc(cnt * sizeof(int16_t)); }
-    launch_f32_to_i16(out_ptr(n, port), (int16_t*)conv_stage_.p, cnt, n.out_dup[port] ? 1 : 0, stream_);
+    launch_f32_to_i16(out_ptr(n, port, parity_), (int16_t*)conv_stage_.p, cnt, n.out_dup[port] ? 1 : 0, stream_);
     hip_check(hipMemcpyAsync(host, conv_stage_.p, cnt * sizeof(int16_t), hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(D2H i16)");
     sync();
 }
@@ -1730,7 +1709,7 @@ void Graph::write_source_i16(uint32_t node, const int16_t* host, size_t frames) 
     if (!cnt) return;
     if (conv_stage_.bytes < cnt * sizeof(int16_t)) { sync(); conv_stage_.alloc(cnt * sizeof(int16_t)); }
     hip_check(hipMemcpyAsync(conv_stage_.p, host, cnt * sizeof(int16_t), hipMemcpyHostToDevice, stream_), "hipMemcpyAsync(H2D i16)");
-    launch_i16_to_f32((const int16_t*)conv_stage_.p, out_ptr(n, 0), cnt, stream_);
+    launch_i16_to_f32((const int16_t*)conv_stage_.p, out_ptr(n, 0, parity_), cnt, stream_);
     sync();   // host buffer is the caller's again on return
 }
 
@@ -1750,7 +1729,7 @@ float* Graph::output_ptr(uint32_t node, uint32_t port, size_t* fpf, bool stream_
     // MX_OVERLAP_AUTO) would not be ordered before it -- so the automatism ends here, for good.  (A host that asked for MX_FLAG_OVERLAP_TAIL knows about mx_graph_tail_stream.)
     // The same holds for a port the tail READS: it is double-buffered while the mode is on, and a raw pointer would see fresh data only every other run.
     if (stream_ordered_consumer && tail_gi_ >= 0 && tail_auto_ && (nodes_[node].group >= tail_gi_ || nodes_[node].out_off2[port] != SIZE_MAX)) end_auto_tail();
-    return out_ptr(nodes_[node], port);
+    return out_ptr(nodes_[node], port, parity_);
 }
 
 int Graph::read_plotter(uint32_t node, uint32_t call, float* left, float* right) {

@@ -207,7 +207,7 @@ private:
     void layout_slab();
     void build_descriptors();
     void upload_group(Group& g);          // descriptors of one group (both parities under MX_FLAG_OVERLAP_TAIL)
-    void upload_group_one(Group& g);
+    void upload_group_one(Group& g, uint32_t parity);   // ... of one parity: desc / extra, or desc_alt / extra_alt
     void run_video_tick(uint64_t t);
     void launch_pending_rgba(Node& n, size_t count, bool with_queued_scales);   // the `count` oldest pending chains of a sink
     // one launch sequence over ticks [call_off, call_off + n_calls) of the current run
@@ -216,14 +216,16 @@ private:
     void od_update(Node& n);                                             // OUTPUT_DEVICE: ModuleT::update with n.params (output_device.rs:152-169), on a quiescent stream
     void od_grow(Node& n, uint32_t channels);                            // ... buffers for a channel count above any seen before
     size_t od_offset(const Node& n, uint32_t tick) const;                // float offset of tick `tick` of the last run in the hand-off
-    void launch_outputs(uint64_t t0, uint32_t call_off, uint32_t n_calls, bool prof, std::vector<hipEvent_t>& ev);   // the span's OutputDevice launches
+    struct ProfSpan;
+    void launch_outputs(uint64_t t0, uint32_t call_off, uint32_t n_calls, ProfSpan* prof);   // the span's OutputDevice launches
     void upload_meters(size_t fpc);                                      // the taps' descriptors (both parities) and record room, on a quiescent stream
-    void launch_meter_taps(uint32_t n_calls, bool prof, std::vector<hipEvent_t>& ev);   // the run's meter launches (after its last span)
+    void launch_meter_taps(uint32_t n_calls, ProfSpan* prof);           // the run's meter launches (after its last span)
     void refresh_gates(Group& g, uint32_t run_calls);
     uint32_t trigger_of_row(const Group& g, uint32_t row) const;        // node id of the Trigger behind row `row` of a gated group, or ~0u
     void stage_upload(void* dst, const void* src, size_t bytes);         // H2D on the graph's stream through page-locked staging
-    const float* in_ptr(const Node& n, uint32_t port, bool null_if_disconnected) const;
-    float* out_ptr(const Node& n, uint32_t port) const;
+    // a port's buffer for buffer parity `parity` (the second buffer of a double-buffered port when it is 1), from the span's first tick
+    const float* in_ptr(const Node& n, uint32_t port, bool null_if_disconnected, uint32_t parity) const;
+    float* out_ptr(const Node& n, uint32_t port, uint32_t parity) const;
 
     std::vector<Node> nodes_;
     std::vector<uint32_t> order_;
@@ -244,8 +246,6 @@ private:
     bool tail_auto_ = false;              // the mode was chosen by the library (short submissions), not asked for with MX_FLAG_OVERLAP_TAIL
     int sin_mode_ = 0;                    // MX_SIN_MODE at build time (0: the reference's float through Ziv's strategy)
     uint32_t parity_ = 0;                 // which buffer of the double-buffered ports the current / last run uses
-    bool building_alt_ = false;           // upload_group is filling desc_alt / extra_alt
-    bool building_main_ = false;          // ... desc / extra (first buffers whatever the current parity is)
     hipStream_t tail_stream_ = nullptr;
     hipEvent_t ev_head_done_ = nullptr;   // recorded on stream_ when a run's earlier groups are queued
     hipEvent_t ev_tail_done_[2] = {nullptr, nullptr};   // recorded on tail_stream_ after the tail of a run (by parity)
@@ -254,21 +254,20 @@ private:
     // The tail launch of run k is HELD BACK until run k + 1 has queued its speculative EqThree launch, and goes behind a gate (k_tail_gate, one wave) that opens when that
     // launch's last workgroup has started: the next run's k_env_ticks runs alone (beside a Mixer bank it took 140 us instead of 9 and the EqThree launch behind it started
     // when the bank was nearly done: no overlap at all), the EqThree workgroups are placed on an empty chip, and the Mixer's waves fill what is left.  Every join
-    // (mx_graph_sync, read-backs, mx_graph_tail_stream, an exchange's submit, a cut run) releases a held launch at once.  MX_TAIL_GATE=0: launched at once as in round 4.
+    // (mx_graph_sync, read-backs, mx_graph_tail_stream, an exchange's submit, a cut run) releases a held launch at once.  The measurements: profiles/r05/short_submission_regime.md.
+    // The tail: every Mixer group from tail_gi_ on (a bank, or a bank and the buses above it), in order; outs: OutputDevices that read the tail's outputs, behind it;
+    // meters: the taps on the tail's outputs, behind those.  prof: the span's profile record (nullptr: not profiled), whose tail events the release records.
     struct TailLaunch { const void* desc = nullptr; uint32_t n = 0, max_ch = 0; size_t frames = 0; int dup_mode = 0; hipEvent_t prof_ev = nullptr; };
-    struct DeferredTail { bool pending = false; std::vector<TailLaunch> items; uint32_t parity = 0; hipEvent_t prof_begin = nullptr;
-                          std::vector<OutRun> outs; hipEvent_t outs_prof_ev = nullptr;
-                          std::vector<MeterRun> meters; hipEvent_t meters_prof_ev = nullptr; } deferred_;   // outs: OutputDevices that read the tail's outputs, behind it   // the tail: every Mixer group from tail_gi_ on (a bank, or a bank and the buses above it), in order
+    struct DeferredTail { bool pending = false; std::vector<TailLaunch> items; uint32_t parity = 0; ProfSpan* prof = nullptr;
+                          std::vector<OutRun> outs; std::vector<MeterRun> meters; } deferred_;
     std::function<void(hipStream_t)> tail_hook_;
     std::vector<hipEvent_t> head_waits_;
     uint64_t n_gated_ = 0, n_at_once_ = 0;
-    bool tail_held_this_span_ = false; std::vector<bool> prof_runs_held_;   // parallel to prof_runs_: that run's tail launch was held back (its events sit on the tail stream)
-    DevBuf gate_flag_; uint32_t gate_seq_ = 0; bool gate_armed_ = false; int tail_gate_ = -1;
+    DevBuf gate_flag_; uint32_t gate_seq_ = 0; bool gate_armed_ = false;
+    bool gate_test_ = false;              // MX_TAIL_GATE_TEST at build time: arm the gate even for a launch that never opens it (tests of its bounded spin)
     void flush_deferred_tail(bool gated);
     void end_auto_tail();                 // the library-chosen second-stream mode ends for good (a host took a raw pointer that mode would not keep fresh)
     void wait_tail(int parity_or_all);    // stream_ waits for the tail launches that have not been waited for (-1: both)
-    DevBuf& desc_buf(Group& g) { return building_alt_ ? g.desc_alt : g.desc; }
-    DevBuf& extra_buf(Group& g) { return (building_alt_ && g.kind == MX_KIND_MIXER) ? g.extra_alt : g.extra; }
     const void* desc_of(const Group& g) const { return (parity_ && g.desc_alt.p) ? g.desc_alt.p : g.desc.p; }
     size_t run_off_frames_ = 0;   // base-rate frames before the span being launched (a run cut at scheduled parameter updates)
     uint64_t gates_version_ = 0;  // bumped whenever a Trigger's params or schedule change
@@ -281,8 +280,6 @@ private:
     std::vector<uint32_t> plotter_nodes_;   // launched Plotter nodes
     std::vector<uint32_t> video_order_;     // the video nodes of order_, in run order
     std::vector<uint32_t> od_nodes_;        // OutputDevice nodes of order_ (never in a launch group: launched after the span's groups, behind their input's producer)
-    std::vector<uint8_t> prof_runs_od_;     // parallel to prof_runs_: 1 OutputDevice launches on stream_ (event groups + 3), 2 on the tail stream (event groups + 4),
-                                            // 4 meter launches on stream_ (groups + 5), 8 on the tail stream (groups + 6)
     // level meters: the taps in set order; launch order puts the taps read on stream_ first (meter_n_head_ of them), then the taps on outputs of
     // the tail (behind the Mixer bank on its stream while the second-stream mode is on).  meter_desc_: MeterDesc[2][n] in launch order, one row
     // per buffer parity; meter_rec_: MeterTick[max ticks][n]; meter_state_: MeterHold[n][2]
@@ -304,8 +301,19 @@ private:
     DevBuf conv_stage_;           // i16 staging for sink / ingest conversions
     size_t last_frames_per_call_ = 0;
     bool prof_on_ = false;
-    std::vector<std::vector<hipEvent_t>> prof_runs_;   // one event list (groups+1) per recorded run
-    std::vector<std::vector<hipEvent_t>> prof_pool_;
+    // the events of one profiled span (pooled: created once, reused), and which of them the span recorded
+    struct ProfSpan {
+        hipEvent_t begin = nullptr;                                     // stream_, before the span's launches
+        std::vector<hipEvent_t> group_end;                              // per launch group, on the stream it ran on
+        hipEvent_t video_end = nullptr, tail_begin = nullptr;           // the per-tick video section (stream_); a held-back tail's start (tail stream)
+        hipEvent_t od_end = nullptr, od_tail_end = nullptr;             // OutputDevice launches on stream_ / behind the tail
+        hipEvent_t meters_end = nullptr, meters_tail_end = nullptr;     // meter launches on stream_ / behind the tail (and its OutputDevices)
+        bool tail_held = false, od = false, od_tail = false, meters = false, meters_tail = false;
+        explicit ProfSpan(size_t n_groups);
+        ProfSpan(const ProfSpan&) = delete; ProfSpan& operator=(const ProfSpan&) = delete;
+        ~ProfSpan();
+    };
+    std::vector<std::unique_ptr<ProfSpan>> prof_runs_, prof_pool_;   // one record per profiled span since the last collect; the records to reuse
     uint32_t last_calls_ = 0;
     // PerformanceInfo bookkeeping (last profiled run)
     std::vector<float> perf_group_ms_;   // per group (+1: video section) of the last collected run

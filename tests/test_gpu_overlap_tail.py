@@ -183,6 +183,38 @@ def test_per_group_times_with_a_held_back_bank():
     assert by_kind["mixer"] < 50.0 and by_kind["eq_three"] < 50.0   # ms over four runs of 16 ticks: event pairs of one stream each, no garbage from unrecorded events
 
 
+def test_profiled_runs_with_an_output_device_and_meters_behind_a_held_back_bank():
+    """mx_graph_profile_* with every profile event a span can record: an OutputDevice on the Master and a meter tap on the Master go behind the held-back bank
+    on the tail stream, a meter tap on a strip's Amplifier (a port the tail reads) goes on the graph's stream.  Every interval is a pair of recorded events:
+    the times are positive and bounded, the node gets its time, and the accounts add up to the tick."""
+    n_strips, batch, n_runs = 64, 16, 4
+    ws, mix, srcs, trigs = strips(n_strips, SR)
+    od = ws.output_device(2, 0, 1)
+    ws.connect(mix, 0, od, 0)
+    g = ws.build(max_ticks_per_run=batch, flags=abi.FLAG_OVERLAP_TAIL)
+    assert g.tail_stream() is not None
+    amp = mix + 6                                            # strip 0's Amplifier
+    g.set_meters([(amp, 0), (mix, 0)])
+    for k, s in enumerate(srcs):
+        g.write_source(s, synth.noise(k, batch * SPT) * np.float32(8.0), batch)
+    g.run_ticks(0, batch)
+    g.sync()
+    g.profile_enable(True)
+    for r in range(1, n_runs + 1):
+        g.run_ticks(r * batch, batch)
+    by_kind, total, n = g.profile_collect()
+    assert n == n_runs and total > 0
+    assert by_kind["eq_three"] > 0 and by_kind["mixer"] > 0
+    assert by_kind["mixer"] < 50.0 and by_kind["eq_three"] < 50.0
+    gated, at_once = g.debug_tail_releases()
+    assert gated > 0, (gated, at_once)
+    info, us = g.performance_info(len(ws.nodes))
+    tick_us = total * 1000.0 / (n_runs * batch)             # the collected runs' mean tick
+    assert us[od] > 0
+    assert abs(sum(us) + info.engine_us - tick_us) <= len(ws.nodes) + 2
+    assert g.read_meters(0, batch).shape == (batch, 2)
+
+
 def test_a_gate_that_nobody_opens_times_out_and_the_results_stand():
     """The gate is an ordering hint, never a dependency: with the speculative EqThree launch in its direct form (MX_EQ_SPEC_DIRECT: a kernel that does not store the
     flag) and the gate armed all the same (MX_TAIL_GATE_TEST -- since round 6 the library arms a gate only for the tiled launch that opens it) every held-back bank
