@@ -10,6 +10,10 @@ whose per-rank chunk length equals the one-GPU job's (T x N ticks per step), the
 stdout carries ONE compact JSON line (benchlegs/line.py: the contract's keys, `roofline` of the dominant launch group -- its own bytes over its own
 hipEvent duration inside the timed region --, `cpu_baseline` = the CPU oracle on a bounded sample, one number per secondary leg); everything the
 legs measured is written to bench_full.json beside this file (stderr only says where).  The legs: benchlegs/*.py.
+
+A plain run does only what the headline figure needs: set up, warm up, time the K steps, dump (--dump-outputs), print the line (`roofline` included:
+its hipEvents sit inside the timed region either way).  --full adds everything else: the oracle replay of the timed submissions, the repeats of the
+clock, every secondary leg, the CPU baselines and, at N > 1, the profiled extra steps, the exchange section and the second tick policy.
 """
 from __future__ import annotations
 
@@ -59,8 +63,11 @@ def parse_args(argv=None):
     ap.add_argument("--video-band-as", default=None, metavar="R/W", help="single GPU: run the video leg as rank R of a W-rank row-band job")
     ap.add_argument("--video-shard", choices=["replicas", "bands"], default="replicas",
                     help="N > 1: independent 8-layer streams per rank (weak scaling), or ONE stream cut into row bands over the ranks (strong scaling)")
-    ap.add_argument("--full-out", default=str(ROOT / "bench_full.json"), help="where rank 0 writes everything the legs measured")
-    ap.add_argument("--headline-only", action="store_true", help="every secondary leg off (profiler passes)")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline figure: the oracle replay of the timed submissions, the repeats, every secondary leg, "
+                    "the CPU baselines, and at N > 1 the profiled extra steps, the exchange section and the second tick policy (off: set up, warm up, time, dump, print the line)")
+    ap.add_argument("--full-out", default=None, help="where rank 0 writes the whole record (default with --full: bench_full.json beside this file; a plain run writes it only "
+                    "when this is given)")
+    ap.add_argument("--headline-only", action="store_true", help="with --full: every secondary leg off (profiler passes)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the Master / Cue buses of the last timed step to DIR/*.npy (benchlegs/dump.py)")
     for flag, what in (("cpu-baseline", "the CPU oracle timed on this host"), ("buses-leg", "the group-bus topology leg"), ("one-stream-leg", "the MX_OVERLAP_AUTO=0 leg"),
                        ("held-leg", "the held-gates comparison leg"), ("other-policy-leg", "N > 1: the second tick policy"), ("scaling-probe", "the one-GPU model of 2 / 4 / 8 ranks"),
@@ -72,11 +79,15 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
-    if args.headline_only:
+    if args.headline_only or not args.full:
         for k in ("cpu_baseline", "buses_leg", "one_stream_leg", "held_leg", "other_policy_leg", "scaling_probe", "t_sweep", "realtime", "north_star", "contract_leg", "rate_leg",
                   "material_leg"):
             setattr(args, "no_" + k, True)
         args.fir_ticks = args.video_frames = args.repeats = 0
+    if not args.full:
+        args.no_headline_parity = True      # (the timed region is the same either way, its per-kernel hipEvents at N = 1 included)
+    elif args.full_out is None:
+        args.full_out = str(ROOT / "bench_full.json")
     return args
 
 
@@ -179,13 +190,13 @@ def main(argv=None):
             step(i)
         torch.cuda.synchronize()
         # per-kernel hipEvents cost a few us of stream time each: at N = 1 they sit inside the timed region (the roofline contract), at N > 1 -- where a
-        # step is shorter -- they are taken on extra steps after it
+        # step is shorter -- they are taken on extra steps after it (--full)
         g.profile_enable(not args.no_profile and not use_dist)
         dt = timed_region(args.warmup, args.steps)                      # THE timed region: exactly K steps
         nxt = args.warmup + args.steps
         n_run = nxt                                                    # submissions the graph has run so far (the oracle replay compares the LAST one)
         dumped = dump.collect(job, ex, nxt - 1) if args.dump_outputs and rank == 0 else None    # (before the N > 1 path's extra steps reuse its slots)
-        if use_dist and not args.no_profile:
+        if use_dist and args.full and not args.no_profile:
             g.profile_enable(True)
             for i in range(3):
                 step(nxt + i)
@@ -235,7 +246,7 @@ def main(argv=None):
             leg("fp_contract", lambda: variants.contract_leg(job, (lambda g2, n, c: parity_of(g2, n, c)) if parity is not None else None))
         if solo and overlap_active and not args.no_profile and not args.no_one_stream_leg:
             leg("one_stream", lambda: variants.one_stream_leg(job))
-        if ex is not None:
+        if ex is not None and args.full:
             full["exchange"] = headline.exchange_section(job, ex, nxt)
             if not args.no_other_policy_leg:
                 T2 = args.ticks_per_step * (1 if scaled else world)
@@ -308,13 +319,15 @@ def main(argv=None):
             out["cpu_baseline_all_cores"] = dict(cpu.audio_all_cores(Workspace, synth, abi, shard, args.strips, SR), build=note)
         if dumped is not None:
             out["dump_outputs"] = {"dir": str(args.dump_outputs), "shapes": dump.write(args.dump_outputs, dumped)}
-        full_text = json.dumps(out, allow_nan=False)
-        try:
-            pathlib.Path(args.full_out).write_text(full_text + "\n")
-            full_ref = os.path.relpath(args.full_out, ROOT) if str(args.full_out).startswith(str(ROOT)) else str(args.full_out)
-        except OSError as e:
-            full_ref = f"(not written: {e})"
-        print(f"[bench.py] everything the legs measured: {full_ref} ({len(full_text)} bytes)", file=sys.stderr)   # (a pointer, not the record: a reader that keeps a tail of the merged streams must still find the line)
+        full_ref = None
+        if args.full_out:
+            full_text = json.dumps(out, allow_nan=False)
+            try:
+                pathlib.Path(args.full_out).write_text(full_text + "\n")
+                full_ref = os.path.relpath(args.full_out, ROOT) if str(args.full_out).startswith(str(ROOT)) else str(args.full_out)
+            except OSError as e:
+                full_ref = f"(not written: {e})"
+            print(f"[bench.py] everything the legs measured: {full_ref} ({len(full_text)} bytes)", file=sys.stderr)   # (a pointer, not the record: a reader that keeps a tail of the merged streams must still find the line)
         text = bench_line.dumps_within_cap(bench_line.compact(out, full_ref))
         # RCCL prints a version banner through C stdio (flushed at exit when stdout is a pipe): drain it first so the JSON line is the LAST thing on stdout
         import ctypes

@@ -48,6 +48,18 @@ def test_a_nan_or_an_oversized_line_is_refused():
     assert len(text) <= line.LINE_HARD_CAP and all(k in got for k in line.CONTRACT + ("roofline", "cpu_baseline", "config")) and got["roofline"] == c["roofline"]
 
 
+def test_a_plain_run_leaves_everything_beside_the_headline_to_full():
+    """bench.py without --full: no oracle replay, no repeats, no secondary leg, no CPU baseline, no record file unless one is named; --full turns them back on."""
+    import bench
+    plain = bench.parse_args(["--gpus", "1", "--steps", "2", "--warmup", "1"])
+    assert not plain.full and plain.full_out is None and plain.no_headline_parity and plain.no_cpu_baseline and plain.no_held_leg and plain.no_realtime
+    assert plain.repeats == plain.video_frames == plain.fir_ticks == 0 and not plain.no_profile
+    full = bench.parse_args(["--gpus", "1", "--steps", "2", "--warmup", "1", "--full"])
+    assert full.full and full.full_out == str(ROOT / "bench_full.json")
+    assert not (full.no_headline_parity or full.no_cpu_baseline or full.no_held_leg or full.no_realtime or full.no_profile)
+    assert full.repeats == 4 and full.video_frames == 4096 and full.fir_ticks == 128
+
+
 def test_bench_py_stays_a_thin_assembler():
     n = len((ROOT / "bench.py").read_text().splitlines())
     assert n <= 400, f"bench.py has {n} lines: legs belong in benchlegs/"

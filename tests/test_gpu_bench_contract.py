@@ -28,7 +28,7 @@ def _run(cmd, tmp_path, timeout=900):
     return _strict(res.stdout), _strict(full.read_text())
 
 
-def _check_contract(line, strips, ticks, steps, warmup):
+def _check_contract(line, strips, ticks, steps, warmup, cpu_baseline=True):
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert key in line, key
     assert line["metric"] == "audio_ch_mixed_per_sec" and line["unit"] == "channel-ticks/s"
@@ -47,6 +47,9 @@ def _check_contract(line, strips, ticks, steps, warmup):
     per_sample = {"eq_three": 8, "mixer": 4}[rf["kernel"]]
     assert rf["algorithmic_bytes_per_launch"] == pytest.approx(per_sample * strips * ticks * 800, rel=0.01)   # (the mixer adds its two bus outputs)
     assert rf["avg_launch_ms"] <= line["ms_per_step"] * 1.02
+    if not cpu_baseline:
+        assert line["cpu_baseline"] is None                    # (measured with --full only)
+        return
     cb = line["cpu_baseline"]
     for key in ("value", "unit", "cores", "kind", "sample"):
         assert key in cb, key
@@ -54,7 +57,7 @@ def _check_contract(line, strips, ticks, steps, warmup):
 
 
 def test_bench_line_has_the_contract_keys_and_consistent_numbers(tmp_path):
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--strips", "64", "--ticks-per-step", "64",
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--full", "--steps", "3", "--warmup", "1", "--strips", "64", "--ticks-per-step", "64",
            "--no-realtime", "--no-t-sweep", "--no-north-star", "--no-held-leg", "--no-material-leg", "--no-scaling-probe", "--fir-ticks", "0", "--repeats", "0", "--video-frames", "0"]
     line, full = _run(cmd, tmp_path)
     _check_contract(line, 64, 64, 3, 1)
@@ -63,9 +66,9 @@ def test_bench_line_has_the_contract_keys_and_consistent_numbers(tmp_path):
 
 
 def test_default_command_line_with_every_leg_on_prints_one_compact_strict_line(tmp_path):
-    """The DEFAULT command's legs, all of them, at small sizes (the driver's command is `python bench.py --gpus 1 --steps K --warmup W`): one line, within the cap,
-    strict JSON, one number per leg; the full record beside it carries the legs themselves."""
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "1", "--strips", "128", "--ticks-per-step", "128", "--fir-ticks", "16",
+    """Every leg of --full, at small sizes: one line, within the cap, strict JSON, one number per leg; the full record beside it carries the legs
+    themselves."""
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--full", "--steps", "4", "--warmup", "1", "--strips", "128", "--ticks-per-step", "128", "--fir-ticks", "16",
            "--video-frames", "256", "--repeats", "1"]
     line, full = _run(cmd, tmp_path, timeout=1500)
     _check_contract(line, 128, 128, 4, 1)
@@ -81,12 +84,25 @@ def test_default_command_line_with_every_leg_on_prints_one_compact_strict_line(t
 def test_a_failing_secondary_leg_does_not_cost_the_run_its_line(tmp_path, monkeypatch):
     """A secondary leg that raises (injected here) is reported -- `leg_errors` in the line and the record, the traceback on stderr -- and the headline line still goes out."""
     monkeypatch.setenv("MX_BENCH_FAIL_LEG", "fir_resample")
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--strips", "64", "--ticks-per-step", "64", "--no-realtime", "--no-t-sweep",
-           "--no-north-star", "--no-held-leg", "--no-material-leg", "--no-scaling-probe", "--no-contract-leg", "--no-buses-leg", "--no-rate-leg", "--fir-ticks", "16", "--repeats", "0",
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--full", "--steps", "3", "--warmup", "1", "--strips", "64", "--ticks-per-step", "64", "--no-realtime",
+           "--no-t-sweep", "--no-north-star", "--no-held-leg", "--no-material-leg", "--no-scaling-probe", "--no-contract-leg", "--no-buses-leg", "--no-rate-leg", "--fir-ticks", "16", "--repeats", "0",
            "--video-frames", "0", "--no-cpu-baseline"]
     line, full = _run(cmd, tmp_path)
     assert line["leg_errors"] == ["fir_resample"] and "injected" in full["leg_errors"]["fir_resample"] and full["fir_resample"] is None
     assert line["value"] > 0 and line["roofline"]["frac"] > 0 and line["headline_parity"]["verdict"] == "bit-exact"
+
+
+def test_a_plain_run_prints_the_headline_and_runs_nothing_else(tmp_path):
+    """Without --full (the command every measurement of the headline runs): the contract's keys and the `roofline` of the timed region, whose hipEvents sit
+    inside it either way -- and none of what --full adds: no oracle replay, no repeats of the clock, no secondary leg, no CPU baseline."""
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--strips", "64", "--ticks-per-step", "64"]
+    line, full = _run(cmd, tmp_path)
+    _check_contract(line, 64, 64, 3, 1, cpu_baseline=False)
+    assert line["headline_parity"] is None and line["legs"] == {} and "leg_errors" not in line
+    assert len(full["repeats"]["ms_per_step"]) == 1 and full["value"] == line["value"]
+    for leg in ("video", "fir_resample", "fp_contract", "one_stream", "realtime", "t_sweep", "group_buses", "rate_44100", "material", "scaling_model",
+                "north_star_realtime", "held_gates", "cpu_baseline_all_cores", "exchange", "other_policy"):
+        assert leg not in full, leg
 
 
 SMALL = ["--steps", "3", "--warmup", "1", "--strips", "64", "--ticks-per-step", "64", "--no-realtime", "--no-t-sweep", "--no-north-star", "--no-held-leg",
@@ -98,7 +114,7 @@ def test_bench_exchange_path_checks_its_own_parity_single_rank_rccl(mode, tmp_pa
     """The N > 1 path of bench.py at N = 1 (--force-combine: a single-rank RCCL communicator): the record carries the parity evidence the first multi-GPU lease will
     produce with no new code -- the exchange's bus against a host sum, in rank order, of the partial buses gathered by a plain all_gather -- and the second tick
     policy beside the headline's."""
-    line, full = _run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--force-combine", "--exchange", mode, *SMALL], tmp_path)
+    line, full = _run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--full", "--force-combine", "--exchange", mode, *SMALL], tmp_path)
     ex = full["exchange"]
     assert ex["mode"] == mode and ex["rccl_ranks"] == 1
     assert ex["parity_check"]["verdict"] == "bit-exact" and ex["parity_check"]["samples_compared"] == 2 * 64 * 1600
@@ -119,7 +135,7 @@ def test_two_rank_rccl_job_is_bit_exact_when_two_gpus_are_visible(tmp_path):
         pytest.skip(f"needs 2 GPUs, found {n}")
     for k, mode in enumerate(("allgather", "slices")):
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(29571 + k),
-               str(ROOT / "bench.py"), "--gpus", "2", "--exchange", mode, *SMALL]
+               str(ROOT / "bench.py"), "--gpus", "2", "--full", "--exchange", mode, *SMALL]
         line, full = _run(cmd, tmp_path)
         assert line["n_gpus"] == 2 and full["exchange"]["rccl_ranks"] == 2 and full["exchange"]["mode"] == mode
         pc = full["exchange"]["parity_check"]
@@ -139,7 +155,7 @@ def _multi_rank_on_one_gpu(world, extra, tmp_path, small=None):
     full = tmp_path / "full.json"
     env = dict(os.environ, MX_BENCH_SHARE_GPU="1", MX_BENCH_DIST_BACKEND="gloo", MX_RCCL_LIB=str(so))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1", "--master-port", str(29581 + world + 16 * len(extra)),
-           str(ROOT / "bench.py"), "--gpus", str(world), *(small or SMALL), *extra, "--full-out", str(full)]
+           str(ROOT / "bench.py"), "--gpus", str(world), "--full", *(small or SMALL), *extra, "--full-out", str(full)]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=str(ROOT), env=env)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]

@@ -21,7 +21,7 @@ pmc() {   # pmc <tag> <counters...> -- <command...>: one counter pass, summary i
   echo $f
 }
 # 2. the same command under the kernel trace
-rm -rf /tmp/kt; timeout 1200 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -- python $REPO/bench.py --full-out /tmp/bench_full_kt.json > $OUT/bench_line_under_rocprof.json 2>/dev/null
+rm -rf /tmp/kt; timeout 1200 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/kt -- python $REPO/bench.py --full --full-out /tmp/bench_full_kt.json > $OUT/bench_line_under_rocprof.json 2>/dev/null
 cp $(find /tmp/kt -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats_default_bench.csv
 # 2b. the headline's window as the kernel trace sees it (no counters): per-dispatch start / end in the default schedule and on one stream -> window_timeline.md
 HL="--headline-only --no-headline-parity --steps 10 --warmup 2 --full-out /tmp/bench_full_hl.json"
@@ -74,10 +74,10 @@ python $REPO/tools/pmc_traffic.py $FF $FW $OUT/fir_pmc_traffic.json $OUT/fir_pmc
 ( cd $REPO && timeout 600 python tools/ctl_probe.py 2048 > $OUT/graph_shapes_probe.txt 2>&1 )
 ( cd $REPO && timeout 900 bash tools/pmc_44k1.sh > $OUT/pmc_44k1.txt 2>&1 )
 cd /tmp
-# 8. LAST: the default command, as the driver runs it -- with this round's counter summaries in place, so that the line's roofline.traffic / limiter /
+# 8. LAST: the default command with every leg (--full) -- with this round's counter summaries in place, so that the line's roofline.traffic / limiter /
 #    sustained clock are the ones just collected on these kernel sources (bench.py copies them only while the recorded source hash matches)
 mkdir -p $REPO/profiles/$R && cp $OUT/*.json $REPO/profiles/$R/ 2>/dev/null
-timeout 900 python $REPO/bench.py --full-out $OUT/bench_full.json > $OUT/bench_default_line.json 2> $OUT/bench_default.err
+timeout 900 python $REPO/bench.py --full --full-out $OUT/bench_full.json > $OUT/bench_default_line.json 2> $OUT/bench_default.err
 wc -c $OUT/bench_default_line.json
 python $REPO/tools/profile_readme.py $OUT $R > $OUT/README.md
 ls -la $OUT
