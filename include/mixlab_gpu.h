@@ -28,7 +28,8 @@ extern "C" {
 #define MX_ABI_VERSION 4u   /* 2: mx_exchange_*, mx_monitor_tick.dropped, mx_monitor_params_ex, packed RGB pixel formats; 3: MX_FLAG_FP_CONTRACT;
                               * 4: mx_graph_read_output_window, per-pixel alpha (MX_PIXFMT_YUVA420P, mx_dframe_*_alpha; the A byte of packed RGBA honoured);
                               *    later, without a bump (only additions): MX_KIND_OUTPUT_DEVICE, mx_graph_read_audio_out, mx_graph_audio_out_lag;
-                              *    mx_port_ref, mx_meter_params, mx_meter_tick, mx_graph_set_meters, mx_graph_read_meters */
+                              *    mx_port_ref, mx_meter_params, mx_meter_tick, mx_graph_set_meters, mx_graph_read_meters;
+                              *    mx_spectrum_params, mx_graph_set_spectra, mx_graph_read_spectra, mx_spectrum_tables */
 
 /* ---- status codes (0 ok, <0 error; cf. MIXLAB_IOCTX_ERROR / MIXLAB_IOCTX_PANIC) ---- */
 enum {
@@ -319,6 +320,54 @@ int mx_graph_set_meters(mx_graph* g, const mx_port_ref* ports, size_t n, const m
  * A window beyond the last run (or a run made before the taps were set), cap < n_ticks x taps, or no taps: MX_ERR_INVALID.  Joins the
  * graph's streams like mx_graph_read_output. */
 int mx_graph_read_meters(mx_graph* g, uint32_t first_tick_in_run, uint32_t n_ticks, mx_meter_tick* dst, size_t cap);
+
+/* Spectrum analyser taps on output ports of a built graph.  Like a meter, a tap observes a port: no module, no edge, the
+ * run order and the fusion plan unchanged; a graph without them launches nothing new.  Meters and spectrum taps are independent sets and may be
+ * set together.  Every run computes, on the device and once per run after its last span, for each tap, tick t and channel the band powers of
+ * a windowed n_fft-point transform.  The numbers are fixed bit for bit (tests/spectrum_model.py restates them in numpy):
+ *   frame     the last N = n_fft frames of the port's stream that end with tick t's last frame, in the port's own rate domain (a Resample
+ *             output has rate * up / down frames per tick).  Frames before the call to mx_graph_set_spectra read as +0.0; the history is
+ *             carried across ticks and runs.  Every call to mx_graph_set_spectra resets every tap's history (no tap survives it, unlike a meter's hold).
+ *   tables    window[i] = the f32 nearest to 0.5 - 0.5 cos(2 pi i / N) (periodic Hann); twiddle[k] = the f32s nearest to cos(2 pi k / N) and
+ *             -sin(2 pi k / N), k < N / 2.  mx_spectrum_tables returns the very tables the kernels use.
+ *   transform z[i] = (x_L[i] * window[i], x_R[i] * window[i]) as (re, im), f32 products; a mono port has im = +0.0.  Then the radix-2
+ *             decimation-in-time data flow on bit-reversed input: log2 N stages s = 0 .., half-size h = 2^s; for every block start b (a
+ *             multiple of 2h) and k < h: w = twiddle[k * N / (2h)], t = (z[b+k+h].re*w.re - z[b+k+h].im*w.im, z[b+k+h].re*w.im + z[b+k+h].im*w.re),
+ *             z[b+k+h] = z[b+k] - t, z[b+k] = z[b+k] + t.  Every f32 operation is rounded on its own (no fused multiply-add); the multiply
+ *             is performed for every twiddle, w = 1 included; subnormals are kept.
+ *   split     bins k = 0 .. N/2, n = (N - k) mod N:  L = (Z[k].re + Z[n].re, Z[k].im - Z[n].im), R = (Z[k].im + Z[n].im, Z[n].re - Z[k].re) in f32
+ *   power     p[k] = (double)c.re * (double)c.re + (double)c.im * (double)c.im: exact products, one f64 rounding
+ *   band j    bins edges[j] <= k < edges[j+1]: 64 f64 partials, partial q adds the p[k] with (k - edges[j]) mod 64 == q in ascending k from
+ *             +0.0, then s[q] = s[q] + s[q ^ m] for m = 32, 16, 8, 4, 2, 1 (the meters' order); the value is (float)(s[0] * (4.0 / ((double)N * N))).
+ *             The scale is a power of two, hence exact; with it a full-scale sine on a bin centre reads 1.0 (0 dB) in a band of that one
+ *             bin: the window sums to N / 2, so the bin's amplitude is N / 4, the split (which drops its halves) doubles it, and
+ *             (N / 2)^2 * 4 / N^2 = 1.  The window also puts a quarter of that into each neighbouring bin: a band that holds all three reads 1.5.
+ * A mono port's [1][*] is 0.  A stereo port stored as one float per frame (the fused L == R strip result) gives both channels from that
+ * float, equal to MX_FLAG_NO_FUSE's records bit for bit.  Non-finite input makes bands NaN or Inf.
+ * Accuracy: both channels travel through one complex transform, so the rounding error of the louder channel leaks into the quieter one.
+ * Against an f64 transform, |sqrt(band) - sqrt(f64 band)| <= (6.66 log2 N + 4) * 2^-24 * sqrt(the f64 power of BOTH channels over all bins):
+ * a channel far more than 120 dB below the other reads the other's rounding floor, not its own spectrum.
+ * One parameter set holds for every tap of the graph (params points at ONE mx_spectrum_params).  edges are bin indices chosen by the
+ * caller (bin k is k * rate / n_fft Hz): the library evaluates no transcendental for them. */
+typedef struct {
+    uint32_t        n_fft;     /* 256, 512, 1024, 2048 or 4096 */
+    uint32_t        n_bands;   /* B: 1 .. 128 */
+    const uint16_t* edges;     /* B + 1 bin indices, strictly ascending, edges[B] <= n_fft / 2 + 1; read during the call only */
+} mx_spectrum_params;
+/* Replaces the graph's spectrum taps with ports[0..n) (n = 0: none; params may then be NULL and the graph launches nothing for them).
+ * Video port: MX_ERR_TYPE.  A node or port out of range, a duplicate (node, port), a port the fusion did not materialise, an n_fft, n_bands
+ * or edges outside the above: MX_ERR_INVALID.  Waits for outstanding work like a read-back but keeps the automatic second-stream mode on.
+ * Device memory: max_ticks_per_run x n x 2 x B floats of records + 4 x n_fft floats of history per tap.  mx_graph_adopt_state does not carry
+ * taps: set them again on the new graph.  The launches count in the profile calls' ms_total only (MX_PROFILE_KINDS is unchanged).  The
+ * per-module path (mx_module_*) exposes no graph handle, so taps cannot be set there. */
+int mx_graph_set_spectra(mx_graph* g, const mx_port_ref* ports, size_t n, const mx_spectrum_params* params);
+/* Ticks [first_tick_in_run, first_tick_in_run + n_ticks) of the last run as floats [tick][tap in set order][channel 0, 1][B]; cap = floats
+ * dst holds.  A window beyond the last run (or a run made before the taps were set), cap < n_ticks x taps x 2 x B, or no taps:
+ * MX_ERR_INVALID.  Joins the graph's streams like mx_graph_read_output. */
+int mx_graph_read_spectra(mx_graph* g, uint32_t first_tick_in_run, uint32_t n_ticks, float* dst, size_t cap);
+/* The tables of the spec for one n_fft: window[n_fft], twiddle_re[n_fft / 2], twiddle_im[n_fft / 2] (any of them may be NULL).  Host only:
+ * touches no device and needs no graph.  Another n_fft: MX_ERR_INVALID. */
+int mx_spectrum_tables(uint32_t n_fft, float* window, float* twiddle_re, float* twiddle_im);
 
 /* Plotter indication (src/module/plotter.rs:37-56) for tick `tick_in_run` of the last run:
  * *fired = 1 and SPT floats in each of left/right when it fired (every 6th call, input connected). */

@@ -107,6 +107,13 @@ public:
     void write_source(uint32_t node, const float* samples, size_t n_ticks = 1) { check(mx_graph_write_source(g_, node, samples, n_ticks)); }
     void read_output(uint32_t node, uint32_t port, float* samples, size_t n_ticks = 1) { check(mx_graph_read_output(g_, node, port, samples, n_ticks)); }
     template <class P> void update(uint32_t node, const P& p) { check(mx_graph_update_params(g_, node, &p, sizeof(P))); }   // ModuleT::update through the engine (engine.rs:312)
+    // spectrum analyser taps (mx_graph_set_spectra): one n_fft and band layout (edges: n_bands + 1 ascending bin indices) for every tap
+    void set_spectra(const std::vector<mx_port_ref>& ports, uint32_t n_fft, const std::vector<uint16_t>& edges) {
+        mx_spectrum_params p{n_fft, edges.empty() ? 0u : (uint32_t)edges.size() - 1u, edges.data()};
+        check(mx_graph_set_spectra(g_, ports.data(), ports.size(), ports.empty() ? nullptr : &p));
+    }
+    // ticks [first, first + n) of the last run as [tick][tap][channel][band]
+    void read_spectra(uint32_t first, uint32_t n, std::vector<float>& dst) { check(mx_graph_read_spectra(g_, first, n, dst.data(), dst.size())); }
     size_t samples_per_tick() const { size_t s = 0; check(mx_graph_samples_per_tick(g_, &s)); return s; }
     mx_graph* handle() const { return g_; }
 private:

@@ -161,6 +161,14 @@ METER_TICK_DTYPE = np.dtype({"names": ["peak", "hold", "sum_sq", "over", "frames
                              "offsets": [0, 8, 16, 32, 40, 44], "itemsize": 48})   # mx_meter_tick
 _proto("mx_graph_set_meters", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 _proto("mx_graph_read_meters", C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t)
+class SpectrumParams(C.Structure):
+    """mx_spectrum_params: one transform size and band layout for every spectrum tap of a graph."""
+    _fields_ = [("n_fft", C.c_uint32), ("n_bands", C.c_uint32), ("edges", C.POINTER(C.c_uint16))]
+
+
+_proto("mx_graph_set_spectra", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
+_proto("mx_graph_read_spectra", C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t)
+_proto("mx_spectrum_tables", C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p)
 _proto("mx_graph_profile_run", C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float))
 _proto("mx_graph_profile_enable", C.c_int, C.c_void_p, C.c_int)
 _proto("mx_graph_profile_collect", C.c_int, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32))
@@ -190,6 +198,31 @@ class MxError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"mixlab_gpu error {code}: {msg}")
         self.code = code
+
+
+def spectrum_tables(n_fft: int):
+    """(window[n_fft], twiddle_re[n_fft // 2], twiddle_im[n_fft // 2]) float32: the tables the spectrum kernels use (host only, no device)"""
+    if n_fft not in (256, 512, 1024, 2048, 4096):   # before any buffer is sized from it
+        raise MxError(MX_ERR_INVALID, "n_fft must be 256, 512, 1024, 2048 or 4096")
+    w, re, im = np.zeros(n_fft, np.float32), np.zeros(n_fft // 2, np.float32), np.zeros(n_fft // 2, np.float32)
+    check(lib.mx_spectrum_tables(n_fft, w.ctypes.data_as(C.c_void_p), re.ctypes.data_as(C.c_void_p), im.ctypes.data_as(C.c_void_p)))
+    return w, re, im
+
+
+def log_band_edges(n_fft: int, n_bands: int, f_lo: float, f_hi: float, rate: float) -> np.ndarray:
+    """n_bands + 1 strictly ascending bin indices (uint16) for mx_spectrum_params.edges: log-spaced between f_lo and f_hi Hz where the
+    bins are dense enough, one bin per band below that.  Bin k is k * rate / n_fft Hz; the last edge is at most n_fft // 2 + 1."""
+    top = n_fft // 2 + 1
+    if not (0 < f_lo < f_hi and rate > 0 and 1 <= n_bands <= min(128, top)):
+        raise ValueError("log_band_edges: need 0 < f_lo < f_hi, rate > 0 and 1 <= n_bands <= min(128, n_fft // 2 + 1)")
+    f = f_lo * (f_hi / f_lo) ** (np.arange(n_bands + 1) / n_bands)
+    e = np.clip(np.rint(f * n_fft / rate), 0, top).astype(np.int64)
+    for j in range(1, n_bands + 1):          # at least one bin per band ...
+        e[j] = max(e[j], e[j - 1] + 1)
+    e[n_bands] = min(e[n_bands], top)
+    for j in range(n_bands - 1, -1, -1):     # ... also where that pushed against the top
+        e[j] = min(e[j], e[j + 1] - 1)
+    return e.astype(np.uint16)
 
 
 def check(rc: int) -> None:
@@ -350,6 +383,31 @@ class Graph:
         n = getattr(self, "_n_meters", 0)
         out = np.zeros((n_ticks, n), dtype=METER_TICK_DTYPE)
         check(lib.mx_graph_read_meters(self._h, first_tick, n_ticks, out.ctypes.data_as(C.c_void_p), out.size))
+        return out
+
+    def set_spectra(self, ports, n_fft: int = 2048, edges=None):
+        """spectrum taps on output ports [(node, port), ...]: every tick, the band powers of a Hann-windowed n_fft-point transform of the
+        port's last n_fft frames.  edges: B + 1 ascending bin indices (log_band_edges makes them); one set for every tap.  Each call
+        starts every tap from silence; [] removes them all."""
+        ports = list(ports)
+        if not ports:
+            check(lib.mx_graph_set_spectra(self._h, None, 0, None))
+            self._spectra = (0, 0)
+            return
+        e = np.ascontiguousarray(edges, dtype=np.uint16)
+        if e.ndim != 1 or e.size < 2 or not np.array_equal(e, np.asarray(edges)):
+            raise ValueError("edges: at least two bin indices that fit 16 bits")
+        pa = (PortRef * len(ports))(*[PortRef(int(n), int(p)) for (n, p) in ports])
+        pr = SpectrumParams(int(n_fft), e.size - 1, e.ctypes.data_as(C.POINTER(C.c_uint16)))
+        check(lib.mx_graph_set_spectra(self._h, pa, len(ports), C.byref(pr)))
+        self._spectra = (len(ports), e.size - 1)
+
+    def read_spectra(self, first_tick: int, n_ticks: int) -> np.ndarray:
+        """ticks [first_tick, first_tick + n_ticks) of the last run: float32 [ticks, taps in set order, channel, band]; 1.0 is a
+        full-scale sine on a bin centre (10 * log10 of a value is its level in dB)"""
+        n, b = getattr(self, "_spectra", (0, 0))
+        out = np.zeros((n_ticks, n, 2, b), dtype=np.float32)
+        check(lib.mx_graph_read_spectra(self._h, first_tick, n_ticks, out.ctypes.data_as(C.c_void_p), out.size))
         return out
 
     def read_output_i16(self, node, port, n_ticks: int, stereo: bool, rate=(1, 1)) -> np.ndarray:

@@ -223,6 +223,18 @@ int mx_graph_read_meters(mx_graph* g, uint32_t first_tick_in_run, uint32_t n_tic
     return guard([&] { REQUIRE(g, "graph is NULL"); g->g->read_meters(first_tick_in_run, n_ticks, reinterpret_cast<mx::MeterTick*>(dst), cap); });
 }
 
+int mx_graph_set_spectra(mx_graph* g, const mx_port_ref* ports, size_t n, const mx_spectrum_params* params) {
+    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->set_spectra(ports, n, params); });
+}
+
+int mx_graph_read_spectra(mx_graph* g, uint32_t first_tick_in_run, uint32_t n_ticks, float* dst, size_t cap) {
+    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->read_spectra(first_tick_in_run, n_ticks, dst, cap); });
+}
+
+int mx_spectrum_tables(uint32_t n_fft, float* window, float* twiddle_re, float* twiddle_im) {   // host only: no device, no graph
+    return guard([&] { REQUIRE(mx::spectrum_tables(n_fft, window, twiddle_re, twiddle_im), "n_fft must be 256, 512, 1024, 2048 or 4096"); });
+}
+
 int mx_graph_read_plotter(mx_graph* g, uint32_t node, uint32_t tick_in_run, float* left, float* right, int* fired) {
     return guard([&] {
         REQUIRE(g && left && right && fired, "NULL argument");

@@ -469,8 +469,9 @@ void Graph::flush_deferred_tail(bool gated) {
     if (prof && !deferred_.outs.empty()) hip_check(hipEventRecord(prof->od_tail_end, tail_stream_), "hipEventRecord");
     deferred_.outs.clear();
     for (const MeterRun& r : deferred_.meters) launch_meters(r, tail_stream_);   // meters on the tail's outputs
-    if (prof && !deferred_.meters.empty()) hip_check(hipEventRecord(prof->meters_tail_end, tail_stream_), "hipEventRecord");
-    deferred_.meters.clear();
+    for (const SpecRun& r : deferred_.spectra) launch_spectra(r, tail_stream_);   // spectrum taps on the tail's outputs
+    if (prof && !(deferred_.meters.empty() && deferred_.spectra.empty())) hip_check(hipEventRecord(prof->meters_tail_end, tail_stream_), "hipEventRecord");
+    deferred_.meters.clear(); deferred_.spectra.clear();
     if (tail_hook_) { auto hook = std::move(tail_hook_); tail_hook_ = nullptr; hook(tail_stream_); }   // (mx_exchange: pack + exchange of that run's buses, behind the bank)
     // recorded AFTER the hook: whoever waits for this tail (wait_tail) is then also ordered behind the hook's reads of the buses on the tail stream -- a later run's Mixer on
     // stream_ must not overwrite them under a pack that is still copying
@@ -509,6 +510,7 @@ void Graph::end_auto_tail() {
     for (Group& g : groups_) { g.desc_alt.free_(); g.extra_alt.free_(); }
     build_descriptors();
     if (!meters_.empty()) upload_meters(meter_fpc_);   // every tap on stream_, the first buffers only
+    if (!spectra_.empty()) upload_spectra(spec_fpc_);
 }
 
 Graph::~Graph() {
@@ -1022,6 +1024,7 @@ void Graph::bind_source(uint32_t node, const void* dev) {
     n.bound = (const float*)dev;
     build_descriptors();
     if (!meters_.empty()) upload_meters(meter_fpc_);
+    if (!spectra_.empty()) upload_spectra(spec_fpc_);
 }
 
 void Graph::set_input_enabled(uint32_t node, uint32_t port, bool enabled) {
@@ -1050,6 +1053,7 @@ void Graph::ensure_capacity(size_t frames) {
     layout_slab();
     build_descriptors();
     if (!meters_.empty()) upload_meters(meter_fpc_);   // the ports moved; room for more ticks
+    if (!spectra_.empty()) upload_spectra(spec_fpc_);
 }
 
 static bool group_launches(const Group& g);
@@ -1058,9 +1062,10 @@ void Graph::run(uint64_t t0, size_t fpc, uint32_t n_calls, float* ms_by_kind, fl
     const size_t frames = fpc * (size_t)n_calls;
     auto drop_schedules = [&] { for (uint32_t id : sched_nodes_) { nodes_[id].sched.clear(); nodes_[id].gate_sched.clear(); } sched_nodes_.clear(); };
     if (frames > cap_frames_) { drop_schedules(); throw Error(MX_ERR_INVALID, "n_ticks exceeds max_ticks_per_run"); }
-    if (n_calls == 0 || fpc == 0) { drop_schedules(); last_calls_ = n_calls; last_frames_per_call_ = fpc; meter_run_ticks_ = 0; return; }
+    if (n_calls == 0 || fpc == 0) { drop_schedules(); last_calls_ = n_calls; last_frames_per_call_ = fpc; meter_run_ticks_ = spec_run_ticks_ = 0; return; }
     hip_check(hipSetDevice(device_), "hipSetDevice");
     if (!meters_.empty() && fpc != meter_fpc_) { sync(); upload_meters(fpc); }   // (the module compat path's call length): frames per tick and record room
+    if (!spectra_.empty() && fpc != spec_fpc_) { sync(); upload_spectra(fpc); }
 
     // ---- scheduled parameter updates (Engine::client_update between two ticks, src/engine.rs:192-214,277-398) ----
     // Trigger updates travel as one gate bit per tick and cost nothing.  Any other module's update cuts the run into spans:
@@ -1172,6 +1177,7 @@ void Graph::run(uint64_t t0, size_t fpc, uint32_t n_calls, float* ms_by_kind, fl
     last_calls_ = n_calls;
     last_frames_per_call_ = fpc;
     meter_run_ticks_ = meters_.empty() ? 0u : n_calls;
+    spec_run_ticks_ = spectra_.empty() ? 0u : n_calls;
     if (prof) ++prof_runs_count_;
     if (ms_by_kind) (void)profile_collect(ms_by_kind, ms_total);
 }
@@ -1258,7 +1264,7 @@ void Graph::run_span(uint64_t t0, size_t fpc, uint32_t call_off, uint32_t n_call
                 if ((int)gi == tail_gi_) {
                     if (deferred_.pending) flush_deferred_tail(false);   // (a run whose earlier groups had no speculative EqThree launch: nothing opened a gate)
                     hip_check(hipEventRecord(ev_head_done_, stream_), "hipEventRecord");
-                    deferred_.items.clear(); deferred_.outs.clear(); deferred_.meters.clear(); deferred_.parity = parity_; deferred_.prof = prof;
+                    deferred_.items.clear(); deferred_.outs.clear(); deferred_.meters.clear(); deferred_.spectra.clear(); deferred_.parity = parity_; deferred_.prof = prof;
                     if (prof) prof->tail_held = true;
                 }
                 deferred_.items.push_back(TailLaunch{desc_of(g), n, g.max_taps, gf, g.dup_mode, prof ? prof->group_end[gi] : nullptr});
@@ -1311,7 +1317,7 @@ void Graph::run_span(uint64_t t0, size_t fpc, uint32_t call_off, uint32_t n_call
     // after everything else of the span on stream_ (the video section included): its profile interval starts at the latest event recorded there
     launch_outputs(t0, call_off, n_calls, prof);
     // the port buffers hold every tick of the run: the meters go once, after its last span
-    if (call_off + n_calls == run_calls) launch_meter_taps(run_calls, prof);
+    if (call_off + n_calls == run_calls) { launch_meter_taps(run_calls, prof); launch_spectrum_taps(run_calls, prof); }
     if (prof) { prof_runs_.push_back(std::move(prof_pool_.back())); prof_pool_.pop_back(); }
 }
 
@@ -1372,7 +1378,7 @@ uint32_t Graph::profile_collect(float* ms_by_kind, float* ms_total) {
         hipEvent_t end = last;
         if (p.od) { perf_od_ms_ += elapsed(last, p.od_end); end = p.od_end; }
         if (p.od_tail) perf_od_ms_ += elapsed(p.group_end.back(), p.od_tail_end);
-        // meter launches: no kind of their own, counted in the total (and so in engine_us): on stream_ last of all, or on the tail stream
+        // meter and spectrum launches: no kind of their own, counted in the total (and so in engine_us): on stream_ last of all, or on the tail stream
         // behind the tail (and its OutputDevices)
         if (p.meters) end = p.meters_end;
         perf_total_ms_ = elapsed(p.begin, end);
@@ -1678,6 +1684,125 @@ void Graph::read_meters(uint32_t first, uint32_t n, MeterTick* dst, size_t cap) 
     wait_tail(-1);
     hip_check(hipMemcpyAsync(dst, (const MeterTick*)meter_rec_.p + (size_t)first * meters_.size(), count * sizeof(MeterTick), hipMemcpyDeviceToHost, stream_),
               "hipMemcpyAsync(D2H)");
+    sync();
+}
+
+// ---- spectrum taps (mixlab_gpu.h mx_graph_set_spectra) ----
+
+void Graph::set_spectra(const mx_port_ref* ports, size_t n, const mx_spectrum_params* params) {
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    if (n && (!ports || !params)) throw Error(MX_ERR_INVALID, "ports / params is NULL");
+    if (n > 0xffffffu) throw Error(MX_ERR_INVALID, "more than 2^24 spectrum taps");
+    std::vector<float> win, tre, tim;
+    if (n) {
+        const uint32_t N = params->n_fft, B = params->n_bands;
+        win.resize(N <= 4096 ? N : 0); tre.resize(win.size() / 2); tim.resize(win.size() / 2);
+        if (N > 4096 || !spectrum_tables(N, win.data(), tre.data(), tim.data())) throw Error(MX_ERR_INVALID, "mx_spectrum_params: n_fft must be 256, 512, 1024, 2048 or 4096");
+        if (B < 1 || B > 128) throw Error(MX_ERR_INVALID, "mx_spectrum_params: n_bands must be 1 .. 128");
+        if (!params->edges) throw Error(MX_ERR_INVALID, "mx_spectrum_params: edges is NULL");
+        for (uint32_t j = 0; j < B; ++j)
+            if (params->edges[j] >= params->edges[j + 1]) throw Error(MX_ERR_INVALID, "mx_spectrum_params: edges must be strictly ascending");
+        if (params->edges[B] > N / 2 + 1) throw Error(MX_ERR_INVALID, "mx_spectrum_params: edges[n_bands] exceeds n_fft / 2 + 1");
+    }
+    std::vector<uint64_t> keys(n);
+    for (size_t i = 0; i < n; ++i) {
+        const mx_port_ref pr = ports[i];
+        if (pr.node >= nodes_.size() || pr.port >= nodes_[pr.node].out_type.size()) throw Error(MX_ERR_INVALID, "spectrum: output terminal out of range");
+        const Node& nd = nodes_[pr.node];
+        if (nd.out_type[pr.port] == MX_VIDEO) throw Error(MX_ERR_TYPE, "spectrum: a video port has no spectrum");
+        if (nd.out_elided[pr.port]) throw Error(MX_ERR_INVALID, "port is not materialised: it only feeds a fused consumer (build with MX_FLAG_NO_FUSE to observe it)");
+        keys[i] = (uint64_t)pr.node << 32 | pr.port;
+    }
+    { std::vector<uint64_t> k = keys; std::sort(k.begin(), k.end()); if (std::adjacent_find(k.begin(), k.end()) != k.end()) throw Error(MX_ERR_INVALID, "spectrum: duplicate (node, port)"); }
+    // like set_meters: the last run's launches are done with the records and histories; the second-stream mode stays on
+    sync();
+    spectra_.assign(ports, ports + n);
+    spec_run_ticks_ = 0;
+    spec_hist_cur_ = 0;
+    spec_rec_.free_();
+    if (spectra_.empty()) { spec_desc_.free_(); spec_hist_.free_(); spec_tab_.free_(); spec_n_fft_ = spec_n_bands_ = 0; return; }
+    const uint32_t N = spec_n_fft_ = params->n_fft, B = spec_n_bands_ = params->n_bands;
+    // tables: window[N] | twiddle (re, im)[N / 2] | edges[B + 1] (u16, padded to whole floats)
+    std::vector<float> tab(2 * (size_t)N + (B + 2) / 2, 0.0f);
+    std::copy(win.begin(), win.end(), tab.begin());
+    for (uint32_t k = 0; k < N / 2; ++k) { tab[N + 2 * k] = tre[k]; tab[N + 2 * k + 1] = tim[k]; }
+    memcpy(tab.data() + 2 * (size_t)N, params->edges, (B + 1) * sizeof(uint16_t));
+    spec_tab_.alloc(tab.size() * sizeof(float));
+    hip_check(hipMemcpy(spec_tab_.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy(spectrum tables)");
+    // every tap's history starts as +0.0: frames before this call read as silence
+    spec_hist_.alloc(2 * n * 2 * (size_t)N * sizeof(float));
+    hip_check(hipMemsetAsync(spec_hist_.p, 0, 2 * n * 2 * (size_t)N * sizeof(float), stream_), "hipMemsetAsync(spectrum history)");
+    hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
+    upload_spectra(spec_fpc_ ? spec_fpc_ : spt_);
+}
+
+// As upload_meters: the descriptors of every tap for both buffer parities in launch order (the taps read on stream_, then those on the tail's
+// outputs), and room for a whole submission's records.  The stream is quiescent.  The histories are untouched: they hold frames, whatever the
+// call length.
+void Graph::upload_spectra(size_t fpc) {
+    spec_fpc_ = fpc;
+    const size_t n = spectra_.size();
+    std::vector<uint32_t> order, tail;
+    for (uint32_t i = 0; i < (uint32_t)n; ++i) {
+        int32_t o = (int32_t)spectra_[i].node;
+        while (nodes_[o].elided && nodes_[o].owner >= 0) o = nodes_[o].owner;   // the node whose launch writes the port
+        (tail_gi_ >= 0 && nodes_[o].group >= tail_gi_ ? tail : order).push_back(i);
+    }
+    spec_n_head_ = (uint32_t)order.size();
+    order.insert(order.end(), tail.begin(), tail.end());
+    std::vector<SpecDesc> d(2 * n);
+    for (uint32_t par = 0; par < 2; ++par)
+        for (size_t k = 0; k < n; ++k) {
+            const mx_port_ref tp = spectra_[order[k]];
+            const Node& nd = nodes_[tp.node];
+            SpecDesc& m = d[par * n + k];
+            if (nd.bound && tp.port == 0) m.p = nd.bound;
+            else m.p = (const float*)slab_.p + (par && nd.out_off2[tp.port] != SIZE_MAX ? nd.out_off2[tp.port] : nd.out_off[tp.port]);
+            m.frames = (uint32_t)(fpc * nd.dom_num / nd.dom_den);
+            m.layout = nd.out_dup[tp.port] ? METER_DUP : (nd.out_type[tp.port] == MX_MONO ? METER_MONO : METER_STEREO);
+            m.slot = order[k]; m._pad = 0;
+        }
+    spec_desc_.alloc(d.size() * sizeof(SpecDesc));
+    hip_check(hipMemcpy(spec_desc_.p, d.data(), d.size() * sizeof(SpecDesc), hipMemcpyHostToDevice), "hipMemcpy(spectrum descriptors)");
+    const size_t need = std::max<size_t>(1, cap_frames_ / fpc) * n * 2 * spec_n_bands_ * sizeof(float);
+    if (!spec_rec_.p || spec_rec_.bytes < need) spec_rec_.alloc(need);
+}
+
+// The run's spectrum launches, after its last span and behind the meters.  launch_meter_taps's ordering argument holds word for word: a tap
+// read on stream_ is queued behind the run's producers through the descriptor of the run's buffer parity; a tap on an output of the tail is
+// held back with it (deferred_.spectra) and goes on the tail stream, covered by ev_tail_done_.  Meters and spectra only read the ports and
+// write disjoint records, so neither disturbs the other.  The histories add one more carried state, with the same argument as the meters'
+// hold: a group's launches of consecutive runs follow each other on that group's stream (a run that changes the stream of the tail's taps has
+// joined the tail first: run()'s wait_tail), and each run reads the buffer the previous one wrote (spec_hist_cur_ flips once per run for
+// both groups, whose slots are disjoint).
+void Graph::launch_spectrum_taps(uint32_t n_calls, ProfSpan* prof) {
+    if (spectra_.empty()) return;
+    const uint32_t n = (uint32_t)spectra_.size(), N = spec_n_fft_;
+    const float* tab = (const float*)spec_tab_.p;
+    float* h0 = (float*)spec_hist_.p + (size_t)spec_hist_cur_ * n * 2 * N;
+    float* h1 = (float*)spec_hist_.p + (size_t)(spec_hist_cur_ ^ 1u) * n * 2 * N;
+    spec_hist_cur_ ^= 1u;
+    SpecRun all{(const SpecDesc*)spec_desc_.p + (size_t)(parity_ & 1u) * n, n, n_calls, n, N, spec_n_bands_,
+                tab, (const float2*)(tab + N), (const uint16_t*)(tab + 2 * (size_t)N), h0, h1, (float*)spec_rec_.p};
+    const uint32_t n_head = overlap_this_run_ ? spec_n_head_ : n;
+    if (n_head < n) { SpecRun t = all; t.desc = all.desc + n_head; t.n = n - n_head; deferred_.spectra.push_back(t); }
+    all.n = n_head;
+    if (n_head) launch_spectra(all, stream_);
+    if (!prof) return;
+    if (n_head) { hip_check(hipEventRecord(prof->meters_end, stream_), "hipEventRecord"); prof->meters = true; }   // (again, when meters recorded it: the later record holds)
+    prof->meters_tail = !(deferred_.meters.empty() && deferred_.spectra.empty());
+}
+
+void Graph::read_spectra(uint32_t first, uint32_t n, float* dst, size_t cap) {
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    if (spectra_.empty()) throw Error(MX_ERR_INVALID, "no spectrum taps are set");
+    if ((uint64_t)first + n > spec_run_ticks_) throw Error(MX_ERR_INVALID, "the window lies beyond the last run (or no run since the spectrum taps were set)");
+    const size_t per_tick = spectra_.size() * 2 * spec_n_bands_, count = (size_t)n * per_tick;
+    if (cap < count) throw Error(MX_ERR_INVALID, "cap is smaller than n_ticks x taps x 2 x n_bands");
+    if (count && !dst) throw Error(MX_ERR_INVALID, "dst is NULL");
+    if (!count) return;
+    wait_tail(-1);
+    hip_check(hipMemcpyAsync(dst, (const float*)spec_rec_.p + (size_t)first * per_tick, count * sizeof(float), hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(D2H)");
     sync();
 }
 

@@ -158,6 +158,9 @@ public:
     // level meters (mx_graph_set_meters / mx_graph_read_meters): taps on output ports, measured once per run after its last span
     void set_meters(const mx_port_ref* ports, size_t n, const mx_meter_params* params);
     void read_meters(uint32_t first, uint32_t n, MeterTick* dst, size_t cap);
+    // spectrum taps (mx_graph_set_spectra / mx_graph_read_spectra): a windowed transform of every tap's last n_fft frames per tick, as band powers
+    void set_spectra(const mx_port_ref* ports, size_t n, const mx_spectrum_params* params);
+    void read_spectra(uint32_t first, uint32_t n, float* dst, size_t cap);
     void read_output_i16(uint32_t node, uint32_t port, int16_t* host, size_t frames);   // sink hand-off format
     void write_source_i16(uint32_t node, const int16_t* host, size_t frames);            // ingest format
     float* output_ptr(uint32_t node, uint32_t port, size_t* floats_per_tick, bool stream_ordered_consumer = true /* false: a caller inside the library that orders itself
@@ -220,6 +223,8 @@ private:
     void launch_outputs(uint64_t t0, uint32_t call_off, uint32_t n_calls, ProfSpan* prof);   // the span's OutputDevice launches
     void upload_meters(size_t fpc);                                      // the taps' descriptors (both parities) and record room, on a quiescent stream
     void launch_meter_taps(uint32_t n_calls, ProfSpan* prof);           // the run's meter launches (after its last span)
+    void upload_spectra(size_t fpc);                                     // the spectrum taps' descriptors (both parities) and record room, on a quiescent stream
+    void launch_spectrum_taps(uint32_t n_calls, ProfSpan* prof);        // the run's spectrum launches (after its last span, behind the meters)
     void refresh_gates(Group& g, uint32_t run_calls);
     uint32_t trigger_of_row(const Group& g, uint32_t row) const;        // node id of the Trigger behind row `row` of a gated group, or ~0u
     void stage_upload(void* dst, const void* src, size_t bytes);         // H2D on the graph's stream through page-locked staging
@@ -259,7 +264,7 @@ private:
     // meters: the taps on the tail's outputs, behind those.  prof: the span's profile record (nullptr: not profiled), whose tail events the release records.
     struct TailLaunch { const void* desc = nullptr; uint32_t n = 0, max_ch = 0; size_t frames = 0; int dup_mode = 0; hipEvent_t prof_ev = nullptr; };
     struct DeferredTail { bool pending = false; std::vector<TailLaunch> items; uint32_t parity = 0; ProfSpan* prof = nullptr;
-                          std::vector<OutRun> outs; std::vector<MeterRun> meters; } deferred_;
+                          std::vector<OutRun> outs; std::vector<MeterRun> meters; std::vector<SpecRun> spectra; } deferred_;   // spectra: spectrum taps on the tail's outputs, behind the meters
     std::function<void(hipStream_t)> tail_hook_;
     std::vector<hipEvent_t> head_waits_;
     uint64_t n_gated_ = 0, n_at_once_ = 0;
@@ -289,6 +294,14 @@ private:
     DevBuf meter_desc_, meter_rec_, meter_state_;
     size_t meter_fpc_ = 0;                  // frames per call the descriptors were built for
     uint32_t meter_run_ticks_ = 0;          // ticks of the last run that measured the current taps (0: none since they were set)
+    // spectrum taps: the same arrangement beside the meters (set order, launch order, spec_n_head_, SpecDesc[2][n]).  spec_rec_:
+    // float[max ticks][n][2][bands]; spec_hist_: float[2][n][2 * n_fft], the buffer a run reads is spec_hist_cur_, it writes the other;
+    // spec_tab_: window, twiddles and band edges on the device
+    std::vector<mx_port_ref> spectra_;
+    uint32_t spec_n_fft_ = 0, spec_n_bands_ = 0, spec_n_head_ = 0, spec_hist_cur_ = 0;
+    DevBuf spec_desc_, spec_rec_, spec_hist_, spec_tab_;
+    size_t spec_fpc_ = 0;
+    uint32_t spec_run_ticks_ = 0;
     float perf_od_ms_ = 0.f;                // OutputDevice launches of the last collected run
     bool prof_this_run_ = false;
     size_t plot_job_off_ = 0;
@@ -307,7 +320,7 @@ private:
         std::vector<hipEvent_t> group_end;                              // per launch group, on the stream it ran on
         hipEvent_t video_end = nullptr, tail_begin = nullptr;           // the per-tick video section (stream_); a held-back tail's start (tail stream)
         hipEvent_t od_end = nullptr, od_tail_end = nullptr;             // OutputDevice launches on stream_ / behind the tail
-        hipEvent_t meters_end = nullptr, meters_tail_end = nullptr;     // meter launches on stream_ / behind the tail (and its OutputDevices)
+        hipEvent_t meters_end = nullptr, meters_tail_end = nullptr;     // meter and spectrum launches on stream_ / behind the tail (and its OutputDevices)
         bool tail_held = false, od = false, od_tail = false, meters = false, meters_tail = false;
         explicit ProfSpan(size_t n_groups);
         ProfSpan(const ProfSpan&) = delete; ProfSpan& operator=(const ProfSpan&) = delete;

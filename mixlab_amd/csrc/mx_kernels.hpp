@@ -168,6 +168,21 @@ struct MeterRun {
     MeterTick* rec; MeterHold* state;        // rec[tick * stride + slot]; state[2 * slot + channel]
 };
 void launch_meters(const MeterRun& r, hipStream_t s);   // k_meter_reduce, then k_meter_hold
+// Spectrum taps (mx_k_spectrum.hip, mixlab_gpu.h mx_graph_set_spectra): one descriptor per tap and buffer parity.  The history of a tap is
+// the last n_fft frames of its stream before the run, in the port's own layout (one float per frame for mono / dup, two for stereo), kept
+// in two buffers of 2 * n_fft floats each that alternate per run (hist[run parity][slot]).
+struct SpecDesc { const float* p; uint32_t frames, layout, slot, _pad; };   // p: the port at tick 0 of the run; layout: METER_*; slot: index in set order
+struct SpecRun {
+    const SpecDesc* desc; uint32_t n;        // the launch's taps
+    uint32_t n_ticks, stride;                // ticks of the run; taps of the whole set (records per tick)
+    uint32_t n_fft, n_bands;
+    const float* window; const float2* twiddle; const uint16_t* edges;   // device tables: n_fft, n_fft / 2, n_bands + 1
+    const float* hist_in; float* hist_out;   // [slot][2 * n_fft]: read by this run, written for the next
+    float* rec;                              // rec[((tick * stride + slot) * 2 + channel) * n_bands + band]
+};
+void launch_spectra(const SpecRun& r, hipStream_t s);   // k_spectrum, then k_spectrum_history
+// the tables of the spectrum spec, correctly rounded f32 (host only): window[n_fft], twiddle re / im [n_fft / 2]; false: n_fft is not a supported size
+bool spectrum_tables(uint32_t n_fft, float* window, float* twiddle_re, float* twiddle_im);
 
 void launch_fir(const FirDesc* d, uint32_t n, uint32_t max_taps, size_t frames, hipStream_t s, bool fc = false);
 void launch_resample(const ResampleDesc* d, uint32_t n, uint32_t max_taps, uint32_t tab_doubles /* max up * taps_per_phase */,
