@@ -29,7 +29,8 @@ extern "C" {
                               * 4: mx_graph_read_output_window, per-pixel alpha (MX_PIXFMT_YUVA420P, mx_dframe_*_alpha; the A byte of packed RGBA honoured);
                               *    later, without a bump (only additions): MX_KIND_OUTPUT_DEVICE, mx_graph_read_audio_out, mx_graph_audio_out_lag;
                               *    mx_port_ref, mx_meter_params, mx_meter_tick, mx_graph_set_meters, mx_graph_read_meters;
-                              *    mx_spectrum_params, mx_graph_set_spectra, mx_graph_read_spectra, mx_spectrum_tables */
+                              *    mx_spectrum_params, mx_graph_set_spectra, mx_graph_read_spectra, mx_spectrum_tables;
+                              *    mx_video_scope_params, mx_graph_set_video_scopes, mx_graph_read_video_scopes, mx_video_scope_record_bytes, mx_video_scope */
 
 /* ---- status codes (0 ok, <0 error; cf. MIXLAB_IOCTX_ERROR / MIXLAB_IOCTX_PANIC) ---- */
 enum {
@@ -640,6 +641,48 @@ int mx_graph_video_output(mx_graph* g, uint32_t node, uint32_t port, mx_dframe**
 /* RGBA8 device buffer a VIDEO_TO_RGBA node wrote on the last tick (width/height 0 = no frame).  Written asynchronously on the graph's
  * stream: read it there, or after mx_graph_sync. */
 int mx_graph_rgba_output(mx_graph* g, uint32_t node, void** device_rgba, int32_t* stride, uint32_t* width, uint32_t* height);
+
+/* Video scope taps: taps on VIDEO output ports of a built graph -- what the meters and the spectrum taps are for the audio
+ * half.  A tap observes a port: no module, no edge, the run order and the fusion plan unchanged; a graph without them launches nothing new
+ * and its video path is unchanged call for call.  On every recorded tick each tap's frame is counted on the device, in one launch, into one
+ * record.  BUILD-SPECIFIED (the reference has no scopes); every number is an integer count, so the records are fixed bit for bit whatever the
+ * order of accumulation (tests/video_scope_model.py restates them in numpy):
+ *   counted   a frame is counted when it is yuv420p or yuva420p (the coverage plane is ignored).  W x H is its visible luma size, the chroma
+ *             planes are (W >> 1) x (H >> 1); stride padding is never counted.  All counts are uint32_t.
+ *   hist      [3][256]: hist[0][v] = luma samples equal to v; hist[1], hist[2] the same for the U and V planes.  Minimum, maximum, mean and the
+ *             legal-range violations (Y < 16, Y > 235, chroma outside 16 .. 240: crushed blacks, blown whites) are sums over these 768
+ *             numbers, taken on the host: the record has NO fields for them.
+ *   wave      [C][256], C = wave_cols (0: absent): wave[c][v] = luma samples of value v in column bucket c = floor(x * C / W), x the sample's
+ *             column, in integer arithmetic -- the waveform monitor's picture.  x * C fits 32 bits for W <= 2^24 (C <= 256); frames are at
+ *             most 16 384 wide.  A bucket without a column (W < C) stays 0.
+ *   vec       [128][128], present when vectorscope != 0: vec[V >> 1][U >> 1] counts the (U, V) pairs of chroma samples at the same chroma position.
+ *   record    per recorded tick and tap: a 32-byte header of uint32_t { present, counted, pixfmt, width, height, tick_in_run, reserved[2] },
+ *             then hist, then wave, then vec: 32 + 4 * (768 + 256 * C + 16384 * [vectorscope != 0]) bytes (mx_video_scope_record_bytes).
+ *             present = 0: the port held no frame that tick (Output = None, io.rs:76) -- everything but tick_in_run is 0.  A frame of another
+ *             pixel format (the A / B outputs of a VideoMixer are clones of its inputs: packed RGB, nv12, deep YUV ...): present = 1,
+ *             counted = 0, pixfmt (mx_pixfmt; MX_PIXFMT_YUVA420P for a yuv420p frame with a coverage plane) and the size filled, every count 0.
+ *             No conversion is specified here: scopes of other formats are a follow-up.  reserved is 0.
+ *   hop       >= 1.  The graph keeps ONE counter c: 0 when the taps are set, incremented once per video tick; a tick is recorded when
+ *             c mod hop == 0 (tested before the increment); c is carried across runs.  A display wants 30 - 60 records a second, not one per
+ *             tick of a 2048-tick run: with wave_cols = 256 and the vectorscope a record is 330 784 bytes.
+ * One parameter set holds for every tap of the graph.  A frame that is still symbolic (an unevaluated cross-fade chain or scaler output) is
+ * materialised on the graph's stream before it is counted: that write is the price of a tap; every picture the graph produces (composite,
+ * RGBA sink, Monitor) is the same byte for byte with and without taps. */
+typedef struct { uint32_t wave_cols /* 0, 64, 128 or 256 */, vectorscope /* 0: no vec */, hop /* >= 1 */; } mx_video_scope_params;
+/* Replaces the graph's scope taps with ports[0..n) (n = 0: none; params may then be NULL and the graph launches nothing for them) and resets c.
+ * Audio port: MX_ERR_TYPE.  A node or port out of range, a duplicate (node, port), wave_cols outside the list, hop = 0: MX_ERR_INVALID.
+ * Device memory: ceil(max_ticks_per_run / hop) x n x record bytes for the last run's records; more than 4 GiB: MX_ERR_NOMEM (raise hop).
+ * Waits for outstanding work like a read-back.  mx_graph_adopt_state does not carry taps: set them again on the new graph. */
+int mx_graph_set_video_scopes(mx_graph* g, const mx_port_ref* ports, size_t n, const mx_video_scope_params* params);
+/* The last run's records, [recorded tick][tap in set order], mx_video_scope_record_bytes each; *n_records = recorded ticks x taps (0 when no
+ * tick of the run was recorded; dst may then be NULL).  cap_bytes smaller than that, no taps, or no run since they were set: MX_ERR_INVALID.
+ * Joins the graph's streams like mx_graph_read_output. */
+int mx_graph_read_video_scopes(mx_graph* g, void* dst, size_t cap_bytes, uint32_t* n_records);
+/* Bytes of one record under `params` (hop is not looked at).  Host only: touches no device.  wave_cols outside the list: MX_ERR_INVALID. */
+int mx_video_scope_record_bytes(const mx_video_scope_params* params, size_t* bytes);
+/* The pixel-path form, beside mx_video_to_rgba: the record of ONE frame into device_record (4-byte aligned device memory of
+ * mx_video_scope_record_bytes bytes), asynchronous on `stream`; present = 1, tick_in_run = 0, hop ignored. */
+int mx_video_scope(const mx_dframe* in, const mx_video_scope_params* params, void* device_record, void* stream);
 
 /* MX_KIND_MONITOR after a run.  Tick `tick_in_run` of the last mx_graph_run_ticks as the codec thread would see it:
  * ts = the tick's timestamp relative to the node's epoch -- the first tick it ever ran (monitor.rs:121-123); when the Video input carried

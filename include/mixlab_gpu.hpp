@@ -114,6 +114,12 @@ public:
     }
     // ticks [first, first + n) of the last run as [tick][tap][channel][band]
     void read_spectra(uint32_t first, uint32_t n, std::vector<float>& dst) { check(mx_graph_read_spectra(g_, first, n, dst.data(), dst.size())); }
+    // video scope taps (mx_graph_set_video_scopes): one parameter set for every tap; an empty list removes them
+    void set_video_scopes(const std::vector<mx_port_ref>& ports, const mx_video_scope_params& p) {
+        check(mx_graph_set_video_scopes(g_, ports.data(), ports.size(), ports.empty() ? nullptr : &p));
+    }
+    // the last run's records [recorded tick][tap], mx_video_scope_record_bytes each; returns how many dst received
+    uint32_t read_video_scopes(std::vector<uint8_t>& dst) { uint32_t n = 0; check(mx_graph_read_video_scopes(g_, dst.data(), dst.size(), &n)); return n; }
     size_t samples_per_tick() const { size_t s = 0; check(mx_graph_samples_per_tick(g_, &s)); return s; }
     mx_graph* handle() const { return g_; }
 private:

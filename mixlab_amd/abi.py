@@ -169,6 +169,14 @@ class SpectrumParams(C.Structure):
 _proto("mx_graph_set_spectra", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 _proto("mx_graph_read_spectra", C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t)
 _proto("mx_spectrum_tables", C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p)
+class VideoScopeParams(C.Structure):
+    """mx_video_scope_params: waveform columns (0, 64, 128, 256), vectorscope on / off, record every hop-th video tick."""
+    _fields_ = [("wave_cols", C.c_uint32), ("vectorscope", C.c_uint32), ("hop", C.c_uint32)]
+
+
+_proto("mx_graph_set_video_scopes", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
+_proto("mx_graph_read_video_scopes", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32))
+_proto("mx_video_scope_record_bytes", C.c_int, C.POINTER(VideoScopeParams), C.POINTER(C.c_size_t))
 _proto("mx_graph_profile_run", C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float))
 _proto("mx_graph_profile_enable", C.c_int, C.c_void_p, C.c_int)
 _proto("mx_graph_profile_collect", C.c_int, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32))
@@ -207,6 +215,29 @@ def spectrum_tables(n_fft: int):
     w, re, im = np.zeros(n_fft, np.float32), np.zeros(n_fft // 2, np.float32), np.zeros(n_fft // 2, np.float32)
     check(lib.mx_spectrum_tables(n_fft, w.ctypes.data_as(C.c_void_p), re.ctypes.data_as(C.c_void_p), im.ctypes.data_as(C.c_void_p)))
     return w, re, im
+
+
+def video_scope_record_bytes(wave_cols: int = 0, vectorscope: bool = False) -> int:
+    """bytes of one video scope record: 32 + 4 * (768 + 256 * wave_cols + 16384 * vectorscope) (host only, no device)"""
+    n = C.c_size_t()
+    check(lib.mx_video_scope_record_bytes(C.byref(VideoScopeParams(int(wave_cols), 1 if vectorscope else 0, 1)), C.byref(n)))
+    return n.value
+
+
+def parse_video_scope_records(raw: np.ndarray, wave_cols: int, vectorscope: bool) -> list:
+    """raw bytes of back-to-back records -> one dict per record: the header fields as ints, hist [3, 256], wave [wave_cols, 256] or None,
+    vec [128, 128] (indexed [V >> 1, U >> 1]) or None, all uint32"""
+    words = video_scope_record_bytes(wave_cols, vectorscope) // 4
+    r = np.ascontiguousarray(raw).view(np.uint32).reshape(-1, words)
+    out = []
+    for w in r:
+        d = dict(zip(("present", "counted", "pixfmt", "width", "height", "tick_in_run"), (int(x) for x in w[:6])))
+        d["reserved"] = (int(w[6]), int(w[7]))
+        d["hist"] = w[8:776].reshape(3, 256)
+        d["wave"] = w[776:776 + 256 * wave_cols].reshape(wave_cols, 256) if wave_cols else None
+        d["vec"] = w[776 + 256 * wave_cols:].reshape(128, 128) if vectorscope else None
+        out.append(d)
+    return out
 
 
 def log_band_edges(n_fft: int, n_bands: int, f_lo: float, f_hi: float, rate: float) -> np.ndarray:
@@ -409,6 +440,30 @@ class Graph:
         out = np.zeros((n_ticks, n, 2, b), dtype=np.float32)
         check(lib.mx_graph_read_spectra(self._h, first_tick, n_ticks, out.ctypes.data_as(C.c_void_p), out.size))
         return out
+
+    def set_video_scopes(self, ports, wave_cols: int = 0, vectorscope: bool = False, hop: int = 1):
+        """video scope taps on video output ports [(node, port), ...]: on every hop-th video tick, the luma / U / V histograms, the
+        waveform's column histograms (wave_cols 0, 64, 128 or 256) and the vectorscope of the port's frame.  One parameter set for every
+        tap; each call resets the hop counter; [] removes the taps."""
+        ports = list(ports)
+        if not ports:
+            check(lib.mx_graph_set_video_scopes(self._h, None, 0, None))
+            self._scopes = (0, 0, False, 1)
+            return
+        pa = (PortRef * len(ports))(*[PortRef(int(n), int(p)) for (n, p) in ports])
+        pr = VideoScopeParams(int(wave_cols), 1 if vectorscope else 0, int(hop))
+        check(lib.mx_graph_set_video_scopes(self._h, pa, len(ports), C.byref(pr)))
+        self._scopes = (len(ports), int(wave_cols), bool(vectorscope), int(hop))
+
+    def read_video_scopes(self) -> list:
+        """the last run's records: a list over its recorded ticks of lists over the taps in set order of parse_video_scope_records dicts"""
+        n, wave_cols, vec, hop = getattr(self, "_scopes", (0, 0, False, 1))
+        rb = video_scope_record_bytes(wave_cols, vec)
+        raw = np.zeros(max(1, -(-self.max_ticks // hop)) * max(1, n) * rb, dtype=np.uint8)
+        got = C.c_uint32()
+        check(lib.mx_graph_read_video_scopes(self._h, raw.ctypes.data_as(C.c_void_p), raw.size, C.byref(got)))
+        recs = parse_video_scope_records(raw[: got.value * rb], wave_cols, vec)
+        return [recs[i:i + n] for i in range(0, len(recs), n)] if n else []
 
     def read_output_i16(self, node, port, n_ticks: int, stereo: bool, rate=(1, 1)) -> np.ndarray:
         out = np.empty(n_ticks * (self.spt * rate[0] // rate[1]) * (2 if stereo else 1), dtype=np.int16)

@@ -265,6 +265,52 @@ void mx_video_scaler_destroy(mx_video_scaler* sc) {
     (void)guard([&] { if (sc) { (void)hipStreamSynchronize(sc->stream); delete sc; } });
 }
 
+int mx_video_scope_record_bytes(const mx_video_scope_params* params, size_t* bytes) {   // host only: no device
+    return guard([&] {
+        REQUIRE(params && bytes, "NULL argument");
+        const uint32_t C = params->wave_cols;
+        REQUIRE(C == 0 || C == 64 || C == 128 || C == 256, "mx_video_scope_params: wave_cols must be 0, 64, 128 or 256");
+        *bytes = mx::scope_record_bytes(C, params->vectorscope);
+    });
+}
+int mx_video_scope(const mx_dframe* in, const mx_video_scope_params* params, void* device_record, void* stream) {
+    return guard([&] {
+        REQUIRE(in && params && device_record, "NULL argument");
+        REQUIRE(((uintptr_t)device_record & 3) == 0, "device_record must be 4-byte aligned");
+        const uint32_t C = params->wave_cols;
+        REQUIRE(C == 0 || C == 64 || C == 128 || C == 256, "mx_video_scope_params: wave_cols must be 0, 64, 128 or 256");
+        DFrame* d = const_cast<DFrame*>(D(in));
+        hipStream_t s = S(stream);
+        mx::ScopeArgs a{};
+        a.wave_cols = C; a.vectorscope = params->vectorscope;
+        a.present = 1;
+        a.pixfmt = (d->fmt == MX_PIXFMT_YUV420P && d->with_alpha) ? (uint32_t)MX_PIXFMT_YUVA420P : d->fmt;
+        a.width = d->width; a.height = d->height;
+        a.rec = static_cast<uint32_t*>(device_record);
+        if (d->fmt == MX_PIXFMT_YUV420P) {
+            d->ensure_pixels(s);
+            mx::flush_scales(s);
+            a.counted = 1;
+            a.y = d->data[0]; a.u = d->data[1]; a.v = d->data[2];
+            a.y_stride = d->stride[0]; a.u_stride = d->stride[1]; a.v_stride = d->stride[2];
+        }
+        // the workgroups ADD their counts: the record starts from zero, on the same stream
+        mx::hip_check(hipMemsetAsync(device_record, 0, mx::scope_record_bytes(C, params->vectorscope), s), "hipMemsetAsync(video scope record)");
+        mx::launch_video_scope(a, s);
+        mx::hip_check(hipGetLastError(), "video scope launch");
+    });
+}
+int mx_graph_set_video_scopes(mx_graph* g, const mx_port_ref* ports, size_t n, const mx_video_scope_params* params) {
+    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->set_video_scopes(ports, n, params); });
+}
+int mx_graph_read_video_scopes(mx_graph* g, void* dst, size_t cap_bytes, uint32_t* n_records) {
+    return guard([&] {
+        REQUIRE(g, "graph is NULL");
+        const size_t n = g->g->read_video_scopes(dst, cap_bytes);
+        if (n_records) *n_records = (uint32_t)n;
+    });
+}
+
 int mx_stream_retired(void* stream) {
     return guard([&] {
         REQUIRE(stream, "stream is NULL (the library's own default video stream is never retired)");

@@ -1062,7 +1062,7 @@ void Graph::run(uint64_t t0, size_t fpc, uint32_t n_calls, float* ms_by_kind, fl
     const size_t frames = fpc * (size_t)n_calls;
     auto drop_schedules = [&] { for (uint32_t id : sched_nodes_) { nodes_[id].sched.clear(); nodes_[id].gate_sched.clear(); } sched_nodes_.clear(); };
     if (frames > cap_frames_) { drop_schedules(); throw Error(MX_ERR_INVALID, "n_ticks exceeds max_ticks_per_run"); }
-    if (n_calls == 0 || fpc == 0) { drop_schedules(); last_calls_ = n_calls; last_frames_per_call_ = fpc; meter_run_ticks_ = spec_run_ticks_ = 0; return; }
+    if (n_calls == 0 || fpc == 0) { drop_schedules(); last_calls_ = n_calls; last_frames_per_call_ = fpc; meter_run_ticks_ = spec_run_ticks_ = 0; scope_n_ = 0; return; }
     hip_check(hipSetDevice(device_), "hipSetDevice");
     if (!meters_.empty() && fpc != meter_fpc_) { sync(); upload_meters(fpc); }   // (the module compat path's call length): frames per tick and record room
     if (!spectra_.empty() && fpc != spec_fpc_) { sync(); upload_spectra(fpc); }
@@ -1109,6 +1109,13 @@ void Graph::run(uint64_t t0, size_t fpc, uint32_t n_calls, float* ms_by_kind, fl
         if (cmax > n.od_cmax) { sync(); od_grow(n, cmax); }
     }
     for (uint32_t id : video_order_) if (nodes_[id].kind == MX_KIND_MONITOR) nodes_[id].mon_ticks.clear();
+    if (!scopes_.empty()) {   // scope taps: the records this run will count into are cleared now, in one fill on stream_ ahead of every launch of the run
+        const uint64_t hop = scope_par_.hop, first = (hop - scope_c_ % hop) % hop;   // the first recorded tick of the run
+        const size_t n_rec = first < n_calls ? (size_t)((n_calls - first + hop - 1) / hop) : 0;
+        if (n_rec > scope_cap_) throw Error(MX_ERR_INTERNAL, "video scopes: the run records more ticks than the taps were sized for");
+        if (n_rec) hip_check(hipMemsetAsync(scope_rec_.p, 0, n_rec * scopes_.size() * scope_rec_bytes_, stream_), "hipMemsetAsync(video scope records)");
+        scope_n_ = 0; scope_run_seen_ = true;
+    }
 
     // Plotter bookkeeping is host logic (plotter.rs:37-40): count += 1 per call, fire on every 6th
     size_t total_fired = 0;
@@ -1309,7 +1316,7 @@ void Graph::run_span(uint64_t t0, size_t fpc, uint32_t call_off, uint32_t n_call
     }
     // video sub-graph: tick by tick (frames arrive per tick; nothing to batch over time)
     if (has_video_) {
-        for (uint32_t c = 0; c < n_calls; ++c) run_video_tick(t0 + (uint64_t)c * fpc);
+        for (uint32_t c = 0; c < n_calls; ++c) { video_tick_in_run_ = call_off + c; run_video_tick(t0 + (uint64_t)c * fpc); }
         flush_scales(stream_);
         for (uint32_t id : video_order_) { Node& vn = nodes_[id]; if (!vn.rgba_pending.empty()) launch_pending_rgba(vn, vn.rgba_pending.size(), false); vn.rgba_calls = 0; }   // the last ticks' sinks
     }
@@ -1806,6 +1813,60 @@ void Graph::read_spectra(uint32_t first, uint32_t n, float* dst, size_t cap) {
     sync();
 }
 
+// ---- video scope taps (mixlab_gpu.h mx_graph_set_video_scopes) ----
+
+void Graph::set_video_scopes(const mx_port_ref* ports, size_t n, const mx_video_scope_params* params) {
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    if (n && (!ports || !params)) throw Error(MX_ERR_INVALID, "ports / params is NULL");
+    if (n > 0xffffffu) throw Error(MX_ERR_INVALID, "more than 2^24 video scope taps");
+    if (n) {
+        const uint32_t C = params->wave_cols;
+        if (C != 0 && C != 64 && C != 128 && C != 256) throw Error(MX_ERR_INVALID, "mx_video_scope_params: wave_cols must be 0, 64, 128 or 256");
+        if (params->hop == 0) throw Error(MX_ERR_INVALID, "mx_video_scope_params: hop must be >= 1");
+    }
+    std::vector<uint64_t> keys(n);
+    for (size_t i = 0; i < n; ++i) {
+        const mx_port_ref pr = ports[i];
+        if (pr.node >= nodes_.size() || pr.port >= nodes_[pr.node].out_type.size()) throw Error(MX_ERR_INVALID, "video scope: output terminal out of range");
+        if (nodes_[pr.node].out_type[pr.port] != MX_VIDEO) throw Error(MX_ERR_TYPE, "video scope: an audio port has no picture (meters and spectrum taps observe audio ports)");
+        keys[i] = (uint64_t)pr.node << 32 | pr.port;
+    }
+    std::sort(keys.begin(), keys.end());
+    if (std::adjacent_find(keys.begin(), keys.end()) != keys.end()) throw Error(MX_ERR_INVALID, "video scope: duplicate (node, port)");
+    size_t rec_bytes = 0, cap = 0;
+    if (n) {
+        rec_bytes = scope_record_bytes(params->wave_cols, params->vectorscope);
+        const size_t max_ticks = std::max<size_t>(1, cap_frames_ / spt_);
+        cap = (max_ticks + params->hop - 1) / params->hop;
+        const unsigned __int128 need = (unsigned __int128)cap * n * rec_bytes;
+        if (need > ((unsigned __int128)4 << 30))
+            throw Error(MX_ERR_NOMEM, "video scopes: the records of one run (ceil(max_ticks_per_run / hop) x taps x record bytes) exceed 4 GiB: raise hop");
+    }
+    sync();   // the last run's launches are done with the records
+    scopes_.assign(ports, ports + n);
+    scope_c_ = 0; scope_n_ = 0; scope_run_seen_ = false; scope_now_ = false;
+    scope_rec_.free_();
+    scope_rec_bytes_ = rec_bytes; scope_cap_ = cap;
+    if (scopes_.empty()) { scope_par_ = mx_video_scope_params{0, 0, 1}; return; }
+    scope_par_ = *params;
+    scope_rec_.alloc(cap * n * rec_bytes);
+}
+
+size_t Graph::read_video_scopes(void* dst, size_t cap_bytes) {
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    if (scopes_.empty()) throw Error(MX_ERR_INVALID, "no video scope taps are set");
+    if (!scope_run_seen_) throw Error(MX_ERR_INVALID, "no run since the video scope taps were set");
+    const size_t count = (size_t)scope_n_ * scopes_.size(), bytes = count * scope_rec_bytes_;
+    if (cap_bytes < bytes) throw Error(MX_ERR_INVALID, "cap_bytes is smaller than recorded ticks x taps x record bytes");
+    if (bytes && !dst) throw Error(MX_ERR_INVALID, "dst is NULL");
+    if (bytes) {
+        wait_tail(-1);
+        hip_check(hipMemcpyAsync(dst, scope_rec_.p, bytes, hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(D2H)");
+        sync();
+    }
+    return count;
+}
+
 void Graph::read_output_i16(uint32_t node, uint32_t port, int16_t* host, size_t frames) {
     hip_check(hipSetDevice(device_), "hipSetDevice");
     wait_tail(-1);
@@ -1874,6 +1935,8 @@ int Graph::read_plotter(uint32_t node, uint32_t call, float* left, float* right)
 // video sub-graph: one Engine::run_tick pass over the video nodes in run order
 // ---------------------------------------------------------------------------------------------
 void Graph::run_video_tick(uint64_t t) {
+    scope_now_ = false;
+    if (!scopes_.empty()) { scope_now_ = scope_c_ % scope_par_.hop == 0; ++scope_c_; }   // the hop counter: tested before the increment
     for (uint32_t id : video_order_) {
         Node& n = nodes_[id];
         switch (n.kind) {
@@ -2007,7 +2070,35 @@ void Graph::run_video_tick(uint64_t t) {
         }
         default: break;
         }
+        // scope taps on this node's ports: its vout is set, nothing downstream has run
+        if (scope_now_) for (uint32_t k = 0; k < (uint32_t)scopes_.size(); ++k) if (scopes_[k].node == id) launch_video_scope(k, n.vout[scopes_[k].port]);
     }
+    if (scope_now_) ++scope_n_;
+}
+
+// One tap's record of the tick being run.  Ordering: everything is on stream_ -- a graph with video nodes never runs anything on the second
+// stream (has_video_ excludes that mode), the run's fill of the records went out on stream_ before its first launch, a frame's producer
+// (a cross-fade, a scaler, a band scaler) launched on stream_ or is launched here (ensure_pixels, then the queued scaler jobs), and whoever
+// writes the frame's memory again is queued behind this launch.  A symbolic frame is materialised: the consumers downstream then read its
+// planes instead of re-evaluating the chain -- the same bytes, every cross-fade step truncates to u8 wherever it runs.
+void Graph::launch_video_scope(uint32_t tap, const Node::VOut& v) {
+    ScopeArgs a{};
+    a.wave_cols = scope_par_.wave_cols; a.vectorscope = scope_par_.vectorscope;
+    a.tick_in_run = video_tick_in_run_;
+    a.rec = reinterpret_cast<uint32_t*>((uint8_t*)scope_rec_.p + ((size_t)scope_n_ * scopes_.size() + tap) * scope_rec_bytes_);
+    if (DFrame* d = v.frame.f) {
+        a.present = 1;
+        a.pixfmt = (d->fmt == MX_PIXFMT_YUV420P && d->with_alpha) ? (uint32_t)MX_PIXFMT_YUVA420P : d->fmt;
+        a.width = d->width; a.height = d->height;
+        if (d->fmt == MX_PIXFMT_YUV420P) {
+            d->ensure_pixels(stream_);
+            flush_scales(stream_);   // a scaler output just asked for (or queued earlier in the tick) must be written before it is read
+            a.counted = 1;
+            a.y = d->data[0]; a.u = d->data[1]; a.v = d->data[2];
+            a.y_stride = d->stride[0]; a.u_stride = d->stride[1]; a.v_stride = d->stride[2];
+        }
+    }
+    mx::launch_video_scope(a, stream_);
 }
 
 void Graph::launch_pending_rgba(Node& n, size_t count, bool with_queued_scales) {

@@ -161,6 +161,9 @@ public:
     // spectrum taps (mx_graph_set_spectra / mx_graph_read_spectra): a windowed transform of every tap's last n_fft frames per tick, as band powers
     void set_spectra(const mx_port_ref* ports, size_t n, const mx_spectrum_params* params);
     void read_spectra(uint32_t first, uint32_t n, float* dst, size_t cap);
+    // video scope taps (mx_graph_set_video_scopes / mx_graph_read_video_scopes): histograms, waveform and vectorscope of the frames on video ports
+    void set_video_scopes(const mx_port_ref* ports, size_t n, const mx_video_scope_params* params);
+    size_t read_video_scopes(void* dst, size_t cap_bytes);   // the last run's records; returns how many
     void read_output_i16(uint32_t node, uint32_t port, int16_t* host, size_t frames);   // sink hand-off format
     void write_source_i16(uint32_t node, const int16_t* host, size_t frames);            // ingest format
     float* output_ptr(uint32_t node, uint32_t port, size_t* floats_per_tick, bool stream_ordered_consumer = true /* false: a caller inside the library that orders itself
@@ -213,6 +216,7 @@ private:
     void upload_group_one(Group& g, uint32_t parity);   // ... of one parity: desc / extra, or desc_alt / extra_alt
     void run_video_tick(uint64_t t);
     void launch_pending_rgba(Node& n, size_t count, bool with_queued_scales);   // the `count` oldest pending chains of a sink
+    void launch_video_scope(uint32_t tap, const Node::VOut& v);          // one tap's record of the tick being run (run_video_tick, on a recorded tick)
     // one launch sequence over ticks [call_off, call_off + n_calls) of the current run
     void run_span(uint64_t t0, size_t fpc, uint32_t call_off, uint32_t n_calls, uint32_t run_calls);
     void apply_params(uint32_t node, const void* params, size_t len);   // update_params without the synchronisation
@@ -302,6 +306,16 @@ private:
     DevBuf spec_desc_, spec_rec_, spec_hist_, spec_tab_;
     size_t spec_fpc_ = 0;
     uint32_t spec_run_ticks_ = 0;
+    // video scope taps: the taps in set order; scope_rec_: the last run's records [recorded tick][tap], scope_cap_ ticks of room.  scope_c_ is the
+    // hop counter (0 when the taps are set, +1 per video tick, carried across runs); a tick is recorded when scope_c_ % hop == 0 before the increment
+    std::vector<mx_port_ref> scopes_;
+    mx_video_scope_params scope_par_{0, 0, 1};
+    size_t scope_rec_bytes_ = 0, scope_cap_ = 0;
+    DevBuf scope_rec_;
+    uint64_t scope_c_ = 0;
+    uint32_t scope_n_ = 0;                  // recorded ticks of the run in progress / of the last run
+    uint32_t video_tick_in_run_ = 0;        // the tick run_video_tick is running, counted from the run's first
+    bool scope_now_ = false, scope_run_seen_ = false;   // the tick being run is recorded; a run was made since the taps were set
     float perf_od_ms_ = 0.f;                // OutputDevice launches of the last collected run
     bool prof_this_run_ = false;
     size_t plot_job_off_ = 0;

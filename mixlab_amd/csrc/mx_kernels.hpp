@@ -183,6 +183,19 @@ struct SpecRun {
 void launch_spectra(const SpecRun& r, hipStream_t s);   // k_spectrum, then k_spectrum_history
 // the tables of the spectrum spec, correctly rounded f32 (host only): window[n_fft], twiddle re / im [n_fft / 2]; false: n_fft is not a supported size
 bool spectrum_tables(uint32_t n_fft, float* window, float* twiddle_re, float* twiddle_im);
+// Video scope taps (mx_k_scope.hip, mixlab_gpu.h mx_graph_set_video_scopes): ONE launch counts one frame into one record -- the 32-byte
+// header, hist[3][256], wave[wave_cols][256], vec[128][128], all u32.  The counters of the record must be zero when the launch starts (the
+// workgroups add their partial counts with integer atomics); the kernel writes the header itself.  counted = 0: header only.
+struct ScopeArgs {
+    const uint8_t* y; const uint8_t* u; const uint8_t* v;   // planes of a counted frame: 16-byte aligned, strides multiples of 16
+    uint32_t y_stride, u_stride, v_stride;
+    uint32_t width, height;                  // luma size; the chroma planes are (width >> 1) x (height >> 1)
+    uint32_t wave_cols, vectorscope;         // mx_video_scope_params
+    uint32_t present, counted, pixfmt, tick_in_run;   // header words
+    uint32_t* rec;                           // the record (device)
+};
+inline size_t scope_record_bytes(uint32_t wave_cols, uint32_t vectorscope) { return 32 + 4 * ((size_t)768 + 256 * (size_t)wave_cols + (vectorscope ? 16384u : 0u)); }
+void launch_video_scope(const ScopeArgs& a, hipStream_t s);
 
 void launch_fir(const FirDesc* d, uint32_t n, uint32_t max_taps, size_t frames, hipStream_t s, bool fc = false);
 void launch_resample(const ResampleDesc* d, uint32_t n, uint32_t max_taps, uint32_t tab_doubles /* max up * taps_per_phase */,

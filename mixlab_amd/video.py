@@ -44,6 +44,7 @@ _proto("mx_video_scaler_destroy", None, C.c_void_p)
 _proto("mx_video_scale_geometry", C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
        C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32))
 _proto("mx_video_to_rgba", C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_void_p)
+_proto("mx_video_scope", C.c_int, C.c_void_p, C.POINTER(abi.VideoScopeParams), C.c_void_p, C.c_void_p)
 _proto("mx_video_sync", C.c_int, C.c_void_p)
 _proto("mx_stream_retired", C.c_int, C.c_void_p)
 _proto("mx_video_mixer_create", C.c_int, C.POINTER(VideoMixerParams), C.c_uint32, C.c_void_p, C.POINTER(C.c_void_p))
@@ -317,6 +318,16 @@ def to_rgba(f: DFrame, matrix_q12=None, stream=None, out: DeviceBuffer | None = 
     if not download:
         return buf
     return buf.download(stream).reshape(f.height, stride)[:, : f.width * 4].reshape(f.height, f.width, 4)
+
+
+def scope(f: DFrame, wave_cols: int = 0, vectorscope: bool = False, stream=None, out: DeviceBuffer | None = None, download=True):
+    """mx_video_scope: the scope record of one frame (histograms, waveform, vectorscope) -> abi.parse_video_scope_records' dict, or the
+    device buffer holding the raw record when download is False"""
+    buf = out or DeviceBuffer(abi.video_scope_record_bytes(wave_cols, vectorscope))
+    check(lib.mx_video_scope(f._h, C.byref(abi.VideoScopeParams(int(wave_cols), 1 if vectorscope else 0, 1)), buf.ptr, stream))
+    if not download:
+        return buf
+    return abi.parse_video_scope_records(buf.download(stream), wave_cols, vectorscope)[0]
 
 
 class VideoMixer:
