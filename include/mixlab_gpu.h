@@ -30,7 +30,8 @@ extern "C" {
                               *    later, without a bump (only additions): MX_KIND_OUTPUT_DEVICE, mx_graph_read_audio_out, mx_graph_audio_out_lag;
                               *    mx_port_ref, mx_meter_params, mx_meter_tick, mx_graph_set_meters, mx_graph_read_meters;
                               *    mx_spectrum_params, mx_graph_set_spectra, mx_graph_read_spectra, mx_spectrum_tables;
-                              *    mx_video_scope_params, mx_graph_set_video_scopes, mx_graph_read_video_scopes, mx_video_scope_record_bytes, mx_video_scope */
+                              *    mx_video_scope_params, mx_graph_set_video_scopes, mx_graph_read_video_scopes, mx_video_scope_record_bytes, mx_video_scope;
+                              *    mx_loudness_params, mx_loudness_tick, mx_graph_set_loudness, mx_graph_read_loudness, mx_loudness_tables, mx_loudness_gate */
 
 /* ---- status codes (0 ok, <0 error; cf. MIXLAB_IOCTX_ERROR / MIXLAB_IOCTX_PANIC) ---- */
 enum {
@@ -369,6 +370,71 @@ int mx_graph_read_spectra(mx_graph* g, uint32_t first_tick_in_run, uint32_t n_ti
 /* The tables of the spec for one n_fft: window[n_fft], twiddle_re[n_fft / 2], twiddle_im[n_fft / 2] (any of them may be NULL).  Host only:
  * touches no device and needs no graph.  Another n_fft: MX_ERR_INVALID. */
 int mx_spectrum_tables(uint32_t n_fft, float* window, float* twiddle_re, float* twiddle_im);
+
+/* Loudness taps on output ports of a built graph: per tick the K-weighted energy of ITU-R BS.1770-4 / EBU R 128 with its
+ * momentary and short-term window sums, and the true peak.  Like a meter, a tap observes a port: no module, no edge, the run order and the
+ * fusion plan unchanged; a graph without them launches nothing new.  Meters, spectrum taps and loudness taps are independent sets and may be
+ * set together.  Every run computes the records on the device, once per run after its last span.  The numbers are fixed bit for bit
+ * (tests/loudness_model.py restates them in numpy); every f64 operation is rounded on its own (no fused multiply-add):
+ *   biquads   computed on the host in f64 from the port's own rate (a Resample output has rate * up / down).  Shelf: f0 = 1681.974450955533,
+ *             G = 3.999843853973347 dB, Q = 0.7071752369554196; K = tan(pi f0 / rate), Vh = 10^(G / 20), Vb = Vh^0.4996667741545416,
+ *             a0 = 1 + K / Q + K^2; b0 = (Vh + Vb K / Q + K^2) / a0, b1 = 2 (K^2 - Vh) / a0, b2 = (Vh - Vb K / Q + K^2) / a0, a1 = 2 (K^2 - 1) / a0,
+ *             a2 = (1 - K / Q + K^2) / a0.  High-pass: f0 = 38.13547087602444, Q = 0.5003270373238773, the same K and denominator form;
+ *             b = (1, -2, 1), a1 = 2 (K^2 - 1) / a0, a2 = (1 - K / Q + K^2) / a0.  At 48 kHz these are BS.1770-4's printed tables.
+ *   filter    per channel on the widened f32 sample, shelf then high-pass, transposed direct form II: y = b0 x + s1; s1 = (b1 x - a1 y) + s2;
+ *             s2 = b2 x - a2 y.  The state S = (s1, s2 of the shelf, s1, s2 of the high-pass) is +0.0 when the taps are set and carried across
+ *             ticks and runs.
+ *   ticks     for tick k of F frames with start state S_k the outputs y[i] are the plain recurrence from S_k, but the next start state is
+ *             S_k+1 = Z_k + P S_k: Z_k is the end state of the same walk from the zero state and P = carry[4][4] what the host gets by
+ *             walking F zero samples from each unit state (column c: from unit state c).  Row r is evaluated as
+ *             ((P[r][0] S0 + P[r][1] S1) + P[r][2] S2) + P[r][3] S3, then Z[r] + that.  This makes the ticks of a run independent of each
+ *             other and the records independent of how ticks are grouped into runs; against the uninterrupted recurrence it moves ksq by
+ *             rounding only (DESIGN.md section 0.5 has the measured figure).
+ *   ksq       per channel 8 f64 partials: partial j adds y[i] * y[i] (the product rounded, then the sum) for i = j (mod 8) in ascending i
+ *             from +0.0; then s[j] = s[j] + s[j ^ m] for m = 4, 2, 1; the value is s[0].
+ *   windows   momentary_sq of tick t = the sum of (ksq[0] + ksq[1]) over ticks t - momentary_ticks + 1 .. t, added in ascending tick from
+ *             +0.0, every tick summed afresh; ticks before the set read +0.0; short_sq the same over short_ticks.  The last 1023 ticks are
+ *             carried across runs.  Loudness in LUFS = -0.691 + 10 log10(window sum / (window ticks x frames)).
+ *   true peak on the unweighted f32 samples: interp[p-1][j], p = 1 .. 3, j = 0 .. 11, is the f32 nearest to sinc(d) (0.5 + 0.5 cos(pi d / 6)),
+ *             d = j - 5 - p / 4, sinc(d) = sin(pi d) / (pi d); v_p[m] = (float) sum over j of (double)interp[p-1][j] * (double)x[m - 11 + j],
+ *             accumulated in ascending j in f64 from +0.0; true_peak = the integer maximum of bits & 0x7fffffff over x[m] and v_1..3[m] for
+ *             the tick's frames m, read as f32.  Frames before the set read +0.0; the last 11 frames are carried across ticks and runs.
+ * A mono port has channels = 1 and every [1] field 0.  A stereo port stored as one float per frame (the fused L == R strip result) gives both
+ * channels from that float, equal to MX_FLAG_NO_FUSE's records bit for bit.  Non-finite input propagates (NaN / Inf).
+ * Every call to mx_graph_set_loudness resets every tap: filter state, window history and interpolator history go to +0.0 (integration over a
+ * programme lives on the host: mx_loudness_gate).  One parameter set holds for every tap of the graph. */
+typedef struct { uint32_t momentary_ticks; uint32_t short_ticks; } mx_loudness_params;   /* each 1 .. 1024; 24 and 180 are 400 ms and 3 s at 60 ticks/s */
+typedef struct {
+    double   ksq[2];        /* K-weighted sum of squares of the tick, per channel */
+    double   momentary_sq;  /* window sum over the last momentary_ticks ticks of (ksq[0] + ksq[1]) */
+    double   short_sq;      /* the same over short_ticks */
+    float    true_peak[2];
+    uint32_t frames;
+    uint32_t channels;
+} mx_loudness_tick;   /* 48 bytes: ksq 0, momentary_sq 16, short_sq 24, true_peak 32, frames 40, channels 44 */
+/* Replaces the graph's loudness taps with ports[0..n) (n = 0: none; params may then be NULL and the graph launches nothing for them).
+ * Video port: MX_ERR_TYPE.  A node or port out of range, a duplicate (node, port), a port the fusion did not materialise, a window length
+ * outside 1 .. 1024, a port whose rate is not above twice the shelf frequency (3 364 Hz): MX_ERR_INVALID.  Waits for outstanding work like a
+ * read-back but keeps the automatic second-stream mode on.  Device memory: max_ticks_per_run x n x (48 bytes of records + 64 bytes of walk
+ * states) + per tap 64 bytes of filter state, 2 x 1023 doubles of window history, 2 x 22 floats of frame history and 208 bytes of coefficients.
+ * mx_graph_adopt_state does not carry taps: set them again on the new graph.  The launches count in the profile calls' ms_total only
+ * (MX_PROFILE_KINDS is unchanged).  The per-module path (mx_module_*) exposes no graph handle, so taps cannot be set there. */
+int mx_graph_set_loudness(mx_graph* g, const mx_port_ref* ports, size_t n, const mx_loudness_params* params);
+/* Ticks [first_tick_in_run, first_tick_in_run + n_ticks) of the last run, laid out [tick][tap] in set order; cap = records dst holds.
+ * A window beyond the last run (or a run made before the taps were set), cap < n_ticks x taps, or no taps: MX_ERR_INVALID.  Joins the
+ * graph's streams like mx_graph_read_output. */
+int mx_graph_read_loudness(mx_graph* g, uint32_t first_tick_in_run, uint32_t n_ticks, mx_loudness_tick* dst, size_t cap);
+/* The tables of the spec for one rate and tick length: biquads[10] (shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2), carry[16] (P[r][c] at
+ * 4 r + c), interp[36] (interp[p-1][j] at 12 (p - 1) + j); any of them may be NULL.  Host only: touches no device and needs no graph.  A rate
+ * that is not finite or not above 3 363.948901911066 (twice the shelf frequency), frames_per_tick outside 1 .. 4 194 304: MX_ERR_INVALID. */
+int mx_loudness_tables(double rate, uint32_t frames_per_tick, double* biquads, double* carry, float* interp);
+/* Gated integration (BS.1770-4) over n_blocks measurement blocks, in f64 on the host: block i has block_sq[i] (a momentary_sq) over
+ * block_frames[i] frames (momentary_ticks x frames) and loudness l_i = -0.691 + 10 log10(block_sq[i] / block_frames[i]).  Keep the blocks with
+ * l_i > -70; Gamma = -0.691 + 10 log10(mean of the kept blocks' mean squares) - 10; keep those of them that also have l_i > Gamma;
+ * *lufs_integrated = -0.691 + 10 log10 of their mean, or -inf with *blocks_kept = 0 when none is left (blocks_kept may be NULL).  Feed every
+ * hop-th tick's momentary_sq: six ticks at 60 ticks/s give the standard's 75 % overlap.  Host only.  A NULL array with n_blocks > 0, a NULL
+ * lufs_integrated or a block of 0 frames: MX_ERR_INVALID. */
+int mx_loudness_gate(const double* block_sq, const uint32_t* block_frames, size_t n_blocks, double* lufs_integrated, size_t* blocks_kept);
 
 /* Plotter indication (src/module/plotter.rs:37-56) for tick `tick_in_run` of the last run:
  * *fired = 1 and SPT floats in each of left/right when it fired (every 6th call, input connected). */

@@ -114,6 +114,13 @@ public:
     }
     // ticks [first, first + n) of the last run as [tick][tap][channel][band]
     void read_spectra(uint32_t first, uint32_t n, std::vector<float>& dst) { check(mx_graph_read_spectra(g_, first, n, dst.data(), dst.size())); }
+    // loudness taps (mx_graph_set_loudness): one pair of windows, in ticks, for every tap
+    void set_loudness(const std::vector<mx_port_ref>& ports, uint32_t momentary_ticks = 24, uint32_t short_ticks = 180) {
+        mx_loudness_params p{momentary_ticks, short_ticks};
+        check(mx_graph_set_loudness(g_, ports.data(), ports.size(), ports.empty() ? nullptr : &p));
+    }
+    // ticks [first, first + n) of the last run as [tick][tap]
+    void read_loudness(uint32_t first, uint32_t n, std::vector<mx_loudness_tick>& dst) { check(mx_graph_read_loudness(g_, first, n, dst.data(), dst.size())); }
     // video scope taps (mx_graph_set_video_scopes): one parameter set for every tap; an empty list removes them
     void set_video_scopes(const std::vector<mx_port_ref>& ports, const mx_video_scope_params& p) {
         check(mx_graph_set_video_scopes(g_, ports.data(), ports.size(), ports.empty() ? nullptr : &p));

@@ -169,6 +169,18 @@ class SpectrumParams(C.Structure):
 _proto("mx_graph_set_spectra", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 _proto("mx_graph_read_spectra", C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t)
 _proto("mx_spectrum_tables", C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p)
+class LoudnessParams(C.Structure):
+    """mx_loudness_params: the momentary and the short-term window in ticks (1 .. 1024 each; 24 and 180 are 400 ms and 3 s at 60 ticks/s)."""
+    _fields_ = [("momentary_ticks", C.c_uint32), ("short_ticks", C.c_uint32)]
+
+
+LOUDNESS_TICK_DTYPE = np.dtype({"names": ["ksq", "momentary_sq", "short_sq", "true_peak", "frames", "channels"],
+                                "formats": [(np.float64, 2), np.float64, np.float64, (np.float32, 2), np.uint32, np.uint32],
+                                "offsets": [0, 16, 24, 32, 40, 44], "itemsize": 48})   # mx_loudness_tick
+_proto("mx_graph_set_loudness", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
+_proto("mx_graph_read_loudness", C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t)
+_proto("mx_loudness_tables", C.c_int, C.c_double, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p)
+_proto("mx_loudness_gate", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_size_t))
 class VideoScopeParams(C.Structure):
     """mx_video_scope_params: waveform columns (0, 64, 128, 256), vectorscope on / off, record every hop-th video tick."""
     _fields_ = [("wave_cols", C.c_uint32), ("vectorscope", C.c_uint32), ("hop", C.c_uint32)]
@@ -215,6 +227,32 @@ def spectrum_tables(n_fft: int):
     w, re, im = np.zeros(n_fft, np.float32), np.zeros(n_fft // 2, np.float32), np.zeros(n_fft // 2, np.float32)
     check(lib.mx_spectrum_tables(n_fft, w.ctypes.data_as(C.c_void_p), re.ctypes.data_as(C.c_void_p), im.ctypes.data_as(C.c_void_p)))
     return w, re, im
+
+
+def loudness_tables(rate: float, frames_per_tick: int):
+    """(biquads float64[10]: shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2; carry float64[4, 4]; interp float32[3, 12]): the tables the
+    loudness kernels use for a port of that rate and tick length (host only, no device)"""
+    bq, carry, interp = np.zeros(10), np.zeros((4, 4)), np.zeros((3, 12), np.float32)
+    check(lib.mx_loudness_tables(float(rate), int(frames_per_tick), bq.ctypes.data_as(C.c_void_p), carry.ctypes.data_as(C.c_void_p),
+                                 interp.ctypes.data_as(C.c_void_p)))
+    return bq, carry, interp
+
+
+def lufs(sq, frames):
+    """loudness in LUFS of a K-weighted sum of squares over `frames` frames per channel (a record's momentary_sq over momentary_ticks x
+    frames, short_sq over short_ticks x frames, ksq[0] + ksq[1] over frames): -0.691 + 10 log10(sq / frames); silence reads -inf"""
+    with np.errstate(divide="ignore"):
+        return -0.691 + 10.0 * np.log10(np.asarray(sq, np.float64) / np.asarray(frames, np.float64))
+
+
+def loudness_gate(block_sq, block_frames):
+    """(integrated loudness in LUFS, blocks kept) of BS.1770-4's two-stage gating over measurement blocks (mx_loudness_gate, host only):
+    block_sq[i] is a momentary_sq, block_frames[i] (or one number for all) its frames; feed every 6th tick at 60 ticks/s"""
+    sq = np.ascontiguousarray(block_sq, np.float64)
+    fr = np.ascontiguousarray(np.broadcast_to(np.asarray(block_frames, np.uint32), sq.shape))
+    out, kept = C.c_double(), C.c_size_t()
+    check(lib.mx_loudness_gate(sq.ctypes.data_as(C.c_void_p), fr.ctypes.data_as(C.c_void_p), sq.size, C.byref(out), C.byref(kept)))
+    return out.value, kept.value
 
 
 def video_scope_record_bytes(wave_cols: int = 0, vectorscope: bool = False) -> int:
@@ -439,6 +477,27 @@ class Graph:
         n, b = getattr(self, "_spectra", (0, 0))
         out = np.zeros((n_ticks, n, 2, b), dtype=np.float32)
         check(lib.mx_graph_read_spectra(self._h, first_tick, n_ticks, out.ctypes.data_as(C.c_void_p), out.size))
+        return out
+
+    def set_loudness(self, ports, momentary_ticks: int = 24, short_ticks: int = 180):
+        """loudness taps on output ports [(node, port), ...]: every tick, the K-weighted sum of squares per channel, its sums over the
+        last momentary_ticks / short_ticks ticks and the true peak.  One window pair for every tap.  Each call starts every tap from
+        silence; [] removes them all."""
+        ports = list(ports)
+        if not ports:
+            check(lib.mx_graph_set_loudness(self._h, None, 0, None))
+            self._n_loudness = 0
+            return
+        pa = (PortRef * len(ports))(*[PortRef(int(n), int(p)) for (n, p) in ports])
+        check(lib.mx_graph_set_loudness(self._h, pa, len(ports), C.byref(LoudnessParams(int(momentary_ticks), int(short_ticks)))))
+        self._n_loudness = len(ports)
+
+    def read_loudness(self, first_tick: int, n_ticks: int) -> np.ndarray:
+        """ticks [first_tick, first_tick + n_ticks) of the last run: a LOUDNESS_TICK_DTYPE array shaped (n_ticks, taps) in set order;
+        lufs(rec["momentary_sq"], momentary_ticks * rec["frames"]) is the momentary loudness"""
+        n = getattr(self, "_n_loudness", 0)
+        out = np.zeros((n_ticks, n), dtype=LOUDNESS_TICK_DTYPE)
+        check(lib.mx_graph_read_loudness(self._h, first_tick, n_ticks, out.ctypes.data_as(C.c_void_p), out.size))
         return out
 
     def set_video_scopes(self, ports, wave_cols: int = 0, vectorscope: bool = False, hop: int = 1):

@@ -3,6 +3,7 @@
 // Convention (mirrors the reference's own FFI fencing, codec/src/ffmpeg/ioctx.rs:51-67,136-152):
 // nothing unwinds across the boundary; every entry point catches, stashes the message in a
 // thread-local, and returns a negative status.
+#include <cmath>
 #include <cstring>
 #include <memory>
 #include <string>
@@ -233,6 +234,45 @@ int mx_graph_read_spectra(mx_graph* g, uint32_t first_tick_in_run, uint32_t n_ti
 
 int mx_spectrum_tables(uint32_t n_fft, float* window, float* twiddle_re, float* twiddle_im) {   // host only: no device, no graph
     return guard([&] { REQUIRE(mx::spectrum_tables(n_fft, window, twiddle_re, twiddle_im), "n_fft must be 256, 512, 1024, 2048 or 4096"); });
+}
+
+int mx_graph_set_loudness(mx_graph* g, const mx_port_ref* ports, size_t n, const mx_loudness_params* params) {
+    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->set_loudness(ports, n, params); });
+}
+
+int mx_graph_read_loudness(mx_graph* g, uint32_t first_tick_in_run, uint32_t n_ticks, mx_loudness_tick* dst, size_t cap) {
+    static_assert(sizeof(mx_loudness_tick) == sizeof(mx::LoudTick) && sizeof(mx_loudness_tick) == 48, "mx_loudness_tick is the kernels' record");
+    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->read_loudness(first_tick_in_run, n_ticks, reinterpret_cast<mx::LoudTick*>(dst), cap); });
+}
+
+int mx_loudness_tables(double rate, uint32_t frames_per_tick, double* biquads, double* carry, float* interp) {   // host only: no device, no graph
+    return guard([&] { REQUIRE(mx::loudness_tables(rate, frames_per_tick, biquads, carry, interp), "rate must be finite and above twice the shelf frequency, frames_per_tick 1 .. 4 194 304"); });
+}
+
+int mx_loudness_gate(const double* block_sq, const uint32_t* block_frames, size_t n_blocks, double* lufs_integrated, size_t* blocks_kept) {   // host only
+    return guard([&] {
+        REQUIRE(lufs_integrated && (!n_blocks || (block_sq && block_frames)), "NULL argument");
+        for (size_t i = 0; i < n_blocks; ++i) REQUIRE(block_frames[i] > 0, "a block of 0 frames");
+        auto loudness = [](double mean_sq) { return -0.691 + 10.0 * std::log10(mean_sq); };
+        auto mean_of = [&](double above, size_t* kept) {   // mean of the mean squares of the blocks louder than both gates
+            double sum = 0.0; size_t k = 0;
+            for (size_t i = 0; i < n_blocks; ++i) {
+                const double z = block_sq[i] / (double)block_frames[i], l = loudness(z);
+                if (l > -70.0 && l > above) { sum += z; ++k; }
+            }
+            *kept = k;
+            return k ? sum / (double)k : 0.0;
+        };
+        size_t k = 0;
+        const double z_abs = mean_of(-HUGE_VAL, &k);
+        double result = -HUGE_VAL;
+        if (k) {
+            const double z_rel = mean_of(loudness(z_abs) - 10.0, &k);
+            if (k) result = loudness(z_rel);
+        }
+        *lufs_integrated = result;
+        if (blocks_kept) *blocks_kept = k;
+    });
 }
 
 int mx_graph_read_plotter(mx_graph* g, uint32_t node, uint32_t tick_in_run, float* left, float* right, int* fired) {

@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <map>
 
 namespace mx {
 
@@ -470,8 +471,9 @@ void Graph::flush_deferred_tail(bool gated) {
     deferred_.outs.clear();
     for (const MeterRun& r : deferred_.meters) launch_meters(r, tail_stream_);   // meters on the tail's outputs
     for (const SpecRun& r : deferred_.spectra) launch_spectra(r, tail_stream_);   // spectrum taps on the tail's outputs
-    if (prof && !(deferred_.meters.empty() && deferred_.spectra.empty())) hip_check(hipEventRecord(prof->meters_tail_end, tail_stream_), "hipEventRecord");
-    deferred_.meters.clear(); deferred_.spectra.clear();
+    for (const LoudRun& r : deferred_.loudness) launch_loudness(r, tail_stream_);   // loudness taps on the tail's outputs
+    if (prof && !(deferred_.meters.empty() && deferred_.spectra.empty() && deferred_.loudness.empty())) hip_check(hipEventRecord(prof->meters_tail_end, tail_stream_), "hipEventRecord");
+    deferred_.meters.clear(); deferred_.spectra.clear(); deferred_.loudness.clear();
     if (tail_hook_) { auto hook = std::move(tail_hook_); tail_hook_ = nullptr; hook(tail_stream_); }   // (mx_exchange: pack + exchange of that run's buses, behind the bank)
     // recorded AFTER the hook: whoever waits for this tail (wait_tail) is then also ordered behind the hook's reads of the buses on the tail stream -- a later run's Mixer on
     // stream_ must not overwrite them under a pack that is still copying
@@ -511,6 +513,7 @@ void Graph::end_auto_tail() {
     build_descriptors();
     if (!meters_.empty()) upload_meters(meter_fpc_);   // every tap on stream_, the first buffers only
     if (!spectra_.empty()) upload_spectra(spec_fpc_);
+    if (!loudness_.empty()) upload_loudness(loud_fpc_);
 }
 
 Graph::~Graph() {
@@ -1025,6 +1028,7 @@ void Graph::bind_source(uint32_t node, const void* dev) {
     build_descriptors();
     if (!meters_.empty()) upload_meters(meter_fpc_);
     if (!spectra_.empty()) upload_spectra(spec_fpc_);
+    if (!loudness_.empty()) upload_loudness(loud_fpc_);
 }
 
 void Graph::set_input_enabled(uint32_t node, uint32_t port, bool enabled) {
@@ -1054,6 +1058,7 @@ void Graph::ensure_capacity(size_t frames) {
     build_descriptors();
     if (!meters_.empty()) upload_meters(meter_fpc_);   // the ports moved; room for more ticks
     if (!spectra_.empty()) upload_spectra(spec_fpc_);
+    if (!loudness_.empty()) upload_loudness(loud_fpc_);
 }
 
 static bool group_launches(const Group& g);
@@ -1062,10 +1067,11 @@ void Graph::run(uint64_t t0, size_t fpc, uint32_t n_calls, float* ms_by_kind, fl
     const size_t frames = fpc * (size_t)n_calls;
     auto drop_schedules = [&] { for (uint32_t id : sched_nodes_) { nodes_[id].sched.clear(); nodes_[id].gate_sched.clear(); } sched_nodes_.clear(); };
     if (frames > cap_frames_) { drop_schedules(); throw Error(MX_ERR_INVALID, "n_ticks exceeds max_ticks_per_run"); }
-    if (n_calls == 0 || fpc == 0) { drop_schedules(); last_calls_ = n_calls; last_frames_per_call_ = fpc; meter_run_ticks_ = spec_run_ticks_ = 0; scope_n_ = 0; return; }
+    if (n_calls == 0 || fpc == 0) { drop_schedules(); last_calls_ = n_calls; last_frames_per_call_ = fpc; meter_run_ticks_ = spec_run_ticks_ = loud_run_ticks_ = 0; scope_n_ = 0; return; }
     hip_check(hipSetDevice(device_), "hipSetDevice");
     if (!meters_.empty() && fpc != meter_fpc_) { sync(); upload_meters(fpc); }   // (the module compat path's call length): frames per tick and record room
     if (!spectra_.empty() && fpc != spec_fpc_) { sync(); upload_spectra(fpc); }
+    if (!loudness_.empty() && fpc != loud_fpc_) { sync(); upload_loudness(fpc); }
 
     // ---- scheduled parameter updates (Engine::client_update between two ticks, src/engine.rs:192-214,277-398) ----
     // Trigger updates travel as one gate bit per tick and cost nothing.  Any other module's update cuts the run into spans:
@@ -1185,6 +1191,7 @@ void Graph::run(uint64_t t0, size_t fpc, uint32_t n_calls, float* ms_by_kind, fl
     last_frames_per_call_ = fpc;
     meter_run_ticks_ = meters_.empty() ? 0u : n_calls;
     spec_run_ticks_ = spectra_.empty() ? 0u : n_calls;
+    loud_run_ticks_ = loudness_.empty() ? 0u : n_calls;
     if (prof) ++prof_runs_count_;
     if (ms_by_kind) (void)profile_collect(ms_by_kind, ms_total);
 }
@@ -1271,7 +1278,7 @@ void Graph::run_span(uint64_t t0, size_t fpc, uint32_t call_off, uint32_t n_call
                 if ((int)gi == tail_gi_) {
                     if (deferred_.pending) flush_deferred_tail(false);   // (a run whose earlier groups had no speculative EqThree launch: nothing opened a gate)
                     hip_check(hipEventRecord(ev_head_done_, stream_), "hipEventRecord");
-                    deferred_.items.clear(); deferred_.outs.clear(); deferred_.meters.clear(); deferred_.spectra.clear(); deferred_.parity = parity_; deferred_.prof = prof;
+                    deferred_.items.clear(); deferred_.outs.clear(); deferred_.meters.clear(); deferred_.spectra.clear(); deferred_.loudness.clear(); deferred_.parity = parity_; deferred_.prof = prof;
                     if (prof) prof->tail_held = true;
                 }
                 deferred_.items.push_back(TailLaunch{desc_of(g), n, g.max_taps, gf, g.dup_mode, prof ? prof->group_end[gi] : nullptr});
@@ -1324,7 +1331,7 @@ void Graph::run_span(uint64_t t0, size_t fpc, uint32_t call_off, uint32_t n_call
     // after everything else of the span on stream_ (the video section included): its profile interval starts at the latest event recorded there
     launch_outputs(t0, call_off, n_calls, prof);
     // the port buffers hold every tick of the run: the meters go once, after its last span
-    if (call_off + n_calls == run_calls) { launch_meter_taps(run_calls, prof); launch_spectrum_taps(run_calls, prof); }
+    if (call_off + n_calls == run_calls) { launch_meter_taps(run_calls, prof); launch_spectrum_taps(run_calls, prof); launch_loudness_taps(run_calls, prof); }
     if (prof) { prof_runs_.push_back(std::move(prof_pool_.back())); prof_pool_.pop_back(); }
 }
 
@@ -1385,7 +1392,7 @@ uint32_t Graph::profile_collect(float* ms_by_kind, float* ms_total) {
         hipEvent_t end = last;
         if (p.od) { perf_od_ms_ += elapsed(last, p.od_end); end = p.od_end; }
         if (p.od_tail) perf_od_ms_ += elapsed(p.group_end.back(), p.od_tail_end);
-        // meter and spectrum launches: no kind of their own, counted in the total (and so in engine_us): on stream_ last of all, or on the tail stream
+        // meter, spectrum and loudness launches: no kind of their own, counted in the total (and so in engine_us): on stream_ last of all, or on the tail stream
         // behind the tail (and its OutputDevices)
         if (p.meters) end = p.meters_end;
         perf_total_ms_ = elapsed(p.begin, end);
@@ -1810,6 +1817,134 @@ void Graph::read_spectra(uint32_t first, uint32_t n, float* dst, size_t cap) {
     if (!count) return;
     wait_tail(-1);
     hip_check(hipMemcpyAsync(dst, (const float*)spec_rec_.p + (size_t)first * per_tick, count * sizeof(float), hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(D2H)");
+    sync();
+}
+
+// ---- loudness taps (mixlab_gpu.h mx_graph_set_loudness) ----
+
+void Graph::set_loudness(const mx_port_ref* ports, size_t n, const mx_loudness_params* params) {
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    if (n && (!ports || !params)) throw Error(MX_ERR_INVALID, "ports / params is NULL");
+    if (n > 0xffffffu) throw Error(MX_ERR_INVALID, "more than 2^24 loudness taps");
+    if (n) {
+        if (params->momentary_ticks < 1 || params->momentary_ticks > 1024) throw Error(MX_ERR_INVALID, "mx_loudness_params: momentary_ticks must be 1 .. 1024");
+        if (params->short_ticks < 1 || params->short_ticks > 1024) throw Error(MX_ERR_INVALID, "mx_loudness_params: short_ticks must be 1 .. 1024");
+    }
+    std::vector<uint64_t> keys(n);
+    for (size_t i = 0; i < n; ++i) {
+        const mx_port_ref pr = ports[i];
+        if (pr.node >= nodes_.size() || pr.port >= nodes_[pr.node].out_type.size()) throw Error(MX_ERR_INVALID, "loudness: output terminal out of range");
+        const Node& nd = nodes_[pr.node];
+        if (nd.out_type[pr.port] == MX_VIDEO) throw Error(MX_ERR_TYPE, "loudness: a video port has no loudness");
+        if (nd.out_elided[pr.port]) throw Error(MX_ERR_INVALID, "port is not materialised: it only feeds a fused consumer (build with MX_FLAG_NO_FUSE to observe it)");
+        if (!loudness_tables(sample_rate_ * nd.dom_num / nd.dom_den, 1, nullptr, nullptr, nullptr)) throw Error(MX_ERR_INVALID, "loudness: the port's rate is not above twice the shelf frequency (3 364 Hz)");
+        keys[i] = (uint64_t)pr.node << 32 | pr.port;
+    }
+    { std::vector<uint64_t> k = keys; std::sort(k.begin(), k.end()); if (std::adjacent_find(k.begin(), k.end()) != k.end()) throw Error(MX_ERR_INVALID, "loudness: duplicate (node, port)"); }
+    // like set_spectra: the last run's launches are done with the records and the carried state; the second-stream mode stays on
+    sync();
+    loudness_.assign(ports, ports + n);
+    loud_run_ticks_ = 0;
+    loud_hist_cur_ = 0;
+    loud_rec_.free_(); loud_walk_.free_();
+    if (loudness_.empty()) { loud_desc_.free_(); loud_tab_.free_(); loud_carry_.free_(); loud_par_ = mx_loudness_params{0, 0}; return; }
+    loud_par_ = *params;
+    // filter state, window history and interpolator history all start as +0.0: the stream before this call reads as silence
+    const size_t carry_bytes = n * (8 + 2 * (size_t)LOUD_HIST_TICKS) * sizeof(double) + 2 * n * 2 * LOUD_HIST_FRAMES * sizeof(float);
+    loud_carry_.alloc(carry_bytes);
+    hip_check(hipMemsetAsync(loud_carry_.p, 0, carry_bytes, stream_), "hipMemsetAsync(loudness state)");
+    hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
+    upload_loudness(loud_fpc_ ? loud_fpc_ : spt_);
+}
+
+// As upload_spectra: the descriptors of every tap for both buffer parities in launch order, room for a whole submission's records and walk
+// states, and -- what depends on the call length here -- each tap's coefficients: the biquads of its port's own rate and the carry matrix of
+// its tick length.  The stream is quiescent.  The carried state is untouched.
+void Graph::upload_loudness(size_t fpc) {
+    loud_fpc_ = fpc;
+    const size_t n = loudness_.size();
+    std::vector<uint32_t> order, tail;
+    for (uint32_t i = 0; i < (uint32_t)n; ++i) {
+        int32_t o = (int32_t)loudness_[i].node;
+        while (nodes_[o].elided && nodes_[o].owner >= 0) o = nodes_[o].owner;   // the node whose launch writes the port
+        (tail_gi_ >= 0 && nodes_[o].group >= tail_gi_ ? tail : order).push_back(i);
+    }
+    loud_n_head_ = (uint32_t)order.size();
+    order.insert(order.end(), tail.begin(), tail.end());
+    std::vector<LoudDesc> d(2 * n);
+    for (uint32_t par = 0; par < 2; ++par)
+        for (size_t k = 0; k < n; ++k) {
+            const mx_port_ref tp = loudness_[order[k]];
+            const Node& nd = nodes_[tp.node];
+            LoudDesc& m = d[par * n + k];
+            if (nd.bound && tp.port == 0) m.p = nd.bound;
+            else m.p = (const float*)slab_.p + (par && nd.out_off2[tp.port] != SIZE_MAX ? nd.out_off2[tp.port] : nd.out_off[tp.port]);
+            m.frames = (uint32_t)(fpc * nd.dom_num / nd.dom_den);
+            m.layout = nd.out_dup[tp.port] ? METER_DUP : (nd.out_type[tp.port] == MX_MONO ? METER_MONO : METER_STEREO);
+            m.slot = order[k]; m._pad = 0;
+        }
+    loud_desc_.alloc(d.size() * sizeof(LoudDesc));
+    hip_check(hipMemcpy(loud_desc_.p, d.data(), d.size() * sizeof(LoudDesc), hipMemcpyHostToDevice), "hipMemcpy(loudness descriptors)");
+    // LoudCoef[n] by slot | interp[36]; taps of one rate domain share one evaluation
+    std::vector<unsigned char> tab(n * sizeof(LoudCoef) + 36 * sizeof(float));
+    std::map<std::pair<uint32_t, uint32_t>, LoudCoef> by_dom;
+    for (size_t i = 0; i < n; ++i) {
+        const Node& nd = nodes_[loudness_[i].node];
+        auto it = by_dom.find({nd.dom_num, nd.dom_den});
+        if (it == by_dom.end()) {
+            LoudCoef c;
+            if (!loudness_tables(sample_rate_ * nd.dom_num / nd.dom_den, (uint32_t)(fpc * nd.dom_num / nd.dom_den), c.bq, c.carry, nullptr))
+                throw Error(MX_ERR_INVALID, "loudness: the call length gives a tick the taps cannot measure");
+            it = by_dom.emplace(std::make_pair(nd.dom_num, nd.dom_den), c).first;
+        }
+        memcpy(tab.data() + i * sizeof(LoudCoef), &it->second, sizeof(LoudCoef));
+    }
+    (void)loudness_tables(sample_rate_, 1, nullptr, nullptr, reinterpret_cast<float*>(tab.data() + n * sizeof(LoudCoef)));   // (the interpolator depends on neither)
+    loud_tab_.alloc(tab.size());
+    hip_check(hipMemcpy(loud_tab_.p, tab.data(), tab.size(), hipMemcpyHostToDevice), "hipMemcpy(loudness tables)");
+    loud_max_ticks_ = (uint32_t)std::max<size_t>(1, cap_frames_ / fpc);
+    const size_t need = (size_t)loud_max_ticks_ * n * sizeof(LoudTick), need_walk = (size_t)loud_max_ticks_ * n * 2 * 4 * sizeof(double);
+    if (!loud_rec_.p || loud_rec_.bytes < need) loud_rec_.alloc(need);
+    if (!loud_walk_.p || loud_walk_.bytes < need_walk) loud_walk_.alloc(need_walk);
+}
+
+// The run's loudness launches, after its last span and behind the spectrum taps.  launch_spectrum_taps's ordering argument holds word for
+// word: a tap read on stream_ is queued behind the run's producers through the descriptor of the run's buffer parity; a tap on an output of
+// the tail is held back with it (deferred_.loudness) and goes on the tail stream, covered by ev_tail_done_.  The three tap sets only read
+// the ports and write disjoint records.  The carried state follows the spectrum history's argument: a group's launches of consecutive runs
+// follow each other on that group's stream, the filter state is updated in place by the one lane that owns it, and each run reads the
+// history buffers the previous one wrote (loud_hist_cur_ flips once per run for both groups, whose slots are disjoint).
+void Graph::launch_loudness_taps(uint32_t n_calls, ProfSpan* prof) {
+    if (loudness_.empty()) return;
+    const uint32_t n = (uint32_t)loudness_.size();
+    double* state = (double*)loud_carry_.p;
+    double* eh = state + (size_t)n * 8;
+    float* xh = (float*)(eh + 2 * (size_t)n * LOUD_HIST_TICKS);
+    const uint32_t cur = loud_hist_cur_;
+    loud_hist_cur_ ^= 1u;
+    LoudRun all{(const LoudDesc*)loud_desc_.p + (size_t)(parity_ & 1u) * n, n, n_calls, n, loud_par_.momentary_ticks, loud_par_.short_ticks,
+                (const LoudCoef*)loud_tab_.p, (const float*)((const LoudCoef*)loud_tab_.p + n), state, (double*)loud_walk_.p, loud_max_ticks_,
+                eh + (size_t)cur * n * LOUD_HIST_TICKS, eh + (size_t)(cur ^ 1u) * n * LOUD_HIST_TICKS,
+                xh + (size_t)cur * n * 2 * LOUD_HIST_FRAMES, xh + (size_t)(cur ^ 1u) * n * 2 * LOUD_HIST_FRAMES, (LoudTick*)loud_rec_.p};
+    const uint32_t n_head = overlap_this_run_ ? loud_n_head_ : n;
+    if (n_head < n) { LoudRun t = all; t.desc = all.desc + n_head; t.n = n - n_head; deferred_.loudness.push_back(t); }
+    all.n = n_head;
+    if (n_head) launch_loudness(all, stream_);
+    if (!prof) return;
+    if (n_head) { hip_check(hipEventRecord(prof->meters_end, stream_), "hipEventRecord"); prof->meters = true; }   // (again, when meters or spectra recorded it: the later record holds)
+    prof->meters_tail = !(deferred_.meters.empty() && deferred_.spectra.empty() && deferred_.loudness.empty());
+}
+
+void Graph::read_loudness(uint32_t first, uint32_t n, LoudTick* dst, size_t cap) {
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    if (loudness_.empty()) throw Error(MX_ERR_INVALID, "no loudness taps are set");
+    if ((uint64_t)first + n > loud_run_ticks_) throw Error(MX_ERR_INVALID, "the window lies beyond the last run (or no run since the loudness taps were set)");
+    const size_t per_tick = loudness_.size(), count = (size_t)n * per_tick;
+    if (cap < count) throw Error(MX_ERR_INVALID, "cap is smaller than n_ticks x taps");
+    if (count && !dst) throw Error(MX_ERR_INVALID, "dst is NULL");
+    if (!count) return;
+    wait_tail(-1);
+    hip_check(hipMemcpyAsync(dst, (const LoudTick*)loud_rec_.p + (size_t)first * per_tick, count * sizeof(LoudTick), hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(D2H)");
     sync();
 }
 

@@ -161,6 +161,9 @@ public:
     // spectrum taps (mx_graph_set_spectra / mx_graph_read_spectra): a windowed transform of every tap's last n_fft frames per tick, as band powers
     void set_spectra(const mx_port_ref* ports, size_t n, const mx_spectrum_params* params);
     void read_spectra(uint32_t first, uint32_t n, float* dst, size_t cap);
+    // loudness taps (mx_graph_set_loudness / mx_graph_read_loudness): K-weighted energy, momentary / short-term window sums and true peak per tick
+    void set_loudness(const mx_port_ref* ports, size_t n, const mx_loudness_params* params);
+    void read_loudness(uint32_t first, uint32_t n, LoudTick* dst, size_t cap);
     // video scope taps (mx_graph_set_video_scopes / mx_graph_read_video_scopes): histograms, waveform and vectorscope of the frames on video ports
     void set_video_scopes(const mx_port_ref* ports, size_t n, const mx_video_scope_params* params);
     size_t read_video_scopes(void* dst, size_t cap_bytes);   // the last run's records; returns how many
@@ -229,6 +232,8 @@ private:
     void launch_meter_taps(uint32_t n_calls, ProfSpan* prof);           // the run's meter launches (after its last span)
     void upload_spectra(size_t fpc);                                     // the spectrum taps' descriptors (both parities) and record room, on a quiescent stream
     void launch_spectrum_taps(uint32_t n_calls, ProfSpan* prof);        // the run's spectrum launches (after its last span, behind the meters)
+    void upload_loudness(size_t fpc);                                    // the loudness taps' descriptors (both parities), coefficients and record room, on a quiescent stream
+    void launch_loudness_taps(uint32_t n_calls, ProfSpan* prof);        // the run's loudness launches (after its last span, behind the spectrum taps)
     void refresh_gates(Group& g, uint32_t run_calls);
     uint32_t trigger_of_row(const Group& g, uint32_t row) const;        // node id of the Trigger behind row `row` of a gated group, or ~0u
     void stage_upload(void* dst, const void* src, size_t bytes);         // H2D on the graph's stream through page-locked staging
@@ -268,7 +273,7 @@ private:
     // meters: the taps on the tail's outputs, behind those.  prof: the span's profile record (nullptr: not profiled), whose tail events the release records.
     struct TailLaunch { const void* desc = nullptr; uint32_t n = 0, max_ch = 0; size_t frames = 0; int dup_mode = 0; hipEvent_t prof_ev = nullptr; };
     struct DeferredTail { bool pending = false; std::vector<TailLaunch> items; uint32_t parity = 0; ProfSpan* prof = nullptr;
-                          std::vector<OutRun> outs; std::vector<MeterRun> meters; std::vector<SpecRun> spectra; } deferred_;   // spectra: spectrum taps on the tail's outputs, behind the meters
+                          std::vector<OutRun> outs; std::vector<MeterRun> meters; std::vector<SpecRun> spectra; std::vector<LoudRun> loudness; } deferred_;   // spectra, loudness: those taps on the tail's outputs, behind the meters
     std::function<void(hipStream_t)> tail_hook_;
     std::vector<hipEvent_t> head_waits_;
     uint64_t n_gated_ = 0, n_at_once_ = 0;
@@ -306,6 +311,16 @@ private:
     DevBuf spec_desc_, spec_rec_, spec_hist_, spec_tab_;
     size_t spec_fpc_ = 0;
     uint32_t spec_run_ticks_ = 0;
+    // loudness taps: the same arrangement again (set order, launch order, loud_n_head_, LoudDesc[2][n]).  loud_rec_: LoudTick[max ticks][n];
+    // loud_walk_: double[n][2][max ticks][4], the run's Z_k / S_k; loud_tab_: LoudCoef[n] by slot, then interp[36]; loud_carry_: what a run
+    // hands to the next -- state double[n][2][4] | window history double[2][n][1023] | frame history float[2][n][2][11], of which a run reads
+    // buffer loud_hist_cur_ and writes the other
+    std::vector<mx_port_ref> loudness_;
+    mx_loudness_params loud_par_{0, 0};
+    uint32_t loud_n_head_ = 0, loud_hist_cur_ = 0, loud_max_ticks_ = 0;
+    DevBuf loud_desc_, loud_rec_, loud_walk_, loud_tab_, loud_carry_;
+    size_t loud_fpc_ = 0;
+    uint32_t loud_run_ticks_ = 0;
     // video scope taps: the taps in set order; scope_rec_: the last run's records [recorded tick][tap], scope_cap_ ticks of room.  scope_c_ is the
     // hop counter (0 when the taps are set, +1 per video tick, carried across runs); a tick is recorded when scope_c_ % hop == 0 before the increment
     std::vector<mx_port_ref> scopes_;
@@ -334,7 +349,7 @@ private:
         std::vector<hipEvent_t> group_end;                              // per launch group, on the stream it ran on
         hipEvent_t video_end = nullptr, tail_begin = nullptr;           // the per-tick video section (stream_); a held-back tail's start (tail stream)
         hipEvent_t od_end = nullptr, od_tail_end = nullptr;             // OutputDevice launches on stream_ / behind the tail
-        hipEvent_t meters_end = nullptr, meters_tail_end = nullptr;     // meter and spectrum launches on stream_ / behind the tail (and its OutputDevices)
+        hipEvent_t meters_end = nullptr, meters_tail_end = nullptr;     // meter, spectrum and loudness launches on stream_ / behind the tail (and its OutputDevices)
         bool tail_held = false, od = false, od_tail = false, meters = false, meters_tail = false;
         explicit ProfSpan(size_t n_groups);
         ProfSpan(const ProfSpan&) = delete; ProfSpan& operator=(const ProfSpan&) = delete;

@@ -183,6 +183,30 @@ struct SpecRun {
 void launch_spectra(const SpecRun& r, hipStream_t s);   // k_spectrum, then k_spectrum_history
 // the tables of the spectrum spec, correctly rounded f32 (host only): window[n_fft], twiddle re / im [n_fft / 2]; false: n_fft is not a supported size
 bool spectrum_tables(uint32_t n_fft, float* window, float* twiddle_re, float* twiddle_im);
+// Loudness taps (mx_k_loudness.hip, mixlab_gpu.h mx_graph_set_loudness): one descriptor per tap and buffer parity, the per-tick record (=
+// mx_loudness_tick) and per tap (slot) the coefficients of its own rate domain.  Carried per tap: the filter state of each channel, the last
+// LOUD_HIST_TICKS ticks' ksq[0] + ksq[1] and the last LOUD_HIST_FRAMES frames of each channel; the two histories are kept twice and
+// alternate per run like the spectrum taps' (read by this run, written for the next).
+static constexpr uint32_t LOUD_HIST_TICKS = 1023, LOUD_HIST_FRAMES = 11, LOUD_MAX_FRAMES = 1u << 22;
+struct LoudDesc { const float* p; uint32_t frames, layout, slot, _pad; };   // as SpecDesc
+struct LoudTick { double ksq[2], momentary_sq, short_sq; float true_peak[2]; uint32_t frames, channels; };
+struct LoudCoef { double bq[10], carry[16]; };   // shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2; P[r][c] row-major
+struct LoudRun {
+    const LoudDesc* desc; uint32_t n;        // the launch's taps
+    uint32_t n_ticks, stride;                // ticks of the run; taps of the whole set (records per tick)
+    uint32_t momentary_ticks, short_ticks;
+    const LoudCoef* coef;                    // [slot]
+    const float* interp;                     // [3][12]
+    double* state;                           // [slot][channel][4]
+    double* walk; uint32_t walk_ticks;       // [slot][channel][walk_ticks][4]: Z_k of the run's ticks, then their start states S_k
+    const double* ehist_in; double* ehist_out;   // [slot][LOUD_HIST_TICKS]
+    const float* xhist_in; float* xhist_out;     // [slot][channel][LOUD_HIST_FRAMES]
+    LoudTick* rec;                           // rec[tick * stride + slot]
+};
+void launch_loudness(const LoudRun& r, hipStream_t s);   // k_loud_peak; k_loud_zero, k_loud_scan, k_loud_energy (a one-tick run: one interleaved walk); k_loud_window
+// the tables of the loudness spec (host only): biquads[10], carry[4][4] for a tick of `frames` frames, interp[3][12]; any may be null.
+// false: rate is not finite or not above twice the shelf frequency, or frames is outside 1 .. LOUD_MAX_FRAMES
+bool loudness_tables(double rate, uint32_t frames, double* biquads, double* carry, float* interp);
 // Video scope taps (mx_k_scope.hip, mixlab_gpu.h mx_graph_set_video_scopes): ONE launch counts one frame into one record -- the 32-byte
 // header, hist[3][256], wave[wave_cols][256], vec[128][128], all u32.  The counters of the record must be zero when the launch starts (the
 // workgroups add their partial counts with integer atomics); the kernel writes the header itself.  counted = 0: header only.
