@@ -31,7 +31,9 @@ extern "C" {
                               *    mx_port_ref, mx_meter_params, mx_meter_tick, mx_graph_set_meters, mx_graph_read_meters;
                               *    mx_spectrum_params, mx_graph_set_spectra, mx_graph_read_spectra, mx_spectrum_tables;
                               *    mx_video_scope_params, mx_graph_set_video_scopes, mx_graph_read_video_scopes, mx_video_scope_record_bytes, mx_video_scope;
-                              *    mx_loudness_params, mx_loudness_tick, mx_graph_set_loudness, mx_graph_read_loudness, mx_loudness_tables, mx_loudness_gate */
+                              *    mx_loudness_params, mx_loudness_tick, mx_graph_set_loudness, mx_graph_read_loudness, mx_loudness_tables, mx_loudness_gate;
+                              *    mx_stereo_params, mx_stereo_tick, mx_graph_set_stereo, mx_graph_read_stereo, mx_graph_read_goniometers, mx_stereo_gonio_record_bytes,
+                              *    mx_stereo_correlation */
 
 /* ---- status codes (0 ok, <0 error; cf. MIXLAB_IOCTX_ERROR / MIXLAB_IOCTX_PANIC) ---- */
 enum {
@@ -435,6 +437,69 @@ int mx_loudness_tables(double rate, uint32_t frames_per_tick, double* biquads, d
  * hop-th tick's momentary_sq: six ticks at 60 ticks/s give the standard's 75 % overlap.  Host only.  A NULL array with n_blocks > 0, a NULL
  * lufs_integrated or a block of 0 frames: MX_ERR_INVALID. */
 int mx_loudness_gate(const double* block_sq, const uint32_t* block_frames, size_t n_blocks, double* lufs_integrated, size_t* blocks_kept);
+
+/* Stereo field taps on STEREO output ports of a built graph: per tick the three sums behind the phase-correlation
+ * meter, balance and width, with their sums over a window of ticks, and -- with grid != 0 -- a goniometer, the audio counterpart of the
+ * vectorscope.  Like a meter, a tap observes a port: no module, no edge, the run order and the fusion plan unchanged; a graph without them
+ * launches nothing new.  Meters, spectrum, video scope, loudness and stereo field taps are independent sets and may be set together.  Every run
+ * computes the records on the device, once per run after its last span.  BUILD-SPECIFIED (the reference has no such instrument); the numbers
+ * are fixed bit for bit (tests/stereo_model.py restates them in numpy); every f64 operation is rounded on its own (no fused multiply-add).
+ * A port stored as one float per frame (the fused L == R strip result) reads as L = R = that float, equal to MX_FLAG_NO_FUSE's records bit for
+ * bit.  Frames are counted in the port's own rate domain, as for meters.
+ *   sum_xy    (xy = ll, rr, lr) the meters' order: 64 partials, partial j adds (double)x[f] * (double)y[f] (exact: 24 + 24 bits) over the
+ *             tick's frames f = j (mod 64) in ascending f from +0.0, one f64 rounding per add; then s[j] = s[j] + s[j ^ k] for k = 32, 16, 8,
+ *             4, 2, 1; the value is s[0].  sum_ll and sum_rr equal a meter's sum_sq[0] and sum_sq[1] on the same port bit for bit.
+ *             Non-finite input propagates into the sums.
+ *   win_xy    the sum of sum_xy over ticks t - window_ticks + 1 .. t, added in ascending tick from +0.0, every tick summed afresh (no running
+ *             sum: nothing drifts, and the grouping of ticks into runs cannot matter); ticks before the set read +0.0.  The last 1023 ticks
+ *             are carried across runs.
+ *   nonfinite frames of the tick whose L or R is NaN or +-Inf.
+ * Correlation, balance, mid and side energy are NOT in the record: they are quotients and roots of the six sums (mid / side energy =
+ * (ll + rr +- 2 lr) / 4); mx_stereo_correlation is the host-side helper for the first.
+ *   goniometer  present when grid != 0: a grid x grid table of uint32_t counts, grid 64 or 128.  For every frame with finite L and R:
+ *             m = L + R and s = L - R in f32, each rounded once; the cell of a value v is t = floorf(v * z), z = 2^zoom_log2 * grid / 4 (a
+ *             power of two: the product is exact), t = fminf(fmaxf(t, -grid / 2), grid / 2 - 1), index (int)t + grid / 2; the frame
+ *             increments gon[cell(m)][cell(s)].  zoom_log2 is 0 .. 8; at 0 the grid spans [-2, 2) on both axes.  An m or s that overflows
+ *             from finite L, R clamps to the edge like any large value.  A frame with a non-finite L or R is not plotted but counted in
+ *             `skipped`.  One counter c per graph: c = 0 and every grid zero when the taps are set; every tick adds its frames to the tap's
+ *             grid, then c += 1; when c mod hop == 0 one record per tap is emitted and the grids are cleared.  c and the partly filled grids
+ *             are carried across runs.  Counts are integers: the order of accumulation cannot matter.
+ *   record    32-byte header uint32_t { tick_in_run (the emitting tick), ticks (= hop), frames (plotted), skipped, grid, zoom_log2,
+ *             reserved[2] (0) }, then the table, row-major [cell(m)][cell(s)]: 32 + 4 grid^2 bytes (mx_stereo_gonio_record_bytes).
+ * With grid = 0 nothing is allocated or launched for the goniometer and hop is ignored.  One parameter set holds for every tap of the graph.
+ * Every call to mx_graph_set_stereo resets every tap and c. */
+typedef struct { uint32_t window_ticks /* 1 .. 1024 */, grid /* 0, 64 or 128 */, zoom_log2 /* 0 .. 8 */, hop /* >= 1 when grid != 0 */; } mx_stereo_params;
+typedef struct {
+    double   sum_ll;        /* this tick */
+    double   sum_rr;
+    double   sum_lr;
+    double   win_ll;        /* the last window_ticks ticks */
+    double   win_rr;
+    double   win_lr;
+    uint32_t frames;
+    uint32_t nonfinite;     /* frames of the tick whose L or R is NaN or +-Inf */
+} mx_stereo_tick;   /* 56 bytes: sum_ll 0, sum_rr 8, sum_lr 16, win_ll 24, win_rr 32, win_lr 40, frames 48, nonfinite 52 */
+/* Replaces the graph's stereo field taps with ports[0..n) (n = 0: none; params may then be NULL and the graph launches nothing for them).
+ * Video or mono port: MX_ERR_TYPE.  A node or port out of range, a duplicate (node, port), a port the fusion did not materialise,
+ * window_ticks outside 1 .. 1024, a grid other than 0, 64, 128, zoom_log2 > 8, hop = 0 with grid != 0: MX_ERR_INVALID.  Goniometer records
+ * of one run (ceil(max_ticks_per_run / hop) x n x record bytes) beyond 4 GiB: MX_ERR_NOMEM (raise hop).  Waits for outstanding work like a
+ * read-back but keeps the automatic second-stream mode on.  Device memory: max_ticks_per_run x n x 56 bytes of records, per tap 2 x 1023 x 3
+ * doubles of window history, and with a goniometer one record per tap of carried grid plus the run's records.  mx_graph_adopt_state does not
+ * carry taps: set them again on the new graph.  The launches count in the profile calls' ms_total only (MX_PROFILE_KINDS is unchanged). */
+int mx_graph_set_stereo(mx_graph* g, const mx_port_ref* ports, size_t n, const mx_stereo_params* params);
+/* Ticks [first_tick_in_run, first_tick_in_run + n_ticks) of the last run, laid out [tick][tap] in set order; cap = records dst holds.
+ * A window beyond the last run (or a run made before the taps were set), cap < n_ticks x taps, or no taps: MX_ERR_INVALID.  Joins the
+ * graph's streams like mx_graph_read_output. */
+int mx_graph_read_stereo(mx_graph* g, uint32_t first_tick_in_run, uint32_t n_ticks, mx_stereo_tick* dst, size_t cap);
+/* The goniometer records the last run emitted, [emission][tap in set order], mx_stereo_gonio_record_bytes each; *n_records = emissions x taps
+ * (0 when the run emitted none; n_records may be NULL).  No taps, taps set with grid = 0, no run since the taps were set, or cap_bytes too
+ * small: MX_ERR_INVALID.  Joins the graph's streams like mx_graph_read_output. */
+int mx_graph_read_goniometers(mx_graph* g, void* dst, size_t cap_bytes, uint32_t* n_records);
+/* Bytes of one goniometer record: 32 + 4 grid^2 (32 with grid = 0).  Host only.  A grid other than 0, 64, 128 or a NULL argument: MX_ERR_INVALID. */
+int mx_stereo_gonio_record_bytes(const mx_stereo_params* params, size_t* bytes);
+/* *r = lr / sqrt(ll * rr) in f64, clamped to [-1, 1]; 0.0 when ll * rr is not a positive finite number (silence on one side reads 0, not NaN)
+ * or the quotient is NaN.  Feed a record's sums or its window sums.  Host only: touches no device and needs no graph.  NULL r: MX_ERR_INVALID. */
+int mx_stereo_correlation(double ll, double rr, double lr, double* r);
 
 /* Plotter indication (src/module/plotter.rs:37-56) for tick `tick_in_run` of the last run:
  * *fired = 1 and SPT floats in each of left/right when it fired (every 6th call, input connected). */

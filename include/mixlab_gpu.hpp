@@ -121,6 +121,14 @@ public:
     }
     // ticks [first, first + n) of the last run as [tick][tap]
     void read_loudness(uint32_t first, uint32_t n, std::vector<mx_loudness_tick>& dst) { check(mx_graph_read_loudness(g_, first, n, dst.data(), dst.size())); }
+    // stereo field taps (mx_graph_set_stereo): one parameter set for every tap; an empty list removes them
+    void set_stereo(const std::vector<mx_port_ref>& ports, const mx_stereo_params& p) {
+        check(mx_graph_set_stereo(g_, ports.data(), ports.size(), ports.empty() ? nullptr : &p));
+    }
+    // ticks [first, first + n) of the last run as [tick][tap]
+    void read_stereo(uint32_t first, uint32_t n, std::vector<mx_stereo_tick>& dst) { check(mx_graph_read_stereo(g_, first, n, dst.data(), dst.size())); }
+    // the goniometer records the last run emitted, [emission][tap], mx_stereo_gonio_record_bytes each; returns how many
+    uint32_t read_goniometers(std::vector<unsigned char>& dst) { uint32_t n = 0; check(mx_graph_read_goniometers(g_, dst.data(), dst.size(), &n)); return n; }
     // video scope taps (mx_graph_set_video_scopes): one parameter set for every tap; an empty list removes them
     void set_video_scopes(const std::vector<mx_port_ref>& ports, const mx_video_scope_params& p) {
         check(mx_graph_set_video_scopes(g_, ports.data(), ports.size(), ports.empty() ? nullptr : &p));

@@ -181,6 +181,19 @@ _proto("mx_graph_set_loudness", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c
 _proto("mx_graph_read_loudness", C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t)
 _proto("mx_loudness_tables", C.c_int, C.c_double, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p)
 _proto("mx_loudness_gate", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_size_t))
+class StereoParams(C.Structure):
+    """mx_stereo_params: the window in ticks (1 .. 1024), the goniometer's grid (0: none, 64, 128), its zoom (0 .. 8) and emission period."""
+    _fields_ = [("window_ticks", C.c_uint32), ("grid", C.c_uint32), ("zoom_log2", C.c_uint32), ("hop", C.c_uint32)]
+
+
+STEREO_TICK_DTYPE = np.dtype({"names": ["sum_ll", "sum_rr", "sum_lr", "win_ll", "win_rr", "win_lr", "frames", "nonfinite"],
+                              "formats": [np.float64] * 6 + [np.uint32] * 2,
+                              "offsets": [0, 8, 16, 24, 32, 40, 48, 52], "itemsize": 56})   # mx_stereo_tick
+_proto("mx_graph_set_stereo", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
+_proto("mx_graph_read_stereo", C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t)
+_proto("mx_graph_read_goniometers", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32))
+_proto("mx_stereo_gonio_record_bytes", C.c_int, C.POINTER(StereoParams), C.POINTER(C.c_size_t))
+_proto("mx_stereo_correlation", C.c_int, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double))
 class VideoScopeParams(C.Structure):
     """mx_video_scope_params: waveform columns (0, 64, 128, 256), vectorscope on / off, record every hop-th video tick."""
     _fields_ = [("wave_cols", C.c_uint32), ("vectorscope", C.c_uint32), ("hop", C.c_uint32)]
@@ -253,6 +266,34 @@ def loudness_gate(block_sq, block_frames):
     out, kept = C.c_double(), C.c_size_t()
     check(lib.mx_loudness_gate(sq.ctypes.data_as(C.c_void_p), fr.ctypes.data_as(C.c_void_p), sq.size, C.byref(out), C.byref(kept)))
     return out.value, kept.value
+
+
+def stereo_gonio_record_bytes(grid: int) -> int:
+    """bytes of one goniometer record: 32 + 4 * grid * grid (host only, no device)"""
+    n = C.c_size_t()
+    check(lib.mx_stereo_gonio_record_bytes(C.byref(StereoParams(1, int(grid), 0, 1)), C.byref(n)))
+    return n.value
+
+
+def stereo_correlation(ll: float, rr: float, lr: float) -> float:
+    """phase correlation lr / sqrt(ll * rr) of a record's sums or window sums, clamped to [-1, 1]; 0.0 when ll * rr is not a positive finite
+    number (mx_stereo_correlation, host only)"""
+    r = C.c_double()
+    check(lib.mx_stereo_correlation(float(ll), float(rr), float(lr), C.byref(r)))
+    return r.value
+
+
+def parse_goniometer_records(raw: np.ndarray, grid: int) -> list:
+    """raw bytes of back-to-back goniometer records -> one dict per record: the header fields as ints and gon [grid, grid] uint32, indexed
+    [cell(L + R), cell(L - R)]"""
+    r = np.ascontiguousarray(raw).view(np.uint32).reshape(-1, 8 + grid * grid)
+    out = []
+    for w in r:
+        d = dict(zip(("tick_in_run", "ticks", "frames", "skipped", "grid", "zoom_log2"), (int(x) for x in w[:6])))
+        d["reserved"] = (int(w[6]), int(w[7]))
+        d["gon"] = w[8:].reshape(grid, grid)
+        out.append(d)
+    return out
 
 
 def video_scope_record_bytes(wave_cols: int = 0, vectorscope: bool = False) -> int:
@@ -499,6 +540,38 @@ class Graph:
         out = np.zeros((n_ticks, n), dtype=LOUDNESS_TICK_DTYPE)
         check(lib.mx_graph_read_loudness(self._h, first_tick, n_ticks, out.ctypes.data_as(C.c_void_p), out.size))
         return out
+
+    def set_stereo(self, ports, window_ticks: int = 180, grid: int = 0, zoom_log2: int = 0, hop: int = 1):
+        """stereo field taps on stereo output ports [(node, port), ...]: every tick, the sums of L L, R R and L R and their sums over the last
+        window_ticks ticks; with grid 64 or 128 a goniometer whose grid is emitted and cleared every hop ticks.  One parameter set for every
+        tap.  Each call resets every tap and the hop counter; [] removes them all."""
+        ports = list(ports)
+        if not ports:
+            check(lib.mx_graph_set_stereo(self._h, None, 0, None))
+            self._stereo = (0, 0, 1)
+            return
+        pa = (PortRef * len(ports))(*[PortRef(int(n), int(p)) for (n, p) in ports])
+        check(lib.mx_graph_set_stereo(self._h, pa, len(ports), C.byref(StereoParams(int(window_ticks), int(grid), int(zoom_log2), int(hop)))))
+        self._stereo = (len(ports), int(grid), max(1, int(hop)))
+
+    def read_stereo(self, first_tick: int, n_ticks: int) -> np.ndarray:
+        """ticks [first_tick, first_tick + n_ticks) of the last run: a STEREO_TICK_DTYPE array shaped (n_ticks, taps) in set order;
+        stereo_correlation(rec["win_ll"], rec["win_rr"], rec["win_lr"]) is the correlation meter's reading"""
+        n = getattr(self, "_stereo", (0, 0, 1))[0]
+        out = np.zeros((n_ticks, n), dtype=STEREO_TICK_DTYPE)
+        check(lib.mx_graph_read_stereo(self._h, first_tick, n_ticks, out.ctypes.data_as(C.c_void_p), out.size))
+        return out
+
+    def read_goniometers(self) -> list:
+        """the goniometer records the last run emitted: a list over its emissions of lists over the taps in set order of
+        parse_goniometer_records dicts"""
+        n, grid, hop = getattr(self, "_stereo", (0, 0, 1))
+        rb = 32 + 4 * grid * grid
+        raw = np.zeros(max(1, -(-self.max_ticks // hop)) * max(1, n) * rb, dtype=np.uint8)
+        got = C.c_uint32()
+        check(lib.mx_graph_read_goniometers(self._h, raw.ctypes.data_as(C.c_void_p), raw.size, C.byref(got)))
+        recs = parse_goniometer_records(raw[: got.value * rb], grid)
+        return [recs[i:i + n] for i in range(0, len(recs), n)] if n else []
 
     def set_video_scopes(self, ports, wave_cols: int = 0, vectorscope: bool = False, hop: int = 1):
         """video scope taps on video output ports [(node, port), ...]: on every hop-th video tick, the luma / U / V histograms, the

@@ -275,6 +275,41 @@ int mx_loudness_gate(const double* block_sq, const uint32_t* block_frames, size_
     });
 }
 
+int mx_graph_set_stereo(mx_graph* g, const mx_port_ref* ports, size_t n, const mx_stereo_params* params) {
+    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->set_stereo(ports, n, params); });
+}
+
+int mx_graph_read_stereo(mx_graph* g, uint32_t first_tick_in_run, uint32_t n_ticks, mx_stereo_tick* dst, size_t cap) {
+    static_assert(sizeof(mx_stereo_tick) == sizeof(mx::StereoTick) && sizeof(mx_stereo_tick) == 56, "mx_stereo_tick is the kernels' record");
+    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->read_stereo(first_tick_in_run, n_ticks, reinterpret_cast<mx::StereoTick*>(dst), cap); });
+}
+
+int mx_graph_read_goniometers(mx_graph* g, void* dst, size_t cap_bytes, uint32_t* n_records) {
+    return guard([&] { REQUIRE(g, "graph is NULL"); const size_t n = g->g->read_goniometers(dst, cap_bytes); if (n_records) *n_records = (uint32_t)n; });
+}
+
+int mx_stereo_gonio_record_bytes(const mx_stereo_params* params, size_t* bytes) {   // host only: no device, no graph
+    return guard([&] {
+        REQUIRE(params && bytes, "NULL argument");
+        REQUIRE(params->grid == 0 || params->grid == 64 || params->grid == 128, "mx_stereo_params: grid must be 0, 64 or 128");
+        *bytes = mx::stereo_gonio_record_bytes(params->grid);
+    });
+}
+
+int mx_stereo_correlation(double ll, double rr, double lr, double* r) {   // host only
+    return guard([&] {
+        REQUIRE(r, "r is NULL");
+        const double p = ll * rr;
+        double v = 0.0;
+        if (p > 0.0 && std::isfinite(p)) {
+            v = lr / std::sqrt(p);
+            v = v < -1.0 ? -1.0 : (v > 1.0 ? 1.0 : v);
+            if (!(v == v)) v = 0.0;   // (a NaN lr under finite energies: the helper never answers NaN)
+        }
+        *r = v;
+    });
+}
+
 int mx_graph_read_plotter(mx_graph* g, uint32_t node, uint32_t tick_in_run, float* left, float* right, int* fired) {
     return guard([&] {
         REQUIRE(g && left && right && fired, "NULL argument");

@@ -472,8 +472,9 @@ void Graph::flush_deferred_tail(bool gated) {
     for (const MeterRun& r : deferred_.meters) launch_meters(r, tail_stream_);   // meters on the tail's outputs
     for (const SpecRun& r : deferred_.spectra) launch_spectra(r, tail_stream_);   // spectrum taps on the tail's outputs
     for (const LoudRun& r : deferred_.loudness) launch_loudness(r, tail_stream_);   // loudness taps on the tail's outputs
-    if (prof && !(deferred_.meters.empty() && deferred_.spectra.empty() && deferred_.loudness.empty())) hip_check(hipEventRecord(prof->meters_tail_end, tail_stream_), "hipEventRecord");
-    deferred_.meters.clear(); deferred_.spectra.clear(); deferred_.loudness.clear();
+    for (const StereoRun& r : deferred_.stereo) launch_stereo(r, tail_stream_);   // stereo field taps on the tail's outputs
+    if (prof && !(deferred_.meters.empty() && deferred_.spectra.empty() && deferred_.loudness.empty() && deferred_.stereo.empty())) hip_check(hipEventRecord(prof->meters_tail_end, tail_stream_), "hipEventRecord");
+    deferred_.meters.clear(); deferred_.spectra.clear(); deferred_.loudness.clear(); deferred_.stereo.clear();
     if (tail_hook_) { auto hook = std::move(tail_hook_); tail_hook_ = nullptr; hook(tail_stream_); }   // (mx_exchange: pack + exchange of that run's buses, behind the bank)
     // recorded AFTER the hook: whoever waits for this tail (wait_tail) is then also ordered behind the hook's reads of the buses on the tail stream -- a later run's Mixer on
     // stream_ must not overwrite them under a pack that is still copying
@@ -514,6 +515,7 @@ void Graph::end_auto_tail() {
     if (!meters_.empty()) upload_meters(meter_fpc_);   // every tap on stream_, the first buffers only
     if (!spectra_.empty()) upload_spectra(spec_fpc_);
     if (!loudness_.empty()) upload_loudness(loud_fpc_);
+    if (!stereo_.empty()) upload_stereo(stereo_fpc_);
 }
 
 Graph::~Graph() {
@@ -1029,6 +1031,7 @@ void Graph::bind_source(uint32_t node, const void* dev) {
     if (!meters_.empty()) upload_meters(meter_fpc_);
     if (!spectra_.empty()) upload_spectra(spec_fpc_);
     if (!loudness_.empty()) upload_loudness(loud_fpc_);
+    if (!stereo_.empty()) upload_stereo(stereo_fpc_);
 }
 
 void Graph::set_input_enabled(uint32_t node, uint32_t port, bool enabled) {
@@ -1059,6 +1062,7 @@ void Graph::ensure_capacity(size_t frames) {
     if (!meters_.empty()) upload_meters(meter_fpc_);   // the ports moved; room for more ticks
     if (!spectra_.empty()) upload_spectra(spec_fpc_);
     if (!loudness_.empty()) upload_loudness(loud_fpc_);
+    if (!stereo_.empty()) upload_stereo(stereo_fpc_);
 }
 
 static bool group_launches(const Group& g);
@@ -1067,11 +1071,12 @@ void Graph::run(uint64_t t0, size_t fpc, uint32_t n_calls, float* ms_by_kind, fl
     const size_t frames = fpc * (size_t)n_calls;
     auto drop_schedules = [&] { for (uint32_t id : sched_nodes_) { nodes_[id].sched.clear(); nodes_[id].gate_sched.clear(); } sched_nodes_.clear(); };
     if (frames > cap_frames_) { drop_schedules(); throw Error(MX_ERR_INVALID, "n_ticks exceeds max_ticks_per_run"); }
-    if (n_calls == 0 || fpc == 0) { drop_schedules(); last_calls_ = n_calls; last_frames_per_call_ = fpc; meter_run_ticks_ = spec_run_ticks_ = loud_run_ticks_ = 0; scope_n_ = 0; return; }
+    if (n_calls == 0 || fpc == 0) { drop_schedules(); last_calls_ = n_calls; last_frames_per_call_ = fpc; meter_run_ticks_ = spec_run_ticks_ = loud_run_ticks_ = stereo_run_ticks_ = 0; stereo_gon_n_ = 0; scope_n_ = 0; return; }
     hip_check(hipSetDevice(device_), "hipSetDevice");
     if (!meters_.empty() && fpc != meter_fpc_) { sync(); upload_meters(fpc); }   // (the module compat path's call length): frames per tick and record room
     if (!spectra_.empty() && fpc != spec_fpc_) { sync(); upload_spectra(fpc); }
     if (!loudness_.empty() && fpc != loud_fpc_) { sync(); upload_loudness(fpc); }
+    if (!stereo_.empty() && fpc != stereo_fpc_) { sync(); upload_stereo(fpc); }
 
     // ---- scheduled parameter updates (Engine::client_update between two ticks, src/engine.rs:192-214,277-398) ----
     // Trigger updates travel as one gate bit per tick and cost nothing.  Any other module's update cuts the run into spans:
@@ -1192,6 +1197,7 @@ void Graph::run(uint64_t t0, size_t fpc, uint32_t n_calls, float* ms_by_kind, fl
     meter_run_ticks_ = meters_.empty() ? 0u : n_calls;
     spec_run_ticks_ = spectra_.empty() ? 0u : n_calls;
     loud_run_ticks_ = loudness_.empty() ? 0u : n_calls;
+    stereo_run_ticks_ = stereo_.empty() ? 0u : n_calls;
     if (prof) ++prof_runs_count_;
     if (ms_by_kind) (void)profile_collect(ms_by_kind, ms_total);
 }
@@ -1278,7 +1284,7 @@ void Graph::run_span(uint64_t t0, size_t fpc, uint32_t call_off, uint32_t n_call
                 if ((int)gi == tail_gi_) {
                     if (deferred_.pending) flush_deferred_tail(false);   // (a run whose earlier groups had no speculative EqThree launch: nothing opened a gate)
                     hip_check(hipEventRecord(ev_head_done_, stream_), "hipEventRecord");
-                    deferred_.items.clear(); deferred_.outs.clear(); deferred_.meters.clear(); deferred_.spectra.clear(); deferred_.loudness.clear(); deferred_.parity = parity_; deferred_.prof = prof;
+                    deferred_.items.clear(); deferred_.outs.clear(); deferred_.meters.clear(); deferred_.spectra.clear(); deferred_.loudness.clear(); deferred_.stereo.clear(); deferred_.parity = parity_; deferred_.prof = prof;
                     if (prof) prof->tail_held = true;
                 }
                 deferred_.items.push_back(TailLaunch{desc_of(g), n, g.max_taps, gf, g.dup_mode, prof ? prof->group_end[gi] : nullptr});
@@ -1331,7 +1337,7 @@ void Graph::run_span(uint64_t t0, size_t fpc, uint32_t call_off, uint32_t n_call
     // after everything else of the span on stream_ (the video section included): its profile interval starts at the latest event recorded there
     launch_outputs(t0, call_off, n_calls, prof);
     // the port buffers hold every tick of the run: the meters go once, after its last span
-    if (call_off + n_calls == run_calls) { launch_meter_taps(run_calls, prof); launch_spectrum_taps(run_calls, prof); launch_loudness_taps(run_calls, prof); }
+    if (call_off + n_calls == run_calls) { launch_meter_taps(run_calls, prof); launch_spectrum_taps(run_calls, prof); launch_loudness_taps(run_calls, prof); launch_stereo_taps(run_calls, prof); }
     if (prof) { prof_runs_.push_back(std::move(prof_pool_.back())); prof_pool_.pop_back(); }
 }
 
@@ -1392,7 +1398,7 @@ uint32_t Graph::profile_collect(float* ms_by_kind, float* ms_total) {
         hipEvent_t end = last;
         if (p.od) { perf_od_ms_ += elapsed(last, p.od_end); end = p.od_end; }
         if (p.od_tail) perf_od_ms_ += elapsed(p.group_end.back(), p.od_tail_end);
-        // meter, spectrum and loudness launches: no kind of their own, counted in the total (and so in engine_us): on stream_ last of all, or on the tail stream
+        // meter, spectrum, loudness and stereo field launches: no kind of their own, counted in the total (and so in engine_us): on stream_ last of all, or on the tail stream
         // behind the tail (and its OutputDevices)
         if (p.meters) end = p.meters_end;
         perf_total_ms_ = elapsed(p.begin, end);
@@ -1946,6 +1952,154 @@ void Graph::read_loudness(uint32_t first, uint32_t n, LoudTick* dst, size_t cap)
     wait_tail(-1);
     hip_check(hipMemcpyAsync(dst, (const LoudTick*)loud_rec_.p + (size_t)first * per_tick, count * sizeof(LoudTick), hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(D2H)");
     sync();
+}
+
+// ---- stereo field taps (mixlab_gpu.h mx_graph_set_stereo) ----
+
+void Graph::set_stereo(const mx_port_ref* ports, size_t n, const mx_stereo_params* params) {
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    if (n && (!ports || !params)) throw Error(MX_ERR_INVALID, "ports / params is NULL");
+    if (n > 0xffffffu) throw Error(MX_ERR_INVALID, "more than 2^24 stereo taps");
+    if (n) {
+        if (params->window_ticks < 1 || params->window_ticks > 1024) throw Error(MX_ERR_INVALID, "mx_stereo_params: window_ticks must be 1 .. 1024");
+        if (params->grid != 0 && params->grid != 64 && params->grid != 128) throw Error(MX_ERR_INVALID, "mx_stereo_params: grid must be 0, 64 or 128");
+        if (params->zoom_log2 > 8) throw Error(MX_ERR_INVALID, "mx_stereo_params: zoom_log2 must be 0 .. 8");
+        if (params->grid && params->hop == 0) throw Error(MX_ERR_INVALID, "mx_stereo_params: hop must be >= 1 with a goniometer");
+    }
+    std::vector<uint64_t> keys(n);
+    for (size_t i = 0; i < n; ++i) {
+        const mx_port_ref pr = ports[i];
+        if (pr.node >= nodes_.size() || pr.port >= nodes_[pr.node].out_type.size()) throw Error(MX_ERR_INVALID, "stereo: output terminal out of range");
+        const Node& nd = nodes_[pr.node];
+        if (nd.out_type[pr.port] != MX_STEREO) throw Error(MX_ERR_TYPE, "stereo: a video or mono port has no stereo field");
+        if (nd.out_elided[pr.port]) throw Error(MX_ERR_INVALID, "port is not materialised: it only feeds a fused consumer (build with MX_FLAG_NO_FUSE to observe it)");
+        keys[i] = (uint64_t)pr.node << 32 | pr.port;
+    }
+    { std::vector<uint64_t> k = keys; std::sort(k.begin(), k.end()); if (std::adjacent_find(k.begin(), k.end()) != k.end()) throw Error(MX_ERR_INVALID, "stereo: duplicate (node, port)"); }
+    const size_t fpc = stereo_fpc_ ? stereo_fpc_ : spt_;
+    if (n && params->grid) stereo_gon_room(fpc, n, params->grid, params->hop);   // (throws before anything changed)
+    // like set_loudness: the last run's launches are done with the records and the carried state; the second-stream mode stays on
+    sync();
+    stereo_.assign(ports, ports + n);
+    stereo_run_ticks_ = 0; stereo_hist_cur_ = 0;
+    stereo_c_ = 0; stereo_gon_n_ = 0; stereo_run_seen_ = false;
+    stereo_rec_.free_(); stereo_gon_rec_.free_(); stereo_carry_.free_(); stereo_gon_carry_.free_();
+    if (stereo_.empty()) { stereo_desc_.free_(); stereo_par_ = mx_stereo_params{0, 0, 0, 0}; return; }
+    stereo_par_ = *params;
+    if (!stereo_par_.grid) stereo_par_.hop = 1;   // (ignored without a goniometer)
+    // window history and carried grids start as zero: the stream before this call reads as +0.0, c = 0
+    const size_t hist_bytes = 2 * n * (size_t)STEREO_HIST_TICKS * 3 * sizeof(double);
+    stereo_carry_.alloc(hist_bytes);
+    hip_check(hipMemsetAsync(stereo_carry_.p, 0, hist_bytes, stream_), "hipMemsetAsync(stereo history)");
+    if (stereo_par_.grid) {
+        const size_t grid_bytes = n * stereo_gonio_record_bytes(stereo_par_.grid);
+        stereo_gon_carry_.alloc(grid_bytes);
+        hip_check(hipMemsetAsync(stereo_gon_carry_.p, 0, grid_bytes, stream_), "hipMemsetAsync(goniometer grids)");
+    }
+    hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
+    upload_stereo(fpc);
+}
+
+// the most goniometer records one run can emit at this call length (a run of T ticks that starts anywhere in a hop emits at most
+// ceil(T / hop)), refused beyond 4 GiB
+size_t Graph::stereo_gon_room(size_t fpc, size_t n, uint32_t grid, uint32_t hop) const {
+    const size_t max_ticks = std::max<size_t>(1, cap_frames_ / fpc), cap = (max_ticks + hop - 1) / hop;
+    if ((unsigned __int128)cap * n * stereo_gonio_record_bytes(grid) > ((unsigned __int128)4 << 30))
+        throw Error(MX_ERR_NOMEM, "stereo: the goniometer records of one run (ceil(max_ticks_per_run / hop) x taps x record bytes) exceed 4 GiB: raise hop");
+    return cap;
+}
+
+// As upload_loudness: the descriptors of every tap for both buffer parities in launch order and room for a whole submission's records.  The
+// stream is quiescent.  The carried state (window history, grids, c) is untouched.
+void Graph::upload_stereo(size_t fpc) {
+    const size_t n = stereo_.size();
+    const size_t gon_cap = stereo_par_.grid ? stereo_gon_room(fpc, n, stereo_par_.grid, stereo_par_.hop) : 0;
+    stereo_fpc_ = fpc;
+    std::vector<uint32_t> order, tail;
+    for (uint32_t i = 0; i < (uint32_t)n; ++i) {
+        int32_t o = (int32_t)stereo_[i].node;
+        while (nodes_[o].elided && nodes_[o].owner >= 0) o = nodes_[o].owner;   // the node whose launch writes the port
+        (tail_gi_ >= 0 && nodes_[o].group >= tail_gi_ ? tail : order).push_back(i);
+    }
+    stereo_n_head_ = (uint32_t)order.size();
+    order.insert(order.end(), tail.begin(), tail.end());
+    std::vector<StereoDesc> d(2 * n);
+    for (uint32_t par = 0; par < 2; ++par)
+        for (size_t k = 0; k < n; ++k) {
+            const mx_port_ref tp = stereo_[order[k]];
+            const Node& nd = nodes_[tp.node];
+            StereoDesc& m = d[par * n + k];
+            if (nd.bound && tp.port == 0) m.p = nd.bound;
+            else m.p = (const float*)slab_.p + (par && nd.out_off2[tp.port] != SIZE_MAX ? nd.out_off2[tp.port] : nd.out_off[tp.port]);
+            m.frames = (uint32_t)(fpc * nd.dom_num / nd.dom_den);
+            m.layout = nd.out_dup[tp.port] ? METER_DUP : METER_STEREO;
+            m.slot = order[k]; m._pad = 0;
+        }
+    stereo_desc_.alloc(d.size() * sizeof(StereoDesc));
+    hip_check(hipMemcpy(stereo_desc_.p, d.data(), d.size() * sizeof(StereoDesc), hipMemcpyHostToDevice), "hipMemcpy(stereo descriptors)");
+    const size_t need = std::max<size_t>(1, cap_frames_ / fpc) * n * sizeof(StereoTick), need_gon = gon_cap * n * stereo_gonio_record_bytes(stereo_par_.grid);
+    if (!stereo_rec_.p || stereo_rec_.bytes < need) stereo_rec_.alloc(need);
+    if (need_gon && (!stereo_gon_rec_.p || stereo_gon_rec_.bytes < need_gon)) stereo_gon_rec_.alloc(need_gon);
+}
+
+// The run's stereo field launches, after its last span and behind the loudness taps.  launch_loudness_taps's ordering argument holds word
+// for word: a tap read on stream_ is queued behind the run's producers through the descriptor of the run's buffer parity; a tap on an output
+// of the tail is held back with it (deferred_.stereo) and goes on the tail stream, covered by ev_tail_done_.  The tap sets only read the
+// ports and write disjoint records.  The carried state follows the loudness history's argument: a group's launches of consecutive runs
+// follow each other on that group's stream, each run reads the history buffers the previous one wrote (stereo_hist_cur_ flips once per run
+// for both groups, whose slots are disjoint), and a tap's carried grid and its records are touched by that tap's group alone -- which is why
+// k_stereo_emit and not a memset on stream_ clears the records.  The counter c lives on the host: the run's phase and emissions are launch
+// arguments.
+void Graph::launch_stereo_taps(uint32_t n_calls, ProfSpan* prof) {
+    if (stereo_.empty()) return;
+    const uint32_t n = (uint32_t)stereo_.size();
+    double* hist = (double*)stereo_carry_.p;
+    const size_t hist_words = (size_t)n * STEREO_HIST_TICKS * 3;
+    const uint32_t cur = stereo_hist_cur_;
+    stereo_hist_cur_ ^= 1u;
+    const uint32_t grid = stereo_par_.grid, hop = stereo_par_.hop, phase = (uint32_t)(stereo_c_ % hop);
+    const uint32_t n_emit = grid ? (uint32_t)(((uint64_t)phase + n_calls) / hop) : 0u;
+    stereo_c_ += n_calls;
+    stereo_gon_n_ = n_emit; stereo_run_seen_ = true;
+    StereoRun all{(const StereoDesc*)stereo_desc_.p + (size_t)(parity_ & 1u) * n, n, n_calls, n, stereo_par_.window_ticks,
+                  hist + (size_t)cur * hist_words, hist + (size_t)(cur ^ 1u) * hist_words, (StereoTick*)stereo_rec_.p,
+                  grid, stereo_par_.zoom_log2, hop, phase, n_emit, 8u + grid * grid, (uint32_t*)stereo_gon_rec_.p, (uint32_t*)stereo_gon_carry_.p};
+    const uint32_t n_head = overlap_this_run_ ? stereo_n_head_ : n;
+    if (n_head < n) { StereoRun t = all; t.desc = all.desc + n_head; t.n = n - n_head; deferred_.stereo.push_back(t); }
+    all.n = n_head;
+    if (n_head) launch_stereo(all, stream_);
+    if (!prof) return;
+    if (n_head) { hip_check(hipEventRecord(prof->meters_end, stream_), "hipEventRecord"); prof->meters = true; }   // (again, when an earlier tap set recorded it: the later record holds)
+    prof->meters_tail = !(deferred_.meters.empty() && deferred_.spectra.empty() && deferred_.loudness.empty() && deferred_.stereo.empty());
+}
+
+void Graph::read_stereo(uint32_t first, uint32_t n, StereoTick* dst, size_t cap) {
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    if (stereo_.empty()) throw Error(MX_ERR_INVALID, "no stereo taps are set");
+    if ((uint64_t)first + n > stereo_run_ticks_) throw Error(MX_ERR_INVALID, "the window lies beyond the last run (or no run since the stereo taps were set)");
+    const size_t per_tick = stereo_.size(), count = (size_t)n * per_tick;
+    if (cap < count) throw Error(MX_ERR_INVALID, "cap is smaller than n_ticks x taps");
+    if (count && !dst) throw Error(MX_ERR_INVALID, "dst is NULL");
+    if (!count) return;
+    wait_tail(-1);
+    hip_check(hipMemcpyAsync(dst, (const StereoTick*)stereo_rec_.p + (size_t)first * per_tick, count * sizeof(StereoTick), hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(D2H)");
+    sync();
+}
+
+size_t Graph::read_goniometers(void* dst, size_t cap_bytes) {
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    if (stereo_.empty()) throw Error(MX_ERR_INVALID, "no stereo taps are set");
+    if (!stereo_par_.grid) throw Error(MX_ERR_INVALID, "the stereo taps were set without a goniometer (grid = 0)");
+    if (!stereo_run_seen_) throw Error(MX_ERR_INVALID, "no run since the stereo taps were set");
+    const size_t count = (size_t)stereo_gon_n_ * stereo_.size(), bytes = count * stereo_gonio_record_bytes(stereo_par_.grid);
+    if (cap_bytes < bytes) throw Error(MX_ERR_INVALID, "cap_bytes is smaller than emissions x taps x record bytes");
+    if (bytes && !dst) throw Error(MX_ERR_INVALID, "dst is NULL");
+    if (bytes) {
+        wait_tail(-1);
+        hip_check(hipMemcpyAsync(dst, stereo_gon_rec_.p, bytes, hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(D2H)");
+        sync();
+    }
+    return count;
 }
 
 // ---- video scope taps (mixlab_gpu.h mx_graph_set_video_scopes) ----

@@ -164,6 +164,10 @@ public:
     // loudness taps (mx_graph_set_loudness / mx_graph_read_loudness): K-weighted energy, momentary / short-term window sums and true peak per tick
     void set_loudness(const mx_port_ref* ports, size_t n, const mx_loudness_params* params);
     void read_loudness(uint32_t first, uint32_t n, LoudTick* dst, size_t cap);
+    // stereo field taps (mx_graph_set_stereo / mx_graph_read_stereo / mx_graph_read_goniometers): the sums behind correlation, balance and width per tick, and the goniometer
+    void set_stereo(const mx_port_ref* ports, size_t n, const mx_stereo_params* params);
+    void read_stereo(uint32_t first, uint32_t n, StereoTick* dst, size_t cap);
+    size_t read_goniometers(void* dst, size_t cap_bytes);   // the last run's emitted records; returns how many
     // video scope taps (mx_graph_set_video_scopes / mx_graph_read_video_scopes): histograms, waveform and vectorscope of the frames on video ports
     void set_video_scopes(const mx_port_ref* ports, size_t n, const mx_video_scope_params* params);
     size_t read_video_scopes(void* dst, size_t cap_bytes);   // the last run's records; returns how many
@@ -234,6 +238,9 @@ private:
     void launch_spectrum_taps(uint32_t n_calls, ProfSpan* prof);        // the run's spectrum launches (after its last span, behind the meters)
     void upload_loudness(size_t fpc);                                    // the loudness taps' descriptors (both parities), coefficients and record room, on a quiescent stream
     void launch_loudness_taps(uint32_t n_calls, ProfSpan* prof);        // the run's loudness launches (after its last span, behind the spectrum taps)
+    void upload_stereo(size_t fpc);                                      // the stereo field taps' descriptors (both parities) and record room, on a quiescent stream
+    void launch_stereo_taps(uint32_t n_calls, ProfSpan* prof);          // the run's stereo field launches (after its last span, behind the loudness taps)
+    size_t stereo_gon_room(size_t fpc, size_t n, uint32_t grid, uint32_t hop) const;   // goniometer records a run can emit; MX_ERR_NOMEM beyond 4 GiB
     void refresh_gates(Group& g, uint32_t run_calls);
     uint32_t trigger_of_row(const Group& g, uint32_t row) const;        // node id of the Trigger behind row `row` of a gated group, or ~0u
     void stage_upload(void* dst, const void* src, size_t bytes);         // H2D on the graph's stream through page-locked staging
@@ -273,7 +280,7 @@ private:
     // meters: the taps on the tail's outputs, behind those.  prof: the span's profile record (nullptr: not profiled), whose tail events the release records.
     struct TailLaunch { const void* desc = nullptr; uint32_t n = 0, max_ch = 0; size_t frames = 0; int dup_mode = 0; hipEvent_t prof_ev = nullptr; };
     struct DeferredTail { bool pending = false; std::vector<TailLaunch> items; uint32_t parity = 0; ProfSpan* prof = nullptr;
-                          std::vector<OutRun> outs; std::vector<MeterRun> meters; std::vector<SpecRun> spectra; std::vector<LoudRun> loudness; } deferred_;   // spectra, loudness: those taps on the tail's outputs, behind the meters
+                          std::vector<OutRun> outs; std::vector<MeterRun> meters; std::vector<SpecRun> spectra; std::vector<LoudRun> loudness; std::vector<StereoRun> stereo; } deferred_;   // spectra, loudness, stereo: those taps on the tail's outputs, behind the meters
     std::function<void(hipStream_t)> tail_hook_;
     std::vector<hipEvent_t> head_waits_;
     uint64_t n_gated_ = 0, n_at_once_ = 0;
@@ -321,6 +328,18 @@ private:
     DevBuf loud_desc_, loud_rec_, loud_walk_, loud_tab_, loud_carry_;
     size_t loud_fpc_ = 0;
     uint32_t loud_run_ticks_ = 0;
+    // stereo field taps: the same arrangement again (set order, launch order, stereo_n_head_, StereoDesc[2][n]).  stereo_rec_: StereoTick[max
+    // ticks][n]; stereo_carry_: window history double[2][n][1023][3], of which a run reads buffer stereo_hist_cur_ and writes the other;
+    // stereo_gon_rec_: the last run's goniometer records [emission][n], stereo_gon_n_ emissions; stereo_gon_carry_: one record-shaped grid per
+    // tap with the ticks since the last emission.  stereo_c_ is the hop counter c (0 when the taps are set, + the ticks of every run)
+    std::vector<mx_port_ref> stereo_;
+    mx_stereo_params stereo_par_{0, 0, 0, 0};
+    uint32_t stereo_n_head_ = 0, stereo_hist_cur_ = 0, stereo_gon_n_ = 0;
+    uint64_t stereo_c_ = 0;
+    bool stereo_run_seen_ = false;
+    DevBuf stereo_desc_, stereo_rec_, stereo_carry_, stereo_gon_rec_, stereo_gon_carry_;
+    size_t stereo_fpc_ = 0;
+    uint32_t stereo_run_ticks_ = 0;
     // video scope taps: the taps in set order; scope_rec_: the last run's records [recorded tick][tap], scope_cap_ ticks of room.  scope_c_ is the
     // hop counter (0 when the taps are set, +1 per video tick, carried across runs); a tick is recorded when scope_c_ % hop == 0 before the increment
     std::vector<mx_port_ref> scopes_;
@@ -349,7 +368,7 @@ private:
         std::vector<hipEvent_t> group_end;                              // per launch group, on the stream it ran on
         hipEvent_t video_end = nullptr, tail_begin = nullptr;           // the per-tick video section (stream_); a held-back tail's start (tail stream)
         hipEvent_t od_end = nullptr, od_tail_end = nullptr;             // OutputDevice launches on stream_ / behind the tail
-        hipEvent_t meters_end = nullptr, meters_tail_end = nullptr;     // meter, spectrum and loudness launches on stream_ / behind the tail (and its OutputDevices)
+        hipEvent_t meters_end = nullptr, meters_tail_end = nullptr;     // meter, spectrum, loudness and stereo field launches on stream_ / behind the tail (and its OutputDevices)
         bool tail_held = false, od = false, od_tail = false, meters = false, meters_tail = false;
         explicit ProfSpan(size_t n_groups);
         ProfSpan(const ProfSpan&) = delete; ProfSpan& operator=(const ProfSpan&) = delete;

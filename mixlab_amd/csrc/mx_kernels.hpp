@@ -207,6 +207,28 @@ void launch_loudness(const LoudRun& r, hipStream_t s);   // k_loud_peak; k_loud_
 // the tables of the loudness spec (host only): biquads[10], carry[4][4] for a tick of `frames` frames, interp[3][12]; any may be null.
 // false: rate is not finite or not above twice the shelf frequency, or frames is outside 1 .. LOUD_MAX_FRAMES
 bool loudness_tables(double rate, uint32_t frames, double* biquads, double* carry, float* interp);
+// Stereo field taps (mx_k_stereo.hip, mixlab_gpu.h mx_graph_set_stereo): one descriptor per tap and buffer parity and the per-tick record
+// (= mx_stereo_tick).  Carried per tap: the last STEREO_HIST_TICKS ticks' three sums, kept twice and alternating per run like the loudness
+// windows' history, and -- with a goniometer -- one grid in the shape of a record (8 header words of which [2] frames and [3] skipped are
+// used, then grid x grid counts) that holds the ticks since the last emission.
+static constexpr uint32_t STEREO_HIST_TICKS = 1023;
+struct StereoDesc { const float* p; uint32_t frames, layout, slot, _pad; };   // as SpecDesc; layout is METER_STEREO or METER_DUP
+struct StereoTick { double sum_ll, sum_rr, sum_lr, win_ll, win_rr, win_lr; uint32_t frames, nonfinite; };
+struct StereoRun {
+    const StereoDesc* desc; uint32_t n;      // the launch's taps
+    uint32_t n_ticks, stride;                // ticks of the run; taps of the whole set (records per tick)
+    uint32_t window_ticks;
+    const double* hist_in; double* hist_out; // [slot][STEREO_HIST_TICKS][3]: read by this run, written for the next
+    StereoTick* rec;                         // rec[tick * stride + slot]
+    // goniometer (grid = 0: none): tick t of the run belongs to group (phase + t) / hop; groups below n_emit are the run's records, the one
+    // the run ends in stays in the carry grid
+    uint32_t grid, zoom_log2, hop, phase;    // phase: the graph's counter c mod hop at the run's first tick
+    uint32_t n_emit, rec_words;              // (phase + n_ticks) / hop; 8 + grid * grid
+    uint32_t* gon_rec;                       // [emission][slot][rec_words]
+    uint32_t* gon_carry;                     // [slot][rec_words]
+};
+inline size_t stereo_gonio_record_bytes(uint32_t grid) { return 32 + 4 * (size_t)grid * grid; }
+void launch_stereo(const StereoRun& r, hipStream_t s);   // k_stereo_emit (a run that emits), k_stereo_reduce, k_stereo_window
 // Video scope taps (mx_k_scope.hip, mixlab_gpu.h mx_graph_set_video_scopes): ONE launch counts one frame into one record -- the 32-byte
 // header, hist[3][256], wave[wave_cols][256], vec[128][128], all u32.  The counters of the record must be zero when the launch starts (the
 // workgroups add their partial counts with integer atomics); the kernel writes the header itself.  counted = 0: header only.
