@@ -227,9 +227,10 @@ int mx_graph_debug_eq_records(mx_graph* g, void** device_records, size_t* bytes)
  * launch opens, or at once (a join released them, or the next run had no such launch).  Tests use it to know which path they exercised. */
 int mx_graph_debug_tail_releases(mx_graph* g, uint64_t* gated, uint64_t* at_once);
 /* DEBUG: which form the first EqThree launch group's last launch took (MX_EQ_LAUNCH_NONE before any).  out[0] the form, out[1] the super-block of a tiled
- * form -- 16 (half lines, two tiles), 32 (whole lines, two tiles) or 321 (whole lines, one tile) -- else 0, out[2] chunks per instance, out[3] the chunk
+ * form -- 16 (half lines, two tiles), 32 (whole lines, two tiles) or 321 (whole lines, one tile) -- else 0 (sequential: see below), out[2] chunks per instance, out[3] the chunk
  * length in samples, out[4] the warm-up of a speculative chunk.  The scan form: out[2] the spans of its time split, out[3] the span length, out[4] the
- * samples its pre-pass reads at the end of each span (the span itself: the full pre-pass).  The sequential form: 1 chunk of the whole stream, no warm-up.
+ * samples its pre-pass reads at the end of each span (the span itself: the full pre-pass).  The sequential form: 1 chunk of the whole stream, no warm-up, and out[1] the
+ * lanes per instance: 1 (one lane walks the stream) or 2 (the split cascade: a lane per 4-pole cascade and a sample-parallel epilogue kernel).
  * Tests use it to know which path a sample rate and tick length reached. */
 #define MX_EQ_LAUNCH_NONE 0u
 #define MX_EQ_LAUNCH_SEQUENTIAL 1u     /* one lane (or the two-lane split cascade) per instance, no speculation */
@@ -247,7 +248,9 @@ int mx_graph_bind_source_device(mx_graph* g, uint32_t node, const void* device_p
 
 /* n_ticks consecutive Engine::run_tick calls (src/engine.rs:400-510) in one submission:
  * tick k of the run uses t = (first_tick + k) * SPT (src/engine.rs:490).  Asynchronous on the
- * graph's stream.  n_ticks <= max_ticks_per_run. */
+ * graph's stream.  n_ticks <= max_ticks_per_run.  first_tick need not continue the previous run's: the clock may start anywhere and
+ * jump between runs (carried state such as an Envelope's last edge keeps its absolute sample time); tested for sample times up to 2^40
+ * and for Envelope distances of 2^32 samples and more (tests/test_gpu_far_clock.py). */
 int mx_graph_run_ticks(mx_graph* g, uint64_t first_tick, uint32_t n_ticks);
 int mx_graph_sync(mx_graph* g);
 

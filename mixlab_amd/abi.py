@@ -420,7 +420,8 @@ class Graph:
 
     def debug_eq_launch(self) -> dict:
         """mx_graph_debug_eq_launch: the form the first EqThree group's last launch took -> {form: one of EQ_LAUNCH, super_block, n_chunks, chunk, warm}
-        (the scan: n_chunks / chunk = the spans of its time split and their length, warm = what its pre-pass reads of each span)"""
+        (the scan: n_chunks / chunk = the spans of its time split and their length, warm = what its pre-pass reads of each span; sequential:
+        super_block = lanes per instance, 1 = one lane, 2 = the split cascade)"""
         v = (C.c_uint32 * 5)()
         check(lib.mx_graph_debug_eq_launch(self._h, v))
         return {"form": EQ_LAUNCH.get(v[0], str(v[0])), "super_block": int(v[1]), "n_chunks": int(v[2]), "chunk": int(v[3]), "warm": int(v[4])}

@@ -1259,6 +1259,7 @@ void Graph::run_span(uint64_t t0, size_t fpc, uint32_t call_off, uint32_t n_call
                         scratch = g.spec.p;
                     }
                     launch_eq_three_exact((const EqDesc*)desc_of(g), (EqState*)g.state.p, n, r, scratch, stream_);
+                    launch[1] = scratch ? 2u : 1u;   // lanes per instance: the split cascade, or one lane
                 }
             } else {
                 EqSplit sp{1u, 5u, 0u, 0u, gf, gf, nullptr, nullptr, nullptr};

@@ -1,6 +1,7 @@
 """Host-side proof obligation of the envelope kernel's exact-division shortcut (see
-mixlab_amd/csrc/mx_audio_kernels.hip: seq_ms): checked exhaustively for every sample distance the
-fast path accepts (dt < 2^32, i.e. > 24 h of audio) at every sample rate of the tick-shape table (tests/tick_shapes.py)."""
+mixlab_amd/csrc/mx_env_math.hpp: ms_of_u32, seq_ms): checked exhaustively for every sample distance the
+fast path accepts (dt < 2^32, i.e. > 24 h of audio) at every sample rate of the tick-shape table (tests/tick_shapes.py).
+Distances of 2^32 and more take the true division: tests/test_gpu_far_clock.py."""
 import pathlib
 import subprocess
 

@@ -13,6 +13,7 @@ import oracle_video as ov
 import synth
 from mixlab_amd import abi, ingest, video
 from mixlab_amd.workspace import Workspace
+from tick_shapes import FAR_EPOCHS, far_first_tick
 
 pytestmark = pytest.mark.gpu
 SR, SPT = 44100, 735
@@ -30,10 +31,8 @@ def upload(hf):
     return video.DFrame(hf.w, hf.h).upload(*hf.visible())
 
 
-@pytest.mark.parametrize("prog,mon", [((1280, 720), (560, 350)), ((320, 180), (560, 350)), ((560, 350), (560, 350)), ((1920, 1080), (1120, 700)), ((350, 560), (560, 350))],
-                         ids=["720p-to-monitor", "upscaled", "same-size-passes-through", "1080p-to-stream-output", "pillarbox"])
-def test_monitor_keeps_every_tick_of_a_submission(prog, mon):
-    T, RUNS, FIRST = 6, 3, 40           # the node first runs on tick 40: its epoch
+def check_monitor_keeps_every_tick(prog, mon, FIRST):
+    T, RUNS = 6, 3                      # the node first runs on tick FIRST: its epoch
     ws = Workspace(SR, 60)
     sa, sb = ws.source_video(), ws.source_video()
     mx = ws.video_mixer(a=0, b=1, fader=0.35)
@@ -104,6 +103,19 @@ def test_monitor_keeps_every_tick_of_a_submission(prog, mon):
             if part[k] is not None:
                 assert all(np.array_equal(x, y) for x, y in zip(part[k], packed[2 + k]))
     assert len(pics) >= 8
+
+
+@pytest.mark.parametrize("prog,mon", [((1280, 720), (560, 350)), ((320, 180), (560, 350)), ((560, 350), (560, 350)), ((1920, 1080), (1120, 700)), ((350, 560), (560, 350))],
+                         ids=["720p-to-monitor", "upscaled", "same-size-passes-through", "1080p-to-stream-output", "pillarbox"])
+def test_monitor_keeps_every_tick_of_a_submission(prog, mon):
+    check_monitor_keeps_every_tick(prog, mon, 40)
+
+
+@pytest.mark.parametrize("epoch", FAR_EPOCHS)
+def test_monitor_timestamps_far_from_tick_zero(epoch):
+    """The same three submissions with the node's epoch next to 2^31 samples, across 2^32 and at 2^40: the timestamp is the exact rational
+    tick start minus epoch (monitor.rs:113-139), and the frames queued for those ticks arrive on them."""
+    check_monitor_keeps_every_tick((320, 180), (560, 350), far_first_tick(epoch, SPT, 18))
 
 
 def test_monitor_passes_source_offsets_and_handles_disconnected_inputs():

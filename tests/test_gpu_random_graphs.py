@@ -25,7 +25,7 @@ from meter_model import METER_TICK, MeterModel, records_equal
 from mixlab_amd import abi
 from mixlab_amd.workspace import Workspace
 from output_device_model import OutputDeviceModel
-from tick_shapes import by_id
+from tick_shapes import FAR_EPOCHS, by_id, far_first_tick
 
 pytestmark = pytest.mark.gpu
 
@@ -413,9 +413,9 @@ def od_args(p):
     return p.channels, (None if p.left < 0 else p.left), (None if p.right < 0 else p.right)
 
 
-def run_full_graph(shape_id, seed, builds, flags):
-    """random_graph(full=True) through 3-4 runs of 1-6 ticks on every build in `builds` against the oracle (in whatever mode it is in):
-    every materialised port, meter records and OutputDevice hand-offs, bit for bit"""
+def run_full_graph(shape_id, seed, builds, flags, first_tick=0):
+    """random_graph(full=True) through 3-4 runs of 1-6 ticks from `first_tick` on every build in `builds` against the oracle (in whatever
+    mode it is in): every materialised port, meter records and OutputDevice hand-offs, bit for bit"""
     shape = by_id(shape_id)
     ws, sources = random_graph(seed, shape.sample_rate, shape.ticks_per_second, full=True)
     spt = ws.spt
@@ -487,7 +487,7 @@ def run_full_graph(shape_id, seed, builds, flags):
     set_taps(taps)
     od_models = {od: OutputDeviceModel(shape.sample_rate, *od_args(ws.nodes[od][1])) for od in ods}
     updatable = [n for n in order if ws.nodes[n][0] in PARAM_KINDS and ws.nodes[n][1]]   # (a Mixer of no channels has none)
-    tick = 0
+    tick = first_tick
     n_runs = int(rng.integers(3, 5))
     for run in range(n_runs):
         L = int(rng.integers(1, MAX_RUN + 1))
@@ -572,3 +572,20 @@ def test_full_random_graph_matches_the_oracle(shape_id, seed):
 def test_full_random_graph_contracted_matches_the_contract_oracle(shape_id, seed):
     with oracle.fp_contract():
         run_full_graph(shape_id, seed, ("fused", "unfused"), abi.FLAG_FP_CONTRACT)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the same graphs with the clock started far from zero: oscillator and FmSine phase, FIR, resampled domains, OutputDevice clip / lag times,
+# meters and scheduled updates at sample times next to 2^31, across 2^32 and at 2^40
+# ---------------------------------------------------------------------------------------------------------------------------
+FAR_SEEDS = [FULL_SEEDS[0], FULL_SEEDS[5], FULL_SEEDS[24], FULL_SEEDS[34], FULL_SEEDS[48], FULL_SEEDS[53]]
+
+
+@pytest.mark.parametrize("epoch", FAR_EPOCHS)
+@pytest.mark.parametrize("shape_id,seed", FAR_SEEDS, ids=[f"{s}-{n}" for s, n in FAR_SEEDS])
+def test_full_random_graph_matches_the_oracle_far_from_tick_zero(shape_id, seed, epoch):
+    """Both sides start at the epoch; nothing is jumped.  Neither keeps a position counter of its own: the oracle's resampler takes
+    tick * frames-per-tick of either domain (oracle/mixlab_oracle.c, ORC_KIND_RESAMPLE), the engine t0 * dom_num / dom_den (Graph::run_span)."""
+    assert {s for s, _ in FAR_SEEDS} == {"44k1", "48k", "44k1_100", "8k_8000"}
+    n_ticks = 4 if epoch == "across_2p32" else 4 * MAX_RUN       # 3-4 runs of 1-6 ticks: sample 2^32 lies in the third tick
+    run_full_graph(shape_id, seed, ("fused", "unfused"), abi.FLAG_EQ_EXACT, first_tick=far_first_tick(epoch, by_id(shape_id).spt, n_ticks))

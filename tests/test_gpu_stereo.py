@@ -10,7 +10,7 @@ from mixlab_amd import abi, ingest, video
 from mixlab_amd.workspace import Workspace
 from test_gpu_audio_parity import strips
 from test_gpu_spectrum import io_graph, wide
-from tick_shapes import by_id
+from tick_shapes import by_id, far_first_tick
 
 pytestmark = pytest.mark.gpu
 
@@ -206,7 +206,7 @@ def test_master_and_cue_in_every_tail_mode_with_the_meters_sums(mode, monkeypatc
         assert gated > 0
 
 
-def test_all_five_tap_sets_together_and_no_sample_or_picture_changes():
+def check_all_five_tap_sets_together(first_tick):
     """a mixed audio + video graph without taps, with the four earlier tap sets, and with stereo taps as well: every output is the same in
     all three, the earlier sets' records are the same with and without stereo taps, and the stereo records are the model's"""
     import oracle_video as ov
@@ -232,7 +232,7 @@ def test_all_five_tap_sets_together_and_no_sample_or_picture_changes():
         res = {}
         for r in range(2):
             g.write_source(au, synth.noise(9 + r, N * 2 * spt), N)
-            g.run_ticks(r * N, N)
+            g.run_ticks(first_tick + r * N, N)
             res[f"rgba{r}"] = video.graph_rgba_output(g, rgba).copy()
             res[f"audio{r}"] = g.read_output(amp, 0, N, True).copy(); res[f"source{r}"] = g.read_output(au, 0, N, True).copy()
             res[f"mon_audio{r}"] = ingest.graph_read_monitor_audio_i16(g, mon, N, spt).copy()
@@ -265,10 +265,20 @@ def test_all_five_tap_sets_together_and_no_sample_or_picture_changes():
         for r in range(3):
             for k, s in enumerate(srcs):
                 g.write_source(s, synth.noise(k + 5 * r, 4 * 800), 4)
-            g.run_ticks(4 * r, 4)
+            g.run_ticks(first_tick + 4 * r, 4)
             per_run.append(np.concatenate([g.read_output(nd, p, 4, True) for nd, p in ports]))
         outs.append(np.concatenate(per_run))
     assert outs[0].tobytes() == outs[1].tobytes()
+
+
+def test_all_five_tap_sets_together_and_no_sample_or_picture_changes():
+    check_all_five_tap_sets_together(0)
+
+
+def test_all_five_tap_sets_together_from_the_2p40_epoch():
+    """The same fixed graphs with the clock started at sample time 2^40: the records and the goniometer emissions equal the models' as they
+    do from tick 0 (the taps count ticks since they were set, never absolute time), and no sample or picture changes with taps set."""
+    check_all_five_tap_sets_together(far_first_tick("at_2p40", 735, 12))
 
 
 def test_non_finite_subnormal_and_large_samples():

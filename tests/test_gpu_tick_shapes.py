@@ -25,7 +25,7 @@ from test_gpu_ingest import AbiMedia, FrameBook
 from test_gpu_random_graphs import MONO, STEREO, port_types, random_graph
 from test_gpu_video_graph import FADERS, MATRIX, cascade, upload
 from test_ingest_oracle import play_media
-from tick_shapes import INVALID, SHAPE_STRIPS, SHAPES, by_id
+from tick_shapes import FAR_EPOCHS, INVALID, SHAPE_STRIPS, SHAPES, by_id, far_first_tick
 
 pytestmark = pytest.mark.gpu
 
@@ -229,7 +229,7 @@ def test_amplifier_modulated_by_a_buffer_takes_the_control_tile(shape):
 # ------------------------------------------------------------------------------------------------
 # 4. oscillators (every waveform), FmSine, and config 1 with its Plotter
 # ------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("hours", [0, 5], ids=["tick0", "5h"])
+@pytest.mark.parametrize("hours", [0, 5, *FAR_EPOCHS], ids=["tick0", "5h", *FAR_EPOCHS])
 @pytest.mark.parametrize("shape", SHAPE_PARAMS)
 def test_oscillators_and_fm_sine_bit_exact(shape, hours):
     sr, tps, spt = shape.sample_rate, shape.ticks_per_second, shape.spt
@@ -245,7 +245,8 @@ def test_oscillators_and_fm_sine_bit_exact(shape, hours):
         fms.append(fm)
     g = ws.build(max_ticks_per_run=T)
     og = oracle.OracleGraph(ws)
-    tick = hours * 3600 * tps
+    # (an epoch of tick_shapes.FAR_EPOCHS: the three runs end below 2^31 samples / the first holds sample 2^32 / they start at 2^40)
+    tick = far_first_tick(hours, spt, T if hours == "across_2p32" else 2 * T + 1) if isinstance(hours, str) else hours * 3600 * tps
     for n in (T, 1, T):
         g.run_ticks(tick, n)
         got_o = [g.read_output(o, 0, n, False) for o in oscs]

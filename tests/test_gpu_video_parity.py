@@ -7,6 +7,7 @@ import pytest
 
 import oracle_video as ov
 from mixlab_amd import abi, video
+from tick_shapes import FAR_EPOCHS, far_first_tick
 
 pytestmark = pytest.mark.gpu
 
@@ -315,8 +316,8 @@ def test_yuv_to_rgba_bit_exact_vs_build_spec(size, matrix):
     assert np.array_equal(got, want)
 
 
-def test_video_mixer_state_machine_matches_oracle():
-    """Frames of different sizes arriving at different rates, expiry by exact rationals, parameter changes."""
+def check_video_mixer_state_machine(first_tick):
+    """Frames of different sizes arriving at different rates, expiry by exact rationals, parameter changes; the clock starts at `first_tick`."""
     SPT = 735
     gm, om = video.VideoMixer(a=0, b=1, fader=0.75), ov.OracleVideoMixer(a=0, b=1, fader=0.75)
     big = [ov.HostFrame(640, 360).fill(10 + k, seed=k) for k in range(4)]
@@ -325,7 +326,7 @@ def test_video_mixer_state_machine_matches_oracle():
     keep = []
     program_seen = 0
     for tick in range(40):
-        t = tick * SPT
+        t = (first_tick + tick) * SPT
         ins_h = [None] * 4
         if tick >= 2 and tick % 2 == 0:            # channel 0: 30 fps, 640x360
             ins_h[0] = (big[(tick // 2) % 4], (1, 30), (0, 1))
@@ -361,7 +362,11 @@ def test_video_mixer_state_machine_matches_oracle():
     # first two ticks: nothing to show yet => None (video_mixer.rs:113-119)
 
 
-def test_video_mixer_frame_expiry_is_exact():
+def test_video_mixer_state_machine_matches_oracle():
+    check_video_mixer_state_machine(0)
+
+
+def check_video_mixer_frame_expiry(first_tick):
     SPT = 735
     gm, om = video.VideoMixer(a=0, b=None, fader=1.0), ov.OracleVideoMixer(a=0, b=None, fader=1.0)
     hf = ov.HostFrame(64, 64).fill(1)
@@ -371,11 +376,23 @@ def test_video_mixer_frame_expiry_is_exact():
     for tick in range(4):
         ins_d = [(d, (1, 30), (0, 1))] if tick == 0 else []
         ins_h = [(hf, (1, 30), (0, 1))] if tick == 0 else []
-        prog, _, _ = gm.run_tick(tick * SPT, ins_d + [None] * (4 - len(ins_d)))
-        want = om.run_tick(tick * SPT, ins_h + [None] * (4 - len(ins_h)))
+        prog, _, _ = gm.run_tick((first_tick + tick) * SPT, ins_d + [None] * (4 - len(ins_d)))
+        want = om.run_tick((first_tick + tick) * SPT, ins_h + [None] * (4 - len(ins_h)))
         seen.append(prog is not None)
         assert (prog is None) == (want is None)
     assert seen == [True, True, False, False]
+
+
+def test_video_mixer_frame_expiry_is_exact():
+    check_video_mixer_frame_expiry(0)
+
+
+@pytest.mark.parametrize("epoch", FAR_EPOCHS)
+def test_video_mixer_frame_expiry_and_state_machine_far_from_tick_zero(epoch):
+    """The two checks above with the clock started next to 2^31 samples, across 2^32 and at 2^40: a stored frame's end is the tick's start
+    t / SAMPLE_RATE plus offset and duration as an exact rational, whatever t is."""
+    check_video_mixer_frame_expiry(far_first_tick(epoch, 735, 4))
+    check_video_mixer_state_machine(far_first_tick(epoch, 735, 40))
 
 
 def test_video_mixer_module_compat_path_host_frames():

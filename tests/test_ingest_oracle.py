@@ -7,10 +7,12 @@ import pytest
 
 import ingest_model as im
 import oracle
+from tick_shapes import FAR_EPOCHS, far_first_tick
 
 
-def play_media(src, acts, sr=44100, spt=735):
-    """drive a MediaSource-like object; a frame the channel refused is offered again on later ticks, in order (the decode thread blocks)"""
+def play_media(src, acts, sr=44100, spt=735, first_tick=0):
+    """drive a MediaSource-like object from tick `first_tick`; a frame the channel refused is offered again on later ticks, in order (the
+    decode thread blocks)"""
     out, backlog = [], []
     for tick, a in enumerate(acts):
         for act in a:
@@ -23,7 +25,7 @@ def play_media(src, acts, sr=44100, spt=735):
             if rc == 0:
                 break
             backlog.pop(0)      # sent, or no receiver (-1: the reference's thread ends, the frame is lost)
-        out.append(src.run_tick(tick * spt))
+        out.append(src.run_tick((first_tick + tick) * spt))
     return out
 
 
@@ -34,6 +36,19 @@ def test_media_source_oracle_equals_python_model(seed):
     want = play_media(im.PyMediaSource(), acts)
     assert got == want
     assert sum(x is not None for x in want) > 20
+
+
+@pytest.mark.parametrize("epoch", FAR_EPOCHS)
+@pytest.mark.parametrize("seed", range(4))
+def test_media_source_pacing_far_from_tick_zero(seed, epoch):
+    """the clock started next to 2^31 samples, across 2^32 and at 2^40: the pacer's epoch is the tick the first frame is received on, an exact rational"""
+    acts = im.media_scenario(seed)
+    t0 = far_first_tick(epoch, 735, len(acts))
+    got = play_media(oracle.OMediaSource(), acts, first_tick=t0)
+    want = play_media(im.PyMediaSource(), acts, first_tick=t0)
+    assert got == want
+    assert sum(x is not None for x in want) > 20
+    assert got == play_media(oracle.OMediaSource(), acts)      # pacing is relative to that epoch: the same frames with the same offsets as from tick 0
 
 
 def test_media_source_hand_worked():
@@ -55,7 +70,7 @@ def test_media_source_hand_worked():
     assert m.run_tick(130 * 735) == (9, F(1, 30), F(0))
 
 
-def play_stream(src, acts, spt=735):
+def play_stream(src, acts, spt=735, first_tick=0):
     out = []
     for tick, a in enumerate(acts):
         for act in a:
@@ -65,7 +80,7 @@ def play_stream(src, acts, spt=735):
                 src.write_audio(act[1], act[2], act[3])
             else:
                 src.write_video(act[1], act[2], act[3], act[4])
-        s, v, z = src.run_tick(tick * spt, 2 * spt)
+        s, v, z = src.run_tick((first_tick + tick) * spt, 2 * spt)
         out.append((s.tobytes(), v, z))
     return out
 
@@ -75,6 +90,17 @@ def test_stream_input_oracle_equals_python_model(seed):
     acts = im.stream_scenario(seed)
     got = play_stream(oracle.OStreamInput(), acts)
     want = play_stream(im.PyStreamInput(), acts)
+    assert got == want
+    assert sum(x[1] is not None for x in want) > 20 and any(x[2] for x in want)
+
+
+@pytest.mark.parametrize("epoch", FAR_EPOCHS)
+@pytest.mark.parametrize("seed", range(4))
+def test_stream_input_pacing_far_from_tick_zero(seed, epoch):
+    acts = im.stream_scenario(seed)
+    t0 = far_first_tick(epoch, 735, len(acts))
+    got = play_stream(oracle.OStreamInput(), acts, first_tick=t0)
+    want = play_stream(im.PyStreamInput(), acts, first_tick=t0)
     assert got == want
     assert sum(x[1] is not None for x in want) > 20 and any(x[2] for x in want)
 
@@ -109,8 +135,7 @@ def test_stream_input_offset_equal_to_tick_is_delivered():
 # ------------------------------------------------------------------------------------------------
 # the C-ABI's host state machines need no device: StreamInput's audio side and its source timing on CPU
 # ------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("seed", range(6))
-def test_stream_input_abi_audio_side_equals_oracle_without_a_gpu(seed):
+def check_stream_input_abi_audio_side(seed, first_tick):
     from mixlab_amd import ingest
     acts = [[a for a in tick if a[0] != "video"] for tick in im.stream_scenario(seed)]   # device frames need a GPU; the rest does not
 
@@ -127,10 +152,32 @@ def test_stream_input_abi_audio_side_equals_oracle_without_a_gpu(seed):
         def run_tick(self, t, n_out):
             return self.s.run_tick(t, n_out)
 
-    got = play_stream(Abi(), acts)
-    want = play_stream(oracle.OStreamInput(44100), acts)
+    got = play_stream(Abi(), acts, first_tick=first_tick)
+    want = play_stream(oracle.OStreamInput(44100), acts, first_tick=first_tick)
     assert got == want
     assert any(x[2] for x in want)
+
+
+@pytest.mark.parametrize("seed", range(6))
+def test_stream_input_abi_audio_side_equals_oracle_without_a_gpu(seed):
+    check_stream_input_abi_audio_side(seed, 0)
+
+
+@pytest.mark.parametrize("epoch", FAR_EPOCHS)
+@pytest.mark.parametrize("seed", range(3))
+def test_stream_input_abi_audio_side_far_from_tick_zero(seed, epoch):
+    check_stream_input_abi_audio_side(seed, far_first_tick(epoch, 735, len(im.stream_scenario(seed))))
+
+
+@pytest.mark.parametrize("epoch", FAR_EPOCHS)
+def test_media_source_abi_pacing_far_from_tick_zero_without_frames(epoch):
+    """A smoke check only (device frames need a GPU: tests/test_gpu_ingest.py): the C ABI's MediaSource at 48 kHz accepts far tick times -- with
+    a medium set and no frame offered, nothing leaves and nothing is refused.  It cannot catch a pacing error; the oracle / model tests above do."""
+    from mixlab_amd import ingest
+    m = ingest.MediaSource(48000, 60)
+    t0 = far_first_tick(epoch, 800, 5)
+    m.set_media(True)
+    assert [m.run_tick((t0 + k) * 800) for k in range(5)] == [None] * 5
 
 
 def test_media_source_abi_without_frames_needs_no_gpu():

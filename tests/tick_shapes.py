@@ -58,3 +58,20 @@ INVALID = [(22050, 60), (44100, 8), (48000, 7), (8000, 3), (30, 60), (44100, 882
 
 def by_id(shape_id: str) -> TickShape:
     return next(s for s in SHAPES if s.id == shape_id)
+
+
+# The clock started far from zero (tests of absolute time: tests/test_gpu_far_clock.py and the `far` parametrisations elsewhere).
+FAR_EPOCHS = ("below_2p31", "across_2p32", "at_2p40")
+
+
+def far_first_tick(epoch: str, spt: int, n_ticks: int) -> int:
+    """The first tick of a stretch of n_ticks ticks of spt samples that
+      below_2p31   ends just below sample time 2^31 (every sample time still fits a signed 32-bit integer),
+      across_2p32  holds sample time 2^32 in its tick of index n_ticks // 2 (at that tick's first sample where spt divides 2^32),
+      at_2p40      starts at the first tick boundary at or after sample time 2^40."""
+    if epoch == "below_2p31":
+        return (1 << 31) // spt - n_ticks - 1
+    if epoch == "across_2p32":
+        return (1 << 32) // spt - n_ticks // 2
+    assert epoch == "at_2p40"
+    return -(-(1 << 40) // spt)
