@@ -105,6 +105,7 @@ Graph::Graph(const mx_node* nodes, size_t n_nodes, const mx_edge* edges, size_t 
     if (sr % tps) throw Error(MX_ERR_INVALID, "sample_rate must be a multiple of ticks_per_second");
     sample_rate_ = (double)sr;
     spt_ = sr / tps;                                                     // src/engine.rs:55
+    tap_fpc_ = spt_;
     tps_ = tps;
     const uint32_t max_ticks = o.max_ticks_per_run ? o.max_ticks_per_run : 1u;
     cap_frames_ = cap_frames_override ? cap_frames_override : spt_ * (size_t)max_ticks;
@@ -469,12 +470,9 @@ void Graph::flush_deferred_tail(bool gated) {
     for (const OutRun& r : deferred_.outs) launch_output_device(r, tail_stream_);   // OutputDevices that read the tail's outputs
     if (prof && !deferred_.outs.empty()) hip_check(hipEventRecord(prof->od_tail_end, tail_stream_), "hipEventRecord");
     deferred_.outs.clear();
-    for (const MeterRun& r : deferred_.meters) launch_meters(r, tail_stream_);   // meters on the tail's outputs
-    for (const SpecRun& r : deferred_.spectra) launch_spectra(r, tail_stream_);   // spectrum taps on the tail's outputs
-    for (const LoudRun& r : deferred_.loudness) launch_loudness(r, tail_stream_);   // loudness taps on the tail's outputs
-    for (const StereoRun& r : deferred_.stereo) launch_stereo(r, tail_stream_);   // stereo field taps on the tail's outputs
-    if (prof && !(deferred_.meters.empty() && deferred_.spectra.empty() && deferred_.loudness.empty() && deferred_.stereo.empty())) hip_check(hipEventRecord(prof->meters_tail_end, tail_stream_), "hipEventRecord");
-    deferred_.meters.clear(); deferred_.spectra.clear(); deferred_.loudness.clear(); deferred_.stereo.clear();
+    for (const auto& t : deferred_.taps) std::visit([&](const auto& r) { launch_taps(r, tail_stream_); }, t);   // the audio tap sets on the tail's outputs, in the sets' order
+    if (prof && !deferred_.taps.empty()) hip_check(hipEventRecord(prof->meters_tail_end, tail_stream_), "hipEventRecord");
+    deferred_.taps.clear();
     if (tail_hook_) { auto hook = std::move(tail_hook_); tail_hook_ = nullptr; hook(tail_stream_); }   // (mx_exchange: pack + exchange of that run's buses, behind the bank)
     // recorded AFTER the hook: whoever waits for this tail (wait_tail) is then also ordered behind the hook's reads of the buses on the tail stream -- a later run's Mixer on
     // stream_ must not overwrite them under a pack that is still copying
@@ -512,10 +510,7 @@ void Graph::end_auto_tail() {
     overlap_this_run_ = false;
     for (Group& g : groups_) { g.desc_alt.free_(); g.extra_alt.free_(); }
     build_descriptors();
-    if (!meters_.empty()) upload_meters(meter_fpc_);   // every tap on stream_, the first buffers only
-    if (!spectra_.empty()) upload_spectra(spec_fpc_);
-    if (!loudness_.empty()) upload_loudness(loud_fpc_);
-    if (!stereo_.empty()) upload_stereo(stereo_fpc_);
+    reupload_taps(tap_fpc_);   // every tap on stream_, the first buffers only
 }
 
 Graph::~Graph() {
@@ -1028,10 +1023,7 @@ void Graph::bind_source(uint32_t node, const void* dev) {
     sync();
     n.bound = (const float*)dev;
     build_descriptors();
-    if (!meters_.empty()) upload_meters(meter_fpc_);
-    if (!spectra_.empty()) upload_spectra(spec_fpc_);
-    if (!loudness_.empty()) upload_loudness(loud_fpc_);
-    if (!stereo_.empty()) upload_stereo(stereo_fpc_);
+    reupload_taps(tap_fpc_);
 }
 
 void Graph::set_input_enabled(uint32_t node, uint32_t port, bool enabled) {
@@ -1059,10 +1051,7 @@ void Graph::ensure_capacity(size_t frames) {
     cap_frames_ = frames;
     layout_slab();
     build_descriptors();
-    if (!meters_.empty()) upload_meters(meter_fpc_);   // the ports moved; room for more ticks
-    if (!spectra_.empty()) upload_spectra(spec_fpc_);
-    if (!loudness_.empty()) upload_loudness(loud_fpc_);
-    if (!stereo_.empty()) upload_stereo(stereo_fpc_);
+    reupload_taps(tap_fpc_);   // the ports moved; room for more ticks
 }
 
 static bool group_launches(const Group& g);
@@ -1071,12 +1060,12 @@ void Graph::run(uint64_t t0, size_t fpc, uint32_t n_calls, float* ms_by_kind, fl
     const size_t frames = fpc * (size_t)n_calls;
     auto drop_schedules = [&] { for (uint32_t id : sched_nodes_) { nodes_[id].sched.clear(); nodes_[id].gate_sched.clear(); } sched_nodes_.clear(); };
     if (frames > cap_frames_) { drop_schedules(); throw Error(MX_ERR_INVALID, "n_ticks exceeds max_ticks_per_run"); }
-    if (n_calls == 0 || fpc == 0) { drop_schedules(); last_calls_ = n_calls; last_frames_per_call_ = fpc; meter_run_ticks_ = spec_run_ticks_ = loud_run_ticks_ = stereo_run_ticks_ = 0; stereo_gon_n_ = 0; scope_n_ = 0; return; }
+    if (n_calls == 0 || fpc == 0) { drop_schedules(); last_calls_ = n_calls; last_frames_per_call_ = fpc; for (AudioTapSet* s : tap_sets()) s->run_ticks = 0; stereo_gon_n_ = 0; scope_n_ = 0; return; }
     hip_check(hipSetDevice(device_), "hipSetDevice");
-    if (!meters_.empty() && fpc != meter_fpc_) { sync(); upload_meters(fpc); }   // (the module compat path's call length): frames per tick and record room
-    if (!spectra_.empty() && fpc != spec_fpc_) { sync(); upload_spectra(fpc); }
-    if (!loudness_.empty() && fpc != loud_fpc_) { sync(); upload_loudness(fpc); }
-    if (!stereo_.empty() && fpc != stereo_fpc_) { sync(); upload_stereo(fpc); }
+    if (fpc != tap_fpc_) {   // (the module compat path's call length): frames per tick and record room
+        const auto sets = tap_sets();
+        if (std::any_of(sets.begin(), sets.end(), [](const AudioTapSet* s) { return !s->empty(); })) { sync(); reupload_taps(fpc); }
+    }
 
     // ---- scheduled parameter updates (Engine::client_update between two ticks, src/engine.rs:192-214,277-398) ----
     // Trigger updates travel as one gate bit per tick and cost nothing.  Any other module's update cuts the run into spans:
@@ -1194,10 +1183,7 @@ void Graph::run(uint64_t t0, size_t fpc, uint32_t n_calls, float* ms_by_kind, fl
     hip_check(hipGetLastError(), "kernel launch");
     last_calls_ = n_calls;
     last_frames_per_call_ = fpc;
-    meter_run_ticks_ = meters_.empty() ? 0u : n_calls;
-    spec_run_ticks_ = spectra_.empty() ? 0u : n_calls;
-    loud_run_ticks_ = loudness_.empty() ? 0u : n_calls;
-    stereo_run_ticks_ = stereo_.empty() ? 0u : n_calls;
+    for (AudioTapSet* s : tap_sets()) s->run_ticks = s->empty() ? 0u : n_calls;
     if (prof) ++prof_runs_count_;
     if (ms_by_kind) (void)profile_collect(ms_by_kind, ms_total);
 }
@@ -1285,7 +1271,7 @@ void Graph::run_span(uint64_t t0, size_t fpc, uint32_t call_off, uint32_t n_call
                 if ((int)gi == tail_gi_) {
                     if (deferred_.pending) flush_deferred_tail(false);   // (a run whose earlier groups had no speculative EqThree launch: nothing opened a gate)
                     hip_check(hipEventRecord(ev_head_done_, stream_), "hipEventRecord");
-                    deferred_.items.clear(); deferred_.outs.clear(); deferred_.meters.clear(); deferred_.spectra.clear(); deferred_.loudness.clear(); deferred_.stereo.clear(); deferred_.parity = parity_; deferred_.prof = prof;
+                    deferred_.items.clear(); deferred_.outs.clear(); deferred_.taps.clear(); deferred_.parity = parity_; deferred_.prof = prof;
                     if (prof) prof->tail_held = true;
                 }
                 deferred_.items.push_back(TailLaunch{desc_of(g), n, g.max_taps, gf, g.dup_mode, prof ? prof->group_end[gi] : nullptr});
@@ -1337,7 +1323,7 @@ void Graph::run_span(uint64_t t0, size_t fpc, uint32_t call_off, uint32_t n_call
     if (prof && has_video_) hip_check(hipEventRecord(prof->video_end, stream_), "hipEventRecord");
     // after everything else of the span on stream_ (the video section included): its profile interval starts at the latest event recorded there
     launch_outputs(t0, call_off, n_calls, prof);
-    // the port buffers hold every tick of the run: the meters go once, after its last span
+    // the port buffers hold every tick of the run: the audio tap sets go once, after its last span, in this order on either stream
     if (call_off + n_calls == run_calls) { launch_meter_taps(run_calls, prof); launch_spectrum_taps(run_calls, prof); launch_loudness_taps(run_calls, prof); launch_stereo_taps(run_calls, prof); }
     if (prof) { prof_runs_.push_back(std::move(prof_pool_.back())); prof_pool_.pop_back(); }
 }
@@ -1595,125 +1581,172 @@ void Graph::audio_out_lag(uint32_t node) {
     nodes_[node].od_lag->store(true);   // AtomicBool::store (output_device.rs:126); nothing else of the graph is touched
 }
 
-// ---- level meters (mixlab_gpu.h mx_graph_set_meters) ----
+// ---- the audio tap sets: level meters, spectrum, loudness and stereo field taps (mixlab_gpu.h mx_graph_set_meters, _spectra, _loudness,
+// _stereo; DESIGN.md sections 0.2, 0.3, 0.5, 0.6).  What the four share comes first, written for "a tap set"; then each set's own part ----
 
-void Graph::set_meters(const mx_port_ref* ports, size_t n, const mx_meter_params* params) {
-    hip_check(hipSetDevice(device_), "hipSetDevice");
+void Graph::check_tap_args(const AudioTapSet& s, const void* ports, const void* params, size_t n) const {
     if (n && (!ports || !params)) throw Error(MX_ERR_INVALID, "ports / params is NULL");
-    if (n > 0xffffffu) throw Error(MX_ERR_INVALID, "more than 2^24 meters");
-    std::vector<MeterTap> taps(n);
+    if (n > 0xffffffu) throw Error(MX_ERR_INVALID, std::string("more than 2^24 ") + s.noun);
+}
+
+// own_check: a set's own check of one tap, behind the shared ones of that tap
+void Graph::check_tap_ports(const AudioTapSet& s, const mx_port_ref* ports, size_t n, const std::function<void(size_t, const Node&)>& own_check) const {
+    const std::string tag = std::string(s.tag) + ": ";
     std::vector<uint64_t> keys(n);
     for (size_t i = 0; i < n; ++i) {
         const mx_port_ref pr = ports[i];
-        if (pr.node >= nodes_.size() || pr.port >= nodes_[pr.node].out_type.size()) throw Error(MX_ERR_INVALID, "meter: output terminal out of range");
+        if (pr.node >= nodes_.size() || pr.port >= nodes_[pr.node].out_type.size()) throw Error(MX_ERR_INVALID, tag + "output terminal out of range");
         const Node& nd = nodes_[pr.node];
-        if (nd.out_type[pr.port] == MX_VIDEO) throw Error(MX_ERR_TYPE, "meter: a video port has no level");
+        if (s.stereo_only ? nd.out_type[pr.port] != MX_STEREO : nd.out_type[pr.port] == MX_VIDEO) throw Error(MX_ERR_TYPE, tag + s.no_type);
         if (nd.out_elided[pr.port]) throw Error(MX_ERR_INVALID, "port is not materialised: it only feeds a fused consumer (build with MX_FLAG_NO_FUSE to observe it)");
-        const float rel = params[i].release;
-        if (!(std::isfinite(rel) && rel > 0.0f && rel <= 1.0f)) throw Error(MX_ERR_INVALID, "mx_meter_params: release must be finite, 0 < release <= 1");
-        taps[i] = MeterTap{pr.node, pr.port, params[i].hold_ticks, rel};
+        if (own_check) own_check(i, nd);
         keys[i] = (uint64_t)pr.node << 32 | pr.port;
     }
-    { std::vector<uint64_t> k = keys; std::sort(k.begin(), k.end()); if (std::adjacent_find(k.begin(), k.end()) != k.end()) throw Error(MX_ERR_INVALID, "meter: duplicate (node, port)"); }
+    std::sort(keys.begin(), keys.end());
+    if (std::adjacent_find(keys.begin(), keys.end()) != keys.end()) throw Error(MX_ERR_INVALID, tag + "duplicate (node, port)");
+}
+
+// The descriptors of every tap for both buffer parities (the second only differs for a port the tail reads, while the second-stream mode is
+// on), in launch order: the taps read on stream_ (s.n_head of them), then those on the tail's outputs.
+std::vector<TapDesc> Graph::tap_descs(AudioTapSet& s, size_t fpc) const {
+    const size_t n = s.ports.size();
+    std::vector<uint32_t> order, tail;
+    for (uint32_t i = 0; i < (uint32_t)n; ++i) {
+        int32_t o = (int32_t)s.ports[i].node;
+        while (nodes_[o].elided && nodes_[o].owner >= 0) o = nodes_[o].owner;   // the node whose launch writes the port
+        (tail_gi_ >= 0 && nodes_[o].group >= tail_gi_ ? tail : order).push_back(i);
+    }
+    s.n_head = (uint32_t)order.size();
+    order.insert(order.end(), tail.begin(), tail.end());
+    std::vector<TapDesc> d(2 * n);
+    for (uint32_t par = 0; par < 2; ++par)
+        for (size_t k = 0; k < n; ++k) {
+            const mx_port_ref tp = s.ports[order[k]];
+            const Node& nd = nodes_[tp.node];
+            TapDesc& m = d[par * n + k];
+            // the port at tick 0 of the run (out_ptr without a span's offset)
+            if (nd.bound && tp.port == 0) m.p = nd.bound;
+            else m.p = (const float*)slab_.p + (par && nd.out_off2[tp.port] != SIZE_MAX ? nd.out_off2[tp.port] : nd.out_off[tp.port]);
+            m.frames = (uint32_t)(fpc * nd.dom_num / nd.dom_den);
+            m.layout = nd.out_dup[tp.port] ? METER_DUP : (nd.out_type[tp.port] == MX_MONO ? METER_MONO : METER_STEREO);
+            m.slot = order[k]; m._pad = 0;
+        }
+    return d;
+}
+
+// ... to the device, and room for a whole submission's records of tick_bytes per tick.  The stream is quiescent.  Whatever a set carries from
+// run to run is untouched: it holds frames and ticks, whatever the call length.
+void Graph::upload_tap_descs(AudioTapSet& s, const void* d, size_t bytes, size_t fpc, size_t tick_bytes) {
+    s.desc.alloc(bytes);
+    hip_check(hipMemcpy(s.desc.p, d, bytes, hipMemcpyHostToDevice), (std::string("hipMemcpy(") + s.tag + " descriptors)").c_str());
+    const size_t need = std::max<size_t>(1, cap_frames_ / fpc) * tick_bytes;
+    if (!s.rec.p || s.rec.bytes < need) s.rec.alloc(need);
+}
+
+void Graph::reupload_taps(size_t fpc) {
+    if (!meters_.empty()) upload_meters(fpc);
+    if (!spectra_.empty()) upload_spectra(fpc);
+    if (!loudness_.empty()) upload_loudness(fpc);
+    if (!stereo_.empty()) upload_stereo(fpc);
+    tap_fpc_ = fpc;
+}
+
+// The run's launches of one tap set, after its last span and behind the sets before it: `all` is the run struct of the whole set, its
+// descriptors those of parity 0.  Why no buffer a tap reads is overwritten before it has read it:
+//  - a tap read on stream_ (every tap when the run is on one stream: a cut run, a short one in the automatic mode, a graph without the mode)
+//    is queued there behind the run's producers and ahead of the next run's launches, which are the only ones that write that port again.  Its
+//    descriptor points at THIS run's buffer parity: the tail-read ports alternate per run, run k + 1 writes the other buffer, and run k + 2 --
+//    the next writer of this one -- comes after the tap on the same stream;
+//  - a tap on an output of the tail (the Mixer bank and the buses above it) is held back with it (deferred_.taps) and goes on the tail
+//    stream behind the tail's last launch.  Those outputs are single buffers written only by the tail, whose next launch (run k + 1's) is
+//    queued behind this one on that same stream.  ev_tail_done_ is recorded after it, so every join -- a read-back of the records,
+//    read_output, a run that reuses this parity -- covers the tap too.
+// The sets only read the ports and write disjoint records, so none disturbs another.  Within a set, the records and the carried state of the
+// two groups of taps are disjoint (slots), and a group's launches of consecutive runs follow each other on that group's stream (a run that
+// changes the stream of the tail's taps has joined the tail first: run()'s wait_tail) -- so state that one run hands to the next, updated
+// in place or through a pair of buffers that flips once per run for both groups, is read after it was written.
+template <class Run> void Graph::launch_tap_set(const AudioTapSet& s, Run all, ProfSpan* prof) {
+    const uint32_t n = all.n;
+    all.desc += (size_t)(parity_ & 1u) * n;
+    const uint32_t n_head = overlap_this_run_ ? s.n_head : n;
+    if (n_head < n) { Run t = all; t.desc += n_head; t.n = n - n_head; deferred_.taps.emplace_back(t); }
+    all.n = n_head;
+    if (n_head) launch_taps(all, stream_);
+    if (!prof) return;
+    if (n_head) { hip_check(hipEventRecord(prof->meters_end, stream_), "hipEventRecord"); prof->meters = true; }   // (again, when an earlier set recorded it: the later record holds)
+    prof->meters_tail = !deferred_.taps.empty();
+}
+
+// ticks [first, first + n) of the last run's records: tick_items items of item_bytes each per tick, cap counted in items
+void Graph::read_taps(const AudioTapSet& s, uint32_t first, uint32_t n, void* dst, size_t cap, size_t tick_items, size_t item_bytes, const char* cap_what) {
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    if (s.empty()) throw Error(MX_ERR_INVALID, std::string("no ") + s.noun + " are set");
+    if ((uint64_t)first + n > s.run_ticks) throw Error(MX_ERR_INVALID, std::string("the window lies beyond the last run (or no run since the ") + s.noun + " were set)");
+    const size_t count = (size_t)n * tick_items;
+    if (cap < count) throw Error(MX_ERR_INVALID, std::string("cap is smaller than ") + cap_what);
+    if (count && !dst) throw Error(MX_ERR_INVALID, "dst is NULL");
+    if (!count) return;
+    wait_tail(-1);
+    hip_check(hipMemcpyAsync(dst, (const char*)s.rec.p + (size_t)first * tick_items * item_bytes, count * item_bytes, hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(D2H)");
+    sync();
+}
+
+// ---- level meters ----
+
+void Graph::set_meters(const mx_port_ref* ports, size_t n, const mx_meter_params* params) {
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    check_tap_args(meters_, ports, params, n);
+    check_tap_ports(meters_, ports, n, [&](size_t i, const Node&) {
+        const float rel = params[i].release;
+        if (!(std::isfinite(rel) && rel > 0.0f && rel <= 1.0f)) throw Error(MX_ERR_INVALID, "mx_meter_params: release must be finite, 0 < release <= 1");
+    });
     // like a read-back: the last run's launches (held-back tail included) are done with the records and states.  The second-stream mode stays on:
-    // the meters read the ports through descriptors of both parities, in stream order with their producers (launch_meter_taps)
+    // the taps read the ports through descriptors of both parities, in stream order with their producers (launch_tap_set)
     sync();
     DevBuf st;
     if (n) {
         st.alloc(n * 2 * sizeof(MeterHold));
         hip_check(hipMemsetAsync(st.p, 0, n * 2 * sizeof(MeterHold), stream_), "hipMemsetAsync(meter state)");
         for (size_t i = 0; i < n; ++i)   // a surviving tap keeps its hold
-            for (size_t j = 0; j < meters_.size(); ++j)
-                if (meters_[j].node == taps[i].node && meters_[j].port == taps[i].port)
+            for (size_t j = 0; j < meters_.ports.size(); ++j)
+                if (meters_.ports[j].node == ports[i].node && meters_.ports[j].port == ports[i].port)
                     hip_check(hipMemcpyAsync((MeterHold*)st.p + 2 * i, (const MeterHold*)meter_state_.p + 2 * j, 2 * sizeof(MeterHold), hipMemcpyDeviceToDevice, stream_),
                               "hipMemcpyAsync(meter state)");
         hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
     }
-    meters_ = std::move(taps);
+    meters_.ports.assign(ports, ports + n);
+    meter_par_.assign(params, params + n);
     meter_state_ = std::move(st);
-    meter_run_ticks_ = 0;
-    meter_rec_.free_();
-    if (meters_.empty()) { meter_desc_.free_(); return; }
-    upload_meters(meter_fpc_ ? meter_fpc_ : spt_);
+    meters_.run_ticks = 0;
+    meters_.rec.free_();
+    if (meters_.empty()) { meters_.desc.free_(); return; }
+    upload_meters(tap_fpc_);
 }
 
-// The descriptors of every tap for both buffer parities (the second only differs for a port the tail reads, while the second-stream mode is on),
-// and room for a whole submission's records.  The stream is quiescent.
+// the shared fields of every descriptor from its TapDesc, then the tap's own parameters
 void Graph::upload_meters(size_t fpc) {
-    meter_fpc_ = fpc;
-    const size_t n = meters_.size();
-    // launch order: the taps read on stream_, then those on the tail's outputs
-    std::vector<uint32_t> order, tail;
-    for (uint32_t i = 0; i < (uint32_t)n; ++i) {
-        int32_t o = (int32_t)meters_[i].node;
-        while (nodes_[o].elided && nodes_[o].owner >= 0) o = nodes_[o].owner;   // the node whose launch writes the port
-        (tail_gi_ >= 0 && nodes_[o].group >= tail_gi_ ? tail : order).push_back(i);
-    }
-    meter_n_head_ = (uint32_t)order.size();
-    order.insert(order.end(), tail.begin(), tail.end());
-    std::vector<MeterDesc> d(2 * n);
-    for (uint32_t par = 0; par < 2; ++par)
-        for (size_t k = 0; k < n; ++k) {
-            const MeterTap& tp = meters_[order[k]];
-            const Node& nd = nodes_[tp.node];
-            MeterDesc& m = d[par * n + k];
-            // the port at tick 0 of the run (out_ptr without a span's offset)
-            if (nd.bound && tp.port == 0) m.p = nd.bound;
-            else m.p = (const float*)slab_.p + (par && nd.out_off2[tp.port] != SIZE_MAX ? nd.out_off2[tp.port] : nd.out_off[tp.port]);
-            m.frames = (uint32_t)(fpc * nd.dom_num / nd.dom_den);
-            m.layout = nd.out_dup[tp.port] ? METER_DUP : (nd.out_type[tp.port] == MX_MONO ? METER_MONO : METER_STEREO);
-            m.slot = order[k]; m.hold_ticks = tp.hold_ticks; m.release = tp.release; m._pad = 0;
-        }
-    meter_desc_.alloc(d.size() * sizeof(MeterDesc));
-    hip_check(hipMemcpy(meter_desc_.p, d.data(), d.size() * sizeof(MeterDesc), hipMemcpyHostToDevice), "hipMemcpy(meter descriptors)");
-    const size_t need = std::max<size_t>(1, cap_frames_ / fpc) * n * sizeof(MeterTick);
-    if (!meter_rec_.p || meter_rec_.bytes < need) meter_rec_.alloc(need);
+    const std::vector<TapDesc> t = tap_descs(meters_, fpc);
+    std::vector<MeterDesc> d(t.size());
+    for (size_t k = 0; k < t.size(); ++k)
+        d[k] = MeterDesc{t[k].p, t[k].frames, t[k].layout, t[k].slot, meter_par_[t[k].slot].hold_ticks, meter_par_[t[k].slot].release, 0};
+    upload_tap_descs(meters_, d.data(), d.size() * sizeof(MeterDesc), fpc, meters_.ports.size() * sizeof(MeterTick));
 }
 
-// The run's meter launches, after its last span.  Why no buffer a meter reads is overwritten before it has read it:
-//  - a tap read on stream_ (every tap when the run is on one stream: a cut run, a short one in the automatic mode, a graph without the mode)
-//    is queued there behind the run's producers and ahead of the next run's launches, which are the only ones that write that port again.  Its
-//    descriptor points at THIS run's buffer parity: the tail-read ports alternate per run, run k + 1 writes the other buffer, and run k + 2 --
-//    the next writer of this one -- comes after the meter on the same stream;
-//  - a tap on an output of the tail (the Mixer bank and the buses above it) is held back with it (deferred_.meters) and goes on the tail
-//    stream behind the tail's last launch.  Those outputs are single buffers written only by the tail, whose next launch (run k + 1's) is
-//    queued behind this one on that same stream.  ev_tail_done_ is recorded after it, so every join -- read_meters, read_output, a run that
-//    reuses this parity -- covers the meter too.
-// The records and hold states of the two groups of taps are disjoint (slots); a later run's meters of a group follow on that group's stream.
 void Graph::launch_meter_taps(uint32_t n_calls, ProfSpan* prof) {
     if (meters_.empty()) return;
-    const uint32_t n = (uint32_t)meters_.size();
-    const MeterDesc* d = (const MeterDesc*)meter_desc_.p + (size_t)(parity_ & 1u) * n;
-    MeterRun all{d, n, n_calls, n, (MeterTick*)meter_rec_.p, (MeterHold*)meter_state_.p};
-    const uint32_t n_head = overlap_this_run_ ? meter_n_head_ : n;
-    if (n_head < n) { MeterRun t = all; t.desc = d + n_head; t.n = n - n_head; deferred_.meters.push_back(t); }
-    all.n = n_head;
-    if (n_head) launch_meters(all, stream_);
-    if (!prof) return;
-    if (n_head) { hip_check(hipEventRecord(prof->meters_end, stream_), "hipEventRecord"); prof->meters = true; }
-    prof->meters_tail = !deferred_.meters.empty();
+    const uint32_t n = meters_.size();
+    launch_tap_set(meters_, MeterRun{(const MeterDesc*)meters_.desc.p, n, n_calls, n, (MeterTick*)meters_.rec.p, (MeterHold*)meter_state_.p}, prof);
 }
 
 void Graph::read_meters(uint32_t first, uint32_t n, MeterTick* dst, size_t cap) {
-    hip_check(hipSetDevice(device_), "hipSetDevice");
-    if (meters_.empty()) throw Error(MX_ERR_INVALID, "no meters are set");
-    if ((uint64_t)first + n > meter_run_ticks_) throw Error(MX_ERR_INVALID, "the window lies beyond the last run (or no run since the meters were set)");
-    const size_t count = (size_t)n * meters_.size();
-    if (cap < count) throw Error(MX_ERR_INVALID, "cap is smaller than n_ticks x meters");
-    if (count && !dst) throw Error(MX_ERR_INVALID, "dst is NULL");
-    if (!count) return;
-    wait_tail(-1);
-    hip_check(hipMemcpyAsync(dst, (const MeterTick*)meter_rec_.p + (size_t)first * meters_.size(), count * sizeof(MeterTick), hipMemcpyDeviceToHost, stream_),
-              "hipMemcpyAsync(D2H)");
-    sync();
+    read_taps(meters_, first, n, dst, cap, meters_.ports.size(), sizeof(MeterTick), "n_ticks x meters");
 }
 
-// ---- spectrum taps (mixlab_gpu.h mx_graph_set_spectra) ----
+// ---- spectrum taps ----
 
 void Graph::set_spectra(const mx_port_ref* ports, size_t n, const mx_spectrum_params* params) {
     hip_check(hipSetDevice(device_), "hipSetDevice");
-    if (n && (!ports || !params)) throw Error(MX_ERR_INVALID, "ports / params is NULL");
-    if (n > 0xffffffu) throw Error(MX_ERR_INVALID, "more than 2^24 spectrum taps");
+    check_tap_args(spectra_, ports, params, n);
     std::vector<float> win, tre, tim;
     if (n) {
         const uint32_t N = params->n_fft, B = params->n_bands;
@@ -1725,23 +1758,14 @@ void Graph::set_spectra(const mx_port_ref* ports, size_t n, const mx_spectrum_pa
             if (params->edges[j] >= params->edges[j + 1]) throw Error(MX_ERR_INVALID, "mx_spectrum_params: edges must be strictly ascending");
         if (params->edges[B] > N / 2 + 1) throw Error(MX_ERR_INVALID, "mx_spectrum_params: edges[n_bands] exceeds n_fft / 2 + 1");
     }
-    std::vector<uint64_t> keys(n);
-    for (size_t i = 0; i < n; ++i) {
-        const mx_port_ref pr = ports[i];
-        if (pr.node >= nodes_.size() || pr.port >= nodes_[pr.node].out_type.size()) throw Error(MX_ERR_INVALID, "spectrum: output terminal out of range");
-        const Node& nd = nodes_[pr.node];
-        if (nd.out_type[pr.port] == MX_VIDEO) throw Error(MX_ERR_TYPE, "spectrum: a video port has no spectrum");
-        if (nd.out_elided[pr.port]) throw Error(MX_ERR_INVALID, "port is not materialised: it only feeds a fused consumer (build with MX_FLAG_NO_FUSE to observe it)");
-        keys[i] = (uint64_t)pr.node << 32 | pr.port;
-    }
-    { std::vector<uint64_t> k = keys; std::sort(k.begin(), k.end()); if (std::adjacent_find(k.begin(), k.end()) != k.end()) throw Error(MX_ERR_INVALID, "spectrum: duplicate (node, port)"); }
+    check_tap_ports(spectra_, ports, n);
     // like set_meters: the last run's launches are done with the records and histories; the second-stream mode stays on
     sync();
-    spectra_.assign(ports, ports + n);
-    spec_run_ticks_ = 0;
+    spectra_.ports.assign(ports, ports + n);
+    spectra_.run_ticks = 0;
     spec_hist_cur_ = 0;
-    spec_rec_.free_();
-    if (spectra_.empty()) { spec_desc_.free_(); spec_hist_.free_(); spec_tab_.free_(); spec_n_fft_ = spec_n_bands_ = 0; return; }
+    spectra_.rec.free_();
+    if (spectra_.empty()) { spectra_.desc.free_(); spec_hist_.free_(); spec_tab_.free_(); spec_n_fft_ = spec_n_bands_ = 0; return; }
     const uint32_t N = spec_n_fft_ = params->n_fft, B = spec_n_bands_ = params->n_bands;
     // tables: window[N] | twiddle (re, im)[N / 2] | edges[B + 1] (u16, padded to whole floats)
     std::vector<float> tab(2 * (size_t)N + (B + 2) / 2, 0.0f);
@@ -1754,149 +1778,69 @@ void Graph::set_spectra(const mx_port_ref* ports, size_t n, const mx_spectrum_pa
     spec_hist_.alloc(2 * n * 2 * (size_t)N * sizeof(float));
     hip_check(hipMemsetAsync(spec_hist_.p, 0, 2 * n * 2 * (size_t)N * sizeof(float), stream_), "hipMemsetAsync(spectrum history)");
     hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
-    upload_spectra(spec_fpc_ ? spec_fpc_ : spt_);
+    upload_spectra(tap_fpc_);
 }
 
-// As upload_meters: the descriptors of every tap for both buffer parities in launch order (the taps read on stream_, then those on the tail's
-// outputs), and room for a whole submission's records.  The stream is quiescent.  The histories are untouched: they hold frames, whatever the
-// call length.
 void Graph::upload_spectra(size_t fpc) {
-    spec_fpc_ = fpc;
-    const size_t n = spectra_.size();
-    std::vector<uint32_t> order, tail;
-    for (uint32_t i = 0; i < (uint32_t)n; ++i) {
-        int32_t o = (int32_t)spectra_[i].node;
-        while (nodes_[o].elided && nodes_[o].owner >= 0) o = nodes_[o].owner;   // the node whose launch writes the port
-        (tail_gi_ >= 0 && nodes_[o].group >= tail_gi_ ? tail : order).push_back(i);
-    }
-    spec_n_head_ = (uint32_t)order.size();
-    order.insert(order.end(), tail.begin(), tail.end());
-    std::vector<SpecDesc> d(2 * n);
-    for (uint32_t par = 0; par < 2; ++par)
-        for (size_t k = 0; k < n; ++k) {
-            const mx_port_ref tp = spectra_[order[k]];
-            const Node& nd = nodes_[tp.node];
-            SpecDesc& m = d[par * n + k];
-            if (nd.bound && tp.port == 0) m.p = nd.bound;
-            else m.p = (const float*)slab_.p + (par && nd.out_off2[tp.port] != SIZE_MAX ? nd.out_off2[tp.port] : nd.out_off[tp.port]);
-            m.frames = (uint32_t)(fpc * nd.dom_num / nd.dom_den);
-            m.layout = nd.out_dup[tp.port] ? METER_DUP : (nd.out_type[tp.port] == MX_MONO ? METER_MONO : METER_STEREO);
-            m.slot = order[k]; m._pad = 0;
-        }
-    spec_desc_.alloc(d.size() * sizeof(SpecDesc));
-    hip_check(hipMemcpy(spec_desc_.p, d.data(), d.size() * sizeof(SpecDesc), hipMemcpyHostToDevice), "hipMemcpy(spectrum descriptors)");
-    const size_t need = std::max<size_t>(1, cap_frames_ / fpc) * n * 2 * spec_n_bands_ * sizeof(float);
-    if (!spec_rec_.p || spec_rec_.bytes < need) spec_rec_.alloc(need);
+    const std::vector<TapDesc> d = tap_descs(spectra_, fpc);
+    upload_tap_descs(spectra_, d.data(), d.size() * sizeof(TapDesc), fpc, spectra_.ports.size() * 2 * spec_n_bands_ * sizeof(float));
 }
 
-// The run's spectrum launches, after its last span and behind the meters.  launch_meter_taps's ordering argument holds word for word: a tap
-// read on stream_ is queued behind the run's producers through the descriptor of the run's buffer parity; a tap on an output of the tail is
-// held back with it (deferred_.spectra) and goes on the tail stream, covered by ev_tail_done_.  Meters and spectra only read the ports and
-// write disjoint records, so neither disturbs the other.  The histories add one more carried state, with the same argument as the meters'
-// hold: a group's launches of consecutive runs follow each other on that group's stream (a run that changes the stream of the tail's taps has
-// joined the tail first: run()'s wait_tail), and each run reads the buffer the previous one wrote (spec_hist_cur_ flips once per run for
-// both groups, whose slots are disjoint).
+// Each run reads the history buffer the previous one wrote: spec_hist_cur_ flips once per run.
 void Graph::launch_spectrum_taps(uint32_t n_calls, ProfSpan* prof) {
     if (spectra_.empty()) return;
-    const uint32_t n = (uint32_t)spectra_.size(), N = spec_n_fft_;
+    const uint32_t n = spectra_.size(), N = spec_n_fft_;
     const float* tab = (const float*)spec_tab_.p;
     float* h0 = (float*)spec_hist_.p + (size_t)spec_hist_cur_ * n * 2 * N;
     float* h1 = (float*)spec_hist_.p + (size_t)(spec_hist_cur_ ^ 1u) * n * 2 * N;
     spec_hist_cur_ ^= 1u;
-    SpecRun all{(const SpecDesc*)spec_desc_.p + (size_t)(parity_ & 1u) * n, n, n_calls, n, N, spec_n_bands_,
-                tab, (const float2*)(tab + N), (const uint16_t*)(tab + 2 * (size_t)N), h0, h1, (float*)spec_rec_.p};
-    const uint32_t n_head = overlap_this_run_ ? spec_n_head_ : n;
-    if (n_head < n) { SpecRun t = all; t.desc = all.desc + n_head; t.n = n - n_head; deferred_.spectra.push_back(t); }
-    all.n = n_head;
-    if (n_head) launch_spectra(all, stream_);
-    if (!prof) return;
-    if (n_head) { hip_check(hipEventRecord(prof->meters_end, stream_), "hipEventRecord"); prof->meters = true; }   // (again, when meters recorded it: the later record holds)
-    prof->meters_tail = !(deferred_.meters.empty() && deferred_.spectra.empty());
+    launch_tap_set(spectra_, SpecRun{(const TapDesc*)spectra_.desc.p, n, n_calls, n, N, spec_n_bands_,
+                                     tab, (const float2*)(tab + N), (const uint16_t*)(tab + 2 * (size_t)N), h0, h1, (float*)spectra_.rec.p}, prof);
 }
 
 void Graph::read_spectra(uint32_t first, uint32_t n, float* dst, size_t cap) {
-    hip_check(hipSetDevice(device_), "hipSetDevice");
-    if (spectra_.empty()) throw Error(MX_ERR_INVALID, "no spectrum taps are set");
-    if ((uint64_t)first + n > spec_run_ticks_) throw Error(MX_ERR_INVALID, "the window lies beyond the last run (or no run since the spectrum taps were set)");
-    const size_t per_tick = spectra_.size() * 2 * spec_n_bands_, count = (size_t)n * per_tick;
-    if (cap < count) throw Error(MX_ERR_INVALID, "cap is smaller than n_ticks x taps x 2 x n_bands");
-    if (count && !dst) throw Error(MX_ERR_INVALID, "dst is NULL");
-    if (!count) return;
-    wait_tail(-1);
-    hip_check(hipMemcpyAsync(dst, (const float*)spec_rec_.p + (size_t)first * per_tick, count * sizeof(float), hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(D2H)");
-    sync();
+    read_taps(spectra_, first, n, dst, cap, spectra_.ports.size() * 2 * spec_n_bands_, sizeof(float), "n_ticks x taps x 2 x n_bands");
 }
 
-// ---- loudness taps (mixlab_gpu.h mx_graph_set_loudness) ----
+// ---- loudness taps ----
 
 void Graph::set_loudness(const mx_port_ref* ports, size_t n, const mx_loudness_params* params) {
     hip_check(hipSetDevice(device_), "hipSetDevice");
-    if (n && (!ports || !params)) throw Error(MX_ERR_INVALID, "ports / params is NULL");
-    if (n > 0xffffffu) throw Error(MX_ERR_INVALID, "more than 2^24 loudness taps");
+    check_tap_args(loudness_, ports, params, n);
     if (n) {
         if (params->momentary_ticks < 1 || params->momentary_ticks > 1024) throw Error(MX_ERR_INVALID, "mx_loudness_params: momentary_ticks must be 1 .. 1024");
         if (params->short_ticks < 1 || params->short_ticks > 1024) throw Error(MX_ERR_INVALID, "mx_loudness_params: short_ticks must be 1 .. 1024");
     }
-    std::vector<uint64_t> keys(n);
-    for (size_t i = 0; i < n; ++i) {
-        const mx_port_ref pr = ports[i];
-        if (pr.node >= nodes_.size() || pr.port >= nodes_[pr.node].out_type.size()) throw Error(MX_ERR_INVALID, "loudness: output terminal out of range");
-        const Node& nd = nodes_[pr.node];
-        if (nd.out_type[pr.port] == MX_VIDEO) throw Error(MX_ERR_TYPE, "loudness: a video port has no loudness");
-        if (nd.out_elided[pr.port]) throw Error(MX_ERR_INVALID, "port is not materialised: it only feeds a fused consumer (build with MX_FLAG_NO_FUSE to observe it)");
+    check_tap_ports(loudness_, ports, n, [&](size_t, const Node& nd) {
         if (!loudness_tables(sample_rate_ * nd.dom_num / nd.dom_den, 1, nullptr, nullptr, nullptr)) throw Error(MX_ERR_INVALID, "loudness: the port's rate is not above twice the shelf frequency (3 364 Hz)");
-        keys[i] = (uint64_t)pr.node << 32 | pr.port;
-    }
-    { std::vector<uint64_t> k = keys; std::sort(k.begin(), k.end()); if (std::adjacent_find(k.begin(), k.end()) != k.end()) throw Error(MX_ERR_INVALID, "loudness: duplicate (node, port)"); }
+    });
     // like set_spectra: the last run's launches are done with the records and the carried state; the second-stream mode stays on
     sync();
-    loudness_.assign(ports, ports + n);
-    loud_run_ticks_ = 0;
+    loudness_.ports.assign(ports, ports + n);
+    loudness_.run_ticks = 0;
     loud_hist_cur_ = 0;
-    loud_rec_.free_(); loud_walk_.free_();
-    if (loudness_.empty()) { loud_desc_.free_(); loud_tab_.free_(); loud_carry_.free_(); loud_par_ = mx_loudness_params{0, 0}; return; }
+    loudness_.rec.free_(); loud_walk_.free_();
+    if (loudness_.empty()) { loudness_.desc.free_(); loud_tab_.free_(); loud_carry_.free_(); loud_par_ = mx_loudness_params{0, 0}; return; }
     loud_par_ = *params;
     // filter state, window history and interpolator history all start as +0.0: the stream before this call reads as silence
     const size_t carry_bytes = n * (8 + 2 * (size_t)LOUD_HIST_TICKS) * sizeof(double) + 2 * n * 2 * LOUD_HIST_FRAMES * sizeof(float);
     loud_carry_.alloc(carry_bytes);
     hip_check(hipMemsetAsync(loud_carry_.p, 0, carry_bytes, stream_), "hipMemsetAsync(loudness state)");
     hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
-    upload_loudness(loud_fpc_ ? loud_fpc_ : spt_);
+    upload_loudness(tap_fpc_);
 }
 
-// As upload_spectra: the descriptors of every tap for both buffer parities in launch order, room for a whole submission's records and walk
-// states, and -- what depends on the call length here -- each tap's coefficients: the biquads of its port's own rate and the carry matrix of
-// its tick length.  The stream is quiescent.  The carried state is untouched.
+// beside the descriptors: room for the walk states and -- what depends on the call length here -- each tap's coefficients, the biquads of its
+// port's own rate and the carry matrix of its tick length
 void Graph::upload_loudness(size_t fpc) {
-    loud_fpc_ = fpc;
-    const size_t n = loudness_.size();
-    std::vector<uint32_t> order, tail;
-    for (uint32_t i = 0; i < (uint32_t)n; ++i) {
-        int32_t o = (int32_t)loudness_[i].node;
-        while (nodes_[o].elided && nodes_[o].owner >= 0) o = nodes_[o].owner;   // the node whose launch writes the port
-        (tail_gi_ >= 0 && nodes_[o].group >= tail_gi_ ? tail : order).push_back(i);
-    }
-    loud_n_head_ = (uint32_t)order.size();
-    order.insert(order.end(), tail.begin(), tail.end());
-    std::vector<LoudDesc> d(2 * n);
-    for (uint32_t par = 0; par < 2; ++par)
-        for (size_t k = 0; k < n; ++k) {
-            const mx_port_ref tp = loudness_[order[k]];
-            const Node& nd = nodes_[tp.node];
-            LoudDesc& m = d[par * n + k];
-            if (nd.bound && tp.port == 0) m.p = nd.bound;
-            else m.p = (const float*)slab_.p + (par && nd.out_off2[tp.port] != SIZE_MAX ? nd.out_off2[tp.port] : nd.out_off[tp.port]);
-            m.frames = (uint32_t)(fpc * nd.dom_num / nd.dom_den);
-            m.layout = nd.out_dup[tp.port] ? METER_DUP : (nd.out_type[tp.port] == MX_MONO ? METER_MONO : METER_STEREO);
-            m.slot = order[k]; m._pad = 0;
-        }
-    loud_desc_.alloc(d.size() * sizeof(LoudDesc));
-    hip_check(hipMemcpy(loud_desc_.p, d.data(), d.size() * sizeof(LoudDesc), hipMemcpyHostToDevice), "hipMemcpy(loudness descriptors)");
+    const size_t n = loudness_.ports.size();
+    const std::vector<TapDesc> d = tap_descs(loudness_, fpc);
+    upload_tap_descs(loudness_, d.data(), d.size() * sizeof(TapDesc), fpc, n * sizeof(LoudTick));
     // LoudCoef[n] by slot | interp[36]; taps of one rate domain share one evaluation
     std::vector<unsigned char> tab(n * sizeof(LoudCoef) + 36 * sizeof(float));
     std::map<std::pair<uint32_t, uint32_t>, LoudCoef> by_dom;
     for (size_t i = 0; i < n; ++i) {
-        const Node& nd = nodes_[loudness_[i].node];
+        const Node& nd = nodes_[loudness_.ports[i].node];
         auto it = by_dom.find({nd.dom_num, nd.dom_den});
         if (it == by_dom.end()) {
             LoudCoef c;
@@ -1910,82 +1854,50 @@ void Graph::upload_loudness(size_t fpc) {
     loud_tab_.alloc(tab.size());
     hip_check(hipMemcpy(loud_tab_.p, tab.data(), tab.size(), hipMemcpyHostToDevice), "hipMemcpy(loudness tables)");
     loud_max_ticks_ = (uint32_t)std::max<size_t>(1, cap_frames_ / fpc);
-    const size_t need = (size_t)loud_max_ticks_ * n * sizeof(LoudTick), need_walk = (size_t)loud_max_ticks_ * n * 2 * 4 * sizeof(double);
-    if (!loud_rec_.p || loud_rec_.bytes < need) loud_rec_.alloc(need);
+    const size_t need_walk = (size_t)loud_max_ticks_ * n * 2 * 4 * sizeof(double);
     if (!loud_walk_.p || loud_walk_.bytes < need_walk) loud_walk_.alloc(need_walk);
 }
 
-// The run's loudness launches, after its last span and behind the spectrum taps.  launch_spectrum_taps's ordering argument holds word for
-// word: a tap read on stream_ is queued behind the run's producers through the descriptor of the run's buffer parity; a tap on an output of
-// the tail is held back with it (deferred_.loudness) and goes on the tail stream, covered by ev_tail_done_.  The three tap sets only read
-// the ports and write disjoint records.  The carried state follows the spectrum history's argument: a group's launches of consecutive runs
-// follow each other on that group's stream, the filter state is updated in place by the one lane that owns it, and each run reads the
-// history buffers the previous one wrote (loud_hist_cur_ flips once per run for both groups, whose slots are disjoint).
+// The filter state is updated in place by the one lane that owns it; each run reads the history buffers the previous one wrote
+// (loud_hist_cur_ flips once per run).
 void Graph::launch_loudness_taps(uint32_t n_calls, ProfSpan* prof) {
     if (loudness_.empty()) return;
-    const uint32_t n = (uint32_t)loudness_.size();
+    const uint32_t n = loudness_.size();
     double* state = (double*)loud_carry_.p;
     double* eh = state + (size_t)n * 8;
     float* xh = (float*)(eh + 2 * (size_t)n * LOUD_HIST_TICKS);
     const uint32_t cur = loud_hist_cur_;
     loud_hist_cur_ ^= 1u;
-    LoudRun all{(const LoudDesc*)loud_desc_.p + (size_t)(parity_ & 1u) * n, n, n_calls, n, loud_par_.momentary_ticks, loud_par_.short_ticks,
-                (const LoudCoef*)loud_tab_.p, (const float*)((const LoudCoef*)loud_tab_.p + n), state, (double*)loud_walk_.p, loud_max_ticks_,
-                eh + (size_t)cur * n * LOUD_HIST_TICKS, eh + (size_t)(cur ^ 1u) * n * LOUD_HIST_TICKS,
-                xh + (size_t)cur * n * 2 * LOUD_HIST_FRAMES, xh + (size_t)(cur ^ 1u) * n * 2 * LOUD_HIST_FRAMES, (LoudTick*)loud_rec_.p};
-    const uint32_t n_head = overlap_this_run_ ? loud_n_head_ : n;
-    if (n_head < n) { LoudRun t = all; t.desc = all.desc + n_head; t.n = n - n_head; deferred_.loudness.push_back(t); }
-    all.n = n_head;
-    if (n_head) launch_loudness(all, stream_);
-    if (!prof) return;
-    if (n_head) { hip_check(hipEventRecord(prof->meters_end, stream_), "hipEventRecord"); prof->meters = true; }   // (again, when meters or spectra recorded it: the later record holds)
-    prof->meters_tail = !(deferred_.meters.empty() && deferred_.spectra.empty() && deferred_.loudness.empty());
+    launch_tap_set(loudness_, LoudRun{(const TapDesc*)loudness_.desc.p, n, n_calls, n, loud_par_.momentary_ticks, loud_par_.short_ticks,
+                                      (const LoudCoef*)loud_tab_.p, (const float*)((const LoudCoef*)loud_tab_.p + n), state, (double*)loud_walk_.p, loud_max_ticks_,
+                                      eh + (size_t)cur * n * LOUD_HIST_TICKS, eh + (size_t)(cur ^ 1u) * n * LOUD_HIST_TICKS,
+                                      xh + (size_t)cur * n * 2 * LOUD_HIST_FRAMES, xh + (size_t)(cur ^ 1u) * n * 2 * LOUD_HIST_FRAMES, (LoudTick*)loudness_.rec.p}, prof);
 }
 
 void Graph::read_loudness(uint32_t first, uint32_t n, LoudTick* dst, size_t cap) {
-    hip_check(hipSetDevice(device_), "hipSetDevice");
-    if (loudness_.empty()) throw Error(MX_ERR_INVALID, "no loudness taps are set");
-    if ((uint64_t)first + n > loud_run_ticks_) throw Error(MX_ERR_INVALID, "the window lies beyond the last run (or no run since the loudness taps were set)");
-    const size_t per_tick = loudness_.size(), count = (size_t)n * per_tick;
-    if (cap < count) throw Error(MX_ERR_INVALID, "cap is smaller than n_ticks x taps");
-    if (count && !dst) throw Error(MX_ERR_INVALID, "dst is NULL");
-    if (!count) return;
-    wait_tail(-1);
-    hip_check(hipMemcpyAsync(dst, (const LoudTick*)loud_rec_.p + (size_t)first * per_tick, count * sizeof(LoudTick), hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(D2H)");
-    sync();
+    read_taps(loudness_, first, n, dst, cap, loudness_.ports.size(), sizeof(LoudTick), "n_ticks x taps");
 }
 
-// ---- stereo field taps (mixlab_gpu.h mx_graph_set_stereo) ----
+// ---- stereo field taps ----
 
 void Graph::set_stereo(const mx_port_ref* ports, size_t n, const mx_stereo_params* params) {
     hip_check(hipSetDevice(device_), "hipSetDevice");
-    if (n && (!ports || !params)) throw Error(MX_ERR_INVALID, "ports / params is NULL");
-    if (n > 0xffffffu) throw Error(MX_ERR_INVALID, "more than 2^24 stereo taps");
+    check_tap_args(stereo_, ports, params, n);
     if (n) {
         if (params->window_ticks < 1 || params->window_ticks > 1024) throw Error(MX_ERR_INVALID, "mx_stereo_params: window_ticks must be 1 .. 1024");
         if (params->grid != 0 && params->grid != 64 && params->grid != 128) throw Error(MX_ERR_INVALID, "mx_stereo_params: grid must be 0, 64 or 128");
         if (params->zoom_log2 > 8) throw Error(MX_ERR_INVALID, "mx_stereo_params: zoom_log2 must be 0 .. 8");
         if (params->grid && params->hop == 0) throw Error(MX_ERR_INVALID, "mx_stereo_params: hop must be >= 1 with a goniometer");
     }
-    std::vector<uint64_t> keys(n);
-    for (size_t i = 0; i < n; ++i) {
-        const mx_port_ref pr = ports[i];
-        if (pr.node >= nodes_.size() || pr.port >= nodes_[pr.node].out_type.size()) throw Error(MX_ERR_INVALID, "stereo: output terminal out of range");
-        const Node& nd = nodes_[pr.node];
-        if (nd.out_type[pr.port] != MX_STEREO) throw Error(MX_ERR_TYPE, "stereo: a video or mono port has no stereo field");
-        if (nd.out_elided[pr.port]) throw Error(MX_ERR_INVALID, "port is not materialised: it only feeds a fused consumer (build with MX_FLAG_NO_FUSE to observe it)");
-        keys[i] = (uint64_t)pr.node << 32 | pr.port;
-    }
-    { std::vector<uint64_t> k = keys; std::sort(k.begin(), k.end()); if (std::adjacent_find(k.begin(), k.end()) != k.end()) throw Error(MX_ERR_INVALID, "stereo: duplicate (node, port)"); }
-    const size_t fpc = stereo_fpc_ ? stereo_fpc_ : spt_;
-    if (n && params->grid) stereo_gon_room(fpc, n, params->grid, params->hop);   // (throws before anything changed)
+    check_tap_ports(stereo_, ports, n);
+    if (n && params->grid) stereo_gon_room(tap_fpc_, n, params->grid, params->hop);   // (throws before anything changed)
     // like set_loudness: the last run's launches are done with the records and the carried state; the second-stream mode stays on
     sync();
-    stereo_.assign(ports, ports + n);
-    stereo_run_ticks_ = 0; stereo_hist_cur_ = 0;
+    stereo_.ports.assign(ports, ports + n);
+    stereo_.run_ticks = 0; stereo_hist_cur_ = 0;
     stereo_c_ = 0; stereo_gon_n_ = 0; stereo_run_seen_ = false;
-    stereo_rec_.free_(); stereo_gon_rec_.free_(); stereo_carry_.free_(); stereo_gon_carry_.free_();
-    if (stereo_.empty()) { stereo_desc_.free_(); stereo_par_ = mx_stereo_params{0, 0, 0, 0}; return; }
+    stereo_.rec.free_(); stereo_gon_rec_.free_(); stereo_carry_.free_(); stereo_gon_carry_.free_();
+    if (stereo_.empty()) { stereo_.desc.free_(); stereo_par_ = mx_stereo_params{0, 0, 0, 0}; return; }
     stereo_par_ = *params;
     if (!stereo_par_.grid) stereo_par_.hop = 1;   // (ignored without a goniometer)
     // window history and carried grids start as zero: the stream before this call reads as +0.0, c = 0
@@ -1998,7 +1910,7 @@ void Graph::set_stereo(const mx_port_ref* ports, size_t n, const mx_stereo_param
         hip_check(hipMemsetAsync(stereo_gon_carry_.p, 0, grid_bytes, stream_), "hipMemsetAsync(goniometer grids)");
     }
     hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
-    upload_stereo(fpc);
+    upload_stereo(tap_fpc_);
 }
 
 // the most goniometer records one run can emit at this call length (a run of T ticks that starts anywhere in a hop emits at most
@@ -2010,50 +1922,21 @@ size_t Graph::stereo_gon_room(size_t fpc, size_t n, uint32_t grid, uint32_t hop)
     return cap;
 }
 
-// As upload_loudness: the descriptors of every tap for both buffer parities in launch order and room for a whole submission's records.  The
-// stream is quiescent.  The carried state (window history, grids, c) is untouched.
+// beside the descriptors: room for the goniometer records a run can emit (refused before anything is touched)
 void Graph::upload_stereo(size_t fpc) {
-    const size_t n = stereo_.size();
-    const size_t gon_cap = stereo_par_.grid ? stereo_gon_room(fpc, n, stereo_par_.grid, stereo_par_.hop) : 0;
-    stereo_fpc_ = fpc;
-    std::vector<uint32_t> order, tail;
-    for (uint32_t i = 0; i < (uint32_t)n; ++i) {
-        int32_t o = (int32_t)stereo_[i].node;
-        while (nodes_[o].elided && nodes_[o].owner >= 0) o = nodes_[o].owner;   // the node whose launch writes the port
-        (tail_gi_ >= 0 && nodes_[o].group >= tail_gi_ ? tail : order).push_back(i);
-    }
-    stereo_n_head_ = (uint32_t)order.size();
-    order.insert(order.end(), tail.begin(), tail.end());
-    std::vector<StereoDesc> d(2 * n);
-    for (uint32_t par = 0; par < 2; ++par)
-        for (size_t k = 0; k < n; ++k) {
-            const mx_port_ref tp = stereo_[order[k]];
-            const Node& nd = nodes_[tp.node];
-            StereoDesc& m = d[par * n + k];
-            if (nd.bound && tp.port == 0) m.p = nd.bound;
-            else m.p = (const float*)slab_.p + (par && nd.out_off2[tp.port] != SIZE_MAX ? nd.out_off2[tp.port] : nd.out_off[tp.port]);
-            m.frames = (uint32_t)(fpc * nd.dom_num / nd.dom_den);
-            m.layout = nd.out_dup[tp.port] ? METER_DUP : METER_STEREO;
-            m.slot = order[k]; m._pad = 0;
-        }
-    stereo_desc_.alloc(d.size() * sizeof(StereoDesc));
-    hip_check(hipMemcpy(stereo_desc_.p, d.data(), d.size() * sizeof(StereoDesc), hipMemcpyHostToDevice), "hipMemcpy(stereo descriptors)");
-    const size_t need = std::max<size_t>(1, cap_frames_ / fpc) * n * sizeof(StereoTick), need_gon = gon_cap * n * stereo_gonio_record_bytes(stereo_par_.grid);
-    if (!stereo_rec_.p || stereo_rec_.bytes < need) stereo_rec_.alloc(need);
+    const size_t n = stereo_.ports.size();
+    const size_t need_gon = stereo_par_.grid ? stereo_gon_room(fpc, n, stereo_par_.grid, stereo_par_.hop) * n * stereo_gonio_record_bytes(stereo_par_.grid) : 0;
+    const std::vector<TapDesc> d = tap_descs(stereo_, fpc);
+    upload_tap_descs(stereo_, d.data(), d.size() * sizeof(TapDesc), fpc, n * sizeof(StereoTick));
     if (need_gon && (!stereo_gon_rec_.p || stereo_gon_rec_.bytes < need_gon)) stereo_gon_rec_.alloc(need_gon);
 }
 
-// The run's stereo field launches, after its last span and behind the loudness taps.  launch_loudness_taps's ordering argument holds word
-// for word: a tap read on stream_ is queued behind the run's producers through the descriptor of the run's buffer parity; a tap on an output
-// of the tail is held back with it (deferred_.stereo) and goes on the tail stream, covered by ev_tail_done_.  The tap sets only read the
-// ports and write disjoint records.  The carried state follows the loudness history's argument: a group's launches of consecutive runs
-// follow each other on that group's stream, each run reads the history buffers the previous one wrote (stereo_hist_cur_ flips once per run
-// for both groups, whose slots are disjoint), and a tap's carried grid and its records are touched by that tap's group alone -- which is why
-// k_stereo_emit and not a memset on stream_ clears the records.  The counter c lives on the host: the run's phase and emissions are launch
-// arguments.
+// Each run reads the window history the previous one wrote (stereo_hist_cur_ flips once per run).  A tap's carried grid and its goniometer
+// records are touched by that tap's group alone -- which is why k_stereo_emit and not a memset on stream_ clears the records.  The counter
+// c lives on the host: the run's phase and emissions are launch arguments.
 void Graph::launch_stereo_taps(uint32_t n_calls, ProfSpan* prof) {
     if (stereo_.empty()) return;
-    const uint32_t n = (uint32_t)stereo_.size();
+    const uint32_t n = stereo_.size();
     double* hist = (double*)stereo_carry_.p;
     const size_t hist_words = (size_t)n * STEREO_HIST_TICKS * 3;
     const uint32_t cur = stereo_hist_cur_;
@@ -2062,29 +1945,13 @@ void Graph::launch_stereo_taps(uint32_t n_calls, ProfSpan* prof) {
     const uint32_t n_emit = grid ? (uint32_t)(((uint64_t)phase + n_calls) / hop) : 0u;
     stereo_c_ += n_calls;
     stereo_gon_n_ = n_emit; stereo_run_seen_ = true;
-    StereoRun all{(const StereoDesc*)stereo_desc_.p + (size_t)(parity_ & 1u) * n, n, n_calls, n, stereo_par_.window_ticks,
-                  hist + (size_t)cur * hist_words, hist + (size_t)(cur ^ 1u) * hist_words, (StereoTick*)stereo_rec_.p,
-                  grid, stereo_par_.zoom_log2, hop, phase, n_emit, 8u + grid * grid, (uint32_t*)stereo_gon_rec_.p, (uint32_t*)stereo_gon_carry_.p};
-    const uint32_t n_head = overlap_this_run_ ? stereo_n_head_ : n;
-    if (n_head < n) { StereoRun t = all; t.desc = all.desc + n_head; t.n = n - n_head; deferred_.stereo.push_back(t); }
-    all.n = n_head;
-    if (n_head) launch_stereo(all, stream_);
-    if (!prof) return;
-    if (n_head) { hip_check(hipEventRecord(prof->meters_end, stream_), "hipEventRecord"); prof->meters = true; }   // (again, when an earlier tap set recorded it: the later record holds)
-    prof->meters_tail = !(deferred_.meters.empty() && deferred_.spectra.empty() && deferred_.loudness.empty() && deferred_.stereo.empty());
+    launch_tap_set(stereo_, StereoRun{(const TapDesc*)stereo_.desc.p, n, n_calls, n, stereo_par_.window_ticks,
+                                      hist + (size_t)cur * hist_words, hist + (size_t)(cur ^ 1u) * hist_words, (StereoTick*)stereo_.rec.p,
+                                      grid, stereo_par_.zoom_log2, hop, phase, n_emit, 8u + grid * grid, (uint32_t*)stereo_gon_rec_.p, (uint32_t*)stereo_gon_carry_.p}, prof);
 }
 
 void Graph::read_stereo(uint32_t first, uint32_t n, StereoTick* dst, size_t cap) {
-    hip_check(hipSetDevice(device_), "hipSetDevice");
-    if (stereo_.empty()) throw Error(MX_ERR_INVALID, "no stereo taps are set");
-    if ((uint64_t)first + n > stereo_run_ticks_) throw Error(MX_ERR_INVALID, "the window lies beyond the last run (or no run since the stereo taps were set)");
-    const size_t per_tick = stereo_.size(), count = (size_t)n * per_tick;
-    if (cap < count) throw Error(MX_ERR_INVALID, "cap is smaller than n_ticks x taps");
-    if (count && !dst) throw Error(MX_ERR_INVALID, "dst is NULL");
-    if (!count) return;
-    wait_tail(-1);
-    hip_check(hipMemcpyAsync(dst, (const StereoTick*)stereo_rec_.p + (size_t)first * per_tick, count * sizeof(StereoTick), hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(D2H)");
-    sync();
+    read_taps(stereo_, first, n, dst, cap, stereo_.ports.size(), sizeof(StereoTick), "n_ticks x taps");
 }
 
 size_t Graph::read_goniometers(void* dst, size_t cap_bytes) {
@@ -2092,7 +1959,7 @@ size_t Graph::read_goniometers(void* dst, size_t cap_bytes) {
     if (stereo_.empty()) throw Error(MX_ERR_INVALID, "no stereo taps are set");
     if (!stereo_par_.grid) throw Error(MX_ERR_INVALID, "the stereo taps were set without a goniometer (grid = 0)");
     if (!stereo_run_seen_) throw Error(MX_ERR_INVALID, "no run since the stereo taps were set");
-    const size_t count = (size_t)stereo_gon_n_ * stereo_.size(), bytes = count * stereo_gonio_record_bytes(stereo_par_.grid);
+    const size_t count = (size_t)stereo_gon_n_ * stereo_.ports.size(), bytes = count * stereo_gonio_record_bytes(stereo_par_.grid);
     if (cap_bytes < bytes) throw Error(MX_ERR_INVALID, "cap_bytes is smaller than emissions x taps x record bytes");
     if (bytes && !dst) throw Error(MX_ERR_INVALID, "dst is NULL");
     if (bytes) {

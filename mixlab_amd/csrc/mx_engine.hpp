@@ -6,6 +6,7 @@
 // dependency level into one launch, and runs n_ticks ticks per submission.
 #pragma once
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <functional>
 #include <hip/hip_runtime.h>
@@ -14,6 +15,7 @@
 #include <memory>
 #include <string>
 #include <deque>
+#include <variant>
 #include <vector>
 
 #include "mx_common.hpp"
@@ -232,14 +234,25 @@ private:
     size_t od_offset(const Node& n, uint32_t tick) const;                // float offset of tick `tick` of the last run in the hand-off
     struct ProfSpan;
     void launch_outputs(uint64_t t0, uint32_t call_off, uint32_t n_calls, ProfSpan* prof);   // the span's OutputDevice launches
-    void upload_meters(size_t fpc);                                      // the taps' descriptors (both parities) and record room, on a quiescent stream
-    void launch_meter_taps(uint32_t n_calls, ProfSpan* prof);           // the run's meter launches (after its last span)
-    void upload_spectra(size_t fpc);                                     // the spectrum taps' descriptors (both parities) and record room, on a quiescent stream
-    void launch_spectrum_taps(uint32_t n_calls, ProfSpan* prof);        // the run's spectrum launches (after its last span, behind the meters)
-    void upload_loudness(size_t fpc);                                    // the loudness taps' descriptors (both parities), coefficients and record room, on a quiescent stream
-    void launch_loudness_taps(uint32_t n_calls, ProfSpan* prof);        // the run's loudness launches (after its last span, behind the spectrum taps)
-    void upload_stereo(size_t fpc);                                      // the stereo field taps' descriptors (both parities) and record room, on a quiescent stream
-    void launch_stereo_taps(uint32_t n_calls, ProfSpan* prof);          // the run's stereo field launches (after its last span, behind the loudness taps)
+    // the audio tap sets (meters, spectrum, loudness, stereo field): what the four share is written once, for "a tap set"
+    struct AudioTapSet;
+    void check_tap_args(const AudioTapSet& s, const void* ports, const void* params, size_t n) const;
+    void check_tap_ports(const AudioTapSet& s, const mx_port_ref* ports, size_t n, const std::function<void(size_t, const Node&)>& own_check = nullptr) const;
+    std::vector<TapDesc> tap_descs(AudioTapSet& s, size_t fpc) const;     // launch order and n_head; TapDesc[2][n] in launch order, one row per buffer parity
+    void upload_tap_descs(AudioTapSet& s, const void* d, size_t bytes, size_t fpc, size_t tick_bytes);   // ... to the device, and room for a whole submission's records
+    template <class Run> void launch_tap_set(const AudioTapSet& s, Run all, ProfSpan* prof);   // the run's launches of one set: on stream_, or held back with the tail
+    void read_taps(const AudioTapSet& s, uint32_t first, uint32_t n, void* dst, size_t cap, size_t tick_items, size_t item_bytes, const char* cap_what);
+    void reupload_taps(size_t fpc);                                      // every set's descriptors, tables and room again (the ports moved, or the call length did), on a quiescent stream
+    std::array<AudioTapSet*, 4> tap_sets() { return {&meters_, &spectra_, &loudness_, &stereo_}; }   // in launch order
+    // each set's own part: what it uploads beside the descriptors, and the run struct of its launches (after the run's last span)
+    void upload_meters(size_t fpc);
+    void upload_spectra(size_t fpc);
+    void upload_loudness(size_t fpc);
+    void upload_stereo(size_t fpc);
+    void launch_meter_taps(uint32_t n_calls, ProfSpan* prof);
+    void launch_spectrum_taps(uint32_t n_calls, ProfSpan* prof);
+    void launch_loudness_taps(uint32_t n_calls, ProfSpan* prof);
+    void launch_stereo_taps(uint32_t n_calls, ProfSpan* prof);
     size_t stereo_gon_room(size_t fpc, size_t n, uint32_t grid, uint32_t hop) const;   // goniometer records a run can emit; MX_ERR_NOMEM beyond 4 GiB
     void refresh_gates(Group& g, uint32_t run_calls);
     uint32_t trigger_of_row(const Group& g, uint32_t row) const;        // node id of the Trigger behind row `row` of a gated group, or ~0u
@@ -277,10 +290,10 @@ private:
     // when the bank was nearly done: no overlap at all), the EqThree workgroups are placed on an empty chip, and the Mixer's waves fill what is left.  Every join
     // (mx_graph_sync, read-backs, mx_graph_tail_stream, an exchange's submit, a cut run) releases a held launch at once.  The measurements: profiles/r05/short_submission_regime.md.
     // The tail: every Mixer group from tail_gi_ on (a bank, or a bank and the buses above it), in order; outs: OutputDevices that read the tail's outputs, behind it;
-    // meters: the taps on the tail's outputs, behind those.  prof: the span's profile record (nullptr: not profiled), whose tail events the release records.
+    // taps: the audio tap sets' launches on the tail's outputs, behind those, in the sets' order.  prof: the span's profile record (nullptr: not profiled), whose tail events the release records.
     struct TailLaunch { const void* desc = nullptr; uint32_t n = 0, max_ch = 0; size_t frames = 0; int dup_mode = 0; hipEvent_t prof_ev = nullptr; };
     struct DeferredTail { bool pending = false; std::vector<TailLaunch> items; uint32_t parity = 0; ProfSpan* prof = nullptr;
-                          std::vector<OutRun> outs; std::vector<MeterRun> meters; std::vector<SpecRun> spectra; std::vector<LoudRun> loudness; std::vector<StereoRun> stereo; } deferred_;   // spectra, loudness, stereo: those taps on the tail's outputs, behind the meters
+                          std::vector<OutRun> outs; std::vector<std::variant<MeterRun, SpecRun, LoudRun, StereoRun>> taps; } deferred_;
     std::function<void(hipStream_t)> tail_hook_;
     std::vector<hipEvent_t> head_waits_;
     uint64_t n_gated_ = 0, n_at_once_ = 0;
@@ -301,45 +314,46 @@ private:
     std::vector<uint32_t> plotter_nodes_;   // launched Plotter nodes
     std::vector<uint32_t> video_order_;     // the video nodes of order_, in run order
     std::vector<uint32_t> od_nodes_;        // OutputDevice nodes of order_ (never in a launch group: launched after the span's groups, behind their input's producer)
-    // level meters: the taps in set order; launch order puts the taps read on stream_ first (meter_n_head_ of them), then the taps on outputs of
-    // the tail (behind the Mixer bank on its stream while the second-stream mode is on).  meter_desc_: MeterDesc[2][n] in launch order, one row
-    // per buffer parity; meter_rec_: MeterTick[max ticks][n]; meter_state_: MeterHold[n][2]
-    struct MeterTap { uint32_t node, port, hold_ticks; float release; };
-    std::vector<MeterTap> meters_;
-    uint32_t meter_n_head_ = 0;
-    DevBuf meter_desc_, meter_rec_, meter_state_;
-    size_t meter_fpc_ = 0;                  // frames per call the descriptors were built for
-    uint32_t meter_run_ticks_ = 0;          // ticks of the last run that measured the current taps (0: none since they were set)
-    // spectrum taps: the same arrangement beside the meters (set order, launch order, spec_n_head_, SpecDesc[2][n]).  spec_rec_:
-    // float[max ticks][n][2][bands]; spec_hist_: float[2][n][2 * n_fft], the buffer a run reads is spec_hist_cur_, it writes the other;
-    // spec_tab_: window, twiddles and band edges on the device
-    std::vector<mx_port_ref> spectra_;
-    uint32_t spec_n_fft_ = 0, spec_n_bands_ = 0, spec_n_head_ = 0, spec_hist_cur_ = 0;
-    DevBuf spec_desc_, spec_rec_, spec_hist_, spec_tab_;
-    size_t spec_fpc_ = 0;
-    uint32_t spec_run_ticks_ = 0;
-    // loudness taps: the same arrangement again (set order, launch order, loud_n_head_, LoudDesc[2][n]).  loud_rec_: LoudTick[max ticks][n];
-    // loud_walk_: double[n][2][max ticks][4], the run's Z_k / S_k; loud_tab_: LoudCoef[n] by slot, then interp[36]; loud_carry_: what a run
-    // hands to the next -- state double[n][2][4] | window history double[2][n][1023] | frame history float[2][n][2][11], of which a run reads
-    // buffer loud_hist_cur_ and writes the other
-    std::vector<mx_port_ref> loudness_;
+    // One audio tap set: the taps in set order (= record slots).  Launch order puts the taps read on stream_ first (n_head of them), then
+    // the taps on outputs of the tail (behind the Mixer bank on its stream while the second-stream mode is on).  desc: the descriptors
+    // [2][n] in launch order, one row per buffer parity; rec: the records [max ticks][n].  tag, noun, no_type: how the messages name the set
+    struct AudioTapSet {
+        const char* tag; const char* noun; const char* no_type;
+        bool stereo_only = false;               // the ports must be stereo (else: anything but video)
+        std::vector<mx_port_ref> ports;
+        uint32_t n_head = 0;
+        uint32_t run_ticks = 0;                 // ticks of the last run that measured the current taps (0: none since they were set)
+        DevBuf desc, rec;
+        bool empty() const { return ports.empty(); }
+        uint32_t size() const { return (uint32_t)ports.size(); }
+    };
+    size_t tap_fpc_ = 0;                        // frames per call every set's descriptors were built for (the tick length until a run says otherwise)
+    // level meters.  desc: MeterDesc; rec: MeterTick; meter_par_: each tap's hold_ticks and release; meter_state_: MeterHold[n][2]
+    AudioTapSet meters_{"meter", "meters", "a video port has no level"};
+    std::vector<mx_meter_params> meter_par_;
+    DevBuf meter_state_;
+    // spectrum taps.  rec: float[2][bands] per tap; spec_hist_: float[2][n][2 * n_fft], the buffer a run reads is spec_hist_cur_, it writes
+    // the other; spec_tab_: window, twiddles and band edges on the device
+    AudioTapSet spectra_{"spectrum", "spectrum taps", "a video port has no spectrum"};
+    uint32_t spec_n_fft_ = 0, spec_n_bands_ = 0, spec_hist_cur_ = 0;
+    DevBuf spec_hist_, spec_tab_;
+    // loudness taps.  rec: LoudTick; loud_walk_: double[n][2][max ticks][4], the run's Z_k / S_k; loud_tab_: LoudCoef[n] by slot, then
+    // interp[36]; loud_carry_: what a run hands to the next -- state double[n][2][4] | window history double[2][n][1023] | frame history
+    // float[2][n][2][11], of which a run reads buffer loud_hist_cur_ and writes the other
+    AudioTapSet loudness_{"loudness", "loudness taps", "a video port has no loudness"};
     mx_loudness_params loud_par_{0, 0};
-    uint32_t loud_n_head_ = 0, loud_hist_cur_ = 0, loud_max_ticks_ = 0;
-    DevBuf loud_desc_, loud_rec_, loud_walk_, loud_tab_, loud_carry_;
-    size_t loud_fpc_ = 0;
-    uint32_t loud_run_ticks_ = 0;
-    // stereo field taps: the same arrangement again (set order, launch order, stereo_n_head_, StereoDesc[2][n]).  stereo_rec_: StereoTick[max
-    // ticks][n]; stereo_carry_: window history double[2][n][1023][3], of which a run reads buffer stereo_hist_cur_ and writes the other;
-    // stereo_gon_rec_: the last run's goniometer records [emission][n], stereo_gon_n_ emissions; stereo_gon_carry_: one record-shaped grid per
-    // tap with the ticks since the last emission.  stereo_c_ is the hop counter c (0 when the taps are set, + the ticks of every run)
-    std::vector<mx_port_ref> stereo_;
+    uint32_t loud_hist_cur_ = 0, loud_max_ticks_ = 0;
+    DevBuf loud_walk_, loud_tab_, loud_carry_;
+    // stereo field taps.  rec: StereoTick; stereo_carry_: window history double[2][n][1023][3], of which a run reads buffer stereo_hist_cur_
+    // and writes the other; stereo_gon_rec_: the last run's goniometer records [emission][n], stereo_gon_n_ emissions; stereo_gon_carry_: one
+    // record-shaped grid per tap with the ticks since the last emission.  stereo_c_ is the hop counter c (0 when the taps are set, + the
+    // ticks of every run)
+    AudioTapSet stereo_{"stereo", "stereo taps", "a video or mono port has no stereo field", true};
     mx_stereo_params stereo_par_{0, 0, 0, 0};
-    uint32_t stereo_n_head_ = 0, stereo_hist_cur_ = 0, stereo_gon_n_ = 0;
+    uint32_t stereo_hist_cur_ = 0, stereo_gon_n_ = 0;
     uint64_t stereo_c_ = 0;
     bool stereo_run_seen_ = false;
-    DevBuf stereo_desc_, stereo_rec_, stereo_carry_, stereo_gon_rec_, stereo_gon_carry_;
-    size_t stereo_fpc_ = 0;
-    uint32_t stereo_run_ticks_ = 0;
+    DevBuf stereo_carry_, stereo_gon_rec_, stereo_gon_carry_;
     // video scope taps: the taps in set order; scope_rec_: the last run's records [recorded tick][tap], scope_cap_ ticks of room.  scope_c_ is the
     // hop counter (0 when the taps are set, +1 per video tick, carried across runs); a tick is recorded when scope_c_ % hop == 0 before the increment
     std::vector<mx_port_ref> scopes_;

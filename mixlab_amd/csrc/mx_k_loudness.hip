@@ -46,7 +46,7 @@ __global__ __launch_bounds__(64) void k_loud_walk(const LoudRun r, uint32_t grou
     __shared__ float buf[64 * LOUD_ROW];
     const uint32_t lane = threadIdx.x;
     const uint32_t i = blockIdx.x / groups, g = blockIdx.x - i * groups;
-    const LoudDesc d = r.desc[i];
+    const TapDesc d = r.desc[i];
     const uint32_t nch = loud_nch(d.layout), tg = 64u / nch;   // ticks of this block
     const uint32_t t0 = g * tg;
     if (t0 >= r.n_ticks) return;   // block-uniform (the grid is sized for 32-tick groups)
@@ -122,7 +122,7 @@ __global__ __launch_bounds__(64) void k_loud_scan(const LoudRun r) {
     const uint32_t idx = blockIdx.x * 64u + threadIdx.x;
     const uint32_t i = idx >> 1, c = idx & 1u;
     if (i >= r.n) return;
-    const LoudDesc d = r.desc[i];
+    const TapDesc d = r.desc[i];
     if (c >= loud_nch(d.layout)) return;
     const double* __restrict__ Pm = r.coef[d.slot].carry;
     double P[16];
@@ -170,7 +170,7 @@ __global__ __launch_bounds__(64 * LOUD_PEAK_WAVES) void k_loud_peak(const LoudRu
     for (uint32_t k = 0; k < 36u; ++k) tab[k] = r.interp[k];
     for (uint64_t w = (uint64_t)blockIdx.x * LOUD_PEAK_WAVES + (threadIdx.x >> 6); w < pairs; w += waves) {   // wave-uniform
         const uint32_t i = (uint32_t)(w / r.n_ticks), t = (uint32_t)(w - (uint64_t)i * r.n_ticks);
-        const LoudDesc d = r.desc[i];
+        const TapDesc d = r.desc[i];
         const uint32_t F = d.frames, nch = loud_nch(d.layout);
         const float* __restrict__ hin = r.xhist_in + (size_t)d.slot * 2u * LOUD_HIST_FRAMES;   // [channel][11]
         // frame q of the run (q >= -11): before the run from the history, else from the port, which holds every tick of the run
@@ -247,7 +247,7 @@ __global__ __launch_bounds__(256) void k_loud_window(const LoudRun r) {
     rec->short_sq = ss;
 }
 
-void launch_loudness(const LoudRun& r, hipStream_t s) {
+void launch_taps(const LoudRun& r, hipStream_t s) {
     if (!r.n || !r.n_ticks) return;
     const uint64_t pairs = (uint64_t)r.n * r.n_ticks;
     const uint32_t pk_blocks = (uint32_t)std::min<uint64_t>((pairs + LOUD_PEAK_WAVES - 1) / LOUD_PEAK_WAVES, 256u * 16u);   // grid-stride beyond 16 blocks per CU

@@ -140,7 +140,7 @@ __global__ __launch_bounds__(256) void k_meter_hold(const MeterDesc* __restrict_
     if (walker) st[ch] = MeterHold{h, a};
 }
 
-void launch_meters(const MeterRun& r, hipStream_t s) {
+void launch_taps(const MeterRun& r, hipStream_t s) {
     if (!r.n || !r.n_ticks) return;
     const uint64_t pairs = (uint64_t)r.n * r.n_ticks;
     const uint32_t blocks = (uint32_t)std::min<uint64_t>((pairs + METER_WAVES - 1) / METER_WAVES, 256u * 16u);   // grid-stride beyond 16 blocks per CU

@@ -51,7 +51,7 @@ __global__ __launch_bounds__(SPEC_THREADS) void k_spectrum(const SpecRun r) {
     const double scale = 4.0 / ((double)N * (double)N);   // a power of two: exact
     for (uint64_t pr = blockIdx.x; pr < pairs; pr += gridDim.x) {   // block-uniform
         const uint32_t i = (uint32_t)(pr / r.n_ticks), t = (uint32_t)(pr - (uint64_t)i * r.n_ticks);
-        const SpecDesc d = r.desc[i];
+        const TapDesc d = r.desc[i];
         const float* __restrict__ hist = r.hist_in + (size_t)d.slot * 2u * N;
         // stream position of the frame's first sample relative to the run's first: >= -N, since the frame ends inside the run
         const int64_t q0 = (int64_t)(t + 1u) * d.frames - (int64_t)N;
@@ -117,7 +117,7 @@ __global__ __launch_bounds__(SPEC_THREADS) void k_spectrum(const SpecRun r) {
 }
 
 __global__ __launch_bounds__(SPEC_THREADS) void k_spectrum_history(const SpecRun r) {
-    const SpecDesc d = r.desc[blockIdx.x];
+    const TapDesc d = r.desc[blockIdx.x];
     const uint32_t N = r.n_fft;
     const float* __restrict__ in = r.hist_in + (size_t)d.slot * 2u * N;
     float* __restrict__ out = r.hist_out + (size_t)d.slot * 2u * N;
@@ -131,7 +131,7 @@ __global__ __launch_bounds__(SPEC_THREADS) void k_spectrum_history(const SpecRun
     }
 }
 
-void launch_spectra(const SpecRun& r, hipStream_t s) {
+void launch_taps(const SpecRun& r, hipStream_t s) {
     if (!r.n || !r.n_ticks) return;
     const uint64_t pairs = (uint64_t)r.n * r.n_ticks;
     const dim3 grid((uint32_t)std::min<uint64_t>(pairs, 256u * 16u)), block(SPEC_THREADS);   // block-stride beyond 16 per CU

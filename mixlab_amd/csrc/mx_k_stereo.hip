@@ -95,7 +95,7 @@ __global__ __launch_bounds__(64 * STEREO_WAVES) void k_stereo_reduce(const Stere
     const uint64_t waves = (uint64_t)gridDim.x * STEREO_WAVES;
     for (uint64_t w = (uint64_t)blockIdx.x * STEREO_WAVES + (threadIdx.x >> 6); w < pairs; w += waves) {   // wave-uniform
         const uint32_t i = (uint32_t)(w / r.n_ticks), t = (uint32_t)(w - (uint64_t)i * r.n_ticks);   // consecutive waves: consecutive ticks of one tap
-        const StereoDesc d = r.desc[i];
+        const TapDesc d = r.desc[i];
         const uint32_t F = d.frames;
         GonTarget g{nullptr, 0.0f, 0.0f, 0u};
         uint32_t* head = nullptr;
@@ -168,7 +168,7 @@ __global__ __launch_bounds__(256) void k_stereo_window(const StereoRun r) {
     rec->win_ll = wl; rec->win_rr = wr; rec->win_lr = wx;
 }
 
-void launch_stereo(const StereoRun& r, hipStream_t s) {
+void launch_taps(const StereoRun& r, hipStream_t s) {
     if (!r.n || !r.n_ticks) return;
     if (r.grid && r.n_emit) {
         const uint64_t words = (uint64_t)r.n * r.n_emit * r.rec_words;

@@ -156,10 +156,14 @@ struct OutRun {
 };
 uint32_t out_route_blocks(size_t frames_per_tick, uint32_t channels);
 void launch_output_device(const OutRun& r, hipStream_t s);
-// Level meters (mx_k_meter.hip, mixlab_gpu.h mx_graph_set_meters): one descriptor per tap and buffer parity, the per-tick record (=
-// mx_meter_tick) and each channel's peak-hold state
+// The audio tap sets (meters, spectrum, loudness, stereo field) read their ports through one descriptor per tap and buffer parity.  Their
+// run structs begin alike -- desc, n, n_ticks, stride -- and launch_taps is overloaded on them, so the engine splits and defers any of them
+// the same way (Graph::launch_tap_set)
 enum : uint32_t { METER_MONO = 0, METER_STEREO = 1, METER_DUP = 2 };   // METER_DUP: stereo stored as one float per frame (L == R)
-struct MeterDesc { const float* p; uint32_t frames, layout, slot, hold_ticks; float release; uint32_t _pad; };   // p: the port at tick 0 of the run; slot: index in set order
+struct TapDesc { const float* p; uint32_t frames, layout, slot, _pad; };   // p: the port at tick 0 of the run; layout: METER_*; slot: index in set order
+// Level meters (mx_k_meter.hip, mixlab_gpu.h mx_graph_set_meters): the descriptor (TapDesc's first four fields, then the tap's own
+// parameters), the per-tick record (= mx_meter_tick) and each channel's peak-hold state
+struct MeterDesc { const float* p; uint32_t frames, layout, slot, hold_ticks; float release; uint32_t _pad; };
 struct MeterTick { float peak[2], hold[2]; double sum_sq[2]; uint32_t over[2], frames, channels; };
 struct MeterHold { float h; uint32_t a; };
 struct MeterRun {
@@ -167,20 +171,19 @@ struct MeterRun {
     uint32_t n_ticks, stride;                // ticks of the run; records per tick (every tap of the set)
     MeterTick* rec; MeterHold* state;        // rec[tick * stride + slot]; state[2 * slot + channel]
 };
-void launch_meters(const MeterRun& r, hipStream_t s);   // k_meter_reduce, then k_meter_hold
+void launch_taps(const MeterRun& r, hipStream_t s);   // k_meter_reduce, then k_meter_hold
 // Spectrum taps (mx_k_spectrum.hip, mixlab_gpu.h mx_graph_set_spectra): one descriptor per tap and buffer parity.  The history of a tap is
 // the last n_fft frames of its stream before the run, in the port's own layout (one float per frame for mono / dup, two for stereo), kept
 // in two buffers of 2 * n_fft floats each that alternate per run (hist[run parity][slot]).
-struct SpecDesc { const float* p; uint32_t frames, layout, slot, _pad; };   // p: the port at tick 0 of the run; layout: METER_*; slot: index in set order
 struct SpecRun {
-    const SpecDesc* desc; uint32_t n;        // the launch's taps
+    const TapDesc* desc; uint32_t n;        // the launch's taps
     uint32_t n_ticks, stride;                // ticks of the run; taps of the whole set (records per tick)
     uint32_t n_fft, n_bands;
     const float* window; const float2* twiddle; const uint16_t* edges;   // device tables: n_fft, n_fft / 2, n_bands + 1
     const float* hist_in; float* hist_out;   // [slot][2 * n_fft]: read by this run, written for the next
     float* rec;                              // rec[((tick * stride + slot) * 2 + channel) * n_bands + band]
 };
-void launch_spectra(const SpecRun& r, hipStream_t s);   // k_spectrum, then k_spectrum_history
+void launch_taps(const SpecRun& r, hipStream_t s);   // k_spectrum, then k_spectrum_history
 // the tables of the spectrum spec, correctly rounded f32 (host only): window[n_fft], twiddle re / im [n_fft / 2]; false: n_fft is not a supported size
 bool spectrum_tables(uint32_t n_fft, float* window, float* twiddle_re, float* twiddle_im);
 // Loudness taps (mx_k_loudness.hip, mixlab_gpu.h mx_graph_set_loudness): one descriptor per tap and buffer parity, the per-tick record (=
@@ -188,11 +191,10 @@ bool spectrum_tables(uint32_t n_fft, float* window, float* twiddle_re, float* tw
 // LOUD_HIST_TICKS ticks' ksq[0] + ksq[1] and the last LOUD_HIST_FRAMES frames of each channel; the two histories are kept twice and
 // alternate per run like the spectrum taps' (read by this run, written for the next).
 static constexpr uint32_t LOUD_HIST_TICKS = 1023, LOUD_HIST_FRAMES = 11, LOUD_MAX_FRAMES = 1u << 22;
-struct LoudDesc { const float* p; uint32_t frames, layout, slot, _pad; };   // as SpecDesc
 struct LoudTick { double ksq[2], momentary_sq, short_sq; float true_peak[2]; uint32_t frames, channels; };
 struct LoudCoef { double bq[10], carry[16]; };   // shelf b0 b1 b2 a1 a2, high-pass b0 b1 b2 a1 a2; P[r][c] row-major
 struct LoudRun {
-    const LoudDesc* desc; uint32_t n;        // the launch's taps
+    const TapDesc* desc; uint32_t n;        // the launch's taps
     uint32_t n_ticks, stride;                // ticks of the run; taps of the whole set (records per tick)
     uint32_t momentary_ticks, short_ticks;
     const LoudCoef* coef;                    // [slot]
@@ -203,7 +205,7 @@ struct LoudRun {
     const float* xhist_in; float* xhist_out;     // [slot][channel][LOUD_HIST_FRAMES]
     LoudTick* rec;                           // rec[tick * stride + slot]
 };
-void launch_loudness(const LoudRun& r, hipStream_t s);   // k_loud_peak; k_loud_zero, k_loud_scan, k_loud_energy (a one-tick run: one interleaved walk); k_loud_window
+void launch_taps(const LoudRun& r, hipStream_t s);   // k_loud_peak; k_loud_zero, k_loud_scan, k_loud_energy (a one-tick run: one interleaved walk); k_loud_window
 // the tables of the loudness spec (host only): biquads[10], carry[4][4] for a tick of `frames` frames, interp[3][12]; any may be null.
 // false: rate is not finite or not above twice the shelf frequency, or frames is outside 1 .. LOUD_MAX_FRAMES
 bool loudness_tables(double rate, uint32_t frames, double* biquads, double* carry, float* interp);
@@ -212,10 +214,9 @@ bool loudness_tables(double rate, uint32_t frames, double* biquads, double* carr
 // windows' history, and -- with a goniometer -- one grid in the shape of a record (8 header words of which [2] frames and [3] skipped are
 // used, then grid x grid counts) that holds the ticks since the last emission.
 static constexpr uint32_t STEREO_HIST_TICKS = 1023;
-struct StereoDesc { const float* p; uint32_t frames, layout, slot, _pad; };   // as SpecDesc; layout is METER_STEREO or METER_DUP
 struct StereoTick { double sum_ll, sum_rr, sum_lr, win_ll, win_rr, win_lr; uint32_t frames, nonfinite; };
 struct StereoRun {
-    const StereoDesc* desc; uint32_t n;      // the launch's taps
+    const TapDesc* desc; uint32_t n;         // the launch's taps (layout is METER_STEREO or METER_DUP)
     uint32_t n_ticks, stride;                // ticks of the run; taps of the whole set (records per tick)
     uint32_t window_ticks;
     const double* hist_in; double* hist_out; // [slot][STEREO_HIST_TICKS][3]: read by this run, written for the next
@@ -228,7 +229,7 @@ struct StereoRun {
     uint32_t* gon_carry;                     // [slot][rec_words]
 };
 inline size_t stereo_gonio_record_bytes(uint32_t grid) { return 32 + 4 * (size_t)grid * grid; }
-void launch_stereo(const StereoRun& r, hipStream_t s);   // k_stereo_emit (a run that emits), k_stereo_reduce, k_stereo_window
+void launch_taps(const StereoRun& r, hipStream_t s);   // k_stereo_emit (a run that emits), k_stereo_reduce, k_stereo_window
 // Video scope taps (mx_k_scope.hip, mixlab_gpu.h mx_graph_set_video_scopes): ONE launch counts one frame into one record -- the 32-byte
 // header, hist[3][256], wave[wave_cols][256], vec[128][128], all u32.  The counters of the record must be zero when the launch starts (the
 // workgroups add their partial counts with integer atomics); the kernel writes the header itself.  counted = 0: header only.

@@ -281,6 +281,55 @@ def test_all_five_tap_sets_together_from_the_2p40_epoch():
     check_all_five_tap_sets_together(far_first_tick("at_2p40", 735, 12))
 
 
+def test_four_audio_tap_sets_through_the_end_of_the_automatic_tail_mode():
+    """The automatic second-stream mode ends (a stream-ordered consumer takes the Master's raw pointer) while meters, spectrum, loudness and
+    stereo taps are set: every set's descriptors are rebuilt for one stream and one buffer per port, and what the taps carry -- a hold
+    longer than a run, the spectrum history, the loudness and stereo windows, the goniometer grid and its counter -- comes through.  The
+    twin desk without taps, driven identically, gives every port."""
+    import test_gpu_loudness as tl
+    import test_gpu_meters as tm
+    import test_gpu_spectrum as ts
+    sr, spt, n, n_strips, n_fft = 48000, 800, 16, 64, 1024
+    edges = abi.log_band_edges(n_fft, 31, 20.0, 20000.0, 48000.0)
+    ws, mix, srcs, trigs = strips(n_strips, sr)
+    plain = ws.build(max_ticks_per_run=n)    # the same desk without taps
+    g = ws.build(max_ticks_per_run=n)
+    where = [(mix, 0), (mix, 1), (mix + 6, 0), (mix + 6 * 64, 0)]   # Master, Cue, the Amplifiers of strips 0 and 63
+    sets = [(tm, [tm.Tap(nd, p, 2, hold_ticks=40) for nd, p in where]), (ts, [ts.Tap(nd, p, 2, n_fft, edges) for nd, p in where]),
+            (tl, [tl.Tap(nd, p, 2, sr, spt) for nd, p in where])]
+    stereo = [Tap(nd, p) for nd, p in where]
+    tm.set_taps(g, sets[0][1]); ts.set_taps(g, sets[1][1], n_fft, edges); tl.set_taps(g, sets[2][1])
+    set_taps(g, stereo, 24, 64, 0, 24)   # hop 24 against runs of 16: the grid of ticks 48 .. 63 is carried through the mode's end
+    noise = [synth.noise(k, 6 * n * spt) * np.float32(8.0) for k in range(n_strips)]
+    n_emitted = 0
+    for r in range(6):
+        if r == 4:   # the mode ends, in both desks
+            assert g.tail_stream() is not None and plain.tail_stream() is not None
+            g.output_device_ptr(mix, 0); plain.output_device_ptr(mix, 0)
+            assert g.tail_stream() is None and plain.tail_stream() is None
+        for gr in (plain, g):
+            for k, tr in enumerate(trigs):
+                gr.update_params(tr, abi.TriggerParams(1 if (k + r) % 3 else 0))
+            for k, s in enumerate(srcs):
+                gr.write_source(s, noise[k][r * n * spt:(r + 1) * n * spt], n)
+            gr.run_ticks(r * n, n)
+        if r in (0, 2):   # not read: the next run is queued behind it first; the models take the desk's ports from the plain graph
+            for t in [t for _, taps in sets for t in taps] + stereo:
+                t.model.run(t.port_data(plain, n), n)
+            continue
+        for nd, p in where:
+            want = plain.read_output(nd, p, n, True).view(np.uint32)
+            assert np.array_equal(g.read_output(nd, p, n, True).view(np.uint32), want), f"run {r}: taps changed port ({nd}, {p})"
+        for mod, taps in sets:
+            mod.check_run(g, taps, n, f"{mod.__name__} run {r}", port_source=plain)
+        _, em = check_run(g, stereo, n, f"stereo run {r}", port_source=plain)
+        assert len(em) == ((r + 1) * n) // 24 - (r * n) // 24
+        n_emitted += len(em)
+        if r == 1:
+            assert g.tail_stream() is not None   # the mode is on: what follows does end it
+    assert n_emitted == 3  # runs 1, 4 and 5 (run 2's emission was not read)
+
+
 def test_non_finite_subnormal_and_large_samples():
     sr, spt, n = 48000, 800, 4
     ws, ss, smn, amp, g = io_graph(sr, 60, n)
