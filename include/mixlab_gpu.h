@@ -657,6 +657,30 @@ uint32_t mx_video_scaler_tap_count(uint32_t src, uint32_t dst);
 int mx_video_scaler_taps(uint32_t src, uint32_t dst, int32_t* first, int32_t* coef, uint32_t* n_taps);
 /* BUILD-SPECIFIED (no reference counterpart): BT.709 limited-range YUV420P -> RGBA8 (+ optional Q12 3x4 matrix). */
 int mx_video_to_rgba(const mx_dframe* in, void* device_rgba, int32_t rgba_stride, const int32_t* matrix_q12 /* 12 or NULL */, void* stream);
+/* The KEYER (BUILD-SPECIFIED; the reference has none): a chroma or luma key computed on the device.  `in` is yuv420p or yuva420p
+ * (anything else: MX_ERR_INVALID -- conversion is the scaler's business); *out is a NEW yuva420p frame of the same size carrying one reference.  Y is copied, U and V are
+ * copied or spill-suppressed, the coverage plane is the key.  Stride padding is never read as picture.  Integer arithmetic throughout, `/` truncates:
+ *   ramp(d; lo, hi) = 0 if d <= lo, else 255 if d >= hi, else ((d - lo) * 255) / (hi - lo)            (tests in this order: lo == hi is a hard key)
+ *   CHROMA, per chroma sample:  du = U - key_u, dv = V - key_v;  d = floor(sqrt((du du + dv dv) << 8))  (the exact integer root: a distance in 1/16 code values, <= 5769)
+ *     ac = ramp(d; near_q4, far_q4);  coverage of luma sample (x, y) = the 2x bilinear upsample, chroma co-sited with luma (2cx, 2cy):
+ *     cx = x >> 1, cy = y >> 1, cx1 = min(cx + (x & 1), W/2 - 1), cy1 = min(cy + (y & 1), H/2 - 1);  k = (ac[cy][cx] + ac[cy][cx1] + ac[cy1][cx] + ac[cy1][cx1] + 2) >> 2
+ *     (on even (x, y) k = ac[cy][cx]: the compositor's chroma samples, which take the coverage of luma (2x, 2y), read the keyer's own chroma decision back)
+ *   LUMA, per luma sample:  k = ramp(Y * 16; near_q4, far_q4); chroma is copied
+ *   both:  if invert, k = 255 - k;  if `in` carries coverage a_in, k = (k * a_in) / 255;  k is the output coverage byte
+ *   SPILL (chroma mode, active iff spill_strength > 0 and spill_far_q4 > far_q4), per chroma sample, whatever `invert` is:
+ *     w = ((255 - ramp(d; far_q4, spill_far_q4)) * spill_strength) / 255;  U' = 128 + tdiv((U - 128) * (255 - w), 255), V likewise (tdiv: signed, toward zero)
+ * Values outside the ranges in the comments below are MX_ERR_INVALID.  Asynchronous on `stream`, like its neighbours. */
+enum { MX_KEY_CHROMA = 0, MX_KEY_LUMA = 1 };
+typedef struct {
+    uint32_t mode;            /* MX_KEY_CHROMA or MX_KEY_LUMA */
+    uint8_t  key_u, key_v;    /* chroma mode: the key colour */
+    uint8_t  invert;          /* 0 or 1 */
+    uint8_t  _pad;            /* 0 */
+    uint32_t near_q4, far_q4; /* distances in 1/16 of a code value; near <= far <= 65535 */
+    uint32_t spill_far_q4;    /* chroma mode; <= 65535 */
+    uint32_t spill_strength;  /* 0 .. 255; must be 0 in luma mode */
+} mx_video_key_params;        /* 24 bytes */
+int mx_video_key(const mx_dframe* in, const mx_video_key_params* params, mx_dframe** out, void* stream);
 int mx_video_sync(void* stream);
 /* A caller-owned hipStream_t that graphs / scalers / mixers launched pictures on is about to be destroyed: release what the library keeps per (device, stream) for its
  * batched video launches (page-locked descriptor staging, device copies, events, an upload stream).  The library frees this itself for streams it created; for a caller's
@@ -698,6 +722,14 @@ int mx_graph_set_video_source_ring(mx_graph* g, uint32_t node, mx_dframe* const*
  * on the graph's stream.  band_rows = 0 removes the transform. */
 int mx_graph_set_video_source_band(mx_graph* g, uint32_t node, uint32_t in_w, uint32_t in_full_h, uint32_t src_row0, uint32_t slice_rows,
                                    uint32_t full_w, uint32_t full_h, uint32_t row0, uint32_t band_rows);
+/* The keyer as a per-source transform (mx_video_key): on every tick the SOURCE_VIDEO node has a frame -- from mx_graph_set_video_source, _ring,
+ * mx_graph_queue_video_source, and therefore mx_media_source_feed / mx_stream_input_feed -- it delivers the keyed yuva420p frame instead, computed on the graph's stream
+ * before the tick's video work.  Frames are immutable, so a frame is keyed once per setting and the result reused while anything still holds the frame (a repeated frame,
+ * or a ring of n frames, costs n launches, not one per tick); a pooled output frame is rewritten only when nothing else holds a reference to it.  params NULL removes the
+ * transform.  MX_ERR_TYPE for a node that is not a SOURCE_VIDEO, MX_ERR_INVALID for bad parameters and together with mx_graph_set_video_source_band (a band-scaled layer
+ * cannot carry coverage).  A source frame that is not yuv420p / yuva420p fails the run with MX_ERR_INVALID, mx_last_error naming the node.  A scope tap on the source's
+ * port sees the keyed frame.  mx_graph_adopt_state does not carry the setting. */
+int mx_graph_set_video_source_key(mx_graph* g, uint32_t node, const mx_video_key_params* params /* NULL removes */);
 /* One frame due on one tick of a SOURCE_VIDEO node: tick `tick` (absolute, as in mx_graph_run_ticks' first_tick + k) emits `frame` with the
  * given duration hint and tick offset; ticks without an entry emit None.  Entries are queued in ascending tick order, one per tick
  * (MX_ERR_INVALID otherwise), and while any is queued they take the place of mx_graph_set_video_source[_ring].  What

@@ -202,6 +202,17 @@ class VideoScopeParams(C.Structure):
 _proto("mx_graph_set_video_scopes", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 _proto("mx_graph_read_video_scopes", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32))
 _proto("mx_video_scope_record_bytes", C.c_int, C.POINTER(VideoScopeParams), C.POINTER(C.c_size_t))
+KEY_CHROMA, KEY_LUMA = 0, 1
+
+
+class VideoKeyParams(C.Structure):
+    """mx_video_key_params (24 bytes): the keyer's mode, key colour, ramp and spill distances in 1/16 of a code value."""
+    _fields_ = [("mode", C.c_uint32), ("key_u", C.c_uint8), ("key_v", C.c_uint8), ("invert", C.c_uint8), ("_pad", C.c_uint8),
+                ("near_q4", C.c_uint32), ("far_q4", C.c_uint32), ("spill_far_q4", C.c_uint32), ("spill_strength", C.c_uint32)]
+
+
+_proto("mx_video_key", C.c_int, C.c_void_p, C.POINTER(VideoKeyParams), C.POINTER(C.c_void_p), C.c_void_p)
+_proto("mx_graph_set_video_source_key", C.c_int, C.c_void_p, C.c_uint32, C.POINTER(VideoKeyParams))
 _proto("mx_graph_profile_run", C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float))
 _proto("mx_graph_profile_enable", C.c_int, C.c_void_p, C.c_int)
 _proto("mx_graph_profile_collect", C.c_int, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32))

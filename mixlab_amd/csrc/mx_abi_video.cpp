@@ -337,6 +337,22 @@ int mx_video_to_rgba(const mx_dframe* in, void* device_rgba, int32_t rgba_stride
     });
 }
 
+int mx_video_key(const mx_dframe* in, const mx_video_key_params* params, mx_dframe** out, void* stream) {
+    return guard([&] {
+        REQUIRE(out, "out is NULL");
+        *out = nullptr;
+        REQUIRE(in && params, "NULL argument");
+        mx::check_key_params(*params);
+        DFrame* d = const_cast<DFrame*>(D(in));
+        REQUIRE(mx::key_input_ok(d), "the keyer takes yuv420p or yuva420p (scale a frame of another format first)");
+        hipStream_t s = S(stream);
+        FrameRef o(DFrame::create(d->width, d->height, s, MX_PIXFMT_YUV420P, true), false);
+        mx::key_into(d, *params, o.f, s);
+        o->retain();
+        *out = H(o.f);
+    });
+}
+
 int mx_video_sync(void* stream) {
     return guard([&] { mx::hip_check(hipStreamSynchronize(S(stream)), "hipStreamSynchronize"); });
 }
@@ -429,6 +445,9 @@ int mx_graph_set_video_source_band(mx_graph* g, uint32_t node, uint32_t in_w, ui
         REQUIRE(g, "graph is NULL");
         g->g->set_video_source_band(node, in_w, in_full_h, src_row0, slice_rows, full_w, full_h, row0, band_rows);
     });
+}
+int mx_graph_set_video_source_key(mx_graph* g, uint32_t node, const mx_video_key_params* params) {
+    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->set_video_source_key(node, params); });
 }
 int mx_graph_video_output(mx_graph* g, uint32_t node, uint32_t port, mx_dframe** out) {
     return guard([&] {

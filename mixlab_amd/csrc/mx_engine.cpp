@@ -519,7 +519,7 @@ Graph::~Graph() {
     if (tail_stream_) (void)hipStreamSynchronize(tail_stream_);
     if (stream_) (void)hipStreamSynchronize(stream_);
     if (tail_stream_) { (void)hipStreamDestroy(tail_stream_); (void)hipEventDestroy(ev_head_done_); for (auto& e : ev_tail_done_) (void)hipEventDestroy(e); }
-    for (Node& n : nodes_) { n.vmixer.reset(); n.vout.clear(); n.vsrc = FrameRef(); n.vsrc_ring.clear(); n.vsrc_sched.clear(); }
+    for (Node& n : nodes_) { n.vmixer.reset(); n.vout.clear(); n.vsrc = FrameRef(); n.vsrc_ring.clear(); n.vsrc_sched.clear(); n.vkey_done.clear(); n.vkey_pool.clear(); }
     prof_runs_.clear(); prof_pool_.clear();
     for (Stage& st : stage_) { if (st.done) (void)hipEventDestroy(st.done); if (st.host) (void)hipHostFree(st.host); }
     // the descriptor ring launch_video_batch keeps per stream goes with a stream this graph OWNS; a caller's stream may be shared with other
@@ -1061,6 +1061,19 @@ void Graph::run(uint64_t t0, size_t fpc, uint32_t n_calls, float* ms_by_kind, fl
     auto drop_schedules = [&] { for (uint32_t id : sched_nodes_) { nodes_[id].sched.clear(); nodes_[id].gate_sched.clear(); } sched_nodes_.clear(); };
     if (frames > cap_frames_) { drop_schedules(); throw Error(MX_ERR_INVALID, "n_ticks exceeds max_ticks_per_run"); }
     if (n_calls == 0 || fpc == 0) { drop_schedules(); last_calls_ = n_calls; last_frames_per_call_ = fpc; for (AudioTapSet* s : tap_sets()) s->run_ticks = 0; stereo_gon_n_ = 0; scope_n_ = 0; return; }
+    // keyed video sources: a frame the keyer cannot take fails the run HERE, before anything of it is launched or any node's state has moved
+    for (uint32_t id : video_order_) {
+        const Node& n = nodes_[id];
+        if (n.kind != MX_KIND_SOURCE_VIDEO || !n.vkey_on) continue;
+        const uint64_t tick0 = t0 / spt_, last = tick0 + n_calls - 1;
+        bool ok = true;
+        for (const Node::VSched& e : n.vsrc_sched) if (e.tick >= tick0 && e.tick <= last) ok = ok && key_input_ok(e.frame.f);
+        if (n.vsrc_sched.empty() || n.vsrc_sched.back().tick < last) {   // ticks of the run past the queue fall through to the ring / the set frame
+            if (!n.vsrc_ring.empty()) { for (const FrameRef& f : n.vsrc_ring) ok = ok && key_input_ok(f.f); }
+            else if (n.vsrc && (n.vsrc_repeat || n.vsrc_pending)) ok = ok && key_input_ok(n.vsrc.f);
+        }
+        if (!ok) { drop_schedules(); throw Error(MX_ERR_INVALID, "node " + std::to_string(id) + " (SOURCE_VIDEO): the keyer takes yuv420p or yuva420p frames (mx_graph_set_video_source_key)"); }
+    }
     hip_check(hipSetDevice(device_), "hipSetDevice");
     if (fpc != tap_fpc_) {   // (the module compat path's call length): frames per tick and record room
         const auto sets = tap_sets();
@@ -2126,6 +2139,7 @@ void Graph::run_video_tick(uint64_t t) {
                 n.vband->run(n.vout[0].frame.f, o.f, stream_);
                 n.vout[0].frame = o;
             }
+            if (n.vkey_on && n.vout[0].frame) n.vout[0].frame = keyed_source_frame(id, n.vout[0].frame);
             break;
         }
         case MX_KIND_VIDEO_MIXER: {
@@ -2284,9 +2298,48 @@ void Graph::set_video_source_band(uint32_t node, uint32_t in_w, uint32_t in_full
                                   uint32_t full_w, uint32_t full_h, uint32_t row0, uint32_t band_rows) {
     if (node >= nodes_.size() || nodes_[node].kind != MX_KIND_SOURCE_VIDEO) throw Error(MX_ERR_INVALID, "node is not a SOURCE_VIDEO");
     Node& nd = nodes_[node];
+    if (band_rows && nd.vkey_on) throw Error(MX_ERR_INVALID, "video source band: the source is keyed (mx_graph_set_video_source_key), and a band-scaled layer cannot carry coverage");
     sync();                                     // a previous band scaler's row buffer may be in use
     nd.vband.reset(); nd.vband_pool.clear();
     if (band_rows) nd.vband = std::make_shared<BandScaler>(in_w, in_full_h, src_row0, slice_rows, full_w, full_h, row0, band_rows);
+}
+
+void Graph::set_video_source_key(uint32_t node, const mx_video_key_params* params) {
+    if (node >= nodes_.size()) throw Error(MX_ERR_INVALID, "node out of range");
+    if (nodes_[node].kind != MX_KIND_SOURCE_VIDEO) throw Error(MX_ERR_TYPE, "video source key: node is not a SOURCE_VIDEO");
+    Node& nd = nodes_[node];
+    if (params) {
+        check_key_params(*params);
+        if (nd.vband) throw Error(MX_ERR_INVALID, "video source key: the source delivers a row band of a scaled layer (mx_graph_set_video_source_band), which cannot carry coverage");
+    }
+    // frames keyed under the old setting are of no use; their output frames stay in the pool and are rewritten once their last holder has let go
+    nd.vkey_done.clear();
+    nd.vkey_on = params != nullptr;
+    if (params) nd.vkey = *params; else nd.vkey_pool.clear();
+}
+
+// The keyed form of `src` on a SOURCE_VIDEO node: keyed once per setting, reused while anything but this list holds the source frame.
+FrameRef Graph::keyed_source_frame(uint32_t id, const FrameRef& src) {
+    Node& n = nodes_[id];
+    if (!key_input_ok(src.f)) throw Error(MX_ERR_INVALID, "node " + std::to_string(id) + " (SOURCE_VIDEO): the keyer takes yuv420p or yuva420p frames");
+    for (size_t i = 0; i < n.vkey_done.size(); ++i)
+        if (n.vkey_done[i].src.f == src.f) return n.vkey_done[i].out;
+    // entries whose source frame only this list still holds can never be asked for again (the oldest goes too when the list is full)
+    for (size_t i = 0; i < n.vkey_done.size();) {
+        if (n.vkey_done[i].src->rc.load(std::memory_order_acquire) == 1) n.vkey_done.erase(n.vkey_done.begin() + (ptrdiff_t)i); else ++i;
+    }
+    if (n.vkey_done.size() >= 32) n.vkey_done.erase(n.vkey_done.begin());
+    FrameRef o;
+    for (auto& f : n.vkey_pool)   // the FrameStager's rule: a pooled frame is rewritten only when the pool alone holds it -- its last reader (a chain launched ticks later included) is on stream_ already
+        if (f->width == src->width && f->height == src->height && f->rc.load(std::memory_order_acquire) == 1) { o = f; break; }
+    if (!o) {
+        if (n.vkey_pool.size() >= 64) n.vkey_pool.erase(n.vkey_pool.begin());   // twice the list above: a frame that leaves the list is still in the pool, so a long ring recycles frames instead of allocating
+        n.vkey_pool.push_back(FrameRef(DFrame::create(src->width, src->height, stream_, MX_PIXFMT_YUV420P, true), false));
+        o = n.vkey_pool.back();
+    }
+    key_into(src.f, n.vkey, o.f, stream_);
+    n.vkey_done.push_back(Node::VKeyed{src, o});
+    return o;
 }
 
 void Graph::queue_video_source(uint32_t node, uint64_t tick, DFrame* frame, Rational dur, Rational off) {

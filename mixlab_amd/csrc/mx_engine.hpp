@@ -67,6 +67,11 @@ struct Node {
     struct VSched { uint64_t tick; FrameRef frame; Rational dur, off; };
     std::deque<VSched> vsrc_sched;                                                                   // SOURCE_VIDEO: frames due on given ticks (MediaSource / StreamInput pacing), oldest first
     std::shared_ptr<BandScaler> vband; std::vector<FrameRef> vband_pool;                             // SOURCE_VIDEO: frames are halo slices, delivered as this rank's row band of the scaled picture
+    // SOURCE_VIDEO: the keyer as a transform (mx_graph_set_video_source_key).  vkey_done: frames keyed under the current setting, newest last -- an entry holds the source
+    // frame (so its address stays its identity) and lives while anything else does; vkey_pool: output frames, rewritten only when the pool alone holds them
+    bool vkey_on = false; mx_video_key_params vkey{};
+    struct VKeyed { FrameRef src, out; };
+    std::vector<VKeyed> vkey_done; std::vector<FrameRef> vkey_pool;
     std::vector<DevBuf> rgba; uint32_t rgba_cur = 0, rgba_w = 0, rgba_h = 0; int32_t rgba_stride = 0;   // VIDEO_TO_RGBA: video_batch_ticks() buffers, written in turn (that many ticks' chains may share a launch); rgba_cur = the last tick's
     struct PendingRgba { ChainRgbaArgs args; std::shared_ptr<LazyChain> keep; };
     std::vector<PendingRgba> rgba_pending;     // VIDEO_TO_RGBA: chains of the last ticks, not launched yet, oldest first (run_video_tick)
@@ -202,6 +207,7 @@ public:
     void set_video_source(uint32_t node, DFrame* frame, Rational dur, Rational off, bool repeat);
     void set_video_source_band(uint32_t node, uint32_t in_w, uint32_t in_full_h, uint32_t src_row0, uint32_t slice_rows, uint32_t full_w, uint32_t full_h, uint32_t row0, uint32_t band_rows);
     void set_video_source_ring(uint32_t node, DFrame* const* frames, size_t n, Rational dur, Rational off);
+    void set_video_source_key(uint32_t node, const mx_video_key_params* params);   // nullptr removes
     void queue_video_source(uint32_t node, uint64_t tick, DFrame* frame, Rational dur, Rational off);
     // what a feed checks BEFORE it takes frames out of a pacing state machine (a rejected feed must not lose media):
     void check_video_queue(uint32_t node, uint64_t first_tick) const;   // queue_video_source(node, first_tick, ...) would be accepted
@@ -224,6 +230,7 @@ private:
     void upload_group(Group& g);          // descriptors of one group (both parities under MX_FLAG_OVERLAP_TAIL)
     void upload_group_one(Group& g, uint32_t parity);   // ... of one parity: desc / extra, or desc_alt / extra_alt
     void run_video_tick(uint64_t t);
+    FrameRef keyed_source_frame(uint32_t id, const FrameRef& src);   // SOURCE_VIDEO with a key set: src keyed under the node's setting (once per frame)
     void launch_pending_rgba(Node& n, size_t count, bool with_queued_scales);   // the `count` oldest pending chains of a sink
     void launch_video_scope(uint32_t tap, const Node::VOut& v);          // one tap's record of the tick being run (run_video_tick, on a recorded tick)
     // one launch sequence over ticks [call_off, call_off + n_calls) of the current run

@@ -731,4 +731,35 @@ void VideoMixer::run_tick(uint64_t t, const VideoInput in[4], FrameRef& out, Fra
     out = o;
 }
 
+// ---------------------------------------------------------------------------------------------
+// the keyer (mixlab_gpu.h mx_video_key; kernel in mx_k_key.hip)
+// ---------------------------------------------------------------------------------------------
+void check_key_params(const mx_video_key_params& p) {
+    if (p.mode != MX_KEY_CHROMA && p.mode != MX_KEY_LUMA) throw Error(MX_ERR_INVALID, "mx_video_key_params: mode must be MX_KEY_CHROMA or MX_KEY_LUMA");
+    if (p.invert > 1 || p._pad != 0) throw Error(MX_ERR_INVALID, "mx_video_key_params: invert must be 0 or 1 and _pad 0");
+    if (p.near_q4 > p.far_q4 || p.far_q4 > 65535u) throw Error(MX_ERR_INVALID, "mx_video_key_params: near_q4 <= far_q4 <= 65535");
+    if (p.spill_far_q4 > 65535u) throw Error(MX_ERR_INVALID, "mx_video_key_params: spill_far_q4 <= 65535");
+    if (p.spill_strength > 255u) throw Error(MX_ERR_INVALID, "mx_video_key_params: spill_strength is 0 .. 255");
+    if (p.mode == MX_KEY_LUMA && p.spill_strength != 0u) throw Error(MX_ERR_INVALID, "mx_video_key_params: a luma key suppresses no spill (spill_strength must be 0)");
+}
+
+bool key_input_ok(const DFrame* in) { return in->fmt == MX_PIXFMT_YUV420P; }   // yuva420p is (yuv420p, with_alpha)
+
+void key_into(DFrame* in, const mx_video_key_params& p, DFrame* out, hipStream_t s) {
+    if (!key_input_ok(in)) throw Error(MX_ERR_INVALID, "the keyer takes yuv420p or yuva420p (scale a frame of another format first)");
+    if (out->fmt != MX_PIXFMT_YUV420P || !out->alpha || out->width != in->width || out->height != in->height) throw Error(MX_ERR_INTERNAL, "key: the output frame is not yuva420p of the input's size");
+    in->ensure_pixels(s);
+    flush_scales(s);   // the input may be a scaler's output whose job is still queued
+    KeyArgs a{};
+    a.y = in->data[0]; a.u = in->data[1]; a.v = in->data[2]; a.a_in = in->alpha;
+    a.y_stride = in->stride[0]; a.u_stride = in->stride[1]; a.v_stride = in->stride[2]; a.a_stride = in->alpha ? in->alpha_stride : 0u;
+    a.oy = out->data[0]; a.ou = out->data[1]; a.ov = out->data[2]; a.oa = out->alpha;
+    a.oy_stride = out->stride[0]; a.ou_stride = out->stride[1]; a.ov_stride = out->stride[2]; a.oa_stride = out->alpha_stride;
+    a.width = in->width; a.height = in->height;
+    a.mode = p.mode; a.key_u = p.key_u; a.key_v = p.key_v; a.invert = p.invert;
+    a.near_q4 = p.near_q4; a.far_q4 = p.far_q4; a.spill_far_q4 = p.spill_far_q4; a.spill_strength = p.spill_strength;
+    launch_video_key(a, s);
+    hip_check(hipGetLastError(), "key launch");
+}
+
 }  // namespace mx

@@ -158,6 +158,24 @@ void launch_yuyv_to_422p(const uint8_t* src, uint32_t src_stride, uint32_t w, ui
 void launch_rgb_to_yuv444(const uint8_t* src, uint32_t src_stride, uint32_t w, uint32_t h, uint32_t bpp, uint32_t ri, uint32_t gi, uint32_t bi, uint8_t* const dst[3], const uint32_t dst_stride[3], hipStream_t s,
                           uint8_t* alpha_dst = nullptr, uint32_t alpha_stride = 0, uint32_t ai = 0);   // alpha_dst: the A byte (byte ai of a four-byte pixel) goes to that plane
 
+// ---- the keyer (mixlab_gpu.h mx_video_key; mx_k_key.hip) ----
+struct KeyArgs {
+    const uint8_t* y; const uint8_t* u; const uint8_t* v; const uint8_t* a_in;   // a_in nullptr: the input carries no coverage
+    uint8_t* oy; uint8_t* ou; uint8_t* ov; uint8_t* oa;
+    uint32_t y_stride, u_stride, v_stride, a_stride, oy_stride, ou_stride, ov_stride, oa_stride;
+    uint32_t width, height;                        // luma size, both even
+    uint32_t mode, key_u, key_v, invert, near_q4, far_q4, spill_far_q4, spill_strength;
+    // launcher-filled
+    uint32_t spill_on, chunks_x, rows_per_thread, n_threads;
+    uint64_t m_ramp, m_spill;                      // ceil(2^40 / (far - near)), ceil(2^40 / (spill_far - far)): the ramps' divisions as a multiply (0 where the span is empty)
+};
+struct DFrame;
+void launch_video_key(KeyArgs a, hipStream_t s);
+void check_key_params(const mx_video_key_params& p);   // MX_ERR_INVALID outside the ranges the header states
+bool key_input_ok(const DFrame* in);                   // yuv420p, with or without a coverage plane
+// `in` keyed under p into `out` (yuva420p of in's size, created by DFrame::create: the kernel leaves its padding as it is), asynchronous on s
+void key_into(DFrame* in, const mx_video_key_params& p, DFrame* out, hipStream_t s);
+
 // ---- exact rationals: MediaTime / MediaDuration (util/src/time.rs:9-75, num_rational::Ratio<i64>) ----
 struct Rational {
     int64_t num = 0, den = 1;

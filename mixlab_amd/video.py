@@ -330,6 +330,26 @@ def scope(f: DFrame, wave_cols: int = 0, vectorscope: bool = False, stream=None,
     return abi.parse_video_scope_records(buf.download(stream), wave_cols, vectorscope)[0]
 
 
+KEY_CHROMA, KEY_LUMA = abi.KEY_CHROMA, abi.KEY_LUMA
+
+
+def KeyParams(mode=KEY_CHROMA, key_u=128, key_v=128, invert=False, near_q4=0, far_q4=0, spill_far_q4=0, spill_strength=0) -> abi.VideoKeyParams:
+    """mx_video_key_params: distances in 1/16 of a code value (near <= far <= 65535); spill is active iff spill_strength > 0 and spill_far_q4 > far_q4"""
+    return abi.VideoKeyParams(int(mode), int(key_u), int(key_v), 1 if invert else 0, 0, int(near_q4), int(far_q4), int(spill_far_q4), int(spill_strength))
+
+
+def key(src: DFrame, params, stream=None) -> DFrame:
+    """mx_video_key: the chroma / luma key of a yuv420p or yuva420p frame as a NEW yuva420p frame (Y copied, U / V copied or spill-suppressed, coverage computed)"""
+    h = C.c_void_p()
+    check(lib.mx_video_key(src._h, C.byref(params), C.byref(h), stream))
+    return DFrame(handle=h.value, stream=stream)
+
+
+def graph_set_video_source_key(g, node, params):
+    """The SOURCE_VIDEO node delivers its frames keyed (mx_graph_set_video_source_key); params None removes the transform."""
+    check(lib.mx_graph_set_video_source_key(g._h, node, C.byref(params) if params is not None else None))
+
+
 class VideoMixer:
     """mx_video_mixer_*: VideoMixer::run_tick on device-resident frames (src/module/video_mixer.rs)."""
 
