@@ -33,7 +33,9 @@ extern "C" {
                               *    mx_video_scope_params, mx_graph_set_video_scopes, mx_graph_read_video_scopes, mx_video_scope_record_bytes, mx_video_scope;
                               *    mx_loudness_params, mx_loudness_tick, mx_graph_set_loudness, mx_graph_read_loudness, mx_loudness_tables, mx_loudness_gate;
                               *    mx_stereo_params, mx_stereo_tick, mx_graph_set_stereo, mx_graph_read_stereo, mx_graph_read_goniometers, mx_stereo_gonio_record_bytes,
-                              *    mx_stereo_correlation */
+                              *    mx_stereo_correlation;
+                              *    mx_limiter_params, mx_limiter_tick, mx_graph_set_limiters, mx_graph_read_limiters, mx_graph_read_limited, mx_graph_read_limited_i16,
+                              *    mx_graph_limited_device_ptr, mx_limiter_weights */
 
 /* ---- status codes (0 ok, <0 error; cf. MIXLAB_IOCTX_ERROR / MIXLAB_IOCTX_PANIC) ---- */
 enum {
@@ -503,6 +505,69 @@ int mx_stereo_gonio_record_bytes(const mx_stereo_params* params, size_t* bytes);
 /* *r = lr / sqrt(ll * rr) in f64, clamped to [-1, 1]; 0.0 when ll * rr is not a positive finite number (silence on one side reads 0, not NaN)
  * or the quotient is NaN.  Feed a record's sums or its window sums.  Host only: touches no device and needs no graph.  NULL r: MX_ERR_INVALID. */
 int mx_stereo_correlation(double ll, double rr, double lr, double* r);
+
+/* Look-ahead limiter taps on audio output ports of a built graph: the one tap set that acts on level.  A tap
+ * observes a port like a meter -- no module, no edge, the run order, the fusion plan and the port itself unchanged; a graph without them
+ * launches nothing new -- and writes a LIMITED COPY of the port, delayed by the lookahead, plus one small record per tick.  The six tap sets
+ * are independent and may be set together.  Every run computes copies and records on the device, once per run after its last span.
+ * BUILD-SPECIFIED (the reference has no limiter; its OutputDevice reports clip and its sinks clamp); the numbers are fixed bit for bit
+ * (tests/limiter_model.py restates them in numpy).  The arithmetic is feed-forward -- a sliding minimum, then FIR smoothing of the gain -- so
+ * every output sample is a function of a bounded window of input frames, and the copies are bit-identical however ticks are grouped into runs.
+ *   parameters  ceiling c: finite, 2^-20 <= c <= 1; lookahead D in frames of the port's own rate domain, 0 <= D <= 512.  One set per graph.
+ *   stream    a tap treats its port as one stream of frames n = 0, 1, ... that starts when the taps are set and continues across ticks and
+ *             runs (first_tick may jump: the stream does not care).  Frames before n = 0 are +0.0.  Every f32 operation is rounded on its
+ *             own (no fused multiply-add).
+ *   level     a[n] = the f32 whose bits are max(bits(L) & 0x7fffffff, bits(R) & 0x7fffffff): the channels of a stereo port are linked; a
+ *             mono port has one.  A stereo port stored as one float per frame (the fused L == R strip result) reads as L = R = that float,
+ *             equal to MX_FLAG_NO_FUSE's copy and records bit for bit.
+ *   required  r[n] = +0.0 if bits(a) >= 0x7f800000 (Inf, NaN); 1.0 if a <= c; else c / min(a, 65536.0f), the correctly rounded f32 quotient
+ *             (the cap keeps every quotient normal; louder samples meet the final clamp).
+ *   hold      m[n] = min(r[n - D] .. r[n]).
+ *   smoothing s[n]: acc = +0.0; for k = 0 .. D ascending: p = w[k] * m[n - k]; acc = acc + p.  w[k] = the f32 nearest to h[k] / sum h,
+ *             h[k] = 1 - cos(2 pi (k + 1) / (D + 2)); D = 0: w = {1}.  mx_limiter_weights returns the very table the kernel uses.
+ *   gain      q = min(m[n], m[n - D]); g[n] = 1.0 if q == 1.0, else min(s[n], r[n - D]).  The first branch makes the limiter exactly
+ *             transparent where nothing within 2 D frames needs limiting; the min makes the ceiling a guarantee whatever the weights round to.
+ *   output    per channel x = input[n - D]; a non-finite x gives +0.0 and is counted; else y[n] = max(-c, min(c, x * g[n])).  The limited copy
+ *             is the port delayed by D frames in the port's LOGICAL layout: interleaved stereo also for a port stored as one float per frame.
+ *   record    over the frames n of the tick: min_gain the smallest g (integer minimum of its bits), peak_out the largest bits of |y| read as
+ *             f32, limited the frames with g < 1, nonfinite the samples replaced, frames and channels of the port.
+ * Carried per tap: the last 2 D input frames, handed from run to run (a run shorter than 2 D frames shifts them).  Every call to
+ * mx_graph_set_limiters resets every tap: the stream starts again from silence.  mx_graph_adopt_state carries no taps. */
+typedef struct { float ceiling; uint32_t lookahead; } mx_limiter_params;
+#define MX_LIMITER_MAX_LOOKAHEAD 512u
+typedef struct {
+    float    min_gain;      /* smallest gain of the tick; 1.0 when nothing was limited */
+    float    peak_out;      /* largest |y| of the tick: <= ceiling */
+    uint32_t limited;       /* frames with gain < 1 */
+    uint32_t nonfinite;     /* samples (not frames) replaced by +0.0 */
+    uint32_t frames;
+    uint32_t channels;
+} mx_limiter_tick;   /* 24 bytes: min_gain 0, peak_out 4, limited 8, nonfinite 12, frames 16, channels 20 */
+/* Replaces the graph's limiter taps with ports[0..n) (n = 0: none; params may then be NULL and the graph launches nothing for them).
+ * Video port: MX_ERR_TYPE.  A node or port out of range, a duplicate (node, port), a port the fusion did not materialise, a ceiling that is
+ * not finite or outside [2^-20, 1], a lookahead above 512: MX_ERR_INVALID.  Device memory that cannot be had: MX_ERR_NOMEM, and the graph is
+ * left without limiter taps.  Waits for outstanding work like a read-back but keeps the automatic second-stream mode on.  Device memory:
+ * max_ticks_per_run x (the sum over the taps of frames x channels floats + n x 24 bytes of records), per tap 2 x 2 x 1024 floats of history,
+ * and the weights.  The launches count in the profile calls' ms_total only (MX_PROFILE_KINDS is unchanged). */
+int mx_graph_set_limiters(mx_graph* g, const mx_port_ref* ports, size_t n, const mx_limiter_params* params);
+/* Ticks [first_tick_in_run, first_tick_in_run + n_ticks) of the last run, laid out [tick][tap] in set order; cap = records dst holds.
+ * A window beyond the last run (or a run made before the taps were set), cap < n_ticks x taps, or no taps: MX_ERR_INVALID.  Joins the
+ * graph's streams like mx_graph_read_output. */
+int mx_graph_read_limiters(mx_graph* g, uint32_t first_tick_in_run, uint32_t n_ticks, mx_limiter_tick* dst, size_t cap);
+/* The limited copy of tap `tap` (its index in set order) over the same kind of window: n_ticks x frames x channels floats, ticks back to
+ * back; *n_samples = that count (n_samples may be NULL; samples = NULL with cap = 0 asks for the count alone).  A tap out of range, a window
+ * beyond the last run, cap too small: MX_ERR_INVALID.  _i16 gives the same samples in the sinks' format (mx_graph_read_output_i16: clamp to
+ * [-1, 1], x 32767, truncation); since |y| <= ceiling <= 1 the clamp never acts. */
+int mx_graph_read_limited(mx_graph* g, size_t tap, uint32_t first_tick_in_run, uint32_t n_ticks, float* samples, size_t cap, size_t* n_samples);
+int mx_graph_read_limited_i16(mx_graph* g, size_t tap, uint32_t first_tick_in_run, uint32_t n_ticks, int16_t* samples, size_t cap, size_t* n_samples);
+/* For zero-copy consumers: *dev = tap `tap`'s copy of tick 0 of a run on the device; tick t of the run starts *floats_per_tick floats
+ * further per tick (the copies of all taps of one tick lie together) and holds frames x channels floats.  The call orders the graph's
+ * stream behind the last run's limiter launches (also those that went out behind a Mixer bank on the second stream); call it again, or
+ * mx_graph_sync, after a later run before reading on another stream.  The pointer holds until the taps are set again or the graph grows. */
+int mx_graph_limited_device_ptr(mx_graph* g, size_t tap, void** dev, size_t* floats_per_tick);
+/* The smoothing weights of the spec for one lookahead: w[lookahead + 1].  Host only: touches no device and needs no graph.  A lookahead above
+ * 512 or a NULL w: MX_ERR_INVALID. */
+int mx_limiter_weights(uint32_t lookahead, float* w);
 
 /* Plotter indication (src/module/plotter.rs:37-56) for tick `tick_in_run` of the last run:
  * *fired = 1 and SPT floats in each of left/right when it fired (every 6th call, input connected). */

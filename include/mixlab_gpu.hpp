@@ -129,6 +129,17 @@ public:
     void read_stereo(uint32_t first, uint32_t n, std::vector<mx_stereo_tick>& dst) { check(mx_graph_read_stereo(g_, first, n, dst.data(), dst.size())); }
     // the goniometer records the last run emitted, [emission][tap], mx_stereo_gonio_record_bytes each; returns how many
     uint32_t read_goniometers(std::vector<unsigned char>& dst) { uint32_t n = 0; check(mx_graph_read_goniometers(g_, dst.data(), dst.size(), &n)); return n; }
+    // limiter taps (mx_graph_set_limiters): one ceiling and lookahead for every tap; an empty list removes them
+    void set_limiters(const std::vector<mx_port_ref>& ports, const mx_limiter_params& p) {
+        check(mx_graph_set_limiters(g_, ports.data(), ports.size(), ports.empty() ? nullptr : &p));
+    }
+    // ticks [first, first + n) of the last run as [tick][tap]
+    void read_limiters(uint32_t first, uint32_t n, std::vector<mx_limiter_tick>& dst) { check(mx_graph_read_limiters(g_, first, n, dst.data(), dst.size())); }
+    // the limited copy of tap `tap` over the same window: frames x channels floats per tick, back to back; returns how many
+    size_t read_limited(size_t tap, uint32_t first, uint32_t n, std::vector<float>& dst) { size_t c = 0; check(mx_graph_read_limited(g_, tap, first, n, dst.data(), dst.size(), &c)); return c; }
+    size_t read_limited_i16(size_t tap, uint32_t first, uint32_t n, std::vector<int16_t>& dst) { size_t c = 0; check(mx_graph_read_limited_i16(g_, tap, first, n, dst.data(), dst.size(), &c)); return c; }
+    // the copy on the device: tick t of the last run at (float*)ptr + t * floats_per_tick
+    void* limited_device_ptr(size_t tap, size_t* floats_per_tick) { void* p = nullptr; check(mx_graph_limited_device_ptr(g_, tap, &p, floats_per_tick)); return p; }
     // video scope taps (mx_graph_set_video_scopes): one parameter set for every tap; an empty list removes them
     void set_video_scopes(const std::vector<mx_port_ref>& ports, const mx_video_scope_params& p) {
         check(mx_graph_set_video_scopes(g_, ports.data(), ports.size(), ports.empty() ? nullptr : &p));

@@ -194,6 +194,22 @@ _proto("mx_graph_read_stereo", C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_
 _proto("mx_graph_read_goniometers", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32))
 _proto("mx_stereo_gonio_record_bytes", C.c_int, C.POINTER(StereoParams), C.POINTER(C.c_size_t))
 _proto("mx_stereo_correlation", C.c_int, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double))
+class LimiterParams(C.Structure):
+    """mx_limiter_params: the ceiling (finite, 2^-20 .. 1) and the lookahead in frames of the port's own rate (0 .. 512)."""
+    _fields_ = [("ceiling", C.c_float), ("lookahead", C.c_uint32)]
+
+
+LIMITER_MAX_LOOKAHEAD = 512   # MX_LIMITER_MAX_LOOKAHEAD
+LIMITER_TILE = 2048           # frames of a run one workgroup of the limiter kernel limits (mx_kernels.hpp LIMIT_TILE): tests put peaks on its edges
+LIMITER_TICK_DTYPE = np.dtype({"names": ["min_gain", "peak_out", "limited", "nonfinite", "frames", "channels"],
+                               "formats": [np.float32, np.float32, np.uint32, np.uint32, np.uint32, np.uint32],
+                               "offsets": [0, 4, 8, 12, 16, 20], "itemsize": 24})   # mx_limiter_tick
+_proto("mx_graph_set_limiters", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
+_proto("mx_graph_read_limiters", C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t)
+_proto("mx_graph_read_limited", C.c_int, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t))
+_proto("mx_graph_read_limited_i16", C.c_int, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t))
+_proto("mx_graph_limited_device_ptr", C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t))
+_proto("mx_limiter_weights", C.c_int, C.c_uint32, C.c_void_p)
 class VideoScopeParams(C.Structure):
     """mx_video_scope_params: waveform columns (0, 64, 128, 256), vectorscope on / off, record every hop-th video tick."""
     _fields_ = [("wave_cols", C.c_uint32), ("vectorscope", C.c_uint32), ("hop", C.c_uint32)]
@@ -277,6 +293,15 @@ def loudness_gate(block_sq, block_frames):
     out, kept = C.c_double(), C.c_size_t()
     check(lib.mx_loudness_gate(sq.ctypes.data_as(C.c_void_p), fr.ctypes.data_as(C.c_void_p), sq.size, C.byref(out), C.byref(kept)))
     return out.value, kept.value
+
+
+def limiter_weights(lookahead: int) -> np.ndarray:
+    """float32[lookahead + 1]: the smoothing weights the limiter kernel uses (mx_limiter_weights, host only, no device)"""
+    if not 0 <= int(lookahead) <= LIMITER_MAX_LOOKAHEAD:   # before any buffer is sized from it
+        raise MxError(MX_ERR_INVALID, "lookahead must be 0 .. 512")
+    w = np.zeros(int(lookahead) + 1, np.float32)
+    check(lib.mx_limiter_weights(int(lookahead), w.ctypes.data_as(C.c_void_p)))
+    return w
 
 
 def stereo_gonio_record_bytes(grid: int) -> int:
@@ -584,6 +609,42 @@ class Graph:
         check(lib.mx_graph_read_goniometers(self._h, raw.ctypes.data_as(C.c_void_p), raw.size, C.byref(got)))
         recs = parse_goniometer_records(raw[: got.value * rb], grid)
         return [recs[i:i + n] for i in range(0, len(recs), n)] if n else []
+
+    def set_limiters(self, ports, ceiling: float = 1.0, lookahead: int = 240):
+        """look-ahead limiter taps on audio output ports [(node, port), ...]: every run writes a limited copy of each port, delayed by
+        `lookahead` frames and never beyond +-ceiling, and one record per tick.  One parameter set for every tap.  Each call starts every
+        tap's stream from silence; [] removes them all."""
+        ports = list(ports)
+        if not ports:
+            check(lib.mx_graph_set_limiters(self._h, None, 0, None))
+            self._n_limiters = 0
+            return
+        pa = (PortRef * len(ports))(*[PortRef(int(n), int(p)) for (n, p) in ports])
+        check(lib.mx_graph_set_limiters(self._h, pa, len(ports), C.byref(LimiterParams(float(ceiling), int(lookahead)))))
+        self._n_limiters = len(ports)
+
+    def read_limiters(self, first_tick: int, n_ticks: int) -> np.ndarray:
+        """ticks [first_tick, first_tick + n_ticks) of the last run: a LIMITER_TICK_DTYPE array shaped (n_ticks, taps) in set order"""
+        n = getattr(self, "_n_limiters", 0)
+        out = np.zeros((n_ticks, n), dtype=LIMITER_TICK_DTYPE)
+        check(lib.mx_graph_read_limiters(self._h, first_tick, n_ticks, out.ctypes.data_as(C.c_void_p), out.size))
+        return out
+
+    def read_limited(self, tap: int, first_tick: int, n_ticks: int, i16: bool = False) -> np.ndarray:
+        """the limited copy of tap `tap` (index in set order) over ticks [first_tick, first_tick + n_ticks) of the last run: float32 (or, with
+        i16, the sinks' int16 format), frames x channels per tick, a stereo port interleaved"""
+        n = C.c_size_t(0)
+        check(lib.mx_graph_read_limited(self._h, tap, first_tick, n_ticks, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=np.int16 if i16 else np.float32)
+        fn = lib.mx_graph_read_limited_i16 if i16 else lib.mx_graph_read_limited
+        check(fn(self._h, tap, first_tick, n_ticks, out.ctypes.data_as(C.c_void_p), out.size, C.byref(n)))
+        return out
+
+    def limited_device_ptr(self, tap: int):
+        """-> (device pointer of tap `tap`'s limited copy of tick 0, floats from one tick's copy to the next)"""
+        p, n = C.c_void_p(), C.c_size_t()
+        check(lib.mx_graph_limited_device_ptr(self._h, tap, C.byref(p), C.byref(n)))
+        return p.value, n.value
 
     def set_video_scopes(self, ports, wave_cols: int = 0, vectorscope: bool = False, hop: int = 1):
         """video scope taps on video output ports [(node, port), ...]: on every hop-th video tick, the luma / U / V histograms, the

@@ -288,6 +288,32 @@ int mx_graph_read_goniometers(mx_graph* g, void* dst, size_t cap_bytes, uint32_t
     return guard([&] { REQUIRE(g, "graph is NULL"); const size_t n = g->g->read_goniometers(dst, cap_bytes); if (n_records) *n_records = (uint32_t)n; });
 }
 
+int mx_graph_set_limiters(mx_graph* g, const mx_port_ref* ports, size_t n, const mx_limiter_params* params) {
+    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->set_limiters(ports, n, params); });
+}
+
+int mx_graph_read_limiters(mx_graph* g, uint32_t first_tick_in_run, uint32_t n_ticks, mx_limiter_tick* dst, size_t cap) {
+    static_assert(sizeof(mx_limiter_tick) == sizeof(mx::LimitTick) && sizeof(mx_limiter_tick) == 24, "mx_limiter_tick is the kernels' record");
+    static_assert(MX_LIMITER_MAX_LOOKAHEAD == mx::LIMIT_MAX_LOOKAHEAD, "the header's bound is the kernels'");
+    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->read_limiters(first_tick_in_run, n_ticks, reinterpret_cast<mx::LimitTick*>(dst), cap); });
+}
+
+int mx_graph_read_limited(mx_graph* g, size_t tap, uint32_t first_tick_in_run, uint32_t n_ticks, float* samples, size_t cap, size_t* n_samples) {
+    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->read_limited(tap, first_tick_in_run, n_ticks, samples, nullptr, cap, n_samples); });
+}
+
+int mx_graph_read_limited_i16(mx_graph* g, size_t tap, uint32_t first_tick_in_run, uint32_t n_ticks, int16_t* samples, size_t cap, size_t* n_samples) {
+    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->read_limited(tap, first_tick_in_run, n_ticks, nullptr, samples, cap, n_samples); });
+}
+
+int mx_graph_limited_device_ptr(mx_graph* g, size_t tap, void** dev, size_t* floats_per_tick) {
+    return guard([&] { REQUIRE(g && dev, "NULL argument"); *dev = g->g->limited_ptr(tap, floats_per_tick); });
+}
+
+int mx_limiter_weights(uint32_t lookahead, float* w) {   // host only: no device, no graph
+    return guard([&] { REQUIRE(mx::limiter_weights(lookahead, w), "lookahead must be 0 .. 512 and w not NULL"); });
+}
+
 int mx_stereo_gonio_record_bytes(const mx_stereo_params* params, size_t* bytes) {   // host only: no device, no graph
     return guard([&] {
         REQUIRE(params && bytes, "NULL argument");

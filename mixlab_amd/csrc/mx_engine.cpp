@@ -1337,7 +1337,7 @@ void Graph::run_span(uint64_t t0, size_t fpc, uint32_t call_off, uint32_t n_call
     // after everything else of the span on stream_ (the video section included): its profile interval starts at the latest event recorded there
     launch_outputs(t0, call_off, n_calls, prof);
     // the port buffers hold every tick of the run: the audio tap sets go once, after its last span, in this order on either stream
-    if (call_off + n_calls == run_calls) { launch_meter_taps(run_calls, prof); launch_spectrum_taps(run_calls, prof); launch_loudness_taps(run_calls, prof); launch_stereo_taps(run_calls, prof); }
+    if (call_off + n_calls == run_calls) { launch_meter_taps(run_calls, prof); launch_spectrum_taps(run_calls, prof); launch_loudness_taps(run_calls, prof); launch_stereo_taps(run_calls, prof); launch_limiter_taps(run_calls, prof); }
     if (prof) { prof_runs_.push_back(std::move(prof_pool_.back())); prof_pool_.pop_back(); }
 }
 
@@ -1398,7 +1398,7 @@ uint32_t Graph::profile_collect(float* ms_by_kind, float* ms_total) {
         hipEvent_t end = last;
         if (p.od) { perf_od_ms_ += elapsed(last, p.od_end); end = p.od_end; }
         if (p.od_tail) perf_od_ms_ += elapsed(p.group_end.back(), p.od_tail_end);
-        // meter, spectrum, loudness and stereo field launches: no kind of their own, counted in the total (and so in engine_us): on stream_ last of all, or on the tail stream
+        // meter, spectrum, loudness, stereo field and limiter launches: no kind of their own, counted in the total (and so in engine_us): on stream_ last of all, or on the tail stream
         // behind the tail (and its OutputDevices)
         if (p.meters) end = p.meters_end;
         perf_total_ms_ = elapsed(p.begin, end);
@@ -1594,8 +1594,8 @@ void Graph::audio_out_lag(uint32_t node) {
     nodes_[node].od_lag->store(true);   // AtomicBool::store (output_device.rs:126); nothing else of the graph is touched
 }
 
-// ---- the audio tap sets: level meters, spectrum, loudness and stereo field taps (mixlab_gpu.h mx_graph_set_meters, _spectra, _loudness,
-// _stereo; DESIGN.md sections 0.2, 0.3, 0.5, 0.6).  What the four share comes first, written for "a tap set"; then each set's own part ----
+// ---- the audio tap sets: level meters, spectrum, loudness, stereo field and limiter taps (mixlab_gpu.h mx_graph_set_meters, _spectra,
+// _loudness, _stereo, _limiters; DESIGN.md sections 0.2, 0.3, 0.5, 0.6, 0.8).  What the five share comes first, written for "a tap set"; then each set's own part ----
 
 void Graph::check_tap_args(const AudioTapSet& s, const void* ports, const void* params, size_t n) const {
     if (n && (!ports || !params)) throw Error(MX_ERR_INVALID, "ports / params is NULL");
@@ -1661,6 +1661,7 @@ void Graph::reupload_taps(size_t fpc) {
     if (!spectra_.empty()) upload_spectra(fpc);
     if (!loudness_.empty()) upload_loudness(fpc);
     if (!stereo_.empty()) upload_stereo(fpc);
+    if (!limiters_.empty()) upload_limiters(fpc);
     tap_fpc_ = fpc;
 }
 
@@ -1981,6 +1982,117 @@ size_t Graph::read_goniometers(void* dst, size_t cap_bytes) {
         sync();
     }
     return count;
+}
+
+// ---- limiter taps (mixlab_gpu.h mx_graph_set_limiters) ----
+
+void Graph::set_limiters(const mx_port_ref* ports, size_t n, const mx_limiter_params* params) {
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    check_tap_args(limiters_, ports, params, n);
+    if (n) {
+        const float c = params->ceiling;
+        if (!(std::isfinite(c) && c >= 0x1p-20f && c <= 1.0f)) throw Error(MX_ERR_INVALID, "mx_limiter_params: ceiling must be finite, 2^-20 <= ceiling <= 1");
+        if (params->lookahead > LIMIT_MAX_LOOKAHEAD) throw Error(MX_ERR_INVALID, "mx_limiter_params: lookahead must be 0 .. 512");
+    }
+    check_tap_ports(limiters_, ports, n);
+    // like set_stereo: the last run's launches are done with the copies, the records and the history; the second-stream mode stays on
+    sync();
+    auto clear = [&] {
+        limiters_.ports.clear(); limiters_.run_ticks = 0; lim_hist_cur_ = 0;
+        limiters_.desc.free_(); limiters_.rec.free_(); lim_out_.free_(); lim_hist_.free_(); lim_w_.free_(); lim_stage_.free_();
+        lim_off_.clear(); lim_floats_.clear(); lim_tick_floats_ = 0; lim_max_frames_ = 0; lim_par_ = mx_limiter_params{0.0f, 0};
+    };
+    clear();
+    if (!n) return;
+    try {
+        limiters_.ports.assign(ports, ports + n);
+        lim_par_ = *params;
+        std::vector<float> w(lim_par_.lookahead + 1u);
+        (void)limiter_weights(lim_par_.lookahead, w.data());
+        lim_w_.alloc(w.size() * sizeof(float));
+        hip_check(hipMemcpy(lim_w_.p, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy(limiter weights)");
+        // every tap's history starts as +0.0: frames before this call read as silence
+        const size_t hist_bytes = 2 * n * (size_t)LIMIT_HIST_FRAMES * sizeof(float2);
+        lim_hist_.alloc(hist_bytes);
+        hip_check(hipMemsetAsync(lim_hist_.p, 0, hist_bytes, stream_), "hipMemsetAsync(limiter history)");
+        hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
+        upload_limiters(tap_fpc_);
+    } catch (...) { clear(); throw; }   // (out of device memory: no limiter taps rather than half a set)
+}
+
+// beside the descriptors: where each tap's copy starts inside a tick of copies, and room for a whole submission's copies
+void Graph::upload_limiters(size_t fpc) {
+    const size_t n = limiters_.ports.size();
+    const std::vector<TapDesc> t = tap_descs(limiters_, fpc);
+    lim_off_.assign(n, 0); lim_floats_.assign(n, 0);
+    size_t sum = 0; uint32_t max_frames = 0;
+    for (size_t i = 0; i < n; ++i) {   // set order
+        const Node& nd = nodes_[limiters_.ports[i].node];
+        const size_t frames = fpc * nd.dom_num / nd.dom_den;
+        if (frames > LIMIT_MAX_FRAMES) throw Error(MX_ERR_INVALID, "limiter: a tick of more than 2^30 frames");
+        lim_off_[i] = sum; lim_floats_[i] = frames * (nd.out_type[limiters_.ports[i].port] == MX_MONO ? 1u : 2u);
+        sum += lim_floats_[i]; max_frames = std::max(max_frames, (uint32_t)frames);
+    }
+    const size_t max_ticks = std::max<size_t>(1, cap_frames_ / fpc);
+    if ((unsigned __int128)max_ticks * sum * sizeof(float) > ((unsigned __int128)1 << 46)) throw Error(MX_ERR_NOMEM, "limiter: the limited copies of one run (max_ticks_per_run x the taps' frames x channels) exceed the device");
+    std::vector<LimitDesc> d(t.size());
+    for (size_t k = 0; k < t.size(); ++k)
+        d[k] = LimitDesc{t[k].p, t[k].frames, t[k].layout, t[k].slot, t[k].layout == METER_MONO ? 1u : 2u, (uint64_t)lim_off_[t[k].slot]};
+    const size_t need = max_ticks * sum * sizeof(float);
+    if (!lim_out_.p || lim_out_.bytes < need) lim_out_.alloc(need);
+    upload_tap_descs(limiters_, d.data(), d.size() * sizeof(LimitDesc), fpc, n * sizeof(LimitTick));
+    lim_tick_floats_ = sum; lim_max_frames_ = max_frames;
+}
+
+// Each run reads the frame history the previous one wrote (lim_hist_cur_ flips once per run).  A tap's copy, records and history are touched
+// by that tap's workgroups alone.
+void Graph::launch_limiter_taps(uint32_t n_calls, ProfSpan* prof) {
+    if (limiters_.empty()) return;
+    const uint32_t n = limiters_.size();
+    float2* hist = (float2*)lim_hist_.p;
+    const size_t hist_items = (size_t)n * LIMIT_HIST_FRAMES;
+    const uint32_t cur = lim_hist_cur_;
+    lim_hist_cur_ ^= 1u;
+    launch_tap_set(limiters_, LimitRun{(const LimitDesc*)limiters_.desc.p, n, n_calls, n, lim_par_.ceiling, lim_par_.lookahead, (const float*)lim_w_.p,
+                                       hist + (size_t)cur * hist_items, hist + (size_t)(cur ^ 1u) * hist_items, (float*)lim_out_.p, lim_tick_floats_,
+                                       (LimitTick*)limiters_.rec.p, lim_max_frames_}, prof);
+}
+
+void Graph::read_limiters(uint32_t first, uint32_t n, LimitTick* dst, size_t cap) {
+    read_taps(limiters_, first, n, dst, cap, limiters_.ports.size(), sizeof(LimitTick), "n_ticks x taps");
+}
+
+void Graph::read_limited(size_t tap, uint32_t first, uint32_t n, float* dst, int16_t* dst_i16, size_t cap, size_t* n_samples) {
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    if (limiters_.empty()) throw Error(MX_ERR_INVALID, "no limiter taps are set");
+    if (tap >= limiters_.ports.size()) throw Error(MX_ERR_INVALID, "limiter: tap out of range");
+    if ((uint64_t)first + n > limiters_.run_ticks) throw Error(MX_ERR_INVALID, "the window lies beyond the last run (or no run since the limiter taps were set)");
+    const size_t width = lim_floats_[tap], count = (size_t)n * width;
+    if (n_samples) *n_samples = count;
+    if (!dst && !dst_i16 && cap == 0) return;   // the count alone
+    if (cap < count) throw Error(MX_ERR_INVALID, "cap is smaller than n_ticks x frames x channels");
+    if (count && !dst && !dst_i16) throw Error(MX_ERR_INVALID, "samples is NULL");
+    if (!count) return;
+    wait_tail(-1);
+    const size_t need = count * (sizeof(float) + sizeof(int16_t));   // f32 staging, then the i16 form
+    if (lim_stage_.bytes < need) { sync(); lim_stage_.alloc(need); }
+    float* stage = (float*)lim_stage_.p;
+    launch_limit_gather((const float*)lim_out_.p + (size_t)first * lim_tick_floats_ + lim_off_[tap], lim_tick_floats_, (uint32_t)width, n, stage, stream_);
+    if (dst_i16) {
+        launch_f32_to_i16(stage, (int16_t*)(stage + count), count, 0, stream_);
+        hip_check(hipMemcpyAsync(dst_i16, stage + count, count * sizeof(int16_t), hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(D2H i16)");
+    } else
+        hip_check(hipMemcpyAsync(dst, stage, count * sizeof(float), hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(D2H)");
+    sync();
+}
+
+float* Graph::limited_ptr(size_t tap, size_t* floats_per_tick) {
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    if (limiters_.empty()) throw Error(MX_ERR_INVALID, "no limiter taps are set");
+    if (tap >= limiters_.ports.size()) throw Error(MX_ERR_INVALID, "limiter: tap out of range");
+    if (floats_per_tick) *floats_per_tick = lim_tick_floats_;
+    wait_tail(-1);   // stream_ is ordered behind a held-back tail's limiter launches too
+    return (float*)lim_out_.p + lim_off_[tap];
 }
 
 // ---- video scope taps (mixlab_gpu.h mx_graph_set_video_scopes) ----

@@ -175,6 +175,12 @@ public:
     void set_stereo(const mx_port_ref* ports, size_t n, const mx_stereo_params* params);
     void read_stereo(uint32_t first, uint32_t n, StereoTick* dst, size_t cap);
     size_t read_goniometers(void* dst, size_t cap_bytes);   // the last run's emitted records; returns how many
+    // limiter taps (mx_graph_set_limiters / mx_graph_read_limiters / mx_graph_read_limited): a look-ahead peak limiter's copy of every tapped port, and one record per tick
+    void set_limiters(const mx_port_ref* ports, size_t n, const mx_limiter_params* params);
+    void read_limiters(uint32_t first, uint32_t n, LimitTick* dst, size_t cap);
+    // ticks [first, first + n) of tap `tap`'s limited copy as f32 (dst_i16 null) or in the sinks' i16 format; both null with cap 0: the count only
+    void read_limited(size_t tap, uint32_t first, uint32_t n, float* dst, int16_t* dst_i16, size_t cap, size_t* n_samples);
+    float* limited_ptr(size_t tap, size_t* floats_per_tick);   // the tap's copy of tick 0 on the device; ticks are floats_per_tick apart
     // video scope taps (mx_graph_set_video_scopes / mx_graph_read_video_scopes): histograms, waveform and vectorscope of the frames on video ports
     void set_video_scopes(const mx_port_ref* ports, size_t n, const mx_video_scope_params* params);
     size_t read_video_scopes(void* dst, size_t cap_bytes);   // the last run's records; returns how many
@@ -241,7 +247,7 @@ private:
     size_t od_offset(const Node& n, uint32_t tick) const;                // float offset of tick `tick` of the last run in the hand-off
     struct ProfSpan;
     void launch_outputs(uint64_t t0, uint32_t call_off, uint32_t n_calls, ProfSpan* prof);   // the span's OutputDevice launches
-    // the audio tap sets (meters, spectrum, loudness, stereo field): what the four share is written once, for "a tap set"
+    // the audio tap sets (meters, spectrum, loudness, stereo field, limiters): what the five share is written once, for "a tap set"
     struct AudioTapSet;
     void check_tap_args(const AudioTapSet& s, const void* ports, const void* params, size_t n) const;
     void check_tap_ports(const AudioTapSet& s, const mx_port_ref* ports, size_t n, const std::function<void(size_t, const Node&)>& own_check = nullptr) const;
@@ -250,16 +256,18 @@ private:
     template <class Run> void launch_tap_set(const AudioTapSet& s, Run all, ProfSpan* prof);   // the run's launches of one set: on stream_, or held back with the tail
     void read_taps(const AudioTapSet& s, uint32_t first, uint32_t n, void* dst, size_t cap, size_t tick_items, size_t item_bytes, const char* cap_what);
     void reupload_taps(size_t fpc);                                      // every set's descriptors, tables and room again (the ports moved, or the call length did), on a quiescent stream
-    std::array<AudioTapSet*, 4> tap_sets() { return {&meters_, &spectra_, &loudness_, &stereo_}; }   // in launch order
+    std::array<AudioTapSet*, 5> tap_sets() { return {&meters_, &spectra_, &loudness_, &stereo_, &limiters_}; }   // in launch order
     // each set's own part: what it uploads beside the descriptors, and the run struct of its launches (after the run's last span)
     void upload_meters(size_t fpc);
     void upload_spectra(size_t fpc);
     void upload_loudness(size_t fpc);
     void upload_stereo(size_t fpc);
+    void upload_limiters(size_t fpc);
     void launch_meter_taps(uint32_t n_calls, ProfSpan* prof);
     void launch_spectrum_taps(uint32_t n_calls, ProfSpan* prof);
     void launch_loudness_taps(uint32_t n_calls, ProfSpan* prof);
     void launch_stereo_taps(uint32_t n_calls, ProfSpan* prof);
+    void launch_limiter_taps(uint32_t n_calls, ProfSpan* prof);
     size_t stereo_gon_room(size_t fpc, size_t n, uint32_t grid, uint32_t hop) const;   // goniometer records a run can emit; MX_ERR_NOMEM beyond 4 GiB
     void refresh_gates(Group& g, uint32_t run_calls);
     uint32_t trigger_of_row(const Group& g, uint32_t row) const;        // node id of the Trigger behind row `row` of a gated group, or ~0u
@@ -300,7 +308,7 @@ private:
     // taps: the audio tap sets' launches on the tail's outputs, behind those, in the sets' order.  prof: the span's profile record (nullptr: not profiled), whose tail events the release records.
     struct TailLaunch { const void* desc = nullptr; uint32_t n = 0, max_ch = 0; size_t frames = 0; int dup_mode = 0; hipEvent_t prof_ev = nullptr; };
     struct DeferredTail { bool pending = false; std::vector<TailLaunch> items; uint32_t parity = 0; ProfSpan* prof = nullptr;
-                          std::vector<OutRun> outs; std::vector<std::variant<MeterRun, SpecRun, LoudRun, StereoRun>> taps; } deferred_;
+                          std::vector<OutRun> outs; std::vector<std::variant<MeterRun, SpecRun, LoudRun, StereoRun, LimitRun>> taps; } deferred_;
     std::function<void(hipStream_t)> tail_hook_;
     std::vector<hipEvent_t> head_waits_;
     uint64_t n_gated_ = 0, n_at_once_ = 0;
@@ -361,6 +369,15 @@ private:
     uint64_t stereo_c_ = 0;
     bool stereo_run_seen_ = false;
     DevBuf stereo_carry_, stereo_gon_rec_, stereo_gon_carry_;
+    // limiter taps.  rec: LimitTick; lim_out_: the limited copies float[max ticks][lim_tick_floats_], a tick being every tap's frames x
+    // channels floats in set order (tap i's start at lim_off_[i], lim_floats_[i] of them); lim_hist_: float2[2][n][LIMIT_HIST_FRAMES], of which
+    // a run reads buffer lim_hist_cur_ and writes the other; lim_w_: the smoothing weights; lim_stage_: the read-backs' staging
+    AudioTapSet limiters_{"limiter", "limiter taps", "a video port has no level to limit"};
+    mx_limiter_params lim_par_{0.0f, 0};
+    uint32_t lim_hist_cur_ = 0, lim_max_frames_ = 0;
+    size_t lim_tick_floats_ = 0;
+    std::vector<size_t> lim_off_, lim_floats_;
+    DevBuf lim_out_, lim_hist_, lim_w_, lim_stage_;
     // video scope taps: the taps in set order; scope_rec_: the last run's records [recorded tick][tap], scope_cap_ ticks of room.  scope_c_ is the
     // hop counter (0 when the taps are set, +1 per video tick, carried across runs); a tick is recorded when scope_c_ % hop == 0 before the increment
     std::vector<mx_port_ref> scopes_;
@@ -389,7 +406,7 @@ private:
         std::vector<hipEvent_t> group_end;                              // per launch group, on the stream it ran on
         hipEvent_t video_end = nullptr, tail_begin = nullptr;           // the per-tick video section (stream_); a held-back tail's start (tail stream)
         hipEvent_t od_end = nullptr, od_tail_end = nullptr;             // OutputDevice launches on stream_ / behind the tail
-        hipEvent_t meters_end = nullptr, meters_tail_end = nullptr;     // meter, spectrum, loudness and stereo field launches on stream_ / behind the tail (and its OutputDevices)
+        hipEvent_t meters_end = nullptr, meters_tail_end = nullptr;     // meter, spectrum, loudness, stereo field and limiter launches on stream_ / behind the tail (and its OutputDevices)
         bool tail_held = false, od = false, od_tail = false, meters = false, meters_tail = false;
         explicit ProfSpan(size_t n_groups);
         ProfSpan(const ProfSpan&) = delete; ProfSpan& operator=(const ProfSpan&) = delete;

@@ -230,6 +230,28 @@ struct StereoRun {
 };
 inline size_t stereo_gonio_record_bytes(uint32_t grid) { return 32 + 4 * (size_t)grid * grid; }
 void launch_taps(const StereoRun& r, hipStream_t s);   // k_stereo_emit (a run that emits), k_stereo_reduce, k_stereo_window
+// Limiter taps (mx_k_limit.hip, mixlab_gpu.h mx_graph_set_limiters): the descriptor (TapDesc's first four fields, then the port's channels
+// and where the tap's limited copy starts inside a tick of copies), the per-tick record (= mx_limiter_tick).  Carried per tap: the last
+// 2 x lookahead frames of its stream as (L, R) pairs -- hist[slot][h] is the frame 2 x lookahead - h before the run's first -- kept twice and
+// alternating per run like the spectrum taps' history.  LIMIT_TILE: frames of a run one workgroup limits.
+static constexpr uint32_t LIMIT_MAX_LOOKAHEAD = 512, LIMIT_HIST_FRAMES = 2 * LIMIT_MAX_LOOKAHEAD, LIMIT_TILE = 2048, LIMIT_MAX_FRAMES = 1u << 30;
+struct LimitDesc { const float* p; uint32_t frames, layout, slot, channels; uint64_t off; };
+struct LimitTick { float min_gain, peak_out; uint32_t limited, nonfinite, frames, channels; };
+struct LimitRun {
+    const LimitDesc* desc; uint32_t n;       // the launch's taps
+    uint32_t n_ticks, stride;                // ticks of the run; taps of the whole set (records per tick)
+    float ceiling; uint32_t lookahead;
+    const float* weights;                    // [lookahead + 1]
+    const float2* hist_in; float2* hist_out; // [slot][LIMIT_HIST_FRAMES]: read by this run, written for the next
+    float* out; size_t tick_floats;          // the copies: out[tick * tick_floats + desc.off + frame * channels + channel]
+    LimitTick* rec;                          // rec[tick * stride + slot]
+    uint32_t max_frames;                     // most frames per tick of any tap of the set
+};
+void launch_taps(const LimitRun& r, hipStream_t s);   // k_limit_init, then k_limit
+// n_ticks rows of `width` floats, `pitch` floats apart, copied back to back (the staging of the limited copies' read-backs)
+void launch_limit_gather(const float* src, size_t pitch, uint32_t width, uint32_t n_ticks, float* dst, hipStream_t s);
+// the smoothing weights of the limiter spec, correctly rounded f32 (host only): w[lookahead + 1]; false: lookahead is above LIMIT_MAX_LOOKAHEAD
+bool limiter_weights(uint32_t lookahead, float* w);
 // Video scope taps (mx_k_scope.hip, mixlab_gpu.h mx_graph_set_video_scopes): ONE launch counts one frame into one record -- the 32-byte
 // header, hist[3][256], wave[wave_cols][256], vec[128][128], all u32.  The counters of the record must be zero when the launch starts (the
 // workgroups add their partial counts with integer atomics); the kernel writes the header itself.  counted = 0: header only.

@@ -1,19 +1,22 @@
 #!/usr/bin/env python
-"""Cost of one audio tap set on the headline-sized desk (DESIGN.md sections 0.2, 0.3, 0.5, 0.6): 1024 config-2 strips into one Mixer at
+"""Cost of one audio tap set on the headline-sized desk (DESIGN.md sections 0.2, 0.3, 0.5, 0.6, 0.8): 1024 config-2 strips into one Mixer at
 48 kHz, with no taps, with 2 taps (the Master and the Cue; not for the meters) and with 1026 taps (these and every strip's Amplifier port,
 stored one float per frame), one-tick runs and 2048-tick runs.  The cases alternate on the one graph (the set's mx_graph_set_* between
 them), three rounds each: a same-box A/B of the wall time per run.
 
-    python tools/tap_cost.py <meters|spectrum|loudness|stereo>
+    python tools/tap_cost.py <meters|spectrum|loudness|stereo|limiter>
 
   meters    hold 0, release 1
   spectrum  n_fft 2048, 31 log bands
   loudness  windows of 24 and 180 ticks
   stereo    a window of 180 ticks and a 64 x 64 goniometer: a record every 6 ticks on the buses, every 60 ticks on 1026 taps, which keeps a
             2048-tick run's records at 0.6 GB
+  limiter   ceiling 0.5, lookahead 240 frames (5 ms).  The limited copies of 1026 taps are 6.6 MB per tick of the graph's
+            max_ticks_per_run (13.4 GB at 2048), so the three cases alternate on a desk built for runs of LIMITER_LONG = 256 ticks (1.7 GB),
+            and the cases without and with 2 taps alternate again on a desk built for 2048-tick runs
 
 Run it under `rocprofv3 --kernel-trace --stats -- python tools/tap_cost.py <set>` for the kernels' own times (k_meter_*, k_spectrum*,
-k_loud_*, k_stereo_*)."""
+k_loud_*, k_stereo_*, k_limit*)."""
 import pathlib
 import statistics
 import sys
@@ -27,6 +30,7 @@ from od_cost import desk  # noqa: E402
 
 SR, SPT, N_STRIPS, N_FFT, N_BANDS = 48000, 800, 1024, 2048, 31
 HOPS = {0: 1, 2: 6, N_STRIPS + 2: 60}   # stereo: the goniometer's hop by the number of taps
+LIMITER_LONG = 256                       # limiter: ticks of the long runs that 1026 taps take part in
 
 
 def set_meters(g, taps):
@@ -43,6 +47,16 @@ def set_loudness(g, taps):
 
 def set_stereo(g, taps):
     g.set_stereo(taps, 180, 64, 0, HOPS[len(taps)])
+
+
+def set_limiter(g, taps):
+    g.set_limiters(taps, 0.5, 240)
+
+
+def read_limiter(g, taps, ticks):
+    r = g.read_limiters(ticks - 1, 1)
+    y = g.read_limited(len(taps) - 2, ticks - 1, 1)
+    assert r.shape == (1, len(taps)) and int(r["frames"][0, 0]) == SPT and y.size == 2 * SPT and float(abs(y).max()) <= 0.5
 
 
 def read_meters(g, taps, ticks):
@@ -72,21 +86,20 @@ SETS = {
     "spectrum": (set_spectrum, read_spectrum, lambda n: f"spectra={n}", True, 2, 5, "spectrum_cost"),
     "loudness": (set_loudness, read_loudness, lambda n: f"loudness={n}", True, 2, 5, "loudness_cost"),
     "stereo": (set_stereo, read_stereo, lambda n: f"stereo={n} hop={HOPS[n]}", True, 2, 5, "stereo_cost"),
+    "limiter": (set_limiter, read_limiter, lambda n: f"limiters={n}", True, 2, 5, "limiter_cost"),
 }
 
 
-def main(which):
-    set_taps, check_read, head, with_buses, warm, long_reps, name = SETS[which]
+def measure(which, max_ticks, cases, lengths):
+    """the cases alternating on one desk built for runs of max_ticks ticks: three rounds per run length, the median printed"""
+    set_taps, check_read, head, _, warm, _, _ = SETS[which]
     ws, srcs, _ = desk(N_STRIPS, SR, False)
-    mix = 0
-    buses = [(mix, 0), (mix, 1)]
-    cases = [[]] + ([buses] if with_buses else []) + [[(mix + 6 * (k + 1), 0) for k in range(N_STRIPS)] + buses]
-    g = ws.build(max_ticks_per_run=2048)
-    x = synth.noise(1, 2048 * SPT)
+    g = ws.build(max_ticks_per_run=max_ticks)
+    x = synth.noise(1, max_ticks * SPT)
     for s in srcs:
-        g.write_source(s, x, 2048)
+        g.write_source(s, x, max_ticks)
     tick = 0
-    for ticks, reps in ((1, 200), (2048, long_reps)):
+    for ticks, reps in lengths:
         res = [[] for _ in cases]
         for rnd in range(3):
             for k, taps in enumerate(cases):
@@ -109,6 +122,18 @@ def main(which):
             algo = ticks * (N_STRIPS * SPT * 4 + 2 * SPT * 8) + ticks * len(cases[-1]) * 48
             print(f"ticks={ticks} algorithmic_bytes={algo}", flush=True)
     g.close()
+
+
+def main(which):
+    _, _, _, with_buses, _, long_reps, name = SETS[which]
+    mix = 0
+    buses = [(mix, 0), (mix, 1)]
+    cases = [[]] + ([buses] if with_buses else []) + [[(mix + 6 * (k + 1), 0) for k in range(N_STRIPS)] + buses]
+    if which == "limiter":
+        measure(which, LIMITER_LONG, cases, ((1, 200), (LIMITER_LONG, 3 * long_reps)))
+        measure(which, 2048, cases[:2], ((2048, long_reps),))
+    else:
+        measure(which, 2048, cases, ((1, 200), (2048, long_reps)))
     print(f"{name} done")
 
 
