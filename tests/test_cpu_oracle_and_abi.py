@@ -108,6 +108,9 @@ def test_oracle_envelope_shape():
     assert abs(out[-1] - 0.8) < 1e-6                                            # sustain after decay
     off = oracle.envelope_run(st, p, 44100.0, 44100, np.zeros(22050, np.float32), 22050)
     assert abs(off[0] - 0.8) < 1e-6 and off[int(0.2 * 44100) + 1] == 0.0        # released after 200 ms
+    # the same samples, exactly: the bit patterns of tests/audio_model.py, the numpy restatement of envelope.rs (test_cpu_audio_model.py compares every sample)
+    assert [int(v) for v in bits([out[0], out[1102], out[-1], off[0], off[8821]])] == [0x00000000, 0x3F7FE247, 0x3F4CCCCD, 0x3F4CCCCD, 0x00000000]
+    assert int(bits(out[1103:1104])[0]) == 0x3F7FFFB4 and int(bits(off[8820:8821])[0]) == 0            # the decay's first sample; the release ends on sample 8820 itself
     # exact-compare gate semantics: 0.5 is neither on nor off (envelope.rs:102,107)
     st2 = oracle.EnvState()
     assert not oracle.envelope_run(st2, p, 44100.0, 0, np.full(100, 0.5, np.float32), 100).any()
