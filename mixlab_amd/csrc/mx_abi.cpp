@@ -214,22 +214,22 @@ int mx_graph_audio_out_lag(mx_graph* g, uint32_t node) {
 }
 
 int mx_graph_set_meters(mx_graph* g, const mx_port_ref* ports, size_t n, const mx_meter_params* params) {
-    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->set_meters(ports, n, params); });
+    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->meters().set(ports, n, params); });
 }
 
 int mx_graph_read_meters(mx_graph* g, uint32_t first_tick_in_run, uint32_t n_ticks, mx_meter_tick* dst, size_t cap) {
     static_assert(sizeof(mx_meter_tick) == 48 && sizeof(mx_meter_tick) == sizeof(mx::MeterTick), "mx_meter_tick is the device record");
     static_assert(offsetof(mx_meter_tick, sum_sq) == offsetof(mx::MeterTick, sum_sq) && offsetof(mx_meter_tick, frames) == offsetof(mx::MeterTick, frames),
                   "mx_meter_tick is the device record");
-    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->read_meters(first_tick_in_run, n_ticks, reinterpret_cast<mx::MeterTick*>(dst), cap); });
+    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->meters().read(first_tick_in_run, n_ticks, dst, cap); });
 }
 
 int mx_graph_set_spectra(mx_graph* g, const mx_port_ref* ports, size_t n, const mx_spectrum_params* params) {
-    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->set_spectra(ports, n, params); });
+    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->spectra().set(ports, n, params); });
 }
 
 int mx_graph_read_spectra(mx_graph* g, uint32_t first_tick_in_run, uint32_t n_ticks, float* dst, size_t cap) {
-    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->read_spectra(first_tick_in_run, n_ticks, dst, cap); });
+    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->spectra().read(first_tick_in_run, n_ticks, dst, cap); });
 }
 
 int mx_spectrum_tables(uint32_t n_fft, float* window, float* twiddle_re, float* twiddle_im) {   // host only: no device, no graph
@@ -237,12 +237,12 @@ int mx_spectrum_tables(uint32_t n_fft, float* window, float* twiddle_re, float* 
 }
 
 int mx_graph_set_loudness(mx_graph* g, const mx_port_ref* ports, size_t n, const mx_loudness_params* params) {
-    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->set_loudness(ports, n, params); });
+    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->loudness().set(ports, n, params); });
 }
 
 int mx_graph_read_loudness(mx_graph* g, uint32_t first_tick_in_run, uint32_t n_ticks, mx_loudness_tick* dst, size_t cap) {
     static_assert(sizeof(mx_loudness_tick) == sizeof(mx::LoudTick) && sizeof(mx_loudness_tick) == 48, "mx_loudness_tick is the kernels' record");
-    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->read_loudness(first_tick_in_run, n_ticks, reinterpret_cast<mx::LoudTick*>(dst), cap); });
+    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->loudness().read(first_tick_in_run, n_ticks, dst, cap); });
 }
 
 int mx_loudness_tables(double rate, uint32_t frames_per_tick, double* biquads, double* carry, float* interp) {   // host only: no device, no graph
@@ -276,38 +276,38 @@ int mx_loudness_gate(const double* block_sq, const uint32_t* block_frames, size_
 }
 
 int mx_graph_set_stereo(mx_graph* g, const mx_port_ref* ports, size_t n, const mx_stereo_params* params) {
-    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->set_stereo(ports, n, params); });
+    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->stereo().set(ports, n, params); });
 }
 
 int mx_graph_read_stereo(mx_graph* g, uint32_t first_tick_in_run, uint32_t n_ticks, mx_stereo_tick* dst, size_t cap) {
     static_assert(sizeof(mx_stereo_tick) == sizeof(mx::StereoTick) && sizeof(mx_stereo_tick) == 56, "mx_stereo_tick is the kernels' record");
-    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->read_stereo(first_tick_in_run, n_ticks, reinterpret_cast<mx::StereoTick*>(dst), cap); });
+    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->stereo().read(first_tick_in_run, n_ticks, dst, cap); });
 }
 
 int mx_graph_read_goniometers(mx_graph* g, void* dst, size_t cap_bytes, uint32_t* n_records) {
-    return guard([&] { REQUIRE(g, "graph is NULL"); const size_t n = g->g->read_goniometers(dst, cap_bytes); if (n_records) *n_records = (uint32_t)n; });
+    return guard([&] { REQUIRE(g, "graph is NULL"); const size_t n = g->g->stereo().read_goniometers(dst, cap_bytes); if (n_records) *n_records = (uint32_t)n; });
 }
 
 int mx_graph_set_limiters(mx_graph* g, const mx_port_ref* ports, size_t n, const mx_limiter_params* params) {
-    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->set_limiters(ports, n, params); });
+    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->limiters().set(ports, n, params); });
 }
 
 int mx_graph_read_limiters(mx_graph* g, uint32_t first_tick_in_run, uint32_t n_ticks, mx_limiter_tick* dst, size_t cap) {
     static_assert(sizeof(mx_limiter_tick) == sizeof(mx::LimitTick) && sizeof(mx_limiter_tick) == 24, "mx_limiter_tick is the kernels' record");
     static_assert(MX_LIMITER_MAX_LOOKAHEAD == mx::LIMIT_MAX_LOOKAHEAD, "the header's bound is the kernels'");
-    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->read_limiters(first_tick_in_run, n_ticks, reinterpret_cast<mx::LimitTick*>(dst), cap); });
+    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->limiters().read(first_tick_in_run, n_ticks, dst, cap); });
 }
 
 int mx_graph_read_limited(mx_graph* g, size_t tap, uint32_t first_tick_in_run, uint32_t n_ticks, float* samples, size_t cap, size_t* n_samples) {
-    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->read_limited(tap, first_tick_in_run, n_ticks, samples, nullptr, cap, n_samples); });
+    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->limiters().read_limited(tap, first_tick_in_run, n_ticks, samples, nullptr, cap, n_samples); });
 }
 
 int mx_graph_read_limited_i16(mx_graph* g, size_t tap, uint32_t first_tick_in_run, uint32_t n_ticks, int16_t* samples, size_t cap, size_t* n_samples) {
-    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->read_limited(tap, first_tick_in_run, n_ticks, nullptr, samples, cap, n_samples); });
+    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->limiters().read_limited(tap, first_tick_in_run, n_ticks, nullptr, samples, cap, n_samples); });
 }
 
 int mx_graph_limited_device_ptr(mx_graph* g, size_t tap, void** dev, size_t* floats_per_tick) {
-    return guard([&] { REQUIRE(g && dev, "NULL argument"); *dev = g->g->limited_ptr(tap, floats_per_tick); });
+    return guard([&] { REQUIRE(g && dev, "NULL argument"); *dev = g->g->limiters().limited_ptr(tap, floats_per_tick); });
 }
 
 int mx_limiter_weights(uint32_t lookahead, float* w) {   // host only: no device, no graph

@@ -8,7 +8,6 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <map>
 
 namespace mx {
 
@@ -470,7 +469,7 @@ void Graph::flush_deferred_tail(bool gated) {
     for (const OutRun& r : deferred_.outs) launch_output_device(r, tail_stream_);   // OutputDevices that read the tail's outputs
     if (prof && !deferred_.outs.empty()) hip_check(hipEventRecord(prof->od_tail_end, tail_stream_), "hipEventRecord");
     deferred_.outs.clear();
-    for (const auto& t : deferred_.taps) std::visit([&](const auto& r) { launch_taps(r, tail_stream_); }, t);   // the audio tap sets on the tail's outputs, in the sets' order
+    for (const AudioTapSet* t : deferred_.taps) t->launch(t->n_head, t->size() - t->n_head, deferred_.parity, tail_stream_);   // the audio tap sets' taps on the tail's outputs, in the sets' order
     if (prof && !deferred_.taps.empty()) hip_check(hipEventRecord(prof->meters_tail_end, tail_stream_), "hipEventRecord");
     deferred_.taps.clear();
     if (tail_hook_) { auto hook = std::move(tail_hook_); tail_hook_ = nullptr; hook(tail_stream_); }   // (mx_exchange: pack + exchange of that run's buses, behind the bank)
@@ -1060,7 +1059,7 @@ void Graph::run(uint64_t t0, size_t fpc, uint32_t n_calls, float* ms_by_kind, fl
     const size_t frames = fpc * (size_t)n_calls;
     auto drop_schedules = [&] { for (uint32_t id : sched_nodes_) { nodes_[id].sched.clear(); nodes_[id].gate_sched.clear(); } sched_nodes_.clear(); };
     if (frames > cap_frames_) { drop_schedules(); throw Error(MX_ERR_INVALID, "n_ticks exceeds max_ticks_per_run"); }
-    if (n_calls == 0 || fpc == 0) { drop_schedules(); last_calls_ = n_calls; last_frames_per_call_ = fpc; for (AudioTapSet* s : tap_sets()) s->run_ticks = 0; stereo_gon_n_ = 0; scope_n_ = 0; return; }
+    if (n_calls == 0 || fpc == 0) { drop_schedules(); last_calls_ = n_calls; last_frames_per_call_ = fpc; for (AudioTapSet* s : taps_) s->empty_run(); scope_n_ = 0; return; }
     // keyed video sources: a frame the keyer cannot take fails the run HERE, before anything of it is launched or any node's state has moved
     for (uint32_t id : video_order_) {
         const Node& n = nodes_[id];
@@ -1076,8 +1075,7 @@ void Graph::run(uint64_t t0, size_t fpc, uint32_t n_calls, float* ms_by_kind, fl
     }
     hip_check(hipSetDevice(device_), "hipSetDevice");
     if (fpc != tap_fpc_) {   // (the module compat path's call length): frames per tick and record room
-        const auto sets = tap_sets();
-        if (std::any_of(sets.begin(), sets.end(), [](const AudioTapSet* s) { return !s->empty(); })) { sync(); reupload_taps(fpc); }
+        if (std::any_of(taps_.begin(), taps_.end(), [](const AudioTapSet* s) { return !s->empty(); })) { sync(); reupload_taps(fpc); }
     }
 
     // ---- scheduled parameter updates (Engine::client_update between two ticks, src/engine.rs:192-214,277-398) ----
@@ -1196,7 +1194,7 @@ void Graph::run(uint64_t t0, size_t fpc, uint32_t n_calls, float* ms_by_kind, fl
     hip_check(hipGetLastError(), "kernel launch");
     last_calls_ = n_calls;
     last_frames_per_call_ = fpc;
-    for (AudioTapSet* s : tap_sets()) s->run_ticks = s->empty() ? 0u : n_calls;
+    for (AudioTapSet* s : taps_) s->run_ticks = s->empty() ? 0u : n_calls;
     if (prof) ++prof_runs_count_;
     if (ms_by_kind) (void)profile_collect(ms_by_kind, ms_total);
 }
@@ -1337,7 +1335,7 @@ void Graph::run_span(uint64_t t0, size_t fpc, uint32_t call_off, uint32_t n_call
     // after everything else of the span on stream_ (the video section included): its profile interval starts at the latest event recorded there
     launch_outputs(t0, call_off, n_calls, prof);
     // the port buffers hold every tick of the run: the audio tap sets go once, after its last span, in this order on either stream
-    if (call_off + n_calls == run_calls) { launch_meter_taps(run_calls, prof); launch_spectrum_taps(run_calls, prof); launch_loudness_taps(run_calls, prof); launch_stereo_taps(run_calls, prof); launch_limiter_taps(run_calls, prof); }
+    if (call_off + n_calls == run_calls) for (AudioTapSet* s : taps_) launch_tap_set(*s, run_calls, prof);
     if (prof) { prof_runs_.push_back(std::move(prof_pool_.back())); prof_pool_.pop_back(); }
 }
 
@@ -1594,79 +1592,28 @@ void Graph::audio_out_lag(uint32_t node) {
     nodes_[node].od_lag->store(true);   // AtomicBool::store (output_device.rs:126); nothing else of the graph is touched
 }
 
-// ---- the audio tap sets: level meters, spectrum, loudness, stereo field and limiter taps (mixlab_gpu.h mx_graph_set_meters, _spectra,
-// _loudness, _stereo, _limiters; DESIGN.md sections 0.2, 0.3, 0.5, 0.6, 0.8).  What the five share comes first, written for "a tap set"; then each set's own part ----
+// ---- the audio tap sets (mx_taps.hpp): what the engine keeps of them is the port a set sees, the list in launch order (taps_) and where a run's launches go ----
 
-void Graph::check_tap_args(const AudioTapSet& s, const void* ports, const void* params, size_t n) const {
-    if (n && (!ports || !params)) throw Error(MX_ERR_INVALID, "ports / params is NULL");
-    if (n > 0xffffffu) throw Error(MX_ERR_INVALID, std::string("more than 2^24 ") + s.noun);
+bool Graph::tap_port(mx_port_ref r, TapPort& t) const {
+    if (r.node >= nodes_.size() || r.port >= nodes_[r.node].out_type.size()) return false;
+    const Node& nd = nodes_[r.node];
+    int32_t o = (int32_t)r.node;
+    while (nodes_[o].elided && nodes_[o].owner >= 0) o = nodes_[o].owner;   // the node whose launch writes the port
+    t.type = nd.out_type[r.port]; t.dup = nd.out_dup[r.port]; t.elided = nd.out_elided[r.port];
+    t.on_tail = tail_gi_ >= 0 && nodes_[o].group >= tail_gi_; t.dom_num = nd.dom_num; t.dom_den = nd.dom_den;
+    for (uint32_t par = 0; par < 2 && !t.elided; ++par)   // the port at tick 0 of the run (out_ptr without a span's offset)
+        t.p[par] = nd.bound && r.port == 0 ? nd.bound : (const float*)slab_.p + (par && nd.out_off2[r.port] != SIZE_MAX ? nd.out_off2[r.port] : nd.out_off[r.port]);
+    return true;
 }
 
-// own_check: a set's own check of one tap, behind the shared ones of that tap
-void Graph::check_tap_ports(const AudioTapSet& s, const mx_port_ref* ports, size_t n, const std::function<void(size_t, const Node&)>& own_check) const {
-    const std::string tag = std::string(s.tag) + ": ";
-    std::vector<uint64_t> keys(n);
-    for (size_t i = 0; i < n; ++i) {
-        const mx_port_ref pr = ports[i];
-        if (pr.node >= nodes_.size() || pr.port >= nodes_[pr.node].out_type.size()) throw Error(MX_ERR_INVALID, tag + "output terminal out of range");
-        const Node& nd = nodes_[pr.node];
-        if (s.stereo_only ? nd.out_type[pr.port] != MX_STEREO : nd.out_type[pr.port] == MX_VIDEO) throw Error(MX_ERR_TYPE, tag + s.no_type);
-        if (nd.out_elided[pr.port]) throw Error(MX_ERR_INVALID, "port is not materialised: it only feeds a fused consumer (build with MX_FLAG_NO_FUSE to observe it)");
-        if (own_check) own_check(i, nd);
-        keys[i] = (uint64_t)pr.node << 32 | pr.port;
-    }
-    std::sort(keys.begin(), keys.end());
-    if (std::adjacent_find(keys.begin(), keys.end()) != keys.end()) throw Error(MX_ERR_INVALID, tag + "duplicate (node, port)");
-}
-
-// The descriptors of every tap for both buffer parities (the second only differs for a port the tail reads, while the second-stream mode is
-// on), in launch order: the taps read on stream_ (s.n_head of them), then those on the tail's outputs.
-std::vector<TapDesc> Graph::tap_descs(AudioTapSet& s, size_t fpc) const {
-    const size_t n = s.ports.size();
-    std::vector<uint32_t> order, tail;
-    for (uint32_t i = 0; i < (uint32_t)n; ++i) {
-        int32_t o = (int32_t)s.ports[i].node;
-        while (nodes_[o].elided && nodes_[o].owner >= 0) o = nodes_[o].owner;   // the node whose launch writes the port
-        (tail_gi_ >= 0 && nodes_[o].group >= tail_gi_ ? tail : order).push_back(i);
-    }
-    s.n_head = (uint32_t)order.size();
-    order.insert(order.end(), tail.begin(), tail.end());
-    std::vector<TapDesc> d(2 * n);
-    for (uint32_t par = 0; par < 2; ++par)
-        for (size_t k = 0; k < n; ++k) {
-            const mx_port_ref tp = s.ports[order[k]];
-            const Node& nd = nodes_[tp.node];
-            TapDesc& m = d[par * n + k];
-            // the port at tick 0 of the run (out_ptr without a span's offset)
-            if (nd.bound && tp.port == 0) m.p = nd.bound;
-            else m.p = (const float*)slab_.p + (par && nd.out_off2[tp.port] != SIZE_MAX ? nd.out_off2[tp.port] : nd.out_off[tp.port]);
-            m.frames = (uint32_t)(fpc * nd.dom_num / nd.dom_den);
-            m.layout = nd.out_dup[tp.port] ? METER_DUP : (nd.out_type[tp.port] == MX_MONO ? METER_MONO : METER_STEREO);
-            m.slot = order[k]; m._pad = 0;
-        }
-    return d;
-}
-
-// ... to the device, and room for a whole submission's records of tick_bytes per tick.  The stream is quiescent.  Whatever a set carries from
-// run to run is untouched: it holds frames and ticks, whatever the call length.
-void Graph::upload_tap_descs(AudioTapSet& s, const void* d, size_t bytes, size_t fpc, size_t tick_bytes) {
-    s.desc.alloc(bytes);
-    hip_check(hipMemcpy(s.desc.p, d, bytes, hipMemcpyHostToDevice), (std::string("hipMemcpy(") + s.tag + " descriptors)").c_str());
-    const size_t need = std::max<size_t>(1, cap_frames_ / fpc) * tick_bytes;
-    if (!s.rec.p || s.rec.bytes < need) s.rec.alloc(need);
-}
-
+// (known wart: an upload that throws leaves the sets before it built for the new call length and tap_fpc_ at the old one)
 void Graph::reupload_taps(size_t fpc) {
-    if (!meters_.empty()) upload_meters(fpc);
-    if (!spectra_.empty()) upload_spectra(fpc);
-    if (!loudness_.empty()) upload_loudness(fpc);
-    if (!stereo_.empty()) upload_stereo(fpc);
-    if (!limiters_.empty()) upload_limiters(fpc);
+    for (AudioTapSet* s : taps_) if (!s->empty()) s->upload(fpc);
     tap_fpc_ = fpc;
 }
 
-// The run's launches of one tap set, after its last span and behind the sets before it: `all` is the run struct of the whole set, its
-// descriptors those of parity 0.  Why no buffer a tap reads is overwritten before it has read it:
+// The run's launches of one tap set, after its last span and behind the sets before it: the set fixes the run struct of the whole set
+// (begin_run), the engine says which taps go where.  Why no buffer a tap reads is overwritten before it has read it:
 //  - a tap read on stream_ (every tap when the run is on one stream: a cut run, a short one in the automatic mode, a graph without the mode)
 //    is queued there behind the run's producers and ahead of the next run's launches, which are the only ones that write that port again.  Its
 //    descriptor points at THIS run's buffer parity: the tail-read ports alternate per run, run k + 1 writes the other buffer, and run k + 2 --
@@ -1679,420 +1626,15 @@ void Graph::reupload_taps(size_t fpc) {
 // two groups of taps are disjoint (slots), and a group's launches of consecutive runs follow each other on that group's stream (a run that
 // changes the stream of the tail's taps has joined the tail first: run()'s wait_tail) -- so state that one run hands to the next, updated
 // in place or through a pair of buffers that flips once per run for both groups, is read after it was written.
-template <class Run> void Graph::launch_tap_set(const AudioTapSet& s, Run all, ProfSpan* prof) {
-    const uint32_t n = all.n;
-    all.desc += (size_t)(parity_ & 1u) * n;
-    const uint32_t n_head = overlap_this_run_ ? s.n_head : n;
-    if (n_head < n) { Run t = all; t.desc += n_head; t.n = n - n_head; deferred_.taps.emplace_back(t); }
-    all.n = n_head;
-    if (n_head) launch_taps(all, stream_);
+void Graph::launch_tap_set(AudioTapSet& s, uint32_t n_calls, ProfSpan* prof) {
+    if (s.empty()) return;
+    s.begin_run(n_calls);
+    const uint32_t n = s.size(), n_head = overlap_this_run_ ? s.n_head : n;
+    if (n_head < n) deferred_.taps.push_back(&s);   // (the rest of the set's run, from its run struct: flush_deferred_tail)
+    if (n_head) s.launch(0, n_head, parity_, stream_);
     if (!prof) return;
     if (n_head) { hip_check(hipEventRecord(prof->meters_end, stream_), "hipEventRecord"); prof->meters = true; }   // (again, when an earlier set recorded it: the later record holds)
     prof->meters_tail = !deferred_.taps.empty();
-}
-
-// ticks [first, first + n) of the last run's records: tick_items items of item_bytes each per tick, cap counted in items
-void Graph::read_taps(const AudioTapSet& s, uint32_t first, uint32_t n, void* dst, size_t cap, size_t tick_items, size_t item_bytes, const char* cap_what) {
-    hip_check(hipSetDevice(device_), "hipSetDevice");
-    if (s.empty()) throw Error(MX_ERR_INVALID, std::string("no ") + s.noun + " are set");
-    if ((uint64_t)first + n > s.run_ticks) throw Error(MX_ERR_INVALID, std::string("the window lies beyond the last run (or no run since the ") + s.noun + " were set)");
-    const size_t count = (size_t)n * tick_items;
-    if (cap < count) throw Error(MX_ERR_INVALID, std::string("cap is smaller than ") + cap_what);
-    if (count && !dst) throw Error(MX_ERR_INVALID, "dst is NULL");
-    if (!count) return;
-    wait_tail(-1);
-    hip_check(hipMemcpyAsync(dst, (const char*)s.rec.p + (size_t)first * tick_items * item_bytes, count * item_bytes, hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(D2H)");
-    sync();
-}
-
-// ---- level meters ----
-
-void Graph::set_meters(const mx_port_ref* ports, size_t n, const mx_meter_params* params) {
-    hip_check(hipSetDevice(device_), "hipSetDevice");
-    check_tap_args(meters_, ports, params, n);
-    check_tap_ports(meters_, ports, n, [&](size_t i, const Node&) {
-        const float rel = params[i].release;
-        if (!(std::isfinite(rel) && rel > 0.0f && rel <= 1.0f)) throw Error(MX_ERR_INVALID, "mx_meter_params: release must be finite, 0 < release <= 1");
-    });
-    // like a read-back: the last run's launches (held-back tail included) are done with the records and states.  The second-stream mode stays on:
-    // the taps read the ports through descriptors of both parities, in stream order with their producers (launch_tap_set)
-    sync();
-    DevBuf st;
-    if (n) {
-        st.alloc(n * 2 * sizeof(MeterHold));
-        hip_check(hipMemsetAsync(st.p, 0, n * 2 * sizeof(MeterHold), stream_), "hipMemsetAsync(meter state)");
-        for (size_t i = 0; i < n; ++i)   // a surviving tap keeps its hold
-            for (size_t j = 0; j < meters_.ports.size(); ++j)
-                if (meters_.ports[j].node == ports[i].node && meters_.ports[j].port == ports[i].port)
-                    hip_check(hipMemcpyAsync((MeterHold*)st.p + 2 * i, (const MeterHold*)meter_state_.p + 2 * j, 2 * sizeof(MeterHold), hipMemcpyDeviceToDevice, stream_),
-                              "hipMemcpyAsync(meter state)");
-        hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
-    }
-    meters_.ports.assign(ports, ports + n);
-    meter_par_.assign(params, params + n);
-    meter_state_ = std::move(st);
-    meters_.run_ticks = 0;
-    meters_.rec.free_();
-    if (meters_.empty()) { meters_.desc.free_(); return; }
-    upload_meters(tap_fpc_);
-}
-
-// the shared fields of every descriptor from its TapDesc, then the tap's own parameters
-void Graph::upload_meters(size_t fpc) {
-    const std::vector<TapDesc> t = tap_descs(meters_, fpc);
-    std::vector<MeterDesc> d(t.size());
-    for (size_t k = 0; k < t.size(); ++k)
-        d[k] = MeterDesc{t[k].p, t[k].frames, t[k].layout, t[k].slot, meter_par_[t[k].slot].hold_ticks, meter_par_[t[k].slot].release, 0};
-    upload_tap_descs(meters_, d.data(), d.size() * sizeof(MeterDesc), fpc, meters_.ports.size() * sizeof(MeterTick));
-}
-
-void Graph::launch_meter_taps(uint32_t n_calls, ProfSpan* prof) {
-    if (meters_.empty()) return;
-    const uint32_t n = meters_.size();
-    launch_tap_set(meters_, MeterRun{(const MeterDesc*)meters_.desc.p, n, n_calls, n, (MeterTick*)meters_.rec.p, (MeterHold*)meter_state_.p}, prof);
-}
-
-void Graph::read_meters(uint32_t first, uint32_t n, MeterTick* dst, size_t cap) {
-    read_taps(meters_, first, n, dst, cap, meters_.ports.size(), sizeof(MeterTick), "n_ticks x meters");
-}
-
-// ---- spectrum taps ----
-
-void Graph::set_spectra(const mx_port_ref* ports, size_t n, const mx_spectrum_params* params) {
-    hip_check(hipSetDevice(device_), "hipSetDevice");
-    check_tap_args(spectra_, ports, params, n);
-    std::vector<float> win, tre, tim;
-    if (n) {
-        const uint32_t N = params->n_fft, B = params->n_bands;
-        win.resize(N <= 4096 ? N : 0); tre.resize(win.size() / 2); tim.resize(win.size() / 2);
-        if (N > 4096 || !spectrum_tables(N, win.data(), tre.data(), tim.data())) throw Error(MX_ERR_INVALID, "mx_spectrum_params: n_fft must be 256, 512, 1024, 2048 or 4096");
-        if (B < 1 || B > 128) throw Error(MX_ERR_INVALID, "mx_spectrum_params: n_bands must be 1 .. 128");
-        if (!params->edges) throw Error(MX_ERR_INVALID, "mx_spectrum_params: edges is NULL");
-        for (uint32_t j = 0; j < B; ++j)
-            if (params->edges[j] >= params->edges[j + 1]) throw Error(MX_ERR_INVALID, "mx_spectrum_params: edges must be strictly ascending");
-        if (params->edges[B] > N / 2 + 1) throw Error(MX_ERR_INVALID, "mx_spectrum_params: edges[n_bands] exceeds n_fft / 2 + 1");
-    }
-    check_tap_ports(spectra_, ports, n);
-    // like set_meters: the last run's launches are done with the records and histories; the second-stream mode stays on
-    sync();
-    spectra_.ports.assign(ports, ports + n);
-    spectra_.run_ticks = 0;
-    spec_hist_cur_ = 0;
-    spectra_.rec.free_();
-    if (spectra_.empty()) { spectra_.desc.free_(); spec_hist_.free_(); spec_tab_.free_(); spec_n_fft_ = spec_n_bands_ = 0; return; }
-    const uint32_t N = spec_n_fft_ = params->n_fft, B = spec_n_bands_ = params->n_bands;
-    // tables: window[N] | twiddle (re, im)[N / 2] | edges[B + 1] (u16, padded to whole floats)
-    std::vector<float> tab(2 * (size_t)N + (B + 2) / 2, 0.0f);
-    std::copy(win.begin(), win.end(), tab.begin());
-    for (uint32_t k = 0; k < N / 2; ++k) { tab[N + 2 * k] = tre[k]; tab[N + 2 * k + 1] = tim[k]; }
-    memcpy(tab.data() + 2 * (size_t)N, params->edges, (B + 1) * sizeof(uint16_t));
-    spec_tab_.alloc(tab.size() * sizeof(float));
-    hip_check(hipMemcpy(spec_tab_.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy(spectrum tables)");
-    // every tap's history starts as +0.0: frames before this call read as silence
-    spec_hist_.alloc(2 * n * 2 * (size_t)N * sizeof(float));
-    hip_check(hipMemsetAsync(spec_hist_.p, 0, 2 * n * 2 * (size_t)N * sizeof(float), stream_), "hipMemsetAsync(spectrum history)");
-    hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
-    upload_spectra(tap_fpc_);
-}
-
-void Graph::upload_spectra(size_t fpc) {
-    const std::vector<TapDesc> d = tap_descs(spectra_, fpc);
-    upload_tap_descs(spectra_, d.data(), d.size() * sizeof(TapDesc), fpc, spectra_.ports.size() * 2 * spec_n_bands_ * sizeof(float));
-}
-
-// Each run reads the history buffer the previous one wrote: spec_hist_cur_ flips once per run.
-void Graph::launch_spectrum_taps(uint32_t n_calls, ProfSpan* prof) {
-    if (spectra_.empty()) return;
-    const uint32_t n = spectra_.size(), N = spec_n_fft_;
-    const float* tab = (const float*)spec_tab_.p;
-    float* h0 = (float*)spec_hist_.p + (size_t)spec_hist_cur_ * n * 2 * N;
-    float* h1 = (float*)spec_hist_.p + (size_t)(spec_hist_cur_ ^ 1u) * n * 2 * N;
-    spec_hist_cur_ ^= 1u;
-    launch_tap_set(spectra_, SpecRun{(const TapDesc*)spectra_.desc.p, n, n_calls, n, N, spec_n_bands_,
-                                     tab, (const float2*)(tab + N), (const uint16_t*)(tab + 2 * (size_t)N), h0, h1, (float*)spectra_.rec.p}, prof);
-}
-
-void Graph::read_spectra(uint32_t first, uint32_t n, float* dst, size_t cap) {
-    read_taps(spectra_, first, n, dst, cap, spectra_.ports.size() * 2 * spec_n_bands_, sizeof(float), "n_ticks x taps x 2 x n_bands");
-}
-
-// ---- loudness taps ----
-
-void Graph::set_loudness(const mx_port_ref* ports, size_t n, const mx_loudness_params* params) {
-    hip_check(hipSetDevice(device_), "hipSetDevice");
-    check_tap_args(loudness_, ports, params, n);
-    if (n) {
-        if (params->momentary_ticks < 1 || params->momentary_ticks > 1024) throw Error(MX_ERR_INVALID, "mx_loudness_params: momentary_ticks must be 1 .. 1024");
-        if (params->short_ticks < 1 || params->short_ticks > 1024) throw Error(MX_ERR_INVALID, "mx_loudness_params: short_ticks must be 1 .. 1024");
-    }
-    check_tap_ports(loudness_, ports, n, [&](size_t, const Node& nd) {
-        if (!loudness_tables(sample_rate_ * nd.dom_num / nd.dom_den, 1, nullptr, nullptr, nullptr)) throw Error(MX_ERR_INVALID, "loudness: the port's rate is not above twice the shelf frequency (3 364 Hz)");
-    });
-    // like set_spectra: the last run's launches are done with the records and the carried state; the second-stream mode stays on
-    sync();
-    loudness_.ports.assign(ports, ports + n);
-    loudness_.run_ticks = 0;
-    loud_hist_cur_ = 0;
-    loudness_.rec.free_(); loud_walk_.free_();
-    if (loudness_.empty()) { loudness_.desc.free_(); loud_tab_.free_(); loud_carry_.free_(); loud_par_ = mx_loudness_params{0, 0}; return; }
-    loud_par_ = *params;
-    // filter state, window history and interpolator history all start as +0.0: the stream before this call reads as silence
-    const size_t carry_bytes = n * (8 + 2 * (size_t)LOUD_HIST_TICKS) * sizeof(double) + 2 * n * 2 * LOUD_HIST_FRAMES * sizeof(float);
-    loud_carry_.alloc(carry_bytes);
-    hip_check(hipMemsetAsync(loud_carry_.p, 0, carry_bytes, stream_), "hipMemsetAsync(loudness state)");
-    hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
-    upload_loudness(tap_fpc_);
-}
-
-// beside the descriptors: room for the walk states and -- what depends on the call length here -- each tap's coefficients, the biquads of its
-// port's own rate and the carry matrix of its tick length
-void Graph::upload_loudness(size_t fpc) {
-    const size_t n = loudness_.ports.size();
-    const std::vector<TapDesc> d = tap_descs(loudness_, fpc);
-    upload_tap_descs(loudness_, d.data(), d.size() * sizeof(TapDesc), fpc, n * sizeof(LoudTick));
-    // LoudCoef[n] by slot | interp[36]; taps of one rate domain share one evaluation
-    std::vector<unsigned char> tab(n * sizeof(LoudCoef) + 36 * sizeof(float));
-    std::map<std::pair<uint32_t, uint32_t>, LoudCoef> by_dom;
-    for (size_t i = 0; i < n; ++i) {
-        const Node& nd = nodes_[loudness_.ports[i].node];
-        auto it = by_dom.find({nd.dom_num, nd.dom_den});
-        if (it == by_dom.end()) {
-            LoudCoef c;
-            if (!loudness_tables(sample_rate_ * nd.dom_num / nd.dom_den, (uint32_t)(fpc * nd.dom_num / nd.dom_den), c.bq, c.carry, nullptr))
-                throw Error(MX_ERR_INVALID, "loudness: the call length gives a tick the taps cannot measure");
-            it = by_dom.emplace(std::make_pair(nd.dom_num, nd.dom_den), c).first;
-        }
-        memcpy(tab.data() + i * sizeof(LoudCoef), &it->second, sizeof(LoudCoef));
-    }
-    (void)loudness_tables(sample_rate_, 1, nullptr, nullptr, reinterpret_cast<float*>(tab.data() + n * sizeof(LoudCoef)));   // (the interpolator depends on neither)
-    loud_tab_.alloc(tab.size());
-    hip_check(hipMemcpy(loud_tab_.p, tab.data(), tab.size(), hipMemcpyHostToDevice), "hipMemcpy(loudness tables)");
-    loud_max_ticks_ = (uint32_t)std::max<size_t>(1, cap_frames_ / fpc);
-    const size_t need_walk = (size_t)loud_max_ticks_ * n * 2 * 4 * sizeof(double);
-    if (!loud_walk_.p || loud_walk_.bytes < need_walk) loud_walk_.alloc(need_walk);
-}
-
-// The filter state is updated in place by the one lane that owns it; each run reads the history buffers the previous one wrote
-// (loud_hist_cur_ flips once per run).
-void Graph::launch_loudness_taps(uint32_t n_calls, ProfSpan* prof) {
-    if (loudness_.empty()) return;
-    const uint32_t n = loudness_.size();
-    double* state = (double*)loud_carry_.p;
-    double* eh = state + (size_t)n * 8;
-    float* xh = (float*)(eh + 2 * (size_t)n * LOUD_HIST_TICKS);
-    const uint32_t cur = loud_hist_cur_;
-    loud_hist_cur_ ^= 1u;
-    launch_tap_set(loudness_, LoudRun{(const TapDesc*)loudness_.desc.p, n, n_calls, n, loud_par_.momentary_ticks, loud_par_.short_ticks,
-                                      (const LoudCoef*)loud_tab_.p, (const float*)((const LoudCoef*)loud_tab_.p + n), state, (double*)loud_walk_.p, loud_max_ticks_,
-                                      eh + (size_t)cur * n * LOUD_HIST_TICKS, eh + (size_t)(cur ^ 1u) * n * LOUD_HIST_TICKS,
-                                      xh + (size_t)cur * n * 2 * LOUD_HIST_FRAMES, xh + (size_t)(cur ^ 1u) * n * 2 * LOUD_HIST_FRAMES, (LoudTick*)loudness_.rec.p}, prof);
-}
-
-void Graph::read_loudness(uint32_t first, uint32_t n, LoudTick* dst, size_t cap) {
-    read_taps(loudness_, first, n, dst, cap, loudness_.ports.size(), sizeof(LoudTick), "n_ticks x taps");
-}
-
-// ---- stereo field taps ----
-
-void Graph::set_stereo(const mx_port_ref* ports, size_t n, const mx_stereo_params* params) {
-    hip_check(hipSetDevice(device_), "hipSetDevice");
-    check_tap_args(stereo_, ports, params, n);
-    if (n) {
-        if (params->window_ticks < 1 || params->window_ticks > 1024) throw Error(MX_ERR_INVALID, "mx_stereo_params: window_ticks must be 1 .. 1024");
-        if (params->grid != 0 && params->grid != 64 && params->grid != 128) throw Error(MX_ERR_INVALID, "mx_stereo_params: grid must be 0, 64 or 128");
-        if (params->zoom_log2 > 8) throw Error(MX_ERR_INVALID, "mx_stereo_params: zoom_log2 must be 0 .. 8");
-        if (params->grid && params->hop == 0) throw Error(MX_ERR_INVALID, "mx_stereo_params: hop must be >= 1 with a goniometer");
-    }
-    check_tap_ports(stereo_, ports, n);
-    if (n && params->grid) stereo_gon_room(tap_fpc_, n, params->grid, params->hop);   // (throws before anything changed)
-    // like set_loudness: the last run's launches are done with the records and the carried state; the second-stream mode stays on
-    sync();
-    stereo_.ports.assign(ports, ports + n);
-    stereo_.run_ticks = 0; stereo_hist_cur_ = 0;
-    stereo_c_ = 0; stereo_gon_n_ = 0; stereo_run_seen_ = false;
-    stereo_.rec.free_(); stereo_gon_rec_.free_(); stereo_carry_.free_(); stereo_gon_carry_.free_();
-    if (stereo_.empty()) { stereo_.desc.free_(); stereo_par_ = mx_stereo_params{0, 0, 0, 0}; return; }
-    stereo_par_ = *params;
-    if (!stereo_par_.grid) stereo_par_.hop = 1;   // (ignored without a goniometer)
-    // window history and carried grids start as zero: the stream before this call reads as +0.0, c = 0
-    const size_t hist_bytes = 2 * n * (size_t)STEREO_HIST_TICKS * 3 * sizeof(double);
-    stereo_carry_.alloc(hist_bytes);
-    hip_check(hipMemsetAsync(stereo_carry_.p, 0, hist_bytes, stream_), "hipMemsetAsync(stereo history)");
-    if (stereo_par_.grid) {
-        const size_t grid_bytes = n * stereo_gonio_record_bytes(stereo_par_.grid);
-        stereo_gon_carry_.alloc(grid_bytes);
-        hip_check(hipMemsetAsync(stereo_gon_carry_.p, 0, grid_bytes, stream_), "hipMemsetAsync(goniometer grids)");
-    }
-    hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
-    upload_stereo(tap_fpc_);
-}
-
-// the most goniometer records one run can emit at this call length (a run of T ticks that starts anywhere in a hop emits at most
-// ceil(T / hop)), refused beyond 4 GiB
-size_t Graph::stereo_gon_room(size_t fpc, size_t n, uint32_t grid, uint32_t hop) const {
-    const size_t max_ticks = std::max<size_t>(1, cap_frames_ / fpc), cap = (max_ticks + hop - 1) / hop;
-    if ((unsigned __int128)cap * n * stereo_gonio_record_bytes(grid) > ((unsigned __int128)4 << 30))
-        throw Error(MX_ERR_NOMEM, "stereo: the goniometer records of one run (ceil(max_ticks_per_run / hop) x taps x record bytes) exceed 4 GiB: raise hop");
-    return cap;
-}
-
-// beside the descriptors: room for the goniometer records a run can emit (refused before anything is touched)
-void Graph::upload_stereo(size_t fpc) {
-    const size_t n = stereo_.ports.size();
-    const size_t need_gon = stereo_par_.grid ? stereo_gon_room(fpc, n, stereo_par_.grid, stereo_par_.hop) * n * stereo_gonio_record_bytes(stereo_par_.grid) : 0;
-    const std::vector<TapDesc> d = tap_descs(stereo_, fpc);
-    upload_tap_descs(stereo_, d.data(), d.size() * sizeof(TapDesc), fpc, n * sizeof(StereoTick));
-    if (need_gon && (!stereo_gon_rec_.p || stereo_gon_rec_.bytes < need_gon)) stereo_gon_rec_.alloc(need_gon);
-}
-
-// Each run reads the window history the previous one wrote (stereo_hist_cur_ flips once per run).  A tap's carried grid and its goniometer
-// records are touched by that tap's group alone -- which is why k_stereo_emit and not a memset on stream_ clears the records.  The counter
-// c lives on the host: the run's phase and emissions are launch arguments.
-void Graph::launch_stereo_taps(uint32_t n_calls, ProfSpan* prof) {
-    if (stereo_.empty()) return;
-    const uint32_t n = stereo_.size();
-    double* hist = (double*)stereo_carry_.p;
-    const size_t hist_words = (size_t)n * STEREO_HIST_TICKS * 3;
-    const uint32_t cur = stereo_hist_cur_;
-    stereo_hist_cur_ ^= 1u;
-    const uint32_t grid = stereo_par_.grid, hop = stereo_par_.hop, phase = (uint32_t)(stereo_c_ % hop);
-    const uint32_t n_emit = grid ? (uint32_t)(((uint64_t)phase + n_calls) / hop) : 0u;
-    stereo_c_ += n_calls;
-    stereo_gon_n_ = n_emit; stereo_run_seen_ = true;
-    launch_tap_set(stereo_, StereoRun{(const TapDesc*)stereo_.desc.p, n, n_calls, n, stereo_par_.window_ticks,
-                                      hist + (size_t)cur * hist_words, hist + (size_t)(cur ^ 1u) * hist_words, (StereoTick*)stereo_.rec.p,
-                                      grid, stereo_par_.zoom_log2, hop, phase, n_emit, 8u + grid * grid, (uint32_t*)stereo_gon_rec_.p, (uint32_t*)stereo_gon_carry_.p}, prof);
-}
-
-void Graph::read_stereo(uint32_t first, uint32_t n, StereoTick* dst, size_t cap) {
-    read_taps(stereo_, first, n, dst, cap, stereo_.ports.size(), sizeof(StereoTick), "n_ticks x taps");
-}
-
-size_t Graph::read_goniometers(void* dst, size_t cap_bytes) {
-    hip_check(hipSetDevice(device_), "hipSetDevice");
-    if (stereo_.empty()) throw Error(MX_ERR_INVALID, "no stereo taps are set");
-    if (!stereo_par_.grid) throw Error(MX_ERR_INVALID, "the stereo taps were set without a goniometer (grid = 0)");
-    if (!stereo_run_seen_) throw Error(MX_ERR_INVALID, "no run since the stereo taps were set");
-    const size_t count = (size_t)stereo_gon_n_ * stereo_.ports.size(), bytes = count * stereo_gonio_record_bytes(stereo_par_.grid);
-    if (cap_bytes < bytes) throw Error(MX_ERR_INVALID, "cap_bytes is smaller than emissions x taps x record bytes");
-    if (bytes && !dst) throw Error(MX_ERR_INVALID, "dst is NULL");
-    if (bytes) {
-        wait_tail(-1);
-        hip_check(hipMemcpyAsync(dst, stereo_gon_rec_.p, bytes, hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(D2H)");
-        sync();
-    }
-    return count;
-}
-
-// ---- limiter taps (mixlab_gpu.h mx_graph_set_limiters) ----
-
-void Graph::set_limiters(const mx_port_ref* ports, size_t n, const mx_limiter_params* params) {
-    hip_check(hipSetDevice(device_), "hipSetDevice");
-    check_tap_args(limiters_, ports, params, n);
-    if (n) {
-        const float c = params->ceiling;
-        if (!(std::isfinite(c) && c >= 0x1p-20f && c <= 1.0f)) throw Error(MX_ERR_INVALID, "mx_limiter_params: ceiling must be finite, 2^-20 <= ceiling <= 1");
-        if (params->lookahead > LIMIT_MAX_LOOKAHEAD) throw Error(MX_ERR_INVALID, "mx_limiter_params: lookahead must be 0 .. 512");
-    }
-    check_tap_ports(limiters_, ports, n);
-    // like set_stereo: the last run's launches are done with the copies, the records and the history; the second-stream mode stays on
-    sync();
-    auto clear = [&] {
-        limiters_.ports.clear(); limiters_.run_ticks = 0; lim_hist_cur_ = 0;
-        limiters_.desc.free_(); limiters_.rec.free_(); lim_out_.free_(); lim_hist_.free_(); lim_w_.free_(); lim_stage_.free_();
-        lim_off_.clear(); lim_floats_.clear(); lim_tick_floats_ = 0; lim_max_frames_ = 0; lim_par_ = mx_limiter_params{0.0f, 0};
-    };
-    clear();
-    if (!n) return;
-    try {
-        limiters_.ports.assign(ports, ports + n);
-        lim_par_ = *params;
-        std::vector<float> w(lim_par_.lookahead + 1u);
-        (void)limiter_weights(lim_par_.lookahead, w.data());
-        lim_w_.alloc(w.size() * sizeof(float));
-        hip_check(hipMemcpy(lim_w_.p, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy(limiter weights)");
-        // every tap's history starts as +0.0: frames before this call read as silence
-        const size_t hist_bytes = 2 * n * (size_t)LIMIT_HIST_FRAMES * sizeof(float2);
-        lim_hist_.alloc(hist_bytes);
-        hip_check(hipMemsetAsync(lim_hist_.p, 0, hist_bytes, stream_), "hipMemsetAsync(limiter history)");
-        hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
-        upload_limiters(tap_fpc_);
-    } catch (...) { clear(); throw; }   // (out of device memory: no limiter taps rather than half a set)
-}
-
-// beside the descriptors: where each tap's copy starts inside a tick of copies, and room for a whole submission's copies
-void Graph::upload_limiters(size_t fpc) {
-    const size_t n = limiters_.ports.size();
-    const std::vector<TapDesc> t = tap_descs(limiters_, fpc);
-    lim_off_.assign(n, 0); lim_floats_.assign(n, 0);
-    size_t sum = 0; uint32_t max_frames = 0;
-    for (size_t i = 0; i < n; ++i) {   // set order
-        const Node& nd = nodes_[limiters_.ports[i].node];
-        const size_t frames = fpc * nd.dom_num / nd.dom_den;
-        if (frames > LIMIT_MAX_FRAMES) throw Error(MX_ERR_INVALID, "limiter: a tick of more than 2^30 frames");
-        lim_off_[i] = sum; lim_floats_[i] = frames * (nd.out_type[limiters_.ports[i].port] == MX_MONO ? 1u : 2u);
-        sum += lim_floats_[i]; max_frames = std::max(max_frames, (uint32_t)frames);
-    }
-    const size_t max_ticks = std::max<size_t>(1, cap_frames_ / fpc);
-    if ((unsigned __int128)max_ticks * sum * sizeof(float) > ((unsigned __int128)1 << 46)) throw Error(MX_ERR_NOMEM, "limiter: the limited copies of one run (max_ticks_per_run x the taps' frames x channels) exceed the device");
-    std::vector<LimitDesc> d(t.size());
-    for (size_t k = 0; k < t.size(); ++k)
-        d[k] = LimitDesc{t[k].p, t[k].frames, t[k].layout, t[k].slot, t[k].layout == METER_MONO ? 1u : 2u, (uint64_t)lim_off_[t[k].slot]};
-    const size_t need = max_ticks * sum * sizeof(float);
-    if (!lim_out_.p || lim_out_.bytes < need) lim_out_.alloc(need);
-    upload_tap_descs(limiters_, d.data(), d.size() * sizeof(LimitDesc), fpc, n * sizeof(LimitTick));
-    lim_tick_floats_ = sum; lim_max_frames_ = max_frames;
-}
-
-// Each run reads the frame history the previous one wrote (lim_hist_cur_ flips once per run).  A tap's copy, records and history are touched
-// by that tap's workgroups alone.
-void Graph::launch_limiter_taps(uint32_t n_calls, ProfSpan* prof) {
-    if (limiters_.empty()) return;
-    const uint32_t n = limiters_.size();
-    float2* hist = (float2*)lim_hist_.p;
-    const size_t hist_items = (size_t)n * LIMIT_HIST_FRAMES;
-    const uint32_t cur = lim_hist_cur_;
-    lim_hist_cur_ ^= 1u;
-    launch_tap_set(limiters_, LimitRun{(const LimitDesc*)limiters_.desc.p, n, n_calls, n, lim_par_.ceiling, lim_par_.lookahead, (const float*)lim_w_.p,
-                                       hist + (size_t)cur * hist_items, hist + (size_t)(cur ^ 1u) * hist_items, (float*)lim_out_.p, lim_tick_floats_,
-                                       (LimitTick*)limiters_.rec.p, lim_max_frames_}, prof);
-}
-
-void Graph::read_limiters(uint32_t first, uint32_t n, LimitTick* dst, size_t cap) {
-    read_taps(limiters_, first, n, dst, cap, limiters_.ports.size(), sizeof(LimitTick), "n_ticks x taps");
-}
-
-void Graph::read_limited(size_t tap, uint32_t first, uint32_t n, float* dst, int16_t* dst_i16, size_t cap, size_t* n_samples) {
-    hip_check(hipSetDevice(device_), "hipSetDevice");
-    if (limiters_.empty()) throw Error(MX_ERR_INVALID, "no limiter taps are set");
-    if (tap >= limiters_.ports.size()) throw Error(MX_ERR_INVALID, "limiter: tap out of range");
-    if ((uint64_t)first + n > limiters_.run_ticks) throw Error(MX_ERR_INVALID, "the window lies beyond the last run (or no run since the limiter taps were set)");
-    const size_t width = lim_floats_[tap], count = (size_t)n * width;
-    if (n_samples) *n_samples = count;
-    if (!dst && !dst_i16 && cap == 0) return;   // the count alone
-    if (cap < count) throw Error(MX_ERR_INVALID, "cap is smaller than n_ticks x frames x channels");
-    if (count && !dst && !dst_i16) throw Error(MX_ERR_INVALID, "samples is NULL");
-    if (!count) return;
-    wait_tail(-1);
-    const size_t need = count * (sizeof(float) + sizeof(int16_t));   // f32 staging, then the i16 form
-    if (lim_stage_.bytes < need) { sync(); lim_stage_.alloc(need); }
-    float* stage = (float*)lim_stage_.p;
-    launch_limit_gather((const float*)lim_out_.p + (size_t)first * lim_tick_floats_ + lim_off_[tap], lim_tick_floats_, (uint32_t)width, n, stage, stream_);
-    if (dst_i16) {
-        launch_f32_to_i16(stage, (int16_t*)(stage + count), count, 0, stream_);
-        hip_check(hipMemcpyAsync(dst_i16, stage + count, count * sizeof(int16_t), hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(D2H i16)");
-    } else
-        hip_check(hipMemcpyAsync(dst, stage, count * sizeof(float), hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(D2H)");
-    sync();
-}
-
-float* Graph::limited_ptr(size_t tap, size_t* floats_per_tick) {
-    hip_check(hipSetDevice(device_), "hipSetDevice");
-    if (limiters_.empty()) throw Error(MX_ERR_INVALID, "no limiter taps are set");
-    if (tap >= limiters_.ports.size()) throw Error(MX_ERR_INVALID, "limiter: tap out of range");
-    if (floats_per_tick) *floats_per_tick = lim_tick_floats_;
-    wait_tail(-1);   // stream_ is ordered behind a held-back tail's limiter launches too
-    return (float*)lim_out_.p + lim_off_[tap];
 }
 
 // ---- video scope taps (mixlab_gpu.h mx_graph_set_video_scopes) ----

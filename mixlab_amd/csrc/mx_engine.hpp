@@ -15,11 +15,11 @@
 #include <memory>
 #include <string>
 #include <deque>
-#include <variant>
 #include <vector>
 
 #include "mx_common.hpp"
 #include "mx_kernels.hpp"
+#include "mx_taps.hpp"
 #include "mx_video.hpp"
 
 namespace mx {
@@ -121,23 +121,23 @@ struct Group {
     int eq_mode = -1;   // EqThree: the one epilogue every instance has (eq_epilogue_mode), or -1 when they differ
 };
 
-class Graph {
+class Graph final : public TapHost {
 public:
     Graph(const mx_node* nodes, size_t n_nodes, const mx_edge* edges, size_t n_edges, const mx_graph_opts& opts,
           size_t cap_frames_override = 0);
     ~Graph();
 
     size_t spt() const { return spt_; }
-    double sample_rate() const { return sample_rate_; }
-    size_t cap_frames() const { return cap_frames_; }
+    double sample_rate() const override { return sample_rate_; }
+    size_t cap_frames() const override { return cap_frames_; }
     const std::vector<uint32_t>& run_order() const { return order_; }
-    hipStream_t stream() const { return stream_; }
-    int device() const { return device_; }
+    hipStream_t stream() const override { return stream_; }
+    int device() const override { return device_; }
     uint32_t ticks_per_second() const { return tps_; }
     hipStream_t tail_stream() { if (tail_gi_ >= 0) flush_deferred_tail(false); return tail_gi_ >= 0 ? tail_stream_ : nullptr; }   // MX_FLAG_OVERLAP_TAIL; asking for it releases a held tail launch: what the caller orders after the stream then includes the last run's
     // debug: the chunk records of the first EqThree group's last speculative launch (device pointer, bytes; nullptr when there is none)
     void* debug_eq_records(size_t* bytes) const;
-    void join_tail() { if (tail_gi_ >= 0) wait_tail(-1); }   // the graph's stream waits for a Mixer bank still running on the tail stream (consumers that read the buses on stream())
+    void join_tail() override { if (tail_gi_ >= 0) wait_tail(-1); }   // the graph's stream waits for a Mixer bank still running on the tail stream (consumers that read the buses on stream())
     size_t n_nodes() const { return nodes_.size(); }
     bool eq_exact() const { return (flags_ & MX_FLAG_EQ_EXACT) || !(flags_ & MX_FLAG_EQ_FAST); }   // the default is the reference's order
     bool fp_contract() const { return (flags_ & MX_FLAG_FP_CONTRACT) != 0; }                       // the contracted order (mixlab_gpu.h)
@@ -154,7 +154,7 @@ public:
     void bind_source(uint32_t node, const void* dev);
     // n_calls ModuleT::run_tick calls of frames_per_call mono samples each, back to back
     void run(uint64_t t0, size_t frames_per_call, uint32_t n_calls, float* ms_by_kind = nullptr, float* ms_total = nullptr);
-    void sync();
+    void sync() override;
     // accumulate per-group hipEvent timings across runs without synchronising (bench: kernel time over the timed region)
     void profile_enable(bool on);
     uint32_t profile_collect(float* ms_by_kind, float* ms_total);   // syncs; returns number of runs collected
@@ -162,25 +162,10 @@ public:
     // OUTPUT_DEVICE: ticks [first, first + n) of the last run (mx_graph_read_audio_out); samples / ticks may be null
     void read_audio_out(uint32_t node, uint32_t first, uint32_t n, float* samples, size_t samples_cap, OutTick* ticks, size_t* n_samples);
     void audio_out_lag(uint32_t node);
-    // level meters (mx_graph_set_meters / mx_graph_read_meters): taps on output ports, measured once per run after its last span
-    void set_meters(const mx_port_ref* ports, size_t n, const mx_meter_params* params);
-    void read_meters(uint32_t first, uint32_t n, MeterTick* dst, size_t cap);
-    // spectrum taps (mx_graph_set_spectra / mx_graph_read_spectra): a windowed transform of every tap's last n_fft frames per tick, as band powers
-    void set_spectra(const mx_port_ref* ports, size_t n, const mx_spectrum_params* params);
-    void read_spectra(uint32_t first, uint32_t n, float* dst, size_t cap);
-    // loudness taps (mx_graph_set_loudness / mx_graph_read_loudness): K-weighted energy, momentary / short-term window sums and true peak per tick
-    void set_loudness(const mx_port_ref* ports, size_t n, const mx_loudness_params* params);
-    void read_loudness(uint32_t first, uint32_t n, LoudTick* dst, size_t cap);
-    // stereo field taps (mx_graph_set_stereo / mx_graph_read_stereo / mx_graph_read_goniometers): the sums behind correlation, balance and width per tick, and the goniometer
-    void set_stereo(const mx_port_ref* ports, size_t n, const mx_stereo_params* params);
-    void read_stereo(uint32_t first, uint32_t n, StereoTick* dst, size_t cap);
-    size_t read_goniometers(void* dst, size_t cap_bytes);   // the last run's emitted records; returns how many
-    // limiter taps (mx_graph_set_limiters / mx_graph_read_limiters / mx_graph_read_limited): a look-ahead peak limiter's copy of every tapped port, and one record per tick
-    void set_limiters(const mx_port_ref* ports, size_t n, const mx_limiter_params* params);
-    void read_limiters(uint32_t first, uint32_t n, LimitTick* dst, size_t cap);
-    // ticks [first, first + n) of tap `tap`'s limited copy as f32 (dst_i16 null) or in the sinks' i16 format; both null with cap 0: the count only
-    void read_limited(size_t tap, uint32_t first, uint32_t n, float* dst, int16_t* dst_i16, size_t cap, size_t* n_samples);
-    float* limited_ptr(size_t tap, size_t* floats_per_tick);   // the tap's copy of tick 0 on the device; ticks are floats_per_tick apart
+    // the audio tap sets (mx_taps.hpp): taps on audio output ports, measured once per run after its last span
+    MeterTaps& meters() { return meters_; } SpectrumTaps& spectra() { return spectra_; } LoudnessTaps& loudness() { return loudness_; }
+    StereoTaps& stereo() { return stereos_; } LimiterTaps& limiters() { return limiters_; }
+    bool tap_port(mx_port_ref r, TapPort& t) const override; size_t tap_fpc() const override { return tap_fpc_; }   // (TapHost: with the accessors marked override, all a set sees of the graph)
     // video scope taps (mx_graph_set_video_scopes / mx_graph_read_video_scopes): histograms, waveform and vectorscope of the frames on video ports
     void set_video_scopes(const mx_port_ref* ports, size_t n, const mx_video_scope_params* params);
     size_t read_video_scopes(void* dst, size_t cap_bytes);   // the last run's records; returns how many
@@ -247,28 +232,8 @@ private:
     size_t od_offset(const Node& n, uint32_t tick) const;                // float offset of tick `tick` of the last run in the hand-off
     struct ProfSpan;
     void launch_outputs(uint64_t t0, uint32_t call_off, uint32_t n_calls, ProfSpan* prof);   // the span's OutputDevice launches
-    // the audio tap sets (meters, spectrum, loudness, stereo field, limiters): what the five share is written once, for "a tap set"
-    struct AudioTapSet;
-    void check_tap_args(const AudioTapSet& s, const void* ports, const void* params, size_t n) const;
-    void check_tap_ports(const AudioTapSet& s, const mx_port_ref* ports, size_t n, const std::function<void(size_t, const Node&)>& own_check = nullptr) const;
-    std::vector<TapDesc> tap_descs(AudioTapSet& s, size_t fpc) const;     // launch order and n_head; TapDesc[2][n] in launch order, one row per buffer parity
-    void upload_tap_descs(AudioTapSet& s, const void* d, size_t bytes, size_t fpc, size_t tick_bytes);   // ... to the device, and room for a whole submission's records
-    template <class Run> void launch_tap_set(const AudioTapSet& s, Run all, ProfSpan* prof);   // the run's launches of one set: on stream_, or held back with the tail
-    void read_taps(const AudioTapSet& s, uint32_t first, uint32_t n, void* dst, size_t cap, size_t tick_items, size_t item_bytes, const char* cap_what);
+    void launch_tap_set(AudioTapSet& s, uint32_t n_calls, ProfSpan* prof);   // the run's launches of one audio tap set: on stream_, or held back with the tail
     void reupload_taps(size_t fpc);                                      // every set's descriptors, tables and room again (the ports moved, or the call length did), on a quiescent stream
-    std::array<AudioTapSet*, 5> tap_sets() { return {&meters_, &spectra_, &loudness_, &stereo_, &limiters_}; }   // in launch order
-    // each set's own part: what it uploads beside the descriptors, and the run struct of its launches (after the run's last span)
-    void upload_meters(size_t fpc);
-    void upload_spectra(size_t fpc);
-    void upload_loudness(size_t fpc);
-    void upload_stereo(size_t fpc);
-    void upload_limiters(size_t fpc);
-    void launch_meter_taps(uint32_t n_calls, ProfSpan* prof);
-    void launch_spectrum_taps(uint32_t n_calls, ProfSpan* prof);
-    void launch_loudness_taps(uint32_t n_calls, ProfSpan* prof);
-    void launch_stereo_taps(uint32_t n_calls, ProfSpan* prof);
-    void launch_limiter_taps(uint32_t n_calls, ProfSpan* prof);
-    size_t stereo_gon_room(size_t fpc, size_t n, uint32_t grid, uint32_t hop) const;   // goniometer records a run can emit; MX_ERR_NOMEM beyond 4 GiB
     void refresh_gates(Group& g, uint32_t run_calls);
     uint32_t trigger_of_row(const Group& g, uint32_t row) const;        // node id of the Trigger behind row `row` of a gated group, or ~0u
     void stage_upload(void* dst, const void* src, size_t bytes);         // H2D on the graph's stream through page-locked staging
@@ -308,7 +273,7 @@ private:
     // taps: the audio tap sets' launches on the tail's outputs, behind those, in the sets' order.  prof: the span's profile record (nullptr: not profiled), whose tail events the release records.
     struct TailLaunch { const void* desc = nullptr; uint32_t n = 0, max_ch = 0; size_t frames = 0; int dup_mode = 0; hipEvent_t prof_ev = nullptr; };
     struct DeferredTail { bool pending = false; std::vector<TailLaunch> items; uint32_t parity = 0; ProfSpan* prof = nullptr;
-                          std::vector<OutRun> outs; std::vector<std::variant<MeterRun, SpecRun, LoudRun, StereoRun, LimitRun>> taps; } deferred_;
+                          std::vector<OutRun> outs; std::vector<AudioTapSet*> taps; } deferred_;
     std::function<void(hipStream_t)> tail_hook_;
     std::vector<hipEvent_t> head_waits_;
     uint64_t n_gated_ = 0, n_at_once_ = 0;
@@ -329,55 +294,9 @@ private:
     std::vector<uint32_t> plotter_nodes_;   // launched Plotter nodes
     std::vector<uint32_t> video_order_;     // the video nodes of order_, in run order
     std::vector<uint32_t> od_nodes_;        // OutputDevice nodes of order_ (never in a launch group: launched after the span's groups, behind their input's producer)
-    // One audio tap set: the taps in set order (= record slots).  Launch order puts the taps read on stream_ first (n_head of them), then
-    // the taps on outputs of the tail (behind the Mixer bank on its stream while the second-stream mode is on).  desc: the descriptors
-    // [2][n] in launch order, one row per buffer parity; rec: the records [max ticks][n].  tag, noun, no_type: how the messages name the set
-    struct AudioTapSet {
-        const char* tag; const char* noun; const char* no_type;
-        bool stereo_only = false;               // the ports must be stereo (else: anything but video)
-        std::vector<mx_port_ref> ports;
-        uint32_t n_head = 0;
-        uint32_t run_ticks = 0;                 // ticks of the last run that measured the current taps (0: none since they were set)
-        DevBuf desc, rec;
-        bool empty() const { return ports.empty(); }
-        uint32_t size() const { return (uint32_t)ports.size(); }
-    };
     size_t tap_fpc_ = 0;                        // frames per call every set's descriptors were built for (the tick length until a run says otherwise)
-    // level meters.  desc: MeterDesc; rec: MeterTick; meter_par_: each tap's hold_ticks and release; meter_state_: MeterHold[n][2]
-    AudioTapSet meters_{"meter", "meters", "a video port has no level"};
-    std::vector<mx_meter_params> meter_par_;
-    DevBuf meter_state_;
-    // spectrum taps.  rec: float[2][bands] per tap; spec_hist_: float[2][n][2 * n_fft], the buffer a run reads is spec_hist_cur_, it writes
-    // the other; spec_tab_: window, twiddles and band edges on the device
-    AudioTapSet spectra_{"spectrum", "spectrum taps", "a video port has no spectrum"};
-    uint32_t spec_n_fft_ = 0, spec_n_bands_ = 0, spec_hist_cur_ = 0;
-    DevBuf spec_hist_, spec_tab_;
-    // loudness taps.  rec: LoudTick; loud_walk_: double[n][2][max ticks][4], the run's Z_k / S_k; loud_tab_: LoudCoef[n] by slot, then
-    // interp[36]; loud_carry_: what a run hands to the next -- state double[n][2][4] | window history double[2][n][1023] | frame history
-    // float[2][n][2][11], of which a run reads buffer loud_hist_cur_ and writes the other
-    AudioTapSet loudness_{"loudness", "loudness taps", "a video port has no loudness"};
-    mx_loudness_params loud_par_{0, 0};
-    uint32_t loud_hist_cur_ = 0, loud_max_ticks_ = 0;
-    DevBuf loud_walk_, loud_tab_, loud_carry_;
-    // stereo field taps.  rec: StereoTick; stereo_carry_: window history double[2][n][1023][3], of which a run reads buffer stereo_hist_cur_
-    // and writes the other; stereo_gon_rec_: the last run's goniometer records [emission][n], stereo_gon_n_ emissions; stereo_gon_carry_: one
-    // record-shaped grid per tap with the ticks since the last emission.  stereo_c_ is the hop counter c (0 when the taps are set, + the
-    // ticks of every run)
-    AudioTapSet stereo_{"stereo", "stereo taps", "a video or mono port has no stereo field", true};
-    mx_stereo_params stereo_par_{0, 0, 0, 0};
-    uint32_t stereo_hist_cur_ = 0, stereo_gon_n_ = 0;
-    uint64_t stereo_c_ = 0;
-    bool stereo_run_seen_ = false;
-    DevBuf stereo_carry_, stereo_gon_rec_, stereo_gon_carry_;
-    // limiter taps.  rec: LimitTick; lim_out_: the limited copies float[max ticks][lim_tick_floats_], a tick being every tap's frames x
-    // channels floats in set order (tap i's start at lim_off_[i], lim_floats_[i] of them); lim_hist_: float2[2][n][LIMIT_HIST_FRAMES], of which
-    // a run reads buffer lim_hist_cur_ and writes the other; lim_w_: the smoothing weights; lim_stage_: the read-backs' staging
-    AudioTapSet limiters_{"limiter", "limiter taps", "a video port has no level to limit"};
-    mx_limiter_params lim_par_{0.0f, 0};
-    uint32_t lim_hist_cur_ = 0, lim_max_frames_ = 0;
-    size_t lim_tick_floats_ = 0;
-    std::vector<size_t> lim_off_, lim_floats_;
-    DevBuf lim_out_, lim_hist_, lim_w_, lim_stage_;
+    MeterTaps meters_{*this}; SpectrumTaps spectra_{*this}; LoudnessTaps loudness_{*this}; StereoTaps stereos_{*this}; LimiterTaps limiters_{*this};
+    const std::array<AudioTapSet*, 5> taps_{&meters_, &spectra_, &loudness_, &stereos_, &limiters_};   // in launch order
     // video scope taps: the taps in set order; scope_rec_: the last run's records [recorded tick][tap], scope_cap_ ticks of room.  scope_c_ is the
     // hop counter (0 when the taps are set, +1 per video tick, carried across runs); a tick is recorded when scope_c_ % hop == 0 before the increment
     std::vector<mx_port_ref> scopes_;

@@ -156,9 +156,9 @@ struct OutRun {
 };
 uint32_t out_route_blocks(size_t frames_per_tick, uint32_t channels);
 void launch_output_device(const OutRun& r, hipStream_t s);
-// The audio tap sets (meters, spectrum, loudness, stereo field) read their ports through one descriptor per tap and buffer parity.  Their
-// run structs begin alike -- desc, n, n_ticks, stride -- and launch_taps is overloaded on them, so the engine splits and defers any of them
-// the same way (Graph::launch_tap_set)
+// The audio tap sets (meters, spectrum, loudness, stereo field, limiter) read their ports through one descriptor per tap and buffer parity.
+// Their run structs begin alike -- desc, n, n_ticks, stride -- and launch_taps is overloaded on them, so the engine splits and defers any of
+// them the same way (TapSetOf::launch in mx_taps.hpp, Graph::launch_tap_set)
 enum : uint32_t { METER_MONO = 0, METER_STEREO = 1, METER_DUP = 2 };   // METER_DUP: stereo stored as one float per frame (L == R)
 struct TapDesc { const float* p; uint32_t frames, layout, slot, _pad; };   // p: the port at tick 0 of the run; layout: METER_*; slot: index in set order
 // Level meters (mx_k_meter.hip, mixlab_gpu.h mx_graph_set_meters): the descriptor (TapDesc's first four fields, then the tap's own

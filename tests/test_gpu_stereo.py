@@ -281,11 +281,12 @@ def test_all_five_tap_sets_together_from_the_2p40_epoch():
     check_all_five_tap_sets_together(far_first_tick("at_2p40", 735, 12))
 
 
-def test_four_audio_tap_sets_through_the_end_of_the_automatic_tail_mode():
-    """The automatic second-stream mode ends (a stream-ordered consumer takes the Master's raw pointer) while meters, spectrum, loudness and
-    stereo taps are set: every set's descriptors are rebuilt for one stream and one buffer per port, and what the taps carry -- a hold
-    longer than a run, the spectrum history, the loudness and stereo windows, the goniometer grid and its counter -- comes through.  The
-    twin desk without taps, driven identically, gives every port."""
+def test_every_audio_tap_set_through_the_end_of_the_automatic_tail_mode():
+    """The automatic second-stream mode ends (a stream-ordered consumer takes the Master's raw pointer) while meters, spectrum, loudness,
+    stereo and limiter taps are set: every set's descriptors are rebuilt for one stream and one buffer per port, and what the taps carry --
+    a hold longer than a run, the spectrum history, the loudness and stereo windows, the goniometer grid and its counter, the limiter's
+    look-ahead history and where each limited copy lies -- comes through.  The twin desk without taps, driven identically, gives every port."""
+    import test_gpu_limiter as tlim
     import test_gpu_loudness as tl
     import test_gpu_meters as tm
     import test_gpu_spectrum as ts
@@ -296,9 +297,9 @@ def test_four_audio_tap_sets_through_the_end_of_the_automatic_tail_mode():
     g = ws.build(max_ticks_per_run=n)
     where = [(mix, 0), (mix, 1), (mix + 6, 0), (mix + 6 * 64, 0)]   # Master, Cue, the Amplifiers of strips 0 and 63
     sets = [(tm, [tm.Tap(nd, p, 2, hold_ticks=40) for nd, p in where]), (ts, [ts.Tap(nd, p, 2, n_fft, edges) for nd, p in where]),
-            (tl, [tl.Tap(nd, p, 2, sr, spt) for nd, p in where])]
+            (tl, [tl.Tap(nd, p, 2, sr, spt) for nd, p in where]), (tlim, [tlim.Tap(nd, p, 2) for nd, p in where])]
     stereo = [Tap(nd, p) for nd, p in where]
-    tm.set_taps(g, sets[0][1]); ts.set_taps(g, sets[1][1], n_fft, edges); tl.set_taps(g, sets[2][1])
+    tm.set_taps(g, sets[0][1]); ts.set_taps(g, sets[1][1], n_fft, edges); tl.set_taps(g, sets[2][1]); tlim.set_taps(g, sets[3][1], 0.5, 64)
     set_taps(g, stereo, 24, 64, 0, 24)   # hop 24 against runs of 16: the grid of ticks 48 .. 63 is carried through the mode's end
     noise = [synth.noise(k, 6 * n * spt) * np.float32(8.0) for k in range(n_strips)]
     n_emitted = 0
