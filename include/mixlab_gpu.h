@@ -113,6 +113,9 @@ typedef struct { uint32_t channels; int32_t left, right; uint32_t _pad; } mx_out
 /* Build-specified audio extras (DESIGN.md "FIR and resampler").  Both are variable-length blobs: the header below
  * followed by the f64 coefficients.  Arithmetic: f32 widened to f64, accumulated in f64 in ascending tap index with
  * separate multiply and add, rounded once to f32 -- the reference's own convention (mixer.rs:62, amplifier.rs:56). */
+/* mx_fir_params: 1 <= n_taps <= 16384.  A launch group (the Fir nodes of one dependency level) whose longest filter keeps the tiled kernel's LDS plan within
+ * 64 KiB -- up to 1605 taps -- runs tiled (k_fir<8> from 8192 frames per run on and up to 1024 taps, else k_fir<4>); a group with a longer filter takes the plain
+ * kernel for all its members (one output per lane, taps and frames from memory).  Same sums, same bits. */
 typedef struct { uint32_t n_taps; uint32_t _pad; /* double taps[n_taps] */ } mx_fir_params;               /* y[n] = sum_k taps[k] x[n-k] per channel */
 typedef struct { uint32_t up, down, taps_per_phase, _pad; /* double taps[up][taps_per_phase] */ } mx_resample_params;
 /*   output sample M (absolute): n = floor(M * down / up), phase = (M * down) mod up, y[M] = sum_k taps[phase][k] x[n-k].

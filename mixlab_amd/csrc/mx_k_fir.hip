@@ -108,6 +108,45 @@ __global__ __launch_bounds__(256) void k_fir_history(const FirDesc* __restrict__
     __syncthreads();
     for (int j = threadIdx.x; j < H; j += 256) d.hist[j] = tmp[j];
 }
+// The plain form for impulse responses whose tiled plan does not fit the LDS a launch may ask for (launch_fir): one output per lane, taps and frames read
+// from memory, the same ascending separate multiply and add (FC: fma).  Every lane of a wave reads the same tap and consecutive frames.
+template <bool FC>
+__global__ __launch_bounds__(256) void k_fir_plain(const FirDesc* __restrict__ descs, size_t frames) {
+    const FirDesc d = descs[blockIdx.y];
+    const int K = (int)d.n_taps, H = K - 1;
+    const double* __restrict__ h = d.taps;
+    for (size_t n = (size_t)blockIdx.x * 256 + threadIdx.x; n < frames; n += (size_t)gridDim.x * 256) {
+        double al = 0.0, ar = 0.0;
+        for (int k = 0; k < K; ++k) {
+            const long long f = (long long)n - k;                    // <= n < frames
+            float2 v = make_float2(0.f, 0.f);
+            if (f >= 0) { if (d.in) v = reinterpret_cast<const float2*>(d.in)[f]; }
+            else { const long long hh = (long long)H + f; if (hh >= 0) v = d.hist[hh]; }   // hist[j] = x[j - (K-1)]
+            al = mul_add<FC>(h[k], (double)v.x, al);
+            ar = mul_add<FC>(h[k], (double)v.y, ar);
+        }
+        reinterpret_cast<float2*>(d.out)[n] = make_float2((float)al, (float)ar);
+    }
+}
+// k_fir_history without K-sized LDS: one block per filter walks the history in chunks of 256 frames in ascending order.  New frame j is old frame
+// j + frames (or an input frame): a chunk reads only frames at or above its own, which no earlier chunk has written, and the barrier keeps the
+// chunk's own reads ahead of its writes -- in place.
+__global__ __launch_bounds__(256) void k_fir_history_chunked(const FirDesc* __restrict__ descs, size_t frames) {
+    const FirDesc d = descs[blockIdx.x];
+    const int H = (int)d.n_taps - 1;
+    for (int c = 0; c < H; c += 256) {                                // block-uniform trip count
+        const int j = c + (int)threadIdx.x;
+        float2 v = make_float2(0.f, 0.f);
+        if (j < H) {
+            const long long f = (long long)frames - H + j;            // index into the input stream
+            if (f >= 0) { if (d.in) v = reinterpret_cast<const float2*>(d.in)[f]; }
+            else { const long long hh = (long long)H + f; if (hh >= 0) v = d.hist[hh]; }
+        }
+        __syncthreads();
+        if (j < H) d.hist[j] = v;
+        __syncthreads();
+    }
+}
 void launch_fir(const FirDesc* d, uint32_t n, uint32_t max_taps, size_t frames, hipStream_t s, bool fc) {
     if (!n || !frames) return;
     // outputs per lane: 8 where the streams are long enough to fill the chip with tiles of 2048 outputs (and the window fits LDS), else 4
@@ -116,6 +155,15 @@ void launch_fir(const FirDesc* d, uint32_t n, uint32_t max_taps, size_t frames, 
     const size_t tile = (size_t)FIR_BLOCK * per;
     const size_t wn = tile + max_taps + per;
     const size_t lds = (size_t)((max_taps + 1) & ~1u) * sizeof(double) + (wn + wn / per + 2) * sizeof(double2);
+    // The tiled plan grows by about 28 bytes per tap.  Past what a launch may ask for without a function attribute (taken as 64 KiB, the
+    // conservative figure: past 1605 taps, 1024 for k_fir<8>'s tile, which falls back to k_fir<4> first; which limit the runtime applies is not measured) the plain kernel runs instead.
+    if (lds > 64 * 1024) {
+        dim3 pgrid(grid_x(frames, 256, 1024), n);
+        if (fc) hipLaunchKernelGGL(k_fir_plain<true>, pgrid, dim3(256), 0, s, d, frames);
+        else hipLaunchKernelGGL(k_fir_plain<false>, pgrid, dim3(256), 0, s, d, frames);
+        hipLaunchKernelGGL(k_fir_history_chunked, dim3(n), dim3(256), 0, s, d, frames);
+        return;
+    }
     dim3 grid(grid_x(frames, (unsigned)tile, 1024), n);
 #define MX_FIR_GO(P, F) hipLaunchKernelGGL((k_fir<P, F>), grid, dim3(FIR_BLOCK), lds, s, d, frames)
     if (per == 8) { if (fc) MX_FIR_GO(8, true); else MX_FIR_GO(8, false); }

@@ -170,6 +170,9 @@ def test_config3_full_size_256_channels_fir_then_resampler_spot_checked_against_
         hist = np.zeros((len(taps) - 1) * 2, np.float32)
         want_f = oracle.fir_run(taps, hist, noise[k])
         assert np.array_equal(bits(g.read_output(outs[k][0], 0, T, True)), bits(want_f)), f"FIR channel {k}"
+        # ... and its resampler output against the oracle resampler fed the oracle's FIR output (k_resample_ps with blocks walking several groups)
+        want_r = oracle.resample_run(table, 160, 147, np.zeros((table.shape[1] - 1) * 2, np.float32), 0, 0, want_f, 800 * T)
+        assert np.array_equal(bits(g.read_output(outs[k][1], 0, T, True, rate=(160, 147))), bits(want_r)), f"resampler channel {k}"
     dev_r = [g.read_output(r, 0, T, True, rate=(160, 147)) for (_f, r) in outs]
     want_m, want_c = oracle.mixer_run([(0.0, 1.0, k % 2 == 0) for k in range(n_ch)], dev_r, 2 * T * 800)
     assert np.array_equal(bits(g.read_output(mix, 0, T, True, rate=(160, 147))), bits(want_m))
