@@ -35,7 +35,8 @@ extern "C" {
                               *    mx_stereo_params, mx_stereo_tick, mx_graph_set_stereo, mx_graph_read_stereo, mx_graph_read_goniometers, mx_stereo_gonio_record_bytes,
                               *    mx_stereo_correlation;
                               *    mx_limiter_params, mx_limiter_tick, mx_graph_set_limiters, mx_graph_read_limiters, mx_graph_read_limited, mx_graph_read_limited_i16,
-                              *    mx_graph_limited_device_ptr, mx_limiter_weights */
+                              *    mx_graph_limited_device_ptr, mx_limiter_weights;
+                              *    mx_tempo_params, mx_graph_set_tempo, mx_graph_read_tempo, mx_tempo_record_bytes, mx_tempo_bpm */
 
 /* ---- status codes (0 ok, <0 error; cf. MIXLAB_IOCTX_ERROR / MIXLAB_IOCTX_PANIC) ---- */
 enum {
@@ -571,6 +572,54 @@ int mx_graph_limited_device_ptr(mx_graph* g, size_t tap, void** dev, size_t* flo
 /* The smoothing weights of the spec for one lookahead: w[lookahead + 1].  Host only: touches no device and needs no graph.  A lookahead above
  * 512 or a NULL w: MX_ERR_INVALID. */
 int mx_limiter_weights(uint32_t lookahead, float* w);
+
+/* Tempo taps on audio output ports of a built graph: the autocorrelation of an onset function per port, from which a
+ * host reads the tempo (BPM) a DJ beat-matches by.  Like a meter, a tap observes a port: no module, no edge, the run order and the fusion plan
+ * unchanged; a graph without them launches nothing new.  The seven tap sets are independent and may be set together.  Every run computes the
+ * records on the device, once per run after its last span.  BUILD-SPECIFIED (the reference has no such instrument); everything below the
+ * mid signal is integer arithmetic, so the records are fixed count for count (tests/tempo_model.py restates them in numpy and Python
+ * integers), they are identical however ticks are grouped into runs, and the order of accumulation cannot matter.
+ *   parameters  hop_frames H: 64, 128 or 256; window_hops W: 64 .. 4096; max_lag L: 16 .. 1024 and L <= W; emit_ticks >= 1.  One set per graph.
+ *   stream    a tap treats its port as one stream of frames that starts when the taps are set (frame 0) and continues across ticks and
+ *             runs, in the port's own rate domain (first_tick may jump: the stream does not care).  A mono port, and a stereo port stored as
+ *             one float per frame (the fused L == R strip result), read as L = R = x: equal to MX_FLAG_NO_FUSE's records byte for byte.
+ *   mid       m = L + R in f32, rounded once.
+ *   quantise  a non-finite m (NaN, +-Inf, also from finite L and R) gives q = 0 and is counted in `nonfinite`; else
+ *             q = (uint32_t)(fminf(fabsf(m), 4.0f) * 1048576.0f): the product is exact, the conversion truncates, q <= 2^22.
+ *   energy    hop h is the stream's frames [h H, (h + 1) H): E[h] = the sum of q^2 as uint64_t, at most 2^52.
+ *   amplitude A[h] = floor(sqrt(E[h])), the exact integer root; A[-1] = 0.
+ *   onset     o[h] = max(A[h] - A[h - 1], 0) >> 6, at most 2^20; o of a negative hop is 0.
+ *   emission  one counter c per graph: c = 0 when the taps are set; every tick does c += 1, and when c mod emit_ticks == 0 every tap emits a
+ *             record.  hl is the last hop whose final frame lies in this tick or an earlier one (none: the whole table is zero).  For
+ *             l = 0 .. L - 1: R[l] = the sum over j = 0 .. W - 1 of o[hl - j] * o[hl - j - l] as uint64_t (at most 2^52: no overflow).  Every
+ *             record is summed afresh from the carried history of W + L - 1 onsets: there is no running sum.
+ *   record    32-byte header uint32_t { tick_in_run (the emitting tick), hops_complete (hl + 1, saturating), nonfinite (frames since the
+ *             previous emission), hop_frames, window_hops, max_lag, reserved[2] (0) }, then R[0 .. L) as uint64_t: 32 + 8 L bytes
+ *             (mx_tempo_record_bytes).
+ * Carried across runs per tap: the energy of the hop in progress, A of the last complete hop, the onset history and nonfinite; per graph: c.
+ * Every call to mx_graph_set_tempo resets every tap and c.  mx_graph_adopt_state carries no taps. */
+typedef struct { uint32_t hop_frames /* 64, 128 or 256 */, window_hops /* 64 .. 4096 */, max_lag /* 16 .. 1024, <= window_hops */, emit_ticks /* >= 1 */; } mx_tempo_params;
+/* Replaces the graph's tempo taps with ports[0..n) (n = 0: none; params may then be NULL and the graph launches nothing for them).  Video port:
+ * MX_ERR_TYPE.  A node or port out of range, a duplicate (node, port), a port the fusion did not materialise, a parameter outside its range:
+ * MX_ERR_INVALID.  The records of one run (ceil(max_ticks_per_run / emit_ticks) x n x record bytes) beyond 4 GiB: MX_ERR_NOMEM (raise
+ * emit_ticks).  Device memory that cannot be had: MX_ERR_NOMEM, and the graph is left without tempo taps.  Waits for outstanding work like a
+ * read-back but keeps the automatic second-stream mode on.  Device memory: the run's records, and per tap 2 x (W + L - 1 + the hops of the
+ * longest run) onsets of 4 bytes plus 8 bytes per hop of the longest run.  The launches count in the profile calls' ms_total only
+ * (MX_PROFILE_KINDS is unchanged). */
+int mx_graph_set_tempo(mx_graph* g, const mx_port_ref* ports, size_t n, const mx_tempo_params* params);
+/* The records the last run emitted, [emission][tap in set order], mx_tempo_record_bytes each; *n_records = emissions x taps (0 when the run
+ * emitted none; n_records may be NULL).  No taps, no run since the taps were set, or cap_bytes too small: MX_ERR_INVALID.  Joins the graph's
+ * streams like mx_graph_read_output. */
+int mx_graph_read_tempo(mx_graph* g, void* dst, size_t cap_bytes, uint32_t* n_records);
+/* Bytes of one tempo record: 32 + 8 max_lag.  Host only.  A parameter outside its range or a NULL argument: MX_ERR_INVALID. */
+int mx_tempo_record_bytes(const mx_tempo_params* params, size_t* bytes);
+/* Tempo of one record, in f64 on the host (needs no graph): the candidate lags are the integers in
+ * [60 rate / (H bpm_hi), 60 rate / (H bpm_lo)] intersected with [1, L - 2]; l* is the first maximum of R over them;
+ * d = 0.5 (R[l* - 1] - R[l* + 1]) / (R[l* - 1] - 2 R[l*] + R[l* + 1]) when that denominator is negative, else 0 (parabolic refinement);
+ * *bpm = 60 rate / (H (l* + d)), *confidence = R[l*] / R[0].  R[0] == 0 (silence, or nothing but non-finite frames) or no candidate lag:
+ * *bpm = 0, *confidence = 0.  rate: the port's own frames per second.  A NULL argument, a header whose parameters are outside their ranges, a
+ * rate or bound that is not finite and positive, or bpm_hi < bpm_lo: MX_ERR_INVALID. */
+int mx_tempo_bpm(const void* record, double rate, double bpm_lo, double bpm_hi, double* bpm, double* confidence);
 
 /* Plotter indication (src/module/plotter.rs:37-56) for tick `tick_in_run` of the last run:
  * *fired = 1 and SPT floats in each of left/right when it fired (every 6th call, input connected). */

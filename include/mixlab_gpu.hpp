@@ -140,6 +140,12 @@ public:
     size_t read_limited_i16(size_t tap, uint32_t first, uint32_t n, std::vector<int16_t>& dst) { size_t c = 0; check(mx_graph_read_limited_i16(g_, tap, first, n, dst.data(), dst.size(), &c)); return c; }
     // the copy on the device: tick t of the last run at (float*)ptr + t * floats_per_tick
     void* limited_device_ptr(size_t tap, size_t* floats_per_tick) { void* p = nullptr; check(mx_graph_limited_device_ptr(g_, tap, &p, floats_per_tick)); return p; }
+    // tempo taps (mx_graph_set_tempo): one parameter set for every tap; an empty list removes them
+    void set_tempo(const std::vector<mx_port_ref>& ports, const mx_tempo_params& p) {
+        check(mx_graph_set_tempo(g_, ports.data(), ports.size(), ports.empty() ? nullptr : &p));
+    }
+    // the tempo records the last run emitted, [emission][tap], mx_tempo_record_bytes each; returns how many (mx_tempo_bpm reads one)
+    uint32_t read_tempo(std::vector<unsigned char>& dst) { uint32_t n = 0; check(mx_graph_read_tempo(g_, dst.data(), dst.size(), &n)); return n; }
     // video scope taps (mx_graph_set_video_scopes): one parameter set for every tap; an empty list removes them
     void set_video_scopes(const std::vector<mx_port_ref>& ports, const mx_video_scope_params& p) {
         check(mx_graph_set_video_scopes(g_, ports.data(), ports.size(), ports.empty() ? nullptr : &p));

@@ -210,6 +210,15 @@ _proto("mx_graph_read_limited", C.c_int, C.c_void_p, C.c_size_t, C.c_uint32, C.c
 _proto("mx_graph_read_limited_i16", C.c_int, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t))
 _proto("mx_graph_limited_device_ptr", C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t))
 _proto("mx_limiter_weights", C.c_int, C.c_uint32, C.c_void_p)
+class TempoParams(C.Structure):
+    """mx_tempo_params: frames per hop (64, 128, 256), the window in hops (64 .. 4096), the lags (16 .. 1024, <= window) and the emission period."""
+    _fields_ = [("hop_frames", C.c_uint32), ("window_hops", C.c_uint32), ("max_lag", C.c_uint32), ("emit_ticks", C.c_uint32)]
+
+
+_proto("mx_graph_set_tempo", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
+_proto("mx_graph_read_tempo", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32))
+_proto("mx_tempo_record_bytes", C.c_int, C.POINTER(TempoParams), C.POINTER(C.c_size_t))
+_proto("mx_tempo_bpm", C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double))
 class VideoScopeParams(C.Structure):
     """mx_video_scope_params: waveform columns (0, 64, 128, 256), vectorscope on / off, record every hop-th video tick."""
     _fields_ = [("wave_cols", C.c_uint32), ("vectorscope", C.c_uint32), ("hop", C.c_uint32)]
@@ -330,6 +339,41 @@ def parse_goniometer_records(raw: np.ndarray, grid: int) -> list:
         d["gon"] = w[8:].reshape(grid, grid)
         out.append(d)
     return out
+
+
+def tempo_record_bytes(hop_frames: int = 128, window_hops: int = 2048, max_lag: int = 512, emit_ticks: int = 6) -> int:
+    """bytes of one tempo record: 32 + 8 * max_lag (mx_tempo_record_bytes, host only, no device)"""
+    n = C.c_size_t()
+    check(lib.mx_tempo_record_bytes(C.byref(TempoParams(int(hop_frames), int(window_hops), int(max_lag), int(emit_ticks))), C.byref(n)))
+    return n.value
+
+
+def parse_tempo_records(raw: np.ndarray, max_lag: int) -> list:
+    """raw bytes of back-to-back tempo records -> one dict per record: the header fields as ints, acf uint64[max_lag] (R[l]) and raw, the
+    record's own bytes (what tempo_bpm takes)"""
+    r = np.ascontiguousarray(raw).view(np.uint8).reshape(-1, 32 + 8 * max_lag)
+    out = []
+    for b in r:
+        w = b[:32].view(np.uint32)
+        d = dict(zip(("tick_in_run", "hops_complete", "nonfinite", "hop_frames", "window_hops", "max_lag"), (int(x) for x in w[:6])))
+        d["reserved"] = (int(w[6]), int(w[7]))
+        d["acf"] = b[32:].view(np.uint64)
+        d["raw"] = b.tobytes()
+        out.append(d)
+    return out
+
+
+def tempo_bpm(record, rate: float, bpm_lo: float, bpm_hi: float):
+    """(bpm, confidence) of one tempo record (its bytes, or a parse_tempo_records dict) for a port of `rate` frames per second, searched
+    between bpm_lo and bpm_hi: the first maximum of the autocorrelation over the lags of that range, refined by a parabola; confidence is
+    R[lag] / R[0]; silence reads (0.0, 0.0) (mx_tempo_bpm, host only)"""
+    raw = record["raw"] if isinstance(record, dict) else bytes(record)
+    buf = (C.c_char * len(raw)).from_buffer_copy(raw)
+    b, c = C.c_double(), C.c_double()
+    if len(raw) < 32 or len(raw) < 32 + 8 * int(np.frombuffer(raw, np.uint32, 8)[5]):   # before the library reads max_lag values from it
+        raise MxError(MX_ERR_INVALID, "a tempo record is 32 + 8 * max_lag bytes")
+    check(lib.mx_tempo_bpm(buf, float(rate), float(bpm_lo), float(bpm_hi), C.byref(b), C.byref(c)))
+    return b.value, c.value
 
 
 def video_scope_record_bytes(wave_cols: int = 0, vectorscope: bool = False) -> int:
@@ -645,6 +689,30 @@ class Graph:
         p, n = C.c_void_p(), C.c_size_t()
         check(lib.mx_graph_limited_device_ptr(self._h, tap, C.byref(p), C.byref(n)))
         return p.value, n.value
+
+    def set_tempo(self, ports, hop_frames: int = 128, window_hops: int = 2048, max_lag: int = 512, emit_ticks: int = 6):
+        """tempo taps on audio output ports [(node, port), ...]: every emit_ticks ticks one record per tap with the autocorrelation, over the
+        last window_hops hops of hop_frames frames, of the port's onset function at lags 0 .. max_lag - 1 (tempo_bpm reads the tempo from
+        it).  One parameter set for every tap.  Each call resets every tap and the emission counter; [] removes them all."""
+        ports = list(ports)
+        if not ports:
+            check(lib.mx_graph_set_tempo(self._h, None, 0, None))
+            self._tempo = (0, 16, 1)
+            return
+        pa = (PortRef * len(ports))(*[PortRef(int(n), int(p)) for (n, p) in ports])
+        check(lib.mx_graph_set_tempo(self._h, pa, len(ports), C.byref(TempoParams(int(hop_frames), int(window_hops), int(max_lag), int(emit_ticks)))))
+        self._tempo = (len(ports), int(max_lag), max(1, int(emit_ticks)))
+
+    def read_tempo(self) -> list:
+        """the tempo records the last run emitted: a list over its emissions of lists over the taps in set order of parse_tempo_records
+        dicts"""
+        n, max_lag, emit = getattr(self, "_tempo", (0, 16, 1))
+        rb = 32 + 8 * max_lag
+        raw = np.zeros(max(1, -(-self.max_ticks // emit)) * max(1, n) * rb, dtype=np.uint8)
+        got = C.c_uint32()
+        check(lib.mx_graph_read_tempo(self._h, raw.ctypes.data_as(C.c_void_p), raw.size, C.byref(got)))
+        recs = parse_tempo_records(raw[: got.value * rb], max_lag)
+        return [recs[i:i + n] for i in range(0, len(recs), n)] if n else []
 
     def set_video_scopes(self, ports, wave_cols: int = 0, vectorscope: bool = False, hop: int = 1):
         """video scope taps on video output ports [(node, port), ...]: on every hop-th video tick, the luma / U / V histograms, the

@@ -314,6 +314,46 @@ int mx_limiter_weights(uint32_t lookahead, float* w) {   // host only: no device
     return guard([&] { REQUIRE(mx::limiter_weights(lookahead, w), "lookahead must be 0 .. 512 and w not NULL"); });
 }
 
+int mx_graph_set_tempo(mx_graph* g, const mx_port_ref* ports, size_t n, const mx_tempo_params* params) {
+    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->tempo().set(ports, n, params); });
+}
+
+int mx_graph_read_tempo(mx_graph* g, void* dst, size_t cap_bytes, uint32_t* n_records) {
+    return guard([&] { REQUIRE(g, "graph is NULL"); const size_t n = g->g->tempo().read_records(dst, cap_bytes); if (n_records) *n_records = (uint32_t)n; });
+}
+
+int mx_tempo_record_bytes(const mx_tempo_params* params, size_t* bytes) {   // host only: no device, no graph
+    return guard([&] {
+        REQUIRE(params && bytes, "NULL argument");
+        REQUIRE(mx::tempo_params_ok(params->hop_frames, params->window_hops, params->max_lag, params->emit_ticks),
+                "mx_tempo_params: hop_frames must be 64, 128 or 256, window_hops 64 .. 4096, max_lag 16 .. 1024 and <= window_hops, emit_ticks >= 1");
+        *bytes = mx::tempo_record_bytes(params->max_lag);
+    });
+}
+
+int mx_tempo_bpm(const void* record, double rate, double bpm_lo, double bpm_hi, double* bpm, double* confidence) {   // host only
+    return guard([&] {
+        REQUIRE(record && bpm && confidence, "NULL argument");
+        uint32_t head[8];
+        std::memcpy(head, record, sizeof head);
+        const uint32_t H = head[3], W = head[4], L = head[5];
+        REQUIRE(mx::tempo_params_ok(H, W, L, 1), "not a tempo record: the header's hop_frames, window_hops or max_lag is outside its range");
+        REQUIRE(std::isfinite(rate) && rate > 0.0 && std::isfinite(bpm_lo) && bpm_lo > 0.0 && std::isfinite(bpm_hi) && bpm_hi >= bpm_lo,
+                "rate, bpm_lo and bpm_hi must be finite and positive, bpm_lo <= bpm_hi");
+        auto R = [&](uint32_t l) { uint64_t v; std::memcpy(&v, (const unsigned char*)record + 32 + 8 * (size_t)l, sizeof v); return (double)v; };
+        *bpm = 0.0; *confidence = 0.0;
+        const double lo = std::max(1.0, std::ceil(60.0 * rate / ((double)H * bpm_hi))), hi = std::min((double)(L - 2), std::floor(60.0 * rate / ((double)H * bpm_lo)));
+        if (R(0) == 0.0 || !(lo <= hi)) return;
+        uint32_t best = (uint32_t)lo;
+        for (uint32_t l = best + 1; l <= (uint32_t)hi; ++l)
+            if (R(l) > R(best)) best = l;   // the first maximum
+        const double den = R(best - 1) - 2.0 * R(best) + R(best + 1);
+        const double d = den < 0.0 ? 0.5 * (R(best - 1) - R(best + 1)) / den : 0.0;
+        *bpm = 60.0 * rate / ((double)H * ((double)best + d));
+        *confidence = R(best) / R(0);
+    });
+}
+
 int mx_stereo_gonio_record_bytes(const mx_stereo_params* params, size_t* bytes) {   // host only: no device, no graph
     return guard([&] {
         REQUIRE(params && bytes, "NULL argument");

@@ -156,7 +156,7 @@ struct OutRun {
 };
 uint32_t out_route_blocks(size_t frames_per_tick, uint32_t channels);
 void launch_output_device(const OutRun& r, hipStream_t s);
-// The audio tap sets (meters, spectrum, loudness, stereo field, limiter) read their ports through one descriptor per tap and buffer parity.
+// The audio tap sets (meters, spectrum, loudness, stereo field, limiter, tempo) read their ports through one descriptor per tap and buffer parity.
 // Their run structs begin alike -- desc, n, n_ticks, stride -- and launch_taps is overloaded on them, so the engine splits and defers any of
 // them the same way (TapSetOf::launch in mx_taps.hpp, Graph::launch_tap_set)
 enum : uint32_t { METER_MONO = 0, METER_STEREO = 1, METER_DUP = 2 };   // METER_DUP: stereo stored as one float per frame (L == R)
@@ -252,6 +252,34 @@ void launch_taps(const LimitRun& r, hipStream_t s);   // k_limit_init, then k_li
 void launch_limit_gather(const float* src, size_t pitch, uint32_t width, uint32_t n_ticks, float* dst, hipStream_t s);
 // the smoothing weights of the limiter spec, correctly rounded f32 (host only): w[lookahead + 1]; false: lookahead is above LIMIT_MAX_LOOKAHEAD
 bool limiter_weights(uint32_t lookahead, float* w);
+// Tempo taps (mx_k_tempo.hip, mixlab_gpu.h mx_graph_set_tempo): the descriptor (TapDesc's first four fields, then the stream position of the
+// tap's port when the descriptors were uploaded: the run's first frame is pos0 + ticks0 x frames, from which every hop a run touches, every
+// emission's last complete hop and hops_complete follow in integers).  Carried per tap: the energy of the hop in progress and A of the last
+// complete hop (each kept twice, alternating per run like the onset history), the frames counted non-finite since the last emission, and the
+// last W + L - 1 onsets.  The onsets live at the front of a linear array behind which a run appends those of the hops it completes, so every
+// emission of the run reads one stretch of it; the array is kept twice and the run writes the next run's front out of place.
+struct TempoDesc { const float* p; uint32_t frames, layout, slot, _pad; uint64_t pos0; };
+struct TempoRun {
+    const TempoDesc* desc; uint32_t n;       // the launch's taps
+    uint32_t n_ticks, stride;                // ticks of the run; taps of the whole set (records per emission)
+    uint32_t log2_hop, window_hops, max_lag, emit_ticks;
+    uint32_t phase, n_emit;                  // the graph's counter c mod emit_ticks at the run's first tick; (phase + n_ticks) / emit_ticks
+    uint64_t ticks0;                         // ticks since the descriptors were uploaded, before this run
+    uint32_t max_touched, max_done;          // the most hops any tap's run touches / completes (grid sizes)
+    uint32_t lin_stride, e_stride;           // words of one tap's linear array; hop energies of one tap
+    uint32_t* lin; uint32_t* lin_next;       // [slot][lin_stride]: W + L - 1 carried onsets, then the run's; the next run's
+    uint64_t* energy;                        // [slot][e_stride]: E of the hops this run completes
+    const uint64_t* part_in; uint64_t* part_out;   // [slot]
+    const uint32_t* amp_in; uint32_t* amp_out;     // [slot]
+    uint32_t* nonfinite;                     // [slot]
+    uint32_t* rec; uint32_t rec_words;       // rec[(emission * stride + slot) * rec_words]: 8 header words, then L uint64_t
+};
+inline size_t tempo_record_bytes(uint32_t max_lag) { return 32 + 8 * (size_t)max_lag; }
+inline bool tempo_params_ok(uint32_t hop_frames, uint32_t window_hops, uint32_t max_lag, uint32_t emit_ticks) {
+    return (hop_frames == 64 || hop_frames == 128 || hop_frames == 256) && window_hops >= 64 && window_hops <= 4096 && max_lag >= 16 && max_lag <= 1024 &&
+           max_lag <= window_hops && emit_ticks >= 1;
+}
+void launch_taps(const TempoRun& r, hipStream_t s);   // k_tempo_emit (a run that emits), k_tempo_energy, k_tempo_onsets, k_tempo_acf (a run that emits)
 // Video scope taps (mx_k_scope.hip, mixlab_gpu.h mx_graph_set_video_scopes): ONE launch counts one frame into one record -- the 32-byte
 // header, hist[3][256], wave[wave_cols][256], vec[128][128], all u32.  The counters of the record must be zero when the launch starts (the
 // workgroups add their partial counts with integer atomics); the kernel writes the header itself.  counted = 0: header only.

@@ -1,4 +1,4 @@
-// mx_taps.cpp -- the audio tap sets.  See mx_taps.hpp.  What the five share comes first, written for "a tap set"; then each set's own part.
+// mx_taps.cpp -- the audio tap sets.  See mx_taps.hpp.  What the six share comes first, written for "a tap set"; then each set's own part.
 #include "mx_taps.hpp"
 
 #include <algorithm>
@@ -360,6 +360,110 @@ float* LimiterTaps::limited_ptr(size_t tap, size_t* floats_per_tick) {
     if (floats_per_tick) *floats_per_tick = tick_floats_;
     host_.join_tail();   // the graph's stream is ordered behind a held-back tail's limiter launches too
     return (float*)out_.p + off_[tap];
+}
+
+// ---- tempo taps ----
+
+void TempoTaps::set(const mx_port_ref* ports_, size_t n, const mx_tempo_params* params) {
+    set_taps(ports_, n, params, [&] {
+        if (n && !tempo_params_ok(params->hop_frames, params->window_hops, params->max_lag, params->emit_ticks))
+            throw Error(MX_ERR_INVALID, "mx_tempo_params: hop_frames must be 64, 128 or 256, window_hops 64 .. 4096, max_lag 16 .. 1024 and <= window_hops, emit_ticks >= 1");
+        check_ports(ports_, n);
+        if (n) room(host_.tap_fpc(), n, *params);   // (throws before anything changed)
+    }, [&] {
+        par_ = *params;
+        // every tap's stream starts at frame 0 with nothing carried, c = 0; the onset arrays are sized and zeroed by the upload that follows
+        alloc_zeroed(state_, n * (2 * sizeof(uint64_t) + 3 * sizeof(uint32_t)), "hipMemsetAsync(tempo state)");
+    });
+}
+
+size_t TempoTaps::room(size_t fpc, size_t n, const mx_tempo_params& p) const {
+    const size_t max_ticks = std::max<size_t>(1, host_.cap_frames() / fpc), cap = (max_ticks + p.emit_ticks - 1) / p.emit_ticks;
+    if ((unsigned __int128)cap * n * tempo_record_bytes(p.max_lag) > ((unsigned __int128)4 << 30))
+        throw Error(MX_ERR_NOMEM, "tempo: the records of one run (ceil(max_ticks_per_run / emit_ticks) x taps x record bytes) exceed 4 GiB: raise emit_ticks");
+    return cap;
+}
+
+// beside the descriptors: every rate domain's stream position so far (the frames per tick change with the call length, the stream goes on),
+// room for the run's records, and the onset arrays -- whose length depends on the hops of the longest run the graph has room for, so a graph
+// that has grown moves the carried onsets into arrays of the new length (a changed call length alone leaves them where they are)
+void TempoTaps::upload(size_t fpc) {
+    const size_t n = ports.size();
+    const size_t need_rec = room(fpc, n, par_) * n * tempo_record_bytes(par_.max_lag);
+    const uint32_t hist = par_.window_hops + par_.max_lag - 1;
+    for (Domain& d : dom_) { d.pos0 += ticks0_ * d.frames; d.frames = 0; }
+    ticks0_ = 0;
+    uint64_t most_hops = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const TapPort t = port(i);
+        auto it = std::find_if(dom_.begin(), dom_.end(), [&](const Domain& d) { return d.num == t.dom_num && d.den == t.dom_den; });
+        if (it == dom_.end()) it = dom_.insert(dom_.end(), Domain{t.dom_num, t.dom_den, 0, 0});
+        it->frames = fpc * t.dom_num / t.dom_den;
+        if (it->frames > LIMIT_MAX_FRAMES) throw Error(MX_ERR_INVALID, "tempo: a tick of more than 2^30 frames");
+        // a run of the most frames, which starts anywhere in a hop; max_ticks x frames <= cap_frames x num / den whatever the call length
+        most_hops = std::max<uint64_t>(most_hops, (uint64_t)((unsigned __int128)host_.cap_frames() * t.dom_num / t.dom_den / par_.hop_frames) + 1);
+    }
+    if (most_hops + hist > 0x7fffffffu) throw Error(MX_ERR_NOMEM, "tempo: the hops of one run exceed the device");
+    const uint32_t lin_stride = (uint32_t)most_hops + hist, e_stride = (uint32_t)most_hops;
+    if (lin_stride != lin_stride_) {
+        DevBuf lin;
+        alloc_zeroed(lin, 2 * n * (size_t)lin_stride * sizeof(uint32_t), "hipMemsetAsync(tempo onsets)");
+        if (lin_.p)   // the carried onsets: the front of each tap's array in the buffer the next run reads
+            hip_check(hipMemcpy2DAsync((uint32_t*)lin.p + (size_t)hist_cur_ * n * lin_stride, (size_t)lin_stride * sizeof(uint32_t),
+                                       (const uint32_t*)lin_.p + (size_t)hist_cur_ * n * lin_stride_, (size_t)lin_stride_ * sizeof(uint32_t),
+                                       (size_t)hist * sizeof(uint32_t), n, hipMemcpyDeviceToDevice, host_.stream()), "hipMemcpy2DAsync(tempo onsets)");
+        hip_check(hipStreamSynchronize(host_.stream()), "hipStreamSynchronize");
+        lin_ = std::move(lin); lin_stride_ = lin_stride;
+    }
+    if (!energy_.p || e_stride != e_stride_) { energy_.alloc(n * (size_t)e_stride * sizeof(uint64_t)); e_stride_ = e_stride; }
+    const std::vector<TapDesc> t = tap_descs(fpc);
+    std::vector<TempoDesc> d(t.size());
+    for (size_t k = 0; k < t.size(); ++k) {
+        const TapPort tp = port(t[k].slot);
+        const Domain& dm = *std::find_if(dom_.begin(), dom_.end(), [&](const Domain& x) { return x.num == tp.dom_num && x.den == tp.dom_den; });
+        d[k] = TempoDesc{t[k].p, t[k].frames, t[k].layout, t[k].slot, 0u, dm.pos0};
+    }
+    upload_tap_descs(d.data(), d.size() * sizeof(TempoDesc), fpc, 0);
+    if (rec.bytes < need_rec) rec.alloc(need_rec);
+}
+
+// Each run reads the partial, the amplitude and the onset array the previous one wrote (they flip once per run).  The emission schedule and
+// every hop count follow from frame counts alone: the counter c and the stream positions live on the host, and the run's phase, emissions
+// and grid sizes are launch arguments.
+void TempoTaps::begin_run(uint32_t n_ticks) {
+    const uint32_t n = size(), emit = par_.emit_ticks, phase = (uint32_t)(c_ % emit);
+    const uint32_t n_emit = (uint32_t)(((uint64_t)phase + n_ticks) / emit);
+    uint32_t max_touched = 1, max_done = 0;
+    for (const Domain& d : dom_) {
+        if (!d.frames) continue;
+        const uint64_t pos = d.pos0 + ticks0_ * d.frames, end = pos + (uint64_t)n_ticks * d.frames, H = par_.hop_frames;
+        max_touched = std::max(max_touched, (uint32_t)((end - 1) / H - pos / H + 1));
+        max_done = std::max(max_done, (uint32_t)(end / H - pos / H));
+    }
+    uint64_t* part = (uint64_t*)state_.p; uint32_t* amp = (uint32_t*)(part + 2 * (size_t)n); uint32_t* bad = amp + 2 * (size_t)n;
+    uint32_t* lin = (uint32_t*)lin_.p; const size_t lin_words = (size_t)n * lin_stride_;
+    const uint32_t cur = flip_hist();
+    uint32_t log2_hop = 6; while ((1u << log2_hop) < par_.hop_frames) ++log2_hop;
+    run_ = TempoRun{(const TempoDesc*)desc.p, n, n_ticks, n, log2_hop, par_.window_hops, par_.max_lag, emit, phase, n_emit, ticks0_, max_touched, max_done,
+                    lin_stride_, e_stride_, lin + (size_t)cur * lin_words, lin + (size_t)(cur ^ 1u) * lin_words, (uint64_t*)energy_.p,
+                    part + (size_t)cur * n, part + (size_t)(cur ^ 1u) * n, amp + (size_t)cur * n, amp + (size_t)(cur ^ 1u) * n, bad,
+                    (uint32_t*)rec.p, 8u + 2u * par_.max_lag};
+    c_ += n_ticks; ticks0_ += n_ticks; n_rec_ = n_emit; run_seen_ = true;
+}
+
+size_t TempoTaps::read_records(void* dst, size_t cap_bytes) {
+    hip_check(hipSetDevice(host_.device()), "hipSetDevice");
+    if (empty()) throw Error(MX_ERR_INVALID, "no tempo taps are set");
+    if (!run_seen_) throw Error(MX_ERR_INVALID, "no run since the tempo taps were set");
+    const size_t count = (size_t)n_rec_ * ports.size(), bytes = count * tempo_record_bytes(par_.max_lag);
+    if (cap_bytes < bytes) throw Error(MX_ERR_INVALID, "cap_bytes is smaller than emissions x taps x record bytes");
+    if (bytes && !dst) throw Error(MX_ERR_INVALID, "dst is NULL");
+    if (bytes) {
+        host_.join_tail();
+        hip_check(hipMemcpyAsync(dst, rec.p, bytes, hipMemcpyDeviceToHost, host_.stream()), "hipMemcpyAsync(D2H)");
+        host_.sync();
+    }
+    return count;
 }
 
 }  // namespace mx

@@ -1,5 +1,5 @@
-// mx_taps.hpp -- the audio tap sets: level meters, spectrum, loudness, stereo field and limiter taps on audio output ports (mixlab_gpu.h
-// mx_graph_set_meters, _spectra, _loudness, _stereo, _limiters; DESIGN.md sections 0.2, 0.3, 0.5, 0.6, 0.8).  What the five share is
+// mx_taps.hpp -- the audio tap sets: level meters, spectrum, loudness, stereo field, limiter and tempo taps on audio output ports (mixlab_gpu.h
+// mx_graph_set_meters, _spectra, _loudness, _stereo, _limiters, _tempo; DESIGN.md sections 0.2, 0.3, 0.5, 0.6, 0.8, 0.9).  What the six share is
 // written once, in AudioTapSet; a set is one subclass that holds its own state, and one entry of Graph's list of sets (mx_engine.hpp), which
 // fixes the launch order.  The kernels, descriptors and run structs are mx_kernels.hpp's.
 #pragma once
@@ -167,6 +167,29 @@ private:
     mx_limiter_params par_{0.0f, 0};
     uint32_t max_frames_ = 0; size_t tick_floats_ = 0; std::vector<size_t> off_, floats_;
     DevBuf out_, hist_, w_, stage_;
+};
+
+// tempo taps (mx_graph_set_tempo / mx_graph_read_tempo): the autocorrelation of an onset function, one record per tap every emit_ticks ticks.
+// rec: the last run's records [emission][n], n_rec_ emissions.  state_: what a run hands to the next beside the onsets -- partial hop energy
+// uint64[2][n] | A of the last complete hop uint32[2][n] | non-finite frames since the last emission uint32[n]; lin_: uint32[2][n][lin_stride_],
+// a tap's W + L - 1 carried onsets and behind them the run's; of the three kept twice a run reads one buffer and writes the other.
+// energy_: uint64[n][e_stride_], E of the hops a run completes.  c_ is the emission counter c (0 when the taps are set, + the ticks of every
+// run).  The stream position of a tap follows from frame counts alone: dom_ holds, per rate domain of the set, the frames per tick and the
+// position when the descriptors were last uploaded; ticks0_ the ticks since.
+struct TempoTaps final : TapSetOf<TempoRun> {
+    explicit TempoTaps(TapHost& h) : TapSetOf(h, "tempo", "tempo taps", "a video port has no tempo", 1, "emissions x taps x record bytes") {}
+    void set(const mx_port_ref* ports, size_t n, const mx_tempo_params* params);
+    size_t read_records(void* dst, size_t cap_bytes);   // the last run's emitted records; returns how many
+    void upload(size_t fpc) override; void begin_run(uint32_t n_ticks) override;
+    void clear() override { clear_shared(); state_.free_(); lin_.free_(); energy_.free_(); dom_.clear(); par_ = mx_tempo_params{0, 0, 0, 0}; n_rec_ = 0; c_ = ticks0_ = 0; lin_stride_ = e_stride_ = 0; run_seen_ = false; }
+    void empty_run() override { run_ticks = 0; n_rec_ = 0; }
+private:
+    struct Domain { uint32_t num, den; uint64_t frames, pos0; };   // frames: per tick at the uploaded call length
+    size_t room(size_t fpc, size_t n, const mx_tempo_params& p) const;   // emissions a run can have; MX_ERR_NOMEM beyond 4 GiB of records
+    mx_tempo_params par_{0, 0, 0, 0};
+    uint32_t n_rec_ = 0, lin_stride_ = 0, e_stride_ = 0; uint64_t c_ = 0, ticks0_ = 0; bool run_seen_ = false;
+    std::vector<Domain> dom_;
+    DevBuf state_, lin_, energy_;
 };
 
 }  // namespace mx

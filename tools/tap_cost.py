@@ -1,10 +1,10 @@
 #!/usr/bin/env python
-"""Cost of one audio tap set on the headline-sized desk (DESIGN.md sections 0.2, 0.3, 0.5, 0.6, 0.8): 1024 config-2 strips into one Mixer at
+"""Cost of one audio tap set on the headline-sized desk (DESIGN.md sections 0.2, 0.3, 0.5, 0.6, 0.8, 0.9): 1024 config-2 strips into one Mixer at
 48 kHz, with no taps, with 2 taps (the Master and the Cue; not for the meters) and with 1026 taps (these and every strip's Amplifier port,
 stored one float per frame), one-tick runs and 2048-tick runs.  The cases alternate on the one graph (the set's mx_graph_set_* between
 them), three rounds each: a same-box A/B of the wall time per run.
 
-    python tools/tap_cost.py <meters|spectrum|loudness|stereo|limiter>
+    python tools/tap_cost.py <meters|spectrum|loudness|stereo|limiter|tempo>
 
   meters    hold 0, release 1
   spectrum  n_fft 2048, 31 log bands
@@ -14,9 +14,10 @@ them), three rounds each: a same-box A/B of the wall time per run.
   limiter   ceiling 0.5, lookahead 240 frames (5 ms).  The limited copies of 1026 taps are 6.6 MB per tick of the graph's
             max_ticks_per_run (13.4 GB at 2048), so the three cases alternate on a desk built for runs of LIMITER_LONG = 256 ticks (1.7 GB),
             and the cases without and with 2 taps alternate again on a desk built for 2048-tick runs
+  tempo     hops of 128 frames, a window of 2048 hops, 512 lags, a record every 6 ticks; one-tick, 256-tick and 2048-tick runs
 
 Run it under `rocprofv3 --kernel-trace --stats -- python tools/tap_cost.py <set>` for the kernels' own times (k_meter_*, k_spectrum*,
-k_loud_*, k_stereo_*, k_limit*)."""
+k_loud_*, k_stereo_*, k_limit*, k_tempo_*)."""
 import pathlib
 import statistics
 import sys
@@ -53,6 +54,15 @@ def set_limiter(g, taps):
     g.set_limiters(taps, 0.5, 240)
 
 
+def set_tempo(g, taps):
+    g.set_tempo(taps, 128, 2048, 512, 6)
+
+
+def read_tempo(g, taps, ticks):
+    rows = g.read_tempo()   # (a one-tick run emits on every sixth run only)
+    assert all(len(row) == len(taps) and row[-2]["hop_frames"] == 128 for row in rows) and (ticks < 6 or rows[-1][-2]["acf"][0] > 0)
+
+
 def read_limiter(g, taps, ticks):
     r = g.read_limiters(ticks - 1, 1)
     y = g.read_limited(len(taps) - 2, ticks - 1, 1)
@@ -87,6 +97,7 @@ SETS = {
     "loudness": (set_loudness, read_loudness, lambda n: f"loudness={n}", True, 2, 5, "loudness_cost"),
     "stereo": (set_stereo, read_stereo, lambda n: f"stereo={n} hop={HOPS[n]}", True, 2, 5, "stereo_cost"),
     "limiter": (set_limiter, read_limiter, lambda n: f"limiters={n}", True, 2, 5, "limiter_cost"),
+    "tempo": (set_tempo, read_tempo, lambda n: f"tempo={n}", True, 2, 5, "tempo_cost"),
 }
 
 
@@ -132,6 +143,8 @@ def main(which):
     if which == "limiter":
         measure(which, LIMITER_LONG, cases, ((1, 200), (LIMITER_LONG, 3 * long_reps)))
         measure(which, 2048, cases[:2], ((2048, long_reps),))
+    elif which == "tempo":
+        measure(which, 2048, cases, ((1, 240), (256, 3 * long_reps), (2048, long_reps)))
     else:
         measure(which, 2048, cases, ((1, 200), (2048, long_reps)))
     print(f"{name} done")
