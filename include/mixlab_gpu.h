@@ -36,7 +36,9 @@ extern "C" {
                               *    mx_stereo_correlation;
                               *    mx_limiter_params, mx_limiter_tick, mx_graph_set_limiters, mx_graph_read_limiters, mx_graph_read_limited, mx_graph_read_limited_i16,
                               *    mx_graph_limited_device_ptr, mx_limiter_weights;
-                              *    mx_tempo_params, mx_graph_set_tempo, mx_graph_read_tempo, mx_tempo_record_bytes, mx_tempo_bpm */
+                              *    mx_tempo_params, mx_graph_set_tempo, mx_graph_read_tempo, mx_tempo_record_bytes, mx_tempo_bpm;
+                              *    mx_tonality_params, mx_graph_set_tonality, mx_graph_read_tonality, mx_tonality_record_bytes, mx_tonality_tables, mx_tonality_chroma,
+                              *    mx_tonality_key */
 
 /* ---- status codes (0 ok, <0 error; cf. MIXLAB_IOCTX_ERROR / MIXLAB_IOCTX_PANIC) ---- */
 enum {
@@ -620,6 +622,75 @@ int mx_tempo_record_bytes(const mx_tempo_params* params, size_t* bytes);
  * *bpm = 0, *confidence = 0.  rate: the port's own frames per second.  A NULL argument, a header whose parameters are outside their ranges, a
  * rate or bound that is not finite and positive, or bpm_hi < bpm_lo: MX_ERR_INVALID. */
 int mx_tempo_bpm(const void* record, double rate, double bpm_lo, double bpm_hi, double* bpm, double* confidence);
+
+/* Tonality taps on audio output ports of a built graph: a constant-Q analysis of a decimated stream per port, from
+ * which a host reads the pitch-class profile and the musical key a DJ mixes harmonically by.  ("key" and "chroma" name the video keyer
+ * here, so this set is called tonality.)  Like a meter, a tap observes a port: no module, no edge, the run order and the fusion plan unchanged;
+ * a graph without them launches nothing new.  The audio tap sets are independent and may be set together.  Every run computes the records on
+ * the device, once per run after its last span.  BUILD-SPECIFIED (the reference has no such instrument); everything after the mid signal is
+ * integer arithmetic, so the records are fixed count for count (tests/tonality_model.py restates them in numpy and Python integers), they
+ * are identical however ticks are grouped into runs, and the order of accumulation cannot matter.
+ *   parameters  decim D: 4 or 8; hop_frames Hc (decimated frames): 128, 256 or 512; octaves O: 2 .. 6, B = 12 O bins; f_lo_mhz >= 1, the lowest
+ *             bin's frequency in millihertz (65406 = C2); emit_ticks >= 1.  One set per graph.
+ *   stream    a tap treats its port as one stream of frames that starts when the taps are set (frame 0) and continues across ticks and
+ *             runs, in the port's own rate domain (first_tick may jump: the stream does not care).  A mono port, and a stereo port stored as
+ *             one float per frame (the fused L == R strip result), read as L = R = x: equal to MX_FLAG_NO_FUSE's records byte for byte.
+ *   mid       m = L + R in f32, rounded once.
+ *   quantise  a non-finite m (NaN, +-Inf, also from finite L and R) gives q = 0 and is counted in `nonfinite`; else
+ *             q = (int32_t)(fminf(fmaxf(m, -2.0f), 2.0f) * 8192.0f): the product is exact, the conversion truncates, |q| <= 2^14.
+ *   decimate  fs_d = rate / D, Tf = 8 D taps: d[n] = (sum over k < Tf of c[k] * q[n D - k]) >> 15, an arithmetic shift (floor); q at a
+ *             negative index is 0; d[n] is complete in the tick that holds input frame n D.  c[k] = round(2^15 h[k] / sum h), where
+ *             h[k] = sin(2 pi (0.45 / D) t) / (pi t) * (0.5 - 0.5 cos(2 pi (k + 1) / (Tf + 1))), t = k - (Tf - 1) / 2: a Hann-windowed sinc
+ *             with cutoff 0.45 fs_d, centred at (Tf - 1) / 2, in f64 on the host.  sum |c[k]| <= 65534, so |d| < 32767: d fits an int16_t
+ *             and nothing is clamped.
+ *   kernels   Q = 17; f_b = f_lo * 2^(b / 12) for b < B; N_b = ceil(Q * fs_d / f_b).  N_0 > 2048, or f_{B-1} * 2^(1/24) >= 0.45 fs_d:
+ *             MX_ERR_INVALID.  For n < N_b: w_b[n] = 0.5 - 0.5 cos(2 pi (n + 1) / (N_b + 1)), phi = 2 pi f_b (n - (N_b - 1)) / fs_d,
+ *             K_re[b][n] = round(16384 w_b[n] cos(phi)), K_im[b][n] = round(-16384 w_b[n] sin(phi)), in f64 on the host; n = N_b - 1 is
+ *             the newest frame.  mx_tonality_tables returns c, N_b and K as the device uses them.
+ *   hop       hop h ends at decimated frame e_h = (h + 1) Hc - 1 and is complete in the tick that holds input frame e_h * D.
+ *             S_re = sum over n < N_b of K_re[b][n] * d[e_h - (N_b - 1) + n], likewise S_im; d at a negative index is 0; |S| <= 2^40.
+ *             M_b[h] = floor(sqrt((S_re >> 10)^2 + (S_im >> 10)^2)): the shifts are floor, the sum is below 2^61, the root is the exact
+ *             integer root.
+ *   emission  one counter c per graph: c = 0 when the taps are set; every tick does c += 1, and when c mod emit_ticks == 0 every tap emits a
+ *             record: C[b] = the sum of M_b[h] over the hops completed since the previous emission, as uint64_t.  Nothing is windowed:
+ *             the host sums records for a longer view (mx_tonality_chroma).
+ *   record    32-byte header uint32_t { tick_in_run (the emitting tick), hops (completed since the previous emission), nonfinite (frames
+ *             arrived since the previous emission), decim, hop_frames, octaves, f_lo_mhz, 0 }, then C[0 .. B) as uint64_t: 32 + 8 B bytes
+ *             (mx_tonality_record_bytes).
+ * Carried across runs per tap: the Tf - 1 + (D - 1) newest quantised frames, the newest 2047 + Hc - 1 decimated frames, C[b] and hops so
+ * far, and nonfinite; per graph: c.  Every call to mx_graph_set_tonality resets every tap and c.  mx_graph_adopt_state carries no taps. */
+typedef struct { uint32_t decim /* D: 4 or 8 */, hop_frames /* Hc, in decimated frames: 128, 256 or 512 */, octaves /* O: 2 .. 6; B = 12 O bins */, f_lo_mhz /* lowest bin's frequency in millihertz, e.g. 65406 = C2 */, emit_ticks /* >= 1 */; } mx_tonality_params;
+/* Replaces the graph's tonality taps with ports[0..n) (n = 0: none; params may then be NULL and the graph launches nothing for them).  Video
+ * port: MX_ERR_TYPE.  A node or port out of range, a duplicate (node, port), a port the fusion did not materialise, a parameter outside its
+ * range, kernels that do not exist at a port's own rate (N_0 > 2048, or the top bin at 0.45 fs_d): MX_ERR_INVALID.  The records of one run
+ * (ceil(max_ticks_per_run / emit_ticks) x n x record bytes) beyond 4 GiB: MX_ERR_NOMEM (raise emit_ticks).  Device memory that cannot be
+ * had: MX_ERR_NOMEM, and the graph is left without tonality taps.  Waits for outstanding work like a read-back but keeps the automatic
+ * second-stream mode on.  Device memory: the run's records, one table set per rate domain among the taps, and per tap 2 x (2047 + Hc - 1 +
+ * the decimated frames of the longest run) x 2 bytes.  The launches count in the profile calls' ms_total only (MX_PROFILE_KINDS is unchanged). */
+int mx_graph_set_tonality(mx_graph* g, const mx_port_ref* ports, size_t n, const mx_tonality_params* params);
+/* The records the last run emitted, [emission][tap in set order], mx_tonality_record_bytes each; *n_records = emissions x taps (0 when the
+ * run emitted none; n_records may be NULL).  No taps, no run since the taps were set, or cap_bytes too small: MX_ERR_INVALID.  Joins the
+ * graph's streams like mx_graph_read_output. */
+int mx_graph_read_tonality(mx_graph* g, void* dst, size_t cap_bytes, uint32_t* n_records);
+/* Bytes of one tonality record: 32 + 8 x 12 x octaves.  Host only.  A parameter outside its range or a NULL argument: MX_ERR_INVALID. */
+int mx_tonality_record_bytes(const mx_tonality_params* params, size_t* bytes);            /* 32 + 8 B */
+/* The tables of the spec for a port of `rate` frames per second, as the device uses them (host only, f64): fir[8 D] = c, len[B] = N_b, and
+ * kern[sum(len)][2] = { K_re, K_im }, bin after bin (kern NULL: sizes only); *kern_pairs = sum(len) (may be NULL).  A NULL params, fir or
+ * len, a parameter outside its range, a rate that is not finite and positive, N_0 > 2048 or the top bin at 0.45 fs_d: MX_ERR_INVALID. */
+int mx_tonality_tables(double rate, const mx_tonality_params* params, int16_t* fir /* 8 D */, uint32_t* len /* B */,
+                       int16_t* kern /* sum(len) x {re, im}, bin after bin; NULL: sizes only */, size_t* kern_pairs);
+/* Pitch-class profile of n_records >= 1 back-to-back records of one tap, in f64 on the host (needs no graph): C[b] summed over the records
+ * as integers, divided by N_b (recomputed from the header and rate), each bin folded into pitch class
+ * (round(12 log2(f_lo / 16.351597831)) + b) mod 12 with C = 0, and the twelve scaled to sum 1; all zero stays zero.  Records whose headers
+ * (decim, hop_frames, octaves, f_lo_mhz) disagree or are outside their ranges, kernels that do not exist at `rate`, a NULL argument or
+ * n_records = 0: MX_ERR_INVALID. */
+int mx_tonality_chroma(const void* records, size_t n_records, double rate, double chroma[12]);   /* host, f64 */
+/* Key of a pitch-class profile, in f64 on the host: the Pearson correlation r of chroma with the 24 rotations of the Krumhansl-Kessler
+ * profiles (major 6.35 2.23 3.48 2.33 4.38 4.09 2.52 5.19 2.39 3.66 2.29 2.88; minor 6.33 2.68 3.52 5.38 2.60 3.53 2.54 4.75 3.98 2.69 3.34
+ * 3.17).  *key = 0 .. 11: major on that tonic (C = 0); 12 .. 23: minor on tonic key - 12; the first maximum wins; *confidence = the best r
+ * minus the second best.  A chroma whose entries are all equal (all zero included): *key = -1, *confidence = 0.  A NULL argument or a chroma entry
+ * that is not finite: MX_ERR_INVALID. */
+int mx_tonality_key(const double chroma[12], int* key, double* confidence);                     /* host, f64 */
 
 /* Plotter indication (src/module/plotter.rs:37-56) for tick `tick_in_run` of the last run:
  * *fired = 1 and SPT floats in each of left/right when it fired (every 6th call, input connected). */

@@ -146,6 +146,12 @@ public:
     }
     // the tempo records the last run emitted, [emission][tap], mx_tempo_record_bytes each; returns how many (mx_tempo_bpm reads one)
     uint32_t read_tempo(std::vector<unsigned char>& dst) { uint32_t n = 0; check(mx_graph_read_tempo(g_, dst.data(), dst.size(), &n)); return n; }
+    // tonality taps (mx_graph_set_tonality): one parameter set for every tap; an empty list removes them
+    void set_tonality(const std::vector<mx_port_ref>& ports, const mx_tonality_params& p) {
+        check(mx_graph_set_tonality(g_, ports.data(), ports.size(), ports.empty() ? nullptr : &p));
+    }
+    // the tonality records the last run emitted, [emission][tap], mx_tonality_record_bytes each; returns how many (mx_tonality_chroma sums them)
+    uint32_t read_tonality(std::vector<unsigned char>& dst) { uint32_t n = 0; check(mx_graph_read_tonality(g_, dst.data(), dst.size(), &n)); return n; }
     // video scope taps (mx_graph_set_video_scopes): one parameter set for every tap; an empty list removes them
     void set_video_scopes(const std::vector<mx_port_ref>& ports, const mx_video_scope_params& p) {
         check(mx_graph_set_video_scopes(g_, ports.data(), ports.size(), ports.empty() ? nullptr : &p));

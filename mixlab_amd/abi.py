@@ -219,6 +219,18 @@ _proto("mx_graph_set_tempo", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_vo
 _proto("mx_graph_read_tempo", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32))
 _proto("mx_tempo_record_bytes", C.c_int, C.POINTER(TempoParams), C.POINTER(C.c_size_t))
 _proto("mx_tempo_bpm", C.c_int, C.c_void_p, C.c_double, C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double))
+class TonalityParams(C.Structure):
+    """mx_tonality_params: decimation (4, 8), the hop in decimated frames (128, 256, 512), octaves (2 .. 6; 12 bins each), the lowest bin's
+    frequency in millihertz and the emission period."""
+    _fields_ = [("decim", C.c_uint32), ("hop_frames", C.c_uint32), ("octaves", C.c_uint32), ("f_lo_mhz", C.c_uint32), ("emit_ticks", C.c_uint32)]
+
+
+_proto("mx_graph_set_tonality", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
+_proto("mx_graph_read_tonality", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32))
+_proto("mx_tonality_record_bytes", C.c_int, C.POINTER(TonalityParams), C.POINTER(C.c_size_t))
+_proto("mx_tonality_tables", C.c_int, C.c_double, C.POINTER(TonalityParams), C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t))
+_proto("mx_tonality_chroma", C.c_int, C.c_void_p, C.c_size_t, C.c_double, C.POINTER(C.c_double))
+_proto("mx_tonality_key", C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double))
 class VideoScopeParams(C.Structure):
     """mx_video_scope_params: waveform columns (0, 64, 128, 256), vectorscope on / off, record every hop-th video tick."""
     _fields_ = [("wave_cols", C.c_uint32), ("vectorscope", C.c_uint32), ("hop", C.c_uint32)]
@@ -374,6 +386,62 @@ def tempo_bpm(record, rate: float, bpm_lo: float, bpm_hi: float):
         raise MxError(MX_ERR_INVALID, "a tempo record is 32 + 8 * max_lag bytes")
     check(lib.mx_tempo_bpm(buf, float(rate), float(bpm_lo), float(bpm_hi), C.byref(b), C.byref(c)))
     return b.value, c.value
+
+
+def tonality_record_bytes(decim: int = 8, hop_frames: int = 512, octaves: int = 5, f_lo_mhz: int = 65406, emit_ticks: int = 30) -> int:
+    """bytes of one tonality record: 32 + 8 * 12 * octaves (mx_tonality_record_bytes, host only, no device)"""
+    n = C.c_size_t()
+    check(lib.mx_tonality_record_bytes(C.byref(TonalityParams(int(decim), int(hop_frames), int(octaves), int(f_lo_mhz), int(emit_ticks))), C.byref(n)))
+    return n.value
+
+
+def tonality_tables(rate: float, decim: int = 8, hop_frames: int = 512, octaves: int = 5, f_lo_mhz: int = 65406):
+    """(fir int16[8 * decim], len uint32[12 * octaves], kern int16[sum(len)][2]) -- the decimator's taps, the kernels' lengths N_b and their
+    {re, im} coefficients, bin after bin -- as the device uses them for a port of `rate` frames per second (mx_tonality_tables, host only)"""
+    par = TonalityParams(int(decim), int(hop_frames), int(octaves), int(f_lo_mhz), 1)
+    fir, ln, pairs = np.zeros(8 * max(0, int(decim)), np.int16), np.zeros(12 * max(0, int(octaves)), np.uint32), C.c_size_t()
+    check(lib.mx_tonality_tables(float(rate), C.byref(par), fir.ctypes.data_as(C.c_void_p), ln.ctypes.data_as(C.c_void_p), None, C.byref(pairs)))
+    kern = np.zeros((pairs.value, 2), np.int16)
+    check(lib.mx_tonality_tables(float(rate), C.byref(par), fir.ctypes.data_as(C.c_void_p), ln.ctypes.data_as(C.c_void_p), kern.ctypes.data_as(C.c_void_p), C.byref(pairs)))
+    return fir, ln, kern
+
+
+def parse_tonality_records(raw: np.ndarray, octaves: int) -> list:
+    """raw bytes of back-to-back tonality records -> one dict per record: the header fields as ints, cq uint64[12 * octaves] (C[b]) and raw,
+    the record's own bytes (what tonality_chroma takes)"""
+    r = np.ascontiguousarray(raw).view(np.uint8).reshape(-1, 32 + 96 * octaves)
+    out = []
+    for b in r:
+        w = b[:32].view(np.uint32)
+        d = dict(zip(("tick_in_run", "hops", "nonfinite", "decim", "hop_frames", "octaves", "f_lo_mhz", "reserved"), (int(x) for x in w)))
+        d["cq"] = b[32:].view(np.uint64)
+        d["raw"] = b.tobytes()
+        out.append(d)
+    return out
+
+
+def tonality_chroma(records, rate: float) -> np.ndarray:
+    """the pitch-class profile float64[12] (C = 0, sum 1 or all zero) of one tap's records -- bytes, or parse_tonality_records dicts --
+    summed, for a port of `rate` frames per second (mx_tonality_chroma, host only)"""
+    raw = b"".join(r["raw"] if isinstance(r, dict) else bytes(r) for r in records)
+    if len(raw) < 32:
+        raise MxError(MX_ERR_INVALID, "a tonality record is 32 + 96 * octaves bytes")
+    rb = 32 + 96 * int(np.frombuffer(raw, np.uint32, 8)[5])   # before the library reads that many bytes per record
+    if len(raw) % rb:
+        raise MxError(MX_ERR_INVALID, "a tonality record is 32 + 96 * octaves bytes")
+    buf = (C.c_char * len(raw)).from_buffer_copy(raw)
+    out = (C.c_double * 12)()
+    check(lib.mx_tonality_chroma(buf, len(raw) // rb, float(rate), out))
+    return np.array(out[:], np.float64)
+
+
+def tonality_key(chroma):
+    """(key, confidence) of a pitch-class profile: key 0 .. 11 major on that tonic (C = 0), 12 .. 23 minor, -1 for a profile without
+    variance; confidence the best Krumhansl-Kessler correlation minus the second best (mx_tonality_key, host only)"""
+    c = (C.c_double * 12)(*[float(x) for x in chroma])
+    k, conf = C.c_int(), C.c_double()
+    check(lib.mx_tonality_key(c, C.byref(k), C.byref(conf)))
+    return k.value, conf.value
 
 
 def video_scope_record_bytes(wave_cols: int = 0, vectorscope: bool = False) -> int:
@@ -712,6 +780,32 @@ class Graph:
         got = C.c_uint32()
         check(lib.mx_graph_read_tempo(self._h, raw.ctypes.data_as(C.c_void_p), raw.size, C.byref(got)))
         recs = parse_tempo_records(raw[: got.value * rb], max_lag)
+        return [recs[i:i + n] for i in range(0, len(recs), n)] if n else []
+
+    def set_tonality(self, ports, decim: int = 8, hop_frames: int = 512, octaves: int = 5, f_lo_mhz: int = 65406, emit_ticks: int = 30):
+        """tonality taps on audio output ports [(node, port), ...]: every emit_ticks ticks one record per tap with, per constant-Q bin (12 per
+        octave from f_lo_mhz up), the magnitudes of the hops completed since the previous record, summed; the analysis runs on the port's mid
+        signal decimated by decim, a hop every hop_frames decimated frames (tonality_chroma and tonality_key read pitch classes and the key
+        from the records).  One parameter set for every tap.  Each call resets every tap and the emission counter; [] removes them all."""
+        ports = list(ports)
+        if not ports:
+            check(lib.mx_graph_set_tonality(self._h, None, 0, None))
+            self._tonality = (0, 2, 1)
+            return
+        pa = (PortRef * len(ports))(*[PortRef(int(n), int(p)) for (n, p) in ports])
+        par = TonalityParams(int(decim), int(hop_frames), int(octaves), int(f_lo_mhz), int(emit_ticks))
+        check(lib.mx_graph_set_tonality(self._h, pa, len(ports), C.byref(par)))
+        self._tonality = (len(ports), int(octaves), max(1, int(emit_ticks)))
+
+    def read_tonality(self) -> list:
+        """the tonality records the last run emitted: a list over its emissions of lists over the taps in set order of
+        parse_tonality_records dicts"""
+        n, octaves, emit = getattr(self, "_tonality", (0, 2, 1))
+        rb = 32 + 96 * octaves
+        raw = np.zeros(max(1, -(-self.max_ticks // emit)) * max(1, n) * rb, dtype=np.uint8)
+        got = C.c_uint32()
+        check(lib.mx_graph_read_tonality(self._h, raw.ctypes.data_as(C.c_void_p), raw.size, C.byref(got)))
+        recs = parse_tonality_records(raw[: got.value * rb], octaves)
         return [recs[i:i + n] for i in range(0, len(recs), n)] if n else []
 
     def set_video_scopes(self, ports, wave_cols: int = 0, vectorscope: bool = False, hop: int = 1):

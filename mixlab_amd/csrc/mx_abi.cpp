@@ -354,6 +354,89 @@ int mx_tempo_bpm(const void* record, double rate, double bpm_lo, double bpm_hi, 
     });
 }
 
+int mx_graph_set_tonality(mx_graph* g, const mx_port_ref* ports, size_t n, const mx_tonality_params* params) {
+    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->tonality().set(ports, n, params); });
+}
+
+int mx_graph_read_tonality(mx_graph* g, void* dst, size_t cap_bytes, uint32_t* n_records) {
+    return guard([&] { REQUIRE(g, "graph is NULL"); const size_t n = g->g->tonality().read_records(dst, cap_bytes); if (n_records) *n_records = (uint32_t)n; });
+}
+
+static const char* const TONALITY_PARAMS = "mx_tonality_params: decim must be 4 or 8, hop_frames 128, 256 or 512, octaves 2 .. 6, f_lo_mhz >= 1, emit_ticks >= 1";
+
+int mx_tonality_record_bytes(const mx_tonality_params* params, size_t* bytes) {   // host only: no device, no graph
+    return guard([&] {
+        REQUIRE(params && bytes, "NULL argument");
+        REQUIRE(mx::tonality_params_ok(params->decim, params->hop_frames, params->octaves, params->f_lo_mhz, params->emit_ticks), TONALITY_PARAMS);
+        *bytes = mx::tonality_record_bytes(params->octaves);
+    });
+}
+
+int mx_tonality_tables(double rate, const mx_tonality_params* params, int16_t* fir, uint32_t* len, int16_t* kern, size_t* kern_pairs) {   // host only
+    return guard([&] {
+        REQUIRE(params && fir && len, "NULL argument");
+        REQUIRE(mx::tonality_params_ok(params->decim, params->hop_frames, params->octaves, params->f_lo_mhz, params->emit_ticks), TONALITY_PARAMS);
+        const int rc = mx::tonality_tables(rate, params->decim, params->octaves, params->f_lo_mhz, fir, len, kern, kern_pairs);
+        REQUIRE(rc != 1, "the lowest bin's kernel, ceil(17 fs_d / f_lo), exceeds 2048 decimated frames");
+        REQUIRE(rc != 2, "the highest bin reaches 0.45 fs_d, the decimator's cutoff");
+        REQUIRE(rc == 0, "rate must be finite and positive");
+    });
+}
+
+int mx_tonality_chroma(const void* records, size_t n_records, double rate, double chroma[12]) {   // host only
+    return guard([&] {
+        REQUIRE(records && chroma && n_records, "NULL argument or no records");
+        uint32_t head[8];
+        std::memcpy(head, records, sizeof head);
+        const uint32_t D = head[3], Hc = head[4], O = head[5], f_lo_mhz = head[6];
+        REQUIRE(mx::tonality_params_ok(D, Hc, O, f_lo_mhz, 1), "not a tonality record: the header's decim, hop_frames, octaves or f_lo_mhz is outside its range");
+        const uint32_t B = 12 * O;
+        const size_t rb = mx::tonality_record_bytes(O);
+        int16_t fir[64]; uint32_t len[72];
+        REQUIRE(mx::tonality_tables(rate, D, O, f_lo_mhz, fir, len, nullptr, nullptr) == 0, "no such kernels at this rate");
+        unsigned __int128 sum[72] = {};
+        for (size_t k = 0; k < n_records; ++k) {
+            const unsigned char* r = (const unsigned char*)records + k * rb;
+            uint32_t h[8];
+            std::memcpy(h, r, sizeof h);
+            REQUIRE(h[3] == D && h[4] == Hc && h[5] == O && h[6] == f_lo_mhz, "the records' headers disagree");
+            for (uint32_t b = 0; b < B; ++b) { uint64_t v; std::memcpy(&v, r + 32 + 8 * (size_t)b, sizeof v); sum[b] += v; }
+        }
+        const long shift = std::lround(12.0 * std::log2((f_lo_mhz / 1000.0) / 16.351597831));
+        double pc[12] = {}, total = 0.0;
+        for (uint32_t b = 0; b < B; ++b) { const double v = (double)sum[b] / (double)len[b]; pc[(((shift + (long)b) % 12) + 12) % 12] += v; }
+        for (double v : pc) total += v;
+        for (int k = 0; k < 12; ++k) chroma[k] = total > 0.0 ? pc[k] / total : 0.0;
+    });
+}
+
+int mx_tonality_key(const double chroma[12], int* key, double* confidence) {   // host only
+    return guard([&] {
+        REQUIRE(chroma && key && confidence, "NULL argument");
+        static const double prof[2][12] = {{6.35, 2.23, 3.48, 2.33, 4.38, 4.09, 2.52, 5.19, 2.39, 3.66, 2.29, 2.88},
+                                           {6.33, 2.68, 3.52, 5.38, 2.60, 3.53, 2.54, 4.75, 3.98, 2.69, 3.34, 3.17}};
+        double mean = 0.0, var = 0.0, lo = chroma[0], hi = chroma[0];
+        for (int k = 0; k < 12; ++k) { REQUIRE(std::isfinite(chroma[k]), "chroma must be finite"); mean += chroma[k] / 12.0; lo = std::min(lo, chroma[k]); hi = std::max(hi, chroma[k]); }
+        for (int k = 0; k < 12; ++k) var += (chroma[k] - mean) * (chroma[k] - mean);
+        *key = -1; *confidence = 0.0;
+        if (lo == hi || !(var > 0.0)) return;   // every entry equal (all zero included): no variance, no correlation
+        double best = -2.0, second = -2.0;
+        for (int m = 0; m < 2; ++m) {
+            double pm = 0.0, pv = 0.0;
+            for (int k = 0; k < 12; ++k) pm += prof[m][k] / 12.0;
+            for (int k = 0; k < 12; ++k) pv += (prof[m][k] - pm) * (prof[m][k] - pm);
+            for (int t = 0; t < 12; ++t) {
+                double cov = 0.0;
+                for (int k = 0; k < 12; ++k) cov += (chroma[(k + t) % 12] - mean) * (prof[m][k] - pm);   // the profile's tonic on pitch class t
+                const double r = cov / std::sqrt(var * pv);
+                if (r > best) { second = best; best = r; *key = 12 * m + t; }
+                else if (r > second) second = r;
+            }
+        }
+        *confidence = best - second;
+    });
+}
+
 int mx_stereo_gonio_record_bytes(const mx_stereo_params* params, size_t* bytes) {   // host only: no device, no graph
     return guard([&] {
         REQUIRE(params && bytes, "NULL argument");

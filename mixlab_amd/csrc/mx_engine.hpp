@@ -164,7 +164,7 @@ public:
     void audio_out_lag(uint32_t node);
     // the audio tap sets (mx_taps.hpp): taps on audio output ports, measured once per run after its last span
     MeterTaps& meters() { return meters_; } SpectrumTaps& spectra() { return spectra_; } LoudnessTaps& loudness() { return loudness_; }
-    StereoTaps& stereo() { return stereos_; } LimiterTaps& limiters() { return limiters_; } TempoTaps& tempo() { return tempos_; }
+    StereoTaps& stereo() { return stereos_; } LimiterTaps& limiters() { return limiters_; } TempoTaps& tempo() { return tempos_; } TonalityTaps& tonality() { return tonalities_; }
     bool tap_port(mx_port_ref r, TapPort& t) const override; size_t tap_fpc() const override { return tap_fpc_; }   // (TapHost: with the accessors marked override, all a set sees of the graph)
     // video scope taps (mx_graph_set_video_scopes / mx_graph_read_video_scopes): histograms, waveform and vectorscope of the frames on video ports
     void set_video_scopes(const mx_port_ref* ports, size_t n, const mx_video_scope_params* params);
@@ -295,8 +295,8 @@ private:
     std::vector<uint32_t> video_order_;     // the video nodes of order_, in run order
     std::vector<uint32_t> od_nodes_;        // OutputDevice nodes of order_ (never in a launch group: launched after the span's groups, behind their input's producer)
     size_t tap_fpc_ = 0;                        // frames per call every set's descriptors were built for (the tick length until a run says otherwise)
-    MeterTaps meters_{*this}; SpectrumTaps spectra_{*this}; LoudnessTaps loudness_{*this}; StereoTaps stereos_{*this}; LimiterTaps limiters_{*this}; TempoTaps tempos_{*this};
-    const std::array<AudioTapSet*, 6> taps_{&meters_, &spectra_, &loudness_, &stereos_, &limiters_, &tempos_};   // in launch order
+    MeterTaps meters_{*this}; SpectrumTaps spectra_{*this}; LoudnessTaps loudness_{*this}; StereoTaps stereos_{*this}; LimiterTaps limiters_{*this}; TempoTaps tempos_{*this}; TonalityTaps tonalities_{*this};
+    const std::array<AudioTapSet*, 7> taps_{&meters_, &spectra_, &loudness_, &stereos_, &limiters_, &tempos_, &tonalities_};   // in launch order
     // video scope taps: the taps in set order; scope_rec_: the last run's records [recorded tick][tap], scope_cap_ ticks of room.  scope_c_ is the
     // hop counter (0 when the taps are set, +1 per video tick, carried across runs); a tick is recorded when scope_c_ % hop == 0 before the increment
     std::vector<mx_port_ref> scopes_;

@@ -156,7 +156,7 @@ struct OutRun {
 };
 uint32_t out_route_blocks(size_t frames_per_tick, uint32_t channels);
 void launch_output_device(const OutRun& r, hipStream_t s);
-// The audio tap sets (meters, spectrum, loudness, stereo field, limiter, tempo) read their ports through one descriptor per tap and buffer parity.
+// The audio tap sets (meters, spectrum, loudness, stereo field, limiter, tempo, tonality) read their ports through one descriptor per tap and buffer parity.
 // Their run structs begin alike -- desc, n, n_ticks, stride -- and launch_taps is overloaded on them, so the engine splits and defers any of
 // them the same way (TapSetOf::launch in mx_taps.hpp, Graph::launch_tap_set)
 enum : uint32_t { METER_MONO = 0, METER_STEREO = 1, METER_DUP = 2 };   // METER_DUP: stereo stored as one float per frame (L == R)
@@ -280,6 +280,41 @@ inline bool tempo_params_ok(uint32_t hop_frames, uint32_t window_hops, uint32_t 
            max_lag <= window_hops && emit_ticks >= 1;
 }
 void launch_taps(const TempoRun& r, hipStream_t s);   // k_tempo_emit (a run that emits), k_tempo_energy, k_tempo_onsets, k_tempo_acf (a run that emits)
+// Tonality taps (mx_k_tonality.hip, mixlab_gpu.h mx_graph_set_tonality): the descriptor is TempoDesc's with the index of the tap's table set
+// (one per rate domain of the set: f_b / fs_d depends on it) in place of the padding.  From pos0 + ticks0 x frames, the run's first frame,
+// follow in integers the decimated frames a run completes (n D in [pos, end)), the hops among them and every emission's hop count.
+// Carried per tap: the TON_QTAIL(D) newest quantised frames and the TON_DHIST(Hc) newest decimated frames (each at the front of an array kept
+// twice, which a run reads and whose other copy it writes), the hops since the last emission (kept twice), and -- updated in place, by the
+// tap's own threads and atomics only -- the sums C[b] and the non-finite frames since the last emission.
+// A table set, at tab + index x tab_stride bytes: int16 fir[8 D] | uint32 len[B] | uint32 off[B] (pairs before bin b) | int16 kern[sum len][2].
+struct TonDesc { const float* p; uint32_t frames, layout, slot, tab; uint64_t pos0; };
+struct TonRun {
+    const TonDesc* desc; uint32_t n;         // the launch's taps
+    uint32_t n_ticks, stride;                // ticks of the run; taps of the whole set (records per emission)
+    uint32_t log2_d, log2_hop, bins, emit_ticks, f_lo_mhz;
+    uint32_t phase, n_emit;                  // the graph's counter c mod emit_ticks at the run's first tick; (phase + n_ticks) / emit_ticks
+    uint64_t ticks0;                         // ticks since the descriptors were uploaded, before this run
+    uint32_t max_groups, max_hops;           // the most stretches of D frames any tap's run holds / hops it completes (grid sizes)
+    uint32_t lin_stride;                     // int16 of one tap's decimated array: TON_DHIST carried, then the run's
+    const int16_t* qt; int16_t* qt_next;     // [slot][TON_QTAIL]
+    int16_t* lin; int16_t* lin_next;         // [slot][lin_stride]
+    const uint32_t* hops_in; uint32_t* hops_out;   // [slot]
+    uint64_t* csum; uint32_t* nonfinite;     // [slot][bins]; [slot]
+    const unsigned char* tab; uint32_t tab_stride;
+    uint32_t* rec; uint32_t rec_words;       // rec[(emission * stride + slot) * rec_words]: 8 header words, then C[0 .. B) as uint64_t
+};
+constexpr uint32_t TON_Q = 17, TON_MAX_KERNEL = 2048;
+inline uint32_t ton_qtail(uint32_t decim) { return 8 * decim - 1 + (decim - 1); }
+inline uint32_t ton_dhist(uint32_t hop_frames) { return TON_MAX_KERNEL - 1 + hop_frames - 1; }
+inline size_t tonality_record_bytes(uint32_t octaves) { return 32 + 8 * 12 * (size_t)octaves; }
+inline bool tonality_params_ok(uint32_t decim, uint32_t hop_frames, uint32_t octaves, uint32_t f_lo_mhz, uint32_t emit_ticks) {
+    return (decim == 4 || decim == 8) && (hop_frames == 128 || hop_frames == 256 || hop_frames == 512) && octaves >= 2 && octaves <= 6 && f_lo_mhz >= 1 &&
+           emit_ticks >= 1;
+}
+// the tables of the spec in f64 on the host: fir[8 D], len[B], and -- kern not NULL -- kern[sum len][2]; *kern_pairs = sum len.  0: fine;
+// 1: N_0 > 2048; 2: the top bin reaches 0.45 fs_d; 3: sum |c| > 65534; 4: rate is not finite and positive
+int tonality_tables(double rate, uint32_t decim, uint32_t octaves, uint32_t f_lo_mhz, int16_t* fir, uint32_t* len, int16_t* kern, size_t* kern_pairs);
+void launch_taps(const TonRun& r, hipStream_t s);   // k_ton_emit, k_ton_decimate, k_ton_cq (a run that completes a hop)
 // Video scope taps (mx_k_scope.hip, mixlab_gpu.h mx_graph_set_video_scopes): ONE launch counts one frame into one record -- the 32-byte
 // header, hist[3][256], wave[wave_cols][256], vec[128][128], all u32.  The counters of the record must be zero when the launch starts (the
 // workgroups add their partial counts with integer atomics); the kernel writes the header itself.  counted = 0: header only.

@@ -1,4 +1,4 @@
-// mx_taps.cpp -- the audio tap sets.  See mx_taps.hpp.  What the six share comes first, written for "a tap set"; then each set's own part.
+// mx_taps.cpp -- the audio tap sets.  See mx_taps.hpp.  What the seven share comes first, written for "a tap set"; then each set's own part.
 #include "mx_taps.hpp"
 
 #include <algorithm>
@@ -456,6 +456,154 @@ size_t TempoTaps::read_records(void* dst, size_t cap_bytes) {
     if (empty()) throw Error(MX_ERR_INVALID, "no tempo taps are set");
     if (!run_seen_) throw Error(MX_ERR_INVALID, "no run since the tempo taps were set");
     const size_t count = (size_t)n_rec_ * ports.size(), bytes = count * tempo_record_bytes(par_.max_lag);
+    if (cap_bytes < bytes) throw Error(MX_ERR_INVALID, "cap_bytes is smaller than emissions x taps x record bytes");
+    if (bytes && !dst) throw Error(MX_ERR_INVALID, "dst is NULL");
+    if (bytes) {
+        host_.join_tail();
+        hip_check(hipMemcpyAsync(dst, rec.p, bytes, hipMemcpyDeviceToHost, host_.stream()), "hipMemcpyAsync(D2H)");
+        host_.sync();
+    }
+    return count;
+}
+
+// ---- tonality taps ----
+
+static const char* const TON_PARAMS_MSG = "mx_tonality_params: decim must be 4 or 8, hop_frames 128, 256 or 512, octaves 2 .. 6, f_lo_mhz >= 1, emit_ticks >= 1";
+
+// the tables' refusals as errors (tonality_tables' codes)
+static void tonality_tables_check(int rc) {
+    if (rc == 1) throw Error(MX_ERR_INVALID, "tonality: the lowest bin's kernel, ceil(17 fs_d / f_lo), exceeds 2048 decimated frames (raise f_lo_mhz or decim)");
+    if (rc == 2) throw Error(MX_ERR_INVALID, "tonality: the highest bin reaches 0.45 fs_d, the decimator's cutoff (fewer octaves, a lower f_lo_mhz or decim 4)");
+    if (rc) throw Error(MX_ERR_INVALID, "tonality: no tables at this rate");
+}
+
+void TonalityTaps::set(const mx_port_ref* ports_, size_t n, const mx_tonality_params* params) {
+    set_taps(ports_, n, params, [&] {
+        if (n && !tonality_params_ok(params->decim, params->hop_frames, params->octaves, params->f_lo_mhz, params->emit_ticks)) throw Error(MX_ERR_INVALID, TON_PARAMS_MSG);
+        check_ports(ports_, n, [&](size_t, const TapPort& t) {   // the kernels must exist at the port's own rate
+            int16_t fir[64]; uint32_t len[72];
+            tonality_tables_check(tonality_tables(host_.sample_rate() * t.dom_num / t.dom_den, params->decim, params->octaves, params->f_lo_mhz, fir, len, nullptr, nullptr));
+        });
+        if (n) room(host_.tap_fpc(), n, *params);   // (throws before anything changed)
+    }, [&] {
+        par_ = *params;
+        // every tap's stream starts at frame 0 with nothing carried, c = 0; the decimated arrays are sized and zeroed by the upload that follows
+        const uint32_t B = 12 * par_.octaves;
+        alloc_zeroed(qt_, 2 * n * (size_t)ton_qtail(par_.decim) * sizeof(int16_t), "hipMemsetAsync(tonality tail)");
+        alloc_zeroed(hops_, 2 * n * sizeof(uint32_t), "hipMemsetAsync(tonality hops)");
+        alloc_zeroed(acc_, n * ((size_t)B * sizeof(uint64_t) + sizeof(uint32_t)), "hipMemsetAsync(tonality sums)");
+    });
+}
+
+size_t TonalityTaps::room(size_t fpc, size_t n, const mx_tonality_params& p) const {
+    const size_t max_ticks = std::max<size_t>(1, host_.cap_frames() / fpc), cap = (max_ticks + p.emit_ticks - 1) / p.emit_ticks;
+    if ((unsigned __int128)cap * n * tonality_record_bytes(p.octaves) > ((unsigned __int128)4 << 30))
+        throw Error(MX_ERR_NOMEM, "tonality: the records of one run (ceil(max_ticks_per_run / emit_ticks) x taps x record bytes) exceed 4 GiB: raise emit_ticks");
+    return cap;
+}
+
+// beside the descriptors: every rate domain's stream position so far and its table set (made when the domain is first seen: the rate of a
+// domain never changes), room for the run's records, and the decimated arrays -- whose length depends on the frames of the longest run the
+// graph has room for, so a graph that has grown moves the carried frames into arrays of the new length
+void TonalityTaps::upload(size_t fpc) {
+    const size_t n = ports.size();
+    const size_t need_rec = room(fpc, n, par_) * n * tonality_record_bytes(par_.octaves);
+    const uint32_t hist = ton_dhist(par_.hop_frames), B = 12 * par_.octaves, Tf = 8 * par_.decim;
+    for (Domain& d : dom_) { d.pos0 += ticks0_ * d.frames; d.frames = 0; }
+    ticks0_ = 0;
+    const size_t n_dom = dom_.size();
+    uint64_t most = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const TapPort t = port(i);
+        auto it = std::find_if(dom_.begin(), dom_.end(), [&](const Domain& d) { return d.num == t.dom_num && d.den == t.dom_den; });
+        if (it == dom_.end()) it = dom_.insert(dom_.end(), Domain{t.dom_num, t.dom_den, 0, 0});
+        it->frames = fpc * t.dom_num / t.dom_den;
+        if (it->frames > LIMIT_MAX_FRAMES) throw Error(MX_ERR_INVALID, "tonality: a tick of more than 2^30 frames");
+        // a run of the most frames, which starts anywhere between two decimated frames
+        most = std::max<uint64_t>(most, (uint64_t)((unsigned __int128)host_.cap_frames() * t.dom_num / t.dom_den / par_.decim) + 1);
+    }
+    if (most + hist > 0x7fffffffu) throw Error(MX_ERR_NOMEM, "tonality: the decimated frames of one run exceed the device");
+    if (dom_.size() != n_dom || !tab_.p) {   // a table set per domain, each padded to the longest
+        std::vector<std::vector<int16_t>> kern(dom_.size());
+        std::vector<std::vector<uint32_t>> len(dom_.size(), std::vector<uint32_t>(B));
+        std::vector<int16_t> fir(dom_.size() * Tf);
+        size_t most_pairs = 0;
+        for (size_t k = 0; k < dom_.size(); ++k) {
+            const double rate = host_.sample_rate() * dom_[k].num / dom_[k].den;
+            size_t pairs = 0;
+            tonality_tables_check(tonality_tables(rate, par_.decim, par_.octaves, par_.f_lo_mhz, fir.data() + k * Tf, len[k].data(), nullptr, &pairs));
+            kern[k].resize(2 * pairs);
+            tonality_tables(rate, par_.decim, par_.octaves, par_.f_lo_mhz, fir.data() + k * Tf, len[k].data(), kern[k].data(), &pairs);
+            most_pairs = std::max(most_pairs, pairs);
+        }
+        const size_t head = Tf * sizeof(int16_t) + 2 * (size_t)B * sizeof(uint32_t), stride = head + most_pairs * 2 * sizeof(int16_t);
+        std::vector<unsigned char> tab(dom_.size() * stride, 0);
+        for (size_t k = 0; k < dom_.size(); ++k) {
+            unsigned char* at = tab.data() + k * stride;
+            std::memcpy(at, fir.data() + k * Tf, Tf * sizeof(int16_t));
+            std::memcpy(at + Tf * sizeof(int16_t), len[k].data(), B * sizeof(uint32_t));
+            std::vector<uint32_t> off(B, 0);
+            for (uint32_t b = 1; b < B; ++b) off[b] = off[b - 1] + len[k][b - 1];
+            std::memcpy(at + Tf * sizeof(int16_t) + B * sizeof(uint32_t), off.data(), B * sizeof(uint32_t));
+            std::memcpy(at + head, kern[k].data(), kern[k].size() * sizeof(int16_t));
+        }
+        tab_.alloc(tab.size());
+        hip_check(hipMemcpy(tab_.p, tab.data(), tab.size(), hipMemcpyHostToDevice), "hipMemcpy(tonality tables)");
+        tab_stride_ = (uint32_t)stride;
+    }
+    const uint32_t lin_stride = ((uint32_t)most + hist + 1u) & ~1u;
+    if (lin_stride != lin_stride_) {
+        DevBuf lin;
+        alloc_zeroed(lin, 2 * n * (size_t)lin_stride * sizeof(int16_t), "hipMemsetAsync(tonality decimated frames)");
+        if (lin_.p)   // the carried frames: the front of each tap's array in the buffer the next run reads
+            hip_check(hipMemcpy2DAsync((int16_t*)lin.p + (size_t)hist_cur_ * n * lin_stride, (size_t)lin_stride * sizeof(int16_t),
+                                       (const int16_t*)lin_.p + (size_t)hist_cur_ * n * lin_stride_, (size_t)lin_stride_ * sizeof(int16_t),
+                                       (size_t)hist * sizeof(int16_t), n, hipMemcpyDeviceToDevice, host_.stream()), "hipMemcpy2DAsync(tonality decimated frames)");
+        hip_check(hipStreamSynchronize(host_.stream()), "hipStreamSynchronize");
+        lin_ = std::move(lin); lin_stride_ = lin_stride;
+    }
+    const std::vector<TapDesc> t = tap_descs(fpc);
+    std::vector<TonDesc> d(t.size());
+    for (size_t k = 0; k < t.size(); ++k) {
+        const TapPort tp = port(t[k].slot);
+        const auto dm = std::find_if(dom_.begin(), dom_.end(), [&](const Domain& x) { return x.num == tp.dom_num && x.den == tp.dom_den; });
+        d[k] = TonDesc{t[k].p, t[k].frames, t[k].layout, t[k].slot, (uint32_t)(dm - dom_.begin()), dm->pos0};
+    }
+    upload_tap_descs(d.data(), d.size() * sizeof(TonDesc), fpc, 0);
+    if (rec.bytes < need_rec) rec.alloc(need_rec);
+}
+
+// Each run reads the quantised tail, the decimated array and the hop count the previous one wrote (they flip once per run).  The emission
+// schedule, every decimated frame and every hop follow from frame counts alone: the counter c and the stream positions live on the host, and
+// the run's phase, emissions and grid sizes are launch arguments.
+void TonalityTaps::begin_run(uint32_t n_ticks) {
+    const uint32_t n = size(), emit = par_.emit_ticks, phase = (uint32_t)(c_ % emit), B = 12 * par_.octaves;
+    const uint32_t n_emit = (uint32_t)(((uint64_t)phase + n_ticks) / emit);
+    uint32_t max_groups = 0, max_hops = 0;
+    const uint64_t D = par_.decim, Hc = par_.hop_frames;
+    for (const Domain& d : dom_) {
+        if (!d.frames) continue;
+        const uint64_t pos = d.pos0 + ticks0_ * d.frames, run = (uint64_t)n_ticks * d.frames, end = pos + run;
+        max_groups = std::max(max_groups, (uint32_t)((run + D - 1) / D));
+        max_hops = std::max(max_hops, (uint32_t)((end + D - 1) / D / Hc - (pos + D - 1) / D / Hc));
+    }
+    const uint32_t cur = flip_hist(), QT = ton_qtail(par_.decim);
+    int16_t* qt = (int16_t*)qt_.p; int16_t* lin = (int16_t*)lin_.p; uint32_t* hops = (uint32_t*)hops_.p;
+    const size_t qt_words = (size_t)n * QT, lin_words = (size_t)n * lin_stride_;
+    uint32_t log2_d = 2; while ((1u << log2_d) < par_.decim) ++log2_d;
+    uint32_t log2_hop = 7; while ((1u << log2_hop) < par_.hop_frames) ++log2_hop;
+    run_ = TonRun{(const TonDesc*)desc.p, n, n_ticks, n, log2_d, log2_hop, B, emit, par_.f_lo_mhz, phase, n_emit, ticks0_, max_groups, max_hops, lin_stride_,
+                  qt + (size_t)cur * qt_words, qt + (size_t)(cur ^ 1u) * qt_words, lin + (size_t)cur * lin_words, lin + (size_t)(cur ^ 1u) * lin_words,
+                  hops + (size_t)cur * n, hops + (size_t)(cur ^ 1u) * n, (uint64_t*)acc_.p, (uint32_t*)((uint64_t*)acc_.p + (size_t)n * B),
+                  (const unsigned char*)tab_.p, tab_stride_, (uint32_t*)rec.p, 8u + 2u * B};
+    c_ += n_ticks; ticks0_ += n_ticks; n_rec_ = n_emit; run_seen_ = true;
+}
+
+size_t TonalityTaps::read_records(void* dst, size_t cap_bytes) {
+    hip_check(hipSetDevice(host_.device()), "hipSetDevice");
+    if (empty()) throw Error(MX_ERR_INVALID, "no tonality taps are set");
+    if (!run_seen_) throw Error(MX_ERR_INVALID, "no run since the tonality taps were set");
+    const size_t count = (size_t)n_rec_ * ports.size(), bytes = count * tonality_record_bytes(par_.octaves);
     if (cap_bytes < bytes) throw Error(MX_ERR_INVALID, "cap_bytes is smaller than emissions x taps x record bytes");
     if (bytes && !dst) throw Error(MX_ERR_INVALID, "dst is NULL");
     if (bytes) {

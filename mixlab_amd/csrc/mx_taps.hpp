@@ -1,5 +1,5 @@
-// mx_taps.hpp -- the audio tap sets: level meters, spectrum, loudness, stereo field, limiter and tempo taps on audio output ports (mixlab_gpu.h
-// mx_graph_set_meters, _spectra, _loudness, _stereo, _limiters, _tempo; DESIGN.md sections 0.2, 0.3, 0.5, 0.6, 0.8, 0.9).  What the six share is
+// mx_taps.hpp -- the audio tap sets: level meters, spectrum, loudness, stereo field, limiter, tempo and tonality taps on audio output ports (mixlab_gpu.h
+// mx_graph_set_meters, _spectra, _loudness, _stereo, _limiters, _tempo, _tonality; DESIGN.md sections 0.2, 0.3, 0.5, 0.6, 0.8, 0.9, 0.10).  What the seven share is
 // written once, in AudioTapSet; a set is one subclass that holds its own state, and one entry of Graph's list of sets (mx_engine.hpp), which
 // fixes the launch order.  The kernels, descriptors and run structs are mx_kernels.hpp's.
 #pragma once
@@ -190,6 +190,28 @@ private:
     uint32_t n_rec_ = 0, lin_stride_ = 0, e_stride_ = 0; uint64_t c_ = 0, ticks0_ = 0; bool run_seen_ = false;
     std::vector<Domain> dom_;
     DevBuf state_, lin_, energy_;
+};
+
+// tonality taps (mx_graph_set_tonality / mx_graph_read_tonality): constant-Q magnitudes of a decimated stream, summed per bin between emissions,
+// one record per tap every emit_ticks ticks.  rec: the last run's records [emission][n], n_rec_ emissions.  qt_: int16[2][n][TON_QTAIL], the newest
+// quantised frames; lin_: int16[2][n][lin_stride_], a tap's TON_DHIST carried decimated frames and behind them the run's; hops_: uint32[2][n],
+// hops since the last emission -- of these three a run reads one buffer and writes the other.  acc_: the sums C uint64[n][B] | non-finite frames
+// uint32[n] since the last emission, updated in place.  tab_: one table set per rate domain of the set (TonRun), tab_stride_ bytes each.
+// c_, dom_ and ticks0_ as for the tempo taps; a domain also holds the index of its table set.
+struct TonalityTaps final : TapSetOf<TonRun> {
+    explicit TonalityTaps(TapHost& h) : TapSetOf(h, "tonality", "tonality taps", "a video port has no tonality", 1, "emissions x taps x record bytes") {}
+    void set(const mx_port_ref* ports, size_t n, const mx_tonality_params* params);
+    size_t read_records(void* dst, size_t cap_bytes);   // the last run's emitted records; returns how many
+    void upload(size_t fpc) override; void begin_run(uint32_t n_ticks) override;
+    void clear() override { clear_shared(); qt_.free_(); lin_.free_(); hops_.free_(); acc_.free_(); tab_.free_(); dom_.clear(); par_ = mx_tonality_params{0, 0, 0, 0, 0}; n_rec_ = 0; c_ = ticks0_ = 0; lin_stride_ = tab_stride_ = 0; run_seen_ = false; }
+    void empty_run() override { run_ticks = 0; n_rec_ = 0; }
+private:
+    struct Domain { uint32_t num, den; uint64_t frames, pos0; };   // frames: per tick at the uploaded call length; the index in dom_ is the table set's
+    size_t room(size_t fpc, size_t n, const mx_tonality_params& p) const;   // emissions a run can have; MX_ERR_NOMEM beyond 4 GiB of records
+    mx_tonality_params par_{0, 0, 0, 0, 0};
+    uint32_t n_rec_ = 0, lin_stride_ = 0, tab_stride_ = 0; uint64_t c_ = 0, ticks0_ = 0; bool run_seen_ = false;
+    std::vector<Domain> dom_;
+    DevBuf qt_, lin_, hops_, acc_, tab_;
 };
 
 }  // namespace mx

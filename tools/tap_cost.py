@@ -1,10 +1,10 @@
 #!/usr/bin/env python
-"""Cost of one audio tap set on the headline-sized desk (DESIGN.md sections 0.2, 0.3, 0.5, 0.6, 0.8, 0.9): 1024 config-2 strips into one Mixer at
+"""Cost of one audio tap set on the headline-sized desk (DESIGN.md sections 0.2, 0.3, 0.5, 0.6, 0.8, 0.9, 0.10): 1024 config-2 strips into one Mixer at
 48 kHz, with no taps, with 2 taps (the Master and the Cue; not for the meters) and with 1026 taps (these and every strip's Amplifier port,
 stored one float per frame), one-tick runs and 2048-tick runs.  The cases alternate on the one graph (the set's mx_graph_set_* between
 them), three rounds each: a same-box A/B of the wall time per run.
 
-    python tools/tap_cost.py <meters|spectrum|loudness|stereo|limiter|tempo>
+    python tools/tap_cost.py <meters|spectrum|loudness|stereo|limiter|tempo|tonality>
 
   meters    hold 0, release 1
   spectrum  n_fft 2048, 31 log bands
@@ -15,9 +15,10 @@ them), three rounds each: a same-box A/B of the wall time per run.
             max_ticks_per_run (13.4 GB at 2048), so the three cases alternate on a desk built for runs of LIMITER_LONG = 256 ticks (1.7 GB),
             and the cases without and with 2 taps alternate again on a desk built for 2048-tick runs
   tempo     hops of 128 frames, a window of 2048 hops, 512 lags, a record every 6 ticks; one-tick, 256-tick and 2048-tick runs
+  tonality  decimation 8, hops of 512 decimated frames, 5 octaves from C2, a record every 30 ticks; one-tick, 256-tick and 2048-tick runs
 
 Run it under `rocprofv3 --kernel-trace --stats -- python tools/tap_cost.py <set>` for the kernels' own times (k_meter_*, k_spectrum*,
-k_loud_*, k_stereo_*, k_limit*, k_tempo_*)."""
+k_loud_*, k_stereo_*, k_limit*, k_tempo_*, k_ton_*)."""
 import pathlib
 import statistics
 import sys
@@ -63,6 +64,15 @@ def read_tempo(g, taps, ticks):
     assert all(len(row) == len(taps) and row[-2]["hop_frames"] == 128 for row in rows) and (ticks < 6 or rows[-1][-2]["acf"][0] > 0)
 
 
+def set_tonality(g, taps):
+    g.set_tonality(taps, 8, 512, 5, 65406, 30)
+
+
+def read_tonality(g, taps, ticks):
+    rows = g.read_tonality()   # (a one-tick run emits on every thirtieth run only)
+    assert all(len(row) == len(taps) and row[-2]["hop_frames"] == 512 for row in rows) and (ticks < 30 or rows[-1][-2]["cq"].any())
+
+
 def read_limiter(g, taps, ticks):
     r = g.read_limiters(ticks - 1, 1)
     y = g.read_limited(len(taps) - 2, ticks - 1, 1)
@@ -98,6 +108,7 @@ SETS = {
     "stereo": (set_stereo, read_stereo, lambda n: f"stereo={n} hop={HOPS[n]}", True, 2, 5, "stereo_cost"),
     "limiter": (set_limiter, read_limiter, lambda n: f"limiters={n}", True, 2, 5, "limiter_cost"),
     "tempo": (set_tempo, read_tempo, lambda n: f"tempo={n}", True, 2, 5, "tempo_cost"),
+    "tonality": (set_tonality, read_tonality, lambda n: f"tonality={n}", True, 2, 5, "tonality_cost"),
 }
 
 
@@ -143,7 +154,7 @@ def main(which):
     if which == "limiter":
         measure(which, LIMITER_LONG, cases, ((1, 200), (LIMITER_LONG, 3 * long_reps)))
         measure(which, 2048, cases[:2], ((2048, long_reps),))
-    elif which == "tempo":
+    elif which in ("tempo", "tonality"):
         measure(which, 2048, cases, ((1, 240), (256, 3 * long_reps), (2048, long_reps)))
     else:
         measure(which, 2048, cases, ((1, 200), (2048, long_reps)))
