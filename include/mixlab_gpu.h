@@ -869,6 +869,29 @@ typedef struct {
     uint32_t spill_strength;  /* 0 .. 255; must be 0 in luma mode */
 } mx_video_key_params;        /* 24 bytes */
 int mx_video_key(const mx_dframe* in, const mx_video_key_params* params, mx_dframe** out, void* stream);
+/* The PLACER (BUILD-SPECIFIED; the reference has none): a crop of a frame resampled into a rectangle of a transparent canvas, on the device --
+ * picture-in-picture, side-by-side, a keyed presenter in a corner, a zoom.  `in` is yuv420p or yuva420p (anything else: MX_ERR_INVALID -- conversion is the scaler's
+ * business); *out is a NEW yuva420p frame of canvas_w x canvas_h carrying one reference, its stride padding as mx_dframe_create_fmt leaves it.  The input's padding, and
+ * input samples outside the crop, are never read as picture.  All quantities are integers.
+ *   CROP PLANES: Y and the input coverage A_in restricted to [crop_x, crop_x + crop_w) x [crop_y, crop_y + crop_h); U and V restricted to the same rectangle with every
+ *     number halved.
+ *   RESAMPLED PLANES Sy, Su, Sv, Sa: the crop planes resampled exactly as the scaler (DESIGN.md "Scaler", mx_video_scaler_taps) resamples a frame that consisted of the
+ *     crop alone: tap tables (crop_w -> dst_w, crop_h -> dst_h) for luma and coverage, (crop_w/2 -> dst_w/2, crop_h/2 -> dst_h/2) for chroma; H pass over every crop
+ *     row t = (sum hc * S + 64) >> 7; V pass clip8((sum vc * t + 2^20) >> 21); tap indices clamp to the CROP, not to the plane.  No letterbox and no aspect rule: the crop
+ *     is stretched to the rectangle (mx_video_scale_geometry is the caller's tool to keep an aspect).  Without input coverage Sa is 255 everywhere.
+ *   CANVAS: luma and coverage at (x, y) are Sy, Sa at (x - dst_x, y - dst_y) when dst_x <= x < dst_x + dst_w and dst_y <= y < dst_y + dst_h, otherwise Y = 0 and
+ *     coverage = 0.  Chroma at (cx, cy) is Su, Sv at (cx - dst_x/2, cy - dst_y/2) inside the halved rectangle, otherwise 0x80.  The tables are always those of the full
+ *     dst_w x dst_h, however much of the rectangle the canvas clips away; a rectangle wholly outside the canvas gives a blank, fully transparent frame and is no error.
+ *     Every number being even, a chroma sample's co-sited luma sample (2cx, 2cy) is inside the rectangle exactly when the chroma sample is: the compositor's coverage
+ *     rule for chroma needs nothing new.
+ * Values outside the ranges in the comments below are MX_ERR_INVALID; so is a crop that does not lie inside `in`.  Stateless; asynchronous on `stream`, like mx_video_key. */
+typedef struct {
+    uint32_t canvas_w, canvas_h;               /* even, >= 2, within what mx_dframe_create_fmt accepts */
+    uint32_t crop_x, crop_y, crop_w, crop_h;   /* even; crop_w = crop_h = 0 (then crop_x = crop_y = 0): the whole frame; otherwise >= 2 and inside the input frame */
+    int32_t  dst_x, dst_y;                     /* even; may be negative or beyond the canvas: the rectangle is clipped */
+    uint32_t dst_w, dst_h;                     /* even, >= 2, <= 16384; crop_w <= 32 * dst_w and crop_h <= 32 * dst_h (at most 130 taps per axis, mx_video_scaler_tap_count) */
+} mx_video_place_params;                       /* 40 bytes */
+int mx_video_place(const mx_dframe* in, const mx_video_place_params* params, mx_dframe** out, void* stream);
 int mx_video_sync(void* stream);
 /* A caller-owned hipStream_t that graphs / scalers / mixers launched pictures on is about to be destroyed: release what the library keeps per (device, stream) for its
  * batched video launches (page-locked descriptor staging, device copies, events, an upload stream).  The library frees this itself for streams it created; for a caller's
@@ -918,6 +941,14 @@ int mx_graph_set_video_source_band(mx_graph* g, uint32_t node, uint32_t in_w, ui
  * cannot carry coverage).  A source frame that is not yuv420p / yuva420p fails the run with MX_ERR_INVALID, mx_last_error naming the node.  A scope tap on the source's
  * port sees the keyed frame.  mx_graph_adopt_state does not carry the setting. */
 int mx_graph_set_video_source_key(mx_graph* g, uint32_t node, const mx_video_key_params* params /* NULL removes */);
+/* The placer as a per-source transform (mx_video_place): on every tick the SOURCE_VIDEO node has a frame -- from any of the feeders listed above --
+ * it delivers the placed yuva420p canvas instead.  With a key set on the same node the order is KEY, THEN PLACE, whichever call came first: the key is decided at the source's
+ * own resolution and its coverage is resampled with the picture.  The keyer's cache and pool rules hold: a frame is transformed once per setting, not once per tick, and a
+ * pooled output is rewritten only when the pool alone holds it; the tap tables are uploaded once per setting (and per size of a whole-frame crop), not per frame.  params NULL
+ * removes the transform.  MX_ERR_TYPE for a node that is not a SOURCE_VIDEO, MX_ERR_INVALID for bad parameters and together with mx_graph_set_video_source_band, in either
+ * order.  A source frame of another format, or a crop outside the frame that arrives, fails the run with MX_ERR_INVALID, mx_last_error naming the node, before anything of the
+ * run is launched.  A scope tap on the source's port sees the placed frame.  mx_graph_adopt_state does not carry the setting. */
+int mx_graph_set_video_source_place(mx_graph* g, uint32_t node, const mx_video_place_params* params /* NULL removes */);
 /* One frame due on one tick of a SOURCE_VIDEO node: tick `tick` (absolute, as in mx_graph_run_ticks' first_tick + k) emits `frame` with the
  * given duration hint and tick offset; ticks without an entry emit None.  Entries are queued in ascending tick order, one per tick
  * (MX_ERR_INVALID otherwise), and while any is queued they take the place of mx_graph_set_video_source[_ring].  What

@@ -160,6 +160,7 @@ public:
     uint32_t read_video_scopes(std::vector<uint8_t>& dst) { uint32_t n = 0; check(mx_graph_read_video_scopes(g_, dst.data(), dst.size(), &n)); return n; }
     // the keyer as a transform of a SOURCE_VIDEO node (mx_graph_set_video_source_key): the node delivers the keyed yuva420p frame; nullptr removes it
     void set_video_source_key(uint32_t node, const mx_video_key_params* p) { check(mx_graph_set_video_source_key(g_, node, p)); }
+    void set_video_source_place(uint32_t node, const mx_video_place_params* p) { check(mx_graph_set_video_source_place(g_, node, p)); }
     size_t samples_per_tick() const { size_t s = 0; check(mx_graph_samples_per_tick(g_, &s)); return s; }
     mx_graph* handle() const { return g_; }
 private:

@@ -250,6 +250,19 @@ class VideoKeyParams(C.Structure):
 
 _proto("mx_video_key", C.c_int, C.c_void_p, C.POINTER(VideoKeyParams), C.POINTER(C.c_void_p), C.c_void_p)
 _proto("mx_graph_set_video_source_key", C.c_int, C.c_void_p, C.c_uint32, C.POINTER(VideoKeyParams))
+
+
+class VideoPlaceParams(C.Structure):
+    """mx_video_place_params (40 bytes): the canvas, the crop of the input (0 x 0: the whole frame) and the rectangle of the canvas it is stretched into."""
+    _fields_ = [("canvas_w", C.c_uint32), ("canvas_h", C.c_uint32), ("crop_x", C.c_uint32), ("crop_y", C.c_uint32), ("crop_w", C.c_uint32), ("crop_h", C.c_uint32),
+                ("dst_x", C.c_int32), ("dst_y", C.c_int32), ("dst_w", C.c_uint32), ("dst_h", C.c_uint32)]
+
+
+# the placer's kernel (mx_video.hpp MX_PLACE_*): a workgroup writes a PLACE_TILE_W x PLACE_TILE_H tile of one canvas PLANE (chroma planes: half the luma numbers);
+# axes of up to PLACE_TAP_BOUND taps (downscales up to 4:1) take the LDS-tiled form, more taps the gather form: tests put sizes and ratios around them
+PLACE_TILE_W, PLACE_TILE_H, PLACE_TAP_BOUND = 64, 16, 18
+_proto("mx_video_place", C.c_int, C.c_void_p, C.POINTER(VideoPlaceParams), C.POINTER(C.c_void_p), C.c_void_p)
+_proto("mx_graph_set_video_source_place", C.c_int, C.c_void_p, C.c_uint32, C.POINTER(VideoPlaceParams))
 _proto("mx_graph_profile_run", C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float))
 _proto("mx_graph_profile_enable", C.c_int, C.c_void_p, C.c_int)
 _proto("mx_graph_profile_collect", C.c_int, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32))

@@ -353,6 +353,23 @@ int mx_video_key(const mx_dframe* in, const mx_video_key_params* params, mx_dfra
     });
 }
 
+int mx_video_place(const mx_dframe* in, const mx_video_place_params* params, mx_dframe** out, void* stream) {
+    return guard([&] {
+        REQUIRE(out, "out is NULL");
+        *out = nullptr;
+        REQUIRE(in && params, "NULL argument");
+        mx::check_place_params(*params);
+        DFrame* d = const_cast<DFrame*>(D(in));
+        if (const char* why = mx::place_input_error(d, *params)) throw Error(MX_ERR_INVALID, why);
+        hipStream_t s = S(stream);
+        auto tabs = mx::make_place_tables(d, *params);
+        FrameRef o(DFrame::create_unfilled(params->canvas_w, params->canvas_h, MX_PIXFMT_YUV420P, true), false);
+        mx::place_into(d, *params, *tabs, o.f, s);
+        o->retain();
+        *out = H(o.f);
+    });
+}
+
 int mx_video_sync(void* stream) {
     return guard([&] { mx::hip_check(hipStreamSynchronize(S(stream)), "hipStreamSynchronize"); });
 }
@@ -448,6 +465,9 @@ int mx_graph_set_video_source_band(mx_graph* g, uint32_t node, uint32_t in_w, ui
 }
 int mx_graph_set_video_source_key(mx_graph* g, uint32_t node, const mx_video_key_params* params) {
     return guard([&] { REQUIRE(g, "graph is NULL"); g->g->set_video_source_key(node, params); });
+}
+int mx_graph_set_video_source_place(mx_graph* g, uint32_t node, const mx_video_place_params* params) {
+    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->set_video_source_place(node, params); });
 }
 int mx_graph_video_output(mx_graph* g, uint32_t node, uint32_t port, mx_dframe** out) {
     return guard([&] {

@@ -518,7 +518,7 @@ Graph::~Graph() {
     if (tail_stream_) (void)hipStreamSynchronize(tail_stream_);
     if (stream_) (void)hipStreamSynchronize(stream_);
     if (tail_stream_) { (void)hipStreamDestroy(tail_stream_); (void)hipEventDestroy(ev_head_done_); for (auto& e : ev_tail_done_) (void)hipEventDestroy(e); }
-    for (Node& n : nodes_) { n.vmixer.reset(); n.vout.clear(); n.vsrc = FrameRef(); n.vsrc_ring.clear(); n.vsrc_sched.clear(); n.vkey_done.clear(); n.vkey_pool.clear(); }
+    for (Node& n : nodes_) { n.vmixer.reset(); n.vout.clear(); n.vsrc = FrameRef(); n.vsrc_ring.clear(); n.vsrc_sched.clear(); n.vkey_done.clear(); n.vkey_pool.clear(); n.vplace_done.clear(); n.vplace_pool.clear(); n.vplace_tabs.reset(); }
     prof_runs_.clear(); prof_pool_.clear();
     for (Stage& st : stage_) { if (st.done) (void)hipEventDestroy(st.done); if (st.host) (void)hipHostFree(st.host); }
     // the descriptor ring launch_video_batch keeps per stream goes with a stream this graph OWNS; a caller's stream may be shared with other
@@ -1060,18 +1060,23 @@ void Graph::run(uint64_t t0, size_t fpc, uint32_t n_calls, float* ms_by_kind, fl
     auto drop_schedules = [&] { for (uint32_t id : sched_nodes_) { nodes_[id].sched.clear(); nodes_[id].gate_sched.clear(); } sched_nodes_.clear(); };
     if (frames > cap_frames_) { drop_schedules(); throw Error(MX_ERR_INVALID, "n_ticks exceeds max_ticks_per_run"); }
     if (n_calls == 0 || fpc == 0) { drop_schedules(); last_calls_ = n_calls; last_frames_per_call_ = fpc; for (AudioTapSet* s : taps_) s->empty_run(); scope_n_ = 0; return; }
-    // keyed video sources: a frame the keyer cannot take fails the run HERE, before anything of it is launched or any node's state has moved
+    // keyed / placed video sources: a frame the transform cannot take fails the run HERE, before anything of it is launched or any node's state has moved
     for (uint32_t id : video_order_) {
         const Node& n = nodes_[id];
-        if (n.kind != MX_KIND_SOURCE_VIDEO || !n.vkey_on) continue;
+        if (n.kind != MX_KIND_SOURCE_VIDEO || !(n.vkey_on || n.vplace_on)) continue;
         const uint64_t tick0 = t0 / spt_, last = tick0 + n_calls - 1;
-        bool ok = true;
-        for (const Node::VSched& e : n.vsrc_sched) if (e.tick >= tick0 && e.tick <= last) ok = ok && key_input_ok(e.frame.f);
+        const char* why = nullptr;
+        auto look = [&](const DFrame* f) {
+            if (why) return;
+            if (n.vkey_on && !key_input_ok(f)) why = "the keyer takes yuv420p or yuva420p frames (mx_graph_set_video_source_key)";
+            else if (n.vplace_on) why = place_input_error(f, n.vplace);
+        };
+        for (const Node::VSched& e : n.vsrc_sched) if (e.tick >= tick0 && e.tick <= last) look(e.frame.f);
         if (n.vsrc_sched.empty() || n.vsrc_sched.back().tick < last) {   // ticks of the run past the queue fall through to the ring / the set frame
-            if (!n.vsrc_ring.empty()) { for (const FrameRef& f : n.vsrc_ring) ok = ok && key_input_ok(f.f); }
-            else if (n.vsrc && (n.vsrc_repeat || n.vsrc_pending)) ok = ok && key_input_ok(n.vsrc.f);
+            if (!n.vsrc_ring.empty()) { for (const FrameRef& f : n.vsrc_ring) look(f.f); }
+            else if (n.vsrc && (n.vsrc_repeat || n.vsrc_pending)) look(n.vsrc.f);
         }
-        if (!ok) { drop_schedules(); throw Error(MX_ERR_INVALID, "node " + std::to_string(id) + " (SOURCE_VIDEO): the keyer takes yuv420p or yuva420p frames (mx_graph_set_video_source_key)"); }
+        if (why) { drop_schedules(); throw Error(MX_ERR_INVALID, "node " + std::to_string(id) + " (SOURCE_VIDEO): " + why); }
     }
     hip_check(hipSetDevice(device_), "hipSetDevice");
     if (fpc != tap_fpc_) {   // (the module compat path's call length): frames per tick and record room
@@ -1793,7 +1798,8 @@ void Graph::run_video_tick(uint64_t t) {
                 n.vband->run(n.vout[0].frame.f, o.f, stream_);
                 n.vout[0].frame = o;
             }
-            if (n.vkey_on && n.vout[0].frame) n.vout[0].frame = keyed_source_frame(id, n.vout[0].frame);
+            if (n.vplace_on && n.vout[0].frame) n.vout[0].frame = placed_source_frame(id, n.vout[0].frame);   // keys first where a key is set
+            else if (n.vkey_on && n.vout[0].frame) n.vout[0].frame = keyed_source_frame(id, n.vout[0].frame);
             break;
         }
         case MX_KIND_VIDEO_MIXER: {
@@ -1953,6 +1959,7 @@ void Graph::set_video_source_band(uint32_t node, uint32_t in_w, uint32_t in_full
     if (node >= nodes_.size() || nodes_[node].kind != MX_KIND_SOURCE_VIDEO) throw Error(MX_ERR_INVALID, "node is not a SOURCE_VIDEO");
     Node& nd = nodes_[node];
     if (band_rows && nd.vkey_on) throw Error(MX_ERR_INVALID, "video source band: the source is keyed (mx_graph_set_video_source_key), and a band-scaled layer cannot carry coverage");
+    if (band_rows && nd.vplace_on) throw Error(MX_ERR_INVALID, "video source band: the source is placed (mx_graph_set_video_source_place), and a band-scaled layer cannot carry coverage");
     sync();                                     // a previous band scaler's row buffer may be in use
     nd.vband.reset(); nd.vband_pool.clear();
     if (band_rows) nd.vband = std::make_shared<BandScaler>(in_w, in_full_h, src_row0, slice_rows, full_w, full_h, row0, band_rows);
@@ -1968,8 +1975,24 @@ void Graph::set_video_source_key(uint32_t node, const mx_video_key_params* param
     }
     // frames keyed under the old setting are of no use; their output frames stay in the pool and are rewritten once their last holder has let go
     nd.vkey_done.clear();
+    nd.vplace_done.clear();   // a placed frame holds the picture as it was keyed
     nd.vkey_on = params != nullptr;
     if (params) nd.vkey = *params; else nd.vkey_pool.clear();
+}
+
+void Graph::set_video_source_place(uint32_t node, const mx_video_place_params* params) {
+    if (node >= nodes_.size()) throw Error(MX_ERR_INVALID, "node out of range");
+    if (nodes_[node].kind != MX_KIND_SOURCE_VIDEO) throw Error(MX_ERR_TYPE, "video source place: node is not a SOURCE_VIDEO");
+    Node& nd = nodes_[node];
+    if (params) {
+        check_place_params(*params);
+        if (nd.vband) throw Error(MX_ERR_INVALID, "video source place: the source delivers a row band of a scaled layer (mx_graph_set_video_source_band), which cannot carry coverage");
+    }
+    // as for the key: frames placed under the old setting are of no use; a canvas of another size needs other frames, so the pool goes too
+    nd.vplace_done.clear(); nd.vplace_pool.clear(); nd.vplace_tabs.reset();
+    nd.vplace_on = params != nullptr;
+    if (params) nd.vplace = *params;
+    nd.vkey_done.clear();   // the keyed frames a placed source needs are the placer's alone and never listed; those listed before must not pin their pool frames
 }
 
 // The keyed form of `src` on a SOURCE_VIDEO node: keyed once per setting, reused while anything but this list holds the source frame.
@@ -1993,6 +2016,38 @@ FrameRef Graph::keyed_source_frame(uint32_t id, const FrameRef& src) {
     }
     key_into(src.f, n.vkey, o.f, stream_);
     n.vkey_done.push_back(Node::VKeyed{src, o});
+    return o;
+}
+
+// The placed form of `src` on a SOURCE_VIDEO node: key (where set), then place -- once per setting, reused while anything but this list holds the source frame.
+FrameRef Graph::placed_source_frame(uint32_t id, const FrameRef& src) {
+    Node& n = nodes_[id];
+    if (n.vkey_on && !key_input_ok(src.f)) throw Error(MX_ERR_INVALID, "node " + std::to_string(id) + " (SOURCE_VIDEO): the keyer takes yuv420p or yuva420p frames");
+    if (const char* why = place_input_error(src.f, n.vplace)) throw Error(MX_ERR_INVALID, "node " + std::to_string(id) + " (SOURCE_VIDEO): " + why);
+    for (size_t i = 0; i < n.vplace_done.size(); ++i)
+        if (n.vplace_done[i].src.f == src.f) return n.vplace_done[i].out;
+    for (size_t i = 0; i < n.vplace_done.size();) {
+        if (n.vplace_done[i].src->rc.load(std::memory_order_acquire) == 1) n.vplace_done.erase(n.vplace_done.begin() + (ptrdiff_t)i); else ++i;
+    }
+    if (n.vplace_done.size() >= 32) n.vplace_done.erase(n.vplace_done.begin());
+    // a pooled frame is rewritten only when the pool alone holds it (keyed_source_frame); the keyed frame between the two passes is read by the placement launched right
+    // behind the key on stream_, and by nobody else
+    auto pooled = [&](std::vector<FrameRef>& pool, uint32_t w, uint32_t h, bool filled) {
+        for (auto& f : pool)
+            if (f->width == w && f->height == h && f->rc.load(std::memory_order_acquire) == 1) return f;
+        if (pool.size() >= 64) pool.erase(pool.begin());
+        pool.push_back(FrameRef(filled ? DFrame::create(w, h, stream_, MX_PIXFMT_YUV420P, true) : DFrame::create_unfilled(w, h, MX_PIXFMT_YUV420P, true), false));
+        return pool.back();
+    };
+    FrameRef in = src;
+    if (n.vkey_on) {
+        in = pooled(n.vkey_pool, src->width, src->height, true);   // the keyer leaves the padding as DFrame::create made it
+        key_into(src.f, n.vkey, in.f, stream_);
+    }
+    if (!n.vplace_tabs || !place_tables_fit(*n.vplace_tabs, in.f, n.vplace)) n.vplace_tabs = make_place_tables(in.f, n.vplace);
+    FrameRef o = pooled(n.vplace_pool, n.vplace.canvas_w, n.vplace.canvas_h, false);   // the placer writes every byte
+    place_into(in.f, n.vplace, *n.vplace_tabs, o.f, stream_);
+    n.vplace_done.push_back(Node::VKeyed{src, o});
     return o;
 }
 

@@ -72,6 +72,11 @@ struct Node {
     bool vkey_on = false; mx_video_key_params vkey{};
     struct VKeyed { FrameRef src, out; };
     std::vector<VKeyed> vkey_done; std::vector<FrameRef> vkey_pool;
+    // SOURCE_VIDEO: the placer as a transform (mx_graph_set_video_source_place), after the key where both are set.  vplace_done / vplace_pool follow the keyer's rules, an
+    // entry's src being the frame the FEEDER delivered (with a key set the keyed frame between the two is a pool frame nobody else sees, and is not listed under the key)
+    bool vplace_on = false; mx_video_place_params vplace{};
+    std::shared_ptr<const PlaceTables> vplace_tabs;   // of the current setting (and, for a whole-frame crop, of the size of the frame seen last)
+    std::vector<VKeyed> vplace_done; std::vector<FrameRef> vplace_pool;
     std::vector<DevBuf> rgba; uint32_t rgba_cur = 0, rgba_w = 0, rgba_h = 0; int32_t rgba_stride = 0;   // VIDEO_TO_RGBA: video_batch_ticks() buffers, written in turn (that many ticks' chains may share a launch); rgba_cur = the last tick's
     struct PendingRgba { ChainRgbaArgs args; std::shared_ptr<LazyChain> keep; };
     std::vector<PendingRgba> rgba_pending;     // VIDEO_TO_RGBA: chains of the last ticks, not launched yet, oldest first (run_video_tick)
@@ -199,6 +204,7 @@ public:
     void set_video_source_band(uint32_t node, uint32_t in_w, uint32_t in_full_h, uint32_t src_row0, uint32_t slice_rows, uint32_t full_w, uint32_t full_h, uint32_t row0, uint32_t band_rows);
     void set_video_source_ring(uint32_t node, DFrame* const* frames, size_t n, Rational dur, Rational off);
     void set_video_source_key(uint32_t node, const mx_video_key_params* params);   // nullptr removes
+    void set_video_source_place(uint32_t node, const mx_video_place_params* params);   // nullptr removes
     void queue_video_source(uint32_t node, uint64_t tick, DFrame* frame, Rational dur, Rational off);
     // what a feed checks BEFORE it takes frames out of a pacing state machine (a rejected feed must not lose media):
     void check_video_queue(uint32_t node, uint64_t first_tick) const;   // queue_video_source(node, first_tick, ...) would be accepted
@@ -222,6 +228,7 @@ private:
     void upload_group_one(Group& g, uint32_t parity);   // ... of one parity: desc / extra, or desc_alt / extra_alt
     void run_video_tick(uint64_t t);
     FrameRef keyed_source_frame(uint32_t id, const FrameRef& src);   // SOURCE_VIDEO with a key set: src keyed under the node's setting (once per frame)
+    FrameRef placed_source_frame(uint32_t id, const FrameRef& src);  // SOURCE_VIDEO with a placement set: src (keyed first where a key is set) placed, once per frame
     void launch_pending_rgba(Node& n, size_t count, bool with_queued_scales);   // the `count` oldest pending chains of a sink
     void launch_video_scope(uint32_t tap, const Node::VOut& v);          // one tap's record of the tick being run (run_video_tick, on a recorded tick)
     // one launch sequence over ticks [call_off, call_off + n_calls) of the current run

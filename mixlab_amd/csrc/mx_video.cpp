@@ -762,4 +762,104 @@ void key_into(DFrame* in, const mx_video_key_params& p, DFrame* out, hipStream_t
     hip_check(hipGetLastError(), "key launch");
 }
 
+// ---------------------------------------------------------------------------------------------
+// the placer (mixlab_gpu.h mx_video_place; kernel in mx_k_place.hip)
+// ---------------------------------------------------------------------------------------------
+void check_place_params(const mx_video_place_params& p) {
+    auto even = [](uint32_t v) { return (v & 1u) == 0u; };
+    if (!even(p.canvas_w) || !even(p.canvas_h) || p.canvas_w < 2 || p.canvas_h < 2 || p.canvas_w > 16384u || p.canvas_h > 16384u)
+        throw Error(MX_ERR_INVALID, "mx_video_place_params: canvas_w / canvas_h must be even, 2 .. 16384");
+    if (!even(p.crop_x) || !even(p.crop_y) || !even(p.crop_w) || !even(p.crop_h)) throw Error(MX_ERR_INVALID, "mx_video_place_params: the crop must be even");
+    if ((p.crop_w == 0) != (p.crop_h == 0)) throw Error(MX_ERR_INVALID, "mx_video_place_params: crop_w and crop_h are both 0 (the whole frame) or both >= 2");
+    if (p.crop_w == 0 && (p.crop_x || p.crop_y)) throw Error(MX_ERR_INVALID, "mx_video_place_params: the whole-frame crop has crop_x = crop_y = 0");
+    if (p.crop_w > 16384u || p.crop_h > 16384u || p.crop_x > 16384u || p.crop_y > 16384u) throw Error(MX_ERR_INVALID, "mx_video_place_params: the crop lies beyond any frame");
+    if ((p.dst_x & 1) || (p.dst_y & 1)) throw Error(MX_ERR_INVALID, "mx_video_place_params: dst_x / dst_y must be even");
+    if (!even(p.dst_w) || !even(p.dst_h) || p.dst_w < 2 || p.dst_h < 2 || p.dst_w > 16384u || p.dst_h > 16384u)
+        throw Error(MX_ERR_INVALID, "mx_video_place_params: dst_w / dst_h must be even, 2 .. 16384");
+    if (p.crop_w && ((uint64_t)p.crop_w > 32ull * p.dst_w || (uint64_t)p.crop_h > 32ull * p.dst_h))
+        throw Error(MX_ERR_INVALID, "mx_video_place_params: the crop is more than 32 times the rectangle (at most 130 taps per axis)");
+}
+
+const char* place_input_error(const DFrame* in, const mx_video_place_params& p) {
+    if (in->fmt != MX_PIXFMT_YUV420P) return "the placer takes yuv420p or yuva420p (scale a frame of another format first)";
+    if (p.crop_w) {
+        if ((uint64_t)p.crop_x + p.crop_w > in->width || (uint64_t)p.crop_y + p.crop_h > in->height) return "the placer's crop lies outside the frame";
+    } else if ((uint64_t)in->width > 32ull * p.dst_w || (uint64_t)in->height > 32ull * p.dst_h) return "the placer's whole-frame crop is more than 32 times the rectangle";
+    return nullptr;
+}
+
+bool place_tables_fit(const PlaceTables& t, const DFrame* in, const mx_video_place_params& p) {
+    return t.cw == (p.crop_w ? p.crop_w : in->width) && t.ch == (p.crop_h ? p.crop_h : in->height) && t.dw == p.dst_w && t.dh == p.dst_h;
+}
+
+// Tables are kept per (device, crop size, rectangle size), the last 16 of them: neither the stateless call nor a graph uploads them per frame, and the call stays
+// asynchronous (freeing a table waits for the device; a table that leaves this list while a launch reads it is freed behind that launch)
+std::shared_ptr<const PlaceTables> make_place_tables(const DFrame* in, const mx_video_place_params& p) {
+    static std::mutex mu;
+    static auto& kept = *new std::vector<std::pair<int, std::shared_ptr<const PlaceTables>>>();   // never destroyed: no hipFree behind the runtime's own teardown
+    int dev = 0;
+    hip_check(hipGetDevice(&dev), "hipGetDevice");
+    std::lock_guard<std::mutex> lk(mu);
+    for (size_t i = 0; i < kept.size(); ++i)
+        if (kept[i].first == dev && place_tables_fit(*kept[i].second, in, p)) {
+            auto hit = kept[i];
+            kept.erase(kept.begin() + (ptrdiff_t)i); kept.push_back(hit);
+            return hit.second;
+        }
+    auto t = std::make_shared<PlaceTables>();
+    t->cw = p.crop_w ? p.crop_w : in->width; t->ch = p.crop_h ? p.crop_h : in->height; t->dw = p.dst_w; t->dh = p.dst_h;
+    std::vector<int32_t> blob;
+    size_t offs[2][4];
+    for (int c = 0; c < 2; ++c) {
+        std::vector<int32_t> f[2], k[2];
+        make_taps(t->cw >> c, t->dw >> c, f[0], k[0]);
+        make_taps(t->ch >> c, t->dh >> c, f[1], k[1]);
+        t->taps[c][0] = tap_count(t->cw >> c, t->dw >> c); t->taps[c][1] = tap_count(t->ch >> c, t->dh >> c);
+        // the tiled form keeps the H pass' values as (t + 8192) in 16 bits: true of every table seen so far (a row's positive taps sum to < 1.2 x 16384), checked here
+        bool fits = t->taps[c][0] <= MX_PLACE_TAP_BOUND && t->taps[c][1] <= MX_PLACE_TAP_BOUND;
+        const uint32_t hn = t->taps[c][0];
+        for (size_t o = 0; fits && o * hn < k[0].size(); ++o) {
+            int64_t pos = 0, neg = 0;
+            for (uint32_t j = 0; j < hn; ++j) { const int32_t v = k[0][o * hn + j]; if (v > 0) pos += v; else neg += v; }
+            if (((255 * pos + 64) >> 7) + 8192 > 65535 || ((255 * neg + 64) >> 7) + 8192 < 0) fits = false;
+        }
+        t->tiled[c] = fits;
+        auto put = [&](const std::vector<int32_t>& v) { while (blob.size() & 3) blob.push_back(0); size_t o = blob.size(); blob.insert(blob.end(), v.begin(), v.end()); return o; };
+        offs[c][0] = put(f[0]); offs[c][1] = put(k[0]); offs[c][2] = put(f[1]); offs[c][3] = put(k[1]);
+    }
+    t->tabs.alloc(blob.size() * sizeof(int32_t));
+    hip_check(hipMemcpy(t->tabs.p, blob.data(), blob.size() * sizeof(int32_t), hipMemcpyHostToDevice), "hipMemcpy(place taps)");
+    for (int c = 0; c < 2; ++c) for (int k = 0; k < 4; ++k) t->tab[c][k] = (const int32_t*)t->tabs.p + offs[c][k];
+    if (kept.size() >= 16) kept.erase(kept.begin());
+    kept.emplace_back(dev, t);
+    return t;
+}
+
+void place_into(DFrame* in, const mx_video_place_params& p, const PlaceTables& t, DFrame* out, hipStream_t s) {
+    if (const char* why = place_input_error(in, p)) throw Error(MX_ERR_INVALID, why);
+    if (out->fmt != MX_PIXFMT_YUV420P || !out->alpha || out->width != p.canvas_w || out->height != p.canvas_h) throw Error(MX_ERR_INTERNAL, "place: the output frame is not yuva420p of the canvas size");
+    if (!place_tables_fit(t, in, p)) throw Error(MX_ERR_INTERNAL, "place: the tap tables belong to another setting");
+    in->ensure_pixels(s);
+    flush_scales(s);   // the input may be a scaler's output whose job is still queued
+    // a rectangle that misses the canvas leaves a blank, transparent frame (and its offsets, which may be anything, out of the kernel's arithmetic)
+    const bool meets = (int64_t)p.dst_x < (int64_t)p.canvas_w && (int64_t)p.dst_y < (int64_t)p.canvas_h && (int64_t)p.dst_x + p.dst_w > 0 && (int64_t)p.dst_y + p.dst_h > 0;
+    PlaceArgs a{};
+    for (int i = 0; i < 4; ++i) {   // Y, coverage, U, V
+        const int c = i >= 2 ? 1 : 0, ip = i >= 2 ? i - 1 : 0;
+        PlacePlane& pp = a.p[i];
+        if (i == 1) { pp.src = in->alpha; pp.src_stride = in->alpha ? in->alpha_stride : 0u; pp.dst = out->alpha; pp.dst_stride = out->alpha_stride; }
+        else { pp.src = in->data[ip]; pp.src_stride = in->stride[ip]; pp.dst = out->data[ip]; pp.dst_stride = out->stride[ip]; }
+        pp.cx = p.crop_x >> c; pp.cy = p.crop_y >> c; pp.cw = t.cw >> c; pp.ch = t.ch >> c;
+        pp.w = p.canvas_w >> c; pp.h = p.canvas_h >> c;
+        if (meets) { pp.rx = p.dst_x / (c ? 2 : 1); pp.ry = p.dst_y / (c ? 2 : 1); pp.rw = p.dst_w >> c; pp.rh = p.dst_h >> c; }   // even offsets: the halves are exact
+        pp.hfirst = t.tab[c][0]; pp.hcoef = t.tab[c][1]; pp.vfirst = t.tab[c][2]; pp.vcoef = t.tab[c][3];
+        pp.hn = t.taps[c][0]; pp.vn = t.taps[c][1];
+        pp.fill = i == 0 ? 0u : (i == 1 ? 0u : 0x80u);
+        pp.pad = i == 0 ? 0u : (i == 1 ? 0xffu : 0x80u);   // DFrame::create: blank picture, opaque coverage plane
+        pp.tiled = t.tiled[c] ? 1u : 0u;
+    }
+    launch_video_place(a, s);
+    hip_check(hipGetLastError(), "place launch");
+}
+
 }  // namespace mx

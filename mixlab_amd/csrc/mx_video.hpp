@@ -176,6 +176,40 @@ bool key_input_ok(const DFrame* in);                   // yuv420p, with or witho
 // `in` keyed under p into `out` (yuva420p of in's size, created by DFrame::create: the kernel leaves its padding as it is), asynchronous on s
 void key_into(DFrame* in, const mx_video_key_params& p, DFrame* out, hipStream_t s);
 
+// ---- the placer (mixlab_gpu.h mx_video_place; mx_k_place.hip) ----
+// A workgroup writes one MX_PLACE_TILE_W x MX_PLACE_TILE_H byte tile of one canvas plane; the LDS-tiled form takes axes of up to MX_PLACE_TAP_BOUND taps.
+enum { MX_PLACE_TILE_W = 64, MX_PLACE_TILE_H = 16, MX_PLACE_TAP_BOUND = 18 };
+struct PlacePlane {
+    const uint8_t* src;                            // the input PLANE (its row 0, column 0); nullptr: no input coverage -- the resampled plane is 255
+    uint8_t* dst;                                  // the canvas plane
+    uint32_t src_stride, dst_stride;
+    uint32_t cx, cy, cw, ch;                       // the crop, in samples of this plane
+    uint32_t w, h;                                 // the canvas plane's visible size
+    int32_t rx, ry; uint32_t rw, rh;               // the rectangle, in samples of this plane (rw = 0: wholly outside the canvas)
+    const int32_t* hfirst; const int32_t* hcoef;   // [rw], [rw][hn]: the tables of (cw -> rw)
+    const int32_t* vfirst; const int32_t* vcoef;   // [rh], [rh][vn]: the tables of (ch -> rh)
+    uint32_t hn, vn;
+    uint32_t fill, pad;                            // the byte outside the rectangle, and the byte of the stride padding (what DFrame::create leaves)
+    uint32_t tiled;                                // the LDS-tiled form may be used (tap counts within the bound, H-pass values within 16 bits)
+    uint32_t tile_start, tiles_x;                  // launcher-filled: the plane's first workgroup, workgroups per tile row
+};
+struct PlaceArgs { PlacePlane p[4]; };             // Y, coverage, U, V
+void launch_video_place(PlaceArgs a, hipStream_t s);
+// the tap tables of one (crop size -> rectangle size), on the device: built once per setting (and per size of a whole-frame crop), not per frame
+struct PlaceTables {
+    uint32_t cw = 0, ch = 0, dw = 0, dh = 0;       // luma sizes
+    DevBuf tabs;
+    const int32_t* tab[2][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};   // [luma/chroma][hfirst,hcoef,vfirst,vcoef]
+    uint32_t taps[2][2] = {{4, 4}, {4, 4}};        // [luma/chroma][h, v]
+    bool tiled[2] = {false, false};
+};
+void check_place_params(const mx_video_place_params& p);                        // MX_ERR_INVALID outside what the header states (all that does not depend on the input)
+const char* place_input_error(const DFrame* in, const mx_video_place_params& p);   // nullptr, or why the placer cannot take this frame under p
+std::shared_ptr<const PlaceTables> make_place_tables(const DFrame* in, const mx_video_place_params& p);
+bool place_tables_fit(const PlaceTables& t, const DFrame* in, const mx_video_place_params& p);
+// `in` placed under p into `out` (yuva420p of the canvas size, contents undefined: every byte of its four planes is written), asynchronous on s
+void place_into(DFrame* in, const mx_video_place_params& p, const PlaceTables& t, DFrame* out, hipStream_t s);
+
 // ---- exact rationals: MediaTime / MediaDuration (util/src/time.rs:9-75, num_rational::Ratio<i64>) ----
 struct Rational {
     int64_t num = 0, den = 1;

@@ -350,6 +350,25 @@ def graph_set_video_source_key(g, node, params):
     check(lib.mx_graph_set_video_source_key(g._h, node, C.byref(params) if params is not None else None))
 
 
+def PlaceParams(canvas_w, canvas_h, dst_x, dst_y, dst_w, dst_h, crop=None) -> abi.VideoPlaceParams:
+    """mx_video_place_params: the crop (x, y, w, h) of the input -- None: the whole frame -- stretched into the rectangle (dst_x, dst_y, dst_w, dst_h) of a transparent
+    canvas_w x canvas_h canvas; every number even, the rectangle may reach beyond the canvas"""
+    cx, cy, cw, ch = crop if crop is not None else (0, 0, 0, 0)
+    return abi.VideoPlaceParams(int(canvas_w), int(canvas_h), int(cx), int(cy), int(cw), int(ch), int(dst_x), int(dst_y), int(dst_w), int(dst_h))
+
+
+def place(src: DFrame, params, stream=None) -> DFrame:
+    """mx_video_place: a crop of a yuv420p or yuva420p frame resampled into a rectangle of a NEW yuva420p canvas, coverage 0 outside the rectangle"""
+    h = C.c_void_p()
+    check(lib.mx_video_place(src._h, C.byref(params), C.byref(h), stream))
+    return DFrame(handle=h.value, stream=stream)
+
+
+def graph_set_video_source_place(g, node, params):
+    """The SOURCE_VIDEO node delivers its frames placed, after the key where one is set (mx_graph_set_video_source_place); params None removes the transform."""
+    check(lib.mx_graph_set_video_source_place(g._h, node, C.byref(params) if params is not None else None))
+
+
 class VideoMixer:
     """mx_video_mixer_*: VideoMixer::run_tick on device-resident frames (src/module/video_mixer.rs)."""
 
