@@ -248,6 +248,10 @@ int mx_graph_debug_tail_releases(mx_graph* g, uint64_t* gated, uint64_t* at_once
 #define MX_EQ_LAUNCH_CONTROL_TILE 5u   /* speculative chunks, tiled kernel with a control tile (an Amplifier modulated by a buffer) */
 #define MX_EQ_LAUNCH_SCAN 6u           /* MX_FLAG_EQ_FAST: the time-parallel scan */
 int mx_graph_debug_eq_launch(mx_graph* g, uint32_t out[5]);
+/* DEBUG: *rows = 1 if some wave of the first EqThree launch group's last launch evaluated its inline Envelope in the ROW form (the tiled kernel, at most two waves per
+ * SIMD: a control tile the wave fills itself, ramping rows evaluated row by row), else 0 -- another form was launched (MX_EQ_ENV_ROWS=0, three or four waves per SIMD,
+ * ragged ticks, no inline Envelope), or no tick of any wave had a ramping row beside none of the general form.  Synchronises.  Tests use it to know the row form ran. */
+int mx_graph_debug_eq_env_rows(mx_graph* g, uint32_t* rows);
 
 /* Feed a SOURCE_* node: n_ticks consecutive tick buffers (SPT mono / 2*SPT interleaved stereo f32). */
 int mx_graph_write_source(mx_graph* g, uint32_t node, const float* host_samples, size_t n_ticks);

@@ -120,6 +120,7 @@ _proto("mx_graph_eq_spec_stats", C.c_int, C.c_void_p, C.POINTER(C.c_uint64), C.P
 _proto("mx_graph_debug_eq_records", C.c_int, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t))
 _proto("mx_graph_debug_tail_releases", C.c_int, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64))
 _proto("mx_graph_debug_eq_launch", C.c_int, C.c_void_p, C.POINTER(C.c_uint32))
+_proto("mx_graph_debug_eq_env_rows", C.c_int, C.c_void_p, C.POINTER(C.c_uint32))
 _proto("mx_graph_eq_repair_stats", C.c_int, C.c_void_p, C.POINTER(C.c_uint64))
 _proto("mx_graph_write_source", C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t)
 _proto("mx_graph_bind_source_device", C.c_int, C.c_void_p, C.c_uint32, C.c_void_p)
@@ -586,6 +587,12 @@ class Graph:
         v = (C.c_uint32 * 5)()
         check(lib.mx_graph_debug_eq_launch(self._h, v))
         return {"form": EQ_LAUNCH.get(v[0], str(v[0])), "super_block": int(v[1]), "n_chunks": int(v[2]), "chunk": int(v[3]), "warm": int(v[4])}
+
+    def debug_eq_env_rows(self) -> bool:
+        """mx_graph_debug_eq_env_rows: did some wave of the first EqThree group's last launch take the row form of the inline Envelope (synchronises)"""
+        v = C.c_uint32()
+        check(lib.mx_graph_debug_eq_env_rows(self._h, C.byref(v)))
+        return bool(v.value)
 
     def debug_eq_records(self):
         """-> (device pointer, bytes) of the first EqThree group's chunk records of the last speculative launch (mx_graph_debug_eq_records)"""

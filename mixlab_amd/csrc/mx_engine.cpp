@@ -331,6 +331,7 @@ Graph::Graph(const mx_node* nodes, size_t n_nodes, const mx_edge* edges, size_t 
     // the bank (140 us instead of 9) with the EqThree launch waiting behind it.  MX_OVERLAP_AUTO=0 turns the automatism off; results are bit-identical either way.
     { const char* const sm = getenv("MX_SIN_MODE"); sin_mode_ = sm ? atoi(sm) : 0; }   // (A/B and tests: mx_k_stream.hip SIN_MODE)
     { const char* const gt = getenv("MX_TAIL_GATE_TEST"); gate_test_ = gt && atoi(gt); }
+    { const char* const er = getenv("MX_EQ_ENV_ROWS"); eq_env_rows_ = !(er && atoi(er) == 0); }   // (A/B, read per graph: tests build both kinds in one process)
     bool overlap_auto = false;
     {
         const char* const ae = getenv("MX_OVERLAP_AUTO");   // read per graph: tests build both kinds in one process
@@ -1250,7 +1251,11 @@ void Graph::run_span(uint64_t t0, size_t fpc, uint32_t call_off, uint32_t n_call
                         if (!gate_flag_.p) { gate_flag_.alloc(64); hip_check(hipMemset(gate_flag_.p, 0, 64), "hipMemset"); }
                         r.started = (uint32_t*)gate_flag_.p; r.started_seq = ++gate_seq_; gate_armed_ = true;
                     }
-                    const bool opens_gate = launch_eq_three_spec((const EqDesc*)desc_of(g), (EqState*)g.state.p, n, r, plan, g.eq_mode, g.spec.p, (uint64_t*)eq_stats_.p, stream_, launch);
+                    if (first_eq) {   // (mx_graph_debug_eq_env_rows: the launch's number, stored by the waves that take the row form)
+                        if (!eq_rows_flag_.p) { eq_rows_flag_.alloc(64); hip_check(hipMemset(eq_rows_flag_.p, 0, 64), "hipMemset"); }
+                        r.env_rows = (uint32_t*)eq_rows_flag_.p; r.env_rows_seq = ++eq_rows_seq_;
+                    }
+                    const bool opens_gate = launch_eq_three_spec((const EqDesc*)desc_of(g), (EqState*)g.state.p, n, r, plan, g.eq_mode, g.spec.p, (uint64_t*)eq_stats_.p, stream_, launch, eq_env_rows_);
                     if (!opens_gate && !gate_test_) gate_armed_ = false;   // the direct form never stores the flag: a gate would spin to its time limit before the bank starts (MX_TAIL_GATE_TEST: tests of that bounded spin)
                     if (deferred_.pending) flush_deferred_tail(true);     // run k's Mixer bank: behind the gate this launch opens
                 } else {
@@ -1278,7 +1283,10 @@ void Graph::run_span(uint64_t t0, size_t fpc, uint32_t call_off, uint32_t n_call
                 launch_eq_three_scan((const EqDesc*)desc_of(g), (EqState*)g.state.p, n, r, (const EqScanTab*)eq_tabs_.p, sp, pp, stream_);
                 launch[0] = MX_EQ_LAUNCH_SCAN; launch[2] = sp.n_split; launch[3] = (uint32_t)sp.span; launch[4] = (uint32_t)sp.warm;
             }
-            if (first_eq) { std::copy(launch, launch + 5, eq_launch_); first_eq = false; }
+            if (first_eq) {
+                std::copy(launch, launch + 5, eq_launch_); first_eq = false;
+                if (!r.env_rows) ++eq_rows_seq_;   // a launch of another form: the flag keeps an older launch's number
+            }
             break;
         }
         case MX_KIND_FM_SINE: launch_fm_sine((const FmDesc*)desc_of(g), n, gf, t0, sample_rate_, stream_, sin_mode_); break;
@@ -1733,6 +1741,14 @@ void* Graph::debug_eq_records(size_t* bytes) const {
         if (g.kind == MX_KIND_EQ_THREE && g.spec.p) { if (bytes) *bytes = g.spec.bytes; return g.spec.p; }
     if (bytes) *bytes = 0;
     return nullptr;
+}
+
+bool Graph::eq_env_rows() {
+    if (!eq_rows_flag_.p || !eq_rows_seq_) return false;
+    sync();
+    uint32_t v = 0;
+    hip_check(hipMemcpy(&v, eq_rows_flag_.p, sizeof v, hipMemcpyDeviceToHost), "hipMemcpy(eq env rows)");
+    return v == eq_rows_seq_;
 }
 
 float* Graph::output_ptr(uint32_t node, uint32_t port, size_t* fpf, bool stream_ordered_consumer) {

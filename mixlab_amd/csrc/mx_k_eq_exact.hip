@@ -22,6 +22,7 @@
 #include <algorithm>
 #include <cmath>
 
+#include "mx_common.hpp"
 #include "mx_k_eq_common.hpp"
 
 namespace mx {
@@ -152,16 +153,29 @@ __device__ __forceinline__ EnvLane env_lane_coeffs(const EnvParams& p, const Env
     e.general = (!nice || (c.tag != 0u && ((((d0 + n) >> 32) != 0) || (off && !off_ok)))) ? 1u : 0u;
     return e;
 }
-// amplifier depth() for sample k of the span (branch-free form; `e.general` lanes are handled by the caller)
+// The Envelope's f32 output (envelope.rs:117) `dt` samples into the lane's phase, from its coefficients (`e.general` lanes are handled by the caller).
+// PH says what the caller knows about the lanes that run it TOGETHER:
+//   ENVP_ANY      nothing: lanes in different phases side by side (the lockstep form) -- branch-free, every lane executes every operation;
+//   ENVP_OFF      every lane is Off or Initial: the identities proven above are dropped (ms - 0.0, 0.0 + p), and the attack select, which only an On lane takes;
+//   ENVP_ON       every lane is On: the select's condition loses its `on &&`;
+//   ENVP_ON_LATE  every lane is On and at or beyond attack_ms (the caller has evaluated `ms < attack_ms` at an earlier sample of the same phase and found it false;
+//                 ms does not decrease with the distance: a correctly rounded quotient times a constant): the select returns `val`, the ramp is not evaluated.
+// The operations that remain are the same expressions on the same values in every form: no rounding moves.
+enum { ENVP_ANY = 0, ENVP_OFF = 1, ENVP_ON = 2, ENVP_ON_LATE = 3 };
+template <bool FC, int PH = ENVP_ANY>
+__device__ __forceinline__ float env_lane_cc(const EnvParams& p, double A, double B, double k, double m0, bool on, uint32_t dt, double sr, double rsr) {
+    const double ms = ms_of_u32(dt, sr, rsr);
+    const double tt = k * (PH == ENVP_OFF ? ms : ms - m0);
+    const double c = __builtin_fmin(tt, 1.0);                  // clamp()'s upper bound (envelope.rs:21-22); no NaN here, see above
+    const double val = PH == ENVP_OFF ? B * (1.0 - c) : mul_add<FC>(B, 1.0 - c, A);
+    if (PH == ENVP_OFF || PH == ENVP_ON_LATE) return (float)val;
+    const double att = p.inv_attack * ms;
+    return (float)(((PH == ENVP_ON || on) && ms < p.attack_ms) ? att : val);   // Envelope stores f32 (envelope.rs:117)
+}
+// amplifier depth() for sample k of the span (the lockstep form)
 template <bool FC>
 __device__ __forceinline__ double env_lane_depth(const EnvParams& p, const EnvLane& e, uint32_t k, double one_minus, double mod_depth, double sr, double rsr) {
-    const double ms = ms_of_u32(e.dt0 + k, sr, rsr);
-    const double tt = e.k * (ms - e.m0);
-    const double c = __builtin_fmin(tt, 1.0);                  // clamp()'s upper bound (envelope.rs:21-22); no NaN here, see above
-    const double val = mul_add<FC>(e.B, 1.0 - c, e.A);
-    const double att = p.inv_attack * ms;
-    const double a = (e.on && ms < p.attack_ms) ? att : val;
-    const float cc = (float)a;                                 // Envelope stores f32 (envelope.rs:117)
+    const float cc = env_lane_cc<FC>(p, e.A, e.B, e.k, e.m0, e.on != 0u, e.dt0 + k, sr, rsr);
     return amp_depth<FC>(one_minus, mod_depth, (double)cc);    // amplifier.rs:71-73
 }
 
@@ -639,6 +653,74 @@ __device__ __forceinline__ void eq_tile_compute(const EqK& K, float* buf, const 
     }
 }
 
+// ROW FORM of the inline Envelope (48 kHz-style ticks, one tile, at most two waves per SIMD).  In the lockstep form (ENVK == 2) one ramping lane makes all 64 evaluate
+// the closed form for every sample of the tick, flat lanes included -- with gates toggling every 30 ticks and chunks 16 ticks apart some lane of a wave is always in a
+// ramp, so every wave-tick paid it.  Here the wave keeps a CONTROL TILE beside the input's (the layout the EQM_AMP_CTL compute already consumes): at the tick's start
+// every lane fills its own row with its constant -- the saturated value of the same formula, which is what the lockstep form computed for a flat lane sample by sample --
+// and per super-block only the rows that ramp are evaluated again, ROW BY ROW: two rows per pass, lanes 0-31 the 32 samples of one and lanes 32-63 those of another.
+// Rows are paired within their phase class, so a pass knows its phase (env_lane_cc): On rows whose tick begins at or beyond attack_ms (ms grows with the distance, so
+// the whole tick lies there), On rows that may still be in the attack, Off rows.  What a pass needs of a row beyond the wave-uniform parameters is the row's distance,
+// its off_amplitude (Off) and where the row lies in the tile: at the tick's start every ramping lane writes that entry to a table in LDS at its RANK within its class
+// (the classes one behind the other, each padded to a whole pair with a copy of its last row: that half pass writes the same values twice), and pass p reads entries
+// 2p and 2p + 1 -- no per-pass search of the row masks, no address arithmetic beyond one add.
+struct EqEnvRow { double off_amp; uint32_t dtk /* dt0 - k0: the distance of chunk-relative sample 0 */; uint32_t where /* byte offset of the row in the tile | its swizzle << 4 */; };
+enum { EQ_ENV_ROW_ENTRIES = 68 };   // 64 rows and a padding entry per class
+// REGISTER NOTE for the ROWS instantiations (re-check after a toolchain change; the figures are in profiles/env_rows/README.md, "Disassembly"): eq_uniform_ptr below and
+// the empty `asm volatile("; my ..." : "+v"(x))` statements in k_eq_three_spec_tiled only steer the register allocator -- the instance's bases (tick table, chunk records,
+// output) stay in SGPRs, and the lane's chunk begin and record address are re-derived where they are used instead of living through every loop.  With them the exact
+// mono-dup kernel has 128 VGPRs and no scratch (without: 6 VGPRs spilled, 28 B per lane), the contracted one 2 spilled / 12 B as the lockstep kernel of that shape
+// (without: 13 / 40 B), the interleaved ones 119 / 121 VGPRs.  Removing them changes no result, only those figures.
+// a wave-uniform pointer, said to be one: it stays in SGPRs instead of a VGPR pair per lane
+template <typename T> __device__ __forceinline__ T* eq_uniform_ptr(T* p) {
+    const uint64_t v = (uint64_t)p;
+    return (T*)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v));
+}
+__device__ __forceinline__ int eq_rank64(uint64_t m) { return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); }   // set bits of m below my lane
+struct EqEnvRowPlan { int p_late, p_early, p_off; };   // passes per class (wave-uniform)
+// the tick's table: called by every lane of the wave; `mine`: my row ramps this tick
+__device__ __forceinline__ EqEnvRowPlan eq_env_rows_plan(const EqK& K, EqEnvRow* tab, const EnvLane& el, const bool mine, const int lane) {
+    const bool on = el.on != 0u;
+    const bool early = on && ms_of_u32(el.dt0, K.sr, K.rsr) < K.env.attack_ms;    // the select's own condition at the tick's first sample
+    const uint64_t m_late = __ballot(mine && on && !early), m_early = __ballot(mine && early), m_off = __ballot(mine && !on);
+    const int n_late = __builtin_popcountll(m_late), n_early = __builtin_popcountll(m_early), n_off = __builtin_popcountll(m_off);
+    const EqEnvRowPlan plan{(n_late + 1) >> 1, (n_early + 1) >> 1, (n_off + 1) >> 1};
+    const int first = !on ? 2 * (plan.p_late + plan.p_early) : (early ? 2 * plan.p_late : 0);
+    const int n = !on ? n_off : (early ? n_early : n_late);
+    const int rank = eq_rank64(!on ? m_off : (early ? m_early : m_late));
+    if (mine) {
+        const EqEnvRow e{el.B, el.dt0 - el.k0, (uint32_t)(lane * 128) | ((uint32_t)EqTileGeo<32>::sw(lane) << 4)};
+        tab[first + rank] = e;
+        if (rank == n - 1 && (n & 1)) tab[first + rank + 1] = e;
+    }
+    return plan;
+}
+template <bool FC, int PH>
+__device__ __forceinline__ const EqEnvRow* eq_env_row_passes(const EqK& K, char* cbuf, const EqEnvRow* e, const int n, const uint32_t soi, const uint32_t slot) {
+    auto pass = [&](const EqEnvRow& row) {
+        const float cc = PH == ENVP_OFF ? env_lane_cc<FC, ENVP_OFF>(K.env, 0.0, row.off_amp, K.env.inv_release, 0.0, false, row.dtk + soi, K.sr, K.rsr)
+                                        : env_lane_cc<FC, PH>(K.env, K.env.sustain, K.env.one_minus_sustain, K.env.inv_decay, K.env.attack_ms, true, row.dtk + soi, K.sr, K.rsr);
+        *reinterpret_cast<float*>(cbuf + (row.where ^ slot)) = cc;            // the swizzle eq_tile_compute reads with
+    };
+    // two passes side by side: both pairs' entries are asked for first, and the two evaluations are independent instruction streams
+    int q = 0;
+#pragma clang loop vectorize(disable) interleave(disable) unroll(disable)
+    for (; q + 1 < n; q += 2, e += 4) { const EqEnvRow r0 = e[0], r1 = e[2]; pass(r0); pass(r1); }
+    if (q < n) { const EqEnvRow r0 = e[0]; pass(r0); e += 2; }
+    return e;
+}
+// the ramping rows' samples of the super-block that begins at chunk-relative sample `so`, into the control tile
+template <int SB, bool FC>
+__device__ __forceinline__ void eq_env_rows(const EqK& K, float* cbuf, const EqEnvRow* tab, const EqEnvRowPlan& plan, const int lane, const int so) {
+    static_assert(SB == 32, "a row is the 32 lanes of half a wave");
+    const int i = lane & 31;
+    const uint32_t soi = (uint32_t)(so + i);                                  // my sample's chunk-relative index
+    const uint32_t slot = (uint32_t)(((i >> 2) << 4) | ((i & 3) << 2));      // its byte offset in an unswizzled row: piece << 4 | element << 2
+    const EqEnvRow* e = tab + (lane >> 5);
+    e = eq_env_row_passes<FC, ENVP_ON_LATE>(K, reinterpret_cast<char*>(cbuf), e, plan.p_late, soi, slot);
+    e = eq_env_row_passes<FC, ENVP_ON>(K, reinterpret_cast<char*>(cbuf), e, plan.p_early, soi, slot);
+    eq_env_row_passes<FC, ENVP_OFF>(K, reinterpret_cast<char*>(cbuf), e, plan.p_off, soi, slot);
+}
+
 // The samples of a super-block whose chunk-relative index lies in [i_lo, i_hi), one at a time, in the general Envelope form: the first super-block of a chunk (the
 // samples before index 0 are still warm-up: OUT = false, the recurrence only), and the one or two super-blocks in which a tick ends (the samples before the boundary
 // with the old tick's state, the rest with the new one's).  `so` is the chunk-relative index of the lane's first tile sample -- per lane with aligned rows; the bounds
@@ -710,24 +792,29 @@ __device__ __forceinline__ void eq_tile_store(const EqTileCtx& c, const float* b
 // 2048 ticks in 1 024 waves: 60 SIMDs with two waves and 60 with none (tools/wave_times.py reads every wave's HW_ID and its time in the launch out of the chunk records);
 // the launch lasts as long as its most crowded SIMD: 0.99 ms where the same work spread evenly takes 0.71.
 enum { EQ_WPB = 4 };
-template <int SB, int KMODE, int KSTEREO, bool FC, int NBUF = 2, bool RT = false>
+template <int SB, int KMODE, int KSTEREO, bool FC, int NBUF = 2, bool RT = false, bool ROWS = false /* the row form of the inline Envelope: eq_env_rows */>
 __global__ __launch_bounds__(64 * EQ_WPB, 4) void k_eq_three_spec_tiled(const EqDesc* __restrict__ descs, const EqState* __restrict__ states, EqRun r, EqSpecPlan plan,
                                                                          uint32_t waves_per_inst, EqChunkRec* __restrict__ recs, uint32_t n_waves) {
     extern __shared__ __attribute__((aligned(16))) float eq_tiles_all[];   // [EQ_WPB][tiles per wave][TILE]
     constexpr int EQ_SB = SB, EQ_TILE = EqTileGeo<SB>::TILE;
-    constexpr int EQ_TILES_PER_WAVE = (NBUF == 2 || KMODE == EQM_AMP_CTL) ? 2 : 1;
+    static_assert(!ROWS || (KMODE == EQM_AMP_ENV && !RT && NBUF == 1 && SB == 32), "the row form: the whole-tick inline Envelope over one whole-line tile");
+    constexpr int EQ_TILES_PER_WAVE = (NBUF == 2 || KMODE == EQM_AMP_CTL || ROWS) ? 2 : 1;
+    constexpr int EQ_WAVE_FLOATS = EQ_TILES_PER_WAVE * EQ_TILE + (ROWS ? EQ_ENV_ROW_ENTRIES * (int)(sizeof(EqEnvRow) / sizeof(float)) : 0);   // (row form: input tile, control tile, row table)
     const uint32_t t_enter = (uint32_t)__builtin_amdgcn_s_memtime();   // (a wave's life inside the launch, kept in its records' padding: mx_graph_debug_eq_records, tools/wave_times.py)
     // (Graph's tail gate: workgroups are placed in order, so when the last one runs every other one of this launch has its place)
     if (r.started && blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) __hip_atomic_store(r.started, r.started_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const uint32_t wib = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave in the group: wave-uniform, so that everything derived from it stays in SGPRs
     const uint32_t wave_id = blockIdx.x * EQ_WPB + wib;
     if (wave_id >= n_waves) return;
-    float* const eq_tiles = eq_tiles_all + wib * (EQ_TILES_PER_WAVE * EQ_TILE);
-    const uint32_t inst = wave_id / waves_per_inst;
+    float* const eq_tiles = eq_tiles_all + wib * EQ_WAVE_FLOATS;
+    const uint32_t inst = ROWS ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(wave_id / waves_per_inst)) : wave_id / waves_per_inst;   // (ROWS: said to be wave-uniform, so that what derives from it -- the tick table's and the records' bases -- stays in SGPRs)
     const EqDesc& d = descs[inst];
     const EqK K = eq_constants(d, r);
     EqTileCtx c;
     c.in = d.in; c.out = d.out;
+    if constexpr (ROWS) {   // the output's base in SGPRs (it is wave-uniform; as a flat address it took two VGPRs through every loop)
+        c.out = eq_uniform_ptr(d.out);
+    }
     c.chunk0 = (wave_id % waves_per_inst) * 64u; c.n_chunks = plan.n_chunks; c.C = plan.chunk; c.F = (uint32_t)r.frames;
     c.lane = (int)(threadIdx.x & 63u);
     eq_tile_bases<SB, RT>(c);
@@ -758,9 +845,12 @@ __global__ __launch_bounds__(64 * EQ_WPB, 4) void k_eq_three_spec_tiled(const Eq
     }
     uint32_t xmin = 0xffffffffu, xmax = 0u;
     const EnvTick* ticks = r.ticks ? r.ticks + (size_t)inst * r.n_calls : nullptr;
+    if constexpr (ROWS) ticks = eq_uniform_ptr(ticks);
     EnvTick cur{}; EnvLane el{};
     const bool nice = env_params_nice(d.env);
-    EqChunkRec* rec = recs + (size_t)inst * plan.n_chunks + (active ? j : 0);
+    EqChunkRec* rec = ROWS ? nullptr : recs + (size_t)inst * plan.n_chunks + (active ? j : 0);   // (ROWS: derived where it is used, from the instance's uniform base)
+    EqChunkRec* const recs_inst = ROWS ? eq_uniform_ptr(recs + (size_t)inst * plan.n_chunks) : nullptr;
+    bool rows_ran = false;   // (ROWS, wave-uniform) some tick of this wave took the row form: mx_graph_debug_eq_env_rows
 
     // One loop per PHASE, not one loop that picks its phase every step: the warm-up, and then -- per tick -- the one epilogue form the tick
     // needs.  With a single loop over the super-blocks that dispatched to the four compute variants, the compiler gave each variant its
@@ -806,6 +896,7 @@ __global__ __launch_bounds__(64 * EQ_WPB, 4) void k_eq_three_spec_tiled(const Eq
         float* buf = begin_sb(g);
         eq_tile_compute<SB, EQM_PLAIN, 0, true, FC>(K, buf, c.lane, (g - n_warm) * EQ_SB - row_shift, warm_from, cur, el, s, xmin, xmax);
     }
+    if constexpr (ROWS) { uint32_t je = active ? j : 0u; asm volatile("; my record %0" : "+v"(je)); rec = recs_inst + je; }
     if (!RT && active) {   // first sample of my chunk: record where the warm-up took me (chunks that started at the stream's start: the exact state)
 #pragma unroll
         for (int k = 0; k < 4; ++k) { rec->start[k] = s.lo[k]; rec->start[4 + k] = s.hi[k]; }
@@ -872,15 +963,40 @@ __global__ __launch_bounds__(64 * EQ_WPB, 4) void k_eq_three_spec_tiled(const Eq
         while (g < total) {
             // a new tick (wave-uniform): its Envelope state, per lane
             const int so0 = (g - n_warm) * EQ_SB;
-            const size_t tk = ((size_t)begin + (size_t)so0) / r.fpc;
+            uint32_t jt = j;
+            if constexpr (ROWS) asm volatile("; my chunk %0" : "+v"(jt));   // (re-derived per tick from the chunk number: `begin` need not stay in registers across the super-block loops)
+            const long long begin_t = (long long)jt * c.C;
+            const size_t tk = ((size_t)begin_t + (size_t)so0) / r.fpc;
             cur = ticks[tk < r.n_calls ? tk : r.n_calls - 1];
-            const uint64_t t = r.t0 + (uint64_t)begin + (uint64_t)so0;
+            const uint64_t t = r.t0 + (uint64_t)begin_t + (uint64_t)so0;
             el = env_lane_coeffs(K.env, cur, t, r.fpc, nice);
-            el.k0 = (uint32_t)so0; el.t_chunk = r.t0 + (uint64_t)begin;
+            el.k0 = (uint32_t)so0; el.t_chunk = r.t0 + (uint64_t)begin_t;
             const int envk = __ballot(active && so0 < len && el.general != 0u) != 0ull ? 3 : (__ballot(active && so0 < len && el.flat == 0u) == 0ull ? 1 : 2);
             const int g_end = g + sb_per_tick < total ? g + sb_per_tick : total;
             if (envk == 1) {
                 for (; g < g_end; ++g) { float* buf = begin_sb(g); const int so = (g - n_warm) * EQ_SB; eq_tile_compute<SB, KMODE, 1, false, FC>(K, buf, c.lane, so, len, cur, el, s, xmin, xmax); eq_tile_store<SB, KSTEREO != 0>(c, buf, so); }
+            } else if (ROWS && envk == 2) {
+                if constexpr (ROWS) {
+                    // the tick's table of ramping rows; my row of the control tile filled with my constant
+                    float* const cbuf = eq_tiles + EQ_TILE;
+                    EqEnvRow* const tab = reinterpret_cast<EqEnvRow*>(eq_tiles + 2 * EQ_TILE);
+                    const EqEnvRowPlan rows = eq_env_rows_plan(K, tab, el, active && so0 < len && el.flat == 0u, c.lane);
+                    const float cc = env_lane_cc<FC>(K.env, el.A, el.B, el.k, el.m0, el.on != 0u, el.dt0, K.sr, K.rsr);
+                    const f4v cc4 = {cc, cc, cc, cc};
+#pragma unroll
+                    for (int q = 0; q < EQ_SB / 4; ++q) reinterpret_cast<f4v*>(cbuf + c.lane * EQ_SB)[q] = cc4;
+                    rows_ran = true;
+                    for (; g < g_end; ++g) {
+                        const int so = (g - n_warm) * EQ_SB;
+                        // (begin_sb with the row passes between the DMA's issue and the wait for it: the wave fills its own round trip)
+                        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                        eq_tile_issue<SB>(c, eq_tiles, so);
+                        eq_env_rows<SB, FC>(K, cbuf, tab, rows, c.lane, so);
+                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                        eq_tile_compute<SB, EQM_AMP_CTL, 0, false, FC>(K, eq_tiles, c.lane, so, len, cur, el, s, xmin, xmax, cbuf);
+                        eq_tile_store<SB, KSTEREO != 0>(c, eq_tiles, so);
+                    }
+                }
             } else if (envk == 2) {
                 for (; g < g_end; ++g) { float* buf = begin_sb(g); const int so = (g - n_warm) * EQ_SB; eq_tile_compute<SB, KMODE, 2, false, FC>(K, buf, c.lane, so, len, cur, el, s, xmin, xmax); eq_tile_store<SB, KSTEREO != 0>(c, buf, so); }
             } else {
@@ -895,6 +1011,12 @@ __global__ __launch_bounds__(64 * EQ_WPB, 4) void k_eq_three_spec_tiled(const Eq
             eq_tile_store<SB, KSTEREO != 0>(c, buf, so);
         }
     }
+    if constexpr (ROWS) {   // (likewise: the record's address is re-derived here, not carried through the loops)
+        uint32_t je = active ? j : 0u;
+        asm volatile("; my record %0" : "+v"(je));
+        rec = recs_inst + je;
+    }
+    if (ROWS && rows_ran && r.env_rows && c.lane == 0) __hip_atomic_store(r.env_rows, r.env_rows_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (active) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) { rec->end[k] = s.lo[k]; rec->end[4 + k] = s.hi[k]; }
@@ -1464,7 +1586,7 @@ int eq_epilogue_mode(uint32_t epi, uint32_t flags, bool has_ctl) {
 }
 
 bool launch_eq_three_spec(const EqDesc* d, EqState* st, uint32_t n, const EqRun& r_in, const EqSpecPlan& plan_in, int uniform_mode, void* scratch, uint64_t* stats, hipStream_t s,
-                          uint32_t* launch) {
+                          uint32_t* launch, bool env_rows) {
     if (!n || !r_in.frames) return false;
     // A stream that is not whole pieces of four samples (735 t frames at 44.1 kHz with t not a multiple of 4): the tiled kernel runs the frames up to the last
     // multiple of four, and the proof / repair kernel -- which ends up holding the exact state there -- walks the one to three samples left (`tail`).
@@ -1494,7 +1616,13 @@ bool launch_eq_three_spec(const EqDesc* d, EqState* st, uint32_t n, const EqRun&
     // 0.311 / 0.476 with one tile; from two waves per SIMD on one whole-line tile is the faster form: 1024 x 2048 in 128 chunks 4.28 against 4.36 ms exact, 3.85 against 4.14
     // contracted -- the contracted order's two-tile form is the half-line one and pays its 1.44x source bytes there)
     const int sb_auto = (size_t)n * wpi <= 1024 ? (r.fc ? 16 : 32) : 321;
-    const int sb = sb_env == 0 ? sb_auto : (!r.fc && sb_env == 32) ? 32 : (sb_env == 16 ? 16 : 321);   // samples per lane per super-block
+    const int sb = sb_env == 0 ? sb_auto : (!r.fc && sb_env == 32) ? 32 : (sb_env == 16 ? 16 : 321);   // samples per lane per super-block (321: one whole-line tile)
+    // The ROW FORM of the inline Envelope (eq_env_rows) where the plan puts at most two waves on a SIMD AND the one-tile form is the choice anyway (more than one wave
+    // per SIMD, or MX_EQ_SPEC_SB=321): one whole-line tile for the input, a control tile the wave fills itself and the row table, 17 KiB of LDS per wave -- two
+    // workgroups of four waves per CU, which is all such a plan asks for (the headline: 2 048 waves).  A wave alone on its SIMD keeps its two tiles: forced into the
+    // row form, 1024 strips x 64 ticks took 0.312 ms against 0.278 (the warm-up, longer than the one-tick chunk, has no row passes to fill its round trips with).
+    // Plans with three or four waves per SIMD keep the lockstep form.  MX_EQ_ENV_ROWS=0 (A/B, read per graph): the lockstep form.
+    const bool rows = env_rows && !no_tiles && (um == 6 || um == 7) && sb == 321 && (size_t)n * wpi <= 2048 && r.fpc % 32 == 0;
     // ragged ticks (RT instantiations): an inline Envelope at a rate whose tick is not whole super-blocks (44.1 kHz: 735) -- chunks of whole ticks, multiples of 4 samples
     // (ticks of at least 64 samples: the RT kernel's boundary walk looks at the current and the next tick only -- with a super-block of 32 samples and row shifts up to 28
     // a shorter tick could end twice inside one block; shorter ragged ticks take the direct form)
@@ -1527,6 +1655,15 @@ bool launch_eq_three_spec(const EqDesc* d, EqState* st, uint32_t n, const EqRun&
 #define MX_GRT(S, F) hipLaunchKernelGGL((k_eq_three_spec_tiled<32, EQM_AMP_ENV, S, F, 1, true>), dim3(nwg), dim3(64 * EQ_WPB), EQ_WPB * lds1, s, d, (const EqState*)st, r, plan, wpi, recs, nwv)
             if (um == 6) { if (r.fc) MX_GRT(0, true); else MX_GRT(0, false); } else { if (r.fc) MX_GRT(1, true); else MX_GRT(1, false); }
 #undef MX_GRT
+        } else
+        if (rows) {
+            const size_t lds_r = (size_t)2 * 64 * 32 * sizeof(float) + EQ_ENV_ROW_ENTRIES * sizeof(EqEnvRow);
+            // 68 KiB per workgroup is above the 64 KiB a launch may ask for unannounced: said before every such launch, for the device that is current (a process drives several)
+#define MX_GRW(S, F) { auto* const kern = k_eq_three_spec_tiled<32, EQM_AMP_ENV, S, F, 1, false, true>; \
+                       hip_check(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(EQ_WPB * lds_r)), "hipFuncSetAttribute(EqThree row form: dynamic LDS)"); \
+                       hipLaunchKernelGGL(kern, dim3(nwg), dim3(64 * EQ_WPB), EQ_WPB * lds_r, s, d, (const EqState*)st, r, plan, wpi, recs, nwv); }
+            if (um == 6) { if (r.fc) MX_GRW(0, true) else MX_GRW(0, false) } else { if (r.fc) MX_GRW(1, true) else MX_GRW(1, false) }
+#undef MX_GRW
         } else
         switch (um) {
         case 0: MX_GT(EQM_PLAIN, 0); break;     case 1: MX_GT(EQM_PLAIN, 1); break;

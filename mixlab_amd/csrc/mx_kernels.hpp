@@ -106,7 +106,8 @@ size_t envelope_scratch_bytes(uint32_t n, size_t frames);
 void launch_env_ticks(const EnvTickDesc* d, uint32_t n, const GateBits& gates, uint32_t n_calls, size_t fpc, uint64_t t0, double sample_rate, EnvTick* ticks, hipStream_t s, bool fc = false);
 // what every EqThree launch needs beyond the descriptors: the per-tick Envelope table (null when no instance folds one)
 struct EqRun { size_t frames; size_t fpc /* samples per tick (call) */; uint32_t n_calls; uint32_t fc /* MX_FLAG_FP_CONTRACT: the contracted order */; uint64_t t0; double sr, rsr /* RN(1 / sr), host */, lo_f, hi_f; const EnvTick* ticks /* [n][n_calls] */;
-               uint32_t* started = nullptr; uint32_t started_seq = 0; /* tiled speculative kernel: its last workgroup stores started_seq there when it starts (every earlier one has been placed by then): Graph's tail gate */ };
+               uint32_t* started = nullptr; uint32_t started_seq = 0; /* tiled speculative kernel: its last workgroup stores started_seq there when it starts (every earlier one has been placed by then): Graph's tail gate */
+               uint32_t* env_rows = nullptr; uint32_t env_rows_seq = 0; /* tiled speculative kernel, row form of the inline Envelope: a wave that took it for some tick stores env_rows_seq there (mx_graph_debug_eq_env_rows) */ };
 // scratch != nullptr: the split-cascade form for few instances (eq_use_poles_split; eq_poles_scratch_bytes of scratch); else one lane per instance
 void launch_eq_three_exact(const EqDesc* d, EqState* st, uint32_t n, const EqRun& r, void* scratch, hipStream_t s);
 bool eq_use_poles_split(uint32_t n, size_t frames);
@@ -124,7 +125,8 @@ void launch_tail_gate(const uint32_t* flag, uint32_t seq, uint32_t limit_us, hip
 int eq_epilogue_mode(uint32_t epi, uint32_t flags, bool has_ctl);   // 0..7: (epilogue kind) * 2 + (stereo store); the specialisation key
 bool launch_eq_three_spec(const EqDesc* d, EqState* st, uint32_t n, const EqRun& r, const EqSpecPlan& plan, int uniform_mode /* 0..7, or -1: mixed */,
                           void* scratch, uint64_t* stats /* [2]: chunks run, chunks repaired */, hipStream_t s,
-                          uint32_t* launch = nullptr /* [5]: what ran, as mx_graph_debug_eq_launch reports it (MX_EQ_LAUNCH_*, super-block, n_chunks, chunk, warm) */);
+                          uint32_t* launch = nullptr /* [5]: what ran, as mx_graph_debug_eq_launch reports it (MX_EQ_LAUNCH_*, super-block, n_chunks, chunk, warm) */,
+                          bool env_rows = true /* false (MX_EQ_ENV_ROWS=0, A/B): the inline Envelope keeps the lockstep form where the row form would be chosen */);
 void eq_plan_split(uint32_t n, size_t frames, double lo_f, double hi_f, EqSplit& sp);
 void launch_fm_sine(const FmDesc* d, uint32_t n, size_t frames, uint64_t t0, double sample_rate, hipStream_t s, int sin_mode /* mx_k_stream.hip SIN_MODE */);
 void launch_mixer(const MixDesc* d, uint32_t n, uint32_t max_ch /* most channels of any mixer in the group */, size_t frames,
