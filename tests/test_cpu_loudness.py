@@ -203,6 +203,22 @@ def test_model_split_anywhere_gives_the_same_records_and_first_ticks_see_silence
     assert (whole["frames"] == f).all() and (whole["channels"] == 2).all()
 
 
+def test_models_run_together_give_each_its_own_records():
+    """run_many does the walks of the taps that share a tick length in one loop over the frames (tests/random_taps.py runs its loudness
+    models that way): mono and stereo taps, two tick lengths, two runs -- every record and every carried state as from run() alone"""
+    rng = np.random.default_rng(77)
+    shapes = [(2, 48000.0, 800), (1, 48000.0, 800), (2, 16000.0, 267), (1, 48000.0, 800), (2, 48000.0, 800)]
+    alone = [lm.LoudnessModel(ch, rate, f, 2, 5) for ch, rate, f in shapes]
+    together = [lm.LoudnessModel(ch, rate, f, 2, 5) for ch, rate, f in shapes]
+    for n in (3, 1, 4):
+        xs = [(rng.standard_normal(n * f * ch) * 1.5).astype(np.float32) for ch, _rate, f in shapes]
+        want = [m.run(x, n) for m, x in zip(alone, xs)]
+        got = lm.run_many(together, xs, n)
+        for a, b, m, w in zip(got, want, together, alone):
+            assert a.tobytes() == b.tobytes() and m.state.tobytes() == w.state.tobytes() and m.e_hist.tobytes() == w.e_hist.tobytes()
+    assert want[0]["ksq"].all() and not np.array_equal(want[0]["ksq"], want[4]["ksq"])
+
+
 def test_window_sums_follow_the_stated_order():
     rate, f, n, m_t, s_t = 48000, 48, 60, 7, 33
     x = (np.random.default_rng(4).standard_normal(n * f) * np.exp2(np.random.default_rng(5).integers(-20, 4, n * f))).astype(np.float32)

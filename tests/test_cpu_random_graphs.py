@@ -9,7 +9,8 @@ import pytest
 import oracle
 from mixlab_amd import abi
 from mixlab_amd.workspace import Workspace
-from test_gpu_random_graphs import FULL_SEEDS, engine_domains, port_types, random_graph
+from random_taps import CLASS_OF, EMITTING, FAULTS, RESETTING, SETS, difference
+from test_gpu_random_graphs import ALL_SETS_RUNS, ALL_SETS_SEEDS, FULL_SEEDS, engine_domains, port_types, random_graph, run_full_graph
 from tick_shapes import by_id
 
 AUDIO_KINDS = {abi.KIND_AMPLIFIER, abi.KIND_ENVELOPE, abi.KIND_EQ_THREE, abi.KIND_FM_SINE, abi.KIND_MIXER, abi.KIND_OSCILLATOR, abi.KIND_PLOTTER,
@@ -128,3 +129,145 @@ def test_oracle_runs_an_output_device_as_a_sink_in_the_engine_run_order():
     og.update_params(od_a, abi.OutputDeviceParams(8, 7, 7, 0))
     og.run_tick(1)
     assert np.all(og.output(amp, 0) == np.float32(1.5))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the random taps of all seven sets (tests/random_taps.py) on the oracle and the models alone: the draws of
+# test_full_random_graph_every_tap_set, what they cover, that there is something to see, and that each way the tap host could be
+# wrong changes the records that test compares
+# ---------------------------------------------------------------------------------------------------------------------------
+def test_full_graphs_and_the_meter_draws_are_unchanged():
+    """random_graph(full=True) and run_full_graph's own stream (default_rng(7000 + seed): meter taps and their params, run lengths,
+    updates, events, lag notes) draw for every existing test id what they drew before the other tap sets got a stream of their own
+    (default_rng(8000 + seed)): the digests were taken before tests/random_taps.py existed.  The second one needs the ports the fused
+    build folds away (the meters are drawn among the others); tests/test_gpu_random_graphs.py asserts that prediction on the device."""
+    h = hashlib.sha256()
+    for shape_id, seed in [("44k1", s) for s in range(64)] + FULL_SEEDS:
+        shape = by_id(shape_id)
+        ws, sources = random_graph(seed, shape.sample_rate, shape.ticks_per_second, full=True)
+        for kind, params in ws.nodes:
+            h.update(bytes([kind])); h.update(abi.params_bytes(params))
+        h.update(repr(sorted(ws.edges)).encode()); h.update(repr(sources).encode())
+    assert h.hexdigest() == "7847646b1e38d2e0bae8cd1d4e045bb068cf35a7970771bf3341f5f304f0538a"
+    h = hashlib.sha256()
+    for shape_id, seed in FULL_SEEDS:
+        drawn = []
+        run_full_graph(shape_id, seed, (), abi.FLAG_EQ_EXACT, collect=drawn)
+        h.update(repr(drawn).encode())
+    assert h.hexdigest() == "3f5021bb53f2c52297929eafd1a5d4e2171a7ddf7869e9fcf42085a75a98a260"
+
+
+_expected = {}
+
+
+def expected(shape_id, seed, fault=None):
+    """(the RandomTaps, [{"run", "ticks", "want": {set: records}}]) of one seed: the oracle and the models alone"""
+    if (seed, fault) not in _expected:
+        runs = []
+        ts = run_full_graph(shape_id, seed, (), abi.FLAG_EQ_EXACT, tap_sets=SETS, n_runs=ALL_SETS_RUNS, fault=fault, collect=runs)
+        if fault is not None:
+            return ts, runs
+        _expected[(seed, fault)] = (ts, runs)
+    return _expected[(seed, fault)]
+
+
+def test_every_set_is_set_again_on_its_own_and_after_a_one_tick_run():
+    empties = 0
+    for shape_id, seed in ALL_SETS_SEEDS:
+        ts, runs = expected(shape_id, seed)
+        assert ALL_SETS_RUNS[0] <= len(runs) < ALL_SETS_RUNS[1] and runs[ts.one_tick_run]["ticks"] == 1 and ts.one_tick_run + 1 < len(runs)
+        assert any(ts.one_tick_run + 1 in ts.plan[name] for name in SETS)
+        assert len({tuple(sorted(ts.plan[name])) for name in SETS}) > 1          # not all at the same runs
+        for name in SETS:
+            assert ts.plan[name] and min(ts.plan[name]) >= 1
+            n_empty = sum(1 for what in ts.plan[name].values() if what == "empty")
+            empties += n_empty
+            if shape_id != "8k_8000":
+                assert sum(1 for ports in ts.orders[name] if not ports) == n_empty, f"{shape_id} {seed}: {name} was left without a tap"
+            assert all(len(set(ports)) == len(ports) <= ts.cap for ports in ts.orders[name])
+    assert empties >= len(SETS)
+
+
+def test_the_taps_cover_every_kind_of_port():
+    """Summed over the seeds, every set taps a Source, an Oscillator or FmSine, an EqThree, an Amplifier, a Mixer, a Fir or Resample, a
+    control line (Trigger or Envelope), a mono and a stereo port, a dup-stored port and a port whose tick is not spt frames -- the stereo
+    field set the stereo ones among them (an EqThree, a Trigger and an Envelope have mono outputs only) -- and no set is given sorted lists only.
+    Most sets also tap an Oscillator's stereo twin, and some the one Mixer without channels these graphs have."""
+    seen = {name: set() for name in SETS}
+    for shape_id, seed in ALL_SETS_SEEDS:
+        ts, _runs = expected(shape_id, seed)
+        for name in SETS:
+            for pt in ts.tapped[name]:
+                seen[name] |= {CLASS_OF[ts.ws.nodes[pt[0]][0]], "mono" if ts.types[pt[0]][pt[1]] == 1 else "stereo"}
+                seen[name] |= {"own_tick"} if ts.frames[pt] != ts.spt else set()
+                seen[name] |= {"dup"} if pt in ts.dup else set()
+                if ts.ws.nodes[pt[0]][0] == abi.KIND_MIXER and not ts.ws.nodes[pt[0]][1]:
+                    seen[name].add("empty_mixer")
+                if ts.ws.nodes[pt[0]][0] == abi.KIND_OSCILLATOR and pt[1] == 1:
+                    seen[name].add("stereo_twin")
+            if any(ports != sorted(ports) for ports in ts.orders[name]):
+                seen[name].add("unsorted")
+    stereo_only = {"source", "oscillator", "amplifier", "mixer", "fir_resample", "stereo", "own_tick", "dup", "unsorted"}
+    for name in SETS:
+        want = stereo_only if name == "stereo" else stereo_only | {"eq", "control", "mono"}
+        assert want <= seen[name], f"{name}: no tap on {sorted(want - seen[name])}"
+    assert sum("empty_mixer" in s for s in seen.values()) >= 2 and sum("stereo_twin" in s for s in seen.values()) >= 5   # (of the seven sets)
+
+
+def something_to_see(name, rec):
+    if rec["ticks"] is None and rec["emitted"] is None:
+        return False
+    if name == "meters":
+        return bool((rec["ticks"]["hold"] > 0).any())
+    if name == "spectra":
+        return bool((rec["ticks"] > 0).any())
+    if name == "loudness":
+        return bool((rec["ticks"]["true_peak"] > 0).any())
+    if name == "stereo":
+        return rec["emitted"] is not None and any(r["gon"].any() for _t, row in rec["emitted"] for r in row)
+    if name == "limiters":
+        return bool((rec["ticks"]["min_gain"] < 1).any()) and any(not np.array_equal(y.view(np.uint32), x.view(np.uint32))
+                                                                   for y, x in zip(rec["limited"], rec["delayed"]))
+    at = 28                                   # a record without its tick_in_run: 28 more bytes of header, then the table
+    if name == "tempo":
+        return any(np.frombuffer(b, "<u8", 1, at)[0] > 0 for _t, row in rec["emitted"] for b in row)
+    return any(int.from_bytes(b[:4], "little") > 0 and np.frombuffer(b, "<u8", -1, at).any() for _t, row in rec["emitted"] for b in row)
+
+
+def test_every_set_has_something_to_see():
+    """not trivially empty records: a band above 0, a true peak above 0, a goniometer emission with cells, a gain below 1 and a limited copy
+    that is not the delayed input, a tempo record with R[0] > 0, a tonality record with hops and a non-zero bin -- each on at least three
+    seeds of 44k1 and three of 48k"""
+    lively = {(name, shape_id): 0 for name in SETS for shape_id in ("44k1", "48k")}
+    for shape_id, seed in ALL_SETS_SEEDS:
+        if shape_id in ("44k1", "48k"):
+            _ts, runs = expected(shape_id, seed)
+            for name in SETS:
+                lively[(name, shape_id)] += any(something_to_see(name, r["want"][name]) for r in runs)
+    print(lively)
+    assert min(lively.values()) >= 3, lively
+
+
+# the seeds the faults are tried on (a 48 kHz desk, 441-frame ticks, and the short ticks: a spectrum's history is longer than a tick there only)
+FAULT_SEEDS = [ALL_SETS_SEEDS[i] for i in (9, 16, 19, 20, 21, 22)]
+APPLIES = {"no_reset": RESETTING, "meters_reset": ("meters",), "reset_per_run": SETS, "c_per_run": EMITTING, "base_frames": SETS,
+           "left_only": SETS, "sorted_order": SETS, "one_tick_late": SETS}
+
+
+@pytest.mark.parametrize("fault", FAULTS)
+def test_a_wrong_tap_host_changes_the_expected_records(fault):
+    """Each fault is one way the device could be wrong that test_full_random_graph_every_tap_set exists to notice (random_taps.FAULTS): with
+    it switched into the EXPECTED side, the records of every set it applies to must differ from the right ones on one of FAULT_SEEDS --
+    by the very comparison the GPU test uses.  The draws are the same with and without the fault."""
+    assert FAULT_SEEDS[0][0] == "48k" and {s for s, _ in FAULT_SEEDS[1:]} == {"44k1_100", "16k_1000", "8k_8000"}
+    caught = {name: [] for name in APPLIES[fault]}
+    for shape_id, seed in FAULT_SEEDS:
+        ts, right = expected(shape_id, seed)
+        ts_f, wrong = expected(shape_id, seed, fault)
+        assert ts_f.orders == ts.orders and [r["ticks"] for r in wrong] == [r["ticks"] for r in right]
+        for name in SETS:
+            if any(difference(name, a["want"][name], b["want"][name]) for a, b in zip(wrong, right)):
+                assert name in caught, f"{fault} changed the {name} records of seed {seed}: it should not touch that set"
+                caught[name].append(seed)
+    print(f"{fault}: caught by " + ", ".join(f"{name} {seeds}" for name, seeds in caught.items()))
+    assert all(caught.values()), f"{fault}: no seed catches it for {[name for name, seeds in caught.items() if not seeds]}"

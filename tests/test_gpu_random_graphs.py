@@ -11,7 +11,8 @@ oracle (README).  The full tests add scheduled updates of ev
 between runs, level meters on a random third of the ports (fed the ORACLE's samples of the port) and the OutputDevice hand-off
 (tests/output_device_model.py fed the oracle's input samples), plus the MX_FLAG_FP_CONTRACT order against the oracle's contract
 mode.  What is under test is the scheduler: run order, levels, sample-rate domains, launch groups, the fusion planner's
-conditions, slab layout, spans cut by scheduled updates, state carry.
+conditions, slab layout, spans cut by scheduled updates, state carry.  The last tests put all seven audio tap sets on those graphs
+(tests/random_taps.py): what is under test there is the shared tap host and the compiler's materialisation of tapped ports.
 """
 import struct
 from fractions import Fraction
@@ -25,6 +26,7 @@ from meter_model import METER_TICK, MeterModel, records_equal
 from mixlab_amd import abi
 from mixlab_amd.workspace import Workspace
 from output_device_model import OutputDeviceModel
+from random_taps import SETS, RandomTaps, difference, join, predict_fusion
 from tick_shapes import FAR_EPOCHS, by_id, far_first_tick
 
 pytestmark = pytest.mark.gpu
@@ -413,9 +415,17 @@ def od_args(p):
     return p.channels, (None if p.left < 0 else p.left), (None if p.right < 0 else p.right)
 
 
-def run_full_graph(shape_id, seed, builds, flags, first_tick=0):
-    """random_graph(full=True) through 3-4 runs of 1-6 ticks from `first_tick` on every build in `builds` against the oracle (in whatever
-    mode it is in): every materialised port, meter records and OutputDevice hand-offs, bit for bit"""
+def run_full_graph(shape_id, seed, builds, flags, first_tick=0, tap_sets=("meters",), n_runs=(3, 5), fault=None, collect=None):
+    """random_graph(full=True) through n_runs[0] .. n_runs[1] - 1 runs of 1-6 ticks from `first_tick` on every build in `builds` against the
+    oracle (in whatever mode it is in): every materialised port, meter records and OutputDevice hand-offs, bit for bit.
+
+    tap_sets = ("meters",): meters on a random third of the ports, drawn from this function's own stream as they always were.  Any other
+    tap_sets (random_taps.SETS: all seven) go through tests/random_taps.py: every set on ports, with parameters and at re-sets of its own,
+    one run (not the last) one tick long, every set's records of every build against its model fed the oracle's samples.  `builds` may be
+    empty: then only the oracle and the models run (the fusion plan predicted, not read from a built graph), the expected records of
+    every run are appended to `collect`, `fault` is random_taps' switch, and the RandomTaps is returned (tests/test_cpu_random_graphs.py)."""
+    legacy = tuple(tap_sets) == ("meters",)
+    assert legacy or (fault is None and collect is None) or not builds
     shape = by_id(shape_id)
     ws, sources = random_graph(seed, shape.sample_rate, shape.ticks_per_second, full=True)
     spt = ws.spt
@@ -446,6 +456,11 @@ def run_full_graph(shape_id, seed, builds, flags, first_tick=0):
 
     ports = {name: [pt for pt in frames if readable(g, *pt)] for name, g in graphs.items()}
     common = [pt for pt in frames if all(pt in ps for ps in ports.values())]
+    folded, stored_dup = predict_fusion(ws, order, n_inputs)
+    if set(graphs) - {"unfused"}:
+        assert {pt for pt in frames if pt not in common} == folded, f"seed {seed}: the fusion plan is not the predicted one"
+    else:
+        common = [pt for pt in common if pt not in folded]
     # taps: a random third, every OutputDevice's input, a dup-stored fused strip port, a resampled port
     dup = []
     if "fused" in graphs:
@@ -456,6 +471,9 @@ def run_full_graph(shape_id, seed, builds, flags, first_tick=0):
                 except abi.MxError:
                     dup.append((n, p))
         assert dup, f"seed {seed}: the first strip's Amplifier is not stored one float per frame"
+        assert dup == [pt for pt in common if pt in stored_dup], f"seed {seed}: the dup-stored ports are not the predicted ones"
+    else:
+        dup = [pt for pt in common if pt in stored_dup]
     resampled = [pt for pt in common if frames[pt] != spt or ws.nodes[pt[0]][0] == abi.KIND_RESAMPLE]   # (a 1/1 Resample is one too)
     if any(ws.nodes[n][0] == abi.KIND_RESAMPLE for n in order):
         assert resampled
@@ -468,8 +486,8 @@ def run_full_graph(shape_id, seed, builds, flags, first_tick=0):
                 t.add(must[int(rng.integers(0, len(must)))])
         return sorted(t)
 
-    taps = draw_taps()
-    assert all(src in taps for src in od_in.values() if src is not None)
+    taps = draw_taps() if legacy else []
+    assert all(src in taps for src in od_in.values() if src is not None) or not legacy
     tap_params = {}
     models = {}
 
@@ -484,16 +502,26 @@ def run_full_graph(shape_id, seed, builds, flags, first_tick=0):
         for g in graphs.values():
             g.set_meters(new, [tap_params[pt] for pt in new])
 
-    set_taps(taps)
+    if legacy:
+        set_taps(taps)
     od_models = {od: OutputDeviceModel(shape.sample_rate, *od_args(ws.nodes[od][1])) for od in ods}
     updatable = [n for n in order if ws.nodes[n][0] in PARAM_KINDS and ws.nodes[n][1]]   # (a Mixer of no channels has none)
     tick = first_tick
-    n_runs = int(rng.integers(3, 5))
+    n_runs = int(rng.integers(*n_runs))
+    if not legacy:
+        _order, dom, _bad = engine_domains(ws)
+        rates = {(n, p): float(shape.sample_rate) * dom[n].numerator / dom[n].denominator for (n, p) in frames}   # as TapHost's users compute it
+        ts = RandomTaps(seed, ws, shape, types, frames, rates, common, dup, resampled, n_runs, tap_sets, fault)
     for run in range(n_runs):
         L = int(rng.integers(1, MAX_RUN + 1))
-        if run == 2:
+        if not legacy:
+            L = 1 if run == ts.one_tick_run else L
+            ts.before_run(run, graphs.values())
+        if run == 2 and legacy:
             taps = sorted({pt for pt in taps if rng.random() < 0.5} | set(draw_taps()))
             set_taps(taps)
+        if legacy and collect is not None:
+            collect.append({"run": run, "ticks": L, "taps": list(taps), "params": [(tap_params[pt].hold_ticks, tap_params[pt].release) for pt in taps]})
         if run and rng.random() < 0.5:   # updates between runs
             for n in rng.choice(updatable, size=min(len(updatable), 3), replace=False):
                 p = random_params(rng, ws, int(n))
@@ -531,9 +559,13 @@ def run_full_graph(shape_id, seed, builds, flags, first_tick=0):
                 pushed, rec = od_models[od].run_tick((tick + k) * spt, x)
                 want_od[od][0].append(pushed); want_od[od][1].append(rec)
         want_meters = np.array(want_meters, dtype=METER_TICK)
+        if not legacy:
+            want_taps = ts.expect_run(L, [{pt: want[pt][k] for pt in frames} for k in range(L)])
+            if collect is not None:
+                collect.append({"run": run, "ticks": L, "want": want_taps})
         for name, g in graphs.items():
             step = 1 if name == "ticked" else L
-            got, got_meters, got_od = {}, [], {od: [[], []] for od in ods}
+            got, got_meters, got_od, got_taps = {}, [], {od: [[], []] for od in ods}, []
             for k0 in range(0, L, step):
                 for (n, ty) in sources:
                     g.write_source(n, data[n][k0 * spt * ty:(k0 + step) * spt * ty], step)
@@ -543,7 +575,10 @@ def run_full_graph(shape_id, seed, builds, flags, first_tick=0):
                 g.run_ticks(tick + k0, step)
                 for pt in ports[name]:
                     got.setdefault(pt, []).append(g.read_output(*pt, step, types[pt[0]][pt[1]] == STEREO, rate=(frames[pt], spt)))
-                got_meters.append(g.read_meters(0, step))
+                if legacy:
+                    got_meters.append(g.read_meters(0, step))
+                else:
+                    got_taps.append((k0, ts.read(g, step, want_taps)))
                 for od in ods:
                     s, r = g.read_audio_out(od, 0, step)
                     got_od[od][0].append(s); got_od[od][1] += [tuple(int(v) for v in q) for q in r.tolist()]
@@ -551,7 +586,12 @@ def run_full_graph(shape_id, seed, builds, flags, first_tick=0):
             for pt, chunks in got.items():
                 a, b = np.concatenate(chunks), np.concatenate(want[pt])
                 assert np.array_equal(bits(a), bits(b)), f"{what}: node {pt[0]} (kind {ws.nodes[pt[0]][0]}) port {pt[1]} differs from the oracle"
-            ok = records_equal(np.concatenate(got_meters), want_meters)
+            if not legacy:
+                got_taps = join(got_taps)
+                for set_name in ts.sets:
+                    d = difference(set_name, got_taps[set_name], want_taps[set_name])
+                    assert d is None, f"{what}: {set_name} taps on {ts.ports[set_name]} with {ts.params[set_name]}: {d}"
+            ok = records_equal(np.concatenate(got_meters), want_meters) if legacy else np.ones(1, bool)
             if not ok.all():
                 k, i = (int(v[0]) for v in np.nonzero(~ok))
                 raise AssertionError(f"{what}: meter on {taps[i]} tick {k}: got {np.concatenate(got_meters)[k, i]}, want {want_meters[k, i]}")
@@ -560,6 +600,13 @@ def run_full_graph(shape_id, seed, builds, flags, first_tick=0):
                 assert a.size == b.size and np.array_equal(bits(a), bits(b)), f"{what}: OutputDevice {od} hand-off differs"
                 assert got_od[od][1] == want_od[od][1], f"{what}: OutputDevice {od} records {got_od[od][1]} != {want_od[od][1]}"
         tick += L
+    if legacy and collect is not None:
+        collect.append({"rng": rng.bit_generator.state["state"]})   # every draw of this function's stream went as it always did
+    if not legacy:
+        if "fused" in graphs:
+            for set_name in ts.sets:
+                assert ts.tapped[set_name] & set(dup), f"seed {seed}: no {set_name} tap ever sat on a dup-stored port"
+        return ts
 
 
 @pytest.mark.parametrize("shape_id,seed", FULL_SEEDS, ids=[f"{s}-{n}" for s, n in FULL_SEEDS])
@@ -589,3 +636,35 @@ def test_full_random_graph_matches_the_oracle_far_from_tick_zero(shape_id, seed,
     assert {s for s, _ in FAR_SEEDS} == {"44k1", "48k", "44k1_100", "8k_8000"}
     n_ticks = 4 if epoch == "across_2p32" else 4 * MAX_RUN       # 3-4 runs of 1-6 ticks: sample 2^32 lies in the third tick
     run_full_graph(shape_id, seed, ("fused", "unfused"), abi.FLAG_EQ_EXACT, first_tick=far_first_tick(epoch, by_id(shape_id).spt, n_ticks))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# the same graphs with all seven audio tap sets (tests/random_taps.py): ports, parameters and re-sets of each set's own, 6-8 runs of
+# 1-6 ticks, every set's records of every build against its numpy model fed the oracle's samples.  tests/test_cpu_random_graphs.py
+# shows what these draws cover and that each way the tap host could be wrong changes the records compared here.
+# ---------------------------------------------------------------------------------------------------------------------------
+ALL_SETS_SEEDS = FULL_SEEDS[:8] + FULL_SEEDS[24:31] + [FULL_SEEDS[36]] + FULL_SEEDS[48:]   # (48k-312 has a Mixer without channels)
+ALL_SETS_RUNS = (6, 9)
+
+
+@pytest.mark.parametrize("shape_id,seed", ALL_SETS_SEEDS, ids=[f"{s}-{n}" for s, n in ALL_SETS_SEEDS])
+def test_full_random_graph_every_tap_set(shape_id, seed):
+    assert len(ALL_SETS_SEEDS) == 23
+    run_full_graph(shape_id, seed, ("fused", "unfused", "ticked", "overlap"), abi.FLAG_EQ_EXACT, tap_sets=SETS, n_runs=ALL_SETS_RUNS)
+
+
+@pytest.mark.parametrize("shape_id,seed", [FULL_SEEDS[1], FULL_SEEDS[25], FULL_SEEDS[48], FULL_SEEDS[51]],
+                         ids=[f"{s}-{n}" for s, n in [FULL_SEEDS[1], FULL_SEEDS[25], FULL_SEEDS[48], FULL_SEEDS[51]]])
+def test_full_random_graph_every_tap_set_contracted(shape_id, seed):
+    with oracle.fp_contract():
+        run_full_graph(shape_id, seed, ("fused", "unfused"), abi.FLAG_FP_CONTRACT, tap_sets=SETS, n_runs=ALL_SETS_RUNS)
+
+
+@pytest.mark.parametrize("epoch", ("at_2p40", "across_2p32"))
+@pytest.mark.parametrize("shape_id,seed", FAR_SEEDS, ids=[f"{s}-{n}" for s, n in FAR_SEEDS])
+def test_full_random_graph_every_tap_set_far_from_tick_zero(shape_id, seed, epoch):
+    """The taps count ticks and frames since they were set: their records are those of the same port samples at any epoch, so this holds
+    the ports they read to the oracle far from zero, and the tap host to taking its own tick where the absolute one is at hand."""
+    n_ticks = 4 if epoch == "across_2p32" else 0       # sample 2^32 lies in the third tick
+    run_full_graph(shape_id, seed, ("fused", "unfused"), abi.FLAG_EQ_EXACT, first_tick=far_first_tick(epoch, by_id(shape_id).spt, n_ticks),
+                   tap_sets=SETS, n_runs=ALL_SETS_RUNS)
