@@ -252,6 +252,10 @@ int mx_graph_debug_eq_launch(mx_graph* g, uint32_t out[5]);
  * SIMD: a control tile the wave fills itself, ramping rows evaluated row by row), else 0 -- another form was launched (MX_EQ_ENV_ROWS=0, three or four waves per SIMD,
  * ragged ticks, no inline Envelope), or no tick of any wave had a ramping row beside none of the general form.  Synchronises.  Tests use it to know the row form ran. */
 int mx_graph_debug_eq_env_rows(mx_graph* g, uint32_t* rows);
+/* DEBUG: *lean = bit 0: some wave of the first EqThree launch group's last launch ran a tick of its whole-tick inline Envelope loops WITHOUT the input tracker (every lane of
+ * the wave had seen two different input patterns in its chunk by then); bit 1: some wave ran them without the multiply by an amplitude of exactly 1.0.  0: MX_EQ_LEAN=0,
+ * another form was launched, or no tick qualified.  Synchronises.  Tests use it to know the lean loops ran. */
+int mx_graph_debug_eq_lean(mx_graph* g, uint32_t* lean);
 
 /* Feed a SOURCE_* node: n_ticks consecutive tick buffers (SPT mono / 2*SPT interleaved stereo f32). */
 int mx_graph_write_source(mx_graph* g, uint32_t node, const float* host_samples, size_t n_ticks);

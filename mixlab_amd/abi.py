@@ -121,6 +121,7 @@ _proto("mx_graph_debug_eq_records", C.c_int, C.c_void_p, C.POINTER(C.c_void_p), 
 _proto("mx_graph_debug_tail_releases", C.c_int, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64))
 _proto("mx_graph_debug_eq_launch", C.c_int, C.c_void_p, C.POINTER(C.c_uint32))
 _proto("mx_graph_debug_eq_env_rows", C.c_int, C.c_void_p, C.POINTER(C.c_uint32))
+_proto("mx_graph_debug_eq_lean", C.c_int, C.c_void_p, C.POINTER(C.c_uint32))
 _proto("mx_graph_eq_repair_stats", C.c_int, C.c_void_p, C.POINTER(C.c_uint64))
 _proto("mx_graph_write_source", C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t)
 _proto("mx_graph_bind_source_device", C.c_int, C.c_void_p, C.c_uint32, C.c_void_p)
@@ -593,6 +594,13 @@ class Graph:
         v = C.c_uint32()
         check(lib.mx_graph_debug_eq_env_rows(self._h, C.byref(v)))
         return bool(v.value)
+
+    def debug_eq_lean(self) -> dict:
+        """mx_graph_debug_eq_lean: did some wave of the first EqThree group's last launch run a tick without the input tracker / without the multiply by an
+        amplitude of 1.0 (synchronises) -> {untracked, unity}"""
+        v = C.c_uint32()
+        check(lib.mx_graph_debug_eq_lean(self._h, C.byref(v)))
+        return {"untracked": bool(v.value & 1), "unity": bool(v.value & 2)}
 
     def debug_eq_records(self):
         """-> (device pointer, bytes) of the first EqThree group's chunk records of the last speculative launch (mx_graph_debug_eq_records)"""

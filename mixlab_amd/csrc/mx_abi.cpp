@@ -143,6 +143,9 @@ int mx_graph_debug_eq_launch(mx_graph* g, uint32_t out[5]) {
 int mx_graph_debug_eq_env_rows(mx_graph* g, uint32_t* rows) {
     return guard([&] { REQUIRE(g && rows, "NULL argument"); *rows = g->g->eq_env_rows() ? 1u : 0u; });
 }
+int mx_graph_debug_eq_lean(mx_graph* g, uint32_t* lean) {
+    return guard([&] { REQUIRE(g && lean, "NULL argument"); *lean = g->g->eq_lean(); });
+}
 
 int mx_graph_eq_repair_stats(mx_graph* g, uint64_t out[8]) {
     return guard([&] {

@@ -332,6 +332,7 @@ Graph::Graph(const mx_node* nodes, size_t n_nodes, const mx_edge* edges, size_t 
     { const char* const sm = getenv("MX_SIN_MODE"); sin_mode_ = sm ? atoi(sm) : 0; }   // (A/B and tests: mx_k_stream.hip SIN_MODE)
     { const char* const gt = getenv("MX_TAIL_GATE_TEST"); gate_test_ = gt && atoi(gt); }
     { const char* const er = getenv("MX_EQ_ENV_ROWS"); eq_env_rows_ = !(er && atoi(er) == 0); }   // (A/B, read per graph: tests build both kinds in one process)
+    { const char* const el = getenv("MX_EQ_LEAN"); eq_lean_ = !(el && atoi(el) == 0); }           // (likewise)
     bool overlap_auto = false;
     {
         const char* const ae = getenv("MX_OVERLAP_AUTO");   // read per graph: tests build both kinds in one process
@@ -1255,6 +1256,7 @@ void Graph::run_span(uint64_t t0, size_t fpc, uint32_t call_off, uint32_t n_call
                         if (!eq_rows_flag_.p) { eq_rows_flag_.alloc(64); hip_check(hipMemset(eq_rows_flag_.p, 0, 64), "hipMemset"); }
                         r.env_rows = (uint32_t*)eq_rows_flag_.p; r.env_rows_seq = ++eq_rows_seq_;
                     }
+                    r.lean = eq_lean_ ? 1u : 0u;
                     const bool opens_gate = launch_eq_three_spec((const EqDesc*)desc_of(g), (EqState*)g.state.p, n, r, plan, g.eq_mode, g.spec.p, (uint64_t*)eq_stats_.p, stream_, launch, eq_env_rows_);
                     if (!opens_gate && !gate_test_) gate_armed_ = false;   // the direct form never stores the flag: a gate would spin to its time limit before the bank starts (MX_TAIL_GATE_TEST: tests of that bounded spin)
                     if (deferred_.pending) flush_deferred_tail(true);     // run k's Mixer bank: behind the gate this launch opens
@@ -1749,6 +1751,14 @@ bool Graph::eq_env_rows() {
     uint32_t v = 0;
     hip_check(hipMemcpy(&v, eq_rows_flag_.p, sizeof v, hipMemcpyDeviceToHost), "hipMemcpy(eq env rows)");
     return v == eq_rows_seq_;
+}
+
+uint32_t Graph::eq_lean() {
+    if (!eq_rows_flag_.p || !eq_rows_seq_) return 0u;
+    sync();
+    uint32_t v[3] = {0u, 0u, 0u};
+    hip_check(hipMemcpy(v, eq_rows_flag_.p, sizeof v, hipMemcpyDeviceToHost), "hipMemcpy(eq lean)");
+    return (v[1] == eq_rows_seq_ ? 1u : 0u) | (v[2] == eq_rows_seq_ ? 2u : 0u);
 }
 
 float* Graph::output_ptr(uint32_t node, uint32_t port, size_t* fpf, bool stream_ordered_consumer) {

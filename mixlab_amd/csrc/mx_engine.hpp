@@ -184,6 +184,7 @@ public:
     void tail_releases(uint64_t* gated, uint64_t* at_once) const { if (gated) *gated = n_gated_; if (at_once) *at_once = n_at_once_; }
     void eq_launch(uint32_t out[5]) const { for (int k = 0; k < 5; ++k) out[k] = eq_launch_[k]; }
     bool eq_env_rows();   // mx_graph_debug_eq_env_rows (synchronises)
+    uint32_t eq_lean();   // mx_graph_debug_eq_lean (synchronises)
     void set_tail_hook(std::function<void(hipStream_t)> hook) { tail_hook_ = std::move(hook); }
     // The NEXT run's first launch waits for `ev` (once).  What mx_exchange asks for its collectives and its combine of step k, which went out behind the bank that run k + 1
     // released: they normally end inside run k + 1's EqThree launch; when the bank outlasts that launch they would run into run k + 2's EqThree workgroups being placed --
@@ -296,6 +297,7 @@ private:
     DevBuf eq_stats_;             // [8] u64 counters of the speculative EqThree kernel's proof / repair pass
     uint32_t eq_launch_[5] = {MX_EQ_LAUNCH_NONE, 0, 0, 0, 0};   // mx_graph_debug_eq_launch: the first EqThree group's last launch
     bool eq_env_rows_ = true;             // MX_EQ_ENV_ROWS at build time (0: the inline Envelope keeps the lockstep form; A/B)
+    bool eq_lean_ = true;                 // MX_EQ_LEAN at build time (0: the EqThree hot loops keep the input tracker and the multiply by an amplitude of 1.0; A/B)
     DevBuf eq_rows_flag_; uint32_t eq_rows_seq_ = 0;   // mx_graph_debug_eq_env_rows: a wave of the first EqThree group's last launch that took the row form stores the launch's number
     struct Stage { void* host = nullptr; size_t cap = 0; hipEvent_t done = nullptr; bool pending = false; };
     Stage stage_[4]; uint32_t stage_next_ = 0;

@@ -77,6 +77,10 @@ __device__ __forceinline__ double env_depth(const EnvParams& p, const EnvTick& k
     return amp_depth<FC>(one_minus, mod_depth, (double)cc);
 }
 __device__ __forceinline__ float amp_apply(float y, double depth, double amplitude) { return (float)((double)y * depth * amplitude); }   // amplifier.rs:56
+// ... where the caller knows amplitude == 1.0 (unity gain): t * 1.0 == t bit for bit for every f64 t -- finite, +-0, subnormal, +-inf -- and a NaN t stays the NaN
+// the multiply by `depth` made (the hardware passes the quieted operand on), so the last multiply is dropped.  Hot loops of the tiled speculative kernel only; the
+// sequential walkers and the repair pass keep amp_apply.
+__device__ __forceinline__ float amp_apply_unity(float y, double depth) { return (float)((double)y * depth); }
 
 // One instance walked sample by sample in time order (the exact kernel, the repair pass): epilogue with a running tick cursor.
 template <bool FC = false>

@@ -21,6 +21,7 @@
 // it takes depends on the input.
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 
 #include "mx_common.hpp"
 #include "mx_k_eq_common.hpp"
@@ -605,7 +606,10 @@ __device__ __forceinline__ EqK eq_constants(const EqDesc& d, const EqRun& r) {
 }
 
 // compute phase over my row of the tile: ENVK as in eq_spec_span (0: no inline Envelope)
-template <int SB, int MODE, int ENVK, bool WARM, bool FC, bool LO_ONLY = false>   // WARM: `len` is the (negative) chunk-relative index of the lane's first warm-up sample; LO_ONLY: the early part of a warm-up, where only the slow cascade runs
+// TRACK = false: the min / max of the input's bit patterns is left as it is.  Its only reader is the repair pass, which asks whether the chunk's input was constant
+// (xmin == xmax) and, if so, for that value; a lane that has seen two different patterns (xmin < xmax) can never answer yes again, so the caller drops the tracking for
+// the ticks at whose start that holds for every lane of the wave (one instruction per sample).  UNITY: the caller has found K.amplitude == 1.0 (amp_apply_unity).
+template <int SB, int MODE, int ENVK, bool WARM, bool FC, bool LO_ONLY = false, bool TRACK = true, bool UNITY = false>   // WARM: `len` is the (negative) chunk-relative index of the lane's first warm-up sample; LO_ONLY: the early part of a warm-up, where only the slow cascade runs
 __device__ __forceinline__ void eq_tile_compute(const EqK& K, float* buf, const int lane, const int so, const int len,
                                                 const EnvTick& cur, const EnvLane& el, EqPoles& s, uint32_t& xmin, uint32_t& xmax, const float* cbuf = nullptr /* EQM_AMP_CTL: the control's tile */) {
     const double g_lo = K.g_lo, g_mid = K.g_mid, g_hi = K.g_hi, lo_f = K.lo_f, hi_f = K.hi_f;
@@ -631,7 +635,7 @@ __device__ __forceinline__ void eq_tile_compute(const EqK& K, float* buf, const 
                 if (MODE == EQM_AMP_CTL) c4 = reinterpret_cast<const f4v*>(cbuf + lane * SB)[pce ^ sw];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const uint32_t b = __float_as_uint(x4[e]); xmin = b < xmin ? b : xmin; xmax = b > xmax ? b : xmax;
+                    if (TRACK) { const uint32_t b = __float_as_uint(x4[e]); xmin = b < xmin ? b : xmin; xmax = b > xmax ? b : xmax; }
                     const float y = eq_step_h<FC>(s, lo_f, hi_f, g_lo, g_mid, g_hi, dx[e], hh[e]);
                     if (MODE == EQM_PLAIN) v[e] = y;
                     else {
@@ -642,7 +646,7 @@ __device__ __forceinline__ void eq_tile_compute(const EqK& K, float* buf, const 
                         else if (ENVK == 1) depth = el.depth;
                         else if (ENVK == 2) depth = env_lane_depth<FC>(K.env, el, kk - el.k0, one_minus, mod_depth, K.sr, K.rsr);
                         else depth = env_depth<FC>(K.env, cur, one_minus, mod_depth, el.t_chunk + kk, K.sr, K.rsr);
-                        v[e] = amp_apply(y, depth, amplitude);
+                        v[e] = UNITY ? amp_apply_unity(y, depth) : amp_apply(y, depth, amplitude);
                     }
                 }
                 row[pce ^ sw] = v;
@@ -665,7 +669,7 @@ __device__ __forceinline__ void eq_tile_compute(const EqK& K, float* buf, const 
 // 2p and 2p + 1 -- no per-pass search of the row masks, no address arithmetic beyond one add.
 struct EqEnvRow { double off_amp; uint32_t dtk /* dt0 - k0: the distance of chunk-relative sample 0 */; uint32_t where /* byte offset of the row in the tile | its swizzle << 4 */; };
 enum { EQ_ENV_ROW_ENTRIES = 68 };   // 64 rows and a padding entry per class
-// REGISTER NOTE for the ROWS instantiations (re-check after a toolchain change; the figures are in profiles/env_rows/README.md, "Disassembly"): eq_uniform_ptr below and
+// REGISTER NOTE for the ROWS instantiations -- and, since the lean loops (profiles/lean_window/README.md), the one-tile lockstep instantiations, UPTR in the kernel -- (re-check after a toolchain change; the figures are in profiles/env_rows/README.md, "Disassembly"): eq_uniform_ptr below and
 // the empty `asm volatile("; my ..." : "+v"(x))` statements in k_eq_three_spec_tiled only steer the register allocator -- the instance's bases (tick table, chunk records,
 // output) stay in SGPRs, and the lane's chunk begin and record address are re-derived where they are used instead of living through every loop.  With them the exact
 // mono-dup kernel has 128 VGPRs and no scratch (without: 6 VGPRs spilled, 28 B per lane), the contracted one 2 spilled / 12 B as the lockstep kernel of that shape
@@ -798,6 +802,11 @@ __global__ __launch_bounds__(64 * EQ_WPB, 4) void k_eq_three_spec_tiled(const Eq
     extern __shared__ __attribute__((aligned(16))) float eq_tiles_all[];   // [EQ_WPB][tiles per wave][TILE]
     constexpr int EQ_SB = SB, EQ_TILE = EqTileGeo<SB>::TILE;
     static_assert(!ROWS || (KMODE == EQM_AMP_ENV && !RT && NBUF == 1 && SB == 32), "the row form: the whole-tick inline Envelope over one whole-line tile");
+    // The ONE-TILE whole-tick inline Envelope kernels (the row form and the one-tile lockstep form: two to four waves per SIMD, multi-tick chunks) have the lean loops, and hold
+    // their wave-uniform bases in SGPRs (REGISTER NOTE above).  The two-tile instantiations are the parent's code: a wave alone on its SIMD walking one-tick chunks never
+    // drops its tracker, and the unity form measured SLOWER there (1024 strips x 64 ticks 0.294 -> 0.307 ms, profiles/lean_window/README.md).
+    constexpr bool LEANK = KMODE == EQM_AMP_ENV && !RT && NBUF == 1;
+    constexpr bool UPTR = LEANK;
     constexpr int EQ_TILES_PER_WAVE = (NBUF == 2 || KMODE == EQM_AMP_CTL || ROWS) ? 2 : 1;
     constexpr int EQ_WAVE_FLOATS = EQ_TILES_PER_WAVE * EQ_TILE + (ROWS ? EQ_ENV_ROW_ENTRIES * (int)(sizeof(EqEnvRow) / sizeof(float)) : 0);   // (row form: input tile, control tile, row table)
     const uint32_t t_enter = (uint32_t)__builtin_amdgcn_s_memtime();   // (a wave's life inside the launch, kept in its records' padding: mx_graph_debug_eq_records, tools/wave_times.py)
@@ -807,12 +816,12 @@ __global__ __launch_bounds__(64 * EQ_WPB, 4) void k_eq_three_spec_tiled(const Eq
     const uint32_t wave_id = blockIdx.x * EQ_WPB + wib;
     if (wave_id >= n_waves) return;
     float* const eq_tiles = eq_tiles_all + wib * EQ_WAVE_FLOATS;
-    const uint32_t inst = ROWS ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(wave_id / waves_per_inst)) : wave_id / waves_per_inst;   // (ROWS: said to be wave-uniform, so that what derives from it -- the tick table's and the records' bases -- stays in SGPRs)
+    const uint32_t inst = UPTR ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(wave_id / waves_per_inst)) : wave_id / waves_per_inst;   // (UPTR: said to be wave-uniform, so that what derives from it -- the tick table's and the records' bases -- stays in SGPRs)
     const EqDesc& d = descs[inst];
     const EqK K = eq_constants(d, r);
     EqTileCtx c;
     c.in = d.in; c.out = d.out;
-    if constexpr (ROWS) {   // the output's base in SGPRs (it is wave-uniform; as a flat address it took two VGPRs through every loop)
+    if constexpr (UPTR) {   // the output's base in SGPRs (it is wave-uniform; as a flat address it took two VGPRs through every loop)
         c.out = eq_uniform_ptr(d.out);
     }
     c.chunk0 = (wave_id % waves_per_inst) * 64u; c.n_chunks = plan.n_chunks; c.C = plan.chunk; c.F = (uint32_t)r.frames;
@@ -845,12 +854,13 @@ __global__ __launch_bounds__(64 * EQ_WPB, 4) void k_eq_three_spec_tiled(const Eq
     }
     uint32_t xmin = 0xffffffffu, xmax = 0u;
     const EnvTick* ticks = r.ticks ? r.ticks + (size_t)inst * r.n_calls : nullptr;
-    if constexpr (ROWS) ticks = eq_uniform_ptr(ticks);
+    if constexpr (UPTR) ticks = eq_uniform_ptr(ticks);
     EnvTick cur{}; EnvLane el{};
     const bool nice = env_params_nice(d.env);
-    EqChunkRec* rec = ROWS ? nullptr : recs + (size_t)inst * plan.n_chunks + (active ? j : 0);   // (ROWS: derived where it is used, from the instance's uniform base)
-    EqChunkRec* const recs_inst = ROWS ? eq_uniform_ptr(recs + (size_t)inst * plan.n_chunks) : nullptr;
+    EqChunkRec* rec = UPTR ? nullptr : recs + (size_t)inst * plan.n_chunks + (active ? j : 0);   // (UPTR: derived where it is used, from the wave's uniform base)
+    EqChunkRec* const recs_wave = UPTR ? eq_uniform_ptr(recs + (size_t)inst * plan.n_chunks + c.chunk0) : nullptr;   // (the wave's first record: lane l's is l behind it; a lane without a chunk points at the first and never writes)
     bool rows_ran = false;   // (ROWS, wave-uniform) some tick of this wave took the row form: mx_graph_debug_eq_env_rows
+    uint32_t lean_ran = 0u;   // (wave-uniform) bit 0: some tick of this wave ran without the min / max tracker, bit 1: without the multiply by 1.0 (mx_graph_debug_eq_lean)
 
     // One loop per PHASE, not one loop that picks its phase every step: the warm-up, and then -- per tick -- the one epilogue form the tick
     // needs.  With a single loop over the super-blocks that dispatched to the four compute variants, the compiler gave each variant its
@@ -896,7 +906,7 @@ __global__ __launch_bounds__(64 * EQ_WPB, 4) void k_eq_three_spec_tiled(const Eq
         float* buf = begin_sb(g);
         eq_tile_compute<SB, EQM_PLAIN, 0, true, FC>(K, buf, c.lane, (g - n_warm) * EQ_SB - row_shift, warm_from, cur, el, s, xmin, xmax);
     }
-    if constexpr (ROWS) { uint32_t je = active ? j : 0u; asm volatile("; my record %0" : "+v"(je)); rec = recs_inst + je; }
+    if constexpr (UPTR) { uint32_t le = active ? (uint32_t)c.lane : 0u; asm volatile("; my record %0" : "+v"(le)); rec = recs_wave + le; }
     if (!RT && active) {   // first sample of my chunk: record where the warm-up took me (chunks that started at the stream's start: the exact state)
 #pragma unroll
         for (int k = 0; k < 4; ++k) { rec->start[k] = s.lo[k]; rec->start[4 + k] = s.hi[k]; }
@@ -960,11 +970,20 @@ __global__ __launch_bounds__(64 * EQ_WPB, 4) void k_eq_three_spec_tiled(const Eq
         }
     } else if constexpr (KMODE == EQM_AMP_ENV) {
         const int sb_per_tick = (int)(r.fpc / EQ_SB);   // chunks are whole ticks, ticks whole super-blocks (launcher)
+        // LEAN LOOPS (r.lean; MX_EQ_LEAN=0: off).  The flat loop and the lockstep / row loop exist in up to four forms, chosen once per tick, wave-uniformly, like envk:
+        // without the multiply by an amplitude of exactly 1.0 (a strip at unity gain; wave-uniform, the same answer every tick), and without the min / max tracker once
+        // every lane that still has samples has seen two different input patterns (eq_tile_compute).  A lane that has tracked nothing holds xmin = 0xffffffff > xmax = 0,
+        // so "proven not constant" is xmin < xmax, never xmin != xmax: such a lane keeps the wave tracking.
+        auto lean_form = [&](const bool track, const bool unity, auto&& tick) {   // tick(TRACK, UNITY) runs the tick's super-blocks in that form
+            if constexpr (!LEANK) { tick(std::true_type{}, std::false_type{}); return; }
+            if (track) { if (unity) tick(std::true_type{}, std::true_type{}); else tick(std::true_type{}, std::false_type{}); }
+            else { if (unity) tick(std::false_type{}, std::true_type{}); else tick(std::false_type{}, std::false_type{}); }
+        };
         while (g < total) {
             // a new tick (wave-uniform): its Envelope state, per lane
             const int so0 = (g - n_warm) * EQ_SB;
             uint32_t jt = j;
-            if constexpr (ROWS) asm volatile("; my chunk %0" : "+v"(jt));   // (re-derived per tick from the chunk number: `begin` need not stay in registers across the super-block loops)
+            if constexpr (UPTR) asm volatile("; my chunk %0" : "+v"(jt));   // (re-derived per tick from the chunk number: `begin` need not stay in registers across the super-block loops)
             const long long begin_t = (long long)jt * c.C;
             const size_t tk = ((size_t)begin_t + (size_t)so0) / r.fpc;
             cur = ticks[tk < r.n_calls ? tk : r.n_calls - 1];
@@ -973,32 +992,43 @@ __global__ __launch_bounds__(64 * EQ_WPB, 4) void k_eq_three_spec_tiled(const Eq
             el.k0 = (uint32_t)so0; el.t_chunk = r.t0 + (uint64_t)begin_t;
             const int envk = __ballot(active && so0 < len && el.general != 0u) != 0ull ? 3 : (__ballot(active && so0 < len && el.flat == 0u) == 0ull ? 1 : 2);
             const int g_end = g + sb_per_tick < total ? g + sb_per_tick : total;
+            const bool track = !LEANK || !r.lean || __ballot(active && so0 < len && !(xmin < xmax)) != 0ull;
+            const bool unity = LEANK && r.lean && K.amplitude == 1.0;
+            if (envk != 3) lean_ran |= (track ? 0u : 1u) | (unity ? 2u : 0u);
             if (envk == 1) {
-                for (; g < g_end; ++g) { float* buf = begin_sb(g); const int so = (g - n_warm) * EQ_SB; eq_tile_compute<SB, KMODE, 1, false, FC>(K, buf, c.lane, so, len, cur, el, s, xmin, xmax); eq_tile_store<SB, KSTEREO != 0>(c, buf, so); }
-            } else if (ROWS && envk == 2) {
+                lean_form(track, unity, [&](auto TR, auto UN) {
+                    for (; g < g_end; ++g) { float* buf = begin_sb(g); const int so = (g - n_warm) * EQ_SB; eq_tile_compute<SB, KMODE, 1, false, FC, false, decltype(TR)::value, decltype(UN)::value>(K, buf, c.lane, so, len, cur, el, s, xmin, xmax); eq_tile_store<SB, KSTEREO != 0>(c, buf, so); }
+                });
+            } else if (envk == 2) {
                 if constexpr (ROWS) {
                     // the tick's table of ramping rows; my row of the control tile filled with my constant
                     float* const cbuf = eq_tiles + EQ_TILE;
                     EqEnvRow* const tab = reinterpret_cast<EqEnvRow*>(eq_tiles + 2 * EQ_TILE);
-                    const EqEnvRowPlan rows = eq_env_rows_plan(K, tab, el, active && so0 < len && el.flat == 0u, c.lane);
+                    int lt = c.lane;
+                    asm volatile("; my lane %0" : "+v"(lt));   // (what the row passes derive from the lane -- table slot, row offset, swizzle -- is derived per tick and does not live through the other ticks' loops)
+                    const EqEnvRowPlan rows = eq_env_rows_plan(K, tab, el, active && so0 < len && el.flat == 0u, lt);
                     const float cc = env_lane_cc<FC>(K.env, el.A, el.B, el.k, el.m0, el.on != 0u, el.dt0, K.sr, K.rsr);
                     const f4v cc4 = {cc, cc, cc, cc};
 #pragma unroll
-                    for (int q = 0; q < EQ_SB / 4; ++q) reinterpret_cast<f4v*>(cbuf + c.lane * EQ_SB)[q] = cc4;
+                    for (int q = 0; q < EQ_SB / 4; ++q) reinterpret_cast<f4v*>(cbuf + lt * EQ_SB)[q] = cc4;
                     rows_ran = true;
-                    for (; g < g_end; ++g) {
-                        const int so = (g - n_warm) * EQ_SB;
-                        // (begin_sb with the row passes between the DMA's issue and the wait for it: the wave fills its own round trip)
-                        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                        eq_tile_issue<SB>(c, eq_tiles, so);
-                        eq_env_rows<SB, FC>(K, cbuf, tab, rows, c.lane, so);
-                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                        eq_tile_compute<SB, EQM_AMP_CTL, 0, false, FC>(K, eq_tiles, c.lane, so, len, cur, el, s, xmin, xmax, cbuf);
-                        eq_tile_store<SB, KSTEREO != 0>(c, eq_tiles, so);
-                    }
+                    lean_form(track, unity, [&](auto TR, auto UN) {
+                        for (; g < g_end; ++g) {
+                            const int so = (g - n_warm) * EQ_SB;
+                            // (begin_sb with the row passes between the DMA's issue and the wait for it: the wave fills its own round trip)
+                            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                            eq_tile_issue<SB>(c, eq_tiles, so);
+                            eq_env_rows<SB, FC>(K, cbuf, tab, rows, lt, so);
+                            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                            eq_tile_compute<SB, EQM_AMP_CTL, 0, false, FC, false, decltype(TR)::value, decltype(UN)::value>(K, eq_tiles, c.lane, so, len, cur, el, s, xmin, xmax, cbuf);
+                            eq_tile_store<SB, KSTEREO != 0>(c, eq_tiles, so);
+                        }
+                    });
+                } else {
+                    lean_form(track, unity, [&](auto TR, auto UN) {
+                        for (; g < g_end; ++g) { float* buf = begin_sb(g); const int so = (g - n_warm) * EQ_SB; eq_tile_compute<SB, KMODE, 2, false, FC, false, decltype(TR)::value, decltype(UN)::value>(K, buf, c.lane, so, len, cur, el, s, xmin, xmax); eq_tile_store<SB, KSTEREO != 0>(c, buf, so); }
+                    });
                 }
-            } else if (envk == 2) {
-                for (; g < g_end; ++g) { float* buf = begin_sb(g); const int so = (g - n_warm) * EQ_SB; eq_tile_compute<SB, KMODE, 2, false, FC>(K, buf, c.lane, so, len, cur, el, s, xmin, xmax); eq_tile_store<SB, KSTEREO != 0>(c, buf, so); }
             } else {
                 for (; g < g_end; ++g) { float* buf = begin_sb(g); const int so = (g - n_warm) * EQ_SB; eq_tile_compute<SB, KMODE, 3, false, FC>(K, buf, c.lane, so, len, cur, el, s, xmin, xmax); eq_tile_store<SB, KSTEREO != 0>(c, buf, so); }
             }
@@ -1011,12 +1041,16 @@ __global__ __launch_bounds__(64 * EQ_WPB, 4) void k_eq_three_spec_tiled(const Eq
             eq_tile_store<SB, KSTEREO != 0>(c, buf, so);
         }
     }
-    if constexpr (ROWS) {   // (likewise: the record's address is re-derived here, not carried through the loops)
-        uint32_t je = active ? j : 0u;
-        asm volatile("; my record %0" : "+v"(je));
-        rec = recs_inst + je;
+    if constexpr (UPTR) {   // (likewise: the record's address is re-derived here, not carried through the loops)
+        uint32_t le = (uint32_t)c.lane;   // (from the lane, which lives through every loop anyway; selected BEHIND the statement, or the value selected after the warm-up is kept for this, in scratch)
+        asm volatile("; my record %0" : "+v"(le));
+        rec = recs_wave + (active ? le : 0u);
     }
     if (ROWS && rows_ran && r.env_rows && c.lane == 0) __hip_atomic_store(r.env_rows, r.env_rows_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (LEANK && r.env_rows && c.lane == 0) {   // (mx_graph_debug_eq_lean: words 1 and 2 of the same flag line)
+        if (lean_ran & 1u) __hip_atomic_store(r.env_rows + 1, r.env_rows_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (lean_ran & 2u) __hip_atomic_store(r.env_rows + 2, r.env_rows_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
     if (active) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) { rec->end[k] = s.lo[k]; rec->end[4 + k] = s.hi[k]; }

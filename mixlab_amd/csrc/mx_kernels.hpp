@@ -107,7 +107,8 @@ void launch_env_ticks(const EnvTickDesc* d, uint32_t n, const GateBits& gates, u
 // what every EqThree launch needs beyond the descriptors: the per-tick Envelope table (null when no instance folds one)
 struct EqRun { size_t frames; size_t fpc /* samples per tick (call) */; uint32_t n_calls; uint32_t fc /* MX_FLAG_FP_CONTRACT: the contracted order */; uint64_t t0; double sr, rsr /* RN(1 / sr), host */, lo_f, hi_f; const EnvTick* ticks /* [n][n_calls] */;
                uint32_t* started = nullptr; uint32_t started_seq = 0; /* tiled speculative kernel: its last workgroup stores started_seq there when it starts (every earlier one has been placed by then): Graph's tail gate */
-               uint32_t* env_rows = nullptr; uint32_t env_rows_seq = 0; /* tiled speculative kernel, row form of the inline Envelope: a wave that took it for some tick stores env_rows_seq there (mx_graph_debug_eq_env_rows) */ };
+               uint32_t* env_rows = nullptr; uint32_t env_rows_seq = 0; /* tiled speculative kernel, row form of the inline Envelope: a wave that took it for some tick stores env_rows_seq there (mx_graph_debug_eq_env_rows); words 1 and 2 of the same line: a wave that ran some tick without the input tracker / without the multiply by an amplitude of 1.0 (mx_graph_debug_eq_lean) */
+               uint32_t lean = 1; /* tiled speculative kernel, whole-tick inline Envelope: the lean forms of its hot loops where they are exact no-ops removed (0: MX_EQ_LEAN=0, A/B) */ };
 // scratch != nullptr: the split-cascade form for few instances (eq_use_poles_split; eq_poles_scratch_bytes of scratch); else one lane per instance
 void launch_eq_three_exact(const EqDesc* d, EqState* st, uint32_t n, const EqRun& r, void* scratch, hipStream_t s);
 bool eq_use_poles_split(uint32_t n, size_t frames);
