@@ -38,7 +38,8 @@ extern "C" {
                               *    mx_graph_limited_device_ptr, mx_limiter_weights;
                               *    mx_tempo_params, mx_graph_set_tempo, mx_graph_read_tempo, mx_tempo_record_bytes, mx_tempo_bpm;
                               *    mx_tonality_params, mx_graph_set_tonality, mx_graph_read_tonality, mx_tonality_record_bytes, mx_tonality_tables, mx_tonality_chroma,
-                              *    mx_tonality_key */
+                              *    mx_tonality_key;
+                              *    mx_multiview_view, mx_multiview_params, mx_multiview_status, mx_video_multiview, mx_graph_set_multiview, mx_graph_multiview_output */
 
 /* ---- status codes (0 ok, <0 error; cf. MIXLAB_IOCTX_ERROR / MIXLAB_IOCTX_PANIC) ---- */
 enum {
@@ -900,6 +901,44 @@ typedef struct {
     uint32_t dst_w, dst_h;                     /* even, >= 2, <= 16384; crop_w <= 32 * dst_w and crop_h <= 32 * dst_h (at most 130 taps per axis, mx_video_scaler_tap_count) */
 } mx_video_place_params;                       /* 40 bytes */
 int mx_video_place(const mx_dframe* in, const mx_video_place_params* params, mx_dframe** out, void* stream);
+/* The MULTIVIEWER (BUILD-SPECIFIED; the reference shows several pictures with one MSE Monitor per module): up to MX_MULTIVIEW_MAX frames, each
+ * resampled into its own rectangle ("view") of ONE opaque canvas with a tally frame round it, in ONE launch that writes every byte of the canvas once -- the A / B / program
+ * and input thumbnails of a vision mixer side by side, red round what is on air, green round the preview.  All quantities are integers.
+ *   VIEW i has the rectangle R = (x, y, w, h) on the canvas, frame included.  Views must not overlap, frames included (touching is allowed).
+ *   INNER RECTANGLE I: R inset by `border` on all four sides.  PICTURE RECTANGLE P: with fit = 0, P = I; with fit = 1,
+ *     (sw, sh, lx, ly) = mx_video_scale_geometry(src_w, src_h, I.w, I.h) (the DynamicScaler's rule, encode.rs:354-374) and P is sw x sh at (I.x + lx, I.y + ly).
+ *   SHOWN: view i is shown when its frame is present (in[i] != NULL), the frame is yuv420p or yuva420p, P.w >= 2 and P.h >= 2, and src_w <= 32 P.w and
+ *     src_h <= 32 P.h (the placer's limit of 130 taps per axis).  A view that is not shown is no error -- it depends on the frames that arrive; bit i of the
+ *     shown mask says which views were shown.
+ *   CANVAS LUMA at (x, y): outside every view's rectangle bg_y; inside a view's R but outside its I border_y; inside I but outside P -- or anywhere in I of a view
+ *     that is not shown -- 0, the scaler's blank (frame.rs:76-138); inside P of a shown view Sy at (x - P.x, y - P.y), where Sy is the WHOLE source luma plane
+ *     resampled to P.w x P.h exactly as mx_video_place's RESAMPLED PLANES with a whole-frame crop: tables (src_w -> P.w, src_h -> P.h) of DESIGN.md "Scaler"
+ *     (mx_video_scaler_taps), H pass t = (sum hc * S + 64) >> 7 over every source row, V pass clip8((sum vc * t + 2^20) >> 21), tap indices clamped to the
+ *     plane's visible area.
+ *   CANVAS CHROMA: the same with every number halved -- tables (src_w/2 -> P.w/2, src_h/2 -> P.h/2), blank 0x80, border_u / border_v, bg_u / bg_v.
+ *   COVERAGE: a source's coverage plane is IGNORED: a multiviewer shows the source, not its key.  Honouring it (a view over a background picture) is a stated follow-up.
+ *   OUTPUT: *out is a NEW opaque yuv420p frame of canvas_w x canvas_h carrying one reference, its stride padding as mx_dframe_create leaves it (Y 0, chroma 0x80).
+ *     The inputs' padding is never read as picture.
+ * Consequences: with fit = 1, I of a shown view is byte for byte what mx_video_scale writes into an I.w x I.h frame; with fit = 0, P equals the Y / U / V of
+ * mx_video_place of the whole frame into that rectangle.
+ * Overlapping views, or any value outside the ranges in the comments below, are MX_ERR_INVALID -- checked on the host before any device is touched.
+ * Stateless; asynchronous on `stream`, like mx_video_place. */
+#define MX_MULTIVIEW_MAX 16
+typedef struct {
+    uint32_t x, y, w, h;                     /* the view's rectangle on the canvas, frame included: even, inside the canvas, w and h >= 2 * border + 2 */
+    uint32_t border;                         /* even, 0 .. 64: thickness of the tally frame */
+    uint8_t  border_y, border_u, border_v;   /* its colour */
+    uint8_t  fit;                            /* 0: stretch to the inner rectangle; 1: keep the aspect (mx_video_scale_geometry) */
+} mx_multiview_view;                         /* 24 bytes */
+typedef struct {
+    uint32_t canvas_w, canvas_h;             /* even, >= 2, within what mx_dframe_create_fmt accepts */
+    uint8_t  bg_y, bg_u, bg_v, _pad;         /* the canvas outside every view; _pad 0 */
+    uint32_t n_views;                        /* 1 .. MX_MULTIVIEW_MAX */
+    uint32_t hop;                            /* graph form only, >= 1; the pixel call ignores it */
+    mx_multiview_view view[MX_MULTIVIEW_MAX];/* entries beyond n_views are not looked at */
+} mx_multiview_params;                       /* 404 bytes */
+int mx_video_multiview(const mx_dframe* const* in /* [n_views], NULL = no frame */, const mx_multiview_params* params,
+                       mx_dframe** out, uint32_t* shown_mask /* may be NULL */, void* stream);
 int mx_video_sync(void* stream);
 /* A caller-owned hipStream_t that graphs / scalers / mixers launched pictures on is about to be destroyed: release what the library keeps per (device, stream) for its
  * batched video launches (page-locked descriptor staging, device copies, events, an upload stream).  The library frees this itself for streams it created; for a caller's
@@ -1076,6 +1115,28 @@ int mx_video_scope_record_bytes(const mx_video_scope_params* params, size_t* byt
 /* The pixel-path form, beside mx_video_to_rgba: the record of ONE frame into device_record (4-byte aligned device memory of
  * mx_video_scope_record_bytes bytes), asynchronous on `stream`; present = 1, tick_in_run = 0, hop ignored. */
 int mx_video_scope(const mx_dframe* in, const mx_video_scope_params* params, void* device_record, void* stream);
+
+/* The multiviewer as a tap on VIDEO output ports (mx_video_multiview): view i shows the frame on ports[i] -- a SOURCE_VIDEO's port (keyed / placed
+ * where such a transform is set: the placed canvas is what is shown) or a VideoMixer's program, A or B.  Like the video scope taps it adds no node and no edge: the run
+ * order is unchanged and so is every picture the graph produces, byte for byte; a graph without the setting launches nothing new.  The same port may appear in several views.
+ *   hop       the scopes' rule with a counter c of its own: c = 0 at the set, a tick is recorded when c mod hop == 0 (tested before the increment), c is carried across runs.
+ *   render    a run renders AT MOST ONE canvas, that of its LAST recorded tick (earlier recorded ticks of the same run are not rendered: nobody could read them), at the
+ *             end of that tick's pass over the video nodes.  A port whose frame is still symbolic (an unevaluated cross-fade chain or scaler output) is materialised first,
+ *             as for a scope tap; then ONE launch follows on the graph's stream.  A port that holds no frame (None), or a frame of another pixel format, is a view not
+ *             shown; present_mask still has its bit for the other format.
+ *   status    recorded: how many ticks of the last run were recorded (0: none, and no canvas); tick_in_run: the rendered tick; present_mask: bit i, ports[i] held a frame
+ *             on that tick; shown_mask: as mx_video_multiview.
+ * mx_graph_set_multiview: n == params->n_views views; n = 0 (params may be NULL) removes the setting.  Audio port: MX_ERR_TYPE.  A node or port out of range,
+ * n != n_views, hop = 0, or parameters mx_video_multiview refuses: MX_ERR_INVALID.  Waits for outstanding work like mx_graph_set_video_scopes and resets c.  The tap tables
+ * are kept per view and rebuilt only when that view's source size or picture rectangle changes; per frame only the launch's small descriptor block is uploaded.
+ * mx_graph_adopt_state does not carry the setting.
+ * mx_graph_multiview_output: the canvas of the last run's last recorded tick, *out carrying one reference for the caller, and the status (may be NULL); recorded = 0 and
+ * *out = NULL when the last run recorded no tick (no error).  No setting, or no run since it was set: MX_ERR_INVALID.  Joins the graph's streams like the other video
+ * read-outs.  Canvases come from a small pool under the placer's rule: a pooled canvas is rewritten only when the pool alone holds it, so one the caller still holds is
+ * never overwritten. */
+typedef struct { uint32_t recorded, tick_in_run, present_mask, shown_mask; } mx_multiview_status;   /* 16 bytes */
+int mx_graph_set_multiview(mx_graph* g, const mx_port_ref* ports, size_t n, const mx_multiview_params* params);   /* n == params->n_views; n = 0 (params may be NULL) removes */
+int mx_graph_multiview_output(mx_graph* g, mx_dframe** out, mx_multiview_status* status);
 
 /* MX_KIND_MONITOR after a run.  Tick `tick_in_run` of the last mx_graph_run_ticks as the codec thread would see it:
  * ts = the tick's timestamp relative to the node's epoch -- the first tick it ever ran (monitor.rs:121-123); when the Video input carried

@@ -161,6 +161,12 @@ public:
     // the keyer as a transform of a SOURCE_VIDEO node (mx_graph_set_video_source_key): the node delivers the keyed yuva420p frame; nullptr removes it
     void set_video_source_key(uint32_t node, const mx_video_key_params* p) { check(mx_graph_set_video_source_key(g_, node, p)); }
     void set_video_source_place(uint32_t node, const mx_video_place_params* p) { check(mx_graph_set_video_source_place(g_, node, p)); }
+    // the multiviewer as a tap on video output ports (mx_graph_set_multiview): ports[i] is shown in view i of p; an empty list removes it
+    void set_multiview(const std::vector<mx_port_ref>& ports, const mx_multiview_params& p) {
+        check(mx_graph_set_multiview(g_, ports.data(), ports.size(), ports.empty() ? nullptr : &p));
+    }
+    // the canvas of the last run's last recorded tick (one reference for the caller: mx_dframe_release), nullptr when the run recorded none
+    mx_dframe* multiview_output(mx_multiview_status* status = nullptr) { mx_dframe* f = nullptr; check(mx_graph_multiview_output(g_, &f, status)); return f; }
     size_t samples_per_tick() const { size_t s = 0; check(mx_graph_samples_per_tick(g_, &s)); return s; }
     mx_graph* handle() const { return g_; }
 private:

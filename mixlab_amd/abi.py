@@ -265,6 +265,32 @@ class VideoPlaceParams(C.Structure):
 PLACE_TILE_W, PLACE_TILE_H, PLACE_TAP_BOUND = 64, 16, 18
 _proto("mx_video_place", C.c_int, C.c_void_p, C.POINTER(VideoPlaceParams), C.POINTER(C.c_void_p), C.c_void_p)
 _proto("mx_graph_set_video_source_place", C.c_int, C.c_void_p, C.c_uint32, C.POINTER(VideoPlaceParams))
+MULTIVIEW_MAX = 16
+
+
+class MultiviewView(C.Structure):
+    """mx_multiview_view (24 bytes): a view's rectangle on the canvas (frame included), the tally frame's thickness and colour, and stretch (0) or keep-aspect (1)."""
+    _fields_ = [("x", C.c_uint32), ("y", C.c_uint32), ("w", C.c_uint32), ("h", C.c_uint32), ("border", C.c_uint32),
+                ("border_y", C.c_uint8), ("border_u", C.c_uint8), ("border_v", C.c_uint8), ("fit", C.c_uint8)]
+
+
+class MultiviewParams(C.Structure):
+    """mx_multiview_params (404 bytes): the canvas, its background colour, the views, and -- in a graph -- render every hop-th video tick."""
+    _fields_ = [("canvas_w", C.c_uint32), ("canvas_h", C.c_uint32), ("bg_y", C.c_uint8), ("bg_u", C.c_uint8), ("bg_v", C.c_uint8), ("_pad", C.c_uint8),
+                ("n_views", C.c_uint32), ("hop", C.c_uint32), ("view", MultiviewView * MULTIVIEW_MAX)]
+
+
+class MultiviewStatus(C.Structure):
+    """mx_multiview_status (16 bytes): recorded ticks of the last run, the tick rendered, which ports held a frame, which views were shown."""
+    _fields_ = [("recorded", C.c_uint32), ("tick_in_run", C.c_uint32), ("present_mask", C.c_uint32), ("shown_mask", C.c_uint32)]
+
+
+# the multiviewer's kernel (mx_video.hpp MX_MULTIVIEW_*): a workgroup writes a MULTIVIEW_TILE_W x MULTIVIEW_TILE_H tile of one canvas PLANE (chroma planes: half the
+# luma numbers); axes of up to MULTIVIEW_TAP_BOUND taps (downscales up to 4.5:1) take the LDS-tiled form, more taps the gather form: tests put sizes and ratios around them
+MULTIVIEW_TILE_W, MULTIVIEW_TILE_H, MULTIVIEW_TAP_BOUND = 64, 16, 20
+_proto("mx_video_multiview", C.c_int, C.POINTER(C.c_void_p), C.POINTER(MultiviewParams), C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_void_p)
+_proto("mx_graph_set_multiview", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(MultiviewParams))
+_proto("mx_graph_multiview_output", C.c_int, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(MultiviewStatus))
 _proto("mx_graph_profile_run", C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float))
 _proto("mx_graph_profile_enable", C.c_int, C.c_void_p, C.c_int)
 _proto("mx_graph_profile_collect", C.c_int, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32))

@@ -316,6 +316,7 @@ int mx_stream_retired(void* stream) {
         REQUIRE(stream, "stream is NULL (the library's own default video stream is never retired)");
         mx::flush_scales((hipStream_t)stream);
         mx::video_stream_retired((hipStream_t)stream);
+        mx::multiview_stream_retired((hipStream_t)stream);
     });
 }
 
@@ -367,6 +368,47 @@ int mx_video_place(const mx_dframe* in, const mx_video_place_params* params, mx_
         mx::place_into(d, *params, *tabs, o.f, s);
         o->retain();
         *out = H(o.f);
+    });
+}
+
+int mx_video_multiview(const mx_dframe* const* in, const mx_multiview_params* params, mx_dframe** out, uint32_t* shown_mask, void* stream) {
+    return guard([&] {
+        REQUIRE(out, "out is NULL");
+        *out = nullptr;
+        if (shown_mask) *shown_mask = 0;
+        REQUIRE(in && params, "NULL argument");
+        mx::check_multiview_params(*params, false);   // host only: nothing below runs for parameters the header refuses
+        hipStream_t s = S(stream);
+        DFrame* f[MX_MULTIVIEW_MAX] = {};
+        for (uint32_t i = 0; i < params->n_views; ++i) {
+            DFrame* d = const_cast<DFrame*>(D(in[i]));
+            if (!d || d->fmt != MX_PIXFMT_YUV420P) continue;   // no frame, or one of another format: the view is not shown
+            d->ensure_pixels(s);
+            f[i] = d;
+        }
+        mx::flush_scales(s);   // an input may be a scaler's output whose job is still queued
+        mx::MultiviewTabs tabs;
+        FrameRef o(DFrame::create_unfilled(params->canvas_w, params->canvas_h, MX_PIXFMT_YUV420P, false), false);
+        const uint32_t shown = mx::multiview_into(f, *params, tabs, o.f, s);
+        if (shown_mask) *shown_mask = shown;
+        o->retain();
+        *out = H(o.f);
+    });
+}
+int mx_graph_set_multiview(mx_graph* g, const mx_port_ref* ports, size_t n, const mx_multiview_params* params) {
+    return guard([&] {
+        // the parameters first: what the header refuses is refused before a graph -- or a device -- is looked at
+        if (n && params) { REQUIRE(n == params->n_views, "multiview: n must equal params->n_views"); mx::check_multiview_params(*params, true); }
+        REQUIRE(g, "graph is NULL");
+        g->g->set_multiview(ports, n, params);
+    });
+}
+int mx_graph_multiview_output(mx_graph* g, mx_dframe** out, mx_multiview_status* status) {
+    return guard([&] {
+        REQUIRE(g && out, "NULL argument");
+        *out = nullptr;
+        FrameRef r = g->g->multiview_output(status);
+        if (r) { r->retain(); *out = H(r.f); }
     });
 }
 

@@ -521,11 +521,12 @@ Graph::~Graph() {
     if (stream_) (void)hipStreamSynchronize(stream_);
     if (tail_stream_) { (void)hipStreamDestroy(tail_stream_); (void)hipEventDestroy(ev_head_done_); for (auto& e : ev_tail_done_) (void)hipEventDestroy(e); }
     for (Node& n : nodes_) { n.vmixer.reset(); n.vout.clear(); n.vsrc = FrameRef(); n.vsrc_ring.clear(); n.vsrc_sched.clear(); n.vkey_done.clear(); n.vkey_pool.clear(); n.vplace_done.clear(); n.vplace_pool.clear(); n.vplace_tabs.reset(); }
+    mv_out_ = FrameRef(); mv_pool_.clear();
     prof_runs_.clear(); prof_pool_.clear();
     for (Stage& st : stage_) { if (st.done) (void)hipEventDestroy(st.done); if (st.host) (void)hipHostFree(st.host); }
     // the descriptor ring launch_video_batch keeps per stream goes with a stream this graph OWNS; a caller's stream may be shared with other
     // graphs / scalers that are launching on it right now (their ring must not be freed under them): its ring lives as long as the process
-    if (own_stream_ && stream_) { video_stream_retired(stream_); (void)hipStreamDestroy(stream_); }
+    if (own_stream_ && stream_) { video_stream_retired(stream_); multiview_stream_retired(stream_); (void)hipStreamDestroy(stream_); }
 }
 
 // Graph-compiler fusion.  A port buffer is a per-tick temporary of Engine::run_tick
@@ -1061,7 +1062,7 @@ void Graph::run(uint64_t t0, size_t fpc, uint32_t n_calls, float* ms_by_kind, fl
     const size_t frames = fpc * (size_t)n_calls;
     auto drop_schedules = [&] { for (uint32_t id : sched_nodes_) { nodes_[id].sched.clear(); nodes_[id].gate_sched.clear(); } sched_nodes_.clear(); };
     if (frames > cap_frames_) { drop_schedules(); throw Error(MX_ERR_INVALID, "n_ticks exceeds max_ticks_per_run"); }
-    if (n_calls == 0 || fpc == 0) { drop_schedules(); last_calls_ = n_calls; last_frames_per_call_ = fpc; for (AudioTapSet* s : taps_) s->empty_run(); scope_n_ = 0; return; }
+    if (n_calls == 0 || fpc == 0) { drop_schedules(); last_calls_ = n_calls; last_frames_per_call_ = fpc; for (AudioTapSet* s : taps_) s->empty_run(); scope_n_ = 0; mv_out_ = FrameRef(); mv_status_ = mx_multiview_status{0, 0, 0, 0}; return; }
     // keyed / placed video sources: a frame the transform cannot take fails the run HERE, before anything of it is launched or any node's state has moved
     for (uint32_t id : video_order_) {
         const Node& n = nodes_[id];
@@ -1133,6 +1134,12 @@ void Graph::run(uint64_t t0, size_t fpc, uint32_t n_calls, float* ms_by_kind, fl
         if (n_rec > scope_cap_) throw Error(MX_ERR_INTERNAL, "video scopes: the run records more ticks than the taps were sized for");
         if (n_rec) hip_check(hipMemsetAsync(scope_rec_.p, 0, n_rec * scopes_.size() * scope_rec_bytes_, stream_), "hipMemsetAsync(video scope records)");
         scope_n_ = 0; scope_run_seen_ = true;
+    }
+    if (!mv_ports_.empty()) {   // the multiviewer renders the run's LAST recorded tick only: which one that is follows from its counter now
+        const uint64_t hop = mv_par_.hop, first = (hop - mv_c_ % hop) % hop;
+        const uint64_t n_rec = first < n_calls ? (n_calls - first + hop - 1) / hop : 0;
+        mv_last_ = n_rec ? (int64_t)(first + (n_rec - 1) * hop) : -1;
+        mv_out_ = FrameRef(); mv_status_ = mx_multiview_status{(uint32_t)n_rec, 0, 0, 0}; mv_run_seen_ = true;
     }
 
     // Plotter bookkeeping is host logic (plotter.rs:37-40): count += 1 per call, fire on every 6th
@@ -1792,6 +1799,8 @@ int Graph::read_plotter(uint32_t node, uint32_t call, float* left, float* right)
 void Graph::run_video_tick(uint64_t t) {
     scope_now_ = false;
     if (!scopes_.empty()) { scope_now_ = scope_c_ % scope_par_.hop == 0; ++scope_c_; }   // the hop counter: tested before the increment
+    mv_now_ = false;
+    if (!mv_ports_.empty()) { mv_now_ = mv_c_ % mv_par_.hop == 0; ++mv_c_; }
     for (uint32_t id : video_order_) {
         Node& n = nodes_[id];
         switch (n.kind) {
@@ -1931,6 +1940,65 @@ void Graph::run_video_tick(uint64_t t) {
         if (scope_now_) for (uint32_t k = 0; k < (uint32_t)scopes_.size(); ++k) if (scopes_[k].node == id) launch_video_scope(k, n.vout[scopes_[k].port]);
     }
     if (scope_now_) ++scope_n_;
+    if (mv_now_ && (int64_t)video_tick_in_run_ == mv_last_) render_multiview();   // every tapped port's vout is set
+}
+
+// The multiviewer's canvas of the tick being run.  Ordering as for a scope tap (launch_video_scope): everything is on stream_; a symbolic frame is materialised
+// first -- the consumers that ran earlier in the tick evaluated the chain themselves, and those of later ticks read the same bytes -- then the queued scaler jobs
+// leave, then the ONE launch.  The canvas is a pool frame nothing but the pool holds: its last reader is on stream_ already, or is the caller, who let go of it.
+void Graph::render_multiview() {
+    DFrame* in[MX_MULTIVIEW_MAX] = {};
+    uint32_t present = 0;
+    for (uint32_t i = 0; i < (uint32_t)mv_ports_.size(); ++i) {
+        DFrame* d = nodes_[mv_ports_[i].node].vout[mv_ports_[i].port].frame.f;
+        if (!d) continue;
+        present |= 1u << i;
+        if (d->fmt != MX_PIXFMT_YUV420P) continue;   // another pixel format: present, not shown
+        d->ensure_pixels(stream_);
+        in[i] = d;
+    }
+    flush_scales(stream_);   // a scaler output just asked for (or queued earlier in the tick) must be written before it is read
+    FrameRef o;
+    for (auto& f : mv_pool_) if (f->rc.load(std::memory_order_acquire) == 1) { o = f; break; }
+    if (!o) {
+        if (mv_pool_.size() >= 8) mv_pool_.erase(mv_pool_.begin());
+        mv_pool_.push_back(FrameRef(DFrame::create_unfilled(mv_par_.canvas_w, mv_par_.canvas_h, MX_PIXFMT_YUV420P, false), false));   // the kernel writes every byte
+        o = mv_pool_.back();
+    }
+    mv_status_.shown_mask = multiview_into(in, mv_par_, mv_tabs_, o.f, stream_);
+    mv_status_.present_mask = present;
+    mv_status_.tick_in_run = video_tick_in_run_;
+    mv_out_ = o;
+}
+
+void Graph::set_multiview(const mx_port_ref* ports, size_t n, const mx_multiview_params* params) {
+    if (n && (!ports || !params)) throw Error(MX_ERR_INVALID, "ports / params is NULL");
+    if (n) {
+        if (n != params->n_views) throw Error(MX_ERR_INVALID, "multiview: n must equal params->n_views");
+        check_multiview_params(*params, true);
+        for (size_t i = 0; i < n; ++i) {
+            const mx_port_ref pr = ports[i];
+            if (pr.node >= nodes_.size() || pr.port >= nodes_[pr.node].out_type.size()) throw Error(MX_ERR_INVALID, "multiview: output terminal out of range");
+            if (nodes_[pr.node].out_type[pr.port] != MX_VIDEO) throw Error(MX_ERR_TYPE, "multiview: an audio port has no picture");
+        }
+    }
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    sync();   // the last run's launch is done with the tables and the pool
+    mv_ports_.assign(ports, ports + n);
+    mv_c_ = 0; mv_last_ = -1; mv_now_ = false; mv_run_seen_ = false;
+    mv_out_ = FrameRef(); mv_pool_.clear(); mv_tabs_ = MultiviewTabs{};
+    mv_status_ = mx_multiview_status{0, 0, 0, 0};
+    mv_par_ = mx_multiview_params{};
+    if (n) mv_par_ = *params;
+}
+
+FrameRef Graph::multiview_output(mx_multiview_status* status) {
+    if (mv_ports_.empty()) throw Error(MX_ERR_INVALID, "no multiview is set");
+    if (!mv_run_seen_) throw Error(MX_ERR_INVALID, "no run since the multiview was set");
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    if (mv_out_) { wait_tail(-1); sync(); }   // a frame crossing the ABI: its pixels are there, whatever stream the caller reads them on
+    if (status) *status = mv_status_;
+    return mv_out_;
 }
 
 // One tap's record of the tick being run.  Ordering: everything is on stream_ -- a graph with video nodes never runs anything on the second

@@ -174,6 +174,9 @@ public:
     // video scope taps (mx_graph_set_video_scopes / mx_graph_read_video_scopes): histograms, waveform and vectorscope of the frames on video ports
     void set_video_scopes(const mx_port_ref* ports, size_t n, const mx_video_scope_params* params);
     size_t read_video_scopes(void* dst, size_t cap_bytes);   // the last run's records; returns how many
+    // the multiviewer as a tap on video ports (mx_graph_set_multiview / mx_graph_multiview_output): the ports' frames tiled on one canvas
+    void set_multiview(const mx_port_ref* ports, size_t n, const mx_multiview_params* params);   // n = 0 removes
+    FrameRef multiview_output(mx_multiview_status* status);   // the canvas of the last run's last recorded tick (null: none recorded)
     void read_output_i16(uint32_t node, uint32_t port, int16_t* host, size_t frames);   // sink hand-off format
     void write_source_i16(uint32_t node, const int16_t* host, size_t frames);            // ingest format
     float* output_ptr(uint32_t node, uint32_t port, size_t* floats_per_tick, bool stream_ordered_consumer = true /* false: a caller inside the library that orders itself
@@ -232,6 +235,7 @@ private:
     FrameRef keyed_source_frame(uint32_t id, const FrameRef& src);   // SOURCE_VIDEO with a key set: src keyed under the node's setting (once per frame)
     FrameRef placed_source_frame(uint32_t id, const FrameRef& src);  // SOURCE_VIDEO with a placement set: src (keyed first where a key is set) placed, once per frame
     void launch_pending_rgba(Node& n, size_t count, bool with_queued_scales);   // the `count` oldest pending chains of a sink
+    void render_multiview();                                             // the canvas of the tick being run (run_video_tick, at the end of the run's last recorded tick)
     void launch_video_scope(uint32_t tap, const Node::VOut& v);          // one tap's record of the tick being run (run_video_tick, on a recorded tick)
     // one launch sequence over ticks [call_off, call_off + n_calls) of the current run
     void run_span(uint64_t t0, size_t fpc, uint32_t call_off, uint32_t n_calls, uint32_t run_calls);
@@ -319,6 +323,17 @@ private:
     uint32_t scope_n_ = 0;                  // recorded ticks of the run in progress / of the last run
     uint32_t video_tick_in_run_ = 0;        // the tick run_video_tick is running, counted from the run's first
     bool scope_now_ = false, scope_run_seen_ = false;   // the tick being run is recorded; a run was made since the taps were set
+    // the multiviewer: the tapped ports in view order; mv_c_ is its own hop counter (the scopes' rule).  A run renders one canvas, at the end of tick mv_last_ (the last
+    // tick of the run its counter records; -1: none); canvases come from mv_pool_, rewritten only when the pool alone holds them
+    std::vector<mx_port_ref> mv_ports_;
+    mx_multiview_params mv_par_{};
+    MultiviewTabs mv_tabs_;
+    std::vector<FrameRef> mv_pool_;
+    FrameRef mv_out_;
+    mx_multiview_status mv_status_{0, 0, 0, 0};
+    uint64_t mv_c_ = 0;
+    int64_t mv_last_ = -1;
+    bool mv_now_ = false, mv_run_seen_ = false;
     float perf_od_ms_ = 0.f;                // OutputDevice launches of the last collected run
     bool prof_this_run_ = false;
     size_t plot_job_off_ = 0;

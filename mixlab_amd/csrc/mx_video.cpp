@@ -2,6 +2,7 @@
 #include "mx_video.hpp"
 
 #include <algorithm>
+#include <array>
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -860,6 +861,117 @@ void place_into(DFrame* in, const mx_video_place_params& p, const PlaceTables& t
     }
     launch_video_place(a, s);
     hip_check(hipGetLastError(), "place launch");
+}
+
+// ---------------------------------------------------------------------------------------------
+// the multiviewer (mixlab_gpu.h mx_video_multiview; kernel in mx_k_multiview.hip)
+// ---------------------------------------------------------------------------------------------
+void check_multiview_params(const mx_multiview_params& p, bool graph_form) {
+    auto even = [](uint32_t v) { return (v & 1u) == 0u; };
+    if (!even(p.canvas_w) || !even(p.canvas_h) || p.canvas_w < 2 || p.canvas_h < 2 || p.canvas_w > 16384u || p.canvas_h > 16384u)
+        throw Error(MX_ERR_INVALID, "mx_multiview_params: canvas_w / canvas_h must be even, 2 .. 16384");
+    if (p._pad != 0) throw Error(MX_ERR_INVALID, "mx_multiview_params: _pad must be 0");
+    if (p.n_views < 1 || p.n_views > MX_MULTIVIEW_MAX) throw Error(MX_ERR_INVALID, "mx_multiview_params: n_views is 1 .. MX_MULTIVIEW_MAX");
+    if (graph_form && p.hop == 0) throw Error(MX_ERR_INVALID, "mx_multiview_params: hop must be >= 1");
+    for (uint32_t i = 0; i < p.n_views; ++i) {
+        const mx_multiview_view& v = p.view[i];
+        const std::string who = "mx_multiview_params: view " + std::to_string(i);
+        if (!even(v.x) || !even(v.y) || !even(v.w) || !even(v.h)) throw Error(MX_ERR_INVALID, who + ": x, y, w, h must be even");
+        if (!even(v.border) || v.border > 64u) throw Error(MX_ERR_INVALID, who + ": border must be even, 0 .. 64");
+        if (v.fit > 1) throw Error(MX_ERR_INVALID, who + ": fit must be 0 or 1");
+        if (v.w < 2u * v.border + 2u || v.h < 2u * v.border + 2u) throw Error(MX_ERR_INVALID, who + ": w and h must be >= 2 * border + 2");
+        if ((uint64_t)v.x + v.w > p.canvas_w || (uint64_t)v.y + v.h > p.canvas_h) throw Error(MX_ERR_INVALID, who + ": the rectangle lies outside the canvas");
+        for (uint32_t k = 0; k < i; ++k) {
+            const mx_multiview_view& o = p.view[k];
+            if (v.x < o.x + o.w && o.x < v.x + v.w && v.y < o.y + o.h && o.y < v.y + v.h) throw Error(MX_ERR_INVALID, who + " overlaps view " + std::to_string(k));
+        }
+    }
+}
+
+// May the LDS-tiled form take this (source -> picture) pair of one plane?  The placer's host check on the H table (t + 8192 fits 16 bits), at this kernel's own tap
+// bound, and every coefficient of both tables an i16 (the kernel keeps them so in LDS).
+static bool multiview_tiled_check(uint32_t sw, uint32_t pw, uint32_t sh, uint32_t ph);
+static bool multiview_tiled_ok(uint32_t sw, uint32_t pw, uint32_t sh, uint32_t ph) {
+    const uint32_t hn = tap_count(sw, pw), vn = tap_count(sh, ph);
+    if (hn > MX_MULTIVIEW_TAP_BOUND || vn > MX_MULTIVIEW_TAP_BOUND) return false;
+    // the answers are kept (the stateless call asks again for every view of every call; a graph asks once per view and size)
+    static std::mutex mu;
+    static auto& known = *new std::map<std::array<uint32_t, 4>, bool>();
+    std::lock_guard<std::mutex> lk(mu);
+    const std::array<uint32_t, 4> key{sw, pw, sh, ph};
+    auto it = known.find(key);
+    if (it != known.end()) return it->second;
+    if (known.size() >= 256) known.clear();
+    return known[key] = multiview_tiled_check(sw, pw, sh, ph);
+}
+static bool multiview_tiled_check(uint32_t sw, uint32_t pw, uint32_t sh, uint32_t ph) {
+    const uint32_t hn = tap_count(sw, pw);
+    std::vector<int32_t> f, k;
+    make_taps(sw, pw, f, k);
+    for (size_t o = 0; o * hn < k.size(); ++o) {
+        int64_t pos = 0, neg = 0;
+        for (uint32_t j = 0; j < hn; ++j) { const int32_t v = k[o * hn + j]; if (v > 0) pos += v; else neg += v; if (v < -32768 || v > 32767) return false; }
+        if (((255 * pos + 64) >> 7) + 8192 > 65535 || ((255 * neg + 64) >> 7) + 8192 < 0) return false;
+    }
+    make_taps(sh, ph, f, k);
+    for (int32_t v : k) if (v < -32768 || v > 32767) return false;
+    return true;
+}
+
+uint32_t multiview_into(DFrame* const* in, const mx_multiview_params& p, MultiviewTabs& tabs, DFrame* out, hipStream_t s) {
+    if (out->fmt != MX_PIXFMT_YUV420P || out->with_alpha || out->width != p.canvas_w || out->height != p.canvas_h) throw Error(MX_ERR_INTERNAL, "multiview: the output frame is not yuv420p of the canvas size");
+    MvView views[MX_MULTIVIEW_MAX * 3];
+    std::memset(views, 0, sizeof views);   // (padding bytes travel to the device too)
+    uint32_t shown = 0;
+    for (uint32_t i = 0; i < p.n_views; ++i) {
+        const mx_multiview_view& v = p.view[i];
+        DFrame* const f = in[i];
+        // the picture rectangle, in luma samples (pw = 0: not shown)
+        uint32_t px = 0, py = 0, pw = 0, ph = 0;
+        if (f && f->fmt == MX_PIXFMT_YUV420P) {
+            if (!f->data[0]) throw Error(MX_ERR_INTERNAL, "multiview: a frame without pixels");
+            const uint32_t ix = v.x + v.border, iy = v.y + v.border, iw = v.w - 2u * v.border, ih = v.h - 2u * v.border;
+            if (v.fit) {
+                const ScaleGeometry g = scaler_geometry(f->width, f->height, iw, ih);
+                px = ix + g.letterbox_x; py = iy + g.letterbox_y; pw = g.scaled_w; ph = g.scaled_h;
+            } else { px = ix; py = iy; pw = iw; ph = ih; }
+            if (pw < 2 || ph < 2 || (uint64_t)f->width > 32ull * pw || (uint64_t)f->height > 32ull * ph) pw = ph = 0;
+        }
+        const PlaceTables* t = nullptr;
+        if (pw) {
+            mx_video_place_params q{};   // a whole-frame crop into pw x ph: the placer's tables, and its list of kept ones
+            q.canvas_w = p.canvas_w; q.canvas_h = p.canvas_h; q.dst_w = pw; q.dst_h = ph;
+            if (!tabs.t[i] || !place_tables_fit(*tabs.t[i], f, q)) {
+                tabs.t[i] = make_place_tables(f, q);
+                for (int c = 0; c < 2; ++c) tabs.tiled[i][c] = multiview_tiled_ok(f->width >> c, pw >> c, f->height >> c, ph >> c);
+            }
+            t = tabs.t[i].get();
+            shown |= 1u << i;
+        }
+        for (int pl = 0; pl < 3; ++pl) {
+            const int c = pl ? 1 : 0;
+            MvView& d = views[i * 3u + (uint32_t)pl];
+            d.rx = (int32_t)(v.x >> c); d.ry = (int32_t)(v.y >> c); d.rw = (int32_t)(v.w >> c); d.rh = (int32_t)(v.h >> c); d.bt = (int32_t)(v.border >> c);   // even numbers: the halves are exact
+            d.border = pl == 0 ? v.border_y : (pl == 1 ? v.border_u : v.border_v);
+            if (!t) continue;
+            d.src = f->data[pl]; d.src_stride = f->stride[pl]; d.sw = f->width >> c; d.sh = f->height >> c;
+            d.px = (int32_t)(px >> c); d.py = (int32_t)(py >> c); d.pw = (int32_t)(pw >> c); d.ph = (int32_t)(ph >> c);
+            d.hfirst = t->tab[c][0]; d.hcoef = t->tab[c][1]; d.vfirst = t->tab[c][2]; d.vcoef = t->tab[c][3];
+            d.hn = t->taps[c][0]; d.vn = t->taps[c][1];
+            d.tiled = tabs.tiled[i][c] ? 1u : 0u;
+        }
+    }
+    MvArgs a{};
+    for (int pl = 0; pl < 3; ++pl) {
+        MvPlane& pp = a.p[pl];
+        pp.dst = out->data[pl]; pp.dst_stride = out->stride[pl]; pp.w = p.canvas_w >> (pl ? 1 : 0); pp.h = p.canvas_h >> (pl ? 1 : 0);
+        pp.bg = pl == 0 ? p.bg_y : (pl == 1 ? p.bg_u : p.bg_v);
+        pp.blank = pl ? 0x80u : 0u; pp.pad = pl ? 0x80u : 0u;   // DFrame::create: blank picture
+    }
+    a.n_views = p.n_views;
+    launch_video_multiview(a, views, s);
+    hip_check(hipGetLastError(), "multiview launch");
+    return shown;
 }
 
 }  // namespace mx

@@ -210,6 +210,41 @@ bool place_tables_fit(const PlaceTables& t, const DFrame* in, const mx_video_pla
 // `in` placed under p into `out` (yuva420p of the canvas size, contents undefined: every byte of its four planes is written), asynchronous on s
 void place_into(DFrame* in, const mx_video_place_params& p, const PlaceTables& t, DFrame* out, hipStream_t s);
 
+// ---- the multiviewer (mixlab_gpu.h mx_video_multiview; mx_k_multiview.hip) ----
+// A workgroup writes one MX_MULTIVIEW_TILE_W x MX_MULTIVIEW_TILE_H byte tile of one canvas plane and walks the views that meet it; the LDS-tiled form takes
+// axes of up to MX_MULTIVIEW_TAP_BOUND taps.
+enum { MX_MULTIVIEW_TILE_W = 64, MX_MULTIVIEW_TILE_H = 16, MX_MULTIVIEW_TAP_BOUND = 20 };
+struct MvView {                                    // one view on one canvas plane, every number in samples of that plane
+    const uint8_t* src;                            // the source PLANE (its row 0, column 0); nullptr: the view is not shown (frame and blank only)
+    const int32_t* hfirst; const int32_t* hcoef;   // [pw], [pw][hn]: the tables of (sw -> pw)
+    const int32_t* vfirst; const int32_t* vcoef;   // [ph], [ph][vn]: the tables of (sh -> ph)
+    uint32_t src_stride, sw, sh;                   // the source plane's stride and visible size
+    uint32_t hn, vn;
+    uint32_t tiled;                                // the LDS-tiled form may be used (tap counts within the bound, H-pass values within 16 bits)
+    int32_t rx, ry, rw, rh;                        // the view's rectangle, frame included
+    int32_t bt;                                    // the frame's thickness: the inner rectangle is the rectangle inset by bt
+    int32_t px, py, pw, ph;                        // the picture rectangle (inside the inner one)
+    uint32_t border;                               // the frame's byte
+    uint32_t _pad;
+};
+struct MvPlane {
+    uint8_t* dst; uint32_t dst_stride, w, h;       // the canvas plane and its visible size
+    uint32_t bg, blank, pad;                       // the byte outside every view, the scaler's blank, the byte of the stride padding
+    uint32_t tile_start, tiles_x;                  // launcher-filled: the plane's first workgroup, workgroups per tile row
+};
+struct MvArgs { MvPlane p[3]; const MvView* views; uint32_t n_views, _pad; };   // views[view * 3 + plane], in device memory
+// views: host array [n_views * 3]; it travels through page-locked staging kept per (device, stream) into device memory, then ONE launch on s
+void launch_video_multiview(MvArgs a, const MvView* views, hipStream_t s);
+void multiview_stream_retired(hipStream_t s);      // the stream is going away: free the staging kept for it
+struct MultiviewTabs {   // per view, of (source size -> picture rectangle): rebuilt only when either changes
+    std::shared_ptr<const PlaceTables> t[16];
+    bool tiled[16][2] = {};   // [view][luma/chroma]: tap counts within MX_MULTIVIEW_TAP_BOUND, H-pass values within 16 bits, every coefficient an i16
+};
+void check_multiview_params(const mx_multiview_params& p, bool graph_form);   // MX_ERR_INVALID outside what the header states; touches no device
+// the frames in[0 .. n_views) (nullptr: no frame; pixels present) under p into `out` (yuv420p of the canvas size, contents undefined: every byte of its three planes
+// is written), asynchronous on s; returns the shown mask
+uint32_t multiview_into(DFrame* const* in, const mx_multiview_params& p, MultiviewTabs& tabs, DFrame* out, hipStream_t s);
+
 // ---- exact rationals: MediaTime / MediaDuration (util/src/time.rs:9-75, num_rational::Ratio<i64>) ----
 struct Rational {
     int64_t num = 0, den = 1;

@@ -369,6 +369,46 @@ def graph_set_video_source_place(g, node, params):
     check(lib.mx_graph_set_video_source_place(g._h, node, C.byref(params) if params is not None else None))
 
 
+def MultiviewView(x, y, w, h, border=0, colour=(0, 0x80, 0x80), fit=1) -> abi.MultiviewView:
+    """mx_multiview_view: the view's rectangle on the canvas (frame included), the tally frame's thickness and (Y, U, V) colour, fit 0 = stretch / 1 = keep the aspect"""
+    return abi.MultiviewView(int(x), int(y), int(w), int(h), int(border), int(colour[0]), int(colour[1]), int(colour[2]), int(fit))
+
+
+def MultiviewParams(canvas_w, canvas_h, views, bg=(0, 0x80, 0x80), hop=1) -> abi.MultiviewParams:
+    """mx_multiview_params: up to 16 non-overlapping views (MultiviewView) on a canvas_w x canvas_h canvas of colour bg; hop: in a graph, render every hop-th video tick"""
+    views = list(views)
+    p = abi.MultiviewParams(int(canvas_w), int(canvas_h), int(bg[0]), int(bg[1]), int(bg[2]), 0, len(views), int(hop))
+    for i, v in enumerate(views[:abi.MULTIVIEW_MAX]):
+        p.view[i] = v
+    return p
+
+
+def multiview(frames, params, stream=None):
+    """mx_video_multiview: frames[i] (a DFrame or None) resampled into view i of a NEW opaque yuv420p canvas, one launch -> (canvas, shown mask)"""
+    frames = list(frames)
+    arr = (C.c_void_p * max(1, len(frames), params.n_views))(*[f.handle if f is not None else None for f in frames])
+    h, shown = C.c_void_p(), C.c_uint32()
+    check(lib.mx_video_multiview(arr, C.byref(params), C.byref(h), C.byref(shown), stream))
+    return DFrame(handle=h.value, stream=stream), shown.value
+
+
+def graph_set_multiview(g, ports, params):
+    """A multiviewer tapped on the graph's video output ports [(node, port), ...], one per view of params (mx_graph_set_multiview); ports [] removes it."""
+    ports = list(ports)
+    if not ports:
+        check(lib.mx_graph_set_multiview(g._h, None, 0, None))
+        return
+    pa = (abi.PortRef * len(ports))(*[abi.PortRef(int(n), int(p)) for (n, p) in ports])
+    check(lib.mx_graph_set_multiview(g._h, pa, len(ports), C.byref(params)))
+
+
+def graph_multiview_output(g):
+    """-> (canvas of the last run's last recorded tick or None, abi.MultiviewStatus) (mx_graph_multiview_output)"""
+    h, st = C.c_void_p(), abi.MultiviewStatus()
+    check(lib.mx_graph_multiview_output(g._h, C.byref(h), C.byref(st)))
+    return (DFrame(handle=h.value) if h.value else None), st
+
+
 class VideoMixer:
     """mx_video_mixer_*: VideoMixer::run_tick on device-resident frames (src/module/video_mixer.rs)."""
 
