@@ -968,8 +968,10 @@ void mx_video_mixer_destroy(mx_video_mixer* m);
 int mx_graph_set_video_source(mx_graph* g, uint32_t node, mx_dframe* frame, int64_t dur_num, int64_t dur_den,
                               int64_t off_num, int64_t off_den, int repeat);
 /* A source that delivers a NEW frame on every tick, cycling through `n` frames (a decoder feeding the graph: MediaSource emits
- * at most one VideoFrame per tick, media_source.rs:93-126): tick k of the graph's life emits frames[k mod n] with the given
- * duration hint and offset.  The graph retains the frames.  n = 0 clears the source. */
+ * at most one VideoFrame per tick, media_source.rs:93-126): the k-th tick on which the ring delivers, counted from 0 at this call, emits
+ * frames[k mod n] with the given duration hint and offset.  The count is carried across runs and does not depend on first_tick; a tick on which
+ * queued frames (mx_graph_queue_video_source) take the ring's place does not advance it -- a decoder that was not asked delivers its next frame
+ * when it is asked again.  A call with n > 0 drops a set frame (mx_graph_set_video_source).  The graph retains the frames.  n = 0 clears the source. */
 int mx_graph_set_video_source_ring(mx_graph* g, uint32_t node, mx_dframe* const* frames, size_t n, int64_t dur_num, int64_t dur_den,
                                    int64_t off_num, int64_t off_den);
 /* Row-band sharding of one composited picture over ranks (mixlab_amd/shard.py): a rank's graph is the cascade at (full_w x
