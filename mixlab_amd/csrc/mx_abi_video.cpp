@@ -301,12 +301,12 @@ int mx_video_scope(const mx_dframe* in, const mx_video_scope_params* params, voi
     });
 }
 int mx_graph_set_video_scopes(mx_graph* g, const mx_port_ref* ports, size_t n, const mx_video_scope_params* params) {
-    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->set_video_scopes(ports, n, params); });
+    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->video_scopes().set(ports, n, params); });
 }
 int mx_graph_read_video_scopes(mx_graph* g, void* dst, size_t cap_bytes, uint32_t* n_records) {
     return guard([&] {
         REQUIRE(g, "graph is NULL");
-        const size_t n = g->g->read_video_scopes(dst, cap_bytes);
+        const size_t n = g->g->video_scopes().read(dst, cap_bytes);
         if (n_records) *n_records = (uint32_t)n;
     });
 }
@@ -400,14 +400,14 @@ int mx_graph_set_multiview(mx_graph* g, const mx_port_ref* ports, size_t n, cons
         // the parameters first: what the header refuses is refused before a graph -- or a device -- is looked at
         if (n && params) { REQUIRE(n == params->n_views, "multiview: n must equal params->n_views"); mx::check_multiview_params(*params, true); }
         REQUIRE(g, "graph is NULL");
-        g->g->set_multiview(ports, n, params);
+        g->g->multiview().set(ports, n, params);
     });
 }
 int mx_graph_multiview_output(mx_graph* g, mx_dframe** out, mx_multiview_status* status) {
     return guard([&] {
         REQUIRE(g && out, "NULL argument");
         *out = nullptr;
-        FrameRef r = g->g->multiview_output(status);
+        FrameRef r = g->g->multiview().output(status);
         if (r) { r->retain(); *out = H(r.f); }
     });
 }

@@ -271,12 +271,15 @@ Graph::Graph(const mx_node* nodes, size_t n_nodes, const mx_edge* edges, size_t 
             mx_monitor_params p; std::memcpy(&p, n.params.data(), sizeof p);
             if (p.width == 0 || p.height == 0 || (p.width & 1) || (p.height & 1) || p.width > 16384 || p.height > 16384)
                 throw Error(MX_ERR_INVALID, "monitor picture must be non-zero, even and at most 16384 a side");
-            n.mon_scaler = std::make_shared<Scaler>(p.width, p.height, stream_);
-            if (n.params.size() == sizeof(mx_monitor_params_ex)) { mx_monitor_params_ex px; std::memcpy(&px, n.params.data(), sizeof px); n.mon_depth = px.queue_depth; }
+            n.mon = std::make_unique<MonitorState>();
+            n.mon->scaler = std::make_shared<Scaler>(p.width, p.height, stream_);
+            if (n.params.size() == sizeof(mx_monitor_params_ex)) { mx_monitor_params_ex px; std::memcpy(&px, n.params.data(), sizeof px); n.mon->depth = px.queue_depth; }
             // without a queue depth every tick of a submission keeps its scaled picture on the device until the next run
-            const uint64_t kept = (uint64_t)(n.mon_depth ? n.mon_depth : std::max<uint32_t>(1u, o.max_ticks_per_run)) * (((uint64_t)p.width + 63) & ~63ull) * p.height * 3 / 2;
+            const uint64_t kept = (uint64_t)(n.mon->depth ? n.mon->depth : std::max<uint32_t>(1u, o.max_ticks_per_run)) * (((uint64_t)p.width + 63) & ~63ull) * p.height * 3 / 2;
             if (kept > (64ull << 30)) throw Error(MX_ERR_NOMEM, "a Monitor that keeps every tick of a submission would hold more than 64 GiB of pictures: give it a queue depth (mx_monitor_params_ex) or fewer ticks per run");
         }
+        if (n.kind == MX_KIND_SOURCE_VIDEO) n.vsrc = std::make_unique<VideoSourceState>();
+        if (n.kind == MX_KIND_VIDEO_TO_RGBA) n.rgba = std::make_unique<RgbaSinkState>();
         if (n.kind == MX_KIND_VIDEO_MIXER || n.kind == MX_KIND_SOURCE_VIDEO || n.kind == MX_KIND_VIDEO_TO_RGBA || n.kind == MX_KIND_MONITOR) has_video_ = true;
         n.vout.resize(n.out_type.size());
     }
@@ -520,8 +523,8 @@ Graph::~Graph() {
     if (tail_stream_) (void)hipStreamSynchronize(tail_stream_);
     if (stream_) (void)hipStreamSynchronize(stream_);
     if (tail_stream_) { (void)hipStreamDestroy(tail_stream_); (void)hipEventDestroy(ev_head_done_); for (auto& e : ev_tail_done_) (void)hipEventDestroy(e); }
-    for (Node& n : nodes_) { n.vmixer.reset(); n.vout.clear(); n.vsrc = FrameRef(); n.vsrc_ring.clear(); n.vsrc_sched.clear(); n.vkey_done.clear(); n.vkey_pool.clear(); n.vplace_done.clear(); n.vplace_pool.clear(); n.vplace_tabs.reset(); }
-    mv_out_ = FrameRef(); mv_pool_.clear();
+    for (Node& n : nodes_) { n.vmixer.reset(); n.vout.clear(); n.vsrc.reset(); n.rgba.reset(); n.mon.reset(); }   // every frame the video nodes hold, while the stream is there
+    multiview_.clear();
     prof_runs_.clear(); prof_pool_.clear();
     for (Stage& st : stage_) { if (st.done) (void)hipEventDestroy(st.done); if (st.host) (void)hipHostFree(st.host); }
     // the descriptor ring launch_video_batch keeps per stream goes with a stream this graph OWNS; a caller's stream may be shared with other
@@ -1062,23 +1065,14 @@ void Graph::run(uint64_t t0, size_t fpc, uint32_t n_calls, float* ms_by_kind, fl
     const size_t frames = fpc * (size_t)n_calls;
     auto drop_schedules = [&] { for (uint32_t id : sched_nodes_) { nodes_[id].sched.clear(); nodes_[id].gate_sched.clear(); } sched_nodes_.clear(); };
     if (frames > cap_frames_) { drop_schedules(); throw Error(MX_ERR_INVALID, "n_ticks exceeds max_ticks_per_run"); }
-    if (n_calls == 0 || fpc == 0) { drop_schedules(); last_calls_ = n_calls; last_frames_per_call_ = fpc; for (AudioTapSet* s : taps_) s->empty_run(); scope_n_ = 0; mv_out_ = FrameRef(); mv_status_ = mx_multiview_status{0, 0, 0, 0}; return; }
+    if (n_calls == 0 || fpc == 0) { drop_schedules(); last_calls_ = n_calls; last_frames_per_call_ = fpc; for (AudioTapSet* s : taps_) s->empty_run(); scopes_.empty_run(); multiview_.empty_run(); return; }
     // keyed / placed video sources: a frame the transform cannot take fails the run HERE, before anything of it is launched or any node's state has moved
     for (uint32_t id : video_order_) {
-        const Node& n = nodes_[id];
-        if (n.kind != MX_KIND_SOURCE_VIDEO || !(n.vkey_on || n.vplace_on)) continue;
-        const uint64_t tick0 = t0 / spt_, last = tick0 + n_calls - 1;
+        const VideoSourceState* vs = nodes_[id].vsrc.get();
+        if (!vs || !vs->transform.active()) continue;
+        const uint64_t tick0 = t0 / spt_;
         const char* why = nullptr;
-        auto look = [&](const DFrame* f) {
-            if (why) return;
-            if (n.vkey_on && !key_input_ok(f)) why = "the keyer takes yuv420p or yuva420p frames (mx_graph_set_video_source_key)";
-            else if (n.vplace_on) why = place_input_error(f, n.vplace);
-        };
-        for (const Node::VSched& e : n.vsrc_sched) if (e.tick >= tick0 && e.tick <= last) look(e.frame.f);
-        if (n.vsrc_sched.empty() || n.vsrc_sched.back().tick < last) {   // ticks of the run past the queue fall through to the ring / the set frame
-            if (!n.vsrc_ring.empty()) { for (const FrameRef& f : n.vsrc_ring) look(f.f); }
-            else if (n.vsrc && (n.vsrc_repeat || n.vsrc_pending)) look(n.vsrc.f);
-        }
+        vs->each_deliverable(tick0, tick0 + n_calls - 1, [&](const DFrame* f) { if (!why) why = vs->transform.input_error(f); });
         if (why) { drop_schedules(); throw Error(MX_ERR_INVALID, "node " + std::to_string(id) + " (SOURCE_VIDEO): " + why); }
     }
     hip_check(hipSetDevice(device_), "hipSetDevice");
@@ -1127,20 +1121,9 @@ void Graph::run(uint64_t t0, size_t fpc, uint32_t n_calls, float* ms_by_kind, fl
         for (const Node::SchedEv& ev : n.sched) { mx_output_device_params q; std::memcpy(&q, ev.params.data(), sizeof q); cmax = std::max(cmax, q.channels); }
         if (cmax > n.od_cmax) { sync(); od_grow(n, cmax); }
     }
-    for (uint32_t id : video_order_) if (nodes_[id].kind == MX_KIND_MONITOR) nodes_[id].mon_ticks.clear();
-    if (!scopes_.empty()) {   // scope taps: the records this run will count into are cleared now, in one fill on stream_ ahead of every launch of the run
-        const uint64_t hop = scope_par_.hop, first = (hop - scope_c_ % hop) % hop;   // the first recorded tick of the run
-        const size_t n_rec = first < n_calls ? (size_t)((n_calls - first + hop - 1) / hop) : 0;
-        if (n_rec > scope_cap_) throw Error(MX_ERR_INTERNAL, "video scopes: the run records more ticks than the taps were sized for");
-        if (n_rec) hip_check(hipMemsetAsync(scope_rec_.p, 0, n_rec * scopes_.size() * scope_rec_bytes_, stream_), "hipMemsetAsync(video scope records)");
-        scope_n_ = 0; scope_run_seen_ = true;
-    }
-    if (!mv_ports_.empty()) {   // the multiviewer renders the run's LAST recorded tick only: which one that is follows from its counter now
-        const uint64_t hop = mv_par_.hop, first = (hop - mv_c_ % hop) % hop;
-        const uint64_t n_rec = first < n_calls ? (n_calls - first + hop - 1) / hop : 0;
-        mv_last_ = n_rec ? (int64_t)(first + (n_rec - 1) * hop) : -1;
-        mv_out_ = FrameRef(); mv_status_ = mx_multiview_status{(uint32_t)n_rec, 0, 0, 0}; mv_run_seen_ = true;
-    }
+    for (uint32_t id : video_order_) if (nodes_[id].mon) nodes_[id].mon->ticks.clear();
+    scopes_.begin_run(n_calls);      // the records this run will count into are cleared now, on stream_ ahead of every launch of the run
+    multiview_.begin_run(n_calls);   // the multiviewer renders the run's LAST recorded tick only
 
     // Plotter bookkeeping is host logic (plotter.rs:37-40): count += 1 per call, fire on every 6th
     size_t total_fired = 0;
@@ -1349,9 +1332,9 @@ void Graph::run_span(uint64_t t0, size_t fpc, uint32_t call_off, uint32_t n_call
     }
     // video sub-graph: tick by tick (frames arrive per tick; nothing to batch over time)
     if (has_video_) {
-        for (uint32_t c = 0; c < n_calls; ++c) { video_tick_in_run_ = call_off + c; run_video_tick(t0 + (uint64_t)c * fpc); }
+        for (uint32_t c = 0; c < n_calls; ++c) run_video_tick(t0 + (uint64_t)c * fpc, call_off + c);
         flush_scales(stream_);
-        for (uint32_t id : video_order_) { Node& vn = nodes_[id]; if (!vn.rgba_pending.empty()) launch_pending_rgba(vn, vn.rgba_pending.size(), false); vn.rgba_calls = 0; }   // the last ticks' sinks
+        for (uint32_t id : video_order_) if (nodes_[id].rgba) nodes_[id].rgba->end_run(stream_);   // the last ticks' sinks
     }
     if (prof && has_video_) hip_check(hipEventRecord(prof->video_end, stream_), "hipEventRecord");
     // after everything else of the span on stream_ (the video section included): its profile interval starts at the latest event recorded there
@@ -1505,7 +1488,7 @@ void Graph::adopt_state(Graph& old, const int32_t* old_of_new, size_t n) {
         if (j < 0) continue;
         Node& nn = nodes_[i]; Node& on = old.nodes_[j];
         if (nn.kind == MX_KIND_PLOTTER) nn.plot_count = on.plot_count;          // plotter.rs:37-40
-        if (nn.kind == MX_KIND_MONITOR) { nn.mon_has_epoch = on.mon_has_epoch; nn.mon_epoch = on.mon_epoch; nn.mon_queued = on.mon_queued; }   // Monitor.epoch (monitor.rs:122)
+        if (nn.mon) { nn.mon->has_epoch = on.mon->has_epoch; nn.mon->epoch = on.mon->epoch; nn.mon->queued = on.mon->queued; }   // Monitor.epoch (monitor.rs:122)
         if (nn.kind == MX_KIND_VIDEO_MIXER && on.vmixer) {                       // stored frames, scalers, expiry times
             mx_video_mixer_params p; std::memcpy(&p, nn.params.data(), sizeof p);
             nn.vmixer = std::move(on.vmixer);
@@ -1522,7 +1505,7 @@ void Graph::adopt_state(Graph& old, const int32_t* old_of_new, size_t n) {
             nn.od_channels = on.od_channels; nn.od_left = on.od_left; nn.od_right = on.od_right; nn.params = on.params;   // (mixlab_gpu.h: the new build's params are not applied)
             if (on.od_lag->exchange(false)) nn.od_lag->store(true);
         }
-        if (nn.kind == MX_KIND_SOURCE_VIDEO) { nn.vsrc_ring = on.vsrc_ring; nn.vsrc_ring_pos = on.vsrc_ring_pos; nn.vsrc_sched = on.vsrc_sched; nn.vband = on.vband; nn.vband_pool = on.vband_pool; nn.vsrc = on.vsrc; nn.vsrc_dur = on.vsrc_dur; nn.vsrc_off = on.vsrc_off; nn.vsrc_repeat = on.vsrc_repeat; nn.vsrc_pending = on.vsrc_pending; }
+        if (nn.vsrc) nn.vsrc->adopt(*on.vsrc);
     }
     hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
 }
@@ -1659,60 +1642,6 @@ void Graph::launch_tap_set(AudioTapSet& s, uint32_t n_calls, ProfSpan* prof) {
     prof->meters_tail = !deferred_.taps.empty();
 }
 
-// ---- video scope taps (mixlab_gpu.h mx_graph_set_video_scopes) ----
-
-void Graph::set_video_scopes(const mx_port_ref* ports, size_t n, const mx_video_scope_params* params) {
-    hip_check(hipSetDevice(device_), "hipSetDevice");
-    if (n && (!ports || !params)) throw Error(MX_ERR_INVALID, "ports / params is NULL");
-    if (n > 0xffffffu) throw Error(MX_ERR_INVALID, "more than 2^24 video scope taps");
-    if (n) {
-        const uint32_t C = params->wave_cols;
-        if (C != 0 && C != 64 && C != 128 && C != 256) throw Error(MX_ERR_INVALID, "mx_video_scope_params: wave_cols must be 0, 64, 128 or 256");
-        if (params->hop == 0) throw Error(MX_ERR_INVALID, "mx_video_scope_params: hop must be >= 1");
-    }
-    std::vector<uint64_t> keys(n);
-    for (size_t i = 0; i < n; ++i) {
-        const mx_port_ref pr = ports[i];
-        if (pr.node >= nodes_.size() || pr.port >= nodes_[pr.node].out_type.size()) throw Error(MX_ERR_INVALID, "video scope: output terminal out of range");
-        if (nodes_[pr.node].out_type[pr.port] != MX_VIDEO) throw Error(MX_ERR_TYPE, "video scope: an audio port has no picture (meters and spectrum taps observe audio ports)");
-        keys[i] = (uint64_t)pr.node << 32 | pr.port;
-    }
-    std::sort(keys.begin(), keys.end());
-    if (std::adjacent_find(keys.begin(), keys.end()) != keys.end()) throw Error(MX_ERR_INVALID, "video scope: duplicate (node, port)");
-    size_t rec_bytes = 0, cap = 0;
-    if (n) {
-        rec_bytes = scope_record_bytes(params->wave_cols, params->vectorscope);
-        const size_t max_ticks = std::max<size_t>(1, cap_frames_ / spt_);
-        cap = (max_ticks + params->hop - 1) / params->hop;
-        const unsigned __int128 need = (unsigned __int128)cap * n * rec_bytes;
-        if (need > ((unsigned __int128)4 << 30))
-            throw Error(MX_ERR_NOMEM, "video scopes: the records of one run (ceil(max_ticks_per_run / hop) x taps x record bytes) exceed 4 GiB: raise hop");
-    }
-    sync();   // the last run's launches are done with the records
-    scopes_.assign(ports, ports + n);
-    scope_c_ = 0; scope_n_ = 0; scope_run_seen_ = false; scope_now_ = false;
-    scope_rec_.free_();
-    scope_rec_bytes_ = rec_bytes; scope_cap_ = cap;
-    if (scopes_.empty()) { scope_par_ = mx_video_scope_params{0, 0, 1}; return; }
-    scope_par_ = *params;
-    scope_rec_.alloc(cap * n * rec_bytes);
-}
-
-size_t Graph::read_video_scopes(void* dst, size_t cap_bytes) {
-    hip_check(hipSetDevice(device_), "hipSetDevice");
-    if (scopes_.empty()) throw Error(MX_ERR_INVALID, "no video scope taps are set");
-    if (!scope_run_seen_) throw Error(MX_ERR_INVALID, "no run since the video scope taps were set");
-    const size_t count = (size_t)scope_n_ * scopes_.size(), bytes = count * scope_rec_bytes_;
-    if (cap_bytes < bytes) throw Error(MX_ERR_INVALID, "cap_bytes is smaller than recorded ticks x taps x record bytes");
-    if (bytes && !dst) throw Error(MX_ERR_INVALID, "dst is NULL");
-    if (bytes) {
-        wait_tail(-1);
-        hip_check(hipMemcpyAsync(dst, scope_rec_.p, bytes, hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(D2H)");
-        sync();
-    }
-    return count;
-}
-
 void Graph::read_output_i16(uint32_t node, uint32_t port, int16_t* host, size_t frames) {
     hip_check(hipSetDevice(device_), "hipSetDevice");
     wait_tail(-1);
@@ -1791,482 +1720,6 @@ int Graph::read_plotter(uint32_t node, uint32_t call, float* left, float* right)
     hip_check(hipMemcpyAsync(right, stage + fpc, fpc * sizeof(float), hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(D2H)");
     sync();
     return 1;
-}
-
-// ---------------------------------------------------------------------------------------------
-// video sub-graph: one Engine::run_tick pass over the video nodes in run order
-// ---------------------------------------------------------------------------------------------
-void Graph::run_video_tick(uint64_t t) {
-    scope_now_ = false;
-    if (!scopes_.empty()) { scope_now_ = scope_c_ % scope_par_.hop == 0; ++scope_c_; }   // the hop counter: tested before the increment
-    mv_now_ = false;
-    if (!mv_ports_.empty()) { mv_now_ = mv_c_ % mv_par_.hop == 0; ++mv_c_; }
-    for (uint32_t id : video_order_) {
-        Node& n = nodes_[id];
-        switch (n.kind) {
-        case MX_KIND_SOURCE_VIDEO: {
-            // Output::from_line_type(Video) = None every tick (io.rs:76); the source fills it when a frame is due
-            n.vout[0] = Node::VOut{};
-            const uint64_t tick = t / spt_;
-            while (!n.vsrc_sched.empty() && n.vsrc_sched.front().tick < tick) n.vsrc_sched.pop_front();   // a tick that was never run
-            if (!n.vsrc_sched.empty()) {   // paced ingest: the tick a MediaSource / StreamInput emitted the frame on, or None
-                if (n.vsrc_sched.front().tick == tick) {
-                    Node::VSched& e = n.vsrc_sched.front();
-                    n.vout[0].frame = e.frame; n.vout[0].dur = e.dur; n.vout[0].off = e.off;
-                    n.vsrc_sched.pop_front();
-                }
-            } else if (!n.vsrc_ring.empty()) {   // a decoder's stream: the next frame of the ring, every tick
-                n.vout[0].frame = n.vsrc_ring[n.vsrc_ring_pos]; n.vout[0].dur = n.vsrc_dur; n.vout[0].off = n.vsrc_off;
-                n.vsrc_ring_pos = (n.vsrc_ring_pos + 1) % n.vsrc_ring.size();
-            } else if (n.vsrc && (n.vsrc_repeat || n.vsrc_pending)) {
-                n.vout[0].frame = n.vsrc; n.vout[0].dur = n.vsrc_dur; n.vout[0].off = n.vsrc_off;
-                n.vsrc_pending = false;
-            }
-            if (n.vband && n.vout[0].frame) {   // row-band sharding: the frame is a halo slice of a smaller layer; deliver this rank's band of its scale
-                FrameRef o;
-                for (auto& f : n.vband_pool) if (f->rc.load(std::memory_order_acquire) == 1) { o = f; break; }   // only the pool holds it
-                if (!o) {
-                    if (n.vband_pool.size() >= 8) n.vband_pool.erase(n.vband_pool.begin());
-                    n.vband_pool.push_back(FrameRef(DFrame::create(n.vband->full_w(), n.vband->band_rows(), stream_), false));
-                    o = n.vband_pool.back();
-                }
-                n.vband->run(n.vout[0].frame.f, o.f, stream_);
-                n.vout[0].frame = o;
-            }
-            if (n.vplace_on && n.vout[0].frame) n.vout[0].frame = placed_source_frame(id, n.vout[0].frame);   // keys first where a key is set
-            else if (n.vkey_on && n.vout[0].frame) n.vout[0].frame = keyed_source_frame(id, n.vout[0].frame);
-            break;
-        }
-        case MX_KIND_VIDEO_MIXER: {
-            VideoInput in[4];
-            for (int i = 0; i < 4; ++i) {
-                const PortRef pr = n.in_src[i];
-                if (pr.node < 0) continue;                                   // Disconnected => None (io.rs:56-57)
-                const Node::VOut& v = nodes_[pr.node].vout[pr.port];
-                if (!v.frame) continue;
-                in[i].frame = v.frame.f; in[i].duration_hint = v.dur; in[i].tick_offset = v.off;
-            }
-            FrameRef o, a, b;
-            n.vmixer->run_tick(t, in, o, a, b);
-            n.vout[0] = Node::VOut{o, Rational::make(1, (int64_t)tps_), Rational::make(0, 1)};   // video_mixer.rs:241-247
-            // A / B are clones of the input VideoFrames, duration and offset included (video_mixer.rs:80-90)
-            mx_video_mixer_params p; std::memcpy(&p, n.params.data(), sizeof p);
-            n.vout[1] = Node::VOut{}; n.vout[2] = Node::VOut{};
-            if (a && p.a >= 0 && p.a < 4) n.vout[1] = Node::VOut{a, in[p.a].duration_hint, in[p.a].tick_offset};
-            if (b && p.b >= 0 && p.b < 4) n.vout[2] = Node::VOut{b, in[p.b].duration_hint, in[p.b].tick_offset};
-            break;
-        }
-        case MX_KIND_MONITOR: {
-            // Monitor::run_tick (monitor.rs:113-139) + the codec thread's use of the Tick (monitor.rs:226-236)
-            Node::MonTick mt;
-            const Rational absolute = Rational::make((int64_t)t, (int64_t)sample_rate_);
-            if (!n.mon_has_epoch) { n.mon_epoch = absolute; n.mon_has_epoch = true; }       // epoch.get_or_insert
-            mt.ts = absolute - n.mon_epoch;                                                  // remove_epoch
-            if (n.mon_depth && n.mon_queued >= n.mon_depth) {                                // try_send on a full channel: the tick is dropped (monitor.rs:163-177)
-                mt.dropped = true;
-                n.mon_ticks.push_back(std::move(mt));
-                break;
-            }
-            if (n.mon_depth) ++n.mon_queued;
-            const PortRef pr = n.in_src[0];
-            const Node::VOut* vp = pr.node < 0 ? nullptr : &nodes_[pr.node].vout[pr.port];   // Disconnected => None (io.rs:56-57)
-            if (vp && vp->frame) {
-                mt.present = true;
-                mt.frame_ts = mt.ts + vp->off;                                               // tick.timestamp + tick_offset
-                mt.dur = vp->dur;
-                mt.frame = n.mon_scaler->scale_keep(vp->frame);                              // VideoCtx::send_frame -> DynamicScaler::scale (encode.rs:287-295)
-            }
-            n.mon_ticks.push_back(std::move(mt));
-            break;
-        }
-        case MX_KIND_VIDEO_TO_RGBA: {
-            const PortRef pr = n.in_src[0];
-            n.rgba_w = n.rgba_h = 0;
-            const Node::VOut* vp = pr.node < 0 ? nullptr : &nodes_[pr.node].vout[pr.port];
-            if (!vp || !vp->frame) {   // no picture this tick: nothing will follow the pending chains soon -- let them go (with whatever scales are queued)
-                if (!n.rgba_pending.empty()) { flush_scales(stream_); launch_pending_rgba(n, n.rgba_pending.size(), false); }
-                break;
-            }
-            DFrame* d = vp->frame.f;
-            const int32_t stride = (int32_t)(((size_t)d->width * 4 + 15) & ~(size_t)15);
-            const size_t need = (size_t)stride * d->height;
-            const uint32_t K = video_batch_ticks();   // ticks whose chains share one launch inside a batched run
-            if (n.rgba.size() != K || n.rgba[0].bytes < need) {
-                if (!n.rgba_pending.empty()) { flush_scales(stream_); launch_pending_rgba(n, n.rgba_pending.size(), false); }
-                sync();
-                n.rgba.clear(); n.rgba.resize(K);
-                for (DevBuf& b : n.rgba) b.alloc(need);
-                n.rgba_cur = 0;
-            }
-            mx_video_to_rgba_params p; std::memcpy(&p, n.params.data(), sizeof p);
-            n.rgba_cur = (n.rgba_cur + 1u) % K;
-            uint8_t* const out = (uint8_t*)n.rgba[n.rgba_cur].p;
-            if (d->lazy) {   // the composite only exists as a cross-fade chain: evaluate it straight into RGBA
-                ChainRgbaArgs c{};
-                fill_chain_rgba_sources(*d->lazy, c, stream_);   // layers that are unevaluated scaler outputs are resampled inside the kernel
-                c.rgba = out; c.rgba_stride = (uint32_t)stride; c.width = d->width; c.height = d->height;
-                c.use_matrix = p.use_matrix;
-                for (int k = 0; k < 12; ++k) c.m[k] = p.matrix_q12[k];
-                // Inside a batched run the sink runs LATE and K ticks at a time (K = video_batch_ticks(), default 16): the chains of ticks k .. k + K - 1
-                // leave in ONE launch together with the scaler tiles ticks k + K .. k + 2K - 1 queued (mx_k_video.hip k_video_batch) -- the
-                // chip then holds waves of several frames in every phase at once instead of marching through load / compute / store in step.
-                // Every K-th sink call is an event: it takes ALL queued scales along (so the scales a chain needs left at its own event
-                // or an earlier one) and, once 2K chains are pending, the K oldest -- always at least K calls old.  A Scaler writes 2K output
-                // frames in turn and the sink K RGBA buffers, so nothing in one launch writes what something else in it reads or writes.
-                // What is still pending when the run ends is launched then.
-                n.rgba_pending.push_back(Node::PendingRgba{c, d->lazy});
-                if ((++n.rgba_calls % K) == 0) {
-                    if (n.rgba_pending.size() >= 2 * (size_t)K) launch_pending_rgba(n, K, true);
-                    else flush_scales(stream_);
-                }
-                n.rgba_w = d->width; n.rgba_h = d->height; n.rgba_stride = stride;
-                break;
-            }
-            if (!n.rgba_pending.empty()) { flush_scales(stream_); launch_pending_rgba(n, n.rgba_pending.size(), false); }
-            d->ensure_pixels(stream_);
-            if (d->fmt != MX_PIXFMT_YUV420P) throw Error(MX_ERR_INVALID, "VIDEO_TO_RGBA takes yuv420p (a VideoMixer output); put a VideoMixer in front of a source of another format");
-            RgbaArgs a;
-            a.y = d->data[0]; a.u = d->data[1]; a.v = d->data[2]; a.rgba = out;
-            a.y_stride = d->stride[0]; a.u_stride = d->stride[1]; a.v_stride = d->stride[2]; a.rgba_stride = (uint32_t)stride;
-            a.width = d->width; a.height = d->height; a.use_matrix = p.use_matrix;
-            for (int k = 0; k < 12; ++k) a.m[k] = p.matrix_q12[k];
-            launch_yuv420_to_rgba(a, stream_);
-            n.rgba_w = d->width; n.rgba_h = d->height; n.rgba_stride = stride;
-            break;
-        }
-        default: break;
-        }
-        // scope taps on this node's ports: its vout is set, nothing downstream has run
-        if (scope_now_) for (uint32_t k = 0; k < (uint32_t)scopes_.size(); ++k) if (scopes_[k].node == id) launch_video_scope(k, n.vout[scopes_[k].port]);
-    }
-    if (scope_now_) ++scope_n_;
-    if (mv_now_ && (int64_t)video_tick_in_run_ == mv_last_) render_multiview();   // every tapped port's vout is set
-}
-
-// The multiviewer's canvas of the tick being run.  Ordering as for a scope tap (launch_video_scope): everything is on stream_; a symbolic frame is materialised
-// first -- the consumers that ran earlier in the tick evaluated the chain themselves, and those of later ticks read the same bytes -- then the queued scaler jobs
-// leave, then the ONE launch.  The canvas is a pool frame nothing but the pool holds: its last reader is on stream_ already, or is the caller, who let go of it.
-void Graph::render_multiview() {
-    DFrame* in[MX_MULTIVIEW_MAX] = {};
-    uint32_t present = 0;
-    for (uint32_t i = 0; i < (uint32_t)mv_ports_.size(); ++i) {
-        DFrame* d = nodes_[mv_ports_[i].node].vout[mv_ports_[i].port].frame.f;
-        if (!d) continue;
-        present |= 1u << i;
-        if (d->fmt != MX_PIXFMT_YUV420P) continue;   // another pixel format: present, not shown
-        d->ensure_pixels(stream_);
-        in[i] = d;
-    }
-    flush_scales(stream_);   // a scaler output just asked for (or queued earlier in the tick) must be written before it is read
-    FrameRef o;
-    for (auto& f : mv_pool_) if (f->rc.load(std::memory_order_acquire) == 1) { o = f; break; }
-    if (!o) {
-        if (mv_pool_.size() >= 8) mv_pool_.erase(mv_pool_.begin());
-        mv_pool_.push_back(FrameRef(DFrame::create_unfilled(mv_par_.canvas_w, mv_par_.canvas_h, MX_PIXFMT_YUV420P, false), false));   // the kernel writes every byte
-        o = mv_pool_.back();
-    }
-    mv_status_.shown_mask = multiview_into(in, mv_par_, mv_tabs_, o.f, stream_);
-    mv_status_.present_mask = present;
-    mv_status_.tick_in_run = video_tick_in_run_;
-    mv_out_ = o;
-}
-
-void Graph::set_multiview(const mx_port_ref* ports, size_t n, const mx_multiview_params* params) {
-    if (n && (!ports || !params)) throw Error(MX_ERR_INVALID, "ports / params is NULL");
-    if (n) {
-        if (n != params->n_views) throw Error(MX_ERR_INVALID, "multiview: n must equal params->n_views");
-        check_multiview_params(*params, true);
-        for (size_t i = 0; i < n; ++i) {
-            const mx_port_ref pr = ports[i];
-            if (pr.node >= nodes_.size() || pr.port >= nodes_[pr.node].out_type.size()) throw Error(MX_ERR_INVALID, "multiview: output terminal out of range");
-            if (nodes_[pr.node].out_type[pr.port] != MX_VIDEO) throw Error(MX_ERR_TYPE, "multiview: an audio port has no picture");
-        }
-    }
-    hip_check(hipSetDevice(device_), "hipSetDevice");
-    sync();   // the last run's launch is done with the tables and the pool
-    mv_ports_.assign(ports, ports + n);
-    mv_c_ = 0; mv_last_ = -1; mv_now_ = false; mv_run_seen_ = false;
-    mv_out_ = FrameRef(); mv_pool_.clear(); mv_tabs_ = MultiviewTabs{};
-    mv_status_ = mx_multiview_status{0, 0, 0, 0};
-    mv_par_ = mx_multiview_params{};
-    if (n) mv_par_ = *params;
-}
-
-FrameRef Graph::multiview_output(mx_multiview_status* status) {
-    if (mv_ports_.empty()) throw Error(MX_ERR_INVALID, "no multiview is set");
-    if (!mv_run_seen_) throw Error(MX_ERR_INVALID, "no run since the multiview was set");
-    hip_check(hipSetDevice(device_), "hipSetDevice");
-    if (mv_out_) { wait_tail(-1); sync(); }   // a frame crossing the ABI: its pixels are there, whatever stream the caller reads them on
-    if (status) *status = mv_status_;
-    return mv_out_;
-}
-
-// One tap's record of the tick being run.  Ordering: everything is on stream_ -- a graph with video nodes never runs anything on the second
-// stream (has_video_ excludes that mode), the run's fill of the records went out on stream_ before its first launch, a frame's producer
-// (a cross-fade, a scaler, a band scaler) launched on stream_ or is launched here (ensure_pixels, then the queued scaler jobs), and whoever
-// writes the frame's memory again is queued behind this launch.  A symbolic frame is materialised: the consumers downstream then read its
-// planes instead of re-evaluating the chain -- the same bytes, every cross-fade step truncates to u8 wherever it runs.
-void Graph::launch_video_scope(uint32_t tap, const Node::VOut& v) {
-    ScopeArgs a{};
-    a.wave_cols = scope_par_.wave_cols; a.vectorscope = scope_par_.vectorscope;
-    a.tick_in_run = video_tick_in_run_;
-    a.rec = reinterpret_cast<uint32_t*>((uint8_t*)scope_rec_.p + ((size_t)scope_n_ * scopes_.size() + tap) * scope_rec_bytes_);
-    if (DFrame* d = v.frame.f) {
-        a.present = 1;
-        a.pixfmt = (d->fmt == MX_PIXFMT_YUV420P && d->with_alpha) ? (uint32_t)MX_PIXFMT_YUVA420P : d->fmt;
-        a.width = d->width; a.height = d->height;
-        if (d->fmt == MX_PIXFMT_YUV420P) {
-            d->ensure_pixels(stream_);
-            flush_scales(stream_);   // a scaler output just asked for (or queued earlier in the tick) must be written before it is read
-            a.counted = 1;
-            a.y = d->data[0]; a.u = d->data[1]; a.v = d->data[2];
-            a.y_stride = d->stride[0]; a.u_stride = d->stride[1]; a.v_stride = d->stride[2];
-        }
-    }
-    mx::launch_video_scope(a, stream_);
-}
-
-void Graph::launch_pending_rgba(Node& n, size_t count, bool with_queued_scales) {
-    count = std::min(count, n.rgba_pending.size());
-    const size_t K = std::min<size_t>(video_batch_ticks(), MX_VB_MAX_CHAINS);   // the sink's K RGBA buffers are written in turn: at most K chains per launch
-    std::vector<ChainRgbaArgs> c(K);
-    size_t i = 0;
-    while (i < count) {
-        const int m = (int)std::min(K, count - i);
-        for (int k = 0; k < m; ++k) c[k] = n.rgba_pending[i + k].args;
-        if (with_queued_scales && i == 0) launch_chains_rgba_after_queued_scales(c.data(), m, stream_);
-        else launch_video_batch(nullptr, 0, c.data(), m, stream_);
-        i += m;
-    }
-    n.rgba_pending.erase(n.rgba_pending.begin(), n.rgba_pending.begin() + count);
-}
-
-void Graph::set_video_source(uint32_t node, DFrame* frame, Rational dur, Rational off, bool repeat) {
-    if (node >= nodes_.size() || nodes_[node].kind != MX_KIND_SOURCE_VIDEO) throw Error(MX_ERR_INVALID, "node is not a SOURCE_VIDEO");
-    Node& n = nodes_[node];
-    n.vsrc = frame ? FrameRef(frame, true) : FrameRef();
-    n.vsrc_dur = dur; n.vsrc_off = off; n.vsrc_repeat = repeat; n.vsrc_pending = frame != nullptr;
-}
-
-void Graph::set_video_source_band(uint32_t node, uint32_t in_w, uint32_t in_full_h, uint32_t src_row0, uint32_t slice_rows,
-                                  uint32_t full_w, uint32_t full_h, uint32_t row0, uint32_t band_rows) {
-    if (node >= nodes_.size() || nodes_[node].kind != MX_KIND_SOURCE_VIDEO) throw Error(MX_ERR_INVALID, "node is not a SOURCE_VIDEO");
-    Node& nd = nodes_[node];
-    if (band_rows && nd.vkey_on) throw Error(MX_ERR_INVALID, "video source band: the source is keyed (mx_graph_set_video_source_key), and a band-scaled layer cannot carry coverage");
-    if (band_rows && nd.vplace_on) throw Error(MX_ERR_INVALID, "video source band: the source is placed (mx_graph_set_video_source_place), and a band-scaled layer cannot carry coverage");
-    sync();                                     // a previous band scaler's row buffer may be in use
-    nd.vband.reset(); nd.vband_pool.clear();
-    if (band_rows) nd.vband = std::make_shared<BandScaler>(in_w, in_full_h, src_row0, slice_rows, full_w, full_h, row0, band_rows);
-}
-
-void Graph::set_video_source_key(uint32_t node, const mx_video_key_params* params) {
-    if (node >= nodes_.size()) throw Error(MX_ERR_INVALID, "node out of range");
-    if (nodes_[node].kind != MX_KIND_SOURCE_VIDEO) throw Error(MX_ERR_TYPE, "video source key: node is not a SOURCE_VIDEO");
-    Node& nd = nodes_[node];
-    if (params) {
-        check_key_params(*params);
-        if (nd.vband) throw Error(MX_ERR_INVALID, "video source key: the source delivers a row band of a scaled layer (mx_graph_set_video_source_band), which cannot carry coverage");
-    }
-    // frames keyed under the old setting are of no use; their output frames stay in the pool and are rewritten once their last holder has let go
-    nd.vkey_done.clear();
-    nd.vplace_done.clear();   // a placed frame holds the picture as it was keyed
-    nd.vkey_on = params != nullptr;
-    if (params) nd.vkey = *params; else nd.vkey_pool.clear();
-}
-
-void Graph::set_video_source_place(uint32_t node, const mx_video_place_params* params) {
-    if (node >= nodes_.size()) throw Error(MX_ERR_INVALID, "node out of range");
-    if (nodes_[node].kind != MX_KIND_SOURCE_VIDEO) throw Error(MX_ERR_TYPE, "video source place: node is not a SOURCE_VIDEO");
-    Node& nd = nodes_[node];
-    if (params) {
-        check_place_params(*params);
-        if (nd.vband) throw Error(MX_ERR_INVALID, "video source place: the source delivers a row band of a scaled layer (mx_graph_set_video_source_band), which cannot carry coverage");
-    }
-    // as for the key: frames placed under the old setting are of no use; a canvas of another size needs other frames, so the pool goes too
-    nd.vplace_done.clear(); nd.vplace_pool.clear(); nd.vplace_tabs.reset();
-    nd.vplace_on = params != nullptr;
-    if (params) nd.vplace = *params;
-    nd.vkey_done.clear();   // the keyed frames a placed source needs are the placer's alone and never listed; those listed before must not pin their pool frames
-}
-
-// The keyed form of `src` on a SOURCE_VIDEO node: keyed once per setting, reused while anything but this list holds the source frame.
-FrameRef Graph::keyed_source_frame(uint32_t id, const FrameRef& src) {
-    Node& n = nodes_[id];
-    if (!key_input_ok(src.f)) throw Error(MX_ERR_INVALID, "node " + std::to_string(id) + " (SOURCE_VIDEO): the keyer takes yuv420p or yuva420p frames");
-    for (size_t i = 0; i < n.vkey_done.size(); ++i)
-        if (n.vkey_done[i].src.f == src.f) return n.vkey_done[i].out;
-    // entries whose source frame only this list still holds can never be asked for again (the oldest goes too when the list is full)
-    for (size_t i = 0; i < n.vkey_done.size();) {
-        if (n.vkey_done[i].src->rc.load(std::memory_order_acquire) == 1) n.vkey_done.erase(n.vkey_done.begin() + (ptrdiff_t)i); else ++i;
-    }
-    if (n.vkey_done.size() >= 32) n.vkey_done.erase(n.vkey_done.begin());
-    FrameRef o;
-    for (auto& f : n.vkey_pool)   // the FrameStager's rule: a pooled frame is rewritten only when the pool alone holds it -- its last reader (a chain launched ticks later included) is on stream_ already
-        if (f->width == src->width && f->height == src->height && f->rc.load(std::memory_order_acquire) == 1) { o = f; break; }
-    if (!o) {
-        if (n.vkey_pool.size() >= 64) n.vkey_pool.erase(n.vkey_pool.begin());   // twice the list above: a frame that leaves the list is still in the pool, so a long ring recycles frames instead of allocating
-        n.vkey_pool.push_back(FrameRef(DFrame::create(src->width, src->height, stream_, MX_PIXFMT_YUV420P, true), false));
-        o = n.vkey_pool.back();
-    }
-    key_into(src.f, n.vkey, o.f, stream_);
-    n.vkey_done.push_back(Node::VKeyed{src, o});
-    return o;
-}
-
-// The placed form of `src` on a SOURCE_VIDEO node: key (where set), then place -- once per setting, reused while anything but this list holds the source frame.
-FrameRef Graph::placed_source_frame(uint32_t id, const FrameRef& src) {
-    Node& n = nodes_[id];
-    if (n.vkey_on && !key_input_ok(src.f)) throw Error(MX_ERR_INVALID, "node " + std::to_string(id) + " (SOURCE_VIDEO): the keyer takes yuv420p or yuva420p frames");
-    if (const char* why = place_input_error(src.f, n.vplace)) throw Error(MX_ERR_INVALID, "node " + std::to_string(id) + " (SOURCE_VIDEO): " + why);
-    for (size_t i = 0; i < n.vplace_done.size(); ++i)
-        if (n.vplace_done[i].src.f == src.f) return n.vplace_done[i].out;
-    for (size_t i = 0; i < n.vplace_done.size();) {
-        if (n.vplace_done[i].src->rc.load(std::memory_order_acquire) == 1) n.vplace_done.erase(n.vplace_done.begin() + (ptrdiff_t)i); else ++i;
-    }
-    if (n.vplace_done.size() >= 32) n.vplace_done.erase(n.vplace_done.begin());
-    // a pooled frame is rewritten only when the pool alone holds it (keyed_source_frame); the keyed frame between the two passes is read by the placement launched right
-    // behind the key on stream_, and by nobody else
-    auto pooled = [&](std::vector<FrameRef>& pool, uint32_t w, uint32_t h, bool filled) {
-        for (auto& f : pool)
-            if (f->width == w && f->height == h && f->rc.load(std::memory_order_acquire) == 1) return f;
-        if (pool.size() >= 64) pool.erase(pool.begin());
-        pool.push_back(FrameRef(filled ? DFrame::create(w, h, stream_, MX_PIXFMT_YUV420P, true) : DFrame::create_unfilled(w, h, MX_PIXFMT_YUV420P, true), false));
-        return pool.back();
-    };
-    FrameRef in = src;
-    if (n.vkey_on) {
-        in = pooled(n.vkey_pool, src->width, src->height, true);   // the keyer leaves the padding as DFrame::create made it
-        key_into(src.f, n.vkey, in.f, stream_);
-    }
-    if (!n.vplace_tabs || !place_tables_fit(*n.vplace_tabs, in.f, n.vplace)) n.vplace_tabs = make_place_tables(in.f, n.vplace);
-    FrameRef o = pooled(n.vplace_pool, n.vplace.canvas_w, n.vplace.canvas_h, false);   // the placer writes every byte
-    place_into(in.f, n.vplace, *n.vplace_tabs, o.f, stream_);
-    n.vplace_done.push_back(Node::VKeyed{src, o});
-    return o;
-}
-
-void Graph::queue_video_source(uint32_t node, uint64_t tick, DFrame* frame, Rational dur, Rational off) {
-    if (node >= nodes_.size() || nodes_[node].kind != MX_KIND_SOURCE_VIDEO) throw Error(MX_ERR_INVALID, "node is not a SOURCE_VIDEO");
-    if (!frame) throw Error(MX_ERR_INVALID, "frame is NULL");
-    Node& nd = nodes_[node];
-    if (!nd.vsrc_sched.empty() && nd.vsrc_sched.back().tick >= tick) throw Error(MX_ERR_INVALID, "video source frames must be queued in tick order, one per tick");
-    nd.vsrc_sched.push_back(Node::VSched{tick, FrameRef(frame, true), dur, off});
-}
-
-void Graph::check_video_queue(uint32_t node, uint64_t first_tick) const {
-    if (node >= nodes_.size() || nodes_[node].kind != MX_KIND_SOURCE_VIDEO) throw Error(MX_ERR_INVALID, "node is not a SOURCE_VIDEO");
-    const Node& nd = nodes_[node];
-    if (!nd.vsrc_sched.empty() && nd.vsrc_sched.back().tick >= first_tick) throw Error(MX_ERR_INVALID, "video source frames must be queued in tick order, one per tick");
-}
-
-void Graph::check_source_write(uint32_t node, size_t frames) const {
-    if (node >= nodes_.size()) throw Error(MX_ERR_INVALID, "node out of range");
-    const Node& n = nodes_[node];
-    if (n.kind != MX_KIND_SOURCE_MONO && n.kind != MX_KIND_SOURCE_STEREO) throw Error(MX_ERR_INVALID, "node is not a SOURCE_*");
-    if (n.bound) throw Error(MX_ERR_INVALID, "source is bound to a caller device buffer");
-    if (frames > cap_frames_) throw Error(MX_ERR_INVALID, "more ticks than max_ticks_per_run");
-}
-
-void Graph::monitor_consume(uint32_t node, uint32_t n_ticks) {
-    if (node >= nodes_.size() || nodes_[node].kind != MX_KIND_MONITOR) throw Error(MX_ERR_INVALID, "node is not a MONITOR");
-    Node& n = nodes_[node];
-    n.mon_queued -= std::min(n.mon_queued, n_ticks);
-}
-
-const Node::MonTick& Graph::monitor_tick(uint32_t node, uint32_t tick_in_run) {
-    if (node >= nodes_.size() || nodes_[node].kind != MX_KIND_MONITOR) throw Error(MX_ERR_INVALID, "node is not a MONITOR");
-    if (tick_in_run >= nodes_[node].mon_ticks.size()) throw Error(MX_ERR_INVALID, "tick_in_run beyond the last run");
-    flush_scales(stream_);
-    sync();          // the caller reads the frame on streams of its own
-    return nodes_[node].mon_ticks[tick_in_run];
-}
-
-Graph::MonitorLayout Graph::monitor_layout(uint32_t node) {
-    if (node >= nodes_.size() || nodes_[node].kind != MX_KIND_MONITOR) throw Error(MX_ERR_INVALID, "node is not a MONITOR");
-    const Scaler& sc = *nodes_[node].mon_scaler;
-    MonitorLayout l{};
-    l.width = sc.out_w(); l.height = sc.out_h();
-    size_t total = 0;                                   // DFrame's own layout for yuv420p (mx_video.cpp alloc_planes): what every kept frame has
-    for (int p = 0; p < 3; ++p) {
-        const uint32_t rb = p ? l.width >> 1 : l.width, rows = p ? l.height >> 1 : l.height;
-        l.stride[p] = (rb + 63u) & ~63u;
-        l.plane_offset[p] = total;
-        total += ((size_t)l.stride[p] * rows + 255) & ~(size_t)255;
-    }
-    l.frame_bytes = total;
-    return l;
-}
-
-void Graph::read_monitor_video(uint32_t node, uint32_t first_tick, uint32_t n_ticks, uint8_t* frames, uint8_t* present) {
-    const MonitorLayout l = monitor_layout(node);
-    Node& n = nodes_[node];
-    if ((size_t)first_tick + n_ticks > n.mon_ticks.size()) throw Error(MX_ERR_INVALID, "ticks beyond the last run");
-    if (n_ticks && (!frames || !present)) throw Error(MX_ERR_INVALID, "NULL argument");
-    if (!n_ticks) return;
-    hip_check(hipSetDevice(device_), "hipSetDevice");
-    const size_t need = (size_t)n_ticks * l.frame_bytes;
-    if (n.mon_pack.bytes < need) { sync(); n.mon_pack.alloc(need); }
-    uint32_t any = 0;
-    for (uint32_t k0 = 0; k0 < n_ticks; k0 += 224) {
-        GatherArgs a{};
-        a.n = std::min<uint32_t>(224u, n_ticks - k0);
-        a.dst = reinterpret_cast<uint4*>((uint8_t*)n.mon_pack.p + (size_t)k0 * l.frame_bytes);
-        a.q_per_frame = (uint32_t)(l.frame_bytes / 16);
-        for (uint32_t k = 0; k < a.n; ++k) {
-            const Node::MonTick& mt = n.mon_ticks[first_tick + k0 + k];
-            present[k0 + k] = mt.present ? 1 : 0;
-            a.src[k] = nullptr;
-            if (!mt.present) continue;
-            const DFrame* f = mt.frame.f;
-            if (f->mem.bytes != l.frame_bytes || f->plane_offset(1) != l.plane_offset[1] || f->plane_offset(2) != l.plane_offset[2])
-                throw Error(MX_ERR_INTERNAL, "a kept monitor frame does not have the monitor layout");
-            a.src[k] = reinterpret_cast<const uint4*>(f->mem.p);
-            ++any;
-        }
-        launch_gather_frames(a, stream_);
-    }
-    if (any) hip_check(hipMemcpyAsync(frames, n.mon_pack.p, need, hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(D2H monitor frames)");
-    sync();
-}
-
-void Graph::read_monitor_audio_i16(uint32_t node, int16_t* host, uint32_t n_ticks) {
-    if (node >= nodes_.size() || nodes_[node].kind != MX_KIND_MONITOR) throw Error(MX_ERR_INVALID, "node is not a MONITOR");
-    if (n_ticks > last_calls_) throw Error(MX_ERR_INVALID, "more ticks than the last run had");
-    if (n_ticks && !host) throw Error(MX_ERR_INVALID, "audio is NULL");
-    const PortRef pr = nodes_[node].in_src[1];
-    const size_t per_tick = 2 * last_frames_per_call_;
-    if (pr.node < 0) { std::memset(host, 0, (size_t)n_ticks * per_tick * sizeof(int16_t)); return; }   // InputRef::Disconnected: the zero buffer
-    read_output_i16((uint32_t)pr.node, (uint32_t)pr.port, host, (size_t)n_ticks * last_frames_per_call_);
-}
-
-void Graph::set_video_source_ring(uint32_t node, DFrame* const* frames, size_t n, Rational dur, Rational off) {
-    if (node >= nodes_.size() || nodes_[node].kind != MX_KIND_SOURCE_VIDEO) throw Error(MX_ERR_INVALID, "node is not a SOURCE_VIDEO");
-    Node& nd = nodes_[node];
-    nd.vsrc_ring.clear(); nd.vsrc_ring_pos = 0;
-    for (size_t i = 0; i < n; ++i) nd.vsrc_ring.push_back(FrameRef(frames[i], true));
-    nd.vsrc_dur = dur; nd.vsrc_off = off;
-    if (n) { nd.vsrc = FrameRef(); nd.vsrc_pending = false; nd.vsrc_repeat = false; }
-}
-
-FrameRef Graph::video_output(uint32_t node, uint32_t port) {
-    if (node >= nodes_.size() || port >= nodes_[node].vout.size() || nodes_[node].out_type[port] != MX_VIDEO)
-        throw Error(MX_ERR_INVALID, "not a video output terminal");
-    FrameRef r = nodes_[node].vout[port].frame;
-    if (r) {   // a frame crossing the ABI must have pixels -- and they must be there: the caller reads them on whatever stream it likes
-        r->ensure_pixels(stream_);
-        flush_scales(stream_);
-        sync();
-    }
-    return r;
-}
-
-void Graph::rgba_output(uint32_t node, void** dev, int32_t* stride, uint32_t* w, uint32_t* h) {
-    if (node >= nodes_.size() || nodes_[node].kind != MX_KIND_VIDEO_TO_RGBA) throw Error(MX_ERR_INVALID, "node is not a VIDEO_TO_RGBA");
-    const Node& n = nodes_[node];
-    if (dev) *dev = n.rgba_w ? n.rgba[n.rgba_cur].p : nullptr;
-    if (stride) *stride = n.rgba_stride;
-    if (w) *w = n.rgba_w;
-    if (h) *h = n.rgba_h;
 }
 
 }  // namespace mx

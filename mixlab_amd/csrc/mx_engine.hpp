@@ -21,6 +21,7 @@
 #include "mx_kernels.hpp"
 #include "mx_taps.hpp"
 #include "mx_video.hpp"
+#include "mx_video_graph.hpp"
 
 namespace mx {
 
@@ -57,37 +58,15 @@ struct Node {
     int32_t fuse_env = -1;                    // EQ_THREE: constant-gate Envelope evaluated inline as the fused Amplifier's control
     std::vector<uint8_t> out_elided;          // per output port: buffer not materialised
     std::vector<uint8_t> out_dup;             // per output port: stereo with L == R stored as ONE float per frame
-    // video nodes (run tick by tick inside Graph::run)
-    struct VOut { FrameRef frame; Rational dur, off; };
+    // video nodes (run tick by tick inside Graph::run): each kind's state is an object of its own (mx_video_graph.hpp), held by the nodes of that kind only
+    using VOut = mx::VOut;
+    using MonTick = MonitorState::Tick;
     std::unique_ptr<VideoMixer> vmixer;       // VIDEO_MIXER
     bool vlazy = false;                       // VIDEO_MIXER: program output handed over as an unevaluated cross-fade chain (graph compiler)
     std::vector<VOut> vout;                   // this tick's video outputs (empty FrameRef = None)
-    FrameRef vsrc; Rational vsrc_dur, vsrc_off; bool vsrc_repeat = false, vsrc_pending = false;   // SOURCE_VIDEO
-    std::vector<FrameRef> vsrc_ring; size_t vsrc_ring_pos = 0;                                       // SOURCE_VIDEO: a new frame every tick, cycling
-    struct VSched { uint64_t tick; FrameRef frame; Rational dur, off; };
-    std::deque<VSched> vsrc_sched;                                                                   // SOURCE_VIDEO: frames due on given ticks (MediaSource / StreamInput pacing), oldest first
-    std::shared_ptr<BandScaler> vband; std::vector<FrameRef> vband_pool;                             // SOURCE_VIDEO: frames are halo slices, delivered as this rank's row band of the scaled picture
-    // SOURCE_VIDEO: the keyer as a transform (mx_graph_set_video_source_key).  vkey_done: frames keyed under the current setting, newest last -- an entry holds the source
-    // frame (so its address stays its identity) and lives while anything else does; vkey_pool: output frames, rewritten only when the pool alone holds them
-    bool vkey_on = false; mx_video_key_params vkey{};
-    struct VKeyed { FrameRef src, out; };
-    std::vector<VKeyed> vkey_done; std::vector<FrameRef> vkey_pool;
-    // SOURCE_VIDEO: the placer as a transform (mx_graph_set_video_source_place), after the key where both are set.  vplace_done / vplace_pool follow the keyer's rules, an
-    // entry's src being the frame the FEEDER delivered (with a key set the keyed frame between the two is a pool frame nobody else sees, and is not listed under the key)
-    bool vplace_on = false; mx_video_place_params vplace{};
-    std::shared_ptr<const PlaceTables> vplace_tabs;   // of the current setting (and, for a whole-frame crop, of the size of the frame seen last)
-    std::vector<VKeyed> vplace_done; std::vector<FrameRef> vplace_pool;
-    std::vector<DevBuf> rgba; uint32_t rgba_cur = 0, rgba_w = 0, rgba_h = 0; int32_t rgba_stride = 0;   // VIDEO_TO_RGBA: video_batch_ticks() buffers, written in turn (that many ticks' chains may share a launch); rgba_cur = the last tick's
-    struct PendingRgba { ChainRgbaArgs args; std::shared_ptr<LazyChain> keep; };
-    std::vector<PendingRgba> rgba_pending;     // VIDEO_TO_RGBA: chains of the last ticks, not launched yet, oldest first (run_video_tick)
-    uint32_t rgba_calls = 0;                   // sink calls that queued a chain in this run
-    // MONITOR: what the sink kept of every tick of the last run
-    struct MonTick { bool present = false, dropped = false; FrameRef frame; Rational ts, frame_ts, dur; };
-    uint32_t mon_depth = 0, mon_queued = 0;    // mx_monitor_params_ex.queue_depth (0 = keep every tick) and the ticks the consumer has not taken yet
-    std::vector<MonTick> mon_ticks;
-    bool mon_has_epoch = false; Rational mon_epoch;
-    std::shared_ptr<Scaler> mon_scaler;
-    DevBuf mon_pack;                           // the packed read-back's device staging
+    std::unique_ptr<VideoSourceState> vsrc;   // SOURCE_VIDEO
+    std::unique_ptr<RgbaSinkState> rgba;      // VIDEO_TO_RGBA
+    std::unique_ptr<MonitorState> mon;        // MONITOR
     // OUTPUT_DEVICE (output_device.rs): the open stream's channel count (0: none), the stored left / right (filtered; -1: None), the largest
     // channel count seen (what the buffers are sized for) and the input's frames per tick
     uint32_t od_channels = 0, od_cmax = 0; int32_t od_left = -1, od_right = -1; uint32_t od_frames = 0;
@@ -132,7 +111,6 @@ public:
           size_t cap_frames_override = 0);
     ~Graph();
 
-    size_t spt() const { return spt_; }
     double sample_rate() const override { return sample_rate_; }
     size_t cap_frames() const override { return cap_frames_; }
     const std::vector<uint32_t>& run_order() const { return order_; }
@@ -171,12 +149,11 @@ public:
     MeterTaps& meters() { return meters_; } SpectrumTaps& spectra() { return spectra_; } LoudnessTaps& loudness() { return loudness_; }
     StereoTaps& stereo() { return stereos_; } LimiterTaps& limiters() { return limiters_; } TempoTaps& tempo() { return tempos_; } TonalityTaps& tonality() { return tonalities_; }
     bool tap_port(mx_port_ref r, TapPort& t) const override; size_t tap_fpc() const override { return tap_fpc_; }   // (TapHost: with the accessors marked override, all a set sees of the graph)
-    // video scope taps (mx_graph_set_video_scopes / mx_graph_read_video_scopes): histograms, waveform and vectorscope of the frames on video ports
-    void set_video_scopes(const mx_port_ref* ports, size_t n, const mx_video_scope_params* params);
-    size_t read_video_scopes(void* dst, size_t cap_bytes);   // the last run's records; returns how many
-    // the multiviewer as a tap on video ports (mx_graph_set_multiview / mx_graph_multiview_output): the ports' frames tiled on one canvas
-    void set_multiview(const mx_port_ref* ports, size_t n, const mx_multiview_params* params);   // n = 0 removes
-    FrameRef multiview_output(mx_multiview_status* status);   // the canvas of the last run's last recorded tick (null: none recorded)
+    // the taps on video ports (mx_video_graph.hpp): the scope taps and the multiviewer, measured tick by tick inside the run
+    VideoScopeTaps& video_scopes() { return scopes_; } MultiviewTap& multiview() { return multiview_; }
+    size_t spt() const override { return spt_; }
+    int out_line(mx_port_ref r) const override { return r.node < nodes_.size() && r.port < nodes_[r.node].out_type.size() ? (int)nodes_[r.node].out_type[r.port] : -1; }
+    const VOut& video_out(mx_port_ref r) const override { return nodes_[r.node].vout[r.port]; }
     void read_output_i16(uint32_t node, uint32_t port, int16_t* host, size_t frames);   // sink hand-off format
     void write_source_i16(uint32_t node, const int16_t* host, size_t frames);            // ingest format
     float* output_ptr(uint32_t node, uint32_t port, size_t* floats_per_tick, bool stream_ordered_consumer = true /* false: a caller inside the library that orders itself
@@ -217,7 +194,7 @@ public:
     const Node::MonTick& monitor_tick(uint32_t node, uint32_t tick_in_run);
     void monitor_consume(uint32_t node, uint32_t n_ticks);
     void read_monitor_audio_i16(uint32_t node, int16_t* host, uint32_t n_ticks);
-    struct MonitorLayout { uint32_t width, height; size_t frame_bytes, plane_offset[3]; uint32_t stride[3]; };
+    using MonitorLayout = MonitorState::Layout;
     MonitorLayout monitor_layout(uint32_t node);
     void read_monitor_video(uint32_t node, uint32_t first_tick, uint32_t n_ticks, uint8_t* frames, uint8_t* present);
     FrameRef video_output(uint32_t node, uint32_t port);
@@ -231,12 +208,8 @@ private:
     void build_descriptors();
     void upload_group(Group& g);          // descriptors of one group (both parities under MX_FLAG_OVERLAP_TAIL)
     void upload_group_one(Group& g, uint32_t parity);   // ... of one parity: desc / extra, or desc_alt / extra_alt
-    void run_video_tick(uint64_t t);
-    FrameRef keyed_source_frame(uint32_t id, const FrameRef& src);   // SOURCE_VIDEO with a key set: src keyed under the node's setting (once per frame)
-    FrameRef placed_source_frame(uint32_t id, const FrameRef& src);  // SOURCE_VIDEO with a placement set: src (keyed first where a key is set) placed, once per frame
-    void launch_pending_rgba(Node& n, size_t count, bool with_queued_scales);   // the `count` oldest pending chains of a sink
-    void render_multiview();                                             // the canvas of the tick being run (run_video_tick, at the end of the run's last recorded tick)
-    void launch_video_scope(uint32_t tap, const Node::VOut& v);          // one tap's record of the tick being run (run_video_tick, on a recorded tick)
+    void run_video_tick(uint64_t t, uint32_t tick_in_run);
+    const Node& node_of_kind(uint32_t node, uint32_t kind, const char* what) const;   // nodes_[node], or MX_ERR_INVALID "node is not a <what>" (a kind's video state is reached through its pointer)
     // one launch sequence over ticks [call_off, call_off + n_calls) of the current run
     void run_span(uint64_t t0, size_t fpc, uint32_t call_off, uint32_t n_calls, uint32_t run_calls);
     void apply_params(uint32_t node, const void* params, size_t len);   // update_params without the synchronisation
@@ -313,27 +286,7 @@ private:
     size_t tap_fpc_ = 0;                        // frames per call every set's descriptors were built for (the tick length until a run says otherwise)
     MeterTaps meters_{*this}; SpectrumTaps spectra_{*this}; LoudnessTaps loudness_{*this}; StereoTaps stereos_{*this}; LimiterTaps limiters_{*this}; TempoTaps tempos_{*this}; TonalityTaps tonalities_{*this};
     const std::array<AudioTapSet*, 7> taps_{&meters_, &spectra_, &loudness_, &stereos_, &limiters_, &tempos_, &tonalities_};   // in launch order
-    // video scope taps: the taps in set order; scope_rec_: the last run's records [recorded tick][tap], scope_cap_ ticks of room.  scope_c_ is the
-    // hop counter (0 when the taps are set, +1 per video tick, carried across runs); a tick is recorded when scope_c_ % hop == 0 before the increment
-    std::vector<mx_port_ref> scopes_;
-    mx_video_scope_params scope_par_{0, 0, 1};
-    size_t scope_rec_bytes_ = 0, scope_cap_ = 0;
-    DevBuf scope_rec_;
-    uint64_t scope_c_ = 0;
-    uint32_t scope_n_ = 0;                  // recorded ticks of the run in progress / of the last run
-    uint32_t video_tick_in_run_ = 0;        // the tick run_video_tick is running, counted from the run's first
-    bool scope_now_ = false, scope_run_seen_ = false;   // the tick being run is recorded; a run was made since the taps were set
-    // the multiviewer: the tapped ports in view order; mv_c_ is its own hop counter (the scopes' rule).  A run renders one canvas, at the end of tick mv_last_ (the last
-    // tick of the run its counter records; -1: none); canvases come from mv_pool_, rewritten only when the pool alone holds them
-    std::vector<mx_port_ref> mv_ports_;
-    mx_multiview_params mv_par_{};
-    MultiviewTabs mv_tabs_;
-    std::vector<FrameRef> mv_pool_;
-    FrameRef mv_out_;
-    mx_multiview_status mv_status_{0, 0, 0, 0};
-    uint64_t mv_c_ = 0;
-    int64_t mv_last_ = -1;
-    bool mv_now_ = false, mv_run_seen_ = false;
+    VideoScopeTaps scopes_{*this}; MultiviewTap multiview_{*this};
     float perf_od_ms_ = 0.f;                // OutputDevice launches of the last collected run
     bool prof_this_run_ = false;
     size_t plot_job_off_ = 0;

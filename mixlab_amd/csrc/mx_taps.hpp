@@ -11,6 +11,8 @@
 
 namespace mx {
 
+struct VOut;   // mx_video_graph.hpp
+
 // One output port as a tap sees it ...
 struct TapPort {
     uint8_t type = 0;                        // mx_line
@@ -29,6 +31,10 @@ struct TapHost {
     virtual int device() const = 0;
     virtual void sync() = 0;                 // everything queued is done, a held-back tail launch included
     virtual void join_tail() = 0;            // stream() waits for the tail launches that have not been waited for, a held-back one released first
+    // what the taps on video ports ask beside (mx_video_graph.hpp)
+    virtual size_t spt() const = 0;                               // base-rate frames per tick
+    virtual int out_line(mx_port_ref r) const = 0;                // the mx_line of an output terminal, -1: there is no such terminal
+    virtual const VOut& video_out(mx_port_ref r) const = 0;       // the frame of the tick being run on a video output terminal
 };
 
 // One audio tap set: the taps in set order (= record slots).  Launch order puts the taps read on the graph's stream first (n_head of them),

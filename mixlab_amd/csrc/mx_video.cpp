@@ -70,7 +70,7 @@ void flush_scales(hipStream_t s) {
     auto it = g_scale_q.find(s);
     if (it != g_scale_q.end()) flush_locked(s, it->second);
 }
-// The queued scales of the stream leave TOGETHER with RGBA chains that do not read them (Graph::run_video_tick: the chains of earlier
+// The queued scales of the stream leave TOGETHER with RGBA chains that do not read them (RgbaSinkState::run_tick: the chains of earlier
 // ticks) -- one launch instead of dependent ones (mx_k_video.hip k_video_batch).
 void launch_chains_rgba_after_queued_scales(const ChainRgbaArgs* chains, int n_chains, hipStream_t s) {
     PendingScales taken;
@@ -569,13 +569,8 @@ FrameRef Scaler::planar_of(const FrameRef& in) {
     const DFrame::Deep* deep = DFrame::deep_of(in->fmt);
     const uint8_t as_fmt = deep ? deep->layout : (in->yuyv() ? (uint8_t)MX_PIXFMT_YUV422P : (uint8_t)MX_PIXFMT_YUV444P);
     const bool want_alpha = DFrame::rgb_of(in->fmt).bpp == 4;   // the A byte is the pixel's coverage (straight alpha): it travels as the planar frame's coverage plane
-    FrameRef out;
-    for (auto& f : rgb_pool_) if (f->width == in->width && f->height == in->height && f->fmt == as_fmt && f->with_alpha == want_alpha && f->rc.load(std::memory_order_acquire) == 1) { out = f; break; }
-    if (!out) {
-        if (rgb_pool_.size() >= 2 * (size_t)video_batch_ticks() + 2) rgb_pool_.erase(rgb_pool_.begin());
-        rgb_pool_.push_back(FrameRef(DFrame::create(in->width, in->height, stream_, as_fmt, want_alpha), false));
-        out = rgb_pool_.back();
-    }
+    FrameRef out = rgb_pool_.take([&](const DFrame& f) { return f.width == in->width && f.height == in->height && f.fmt == as_fmt && f.with_alpha == want_alpha; },
+                                  [&] { return DFrame::create(in->width, in->height, stream_, as_fmt, want_alpha); });
     if (deep) {
         DeepArgs a{};
         for (int p = 0; p < 3; ++p) {
@@ -626,10 +621,9 @@ FrameRef Scaler::scale_keep(const FrameRef& in0) {
     const FrameRef in = planar_of(in0);
     if (in.f != in0.f && in->width == out_w_ && in->height == out_h_ && in->fmt == MX_PIXFMT_YUV420P) return in;
     if (!frame_ || in_w_ != in->width || in_h_ != in->height || in_fmt_ != in->fmt || in_alpha_ != in->with_alpha) retarget(in->width, in->height, in->fmt, in->with_alpha);
-    FrameRef out;
-    // (a layer that carries coverage keeps it through this path too: pool frames are made like retarget()'s ring frames, with a coverage plane when the input has one)
-    for (auto& f : keep_pool_) if (f->with_alpha == in_alpha_ && f->rc.load(std::memory_order_acquire) == 1) { out = f; break; }   // only the pool holds it
-    if (!out) { keep_pool_.push_back(FrameRef(DFrame::create(out_w_, out_h_, stream_, MX_PIXFMT_YUV420P, in_alpha_), false)); out = keep_pool_.back(); }
+    // (a layer that carries coverage keeps it through this path too: pool frames are made like retarget()'s ring frames, with a coverage plane when the input has one.
+    // Every frame of the pool is out_w_ x out_h_ yuv420p, and retarget() clears it: the coverage plane is all there is to match on)
+    FrameRef out = keep_pool_.take([&](const DFrame& f) { return f.with_alpha == in_alpha_; }, [&] { return DFrame::create(out_w_, out_h_, stream_, MX_PIXFMT_YUV420P, in_alpha_); });
     if (t_->geo.scaled_w == 0 || t_->geo.scaled_h == 0) return out;
     scale_into(in, t_, out, tmp_plane_, stream_);
     return out;
@@ -663,11 +657,7 @@ void VideoMixer::rebind(hipStream_t s, bool lazy_program, uint32_t ticks_per_sec
 }
 
 FrameRef VideoMixer::fresh_output(uint32_t w, uint32_t h) {
-    for (auto& f : pool_)
-        if (f->width == w && f->height == h && f->rc.load(std::memory_order_acquire) == 1) return f;   // only the pool holds it
-    if (pool_.size() >= 8) pool_.erase(pool_.begin());
-    pool_.push_back(FrameRef(DFrame::create(w, h, stream_), false));
-    return pool_.back();
+    return pool_.take([&](const DFrame& f) { return f.width == w && f.height == h; }, [&] { return DFrame::create(w, h, stream_); });
 }
 
 void VideoMixer::rescale(Channel& ch, uint32_t tw, uint32_t th) {   // Channel::rescale, video_mixer.rs:261-274

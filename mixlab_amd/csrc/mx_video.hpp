@@ -57,9 +57,9 @@ struct RgbaArgs {
 
 void launch_crossfade(const FadeArgs& a, hipStream_t s);
 void launch_scale_wide(const ScaleArgs& a, hipStream_t s);   // two passes through ScalePlane::tmp, any tap counts
-bool scale_tile_origins_match(uint32_t src, uint32_t dst, const int32_t* first);
+bool scale_tile_origins_match(uint32_t src, uint32_t dst, const int32_t* first);     // f64 window-origin formula of the tiled / inline scalers == tap table, every output
 uint32_t scale_origin_magic(uint32_t dst);   // floor(2^32 / (2 dst)): ScalePlane::mh / mv
-bool scale_tile_origins_match_m(uint32_t src, uint32_t dst, const int32_t* first);   // the integer form the tiled kernel uses == tap table, every output   // f64 window-origin formula of the tiled / inline scalers == tap table, every output
+bool scale_tile_origins_match_m(uint32_t src, uint32_t dst, const int32_t* first);   // the integer form the tiled kernel uses == tap table, every output
 
 // A chain of cross-fades evaluated per pixel in registers:  v = src[0];  for k >= 1:
 //   v = v_is_a[k-1] ? fade(v, src[k]) : fade(src[k], v)   with fade(a,b) = (a*f + b*(255-f)) / 255, f = fade[k-1]
@@ -376,6 +376,23 @@ inline FrameRef::FrameRef(DFrame* p, bool add_ref) : f(p) { if (f && add_ref) f-
 inline FrameRef::FrameRef(const FrameRef& o) : f(o.f) { if (f) f->retain(); }
 inline FrameRef::~FrameRef() { if (f) f->release(); }
 
+// Frames handed out over and over, oldest first.  The one rule of reuse: a pooled frame is rewritten only when the pool alone holds it -- its last reader (a
+// chain launched ticks later included) is on the stream already, or was a caller who let go of it.  (FrameStager::take_frame orders reuse with an event
+// across streams: another rule, not this one.)
+struct FramePool {
+    explicit FramePool(size_t cap_ = SIZE_MAX) : cap(cap_) {}
+    size_t cap;
+    std::vector<FrameRef> frames;
+    // the first frame `match` accepts that nobody else holds; else a frame from `make` (a DFrame* with its one reference), the oldest leaving a full pool for it
+    template <class Match, class Make> FrameRef take(Match match, Make make) {
+        for (const FrameRef& f : frames) if (match(*f.f) && f->rc.load(std::memory_order_acquire) == 1) return f;
+        if (frames.size() >= cap) frames.erase(frames.begin());
+        frames.push_back(FrameRef(make(), false));
+        return frames.back();
+    }
+    void clear() { frames.clear(); }
+};
+
 // flatten (a, b, fade) into a chain: extends a's (or b's) chain when that side is lazy
 std::shared_ptr<LazyChain> make_chain(const FrameRef& a, const FrameRef& b, uint8_t fade, hipStream_t s);
 void fill_chain_sources(const LazyChain& c, ChainSrc (&src)[MX_CHAIN_MAX_SRC], uint32_t& n_src,
@@ -434,8 +451,8 @@ private:
     uint8_t in_fmt_ = MX_PIXFMT_YUV420P;
     bool in_alpha_ = false;          // the input carries a coverage plane: so do the output frames
     FrameRef frame_;                 // cached blank output frame (encode.rs:382) -- the one the latest scale() wrote
-    std::vector<FrameRef> keep_pool_; // scale_keep's outputs: blank frames of this context's letterbox geometry, reused once released
-    std::vector<FrameRef> rgb_pool_; // yuv444p frames a packed RGB input is converted into before it is resampled
+    FramePool keep_pool_;            // scale_keep's outputs: blank frames of this context's letterbox geometry, reused once released (no cap: a sink keeps a submission's ticks)
+    FramePool rgb_pool_{2 * (size_t)video_batch_ticks() + 2};   // yuv444p frames a packed RGB input is converted into before it is resampled
     FrameRef planar_of(const FrameRef& in);
     std::vector<FrameRef> ring_;     // 2 * video_batch_ticks() of them, used in turn: the RGBA chains that read the last K may be launched together with the next K scales
     uint32_t ring_pos_ = 0;
@@ -478,7 +495,7 @@ private:
     Channel ch_[4];
     // output frames are fresh each tick in the reference; here a small ring recycles them once the
     // caller has dropped its references
-    std::vector<FrameRef> pool_;
+    FramePool pool_{8};
     FrameRef fresh_output(uint32_t w, uint32_t h);
 public:
     ~VideoMixer();

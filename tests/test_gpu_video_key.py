@@ -209,6 +209,43 @@ def test_ring_of_three_frames_over_a_batched_run_keeps_every_ticks_picture():
         assert planes is not None and all(np.array_equal(x, y) for x, y in zip(planes, want[k % 3])), f"queued: tick {k}"
 
 
+LONG_RING_HANDLES = 32   # distinct keyed frames one pass of the 40-frame ring delivers tick by tick.  MEASURED on the commit before the transform left Graph, not derived
+
+
+def test_ring_longer_than_the_done_list_recycles_keyed_frames_within_the_pool_cap():
+    """A ring of 40 distinct frames, more than the 32 entries the list of keyed frames holds, so every tick keys anew and the output frames come out of
+    the pool.  Two passes in ONE submission with a Monitor (its copies are its own, so the keyed frames recycle), then one pass tick by tick: every picture
+    is the model's, and the pass hands out a fixed number of distinct frames -- no fewer than the list pins, no more than the pool's cap of 64."""
+    W, H, N = 66, 34, 40
+    p = DEFAULT_CHROMA
+    pics = [km.green_screen(W, H, seed=s) for s in range(1, N + 1)]
+    keyed = [key_model(*pic, p) for pic in pics]
+    B = ov.HostFrame(W, H).fill(2, seed=9)
+    want = []
+    for pic in pics:
+        w = ov.HostFrame(W, H); ov.blank(w); ov.crossfade(w, model_layer(*pic, p), B, 0.8)
+        want.append([x.copy() for x in w.visible()])
+    g, sa, sb, m, mon = mixer_graph(2 * N, monitor=(W, H))
+    dB = video.DFrame(W, H).upload(*B.visible())
+    video.graph_set_video_source(g, sb, dB, repeat=True)
+    video.graph_set_video_source_key(g, sa, kp(p))
+    ring = [upload(*pic) for pic in pics]
+    video.graph_set_video_source_ring(g, sa, ring)
+    g.run_ticks(0, 2 * N)
+    for k, planes in enumerate(ingest.graph_read_monitor_video(g, mon, 0, 2 * N)):
+        assert planes is not None and all(np.array_equal(x, y) for x, y in zip(planes, want[k % N])), f"batched: tick {k}"
+    handles = set()
+    for k in range(N):
+        g.run_ticks(2 * N + k, 1)
+        out = video.graph_video_output(g, sa, 0)
+        assert_keyed(out, keyed[k], f"tick by tick: tick {k}")
+        handles.add(out.handle)
+        del out
+    print(f"distinct keyed frames in one pass of the ring: {len(handles)}")
+    assert 32 <= LONG_RING_HANDLES <= 64
+    assert len(handles) == LONG_RING_HANDLES
+
+
 def test_removing_the_key_gives_the_pictures_of_a_graph_that_never_had_it():
     W, H = 130, 74
     pic = km.green_screen(W, H, seed=6)

@@ -241,6 +241,46 @@ def test_ring_of_three_frames_over_a_batched_run_keeps_every_ticks_picture():
         assert planes is not None and all(np.array_equal(x, y) for x, y in zip(planes, want[k % 3])), f"queued: tick {k}"
 
 
+LONG_RING_HANDLES = 32   # distinct placed frames one pass of the 40-frame ring delivers tick by tick.  MEASURED on the commit before the transform left Graph, not derived
+
+
+def test_ring_longer_than_the_done_list_recycles_placed_frames_within_the_pool_cap():
+    """A ring of 40 distinct frames, more than the 32 entries the list of placed frames holds, keyed and placed: every tick keys into one pool (frames no
+    list holds) and places into the other.  Two passes in ONE submission with a Monitor (its copies are its own, so the placed frames recycle), then one pass
+    tick by tick: every picture is the model's, and the pass hands out a fixed number of distinct frames -- no fewer than the list pins, no more than the
+    pool's cap of 64."""
+    Wc, Hc, N = 66, 34, 40
+    p = PlaceP(Wc, Hc, 20, -4, 40, 24, 2, 2, 60, 30)
+    pics = [km.green_screen(Wc, Hc, seed=s) for s in range(1, N + 1)]
+    B = ov.HostFrame(Wc, Hc).fill(2, seed=9)
+    placed, want = [], []
+    for pic in pics:
+        yk, uk, vk, k = key_model(*pic, DEFAULT_CHROMA)
+        placed.append(place_model(yk, uk, vk, p, k))
+        w = ov.HostFrame(Wc, Hc); ov.blank(w); ov.crossfade(w, model_layer(placed[-1]), B, 0.8)
+        want.append([x.copy() for x in w.visible()])
+    g, sa, sb, m, mon = mixer_graph(2 * N, monitor=(Wc, Hc))
+    dB = video.DFrame(Wc, Hc).upload(*B.visible())
+    video.graph_set_video_source(g, sb, dB, repeat=True)
+    video.graph_set_video_source_key(g, sa, kp(DEFAULT_CHROMA))
+    video.graph_set_video_source_place(g, sa, pp(p))
+    ring = [upload(*pic, pad_seed=s) for s, pic in enumerate(pics)]
+    video.graph_set_video_source_ring(g, sa, ring)
+    g.run_ticks(0, 2 * N)
+    for k, planes in enumerate(ingest.graph_read_monitor_video(g, mon, 0, 2 * N)):
+        assert planes is not None and all(np.array_equal(x, y) for x, y in zip(planes, want[k % N])), f"batched: tick {k}"
+    handles = set()
+    for k in range(N):
+        g.run_ticks(2 * N + k, 1)
+        out = video.graph_video_output(g, sa, 0)
+        assert_planes(out, placed[k], f"tick by tick: tick {k}")
+        handles.add(out.handle)
+        del out
+    print(f"distinct placed frames in one pass of the ring: {len(handles)}")
+    assert 32 <= LONG_RING_HANDLES <= 64
+    assert len(handles) == LONG_RING_HANDLES
+
+
 def test_removing_the_placement_gives_the_pictures_of_a_graph_that_never_had_it():
     pic = km.green_screen(W, H, seed=6)
     B = ov.HostFrame(W, H).fill(1, seed=1)
