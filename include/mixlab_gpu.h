@@ -878,6 +878,44 @@ typedef struct {
     uint32_t spill_strength;  /* 0 .. 255; must be 0 in luma mode */
 } mx_video_key_params;        /* 24 bytes */
 int mx_video_key(const mx_dframe* in, const mx_video_key_params* params, mx_dframe** out, void* stream);
+/* The COLOUR CORRECTOR (BUILD-SPECIFIED; the reference has none): a luma curve, a chroma matrix and a 3D LUT applied to ONE frame in ONE launch
+ * on the device -- what matches camera 2 to camera 1 once the scopes have shown the difference.  `in` is yuv420p or yuva420p (anything else: MX_ERR_INVALID); *out is a NEW
+ * frame of the same size and the same format carrying one reference.  A coverage plane is copied byte for byte.  Stride padding is left as mx_dframe_create_fmt leaves it
+ * and is never read as picture.  All quantities are integers; `>>` on a negative value is the arithmetic shift (floor); clip8 clamps to 0 .. 255.
+ * The three stages run in this order, each switched by a flag bit; with no bit set the visible area is a copy.
+ *   CURVE (MX_GRADE_CURVE), per luma sample:  y1 = curve_y[Y]  (a table of 256 bytes); without the bit y1 = Y.
+ *   CHROMA (MX_GRADE_CHROMA), per chroma sample, du = U - 128, dv = V - 128:
+ *     u1 = clip8(128 + ((m_uu du + m_uv dv + off_u + 2048) >> 12));  v1 = clip8(128 + ((m_vu du + m_vv dv + off_v + 2048) >> 12))
+ *     coefficients Q12 with |m| <= 32767, offsets Q12 with |off| <= 255 * 4096: every sum fits an int32.  Without the bit u1 = U, v1 = V.
+ *   LUT (MX_GRADE_LUT) needs an mx_video_lut: a lattice of N = 2^k + 1 nodes per axis, k = lattice_log2 in {4, 5} (N = 17 or 33).  The node at (iy, iu, iv) is three
+ *     uint16 (Y', U', V') in Q4, each 0 .. 4096 (4096 stands for code value 256, so the top node of the identity is exact; a larger value is MX_ERR_INVALID at
+ *     creation), stored at nodes[((iy N + iu) N + iv) 3 + c].  With sh = 8 - k and S = 2^sh, the evaluation at (a, b, c) = (Y, U, V):
+ *       the cell is (a >> sh, b >> sh, c >> sh), the fractions f = (a & (S-1), b & (S-1), c & (S-1));  TETRAHEDRAL interpolation: order the axes by fraction,
+ *       f1 >= f2 >= f3; walk from the cell's low corner one step along the axis of f1, then of f2, then of f3: nodes n0 .. n3, weights S - f1, f1 - f2, f2 - f3, f3
+ *       (equal fractions give the vertex they would disagree on the weight 0: no tie rule is needed);  per output channel acc = sum w_i n_i[ch] (<= 65536) and the
+ *       result is min(255, (acc + 8 S) >> (sh + 4)).  The identity lattice (node = 16 S index per axis) returns its input exactly.
+ *     LUMA sample (x, y):  Y' = LUT_Y(y1, u1[y>>1][x>>1], v1[y>>1][x>>1]) -- the chroma of its own 2 x 2 block, no upsample.
+ *     CHROMA sample (cx, cy):  (U', V') = LUT_UV(ym, u1, v1) with ym = (y1[2cy][2cx] + y1[2cy][2cx+1] + y1[2cy+1][2cx] + y1[2cy+1][2cx+1] + 2) >> 2, the block's mean
+ *     of the CURVED luma.  Without the bit Y' = y1, U' = u1, V' = v1.
+ * A flag bit outside the three, a coefficient or offset out of range, the LUT bit without a LUT and a LUT without the bit are MX_ERR_INVALID.  Asynchronous on `stream`,
+ * like its neighbours.  Out of scope: the grade on a band-scaled source and on mixer output ports, other pixel formats, 65-point lattices, and reading .cube files (the
+ * host resamples them to the lattice). */
+enum { MX_GRADE_CURVE = 1, MX_GRADE_CHROMA = 2, MX_GRADE_LUT = 4 };
+typedef struct {
+    uint32_t flags;                                  /* MX_GRADE_* bits */
+    uint8_t  curve_y[256];
+    int32_t  m_uu, m_uv, m_vu, m_vv, off_u, off_v;   /* Q12 */
+} mx_video_grade_params;                             /* 284 bytes */
+typedef struct mx_video_lut mx_video_lut;            /* immutable, reference-counted, uploaded once at creation */
+int  mx_video_lut_create(uint32_t lattice_log2, const uint16_t* nodes /* [N][N][N][3] */, mx_video_lut** out);   /* one reference for the caller; checks come before any device work */
+int  mx_video_lut_retain(mx_video_lut* lut);
+void mx_video_lut_release(mx_video_lut* lut);
+int  mx_video_lut_identity(uint32_t lattice_log2, uint16_t* nodes /* [N][N][N][3] */);   /* host only */
+/* Host only, f64: curve_y[i] = clip8(rint(255 * clamp((i - black) / (white - black), 0, 1) ^ (1 / gamma))), the matrix rint(4096 * saturation * [[cos h, sin h],
+ * [-sin h, cos h]]) (rows u, v), zero offsets, flags CURVE | CHROMA.  MX_ERR_INVALID for white <= black, gamma <= 0 or a coefficient outside +-32767;
+ * (0, 255, 1, 1, 0) gives the identity table and 4096 * I exactly. */
+int  mx_video_grade_procamp(double black, double white, double gamma, double saturation, double hue_degrees, mx_video_grade_params* out);
+int  mx_video_grade(const mx_dframe* in, const mx_video_grade_params* params, const mx_video_lut* lut /* NULL iff the LUT bit is clear */, mx_dframe** out, void* stream);
 /* The PLACER (BUILD-SPECIFIED; the reference has none): a crop of a frame resampled into a rectangle of a transparent canvas, on the device --
  * picture-in-picture, side-by-side, a keyed presenter in a corner, a zoom.  `in` is yuv420p or yuva420p (anything else: MX_ERR_INVALID -- conversion is the scaler's
  * business); *out is a NEW yuva420p frame of canvas_w x canvas_h carrying one reference, its stride padding as mx_dframe_create_fmt leaves it.  The input's padding, and
@@ -998,6 +1036,16 @@ int mx_graph_set_video_source_key(mx_graph* g, uint32_t node, const mx_video_key
  * order.  A source frame of another format, or a crop outside the frame that arrives, fails the run with MX_ERR_INVALID, mx_last_error naming the node, before anything of the
  * run is launched.  A scope tap on the source's port sees the placed frame.  mx_graph_adopt_state does not carry the setting. */
 int mx_graph_set_video_source_place(mx_graph* g, uint32_t node, const mx_video_place_params* params /* NULL removes */);
+/* The colour corrector as a per-source transform (mx_video_grade), under the keyer's rules: it applies to every frame the SOURCE_VIDEO node
+ * delivers, whichever feeder brought it; a frame is graded once per setting and the result reused (a ring of n frames costs n launches, not one per tick); output frames
+ * come from a pool and are rewritten only when the pool alone holds them.  The graph retains `lut`, so the caller may release it at once.  Where several transforms are set
+ * on a node the order is GRADE, THEN KEY, THEN PLACE, whatever the call order: the input is corrected first and the key is decided on the corrected colour.  A scope tap on
+ * the source's port sees the graded frame.  Setting it again drops what was cached under the old setting, from the next run on; params NULL removes the transform (lut is
+ * then ignored).  MX_ERR_TYPE for a node that is not a SOURCE_VIDEO; MX_ERR_INVALID for a flag bit outside the three, a coefficient out of range, the LUT bit with no LUT
+ * or a LUT without the bit, and together with mx_graph_set_video_source_band, in either call order (grading a band-scaled layer is a stated follow-up); each leaves the
+ * graph usable.  A source frame that is not yuv420p / yuva420p fails the run with MX_ERR_INVALID before anything is launched, mx_last_error naming the node.
+ * mx_graph_adopt_state does not carry the setting. */
+int mx_graph_set_video_source_grade(mx_graph* g, uint32_t node, const mx_video_grade_params* params /* NULL removes */, mx_video_lut* lut);
 /* One frame due on one tick of a SOURCE_VIDEO node: tick `tick` (absolute, as in mx_graph_run_ticks' first_tick + k) emits `frame` with the
  * given duration hint and tick offset; ticks without an entry emit None.  Entries are queued in ascending tick order, one per tick
  * (MX_ERR_INVALID otherwise), and while any is queued they take the place of mx_graph_set_video_source[_ring].  What

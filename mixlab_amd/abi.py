@@ -254,6 +254,24 @@ _proto("mx_video_key", C.c_int, C.c_void_p, C.POINTER(VideoKeyParams), C.POINTER
 _proto("mx_graph_set_video_source_key", C.c_int, C.c_void_p, C.c_uint32, C.POINTER(VideoKeyParams))
 
 
+GRADE_CURVE, GRADE_CHROMA, GRADE_LUT = 1, 2, 4
+
+
+class VideoGradeParams(C.Structure):
+    """mx_video_grade_params (284 bytes): the stages' flag bits, the luma curve, the Q12 chroma matrix (rows u, v) and offsets."""
+    _fields_ = [("flags", C.c_uint32), ("curve_y", C.c_uint8 * 256), ("m_uu", C.c_int32), ("m_uv", C.c_int32), ("m_vu", C.c_int32), ("m_vv", C.c_int32),
+                ("off_u", C.c_int32), ("off_v", C.c_int32)]
+
+
+_proto("mx_video_lut_create", C.c_int, C.c_uint32, C.c_void_p, C.POINTER(C.c_void_p))
+_proto("mx_video_lut_retain", C.c_int, C.c_void_p)
+_proto("mx_video_lut_release", None, C.c_void_p)
+_proto("mx_video_lut_identity", C.c_int, C.c_uint32, C.c_void_p)
+_proto("mx_video_grade_procamp", C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(VideoGradeParams))
+_proto("mx_video_grade", C.c_int, C.c_void_p, C.POINTER(VideoGradeParams), C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p)
+_proto("mx_graph_set_video_source_grade", C.c_int, C.c_void_p, C.c_uint32, C.POINTER(VideoGradeParams), C.c_void_p)
+
+
 class VideoPlaceParams(C.Structure):
     """mx_video_place_params (40 bytes): the canvas, the crop of the input (0 x 0: the whole frame) and the rectangle of the canvas it is stretched into."""
     _fields_ = [("canvas_w", C.c_uint32), ("canvas_h", C.c_uint32), ("crop_x", C.c_uint32), ("crop_y", C.c_uint32), ("crop_w", C.c_uint32), ("crop_h", C.c_uint32),

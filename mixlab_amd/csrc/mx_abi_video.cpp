@@ -19,6 +19,7 @@ static inline mx_dframe* H(DFrame* p) { return reinterpret_cast<mx_dframe*>(p); 
 
 struct mx_video_mixer { std::unique_ptr<mx::VideoMixer> m; };
 struct mx_graph { std::unique_ptr<mx::Graph> g; };   // same layout as in mx_abi.cpp
+struct mx_video_lut { std::atomic<int> rc{1}; std::shared_ptr<const mx::LutTables> t; };   // whoever grades with it (a graph's source transform) shares t, not the handle
 
 extern "C" const char* mx_last_error(void);
 void mx_set_last_error(const std::string& s);   // mx_abi.cpp
@@ -354,6 +355,44 @@ int mx_video_key(const mx_dframe* in, const mx_video_key_params* params, mx_dfra
     });
 }
 
+int mx_video_lut_create(uint32_t lattice_log2, const uint16_t* nodes, mx_video_lut** out) {
+    return guard([&] {
+        REQUIRE(out, "out is NULL");
+        *out = nullptr;
+        mx::check_lut_nodes(lattice_log2, nodes);   // before any device work
+        auto l = std::make_unique<mx_video_lut>();
+        l->t = mx::make_lut_tables(lattice_log2, nodes);
+        *out = l.release();
+    });
+}
+int mx_video_lut_retain(mx_video_lut* lut) {
+    return guard([&] { REQUIRE(lut, "lut is NULL"); lut->rc.fetch_add(1, std::memory_order_relaxed); });
+}
+void mx_video_lut_release(mx_video_lut* lut) {
+    if (lut && lut->rc.fetch_sub(1, std::memory_order_acq_rel) == 1) delete lut;
+}
+int mx_video_lut_identity(uint32_t lattice_log2, uint16_t* nodes) {
+    return guard([&] { mx::lut_identity(lattice_log2, nodes); });
+}
+int mx_video_grade_procamp(double black, double white, double gamma, double saturation, double hue_degrees, mx_video_grade_params* out) {
+    return guard([&] { REQUIRE(out, "out is NULL"); mx::grade_procamp(black, white, gamma, saturation, hue_degrees, *out); });
+}
+int mx_video_grade(const mx_dframe* in, const mx_video_grade_params* params, const mx_video_lut* lut, mx_dframe** out, void* stream) {
+    return guard([&] {
+        REQUIRE(out, "out is NULL");
+        *out = nullptr;
+        REQUIRE(in && params, "NULL argument");
+        mx::check_grade_params(*params, lut != nullptr);
+        DFrame* d = const_cast<DFrame*>(D(in));
+        REQUIRE(mx::key_input_ok(d), "the colour corrector takes yuv420p or yuva420p (scale a frame of another format first)");
+        hipStream_t s = S(stream);
+        FrameRef o(DFrame::create(d->width, d->height, s, MX_PIXFMT_YUV420P, d->with_alpha), false);
+        mx::grade_into(d, *params, lut ? lut->t.get() : nullptr, o.f, s);
+        o->retain();
+        *out = H(o.f);
+    });
+}
+
 int mx_video_place(const mx_dframe* in, const mx_video_place_params* params, mx_dframe** out, void* stream) {
     return guard([&] {
         REQUIRE(out, "out is NULL");
@@ -510,6 +549,9 @@ int mx_graph_set_video_source_key(mx_graph* g, uint32_t node, const mx_video_key
 }
 int mx_graph_set_video_source_place(mx_graph* g, uint32_t node, const mx_video_place_params* params) {
     return guard([&] { REQUIRE(g, "graph is NULL"); g->g->set_video_source_place(node, params); });
+}
+int mx_graph_set_video_source_grade(mx_graph* g, uint32_t node, const mx_video_grade_params* params, mx_video_lut* lut) {
+    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->set_video_source_grade(node, params, (params && lut) ? lut->t : nullptr); });
 }
 int mx_graph_video_output(mx_graph* g, uint32_t node, uint32_t port, mx_dframe** out) {
     return guard([&] {

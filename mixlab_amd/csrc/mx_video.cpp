@@ -3,6 +3,7 @@
 
 #include <algorithm>
 #include <array>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <map>
@@ -751,6 +752,92 @@ void key_into(DFrame* in, const mx_video_key_params& p, DFrame* out, hipStream_t
     a.near_q4 = p.near_q4; a.far_q4 = p.far_q4; a.spill_far_q4 = p.spill_far_q4; a.spill_strength = p.spill_strength;
     launch_video_key(a, s);
     hip_check(hipGetLastError(), "key launch");
+}
+
+// ---------------------------------------------------------------------------------------------
+// the colour corrector (mixlab_gpu.h mx_video_grade; kernel in mx_k_grade.hip)
+// ---------------------------------------------------------------------------------------------
+void check_grade_params(const mx_video_grade_params& p, bool has_lut) {
+    if (p.flags & ~(uint32_t)(MX_GRADE_CURVE | MX_GRADE_CHROMA | MX_GRADE_LUT)) throw Error(MX_ERR_INVALID, "mx_video_grade_params: flags holds a bit outside MX_GRADE_CURVE | MX_GRADE_CHROMA | MX_GRADE_LUT");
+    for (int32_t m : {p.m_uu, p.m_uv, p.m_vu, p.m_vv}) if (m > 32767 || m < -32767) throw Error(MX_ERR_INVALID, "mx_video_grade_params: a matrix coefficient lies outside +-32767");
+    for (int32_t o : {p.off_u, p.off_v}) if (o > 255 * 4096 || o < -255 * 4096) throw Error(MX_ERR_INVALID, "mx_video_grade_params: an offset lies outside +-255 * 4096");
+    if ((p.flags & MX_GRADE_LUT) && !has_lut) throw Error(MX_ERR_INVALID, "mx_video_grade: MX_GRADE_LUT is set and lut is NULL");
+    if (!(p.flags & MX_GRADE_LUT) && has_lut) throw Error(MX_ERR_INVALID, "mx_video_grade: a lut is given and MX_GRADE_LUT is not set");
+}
+
+static uint32_t lut_axis(uint32_t lattice_log2) {
+    if (lattice_log2 != 4u && lattice_log2 != 5u) throw Error(MX_ERR_INVALID, "mx_video_lut: lattice_log2 must be 4 or 5 (17 or 33 nodes per axis)");
+    return (1u << lattice_log2) + 1u;
+}
+
+void check_lut_nodes(uint32_t lattice_log2, const uint16_t* nodes) {
+    const size_t n = lut_axis(lattice_log2), count = n * n * n * 3;
+    if (!nodes) throw Error(MX_ERR_INVALID, "mx_video_lut: nodes is NULL");
+    for (size_t i = 0; i < count; ++i) if (nodes[i] > 4096u) throw Error(MX_ERR_INVALID, "mx_video_lut: a node value above 4096 (Q4 of code value 256)");
+}
+
+std::shared_ptr<const LutTables> make_lut_tables(uint32_t lattice_log2, const uint16_t* nodes) {
+    check_lut_nodes(lattice_log2, nodes);
+    auto t = std::make_shared<LutTables>();
+    t->k = lattice_log2; t->n = lut_axis(lattice_log2);
+    const size_t count = (size_t)t->n * t->n * t->n;
+    t->y_bytes = (count * 2 + 15) & ~(size_t)15; t->uv_bytes = (count * 4 + 15) & ~(size_t)15;
+    std::vector<uint8_t> host(t->y_bytes + t->uv_bytes, 0);
+    uint16_t* hy = reinterpret_cast<uint16_t*>(host.data());
+    uint32_t* huv = reinterpret_cast<uint32_t*>(host.data() + t->y_bytes);
+    for (size_t i = 0; i < count; ++i) { hy[i] = nodes[3 * i]; huv[i] = (uint32_t)nodes[3 * i + 1] | (uint32_t)nodes[3 * i + 2] << 16; }
+    t->dev.alloc(host.size());
+    hip_check(hipMemcpy(t->dev.p, host.data(), host.size(), hipMemcpyHostToDevice), "hipMemcpy(H2D lut)");
+    return t;
+}
+
+void lut_identity(uint32_t lattice_log2, uint16_t* nodes) {
+    const uint32_t n = lut_axis(lattice_log2), step = 16u << (8u - lattice_log2);   // 16 S
+    if (!nodes) throw Error(MX_ERR_INVALID, "mx_video_lut_identity: nodes is NULL");
+    for (uint32_t iy = 0; iy < n; ++iy) for (uint32_t iu = 0; iu < n; ++iu) for (uint32_t iv = 0; iv < n; ++iv) {
+        uint16_t* o = nodes + (((size_t)iy * n + iu) * n + iv) * 3;
+        o[0] = (uint16_t)(step * iy); o[1] = (uint16_t)(step * iu); o[2] = (uint16_t)(step * iv);
+    }
+}
+
+void grade_procamp(double black, double white, double gamma, double saturation, double hue_degrees, mx_video_grade_params& out) {
+    if (!(white > black) || !(gamma > 0.0) || !std::isfinite(black) || !std::isfinite(white) || !std::isfinite(gamma))
+        throw Error(MX_ERR_INVALID, "mx_video_grade_procamp: white > black and gamma > 0, all finite");
+    const double h = hue_degrees * (M_PI / 180.0), c = 4096.0 * saturation * std::cos(h), s = 4096.0 * saturation * std::sin(h);
+    const double m[4] = {std::rint(c), std::rint(s), std::rint(-s), std::rint(c)};
+    for (double x : m) if (!(std::fabs(x) <= 32767.0)) throw Error(MX_ERR_INVALID, "mx_video_grade_procamp: saturation gives a coefficient outside +-32767");
+    mx_video_grade_params p{};
+    p.flags = MX_GRADE_CURVE | MX_GRADE_CHROMA;
+    for (int i = 0; i < 256; ++i) {
+        const double t = std::min(1.0, std::max(0.0, ((double)i - black) / (white - black)));
+        const double v = std::rint(255.0 * std::pow(t, 1.0 / gamma));
+        p.curve_y[i] = (uint8_t)std::min(255.0, std::max(0.0, v));
+    }
+    p.m_uu = (int32_t)m[0]; p.m_uv = (int32_t)m[1]; p.m_vu = (int32_t)m[2]; p.m_vv = (int32_t)m[3];
+    out = p;
+}
+
+void grade_into(DFrame* in, const mx_video_grade_params& p, const LutTables* lut, DFrame* out, hipStream_t s) {
+    if (!key_input_ok(in)) throw Error(MX_ERR_INVALID, "the colour corrector takes yuv420p or yuva420p (scale a frame of another format first)");
+    if (out->fmt != MX_PIXFMT_YUV420P || out->width != in->width || out->height != in->height || (out->alpha != nullptr) != in->with_alpha)
+        throw Error(MX_ERR_INTERNAL, "grade: the output frame is not of the input's size and format");
+    in->ensure_pixels(s);
+    flush_scales(s);   // the input may be a scaler's output whose job is still queued
+    GradeArgs a{};
+    a.y = in->data[0]; a.u = in->data[1]; a.v = in->data[2]; a.a_in = in->alpha;
+    a.y_stride = in->stride[0]; a.u_stride = in->stride[1]; a.v_stride = in->stride[2]; a.a_stride = in->alpha ? in->alpha_stride : 0u;
+    a.oy = out->data[0]; a.ou = out->data[1]; a.ov = out->data[2]; a.oa = out->alpha;
+    a.oy_stride = out->stride[0]; a.ou_stride = out->stride[1]; a.ov_stride = out->stride[2]; a.oa_stride = out->alpha ? out->alpha_stride : 0u;
+    a.width = in->width; a.height = in->height;
+    a.flags = p.flags;
+    a.m_uu = p.m_uu; a.m_uv = p.m_uv; a.m_vu = p.m_vu; a.m_vv = p.m_vv; a.off_u = p.off_u; a.off_v = p.off_v;
+    std::memcpy(a.curve, p.curve_y, 256);
+    if (p.flags & MX_GRADE_LUT) {
+        if (!lut) throw Error(MX_ERR_INTERNAL, "grade: the LUT stage is on and there is no lattice");
+        a.lut_y = lut->y(); a.lut_uv = lut->uv(); a.lut_k = lut->k;
+    }
+    launch_video_grade(a, s);
+    hip_check(hipGetLastError(), "grade launch");
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -176,6 +176,37 @@ bool key_input_ok(const DFrame* in);                   // yuv420p, with or witho
 // `in` keyed under p into `out` (yuva420p of in's size, created by DFrame::create: the kernel leaves its padding as it is), asynchronous on s
 void key_into(DFrame* in, const mx_video_key_params& p, DFrame* out, hipStream_t s);
 
+// ---- the colour corrector (mixlab_gpu.h mx_video_grade; mx_k_grade.hip) ----
+struct GradeArgs {
+    const uint8_t* y; const uint8_t* u; const uint8_t* v; const uint8_t* a_in;   // a_in nullptr: no coverage plane (then oa is nullptr too)
+    uint8_t* oy; uint8_t* ou; uint8_t* ov; uint8_t* oa;
+    uint32_t y_stride, u_stride, v_stride, a_stride, oy_stride, ou_stride, ov_stride, oa_stride;
+    uint32_t width, height;                        // luma size, both even
+    uint32_t flags;                                // MX_GRADE_* bits
+    int32_t m_uu, m_uv, m_vu, m_vv, off_u, off_v;
+    const uint16_t* lut_y; const uint32_t* lut_uv; // the lattice on the device (LutTables): Y' per node, and U' | V' << 16 per node
+    uint32_t lut_k;                                // lattice_log2
+    // launcher-filled
+    uint32_t chunks_x, n_threads;
+    uint8_t curve[256];                            // read out of the kernel arguments with a per-lane index
+};
+// The lattice of an mx_video_lut as the kernel reads it: ONE allocation, Y' (uint16 per node, padded to 16 bytes) followed by U' | V' << 16 (uint32 per node).
+// A luma sample gathers 4 x 2 bytes and a chroma sample 4 x 4 bytes instead of 4 x 6 of the interleaved nodes, and the 17-lattice (29 504 bytes) fits the L1.
+struct LutTables {
+    uint32_t k = 0, n = 0;                         // lattice_log2, nodes per axis
+    DevBuf dev; size_t y_bytes = 0, uv_bytes = 0;  // both multiples of 16
+    const uint16_t* y() const { return (const uint16_t*)dev.p; }
+    const uint32_t* uv() const { return (const uint32_t*)((const uint8_t*)dev.p + y_bytes); }
+};
+void launch_video_grade(GradeArgs a, hipStream_t s);
+void check_grade_params(const mx_video_grade_params& p, bool has_lut);   // MX_ERR_INVALID outside what the header states
+void check_lut_nodes(uint32_t lattice_log2, const uint16_t* nodes);      // likewise; touches no device
+std::shared_ptr<const LutTables> make_lut_tables(uint32_t lattice_log2, const uint16_t* nodes);   // checked nodes, uploaded (synchronous)
+void lut_identity(uint32_t lattice_log2, uint16_t* nodes);
+void grade_procamp(double black, double white, double gamma, double saturation, double hue_degrees, mx_video_grade_params& out);
+// `in` graded under p into `out` (in's size and format, created by DFrame::create: the kernel leaves its padding as it is), asynchronous on s
+void grade_into(DFrame* in, const mx_video_grade_params& p, const LutTables* lut, DFrame* out, hipStream_t s);
+
 // ---- the placer (mixlab_gpu.h mx_video_place; mx_k_place.hip) ----
 // A workgroup writes one MX_PLACE_TILE_W x MX_PLACE_TILE_H byte tile of one canvas plane; the LDS-tiled form takes axes of up to MX_PLACE_TAP_BOUND taps.
 enum { MX_PLACE_TILE_W = 64, MX_PLACE_TILE_H = 16, MX_PLACE_TAP_BOUND = 18 };

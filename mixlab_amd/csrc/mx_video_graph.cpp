@@ -15,10 +15,20 @@ void SourceTransform::DoneCache::make_room() {
     if (list.size() >= 32) list.erase(list.begin());
 }
 
+void SourceTransform::set_grade(const mx_video_grade_params* p, std::shared_ptr<const LutTables> lut) {
+    // frames graded under the old setting are of no use, and neither is what was keyed or placed from them; the output frames stay in the pool (they match on size
+    // and coverage, not on the setting) and are rewritten once their last holder has let go.  The old lattice lives until the launches that read it are behind the
+    // new setting's on the stream: hipFree waits for the device
+    graded_.clear(); keyed_.clear(); placed_.clear();
+    grade_on_ = p != nullptr;
+    if (p) { grade_ = *p; grade_lut_ = std::move(lut); } else { grade_lut_.reset(); grade_pool_.clear(); }
+}
+
 void SourceTransform::set_key(const mx_video_key_params* p) {
     // frames keyed under the old setting are of no use; their output frames stay in the pool and are rewritten once their last holder has let go
     keyed_.clear();
     placed_.clear();   // a placed frame holds the picture as it was keyed
+    graded_.clear();   // listed only while the grade is the last stage: entries from before must not pin their pool frames
     key_on_ = p != nullptr;
     if (p) key_ = *p; else key_pool_.clear();
 }
@@ -29,26 +39,37 @@ void SourceTransform::set_place(const mx_video_place_params* p) {
     place_on_ = p != nullptr;
     if (p) place_ = *p;
     keyed_.clear();   // the keyed frames a placed source needs are the placer's alone and never listed; those listed before must not pin their pool frames
+    graded_.clear();  // likewise
 }
 
 const char* SourceTransform::input_error(const DFrame* f) const {
+    if (grade_on_ && !key_input_ok(f)) return "the colour corrector takes yuv420p or yuva420p frames (mx_graph_set_video_source_grade)";
     if (key_on_ && !key_input_ok(f)) return "the keyer takes yuv420p or yuva420p frames (mx_graph_set_video_source_key)";
-    return place_on_ ? place_input_error(f, place_) : nullptr;
+    return place_on_ ? place_input_error(f, place_) : nullptr;   // the grade and the key keep the frame's size, so the crop is checked against the frame as it arrives
 }
 
-// `src` keyed (where a key is set), then placed (where a placement is): once per setting, reused while anything but the list holds the source frame.
+// `src` graded (where a grade is set), then keyed (where a key is), then placed (where a placement is): once per setting, reused while anything but the list holds
+// the source frame.
 FrameRef SourceTransform::apply(const FrameRef& src, hipStream_t s) {
     // Graph::run looked at every frame the run can deliver before it launched anything
     if (input_error(src.f)) throw Error(MX_ERR_INTERNAL, "a video source's transform met a frame the run's check of its frames did not see");
-    DoneCache& done = place_on_ ? placed_ : keyed_;
+    DoneCache& done = place_on_ ? placed_ : (key_on_ ? keyed_ : graded_);
     if (FrameRef o = done.find(src.f)) return o;
     done.make_room();
     FrameRef o = src;
-    if (key_on_) {   // both pools match on the size: the key's frames have the source frames' sizes, which may differ from one to the next
+    if (grade_on_) {   // the pools match on the size (and this one on the coverage plane): the frames have the source frames' sizes, which may differ from one to the next
+        const uint32_t w = src->width, h = src->height;
+        const bool al = src->with_alpha;
+        o = grade_pool_.take([&](const DFrame& f) { return f.width == w && f.height == h && f.with_alpha == al; },
+                             [&] { return DFrame::create(w, h, s, MX_PIXFMT_YUV420P, al); });   // the corrector leaves the padding as DFrame::create made it
+        grade_into(src.f, grade_, grade_lut_.get(), o.f, s);
+    }
+    if (key_on_) {
+        const FrameRef in = o;
         const uint32_t w = src->width, h = src->height;
         o = key_pool_.take([&](const DFrame& f) { return f.width == w && f.height == h; },
                            [&] { return DFrame::create(w, h, s, MX_PIXFMT_YUV420P, true); });   // the keyer leaves the padding as DFrame::create made it
-        key_into(src.f, key_, o.f, s);
+        key_into(in.f, key_, o.f, s);
     }
     if (place_on_) {
         const FrameRef in = o;
@@ -92,7 +113,7 @@ void VideoSourceState::adopt(const VideoSourceState& old) {
     sched = old.sched;
     band = old.band; band_pool = old.band_pool;
     frame = old.frame; dur = old.dur; off = old.off; repeat = old.repeat; pending = old.pending;
-    // `transform` is NOT carried: mixlab_gpu.h says of mx_graph_set_video_source_key and of _place "mx_graph_adopt_state does not carry the setting"
+    // `transform` is NOT carried: mixlab_gpu.h says of mx_graph_set_video_source_grade, of _key and of _place "mx_graph_adopt_state does not carry the setting"
 }
 
 // ---- VIDEO_TO_RGBA ----
@@ -408,6 +429,7 @@ void Graph::set_video_source(uint32_t node, DFrame* frame, Rational dur, Rationa
 void Graph::set_video_source_band(uint32_t node, uint32_t in_w, uint32_t in_full_h, uint32_t src_row0, uint32_t slice_rows,
                                   uint32_t full_w, uint32_t full_h, uint32_t row0, uint32_t band_rows) {
     VideoSourceState& v = *node_of_kind(node, MX_KIND_SOURCE_VIDEO, "SOURCE_VIDEO").vsrc;
+    if (band_rows && v.transform.grade_on()) throw Error(MX_ERR_INVALID, "video source band: the source is graded (mx_graph_set_video_source_grade); grading a band-scaled layer is not supported");
     if (band_rows && v.transform.key_on()) throw Error(MX_ERR_INVALID, "video source band: the source is keyed (mx_graph_set_video_source_key), and a band-scaled layer cannot carry coverage");
     if (band_rows && v.transform.place_on()) throw Error(MX_ERR_INVALID, "video source band: the source is placed (mx_graph_set_video_source_place), and a band-scaled layer cannot carry coverage");
     sync();                                     // a previous band scaler's row buffer may be in use
@@ -424,6 +446,17 @@ void Graph::set_video_source_key(uint32_t node, const mx_video_key_params* param
         if (v.band) throw Error(MX_ERR_INVALID, "video source key: the source delivers a row band of a scaled layer (mx_graph_set_video_source_band), which cannot carry coverage");
     }
     v.transform.set_key(params);
+}
+
+void Graph::set_video_source_grade(uint32_t node, const mx_video_grade_params* params, std::shared_ptr<const LutTables> lut) {
+    if (node >= nodes_.size()) throw Error(MX_ERR_INVALID, "node out of range");
+    if (nodes_[node].kind != MX_KIND_SOURCE_VIDEO) throw Error(MX_ERR_TYPE, "video source grade: node is not a SOURCE_VIDEO");
+    VideoSourceState& v = *nodes_[node].vsrc;
+    if (params) {
+        check_grade_params(*params, lut != nullptr);
+        if (v.band) throw Error(MX_ERR_INVALID, "video source grade: the source delivers a row band of a scaled layer (mx_graph_set_video_source_band); grading a band-scaled layer is not supported");
+    }
+    v.transform.set_grade(params, std::move(lut));
 }
 
 void Graph::set_video_source_place(uint32_t node, const mx_video_place_params* params) {

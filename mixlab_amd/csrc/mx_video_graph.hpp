@@ -24,21 +24,23 @@ struct HopCounter {
     bool tick() { return c++ % hop == 0; }   // record this tick?  Then advance
 };
 
-// The keyer and the placer as a transform of a SOURCE_VIDEO's frames (mx_graph_set_video_source_key / _place): key, then place, where both are set.  A frame is
-// transformed once per setting.
+// The colour corrector, the keyer and the placer as a transform of a SOURCE_VIDEO's frames (mx_graph_set_video_source_grade / _key / _place): grade, then key, then
+// place, where several are set.  A frame is transformed once per setting.
 class SourceTransform {
 public:
+    void set_grade(const mx_video_grade_params* p, std::shared_ptr<const LutTables> lut);   // nullptr removes; the parameters were checked
     void set_key(const mx_video_key_params* p);       // nullptr removes; the parameters were checked
     void set_place(const mx_video_place_params* p);   // likewise
+    bool grade_on() const { return grade_on_; }
     bool key_on() const { return key_on_; }
     bool place_on() const { return place_on_; }
-    bool active() const { return key_on_ || place_on_; }
+    bool active() const { return grade_on_ || key_on_ || place_on_; }
     const char* input_error(const DFrame* f) const;   // nullptr, or why the transform cannot take this frame
     FrameRef apply(const FrameRef& src, hipStream_t s);
 private:
     // Frames transformed under the current setting, newest last: an entry holds the source frame (so its address stays its identity) and lives while anything
-    // else does.  With a placement set, src is the frame the FEEDER delivered: the keyed frame between the two passes is a pool frame nobody else sees, read by
-    // the placement launched right behind the key on the stream, and is listed nowhere.
+    // else does.  With several stages set, src is the frame the FEEDER delivered and out the LAST stage's frame: a graded or keyed frame between two passes is a
+    // pool frame nobody else sees, read by the pass launched right behind it on the stream, and is listed nowhere.
     struct DoneCache {
         struct Entry { FrameRef src, out; };
         std::vector<Entry> list;
@@ -46,13 +48,15 @@ private:
         void make_room();   // entries whose source frame only this list still holds can never be asked for again; the oldest goes too when the list is full (32)
         void clear() { list.clear(); }
     };
-    bool key_on_ = false, place_on_ = false;
+    bool grade_on_ = false, key_on_ = false, place_on_ = false;
+    mx_video_grade_params grade_{};
+    std::shared_ptr<const LutTables> grade_lut_;      // retained for as long as the setting stands: the caller may release its handle at once
     mx_video_key_params key_{};
     mx_video_place_params place_{};
     std::shared_ptr<const PlaceTables> place_tabs_;   // of the current setting (and, for a whole-frame crop, of the size of the frame seen last)
-    DoneCache keyed_, placed_;   // keyed_ is used only while no placement is set
+    DoneCache graded_, keyed_, placed_;   // the list of the LAST stage set is the one in use: placed_, else keyed_, else graded_
     // output frames.  64 is twice the list above: a frame that leaves the list is still in the pool, so a long ring recycles frames instead of allocating
-    FramePool key_pool_{64}, place_pool_{64};
+    FramePool grade_pool_{64}, key_pool_{64}, place_pool_{64};
 };
 
 struct VideoSourceState {   // SOURCE_VIDEO

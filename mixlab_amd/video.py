@@ -350,6 +350,75 @@ def graph_set_video_source_key(g, node, params):
     check(lib.mx_graph_set_video_source_key(g._h, node, C.byref(params) if params is not None else None))
 
 
+GRADE_CURVE, GRADE_CHROMA, GRADE_LUT = abi.GRADE_CURVE, abi.GRADE_CHROMA, abi.GRADE_LUT
+
+
+def GradeParams(flags=0, curve_y=None, matrix=(4096, 0, 0, 4096), offsets=(0, 0)) -> abi.VideoGradeParams:
+    """mx_video_grade_params: the MX_GRADE_* bits, the 256-entry luma table (None: the identity), the Q12 matrix (m_uu, m_uv, m_vu, m_vv) and the Q12 offsets (off_u, off_v)"""
+    p = abi.VideoGradeParams()
+    p.flags = int(flags)
+    table = np.arange(256, dtype=np.uint8) if curve_y is None else np.ascontiguousarray(curve_y, dtype=np.uint8)
+    if table.shape != (256,):
+        raise ValueError("curve_y must hold 256 bytes")
+    C.memmove(p.curve_y, table.ctypes.data, 256)
+    p.m_uu, p.m_uv, p.m_vu, p.m_vv = (int(x) for x in matrix)
+    p.off_u, p.off_v = (int(x) for x in offsets)
+    return p
+
+
+def grade_procamp(black=0.0, white=255.0, gamma=1.0, saturation=1.0, hue_degrees=0.0) -> abi.VideoGradeParams:
+    """mx_video_grade_procamp (host, f64): black / white points and gamma as the luma table, saturation and hue as the chroma matrix; flags CURVE | CHROMA"""
+    p = abi.VideoGradeParams()
+    check(lib.mx_video_grade_procamp(float(black), float(white), float(gamma), float(saturation), float(hue_degrees), C.byref(p)))
+    return p
+
+
+def lut_identity(lattice_log2: int) -> np.ndarray:
+    """mx_video_lut_identity (host): the [N][N][N][3] uint16 lattice, N = 2^lattice_log2 + 1, that returns its input"""
+    n = (1 << int(lattice_log2)) + 1 if 0 <= int(lattice_log2) < 16 else 1
+    nodes = np.zeros((n, n, n, 3), np.uint16)
+    check(lib.mx_video_lut_identity(int(lattice_log2), nodes.ctypes.data_as(C.c_void_p)))
+    return nodes
+
+
+class Lut:
+    """mx_video_lut: an immutable 3D lattice on the device, [N][N][N][3] uint16 in Q4 (0 .. 4096), N = 17 (lattice_log2 4) or 33 (5); indexed [iy][iu][iv][Y'U'V']"""
+
+    def __init__(self, lattice_log2: int, nodes):
+        self._h = C.c_void_p()
+        nodes = np.ascontiguousarray(nodes, dtype=np.uint16)
+        n = (1 << int(lattice_log2)) + 1 if 0 <= int(lattice_log2) < 16 else 0
+        if n and nodes.size != n * n * n * 3:
+            raise ValueError("nodes must hold N^3 x 3 values")
+        check(lib.mx_video_lut_create(int(lattice_log2), nodes.ctypes.data_as(C.c_void_p), C.byref(self._h)))
+        self.lattice_log2 = int(lattice_log2)
+
+    @property
+    def handle(self):
+        return self._h
+
+    def release(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            lib.mx_video_lut_release(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        self.release()
+
+
+def grade(src: DFrame, params, lut: Lut | None = None, stream=None) -> DFrame:
+    """mx_video_grade: curve, chroma matrix and 3D LUT of a yuv420p or yuva420p frame as a NEW frame of the same size and format (a coverage plane is copied)"""
+    h = C.c_void_p()
+    check(lib.mx_video_grade(src._h, C.byref(params), lut.handle if lut is not None else None, C.byref(h), stream))
+    return DFrame(handle=h.value, stream=stream)
+
+
+def graph_set_video_source_grade(g, node, params, lut: Lut | None = None):
+    """The SOURCE_VIDEO node delivers its frames graded, ahead of the key and the placement where they are set (mx_graph_set_video_source_grade); params None removes
+    the transform.  The graph retains the lattice: the caller may release `lut` at once."""
+    check(lib.mx_graph_set_video_source_grade(g._h, node, C.byref(params) if params is not None else None, lut.handle if lut is not None else None))
+
+
 def PlaceParams(canvas_w, canvas_h, dst_x, dst_y, dst_w, dst_h, crop=None) -> abi.VideoPlaceParams:
     """mx_video_place_params: the crop (x, y, w, h) of the input -- None: the whole frame -- stretched into the rectangle (dst_x, dst_y, dst_w, dst_h) of a transparent
     canvas_w x canvas_h canvas; every number even, the rectangle may reach beyond the canvas"""
