@@ -39,7 +39,8 @@ extern "C" {
                               *    mx_tempo_params, mx_graph_set_tempo, mx_graph_read_tempo, mx_tempo_record_bytes, mx_tempo_bpm;
                               *    mx_tonality_params, mx_graph_set_tonality, mx_graph_read_tonality, mx_tonality_record_bytes, mx_tonality_tables, mx_tonality_chroma,
                               *    mx_tonality_key;
-                              *    mx_multiview_view, mx_multiview_params, mx_multiview_status, mx_video_multiview, mx_graph_set_multiview, mx_graph_multiview_output */
+                              *    mx_multiview_view, mx_multiview_params, mx_multiview_status, mx_video_multiview, mx_graph_set_multiview, mx_graph_multiview_output;
+                              *    mx_video_matte_params, mx_video_matte, mx_video_matte_check, mx_video_matte_wipe, mx_graph_set_video_source_matte */
 
 /* ---- status codes (0 ok, <0 error; cf. MIXLAB_IOCTX_ERROR / MIXLAB_IOCTX_PANIC) ---- */
 enum {
@@ -916,6 +917,58 @@ int  mx_video_lut_identity(uint32_t lattice_log2, uint16_t* nodes /* [N][N][N][3
  * (0, 255, 1, 1, 0) gives the identity table and 4096 * I exactly. */
 int  mx_video_grade_procamp(double black, double white, double gamma, double saturation, double hue_degrees, mx_video_grade_params* out);
 int  mx_video_grade(const mx_dframe* in, const mx_video_grade_params* params, const mx_video_lut* lut /* NULL iff the LUT bit is clear */, mx_dframe** out, void* stream);
+/* The MATTE REFINER (BUILD-SPECIFIED; the reference has none): the knobs behind a keyer -- clean (clip), choke (shrink / grow), soften -- and
+ * a garbage mask, applied to the coverage plane of ONE frame in ONE launch on the device.  A rectangle or a circle written into layer B's coverage with the
+ * VideoMixer's fader at rest on 0 is a wipe or an iris: out = (A (255 - aB) + B aB) / 255 through the compositor as it stands.
+ * `in` is yuv420p or yuva420p, W x H (anything else: MX_ERR_INVALID); *out is a NEW yuva420p frame of the same size carrying one reference.  Y, U and V are copied
+ * byte for byte; the coverage plane is computed as below from A_in, the input's coverage, or 255 everywhere without one.  Stride padding is never read as picture,
+ * and the output's padding is what mx_dframe_create_fmt leaves.  Everything is an integer; `/` truncates, `>>` is of a non-negative value.
+ * Every field of a stage whose flag bit is clear must be 0 and anything out of the ranges stated with the fields is MX_ERR_INVALID; with no bit set the frame is
+ * copied, with an opaque plane where the input had none.  The stages run in this order, each per luma sample (x, y); a stage that is off passes its input on:
+ *   CLEAN:  a1 = 0 if A_in <= clean_black; else 255 if A_in >= clean_white; else ((A_in - clean_black) 255) / (clean_white - clean_black).  The tests are made in
+ *     this order, so black == white is a hard clip and (0, 255) is the identity.
+ *   CHOKE, r = |choke|:  a2(x, y) = the minimum (choke > 0, the matte shrinks) or the maximum (choke < 0, it grows) of a1(cl(x + i, W), cl(y + j, H)) over
+ *     |i|, |j| <= r, with cl(t, n) = min(max(t, 0), n - 1): a square window clamped to the plane.
+ *   SOFTEN, s = soften, b_s[k] = C(2s, k + s) for k = -s .. s (sum 4^s):
+ *     a3(x, y) = (sum_j sum_i b_s[j] b_s[i] a2(cl(x + i, W), cl(y + j, H)) + 2^(4s - 1)) >> 4s -- ONE rounding, at the end.  The largest sum is 255 2^24 < 2^32:
+ *     that is why 6 is the limit and why the two passes of a separable form need no rounding between them.
+ *   MASK, with px = 16 x + 8, py = 16 y + 8 (the sample's centre in Q4 luma pixels):
+ *     RECT:    d = min(px - x0, x1 - px, py - y0, y1 - py)
+ *     CIRCLE:  d = x1 - isqrt((px - x0)^2 + (py - y0)^2), isqrt the EXACT floor of the root (the argument stays below 2^43)
+ *     m = 0 if d <= 0; else 255 if d >= mask_feather_q4; else (d 255) / mask_feather_q4 -- in this order, so feather 0 is a hard edge; the feather lies inside
+ *     the shape.  If mask_invert, m = 255 - m.  The result is (a3 m) / 255.
+ * Coverage is decided per luma sample; the compositor's rule that a chroma sample takes the coverage of luma (2x, 2y) stands.  Asynchronous on `stream`, like its
+ * neighbours.  Out of scope: the refiner on mixer output ports and on band-scaled sources, other shapes (ellipse, diamond, line) and other structuring elements,
+ * radii above 6, temporal smoothing, and a wipe setting inside the VideoMixer. */
+#define MX_MATTE_CLEAN 1u
+#define MX_MATTE_CHOKE 2u
+#define MX_MATTE_SOFTEN 4u
+#define MX_MATTE_MASK 8u
+#define MX_MATTE_MASK_RECT 0u
+#define MX_MATTE_MASK_CIRCLE 1u
+typedef struct {
+    uint32_t flags;                      /* MX_MATTE_* bits, no other */
+    uint8_t  clean_black, clean_white;   /* CLEAN: black <= white */
+    int8_t   choke;                      /* CHOKE: -6 .. 6, not 0; > 0 shrinks, < 0 grows */
+    uint8_t  soften;                     /* SOFTEN: 1 .. 6 */
+    uint32_t mask_shape, mask_invert;    /* MASK: RECT | CIRCLE; 0 | 1 */
+    int32_t  mask_x0, mask_y0, mask_x1, mask_y1;   /* Q4 luma pixels, |.| <= 2^20.  RECT: the edges, x0 <= x1, y0 <= y1.  CIRCLE: centre (x0, y0), radius x1 >= 0, y1 = 0 */
+    uint32_t mask_feather_q4;            /* 0 .. 65535 */
+} mx_video_matte_params;                 /* 36 bytes */
+int mx_video_matte(const mx_dframe* in, const mx_video_matte_params* params, mx_dframe** out, void* stream);
+/* Host only: the parameter checks of mx_video_matte alone (MX_OK or MX_ERR_INVALID, mx_last_error saying which rule), made before any device work. */
+int mx_video_matte_check(const mx_video_matte_params* params);
+/* Host only: a MASK-only setting for a wipe of a w x h frame at position pos (0 .. 65536) with feather f = feather_q4 (0 .. 65535), in 64-bit integers, B = 2^20:
+ *   LEFT:  RECT (-B, -B, (pos (16 w + f)) >> 16, B);   TOP:  RECT (-B, -B, B, (pos (16 h + f)) >> 16);
+ *   BOX:   hx = (pos (8 w + f)) >> 16, hy = (pos (8 h + f)) >> 16, RECT (8 w - hx, 8 h - hy, 8 w + hx, 8 h + hy);
+ *   IRIS:  CIRCLE at (8 w, 8 h), radius (pos (isqrt((8 w)^2 + (8 h)^2) + 1 + f)) >> 16.
+ * pos = 0 covers nothing and pos = 65536 leaves every sample at 255.  MX_ERR_INVALID for another kind, pos or feather out of range, or a size that is not even,
+ * non-zero and at most 16384. */
+#define MX_WIPE_LEFT 0u
+#define MX_WIPE_TOP 1u
+#define MX_WIPE_BOX 2u
+#define MX_WIPE_IRIS 3u
+int mx_video_matte_wipe(uint32_t kind, uint32_t pos, uint32_t feather_q4, uint32_t w, uint32_t h, mx_video_matte_params* out);
 /* The PLACER (BUILD-SPECIFIED; the reference has none): a crop of a frame resampled into a rectangle of a transparent canvas, on the device --
  * picture-in-picture, side-by-side, a keyed presenter in a corner, a zoom.  `in` is yuv420p or yuva420p (anything else: MX_ERR_INVALID -- conversion is the scaler's
  * business); *out is a NEW yuva420p frame of canvas_w x canvas_h carrying one reference, its stride padding as mx_dframe_create_fmt leaves it.  The input's padding, and
@@ -1036,6 +1089,15 @@ int mx_graph_set_video_source_key(mx_graph* g, uint32_t node, const mx_video_key
  * order.  A source frame of another format, or a crop outside the frame that arrives, fails the run with MX_ERR_INVALID, mx_last_error naming the node, before anything of the
  * run is launched.  A scope tap on the source's port sees the placed frame.  mx_graph_adopt_state does not carry the setting. */
 int mx_graph_set_video_source_place(mx_graph* g, uint32_t node, const mx_video_place_params* params /* NULL removes */);
+/* The matte refiner as a per-source transform (mx_video_matte), under the keyer's rules: it applies to every frame the SOURCE_VIDEO node
+ * delivers, whichever feeder brought it; a frame is refined once per setting and the result reused (a ring of n frames costs n launches, not one per tick; the 32 most
+ * recent pairs are kept); output frames come from a pool and are rewritten only when the pool alone holds them.  Where several transforms are set on a node the order is
+ * GRADE, THEN KEY, THEN MATTE, THEN PLACE, whatever the call order: the matte refines what the key decided and the placer resamples the refined plane.  A scope tap on
+ * the source's port sees the matted frame.  Setting it again (a wipe moving every tick) drops what every stage had cached, from the next run on; params NULL removes
+ * the transform.  MX_ERR_TYPE for a node that is not a SOURCE_VIDEO; MX_ERR_INVALID for whatever mx_video_matte_check refuses, and together with
+ * mx_graph_set_video_source_band, in either call order (mx_last_error names the other setting); each leaves the graph usable.  A source frame that is not yuv420p /
+ * yuva420p fails the run with MX_ERR_INVALID before anything is launched, mx_last_error naming the node.  mx_graph_adopt_state does not carry the setting. */
+int mx_graph_set_video_source_matte(mx_graph* g, uint32_t node, const mx_video_matte_params* params /* NULL removes */);
 /* The colour corrector as a per-source transform (mx_video_grade), under the keyer's rules: it applies to every frame the SOURCE_VIDEO node
  * delivers, whichever feeder brought it; a frame is graded once per setting and the result reused (a ring of n frames costs n launches, not one per tick); output frames
  * come from a pool and are rewritten only when the pool alone holds them.  The graph retains `lut`, so the caller may release it at once.  Where several transforms are set

@@ -163,6 +163,8 @@ public:
     void set_video_source_place(uint32_t node, const mx_video_place_params* p) { check(mx_graph_set_video_source_place(g_, node, p)); }
     // the colour corrector as a transform of a SOURCE_VIDEO node (mx_graph_set_video_source_grade): graded first, then keyed, then placed; the graph retains lut; nullptr removes it
     void set_video_source_grade(uint32_t node, const mx_video_grade_params* p, mx_video_lut* lut = nullptr) { check(mx_graph_set_video_source_grade(g_, node, p, lut)); }
+    // the matte refiner as a transform of a SOURCE_VIDEO node (mx_graph_set_video_source_matte): after the key, ahead of the placement; nullptr removes it
+    void set_video_source_matte(uint32_t node, const mx_video_matte_params* p) { check(mx_graph_set_video_source_matte(g_, node, p)); }
     // the multiviewer as a tap on video output ports (mx_graph_set_multiview): ports[i] is shown in view i of p; an empty list removes it
     void set_multiview(const std::vector<mx_port_ref>& ports, const mx_multiview_params& p) {
         check(mx_graph_set_multiview(g_, ports.data(), ports.size(), ports.empty() ? nullptr : &p));

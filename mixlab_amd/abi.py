@@ -272,6 +272,24 @@ _proto("mx_video_grade", C.c_int, C.c_void_p, C.POINTER(VideoGradeParams), C.c_v
 _proto("mx_graph_set_video_source_grade", C.c_int, C.c_void_p, C.c_uint32, C.POINTER(VideoGradeParams), C.c_void_p)
 
 
+MATTE_CLEAN, MATTE_CHOKE, MATTE_SOFTEN, MATTE_MASK = 1, 2, 4, 8
+MATTE_MASK_RECT, MATTE_MASK_CIRCLE = 0, 1
+WIPE_LEFT, WIPE_TOP, WIPE_BOX, WIPE_IRIS = 0, 1, 2, 3
+
+
+class VideoMatteParams(C.Structure):
+    """mx_video_matte_params (36 bytes): the stages' flag bits, the clean points, the choke and soften radii, the mask's shape, Q4 geometry and feather."""
+    _fields_ = [("flags", C.c_uint32), ("clean_black", C.c_uint8), ("clean_white", C.c_uint8), ("choke", C.c_int8), ("soften", C.c_uint8),
+                ("mask_shape", C.c_uint32), ("mask_invert", C.c_uint32), ("mask_x0", C.c_int32), ("mask_y0", C.c_int32), ("mask_x1", C.c_int32),
+                ("mask_y1", C.c_int32), ("mask_feather_q4", C.c_uint32)]
+
+
+_proto("mx_video_matte", C.c_int, C.c_void_p, C.POINTER(VideoMatteParams), C.POINTER(C.c_void_p), C.c_void_p)
+_proto("mx_video_matte_check", C.c_int, C.POINTER(VideoMatteParams))
+_proto("mx_video_matte_wipe", C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(VideoMatteParams))
+_proto("mx_graph_set_video_source_matte", C.c_int, C.c_void_p, C.c_uint32, C.POINTER(VideoMatteParams))
+
+
 class VideoPlaceParams(C.Structure):
     """mx_video_place_params (40 bytes): the canvas, the crop of the input (0 x 0: the whole frame) and the rectangle of the canvas it is stretched into."""
     _fields_ = [("canvas_w", C.c_uint32), ("canvas_h", C.c_uint32), ("crop_x", C.c_uint32), ("crop_y", C.c_uint32), ("crop_w", C.c_uint32), ("crop_h", C.c_uint32),

@@ -393,6 +393,28 @@ int mx_video_grade(const mx_dframe* in, const mx_video_grade_params* params, con
     });
 }
 
+int mx_video_matte_check(const mx_video_matte_params* params) {
+    return guard([&] { REQUIRE(params, "params is NULL"); mx::check_matte_params(*params); });
+}
+int mx_video_matte_wipe(uint32_t kind, uint32_t pos, uint32_t feather_q4, uint32_t w, uint32_t h, mx_video_matte_params* out) {
+    return guard([&] { REQUIRE(out, "out is NULL"); mx::matte_wipe(kind, pos, feather_q4, w, h, *out); });
+}
+int mx_video_matte(const mx_dframe* in, const mx_video_matte_params* params, mx_dframe** out, void* stream) {
+    return guard([&] {
+        REQUIRE(out, "out is NULL");
+        *out = nullptr;
+        REQUIRE(in && params, "NULL argument");
+        mx::check_matte_params(*params);   // before any device work
+        DFrame* d = const_cast<DFrame*>(D(in));
+        REQUIRE(mx::key_input_ok(d), "the matte refiner takes yuv420p or yuva420p (scale a frame of another format first)");
+        hipStream_t s = S(stream);
+        FrameRef o(DFrame::create(d->width, d->height, s, MX_PIXFMT_YUV420P, true), false);
+        mx::matte_into(d, *params, o.f, s);
+        o->retain();
+        *out = H(o.f);
+    });
+}
+
 int mx_video_place(const mx_dframe* in, const mx_video_place_params* params, mx_dframe** out, void* stream) {
     return guard([&] {
         REQUIRE(out, "out is NULL");
@@ -552,6 +574,9 @@ int mx_graph_set_video_source_place(mx_graph* g, uint32_t node, const mx_video_p
 }
 int mx_graph_set_video_source_grade(mx_graph* g, uint32_t node, const mx_video_grade_params* params, mx_video_lut* lut) {
     return guard([&] { REQUIRE(g, "graph is NULL"); g->g->set_video_source_grade(node, params, (params && lut) ? lut->t : nullptr); });
+}
+int mx_graph_set_video_source_matte(mx_graph* g, uint32_t node, const mx_video_matte_params* params) {
+    return guard([&] { REQUIRE(g, "graph is NULL"); g->g->set_video_source_matte(node, params); });
 }
 int mx_graph_video_output(mx_graph* g, uint32_t node, uint32_t port, mx_dframe** out) {
     return guard([&] {

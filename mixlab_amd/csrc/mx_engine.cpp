@@ -1066,7 +1066,7 @@ void Graph::run(uint64_t t0, size_t fpc, uint32_t n_calls, float* ms_by_kind, fl
     auto drop_schedules = [&] { for (uint32_t id : sched_nodes_) { nodes_[id].sched.clear(); nodes_[id].gate_sched.clear(); } sched_nodes_.clear(); };
     if (frames > cap_frames_) { drop_schedules(); throw Error(MX_ERR_INVALID, "n_ticks exceeds max_ticks_per_run"); }
     if (n_calls == 0 || fpc == 0) { drop_schedules(); last_calls_ = n_calls; last_frames_per_call_ = fpc; for (AudioTapSet* s : taps_) s->empty_run(); scopes_.empty_run(); multiview_.empty_run(); return; }
-    // graded / keyed / placed video sources: a frame the transform cannot take fails the run HERE, before anything of it is launched or any node's state has moved
+    // graded / keyed / matted / placed video sources: a frame the transform cannot take fails the run HERE, before anything of it is launched or any node's state has moved
     for (uint32_t id : video_order_) {
         const VideoSourceState* vs = nodes_[id].vsrc.get();
         if (!vs || !vs->transform.active()) continue;

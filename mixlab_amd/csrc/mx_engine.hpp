@@ -188,6 +188,7 @@ public:
     void set_video_source_key(uint32_t node, const mx_video_key_params* params);   // nullptr removes
     void set_video_source_place(uint32_t node, const mx_video_place_params* params);   // nullptr removes
     void set_video_source_grade(uint32_t node, const mx_video_grade_params* params, std::shared_ptr<const LutTables> lut);   // nullptr removes
+    void set_video_source_matte(uint32_t node, const mx_video_matte_params* params);   // nullptr removes
     void queue_video_source(uint32_t node, uint64_t tick, DFrame* frame, Rational dur, Rational off);
     // what a feed checks BEFORE it takes frames out of a pacing state machine (a rejected feed must not lose media):
     void check_video_queue(uint32_t node, uint64_t first_tick) const;   // queue_video_source(node, first_tick, ...) would be accepted

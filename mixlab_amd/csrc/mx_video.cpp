@@ -841,6 +841,87 @@ void grade_into(DFrame* in, const mx_video_grade_params& p, const LutTables* lut
 }
 
 // ---------------------------------------------------------------------------------------------
+// the matte refiner (mixlab_gpu.h mx_video_matte; kernel in mx_k_matte.hip)
+// ---------------------------------------------------------------------------------------------
+void check_matte_params(const mx_video_matte_params& p) {
+    constexpr int32_t B = 1 << 20;
+    if (p.flags & ~(uint32_t)(MX_MATTE_CLEAN | MX_MATTE_CHOKE | MX_MATTE_SOFTEN | MX_MATTE_MASK)) throw Error(MX_ERR_INVALID, "mx_video_matte_params: flags holds a bit outside the four MX_MATTE_* stages");
+    if (p.flags & MX_MATTE_CLEAN) {
+        if (p.clean_black > p.clean_white) throw Error(MX_ERR_INVALID, "mx_video_matte_params: clean_black <= clean_white");
+    } else if (p.clean_black || p.clean_white) throw Error(MX_ERR_INVALID, "mx_video_matte_params: MX_MATTE_CLEAN is clear and a clean field is not 0");
+    if (p.flags & MX_MATTE_CHOKE) {
+        if (p.choke == 0 || p.choke < -6 || p.choke > 6) throw Error(MX_ERR_INVALID, "mx_video_matte_params: choke is -6 .. 6 and not 0");
+    } else if (p.choke) throw Error(MX_ERR_INVALID, "mx_video_matte_params: MX_MATTE_CHOKE is clear and choke is not 0");
+    if (p.flags & MX_MATTE_SOFTEN) {
+        if (p.soften < 1 || p.soften > 6) throw Error(MX_ERR_INVALID, "mx_video_matte_params: soften is 1 .. 6");
+    } else if (p.soften) throw Error(MX_ERR_INVALID, "mx_video_matte_params: MX_MATTE_SOFTEN is clear and soften is not 0");
+    if (p.flags & MX_MATTE_MASK) {
+        if (p.mask_shape != MX_MATTE_MASK_RECT && p.mask_shape != MX_MATTE_MASK_CIRCLE) throw Error(MX_ERR_INVALID, "mx_video_matte_params: mask_shape must be MX_MATTE_MASK_RECT or MX_MATTE_MASK_CIRCLE");
+        if (p.mask_invert > 1u) throw Error(MX_ERR_INVALID, "mx_video_matte_params: mask_invert must be 0 or 1");
+        for (int32_t c : {p.mask_x0, p.mask_y0, p.mask_x1, p.mask_y1}) if (c > B || c < -B) throw Error(MX_ERR_INVALID, "mx_video_matte_params: a mask coordinate lies outside +-2^20");
+        if (p.mask_feather_q4 > 65535u) throw Error(MX_ERR_INVALID, "mx_video_matte_params: mask_feather_q4 <= 65535");
+        if (p.mask_shape == MX_MATTE_MASK_RECT) {
+            if (p.mask_x0 > p.mask_x1 || p.mask_y0 > p.mask_y1) throw Error(MX_ERR_INVALID, "mx_video_matte_params: a rectangle has x0 <= x1 and y0 <= y1");
+        } else {
+            if (p.mask_x1 < 0) throw Error(MX_ERR_INVALID, "mx_video_matte_params: a circle's radius (mask_x1) is not negative");
+            if (p.mask_y1 != 0) throw Error(MX_ERR_INVALID, "mx_video_matte_params: a circle has mask_y1 0");
+        }
+    } else if (p.mask_shape || p.mask_invert || p.mask_x0 || p.mask_y0 || p.mask_x1 || p.mask_y1 || p.mask_feather_q4)
+        throw Error(MX_ERR_INVALID, "mx_video_matte_params: MX_MATTE_MASK is clear and a mask field is not 0");
+}
+
+static uint64_t isqrt_u64(uint64_t x) {   // exact floor of the root
+    uint64_t r = (uint64_t)std::sqrt((double)x);
+    while (r * r > x) --r;
+    while ((r + 1) * (r + 1) <= x) ++r;
+    return r;
+}
+
+void matte_wipe(uint32_t kind, uint32_t pos, uint32_t feather_q4, uint32_t w, uint32_t h, mx_video_matte_params& out) {
+    if (kind > MX_WIPE_IRIS) throw Error(MX_ERR_INVALID, "mx_video_matte_wipe: kind must be MX_WIPE_LEFT, _TOP, _BOX or _IRIS");
+    if (pos > 65536u) throw Error(MX_ERR_INVALID, "mx_video_matte_wipe: pos is 0 .. 65536");
+    if (feather_q4 > 65535u) throw Error(MX_ERR_INVALID, "mx_video_matte_wipe: feather_q4 <= 65535");
+    if (!w || !h || (w & 1u) || (h & 1u) || w > 16384u || h > 16384u) throw Error(MX_ERR_INVALID, "mx_video_matte_wipe: frame size must be even, non-zero and at most 16384");
+    const int64_t B = 1 << 20, f = feather_q4, W = w, H = h, P = pos;
+    mx_video_matte_params p{};
+    p.flags = MX_MATTE_MASK;
+    p.mask_feather_q4 = feather_q4;
+    p.mask_shape = kind == MX_WIPE_IRIS ? MX_MATTE_MASK_CIRCLE : MX_MATTE_MASK_RECT;
+    if (kind == MX_WIPE_LEFT) { p.mask_x0 = (int32_t)-B; p.mask_y0 = (int32_t)-B; p.mask_x1 = (int32_t)((P * (16 * W + f)) >> 16); p.mask_y1 = (int32_t)B; }
+    else if (kind == MX_WIPE_TOP) { p.mask_x0 = (int32_t)-B; p.mask_y0 = (int32_t)-B; p.mask_x1 = (int32_t)B; p.mask_y1 = (int32_t)((P * (16 * H + f)) >> 16); }
+    else if (kind == MX_WIPE_BOX) {
+        const int64_t hx = (P * (8 * W + f)) >> 16, hy = (P * (8 * H + f)) >> 16;
+        p.mask_x0 = (int32_t)(8 * W - hx); p.mask_y0 = (int32_t)(8 * H - hy); p.mask_x1 = (int32_t)(8 * W + hx); p.mask_y1 = (int32_t)(8 * H + hy);
+    } else {
+        p.mask_x0 = (int32_t)(8 * W); p.mask_y0 = (int32_t)(8 * H);
+        p.mask_x1 = (int32_t)((P * ((int64_t)isqrt_u64((uint64_t)(8 * W * 8 * W + 8 * H * 8 * H)) + 1 + f)) >> 16);
+    }
+    check_matte_params(p);   // every formula stays inside +-2^20 for frames up to 16384
+    out = p;
+}
+
+void matte_into(DFrame* in, const mx_video_matte_params& p, DFrame* out, hipStream_t s) {
+    if (!key_input_ok(in)) throw Error(MX_ERR_INVALID, "the matte refiner takes yuv420p or yuva420p (scale a frame of another format first)");
+    if (out->fmt != MX_PIXFMT_YUV420P || !out->alpha || out->width != in->width || out->height != in->height) throw Error(MX_ERR_INTERNAL, "matte: the output frame is not yuva420p of the input's size");
+    check_matte_params(p);
+    in->ensure_pixels(s);
+    flush_scales(s);   // the input may be a scaler's output whose job is still queued
+    MatteArgs a{};
+    a.y = in->data[0]; a.u = in->data[1]; a.v = in->data[2]; a.a_in = in->alpha;
+    a.y_stride = in->stride[0]; a.u_stride = in->stride[1]; a.v_stride = in->stride[2]; a.a_stride = in->alpha ? in->alpha_stride : 0u;
+    a.oy = out->data[0]; a.ou = out->data[1]; a.ov = out->data[2]; a.oa = out->alpha;
+    a.oy_stride = out->stride[0]; a.ou_stride = out->stride[1]; a.ov_stride = out->stride[2]; a.oa_stride = out->alpha_stride;
+    a.width = in->width; a.height = in->height;
+    a.flags = p.flags;
+    a.clean_black = p.clean_black; a.clean_white = p.clean_white;
+    a.choke_r = (uint32_t)(p.choke < 0 ? -p.choke : p.choke); a.choke_grow = p.choke < 0 ? 1u : 0u; a.soften = p.soften;
+    a.mask_shape = p.mask_shape; a.mask_invert = p.mask_invert; a.mask_feather = p.mask_feather_q4;
+    a.mask_x0 = p.mask_x0; a.mask_y0 = p.mask_y0; a.mask_x1 = p.mask_x1; a.mask_y1 = p.mask_y1;
+    launch_video_matte(a, s);
+    hip_check(hipGetLastError(), "matte launch");
+}
+
+// ---------------------------------------------------------------------------------------------
 // the placer (mixlab_gpu.h mx_video_place; kernel in mx_k_place.hip)
 // ---------------------------------------------------------------------------------------------
 void check_place_params(const mx_video_place_params& p) {

@@ -207,6 +207,28 @@ void grade_procamp(double black, double white, double gamma, double saturation, 
 // `in` graded under p into `out` (in's size and format, created by DFrame::create: the kernel leaves its padding as it is), asynchronous on s
 void grade_into(DFrame* in, const mx_video_grade_params& p, const LutTables* lut, DFrame* out, hipStream_t s);
 
+// ---- the matte refiner (mixlab_gpu.h mx_video_matte; mx_k_matte.hip) ----
+struct MatteArgs {
+    const uint8_t* y; const uint8_t* u; const uint8_t* v; const uint8_t* a_in;   // a_in nullptr: the input carries no coverage (255 everywhere)
+    uint8_t* oy; uint8_t* ou; uint8_t* ov; uint8_t* oa;
+    uint32_t y_stride, u_stride, v_stride, a_stride, oy_stride, ou_stride, ov_stride, oa_stride;
+    uint32_t width, height;                        // luma size, both even
+    uint32_t flags;                                // MX_MATTE_* bits
+    uint32_t clean_black, clean_white;
+    uint32_t choke_r, choke_grow, soften;          // |choke| (0: off), choke < 0, soften (0: off)
+    uint32_t mask_shape, mask_invert, mask_feather;
+    int32_t mask_x0, mask_y0, mask_x1, mask_y1;
+    // launcher-filled
+    uint32_t cw8, lw16, chunks_x, n_threads, tiles_x, n_tiles;
+    uint32_t binom[13];                            // C(2 soften, k)
+    uint64_t m_clean, m_feather;                   // ceil(2^40 / (white - black)), ceil(2^40 / feather): the ramps' divisions as a multiply (0 where the span is empty)
+};
+void launch_video_matte(MatteArgs a, hipStream_t s);
+void check_matte_params(const mx_video_matte_params& p);   // MX_ERR_INVALID outside what the header states; touches no device
+void matte_wipe(uint32_t kind, uint32_t pos, uint32_t feather_q4, uint32_t w, uint32_t h, mx_video_matte_params& out);   // host only
+// `in` refined under p into `out` (yuva420p of in's size, created by DFrame::create: the kernel leaves its padding as it is), asynchronous on s
+void matte_into(DFrame* in, const mx_video_matte_params& p, DFrame* out, hipStream_t s);
+
 // ---- the placer (mixlab_gpu.h mx_video_place; mx_k_place.hip) ----
 // A workgroup writes one MX_PLACE_TILE_W x MX_PLACE_TILE_H byte tile of one canvas plane; the LDS-tiled form takes axes of up to MX_PLACE_TAP_BOUND taps.
 enum { MX_PLACE_TILE_W = 64, MX_PLACE_TILE_H = 16, MX_PLACE_TAP_BOUND = 18 };

@@ -19,7 +19,7 @@ void SourceTransform::set_grade(const mx_video_grade_params* p, std::shared_ptr<
     // frames graded under the old setting are of no use, and neither is what was keyed or placed from them; the output frames stay in the pool (they match on size
     // and coverage, not on the setting) and are rewritten once their last holder has let go.  The old lattice lives until the launches that read it are behind the
     // new setting's on the stream: hipFree waits for the device
-    graded_.clear(); keyed_.clear(); placed_.clear();
+    clear_done();
     grade_on_ = p != nullptr;
     if (p) { grade_ = *p; grade_lut_ = std::move(lut); } else { grade_lut_.reset(); grade_pool_.clear(); }
 }
@@ -27,10 +27,18 @@ void SourceTransform::set_grade(const mx_video_grade_params* p, std::shared_ptr<
 void SourceTransform::set_key(const mx_video_key_params* p) {
     // frames keyed under the old setting are of no use; their output frames stay in the pool and are rewritten once their last holder has let go
     keyed_.clear();
-    placed_.clear();   // a placed frame holds the picture as it was keyed
+    matted_.clear(); placed_.clear();   // a matted or placed frame holds the picture as it was keyed
     graded_.clear();   // listed only while the grade is the last stage: entries from before must not pin their pool frames
     key_on_ = p != nullptr;
     if (p) key_ = *p; else key_pool_.clear();
+}
+
+void SourceTransform::set_matte(const mx_video_matte_params* p) {
+    // as for the key: frames refined under the old setting are of no use, nor what was placed from them; the lists of the stages ahead are in use only while theirs
+    // is the last stage, and entries from before must not pin their pool frames.  The output frames stay in the pool and are rewritten once their last holder has let go
+    clear_done();
+    matte_on_ = p != nullptr;
+    if (p) matte_ = *p; else matte_pool_.clear();
 }
 
 void SourceTransform::set_place(const mx_video_place_params* p) {
@@ -39,21 +47,22 @@ void SourceTransform::set_place(const mx_video_place_params* p) {
     place_on_ = p != nullptr;
     if (p) place_ = *p;
     keyed_.clear();   // the keyed frames a placed source needs are the placer's alone and never listed; those listed before must not pin their pool frames
-    graded_.clear();  // likewise
+    graded_.clear(); matted_.clear();  // likewise
 }
 
 const char* SourceTransform::input_error(const DFrame* f) const {
     if (grade_on_ && !key_input_ok(f)) return "the colour corrector takes yuv420p or yuva420p frames (mx_graph_set_video_source_grade)";
     if (key_on_ && !key_input_ok(f)) return "the keyer takes yuv420p or yuva420p frames (mx_graph_set_video_source_key)";
-    return place_on_ ? place_input_error(f, place_) : nullptr;   // the grade and the key keep the frame's size, so the crop is checked against the frame as it arrives
+    if (matte_on_ && !key_input_ok(f)) return "the matte refiner takes yuv420p or yuva420p frames (mx_graph_set_video_source_matte)";
+    return place_on_ ? place_input_error(f, place_) : nullptr;   // the grade, the key and the matte keep the frame's size, so the crop is checked against the frame as it arrives
 }
 
-// `src` graded (where a grade is set), then keyed (where a key is), then placed (where a placement is): once per setting, reused while anything but the list holds
+// `src` graded (where a grade is set), then keyed (where a key is), then matted (where a matte is), then placed (where a placement is): once per setting, reused while anything but the list holds
 // the source frame.
 FrameRef SourceTransform::apply(const FrameRef& src, hipStream_t s) {
     // Graph::run looked at every frame the run can deliver before it launched anything
     if (input_error(src.f)) throw Error(MX_ERR_INTERNAL, "a video source's transform met a frame the run's check of its frames did not see");
-    DoneCache& done = place_on_ ? placed_ : (key_on_ ? keyed_ : graded_);
+    DoneCache& done = place_on_ ? placed_ : (matte_on_ ? matted_ : (key_on_ ? keyed_ : graded_));
     if (FrameRef o = done.find(src.f)) return o;
     done.make_room();
     FrameRef o = src;
@@ -70,6 +79,13 @@ FrameRef SourceTransform::apply(const FrameRef& src, hipStream_t s) {
         o = key_pool_.take([&](const DFrame& f) { return f.width == w && f.height == h; },
                            [&] { return DFrame::create(w, h, s, MX_PIXFMT_YUV420P, true); });   // the keyer leaves the padding as DFrame::create made it
         key_into(in.f, key_, o.f, s);
+    }
+    if (matte_on_) {   // refines what the key decided (or the coverage the frame came with); the placer resamples the refined plane
+        const FrameRef in = o;
+        const uint32_t w = src->width, h = src->height;
+        o = matte_pool_.take([&](const DFrame& f) { return f.width == w && f.height == h; },
+                             [&] { return DFrame::create(w, h, s, MX_PIXFMT_YUV420P, true); });   // the refiner leaves the padding as DFrame::create made it
+        matte_into(in.f, matte_, o.f, s);
     }
     if (place_on_) {
         const FrameRef in = o;
@@ -113,7 +129,7 @@ void VideoSourceState::adopt(const VideoSourceState& old) {
     sched = old.sched;
     band = old.band; band_pool = old.band_pool;
     frame = old.frame; dur = old.dur; off = old.off; repeat = old.repeat; pending = old.pending;
-    // `transform` is NOT carried: mixlab_gpu.h says of mx_graph_set_video_source_grade, of _key and of _place "mx_graph_adopt_state does not carry the setting"
+    // `transform` is NOT carried: mixlab_gpu.h says of mx_graph_set_video_source_grade, of _key, of _matte and of _place "mx_graph_adopt_state does not carry the setting"
 }
 
 // ---- VIDEO_TO_RGBA ----
@@ -431,6 +447,7 @@ void Graph::set_video_source_band(uint32_t node, uint32_t in_w, uint32_t in_full
     VideoSourceState& v = *node_of_kind(node, MX_KIND_SOURCE_VIDEO, "SOURCE_VIDEO").vsrc;
     if (band_rows && v.transform.grade_on()) throw Error(MX_ERR_INVALID, "video source band: the source is graded (mx_graph_set_video_source_grade); grading a band-scaled layer is not supported");
     if (band_rows && v.transform.key_on()) throw Error(MX_ERR_INVALID, "video source band: the source is keyed (mx_graph_set_video_source_key), and a band-scaled layer cannot carry coverage");
+    if (band_rows && v.transform.matte_on()) throw Error(MX_ERR_INVALID, "video source band: the source is matted (mx_graph_set_video_source_matte), and a band-scaled layer cannot carry coverage");
     if (band_rows && v.transform.place_on()) throw Error(MX_ERR_INVALID, "video source band: the source is placed (mx_graph_set_video_source_place), and a band-scaled layer cannot carry coverage");
     sync();                                     // a previous band scaler's row buffer may be in use
     v.band.reset(); v.band_pool.clear();
@@ -457,6 +474,17 @@ void Graph::set_video_source_grade(uint32_t node, const mx_video_grade_params* p
         if (v.band) throw Error(MX_ERR_INVALID, "video source grade: the source delivers a row band of a scaled layer (mx_graph_set_video_source_band); grading a band-scaled layer is not supported");
     }
     v.transform.set_grade(params, std::move(lut));
+}
+
+void Graph::set_video_source_matte(uint32_t node, const mx_video_matte_params* params) {
+    if (node >= nodes_.size()) throw Error(MX_ERR_INVALID, "node out of range");
+    if (nodes_[node].kind != MX_KIND_SOURCE_VIDEO) throw Error(MX_ERR_TYPE, "video source matte: node is not a SOURCE_VIDEO");
+    VideoSourceState& v = *nodes_[node].vsrc;
+    if (params) {
+        check_matte_params(*params);
+        if (v.band) throw Error(MX_ERR_INVALID, "video source matte: the source delivers a row band of a scaled layer (mx_graph_set_video_source_band), which cannot carry coverage");
+    }
+    v.transform.set_matte(params);
 }
 
 void Graph::set_video_source_place(uint32_t node, const mx_video_place_params* params) {

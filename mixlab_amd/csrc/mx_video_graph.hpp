@@ -1,5 +1,5 @@
-// mx_video_graph.hpp -- what the engine keeps per video node and per video tap, out of Graph and Node: the state of a SOURCE_VIDEO (with the keyer and the
-// placer as its SourceTransform), of a VIDEO_TO_RGBA sink and of a MONITOR, and the two taps on video ports -- the scope taps and the multiviewer.  Graph
+// mx_video_graph.hpp -- what the engine keeps per video node and per video tap, out of Graph and Node: the state of a SOURCE_VIDEO (with the colour corrector, the keyer,
+// the matte refiner and the placer as its SourceTransform), of a VIDEO_TO_RGBA sink and of a MONITOR, and the two taps on video ports -- the scope taps and the multiviewer.  Graph
 // (mx_engine.hpp) walks the video nodes tick by tick and calls in here; the taps see it through TapHost (mx_taps.hpp), like the audio tap sets.
 #pragma once
 #include <deque>
@@ -24,22 +24,24 @@ struct HopCounter {
     bool tick() { return c++ % hop == 0; }   // record this tick?  Then advance
 };
 
-// The colour corrector, the keyer and the placer as a transform of a SOURCE_VIDEO's frames (mx_graph_set_video_source_grade / _key / _place): grade, then key, then
-// place, where several are set.  A frame is transformed once per setting.
+// The colour corrector, the keyer, the matte refiner and the placer as a transform of a SOURCE_VIDEO's frames (mx_graph_set_video_source_grade / _key / _matte /
+// _place): grade, then key, then matte, then place, where several are set.  A frame is transformed once per setting.
 class SourceTransform {
 public:
     void set_grade(const mx_video_grade_params* p, std::shared_ptr<const LutTables> lut);   // nullptr removes; the parameters were checked
     void set_key(const mx_video_key_params* p);       // nullptr removes; the parameters were checked
+    void set_matte(const mx_video_matte_params* p);   // likewise
     void set_place(const mx_video_place_params* p);   // likewise
     bool grade_on() const { return grade_on_; }
     bool key_on() const { return key_on_; }
+    bool matte_on() const { return matte_on_; }
     bool place_on() const { return place_on_; }
-    bool active() const { return grade_on_ || key_on_ || place_on_; }
+    bool active() const { return grade_on_ || key_on_ || matte_on_ || place_on_; }
     const char* input_error(const DFrame* f) const;   // nullptr, or why the transform cannot take this frame
     FrameRef apply(const FrameRef& src, hipStream_t s);
 private:
     // Frames transformed under the current setting, newest last: an entry holds the source frame (so its address stays its identity) and lives while anything
-    // else does.  With several stages set, src is the frame the FEEDER delivered and out the LAST stage's frame: a graded or keyed frame between two passes is a
+    // else does.  With several stages set, src is the frame the FEEDER delivered and out the LAST stage's frame: a graded, keyed or matted frame between two passes is a
     // pool frame nobody else sees, read by the pass launched right behind it on the stream, and is listed nowhere.
     struct DoneCache {
         struct Entry { FrameRef src, out; };
@@ -48,15 +50,17 @@ private:
         void make_room();   // entries whose source frame only this list still holds can never be asked for again; the oldest goes too when the list is full (32)
         void clear() { list.clear(); }
     };
-    bool grade_on_ = false, key_on_ = false, place_on_ = false;
+    bool grade_on_ = false, key_on_ = false, matte_on_ = false, place_on_ = false;
     mx_video_grade_params grade_{};
     std::shared_ptr<const LutTables> grade_lut_;      // retained for as long as the setting stands: the caller may release its handle at once
     mx_video_key_params key_{};
+    mx_video_matte_params matte_{};
     mx_video_place_params place_{};
     std::shared_ptr<const PlaceTables> place_tabs_;   // of the current setting (and, for a whole-frame crop, of the size of the frame seen last)
-    DoneCache graded_, keyed_, placed_;   // the list of the LAST stage set is the one in use: placed_, else keyed_, else graded_
+    DoneCache graded_, keyed_, matted_, placed_;   // the list of the LAST stage set is the one in use: placed_, else matted_, else keyed_, else graded_
+    void clear_done() { graded_.clear(); keyed_.clear(); matted_.clear(); placed_.clear(); }
     // output frames.  64 is twice the list above: a frame that leaves the list is still in the pool, so a long ring recycles frames instead of allocating
-    FramePool grade_pool_{64}, key_pool_{64}, place_pool_{64};
+    FramePool grade_pool_{64}, key_pool_{64}, matte_pool_{64}, place_pool_{64};
 };
 
 struct VideoSourceState {   // SOURCE_VIDEO
@@ -69,7 +73,7 @@ struct VideoSourceState {   // SOURCE_VIDEO
     std::shared_ptr<BandScaler> band; FramePool band_pool{8};
     SourceTransform transform;
 
-    VOut due(uint64_t tick, hipStream_t s);   // the frame due on `tick`: queue, then ring, then set frame; banded, then placed or keyed
+    VOut due(uint64_t tick, hipStream_t s);   // the frame due on `tick`: queue, then ring, then set frame; banded, then transformed
     // every frame a run over ticks [tick0, last] may deliver, before any of it has run
     template <class Look> void each_deliverable(uint64_t tick0, uint64_t last, Look look) const {
         for (const Sched& e : sched) if (e.tick >= tick0 && e.tick <= last) look(e.frame.f);

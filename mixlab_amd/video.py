@@ -419,6 +419,56 @@ def graph_set_video_source_grade(g, node, params, lut: Lut | None = None):
     check(lib.mx_graph_set_video_source_grade(g._h, node, C.byref(params) if params is not None else None, lut.handle if lut is not None else None))
 
 
+MATTE_CLEAN, MATTE_CHOKE, MATTE_SOFTEN, MATTE_MASK = abi.MATTE_CLEAN, abi.MATTE_CHOKE, abi.MATTE_SOFTEN, abi.MATTE_MASK
+MATTE_MASK_RECT, MATTE_MASK_CIRCLE = abi.MATTE_MASK_RECT, abi.MATTE_MASK_CIRCLE
+WIPE_LEFT, WIPE_TOP, WIPE_BOX, WIPE_IRIS = abi.WIPE_LEFT, abi.WIPE_TOP, abi.WIPE_BOX, abi.WIPE_IRIS
+
+
+def MatteParams(clean=None, choke=0, soften=0, mask=None, invert=False, feather_q4=0, shape=MATTE_MASK_RECT) -> abi.VideoMatteParams:
+    """mx_video_matte_params: clean (black, white) or None; choke -6 .. 6 (0: off; > 0 shrinks); soften 0 .. 6 (0: off); mask (x0, y0, x1, y1) in Q4 luma pixels or
+    None -- a rectangle's edges, or with shape MATTE_MASK_CIRCLE the centre, the radius and 0.  The flag bits follow from what is given."""
+    p = abi.VideoMatteParams()
+    if clean is not None:
+        p.flags |= MATTE_CLEAN
+        p.clean_black, p.clean_white = (int(x) for x in clean)
+    if choke:
+        p.flags |= MATTE_CHOKE
+        p.choke = int(choke)
+    if soften:
+        p.flags |= MATTE_SOFTEN
+        p.soften = int(soften)
+    if mask is not None:
+        p.flags |= MATTE_MASK
+        p.mask_shape, p.mask_invert, p.mask_feather_q4 = int(shape), int(bool(invert)), int(feather_q4)
+        p.mask_x0, p.mask_y0, p.mask_x1, p.mask_y1 = (int(x) for x in mask)
+    return p
+
+
+def matte_check(params) -> None:
+    """mx_video_matte_check (host): raises MxError(MX_ERR_INVALID) for a setting mx_video_matte would refuse"""
+    check(lib.mx_video_matte_check(C.byref(params)))
+
+
+def matte_wipe(kind: int, pos: int, feather_q4: int, w: int, h: int) -> abi.VideoMatteParams:
+    """mx_video_matte_wipe (host): the MASK-only setting of a WIPE_LEFT / _TOP / _BOX / _IRIS at pos 0 .. 65536 over a w x h frame"""
+    p = abi.VideoMatteParams()
+    check(lib.mx_video_matte_wipe(int(kind), int(pos), int(feather_q4), int(w), int(h), C.byref(p)))
+    return p
+
+
+def matte(src: DFrame, params, stream=None) -> DFrame:
+    """mx_video_matte: clean, choke, soften and garbage mask of the coverage of a yuv420p or yuva420p frame as a NEW yuva420p frame (Y, U, V copied)"""
+    h = C.c_void_p()
+    check(lib.mx_video_matte(src._h, C.byref(params), C.byref(h), stream))
+    return DFrame(handle=h.value, stream=stream)
+
+
+def graph_set_video_source_matte(g, node, params):
+    """The SOURCE_VIDEO node delivers its frames matted, after the grade and the key and ahead of the placement where they are set
+    (mx_graph_set_video_source_matte); None removes the transform."""
+    check(lib.mx_graph_set_video_source_matte(g._h, node, C.byref(params) if params is not None else None))
+
+
 def PlaceParams(canvas_w, canvas_h, dst_x, dst_y, dst_w, dst_h, crop=None) -> abi.VideoPlaceParams:
     """mx_video_place_params: the crop (x, y, w, h) of the input -- None: the whole frame -- stretched into the rectangle (dst_x, dst_y, dst_w, dst_h) of a transparent
     canvas_w x canvas_h canvas; every number even, the rectangle may reach beyond the canvas"""
