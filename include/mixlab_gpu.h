@@ -40,7 +40,10 @@ extern "C" {
                               *    mx_tonality_params, mx_graph_set_tonality, mx_graph_read_tonality, mx_tonality_record_bytes, mx_tonality_tables, mx_tonality_chroma,
                               *    mx_tonality_key;
                               *    mx_multiview_view, mx_multiview_params, mx_multiview_status, mx_video_multiview, mx_graph_set_multiview, mx_graph_multiview_output;
-                              *    mx_video_matte_params, mx_video_matte, mx_video_matte_check, mx_video_matte_wipe, mx_graph_set_video_source_matte */
+                              *    mx_video_matte_params, mx_video_matte, mx_video_matte_check, mx_video_matte_wipe, mx_graph_set_video_source_matte;
+                              *    mx_deck, mx_deck_params, mx_deck_head, mx_deck_tick, mx_deck_create, mx_deck_destroy, mx_deck_load_i16, mx_deck_set, mx_deck_seek,
+                              *    mx_deck_schedule, mx_deck_check, mx_deck_plan, mx_deck_feed, mx_deck_read_ticks, mx_deck_state, mx_deck_step, mx_deck_tables,
+                              *    mx_deck_debug_last_feed */
 
 /* ---- status codes (0 ok, <0 error; cf. MIXLAB_IOCTX_ERROR / MIXLAB_IOCTX_PANIC) ---- */
 enum {
@@ -747,6 +750,107 @@ void mx_pcm_ring_destroy(mx_pcm_ring* r);
 int mx_pcm_ring_push_i16(mx_pcm_ring* r, const int16_t* samples, size_t n_samples);
 int mx_pcm_ring_queued(const mx_pcm_ring* r, size_t* n_samples);
 int mx_pcm_ring_feed(mx_pcm_ring* r, mx_graph* g, uint32_t node, uint32_t n_ticks, size_t* zero_filled);
+
+/* ---- the deck: a track in device memory played at variable speed into a SOURCE_STEREO node ----
+ * BUILD-SPECIFIED (no reference module): the pitch fader, cue jump, loop roll, brake and back-spin a host would otherwise resample on the CPU and push over PCIe
+ * every tick.  A deck is a feeder of a MX_KIND_SOURCE_STEREO node, in the family of mx_pcm_ring_feed: an object of its own that owns a device-resident track and,
+ * before a run, writes that run's ticks into the node's port buffer with ONE kernel launch for all decks and ticks of the call.  The graph itself is unchanged.
+ *
+ * TRACK     stereo i16 interleaved (4 bytes per frame), n_frames frames, 1 <= n_frames <= 2^30, zeroed at creation.  Frames outside [0, n_frames) read as +0.  A sample
+ *           is (float)s / 32768.0f (stream_input.rs:167-173; exact).
+ * POSITION  pos: int64 in Q32.32 track frames.  step: the advance per output frame, 2^32 = unity, negative = backwards, |step| <= 4 * 2^32.  A tick of spt output
+ *           frames has (pos, step, dstep); frame n of it reads the track at
+ *               u(n) = pos + n * step + dstep * (n * (n - 1) / 2)
+ *           and after the tick pos = u(spt), step += spt * dstep.  64-bit integer arithmetic throughout: exact, and independent of how ticks are grouped into feeds.
+ * PARAMS    mx_deck_params: step_q32 the TARGET step; slew_q32 the largest change of step per output frame, 0 .. 2^24 (0: the step jumps); loop_in < loop_out in
+ *           frames; flags MX_DECK_PLAY | MX_DECK_LOOP.  With MX_DECK_LOOP: 0 <= loop_in < loop_out <= n_frames; without it the loop points are not looked at.
+ * A TICK    begins with these steps, in this order:
+ *             1. a pending seek sets pos;  2. pending parameters replace the current ones;
+ *             3. pos is clamped to [-2^20, n_frames + 2^20] frames (a deck left running past its end cannot overflow);
+ *             4. the tick is LOOPING when MX_DECK_LOOP is set and either the previous tick was looping under the same (loop_in, loop_out), or
+ *                loop_in * 2^32 <= pos < loop_out * 2^32;
+ *             5. without MX_DECK_PLAY the tick is written as zeros, pos and step stand still, and its record has dstep = 0, bank = 0.  Otherwise the slew is resolved:
+ *                slew = 0: step = target, dstep = 0.  Else dstep = clamp((target - step) / spt, -slew, +slew) with C's truncating division, and if that is 0,
+ *                step = target.  (A brake, a spin-up, a pitch bend without a click.)
+ *           In a looping tick every u(n), and pos after the tick, is folded: u' = in_q + floormod(u - in_q, len_q), in_q = loop_in * 2^32, len_q = (loop_out - loop_in) * 2^32
+ *           (floormod: the remainder with the sign of len_q, i.e. in [0, len_q)); in both directions and for any number of wraps per tick.  In any other tick u' = u.
+ *           It follows that a loop set with the head inside it always catches (how loop buttons work), that a loop shorter than one tick's travel may be passed over when
+ *           it is entered from outside, and that a seek while the loop stays set lands folded into the loop (clear MX_DECK_LOOP in the same event to leave it).
+ *           The taps around a folded position read the track's LINEAR neighbours; they are not folded.
+ * FILTER    windowed-sinc polyphase, L = 32 taps, P = 256 phases, blended linearly between neighbouring phase rows; four banks b with cutoff fc_b = 1, 3/4, 1/2, 1/4
+ *           of the output Nyquist.  With idx = u' >> 32 (arithmetic), p = (u' >> 24) & 255, w = (double)(u' & 0xFFFFFF) * 2^-24, per channel, acc = 0.0, for k = 0 .. 31
+ *           ascending:
+ *               c_k = (double)T[b][p][k] + w * ((double)T[b][p + 1][k] - (double)T[b][p][k]);      acc = acc + c_k * (double)x[idx - 15 + k];
+ *           every multiply and add a separate f64 operation (never fused), acc rounded once to f32.  MX_FLAG_FP_CONTRACT does not apply: a deck is no graph member.
+ *           The bank is chosen per tick from m = max(|step|, |step + (spt - 1) * dstep|) (step as resolved in 5.) by integer comparison:
+ *               m <= 2^32: 0;   else 3 m <= 4 * 2^32: 1;   else m <= 2 * 2^32: 2;   else 3.
+ * TABLES    T[b]: P + 1 = 257 rows of L = 32 f32.  T[b][p][k] = g(fc_b, (k - 15) - p / 256) / (the sum of g over the row's 32 k), rounded to the nearest f32, where
+ *               g(fc, x) = fc * sinc(fc * x) * I0(9 * sqrt(1 - (x / 16)^2)) / I0(9),   sinc(t) = sin(pi t) / (pi t), sinc(0) = 1,   I0 the modified Bessel function
+ *           (|x| <= 16 for every entry).  DC passes at gain 1.  In bank 0, rows 0 and 256 are exact unit impulses at k = 15 and k = 16, so AT step = 2^32 FROM AN
+ *           INTEGER POSITION THE OUTPUT IS THE TRACK, BIT FOR BIT.
+ * RECORDS   mx_deck_tick, one per tick of the last feed: pos / step as the tick began (after 1. - 5.), dstep, loop_in and loop_len in frames (0, 0 unless looping),
+ *           bank, and flags: MX_DECK_TICK_PLAY, MX_DECK_TICK_LOOPING, and for a playing tick that is not looping, with m as above,
+ *               MX_DECK_TICK_BEFORE  when pos + (spt - 1) * m <  -16 * 2^32             (no tap of the tick reaches frame 0: the tick is zeros),
+ *               MX_DECK_TICK_PAST    when pos - (spt - 1) * m >= (n_frames + 15) * 2^32 (no tap reaches below n_frames: zeros).
+ * Out of scope: key-lock (a change of tempo without a change of pitch), more than two channels, tracks above 2^30 frames, a deck as a member of the graph.
+ */
+#define MX_DECK_PLAY 1u
+#define MX_DECK_LOOP 2u
+#define MX_DECK_TICK_PLAY 1u
+#define MX_DECK_TICK_LOOPING 2u
+#define MX_DECK_TICK_BEFORE 4u
+#define MX_DECK_TICK_PAST 8u
+#define MX_DECK_TAPS 32
+#define MX_DECK_PHASES 256
+#define MX_DECK_BANKS 4
+#define MX_DECK_CHUNK 256        /* output frames one workgroup of the feed kernel writes (a lane per frame); tests size their tick lengths around it */
+#define MX_DECK_MAX_SPT 1048576  /* frames per tick mx_deck_plan / mx_deck_feed accept */
+typedef struct mx_deck mx_deck;
+typedef struct { int64_t step_q32; int64_t slew_q32; int64_t loop_in; int64_t loop_out; uint32_t flags; uint32_t _pad; } mx_deck_params;
+/* where the head stands between ticks: pos, the CURRENT step, the current parameters, and whether the last tick was looping, under which points */
+typedef struct { int64_t pos_q32; int64_t step_q32; mx_deck_params params; int64_t last_loop_in; int64_t last_loop_out; uint32_t last_looping; uint32_t _pad; } mx_deck_head;
+typedef struct { int64_t pos_q32; int64_t step_q32; int64_t dstep_q32; int64_t loop_in; int64_t loop_len; uint32_t flags; uint32_t bank; } mx_deck_tick;
+
+/* A zeroed track of n_frames on `device` (-1: the current one).  The head starts at pos 0, step 0, params all 0 (not playing).  n_frames outside 1 .. 2^30: MX_ERR_INVALID. */
+int mx_deck_create(uint64_t n_frames, int device, mx_deck** out);
+void mx_deck_destroy(mx_deck* d);
+/* Fill frames [first_frame, first_frame + n_frames) from `interleaved` (L R L R ..., 2 x n_frames int16).  Synchronous: the host buffer is the caller's again on return,
+ * so a long track can be loaded in pieces while the head plays elsewhere (a piece a feed in flight is reading is the caller's race).  A feed waits for the last load
+ * issued before it.  A range outside the track: MX_ERR_INVALID. */
+int mx_deck_load_i16(mx_deck* d, uint64_t first_frame, const int16_t* interleaved, uint64_t n_frames);
+/* Parameters / a seek (Q32.32 frames, any value: step 3 clamps it) that take effect at tick 0 of the NEXT feed: mx_deck_schedule(d, 0, params, NULL) and (d, 0, NULL, &pos). */
+int mx_deck_set(mx_deck* d, const mx_deck_params* params);
+int mx_deck_seek(mx_deck* d, int64_t pos_q32);
+/* ... at tick `tick_in_feed` of the next feed (a 2048-tick submission is 34 s of music).  Either may be NULL.  A later params / seek for the same tick replaces an
+ * earlier one; at one tick the seek applies before the params (steps 1., 2.).  Params are checked here (mx_deck_check).  The feed clears the schedule; a feed that does not
+ * reach a scheduled tick fails with MX_ERR_INVALID and drops the schedule, like mx_graph_run_ticks. */
+int mx_deck_schedule(mx_deck* d, uint32_t tick_in_feed, const mx_deck_params* params, const int64_t* seek_pos_q32);
+/* Host only: the parameter rules alone (MX_OK or MX_ERR_INVALID, mx_last_error saying which): |step_q32| <= 4 * 2^32, 0 <= slew_q32 <= 2^24, no flag bit outside
+ * PLAY | LOOP, _pad = 0, with LOOP 0 <= loop_in < loop_out <= n_frames, and 1 <= n_frames <= 2^30. */
+int mx_deck_check(const mx_deck_params* params, uint64_t n_frames);
+/* Host only, pure: advance `in` by ONE tick of spt frames (1 .. MX_DECK_MAX_SPT) over a track of n_frames, with this tick's pending params / seek (or NULL): *tick is the
+ * tick's record, *out the head after it (out may alias in).  The very function mx_deck_feed runs per tick.  params that mx_deck_check refuses, |in->step_q32| > 4 * 2^32,
+ * spt or n_frames out of range, a NULL in / tick / out: MX_ERR_INVALID. */
+int mx_deck_plan(const mx_deck_head* in, const mx_deck_params* params, const int64_t* seek_pos_q32, uint32_t spt, uint64_t n_frames, mx_deck_tick* tick, mx_deck_head* out);
+/* Write the next n_ticks ticks of decks[i] into SOURCE_STEREO node nodes[i] of `g`, i < n, for the coming mx_graph_run_ticks(g, ., n_ticks): one launch for all decks
+ * and ticks, on the graph's stream, into the buffer mx_graph_write_source would fill.  Asynchronous: nothing waits for the device (the per-tick descriptors go up from
+ * page-locked staging that is reused only after the launch that read it has finished).  spt is the graph's.  A node that is not a SOURCE_STEREO, a bound source,
+ * n_ticks = 0 or above max_ticks_per_run, a duplicate node or deck, a deck on another device, a schedule beyond n_ticks: MX_ERR_INVALID, the graph stays usable and the
+ * decks stand where they stood (their schedules are dropped). */
+int mx_deck_feed(mx_deck* const* decks, const uint32_t* nodes, size_t n, mx_graph* g, uint32_t n_ticks);
+/* Records [first, first + n) of the deck's last feed.  Host data: no read-back, no synchronisation.  A window beyond that feed: MX_ERR_INVALID. */
+int mx_deck_read_ticks(const mx_deck* d, uint32_t first, uint32_t n, mx_deck_tick* dst);
+/* Where the head stands now (after the last feed). */
+int mx_deck_state(const mx_deck* d, mx_deck_head* out);
+/* Host only: *step_q32 = the integer nearest to speed * track_rate / graph_rate * 2^32 (exactly; ties to even): a 44 100 Hz file in a 48 000 Hz graph at speed 1 is
+ * 3 946 001 203.  speed = target_bpm / the BPM mx_tempo_bpm reads.  A rate of 0, a speed that is not finite, |result| > 4 * 2^32: MX_ERR_INVALID. */
+int mx_deck_step(uint32_t track_rate, uint32_t graph_rate, double speed, int64_t* step_q32);
+/* Host only: bank `bank` (0 .. 3) of the coefficient tables, 257 x 32 floats. */
+int mx_deck_tables(uint32_t bank, float* out);
+/* DEBUG: what the last mx_deck_feed of this process launched: out[0] ticks written as zeros (not playing, BEFORE, PAST), out[1] ticks whose chunks all took the
+ * streaming form (the chunk's track window staged in LDS), out[2] ticks with at least one chunk in the gather form (a loop fold or a change of direction inside the
+ * chunk: taps read from the track one by one), out[3 .. 5] the same counted in chunks of MX_DECK_CHUNK frames.  Tests use it to know every form ran. */
+int mx_deck_debug_last_feed(uint32_t out[6]);
 
 /* ---------------------------------------------------------------------------------------------- */
 /* pixel path: device-resident yuv420p frames, VideoMixer, scaler, colour                          */

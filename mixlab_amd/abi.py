@@ -345,6 +345,34 @@ _proto("mx_pcm_ring_destroy", None, C.c_void_p)
 _proto("mx_pcm_ring_push_i16", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)
 _proto("mx_pcm_ring_queued", C.c_int, C.c_void_p, C.POINTER(C.c_size_t))
 _proto("mx_pcm_ring_feed", C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_size_t))
+# the deck (mixlab_amd/deck.py): a track in device memory played at variable speed into a SOURCE_STEREO node
+DECK_PLAY, DECK_LOOP = 1, 2
+DECK_TICK_PLAY, DECK_TICK_LOOPING, DECK_TICK_BEFORE, DECK_TICK_PAST = 1, 2, 4, 8
+DECK_TAPS, DECK_PHASES, DECK_BANKS = 32, 256, 4
+DECK_CHUNK = 256          # MX_DECK_CHUNK: output frames one workgroup of the feed kernel writes
+DECK_MAX_SPT = 1 << 20    # MX_DECK_MAX_SPT
+class DeckParams(C.Structure):
+    _fields_ = [("step_q32", C.c_int64), ("slew_q32", C.c_int64), ("loop_in", C.c_int64), ("loop_out", C.c_int64), ("flags", C.c_uint32), ("_pad", C.c_uint32)]
+class DeckHead(C.Structure):
+    _fields_ = [("pos_q32", C.c_int64), ("step_q32", C.c_int64), ("params", DeckParams), ("last_loop_in", C.c_int64), ("last_loop_out", C.c_int64),
+                ("last_looping", C.c_uint32), ("_pad", C.c_uint32)]
+class DeckTick(C.Structure):
+    _fields_ = [("pos_q32", C.c_int64), ("step_q32", C.c_int64), ("dstep_q32", C.c_int64), ("loop_in", C.c_int64), ("loop_len", C.c_int64),
+                ("flags", C.c_uint32), ("bank", C.c_uint32)]
+_proto("mx_deck_create", C.c_int, C.c_uint64, C.c_int, C.POINTER(C.c_void_p))
+_proto("mx_deck_destroy", None, C.c_void_p)
+_proto("mx_deck_load_i16", C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64)
+_proto("mx_deck_set", C.c_int, C.c_void_p, C.POINTER(DeckParams))
+_proto("mx_deck_seek", C.c_int, C.c_void_p, C.c_int64)
+_proto("mx_deck_schedule", C.c_int, C.c_void_p, C.c_uint32, C.POINTER(DeckParams), C.POINTER(C.c_int64))
+_proto("mx_deck_check", C.c_int, C.POINTER(DeckParams), C.c_uint64)
+_proto("mx_deck_plan", C.c_int, C.POINTER(DeckHead), C.POINTER(DeckParams), C.POINTER(C.c_int64), C.c_uint32, C.c_uint64, C.POINTER(DeckTick), C.POINTER(DeckHead))
+_proto("mx_deck_feed", C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.c_size_t, C.c_void_p, C.c_uint32)
+_proto("mx_deck_read_ticks", C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(DeckTick))
+_proto("mx_deck_state", C.c_int, C.c_void_p, C.POINTER(DeckHead))
+_proto("mx_deck_step", C.c_int, C.c_uint32, C.c_uint32, C.c_double, C.POINTER(C.c_int64))
+_proto("mx_deck_tables", C.c_int, C.c_uint32, C.c_void_p)
+_proto("mx_deck_debug_last_feed", C.c_int, C.POINTER(C.c_uint32))
 _proto("mx_module_create", C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p))
 _proto("mx_module_create_ex", C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(GraphOpts), C.POINTER(C.c_void_p))
 _proto("mx_module_update", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)

@@ -1,0 +1,93 @@
+// mx_abi_deck.cpp -- extern "C" entry points of the deck (include/mixlab_gpu.h, "the deck").
+// Same fencing convention as mx_abi.cpp: catch everything, stash the message, return a status.
+#include <cstring>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "mx_deck.hpp"
+#include "mx_engine.hpp"
+
+using mx::Deck;
+using mx::Error;
+
+struct mx_graph { std::unique_ptr<mx::Graph> g; };   // same layout as in mx_abi.cpp
+struct mx_deck { Deck d; mx_deck(uint64_t n_frames, int device) : d(n_frames, device) {} };
+
+void mx_set_last_error(const std::string& s);   // mx_abi.cpp
+
+template <class F>
+static int guard(F&& f) noexcept {
+    try {
+        f();
+        return MX_OK;
+    } catch (const Error& e) {
+        mx_set_last_error(e.what());
+        return e.code;
+    } catch (const std::bad_alloc&) {
+        mx_set_last_error("host allocation failed");
+        return MX_ERR_NOMEM;
+    } catch (const std::exception& e) {
+        mx_set_last_error(std::string("internal error: ") + e.what());
+        return MX_ERR_INTERNAL;
+    } catch (...) {
+        mx_set_last_error("internal error: unknown exception");
+        return MX_ERR_INTERNAL;
+    }
+}
+#define REQUIRE(cond, msg) do { if (!(cond)) throw Error(MX_ERR_INVALID, msg); } while (0)
+
+extern "C" {
+
+int mx_deck_create(uint64_t n_frames, int device, mx_deck** out) {
+    return guard([&] { REQUIRE(out, "out is NULL"); *out = nullptr; *out = new mx_deck(n_frames, device); });
+}
+void mx_deck_destroy(mx_deck* d) { (void)guard([&] { delete d; }); }
+
+int mx_deck_load_i16(mx_deck* d, uint64_t first_frame, const int16_t* interleaved, uint64_t n_frames) {
+    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.load_i16(first_frame, interleaved, n_frames); });
+}
+int mx_deck_set(mx_deck* d, const mx_deck_params* params) {
+    return guard([&] { REQUIRE(d && params, "NULL argument"); d->d.schedule(0, params, nullptr); });
+}
+int mx_deck_seek(mx_deck* d, int64_t pos_q32) {
+    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.schedule(0, nullptr, &pos_q32); });
+}
+int mx_deck_schedule(mx_deck* d, uint32_t tick_in_feed, const mx_deck_params* params, const int64_t* seek_pos_q32) {
+    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.schedule(tick_in_feed, params, seek_pos_q32); });
+}
+int mx_deck_check(const mx_deck_params* params, uint64_t n_frames) {
+    return guard([&] { REQUIRE(params, "params is NULL"); mx::deck_check(*params, n_frames); });
+}
+int mx_deck_plan(const mx_deck_head* in, const mx_deck_params* params, const int64_t* seek_pos_q32, uint32_t spt, uint64_t n_frames, mx_deck_tick* tick, mx_deck_head* out) {
+    return guard([&] { REQUIRE(in && tick && out, "NULL argument"); mx::deck_plan(*in, params, seek_pos_q32, spt, n_frames, *tick, *out); });
+}
+int mx_deck_feed(mx_deck* const* decks, const uint32_t* nodes, size_t n, mx_graph* g, uint32_t n_ticks) {
+    return guard([&] {
+        REQUIRE(g, "graph is NULL");
+        REQUIRE(!n || (decks && nodes), "decks / nodes is NULL");
+        std::vector<Deck*> ds(n);
+        for (size_t i = 0; i < n; ++i) ds[i] = decks[i] ? &decks[i]->d : nullptr;
+        Deck::feed(ds.data(), nodes, n, *g->g, n_ticks);
+    });
+}
+int mx_deck_read_ticks(const mx_deck* d, uint32_t first, uint32_t n, mx_deck_tick* dst) {
+    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.read_ticks(first, n, dst); });
+}
+int mx_deck_state(const mx_deck* d, mx_deck_head* out) {
+    return guard([&] { REQUIRE(d && out, "NULL argument"); *out = d->d.head(); });
+}
+int mx_deck_step(uint32_t track_rate, uint32_t graph_rate, double speed, int64_t* step_q32) {
+    return guard([&] { REQUIRE(step_q32, "step_q32 is NULL"); *step_q32 = mx::deck_step(track_rate, graph_rate, speed); });
+}
+int mx_deck_tables(uint32_t bank, float* out) {
+    return guard([&] {
+        REQUIRE(out, "out is NULL"); REQUIRE(bank < MX_DECK_BANKS, "bank outside 0 .. 3");
+        std::memcpy(out, mx::deck_tables_host() + (size_t)bank * mx::DECK_BANK_FLOATS, (size_t)mx::DECK_BANK_FLOATS * sizeof(float));
+    });
+}
+int mx_deck_debug_last_feed(uint32_t out[6]) {
+    return guard([&] { REQUIRE(out, "out is NULL"); Deck::debug_last_feed(out); });
+}
+
+}  // extern "C"

@@ -1,0 +1,293 @@
+// mx_deck.cpp -- the deck's host side: parameter rules, the per-tick state machine (mx_deck_plan), the coefficient tables, the track, and the feed that turns the
+// coming ticks of many decks into one descriptor block and one launch (include/mixlab_gpu.h "the deck").
+#include "mx_deck.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <mutex>
+#include <string>
+
+#include "mx_engine.hpp"
+#include "mx_kernels.hpp"
+
+namespace mx {
+
+static const int64_t kOne = (int64_t)1 << DECK_Q, kMaxStep = 4 * kOne, kMaxSlew = (int64_t)1 << 24, kMargin = (int64_t)1 << 20;
+static const uint64_t kMaxFrames = (uint64_t)1 << 30;
+
+void deck_check(const mx_deck_params& p, uint64_t n_frames) {
+    if (n_frames < 1 || n_frames > kMaxFrames) throw Error(MX_ERR_INVALID, "deck: n_frames outside 1 .. 2^30");
+    if (p.step_q32 > kMaxStep || p.step_q32 < -kMaxStep) throw Error(MX_ERR_INVALID, "deck: |step_q32| above 4 * 2^32");
+    if (p.slew_q32 < 0 || p.slew_q32 > kMaxSlew) throw Error(MX_ERR_INVALID, "deck: slew_q32 outside 0 .. 2^24");
+    if (p.flags & ~(MX_DECK_PLAY | MX_DECK_LOOP)) throw Error(MX_ERR_INVALID, "deck: a flag bit outside MX_DECK_PLAY | MX_DECK_LOOP");
+    if (p._pad) throw Error(MX_ERR_INVALID, "deck: _pad must be 0");
+    if ((p.flags & MX_DECK_LOOP) && !(p.loop_in >= 0 && p.loop_in < p.loop_out && p.loop_out <= (int64_t)n_frames))
+        throw Error(MX_ERR_INVALID, "deck: with MX_DECK_LOOP, 0 <= loop_in < loop_out <= n_frames");
+}
+
+static inline int64_t iabs64(int64_t v) { return v < 0 ? -v : v; }
+
+void deck_plan(const mx_deck_head& in, const mx_deck_params* params, const int64_t* seek, uint32_t spt, uint64_t n_frames, mx_deck_tick& tick, mx_deck_head& out) {
+    if (spt < 1 || spt > MX_DECK_MAX_SPT) throw Error(MX_ERR_INVALID, "deck: frames per tick outside 1 .. MX_DECK_MAX_SPT");
+    if (params) deck_check(*params, n_frames);
+    else if (n_frames < 1 || n_frames > kMaxFrames) throw Error(MX_ERR_INVALID, "deck: n_frames outside 1 .. 2^30");
+    if (in.step_q32 > kMaxStep || in.step_q32 < -kMaxStep) throw Error(MX_ERR_INVALID, "deck: the head's |step_q32| is above 4 * 2^32");
+    mx_deck_head h = in;
+    if (seek) h.pos_q32 = *seek;                                                                   // 1.
+    if (params) h.params = *params;                                                                // 2.
+    const mx_deck_params& p = h.params;
+    const int64_t lo = -kMargin * kOne, hi = ((int64_t)n_frames + kMargin) * kOne;                 // 3.
+    h.pos_q32 = std::min(std::max(h.pos_q32, lo), hi);
+    const bool looping = (p.flags & MX_DECK_LOOP) &&                                               // 4.
+        ((h.last_looping && h.last_loop_in == p.loop_in && h.last_loop_out == p.loop_out) || (h.pos_q32 >= p.loop_in * kOne && h.pos_q32 < p.loop_out * kOne));
+    const bool play = (p.flags & MX_DECK_PLAY) != 0;
+    int64_t dstep = 0, m = 0;
+    if (play) {                                                                                    // 5.
+        if (p.slew_q32 == 0) h.step_q32 = p.step_q32;
+        else {
+            dstep = std::min(std::max((p.step_q32 - h.step_q32) / (int64_t)spt, -p.slew_q32), p.slew_q32);
+            if (dstep == 0) h.step_q32 = p.step_q32;
+        }
+        m = std::max(iabs64(h.step_q32), iabs64(h.step_q32 + (int64_t)(spt - 1) * dstep));
+    }
+    tick.pos_q32 = h.pos_q32; tick.step_q32 = h.step_q32; tick.dstep_q32 = dstep;
+    tick.loop_in = looping ? p.loop_in : 0; tick.loop_len = looping ? p.loop_out - p.loop_in : 0;
+    tick.bank = !play || m <= kOne ? 0u : 3 * m <= 4 * kOne ? 1u : m <= 2 * kOne ? 2u : 3u;
+    tick.flags = (play ? MX_DECK_TICK_PLAY : 0u) | (looping ? MX_DECK_TICK_LOOPING : 0u);
+    if (play && !looping) {
+        if (h.pos_q32 + (int64_t)(spt - 1) * m < -16 * kOne) tick.flags |= MX_DECK_TICK_BEFORE;
+        if (h.pos_q32 - (int64_t)(spt - 1) * m >= ((int64_t)n_frames + 15) * kOne) tick.flags |= MX_DECK_TICK_PAST;
+    }
+    if (play) {
+        h.pos_q32 = deck_u(h.pos_q32, h.step_q32, dstep, spt);
+        if (looping) h.pos_q32 = deck_fold(h.pos_q32, p.loop_in * kOne, (p.loop_out - p.loop_in) * kOne);
+        h.step_q32 += (int64_t)spt * dstep;
+    }
+    h.last_looping = looping ? 1u : 0u; h.last_loop_in = looping ? p.loop_in : 0; h.last_loop_out = looping ? p.loop_out : 0; h._pad = 0;
+    out = h;
+}
+
+int64_t deck_step(uint32_t track_rate, uint32_t graph_rate, double speed) {
+    if (!track_rate || !graph_rate) throw Error(MX_ERR_INVALID, "deck: a rate of 0");
+    if (!std::isfinite(speed)) throw Error(MX_ERR_INVALID, "deck: speed is not finite");
+    const char* const too_fast = "deck: the step is above 4 * 2^32 in magnitude";
+    if (std::fabs(speed) * (double)track_rate / (double)graph_rate > 5.0) throw Error(MX_ERR_INVALID, too_fast);
+    // exactly: |speed| = M 2^e (M < 2^53), the step = M track_rate 2^(32 + e) / graph_rate rounded to nearest, ties to even
+    int e = 0;
+    const double fr = std::frexp(std::fabs(speed), &e);
+    unsigned __int128 num = (unsigned __int128)(uint64_t)std::ldexp(fr, 53) * track_rate, den = graph_rate;
+    const int sh = 32 + e - 53;
+    if (sh >= 0) num <<= sh;                 // (sh <= 15 here: |speed| <= 5 * 2^32)
+    else if (-sh > 90) return 0;             // below 2^-6 of a unit
+    else den <<= -sh;
+    unsigned __int128 q = num / den; const unsigned __int128 r = num % den;
+    if (2 * r > den || (2 * r == den && (q & 1))) ++q;
+    if (q > (unsigned __int128)kMaxStep) throw Error(MX_ERR_INVALID, too_fast);
+    return speed < 0 ? -(int64_t)q : (int64_t)q;
+}
+
+// ---- tables (the header's TABLES), evaluated in long double so that the one rounding to f32 is the nearest f32 of the exact value ----
+static long double bessel_i0(long double x) {
+    long double term = 1.0L, sum = 1.0L;
+    const long double q = x * x / 4.0L;
+    for (int k = 1; k < 200; ++k) { term *= q / ((long double)k * k); sum += term; if (term < sum * 1e-25L) break; }
+    return sum;
+}
+const float* deck_tables_host() {
+    static std::vector<float> tab;
+    static std::once_flag once;
+    std::call_once(once, [] {
+        tab.assign((size_t)MX_DECK_BANKS * DECK_BANK_FLOATS, 0.0f);
+        const long double pi = 3.14159265358979323846264338327950288L, i0_9 = bessel_i0(9.0L);
+        for (int b = 0; b < MX_DECK_BANKS; ++b) {
+            const int fc4 = 4 - b;   // fc = fc4 / 4
+            for (int p = 0; p <= MX_DECK_PHASES; ++p) {
+                long double g[MX_DECK_TAPS], sum = 0.0L;
+                for (int k = 0; k < MX_DECK_TAPS; ++k) {
+                    const int x256 = (k - 15) * 256 - p;             // x = x256 / 256, fc x = N / 1024
+                    const int N = fc4 * x256;
+                    long double sinc = 1.0L;
+                    if (N != 0) {
+                        // sin(pi N / 1024) with the argument reduced exactly: N = 1024 h + r, |r| <= 512
+                        int h = (N >= 0 ? N + 512 : N - 511) / 1024; int r = N - 1024 * h;
+                        const long double s = r == 0 ? 0.0L : sinl(pi * (long double)r / 1024.0L);
+                        sinc = ((h & 1) ? -s : s) / (pi * (long double)N / 1024.0L);
+                    }
+                    const long double xr = (long double)x256 / 4096.0L;   // x / 16
+                    const long double in = 1.0L - xr * xr;
+                    g[k] = ((long double)fc4 / 4.0L) * sinc * bessel_i0(9.0L * sqrtl(in > 0.0L ? in : 0.0L)) / i0_9;
+                    sum += g[k];
+                }
+                for (int k = 0; k < MX_DECK_TAPS; ++k) tab[(size_t)b * DECK_BANK_FLOATS + (size_t)p * MX_DECK_TAPS + k] = (float)(g[k] / sum);
+            }
+        }
+    });
+    return tab.data();
+}
+
+// the tables on a device, uploaded on first use and kept for the life of the process
+static const float* deck_tables_device(int device) {
+    static std::mutex mu;
+    static std::vector<std::pair<int, float*>> have;
+    std::lock_guard<std::mutex> lock(mu);
+    for (auto& h : have) if (h.first == device) return h.second;
+    float* p = nullptr;
+    const size_t bytes = (size_t)MX_DECK_BANKS * DECK_BANK_FLOATS * sizeof(float);
+    hip_check(hipMalloc((void**)&p, bytes), "hipMalloc(deck tables)");
+    hip_check(hipMemcpy(p, deck_tables_host(), bytes, hipMemcpyHostToDevice), "hipMemcpy(deck tables)");
+    have.push_back({device, p});
+    return p;
+}
+
+// ---- the deck ----
+Deck::Deck(uint64_t n_frames, int device) : n_frames_(n_frames), device_(device) {
+    if (n_frames < 1 || n_frames > kMaxFrames) throw Error(MX_ERR_INVALID, "deck: n_frames outside 1 .. 2^30");
+    if (device_ < 0) hip_check(hipGetDevice(&device_), "hipGetDevice");
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    track_.alloc(n_frames * 4);
+    hip_check(hipStreamCreateWithFlags(&load_stream_, hipStreamNonBlocking), "hipStreamCreate(deck)");
+    hip_check(hipEventCreateWithFlags(&loaded_, hipEventDisableTiming), "hipEventCreate");
+    hip_check(hipMemsetAsync(track_.p, 0, n_frames * 4, load_stream_), "hipMemsetAsync(deck track)");
+    hip_check(hipStreamSynchronize(load_stream_), "hipStreamSynchronize");
+}
+
+Deck::~Deck() {
+    (void)hipSetDevice(device_);
+    (void)hipDeviceSynchronize();   // a feed in flight may still read the track
+    if (loaded_) (void)hipEventDestroy(loaded_);
+    if (load_stream_) (void)hipStreamDestroy(load_stream_);
+}
+
+void Deck::load_i16(uint64_t first, const int16_t* interleaved, uint64_t n) {
+    if (first > n_frames_ || n > n_frames_ - first) throw Error(MX_ERR_INVALID, "deck: the loaded range lies outside the track");
+    if (!n) return;
+    if (!interleaved) throw Error(MX_ERR_INVALID, "deck: interleaved is NULL");
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    hip_check(hipMemcpyAsync((char*)track_.p + first * 4, interleaved, n * 4, hipMemcpyHostToDevice, load_stream_), "hipMemcpyAsync(deck load)");
+    hip_check(hipEventRecord(loaded_, load_stream_), "hipEventRecord");
+    load_pending_ = true;
+    hip_check(hipStreamSynchronize(load_stream_), "hipStreamSynchronize");   // the host buffer is the caller's again
+}
+
+void Deck::schedule(uint32_t tick, const mx_deck_params* params, const int64_t* seek) {
+    if (params) deck_check(*params, n_frames_);
+    if (!params && !seek) return;
+    auto it = std::find_if(sched_.begin(), sched_.end(), [&](const Event& e) { return e.tick == tick; });
+    if (it == sched_.end()) { sched_.push_back(Event{tick, false, false, mx_deck_params{}, 0}); it = sched_.end() - 1; }
+    if (params) { it->has_params = true; it->params = *params; }
+    if (seek) { it->has_seek = true; it->seek = *seek; }
+}
+
+void Deck::read_ticks(uint32_t first, uint32_t n, mx_deck_tick* dst) const {
+    if (first > ticks_.size() || n > ticks_.size() - first) throw Error(MX_ERR_INVALID, "deck: a window beyond the last feed");
+    if (n && !dst) throw Error(MX_ERR_INVALID, "deck: dst is NULL");
+    if (n) std::memcpy(dst, ticks_.data() + first, (size_t)n * sizeof(mx_deck_tick));
+}
+
+// ---- the feed ----
+// The descriptor block of a feed -- DeckDev[n] then DeckTickDev[n x n_ticks] -- is written into one of kSlots page-locked buffers, copied by a kernel into that slot's
+// device buffer and read there by the feed kernel; the event recorded behind the feed kernel says when both are free again.  A slot is taken round-robin, so the host
+// waits only when kSlots feeds are in flight at once (and then for the oldest): a steady tick-by-tick host never does.
+namespace {
+struct Slot { void* host = nullptr; size_t host_cap = 0; DevBuf dev; hipEvent_t done = nullptr; bool pending = false; int device = -1; };
+constexpr int kSlots = 4;
+struct FeedState {
+    std::mutex mu;
+    Slot slots[kSlots]; int next = 0;
+    std::vector<DeckTickDev> last; uint32_t last_spt = 0;   // the last feed's ticks, for mx_deck_debug_last_feed
+} feed_state;
+}  // namespace
+
+void Deck::feed(Deck* const* decks, const uint32_t* nodes, size_t n, Graph& g, uint32_t n_ticks) {
+    auto drop = [&] { for (size_t i = 0; i < n; ++i) if (decks && decks[i]) decks[i]->sched_.clear(); };
+    try {
+        if (!n) return;
+        if (!decks || !nodes) throw Error(MX_ERR_INVALID, "deck feed: decks / nodes is NULL");
+        if (n > 0xffffffu) throw Error(MX_ERR_INVALID, "deck feed: more than 2^24 decks");
+        if (!n_ticks) throw Error(MX_ERR_INVALID, "deck feed: n_ticks is 0");
+        const size_t spt = g.spt();
+        if (spt < 1 || spt > MX_DECK_MAX_SPT) throw Error(MX_ERR_INVALID, "deck feed: the graph's frames per tick are outside 1 .. MX_DECK_MAX_SPT");
+        for (size_t i = 0; i < n; ++i) if (!decks[i]) throw Error(MX_ERR_INVALID, "deck feed: a deck is NULL");
+        std::vector<float*> outs(n);
+        for (size_t i = 0; i < n; ++i) {
+            if (decks[i]->device_ != g.device()) throw Error(MX_ERR_INVALID, "deck feed: deck " + std::to_string(i) + " lives on another device than the graph");
+            outs[i] = g.source_feed_ptr(nodes[i], (size_t)n_ticks * spt);
+            for (const Event& e : decks[i]->sched_)
+                if (e.tick >= n_ticks) throw Error(MX_ERR_INVALID, "deck feed: deck " + std::to_string(i) + " has an event scheduled at tick " + std::to_string(e.tick) + ", beyond this feed");
+        }
+        {
+            std::vector<const Deck*> d(decks, decks + n); std::vector<uint32_t> nd(nodes, nodes + n);
+            std::sort(d.begin(), d.end()); std::sort(nd.begin(), nd.end());
+            if (std::adjacent_find(d.begin(), d.end()) != d.end()) throw Error(MX_ERR_INVALID, "deck feed: a deck is named twice");
+            if (std::adjacent_find(nd.begin(), nd.end()) != nd.end()) throw Error(MX_ERR_INVALID, "deck feed: a node is named twice");
+        }
+        hip_check(hipSetDevice(g.device()), "hipSetDevice");
+        const float* tables = deck_tables_device(g.device());
+
+        std::lock_guard<std::mutex> lock(feed_state.mu);
+        Slot& sl = feed_state.slots[feed_state.next];
+        feed_state.next = (feed_state.next + 1) % kSlots;
+        if (sl.pending) { hip_check(hipSetDevice(sl.device), "hipSetDevice"); hip_check(hipEventSynchronize(sl.done), "hipEventSynchronize"); sl.pending = false; hip_check(hipSetDevice(g.device()), "hipSetDevice"); }
+        const size_t head_bytes = (n * sizeof(DeckDev) + 15) & ~(size_t)15, bytes = head_bytes + n * (size_t)n_ticks * sizeof(DeckTickDev);
+        if (sl.host_cap < bytes) {
+            if (sl.host) (void)hipHostFree(sl.host);
+            sl.host = nullptr; sl.host_cap = 0;
+            hip_check(hipHostMalloc(&sl.host, bytes, hipHostMallocDefault), "hipHostMalloc(deck staging)");
+            sl.host_cap = bytes;
+        }
+        if (sl.dev.bytes < bytes || sl.device != g.device()) {
+            if (sl.done) { (void)hipEventDestroy(sl.done); sl.done = nullptr; }
+            sl.dev.free_(); sl.dev.alloc(bytes); sl.device = g.device();
+        }
+        if (!sl.done) hip_check(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming), "hipEventCreate");
+
+        DeckDev* dd = (DeckDev*)sl.host;
+        DeckTickDev* td = (DeckTickDev*)((char*)sl.host + head_bytes);
+        std::vector<mx_deck_head> heads(n);
+        std::vector<std::vector<mx_deck_tick>> recs(n);
+        bool phase_varies = false;
+        for (size_t i = 0; i < n; ++i) {
+            Deck& d = *decks[i];
+            dd[i] = DeckDev{(const uint32_t*)d.track_.p, outs[i], (int64_t)d.n_frames_};
+            mx_deck_head h = d.head_;
+            recs[i].resize(n_ticks);
+            std::vector<const Event*> at(d.sched_.empty() ? 0 : n_ticks, nullptr);
+            for (const Event& e : d.sched_) at[e.tick] = &e;
+            for (uint32_t t = 0; t < n_ticks; ++t) {
+                const Event* e = at.empty() ? nullptr : at[t];
+                mx_deck_tick& r = recs[i][t];
+                deck_plan(h, e && e->has_params ? &e->params : nullptr, e && e->has_seek ? &e->seek : nullptr, (uint32_t)spt, d.n_frames_, r, h);
+                const bool zero = !(r.flags & MX_DECK_TICK_PLAY) || (r.flags & (MX_DECK_TICK_BEFORE | MX_DECK_TICK_PAST));
+                td[i * (size_t)n_ticks + t] = DeckTickDev{r.pos_q32, r.step_q32, r.dstep_q32, (uint32_t)r.loop_in, (uint32_t)r.loop_len,
+                                                         zero ? (uint32_t)DECK_FORM_ZERO : (uint32_t)DECK_FORM_PLAY, r.bank};
+                if (!zero && deck_phase_varies(td[i * (size_t)n_ticks + t])) phase_varies = true;
+            }
+            heads[i] = h;
+        }
+        for (size_t i = 0; i < n; ++i)
+            if (decks[i]->load_pending_) { hip_check(hipStreamWaitEvent(g.stream(), decks[i]->loaded_, 0), "hipStreamWaitEvent"); decks[i]->load_pending_ = false; }
+        launch_upload(sl.dev.p, sl.host, bytes, g.stream());
+        launch_deck_feed((const DeckDev*)sl.dev.p, (const DeckTickDev*)((const char*)sl.dev.p + head_bytes), tables, (uint32_t)n, n_ticks, (uint32_t)spt, phase_varies, g.stream());
+        hip_check(hipGetLastError(), "deck feed launch");
+        hip_check(hipEventRecord(sl.done, g.stream()), "hipEventRecord");
+        sl.pending = true;
+        feed_state.last.assign(td, td + n * (size_t)n_ticks); feed_state.last_spt = (uint32_t)spt;
+        for (size_t i = 0; i < n; ++i) { decks[i]->head_ = heads[i]; decks[i]->ticks_ = std::move(recs[i]); decks[i]->sched_.clear(); }
+    } catch (...) { drop(); throw; }
+}
+
+void Deck::debug_last_feed(uint32_t out[6]) {
+    std::lock_guard<std::mutex> lock(feed_state.mu);
+    for (int k = 0; k < 6; ++k) out[k] = 0;
+    const uint32_t spt = feed_state.last_spt, chunks = (spt + MX_DECK_CHUNK - 1) / MX_DECK_CHUNK;
+    for (const DeckTickDev& t : feed_state.last) {
+        if (t.form == DECK_FORM_ZERO) { ++out[0]; out[3] += chunks; continue; }
+        uint32_t gathered = 0;
+        for (uint32_t c = 0; c < chunks; ++c)
+            if (!deck_chunk_plan(t, c * MX_DECK_CHUNK, std::min<uint32_t>(MX_DECK_CHUNK, spt - c * MX_DECK_CHUNK)).stream) ++gathered;
+        ++out[gathered ? 2 : 1]; out[4] += chunks - gathered; out[5] += gathered;
+    }
+}
+
+}  // namespace mx

@@ -1,0 +1,81 @@
+// mx_deck.hpp -- the deck (include/mixlab_gpu.h "the deck"): host state machine, the descriptors its feed kernel reads, and the launch plan both sides share (internal).
+#pragma once
+#include <cstdint>
+#include <vector>
+
+#include "mx_common.hpp"
+
+namespace mx {
+
+class Graph;
+
+enum { DECK_Q = 32, DECK_WINDOW = 4 * MX_DECK_CHUNK + MX_DECK_TAPS, DECK_BANK_FLOATS = (MX_DECK_PHASES + 1) * MX_DECK_TAPS };
+
+// what the kernel knows of one deck of a feed
+struct DeckDev { const uint32_t* track; float* out; int64_t n_frames; };
+// ... and of one tick of it: mx_deck_tick without what the kernel does not read, plus the form the host chose for the tick
+enum { DECK_FORM_ZERO = 0, DECK_FORM_PLAY = 1 };
+struct DeckTickDev { int64_t pos, step, dstep; uint32_t loop_in, loop_len; uint32_t form, bank; };
+
+// u(n) of a tick (the header's POSITION)
+__host__ __device__ inline int64_t deck_u(int64_t pos, int64_t step, int64_t dstep, int64_t n) { return pos + n * step + dstep * (n * (n - 1) / 2); }
+// floor division / floormod by a positive divisor
+__host__ __device__ inline int64_t deck_floordiv(int64_t a, int64_t b) { int64_t q = a / b; if ((a % b) != 0 && a < 0) --q; return q; }
+__host__ __device__ inline int64_t deck_fold(int64_t u, int64_t in_q, int64_t len_q) { int64_t r = (u - in_q) % len_q; if (r < 0) r += len_q; return in_q + r; }
+
+// the lanes of a tick differ in phase unless it moves by whole frames at a constant step (then two coefficient rows serve the whole tick)
+__host__ __device__ inline bool deck_phase_varies(const DeckTickDev& t) { return t.dstep != 0 || (t.step & 0xFFFFFFFFll) != 0; }
+
+// The launch plan of one chunk (frames [n0, n0 + cnt) of a playing tick), the same on the host (mx_deck_debug_last_feed) and in the kernel: the chunk STREAMS when its
+// positions move in one direction and, in a looping tick, lie within one wrap of the loop -- then its taps read the frames [lo, lo + len) and `shift` (a multiple of the
+// loop length, Q32) is what folding subtracts from every u of the chunk.  Anything else GATHERS.
+struct DeckChunkPlan { bool stream; int64_t lo; uint32_t len; int64_t shift; };
+__host__ __device__ inline DeckChunkPlan deck_chunk_plan(const DeckTickDev& t, uint32_t n0, uint32_t cnt) {
+    DeckChunkPlan p{false, 0, 0, 0};
+    const int64_t s0 = t.step + (int64_t)n0 * t.dstep, s1 = t.step + (int64_t)(n0 + cnt - 1) * t.dstep;   // the increments inside the chunk lie between these
+    if ((s0 < 0 && s1 > 0) || (s0 > 0 && s1 < 0)) return p;
+    int64_t ua = deck_u(t.pos, t.step, t.dstep, n0), ub = deck_u(t.pos, t.step, t.dstep, (int64_t)n0 + cnt - 1);
+    if (ua > ub) { const int64_t x = ua; ua = ub; ub = x; }
+    if (t.loop_len) {
+        const int64_t in_q = (int64_t)t.loop_in << DECK_Q, len_q = (int64_t)t.loop_len << DECK_Q;
+        const int64_t wa = deck_floordiv(ua - in_q, len_q);
+        if (wa != deck_floordiv(ub - in_q, len_q)) return p;
+        p.shift = wa * len_q;
+    }
+    const int64_t lo = ((ua - p.shift) >> DECK_Q) - 15, hi = ((ub - p.shift) >> DECK_Q) + 16;
+    if (hi - lo + 1 > (int64_t)DECK_WINDOW) return p;   // (cannot happen while |step| <= 4 * 2^32: 4 (cnt - 1) + 32 frames at the most)
+    p.stream = true; p.lo = lo; p.len = (uint32_t)(hi - lo + 1);
+    return p;
+}
+
+// ---- host ----
+void deck_check(const mx_deck_params& p, uint64_t n_frames);                         // throws Error(MX_ERR_INVALID) naming the rule
+void deck_plan(const mx_deck_head& in, const mx_deck_params* params, const int64_t* seek, uint32_t spt, uint64_t n_frames, mx_deck_tick& tick, mx_deck_head& out);
+int64_t deck_step(uint32_t track_rate, uint32_t graph_rate, double speed);
+const float* deck_tables_host();                                                       // MX_DECK_BANKS x DECK_BANK_FLOATS, computed once
+
+class Deck {
+public:
+    Deck(uint64_t n_frames, int device);
+    ~Deck();
+    Deck(const Deck&) = delete; Deck& operator=(const Deck&) = delete;
+    void load_i16(uint64_t first, const int16_t* interleaved, uint64_t n);
+    void schedule(uint32_t tick, const mx_deck_params* params, const int64_t* seek);
+    void read_ticks(uint32_t first, uint32_t n, mx_deck_tick* dst) const;
+    const mx_deck_head& head() const { return head_; }
+    uint64_t n_frames() const { return n_frames_; }
+    int device() const { return device_; }
+    static void feed(Deck* const* decks, const uint32_t* nodes, size_t n, Graph& g, uint32_t n_ticks);
+    static void debug_last_feed(uint32_t out[6]);
+
+private:
+    struct Event { uint32_t tick; bool has_params, has_seek; mx_deck_params params; int64_t seek; };
+    uint64_t n_frames_; int device_;
+    DevBuf track_;
+    hipStream_t load_stream_ = nullptr; hipEvent_t loaded_ = nullptr; bool load_pending_ = false;
+    mx_deck_head head_{};
+    std::vector<Event> sched_;          // at most one per tick, in no order
+    std::vector<mx_deck_tick> ticks_;   // the last feed's records
+};
+
+}  // namespace mx

@@ -1020,6 +1020,12 @@ void Graph::write_source(uint32_t node, const float* host, size_t frames) {
     hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");  // host buffer is the caller's again on return
 }
 
+float* Graph::source_feed_ptr(uint32_t node, size_t frames) {
+    check_source_write(node, frames);
+    if (nodes_[node].kind != MX_KIND_SOURCE_STEREO) throw Error(MX_ERR_INVALID, "node is not a SOURCE_STEREO");
+    return out_ptr(nodes_[node], 0, parity_);
+}
+
 void Graph::bind_source(uint32_t node, const void* dev) {
     if (node >= nodes_.size()) throw Error(MX_ERR_INVALID, "node out of range");
     Node& n = nodes_[node];

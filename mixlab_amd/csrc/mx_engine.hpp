@@ -193,6 +193,7 @@ public:
     // what a feed checks BEFORE it takes frames out of a pacing state machine (a rejected feed must not lose media):
     void check_video_queue(uint32_t node, uint64_t first_tick) const;   // queue_video_source(node, first_tick, ...) would be accepted
     void check_source_write(uint32_t node, size_t frames) const;        // write_source[_i16](node, ..., frames) would be accepted
+    float* source_feed_ptr(uint32_t node, size_t frames);               // ... of a SOURCE_STEREO: the buffer it would fill, for a device-side feeder that writes it on stream() (mx_deck_feed)
     const Node::MonTick& monitor_tick(uint32_t node, uint32_t tick_in_run);
     void monitor_consume(uint32_t node, uint32_t n_ticks);
     void read_monitor_audio_i16(uint32_t node, int16_t* host, uint32_t n_ticks);

@@ -338,4 +338,9 @@ void launch_resample(const ResampleDesc* d, uint32_t n, uint32_t max_taps, uint3
                      uint64_t in_base, uint64_t out_base, hipStream_t s, uint32_t common_up = 0 /* every channel's `up` when they all agree, else 0 */, bool fc = false,
                      uint32_t common_taps = 0, uint32_t common_down = 0 /* likewise taps_per_phase and `down` */);
 
+// the deck's feed (mx_deck.hpp, mx_k_deck.hip): one launch over n decks x n_ticks ticks x ceil(spt / MX_DECK_CHUNK) chunks; tick t of deck i goes to decks[i].out + t * 2 * spt
+struct DeckDev; struct DeckTickDev;
+void launch_deck_feed(const DeckDev* decks, const DeckTickDev* ticks, const float* tables, uint32_t n, uint32_t n_ticks, uint32_t spt,
+                      bool phase_varies /* some playing tick's lanes differ in phase: the kernel with the bank in LDS */, hipStream_t s);
+
 }  // namespace mx

@@ -1,0 +1,111 @@
+"""The deck (include/mixlab_gpu.h "the deck"): a track in device memory played at variable speed into a SOURCE_STEREO node.
+
+    deck = Deck(len(track) // 2); deck.load(track_i16)
+    deck.set(step_q32=deck_step(44100, 48000, 1.08), flags=abi.DECK_PLAY)
+    feed([deck], [source_node], graph, n_ticks); graph.run_ticks(first_tick, n_ticks)
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import abi
+from .abi import DeckHead, DeckParams, DeckTick, check, lib
+
+ONE = 1 << 32   # unity step / one track frame in Q32.32
+
+
+def params(step_q32=0, slew_q32=0, loop_in=0, loop_out=0, flags=0) -> DeckParams:
+    return DeckParams(int(step_q32), int(slew_q32), int(loop_in), int(loop_out), int(flags), 0)
+
+
+def deck_check(p: DeckParams, n_frames: int) -> None:
+    """the parameter rules alone (host only); raises MxError"""
+    check(lib.mx_deck_check(C.byref(p), int(n_frames)))
+
+
+def deck_step(track_rate: int, graph_rate: int, speed: float) -> int:
+    """the Q32 step nearest to speed * track_rate / graph_rate (host only)"""
+    out = C.c_int64()
+    check(lib.mx_deck_step(int(track_rate), int(graph_rate), float(speed), C.byref(out)))
+    return out.value
+
+
+def deck_tables(bank: int) -> np.ndarray:
+    """float32[257, 32]: coefficient bank `bank` as the kernel reads it (host only)"""
+    if not 0 <= bank < abi.DECK_BANKS:   # before any buffer is handed over
+        raise abi.MxError(abi.MX_ERR_INVALID, "bank outside 0 .. 3")
+    t = np.zeros((abi.DECK_PHASES + 1, abi.DECK_TAPS), np.float32)
+    check(lib.mx_deck_tables(bank, t.ctypes.data_as(C.c_void_p)))
+    return t
+
+
+def deck_plan(head: DeckHead, spt: int, n_frames: int, p: DeckParams | None = None, seek: int | None = None):
+    """one tick of the host state machine (pure, host only): (DeckTick, DeckHead after it)"""
+    tick, out = DeckTick(), DeckHead()
+    s = C.c_int64(seek) if seek is not None else None
+    check(lib.mx_deck_plan(C.byref(head), C.byref(p) if p is not None else None, C.byref(s) if s is not None else None, int(spt), int(n_frames),
+                           C.byref(tick), C.byref(out)))
+    return tick, out
+
+
+def debug_last_feed() -> dict:
+    out = (C.c_uint32 * 6)()
+    check(lib.mx_deck_debug_last_feed(out))
+    return dict(zip(("ticks_zero", "ticks_stream", "ticks_gather", "chunks_zero", "chunks_stream", "chunks_gather"), (int(v) for v in out)))
+
+
+class Deck:
+    """Thin RAII wrapper of mx_deck_*."""
+
+    def __init__(self, n_frames: int, device: int = -1):
+        self._h = C.c_void_p()
+        self.n_frames = int(n_frames)
+        check(lib.mx_deck_create(self.n_frames, device, C.byref(self._h)))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            lib.mx_deck_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def load(self, interleaved_i16: np.ndarray, first_frame: int = 0):
+        a = np.ascontiguousarray(interleaved_i16, dtype=np.int16).reshape(-1)
+        check(lib.mx_deck_load_i16(self._h, int(first_frame), a.ctypes.data_as(C.c_void_p), a.size // 2))
+
+    def set(self, p: DeckParams | None = None, **kw):
+        p = p if p is not None else params(**kw)
+        check(lib.mx_deck_set(self._h, C.byref(p)))
+
+    def seek(self, pos_q32: int):
+        check(lib.mx_deck_seek(self._h, int(pos_q32)))
+
+    def schedule(self, tick_in_feed: int, p: DeckParams | None = None, seek: int | None = None):
+        s = C.c_int64(seek) if seek is not None else None
+        check(lib.mx_deck_schedule(self._h, int(tick_in_feed), C.byref(p) if p is not None else None, C.byref(s) if s is not None else None))
+
+    def read_ticks(self, first: int, n: int) -> list[DeckTick]:
+        arr = (DeckTick * max(1, n))()
+        check(lib.mx_deck_read_ticks(self._h, int(first), int(n), arr))
+        return list(arr[:n])
+
+    def state(self) -> DeckHead:
+        h = DeckHead()
+        check(lib.mx_deck_state(self._h, C.byref(h)))
+        return h
+
+
+def feed(decks, nodes, graph, n_ticks: int) -> None:
+    """write the next n_ticks ticks of every deck into its SOURCE_STEREO node of `graph`: one launch, asynchronous on the graph's stream"""
+    n = len(decks)
+    if len(nodes) != n:
+        raise ValueError("one node per deck")
+    hs = (C.c_void_p * max(1, n))(*[d._h.value for d in decks])
+    ns = (C.c_uint32 * max(1, n))(*[int(x) for x in nodes])
+    check(lib.mx_deck_feed(hs, ns, n, graph._h, int(n_ticks)))
