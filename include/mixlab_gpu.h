@@ -43,7 +43,9 @@ extern "C" {
                               *    mx_video_matte_params, mx_video_matte, mx_video_matte_check, mx_video_matte_wipe, mx_graph_set_video_source_matte;
                               *    mx_deck, mx_deck_params, mx_deck_head, mx_deck_tick, mx_deck_create, mx_deck_destroy, mx_deck_load_i16, mx_deck_set, mx_deck_seek,
                               *    mx_deck_schedule, mx_deck_check, mx_deck_plan, mx_deck_feed, mx_deck_read_ticks, mx_deck_state, mx_deck_step, mx_deck_tables,
-                              *    mx_deck_debug_last_feed */
+                              *    mx_deck_debug_last_feed;
+                              *    mx_deck_keylock, mx_deck_grain, mx_deck_set_keylock, mx_deck_keylock_check, mx_deck_keylock_search, mx_deck_grain_count, mx_deck_read_grains,
+                              *    mx_deck_debug_last_keylock */
 
 /* ---- status codes (0 ok, <0 error; cf. MIXLAB_IOCTX_ERROR / MIXLAB_IOCTX_PANIC) ---- */
 enum {
@@ -792,7 +794,8 @@ int mx_pcm_ring_feed(mx_pcm_ring* r, mx_graph* g, uint32_t node, uint32_t n_tick
  *           bank, and flags: MX_DECK_TICK_PLAY, MX_DECK_TICK_LOOPING, and for a playing tick that is not looping, with m as above,
  *               MX_DECK_TICK_BEFORE  when pos + (spt - 1) * m <  -16 * 2^32             (no tap of the tick reaches frame 0: the tick is zeros),
  *               MX_DECK_TICK_PAST    when pos - (spt - 1) * m >= (n_frames + 15) * 2^32 (no tap reaches below n_frames: zeros).
- * Out of scope: key-lock (a change of tempo without a change of pitch), more than two channels, tracks above 2^30 frames, a deck as a member of the graph.
+ * Key-lock (a change of tempo without a change of pitch) is an optional way to render a playing tick: see KEY-LOCK below the deck's calls.
+ * Out of scope: more than two channels, tracks above 2^30 frames, a deck as a member of the graph.
  */
 #define MX_DECK_PLAY 1u
 #define MX_DECK_LOOP 2u
@@ -851,6 +854,59 @@ int mx_deck_tables(uint32_t bank, float* out);
  * streaming form (the chunk's track window staged in LDS), out[2] ticks with at least one chunk in the gather form (a loop fold or a change of direction inside the
  * chunk: taps read from the track one by one), out[3 .. 5] the same counted in chunks of MX_DECK_CHUNK frames.  Tests use it to know every form ran. */
 int mx_deck_debug_last_feed(uint32_t out[6]);
+
+/* ---- KEY-LOCK: tempo without pitch change, by overlap-add of grains placed by a waveform-similarity search (WSOLA), in integers ----
+ * BUILD-SPECIFIED.  An optional rendering mode of a deck, set by mx_deck_set_keylock.  The head keeps moving exactly as mx_deck_plan says -- seek, slew, loop, clamp and
+ * the tick records are what they were; params.step_q32 stays the TEMPO, the speed at which the head crosses the track.  Only what is written for a PLAYING tick changes:
+ * the waveform is read in grains, each at the step pitch_q32, started wherever the head stands.  A deck that never sets key-lock is untouched in every respect.
+ *
+ * SETTINGS   mx_deck_keylock: 2^30 <= pitch_q32 <= 4 * 2^32 (mx_deck_step(track_rate, graph_rate, 1.0) is the original key, a factor 2^(k/12) a transposition); hop a
+ *            power of two, 256 .. 8192; overlap a power of two, 16 .. min(hop / 2, 1024); radius 0 .. 1024; _pad = 0.  Recommended at 44.1 / 48 kHz: 1024 / 256 / 512
+ *            (about 21 ms, 5 ms, +-11 ms).  Below: H = hop, V = overlap, R = radius, p = pitch_q32.
+ * CLOCK      a key-locked deck counts its PLAYING output frames in t.  Grain j starts at t = j * H, which is some frame n of some tick of some feed; its nominal
+ *            position is a_j = u'(n) of that tick (the folded position of POSITION / A TICK above).  The clock restarts -- t = 0, and grain 0 has no previous grain --
+ *            at creation, at every mx_deck_set_keylock (also one that repeats the setting, and NULL), after any tick that is not playing, and when the deck is fed
+ *            into another graph (another mx_graph handle) than its last feed was.  A seek does NOT restart it: the cross-fade then runs from the old place to the
+ *            new one, a click-free cue jump.  Neither does a change of step, a loop, nor a BEFORE / PAST tick.  All of this the host can compute.
+ * POSITION   a grain with no previous grain has g_j = a_j, delta = 0, dist = 0.  Otherwise, with c = g_(j-1) + H * p (where the previous grain would continue),
+ *            C = c >> 32, A = a_j >> 32 (arithmetic shifts), s[f] = L[f] + R[f] of the raw int16 track and 0 outside [0, n_frames):
+ *                D(delta) = sum over i = 0 .. V - 1 of |s[C + i] - s[A + delta + i]|,   delta in [-R, R]        (at most 1024 * 131 070: it fits 32 bits)
+ *            delta_j is the delta of the smallest D; ties go to the smallest |delta|, then to the negative delta.  g_j = (A + delta_j) * 2^32 + (c - C * 2^32): the grain
+ *            continues c's fractional phase.  With R = 0 no search runs: delta = 0, dist = 0 (plain overlap-add).
+ * OUTPUT     output frame t = j * H + m, 0 <= m < H.  G_j(m) is the deck's FILTER evaluated at u = g_j + m * p and rounded to f32 as the deck rounds it: 32 taps, the
+ *            row blend, unfused f64 sums in ascending k; the taps read the track's linear neighbours and u is never folded, so a grain may read up to (H + V) * p
+ *            frames past a loop's end.  The bank is chosen by the bank rule from m = p, once per setting.  If grain j has a previous grain and m < V:
+ *                a = (double)G_(j-1)(H + m),  b = (double)G_j(m),  w = (double)m / (double)V,  y = (float)(a + w * (b - a)),   every operation separate;
+ *            otherwise y = G_j(m).  Both channels use the same positions.  MX_DECK_TICK_BEFORE / _PAST stay in the records, but a key-locked playing tick is always
+ *            rendered by this rule: zeros come out by themselves where there is no track.  A tick that is not playing is zeros.
+ * IT FOLLOWS that the result does not depend on how ticks are grouped into feeds; that with p equal to a constant step (no slew, no loop fold, no seek) every c equals
+ *            the next a, every delta is 0 and the output is the plain deck's bit for bit (a + w * (a - a) = a), which at unity from an integer position is the track
+ *            itself; and that a negative step moves the head backwards while every grain still reads forwards.
+ * RECORDS    mx_deck_grain, one per grain that STARTED in the last feed: a_q32, g_q32, the tick of the feed and the frame of that tick it starts at, delta, dist, and
+ *            flags: MX_DECK_GRAIN_FIRST for a grain with no previous one.  a, tick, frame and flags are host data; g, delta and dist are computed on the device.
+ * Out of scope: formant preservation, phase-vocoder stretching, grains read backwards, per-tick scheduling of key-lock settings, more than two channels.
+ */
+#define MX_DECK_GRAIN_FIRST 1u
+typedef struct { int64_t pitch_q32; uint32_t hop; uint32_t overlap; uint32_t radius; uint32_t _pad; } mx_deck_keylock;
+typedef struct { int64_t a_q32; int64_t g_q32; uint32_t tick; uint32_t frame; int32_t delta; uint32_t dist; uint32_t flags; uint32_t _pad; } mx_deck_grain;
+/* Key-lock with these settings from tick 0 of the NEXT feed on; NULL: off.  Not part of the schedule: a refused feed leaves it set.  Settings that
+ * mx_deck_keylock_check refuses: MX_ERR_INVALID, and the deck keeps what it had. */
+int mx_deck_set_keylock(mx_deck* d, const mx_deck_keylock* k);
+/* Host only: the SETTINGS rules alone. */
+int mx_deck_keylock_check(const mx_deck_keylock* k);
+/* Host only, pure: the search rule of POSITION alone, in plain C++ -- *delta and *dist for a previous grain continuing at frame C and a nominal frame A, over a track of
+ * n_frames interleaved stereo frames.  overlap 1 .. 1024 (any value, not only the powers of two a setting may have), radius 0 .. 1024 (0: the one candidate's D),
+ * |C|, |A| <= 2^40.  Anything else, a NULL pointer, n_frames outside 1 .. 2^30: MX_ERR_INVALID. */
+int mx_deck_keylock_search(const int16_t* interleaved, uint64_t n_frames, int64_t C, int64_t A, uint32_t overlap, uint32_t radius, int32_t* delta, uint32_t* dist);
+/* How many grains started in the deck's last feed (0 for a plain deck).  Host data: no synchronisation. */
+int mx_deck_grain_count(const mx_deck* d, uint32_t* n);
+/* Grain records [first, first + n) of the last feed.  THE ONE CALL OF THE DECK THAT WAITS for the feed's kernels (g, delta and dist come back from the device); it is
+ * indication only and never needed to play.  A window beyond the last feed's grains: MX_ERR_INVALID. */
+int mx_deck_read_grains(mx_deck* d, uint32_t first, uint32_t n, mx_deck_grain* dst);
+/* DEBUG: the key-locked decks of the last mx_deck_feed of this process: out[0] grains placed by a search, out[1] grains without one (a first grain, or radius 0),
+ * out[2] render chunks (MX_DECK_CHUNK frames of a playing tick) with at least one fading lane, out[3] render chunks with a grain start after their first lane.
+ * mx_deck_debug_last_feed counts the plain decks of the feed only. */
+int mx_deck_debug_last_keylock(uint32_t out[4]);
 
 /* ---------------------------------------------------------------------------------------------- */
 /* pixel path: device-resident yuv420p frames, VideoMixer, scaler, colour                          */

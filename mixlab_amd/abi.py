@@ -373,6 +373,19 @@ _proto("mx_deck_state", C.c_int, C.c_void_p, C.POINTER(DeckHead))
 _proto("mx_deck_step", C.c_int, C.c_uint32, C.c_uint32, C.c_double, C.POINTER(C.c_int64))
 _proto("mx_deck_tables", C.c_int, C.c_uint32, C.c_void_p)
 _proto("mx_deck_debug_last_feed", C.c_int, C.POINTER(C.c_uint32))
+# ... key-locked (the header's KEY-LOCK): tempo without pitch change by overlap-add of searched grains
+DECK_GRAIN_FIRST = 1
+class DeckKeylock(C.Structure):
+    _fields_ = [("pitch_q32", C.c_int64), ("hop", C.c_uint32), ("overlap", C.c_uint32), ("radius", C.c_uint32), ("_pad", C.c_uint32)]
+class DeckGrain(C.Structure):
+    _fields_ = [("a_q32", C.c_int64), ("g_q32", C.c_int64), ("tick", C.c_uint32), ("frame", C.c_uint32), ("delta", C.c_int32), ("dist", C.c_uint32),
+                ("flags", C.c_uint32), ("_pad", C.c_uint32)]
+_proto("mx_deck_set_keylock", C.c_int, C.c_void_p, C.POINTER(DeckKeylock))
+_proto("mx_deck_keylock_check", C.c_int, C.POINTER(DeckKeylock))
+_proto("mx_deck_keylock_search", C.c_int, C.c_void_p, C.c_uint64, C.c_int64, C.c_int64, C.c_uint32, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_uint32))
+_proto("mx_deck_grain_count", C.c_int, C.c_void_p, C.POINTER(C.c_uint32))
+_proto("mx_deck_read_grains", C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(DeckGrain))
+_proto("mx_deck_debug_last_keylock", C.c_int, C.POINTER(C.c_uint32))
 _proto("mx_module_create", C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p))
 _proto("mx_module_create_ex", C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(GraphOpts), C.POINTER(C.c_void_p))
 _proto("mx_module_update", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)

@@ -89,5 +89,23 @@ int mx_deck_tables(uint32_t bank, float* out) {
 int mx_deck_debug_last_feed(uint32_t out[6]) {
     return guard([&] { REQUIRE(out, "out is NULL"); Deck::debug_last_feed(out); });
 }
+int mx_deck_set_keylock(mx_deck* d, const mx_deck_keylock* k) {
+    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.set_keylock(k); });
+}
+int mx_deck_keylock_check(const mx_deck_keylock* k) {
+    return guard([&] { REQUIRE(k, "settings are NULL"); mx::deck_keylock_check(*k); });
+}
+int mx_deck_keylock_search(const int16_t* interleaved, uint64_t n_frames, int64_t C, int64_t A, uint32_t overlap, uint32_t radius, int32_t* delta, uint32_t* dist) {
+    return guard([&] { REQUIRE(delta && dist, "NULL argument"); mx::deck_keylock_search(interleaved, n_frames, C, A, overlap, radius, *delta, *dist); });
+}
+int mx_deck_grain_count(const mx_deck* d, uint32_t* n) {
+    return guard([&] { REQUIRE(d && n, "NULL argument"); *n = d->d.grain_count(); });
+}
+int mx_deck_read_grains(mx_deck* d, uint32_t first, uint32_t n, mx_deck_grain* dst) {
+    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.read_grains(first, n, dst); });
+}
+int mx_deck_debug_last_keylock(uint32_t out[4]) {
+    return guard([&] { REQUIRE(out, "out is NULL"); Deck::debug_last_keylock(out); });
+}
 
 }  // extern "C"

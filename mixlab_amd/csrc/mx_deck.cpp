@@ -196,6 +196,8 @@ struct FeedState {
     std::mutex mu;
     Slot slots[kSlots]; int next = 0;
     std::vector<DeckTickDev> last; uint32_t last_spt = 0;   // the last feed's ticks, for mx_deck_debug_last_feed
+    struct KlTick { KlTickDev t; uint32_t log_hop, overlap; };
+    std::vector<KlTick> last_kl; uint32_t kl_searched = 0, kl_unsearched = 0;   // ... and its key-locked ticks and grains, for mx_deck_debug_last_keylock
 } feed_state;
 }  // namespace
 
@@ -229,7 +231,12 @@ void Deck::feed(Deck* const* decks, const uint32_t* nodes, size_t n, Graph& g, u
         Slot& sl = feed_state.slots[feed_state.next];
         feed_state.next = (feed_state.next + 1) % kSlots;
         if (sl.pending) { hip_check(hipSetDevice(sl.device), "hipSetDevice"); hip_check(hipEventSynchronize(sl.done), "hipEventSynchronize"); sl.pending = false; hip_check(hipSetDevice(g.device()), "hipSetDevice"); }
-        const size_t head_bytes = (n * sizeof(DeckDev) + 15) & ~(size_t)15, bytes = head_bytes + n * (size_t)n_ticks * sizeof(DeckTickDev);
+        size_t nk = 0, grain_cap = 0;   // key-locked decks, and room for their grain starts: ceil(spt / hop) a tick at the most
+        for (size_t i = 0; i < n; ++i)
+            if (decks[i]->kl_on_) { ++nk; grain_cap += (size_t)n_ticks * (spt / decks[i]->kl_.hop + 1); }
+        const size_t head_bytes = (n * sizeof(DeckDev) + 15) & ~(size_t)15, plain_bytes = (head_bytes + n * (size_t)n_ticks * sizeof(DeckTickDev) + 15) & ~(size_t)15;
+        const size_t bytes = nk ? plain_bytes + nk * sizeof(KlDeckDev) + nk * (size_t)n_ticks * sizeof(KlTickDev) + grain_cap * sizeof(KlGrainIn)
+                                : head_bytes + n * (size_t)n_ticks * sizeof(DeckTickDev);
         if (sl.host_cap < bytes) {
             if (sl.host) (void)hipHostFree(sl.host);
             sl.host = nullptr; sl.host_cap = 0;
@@ -242,39 +249,176 @@ void Deck::feed(Deck* const* decks, const uint32_t* nodes, size_t n, Graph& g, u
         }
         if (!sl.done) hip_check(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming), "hipEventCreate");
 
+        // plain decks take the first n_plain entries of DeckDev / DeckTickDev, in the order given; key-locked decks have descriptors of their own behind them
         DeckDev* dd = (DeckDev*)sl.host;
         DeckTickDev* td = (DeckTickDev*)((char*)sl.host + head_bytes);
+        KlDeckDev* kd = (KlDeckDev*)((char*)sl.host + plain_bytes);
+        KlTickDev* kt = (KlTickDev*)(kd + nk);
+        KlGrainIn* kg = (KlGrainIn*)(kt + nk * (size_t)n_ticks);
         std::vector<mx_deck_head> heads(n);
         std::vector<std::vector<mx_deck_tick>> recs(n);
+        std::vector<std::vector<mx_deck_grain>> grains(nk);
+        std::vector<uint64_t> clocks(nk);
         bool phase_varies = false;
+        size_t ip = 0, ik = 0, grain_at = 0;
         for (size_t i = 0; i < n; ++i) {
             Deck& d = *decks[i];
-            dd[i] = DeckDev{(const uint32_t*)d.track_.p, outs[i], (int64_t)d.n_frames_};
+            const bool kl = d.kl_on_;
+            if (!kl) dd[ip] = DeckDev{(const uint32_t*)d.track_.p, outs[i], (int64_t)d.n_frames_};
             mx_deck_head h = d.head_;
             recs[i].resize(n_ticks);
             std::vector<const Event*> at(d.sched_.empty() ? 0 : n_ticks, nullptr);
             for (const Event& e : d.sched_) at[e.tick] = &e;
+            uint64_t clock = kl && d.last_graph_ == &g ? d.kl_t_ : 0;   // (another graph restarts the grain clock)
+            const uint32_t hop = d.kl_.hop;
+            uint32_t next = 2;                                           // rec[] index of the next grain to start
             for (uint32_t t = 0; t < n_ticks; ++t) {
                 const Event* e = at.empty() ? nullptr : at[t];
                 mx_deck_tick& r = recs[i][t];
                 deck_plan(h, e && e->has_params ? &e->params : nullptr, e && e->has_seek ? &e->seek : nullptr, (uint32_t)spt, d.n_frames_, r, h);
-                const bool zero = !(r.flags & MX_DECK_TICK_PLAY) || (r.flags & (MX_DECK_TICK_BEFORE | MX_DECK_TICK_PAST));
-                td[i * (size_t)n_ticks + t] = DeckTickDev{r.pos_q32, r.step_q32, r.dstep_q32, (uint32_t)r.loop_in, (uint32_t)r.loop_len,
-                                                         zero ? (uint32_t)DECK_FORM_ZERO : (uint32_t)DECK_FORM_PLAY, r.bank};
-                if (!zero && deck_phase_varies(td[i * (size_t)n_ticks + t])) phase_varies = true;
+                if (!kl) {
+                    const bool zero = !(r.flags & MX_DECK_TICK_PLAY) || (r.flags & (MX_DECK_TICK_BEFORE | MX_DECK_TICK_PAST));
+                    td[ip * (size_t)n_ticks + t] = DeckTickDev{r.pos_q32, r.step_q32, r.dstep_q32, (uint32_t)r.loop_in, (uint32_t)r.loop_len,
+                                                              zero ? (uint32_t)DECK_FORM_ZERO : (uint32_t)DECK_FORM_PLAY, r.bank};
+                    if (!zero && deck_phase_varies(td[ip * (size_t)n_ticks + t])) phase_varies = true;
+                    continue;
+                }
+                KlTickDev& k = kt[ik * (size_t)n_ticks + t];
+                if (!(r.flags & MX_DECK_TICK_PLAY)) { k = KlTickDev{0, 0, 0, 0}; clock = 0; continue; }   // (a tick that is not playing restarts the grain clock)
+                const uint32_t m0 = (uint32_t)(clock & (hop - 1));
+                k = KlTickDev{m0, m0 ? next - 1 : next, (clock >> d.kl_log_hop_) == 0 ? 1u : 0u, 1u};
+                for (uint64_t fr = (hop - m0) & (hop - 1); fr < spt; fr += hop) {   // the grain starts of this tick
+                    int64_t a = deck_u(r.pos_q32, r.step_q32, r.dstep_q32, (int64_t)fr);
+                    if (r.flags & MX_DECK_TICK_LOOPING) a = deck_fold(a, r.loop_in * kOne, r.loop_len * kOne);
+                    const bool first = clock + fr == 0;
+                    grains[ik].push_back(mx_deck_grain{a, 0, t, (uint32_t)fr, 0, 0u, first ? (uint32_t)MX_DECK_GRAIN_FIRST : 0u, 0u});
+                    kg[grain_at + grains[ik].size() - 1] = KlGrainIn{a, first ? 1u : 0u, 0u};
+                    ++next;
+                }
+                clock += spt;
             }
             heads[i] = h;
+            if (kl) {
+                kd[ik] = KlDeckDev{(const uint32_t*)d.track_.p, outs[i], (int64_t)d.n_frames_, d.kl_.pitch_q32, nullptr, (int64_t*)d.kl_state_.p,
+                                   (const KlGrainIn*)((const char*)sl.dev.p + ((const char*)(kg + grain_at) - (const char*)sl.host)),
+                                   (uint32_t)grains[ik].size(), d.kl_log_hop_, d.kl_.overlap, d.kl_.radius, d.kl_bank_, 0u};
+                clocks[ik] = clock;
+                grain_at += grains[ik].size();
+                ++ik;
+            } else ++ip;
+        }
+        // the last things that can fail: room for the grain records of each key-locked deck.  A deck that changes graphs waits for the device once -- its state and
+        // record buffers may still be in use on the other graph's stream.
+        for (size_t i = 0, k = 0; i < n; ++i) {
+            Deck& d = *decks[i];
+            if (!d.kl_on_) continue;
+            if (d.last_graph_ && d.last_graph_ != &g) hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+            const size_t need = (2 + grains[k].size()) * sizeof(KlRec);
+            if (d.kl_rec_.bytes < need) {
+                d.fetch_grains();            // the last feed's records, before their buffer goes
+                d.kl_rec_.free_(); d.kl_rec_.alloc(2 * need);
+            }
+            kd[k++].rec = (KlRec*)d.kl_rec_.p;
         }
         for (size_t i = 0; i < n; ++i)
             if (decks[i]->load_pending_) { hip_check(hipStreamWaitEvent(g.stream(), decks[i]->loaded_, 0), "hipStreamWaitEvent"); decks[i]->load_pending_ = false; }
-        launch_upload(sl.dev.p, sl.host, bytes, g.stream());
-        launch_deck_feed((const DeckDev*)sl.dev.p, (const DeckTickDev*)((const char*)sl.dev.p + head_bytes), tables, (uint32_t)n, n_ticks, (uint32_t)spt, phase_varies, g.stream());
+        launch_upload(sl.dev.p, sl.host, nk ? (size_t)((const char*)(kg + grain_at) - (const char*)sl.host) : bytes, g.stream());
+        launch_deck_feed((const DeckDev*)sl.dev.p, (const DeckTickDev*)((const char*)sl.dev.p + head_bytes), tables, (uint32_t)ip, n_ticks, (uint32_t)spt, phase_varies, g.stream());
+        launch_deck_keylock((const KlDeckDev*)((const char*)sl.dev.p + plain_bytes), (const KlTickDev*)((const char*)sl.dev.p + plain_bytes + nk * sizeof(KlDeckDev)), tables,
+                            (uint32_t)nk, n_ticks, (uint32_t)spt, g.stream());
         hip_check(hipGetLastError(), "deck feed launch");
         hip_check(hipEventRecord(sl.done, g.stream()), "hipEventRecord");
         sl.pending = true;
-        feed_state.last.assign(td, td + n * (size_t)n_ticks); feed_state.last_spt = (uint32_t)spt;
-        for (size_t i = 0; i < n; ++i) { decks[i]->head_ = heads[i]; decks[i]->ticks_ = std::move(recs[i]); decks[i]->sched_.clear(); }
+        feed_state.last.assign(td, td + ip * (size_t)n_ticks); feed_state.last_spt = (uint32_t)spt;
+        feed_state.last_kl.clear(); feed_state.kl_searched = feed_state.kl_unsearched = 0;
+        for (size_t i = 0, k = 0; i < n; ++i) {
+            Deck& d = *decks[i];
+            d.head_ = heads[i]; d.ticks_ = std::move(recs[i]); d.sched_.clear(); d.last_graph_ = &g;
+            if (!d.kl_on_) { d.grains_.clear(); d.grains_fetched_ = true; continue; }
+            for (const mx_deck_grain& gr : grains[k]) ++((gr.flags & MX_DECK_GRAIN_FIRST) || !d.kl_.radius ? feed_state.kl_unsearched : feed_state.kl_searched);
+            for (uint32_t t = 0; t < n_ticks; ++t) feed_state.last_kl.push_back(FeedState::KlTick{kt[k * (size_t)n_ticks + t], d.kl_log_hop_, d.kl_.overlap});
+            d.kl_t_ = clocks[k]; d.grains_ = std::move(grains[k]); d.grains_fetched_ = d.grains_.empty();
+            ++k;
+        }
     } catch (...) { drop(); throw; }
+}
+
+// ---- key-lock ----
+void deck_keylock_check(const mx_deck_keylock& k) {
+    auto pow2 = [](uint32_t v) { return v && !(v & (v - 1)); };
+    if (k.pitch_q32 < kOne / 4 || k.pitch_q32 > kMaxStep) throw Error(MX_ERR_INVALID, "deck key-lock: pitch_q32 outside 2^30 .. 4 * 2^32");
+    if (!pow2(k.hop) || k.hop < 256 || k.hop > 8192) throw Error(MX_ERR_INVALID, "deck key-lock: hop is not a power of two in 256 .. 8192");
+    if (!pow2(k.overlap) || k.overlap < 16 || k.overlap > std::min<uint32_t>(k.hop / 2, 1024)) throw Error(MX_ERR_INVALID, "deck key-lock: overlap is not a power of two in 16 .. min(hop / 2, 1024)");
+    if (k.radius > 1024) throw Error(MX_ERR_INVALID, "deck key-lock: radius above 1024");
+    if (k._pad) throw Error(MX_ERR_INVALID, "deck key-lock: _pad must be 0");
+}
+
+void deck_keylock_search(const int16_t* x, uint64_t n_frames, int64_t C, int64_t A, uint32_t overlap, uint32_t radius, int32_t& delta, uint32_t& dist) {
+    const int64_t far = (int64_t)1 << 40;
+    if (!x) throw Error(MX_ERR_INVALID, "deck key-lock search: interleaved is NULL");
+    if (n_frames < 1 || n_frames > kMaxFrames) throw Error(MX_ERR_INVALID, "deck key-lock search: n_frames outside 1 .. 2^30");
+    if (overlap < 1 || overlap > 1024 || radius > 1024) throw Error(MX_ERR_INVALID, "deck key-lock search: overlap outside 1 .. 1024 or radius above 1024");
+    if (C < -far || C > far || A < -far || A > far) throw Error(MX_ERR_INVALID, "deck key-lock search: |C| or |A| above 2^40 frames");
+    auto s = [&](int64_t f) -> int32_t { return f < 0 || f >= (int64_t)n_frames ? 0 : (int32_t)x[2 * f] + (int32_t)x[2 * f + 1]; };
+    bool have = false;
+    // scanned in the tie order itself -- 0, -1, +1, -2, +2, ... -- so that a strictly smaller D is the only thing that replaces the best so far
+    for (int64_t q = 0; q <= (int64_t)radius; ++q)
+        for (int sgn = -1; sgn <= 1; sgn += 2) {
+            if (q == 0 && sgn > 0) continue;
+            const int64_t dl = sgn * q;
+            uint32_t D = 0;
+            for (uint32_t i = 0; i < overlap; ++i) { const int32_t v = s(C + i) - s(A + dl + i); D += (uint32_t)(v < 0 ? -v : v); }
+            if (!have || D < dist) { have = true; dist = D; delta = (int32_t)dl; }
+        }
+}
+
+void Deck::set_keylock(const mx_deck_keylock* k) {
+    if (k) {
+        deck_keylock_check(*k);
+        if (!kl_state_.p) { hip_check(hipSetDevice(device_), "hipSetDevice"); kl_state_.alloc(2 * sizeof(int64_t)); }
+        kl_ = *k;
+        kl_bank_ = k->pitch_q32 <= kOne ? 0u : 3 * k->pitch_q32 <= 4 * kOne ? 1u : k->pitch_q32 <= 2 * kOne ? 2u : 3u;
+        kl_log_hop_ = 0;
+        while ((1u << kl_log_hop_) < k->hop) ++kl_log_hop_;
+    }
+    kl_on_ = k != nullptr;
+    kl_t_ = 0;
+}
+
+void Deck::fetch_grains() {
+    if (grains_fetched_) return;
+    hip_check(hipSetDevice(device_), "hipSetDevice");
+    hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+    std::vector<KlRec> r(grains_.size());
+    hip_check(hipMemcpy(r.data(), (const KlRec*)kl_rec_.p + 2, r.size() * sizeof(KlRec), hipMemcpyDeviceToHost), "hipMemcpy(deck grains)");
+    for (size_t k = 0; k < r.size(); ++k) { grains_[k].g_q32 = r[k].g; grains_[k].delta = r[k].delta; grains_[k].dist = r[k].dist; }
+    grains_fetched_ = true;
+}
+
+void Deck::read_grains(uint32_t first, uint32_t n, mx_deck_grain* dst) {
+    if (first > grains_.size() || n > grains_.size() - first) throw Error(MX_ERR_INVALID, "deck: a window beyond the last feed's grains");
+    if (n && !dst) throw Error(MX_ERR_INVALID, "deck: dst is NULL");
+    if (!n) return;
+    fetch_grains();
+    std::memcpy(dst, grains_.data() + first, (size_t)n * sizeof(mx_deck_grain));
+}
+
+void Deck::debug_last_keylock(uint32_t out[4]) {
+    std::lock_guard<std::mutex> lock(feed_state.mu);
+    out[0] = feed_state.kl_searched; out[1] = feed_state.kl_unsearched; out[2] = out[3] = 0;
+    const uint32_t spt = feed_state.last_spt;
+    for (const FeedState::KlTick& k : feed_state.last_kl) {
+        if (!k.t.play) continue;
+        const uint32_t hop = 1u << k.log_hop;
+        for (uint32_t n0 = 0; n0 < spt; n0 += MX_DECK_CHUNK) {
+            const uint32_t a = k.t.m0 + n0, b = a + std::min<uint32_t>(MX_DECK_CHUNK, spt - n0) - 1;   // the chunk's clock, first and last lane
+            if ((a >> k.log_hop) != (b >> k.log_hop)) ++out[3];
+            bool fades = false;
+            for (uint32_t dj = a >> k.log_hop; dj <= (b >> k.log_hop); ++dj)   // per grain of the chunk, the smallest m is that of its first lane
+                if ((std::max(a, dj * hop) & (hop - 1)) < k.overlap && !(k.t.first0 && dj == 0)) fades = true;
+            if (fades) ++out[2];
+        }
+    }
 }
 
 void Deck::debug_last_feed(uint32_t out[6]) {

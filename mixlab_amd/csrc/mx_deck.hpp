@@ -48,7 +48,18 @@ __host__ __device__ inline DeckChunkPlan deck_chunk_plan(const DeckTickDev& t, u
     return p;
 }
 
+// ---- key-lock (the header's KEY-LOCK; mx_k_deck_keylock.hip) ----
+// what the two kernels know of one key-locked deck of a feed.  rec[0], rec[1]: the two grains before the feed's first (from `state`, which the search kernel reads at its
+// start and writes at its end); rec[2 + k]: grain k of grains[0 .. n_grains).
+struct KlGrainIn { int64_t a; uint32_t first, _pad; };
+struct KlRec { int64_t g; int32_t delta; uint32_t dist; };
+struct KlDeckDev { const uint32_t* track; float* out; int64_t n_frames, pitch; KlRec* rec; int64_t* state; const KlGrainIn* grains; uint32_t n_grains, log_hop, overlap, radius, bank, _pad; };
+// ... and of one tick of it: frame n has clock tt = m0 + n, lies in grain rec[gi0 + (tt >> log_hop)] at m = tt & (hop - 1); first0: grain rec[gi0] has no previous grain
+struct KlTickDev { uint32_t m0, gi0, first0, play; };
+
 // ---- host ----
+void deck_keylock_check(const mx_deck_keylock& k);                                   // throws Error(MX_ERR_INVALID) naming the rule
+void deck_keylock_search(const int16_t* interleaved, uint64_t n_frames, int64_t C, int64_t A, uint32_t overlap, uint32_t radius, int32_t& delta, uint32_t& dist);
 void deck_check(const mx_deck_params& p, uint64_t n_frames);                         // throws Error(MX_ERR_INVALID) naming the rule
 void deck_plan(const mx_deck_head& in, const mx_deck_params* params, const int64_t* seek, uint32_t spt, uint64_t n_frames, mx_deck_tick& tick, mx_deck_head& out);
 int64_t deck_step(uint32_t track_rate, uint32_t graph_rate, double speed);
@@ -67,8 +78,13 @@ public:
     int device() const { return device_; }
     static void feed(Deck* const* decks, const uint32_t* nodes, size_t n, Graph& g, uint32_t n_ticks);
     static void debug_last_feed(uint32_t out[6]);
+    void set_keylock(const mx_deck_keylock* k);                            // NULL: off.  Restarts the grain clock.
+    uint32_t grain_count() const { return (uint32_t)grains_.size(); }
+    void read_grains(uint32_t first, uint32_t n, mx_deck_grain* dst);      // waits for the device
+    static void debug_last_keylock(uint32_t out[4]);
 
 private:
+    void fetch_grains();
     struct Event { uint32_t tick; bool has_params, has_seek; mx_deck_params params; int64_t seek; };
     uint64_t n_frames_; int device_;
     DevBuf track_;
@@ -76,6 +92,14 @@ private:
     mx_deck_head head_{};
     std::vector<Event> sched_;          // at most one per tick, in no order
     std::vector<mx_deck_tick> ticks_;   // the last feed's records
+    // key-lock: the setting, the grain clock t (playing output frames since the last restart), and the graph of the last feed (another one restarts the clock)
+    bool kl_on_ = false; mx_deck_keylock kl_{}; uint32_t kl_bank_ = 0, kl_log_hop_ = 0;
+    uint64_t kl_t_ = 0;
+    const Graph* last_graph_ = nullptr;
+    DevBuf kl_state_;                   // g of the last two grains, 2 x int64: written and read by the search kernel only
+    DevBuf kl_rec_;                     // KlRec x (2 + the grains of the last feed)
+    std::vector<mx_deck_grain> grains_; // the last feed's grain records; g / delta / dist are fetched from kl_rec_ by read_grains
+    bool grains_fetched_ = true;
 };
 
 }  // namespace mx

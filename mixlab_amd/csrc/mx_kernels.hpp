@@ -342,5 +342,8 @@ void launch_resample(const ResampleDesc* d, uint32_t n, uint32_t max_taps, uint3
 struct DeckDev; struct DeckTickDev;
 void launch_deck_feed(const DeckDev* decks, const DeckTickDev* ticks, const float* tables, uint32_t n, uint32_t n_ticks, uint32_t spt,
                       bool phase_varies /* some playing tick's lanes differ in phase: the kernel with the bank in LDS */, hipStream_t s);
+// the key-locked decks of a feed (mx_deck.hpp, mx_k_deck_keylock.hip): the grain search, one workgroup per deck, then the render over n decks x n_ticks ticks x chunks
+struct KlDeckDev; struct KlTickDev;
+void launch_deck_keylock(const KlDeckDev* decks, const KlTickDev* ticks, const float* tables, uint32_t n, uint32_t n_ticks, uint32_t spt, hipStream_t s);
 
 }  // namespace mx

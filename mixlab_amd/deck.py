@@ -3,6 +3,10 @@
     deck = Deck(len(track) // 2); deck.load(track_i16)
     deck.set(step_q32=deck_step(44100, 48000, 1.08), flags=abi.DECK_PLAY)
     feed([deck], [source_node], graph, n_ticks); graph.run_ticks(first_tick, n_ticks)
+
+Key-lock (the header's KEY-LOCK) keeps the key while the step sets the tempo:
+
+    deck.set_keylock(keylock(pitch_q32=deck_step(44100, 48000, 1.0)))     # hop 1024, overlap 256, radius 512
 """
 from __future__ import annotations
 
@@ -11,7 +15,7 @@ import ctypes as C
 import numpy as np
 
 from . import abi
-from .abi import DeckHead, DeckParams, DeckTick, check, lib
+from .abi import DeckGrain, DeckHead, DeckKeylock, DeckParams, DeckTick, check, lib
 
 ONE = 1 << 32   # unity step / one track frame in Q32.32
 
@@ -56,6 +60,30 @@ def debug_last_feed() -> dict:
     return dict(zip(("ticks_zero", "ticks_stream", "ticks_gather", "chunks_zero", "chunks_stream", "chunks_gather"), (int(v) for v in out)))
 
 
+def keylock(pitch_q32=ONE, hop=1024, overlap=256, radius=512) -> DeckKeylock:
+    """key-lock settings; the defaults are the header's recommendation at 44.1 / 48 kHz"""
+    return DeckKeylock(int(pitch_q32), int(hop), int(overlap), int(radius), 0)
+
+
+def keylock_check(k: DeckKeylock) -> None:
+    """the key-lock setting rules alone (host only); raises MxError"""
+    check(lib.mx_deck_keylock_check(C.byref(k)))
+
+
+def keylock_search(interleaved_i16: np.ndarray, C_frame: int, A_frame: int, overlap: int, radius: int):
+    """the grain search rule alone (host only, pure): (delta, dist)"""
+    a = np.ascontiguousarray(interleaved_i16, dtype=np.int16).reshape(-1)
+    delta, dist = C.c_int32(), C.c_uint32()
+    check(lib.mx_deck_keylock_search(a.ctypes.data_as(C.c_void_p), a.size // 2, int(C_frame), int(A_frame), int(overlap), int(radius), C.byref(delta), C.byref(dist)))
+    return delta.value, dist.value
+
+
+def debug_last_keylock() -> dict:
+    out = (C.c_uint32 * 4)()
+    check(lib.mx_deck_debug_last_keylock(out))
+    return dict(zip(("grains_searched", "grains_unsearched", "chunks_fading", "chunks_straddling"), (int(v) for v in out)))
+
+
 class Deck:
     """Thin RAII wrapper of mx_deck_*."""
 
@@ -93,6 +121,23 @@ class Deck:
     def read_ticks(self, first: int, n: int) -> list[DeckTick]:
         arr = (DeckTick * max(1, n))()
         check(lib.mx_deck_read_ticks(self._h, int(first), int(n), arr))
+        return list(arr[:n])
+
+    def set_keylock(self, k: DeckKeylock | None = None, **kw):
+        """key-lock from the next feed on; set_keylock(None) with no keywords turns it off"""
+        k = k if k is not None else (keylock(**kw) if kw else None)
+        check(lib.mx_deck_set_keylock(self._h, C.byref(k) if k is not None else None))
+
+    def grain_count(self) -> int:
+        n = C.c_uint32()
+        check(lib.mx_deck_grain_count(self._h, C.byref(n)))
+        return n.value
+
+    def read_grains(self, first: int = 0, n: int | None = None) -> list[DeckGrain]:
+        """the grains that started in the last feed; waits for the feed's kernels"""
+        n = self.grain_count() - first if n is None else n
+        arr = (DeckGrain * max(1, n))()
+        check(lib.mx_deck_read_grains(self._h, int(first), int(n), arr))
         return list(arr[:n])
 
     def state(self) -> DeckHead:
