@@ -15,6 +15,7 @@ import video_scope_model as sm
 from mixlab_amd import ingest, video
 from mixlab_amd.workspace import Workspace
 from test_cpu_random_video import DIGEST, SEEDS
+from test_cpu_random_video_chain import grade_abi, matte_abi
 from test_gpu_video_graph import MATRIX
 from test_gpu_video_place import kp, pp, upload
 
@@ -22,14 +23,14 @@ pytestmark = pytest.mark.gpu
 
 
 @functools.lru_cache(maxsize=2)
-def scenario_of(seed):
-    return rv.scenario(seed)
+def scenario_of(seed, chain=False):
+    return rv.scenario(seed, chain=True) if chain else rv.scenario(seed)
 
 
 @functools.lru_cache(maxsize=2)
-def expected(seed, kind):
+def expected(seed, kind, chain=False):
     """shared between the parametrisations of a seed (they follow each other); never modified"""
-    sc = scenario_of(seed)
+    sc = scenario_of(seed, chain)
     return rv.expect(sc, rv.groupings(sc, kind))
 
 
@@ -103,6 +104,17 @@ def apply_event(g, sc, e, dev):
         video.graph_set_video_source_key(g, e["src"], kp(km.KeyP(**e["params"])) if e["params"] else None)
     elif op == "place":
         video.graph_set_video_source_place(g, e["src"], pp(pm.PlaceP(**e["params"])) if e["params"] else None)
+    elif op == "grade":
+        if e["params"] is None:
+            video.graph_set_video_source_grade(g, e["src"], None)
+        else:
+            p = rv.grade_p(e["params"])
+            lut = video.Lut(p.k, p.nodes) if p.nodes is not None else None       # a handle of the caller's own: the graph retains the lattice
+            video.graph_set_video_source_grade(g, e["src"], grade_abi(e["params"]), lut)
+            if lut is not None:
+                lut.release()                                                    # ... so it is let go of straight after the call, before any run
+    elif op == "matte":
+        video.graph_set_video_source_matte(g, e["src"], matte_abi(e["params"]) if e["params"] is not None else None)   # a wipe: through video.matte_wipe
     elif op == "band":
         b = e["params"] or dict(in_w=0, in_full_h=0, src_row0=0, slice_rows=0, full_w=0, full_h=0, row0=0, band_rows=0)
         video.graph_set_video_source_band(g, e["src"], b["in_w"], b["in_full_h"], b["src_row0"], b["slice_rows"], b["full_w"], b["full_h"], b["row0"], b["band_rows"])
@@ -119,12 +131,16 @@ def apply_event(g, sc, e, dev):
         raise AssertionError(op)
 
 
-def run_scenario(seed, grouping, inline, observe, monkeypatch):
+def run_scenario(seed, grouping, inline, observe, monkeypatch, chain=False):
     """Builds the graph of scenario `seed`, applies it run by run under `grouping` and compares, after every run, what the model expects.  observe "sinks": only
     what a program would read -- the RGBA sinks, the Monitor, the scope records, the multiview canvas and status: symbolic frames stay symbolic; "ports":
-    every video port is downloaded as well (which materialises it)."""
+    every video port is downloaded as well (which materialises it).  chain: the scenario of the chain family (tests/test_gpu_random_video_chain.py); there, batched
+    and with the ports read, the frame read from the first chain source's port is KEPT on every second run: a frame a caller holds is never rewritten, whatever
+    re-sets followed."""
     monkeypatch.setenv("MX_SCALE_INLINE", inline)
-    sc, want = scenario_of(seed), expected(seed, grouping)
+    sc, want = scenario_of(seed, chain), expected(seed, grouping, chain)
+    hold_port = next(((s, 0) for s, d in enumerate(sc["sources"]) if d.get("stages")), None) if (chain and grouping == "batched") else None
+    held_frames = []                                                # (run, frame, expected picture): the test, not the graph, holds it
     g = build(sc)
     keep, made = [], {}
 
@@ -175,10 +191,15 @@ def run_scenario(seed, grouping, inline, observe, monkeypatch):
                     held.append((i, canvas, r["mv"]["canvas"]))
         if observe == "ports":
             for (node, port), pic in r["ports"].items():
-                bad = frame_differs(video.graph_video_output(g, node, port), pic)
+                d = video.graph_video_output(g, node, port)
+                bad = frame_differs(d, pic)
                 assert not bad, f"{where}: tick {r['start'] + r['n'] - 1}: port ({node}, {port}): {bad}"
+                if (node, port) == hold_port and d is not None and i % 2 == 0:
+                    held_frames.append((i, d, pic))
     for i, canvas, planes in held:
         assert not planes_differ(canvas.download(), planes), f"seed {seed}: the canvas of run {i}, held by the caller, was rewritten: {planes_differ(canvas.download(), planes)}"
+    for i, d, pic in held_frames:
+        assert not frame_differs(d, pic), f"seed {seed}: the frame of run {i} on port {hold_port}, held by the caller, was rewritten: {frame_differs(d, pic)}"
     g.close()
 
 
