@@ -190,7 +190,7 @@ void Deck::read_ticks(uint32_t first, uint32_t n, mx_deck_tick* dst) const {
 // device buffer and read there by the feed kernel; the event recorded behind the feed kernel says when both are free again.  A slot is taken round-robin, so the host
 // waits only when kSlots feeds are in flight at once (and then for the oldest): a steady tick-by-tick host never does.
 namespace {
-struct Slot { void* host = nullptr; size_t host_cap = 0; DevBuf dev; hipEvent_t done = nullptr; bool pending = false; int device = -1; };
+struct Slot { void* host = nullptr; size_t host_cap = 0; DevBuf dev; hipEvent_t done = nullptr; bool pending = false; int device = -1; hipStream_t stream = nullptr; };
 constexpr int kSlots = 4;
 struct FeedState {
     std::mutex mu;
@@ -200,6 +200,19 @@ struct FeedState {
     std::vector<KlTick> last_kl; uint32_t kl_searched = 0, kl_unsearched = 0;   // ... and its key-locked ticks and grains, for mx_deck_debug_last_keylock
 } feed_state;
 }  // namespace
+
+// A slot's event remembers the stream it was last recorded on, and the runtime looks at that stream when the event is waited for or recorded again: an event must
+// not outlive it.  The graph whose stream goes away says so here (the stream still there, its work done): the slots it was the last to use give up their events.
+void deck_stream_retired(hipStream_t s) {
+    std::lock_guard<std::mutex> lock(feed_state.mu);
+    for (Slot& sl : feed_state.slots) {
+        if (!sl.done || sl.stream != s) continue;
+        (void)hipSetDevice(sl.device);
+        if (sl.pending) (void)hipEventSynchronize(sl.done);
+        (void)hipEventDestroy(sl.done);
+        sl.done = nullptr; sl.pending = false; sl.stream = nullptr;
+    }
+}
 
 void Deck::feed(Deck* const* decks, const uint32_t* nodes, size_t n, Graph& g, uint32_t n_ticks) {
     auto drop = [&] { for (size_t i = 0; i < n; ++i) if (decks && decks[i]) decks[i]->sched_.clear(); };
@@ -328,7 +341,7 @@ void Deck::feed(Deck* const* decks, const uint32_t* nodes, size_t n, Graph& g, u
                             (uint32_t)nk, n_ticks, (uint32_t)spt, g.stream());
         hip_check(hipGetLastError(), "deck feed launch");
         hip_check(hipEventRecord(sl.done, g.stream()), "hipEventRecord");
-        sl.pending = true;
+        sl.pending = true; sl.stream = g.stream();
         feed_state.last.assign(td, td + ip * (size_t)n_ticks); feed_state.last_spt = (uint32_t)spt;
         feed_state.last_kl.clear(); feed_state.kl_searched = feed_state.kl_unsearched = 0;
         for (size_t i = 0, k = 0; i < n; ++i) {

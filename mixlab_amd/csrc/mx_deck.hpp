@@ -64,6 +64,7 @@ void deck_check(const mx_deck_params& p, uint64_t n_frames);                    
 void deck_plan(const mx_deck_head& in, const mx_deck_params* params, const int64_t* seek, uint32_t spt, uint64_t n_frames, mx_deck_tick& tick, mx_deck_head& out);
 int64_t deck_step(uint32_t track_rate, uint32_t graph_rate, double speed);
 const float* deck_tables_host();                                                       // MX_DECK_BANKS x DECK_BANK_FLOATS, computed once
+void deck_stream_retired(hipStream_t s);                                               // the stream is going away: the feed's staging slots last used on it let go of it
 
 class Deck {
 public:

@@ -2,6 +2,7 @@
 #include <chrono>
 
 #include "mx_engine.hpp"
+#include "mx_deck.hpp"
 
 #include <cstdio>
 
@@ -529,6 +530,7 @@ Graph::~Graph() {
     for (Stage& st : stage_) { if (st.done) (void)hipEventDestroy(st.done); if (st.host) (void)hipHostFree(st.host); }
     // the descriptor ring launch_video_batch keeps per stream goes with a stream this graph OWNS; a caller's stream may be shared with other
     // graphs / scalers that are launching on it right now (their ring must not be freed under them): its ring lives as long as the process
+    if (stream_) deck_stream_retired(stream_);   // (a caller's stream too: the caller may destroy it once the graph is gone)
     if (own_stream_ && stream_) { video_stream_retired(stream_); multiview_stream_retired(stream_); (void)hipStreamDestroy(stream_); }
 }
 

@@ -132,32 +132,43 @@ def _cases():
     return out
 
 
+STEP_POOL = [0, ONE, -ONE, frames(0.92), frames(1.08), -frames(1.5), EDGE1, EDGE1 + 1, 2 * ONE + 1, 4 * ONE, -4 * ONE, frames(0.5), 1]
+SLEW_POOL = [0, 0, 1, 1 << 24, frames(1.0) // 2000, frames(2.0) // 600]
+
+
+def draw_event(rng, n_frames: int, loop, first: bool):
+    """one tick's draw of the command stream: ((Params or None, seek or None) or None for a tick without an event, the loop now set).  `first` forces an event with
+    params and a seek (a deck's very first tick)"""
+    r = rng.random()
+    if r < 0.45 and not first:
+        return None, loop
+    params = seek = None
+    if r < 0.85 or first:
+        toggle = rng.random()
+        if toggle < 0.3:
+            a = int(rng.integers(0, max(1, n_frames - 1)))
+            loop = (a, int(rng.integers(a + 1, min(n_frames, a + 1 + int(rng.choice([1, 3, 40, 600, 3000]))) + 1)))
+        elif toggle < 0.5:
+            loop = None
+        slew = int(rng.choice(SLEW_POOL))
+        params = play(int(rng.choice(STEP_POOL)), slew=slew, loop=loop, on=rng.random() > 0.1)
+    if r >= 0.7 or first:
+        where = rng.random()
+        seek = frames(float(rng.uniform(-60, n_frames + 60))) if where < 0.7 else frames(float(rng.uniform(loop[0], loop[1]))) if loop else frames(n_frames + 3000.5)
+    return (params, seek), loop
+
+
 def random_stream(seed: int, n_frames: int, n_feeds: int, max_ticks: int) -> list:
     """feeds of 1 .. max_ticks ticks with sets, seeks, scheduled events and loop toggles at random ticks"""
     rng = np.random.default_rng(seed)
     feeds, loop = [], None
-    step_pool = [0, ONE, -ONE, frames(0.92), frames(1.08), -frames(1.5), EDGE1, EDGE1 + 1, 2 * ONE + 1, 4 * ONE, -4 * ONE, frames(0.5), 1]
     for _f in range(n_feeds):
         n_ticks = int(rng.integers(1, max_ticks + 1))
         events = []
         for t in range(n_ticks):
-            r = rng.random()
-            if r < 0.45 and not (_f == 0 and t == 0):
-                continue
-            params = seek = None
-            if r < 0.85 or (_f == 0 and t == 0):
-                toggle = rng.random()
-                if toggle < 0.3:
-                    a = int(rng.integers(0, max(1, n_frames - 1)))
-                    loop = (a, int(rng.integers(a + 1, min(n_frames, a + 1 + int(rng.choice([1, 3, 40, 600, 3000]))) + 1)))
-                elif toggle < 0.5:
-                    loop = None
-                slew = int(rng.choice([0, 0, 1, 1 << 24, frames(1.0) // 2000, frames(2.0) // 600]))
-                params = play(int(rng.choice(step_pool)), slew=slew, loop=loop, on=rng.random() > 0.1)
-            if r >= 0.7 or (_f == 0 and t == 0):
-                where = rng.random()
-                seek = frames(float(rng.uniform(-60, n_frames + 60))) if where < 0.7 else frames(float(rng.uniform(loop[0], loop[1]))) if loop else frames(n_frames + 3000.5)
-            events.append((t, params, seek))
+            ev, loop = draw_event(rng, n_frames, loop, _f == 0 and t == 0)
+            if ev is not None:
+                events.append((t, *ev))
         feeds.append(Feed(n_ticks, events))
     return feeds
 

@@ -166,22 +166,31 @@ CHUNK = dc.CHUNK
 def keylock_counts(case: KCase, results) -> dict:
     """the four numbers summed over the feeds of a case: results = run_model(case, ...).  A chunk fades when a frame of it has m < overlap in a grain that has a
     previous one; it straddles when a grain starts after its first frame.  The clock is walked as the header says."""
-    c = dict.fromkeys(("grains_searched", "grains_unsearched", "chunks_fading", "chunks_straddling"), 0)
+    c = dict.fromkeys(COUNT_KEYS, 0)
     kl, t = None, 0
     for f, (_s, recs, grains) in zip(case.feeds, results):
         if f.keylock != KEEP:
             kl, t = f.keylock, 0
         if kl is None:
             continue
-        for g in grains:
-            c["grains_unsearched" if g.flags & 1 or kl.radius == 0 else "grains_searched"] += 1
-        for r in recs:
-            if not r.flags & 1:
-                t = 0
-                continue
-            for n0 in range(0, case.spt, CHUNK):
-                ts = np.arange(t + n0, t + min(n0 + CHUNK, case.spt))
-                c["chunks_fading"] += bool(np.any((ts % kl.hop < kl.overlap) & (ts >= kl.hop)))
-                c["chunks_straddling"] += bool(np.any(ts[1:] % kl.hop == 0))
-            t += case.spt
+        t = count_feed(c, kl, t, recs, grains, case.spt)
     return c
+
+
+COUNT_KEYS = ("grains_searched", "grains_unsearched", "chunks_fading", "chunks_straddling")
+
+
+def count_feed(c: dict, kl: Keylock, t: int, recs, grains, spt: int) -> int:
+    """adds one feed of a deck key-locked with kl to the four numbers; t is the deck's clock as the feed begins.  -> the clock after it"""
+    for g in grains:
+        c["grains_unsearched" if g.flags & 1 or kl.radius == 0 else "grains_searched"] += 1
+    for r in recs:
+        if not r.flags & 1:
+            t = 0
+            continue
+        for n0 in range(0, spt, CHUNK):
+            ts = np.arange(t + n0, t + min(n0 + CHUNK, spt))
+            c["chunks_fading"] += bool(np.any((ts % kl.hop < kl.overlap) & (ts >= kl.hop)))
+            c["chunks_straddling"] += bool(np.any(ts[1:] % kl.hop == 0))
+        t += spt
+    return t

@@ -87,6 +87,10 @@ class KeylockModel:
     def schedule(self, tick, params=None, seek=None):
         self.deck.schedule(tick, params, seek)
 
+    def load(self, first_frame: int, interleaved_i16):
+        self.deck.load(first_frame, interleaved_i16)
+        self.s = sums(self.deck.track, self.mis)
+
     def feed(self, n_ticks: int, spt: int, graph=0):
         """(float32 [n_ticks * spt * 2], [Tick], [Grain])"""
         d, k, mis = self.deck, self.kl, self.mis

@@ -111,6 +111,7 @@ class RandomTaps:
         self.ws, self.shape, self.types, self.frames, self.rates = ws, shape, types, frames, rates
         self.spt, self.sets, self.fault, self.cap = ws.spt, tuple(tap_sets), fault, cap
         self.dup, self.resampled = list(dup), list(resampled)
+        self.also = []                              # further pools every set takes a port of (the deck sessions: the stereo source ports)
         self.cand = {name: [pt for pt in common if self.accepts(name, pt)] for name in self.sets}
         for name in self.sets:
             out = sorted({self.rates[pt] for pt in common if pt not in self.cand[name] and name != "stereo"})
@@ -229,7 +230,9 @@ class RandomTaps:
         need(self.resampled)
         need([pt for pt in cand if self.types[pt[0]][pt[1]] == MONO])
         need([pt for pt in cand if self.types[pt[0]][pt[1]] == STEREO])
-        cap = min(self.cap, CAPS.get(name, self.cap))
+        for pool in self.also:
+            need(pool)
+        cap =min(self.cap, CAPS.get(name, self.cap))
         for pt in keep:
             if len(chosen) < cap and pt not in chosen:
                 chosen.append(pt)

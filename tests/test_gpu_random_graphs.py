@@ -13,6 +13,7 @@ between runs, level meters on a random third of the ports (fed the ORACLE's samp
 mode.  What is under test is the scheduler: run order, levels, sample-rate domains, launch groups, the fusion planner's
 conditions, slab layout, spans cut by scheduled updates, state carry.  The last tests put all seven audio tap sets on those graphs
 (tests/random_taps.py): what is under test there is the shared tap host and the compiler's materialisation of tapped ports.
+tests/test_gpu_random_decks.py runs the same graphs with decks on their stereo sources (run_full_graph(decks=...), tests/random_decks.py).
 """
 import struct
 from fractions import Fraction
@@ -258,10 +259,18 @@ def _full_graph(seed, sr, tps):
             continue
         if pool:
             ws.connect(*pool[int(rng.integers(0, len(pool)))], n, port)
+    drop_refused_edges(ws, intended)
+    return ws, sources
+
+
+def drop_refused_edges(ws, intended):
+    """drops one forward edge of the first module the engine would refuse (engine_domains), again and again until the graph builds; `intended`
+    is the domain each module was meant to live in (the base one where it names none).  No draws."""
+    base = Fraction(1)
     while True:
         _order, dom, bad = engine_domains(ws)
         if bad is None:
-            return ws, sources
+            return
         n, why = bad
         kind, params = ws.nodes[n]
         conn = [(k, ws._conn[(n, k)]) for k in range(n_inputs(kind, params)) if (n, k) in ws._conn]
@@ -415,7 +424,7 @@ def od_args(p):
     return p.channels, (None if p.left < 0 else p.left), (None if p.right < 0 else p.right)
 
 
-def run_full_graph(shape_id, seed, builds, flags, first_tick=0, tap_sets=("meters",), n_runs=(3, 5), fault=None, collect=None):
+def run_full_graph(shape_id, seed, builds, flags, first_tick=0, tap_sets=("meters",), n_runs=(3, 5), fault=None, collect=None, decks=None):
     """random_graph(full=True) through n_runs[0] .. n_runs[1] - 1 runs of 1-6 ticks from `first_tick` on every build in `builds` against the
     oracle (in whatever mode it is in): every materialised port, meter records and OutputDevice hand-offs, bit for bit.
 
@@ -423,11 +432,16 @@ def run_full_graph(shape_id, seed, builds, flags, first_tick=0, tap_sets=("meter
     tap_sets (random_taps.SETS: all seven) go through tests/random_taps.py: every set on ports, with parameters and at re-sets of its own,
     one run (not the last) one tick long, every set's records of every build against its model fed the oracle's samples.  `builds` may be
     empty: then only the oracle and the models run (the fusion plan predicted, not read from a built graph), the expected records of
-    every run are appended to `collect`, `fault` is random_taps' switch, and the RandomTaps is returned (tests/test_cpu_random_graphs.py)."""
+    every run are appended to `collect`, `fault` is random_taps' switch, and the RandomTaps is returned (tests/test_cpu_random_graphs.py).
+
+    decks = random_decks.session(...): further stereo sources are grafted into the graph and every stereo source gets a deck, fed in most runs
+    and written by the host in the others (tests/random_decks.py); each build's tick records, grain records, debug counts and deck state are
+    compared with the models' per run, and the DeckSession is returned (its `taps` the RandomTaps, if any).  None: nothing of that, not a draw."""
     legacy = tuple(tap_sets) == ("meters",)
     assert legacy or (fault is None and collect is None) or not builds
     shape = by_id(shape_id)
     ws, sources = random_graph(seed, shape.sample_rate, shape.ticks_per_second, full=True)
+    ds = decks(seed, ws, sources, shape) if decks is not None else None   # (grafts its sources into ws before anything is built)
     spt = ws.spt
     rng = np.random.default_rng(7000 + seed)
     og = oracle.OracleGraph(ws)
@@ -512,6 +526,11 @@ def run_full_graph(shape_id, seed, builds, flags, first_tick=0, tap_sets=("meter
         _order, dom, _bad = engine_domains(ws)
         rates = {(n, p): float(shape.sample_rate) * dom[n].numerator / dom[n].denominator for (n, p) in frames}   # as TapHost's users compute it
         ts = RandomTaps(seed, ws, shape, types, frames, rates, common, dup, resampled, n_runs, tap_sets, fault)
+    if ds is not None:
+        ds.start(n_runs, graphs)
+        ds.taps = None if legacy else ts
+        if not legacy:                   # every set takes a deck's port: tempo and tonality of a deck are the pairing the README describes
+            ts.also.append([(n, 0) for n in ds.nodes if (n, 0) in common])
     for run in range(n_runs):
         L = int(rng.integers(1, MAX_RUN + 1))
         if not legacy:
@@ -541,6 +560,9 @@ def run_full_graph(shape_id, seed, builds, flags, first_tick=0, tap_sets=("meter
                 for k in sorted(set(rng.integers(0, L, size=int(rng.integers(1, 3))).tolist())):
                     events.setdefault(k, []).append((n, random_params(rng, ws, n)))
         data = {n: (synth.noise(9000 + 97 * seed + 13 * run + n, L * spt * ty) * np.float32(1.5)).astype(np.float32) for (n, ty) in sources}
+        if ds is not None:               # the deck-fed sources hold what the decks' models play
+            ds.before_run(run, L)
+            data.update(ds.expect_run())
         # the oracle, tick by tick; the models take the oracle's samples
         want, want_meters, want_od = {}, [], {od: ([], []) for od in ods}
         for k in range(L):
@@ -563,16 +585,24 @@ def run_full_graph(shape_id, seed, builds, flags, first_tick=0, tap_sets=("meter
             want_taps = ts.expect_run(L, [{pt: want[pt][k] for pt in frames} for k in range(L)])
             if collect is not None:
                 collect.append({"run": run, "ticks": L, "want": want_taps})
+        if ds is not None and collect is not None:
+            collect.append({"run": run, "ticks": L, "ports": {pt: b"".join(x.tobytes() for x in want[pt]) for pt in frames}, "decks": ds.want,
+                            "taps": {} if legacy else {name: list(ts.ports[name]) for name in ts.sets}})
         for name, g in graphs.items():
             step = 1 if name == "ticked" else L
             got, got_meters, got_od, got_taps = {}, [], {od: [[], []] for od in ods}, []
             for k0 in range(0, L, step):
                 for (n, ty) in sources:
-                    g.write_source(n, data[n][k0 * spt * ty:(k0 + step) * spt * ty], step)
+                    if ds is None or not ds.fed(n):
+                        g.write_source(n, data[n][k0 * spt * ty:(k0 + step) * spt * ty], step)
                 for k in range(k0, k0 + step):
                     for (n, p) in events.get(k, []):
                         g.schedule_params(n, k - k0, p)
+                if ds is not None:
+                    ds.feed(name, g, k0, step)
                 g.run_ticks(tick + k0, step)
+                if ds is not None:
+                    ds.read(name, k0, step)
                 for pt in ports[name]:
                     got.setdefault(pt, []).append(g.read_output(*pt, step, types[pt[0]][pt[1]] == STEREO, rate=(frames[pt], spt)))
                 if legacy:
@@ -599,14 +629,19 @@ def run_full_graph(shape_id, seed, builds, flags, first_tick=0, tap_sets=("meter
                 a, b = np.concatenate(got_od[od][0]), np.concatenate(want_od[od][0])
                 assert a.size == b.size and np.array_equal(bits(a), bits(b)), f"{what}: OutputDevice {od} hand-off differs"
                 assert got_od[od][1] == want_od[od][1], f"{what}: OutputDevice {od} records {got_od[od][1]} != {want_od[od][1]}"
+            if ds is not None:
+                d = ds.difference(name)
+                assert d is None, f"{what}: {d}"
         tick += L
     if legacy and collect is not None:
         collect.append({"rng": rng.bit_generator.state["state"]})   # every draw of this function's stream went as it always did
+    if ds is not None:
+        ds.close()
     if not legacy:
         if "fused" in graphs:
             for set_name in ts.sets:
                 assert ts.tapped[set_name] & set(dup), f"seed {seed}: no {set_name} tap ever sat on a dup-stored port"
-        return ts
+    return ds if ds is not None else None if legacy else ts
 
 
 @pytest.mark.parametrize("shape_id,seed", FULL_SEEDS, ids=[f"{s}-{n}" for s, n in FULL_SEEDS])
