@@ -739,7 +739,9 @@ int mx_graph_performance_info(mx_graph* g, mx_performance_info* info, uint64_t* 
  * old_node_of_new[i] = index in `old_graph` of the module that is node i of `new_graph`, or -1 for a new module
  * (EqThree poles and delay line, Envelope state, FIR / resampler history, Plotter count, VideoMixer stored frames and
  * scalers, pending video sources).  Kinds must match (MX_ERR_TYPE).  VideoMixers are MOVED: destroy `old_graph`
- * afterwards, do not run it. */
+ * afterwards, do not run it.  A FIR / resampler whose length changed starts from silence.  A module that a graph never runs
+ * (it sits in a cycle that feeds no terminal module, src/engine.rs:428-430) persists like any other: its state waits, from
+ * edit to edit, until a graph runs it again. */
 int mx_graph_adopt_state(mx_graph* new_graph, mx_graph* old_graph, const int32_t* old_node_of_new, size_t n);
 
 /* Ingest re-blocking (StreamInput::run_tick, src/module/stream_input.rs:92-124): decoded audio arrives as i16 frames of
@@ -866,7 +868,8 @@ int mx_deck_debug_last_feed(uint32_t out[6]);
  * CLOCK      a key-locked deck counts its PLAYING output frames in t.  Grain j starts at t = j * H, which is some frame n of some tick of some feed; its nominal
  *            position is a_j = u'(n) of that tick (the folded position of POSITION / A TICK above).  The clock restarts -- t = 0, and grain 0 has no previous grain --
  *            at creation, at every mx_deck_set_keylock (also one that repeats the setting, and NULL), after any tick that is not playing, and when the deck is fed
- *            into another graph (another mx_graph handle) than its last feed was.  A seek does NOT restart it: the cross-fade then runs from the old place to the
+ *            into another graph (another mx_graph handle) than its last feed was -- a graph that took over that graph's state with mx_graph_adopt_state is not
+ *            another graph: a topology edit does not restart the clock.  A seek does NOT restart it: the cross-fade then runs from the old place to the
  *            new one, a click-free cue jump.  Neither does a change of step, a loop, nor a BEFORE / PAST tick.  All of this the host can compute.
  * POSITION   a grain with no previous grain has g_j = a_j, delta = 0, dist = 0.  Otherwise, with c = g_(j-1) + H * p (where the previous grain would continue),
  *            C = c >> 32, A = a_j >> 32 (arithmetic shifts), s[f] = L[f] + R[f] of the raw int16 track and 0 outside [0, n_frames):

@@ -282,7 +282,7 @@ void Deck::feed(Deck* const* decks, const uint32_t* nodes, size_t n, Graph& g, u
             recs[i].resize(n_ticks);
             std::vector<const Event*> at(d.sched_.empty() ? 0 : n_ticks, nullptr);
             for (const Event& e : d.sched_) at[e.tick] = &e;
-            uint64_t clock = kl && d.last_graph_ == &g ? d.kl_t_ : 0;   // (another graph restarts the grain clock)
+            uint64_t clock = kl && d.last_lineage_ == g.lineage() ? d.kl_t_ : 0;   // (another graph restarts the grain clock; one that adopted the last one's state is not another)
             const uint32_t hop = d.kl_.hop;
             uint32_t next = 2;                                           // rec[] index of the next grain to start
             for (uint32_t t = 0; t < n_ticks; ++t) {
@@ -346,7 +346,7 @@ void Deck::feed(Deck* const* decks, const uint32_t* nodes, size_t n, Graph& g, u
         feed_state.last_kl.clear(); feed_state.kl_searched = feed_state.kl_unsearched = 0;
         for (size_t i = 0, k = 0; i < n; ++i) {
             Deck& d = *decks[i];
-            d.head_ = heads[i]; d.ticks_ = std::move(recs[i]); d.sched_.clear(); d.last_graph_ = &g;
+            d.head_ = heads[i]; d.ticks_ = std::move(recs[i]); d.sched_.clear(); d.last_graph_ = &g; d.last_lineage_ = g.lineage();
             if (!d.kl_on_) { d.grains_.clear(); d.grains_fetched_ = true; continue; }
             for (const mx_deck_grain& gr : grains[k]) ++((gr.flags & MX_DECK_GRAIN_FIRST) || !d.kl_.radius ? feed_state.kl_unsearched : feed_state.kl_searched);
             for (uint32_t t = 0; t < n_ticks; ++t) feed_state.last_kl.push_back(FeedState::KlTick{kt[k * (size_t)n_ticks + t], d.kl_log_hop_, d.kl_.overlap});

@@ -97,6 +97,7 @@ private:
     bool kl_on_ = false; mx_deck_keylock kl_{}; uint32_t kl_bank_ = 0, kl_log_hop_ = 0;
     uint64_t kl_t_ = 0;
     const Graph* last_graph_ = nullptr;
+    uint64_t last_lineage_ = 0;               // Graph::lineage() of that feed: a graph that adopted the last one's state is the same graph to the grain clock
     DevBuf kl_state_;                   // g of the last two grains, 2 x int64: written and read by the search kernel only
     DevBuf kl_rec_;                     // KlRec x (2 + the grains of the last feed)
     std::vector<mx_deck_grain> grains_; // the last feed's grain records; g / delta / dist are fetched from kl_rec_ by read_grains

@@ -1464,6 +1464,17 @@ std::vector<Graph::StateLoc> Graph::state_locs(uint32_t id) const {
     return out;
 }
 
+size_t Graph::state_bytes(uint32_t id) const {
+    const Node& n = nodes_[id];
+    switch (n.kind) {
+    case MX_KIND_EQ_THREE: return sizeof(EqState);
+    case MX_KIND_ENVELOPE: return sizeof(EnvState);
+    case MX_KIND_FIR: { mx_fir_params q; std::memcpy(&q, n.params.data(), sizeof q); return (size_t)q.n_taps * sizeof(float2); }
+    case MX_KIND_RESAMPLE: { mx_resample_params q; std::memcpy(&q, n.params.data(), sizeof q); return (size_t)q.taps_per_phase * sizeof(float2); }
+    default: return 0;
+    }
+}
+
 void Graph::adopt_state(Graph& old, const int32_t* old_of_new, size_t n) {
     if (n != nodes_.size()) throw Error(MX_ERR_INVALID, "old_node_of_new must have one entry per node of the new graph");
     if (n && !old_of_new) throw Error(MX_ERR_INVALID, "old_node_of_new is NULL");
@@ -1474,6 +1485,7 @@ void Graph::adopt_state(Graph& old, const int32_t* old_of_new, size_t n) {
         if (old.nodes_[j].kind != nodes_[i].kind) throw Error(MX_ERR_TYPE, "a module cannot change kind across a topology edit");
     }
     old.sync(); sync();
+    lineage_ = old.lineage_;   // to a key-locked deck this graph is the old one: its grain clock goes on (mx_deck_feed)
     hip_check(hipSetDevice(device_), "hipSetDevice");
     std::vector<CopyJob> jobs;   // thousands of small states (a 1024-strip graph: 2048 of 24 - 136 bytes): one launch, not one copy each
     for (size_t i = 0; i < n; ++i) {
@@ -1483,6 +1495,20 @@ void Graph::adopt_state(Graph& old, const int32_t* old_of_new, size_t n) {
         for (size_t k = 0; k < a.size() && k < b.size(); ++k)
             if (a[k].bytes == b[k].bytes && a[k].bytes)   // a filter whose length changed starts from silence
                 jobs.push_back(CopyJob{a[k].p, b[k].p, a[k].bytes});
+        // A module outside the run order (a cycle that feeds no terminal module) is served by no launch and has no state on the device, but
+        // it persists like any other: what it carried waits on the host until an edit brings it back into the order.
+        Node& nn = nodes_[i]; const Node& on = old.nodes_[j];
+        if (a.empty() && state_bytes((uint32_t)i)) {
+            if (!b.empty()) {
+                nn.parked.resize(b[0].bytes);
+                hip_check(hipMemcpy(nn.parked.data(), b[0].p, b[0].bytes, hipMemcpyDeviceToHost), "hipMemcpy(parked state)");
+            } else {
+                nn.parked = on.parked;
+            }
+            if (nn.parked.size() != state_bytes((uint32_t)i)) nn.parked.clear();   // a filter whose length changed starts from silence
+        } else if (!a.empty() && b.empty() && on.parked.size() == a[0].bytes && a[0].bytes) {
+            hip_check(hipMemcpy(a[0].p, on.parked.data(), a[0].bytes, hipMemcpyHostToDevice), "hipMemcpy(parked state)");
+        }
     }
     DevBuf job_buf;
     if (!jobs.empty()) {

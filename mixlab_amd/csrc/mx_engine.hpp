@@ -41,6 +41,7 @@ struct Node {
     uint32_t in_dom_num = 1, in_dom_den = 1;  // ... of the input ports
     uint32_t slot = 0;                        // index inside its (level, kind) group
     int group = -1;
+    std::vector<uint8_t> parked;              // the carried state of a module no launch of this graph serves (it is outside the run order): kept on the host from one topology edit to the next
     int sub_key = 0;                          // EQ_THREE: 1 + the epilogue mode the graph compiler gave the node (launch groups are of one mode); 0 otherwise
     // parameter updates queued for ticks inside the next run (Engine::client_update between two ticks, src/engine.rs:192-214)
     struct SchedEv { uint32_t tick; std::vector<uint8_t> params; };
@@ -115,6 +116,8 @@ public:
     size_t cap_frames() const override { return cap_frames_; }
     const std::vector<uint32_t>& run_order() const { return order_; }
     hipStream_t stream() const override { return stream_; }
+    // what a deck takes for "the same graph": unique per built graph, and taken over by the graph that adopts this one's state (a topology edit)
+    uint64_t lineage() const { return lineage_; }
     int device() const override { return device_; }
     uint32_t ticks_per_second() const { return tps_; }
     hipStream_t tail_stream() { if (tail_gi_ >= 0) flush_deferred_tail(false); return tail_gi_ >= 0 ? tail_stream_ : nullptr; }   // MX_FLAG_OVERLAP_TAIL; asking for it releases a held tail launch: what the caller orders after the stream then includes the last run's
@@ -206,6 +209,9 @@ public:
 private:
     struct StateLoc { void* p; size_t bytes; };
     std::vector<StateLoc> state_locs(uint32_t node) const;
+    uint64_t lineage_ = next_lineage();
+    static uint64_t next_lineage() { static std::atomic<uint64_t> n{0}; return ++n; }
+    size_t state_bytes(uint32_t node) const;   // what state_locs(node) holds where a launch serves the node, from its kind and params alone
     void plan_fusion();
     void layout_slab();
     void build_descriptors();

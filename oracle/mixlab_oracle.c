@@ -346,6 +346,7 @@ typedef struct {
     uint32_t source_ring;  /* 0: `source` is this tick's block; R > 0: `source` holds R ticks and tick t reads block t mod R */
     uint32_t dom_num, dom_den, in_dom_num, in_dom_den;   /* sample-rate domain (Resample changes it) */
     float* hist;           /* Fir / Resample carried input frames */
+    uint32_t hist_taps;    /* the length they are carried for: Fir n_taps, Resample taps_per_phase (hist holds 2 floats each) */
     int ran;               /* produced output this tick (back-edges read Disconnected) */
 } onode;
 
@@ -425,6 +426,10 @@ orc_graph* orc_graph_build(const orc_node* nodes, size_t n_nodes, const orc_edge
         n->plot.count = 0;
         n->plot_l = (float*)calloc(g->spt, sizeof(float));
         n->plot_r = (float*)calloc(g->spt, sizeof(float));
+        /* the carried input frames: every Fir / Resample has them, also one the run order leaves out (it persists across a topology edit) */
+        if (n->kind == ORC_KIND_FIR && n->params_len >= 8) n->hist_taps = ((const uint32_t*)n->params)[0];
+        if (n->kind == ORC_KIND_RESAMPLE && n->params_len >= 16) n->hist_taps = ((const uint32_t*)n->params)[2];
+        if (n->hist_taps) n->hist = (float*)calloc(2 * (size_t)n->hist_taps, sizeof(float));
     }
     for (size_t e = 0; e < n_edges; e++) {
         const orc_edge* ed = &edges[e];
@@ -466,9 +471,7 @@ orc_graph* orc_graph_build(const orc_node* nodes, size_t n_nodes, const orc_edge
             uint64_t a = (uint64_t)n->in_dom_num * h[0], b = (uint64_t)n->in_dom_den * h[1], x = a, y = b;
             while (y) { uint64_t t = x % y; x = y; y = t; }
             n->dom_num = (uint32_t)(a / x); n->dom_den = (uint32_t)(b / x);
-            n->hist = (float*)calloc(2 * (size_t)h[2], sizeof(float));
         }
-        if (n->kind == ORC_KIND_FIR) n->hist = (float*)calloc(2 * (size_t)((const uint32_t*)n->params)[0], sizeof(float));
     }
     free(pos);
     for (size_t i = 0; i < n_nodes; i++) {
@@ -623,4 +626,49 @@ int orc_graph_plotter_indication(const orc_graph* g, uint32_t node, float* left,
 size_t orc_graph_run_order(const orc_graph* g, uint32_t* order, size_t cap) {
     for (size_t i = 0; i < g->n_order && i < cap; i++) order[i] = g->order[i];
     return g->n_order;
+}
+
+/* Topology edit (include/mixlab_gpu.h, mx_graph_adopt_state): the edited graph is built anew and takes over the state of every module that
+ * survives -- EqThree poles and delay line, Envelope state, Fir / Resample history, Plotter count.  old_node_of_new[i] is the index in
+ * `old` of the module that is node i of `g`, or -1 for a new module.  Kinds must match (-2, nothing copied); a bad length or index is -1.
+ * A history is carried only where the carried length is the same: a filter whose length changed starts from silence.  Params are not
+ * state: the new graph keeps the ones it was built with. */
+int orc_graph_adopt_state(orc_graph* g, const orc_graph* old, const int32_t* old_node_of_new, size_t n) {
+    if (!g || !old || g == old || n != g->n_nodes || (n && !old_node_of_new)) return -1;
+    for (size_t i = 0; i < n; i++) {
+        const int32_t j = old_node_of_new[i];
+        if (j < 0) continue;
+        if ((size_t)j >= old->n_nodes) return -1;
+        if (old->nodes[j].kind != g->nodes[i].kind) return -2;
+    }
+    for (size_t i = 0; i < n; i++) {
+        const int32_t j = old_node_of_new[i];
+        if (j < 0) continue;
+        onode* a = &g->nodes[i]; const onode* b = &old->nodes[j];
+        a->eq = b->eq; a->env = b->env; a->plot = b->plot;
+        if (a->hist && b->hist && a->hist_taps == b->hist_taps) memcpy(a->hist, b->hist, 2 * (size_t)a->hist_taps * sizeof(float));
+    }
+    return 0;
+}
+
+/* a node's carried state as bytes (EqThree, Envelope, Plotter count, then the history): returns the size, copies min(size, cap) */
+size_t orc_graph_node_state(const orc_graph* g, uint32_t node, void* dst, size_t cap) {
+    if (node >= g->n_nodes) return 0;
+    const onode* n = &g->nodes[node];
+    const size_t hb = n->hist ? 2 * (size_t)n->hist_taps * sizeof(float) : 0;
+    const size_t total = sizeof n->eq + sizeof n->env + sizeof n->plot + hb;
+    uint8_t* tmp = (uint8_t*)malloc(total);
+    memcpy(tmp, &n->eq, sizeof n->eq); memcpy(tmp + sizeof n->eq, &n->env, sizeof n->env);
+    memcpy(tmp + sizeof n->eq + sizeof n->env, &n->plot, sizeof n->plot);
+    if (hb) memcpy(tmp + total - hb, n->hist, hb);
+    if (dst) memcpy(dst, tmp, total < cap ? total : cap);
+    free(tmp);
+    return total;
+}
+
+/* the carried history itself, writable (tests/random_edits.py's fault catalogue writes what a wrong adopt would leave there) */
+float* orc_graph_hist(orc_graph* g, uint32_t node, size_t* n_floats) {
+    if (node >= g->n_nodes) return NULL;
+    if (n_floats) *n_floats = g->nodes[node].hist ? 2 * (size_t)g->nodes[node].hist_taps : 0;
+    return g->nodes[node].hist;
 }

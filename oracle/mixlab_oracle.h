@@ -156,6 +156,14 @@ const float* orc_graph_output(const orc_graph* g, uint32_t node, uint32_t port, 
 int orc_graph_plotter_indication(const orc_graph* g, uint32_t node, float* left, float* right);
 /* number of nodes in run order; order[i] filled */
 size_t orc_graph_run_order(const orc_graph* g, uint32_t* order, size_t cap);
+/* Topology edit (mx_graph_adopt_state as include/mixlab_gpu.h describes it): `g`, built anew, takes over eq / env / plot / hist of every
+ * surviving module; old_node_of_new[i] = the module's index in `old`, -1 = new.  0; -2 where a kind differs; -1 on a bad length or index.
+ * A Fir / Resample history is carried only where n_taps / taps_per_phase is unchanged. */
+int orc_graph_adopt_state(orc_graph* g, const orc_graph* old, const int32_t* old_node_of_new, size_t n);
+/* a node's carried state as bytes, for comparisons: returns its size and copies min(size, cap) into dst (may be NULL) */
+size_t orc_graph_node_state(const orc_graph* g, uint32_t node, void* dst, size_t cap);
+/* the carried Fir / Resample history (2 floats per carried frame), writable; NULL where the node has none */
+float* orc_graph_hist(orc_graph* g, uint32_t node, size_t* n_floats);
 
 /* rational time helpers used by VideoMixer frame expiry (util/src/time.rs:9-75) */
 typedef struct { int64_t num, den; } orc_rational;

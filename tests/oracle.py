@@ -78,6 +78,11 @@ lib.orc_graph_output.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C
 lib.orc_graph_plotter_indication.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
 lib.orc_graph_run_order.restype = C.c_size_t
 lib.orc_graph_run_order.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_size_t]
+lib.orc_graph_adopt_state.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_size_t]
+lib.orc_graph_node_state.restype = C.c_size_t
+lib.orc_graph_node_state.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t]
+lib.orc_graph_hist.restype = C.POINTER(C.c_float)
+lib.orc_graph_hist.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_size_t)]
 lib.orc_crossfade_factor.restype = C.c_uint8
 lib.orc_crossfade_factor.argtypes = [C.c_double]
 lib.orc_rational_new.restype = Rational
@@ -238,6 +243,28 @@ class OracleGraph:
         rc = lib.orc_graph_plotter_indication(self._h, node, _p(l), _p(r))
         assert rc >= 0
         return (l, r) if rc == 1 else None
+
+    def adopt_state(self, old: "OracleGraph", old_node_of_new):
+        """Topology edit (mx_graph_adopt_state as include/mixlab_gpu.h describes it): this graph, built anew, takes over the EqThree, Envelope,
+        Plotter and Fir / Resample state of every module that survives; old_node_of_new[i] = its index in `old`, -1 = a new module"""
+        arr = (C.c_int32 * max(1, len(old_node_of_new)))(*old_node_of_new)
+        rc = lib.orc_graph_adopt_state(self._h, old._h, arr, len(old_node_of_new))
+        if rc == -2:
+            raise TypeError("a module cannot change kind across a topology edit")
+        assert rc == 0
+
+    def node_state(self, node) -> bytes:
+        """the node's carried state (EqThree, Envelope, Plotter count, Fir / Resample history) as bytes"""
+        n = lib.orc_graph_node_state(self._h, node, None, 0)
+        buf = C.create_string_buffer(n)
+        lib.orc_graph_node_state(self._h, node, buf, n)
+        return buf.raw
+
+    def hist(self, node):
+        """the Fir / Resample history as a writable view (2 floats per carried frame), None where the node has none"""
+        n = C.c_size_t()
+        ptr = lib.orc_graph_hist(self._h, node, C.byref(n))
+        return np.ctypeslib.as_array(ptr, shape=(n.value,)) if ptr and n.value else None
 
     def run_order(self):
         arr = (C.c_uint32 * max(1, len(self.ws.nodes)))()

@@ -142,6 +142,82 @@ def test_topology_edit_keeps_eq_envelope_and_fir_state():
         assert np.array_equal(bits(got_amp), bits(want_amp)), f"EqThree / Envelope state lost across the edit (run {run})"
 
 
+def parked_workspace(parked, taps, rs_taps):
+    """EqThree, Envelope, Fir and Resample behind a source each.  parked: every one of them sits in a cycle that feeds no terminal module
+    instead (EqThree -> Panner -> Splitter -> EqThree and the like), so the engine never runs it (engine.rs:428-430) and no launch serves it"""
+    ws = Workspace(SR, 60)
+    s = ws.source_mono(); eq = ws.eq_three(3.0, -6.0, 4.5)
+    gs = ws.source_mono(); env = ws.envelope(25.0, 500.0, 0.8, 200.0)
+    ss = ws.source_stereo(); fir = ws.fir(taps)
+    sr = ws.source_stereo(); rs = ws.resample(2, 1, rs_taps)
+    ids = {"s": s, "eq": eq, "gs": gs, "env": env, "ss": ss, "fir": fir, "sr": sr, "rs": rs}
+    if not parked:
+        ws.connect(s, 0, eq, 0); ws.connect(gs, 0, env, 0); ws.connect(ss, 0, fir, 0); ws.connect(sr, 0, rs, 0)
+        return ws, ids
+    for node in (eq, env):
+        pan = ws.stereo_panner(); split = ws.stereo_splitter()
+        ws.connect(node, 0, pan, 0); ws.connect(node, 0, pan, 1); ws.connect(pan, 0, split, 0); ws.connect(split, 0, node, 0)
+    for node in (fir, rs):
+        amp = ws.amplifier(1.0, 0.0)
+        ws.connect(node, 0, amp, 0); ws.connect(amp, 0, node, 0)
+    return ws, ids
+
+
+def test_topology_edit_keeps_the_state_of_modules_outside_the_run_order():
+    """A module in a cycle that feeds no terminal module is not run, but it persists (Engine::client_update keeps the module; only
+    connections changed): when a later edit brings it back into the run order it goes on from the state it had.  Three graphs: the four
+    stateful modules run, then sit in such cycles for one edit, then run again -- against the per-module oracle that simply is not
+    called in between.  The device has no state region for a node no launch serves, so the state crosses the middle graph on the host."""
+    T = 4
+    taps = np.asarray(synth.uniform(5, 16, -0.3, 0.3), dtype=np.float64)
+    rs_taps = np.asarray(synth.uniform(6, 2 * 5, -0.3, 0.3), dtype=np.float64).reshape(2, 5)
+    x = synth.noise(51, 3 * T * SPT)
+    xs = synth.noise(52, 3 * T * 2 * SPT)
+    xr = synth.noise(53, 3 * T * 2 * SPT)
+    gate = np.zeros(3 * T * SPT, np.float32); gate[100:2 * T * SPT + 300] = 1.0
+
+    def run(g, ids, r):
+        g.write_source(ids["s"], x[r * T * SPT:(r + 1) * T * SPT], T)
+        g.write_source(ids["gs"], gate[r * T * SPT:(r + 1) * T * SPT], T)
+        g.write_source(ids["ss"], xs[r * T * 2 * SPT:(r + 1) * T * 2 * SPT], T)
+        g.write_source(ids["sr"], xr[r * T * 2 * SPT:(r + 1) * T * 2 * SPT], T)
+        g.run_ticks(r * T, T)
+
+    # the oracle: runs 0 and 2 only, the state kept in between
+    est = oracle.eq_three_new(SR); vst = oracle.EnvState()
+    hist = np.zeros((len(taps) - 1) * 2, np.float32); rhist = np.zeros((rs_taps.shape[1] - 1) * 2, np.float32)
+    want = {}
+    for r in (0, 2):
+        sl = slice(r * T * SPT, (r + 1) * T * SPT)
+        sl2 = slice(r * T * 2 * SPT, (r + 1) * T * 2 * SPT)
+        want[("eq", r)] = oracle.eq_three_run(est, (3.0, -6.0, 4.5), x[sl])
+        want[("env", r)] = np.concatenate([oracle.envelope_run(vst, (25.0, 500.0, 0.8, 200.0), SR, k * SPT, gate[k * SPT:(k + 1) * SPT], SPT)
+                                           for k in range(r * T, (r + 1) * T)])
+        want[("fir", r)] = oracle.fir_run(taps, hist, xs[sl2])
+        want[("rs", r)] = np.concatenate([oracle.resample_run(rs_taps, 2, 1, rhist, k * SPT, k * 2 * SPT, xr[k * 2 * SPT:(k + 1) * 2 * SPT], 2 * SPT)
+                                          for k in range(r * T, (r + 1) * T)])
+
+    def check(g, ids, r):
+        assert np.array_equal(bits(g.read_output(ids["eq"], 0, T, False)), bits(want[("eq", r)])), f"EqThree, run {r}"
+        assert np.array_equal(bits(g.read_output(ids["env"], 0, T, False)), bits(want[("env", r)])), f"Envelope, run {r}"
+        assert np.array_equal(bits(g.read_output(ids["fir"], 0, T, True)), bits(want[("fir", r)])), f"Fir, run {r}"
+        assert np.array_equal(bits(g.read_output(ids["rs"], 0, T, True, rate=(2 * SPT, SPT))), bits(want[("rs", r)])), f"Resample, run {r}"
+
+    ws0, id0 = parked_workspace(False, taps, rs_taps)
+    g0 = ws0.build(max_ticks_per_run=T, flags=abi.FLAG_EQ_EXACT)
+    run(g0, id0, 0); check(g0, id0, 0)
+    ws1, id1 = parked_workspace(True, taps, rs_taps)
+    g1 = ws1.build(max_ticks_per_run=T, flags=abi.FLAG_EQ_EXACT)
+    assert not {id1[k] for k in ("eq", "env", "fir", "rs")} & set(g1.run_order())
+    g1.adopt_state(g0, list(range(len(ws0.nodes))) + [-1] * (len(ws1.nodes) - len(ws0.nodes)))
+    g0.close()
+    run(g1, id1, 1)
+    g2 = ws0.build(max_ticks_per_run=T, flags=abi.FLAG_EQ_EXACT)
+    g2.adopt_state(g1, list(range(len(ws0.nodes))))
+    g1.close()
+    run(g2, id0, 2); check(g2, id0, 2)
+
+
 def test_topology_edit_refuses_kind_change_and_bad_maps():
     ws = Workspace(SR, 60)
     s = ws.source_mono(); e = ws.eq_three(0.0, 0.0, 0.0); ws.connect(s, 0, e, 0)

@@ -14,6 +14,7 @@ mode.  What is under test is the scheduler: run order, levels, sample-rate domai
 conditions, slab layout, spans cut by scheduled updates, state carry.  The last tests put all seven audio tap sets on those graphs
 (tests/random_taps.py): what is under test there is the shared tap host and the compiler's materialisation of tapped ports.
 tests/test_gpu_random_decks.py runs the same graphs with decks on their stereo sources (run_full_graph(decks=...), tests/random_decks.py).
+tests/test_gpu_random_edits.py runs them through topology edits (tests/random_edits.py, a runner of its own built from the pieces here).
 """
 import struct
 from fractions import Fraction
@@ -154,38 +155,37 @@ def engine_domains(ws):
     return order, dom, None
 
 
-def _full_graph(seed, sr, tps):
-    """Every audio kind the oracle runs.  Each module is given a sample-rate domain when it is created -- the base one or the output
-    domain of an existing Resample -- and its inputs are drawn from ports of that domain (earlier or later modules: cycles happen
-    inside resampled domains too); a few inputs are drawn from any domain on purpose.  Where a cycle makes such an edge a forward
-    one, or leaves a module without the inputs that gave it its domain, the engine would refuse the graph: those edges are dropped
-    (engine_domains) until it builds.  A drawn edge from a resampled port into a base-domain module that the run order makes a
-    back-edge stays: it reads Disconnected."""
-    rng = np.random.default_rng(seed)
-    ws = Workspace(sr, tps)
-    spt = ws.spt
-    base = Fraction(1)
-    domains = [base]
-    outs = {}                          # (line type, domain) -> [(node, port)]
-    ins = []                           # (node, port, type, domain)
-    intended = {}
-    sources = []
+FULL_KINDS = ["src_m", "src_s", "osc", "trig", "eq", "env", "amp", "pan", "split", "mix", "plot", "fm", "fir", "rs", "rs", "amp", "pan", "split", "mix", "fir"]
 
-    def out(n, p, ty, d):
-        outs.setdefault((ty, d), []).append((n, p))
 
-    def pick_domain(kind=None):
-        if kind in RATE_BOUND or len(domains) == 1 or rng.random() < 0.45:
-            return base
-        return domains[int(rng.integers(1, len(domains)))]
+class FullDraw:
+    """What `_full_graph` draws its modules against -- the sample-rate domains there are, the output ports by (line type, domain), the inputs
+    still to be connected, the domain each module was meant for, the sources -- and the per-kind draw itself: `module(k)` draws one module of
+    FULL_KINDS' kind k, `sink()` an OutputDevice.  tests/random_edits.py draws an edit's new modules by these rules."""
 
-    for _ in range(int(rng.integers(10, 36))):
-        k = rng.choice(["src_m", "src_s", "osc", "trig", "eq", "env", "amp", "pan", "split", "mix", "plot", "fm", "fir", "rs", "rs",
-                        "amp", "pan", "split", "mix", "fir"])
+    def __init__(self, rng, ws):
+        self.rng, self.ws = rng, ws
+        self.base = Fraction(1)
+        self.domains = [self.base]
+        self.outs = {}                     # (line type, domain) -> [(node, port)]
+        self.ins = []                      # (node, port, type, domain)
+        self.intended = {}
+        self.sources = []
+
+    def out(self, n, p, ty, d):
+        self.outs.setdefault((ty, d), []).append((n, p))
+
+    def pick_domain(self, kind=None):
+        if kind in RATE_BOUND or len(self.domains) == 1 or self.rng.random() < 0.45:
+            return self.base
+        return self.domains[int(self.rng.integers(1, len(self.domains)))]
+
+    def module(self, k):
+        rng, ws, base, out, ins = self.rng, self.ws, self.base, self.out, self.ins
         if k == "src_m":
-            n = ws.source_mono(); sources.append((n, MONO)); out(n, 0, MONO, base)
+            n = ws.source_mono(); self.sources.append((n, MONO)); out(n, 0, MONO, base)
         elif k == "src_s":
-            n = ws.source_stereo(); sources.append((n, STEREO)); out(n, 0, STEREO, base)
+            n = ws.source_stereo(); self.sources.append((n, STEREO)); out(n, 0, STEREO, base)
         elif k == "osc":
             n = ws.oscillator(float(rng.uniform(50, 2000)), int(rng.integers(0, 6)))
             out(n, 0, MONO, base); out(n, 1, STEREO, base)
@@ -202,21 +202,21 @@ def _full_graph(seed, sr, tps):
         elif k == "plot":
             n = ws.plotter(); ins.append((n, 0, STEREO, base))
         elif k == "rs":
-            d = pick_domain()
-            cand = [r for r in RATIOS if (spt * d * Fraction(*r)).denominator == 1 and (spt * Fraction(*r)).denominator == 1]
+            d = self.pick_domain()
+            cand = [r for r in RATIOS if (ws.spt * d * Fraction(*r)).denominator == 1 and (ws.spt * Fraction(*r)).denominator == 1]
             up, down = cand[int(rng.integers(0, len(cand)))]
             n = ws.resample(up, down, rng.uniform(-0.5, 0.5, (up, int(rng.integers(1, 9)))))
-            feed = outs.get((STEREO, d), [])
+            feed = self.outs.get((STEREO, d), [])
             if feed:                   # fed at once from its own domain, so its output domain is the one drawn
                 ws.connect(*feed[int(rng.integers(0, len(feed)))], n, 0)
             else:
                 ins.append((n, 0, STEREO, d))
             nd = d * Fraction(up, down)
-            if nd not in domains:
-                domains.append(nd)
+            if nd not in self.domains:
+                self.domains.append(nd)
             out(n, 0, STEREO, nd)
         else:
-            d = pick_domain()
+            d = self.pick_domain()
             if k == "amp":
                 n = ws.amplifier(float(rng.uniform(0.1, 2.0)), float(rng.uniform(0.0, 1.0)))
                 ins += [(n, 0, STEREO, d), (n, 1, MONO, d)]; out(n, 0, STEREO, d)
@@ -231,7 +231,42 @@ def _full_graph(seed, sr, tps):
                 n = ws.mixer([(float(rng.uniform(-24, 6)), float(rng.uniform(0, 1)), bool(rng.integers(0, 2))) for _ in range(w)])
                 ins += [(n, c, STEREO, d) for c in range(w)]
                 out(n, 0, STEREO, d); out(n, 1, STEREO, d)
-        intended[n] = d if k not in ("src_m", "src_s", "osc", "trig", "eq", "env", "fm", "plot") else base
+        self.intended[n] = d if k not in ("src_m", "src_s", "osc", "trig", "eq", "env", "fm", "plot") else base
+        return n
+
+    def sink(self):
+        """left / right None, inside the channel range or beyond it (the node filters those), sometimes the same channel"""
+        od = self.ws.output_device(*random_od(self.rng))
+        d = self.pick_domain()
+        self.intended[od] = d
+        self.ins.append((od, 0, STEREO, d))
+        return od
+
+    def connect_input(self, n, port, ty, d):
+        rng = self.rng
+        if rng.random() < 0.15:                      # any domain: kept where the run order makes it a back-edge
+            pool = [x for (t2, _d2), xs in self.outs.items() if t2 == ty for x in xs]
+        elif rng.random() < 0.85:
+            pool = self.outs.get((ty, d), [])
+        else:
+            return
+        if pool:
+            self.ws.connect(*pool[int(rng.integers(0, len(pool)))], n, port)
+
+
+def _full_graph(seed, sr, tps):
+    """Every audio kind the oracle runs.  Each module is given a sample-rate domain when it is created -- the base one or the output
+    domain of an existing Resample -- and its inputs are drawn from ports of that domain (earlier or later modules: cycles happen
+    inside resampled domains too); a few inputs are drawn from any domain on purpose.  Where a cycle makes such an edge a forward
+    one, or leaves a module without the inputs that gave it its domain, the engine would refuse the graph: those edges are dropped
+    (engine_domains) until it builds.  A drawn edge from a resampled port into a base-domain module that the run order makes a
+    back-edge stays: it reads Disconnected."""
+    rng = np.random.default_rng(seed)
+    ws = Workspace(sr, tps)
+    dr = FullDraw(rng, ws)
+    base, out, sources = dr.base, dr.out, dr.sources
+    for _ in range(int(rng.integers(10, 36))):
+        dr.module(rng.choice(FULL_KINDS))
     # strips like the benchmark's; the first one is left whole and feeds a Mixer nobody reads, so it runs and the fused graph stores its
     # Amplifier's output one float per frame (a dup-stored port); the others deviate at random
     for i in range(int(rng.integers(1, 4))):
@@ -243,23 +278,13 @@ def _full_graph(seed, sr, tps):
             ws.connect(a, 0, bus, 0)
             continue
         out(e, 0, MONO, base); out(v, 0, MONO, base); out(t, 0, MONO, base); out(p, 0, STEREO, base); out(a, 0, STEREO, base)
-        ins += [(e, 0, MONO, base), (p, 0, MONO, base), (p, 1, MONO, base), (a, 0, STEREO, base), (a, 1, MONO, base), (v, 0, MONO, base)]
-    # 0-2 sinks; left / right None, inside the channel range or beyond it (the node filters those), sometimes the same channel
+        dr.ins += [(e, 0, MONO, base), (p, 0, MONO, base), (p, 1, MONO, base), (a, 0, STEREO, base), (a, 1, MONO, base), (v, 0, MONO, base)]
+    # 0-2 sinks
     for _ in range(int(rng.integers(0, 3))):
-        od = ws.output_device(*random_od(rng))
-        d = pick_domain()
-        intended[od] = d
-        ins.append((od, 0, STEREO, d))
-    for (n, port, ty, d) in ins:
-        if rng.random() < 0.15:                      # any domain: kept where the run order makes it a back-edge
-            pool = [x for (t2, _d2), xs in outs.items() if t2 == ty for x in xs]
-        elif rng.random() < 0.85:
-            pool = outs.get((ty, d), [])
-        else:
-            continue
-        if pool:
-            ws.connect(*pool[int(rng.integers(0, len(pool)))], n, port)
-    drop_refused_edges(ws, intended)
+        dr.sink()
+    for (n, port, ty, d) in dr.ins:
+        dr.connect_input(n, port, ty, d)
+    drop_refused_edges(ws, dr.intended)
     return ws, sources
 
 
@@ -327,15 +352,15 @@ def random_params(rng, ws, node):
     return None
 
 
+OUT_TYPES = {abi.KIND_AMPLIFIER: [STEREO], abi.KIND_ENVELOPE: [MONO], abi.KIND_EQ_THREE: [MONO], abi.KIND_MIXER: [STEREO, STEREO],
+             abi.KIND_OSCILLATOR: [MONO, STEREO], abi.KIND_PLOTTER: [], abi.KIND_STEREO_PANNER: [STEREO],
+             abi.KIND_STEREO_SPLITTER: [MONO, MONO], abi.KIND_TRIGGER: [MONO], abi.KIND_SOURCE_MONO: [MONO],
+             abi.KIND_SOURCE_STEREO: [STEREO], abi.KIND_FM_SINE: [STEREO], abi.KIND_FIR: [STEREO], abi.KIND_RESAMPLE: [STEREO],
+             abi.KIND_OUTPUT_DEVICE: []}
+
+
 def port_types(ws):
-    res = []
-    for kind, params in ws.nodes:
-        res.append({abi.KIND_AMPLIFIER: [STEREO], abi.KIND_ENVELOPE: [MONO], abi.KIND_EQ_THREE: [MONO], abi.KIND_MIXER: [STEREO, STEREO],
-                    abi.KIND_OSCILLATOR: [MONO, STEREO], abi.KIND_PLOTTER: [], abi.KIND_STEREO_PANNER: [STEREO],
-                    abi.KIND_STEREO_SPLITTER: [MONO, MONO], abi.KIND_TRIGGER: [MONO], abi.KIND_SOURCE_MONO: [MONO],
-                    abi.KIND_SOURCE_STEREO: [STEREO], abi.KIND_FM_SINE: [STEREO], abi.KIND_FIR: [STEREO], abi.KIND_RESAMPLE: [STEREO],
-                    abi.KIND_OUTPUT_DEVICE: []}[kind])
-    return res
+    return [OUT_TYPES[kind] for kind, _params in ws.nodes]
 
 
 @pytest.mark.parametrize("seed", list(range(64)))
