@@ -45,7 +45,8 @@ extern "C" {
                               *    mx_deck_schedule, mx_deck_check, mx_deck_plan, mx_deck_feed, mx_deck_read_ticks, mx_deck_state, mx_deck_step, mx_deck_tables,
                               *    mx_deck_debug_last_feed;
                               *    mx_deck_keylock, mx_deck_grain, mx_deck_set_keylock, mx_deck_keylock_check, mx_deck_keylock_search, mx_deck_grain_count, mx_deck_read_grains,
-                              *    mx_deck_debug_last_keylock */
+                              *    mx_deck_debug_last_keylock;
+                              *    mx_plan_node, mx_plan_info, mx_graph_debug_plan */
 
 /* ---- status codes (0 ok, <0 error; cf. MIXLAB_IOCTX_ERROR / MIXLAB_IOCTX_PANIC) ---- */
 enum {
@@ -263,6 +264,37 @@ int mx_graph_debug_eq_env_rows(mx_graph* g, uint32_t* rows);
  * the wave had seen two different input patterns in its chunk by then); bit 1: some wave ran them without the multiply by an amplitude of exactly 1.0.  0: MX_EQ_LEAN=0,
  * another form was launched, or no tick qualified.  Synchronises.  Tests use it to know the lean loops ran. */
 int mx_graph_debug_eq_lean(mx_graph* g, uint32_t* lean);
+/* DEBUG: what the graph compiler decides about a topology, WITHOUT a device: the run order, levels, sample-rate domains, the fusion plan, the launch groups, the
+ * overlap-tail candidate and the slab layout, computed by the very code mx_graph_build runs before it opens the device.  Invalid graphs get the codes and messages
+ * mx_graph_build gives them.  overlap_auto: what the environment's MX_OVERLAP_AUTO would say (0: the automatic second-stream mode off); cap_frames: frames per run
+ * the slab is laid out for (0: samples per tick * max_ticks_per_run).  The tail candidate is reported as the compiler names it and the layout gives its ports their
+ * second buffers; whether a build takes an AUTOMATIC candidate also depends on the device memory that is free then.  nodes_out: one record per node; info may be NULL. */
+typedef struct mx_plan_node {
+    int32_t pos;                  /* position in the run order; -1: outside it */
+    int32_t level, group;         /* dependency level; launch group (-1: none -- elided, an OutputDevice, or outside the run order) */
+    uint32_t slot;                /* index inside the group */
+    int32_t sub_key;              /* EqThree: 1 + the epilogue mode its group is specialised for; 0 otherwise */
+    uint32_t dom_num, dom_den, in_dom_num, in_dom_den;   /* sample-rate domain of the outputs / the inputs, relative to the graph's rate */
+    uint32_t elided;              /* 1: never launched, its work is folded into `owner`'s kernel */
+    int32_t owner;                /* -1: none */
+    int32_t fuse_pan, fuse_amp, fuse_trigger, fuse_env;   /* the nodes folded into this one (-1: none) */
+    uint32_t n_out;               /* output ports (at most 4) */
+    uint8_t out_elided[4];        /* per output port: no buffer */
+    uint8_t out_dup[4];           /* per output port: stereo with L == R stored as one float per frame */
+    uint64_t out_off[4];          /* per output port: offset of its buffer in the slab, in floats; UINT64_MAX: none */
+    uint64_t out_off2[4];         /* ... of its second buffer (a port the overlap tail reads); UINT64_MAX: none */
+} mx_plan_node;
+typedef struct mx_plan_info {
+    uint64_t n_order, n_groups;   /* nodes in the run order; launch groups */
+    uint64_t slab_floats;         /* the whole slab */
+    uint64_t zero_off, zero_floats;   /* the region Disconnected inputs read */
+    int32_t tail_first_group;     /* overlap-tail candidate: its first group (every later group belongs to it); -1: none */
+    uint32_t tail_ports;          /* ... the output ports it would double-buffer */
+    uint32_t tail_auto;           /* ... 1: by the automatic rule, 0: asked for with MX_FLAG_OVERLAP_TAIL */
+    uint32_t has_video;
+} mx_plan_info;
+int mx_graph_debug_plan(const mx_node* nodes, size_t n_nodes, const mx_edge* edges, size_t n_edges, const mx_graph_opts* opts,
+                        uint32_t overlap_auto, size_t cap_frames, mx_plan_node* nodes_out, mx_plan_info* info);
 
 /* Feed a SOURCE_* node: n_ticks consecutive tick buffers (SPT mono / 2*SPT interleaved stereo f32). */
 int mx_graph_write_source(mx_graph* g, uint32_t node, const float* host_samples, size_t n_ticks);

@@ -123,6 +123,27 @@ _proto("mx_graph_debug_eq_launch", C.c_int, C.c_void_p, C.POINTER(C.c_uint32))
 _proto("mx_graph_debug_eq_env_rows", C.c_int, C.c_void_p, C.POINTER(C.c_uint32))
 _proto("mx_graph_debug_eq_lean", C.c_int, C.c_void_p, C.POINTER(C.c_uint32))
 _proto("mx_graph_eq_repair_stats", C.c_int, C.c_void_p, C.POINTER(C.c_uint64))
+PLAN_NONE = 2**64 - 1   # mx_plan_node.out_off / out_off2: no buffer
+
+
+class PlanNode(C.Structure):
+    """mx_plan_node: what the graph compiler says about one node (mx_graph_debug_plan)."""
+    _fields_ = [("pos", C.c_int32), ("level", C.c_int32), ("group", C.c_int32), ("slot", C.c_uint32), ("sub_key", C.c_int32),
+                ("dom_num", C.c_uint32), ("dom_den", C.c_uint32), ("in_dom_num", C.c_uint32), ("in_dom_den", C.c_uint32),
+                ("elided", C.c_uint32), ("owner", C.c_int32),
+                ("fuse_pan", C.c_int32), ("fuse_amp", C.c_int32), ("fuse_trigger", C.c_int32), ("fuse_env", C.c_int32),
+                ("n_out", C.c_uint32), ("out_elided", C.c_uint8 * 4), ("out_dup", C.c_uint8 * 4),
+                ("out_off", C.c_uint64 * 4), ("out_off2", C.c_uint64 * 4)]
+
+
+class PlanInfo(C.Structure):
+    """mx_plan_info: the plan as a whole (mx_graph_debug_plan)."""
+    _fields_ = [("n_order", C.c_uint64), ("n_groups", C.c_uint64), ("slab_floats", C.c_uint64), ("zero_off", C.c_uint64), ("zero_floats", C.c_uint64),
+                ("tail_first_group", C.c_int32), ("tail_ports", C.c_uint32), ("tail_auto", C.c_uint32), ("has_video", C.c_uint32)]
+
+
+_proto("mx_graph_debug_plan", C.c_int, C.POINTER(Node), C.c_size_t, C.POINTER(Edge), C.c_size_t, C.POINTER(GraphOpts), C.c_uint32, C.c_size_t,
+       C.POINTER(PlanNode), C.POINTER(PlanInfo))
 _proto("mx_graph_write_source", C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t)
 _proto("mx_graph_bind_source_device", C.c_int, C.c_void_p, C.c_uint32, C.c_void_p)
 _proto("mx_graph_run_ticks", C.c_int, C.c_void_p, C.c_uint64, C.c_uint32)
@@ -617,22 +638,38 @@ def params_bytes(p) -> bytes:
     return bytes(p)
 
 
+def _graph_arrays(nodes, edges):
+    """(mx_node[], mx_edge[], the buffers the node array points into) for a list of (kind, params) and of edge tuples."""
+    keep = []
+    n_arr = (Node * max(1, len(nodes)))()
+    for i, (kind, p) in enumerate(nodes):
+        blob = params_bytes(p)
+        buf = C.create_string_buffer(blob, len(blob)) if blob else None
+        keep.append(buf)
+        n_arr[i] = Node(kind, len(blob), C.cast(buf, C.c_void_p) if buf else None)
+    e_arr = (Edge * max(1, len(edges)))()
+    for i, e in enumerate(edges):
+        e_arr[i] = Edge(*e)
+    return n_arr, e_arr, keep
+
+
+def debug_plan(nodes, edges, sample_rate=44100, ticks_per_second=60, max_ticks_per_run=1, flags=0, overlap_auto=1, cap_frames=0):
+    """mx_graph_debug_plan: (one PlanNode per node, PlanInfo) of the graph mx_graph_build would compile.  Needs no device; raises what a build raises."""
+    n_arr, e_arr, _keep = _graph_arrays(nodes, edges)
+    opts = GraphOpts(sample_rate, ticks_per_second, max_ticks_per_run, flags, -1, 0, None)
+    out = (PlanNode * max(1, len(nodes)))()
+    info = PlanInfo()
+    check(lib.mx_graph_debug_plan(n_arr, len(nodes), e_arr, len(edges), C.byref(opts), overlap_auto, cap_frames, out, C.byref(info)))
+    return list(out[: len(nodes)]), info
+
+
 class Graph:
     """Thin RAII wrapper of mx_graph_* (a frozen Workspace, src/engine/workspace.rs:13-19)."""
 
     def __init__(self, nodes, edges, sample_rate=44100, ticks_per_second=60, max_ticks_per_run=1, flags=0,
                  device=-1, stream=None):
         self._h = C.c_void_p()
-        blobs = [params_bytes(p) for (_k, p) in nodes]
-        self._keep = []
-        n_arr = (Node * max(1, len(nodes)))()
-        for i, ((kind, _p), blob) in enumerate(zip(nodes, blobs)):
-            buf = C.create_string_buffer(blob, len(blob)) if blob else None
-            self._keep.append(buf)
-            n_arr[i] = Node(kind, len(blob), C.cast(buf, C.c_void_p) if buf else None)
-        e_arr = (Edge * max(1, len(edges)))()
-        for i, e in enumerate(edges):
-            e_arr[i] = Edge(*e)
+        n_arr, e_arr, self._keep = _graph_arrays(nodes, edges)
         opts = GraphOpts(sample_rate, ticks_per_second, max_ticks_per_run, flags, device, 0, stream)
         check(lib.mx_graph_build(n_arr, len(nodes), e_arr, len(edges), C.byref(opts), C.byref(self._h)))
         spt = C.c_size_t()

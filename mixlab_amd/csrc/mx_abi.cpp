@@ -8,12 +8,10 @@
 #include <memory>
 #include <string>
 
-#include "mx_engine.hpp"
+#include "mx_abi_common.hpp"
 
 using mx::Error;
 using mx::Graph;
-
-struct mx_graph { std::unique_ptr<Graph> g; };
 
 struct mx_module {
     uint32_t kind = 0;
@@ -24,29 +22,7 @@ struct mx_module {
 };
 
 static thread_local std::string t_last_error;
-void mx_set_last_error(const std::string& s) { t_last_error = s; }   // shared with mx_abi_video.cpp
-
-template <class F>
-static int guard(F&& f) noexcept {
-    try {
-        f();
-        return MX_OK;
-    } catch (const Error& e) {
-        t_last_error = e.what();
-        return e.code;
-    } catch (const std::bad_alloc&) {
-        t_last_error = "host allocation failed";
-        return MX_ERR_NOMEM;
-    } catch (const std::exception& e) {
-        t_last_error = std::string("internal error: ") + e.what();
-        return MX_ERR_INTERNAL;
-    } catch (...) {
-        t_last_error = "internal error: unknown exception";
-        return MX_ERR_INTERNAL;
-    }
-}
-
-#define REQUIRE(cond, msg) do { if (!(cond)) throw Error(MX_ERR_INVALID, msg); } while (0)
+void mx_set_last_error(const std::string& s) { t_last_error = s; }   // the one writer: guard() (mx_abi_common.hpp) and every mx_abi*.cpp go through it
 
 extern "C" {
 
@@ -56,7 +32,7 @@ uint32_t mx_abi_version(void) { return MX_ABI_VERSION; }
 int mx_device_count(void) {
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess) { t_last_error = std::string("hipGetDeviceCount: ") + hipGetErrorString(e); (void)hipGetLastError(); return MX_ERR_DEVICE; }
+    if (e != hipSuccess) { mx_set_last_error(std::string("hipGetDeviceCount: ") + hipGetErrorString(e)); (void)hipGetLastError(); return MX_ERR_DEVICE; }
     return n;
 }
 
@@ -71,6 +47,42 @@ int mx_graph_build(const mx_node* nodes, size_t n_nodes, const mx_edge* edges, s
         auto h = std::make_unique<mx_graph>();
         h->g = std::make_unique<Graph>(nodes, n_nodes, edges, n_edges, o);
         *out = h.release();
+    });
+}
+
+// The compiler alone: the very compile_plan / layout_slab a build goes through, and no device.
+int mx_graph_debug_plan(const mx_node* nodes, size_t n_nodes, const mx_edge* edges, size_t n_edges, const mx_graph_opts* opts,
+                        uint32_t overlap_auto, size_t cap_frames, mx_plan_node* nodes_out, mx_plan_info* info) {
+    return guard([&] {
+        REQUIRE(nodes_out || !n_nodes, "nodes_out is NULL");
+        mx_graph_opts o{};
+        o.device = -1;
+        if (opts) o = *opts;
+        mx::PlanEnv env; env.overlap_auto = overlap_auto != 0; env.cap_frames = cap_frames;
+        const mx::Plan P = mx::compile_plan(nodes, n_nodes, edges, n_edges, o, env);
+        const mx::SlabLayout L = mx::layout_slab(P, P.cap_frames, P.tail_first >= 0);
+        for (size_t i = 0; i < n_nodes; ++i) {
+            const mx::PlanNode& n = P.nodes[i];
+            mx_plan_node r{};
+            r.pos = n.pos; r.level = n.level; r.group = n.group; r.slot = n.slot; r.sub_key = n.sub_key;
+            r.dom_num = n.dom_num; r.dom_den = n.dom_den; r.in_dom_num = n.in_dom_num; r.in_dom_den = n.in_dom_den;
+            r.elided = n.elided ? 1u : 0u; r.owner = n.owner;
+            r.fuse_pan = n.fuse_pan; r.fuse_amp = n.fuse_amp; r.fuse_trigger = n.fuse_trigger; r.fuse_env = n.fuse_env;
+            r.n_out = (uint32_t)n.out_type.size();
+            for (size_t k = 0; k < 4; ++k) {
+                const bool have = k < n.out_type.size();
+                r.out_elided[k] = have && n.out_elided[k]; r.out_dup[k] = have && n.out_dup[k];
+                r.out_off[k] = have && L.out_off[i][k] != SIZE_MAX ? L.out_off[i][k] : UINT64_MAX;
+                r.out_off2[k] = have && L.out_off2[i][k] != SIZE_MAX ? L.out_off2[i][k] : UINT64_MAX;
+            }
+            nodes_out[i] = r;
+        }
+        if (!info) return;
+        *info = mx_plan_info{};
+        info->n_order = P.order.size(); info->n_groups = P.groups.size();
+        info->slab_floats = L.floats; info->zero_off = L.zero_off; info->zero_floats = L.zero_floats;
+        info->tail_first_group = P.tail_first; info->tail_ports = (uint32_t)P.tail_ports.size();
+        info->tail_auto = P.tail_auto ? 1u : 0u; info->has_video = P.has_video ? 1u : 0u;
     });
 }
 

@@ -4,35 +4,13 @@
 #include <string>
 
 #include "mx_exchange.hpp"
+#include "mx_abi_common.hpp"
 
 using mx::Error;
 
-struct mx_graph { std::unique_ptr<mx::Graph> g; };   // same layout as in mx_abi.cpp
 struct mx_loopback_group { mx::LoopbackGroup grp; explicit mx_loopback_group(uint32_t w) : grp(w) {} };
 struct mx_exchange { std::unique_ptr<mx::Exchange> x; };
 
-void mx_set_last_error(const std::string& s);   // mx_abi.cpp
-
-template <class F>
-static int guard(F&& f) noexcept {
-    try {
-        f();
-        return MX_OK;
-    } catch (const Error& e) {
-        mx_set_last_error(e.what());
-        return e.code;
-    } catch (const std::bad_alloc&) {
-        mx_set_last_error("host allocation failed");
-        return MX_ERR_NOMEM;
-    } catch (const std::exception& e) {
-        mx_set_last_error(std::string("internal error: ") + e.what());
-        return MX_ERR_INTERNAL;
-    } catch (...) {
-        mx_set_last_error("internal error: unknown exception");
-        return MX_ERR_INTERNAL;
-    }
-}
-#define REQUIRE(cond, msg) do { if (!(cond)) throw Error(MX_ERR_INVALID, msg); } while (0)
 
 extern "C" {
 

@@ -7,6 +7,7 @@
 
 #include "mx_engine.hpp"
 #include "mx_ingest.hpp"
+#include "mx_abi_common.hpp"
 
 using mx::DFrame;
 using mx::Error;
@@ -15,7 +16,6 @@ using mx::Rational;
 static inline DFrame* D(mx_dframe* p) { return reinterpret_cast<DFrame*>(p); }
 static inline mx_dframe* H(DFrame* p) { return reinterpret_cast<mx_dframe*>(p); }
 
-struct mx_graph { std::unique_ptr<mx::Graph> g; };   // same layout as in mx_abi.cpp
 struct mx_media_source { mx::MediaSource m; mx_media_source(uint32_t sr, uint32_t tps) : m(sr, tps) {} };
 struct mx_stream_input {
     mx::StreamInput s; uint32_t sr;
@@ -25,28 +25,6 @@ struct mx_stream_input {
 };
 struct mx_frame_stager { mx::FrameStager st; explicit mx_frame_stager(uint32_t slots) : st(slots) {} };
 
-void mx_set_last_error(const std::string& s);   // mx_abi.cpp
-
-template <class F>
-static int guard(F&& f) noexcept {
-    try {
-        f();
-        return MX_OK;
-    } catch (const Error& e) {
-        mx_set_last_error(e.what());
-        return e.code;
-    } catch (const std::bad_alloc&) {
-        mx_set_last_error("host allocation failed");
-        return MX_ERR_NOMEM;
-    } catch (const std::exception& e) {
-        mx_set_last_error(std::string("internal error: ") + e.what());
-        return MX_ERR_INTERNAL;
-    } catch (...) {
-        mx_set_last_error("internal error: unknown exception");
-        return MX_ERR_INTERNAL;
-    }
-}
-#define REQUIRE(cond, msg) do { if (!(cond)) throw Error(MX_ERR_INVALID, msg); } while (0)
 
 static Rational R(int64_t n, int64_t d) { return Rational::make(n, d ? d : 1); }
 static void put(mx_video_input* out, mx::TickVideo& v) {

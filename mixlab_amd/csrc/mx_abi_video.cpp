@@ -7,6 +7,7 @@
 
 #include "mx_engine.hpp"
 #include "mx_video.hpp"
+#include "mx_abi_common.hpp"
 
 using mx::DFrame;
 using mx::Error;
@@ -18,32 +19,9 @@ static inline const DFrame* D(const mx_dframe* p) { return reinterpret_cast<cons
 static inline mx_dframe* H(DFrame* p) { return reinterpret_cast<mx_dframe*>(p); }
 
 struct mx_video_mixer { std::unique_ptr<mx::VideoMixer> m; };
-struct mx_graph { std::unique_ptr<mx::Graph> g; };   // same layout as in mx_abi.cpp
 struct mx_video_lut { std::atomic<int> rc{1}; std::shared_ptr<const mx::LutTables> t; };   // whoever grades with it (a graph's source transform) shares t, not the handle
 
 extern "C" const char* mx_last_error(void);
-void mx_set_last_error(const std::string& s);   // mx_abi.cpp
-
-template <class F>
-static int guard(F&& f) noexcept {
-    try {
-        f();
-        return MX_OK;
-    } catch (const Error& e) {
-        mx_set_last_error(e.what());
-        return e.code;
-    } catch (const std::bad_alloc&) {
-        mx_set_last_error("host allocation failed");
-        return MX_ERR_NOMEM;
-    } catch (const std::exception& e) {
-        mx_set_last_error(std::string("internal error: ") + e.what());
-        return MX_ERR_INTERNAL;
-    } catch (...) {
-        mx_set_last_error("internal error: unknown exception");
-        return MX_ERR_INTERNAL;
-    }
-}
-#define REQUIRE(cond, msg) do { if (!(cond)) throw Error(MX_ERR_INVALID, msg); } while (0)
 
 static hipStream_t default_video_stream() {
     static std::once_flag once;

@@ -29,40 +29,6 @@ void DevBuf::free_() {
     p = nullptr; bytes = 0;
 }
 
-// ModuleT::inputs()/outputs() of each kind (reference file:line in include/mixlab_gpu.h)
-static void kind_ports(uint32_t kind, size_t params_len, std::vector<uint8_t>& in, std::vector<uint8_t>& out) {
-    auto need = [&](size_t sz, const char* name) {
-        if (params_len != sz) throw Error(MX_ERR_INVALID, std::string("params_len does not match ") + name);
-    };
-    switch (kind) {
-    case MX_KIND_AMPLIFIER: need(sizeof(mx_amplifier_params), "mx_amplifier_params"); in = {MX_STEREO, MX_MONO}; out = {MX_STEREO}; break;
-    case MX_KIND_ENVELOPE: need(sizeof(mx_envelope_params), "mx_envelope_params"); in = {MX_MONO}; out = {MX_MONO}; break;
-    case MX_KIND_EQ_THREE: need(sizeof(mx_eq_three_params), "mx_eq_three_params"); in = {MX_MONO}; out = {MX_MONO}; break;
-    case MX_KIND_FM_SINE: need(sizeof(mx_fm_sine_params), "mx_fm_sine_params"); in = {MX_MONO}; out = {MX_STEREO}; break;
-    case MX_KIND_MIXER: {
-        if (params_len % sizeof(mx_mixer_channel_params)) throw Error(MX_ERR_INVALID, "mixer params_len is not a multiple of mx_mixer_channel_params");
-        in.assign(params_len / sizeof(mx_mixer_channel_params), MX_STEREO); out = {MX_STEREO, MX_STEREO}; break;
-    }
-    case MX_KIND_OSCILLATOR: need(sizeof(mx_oscillator_params), "mx_oscillator_params"); in = {}; out = {MX_MONO, MX_STEREO}; break;
-    case MX_KIND_PLOTTER: need(0, "() (Plotter has no params)"); in = {MX_STEREO}; out = {}; break;
-    case MX_KIND_STEREO_PANNER: need(0, "()"); in = {MX_MONO, MX_MONO}; out = {MX_STEREO}; break;
-    case MX_KIND_STEREO_SPLITTER: need(0, "()"); in = {MX_STEREO}; out = {MX_MONO, MX_MONO}; break;
-    case MX_KIND_TRIGGER: need(sizeof(mx_trigger_params), "mx_trigger_params"); in = {}; out = {MX_MONO}; break;
-    case MX_KIND_SOURCE_MONO: in = {}; out = {MX_MONO}; break;
-    case MX_KIND_SOURCE_STEREO: in = {}; out = {MX_STEREO}; break;
-    case MX_KIND_VIDEO_MIXER: need(sizeof(mx_video_mixer_params), "mx_video_mixer_params"); in.assign(4, MX_VIDEO); out.assign(3, MX_VIDEO); break;  // video_mixer.rs:42-49
-    case MX_KIND_SOURCE_VIDEO: in = {}; out = {MX_VIDEO}; break;
-    case MX_KIND_FIR: in = {MX_STEREO}; out = {MX_STEREO}; break;        // blob checked in the constructor
-    case MX_KIND_RESAMPLE: in = {MX_STEREO}; out = {MX_STEREO}; break;
-    case MX_KIND_VIDEO_TO_RGBA: need(sizeof(mx_video_to_rgba_params), "mx_video_to_rgba_params"); in = {MX_VIDEO}; out = {}; break;
-    case MX_KIND_MONITOR:   // monitor.rs:99-102
-        if (params_len != sizeof(mx_monitor_params_ex)) need(sizeof(mx_monitor_params), "mx_monitor_params (or mx_monitor_params_ex)");
-        in = {MX_VIDEO, MX_STEREO}; out = {}; break;
-    case MX_KIND_OUTPUT_DEVICE: need(sizeof(mx_output_device_params), "mx_output_device_params"); in = {MX_STEREO}; out = {}; break;   // output_device.rs:80-81
-    default: throw Error(MX_ERR_INVALID, "unknown module kind");
-    }
-}
-
 // first column of A^n for the 4-pole cascade's one-sample matrix A (lower-triangular Toeplitz,
 // first column f^k (1-f)): binary exponentiation on polynomials mod x^4, in long double
 static void toeplitz_pow_ld(long double f, uint64_t n, long double res[4]) {
@@ -89,368 +55,193 @@ static void toeplitz_apply_ld(const long double a[4], const long double v[4], lo
     for (int i = 0; i < 4; ++i) { y[i] = 0.0L; for (int k = 0; k <= i; ++k) y[i] += a[k] * v[i - k]; }
 }
 
-static void check_output_device_params(const void* params) {
-    mx_output_device_params p; std::memcpy(&p, params, sizeof p);
-    if (p.channels > 256 || p.left < -1 || p.right < -1) throw Error(MX_ERR_INVALID, "mx_output_device_params: channels <= 256, left / right >= -1 (-1 = None)");
-}
-
 static inline size_t floats_per_frame(uint8_t lt) { return lt == MX_MONO ? 1 : (lt == MX_STEREO ? 2 : 0); }
 
-Graph::Graph(const mx_node* nodes, size_t n_nodes, const mx_edge* edges, size_t n_edges, const mx_graph_opts& o,
-             size_t cap_frames_override) {
-    if (n_nodes && !nodes) throw Error(MX_ERR_INVALID, "nodes is NULL");
-    if (n_edges && !edges) throw Error(MX_ERR_INVALID, "edges is NULL");
-    const uint32_t sr = o.sample_rate ? o.sample_rate : 44100u;          // src/engine.rs:53
-    const uint32_t tps = o.ticks_per_second ? o.ticks_per_second : 60u;  // src/engine.rs:54
-    if (sr % tps) throw Error(MX_ERR_INVALID, "sample_rate must be a multiple of ticks_per_second");
-    sample_rate_ = (double)sr;
-    spt_ = sr / tps;                                                     // src/engine.rs:55
-    tap_fpc_ = spt_;
-    tps_ = tps;
-    const uint32_t max_ticks = o.max_ticks_per_run ? o.max_ticks_per_run : 1u;
-    cap_frames_ = cap_frames_override ? cap_frames_override : spt_ * (size_t)max_ticks;
-    flags_ = o.flags;
-    if ((flags_ & MX_FLAG_FP_CONTRACT) && (flags_ & MX_FLAG_EQ_FAST) && !(flags_ & MX_FLAG_EQ_EXACT))
-        throw Error(MX_ERR_INVALID, "MX_FLAG_FP_CONTRACT is a mode of the exact-order kernels: not with MX_FLAG_EQ_FAST");
+static PlanEnv plan_env(size_t cap_frames) {
+    const char* const ae = getenv("MX_OVERLAP_AUTO");   // read per graph: tests build both kinds in one process
+    PlanEnv env; env.overlap_auto = !(ae && atoi(ae) == 0); env.cap_frames = cap_frames;
+    return env;
+}
 
-    if (o.device >= 0) { hip_check(hipSetDevice(o.device), "hipSetDevice"); device_ = o.device; }
-    else hip_check(hipGetDevice(&device_), "hipGetDevice");
-    if (o.stream) { stream_ = (hipStream_t)o.stream; own_stream_ = false; }
-    else { hip_check(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking), "hipStreamCreate"); own_stream_ = true; }
-
-    // host-side coefficients: same libm as the reference on this host (eq_three.rs:113-115)
-    lo_f_ = 2.0 * std::sin(3.14159265358979323846264338327950288 * 420.0 / sample_rate_);
-    hi_f_ = 2.0 * std::sin(3.14159265358979323846264338327950288 * 2700.0 / sample_rate_);
-
-    nodes_.resize(n_nodes);
+// The compiler first (mx_plan.hpp: every topology decision, no device), then the device: stream, the tail candidate taken or not, slab, descriptors, per-kind state.
+Graph::Graph(const mx_node* nodes, size_t n_nodes, const mx_edge* edges, size_t n_edges, const mx_graph_opts& o, size_t cap_frames_override)
+    : plan_(compile_plan(nodes, n_nodes, edges, n_edges, o, plan_env(cap_frames_override))) {
+    flags_ = plan_.flags; tps_ = plan_.tps; sample_rate_ = (double)plan_.sample_rate;
+    spt_ = plan_.spt; tap_fpc_ = spt_; cap_frames_ = plan_.cap_frames;
+    open_device(o);
+    nodes_.reserve(n_nodes);
     for (size_t i = 0; i < n_nodes; ++i) {
-        Node& n = nodes_[i];
-        n.kind = nodes[i].kind;
-        if (nodes[i].params_len && !nodes[i].params) throw Error(MX_ERR_INVALID, "node params is NULL");
-        n.params.assign((const uint8_t*)nodes[i].params, (const uint8_t*)nodes[i].params + nodes[i].params_len);
-        kind_ports(n.kind, n.params.size(), n.in_type, n.out_type);
-        n.in_src.assign(n.in_type.size(), PortRef{});
-        n.out_off.assign(n.out_type.size(), 0);
-        n.out_off2.assign(n.out_type.size(), SIZE_MAX);
-        if (n.kind == MX_KIND_OUTPUT_DEVICE) { check_output_device_params(n.params.data()); n.od_lag.reset(new std::atomic<bool>(false)); }
+        nodes_.emplace_back(plan_.nodes[i]);
+        nodes_[i].params.assign((const uint8_t*)nodes[i].params, (const uint8_t*)nodes[i].params + nodes[i].params_len);
     }
-    for (size_t e = 0; e < n_edges; ++e) {
-        const mx_edge& ed = edges[e];
-        if (ed.src_node >= n_nodes || ed.dst_node >= n_nodes) throw Error(MX_ERR_INVALID, "edge references a node out of range");
-        Node& s = nodes_[ed.src_node];
-        Node& d = nodes_[ed.dst_node];
-        if (ed.src_port >= s.out_type.size() || ed.dst_port >= d.in_type.size()) throw Error(MX_ERR_INVALID, "edge references a terminal out of range");
-        if (s.out_type[ed.src_port] != d.in_type[ed.dst_port])   // Workspace::connect, workspace.rs:97-114
-            throw Error(MX_ERR_TYPE, "line type mismatch on connection");
-        d.in_src[ed.dst_port] = PortRef{(int32_t)ed.src_node, ed.src_port};
-    }
-
-    // Run order: DFS through inputs from terminal modules (src/engine.rs:408-457).  The reference
-    // iterates a HashSet (unspecified order); ascending id is one of its valid orders.
-    std::vector<uint8_t> feeds(n_nodes, 0), seen(n_nodes, 0);
-    for (size_t e = 0; e < n_edges; ++e) feeds[edges[e].src_node] = 1;
-    // iterative DFS (graphs with 1e5 nodes must not blow the stack)
-    struct Frame { uint32_t id; uint32_t next; };
-    std::vector<Frame> stack;
-    for (uint32_t root = 0; root < n_nodes; ++root) {
-        if (feeds[root] || seen[root]) continue;
-        seen[root] = 1; stack.push_back({root, 0});
-        while (!stack.empty()) {
-            Frame& f = stack.back();
-            Node& n = nodes_[f.id];
-            if (f.next < n.in_src.size()) {
-                const PortRef pr = n.in_src[f.next++];
-                if (pr.node >= 0 && !seen[pr.node]) { seen[pr.node] = 1; stack.push_back({(uint32_t)pr.node, 0}); }
-            } else {
-                order_.push_back(f.id);
-                stack.pop_back();
-            }
-        }
-    }
-    // A cycle with no terminal module is never reached from a terminal, so the reference never runs
-    // it (engine.rs:428-430); we mirror that: such nodes stay out of order_.
-
-    // dependency levels; an input whose producer runs later this tick is a back-edge and reads
-    // Disconnected (engine.rs:479-482: buffers.get(output_id) is None)
-    std::vector<int64_t> pos(n_nodes, -1);
-    for (size_t i = 0; i < order_.size(); ++i) pos[order_[i]] = (int64_t)i;
-    for (uint32_t id : order_) {
-        Node& n = nodes_[id];
-        int lvl = 0;
-        for (PortRef& pr : n.in_src) {
-            if (pr.node < 0) continue;
-            if (pos[pr.node] < 0 || pos[pr.node] >= pos[id]) { pr.node = -1; continue; }  // back-edge => Disconnected
-            lvl = std::max(lvl, nodes_[pr.node].level + 1);
-        }
-        n.level = lvl;
-        n.in_src_orig = n.in_src;
-    }
-    // variable-length blobs of the build-specified modules
-    for (const Node& n : nodes_) {
-        if (n.kind == MX_KIND_FIR) {
-            mx_fir_params h{}; if (n.params.size() >= sizeof h) std::memcpy(&h, n.params.data(), sizeof h);
-            if (n.params.size() < sizeof h || h.n_taps == 0 || h.n_taps > 16384 || n.params.size() != sizeof h + (size_t)h.n_taps * sizeof(double))
-                throw Error(MX_ERR_INVALID, "mx_fir_params: params_len must be 8 + 8 * n_taps (1 <= n_taps <= 16384)");
-        } else if (n.kind == MX_KIND_RESAMPLE) {
-            mx_resample_params h{}; if (n.params.size() >= sizeof h) std::memcpy(&h, n.params.data(), sizeof h);
-            if (n.params.size() < sizeof h || !h.up || !h.down || !h.taps_per_phase || h.taps_per_phase > 4096 ||
-                n.params.size() != sizeof h + (size_t)h.up * h.taps_per_phase * sizeof(double))
-                throw Error(MX_ERR_INVALID, "mx_resample_params: params_len must be 16 + 8 * up * taps_per_phase");
-        }
-    }
-    // sample-rate domains: every input of a node must live in one domain; Resample multiplies it by up / down
-    auto gcd_u = [](uint64_t a, uint64_t b) { while (b) { const uint64_t t = a % b; a = b; b = t; } return a ? a : 1; };
-    for (uint32_t id : order_) {
-        Node& n = nodes_[id];
-        bool have = false; uint32_t dn = 1, dd = 1;
-        for (const PortRef& pr : n.in_src) {
-            if (pr.node < 0 || n.in_type[&pr - n.in_src.data()] == MX_VIDEO) continue;
-            const Node& sn = nodes_[pr.node];
-            if (have && (sn.dom_num != dn || sn.dom_den != dd)) throw Error(MX_ERR_TYPE, "inputs of a module live in different sample-rate domains");
-            dn = sn.dom_num; dd = sn.dom_den; have = true;
-        }
-        n.in_dom_num = dn; n.in_dom_den = dd; n.dom_num = dn; n.dom_den = dd;
-        if (n.kind == MX_KIND_RESAMPLE) {
-            mx_resample_params h; std::memcpy(&h, n.params.data(), sizeof h);
-            const uint64_t a = (uint64_t)dn * h.up, b = (uint64_t)dd * h.down, g = gcd_u(a, b);
-            n.dom_num = (uint32_t)(a / g); n.dom_den = (uint32_t)(b / g);
-        }
-        if ((spt_ * n.dom_num) % n.dom_den) throw Error(MX_ERR_INVALID, "resampling ratio does not give a whole number of samples per tick");
-        const bool rate_dependent = n.kind == MX_KIND_EQ_THREE || n.kind == MX_KIND_ENVELOPE || n.kind == MX_KIND_OSCILLATOR || n.kind == MX_KIND_FM_SINE;
-        if (n.kind == MX_KIND_PLOTTER && (n.in_dom_num != 1 || n.in_dom_den != 1))
-            throw Error(MX_ERR_INVALID, "Plotter is only accepted in the base sample-rate domain");
-        if (rate_dependent && (n.dom_num != 1 || n.dom_den != 1))
-            throw Error(MX_ERR_INVALID, "EqThree / Envelope / Oscillator / FmSine depend on the sample rate and are only accepted in the base domain");
-    }
-    for (Node& n : nodes_) { n.out_elided.assign(n.out_type.size(), 0); n.out_dup.assign(n.out_type.size(), 0); }
-    if (!(flags_ & MX_FLAG_NO_FUSE)) plan_fusion();
-    // groups: (level, kind); nodes folded into another node's kernel are never launched.  EqThree nodes also by the epilogue the compiler gave them (plain, -> Panner,
-    // -> Amplifier with a constant / a buffer / an inline Envelope as control; stereo or one float per frame): a launch group of ONE mode takes the kernel
-    // specialised for it -- sixteen strips of another mode among a thousand put the whole group on the general direct-load form (29 ms against 5, tools/ctl_probe.py)
-    auto eq_key = [&](const Node& nd) -> int {
-        if (nd.kind != MX_KIND_EQ_THREE) return 0;
-        const uint32_t epi = nd.fuse_amp >= 0 ? 2u : (nd.fuse_pan >= 0 ? 1u : 0u);
-        uint32_t fl = 0;
-        if (nd.fuse_amp >= 0 ? nodes_[nd.fuse_amp].out_dup[0] : (nd.fuse_pan >= 0 && nodes_[nd.fuse_pan].out_dup[0])) fl |= MX_EQF_MONO_DUP;
-        if (nd.fuse_env >= 0) fl |= MX_EQF_ENV;
-        const bool has_ctl = nd.fuse_amp >= 0 && nd.fuse_env < 0 && nodes_[nd.fuse_amp].in_src[1].node >= 0;
-        return 1 + eq_epilogue_mode(epi, fl, has_ctl);
-    };
-    for (Node& n : nodes_) n.sub_key = eq_key(n);
-    std::vector<uint32_t> sorted;
-    for (uint32_t id : order_) if (!nodes_[id].elided && nodes_[id].kind != MX_KIND_OUTPUT_DEVICE) sorted.push_back(id);
-    for (uint32_t id : order_) if (nodes_[id].kind == MX_KIND_OUTPUT_DEVICE) od_nodes_.push_back(id);
-    std::stable_sort(sorted.begin(), sorted.end(), [&](uint32_t a, uint32_t b) {
-        if (nodes_[a].level != nodes_[b].level) return nodes_[a].level < nodes_[b].level;
-        if (nodes_[a].kind != nodes_[b].kind) return nodes_[a].kind < nodes_[b].kind;
-        if (nodes_[a].sub_key != nodes_[b].sub_key) return nodes_[a].sub_key < nodes_[b].sub_key;
-        const uint64_t da = ((uint64_t)nodes_[a].dom_num << 32) | nodes_[a].dom_den, db = ((uint64_t)nodes_[b].dom_num << 32) | nodes_[b].dom_den;
-        return da < db;
-    });
-    for (uint32_t id : sorted) {
-        Node& n = nodes_[id];
-        if (groups_.empty() || groups_.back().level != n.level || groups_.back().kind != n.kind || groups_.back().sub_key != n.sub_key ||
-            groups_.back().dom_num != n.dom_num || groups_.back().dom_den != n.dom_den ||
-            groups_.back().in_dom_num != n.in_dom_num || groups_.back().in_dom_den != n.in_dom_den) {
-            Group g; g.level = n.level; g.kind = n.kind; g.sub_key = n.sub_key;
-            g.dom_num = n.dom_num; g.dom_den = n.dom_den; g.in_dom_num = n.in_dom_num; g.in_dom_den = n.in_dom_den;
-            groups_.push_back(std::move(g));
-        }
-        n.group = (int)groups_.size() - 1;
-        n.slot = (uint32_t)groups_.back().nodes.size();
-        groups_.back().nodes.push_back(id);
-    }
-    for (uint32_t id = 0; id < nodes_.size(); ++id) if (nodes_[id].kind == MX_KIND_PLOTTER && nodes_[id].group >= 0) plotter_nodes_.push_back(id);
-    for (uint32_t id : order_) if (nodes_[id].kind == MX_KIND_VIDEO_MIXER || nodes_[id].kind == MX_KIND_SOURCE_VIDEO || nodes_[id].kind == MX_KIND_VIDEO_TO_RGBA || nodes_[id].kind == MX_KIND_MONITOR) video_order_.push_back(id);
+    groups_.reserve(plan_.groups.size());
+    for (const PlanGroup& g : plan_.groups) groups_.emplace_back(g);
     // video nodes: per-node state lives on the host, pixels on the graph's stream
     for (Node& n : nodes_) {
         if (n.kind == MX_KIND_VIDEO_MIXER) {
             mx_video_mixer_params p; std::memcpy(&p, n.params.data(), sizeof p);
-            n.vmixer.reset(new VideoMixer(p, sr, stream_));
+            n.vmixer.reset(new VideoMixer(p, plan_.sample_rate, stream_));
+            if (!(flags_ & MX_FLAG_NO_FUSE)) n.vmixer->set_lazy_program(n.vlazy, tps_);
         }
         if (n.kind == MX_KIND_MONITOR) {
             mx_monitor_params p; std::memcpy(&p, n.params.data(), sizeof p);
-            if (p.width == 0 || p.height == 0 || (p.width & 1) || (p.height & 1) || p.width > 16384 || p.height > 16384)
-                throw Error(MX_ERR_INVALID, "monitor picture must be non-zero, even and at most 16384 a side");
             n.mon = std::make_unique<MonitorState>();
             n.mon->scaler = std::make_shared<Scaler>(p.width, p.height, stream_);
             if (n.params.size() == sizeof(mx_monitor_params_ex)) { mx_monitor_params_ex px; std::memcpy(&px, n.params.data(), sizeof px); n.mon->depth = px.queue_depth; }
-            // without a queue depth every tick of a submission keeps its scaled picture on the device until the next run
-            const uint64_t kept = (uint64_t)(n.mon->depth ? n.mon->depth : std::max<uint32_t>(1u, o.max_ticks_per_run)) * (((uint64_t)p.width + 63) & ~63ull) * p.height * 3 / 2;
-            if (kept > (64ull << 30)) throw Error(MX_ERR_NOMEM, "a Monitor that keeps every tick of a submission would hold more than 64 GiB of pictures: give it a queue depth (mx_monitor_params_ex) or fewer ticks per run");
         }
         if (n.kind == MX_KIND_SOURCE_VIDEO) n.vsrc = std::make_unique<VideoSourceState>();
         if (n.kind == MX_KIND_VIDEO_TO_RGBA) n.rgba = std::make_unique<RgbaSinkState>();
-        if (n.kind == MX_KIND_VIDEO_MIXER || n.kind == MX_KIND_SOURCE_VIDEO || n.kind == MX_KIND_VIDEO_TO_RGBA || n.kind == MX_KIND_MONITOR) has_video_ = true;
         n.vout.resize(n.out_type.size());
     }
-    // a VideoMixer whose program output feeds exactly one video node of this graph hands it over as an
-    // unevaluated cross-fade chain: a cascade of mixers becomes one fused pass (mx_k_video.hip k_fade_chain*)
-    if (!(flags_ & MX_FLAG_NO_FUSE)) {
-        std::vector<uint32_t> n_cons(nodes_.size(), 0); std::vector<uint8_t> ok(nodes_.size(), 1);
-        for (const Node& n : nodes_)
-            for (const PortRef& pr : n.in_src)
-                if (pr.node >= 0 && nodes_[pr.node].kind == MX_KIND_VIDEO_MIXER && pr.port == 0) {
-                    n_cons[pr.node]++;
-                    if (n.kind != MX_KIND_VIDEO_MIXER && n.kind != MX_KIND_VIDEO_TO_RGBA) ok[pr.node] = 0;
-                }
-        for (size_t i = 0; i < nodes_.size(); ++i)
-            if (nodes_[i].vmixer) { nodes_[i].vlazy = n_cons[i] == 1 && ok[i]; nodes_[i].vmixer->set_lazy_program(nodes_[i].vlazy, tps); }
-    }
-    // time-parallel EqThree tables (unused in MX_FLAG_EQ_EXACT mode)
-    {
-        std::vector<EqScanTab> tabs(4);
-        const long double fs[2] = {(long double)lo_f_, (long double)hi_f_};
-        for (int v = 0; v < 4; ++v) {
-            const uint64_t L = 4ull << v;
-            for (int f = 0; f < 2; ++f) {
-                for (int j = 0; j <= 64; ++j) toeplitz_pow(fs[f], L * (uint64_t)j, tabs[v].pw[f][j]);
-                for (int k = 0; k < 6; ++k) toeplitz_pow(fs[f], L << k, tabs[v].p2[f][k]);
-                // phase-A tables: s' = A s + b x + c with b = (f, f^2, f^3, f^4), c = VSA (1, f, f^2, f^3) (eq_three.rs:117-124)
-                const long double ff = fs[f], vsa = 1.0L / 4294967295.0L;
-                const long double b[4] = {ff, ff * ff, ff * ff * ff, ff * ff * ff * ff};
-                const long double c[4] = {vsa, vsa * ff, vsa * ff * ff, vsa * ff * ff * ff};
-                long double sum[4] = {0, 0, 0, 0};
-                for (uint64_t m = 0; m < 32; ++m) {
-                    long double am[4], hb[4];
-                    toeplitz_pow_ld(ff, m, am);
-                    toeplitz_apply_ld(am, b, hb);
-                    for (int q = 0; q < 4; ++q) tabs[v].h[f][m][q] = (double)hb[q];
-                    if (m < L) for (int q = 0; q < 4; ++q) sum[q] += am[q];
-                }
-                long double cz[4];
-                toeplitz_apply_ld(sum, c, cz);
-                for (int q = 0; q < 4; ++q) tabs[v].cz[f][q] = (double)cz[q];
-            }
-        }
-        eq_tabs_.alloc(tabs.size() * sizeof(EqScanTab));
-        hip_check(hipMemcpy(eq_tabs_.p, tabs.data(), tabs.size() * sizeof(EqScanTab), hipMemcpyHostToDevice), "hipMemcpy(eq tabs)");
-    }
-    // MX_FLAG_OVERLAP_TAIL: the last launch group, if it is a Mixer bank alone on the highest level of an audio-only graph, may run beside
-    // the next run's earlier groups; every port it reads gets a second buffer (the next run must not overwrite what it is still reading)
-    // AUTOMATIC (round 5) for graphs with at least 64 EqThree instances and submissions of at least 16 ticks, while the second buffers stay below MX_OVERLAP_AUTO_MAX_GB
-    // (default 32) and a quarter of the free device memory: the bank's launch is held back until the next run's EqThree launch has been placed (flush_deferred_tail,
-    // k_tail_gate) and then shares the SIMDs with it -- 1024 strips x 2048 ticks 5.42 -> 4.84 ms, x 256 ticks 0.915 -> 0.860, 128 strips x 2048 ticks 0.934 -> 0.875
-    // (profiles/r05/short_submission_regime.md).  Launched at once instead (round 4's form) the same mode LOST from 256 ticks up: the next run's k_env_ticks ran beside
-    // the bank (140 us instead of 9) with the EqThree launch waiting behind it.  MX_OVERLAP_AUTO=0 turns the automatism off; results are bit-identical either way.
-    { const char* const sm = getenv("MX_SIN_MODE"); sin_mode_ = sm ? atoi(sm) : 0; }   // (A/B and tests: mx_k_stream.hip SIN_MODE)
-    { const char* const gt = getenv("MX_TAIL_GATE_TEST"); gate_test_ = gt && atoi(gt); }
-    { const char* const er = getenv("MX_EQ_ENV_ROWS"); eq_env_rows_ = !(er && atoi(er) == 0); }   // (A/B, read per graph: tests build both kinds in one process)
-    { const char* const el = getenv("MX_EQ_LEAN"); eq_lean_ = !(el && atoi(el) == 0); }           // (likewise)
-    bool overlap_auto = false;
-    {
-        const char* const ae = getenv("MX_OVERLAP_AUTO");   // read per graph: tests build both kinds in one process
-        const bool auto_on = !(ae && atoi(ae) == 0);
-        const size_t max_ticks = spt_ ? cap_frames_ / spt_ : 0;
-        size_t n_eq = 0;
-        for (const Group& g : groups_) if (g.kind == MX_KIND_EQ_THREE) n_eq = std::max(n_eq, g.nodes.size());
-        overlap_auto = auto_on && eq_exact() && n_eq >= 64 && max_ticks >= 16;
-    }
-    // The tail is every Mixer group at the END of the launch order: a bank, or a bank and the buses above it (group buses -> master).  What its groups read from the
-    // groups before them is double-buffered; what they read from each other is not (they run in order on the one tail stream).
-    size_t t_first = groups_.size();
-    while (t_first > 0 && groups_[t_first - 1].kind == MX_KIND_MIXER) --t_first;
-    if (((flags_ & MX_FLAG_OVERLAP_TAIL) || overlap_auto) && !has_video_ && groups_.size() >= 2 && t_first >= 1 && t_first < groups_.size() &&
-        groups_[t_first - 1].level < groups_[t_first].level && plotter_nodes_.empty()) {
-        bool ok = true;
-        std::vector<std::pair<uint32_t, uint32_t>> ports;
-        for (size_t tg = t_first; tg < groups_.size() && ok; ++tg)
-            for (uint32_t id : groups_[tg].nodes) {
-                for (const PortRef& pr : nodes_[id].in_src) {
-                    if (pr.node < 0) continue;
-                    const Node& sn = nodes_[pr.node];
-                    if (sn.group >= (int)t_first && sn.group < (int)tg) continue;   // another tail group's output: same stream, in order
-                    if (sn.kind == MX_KIND_SOURCE_MONO || sn.kind == MX_KIND_SOURCE_STEREO || sn.group >= (int)tg) { ok = false; break; }   // a source is rewritten by the caller while the tail may still read it
-                    if (std::find(ports.begin(), ports.end(), std::make_pair((uint32_t)pr.node, (uint32_t)pr.port)) == ports.end()) ports.push_back({(uint32_t)pr.node, pr.port});
-                }
-                if (!ok) break;
-            }
-        if (ok && overlap_auto && !(flags_ & MX_FLAG_OVERLAP_TAIL)) {   // the second buffers must be affordable (an upper bound: every port as interleaved stereo)
-            const char* const ge = getenv("MX_OVERLAP_AUTO_MAX_GB");
-            const double max_gb = ge ? atof(ge) : 32.0;
-            size_t free_b = 0, total_b = 0;
-            if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
-            const double extra = (double)ports.size() * (double)cap_frames_ * 8.0;
-            if (extra > max_gb * 1073741824.0 || extra > (double)free_b / 4.0) ok = false;
-        }
-        if (ok) {
-            tail_gi_ = (int)t_first;
-            tail_auto_ = !(flags_ & MX_FLAG_OVERLAP_TAIL);
-            for (auto& pp : ports) nodes_[pp.first].out_off2[pp.second] = 0;   // marked; layout_slab gives it its offset
-            hip_check(hipStreamCreateWithFlags(&tail_stream_, hipStreamNonBlocking), "hipStreamCreate(tail)");
-            hip_check(hipEventCreateWithFlags(&ev_head_done_, hipEventDisableTiming), "hipEventCreate");
-            for (auto& e : ev_tail_done_) hip_check(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate");
-        }
-    }
+    upload_eq_tables();
+    if (accept_tail()) tail_gi_ = plan_.tail_first;
     layout_slab();
     build_descriptors();
     // OutputDevice: created from the empty state, its params applied as the adapter's first update
     for (Node& n : nodes_) {
         if (n.kind != MX_KIND_OUTPUT_DEVICE) continue;
-        n.od_frames = (uint32_t)(spt_ * n.in_dom_num / n.in_dom_den);
-        const OutState st0{-1, -1, 0u, 0u};
-        n.od_state.alloc(sizeof(OutState));
-        hip_check(hipMemcpy(n.od_state.p, &st0, sizeof st0, hipMemcpyHostToDevice), "hipMemcpy(output device state)");
-        n.od_rec.alloc(std::max<size_t>(1, cap_frames_ / spt_) * sizeof(OutTick));
-        od_update(n);
+        n.od = std::make_unique<OutputDeviceState>((uint32_t)(spt_ * n.in_dom_num / n.in_dom_den), od_ticks());
+        n.od->update(n.params.data(), od_ticks(), stream_);
         hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
     }
 }
 
+void Graph::open_device(const mx_graph_opts& o) {
+    if (o.device >= 0) { hip_check(hipSetDevice(o.device), "hipSetDevice"); device_ = o.device; }
+    else hip_check(hipGetDevice(&device_), "hipGetDevice");
+    if (o.stream) { stream_ = (hipStream_t)o.stream; own_stream_ = false; }
+    else { hip_check(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking), "hipStreamCreate"); own_stream_ = true; }
+    { const char* const sm = getenv("MX_SIN_MODE"); sin_mode_ = sm ? atoi(sm) : 0; }   // (A/B and tests: mx_k_stream.hip SIN_MODE)
+    { const char* const gt = getenv("MX_TAIL_GATE_TEST"); gate_test_ = gt && atoi(gt); }
+    { const char* const er = getenv("MX_EQ_ENV_ROWS"); eq_env_rows_ = !(er && atoi(er) == 0); }   // (A/B, read per graph: tests build both kinds in one process)
+    { const char* const el = getenv("MX_EQ_LEAN"); eq_lean_ = !(el && atoi(el) == 0); }           // (likewise)
+}
+
+void Graph::upload_eq_tables() {
+    // host-side coefficients: same libm as the reference on this host (eq_three.rs:113-115)
+    lo_f_ = 2.0 * std::sin(3.14159265358979323846264338327950288 * 420.0 / sample_rate_);
+    hi_f_ = 2.0 * std::sin(3.14159265358979323846264338327950288 * 2700.0 / sample_rate_);
+    std::vector<EqScanTab> tabs(4);
+    const long double fs[2] = {(long double)lo_f_, (long double)hi_f_};
+    for (int v = 0; v < 4; ++v) {
+        const uint64_t L = 4ull << v;
+        for (int f = 0; f < 2; ++f) {
+            for (int j = 0; j <= 64; ++j) toeplitz_pow(fs[f], L * (uint64_t)j, tabs[v].pw[f][j]);
+            for (int k = 0; k < 6; ++k) toeplitz_pow(fs[f], L << k, tabs[v].p2[f][k]);
+            // phase-A tables: s' = A s + b x + c with b = (f, f^2, f^3, f^4), c = VSA (1, f, f^2, f^3) (eq_three.rs:117-124)
+            const long double ff = fs[f], vsa = 1.0L / 4294967295.0L;
+            const long double b[4] = {ff, ff * ff, ff * ff * ff, ff * ff * ff * ff};
+            const long double c[4] = {vsa, vsa * ff, vsa * ff * ff, vsa * ff * ff * ff};
+            long double sum[4] = {0, 0, 0, 0};
+            for (uint64_t m = 0; m < 32; ++m) {
+                long double am[4], hb[4];
+                toeplitz_pow_ld(ff, m, am);
+                toeplitz_apply_ld(am, b, hb);
+                for (int q = 0; q < 4; ++q) tabs[v].h[f][m][q] = (double)hb[q];
+                if (m < L) for (int q = 0; q < 4; ++q) sum[q] += am[q];
+            }
+            long double cz[4];
+            toeplitz_apply_ld(sum, c, cz);
+            for (int q = 0; q < 4; ++q) tabs[v].cz[f][q] = (double)cz[q];
+        }
+    }
+    eq_tabs_.alloc(tabs.size() * sizeof(EqScanTab));
+    hip_check(hipMemcpy(eq_tabs_.p, tabs.data(), tabs.size() * sizeof(EqScanTab), hipMemcpyHostToDevice), "hipMemcpy(eq tabs)");
+}
+
+// The plan names the overlap-tail candidate (mx_plan.cpp tail_candidate); one the library chose itself is taken only while its second buffers stay below
+// MX_OVERLAP_AUTO_MAX_GB (default 32) and a quarter of the free device memory (an upper bound: every port as interleaved stereo).
+bool Graph::accept_tail() {
+    if (plan_.tail_first < 0) return false;
+    if (plan_.tail_auto) {
+        const char* const ge = getenv("MX_OVERLAP_AUTO_MAX_GB");
+        const double max_gb = ge ? atof(ge) : 32.0;
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
+        const double extra = (double)plan_.tail_ports.size() * (double)cap_frames_ * 8.0;
+        if (extra > max_gb * 1073741824.0 || extra > (double)free_b / 4.0) return false;
+    }
+    tail_auto_ = plan_.tail_auto;
+    hip_check(hipStreamCreateWithFlags(&tail_stream_, hipStreamNonBlocking), "hipStreamCreate(tail)");
+    hip_check(hipEventCreateWithFlags(&ev_head_done_, hipEventDisableTiming), "hipEventCreate");
+    for (auto& e : ev_tail_done_) hip_check(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate");
+    return true;
+}
+
+OutputDeviceState::OutputDeviceState(uint32_t frames_per_tick, size_t ticks) : frames(frames_per_tick) {
+    const OutState st0{-1, -1, 0u, 0u};
+    state.alloc(sizeof(OutState));
+    hip_check(hipMemcpy(state.p, &st0, sizeof st0, hipMemcpyHostToDevice), "hipMemcpy(output device state)");
+    rec.alloc(ticks * sizeof(OutTick));
+}
+
 // A channel count above any seen before: the scratch grows (its samples kept, the new part zero: Vec::resize, output_device.rs:185) and the
 // per-run buffers are sized for a whole submission of it.  The stream is quiescent (construction, or behind sync()).
-void Graph::od_grow(Node& n, uint32_t channels) {
-    if (channels <= n.od_cmax) return;
-    const size_t F = n.od_frames, ticks = std::max<size_t>(1, cap_frames_ / spt_);
-    DevBuf sc; sc.alloc(F * channels * sizeof(float));
-    hip_check(hipMemsetAsync(sc.p, 0, F * channels * sizeof(float), stream_), "hipMemsetAsync(output device scratch)");
-    if (n.od_cmax) hip_check(hipMemcpyAsync(sc.p, n.od_scratch.p, F * n.od_cmax * sizeof(float), hipMemcpyDeviceToDevice, stream_), "hipMemcpyAsync(output device scratch)");
-    hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
-    n.od_scratch = std::move(sc);
-    n.od_out.alloc(ticks * F * channels * sizeof(float));
-    n.od_part.alloc(ticks * out_route_blocks(F, channels) * sizeof(uint32_t));
-    n.od_cmax = channels;
+void OutputDeviceState::grow(uint32_t ch, size_t ticks, hipStream_t stream) {
+    if (ch <= cmax) return;
+    const size_t F = frames;
+    DevBuf sc; sc.alloc(F * ch * sizeof(float));
+    hip_check(hipMemsetAsync(sc.p, 0, F * ch * sizeof(float), stream), "hipMemsetAsync(output device scratch)");
+    if (cmax) hip_check(hipMemcpyAsync(sc.p, scratch.p, F * cmax * sizeof(float), hipMemcpyDeviceToDevice, stream), "hipMemcpyAsync(output device scratch)");
+    hip_check(hipStreamSynchronize(stream), "hipStreamSynchronize");
+    scratch = std::move(sc);
+    out.alloc(ticks * F * ch * sizeof(float));
+    part.alloc(ticks * out_route_blocks(F, ch) * sizeof(uint32_t));
+    cmax = ch;
 }
 
-// OutputDevice::update (output_device.rs:152-169) for n.params; `device` has already been resolved by the adapter into `channels`
-void Graph::od_update(Node& n) {
-    mx_output_device_params p; std::memcpy(&p, n.params.data(), sizeof p);
-    n.od_channels = p.channels;
+// OutputDevice::update (output_device.rs:152-169); `device` has already been resolved by the adapter into `channels`
+void OutputDeviceState::update(const void* params, size_t ticks, hipStream_t stream) {
+    mx_output_device_params p; std::memcpy(&p, params, sizeof p);
+    channels = p.channels;
     if (!p.channels) return;   // no stream: the stored left / right stay, nothing is zeroed
-    od_grow(n, p.channels);
+    grow(p.channels, ticks, stream);
     // the STORED (filtered) assignment against the requested one: a repeated request for a channel the stream lacks zeroes again every time
-    if (n.od_left != p.left || n.od_right != p.right)
-        hip_check(hipMemsetAsync(n.od_scratch.p, 0, (size_t)n.od_frames * n.od_cmax * sizeof(float), stream_), "hipMemsetAsync(output device scratch)");
-    n.od_left = p.left >= 0 && (uint32_t)p.left < p.channels ? p.left : -1;
-    n.od_right = p.right >= 0 && (uint32_t)p.right < p.channels ? p.right : -1;
+    if (left != p.left || right != p.right)
+        hip_check(hipMemsetAsync(scratch.p, 0, (size_t)frames * cmax * sizeof(float), stream), "hipMemsetAsync(output device scratch)");
+    left = p.left >= 0 && (uint32_t)p.left < p.channels ? p.left : -1;
+    right = p.right >= 0 && (uint32_t)p.right < p.channels ? p.right : -1;
 }
 
-size_t Graph::od_offset(const Node& n, uint32_t tick) const {
+size_t OutputDeviceState::offset(uint32_t tick) const {
     size_t off = 0;
-    for (const Node::OdSpan& sp : n.od_spans)
-        if (tick > sp.first) off += (size_t)std::min(tick - sp.first, sp.n) * n.od_frames * sp.channels;
+    for (const Span& sp : spans)
+        if (tick > sp.first) off += (size_t)std::min(tick - sp.first, sp.n) * frames * sp.channels;
     return off;
+}
+
+// the module persists across a topology edit: its stored assignment, scratch, clip / lag times and statuses, a pending lag note
+void OutputDeviceState::adopt(OutputDeviceState& old, size_t ticks, hipStream_t stream) {
+    grow(old.cmax, ticks, stream);
+    if (old.cmax) {
+        const size_t bytes = (size_t)std::min(frames * cmax, old.frames * old.cmax) * sizeof(float);
+        hip_check(hipMemcpyAsync(scratch.p, old.scratch.p, bytes, hipMemcpyDeviceToDevice, stream), "hipMemcpyAsync(output device scratch)");
+    }
+    hip_check(hipMemcpyAsync(state.p, old.state.p, sizeof(OutState), hipMemcpyDeviceToDevice, stream), "hipMemcpyAsync(output device state)");
+    channels = old.channels; left = old.left; right = old.right;
+    if (old.lag.exchange(false)) lag.store(true);
 }
 
 // The span's OutputDevice launches.  One that reads an output of the tail (MX_FLAG_OVERLAP_TAIL / automatic mode) is held back with it and goes
 // behind it on the tail stream, where the events that join the tail cover it; any other runs on stream_ after the span's groups.
 void Graph::launch_outputs(uint64_t t0, uint32_t call_off, uint32_t n_calls, ProfSpan* prof) {
     bool here = false;
-    for (uint32_t id : od_nodes_) {
+    for (uint32_t id : plan_.od_nodes) {
         Node& n = nodes_[id];
         const PortRef src = n.in_src[0];
         int32_t o = src.node;
         while (o >= 0 && nodes_[o].elided && nodes_[o].owner >= 0) o = nodes_[o].owner;
         const bool on_tail = overlap_this_run_ && o >= 0 && nodes_[o].group >= tail_gi_;
-        const uint32_t C = n.od_channels;
-        const size_t base = od_offset(n, call_off);
-        n.od_spans.push_back(Node::OdSpan{call_off, n_calls, C});
+        OutputDeviceState& od = *n.od;
+        const uint32_t C = od.channels;
+        const size_t base = od.offset(call_off);
+        od.spans.push_back(OutputDeviceState::Span{call_off, n_calls, C});
         OutRun r{};
         r.in = in_ptr(n, 0, false, parity_); r.dup = src.node >= 0 && nodes_[src.node].out_dup[src.port] ? 1u : 0u;
-        r.frames = n.od_frames; r.channels = C; r.left = n.od_left; r.right = n.od_right; r.n_ticks = n_calls;
-        r.scratch = (float*)n.od_scratch.p; r.out = (float*)n.od_out.p + base; r.partial = (uint32_t*)n.od_part.p;
-        r.state = (OutState*)n.od_state.p; r.rec = (OutTick*)n.od_rec.p + call_off;
-        r.t0 = t0; r.spt = (uint32_t)spt_; r.rate = (uint32_t)sample_rate_; r.lag = call_off == 0 && n.od_lag_run ? 1u : 0u;
+        r.frames = od.frames; r.channels = C; r.left = od.left; r.right = od.right; r.n_ticks = n_calls;
+        r.scratch = (float*)od.scratch.p; r.out = (float*)od.out.p + base; r.partial = (uint32_t*)od.part.p;
+        r.state = (OutState*)od.state.p; r.rec = (OutTick*)od.rec.p + call_off;
+        r.t0 = t0; r.spt = (uint32_t)spt_; r.rate = (uint32_t)sample_rate_; r.lag = call_off == 0 && od.lag_run ? 1u : 0u;
         if (on_tail) deferred_.outs.push_back(r);
         else { launch_output_device(r, stream_); here = true; }
     }
@@ -504,8 +295,7 @@ void Graph::end_auto_tail() {
         for (size_t k = 0; k < n.out_type.size(); ++k) {
             if (n.out_off2[k] == SIZE_MAX) continue;
             if (parity_ && n.out_off[k] != SIZE_MAX) {
-                const size_t fl = (n.out_dup[k] ? 1 : floats_per_frame(n.out_type[k])) * (cap_frames_ * n.dom_num / n.dom_den + 1);
-                hip_check(hipMemcpyAsync((float*)slab_.p + n.out_off[k], (const float*)slab_.p + n.out_off2[k], fl * sizeof(float), hipMemcpyDeviceToDevice, stream_), "hipMemcpyAsync(D2D)");
+                hip_check(hipMemcpyAsync((float*)slab_.p + n.out_off[k], (const float*)slab_.p + n.out_off2[k], port_floats(n, k, cap_frames_) * sizeof(float), hipMemcpyDeviceToDevice, stream_), "hipMemcpyAsync(D2D)");
             }
             n.out_off2[k] = SIZE_MAX;
         }
@@ -534,109 +324,14 @@ Graph::~Graph() {
     if (own_stream_ && stream_) { video_stream_retired(stream_); multiview_stream_retired(stream_); (void)hipStreamDestroy(stream_); }
 }
 
-// Graph-compiler fusion.  A port buffer is a per-tick temporary of Engine::run_tick
-// (src/engine.rs:461,504-506), observable only through connections, so a port whose only consumers
-// are folded into its producer's kernel need not exist.  Two patterns, both bit-identical to the
-// separate modules because the folded arithmetic is applied to the very f32 the producer stores:
-//   F1  EqThree -> StereoPanner(L = R = that EQ) [-> Amplifier input]   => epilogue of the EQ kernel
-//   F2  Trigger (single consumer) -> Envelope gate                       => constant gate, no buffer
-void Graph::plan_fusion() {
-    const size_t N = nodes_.size();
-    std::vector<std::vector<std::vector<std::pair<uint32_t, uint32_t>>>> cons(N);
-    for (size_t i = 0; i < N; ++i) cons[i].resize(nodes_[i].out_type.size());
-    for (uint32_t id : order_)
-        for (uint32_t k = 0; k < nodes_[id].in_src.size(); ++k) {
-            const PortRef pr = nodes_[id].in_src[k];
-            if (pr.node >= 0) cons[pr.node][pr.port].push_back({id, k});
-        }
-    // does `from` (transitively, through its inputs) depend on `target`?  bounded search, conservative
-    auto depends_on = [&](int32_t from, uint32_t target) {
-        std::vector<int32_t> st{from};
-        size_t visited = 0;
-        while (!st.empty()) {
-            const int32_t x = st.back(); st.pop_back();
-            if ((uint32_t)x == target) return true;
-            if (++visited > 256) return true;
-            for (const PortRef& pr : nodes_[x].in_src) if (pr.node >= 0) st.push_back(pr.node);
-        }
-        return false;
-    };
-    for (uint32_t e : order_) {
-        Node& E = nodes_[e];
-        if (E.kind != MX_KIND_EQ_THREE) continue;
-        const auto& c = cons[e][0];
-        if (c.size() != 2 || c[0].first != c[1].first || c[0].second == c[1].second) continue;
-        const uint32_t p = c[0].first;
-        Node& P = nodes_[p];
-        if (P.kind != MX_KIND_STEREO_PANNER || P.elided) continue;
-        E.fuse_pan = (int32_t)p; E.out_elided[0] = 1;
-        P.elided = true; P.owner = (int32_t)e;
-        const auto& pc = cons[p][0];
-        if (pc.size() == 1 && nodes_[pc[0].first].kind == MX_KIND_AMPLIFIER && pc[0].second == 0) {
-            const uint32_t a = pc[0].first;
-            Node& A = nodes_[a];
-            const PortRef ctl = A.in_src[1];
-            if (ctl.node < 0 || !depends_on(ctl.node, e)) {
-                E.fuse_amp = (int32_t)a; P.out_elided[0] = 1;
-                A.elided = true; A.owner = (int32_t)e;
-                if (ctl.node >= 0) E.level = std::max(E.level, nodes_[ctl.node].level + 1);   // the fused kernel reads the control port
-            }
-        }
-    }
-    for (uint32_t v : order_) {
-        Node& V = nodes_[v];
-        if (V.kind != MX_KIND_ENVELOPE) continue;
-        const PortRef g = V.in_src[0];
-        if (g.node < 0 || nodes_[g.node].kind != MX_KIND_TRIGGER || cons[g.node][0].size() != 1) continue;
-        Node& G = nodes_[g.node];
-        V.fuse_trigger = g.node;
-        G.elided = true; G.owner = (int32_t)v; G.out_elided[0] = 1;
-    }
-    for (uint32_t e : order_) {
-        Node& E = nodes_[e];
-        if (E.kind != MX_KIND_EQ_THREE || E.fuse_pan < 0) continue;
-        // F3: the fused Amplifier's control is a constant-gate Envelope that feeds nothing else: its closed form
-        // (envelope.rs:34-58) is evaluated in the epilogue; for a constant gate only the run's first sample can
-        // change the Envelope's state, so no per-sample state machine is needed
-        if (E.fuse_amp >= 0) {
-            const PortRef ctl = nodes_[E.fuse_amp].in_src[1];
-            if (ctl.node >= 0 && nodes_[ctl.node].kind == MX_KIND_ENVELOPE && nodes_[ctl.node].fuse_trigger >= 0 &&
-                cons[ctl.node][0].size() == 1) {
-                Node& V = nodes_[ctl.node];
-                E.fuse_env = ctl.node;
-                V.elided = true; V.owner = (int32_t)e; V.out_elided[0] = 1;
-            }
-        }
-        // F4: the fused result is stereo with L == R by construction; if only Mixers read it, store one float per frame
-        const uint32_t x = (uint32_t)(E.fuse_amp >= 0 ? E.fuse_amp : E.fuse_pan);
-        const auto& xc = cons[x][0];
-        bool only_mixers = !xc.empty();
-        for (const auto& c : xc) only_mixers = only_mixers && (nodes_[c.first].kind == MX_KIND_MIXER || nodes_[c.first].kind == MX_KIND_OUTPUT_DEVICE);   // (an OutputDevice expands it)
-        if (only_mixers) nodes_[x].out_dup[0] = 1;
-    }
-}
-
+// where mx::layout_slab puts the ports for cap_frames_ (second buffers while the tail mode is on), and the slab itself
 void Graph::layout_slab() {
-    size_t off = 0;
-    auto bump = [&](size_t floats) { size_t o = off; off += (floats + 63) & ~(size_t)63; return o; };  // 256-byte aligned
-    // Disconnected inputs read this region (io.rs:8-9); a node behind a Resample runs cap_frames * up / down frames per
-    // launch, so the region is sized for the largest sample-rate domain of the graph
-    size_t zero_frames = cap_frames_;
-    for (const Node& n : nodes_) {
-        zero_frames = std::max(zero_frames, cap_frames_ * n.dom_num / n.dom_den + 1);
-        zero_frames = std::max(zero_frames, cap_frames_ * n.in_dom_num / n.in_dom_den + 1);
-    }
-    zero_off_ = bump(2 * zero_frames);
-    for (Node& n : nodes_)
-        for (size_t k = 0; k < n.out_type.size(); ++k)
-        {
-            const size_t fl = (n.out_dup[k] ? 1 : floats_per_frame(n.out_type[k])) * (cap_frames_ * n.dom_num / n.dom_den + 1);
-            n.out_off[k] = n.out_elided[k] ? SIZE_MAX : bump(fl);
-            if (n.out_off2[k] != SIZE_MAX) n.out_off2[k] = n.out_elided[k] ? SIZE_MAX : bump(fl);
-        }
-    slab_floats_ = off;
-    slab_.alloc(off * sizeof(float));
-    hip_check(hipMemsetAsync(slab_.p, 0, off * sizeof(float), stream_), "hipMemsetAsync(slab)");
+    SlabLayout L = mx::layout_slab(plan_, cap_frames_, tail_gi_ >= 0);
+    for (size_t i = 0; i < nodes_.size(); ++i) { nodes_[i].out_off = std::move(L.out_off[i]); nodes_[i].out_off2 = std::move(L.out_off2[i]); }
+    zero_off_ = L.zero_off;
+    slab_floats_ = L.floats;
+    slab_.alloc(L.floats * sizeof(float));
+    hip_check(hipMemsetAsync(slab_.p, 0, L.floats * sizeof(float), stream_), "hipMemsetAsync(slab)");
     hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
 }
 
@@ -728,7 +423,7 @@ void Graph::upload_group_one(Group& g, uint32_t parity) {
             d[i] = e;
             const int em = eq_epilogue_mode(e.epi, e.flags, e.ctl != nullptr);
             g.eq_mode = i == 0 ? em : (g.eq_mode == em ? em : -1);
-            // the groups were cut by eq_key()'s idea of this mode (from the fusion plan); the descriptor's is the one the kernels see.  If they ever disagree a group
+            // the groups were cut by the plan's idea of this mode (sub_key, from the fusion plan: mx_plan.cpp cut_groups); the descriptor's is the one the kernels see.  If they ever disagree a group
             // silently falls to the general direct-load kernel (29 ms against 5): refuse loudly instead
             if (nd.sub_key != 0 && nd.sub_key != 1 + em && !eq_mode_warned_) {   // (results are right either way: say it, once per graph, and go on)
                 eq_mode_warned_ = true;
@@ -817,7 +512,7 @@ void Graph::upload_group_one(Group& g, uint32_t parity) {
     }
     case MX_KIND_FIR: {
         size_t tt = 0, th = 0; g.max_taps = 0;
-        for (uint32_t id : g.nodes) { mx_fir_params h; std::memcpy(&h, nodes_[id].params.data(), sizeof h); tt += h.n_taps; th += h.n_taps; g.max_taps = std::max(g.max_taps, h.n_taps); }
+        for (uint32_t id : g.nodes) { const uint32_t h = history_frames(nodes_[id]); tt += h; th += h; g.max_taps = std::max(g.max_taps, h); }
         std::vector<double> taps(tt);
         if (g.extra.bytes < tt * sizeof(double) || !g.extra.p) g.extra.alloc(tt * sizeof(double));
         if (!g.state.p) { g.state.alloc(th * sizeof(float2)); hip_check(hipMemset(g.state.p, 0, th * sizeof(float2)), "hipMemset"); }
@@ -825,10 +520,10 @@ void Graph::upload_group_one(Group& g, uint32_t parity) {
         size_t o = 0;
         for (size_t i = 0; i < n; ++i) {
             const Node& nd = nodes_[g.nodes[i]];
-            mx_fir_params h; std::memcpy(&h, nd.params.data(), sizeof h);
-            std::memcpy(&taps[o], nd.params.data() + sizeof h, (size_t)h.n_taps * sizeof(double));
-            d[i] = FirDesc{in_ptr(nd, 0, false, parity), out_ptr(nd, 0, parity), (const double*)g.extra.p + o, (float2*)g.state.p + o, h.n_taps, 0u};
-            o += h.n_taps;
+            const uint32_t n_taps = history_frames(nd);
+            std::memcpy(&taps[o], nd.params.data() + sizeof(mx_fir_params), (size_t)n_taps * sizeof(double));
+            d[i] = FirDesc{in_ptr(nd, 0, false, parity), out_ptr(nd, 0, parity), (const double*)g.extra.p + o, (float2*)g.state.p + o, n_taps, 0u};
+            o += n_taps;
         }
         hip_check(hipMemcpy(g.extra.p, taps.data(), tt * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(fir taps)");
         up(desc, d.data(), n * sizeof(FirDesc));
@@ -838,12 +533,13 @@ void Graph::upload_group_one(Group& g, uint32_t parity) {
         size_t tt = 0, th = 0; g.max_taps = 0;
         g.rs_tab_doubles = 0; g.rs_win_frames = 0; g.rs_common_up = 0; g.rs_common_taps = 0; g.rs_common_down = 0; bool rs_first = true;
         for (uint32_t id : g.nodes) {
-            mx_resample_params h; std::memcpy(&h, nodes_[id].params.data(), sizeof h);
-            tt += (size_t)h.up * h.taps_per_phase; th += h.taps_per_phase; g.max_taps = std::max(g.max_taps, h.taps_per_phase);
-            g.rs_tab_doubles = (uint32_t)std::min<uint64_t>(0xffffffffu, std::max<uint64_t>(g.rs_tab_doubles, (uint64_t)h.up * h.taps_per_phase));
-            g.rs_win_frames = (uint32_t)std::min<uint64_t>(0xffffffffu, std::max<uint64_t>(g.rs_win_frames, (uint64_t)255 * h.down / h.up + 2 + h.taps_per_phase));
-            if (rs_first) { g.rs_common_up = h.up; g.rs_common_taps = h.taps_per_phase; g.rs_common_down = h.down; rs_first = false; }   // every node's ratio and taps per phase, where they agree
-            else { if (g.rs_common_up != h.up) g.rs_common_up = 0; if (g.rs_common_taps != h.taps_per_phase) g.rs_common_taps = 0; if (g.rs_common_down != h.down) g.rs_common_down = 0; }
+            mx_resample_params h; std::memcpy(&h, nodes_[id].params.data(), sizeof h);   // the ratio; the taps per phase are the plan's history length
+            const uint32_t tpp = history_frames(nodes_[id]);
+            tt += (size_t)h.up * tpp; th += tpp; g.max_taps = std::max(g.max_taps, tpp);
+            g.rs_tab_doubles = (uint32_t)std::min<uint64_t>(0xffffffffu, std::max<uint64_t>(g.rs_tab_doubles, (uint64_t)h.up * tpp));
+            g.rs_win_frames = (uint32_t)std::min<uint64_t>(0xffffffffu, std::max<uint64_t>(g.rs_win_frames, (uint64_t)255 * h.down / h.up + 2 + tpp));
+            if (rs_first) { g.rs_common_up = h.up; g.rs_common_taps = tpp; g.rs_common_down = h.down; rs_first = false; }   // every node's ratio and taps per phase, where they agree
+            else { if (g.rs_common_up != h.up) g.rs_common_up = 0; if (g.rs_common_taps != tpp) g.rs_common_taps = 0; if (g.rs_common_down != h.down) g.rs_common_down = 0; }
         }
         std::vector<double> taps(tt);
         if (g.extra.bytes < tt * sizeof(double) || !g.extra.p) g.extra.alloc(tt * sizeof(double));
@@ -853,10 +549,11 @@ void Graph::upload_group_one(Group& g, uint32_t parity) {
         for (size_t i = 0; i < n; ++i) {
             const Node& nd = nodes_[g.nodes[i]];
             mx_resample_params h; std::memcpy(&h, nd.params.data(), sizeof h);
-            const size_t cnt = (size_t)h.up * h.taps_per_phase;
+            const uint32_t tpp = history_frames(nd);
+            const size_t cnt = (size_t)h.up * tpp;
             std::memcpy(&taps[o], nd.params.data() + sizeof h, cnt * sizeof(double));
-            d[i] = ResampleDesc{in_ptr(nd, 0, false, parity), out_ptr(nd, 0, parity), (const double*)g.extra.p + o, (float2*)g.state.p + oh, h.up, h.down, h.taps_per_phase, 0u};
-            o += cnt; oh += h.taps_per_phase;
+            d[i] = ResampleDesc{in_ptr(nd, 0, false, parity), out_ptr(nd, 0, parity), (const double*)g.extra.p + o, (float2*)g.state.p + oh, h.up, h.down, tpp, 0u};
+            o += cnt; oh += tpp;
         }
         hip_check(hipMemcpy(g.extra.p, taps.data(), tt * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(resample taps)");
         up(desc, d.data(), n * sizeof(ResampleDesc));
@@ -892,7 +589,7 @@ void Graph::apply_params(uint32_t node, const void* params, size_t len) {
     Node& n = nodes_[node];
     if (len) std::memcpy(n.params.data(), params, len);
     if (n.kind == MX_KIND_TRIGGER) { ++gates_version_; return; }
-    if (n.kind == MX_KIND_OUTPUT_DEVICE) { od_update(n); return; }
+    if (n.kind == MX_KIND_OUTPUT_DEVICE) { n.od->update(n.params.data(), od_ticks(), stream_); return; }
     if (n.kind == MX_KIND_VIDEO_MIXER && n.vmixer) {
         mx_video_mixer_params p; std::memcpy(&p, n.params.data(), sizeof p);
         n.vmixer->update(p);
@@ -1042,8 +739,8 @@ void Graph::bind_source(uint32_t node, const void* dev) {
 void Graph::set_input_enabled(uint32_t node, uint32_t port, bool enabled) {
     if (node >= nodes_.size() || port >= nodes_[node].in_src.size()) throw Error(MX_ERR_INVALID, "input terminal out of range");
     Node& n = nodes_[node];
-    if (n.in_src_orig.size() != n.in_src.size()) return;  // node is outside the run order
-    const PortRef want = enabled ? n.in_src_orig[port] : PortRef{};
+    if (n.pos < 0) return;  // node is outside the run order
+    const PortRef want = enabled ? plan_.nodes[node].in_src[port] : PortRef{};   // the plan keeps what was connected
     if (want.node == n.in_src[port].node && want.port == n.in_src[port].port) return;
     sync();
     n.in_src[port] = want;
@@ -1075,7 +772,7 @@ void Graph::run(uint64_t t0, size_t fpc, uint32_t n_calls, float* ms_by_kind, fl
     if (frames > cap_frames_) { drop_schedules(); throw Error(MX_ERR_INVALID, "n_ticks exceeds max_ticks_per_run"); }
     if (n_calls == 0 || fpc == 0) { drop_schedules(); last_calls_ = n_calls; last_frames_per_call_ = fpc; for (AudioTapSet* s : taps_) s->empty_run(); scopes_.empty_run(); multiview_.empty_run(); return; }
     // graded / keyed / matted / placed video sources: a frame the transform cannot take fails the run HERE, before anything of it is launched or any node's state has moved
-    for (uint32_t id : video_order_) {
+    for (uint32_t id : plan_.video_order) {
         const VideoSourceState* vs = nodes_[id].vsrc.get();
         if (!vs || !vs->transform.active()) continue;
         const uint64_t tick0 = t0 / spt_;
@@ -1120,22 +817,22 @@ void Graph::run(uint64_t t0, size_t fpc, uint32_t n_calls, float* ms_by_kind, fl
         }
     };
     if (any_sched) apply_at(0);
-    for (uint32_t id : od_nodes_) {   // the lag flag is swapped by the run's first tick (output_device.rs:219); the spans of this run replace the last run's
+    for (uint32_t id : plan_.od_nodes) {   // the lag flag is swapped by the run's first tick (output_device.rs:219); the spans of this run replace the last run's
         Node& n = nodes_[id];
-        n.od_lag_run = n.od_lag->exchange(false);
-        n.od_spans.clear();
+        n.od->lag_run = n.od->lag.exchange(false);
+        n.od->spans.clear();
         // a scheduled update to more channels than any before: the buffers grow now, not between two spans (the hand-off holds every span's ticks)
         uint32_t cmax = 0;
         for (const Node::SchedEv& ev : n.sched) { mx_output_device_params q; std::memcpy(&q, ev.params.data(), sizeof q); cmax = std::max(cmax, q.channels); }
-        if (cmax > n.od_cmax) { sync(); od_grow(n, cmax); }
+        if (cmax > n.od->cmax) { sync(); n.od->grow(cmax, od_ticks(), stream_); }
     }
-    for (uint32_t id : video_order_) if (nodes_[id].mon) nodes_[id].mon->ticks.clear();
+    for (uint32_t id : plan_.video_order) if (nodes_[id].mon) nodes_[id].mon->ticks.clear();
     scopes_.begin_run(n_calls);      // the records this run will count into are cleared now, on stream_ ahead of every launch of the run
     multiview_.begin_run(n_calls);   // the multiviewer renders the run's LAST recorded tick only
 
     // Plotter bookkeeping is host logic (plotter.rs:37-40): count += 1 per call, fire on every 6th
     size_t total_fired = 0;
-    for (uint32_t pid : plotter_nodes_) {
+    for (uint32_t pid : plan_.plotter_nodes) {
         Node& n = nodes_[pid];
         n.plot_fired.assign(n_calls, 0);
         n.plot_slot.assign(n_calls, -1);
@@ -1339,12 +1036,12 @@ void Graph::run_span(uint64_t t0, size_t fpc, uint32_t call_off, uint32_t n_call
         ++gi;
     }
     // video sub-graph: tick by tick (frames arrive per tick; nothing to batch over time)
-    if (has_video_) {
+    if (plan_.has_video) {
         for (uint32_t c = 0; c < n_calls; ++c) run_video_tick(t0 + (uint64_t)c * fpc, call_off + c);
         flush_scales(stream_);
-        for (uint32_t id : video_order_) if (nodes_[id].rgba) nodes_[id].rgba->end_run(stream_);   // the last ticks' sinks
+        for (uint32_t id : plan_.video_order) if (nodes_[id].rgba) nodes_[id].rgba->end_run(stream_);   // the last ticks' sinks
     }
-    if (prof && has_video_) hip_check(hipEventRecord(prof->video_end, stream_), "hipEventRecord");
+    if (prof && plan_.has_video) hip_check(hipEventRecord(prof->video_end, stream_), "hipEventRecord");
     // after everything else of the span on stream_ (the video section included): its profile interval starts at the latest event recorded there
     launch_outputs(t0, call_off, n_calls, prof);
     // the port buffers hold every tick of the run: the audio tap sets go once, after its last span, in this order on either stream
@@ -1397,7 +1094,7 @@ uint32_t Graph::profile_collect(float* ms_by_kind, float* ms_total) {
             if (ms_by_kind) ms_by_kind[groups_[i].kind] += ms;
             perf_group_ms_[i] = ms;
         }
-        if (has_video_) {
+        if (plan_.has_video) {
             const float ms = elapsed(last, p.video_end);
             if (ms_by_kind) ms_by_kind[MX_KIND_VIDEO_MIXER] += ms;
             perf_group_ms_[groups_.size()] = ms;
@@ -1450,9 +1147,7 @@ std::vector<Graph::StateLoc> Graph::state_locs(uint32_t id) const {
         if (n.group >= 0 && groups_[n.group].state.p) {
             size_t off = 0, mine = 0;
             for (uint32_t other : groups_[n.group].nodes) {
-                size_t h;
-                if (n.kind == MX_KIND_FIR) { mx_fir_params q; std::memcpy(&q, nodes_[other].params.data(), sizeof q); h = q.n_taps; }
-                else { mx_resample_params q; std::memcpy(&q, nodes_[other].params.data(), sizeof q); h = q.taps_per_phase; }
+                const size_t h = history_frames(nodes_[other]);
                 if (other == id) { mine = h; break; }
                 off += h;
             }
@@ -1469,8 +1164,7 @@ size_t Graph::state_bytes(uint32_t id) const {
     switch (n.kind) {
     case MX_KIND_EQ_THREE: return sizeof(EqState);
     case MX_KIND_ENVELOPE: return sizeof(EnvState);
-    case MX_KIND_FIR: { mx_fir_params q; std::memcpy(&q, n.params.data(), sizeof q); return (size_t)q.n_taps * sizeof(float2); }
-    case MX_KIND_RESAMPLE: { mx_resample_params q; std::memcpy(&q, n.params.data(), sizeof q); return (size_t)q.taps_per_phase * sizeof(float2); }
+    case MX_KIND_FIR: case MX_KIND_RESAMPLE: return (size_t)history_frames(n) * sizeof(float2);
     default: return 0;
     }
 }
@@ -1530,14 +1224,8 @@ void Graph::adopt_state(Graph& old, const int32_t* old_of_new, size_t n) {
             nn.vmixer->update(p);
         }
         if (nn.kind == MX_KIND_OUTPUT_DEVICE) {   // the module persists: its stored assignment, scratch, clip / lag times and statuses, a pending lag note
-            od_grow(nn, on.od_cmax);
-            if (on.od_cmax) {
-                const size_t bytes = (size_t)std::min(nn.od_frames * nn.od_cmax, on.od_frames * on.od_cmax) * sizeof(float);
-                hip_check(hipMemcpyAsync(nn.od_scratch.p, on.od_scratch.p, bytes, hipMemcpyDeviceToDevice, stream_), "hipMemcpyAsync(output device scratch)");
-            }
-            hip_check(hipMemcpyAsync(nn.od_state.p, on.od_state.p, sizeof(OutState), hipMemcpyDeviceToDevice, stream_), "hipMemcpyAsync(output device state)");
-            nn.od_channels = on.od_channels; nn.od_left = on.od_left; nn.od_right = on.od_right; nn.params = on.params;   // (mixlab_gpu.h: the new build's params are not applied)
-            if (on.od_lag->exchange(false)) nn.od_lag->store(true);
+            nn.od->adopt(*on.od, od_ticks(), stream_);
+            nn.params = on.params;   // (mixlab_gpu.h: the new build's params are not applied)
         }
         if (nn.vsrc) nn.vsrc->adopt(*on.vsrc);
     }
@@ -1573,17 +1261,17 @@ Graph::Perf Graph::performance_info(uint64_t* module_us, size_t cap) {
         accounted += us;
         if (module_us) for (uint32_t id : members) module_us[id] += (uint64_t)(us / (double)members.size() + 0.5);
     }
-    if (has_video_ && perf_group_ms_.size() > groups_.size()) {   // the per-tick video section
+    if (plan_.has_video && perf_group_ms_.size() > groups_.size()) {   // the per-tick video section
         std::vector<uint32_t> members;
         for (size_t i = 0; i < nodes_.size(); ++i) if (nodes_[i].kind == MX_KIND_VIDEO_MIXER || nodes_[i].kind == MX_KIND_VIDEO_TO_RGBA || nodes_[i].kind == MX_KIND_MONITOR) members.push_back((uint32_t)i);
         const double us = perf_group_ms_[groups_.size()] * 1000.0 / calls;
         accounted += us;
         if (module_us) for (uint32_t id : members) module_us[id] += (uint64_t)(us / (double)members.size() + 0.5);
     }
-    if (!od_nodes_.empty()) {   // OutputDevice launches, split evenly over the nodes
+    if (!plan_.od_nodes.empty()) {   // OutputDevice launches, split evenly over the nodes
         const double us = perf_od_ms_ * 1000.0 / calls;
         accounted += us;
-        if (module_us) for (uint32_t id : od_nodes_) module_us[id] += (uint64_t)(us / (double)od_nodes_.size() + 0.5);
+        if (module_us) for (uint32_t id : plan_.od_nodes) module_us[id] += (uint64_t)(us / (double)plan_.od_nodes.size() + 0.5);
     }
     pf.engine_us = (uint64_t)std::max(0.0, tick_us - accounted + 0.5);             // PerformanceAccount::Engine = tick - modules (timing.rs:43)
     return pf;
@@ -1616,19 +1304,19 @@ void Graph::read_audio_out(uint32_t node, uint32_t first, uint32_t n, float* sam
     if (node >= nodes_.size() || nodes_[node].kind != MX_KIND_OUTPUT_DEVICE) throw Error(MX_ERR_INVALID, "node is not an OUTPUT_DEVICE");
     if ((uint64_t)first + n > last_calls_) throw Error(MX_ERR_INVALID, "the window lies beyond the last run");
     const Node& nd = nodes_[node];
-    const size_t a = od_offset(nd, first), b = od_offset(nd, first + n);
+    const size_t a = nd.od->offset(first), b = nd.od->offset(first + n);
     if (n_samples) *n_samples = b - a;
     if (!samples && !ticks) return;
     if (samples && samples_cap < b - a) throw Error(MX_ERR_INVALID, "samples_cap is smaller than the window's samples");
     wait_tail(-1);
-    if (samples && b > a) hip_check(hipMemcpyAsync(samples, (const float*)nd.od_out.p + a, (b - a) * sizeof(float), hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(D2H)");
-    if (ticks && n) hip_check(hipMemcpyAsync(ticks, (const OutTick*)nd.od_rec.p + first, (size_t)n * sizeof(OutTick), hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(D2H)");
+    if (samples && b > a) hip_check(hipMemcpyAsync(samples, (const float*)nd.od->out.p + a, (b - a) * sizeof(float), hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(D2H)");
+    if (ticks && n) hip_check(hipMemcpyAsync(ticks, (const OutTick*)nd.od->rec.p + first, (size_t)n * sizeof(OutTick), hipMemcpyDeviceToHost, stream_), "hipMemcpyAsync(D2H)");
     sync();
 }
 
 void Graph::audio_out_lag(uint32_t node) {
     if (node >= nodes_.size() || nodes_[node].kind != MX_KIND_OUTPUT_DEVICE) throw Error(MX_ERR_INVALID, "node is not an OUTPUT_DEVICE");
-    nodes_[node].od_lag->store(true);   // AtomicBool::store (output_device.rs:126); nothing else of the graph is touched
+    nodes_[node].od->lag.store(true);   // AtomicBool::store (output_device.rs:126); nothing else of the graph is touched
 }
 
 // ---- the audio tap sets (mx_taps.hpp): what the engine keeps of them is the port a set sees, the list in launch order (taps_) and where a run's launches go ----

@@ -19,30 +19,41 @@
 
 #include "mx_common.hpp"
 #include "mx_kernels.hpp"
+#include "mx_plan.hpp"
 #include "mx_taps.hpp"
 #include "mx_video.hpp"
 #include "mx_video_graph.hpp"
 
 namespace mx {
 
-struct PortRef { int32_t node = -1; uint32_t port = 0; };
+// OUTPUT_DEVICE (output_device.rs): what the module carries from run to run, held by the nodes of that kind only.  Every call below wants a quiescent stream.
+struct OutputDeviceState {
+    // the open stream's channel count (0: none), the stored left / right (filtered; -1: None), the largest channel count seen (what the
+    // buffers are sized for) and the input's frames per tick
+    uint32_t channels = 0, cmax = 0; int32_t left = -1, right = -1; const uint32_t frames;
+    DevBuf scratch;                 // the persistent scratch: frames * cmax floats, only ever grows (:185)
+    DevBuf state;                   // OutState
+    DevBuf out, rec, part;          // the last run's hand-off, per-tick records (OutTick) and the route kernel's clip partials
+    std::atomic<bool> lag{false};   // set by the cpal callback (mx_graph_audio_out_lag), swapped by the next run
+    bool lag_run = false;           // ... taken by the current run
+    struct Span { uint32_t first, n, channels; };
+    std::vector<Span> spans;        // the last run's spans, in order (the hand-off is their ticks back to back)
+    // `ticks`: the ticks of a whole submission, what the per-run buffers are sized for
+    OutputDeviceState(uint32_t frames_per_tick, size_t ticks);                    // the empty state (no stream, nothing assigned)
+    void grow(uint32_t channels, size_t ticks, hipStream_t stream);               // buffers for a channel count above any seen before
+    void update(const void* params, size_t ticks, hipStream_t stream);            // ModuleT::update (output_device.rs:152-169) with mx_output_device_params
+    size_t offset(uint32_t tick) const;                                           // float offset of tick `tick` of the last run in the hand-off
+    void adopt(OutputDeviceState& old, size_t ticks, hipStream_t stream);         // a topology edit: the module persists
+};
 
-struct Node {
-    uint32_t kind = 0;
+// A node of a built graph: what the compiler said about it (mx_plan.hpp; Graph rewrites in_src alone, in set_input_enabled), where layout_slab put
+// its ports, and the state it carries while the graph runs.
+struct Node : PlanNode {
     std::vector<uint8_t> params;
-    std::vector<uint8_t> in_type, out_type;   // mx_line per terminal (ModuleT::inputs()/outputs())
-    std::vector<PortRef> in_src;              // workspace.connections (back-edges already cut)
-    std::vector<PortRef> in_src_orig;         // in_src before set_input_enabled() toggles
-    std::vector<size_t> out_off;              // float offset of each output port in the slab
-    std::vector<size_t> out_off2;             // MX_FLAG_OVERLAP_TAIL: second buffer of a port the tail group reads (SIZE_MAX: none)
+    std::vector<size_t> out_off;              // float offset of each output port in the slab (layout_slab)
+    std::vector<size_t> out_off2;             // MX_FLAG_OVERLAP_TAIL: second buffer of a port the tail group reads (SIZE_MAX: none); dropped when the mode ends
     const float* bound = nullptr;             // SOURCE_*: caller-bound device buffer
-    int level = 0;
-    uint32_t dom_num = 1, dom_den = 1;        // sample-rate domain of the OUTPUT ports relative to the graph's rate (Resample changes it)
-    uint32_t in_dom_num = 1, in_dom_den = 1;  // ... of the input ports
-    uint32_t slot = 0;                        // index inside its (level, kind) group
-    int group = -1;
     std::vector<uint8_t> parked;              // the carried state of a module no launch of this graph serves (it is outside the run order): kept on the host from one topology edit to the next
-    int sub_key = 0;                          // EQ_THREE: 1 + the epilogue mode the graph compiler gave the node (launch groups are of one mode); 0 otherwise
     // parameter updates queued for ticks inside the next run (Engine::client_update between two ticks, src/engine.rs:192-214)
     struct SchedEv { uint32_t tick; std::vector<uint8_t> params; };
     std::vector<SchedEv> sched;
@@ -51,45 +62,23 @@ struct Node {
     uint64_t plot_count = 0;
     std::vector<uint8_t> plot_fired;          // per call of the last run
     std::vector<int32_t> plot_slot;           // staging slot per call (-1 = not fired)
-    // graph-compiler fusion (Graph::plan_fusion)
-    bool elided = false;                      // never launched: its work is folded into `owner`'s kernel
-    int32_t owner = -1;                       // node whose descriptors carry this node's params
-    int32_t fuse_pan = -1, fuse_amp = -1;     // EQ_THREE: StereoPanner / Amplifier folded into the epilogue
-    int32_t fuse_trigger = -1;                // ENVELOPE: Trigger folded in as a constant gate
-    int32_t fuse_env = -1;                    // EQ_THREE: constant-gate Envelope evaluated inline as the fused Amplifier's control
-    std::vector<uint8_t> out_elided;          // per output port: buffer not materialised
-    std::vector<uint8_t> out_dup;             // per output port: stereo with L == R stored as ONE float per frame
     // video nodes (run tick by tick inside Graph::run): each kind's state is an object of its own (mx_video_graph.hpp), held by the nodes of that kind only
     using VOut = mx::VOut;
     using MonTick = MonitorState::Tick;
     std::unique_ptr<VideoMixer> vmixer;       // VIDEO_MIXER
-    bool vlazy = false;                       // VIDEO_MIXER: program output handed over as an unevaluated cross-fade chain (graph compiler)
     std::vector<VOut> vout;                   // this tick's video outputs (empty FrameRef = None)
     std::unique_ptr<VideoSourceState> vsrc;   // SOURCE_VIDEO
     std::unique_ptr<RgbaSinkState> rgba;      // VIDEO_TO_RGBA
     std::unique_ptr<MonitorState> mon;        // MONITOR
-    // OUTPUT_DEVICE (output_device.rs): the open stream's channel count (0: none), the stored left / right (filtered; -1: None), the largest
-    // channel count seen (what the buffers are sized for) and the input's frames per tick
-    uint32_t od_channels = 0, od_cmax = 0; int32_t od_left = -1, od_right = -1; uint32_t od_frames = 0;
-    DevBuf od_scratch;                         // the persistent scratch: od_frames * od_cmax floats, only ever grows (:185)
-    DevBuf od_state;                           // OutState
-    DevBuf od_out, od_rec, od_part;            // the last run's hand-off, per-tick records (OutTick) and the route kernel's clip partials
-    std::unique_ptr<std::atomic<bool>> od_lag; // set by the cpal callback (mx_graph_audio_out_lag), swapped by the next run
-    bool od_lag_run = false;                   // ... taken by the current run
-    struct OdSpan { uint32_t first, n, channels; };
-    std::vector<OdSpan> od_spans;              // the last run's spans, in order (the hand-off is their ticks back to back)
+    std::unique_ptr<OutputDeviceState> od;    // OUTPUT_DEVICE
+    explicit Node(const PlanNode& p) : PlanNode(p) {}
 };
 
-struct Group {
-    int level = 0;
-    uint32_t kind = 0;
-    int sub_key = 0;
-    uint32_t dom_num = 1, dom_den = 1, in_dom_num = 1, in_dom_den = 1;   // every node of a group shares one rate domain
+struct Group : PlanGroup {
     uint32_t max_taps = 0;   // Fir / Resample: most taps; Mixer: most channels
     uint32_t rs_common_taps = 0, rs_common_down = 0;   // ... and their taps per phase / decimation factor, likewise
     uint32_t rs_common_up = 0;   // Resample: the nodes' interpolation factor when they all have the same (the staged kernel's table stride becomes a constant)
     uint32_t rs_tab_doubles = 0, rs_win_frames = 0;   // Resample: LDS plan of the staged kernel (largest table / input window of the group)
-    std::vector<uint32_t> nodes;
     DevBuf desc;     // kind-specific descriptor array
     DevBuf desc_alt, extra_alt;   // MX_FLAG_OVERLAP_TAIL: the same for the other parity of the double-buffered ports (extra_alt: Mixer only)
     DevBuf state;    // EnvState[] / EqState[]
@@ -104,6 +93,7 @@ struct Group {
     DevBuf env_ticks;   // EqThree: EnvTick[n][n_calls] of the current launch
     DevBuf spec;        // EqThree: chunk records of the speculative exact kernel; Envelope: marker bitmaps and per-segment states of a long stream (mx_k_envelope.hip)
     int eq_mode = -1;   // EqThree: the one epilogue every instance has (eq_epilogue_mode), or -1 when they differ
+    explicit Group(const PlanGroup& g) : PlanGroup(g) {}
 };
 
 class Graph final : public TapHost {
@@ -114,7 +104,7 @@ public:
 
     double sample_rate() const override { return sample_rate_; }
     size_t cap_frames() const override { return cap_frames_; }
-    const std::vector<uint32_t>& run_order() const { return order_; }
+    const std::vector<uint32_t>& run_order() const { return plan_.order; }
     hipStream_t stream() const override { return stream_; }
     // what a deck takes for "the same graph": unique per built graph, and taken over by the graph that adopts this one's state (a topology edit)
     uint64_t lineage() const { return lineage_; }
@@ -212,8 +202,10 @@ private:
     uint64_t lineage_ = next_lineage();
     static uint64_t next_lineage() { static std::atomic<uint64_t> n{0}; return ++n; }
     size_t state_bytes(uint32_t node) const;   // what state_locs(node) holds where a launch serves the node, from its kind and params alone
-    void plan_fusion();
-    void layout_slab();
+    void open_device(const mx_graph_opts& opts);     // the device, the stream, what the environment says about the kernels' forms, the EqThree tables
+    void upload_eq_tables();                         // time-parallel EqThree tables (unused in MX_FLAG_EQ_EXACT mode)
+    bool accept_tail();                              // the plan's overlap-tail candidate: taken (second stream and events created) or rejected (an automatic one that is not affordable)
+    void layout_slab();                              // mx::layout_slab for cap_frames_, the offsets into the nodes, the slab allocated and cleared
     void build_descriptors();
     void upload_group(Group& g);          // descriptors of one group (both parities under MX_FLAG_OVERLAP_TAIL)
     void upload_group_one(Group& g, uint32_t parity);   // ... of one parity: desc / extra, or desc_alt / extra_alt
@@ -222,9 +214,7 @@ private:
     // one launch sequence over ticks [call_off, call_off + n_calls) of the current run
     void run_span(uint64_t t0, size_t fpc, uint32_t call_off, uint32_t n_calls, uint32_t run_calls);
     void apply_params(uint32_t node, const void* params, size_t len);   // update_params without the synchronisation
-    void od_update(Node& n);                                             // OUTPUT_DEVICE: ModuleT::update with n.params (output_device.rs:152-169), on a quiescent stream
-    void od_grow(Node& n, uint32_t channels);                            // ... buffers for a channel count above any seen before
-    size_t od_offset(const Node& n, uint32_t tick) const;                // float offset of tick `tick` of the last run in the hand-off
+    size_t od_ticks() const { return std::max<size_t>(1, cap_frames_ / spt_); }   // OUTPUT_DEVICE: the ticks of a whole submission
     struct ProfSpan;
     void launch_outputs(uint64_t t0, uint32_t call_off, uint32_t n_calls, ProfSpan* prof);   // the span's OutputDevice launches
     void launch_tap_set(AudioTapSet& s, uint32_t n_calls, ProfSpan* prof);   // the run's launches of one audio tap set: on stream_, or held back with the tail
@@ -236,11 +226,10 @@ private:
     const float* in_ptr(const Node& n, uint32_t port, bool null_if_disconnected, uint32_t parity) const;
     float* out_ptr(const Node& n, uint32_t port, uint32_t parity) const;
 
+    const Plan plan_;             // what compile_plan said, untouched: the nodes' and groups' plan parts start as copies of it
     std::vector<Node> nodes_;
-    std::vector<uint32_t> order_;
     std::vector<Group> groups_;   // sorted by (level, kind)
     uint32_t flags_ = 0;
-    bool has_video_ = false;
     uint32_t tps_ = 60;
     double sample_rate_ = 44100.0;
     size_t spt_ = 735;
@@ -289,9 +278,6 @@ private:
     Stage stage_[4]; uint32_t stage_next_ = 0;
     uint32_t prof_runs_count_ = 0;
     std::vector<uint32_t> sched_nodes_;     // nodes with a pending schedule (a 60 000-node graph must not be walked per tick)
-    std::vector<uint32_t> plotter_nodes_;   // launched Plotter nodes
-    std::vector<uint32_t> video_order_;     // the video nodes of order_, in run order
-    std::vector<uint32_t> od_nodes_;        // OutputDevice nodes of order_ (never in a launch group: launched after the span's groups, behind their input's producer)
     size_t tap_fpc_ = 0;                        // frames per call every set's descriptors were built for (the tick length until a run says otherwise)
     MeterTaps meters_{*this}; SpectrumTaps spectra_{*this}; LoudnessTaps loudness_{*this}; StereoTaps stereos_{*this}; LimiterTaps limiters_{*this}; TempoTaps tempos_{*this}; TonalityTaps tonalities_{*this};
     const std::array<AudioTapSet*, 7> taps_{&meters_, &spectra_, &loudness_, &stereos_, &limiters_, &tempos_, &tonalities_};   // in launch order

@@ -393,7 +393,7 @@ void Graph::run_video_tick(uint64_t t, uint32_t tick_in_run) {
         const PortRef pr = n.in_src[i];
         return pr.node < 0 ? nullptr : &nodes_[pr.node].vout[pr.port];
     };
-    for (uint32_t id : video_order_) {
+    for (uint32_t id : plan_.video_order) {
         Node& n = nodes_[id];
         switch (n.kind) {
         case MX_KIND_SOURCE_VIDEO:

@@ -43,8 +43,9 @@ CLASS_OF = {abi.KIND_SOURCE_MONO: "source", abi.KIND_SOURCE_STEREO: "source", ab
 
 
 def predict_fusion(ws, order, n_inputs):
-    """Graph::plan_fusion (mx_engine.cpp) restated: -> (ports the default build folds away, stereo ports it stores one float per frame).
-    The GPU test asserts both against the built graph, so the CPU test, which has none, draws the very same taps."""
+    """plan_fusion (mx_plan.cpp) restated: -> (ports the default build folds away, stereo ports it stores one float per frame).
+    The GPU test asserts both against the built graph and tests/test_cpu_graph_plan.py against the compiler itself (mx_graph_debug_plan), so the
+    CPU test, which builds no graph, draws the very same taps."""
     pos = {n: i for i, n in enumerate(order)}
     kind = lambda n: ws.nodes[n][0]
     in_src, cons = {}, {}

@@ -99,3 +99,49 @@ def test_inline_envelope_state_carries_across_runs_and_gate_flips():
         assert_bit_exact(gf.read_output(mix, 0, T, True), gu.read_output(mix, 0, T, True), f"master run {run}")
         for k in range(3):
             assert_bit_exact(gf.read_output(mix + 6 * k + 6, 0, T, True), gu.read_output(mix + 6 * k + 6, 0, T, True), f"strip {k} run {run}")
+
+
+def plan_graphs():
+    """64-frame ticks.  Two strips into a Mixer, the second strip's Amplifier controlled by a Trigger -> Envelope; a Resample 3 / 2 with a Fir behind it"""
+    ws = Workspace(64 * 60, 60)
+    amps = []
+    for i in range(2):
+        s = ws.source_mono(); e = ws.eq_three(3.0, -6.0, 1.5); p = ws.stereo_panner(); a = ws.amplifier(1.0, 0.5)
+        ws.connect(s, 0, e, 0); ws.connect(e, 0, p, 0); ws.connect(e, 0, p, 1); ws.connect(p, 0, a, 0)
+        amps.append(a)
+    t = ws.trigger(True); v = ws.envelope(); ws.connect(t, 0, v, 0); ws.connect(v, 0, amps[1], 1)
+    m = ws.mixer([(0.0, 1.0, False)] * 2); ws.connect(amps[0], 0, m, 0); ws.connect(amps[1], 0, m, 1)
+    rs = Workspace(64 * 60, 60)
+    s = rs.source_stereo(); r = rs.resample(3, 2, np.full((3, 4), 0.25)); f = rs.fir([0.5, 0.25, 0.25]); rs.connect(s, 0, r, 0); rs.connect(r, 0, f, 0)
+    return {"fused": (ws, 0), "unfused": (ws, abi.FLAG_NO_FUSE), "resampled": (rs, 0)}
+
+
+@pytest.mark.parametrize("name", ["fused", "unfused", "resampled"])
+def test_the_built_graph_is_the_one_the_host_only_plan_describes(name):
+    ws, flags = plan_graphs()[name]
+    recs, info = abi.debug_plan(ws.nodes, ws.edges, ws.sample_rate, ws.ticks_per_second, 2, flags)
+    g = ws.build(max_ticks_per_run=2, flags=flags)
+    order = [n for _pos, n in sorted((r.pos, n) for n, r in enumerate(recs) if r.pos >= 0)]
+    assert g.run_order() == order and info.n_order == len(order)
+    g.run_ticks(0, 2)
+    elided, dup, not_there, one_float = set(), set(), set(), set()
+    for n, r in enumerate(recs):
+        for p in range(r.n_out):
+            if r.out_elided[p]:
+                elided.add((n, p))
+            if r.out_dup[p]:
+                dup.add((n, p))
+            try:
+                g.read_output(n, p, 1, True, rate=(r.dom_num, r.dom_den))   # (room for a stereo port; a mono one fills half)
+            except abi.MxError as e:
+                assert "not materialised" in str(e)
+                not_there.add((n, p))
+            try:
+                g.output_device_ptr(n, p)
+            except abi.MxError as e:
+                assert (n, p) in not_there or "one float per frame" in str(e)
+                if (n, p) not in not_there:
+                    one_float.add((n, p))
+    assert not_there == elided and one_float == dup
+    assert (name == "fused") == bool(elided) and (name == "fused") == bool(dup)
+    g.close()

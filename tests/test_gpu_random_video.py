@@ -71,6 +71,10 @@ def frame_differs(d, pic):
 
 
 def build(sc):
+    return workspace(sc).build(max_ticks_per_run=rv.MAX_RUN)
+
+
+def workspace(sc):
     ws = Workspace(sc["rate"], 60)
     for _ in sc["sources"]:
         ws.source_video()
@@ -88,7 +92,7 @@ def build(sc):
         mo = sc["monitor"]
         assert ws.monitor(mo["width"], mo["height"]) == mo["node"]
         ws.connect(mo["mixer"] + sc["n_sources"], 0, mo["node"], 0)
-    return ws.build(max_ticks_per_run=rv.MAX_RUN)
+    return ws
 
 
 def apply_event(g, sc, e, dev):
