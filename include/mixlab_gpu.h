@@ -46,6 +46,8 @@ extern "C" {
                               *    mx_deck_debug_last_feed;
                               *    mx_deck_keylock, mx_deck_grain, mx_deck_set_keylock, mx_deck_keylock_check, mx_deck_keylock_search, mx_deck_grain_count, mx_deck_read_grains,
                               *    mx_deck_debug_last_keylock;
+                              *    mx_deck_analysis, mx_deck_column, mx_deck_grid, mx_deck_analysis_check, mx_deck_analysis_bands, mx_deck_analyse, mx_deck_column_count,
+                              *    mx_deck_read_columns, mx_deck_read_autocorr, mx_deck_columns_host, mx_deck_beatgrid, mx_deck_debug_last_analysis;
                               *    mx_plan_node, mx_plan_info, mx_graph_debug_plan */
 
 /* ---- status codes (0 ok, <0 error; cf. MIXLAB_IOCTX_ERROR / MIXLAB_IOCTX_PANIC) ---- */
@@ -942,6 +944,67 @@ int mx_deck_read_grains(mx_deck* d, uint32_t first, uint32_t n, mx_deck_grain* d
  * out[2] render chunks (MX_DECK_CHUNK frames of a playing tick) with at least one fading lane, out[3] render chunks with a grain start after their first lane.
  * mx_deck_debug_last_feed counts the plain decks of the feed only. */
 int mx_deck_debug_last_keylock(uint32_t out[4]);
+
+/* ---- ANALYSIS: the band waveform overview, the onset autocorrelation and the beat grid of a whole track, before it sounds ----
+ * BUILD-SPECIFIED.  One pass over the track as it lies in device memory, on the deck's own load stream: what a host needs at load time -- the coloured overview
+ * (low / mid / high per column), the tempo, and where the beats are.  Everything up to the read-out of the beat grid is integer arithmetic, so no order of accumulation
+ * matters and the records are fixed count for count.  A deck that never calls mx_deck_analyse is untouched in every respect.
+ *
+ * SETTINGS   mx_deck_analysis: column C a power of two, 64 .. 4096 frames; taps K odd, 1 .. 127; max_lag L 16 .. 1024; _pad 0; lo[0 .. K) and hi[0 .. K) two low-pass
+ *            tap tables in Q14, each with sum |c_k| <= 32767, entries at index K and above 0.  mx_deck_analysis_check enforces exactly these rules.
+ *            mx_deck_analysis_bands fills the tables (TABLES); worth starting from: 200 Hz / 2.5 kHz, K = 63, C = 512, L = 256.
+ * SIGNAL     s[f] = L[f] + R[f] of the raw int16 track, 0 outside [0, n_frames) (key-lock's s; |s| <= 65536).  With D = (K - 1) / 2:
+ *                a1[f] = sum_k lo[k] s[f - D + k],   a2[f] = sum_k hi[k] s[f - D + k]      (|a| <= 65536 * 32767 < 2^31: int32 is exact -- why the tap rule is what it is)
+ *                low[f] = a1[f] >> 14,  b[f] = a2[f] >> 14  (arithmetic shifts: floor),  mid[f] = b[f] - low[f],  high[f] = s[f] - b[f]
+ *            so low + mid + high = s for every frame, exactly.
+ * COLUMNS    N = ceil(n_frames / C).  Column c covers the frames f of [c C, (c + 1) C) with f < n_frames; the last may be short, and frames beyond the track contribute
+ *            to nothing.  mx_deck_column, 56 bytes: smin, smax the extremes of s over the column; peak[3] = max |band| for low, mid, high; energy[3] = sum band^2;
+ *            e = sum s^2 (at most 2^44); onset as below.
+ * ONSET      the tempo taps' rule: A[c] = floor(sqrt(e[c])), the exact integer root, A[-1] = 0; onset[c] = max(A[c] - A[c - 1], 0) >> 6 (<= 2^16).
+ * AUTOCORR   for l = 0 .. L - 1: R[l] = sum_{c = 0}^{N - 1 - l} onset[c] onset[c + l] as uint64 (0 when l >= N; at most 2^32 * 2^24: no overflow).
+ * BEAT GRID  mx_deck_beatgrid, host only and pure.  The lag follows EXACTLY mx_tempo_bpm's rule with C in place of hop_frames: the candidate lags are the integers of
+ *            [60 rate / (C bpm_hi), 60 rate / (C bpm_lo)] within [1, L - 2], l* the first maximum of R over them, d that function's parabolic term.  P = (double)l* + d.
+ *            For phi = 0 .. ceil(P) - 1: S(phi) = sum_{k = 0, 1, ...} onset[i_k] as uint64, i_k = (int64)floor((double)phi + (double)k * P) while i_k < n_cols -- the
+ *            multiply and the add separate f64 operations, never fused.  The phase is the smallest phi of the largest S.  mx_deck_grid: bpm = 60 rate / (C P),
+ *            period_columns = P, confidence = R[l*] / R[0], first_beat_frame = phi C, lag = l*, phase_column = phi; beat j lies near frame (phi + j P) C.
+ *            With R[0] = 0 or no candidate lag everything is 0 -- and also when P lies outside [1, L]: the vertex of the parabola runs away only from a "maximum" at
+ *            the edge of the candidate range whose neighbour outside the range is larger, and such a period places no beats.
+ * TABLES     mx_deck_analysis_bands: Hann-windowed sincs at cutoffs f_lo < f_hi < rate / 2.  g_k = fc sinc(fc (k - D)) w_k, fc = 2 f / rate, sinc(x) = sin(pi x) / (pi x),
+ *            w_k = 0.5 - 0.5 cos(2 pi (k + 1) / (K + 1)), evaluated in f64 for k <= D and mirrored; each tap the nearest integer of 16384 g_k / sum g; the centre tap then
+ *            adjusted so that sum c = 16384 exactly: DC passes at gain 1, and a constant track has mid = high = 0 away from its ends.
+ * Out of scope: gated-loudness (LUFS) auto-gain and whole-track key (the columns' e and peaks serve a plain gain; key can follow on the same pass); tempo that changes
+ * within a track, downbeat / bar detection; analysis of a range instead of the whole track; more than two channels; any change to how a deck plays. */
+typedef struct { uint32_t column; uint32_t taps; uint32_t max_lag; uint32_t _pad; int16_t lo[127]; int16_t hi[127]; } mx_deck_analysis;
+typedef struct { int32_t smin, smax; uint32_t peak[3]; uint32_t onset; uint64_t energy[3]; uint64_t e; } mx_deck_column;
+typedef struct { double bpm, period_columns, confidence; uint64_t first_beat_frame; uint32_t lag, phase_column; } mx_deck_grid;
+/* Host only: the SETTINGS rules alone; MX_ERR_INVALID names the rule in mx_last_error. */
+int mx_deck_analysis_check(const mx_deck_analysis* a);
+/* Host only: TABLES.  Sets a->taps and fills a->lo / a->hi (entries from `taps` on 0); column, max_lag and _pad are left alone.  rate not finite and positive, cutoffs
+ * not 0 < f_lo < f_hi < rate / 2, taps even or outside 1 .. 127, or tables whose sum |c| exceeds 32767 (cutoffs close to rate / 2): MX_ERR_INVALID, *a untouched. */
+int mx_deck_analysis_bands(double rate, double f_lo, double f_hi, uint32_t taps, mx_deck_analysis* a);
+/* Analyse the whole track as loaded now.  Asynchronous, on the deck's own load stream: ordered after earlier mx_deck_load_i16 calls and before later ones; it uses
+ * neither a graph's stream nor the host, and feeds are not ordered against it (both only read the track).  The results live in device memory the deck owns,
+ * N * 56 + N * 4 + L * 8 bytes; a later analysis replaces them, NULL frees them.  The result is a snapshot: a later load does not invalidate it.  Settings that fail the
+ * check: MX_ERR_INVALID, and the deck keeps what it had.  Memory that cannot be had: MX_ERR_NOMEM, and the deck is left without an analysis. */
+int mx_deck_analyse(mx_deck* d, const mx_deck_analysis* a);
+/* Host only: *n = ceil(n_frames / column).  n_frames outside 1 .. 2^30 or a column the check refuses: MX_ERR_INVALID. */
+int mx_deck_column_count(uint64_t n_frames, uint32_t column, uint64_t* n);
+/* Columns [first, first + n) of the deck's analysis; waits for it (as mx_deck_read_grains waits for a feed).  No analysis, or a window beyond N: MX_ERR_INVALID. */
+int mx_deck_read_columns(mx_deck* d, uint64_t first, uint64_t n, mx_deck_column* dst);
+/* R[0 .. L) of the deck's analysis into R[0 .. cap); waits for it.  No analysis, or cap below L: MX_ERR_INVALID. */
+int mx_deck_read_autocorr(mx_deck* d, uint64_t* R, uint32_t cap);
+/* Host only, pure: COLUMNS and ONSET in plain C++ for columns [first, first + n) of a track of n_frames interleaved stereo frames (1 .. 2^30) -- how the rules are
+ * tested without a device, and the single-thread baseline of the device path.  R_or_null not NULL: AUTOCORR too, into R_or_null[0 .. max_lag); that needs all the
+ * columns, first = 0 and n = N.  Settings the check refuses, a window beyond N, R_or_null with another window, a NULL pointer: MX_ERR_INVALID. */
+int mx_deck_columns_host(const int16_t* interleaved, uint64_t n_frames, const mx_deck_analysis* a, uint64_t first, uint64_t n, mx_deck_column* cols, uint64_t* R_or_null);
+/* Host only, pure: BEAT GRID from n_cols columns and R[0 .. max_lag).  column / max_lag outside the SETTINGS rules, rate, bpm_lo, bpm_hi not finite and positive or
+ * bpm_lo > bpm_hi, a NULL pointer (cols may be NULL when n_cols is 0): MX_ERR_INVALID. */
+int mx_deck_beatgrid(const mx_deck_column* cols, uint64_t n_cols, const uint64_t* R, uint32_t max_lag, uint32_t column, double rate, double bpm_lo, double bpm_hi,
+                     mx_deck_grid* out);
+/* DEBUG: what the last mx_deck_analyse of this process launched for the columns: out[0] workgroups that each covered several columns (C < 1024), out[1] workgroups
+ * that each took one column in several tiles of 1024 frames (C > 1024), out[2] 1 when the track was shorter than the halo (n_frames < K - 1: one workgroup, a lane
+ * per frame), out[3] workgroups of one column in one tile (C = 1024).  Tests use it to know every form ran. */
+int mx_deck_debug_last_analysis(uint32_t out[4]);
 
 /* ---------------------------------------------------------------------------------------------- */
 /* pixel path: device-resident yuv420p frames, VideoMixer, scaler, colour                          */

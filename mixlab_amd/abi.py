@@ -407,6 +407,25 @@ _proto("mx_deck_keylock_search", C.c_int, C.c_void_p, C.c_uint64, C.c_int64, C.c
 _proto("mx_deck_grain_count", C.c_int, C.c_void_p, C.POINTER(C.c_uint32))
 _proto("mx_deck_read_grains", C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(DeckGrain))
 _proto("mx_deck_debug_last_keylock", C.c_int, C.POINTER(C.c_uint32))
+# ... analysed (the header's ANALYSIS): band waveform columns, onset autocorrelation and beat grid of the whole track
+DECK_ANALYSIS_MAX_TAPS = 127
+class DeckAnalysis(C.Structure):
+    _fields_ = [("column", C.c_uint32), ("taps", C.c_uint32), ("max_lag", C.c_uint32), ("_pad", C.c_uint32),
+                ("lo", C.c_int16 * DECK_ANALYSIS_MAX_TAPS), ("hi", C.c_int16 * DECK_ANALYSIS_MAX_TAPS)]
+class DeckColumn(C.Structure):
+    _fields_ = [("smin", C.c_int32), ("smax", C.c_int32), ("peak", C.c_uint32 * 3), ("onset", C.c_uint32), ("energy", C.c_uint64 * 3), ("e", C.c_uint64)]
+class DeckGrid(C.Structure):
+    _fields_ = [("bpm", C.c_double), ("period_columns", C.c_double), ("confidence", C.c_double), ("first_beat_frame", C.c_uint64),
+                ("lag", C.c_uint32), ("phase_column", C.c_uint32)]
+_proto("mx_deck_analysis_check", C.c_int, C.POINTER(DeckAnalysis))
+_proto("mx_deck_analysis_bands", C.c_int, C.c_double, C.c_double, C.c_double, C.c_uint32, C.POINTER(DeckAnalysis))
+_proto("mx_deck_analyse", C.c_int, C.c_void_p, C.POINTER(DeckAnalysis))
+_proto("mx_deck_column_count", C.c_int, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64))
+_proto("mx_deck_read_columns", C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p)
+_proto("mx_deck_read_autocorr", C.c_int, C.c_void_p, C.c_void_p, C.c_uint32)
+_proto("mx_deck_columns_host", C.c_int, C.c_void_p, C.c_uint64, C.POINTER(DeckAnalysis), C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p)
+_proto("mx_deck_beatgrid", C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_double, C.POINTER(DeckGrid))
+_proto("mx_deck_debug_last_analysis", C.c_int, C.POINTER(C.c_uint32))
 _proto("mx_module_create", C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p))
 _proto("mx_module_create_ex", C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(GraphOpts), C.POINTER(C.c_void_p))
 _proto("mx_module_update", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)

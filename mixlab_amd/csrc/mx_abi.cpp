@@ -361,13 +361,8 @@ int mx_tempo_bpm(const void* record, double rate, double bpm_lo, double bpm_hi, 
                 "rate, bpm_lo and bpm_hi must be finite and positive, bpm_lo <= bpm_hi");
         auto R = [&](uint32_t l) { uint64_t v; std::memcpy(&v, (const unsigned char*)record + 32 + 8 * (size_t)l, sizeof v); return (double)v; };
         *bpm = 0.0; *confidence = 0.0;
-        const double lo = std::max(1.0, std::ceil(60.0 * rate / ((double)H * bpm_hi))), hi = std::min((double)(L - 2), std::floor(60.0 * rate / ((double)H * bpm_lo)));
-        if (R(0) == 0.0 || !(lo <= hi)) return;
-        uint32_t best = (uint32_t)lo;
-        for (uint32_t l = best + 1; l <= (uint32_t)hi; ++l)
-            if (R(l) > R(best)) best = l;   // the first maximum
-        const double den = R(best - 1) - 2.0 * R(best) + R(best + 1);
-        const double d = den < 0.0 ? 0.5 * (R(best - 1) - R(best + 1)) / den : 0.0;
+        uint32_t best = 0; double d = 0.0;
+        if (!mx::tempo_lag(R, L, H, rate, bpm_lo, bpm_hi, best, d)) return;
         *bpm = 60.0 * rate / ((double)H * ((double)best + d));
         *confidence = R(best) / R(0);
     });

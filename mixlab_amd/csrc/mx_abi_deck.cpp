@@ -85,5 +85,33 @@ int mx_deck_read_grains(mx_deck* d, uint32_t first, uint32_t n, mx_deck_grain* d
 int mx_deck_debug_last_keylock(uint32_t out[4]) {
     return guard([&] { REQUIRE(out, "out is NULL"); Deck::debug_last_keylock(out); });
 }
+int mx_deck_analysis_check(const mx_deck_analysis* a) {
+    return guard([&] { REQUIRE(a, "settings are NULL"); mx::deck_analysis_check(*a); });
+}
+int mx_deck_analysis_bands(double rate, double f_lo, double f_hi, uint32_t taps, mx_deck_analysis* a) {
+    return guard([&] { REQUIRE(a, "settings are NULL"); mx::deck_analysis_bands(rate, f_lo, f_hi, taps, *a); });
+}
+int mx_deck_analyse(mx_deck* d, const mx_deck_analysis* a) {
+    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.analyse(a); });
+}
+int mx_deck_column_count(uint64_t n_frames, uint32_t column, uint64_t* n) {
+    return guard([&] { REQUIRE(n, "n is NULL"); *n = mx::deck_column_count(n_frames, column); });
+}
+int mx_deck_read_columns(mx_deck* d, uint64_t first, uint64_t n, mx_deck_column* dst) {
+    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.read_columns(first, n, dst); });
+}
+int mx_deck_read_autocorr(mx_deck* d, uint64_t* R, uint32_t cap) {
+    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.read_autocorr(R, cap); });
+}
+int mx_deck_columns_host(const int16_t* interleaved, uint64_t n_frames, const mx_deck_analysis* a, uint64_t first, uint64_t n, mx_deck_column* cols, uint64_t* R_or_null) {
+    return guard([&] { REQUIRE(a, "settings are NULL"); mx::deck_columns_host(interleaved, n_frames, *a, first, n, cols, R_or_null); });
+}
+int mx_deck_beatgrid(const mx_deck_column* cols, uint64_t n_cols, const uint64_t* R, uint32_t max_lag, uint32_t column, double rate, double bpm_lo, double bpm_hi,
+                     mx_deck_grid* out) {
+    return guard([&] { REQUIRE(out, "out is NULL"); mx::deck_beatgrid(cols, n_cols, R, max_lag, column, rate, bpm_lo, bpm_hi, *out); });
+}
+int mx_deck_debug_last_analysis(uint32_t out[4]) {
+    return guard([&] { REQUIRE(out, "out is NULL"); Deck::debug_last_analysis(out); });
+}
 
 }  // extern "C"

@@ -60,6 +60,12 @@ struct KlTickDev { uint32_t m0, gi0, first0, play; };
 // ---- host ----
 void deck_keylock_check(const mx_deck_keylock& k);                                   // throws Error(MX_ERR_INVALID) naming the rule
 void deck_keylock_search(const int16_t* interleaved, uint64_t n_frames, int64_t C, int64_t A, uint32_t overlap, uint32_t radius, int32_t& delta, uint32_t& dist);
+// analysis (the header's ANALYSIS; mx_k_deck_analyse.hip)
+void deck_analysis_check(const mx_deck_analysis& a);                                 // throws Error(MX_ERR_INVALID) naming the rule
+void deck_analysis_bands(double rate, double f_lo, double f_hi, uint32_t taps, mx_deck_analysis& a);
+uint64_t deck_column_count(uint64_t n_frames, uint32_t column);
+void deck_columns_host(const int16_t* interleaved, uint64_t n_frames, const mx_deck_analysis& a, uint64_t first, uint64_t n, mx_deck_column* cols, uint64_t* R_or_null);
+void deck_beatgrid(const mx_deck_column* cols, uint64_t n_cols, const uint64_t* R, uint32_t max_lag, uint32_t column, double rate, double bpm_lo, double bpm_hi, mx_deck_grid& out);
 void deck_check(const mx_deck_params& p, uint64_t n_frames);                         // throws Error(MX_ERR_INVALID) naming the rule
 void deck_plan(const mx_deck_head& in, const mx_deck_params* params, const int64_t* seek, uint32_t spt, uint64_t n_frames, mx_deck_tick& tick, mx_deck_head& out);
 int64_t deck_step(uint32_t track_rate, uint32_t graph_rate, double speed);
@@ -83,6 +89,10 @@ public:
     uint32_t grain_count() const { return (uint32_t)grains_.size(); }
     void read_grains(uint32_t first, uint32_t n, mx_deck_grain* dst);      // waits for the device
     static void debug_last_keylock(uint32_t out[4]);
+    void analyse(const mx_deck_analysis* a);                               // NULL: frees the results.  Asynchronous on the load stream.
+    void read_columns(uint64_t first, uint64_t n, mx_deck_column* dst);    // waits for the analysis
+    void read_autocorr(uint64_t* R, uint32_t cap);                         // waits for the analysis
+    static void debug_last_analysis(uint32_t out[4]);
 
 private:
     void fetch_grains();
@@ -102,6 +112,9 @@ private:
     DevBuf kl_rec_;                     // KlRec x (2 + the grains of the last feed)
     std::vector<mx_deck_grain> grains_; // the last feed's grain records; g / delta / dist are fetched from kl_rec_ by read_grains
     bool grains_fetched_ = true;
+    // analysis: one buffer -- columns (an_cols_ x 56 bytes), R (an_lag_ x 8), onsets (an_cols_ x 4) -- written on load_stream_ only; an_cols_ = 0: none
+    DevBuf an_;
+    uint64_t an_cols_ = 0; uint32_t an_lag_ = 0;
 };
 
 }  // namespace mx

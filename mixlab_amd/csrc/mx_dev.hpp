@@ -35,6 +35,14 @@ __device__ __forceinline__ float2 ld2(const float* __restrict__ p, size_t h, siz
     return r;
 }
 
+// floor(sqrt(e)), e < 2^53: the f64 root of an exactly represented value is within one of it (the tempo taps' onsets and the deck analysis', device and host)
+__host__ __device__ __forceinline__ uint32_t tempo_root(uint64_t e) {
+    uint64_t r = (uint64_t)sqrt((double)e);
+    if (r * r > e) --r;
+    else if ((r + 1) * (r + 1) <= e) ++r;
+    return (uint32_t)r;
+}
+
 inline unsigned grid_x(size_t items, unsigned block, unsigned cap) {
     size_t b = (items + block - 1) / block;
     if (b < 1) b = 1;

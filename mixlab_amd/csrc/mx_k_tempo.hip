@@ -37,14 +37,6 @@ __device__ __forceinline__ uint32_t tempo_quantise(float l, float rr, bool& bad)
     return bad ? 0u : (uint32_t)(fminf(fabsf(m), 4.0f) * 1048576.0f);
 }
 
-// floor(sqrt(e)), e < 2^53: the f64 root of an exactly represented value is within one of it
-__device__ __forceinline__ uint32_t tempo_root(uint64_t e) {
-    uint64_t r = (uint64_t)sqrt((double)e);
-    if (r * r > e) --r;
-    else if ((r + 1) * (r + 1) <= e) ++r;
-    return (uint32_t)r;
-}
-
 __global__ __launch_bounds__(256) void k_tempo_emit(const TempoRun r) {
     const uint64_t idx = (uint64_t)blockIdx.x * 256u + threadIdx.x;
     if (idx >= (uint64_t)r.n * r.n_emit) return;

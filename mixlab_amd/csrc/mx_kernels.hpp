@@ -8,6 +8,9 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <algorithm>
+#include <cmath>
+
 namespace mx {
 
 // src/module/amplifier.rs:38-60
@@ -282,6 +285,20 @@ inline bool tempo_params_ok(uint32_t hop_frames, uint32_t window_hops, uint32_t 
     return (hop_frames == 64 || hop_frames == 128 || hop_frames == 256) && window_hops >= 64 && window_hops <= 4096 && max_lag >= 16 && max_lag <= 1024 &&
            max_lag <= window_hops && emit_ticks >= 1;
 }
+// The lag rule of mx_tempo_bpm and mx_deck_beatgrid (host only): over R(0 .. L - 1) of an onset function hopped every `hop` frames, the candidate lags are the integers
+// of [60 rate / (hop bpm_hi), 60 rate / (hop bpm_lo)] within [1, L - 2], `best` the first maximum of R over them and d the vertex of the parabola through R(best - 1),
+// R(best), R(best + 1) where that one opens downwards, else 0.  false: R(0) = 0 or no candidate.  R returns double.
+template <class RF>
+inline bool tempo_lag(RF&& R, uint32_t L, uint32_t hop, double rate, double bpm_lo, double bpm_hi, uint32_t& best, double& d) {
+    const double lo = std::max(1.0, std::ceil(60.0 * rate / ((double)hop * bpm_hi))), hi = std::min((double)(L - 2), std::floor(60.0 * rate / ((double)hop * bpm_lo)));
+    if (R(0) == 0.0 || !(lo <= hi)) return false;
+    best = (uint32_t)lo;
+    for (uint32_t l = best + 1; l <= (uint32_t)hi; ++l)
+        if (R(l) > R(best)) best = l;   // the first maximum
+    const double den = R(best - 1) - 2.0 * R(best) + R(best + 1);
+    d = den < 0.0 ? 0.5 * (R(best - 1) - R(best + 1)) / den : 0.0;
+    return true;
+}
 void launch_taps(const TempoRun& r, hipStream_t s);   // k_tempo_emit (a run that emits), k_tempo_energy, k_tempo_onsets, k_tempo_acf (a run that emits)
 // Tonality taps (mx_k_tonality.hip, mixlab_gpu.h mx_graph_set_tonality): the descriptor is TempoDesc's with the index of the tap's table set
 // (one per rate domain of the set: f_b / fs_d depends on it) in place of the padding.  From pos0 + ticks0 x frames, the run's first frame,
@@ -345,5 +362,12 @@ void launch_deck_feed(const DeckDev* decks, const DeckTickDev* ticks, const floa
 // the key-locked decks of a feed (mx_deck.hpp, mx_k_deck_keylock.hip): the grain search, one workgroup per deck, then the render over n decks x n_ticks ticks x chunks
 struct KlDeckDev; struct KlTickDev;
 void launch_deck_keylock(const KlDeckDev* decks, const KlTickDev* ticks, const float* tables, uint32_t n, uint32_t n_ticks, uint32_t spt, hipStream_t s);
+// the analysis of a deck's track (mx_deck.hpp, mx_k_deck_analyse.hip): columns -> cols (n_cols x 56 bytes), their onsets -> cols and `onsets`, the autocorrelation -> R
+// (max_lag words, zeroed here first); all on stream s.  The tap tables widened to int32 and padded with zeros travel as a kernel argument.  forms[DECK_AN_*]: what was
+// launched (mx_deck_debug_last_analysis).  Settings the check passes, n_cols = ceil(n_frames / column).
+struct DeckAnalyseTaps { int32_t lo[128], hi[128]; };
+enum { DECK_AN_SEVERAL = 0, DECK_AN_TILED = 1, DECK_AN_SHORT = 2, DECK_AN_ONE = 3 };
+void launch_deck_analyse(const uint32_t* track, uint64_t n_frames, uint32_t column, uint32_t K, uint32_t max_lag, const DeckAnalyseTaps& taps, void* cols, uint32_t* onsets,
+                         uint64_t* R, uint64_t n_cols, uint32_t forms[4], hipStream_t s);
 
 }  // namespace mx

@@ -7,6 +7,12 @@
 Key-lock (the header's KEY-LOCK) keeps the key while the step sets the tempo:
 
     deck.set_keylock(keylock(pitch_q32=deck_step(44100, 48000, 1.0)))     # hop 1024, overlap 256, radius 512
+
+Analysis (the header's ANALYSIS) looks at the whole track before it sounds -- overview columns, tempo, beat grid:
+
+    deck.analyse(rate=44100.0)                                            # 200 Hz / 2.5 kHz, 63 taps, columns of 512 frames, 256 lags
+    cols, R = deck.read_columns(), deck.read_autocorr()
+    grid = beatgrid(cols, R, 512, 44100.0, 60.0, 200.0)                   # grid.bpm, grid.first_beat_frame, grid.period_columns
 """
 from __future__ import annotations
 
@@ -15,7 +21,7 @@ import ctypes as C
 import numpy as np
 
 from . import abi
-from .abi import DeckGrain, DeckHead, DeckKeylock, DeckParams, DeckTick, check, lib
+from .abi import DeckAnalysis, DeckGrain, DeckGrid, DeckHead, DeckKeylock, DeckParams, DeckTick, check, lib
 
 ONE = 1 << 32   # unity step / one track frame in Q32.32
 
@@ -84,6 +90,68 @@ def debug_last_keylock() -> dict:
     return dict(zip(("grains_searched", "grains_unsearched", "chunks_fading", "chunks_straddling"), (int(v) for v in out)))
 
 
+# mx_deck_column as a numpy record: 56 bytes, the header's layout
+COLUMN_DTYPE = np.dtype([("smin", "<i4"), ("smax", "<i4"), ("peak", "<u4", (3,)), ("onset", "<u4"), ("energy", "<u8", (3,)), ("e", "<u8")])
+
+
+def analysis(column=512, max_lag=256, lo=(16384,), hi=(16384,), taps=None) -> DeckAnalysis:
+    """analysis settings from two Q14 tap tables (the header's ANALYSIS); analysis_bands() designs them"""
+    a = DeckAnalysis()
+    a.column, a.taps, a.max_lag, a._pad = int(column), int(len(lo) if taps is None else taps), int(max_lag), 0
+    if len(lo) != len(hi) or len(lo) > abi.DECK_ANALYSIS_MAX_TAPS:
+        raise ValueError("lo and hi hold the same number of taps, 127 at the most")
+    for k, (l, h) in enumerate(zip(lo, hi)):
+        a.lo[k], a.hi[k] = int(l), int(h)
+    return a
+
+
+def analysis_bands(rate=48000.0, f_lo=200.0, f_hi=2500.0, taps=63, column=512, max_lag=256) -> DeckAnalysis:
+    """settings with Hann-windowed sinc tables at the two cutoffs (mx_deck_analysis_bands, host only); the defaults are the header's recommendation"""
+    a = DeckAnalysis()
+    a.column, a.max_lag = int(column), int(max_lag)
+    check(lib.mx_deck_analysis_bands(float(rate), float(f_lo), float(f_hi), int(taps), C.byref(a)))
+    return a
+
+
+def analysis_check(a: DeckAnalysis) -> None:
+    """the analysis setting rules alone (host only); raises MxError"""
+    check(lib.mx_deck_analysis_check(C.byref(a)))
+
+
+def column_count(n_frames: int, column: int) -> int:
+    n = C.c_uint64()
+    check(lib.mx_deck_column_count(int(n_frames), int(column), C.byref(n)))
+    return n.value
+
+
+def columns_host(interleaved_i16: np.ndarray, a: DeckAnalysis, first: int = 0, n: int | None = None, autocorr: bool = False):
+    """the column and onset rules in plain C++ on the host (pure): COLUMN_DTYPE[n]; with autocorr (all the columns only) also R as uint64[max_lag]"""
+    x = np.ascontiguousarray(interleaved_i16, dtype=np.int16).reshape(-1)
+    if n is None:
+        n = column_count(x.size // 2, a.column) - first
+    cols = np.zeros(max(1, n), COLUMN_DTYPE)
+    R = np.zeros(a.max_lag, np.uint64) if autocorr else None
+    check(lib.mx_deck_columns_host(x.ctypes.data_as(C.c_void_p), x.size // 2, C.byref(a), int(first), int(n), cols.ctypes.data_as(C.c_void_p),
+                                   R.ctypes.data_as(C.c_void_p) if autocorr else None))
+    return (cols[:n], R) if autocorr else cols[:n]
+
+
+def beatgrid(cols: np.ndarray, R: np.ndarray, column: int, rate: float, bpm_lo: float, bpm_hi: float) -> DeckGrid:
+    """tempo and beat phase from columns and their autocorrelation (mx_deck_beatgrid, host only, pure)"""
+    cols = np.ascontiguousarray(cols, dtype=COLUMN_DTYPE)
+    R = np.ascontiguousarray(R, dtype=np.uint64)
+    g = DeckGrid()
+    check(lib.mx_deck_beatgrid(cols.ctypes.data_as(C.c_void_p) if cols.size else None, cols.size, R.ctypes.data_as(C.c_void_p), R.size, int(column),
+                               float(rate), float(bpm_lo), float(bpm_hi), C.byref(g)))
+    return g
+
+
+def debug_last_analysis() -> dict:
+    out = (C.c_uint32 * 4)()
+    check(lib.mx_deck_debug_last_analysis(out))
+    return dict(zip(("wgs_several_columns", "wgs_tiled_column", "short_track", "wgs_one_column"), (int(v) for v in out)))
+
+
 class Deck:
     """Thin RAII wrapper of mx_deck_*."""
 
@@ -139,6 +207,32 @@ class Deck:
         arr = (DeckGrain * max(1, n))()
         check(lib.mx_deck_read_grains(self._h, int(first), int(n), arr))
         return list(arr[:n])
+
+    def analyse(self, a: DeckAnalysis | None = None, **kw):
+        """analyse the whole track as loaded now, asynchronously on the deck's own stream; keywords are analysis_bands()'s; analyse(None) frees the results"""
+        a = a if a is not None else (analysis_bands(**kw) if kw else None)
+        try:
+            check(lib.mx_deck_analyse(self._h, C.byref(a) if a is not None else None))
+        except abi.MxError as e:
+            if e.code != abi.MX_ERR_INVALID:   # refused settings: the deck keeps what it had; anything else (no memory) leaves it without an analysis
+                self._analysis = None
+            raise
+        self._analysis = (column_count(self.n_frames, a.column), a.max_lag) if a is not None else None
+
+    def read_columns(self, first: int = 0, n: int | None = None) -> np.ndarray:
+        """COLUMN_DTYPE[n] of the analysis; waits for it"""
+        n = (self._analysis[0] - first if getattr(self, "_analysis", None) else 0) if n is None else n
+        cols = np.zeros(max(1, n), COLUMN_DTYPE)
+        check(lib.mx_deck_read_columns(self._h, int(first), int(n), cols.ctypes.data_as(C.c_void_p)))
+        return cols[:n]
+
+    def read_autocorr(self, cap: int | None = None) -> np.ndarray:
+        """R as uint64[max_lag] of the analysis; waits for it.  cap is the room offered to the library (by default max_lag): the library fills max_lag of it"""
+        lag = self._analysis[1] if getattr(self, "_analysis", None) else 0   # (the settings of the last analyse() that succeeded: the library has no call that tells them)
+        cap = lag if cap is None else cap
+        R = np.zeros(max(1, cap), np.uint64)
+        check(lib.mx_deck_read_autocorr(self._h, R.ctypes.data_as(C.c_void_p), int(cap)))
+        return R[:lag]
 
     def state(self) -> DeckHead:
         h = DeckHead()
