@@ -48,7 +48,10 @@ extern "C" {
                               *    mx_deck_debug_last_keylock;
                               *    mx_deck_analysis, mx_deck_column, mx_deck_grid, mx_deck_analysis_check, mx_deck_analysis_bands, mx_deck_analyse, mx_deck_column_count,
                               *    mx_deck_read_columns, mx_deck_read_autocorr, mx_deck_columns_host, mx_deck_beatgrid, mx_deck_debug_last_analysis;
-                              *    mx_plan_node, mx_plan_info, mx_graph_debug_plan */
+                              *    mx_plan_node, mx_plan_info, mx_graph_debug_plan;
+                              *    mx_deck_tonality, mx_deck_tonality_check, mx_deck_tonality_count, mx_deck_analyse_tonality, mx_deck_read_tonality, mx_deck_tonality_host,
+                              *    mx_deck_debug_last_tonality, mx_deck_loudness, mx_deck_loudness_check, mx_deck_loudness_count, mx_deck_analyse_loudness,
+                              *    mx_deck_read_loudness, mx_deck_loudness_host, mx_deck_debug_last_loudness, mx_deck_loudness_gain, mx_tonality_camelot */
 
 /* ---- status codes (0 ok, <0 error; cf. MIXLAB_IOCTX_ERROR / MIXLAB_IOCTX_PANIC) ---- */
 enum {
@@ -1005,6 +1008,97 @@ int mx_deck_beatgrid(const mx_deck_column* cols, uint64_t n_cols, const uint64_t
  * that each took one column in several tiles of 1024 frames (C > 1024), out[2] 1 when the track was shorter than the halo (n_frames < K - 1: one workgroup, a lane
  * per frame), out[3] workgroups of one column in one tile (C = 1024).  Tests use it to know every form ran. */
 int mx_deck_debug_last_analysis(uint32_t out[4]);
+
+/* ---- KEY AND LOUDNESS: the whole track's constant-Q sums and its K-weighted loudness, before it sounds ----
+ * BUILD-SPECIFIED.  Two more analyses of the track as it lies in device memory, each asynchronous on the deck's own load stream like mx_deck_analyse: ordered after
+ * earlier mx_deck_load_i16 calls and before later ones, not ordered against feeds (both only read the track).  Each keeps its results in device memory the deck owns; a
+ * later call of the same kind replaces them, NULL frees them; a result is a snapshot that a later load does not invalidate.  The two are independent of each other and
+ * of mx_deck_analyse's results.  No arithmetic rule is new: the tonality taps' and the loudness taps' texts above hold word for word, read over one stream that is the
+ * track.  A deck that never calls them is untouched in every respect.
+ *
+ * TONALITY
+ * SETTINGS   mx_deck_tonality: decim D, hop_frames Hc, octaves O and f_lo_mhz under the tonality taps' rules (D 4 or 8; Hc 128, 256 or 512; O 2 .. 6; f_lo_mhz >= 1),
+ *            and the kernels must exist at `rate` as mx_tonality_tables says (it refuses N_0 > 2048 and a top bin at 0.45 fs_d); segment_hops G 1 .. 65536; rate finite
+ *            and positive; _pad 0.  mx_deck_tonality_check enforces exactly these rules.
+ * STREAM     F = G Hc D frames make a segment, n_seg = ceil(n_frames / F).  The stream is frames 0 .. n_seg F - 1 of the track; frames at or beyond n_frames read as 0
+ *            (the deck's own rule).  Every hop of that stream counts, so every segment has G hops.
+ * QUANTISE   s[f] = L[f] + R[f] of the raw int16 (key-lock's and ANALYSIS' s); q[f] = s[f] / 4 with C's integer division, which truncates toward zero.  That IS the
+ *            tap's q for L = l / 32768, R = r / 32768: m = (l + r) / 32768 is exact in f32, |m| <= 2, and trunc(m 8192) = trunc(s / 4).  It is not s >> 2 (they differ
+ *            for a negative s that is no multiple of 4).  nonfinite is always 0.
+ * DECIMATE, KERNELS, HOP   the tonality taps' text unchanged, with the tables of mx_tonality_tables(rate, ...): d[n] = (sum_k c[k] q[n D - k]) >> 15,
+ *            M_b[h] = isqrt((S_re >> 10)^2 + (S_im >> 10)^2); q and d at negative indices are 0.
+ * RECORDS    n_seg records of mx_tonality_record_bytes each, in the tap's own layout (mx_tonality_chroma and mx_tonality_key take them as they are): the header is
+ *            { g, G, 0, D, Hc, O, f_lo_mhz, 0 }, and C[b] = the sum of M_b[h] over the hops h of [g G, (g + 1) G).
+ * IT FOLLOWS that record g equals byte for byte what a tonality tap with emit_ticks 1 emits for tick g of a run over the zero-padded track, L = l / 32768 and
+ *            R = r / 32768, in ticks of F frames: hop h completes in the tick that holds input frame ((h + 1) Hc - 1) D, which lies in [g F, (g + 1) F) exactly for the
+ *            hops of segment g (tests/tonality_model.py is held to that).
+ *
+ * LOUDNESS
+ * SETTINGS   mx_deck_loudness: rate as mx_loudness_tables accepts it; block_frames F 64 .. 65536; momentary_blocks M and short_blocks S 1 .. 1024 each; _pad 0.
+ *            mx_deck_loudness_check enforces exactly these rules.
+ * STREAM     n_blocks = ceil(n_frames / F); block k is frames [k F, (k + 1) F), frames at or beyond n_frames read as +0.0f.  A sample is (float)s / 32768.0f per channel
+ *            (exact; the deck's rule).
+ * RULE       the loudness taps' text unchanged with "tick" read as "block": the biquads and P = carry of mx_loudness_tables(rate, F); the transposed direct form II walk
+ *            with every f64 operation rounded on its own; S_0 = +0.0, S_k+1 = Z_k + P S_k with the rows summed left to right; ksq from 8 partials and the 4-2-1
+ *            butterfly; both window sums afresh in ascending block from +0.0, blocks before the first reading +0.0; the true peak through interp with 11 frames of
+ *            run-in that read +0.0 before frame 0 and are the track's own from then on.
+ * RECORDS    mx_loudness_tick itself, n_blocks of them, with frames = F and channels = 2.
+ * IT FOLLOWS that the records equal bit for bit what a loudness tap reads from this deck played at unity from frame 0 into a graph of F frames per tick
+ *            (tests/loudness_model.py is held to that).
+ *
+ * READ-OUTS  mx_deck_loudness_gain: gated integrated loudness, true peak and the gain that reaches a target under a ceiling, from the records.  mx_tonality_camelot: the
+ *            wheel position of a key ("8A").  Both host only, pure, f64.
+ * Out of scope: key tracked within a track beyond what the segment records allow a host to do; tuning other than A = 440 (move f_lo_mhz); analysis of a range of the
+ * track; more than two channels; applying the gain (the host sets it on the strip); any change to how a deck plays or to any tap. */
+typedef struct { double rate; uint32_t decim, hop_frames, octaves, f_lo_mhz; uint32_t segment_hops; uint32_t _pad; } mx_deck_tonality;   /* 32 bytes */
+typedef struct { double rate; uint32_t block_frames, momentary_blocks, short_blocks, _pad; } mx_deck_loudness;   /* 24 bytes */
+/* Host only: the TONALITY SETTINGS rules alone; MX_ERR_INVALID names the rule in mx_last_error. */
+int mx_deck_tonality_check(const mx_deck_tonality* t);
+/* Host only: *n_seg = ceil(n_frames / (G Hc D)).  n_frames outside 1 .. 2^30, settings the check refuses, NULL: MX_ERR_INVALID. */
+int mx_deck_tonality_count(uint64_t n_frames, const mx_deck_tonality* t, uint64_t* n_seg);
+/* Analyse the whole track's tonality as loaded now (above).  Device memory: n_seg records, n_seg G Hc int16 of decimated frames, and one table set.  Settings that fail the
+ * check: MX_ERR_INVALID, and the deck keeps what it had.  Memory that cannot be had: MX_ERR_NOMEM, and the deck is left without this analysis.  NULL frees it. */
+int mx_deck_analyse_tonality(mx_deck* d, const mx_deck_tonality* t);
+/* Records [first, first + n) into dst[0 .. cap_bytes); waits for the analysis, like mx_deck_read_columns.  No analysis, a window beyond n_seg, cap_bytes below
+ * n x record bytes, NULL: MX_ERR_INVALID. */
+int mx_deck_read_tonality(mx_deck* d, uint64_t first, uint64_t n, void* dst, size_t cap_bytes);
+/* Host only, pure: the TONALITY rules in plain C++ for segments [first, first + n) of a track of n_frames interleaved stereo frames (1 .. 2^30), n x record bytes into
+ * dst -- how the rules are tested without a device, and the single-thread baseline of the device path.  Settings the check refuses, a window beyond n_seg, NULL:
+ * MX_ERR_INVALID. */
+int mx_deck_tonality_host(const int16_t* interleaved, uint64_t n_frames, const mx_deck_tonality* t, uint64_t first, uint64_t n, void* dst);
+/* DEBUG: what the last mx_deck_analyse_tonality of this process launched: out[0] decimator workgroups (256 lanes; 512 decimated frames each from one staged window of
+ * quantised frames), out[1] constant-Q workgroups that took a full 8 hops of a segment (256 lanes: 8 hops staged at once, a wave per bin, every table entry loaded once
+ * for the 8), out[2] constant-Q workgroups that took fewer (the tail of a segment, or G < 8), out[3] workgroups of the kernel that writes the headers and zeroes the sums
+ * (256 lanes, one per 64-bit word).  Tests use it to know every form ran. */
+int mx_deck_debug_last_tonality(uint32_t out[4]);
+/* Host only: the LOUDNESS SETTINGS rules alone; MX_ERR_INVALID names the rule in mx_last_error. */
+int mx_deck_loudness_check(const mx_deck_loudness* l);
+/* Host only: *n_blocks = ceil(n_frames / block_frames).  n_frames outside 1 .. 2^30, block_frames outside 64 .. 65536, NULL: MX_ERR_INVALID. */
+int mx_deck_loudness_count(uint64_t n_frames, uint32_t block_frames, uint64_t* n_blocks);
+/* Analyse the whole track's loudness as loaded now (above).  Device memory: n_blocks x (48 bytes of records + 64 bytes of walk states).  Refusals as
+ * mx_deck_analyse_tonality; NULL frees it. */
+int mx_deck_analyse_loudness(mx_deck* d, const mx_deck_loudness* l);
+/* Records [first, first + n); waits for the analysis.  No analysis, a window beyond n_blocks, NULL: MX_ERR_INVALID. */
+int mx_deck_read_loudness(mx_deck* d, uint64_t first, uint64_t n, mx_loudness_tick* dst);
+/* Host only, pure: the LOUDNESS rules in plain C++ for the whole track (the state is a recurrence: there is no window), n_blocks records into dst[0 .. cap).  Settings
+ * the check refuses, n_frames outside 1 .. 2^30, cap below n_blocks, NULL: MX_ERR_INVALID. */
+int mx_deck_loudness_host(const int16_t* interleaved, uint64_t n_frames, const mx_deck_loudness* l, mx_loudness_tick* dst, uint64_t cap);
+/* DEBUG: what the last mx_deck_analyse_loudness of this process launched: out[0] true-peak workgroups (256 lanes; a tile of 1024 frames staged once with its 11-frame
+ * run-in, a lane per frame), out[1] walk workgroups of EACH of the two walks (one wave; 32 blocks, a lane per block and channel), out[2] steps of the one serial scan
+ * (n_blocks; one lane per channel), out[3] window workgroups (256 lanes, one per block).  Tests use it to know every form ran. */
+int mx_deck_debug_last_loudness(uint32_t out[4]);
+/* Host only, pure, f64: programme loudness, true peak and gain from n records of one analysis (or one tap).  The measurement blocks are the records
+ * i = i0, i0 + hop_blocks, ... < n with i0 = min(momentary_blocks - 1, n - 1); each has block_sq = recs[i].momentary_sq over momentary_blocks x recs[i].frames frames.
+ * *lufs = what mx_loudness_gate says of them (-inf when nothing passes the gates); *peak_dbtp = 20 log10 of the largest true_peak over all records and both channels,
+ * -inf for 0; *gain_db = min(target_lufs - *lufs, ceiling_dbtp - *peak_dbtp), and 0 when *lufs is -inf.  With F = 4800 at 48 kHz, momentary_blocks = 4 and
+ * hop_blocks = 1 the blocks are the standard's 400 ms at 75 % overlap.  n = 0, hop_blocks = 0, momentary_blocks outside 1 .. 1024, a record of 0 frames, NULL, a target or
+ * ceiling that is not finite: MX_ERR_INVALID. */
+int mx_deck_loudness_gain(const mx_loudness_tick* recs, uint64_t n, uint32_t momentary_blocks, uint32_t hop_blocks, double target_lufs, double ceiling_dbtp,
+                          double* lufs, double* peak_dbtp, double* gain_db);
+/* Host only: the Camelot wheel position DJs read for a key of mx_tonality_key.  With t the tonic: major (key 0 .. 11, t = key): *number = ((7 t + 7) mod 12) + 1,
+ * *minor = 0 ("B"); minor (key 12 .. 23, t = key - 12): *number = ((7 t + 4) mod 12) + 1, *minor = 1 ("A").  C major is 8B, A minor 8A, B major 1B.  A key outside
+ * 0 .. 23 (-1 included) or NULL: MX_ERR_INVALID. */
+int mx_tonality_camelot(int key, uint32_t* number, uint32_t* minor);
 
 /* ---------------------------------------------------------------------------------------------- */
 /* pixel path: device-resident yuv420p frames, VideoMixer, scaler, colour                          */

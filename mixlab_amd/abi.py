@@ -426,6 +426,27 @@ _proto("mx_deck_read_autocorr", C.c_int, C.c_void_p, C.c_void_p, C.c_uint32)
 _proto("mx_deck_columns_host", C.c_int, C.c_void_p, C.c_uint64, C.POINTER(DeckAnalysis), C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p)
 _proto("mx_deck_beatgrid", C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_double, C.POINTER(DeckGrid))
 _proto("mx_deck_debug_last_analysis", C.c_int, C.POINTER(C.c_uint32))
+# ... its key and loudness (the header's KEY AND LOUDNESS): the tonality and loudness taps' rules over the whole track
+class DeckTonality(C.Structure):
+    _fields_ = [("rate", C.c_double), ("decim", C.c_uint32), ("hop_frames", C.c_uint32), ("octaves", C.c_uint32), ("f_lo_mhz", C.c_uint32),
+                ("segment_hops", C.c_uint32), ("_pad", C.c_uint32)]
+class DeckLoudness(C.Structure):
+    _fields_ = [("rate", C.c_double), ("block_frames", C.c_uint32), ("momentary_blocks", C.c_uint32), ("short_blocks", C.c_uint32), ("_pad", C.c_uint32)]
+_proto("mx_deck_tonality_check", C.c_int, C.POINTER(DeckTonality))
+_proto("mx_deck_tonality_count", C.c_int, C.c_uint64, C.POINTER(DeckTonality), C.POINTER(C.c_uint64))
+_proto("mx_deck_analyse_tonality", C.c_int, C.c_void_p, C.POINTER(DeckTonality))
+_proto("mx_deck_read_tonality", C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_size_t)
+_proto("mx_deck_tonality_host", C.c_int, C.c_void_p, C.c_uint64, C.POINTER(DeckTonality), C.c_uint64, C.c_uint64, C.c_void_p)
+_proto("mx_deck_debug_last_tonality", C.c_int, C.POINTER(C.c_uint32))
+_proto("mx_deck_loudness_check", C.c_int, C.POINTER(DeckLoudness))
+_proto("mx_deck_loudness_count", C.c_int, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64))
+_proto("mx_deck_analyse_loudness", C.c_int, C.c_void_p, C.POINTER(DeckLoudness))
+_proto("mx_deck_read_loudness", C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p)
+_proto("mx_deck_loudness_host", C.c_int, C.c_void_p, C.c_uint64, C.POINTER(DeckLoudness), C.c_void_p, C.c_uint64)
+_proto("mx_deck_debug_last_loudness", C.c_int, C.POINTER(C.c_uint32))
+_proto("mx_deck_loudness_gain", C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
+       C.POINTER(C.c_double))
+_proto("mx_tonality_camelot", C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32))
 _proto("mx_module_create", C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p))
 _proto("mx_module_create_ex", C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(GraphOpts), C.POINTER(C.c_void_p))
 _proto("mx_module_update", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)

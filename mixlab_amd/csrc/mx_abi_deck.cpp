@@ -1,5 +1,7 @@
 // mx_abi_deck.cpp -- extern "C" entry points of the deck (include/mixlab_gpu.h, "the deck").
 // Same fencing convention as mx_abi.cpp: catch everything, stash the message, return a status.
+#include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <memory>
 #include <string>
@@ -112,6 +114,71 @@ int mx_deck_beatgrid(const mx_deck_column* cols, uint64_t n_cols, const uint64_t
 }
 int mx_deck_debug_last_analysis(uint32_t out[4]) {
     return guard([&] { REQUIRE(out, "out is NULL"); Deck::debug_last_analysis(out); });
+}
+int mx_deck_tonality_check(const mx_deck_tonality* t) {
+    return guard([&] { REQUIRE(t, "settings are NULL"); mx::deck_tonality_check(*t); });
+}
+int mx_deck_tonality_count(uint64_t n_frames, const mx_deck_tonality* t, uint64_t* n_seg) {
+    return guard([&] { REQUIRE(t && n_seg, "NULL argument"); *n_seg = mx::deck_tonality_count(n_frames, *t); });
+}
+int mx_deck_analyse_tonality(mx_deck* d, const mx_deck_tonality* t) {
+    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.analyse_tonality(t); });
+}
+int mx_deck_read_tonality(mx_deck* d, uint64_t first, uint64_t n, void* dst, size_t cap_bytes) {
+    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.read_tonality(first, n, dst, cap_bytes); });
+}
+int mx_deck_tonality_host(const int16_t* interleaved, uint64_t n_frames, const mx_deck_tonality* t, uint64_t first, uint64_t n, void* dst) {
+    return guard([&] { REQUIRE(t, "settings are NULL"); mx::deck_tonality_host(interleaved, n_frames, *t, first, n, dst); });
+}
+int mx_deck_debug_last_tonality(uint32_t out[4]) {
+    return guard([&] { REQUIRE(out, "out is NULL"); Deck::debug_last_tonality(out); });
+}
+int mx_deck_loudness_check(const mx_deck_loudness* l) {
+    return guard([&] { REQUIRE(l, "settings are NULL"); mx::deck_loudness_check(*l); });
+}
+int mx_deck_loudness_count(uint64_t n_frames, uint32_t block_frames, uint64_t* n_blocks) {
+    return guard([&] { REQUIRE(n_blocks, "n_blocks is NULL"); *n_blocks = mx::deck_loudness_count(n_frames, block_frames); });
+}
+int mx_deck_analyse_loudness(mx_deck* d, const mx_deck_loudness* l) {
+    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.analyse_loudness(l); });
+}
+int mx_deck_read_loudness(mx_deck* d, uint64_t first, uint64_t n, mx_loudness_tick* dst) {
+    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.read_loudness(first, n, dst); });
+}
+int mx_deck_loudness_host(const int16_t* interleaved, uint64_t n_frames, const mx_deck_loudness* l, mx_loudness_tick* dst, uint64_t cap) {
+    return guard([&] { REQUIRE(l, "settings are NULL"); mx::deck_loudness_host(interleaved, n_frames, *l, dst, cap); });
+}
+int mx_deck_debug_last_loudness(uint32_t out[4]) {
+    return guard([&] { REQUIRE(out, "out is NULL"); Deck::debug_last_loudness(out); });
+}
+int mx_deck_loudness_gain(const mx_loudness_tick* recs, uint64_t n, uint32_t momentary_blocks, uint32_t hop_blocks, double target_lufs, double ceiling_dbtp,
+                          double* lufs, double* peak_dbtp, double* gain_db) {
+    return guard([&] {
+        REQUIRE(recs && lufs && peak_dbtp && gain_db, "NULL argument");
+        REQUIRE(n > 0 && hop_blocks > 0, "no records, or hop_blocks is 0");
+        REQUIRE(momentary_blocks >= 1 && momentary_blocks <= 1024, "momentary_blocks outside 1 .. 1024");
+        REQUIRE(std::isfinite(target_lufs) && std::isfinite(ceiling_dbtp), "target_lufs or ceiling_dbtp is not finite");
+        std::vector<double> sq; std::vector<uint32_t> fr;
+        for (uint64_t i = std::min<uint64_t>(momentary_blocks - 1, n - 1); i < n; i += hop_blocks) {
+            const uint64_t f = (uint64_t)momentary_blocks * recs[i].frames;
+            REQUIRE(f > 0 && f <= 0xffffffffu, "a record of 0 frames, or a measurement block beyond 2^32 frames");
+            sq.push_back(recs[i].momentary_sq); fr.push_back((uint32_t)f);
+        }
+        double l = 0.0;
+        if (mx_loudness_gate(sq.data(), fr.data(), sq.size(), &l, nullptr) != MX_OK) throw Error(MX_ERR_INVALID, mx_last_error());
+        float peak = 0.0f;
+        for (uint64_t i = 0; i < n; ++i) peak = std::max(peak, std::max(recs[i].true_peak[0], recs[i].true_peak[1]));
+        const double p = peak > 0.0f ? 20.0 * std::log10((double)peak) : -HUGE_VAL;
+        *lufs = l; *peak_dbtp = p;
+        *gain_db = l == -HUGE_VAL ? 0.0 : std::min(target_lufs - l, ceiling_dbtp - p);
+    });
+}
+int mx_tonality_camelot(int key, uint32_t* number, uint32_t* minor) {
+    return guard([&] {
+        REQUIRE(number && minor, "NULL argument"); REQUIRE(key >= 0 && key <= 23, "key outside 0 .. 23");
+        const int m = key >= 12, t = key - 12 * m;
+        *number = (uint32_t)((7 * t + (m ? 4 : 7)) % 12) + 1u; *minor = (uint32_t)m;
+    });
 }
 
 }  // extern "C"

@@ -66,6 +66,13 @@ void deck_analysis_bands(double rate, double f_lo, double f_hi, uint32_t taps, m
 uint64_t deck_column_count(uint64_t n_frames, uint32_t column);
 void deck_columns_host(const int16_t* interleaved, uint64_t n_frames, const mx_deck_analysis& a, uint64_t first, uint64_t n, mx_deck_column* cols, uint64_t* R_or_null);
 void deck_beatgrid(const mx_deck_column* cols, uint64_t n_cols, const uint64_t* R, uint32_t max_lag, uint32_t column, double rate, double bpm_lo, double bpm_hi, mx_deck_grid& out);
+// whole-track tonality and loudness (the header's KEY AND LOUDNESS; mx_k_deck_tonality.hip, mx_k_deck_loudness.hip)
+void deck_tonality_check(const mx_deck_tonality& t);                                 // throws Error(MX_ERR_INVALID) naming the rule
+uint64_t deck_tonality_count(uint64_t n_frames, const mx_deck_tonality& t);
+void deck_tonality_host(const int16_t* interleaved, uint64_t n_frames, const mx_deck_tonality& t, uint64_t first, uint64_t n, void* dst);
+void deck_loudness_check(const mx_deck_loudness& l);                                 // throws Error(MX_ERR_INVALID) naming the rule
+uint64_t deck_loudness_count(uint64_t n_frames, uint32_t block_frames);
+void deck_loudness_host(const int16_t* interleaved, uint64_t n_frames, const mx_deck_loudness& l, mx_loudness_tick* dst, uint64_t cap);
 void deck_check(const mx_deck_params& p, uint64_t n_frames);                         // throws Error(MX_ERR_INVALID) naming the rule
 void deck_plan(const mx_deck_head& in, const mx_deck_params* params, const int64_t* seek, uint32_t spt, uint64_t n_frames, mx_deck_tick& tick, mx_deck_head& out);
 int64_t deck_step(uint32_t track_rate, uint32_t graph_rate, double speed);
@@ -93,6 +100,12 @@ public:
     void read_columns(uint64_t first, uint64_t n, mx_deck_column* dst);    // waits for the analysis
     void read_autocorr(uint64_t* R, uint32_t cap);                         // waits for the analysis
     static void debug_last_analysis(uint32_t out[4]);
+    void analyse_tonality(const mx_deck_tonality* t);                      // NULL: frees the results.  Asynchronous on the load stream.
+    void read_tonality(uint64_t first, uint64_t n, void* dst, size_t cap_bytes);   // waits for the analysis
+    static void debug_last_tonality(uint32_t out[4]);
+    void analyse_loudness(const mx_deck_loudness* l);                      // NULL: frees the results.  Asynchronous on the load stream.
+    void read_loudness(uint64_t first, uint64_t n, mx_loudness_tick* dst);  // waits for the analysis
+    static void debug_last_loudness(uint32_t out[4]);
 
 private:
     void fetch_grains();
@@ -115,6 +128,12 @@ private:
     // analysis: one buffer -- columns (an_cols_ x 56 bytes), R (an_lag_ x 8), onsets (an_cols_ x 4) -- written on load_stream_ only; an_cols_ = 0: none
     DevBuf an_;
     uint64_t an_cols_ = 0; uint32_t an_lag_ = 0;
+    // whole-track tonality: one buffer -- ton_segs_ records of ton_rec_bytes_, then the decimated frames -- and the table set of ton_tab_for_ with its decimator taps ton_fir_ (kept while the settings
+    // that shape them stay); loudness: one buffer -- loud_blocks_ records, then the walk states.  All written on load_stream_ only; a count of 0: none
+    DevBuf ton_, ton_tab_;
+    uint64_t ton_segs_ = 0; size_t ton_rec_bytes_ = 0; mx_deck_tonality ton_tab_for_{}; int16_t ton_fir_[64] = {};
+    DevBuf loud_;
+    uint64_t loud_blocks_ = 0;
 };
 
 }  // namespace mx

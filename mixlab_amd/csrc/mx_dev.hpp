@@ -43,6 +43,14 @@ __host__ __device__ __forceinline__ uint32_t tempo_root(uint64_t e) {
     return (uint32_t)r;
 }
 
+// floor(sqrt(x)), x < 2^61: the f64 root of the rounded x is within one of it (the tonality taps' magnitudes and the deck's whole-track tonality, device and host)
+__host__ __device__ __forceinline__ uint64_t ton_root(uint64_t x) {
+    uint64_t r = (uint64_t)sqrt((double)x);
+    while (r * r > x) --r;
+    while ((r + 1) * (r + 1) <= x) ++r;
+    return r;
+}
+
 inline unsigned grid_x(size_t items, unsigned block, unsigned cap) {
     size_t b = (items + block - 1) / block;
     if (b < 1) b = 1;

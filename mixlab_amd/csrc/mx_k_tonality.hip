@@ -45,14 +45,6 @@ __device__ __forceinline__ int32_t ton_frame(const TonDesc& d, uint64_t f, bool&
     return ton_quantise(a, b, bad);
 }
 
-// floor(sqrt(x)), x < 2^61: the f64 root of the rounded x is within one of it
-__device__ __forceinline__ uint64_t ton_root(uint64_t x) {
-    uint64_t r = (uint64_t)sqrt((double)x);
-    while (r * r > x) --r;
-    while ((r + 1) * (r + 1) <= x) ++r;
-    return r;
-}
-
 // where a count or a sum of tick `tick` of the run goes: the record of the tick's emission, or what is carried behind the run's last one
 __device__ __forceinline__ uint32_t* ton_record(const TonRun& r, const TonDesc& d, uint64_t tick) {
     const uint64_t grp = ((uint64_t)r.phase + tick) / r.emit_ticks;

@@ -21,7 +21,7 @@ import ctypes as C
 import numpy as np
 
 from . import abi
-from .abi import DeckAnalysis, DeckGrain, DeckGrid, DeckHead, DeckKeylock, DeckParams, DeckTick, check, lib
+from .abi import DeckAnalysis, DeckGrain, DeckGrid, DeckHead, DeckKeylock, DeckLoudness, DeckParams, DeckTick, DeckTonality, check, lib
 
 ONE = 1 << 32   # unity step / one track frame in Q32.32
 
@@ -152,6 +152,87 @@ def debug_last_analysis() -> dict:
     return dict(zip(("wgs_several_columns", "wgs_tiled_column", "short_track", "wgs_one_column"), (int(v) for v in out)))
 
 
+def tonality(rate=48000.0, decim=8, hop_frames=512, octaves=5, f_lo_mhz=65406, segment_hops=64) -> DeckTonality:
+    """whole-track tonality settings (the header's KEY AND LOUDNESS); the defaults are five octaves from C2 in segments of 64 hops (5.5 s at 48 kHz)"""
+    return DeckTonality(float(rate), int(decim), int(hop_frames), int(octaves), int(f_lo_mhz), int(segment_hops), 0)
+
+
+def tonality_check(t: DeckTonality) -> None:
+    """the tonality setting rules alone (host only); raises MxError"""
+    check(lib.mx_deck_tonality_check(C.byref(t)))
+
+
+def tonality_count(n_frames: int, t: DeckTonality) -> int:
+    n = C.c_uint64()
+    check(lib.mx_deck_tonality_count(int(n_frames), C.byref(t), C.byref(n)))
+    return n.value
+
+
+def tonality_host(interleaved_i16: np.ndarray, t: DeckTonality, first: int = 0, n: int | None = None) -> list:
+    """the tonality rules in plain C++ on the host (pure): segments [first, first + n) as abi.parse_tonality_records dicts"""
+    x = np.ascontiguousarray(interleaved_i16, dtype=np.int16).reshape(-1)
+    if n is None:
+        n = tonality_count(x.size // 2, t) - first
+    tonality_check(t)   # before a buffer is sized from the settings
+    rb = 32 + 96 * t.octaves
+    raw = np.zeros(max(1, n) * rb, np.uint8)
+    check(lib.mx_deck_tonality_host(x.ctypes.data_as(C.c_void_p), x.size // 2, C.byref(t), int(first), int(n), raw.ctypes.data_as(C.c_void_p)))
+    return abi.parse_tonality_records(raw[:n * rb], t.octaves)
+
+
+def debug_last_tonality() -> dict:
+    out = (C.c_uint32 * 4)()
+    check(lib.mx_deck_debug_last_tonality(out))
+    return dict(zip(("wgs_decimate", "wgs_cq_full", "wgs_cq_part", "wgs_head"), (int(v) for v in out)))
+
+
+def loudness(rate=48000.0, block_frames=4800, momentary_blocks=4, short_blocks=30) -> DeckLoudness:
+    """whole-track loudness settings (the header's KEY AND LOUDNESS); the defaults are 100 ms blocks at 48 kHz, 400 ms and 3 s windows"""
+    return DeckLoudness(float(rate), int(block_frames), int(momentary_blocks), int(short_blocks), 0)
+
+
+def loudness_check(l: DeckLoudness) -> None:
+    """the loudness setting rules alone (host only); raises MxError"""
+    check(lib.mx_deck_loudness_check(C.byref(l)))
+
+
+def loudness_count(n_frames: int, block_frames: int) -> int:
+    n = C.c_uint64()
+    check(lib.mx_deck_loudness_count(int(n_frames), int(block_frames), C.byref(n)))
+    return n.value
+
+
+def loudness_host(interleaved_i16: np.ndarray, l: DeckLoudness) -> np.ndarray:
+    """the loudness rules in plain C++ on the host (pure), the whole track: abi.LOUDNESS_TICK_DTYPE[n_blocks]"""
+    x = np.ascontiguousarray(interleaved_i16, dtype=np.int16).reshape(-1)
+    n = loudness_count(x.size // 2, l.block_frames)
+    out = np.zeros(n, abi.LOUDNESS_TICK_DTYPE)
+    check(lib.mx_deck_loudness_host(x.ctypes.data_as(C.c_void_p), x.size // 2, C.byref(l), out.ctypes.data_as(C.c_void_p), n))
+    return out
+
+
+def debug_last_loudness() -> dict:
+    out = (C.c_uint32 * 4)()
+    check(lib.mx_deck_debug_last_loudness(out))
+    return dict(zip(("wgs_peak", "wgs_walk", "scan_steps", "wgs_window"), (int(v) for v in out)))
+
+
+def loudness_gain(recs: np.ndarray, momentary_blocks: int = 4, hop_blocks: int = 1, target_lufs: float = -14.0, ceiling_dbtp: float = -1.0):
+    """(integrated LUFS, true peak in dBTP, gain in dB that reaches the target under the ceiling) from loudness records (mx_deck_loudness_gain, host only)"""
+    r = np.ascontiguousarray(recs, dtype=abi.LOUDNESS_TICK_DTYPE)
+    lufs, peak, gain = C.c_double(), C.c_double(), C.c_double()
+    check(lib.mx_deck_loudness_gain(r.ctypes.data_as(C.c_void_p) if r.size else None, r.size, int(momentary_blocks), int(hop_blocks), float(target_lufs),
+                                    float(ceiling_dbtp), C.byref(lufs), C.byref(peak), C.byref(gain)))
+    return lufs.value, peak.value, gain.value
+
+
+def camelot(key: int) -> str:
+    """the Camelot wheel position of a key of abi.tonality_key: "8B" is C major, "8A" A minor (mx_tonality_camelot, host only)"""
+    number, minor = C.c_uint32(), C.c_uint32()
+    check(lib.mx_tonality_camelot(int(key), C.byref(number), C.byref(minor)))
+    return f"{number.value}{'A' if minor.value else 'B'}"
+
+
 class Deck:
     """Thin RAII wrapper of mx_deck_*."""
 
@@ -233,6 +314,49 @@ class Deck:
         R = np.zeros(max(1, cap), np.uint64)
         check(lib.mx_deck_read_autocorr(self._h, R.ctypes.data_as(C.c_void_p), int(cap)))
         return R[:lag]
+
+    def analyse_tonality(self, t: DeckTonality | None = None, **kw):
+        """the whole track's constant-Q sums per segment, asynchronously on the deck's own stream; keywords are tonality()'s; analyse_tonality(None) frees them"""
+        t = t if t is not None else (tonality(**kw) if kw else None)
+        try:
+            check(lib.mx_deck_analyse_tonality(self._h, C.byref(t) if t is not None else None))
+        except abi.MxError as e:
+            if e.code != abi.MX_ERR_INVALID:
+                self._tonality = None
+            raise
+        self._tonality = (tonality_count(self.n_frames, t), t.octaves) if t is not None else None
+
+    def read_tonality(self, first: int = 0, n: int | None = None) -> list:
+        """segments [first, first + n) of the tonality analysis as abi.parse_tonality_records dicts; waits for it"""
+        segs, octaves = getattr(self, "_tonality", None) or (0, 2)
+        n = segs - first if n is None else n
+        rb = 32 + 96 * octaves
+        raw = np.zeros(max(1, n) * rb, np.uint8)
+        check(lib.mx_deck_read_tonality(self._h, int(first), int(n), raw.ctypes.data_as(C.c_void_p), max(0, n) * rb))
+        return abi.parse_tonality_records(raw[:n * rb], octaves)
+
+    def key(self, rate: float):
+        """(key, confidence, Camelot position such as "8A") of the whole track from the summed segment records; key -1 (no variance) has position \"\""""
+        k, conf = abi.tonality_key(abi.tonality_chroma(self.read_tonality(), rate))
+        return k, conf, (camelot(k) if k >= 0 else "")
+
+    def analyse_loudness(self, l: DeckLoudness | None = None, **kw):
+        """the whole track's loudness records per block, asynchronously on the deck's own stream; keywords are loudness()'s; analyse_loudness(None) frees them"""
+        l = l if l is not None else (loudness(**kw) if kw else None)
+        try:
+            check(lib.mx_deck_analyse_loudness(self._h, C.byref(l) if l is not None else None))
+        except abi.MxError as e:
+            if e.code != abi.MX_ERR_INVALID:
+                self._loudness = None
+            raise
+        self._loudness = loudness_count(self.n_frames, l.block_frames) if l is not None else None
+
+    def read_loudness(self, first: int = 0, n: int | None = None) -> np.ndarray:
+        """abi.LOUDNESS_TICK_DTYPE[n] of the loudness analysis; waits for it"""
+        n = ((getattr(self, "_loudness", None) or 0) - first) if n is None else n
+        out = np.zeros(max(1, n), abi.LOUDNESS_TICK_DTYPE)
+        check(lib.mx_deck_read_loudness(self._h, int(first), int(n), out.ctypes.data_as(C.c_void_p)))
+        return out[:n]
 
     def state(self) -> DeckHead:
         h = DeckHead()
