@@ -51,7 +51,10 @@ extern "C" {
                               *    mx_plan_node, mx_plan_info, mx_graph_debug_plan;
                               *    mx_deck_tonality, mx_deck_tonality_check, mx_deck_tonality_count, mx_deck_analyse_tonality, mx_deck_read_tonality, mx_deck_tonality_host,
                               *    mx_deck_debug_last_tonality, mx_deck_loudness, mx_deck_loudness_check, mx_deck_loudness_count, mx_deck_analyse_loudness,
-                              *    mx_deck_read_loudness, mx_deck_loudness_host, mx_deck_debug_last_loudness, mx_deck_loudness_gain, mx_tonality_camelot */
+                              *    mx_deck_read_loudness, mx_deck_loudness_host, mx_deck_debug_last_loudness, mx_deck_loudness_gain, mx_tonality_camelot;
+                              *    mx_deck_finegrid, mx_deck_comb, mx_deck_beats, mx_deck_fine_pick, mx_deck_sync_result, mx_deck_finegrid_check, mx_deck_finegrid_count,
+                              *    mx_deck_finegrid_span, mx_deck_analyse_finegrid, mx_deck_read_finegrid, mx_deck_read_fine_onsets, mx_deck_finegrid_host,
+                              *    mx_deck_finegrid_pick, mx_deck_finegrid_period, mx_deck_sync, mx_deck_debug_last_finegrid */
 
 /* ---- status codes (0 ok, <0 error; cf. MIXLAB_IOCTX_ERROR / MIXLAB_IOCTX_PANIC) ---- */
 enum {
@@ -1099,6 +1102,90 @@ int mx_deck_loudness_gain(const mx_loudness_tick* recs, uint64_t n, uint32_t mom
  * *minor = 0 ("B"); minor (key 12 .. 23, t = key - 12): *number = ((7 t + 4) mod 12) + 1, *minor = 1 ("A").  C major is 8B, A minor 8A, B major 1B.  A key outside
  * 0 .. 23 (-1 included) or NULL: MX_ERR_INVALID. */
 int mx_tonality_camelot(int key, uint32_t* number, uint32_t* minor);
+
+/* ---- FINE GRID: the beat period and phase of a whole track to a fine hop, by a comb search on the device, and the arithmetic that puts two decks in time ----
+ * BUILD-SPECIFIED.  mx_deck_beatgrid reads a tempo: its period comes from a parabola through three lags of columns (good to about 1e-3 of a beat, which over the 1 200
+ * beats of a ten-minute track is more than a beat) and its phase is good to a column.  This section turns that read-out into a grid: around a coarse period it tries
+ * up to 8192 candidate periods, each at every integer phase, and scores each by the onset weight a comb of that period and phase collects over the track.  A fourth
+ * analysis on the deck's own load stream, with the ownership rules of the other three and independent of their results; integers throughout, so the records are fixed
+ * count for count.  A deck that never calls it is untouched in every respect, and mx_deck_analyse / mx_deck_beatgrid / mx_deck_grid are what they were.
+ *
+ * SETTINGS   mx_deck_finegrid: hop h a power of two, 16 .. 256 frames; n_periods 1 .. 8192; candidate j has the period P_j = period0_q16 + j * dperiod_q16 in fine hops,
+ *            Q16, and every P_j lies in [4 * 65536, 32768 * 65536]; dperiod_q16 >= 1 unless n_periods is 1; first_hop < N; max_beats 0 (all teeth) or >= 2; _pad 0.
+ *            mx_deck_finegrid_check enforces exactly these rules for a track of n_frames (1 .. 2^30).
+ * ONSETS     N = ceil(n_frames / h).  s[f] = L[f] + R[f] of the raw int16 track (ANALYSIS' and key-lock's s).  e[i] = the sum of s[f]^2 over the frames f of
+ *            [i h, (i + 1) h) with f < n_frames (at most 2^40); A[i] = floor(sqrt(e[i])), the exact integer root, A[-1] = 0; o[i] = max(A[i] - A[i - 1], 0) >> 4
+ *            (subtract, clamp, then shift; at most 2^16).  The tooth weight is w[i] = o[i - 1] + 2 o[i] + o[i + 1] with o read as 0 outside [0, N) (at most 2^18):
+ *            a tooth three hops wide and centre-weighted, so that a comb with an integer phase and a fractional period can sit on every beat of a track whose beats
+ *            do not fall on hops.
+ * COMB       for candidate j and each integer phase phi, 0 <= phi < ceil(P_j) = (P_j + 65535) >> 16:
+ *                S(j, phi) = sum over k = 0, 1, ... of w[i_k],    i_k = first_hop + phi + ((k * P_j) >> 16)
+ *            the sum stopping at the first k with i_k >= N, or at k = max_beats when that is not 0.  64-bit integers: k * P_j < 2^57, S < 2^44.  The record of
+ *            candidate j, mx_deck_comb (16 bytes): score the largest S, phase the smallest phi that reaches it, beats the number of teeth that phase summed (0 when
+ *            its first tooth already lies beyond the track).
+ * PICK       mx_deck_finegrid_pick, host only and pure: the largest score, then the smallest j.  mx_deck_beats in track frames, Q32.32:
+ *            period_q32 = (P_j * h) << 16, first_q32 = ((first_hop + phase) * h + h / 2) << 32 -- the centre of tooth 0; beat n lies at first_q32 + n * period_q32.
+ *            mx_deck_fine_pick adds index j, score, n_beats = beats and bpm = (60.0 * rate * 65536.0) / ((double)P_j * (double)h), every f64 operation separate and left
+ *            to right.  With every score 0 the result is all zero.
+ * SPAN       mx_deck_finegrid_span, host only and pure, fills the settings of one stage of a search from a centre period c and a half-width (both Q16 hops), a beat
+ *            limit B (0: the whole track), N and h.  K = ceil(N * 65536 / c), the teeth of phase 0 that fit, or B if B is not 0 and smaller; dperiod = max(1,
+ *            floor(32768 / K)), so neighbouring candidates move the last tooth by at most half a hop; m = min(ceil(half-width / dperiod), 4095), further cut on either
+ *            side to what stays within [4 * 65536, 32768 * 65536]; n_periods = m_below + m_above + 1 with c itself a candidate; first_hop 0, max_beats B.
+ *            *clipped says whether any cut was made.  Two stages reach the whole track's precision: stage one from the coarse period c with a half-width of
+ *            ceil(c / 50) (+-2 %) and B = 64, stage two from stage one's winner with a half-width of 4 x stage one's dperiod and B = 0.  (Four, not one: a tooth
+ *            reaches 1.5 hops to either side of its centre and the beat itself is quantised to a hop, so every candidate whose LAST tooth of stage one lies within 2
+ *            hops of the true one can collect the same onsets and win; neighbours move that tooth by at most half a hop, which makes 4 steps.)
+ *            mx_deck_finegrid_period converts mx_deck_grid.period_columns: the integer nearest to period_columns * C / h * 65536 (C / h a power of two: one
+ *            rounding, ties to even).
+ * SYNC       mx_deck_sync, host only, pure, exact (128-bit integers, as mx_deck_step): from the leader's beats, position and step and the follower's beats and
+ *            position, all as of the start of the same tick, the follower's step and the position it must stand at so that its beats fall on the leader's.  With Pl,
+ *            Pf the two periods, every division rounded to nearest, ties to even:
+ *                step  = sign(leader_step) * round(|leader_step| * Pf / Pl)                              (|step| > 4 * 2^32: MX_ERR_INVALID)
+ *                a     = floor_mod(leader_pos - first_l, Pl),   b = round(a * Pf / Pl),   c = floor_mod(follower_pos - first_f, Pf)
+ *                delta = b - c, then Pf added or subtracted until it lies in (-Pf / 2, Pf / 2],   seek = follower_pos + delta
+ *            The host hands step and seek to mx_deck_schedule for that tick.  A period outside [1, 2^56], a position or first beat beyond 2^62 in magnitude: MX_ERR_INVALID.
+ * Out of scope: a key-locked leader or follower (under KEY-LOCK the head still crosses the track as mx_deck_plan says, so the arithmetic holds for the head; what the
+ * grains make audible of it is KEY-LOCK's business, and nothing here refuses such a deck); tempo that changes within a track; downbeats and bars; phases finer than a
+ * hop; a search over a range of the track other than "from first_hop on". */
+#define MX_DECK_FINEGRID_LANES 256u       /* phases one pass of a comb workgroup covers (a lane per phase); tests size their candidates around it */
+#define MX_DECK_FINEGRID_MAX_PERIODS 8192u
+typedef struct { uint32_t hop; uint32_t n_periods; uint64_t period0_q16; uint32_t dperiod_q16; uint32_t first_hop; uint32_t max_beats; uint32_t _pad; } mx_deck_finegrid;   /* 32 bytes */
+typedef struct { uint64_t score; uint32_t phase; uint32_t beats; } mx_deck_comb;   /* 16 bytes */
+typedef struct { int64_t first_q32; int64_t period_q32; } mx_deck_beats;
+typedef struct { mx_deck_beats grid; uint64_t score; double bpm; uint32_t index; uint32_t n_beats; } mx_deck_fine_pick;   /* 40 bytes */
+typedef struct { int64_t step_q32; int64_t seek_q32; int64_t delta_q32; } mx_deck_sync_result;
+/* Host only: the SETTINGS rules alone for a track of n_frames; MX_ERR_INVALID names the rule in mx_last_error. */
+int mx_deck_finegrid_check(const mx_deck_finegrid* s, uint64_t n_frames);
+/* Host only: *n_hops = N = ceil(n_frames / hop).  n_frames outside 1 .. 2^30 or a hop the check refuses: MX_ERR_INVALID. */
+int mx_deck_finegrid_count(uint64_t n_frames, uint32_t hop, uint64_t* n_hops);
+/* Host only, pure: SPAN.  centre_q16 outside [4 * 65536, 32768 * 65536], n_hops outside 1 .. 2^26, a hop the check refuses, beat_limit 1, NULL (clipped may be NULL):
+ * MX_ERR_INVALID, *s untouched. */
+int mx_deck_finegrid_span(uint64_t centre_q16, uint64_t halfwidth_q16, uint32_t beat_limit, uint64_t n_hops, uint32_t hop, mx_deck_finegrid* s, uint32_t* clipped);
+/* Host only: SPAN's conversion of a coarse period.  A value that is not finite, column outside ANALYSIS' rule, a hop the check refuses, a result outside
+ * [4 * 65536, 32768 * 65536]: MX_ERR_INVALID. */
+int mx_deck_finegrid_period(double period_columns, uint32_t column, uint32_t hop, uint64_t* period_q16);
+/* Score every candidate over the whole track as loaded now.  Asynchronous on the deck's own load stream, like mx_deck_analyse: ordered after earlier loads and before
+ * later ones, not ordered against feeds.  Device memory the deck owns: 8192 * 16 + N * 4 bytes (room for any n_periods, so a second stage at the same hop never grows
+ * the buffer); a later call replaces the result (a buffer that must grow, for a smaller hop, waits for the stream first), NULL frees it; the result is a snapshot that a later load does not invalidate, and each call computes w afresh.  Settings the check refuses:
+ * MX_ERR_INVALID, and the deck keeps what it had.  Memory that cannot be had: MX_ERR_NOMEM, and the deck is left without a fine grid. */
+int mx_deck_analyse_finegrid(mx_deck* d, const mx_deck_finegrid* s);
+/* Records [first, first + n) of the deck's fine grid; waits for it, like mx_deck_read_columns.  No fine grid, a window beyond n_periods, NULL: MX_ERR_INVALID. */
+int mx_deck_read_finegrid(mx_deck* d, uint64_t first, uint64_t n, mx_deck_comb* dst);
+/* w[first .. first + n) of the deck's fine grid; waits for it.  No fine grid, a window beyond N, NULL: MX_ERR_INVALID. */
+int mx_deck_read_fine_onsets(mx_deck* d, uint64_t first, uint64_t n, uint32_t* w);
+/* Host only, pure: ONSETS and COMB in plain C++ over a track of n_frames interleaved stereo frames: n_periods records into recs, and w[0 .. N) into w_or_null when it is
+ * not NULL -- how the rules are tested without a device, and the single-thread baseline of the device path.  Settings the check refuses, NULL: MX_ERR_INVALID. */
+int mx_deck_finegrid_host(const int16_t* interleaved, uint64_t n_frames, const mx_deck_finegrid* s, mx_deck_comb* recs, uint32_t* w_or_null);
+/* Host only, pure: PICK from the n_periods records of settings s.  s outside the SETTINGS rules (first_hop is not held against a track), rate not finite and positive,
+ * NULL: MX_ERR_INVALID. */
+int mx_deck_finegrid_pick(const mx_deck_comb* recs, const mx_deck_finegrid* s, double rate, mx_deck_fine_pick* out);
+/* Host only, pure, exact: SYNC. */
+int mx_deck_sync(const mx_deck_beats* leader, int64_t leader_pos_q32, int64_t leader_step_q32, const mx_deck_beats* follower, int64_t follower_pos_q32,
+                 mx_deck_sync_result* out);
+/* DEBUG: what the last mx_deck_analyse_finegrid of this process launched: out[0] comb workgroups (one per candidate, MX_DECK_FINEGRID_LANES lanes) whose phases fit one
+ * pass of the lanes, out[1] comb workgroups that looped over the phases in strides, out[2] onset workgroups (256 lanes; 256 hops of w each), out[3] the trip count of
+ * the comb kernel's loop over k (the teeth of phase 0 at the smallest period, or max_beats).  Tests use it to know every form ran. */
+int mx_deck_debug_last_finegrid(uint32_t out[4]);
 
 /* ---------------------------------------------------------------------------------------------- */
 /* pixel path: device-resident yuv420p frames, VideoMixer, scaler, colour                          */

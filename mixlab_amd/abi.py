@@ -447,6 +447,32 @@ _proto("mx_deck_debug_last_loudness", C.c_int, C.POINTER(C.c_uint32))
 _proto("mx_deck_loudness_gain", C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double),
        C.POINTER(C.c_double))
 _proto("mx_tonality_camelot", C.c_int, C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32))
+# ... its fine beat grid and sync (the header's FINE GRID): a comb search over candidate periods and phases, and the arithmetic that aligns two decks
+DECK_FINEGRID_LANES = 256          # MX_DECK_FINEGRID_LANES: phases one pass of a comb workgroup covers
+DECK_FINEGRID_MAX_PERIODS = 8192   # MX_DECK_FINEGRID_MAX_PERIODS
+class DeckFinegrid(C.Structure):
+    _fields_ = [("hop", C.c_uint32), ("n_periods", C.c_uint32), ("period0_q16", C.c_uint64), ("dperiod_q16", C.c_uint32), ("first_hop", C.c_uint32),
+                ("max_beats", C.c_uint32), ("_pad", C.c_uint32)]
+class DeckComb(C.Structure):
+    _fields_ = [("score", C.c_uint64), ("phase", C.c_uint32), ("beats", C.c_uint32)]
+class DeckBeats(C.Structure):
+    _fields_ = [("first_q32", C.c_int64), ("period_q32", C.c_int64)]
+class DeckFinePick(C.Structure):
+    _fields_ = [("grid", DeckBeats), ("score", C.c_uint64), ("bpm", C.c_double), ("index", C.c_uint32), ("n_beats", C.c_uint32)]
+class DeckSyncResult(C.Structure):
+    _fields_ = [("step_q32", C.c_int64), ("seek_q32", C.c_int64), ("delta_q32", C.c_int64)]
+DECK_COMB_DTYPE = np.dtype([("score", "<u8"), ("phase", "<u4"), ("beats", "<u4")])   # mx_deck_comb as a numpy record: 16 bytes
+_proto("mx_deck_finegrid_check", C.c_int, C.POINTER(DeckFinegrid), C.c_uint64)
+_proto("mx_deck_finegrid_count", C.c_int, C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64))
+_proto("mx_deck_finegrid_span", C.c_int, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(DeckFinegrid), C.POINTER(C.c_uint32))
+_proto("mx_deck_finegrid_period", C.c_int, C.c_double, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64))
+_proto("mx_deck_analyse_finegrid", C.c_int, C.c_void_p, C.POINTER(DeckFinegrid))
+_proto("mx_deck_read_finegrid", C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p)
+_proto("mx_deck_read_fine_onsets", C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p)
+_proto("mx_deck_finegrid_host", C.c_int, C.c_void_p, C.c_uint64, C.POINTER(DeckFinegrid), C.c_void_p, C.c_void_p)
+_proto("mx_deck_finegrid_pick", C.c_int, C.c_void_p, C.POINTER(DeckFinegrid), C.c_double, C.POINTER(DeckFinePick))
+_proto("mx_deck_sync", C.c_int, C.POINTER(DeckBeats), C.c_int64, C.c_int64, C.POINTER(DeckBeats), C.c_int64, C.POINTER(DeckSyncResult))
+_proto("mx_deck_debug_last_finegrid", C.c_int, C.POINTER(C.c_uint32))
 _proto("mx_module_create", C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p))
 _proto("mx_module_create_ex", C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(GraphOpts), C.POINTER(C.c_void_p))
 _proto("mx_module_update", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)

@@ -180,5 +180,39 @@ int mx_tonality_camelot(int key, uint32_t* number, uint32_t* minor) {
         *number = (uint32_t)((7 * t + (m ? 4 : 7)) % 12) + 1u; *minor = (uint32_t)m;
     });
 }
+int mx_deck_finegrid_check(const mx_deck_finegrid* s, uint64_t n_frames) {
+    return guard([&] { REQUIRE(s, "settings are NULL"); mx::deck_finegrid_check(*s, n_frames, true); });
+}
+int mx_deck_finegrid_count(uint64_t n_frames, uint32_t hop, uint64_t* n_hops) {
+    return guard([&] { REQUIRE(n_hops, "n_hops is NULL"); *n_hops = mx::deck_finegrid_count(n_frames, hop); });
+}
+int mx_deck_finegrid_span(uint64_t centre_q16, uint64_t halfwidth_q16, uint32_t beat_limit, uint64_t n_hops, uint32_t hop, mx_deck_finegrid* s, uint32_t* clipped) {
+    return guard([&] { REQUIRE(s, "settings are NULL"); mx::deck_finegrid_span(centre_q16, halfwidth_q16, beat_limit, n_hops, hop, *s, clipped); });
+}
+int mx_deck_finegrid_period(double period_columns, uint32_t column, uint32_t hop, uint64_t* period_q16) {
+    return guard([&] { REQUIRE(period_q16, "period_q16 is NULL"); *period_q16 = mx::deck_finegrid_period(period_columns, column, hop); });
+}
+int mx_deck_analyse_finegrid(mx_deck* d, const mx_deck_finegrid* s) {
+    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.analyse_finegrid(s); });
+}
+int mx_deck_read_finegrid(mx_deck* d, uint64_t first, uint64_t n, mx_deck_comb* dst) {
+    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.read_finegrid(first, n, dst); });
+}
+int mx_deck_read_fine_onsets(mx_deck* d, uint64_t first, uint64_t n, uint32_t* w) {
+    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.read_fine_onsets(first, n, w); });
+}
+int mx_deck_finegrid_host(const int16_t* interleaved, uint64_t n_frames, const mx_deck_finegrid* s, mx_deck_comb* recs, uint32_t* w_or_null) {
+    return guard([&] { REQUIRE(s, "settings are NULL"); mx::deck_finegrid_host(interleaved, n_frames, *s, recs, w_or_null); });
+}
+int mx_deck_finegrid_pick(const mx_deck_comb* recs, const mx_deck_finegrid* s, double rate, mx_deck_fine_pick* out) {
+    return guard([&] { REQUIRE(s && out, "NULL argument"); mx::deck_finegrid_pick(recs, *s, rate, *out); });
+}
+int mx_deck_sync(const mx_deck_beats* leader, int64_t leader_pos_q32, int64_t leader_step_q32, const mx_deck_beats* follower, int64_t follower_pos_q32,
+                 mx_deck_sync_result* out) {
+    return guard([&] { REQUIRE(leader && follower && out, "NULL argument"); mx::deck_sync(*leader, leader_pos_q32, leader_step_q32, *follower, follower_pos_q32, *out); });
+}
+int mx_deck_debug_last_finegrid(uint32_t out[4]) {
+    return guard([&] { REQUIRE(out, "out is NULL"); Deck::debug_last_finegrid(out); });
+}
 
 }  // extern "C"

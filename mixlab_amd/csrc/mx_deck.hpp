@@ -73,6 +73,14 @@ void deck_tonality_host(const int16_t* interleaved, uint64_t n_frames, const mx_
 void deck_loudness_check(const mx_deck_loudness& l);                                 // throws Error(MX_ERR_INVALID) naming the rule
 uint64_t deck_loudness_count(uint64_t n_frames, uint32_t block_frames);
 void deck_loudness_host(const int16_t* interleaved, uint64_t n_frames, const mx_deck_loudness& l, mx_loudness_tick* dst, uint64_t cap);
+// the fine beat grid and sync (the header's FINE GRID; mx_deck_finegrid.cpp, mx_k_deck_finegrid.hip)
+void deck_finegrid_check(const mx_deck_finegrid& s, uint64_t n_frames, bool with_track);   // throws Error(MX_ERR_INVALID) naming the rule; without a track: every rule but first_hop < N
+uint64_t deck_finegrid_count(uint64_t n_frames, uint32_t hop);
+void deck_finegrid_span(uint64_t centre_q16, uint64_t halfwidth_q16, uint32_t beat_limit, uint64_t n_hops, uint32_t hop, mx_deck_finegrid& out, uint32_t* clipped_or_null);
+uint64_t deck_finegrid_period(double period_columns, uint32_t column, uint32_t hop);
+void deck_finegrid_host(const int16_t* interleaved, uint64_t n_frames, const mx_deck_finegrid& s, mx_deck_comb* recs, uint32_t* w_or_null);
+void deck_finegrid_pick(const mx_deck_comb* recs, const mx_deck_finegrid& s, double rate, mx_deck_fine_pick& out);
+void deck_sync(const mx_deck_beats& leader, int64_t leader_pos, int64_t leader_step, const mx_deck_beats& follower, int64_t follower_pos, mx_deck_sync_result& out);
 void deck_check(const mx_deck_params& p, uint64_t n_frames);                         // throws Error(MX_ERR_INVALID) naming the rule
 void deck_plan(const mx_deck_head& in, const mx_deck_params* params, const int64_t* seek, uint32_t spt, uint64_t n_frames, mx_deck_tick& tick, mx_deck_head& out);
 int64_t deck_step(uint32_t track_rate, uint32_t graph_rate, double speed);
@@ -106,6 +114,10 @@ public:
     void analyse_loudness(const mx_deck_loudness* l);                      // NULL: frees the results.  Asynchronous on the load stream.
     void read_loudness(uint64_t first, uint64_t n, mx_loudness_tick* dst);  // waits for the analysis
     static void debug_last_loudness(uint32_t out[4]);
+    void analyse_finegrid(const mx_deck_finegrid* s);                      // NULL: frees the results.  Asynchronous on the load stream.
+    void read_finegrid(uint64_t first, uint64_t n, mx_deck_comb* dst);     // waits for the analysis
+    void read_fine_onsets(uint64_t first, uint64_t n, uint32_t* w);        // waits for the analysis
+    static void debug_last_finegrid(uint32_t out[4]);
 
 private:
     void fetch_grains();
@@ -134,6 +146,9 @@ private:
     uint64_t ton_segs_ = 0; size_t ton_rec_bytes_ = 0; mx_deck_tonality ton_tab_for_{}; int16_t ton_fir_[64] = {};
     DevBuf loud_;
     uint64_t loud_blocks_ = 0;
+    // fine grid: one buffer -- room for 8192 comb records, then w (fg_hops_ x 4 bytes) -- written on load_stream_ only; fg_periods_ = 0: none
+    DevBuf fg_;
+    uint32_t fg_periods_ = 0; uint64_t fg_hops_ = 0;
 };
 
 }  // namespace mx

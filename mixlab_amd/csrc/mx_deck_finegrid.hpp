@@ -1,0 +1,48 @@
+// mx_deck_finegrid.hpp -- the deck's fine beat grid (include/mixlab_gpu.h "FINE GRID"): the rules that the host function
+// (mx_deck_finegrid.cpp) and the kernels (mx_k_deck_finegrid.hip) both evaluate, stated once, and the launch (internal).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "mx_common.hpp"
+#include "mx_dev.hpp"
+
+namespace mx {
+
+enum { FG_LANES = MX_DECK_FINEGRID_LANES, FG_TILE = 256, FG_HALO_BEFORE = 2, FG_HALO_AFTER = 1 };
+static const uint64_t FG_PERIOD_MIN = (uint64_t)4 << 16, FG_PERIOD_MAX = (uint64_t)32768 << 16;
+
+// s^2 of one track frame as the deck stores it (L in the low half); at most 2^32
+__host__ __device__ inline uint64_t fg_square(uint32_t frame) {
+    const int32_t s = (int32_t)(int16_t)(frame & 0xffffu) + (int32_t)(int16_t)(frame >> 16);
+    const uint32_t m = (uint32_t)(s < 0 ? -s : s);
+    return (uint64_t)m * m;
+}
+// o[i] from A[i] and A[i - 1]: subtract, clamp, then shift
+__host__ __device__ inline uint32_t fg_onset(uint32_t a, uint32_t before) { return (a > before ? a - before : 0u) >> 4; }
+// the tooth weight from three onsets
+__host__ __device__ inline uint32_t fg_tooth(uint32_t o_before, uint32_t o, uint32_t o_after) { return o_before + 2u * o + o_after; }
+// ceil(P): the phases of a candidate
+__host__ __device__ inline uint32_t fg_phases(uint64_t P) { return (uint32_t)((P + 65535u) >> 16); }
+// one (candidate, phase) against another under the tie rule: the larger score, then the smaller phase
+__host__ __device__ inline bool fg_better(uint64_t s, uint32_t phi, uint64_t s0, uint32_t phi0) { return s > s0 || (s == s0 && phi < phi0); }
+// the teeth of phase 0 that fit N hops from first_hop on at period P, cut at max_beats: the trip count of the loop over k (first_hop < N)
+inline uint64_t fg_trip(uint64_t N, uint32_t first_hop, uint64_t P, uint32_t max_beats) {
+    const uint64_t fit = (((N - first_hop) << 16) + P - 1u) / P;   // the k with (k P) >> 16 < N - first_hop, i.e. k P < (N - first_hop) 2^16
+    return max_beats && max_beats < fit ? max_beats : fit;
+}
+
+struct DkFineArgs {
+    const uint32_t* track; int64_t n_frames;
+    uint32_t log_hop, N;          // N <= 2^26
+    uint32_t n_periods, first_hop;
+    uint64_t period0, dperiod;
+    uint32_t trip;                // fg_trip at period0, the smallest period (at most 2^24)
+    uint32_t* w;                  // [N]
+    mx_deck_comb* rec;            // [n_periods]
+};
+enum { DK_FINE_FORM_ONE_PASS = 0, DK_FINE_FORM_STRIDED = 1, DK_FINE_FORM_ONSET = 2, DK_FINE_FORM_TRIP = 3 };
+void launch_deck_finegrid(const DkFineArgs& a, uint32_t forms[4], hipStream_t s);
+
+}  // namespace mx

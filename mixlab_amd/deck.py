@@ -13,6 +13,12 @@ Analysis (the header's ANALYSIS) looks at the whole track before it sounds -- ov
     deck.analyse(rate=44100.0)                                            # 200 Hz / 2.5 kHz, 63 taps, columns of 512 frames, 256 lags
     cols, R = deck.read_columns(), deck.read_autocorr()
     grid = beatgrid(cols, R, 512, 44100.0, 60.0, 200.0)                   # grid.bpm, grid.first_beat_frame, grid.period_columns
+
+The fine grid (the header's FINE GRID) turns that read-out into beats good to a hop of 64 frames over the whole track, and two grids into a sync:
+
+    beats = deck.refine_grid(grid, 512, 44100.0).grid                     # first_q32, period_q32: beat n lies at first + n * period
+    step, seek, _ = deck_sync(leader_beats, leader.state().pos_q32, leader.state().step_q32, beats, deck.state().pos_q32)
+    deck.schedule(0, params(step_q32=step, flags=abi.DECK_PLAY), seek)    # the follower's beats now fall on the leader's, and stay there
 """
 from __future__ import annotations
 
@@ -21,7 +27,8 @@ import ctypes as C
 import numpy as np
 
 from . import abi
-from .abi import DeckAnalysis, DeckGrain, DeckGrid, DeckHead, DeckKeylock, DeckLoudness, DeckParams, DeckTick, DeckTonality, check, lib
+from .abi import (DeckAnalysis, DeckBeats, DeckFinegrid, DeckFinePick, DeckGrain, DeckGrid, DeckHead, DeckKeylock, DeckLoudness, DeckParams, DeckSyncResult, DeckTick,
+                  DeckTonality, check, lib)
 
 ONE = 1 << 32   # unity step / one track frame in Q32.32
 
@@ -233,12 +240,79 @@ def camelot(key: int) -> str:
     return f"{number.value}{'A' if minor.value else 'B'}"
 
 
+def finegrid(hop=64, n_periods=1, period0_q16=4 << 16, dperiod_q16=0, first_hop=0, max_beats=0) -> DeckFinegrid:
+    """fine-grid settings (the header's FINE GRID): candidate j has the period period0_q16 + j * dperiod_q16 in hops of `hop` frames, Q16"""
+    return DeckFinegrid(int(hop), int(n_periods), int(period0_q16), int(dperiod_q16), int(first_hop), int(max_beats), 0)
+
+
+def finegrid_check(s: DeckFinegrid, n_frames: int) -> None:
+    """the fine-grid setting rules alone for a track of n_frames (host only); raises MxError"""
+    check(lib.mx_deck_finegrid_check(C.byref(s), int(n_frames)))
+
+
+def finegrid_count(n_frames: int, hop: int) -> int:
+    n = C.c_uint64()
+    check(lib.mx_deck_finegrid_count(int(n_frames), int(hop), C.byref(n)))
+    return n.value
+
+
+def finegrid_span(centre_q16: int, halfwidth_q16: int, beat_limit: int, n_hops: int, hop: int):
+    """the settings of one stage of a search round a centre period (mx_deck_finegrid_span, host only, pure): (DeckFinegrid, clipped)"""
+    s, clipped = DeckFinegrid(), C.c_uint32()
+    check(lib.mx_deck_finegrid_span(int(centre_q16), int(halfwidth_q16), int(beat_limit), int(n_hops), int(hop), C.byref(s), C.byref(clipped)))
+    return s, bool(clipped.value)
+
+
+def finegrid_period(period_columns: float, column: int, hop: int) -> int:
+    """a coarse DeckGrid.period_columns in fine hops, Q16 (mx_deck_finegrid_period, host only)"""
+    p = C.c_uint64()
+    check(lib.mx_deck_finegrid_period(float(period_columns), int(column), int(hop), C.byref(p)))
+    return p.value
+
+
+def finegrid_host(interleaved_i16: np.ndarray, s: DeckFinegrid, onsets: bool = False):
+    """the fine-grid rules in plain C++ on the host (pure): abi.DECK_COMB_DTYPE[n_periods]; with onsets also w as uint32[N]"""
+    x = np.ascontiguousarray(interleaved_i16, dtype=np.int16).reshape(-1)
+    finegrid_check(s, x.size // 2)   # before a buffer is sized from the settings
+    recs = np.zeros(s.n_periods, abi.DECK_COMB_DTYPE)
+    w = np.zeros(finegrid_count(x.size // 2, s.hop), np.uint32) if onsets else None
+    check(lib.mx_deck_finegrid_host(x.ctypes.data_as(C.c_void_p), x.size // 2, C.byref(s), recs.ctypes.data_as(C.c_void_p), w.ctypes.data_as(C.c_void_p) if onsets else None))
+    return (recs, w) if onsets else recs
+
+
+def finegrid_pick(recs: np.ndarray, s: DeckFinegrid, rate: float) -> DeckFinePick:
+    """the best candidate of one stage as beats in track frames, Q32.32 (mx_deck_finegrid_pick, host only, pure): .grid, .index, .score, .n_beats, .bpm"""
+    r = np.ascontiguousarray(recs, dtype=abi.DECK_COMB_DTYPE)
+    if r.size != s.n_periods:
+        raise ValueError("one record per candidate period")
+    out = DeckFinePick()
+    check(lib.mx_deck_finegrid_pick(r.ctypes.data_as(C.c_void_p), C.byref(s), float(rate), C.byref(out)))
+    return out
+
+
+def deck_sync(leader: DeckBeats, leader_pos_q32: int, leader_step_q32: int, follower: DeckBeats, follower_pos_q32: int):
+    """(step, seek, delta) that put the follower's beats on the leader's, all Q32.32 and exact (mx_deck_sync, host only, pure); hand step and seek to Deck.schedule"""
+    out = DeckSyncResult()
+    check(lib.mx_deck_sync(C.byref(leader), int(leader_pos_q32), int(leader_step_q32), C.byref(follower), int(follower_pos_q32), C.byref(out)))
+    return out.step_q32, out.seek_q32, out.delta_q32
+
+
+def debug_last_finegrid() -> dict:
+    out = (C.c_uint32 * 4)()
+    check(lib.mx_deck_debug_last_finegrid(out))
+    return dict(zip(("wgs_one_pass", "wgs_strided", "wgs_onset", "trip"), (int(v) for v in out)))
+
+
+_NOT_GIVEN = object()   # Deck.analyse_finegrid: no settings argument at all, as against None
+
+
 class Deck:
     """Thin RAII wrapper of mx_deck_*."""
 
     def __init__(self, n_frames: int, device: int = -1):
         self._h = C.c_void_p()
         self.n_frames = int(n_frames)
+        self._finegrid = None   # (n_periods, N) of the last analyse_finegrid() that succeeded: the library has no call that tells them
         check(lib.mx_deck_create(self.n_frames, device, C.byref(self._h)))
 
     def close(self):
@@ -357,6 +431,53 @@ class Deck:
         out = np.zeros(max(1, n), abi.LOUDNESS_TICK_DTYPE)
         check(lib.mx_deck_read_loudness(self._h, int(first), int(n), out.ctypes.data_as(C.c_void_p)))
         return out[:n]
+
+    def analyse_finegrid(self, s: DeckFinegrid | None = _NOT_GIVEN, **kw):
+        """score every candidate period of the settings over the whole track, asynchronously on the deck's own stream; keywords are finegrid()'s;
+        analyse_finegrid(None) frees the result.  There are no default settings (a search needs a period to search round): a call with neither
+        settings nor keywords, or with both, is a TypeError"""
+        if (s is _NOT_GIVEN) == (not kw):
+            raise TypeError("analyse_finegrid takes settings (None frees the result) or finegrid()'s keywords, one of the two")
+        if s is _NOT_GIVEN:
+            s = finegrid(**kw)
+        try:
+            check(lib.mx_deck_analyse_finegrid(self._h, C.byref(s) if s is not None else None))
+        except abi.MxError as e:
+            if e.code != abi.MX_ERR_INVALID:
+                self._finegrid = None
+            raise
+        self._finegrid = (s.n_periods, finegrid_count(self.n_frames, s.hop)) if s is not None else None
+
+    def read_finegrid(self, first: int = 0, n: int | None = None) -> np.ndarray:
+        """abi.DECK_COMB_DTYPE[n] of the fine grid, one record per candidate period; waits for it"""
+        n = ((self._finegrid or (0, 0))[0] - first) if n is None else n
+        out = np.zeros(max(1, n), abi.DECK_COMB_DTYPE)
+        check(lib.mx_deck_read_finegrid(self._h, int(first), int(n), out.ctypes.data_as(C.c_void_p)))
+        return out[:n]
+
+    def read_fine_onsets(self, first: int = 0, n: int | None = None) -> np.ndarray:
+        """the tooth weights w as uint32[n] of the fine grid; waits for it"""
+        n = ((self._finegrid or (0, 0))[1] - first) if n is None else n
+        w = np.zeros(max(1, n), np.uint32)
+        check(lib.mx_deck_read_fine_onsets(self._h, int(first), int(n), w.ctypes.data_as(C.c_void_p)))
+        return w[:n]
+
+    def refine_grid(self, grid: DeckGrid, column: int, rate: float, hop: int = 64) -> DeckFinePick:
+        """the coarse grid of beatgrid() refined to a fine hop in the header's two stages: +-2 % round the coarse period over the first 64 beats, then
+        +- 4 x stage one's spacing round its winner over the whole track.  Waits for the device twice.  A grid without a period, or a stage that finds
+        nothing (a silent track), gives the all-zero pick."""
+        if not grid.period_columns > 0.0:
+            return DeckFinePick()
+        n_hops = finegrid_count(self.n_frames, hop)
+        centre = finegrid_period(grid.period_columns, column, hop)
+        one, _ = finegrid_span(centre, (centre + 49) // 50, 64, n_hops, hop)
+        self.analyse_finegrid(one)
+        first = finegrid_pick(self.read_finegrid(), one, rate)
+        if not first.score:
+            return first
+        two, _ = finegrid_span(one.period0_q16 + first.index * one.dperiod_q16, 4 * one.dperiod_q16, 0, n_hops, hop)
+        self.analyse_finegrid(two)
+        return finegrid_pick(self.read_finegrid(), two, rate)
 
     def state(self) -> DeckHead:
         h = DeckHead()
