@@ -94,16 +94,16 @@ int mx_deck_analysis_bands(double rate, double f_lo, double f_hi, uint32_t taps,
     return guard([&] { REQUIRE(a, "settings are NULL"); mx::deck_analysis_bands(rate, f_lo, f_hi, taps, *a); });
 }
 int mx_deck_analyse(mx_deck* d, const mx_deck_analysis* a) {
-    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.analyse(a); });
+    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.columns.analyse(a); });
 }
 int mx_deck_column_count(uint64_t n_frames, uint32_t column, uint64_t* n) {
     return guard([&] { REQUIRE(n, "n is NULL"); *n = mx::deck_column_count(n_frames, column); });
 }
 int mx_deck_read_columns(mx_deck* d, uint64_t first, uint64_t n, mx_deck_column* dst) {
-    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.read_columns(first, n, dst); });
+    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.columns.read_columns(first, n, dst); });
 }
 int mx_deck_read_autocorr(mx_deck* d, uint64_t* R, uint32_t cap) {
-    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.read_autocorr(R, cap); });
+    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.columns.read_autocorr(R, cap); });
 }
 int mx_deck_columns_host(const int16_t* interleaved, uint64_t n_frames, const mx_deck_analysis* a, uint64_t first, uint64_t n, mx_deck_column* cols, uint64_t* R_or_null) {
     return guard([&] { REQUIRE(a, "settings are NULL"); mx::deck_columns_host(interleaved, n_frames, *a, first, n, cols, R_or_null); });
@@ -113,7 +113,7 @@ int mx_deck_beatgrid(const mx_deck_column* cols, uint64_t n_cols, const uint64_t
     return guard([&] { REQUIRE(out, "out is NULL"); mx::deck_beatgrid(cols, n_cols, R, max_lag, column, rate, bpm_lo, bpm_hi, *out); });
 }
 int mx_deck_debug_last_analysis(uint32_t out[4]) {
-    return guard([&] { REQUIRE(out, "out is NULL"); Deck::debug_last_analysis(out); });
+    return guard([&] { REQUIRE(out, "out is NULL"); mx::DeckColumns::debug_last(out); });
 }
 int mx_deck_tonality_check(const mx_deck_tonality* t) {
     return guard([&] { REQUIRE(t, "settings are NULL"); mx::deck_tonality_check(*t); });
@@ -122,16 +122,16 @@ int mx_deck_tonality_count(uint64_t n_frames, const mx_deck_tonality* t, uint64_
     return guard([&] { REQUIRE(t && n_seg, "NULL argument"); *n_seg = mx::deck_tonality_count(n_frames, *t); });
 }
 int mx_deck_analyse_tonality(mx_deck* d, const mx_deck_tonality* t) {
-    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.analyse_tonality(t); });
+    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.tonality.analyse(t); });
 }
 int mx_deck_read_tonality(mx_deck* d, uint64_t first, uint64_t n, void* dst, size_t cap_bytes) {
-    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.read_tonality(first, n, dst, cap_bytes); });
+    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.tonality.read(first, n, dst, cap_bytes); });
 }
 int mx_deck_tonality_host(const int16_t* interleaved, uint64_t n_frames, const mx_deck_tonality* t, uint64_t first, uint64_t n, void* dst) {
     return guard([&] { REQUIRE(t, "settings are NULL"); mx::deck_tonality_host(interleaved, n_frames, *t, first, n, dst); });
 }
 int mx_deck_debug_last_tonality(uint32_t out[4]) {
-    return guard([&] { REQUIRE(out, "out is NULL"); Deck::debug_last_tonality(out); });
+    return guard([&] { REQUIRE(out, "out is NULL"); mx::DeckTonality::debug_last(out); });
 }
 int mx_deck_loudness_check(const mx_deck_loudness* l) {
     return guard([&] { REQUIRE(l, "settings are NULL"); mx::deck_loudness_check(*l); });
@@ -140,16 +140,16 @@ int mx_deck_loudness_count(uint64_t n_frames, uint32_t block_frames, uint64_t* n
     return guard([&] { REQUIRE(n_blocks, "n_blocks is NULL"); *n_blocks = mx::deck_loudness_count(n_frames, block_frames); });
 }
 int mx_deck_analyse_loudness(mx_deck* d, const mx_deck_loudness* l) {
-    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.analyse_loudness(l); });
+    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.loudness.analyse(l); });
 }
 int mx_deck_read_loudness(mx_deck* d, uint64_t first, uint64_t n, mx_loudness_tick* dst) {
-    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.read_loudness(first, n, dst); });
+    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.loudness.read(first, n, dst); });
 }
 int mx_deck_loudness_host(const int16_t* interleaved, uint64_t n_frames, const mx_deck_loudness* l, mx_loudness_tick* dst, uint64_t cap) {
     return guard([&] { REQUIRE(l, "settings are NULL"); mx::deck_loudness_host(interleaved, n_frames, *l, dst, cap); });
 }
 int mx_deck_debug_last_loudness(uint32_t out[4]) {
-    return guard([&] { REQUIRE(out, "out is NULL"); Deck::debug_last_loudness(out); });
+    return guard([&] { REQUIRE(out, "out is NULL"); mx::DeckLoudness::debug_last(out); });
 }
 int mx_deck_loudness_gain(const mx_loudness_tick* recs, uint64_t n, uint32_t momentary_blocks, uint32_t hop_blocks, double target_lufs, double ceiling_dbtp,
                           double* lufs, double* peak_dbtp, double* gain_db) {
@@ -193,13 +193,13 @@ int mx_deck_finegrid_period(double period_columns, uint32_t column, uint32_t hop
     return guard([&] { REQUIRE(period_q16, "period_q16 is NULL"); *period_q16 = mx::deck_finegrid_period(period_columns, column, hop); });
 }
 int mx_deck_analyse_finegrid(mx_deck* d, const mx_deck_finegrid* s) {
-    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.analyse_finegrid(s); });
+    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.finegrid.analyse(s); });
 }
 int mx_deck_read_finegrid(mx_deck* d, uint64_t first, uint64_t n, mx_deck_comb* dst) {
-    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.read_finegrid(first, n, dst); });
+    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.finegrid.read(first, n, dst); });
 }
 int mx_deck_read_fine_onsets(mx_deck* d, uint64_t first, uint64_t n, uint32_t* w) {
-    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.read_fine_onsets(first, n, w); });
+    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.finegrid.read_onsets(first, n, w); });
 }
 int mx_deck_finegrid_host(const int16_t* interleaved, uint64_t n_frames, const mx_deck_finegrid* s, mx_deck_comb* recs, uint32_t* w_or_null) {
     return guard([&] { REQUIRE(s, "settings are NULL"); mx::deck_finegrid_host(interleaved, n_frames, *s, recs, w_or_null); });
@@ -212,7 +212,7 @@ int mx_deck_sync(const mx_deck_beats* leader, int64_t leader_pos_q32, int64_t le
     return guard([&] { REQUIRE(leader && follower && out, "NULL argument"); mx::deck_sync(*leader, leader_pos_q32, leader_step_q32, *follower, follower_pos_q32, *out); });
 }
 int mx_deck_debug_last_finegrid(uint32_t out[4]) {
-    return guard([&] { REQUIRE(out, "out is NULL"); Deck::debug_last_finegrid(out); });
+    return guard([&] { REQUIRE(out, "out is NULL"); mx::DeckFineGrid::debug_last(out); });
 }
 
 }  // extern "C"

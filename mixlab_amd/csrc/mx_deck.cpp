@@ -1,5 +1,6 @@
 // mx_deck.cpp -- the deck's host side: parameter rules, the per-tick state machine (mx_deck_plan), the coefficient tables, the track, and the feed that turns the
-// coming ticks of many decks into one descriptor block and one launch (include/mixlab_gpu.h "the deck").
+// coming ticks of many decks into one descriptor block and one launch (include/mixlab_gpu.h "the deck").  Key-lock beside the feed is
+// mx_deck_keylock.cpp's, and each whole-track analysis has a file of its own (mx_deck_analysis.hpp).
 #include "mx_deck.hpp"
 
 #include <algorithm>
@@ -15,10 +16,9 @@
 namespace mx {
 
 static const int64_t kOne = (int64_t)1 << DECK_Q, kMaxStep = 4 * kOne, kMaxSlew = (int64_t)1 << 24, kMargin = (int64_t)1 << 20;
-static const uint64_t kMaxFrames = (uint64_t)1 << 30;
 
 void deck_check(const mx_deck_params& p, uint64_t n_frames) {
-    if (n_frames < 1 || n_frames > kMaxFrames) throw Error(MX_ERR_INVALID, "deck: n_frames outside 1 .. 2^30");
+    if (n_frames < 1 || n_frames > kDeckMaxFrames) throw Error(MX_ERR_INVALID, "deck: n_frames outside 1 .. 2^30");
     if (p.step_q32 > kMaxStep || p.step_q32 < -kMaxStep) throw Error(MX_ERR_INVALID, "deck: |step_q32| above 4 * 2^32");
     if (p.slew_q32 < 0 || p.slew_q32 > kMaxSlew) throw Error(MX_ERR_INVALID, "deck: slew_q32 outside 0 .. 2^24");
     if (p.flags & ~(MX_DECK_PLAY | MX_DECK_LOOP)) throw Error(MX_ERR_INVALID, "deck: a flag bit outside MX_DECK_PLAY | MX_DECK_LOOP");
@@ -32,7 +32,7 @@ static inline int64_t iabs64(int64_t v) { return v < 0 ? -v : v; }
 void deck_plan(const mx_deck_head& in, const mx_deck_params* params, const int64_t* seek, uint32_t spt, uint64_t n_frames, mx_deck_tick& tick, mx_deck_head& out) {
     if (spt < 1 || spt > MX_DECK_MAX_SPT) throw Error(MX_ERR_INVALID, "deck: frames per tick outside 1 .. MX_DECK_MAX_SPT");
     if (params) deck_check(*params, n_frames);
-    else if (n_frames < 1 || n_frames > kMaxFrames) throw Error(MX_ERR_INVALID, "deck: n_frames outside 1 .. 2^30");
+    else if (n_frames < 1 || n_frames > kDeckMaxFrames) throw Error(MX_ERR_INVALID, "deck: n_frames outside 1 .. 2^30");
     if (in.step_q32 > kMaxStep || in.step_q32 < -kMaxStep) throw Error(MX_ERR_INVALID, "deck: the head's |step_q32| is above 4 * 2^32");
     mx_deck_head h = in;
     if (seek) h.pos_q32 = *seek;                                                                   // 1.
@@ -143,7 +143,7 @@ static const float* deck_tables_device(int device) {
 
 // ---- the deck ----
 Deck::Deck(uint64_t n_frames, int device) : n_frames_(n_frames), device_(device) {
-    if (n_frames < 1 || n_frames > kMaxFrames) throw Error(MX_ERR_INVALID, "deck: n_frames outside 1 .. 2^30");
+    if (n_frames < 1 || n_frames > kDeckMaxFrames) throw Error(MX_ERR_INVALID, "deck: n_frames outside 1 .. 2^30");
     if (device_ < 0) hip_check(hipGetDevice(&device_), "hipGetDevice");
     hip_check(hipSetDevice(device_), "hipSetDevice");
     track_.alloc(n_frames * 4);
@@ -151,6 +151,7 @@ Deck::Deck(uint64_t n_frames, int device) : n_frames_(n_frames), device_(device)
     hip_check(hipEventCreateWithFlags(&loaded_, hipEventDisableTiming), "hipEventCreate");
     hip_check(hipMemsetAsync(track_.p, 0, n_frames * 4, load_stream_), "hipMemsetAsync(deck track)");
     hip_check(hipStreamSynchronize(load_stream_), "hipStreamSynchronize");
+    for_analyses_ = DeckTrack{(const uint32_t*)track_.p, n_frames_, device_, load_stream_};
 }
 
 Deck::~Deck() {
@@ -197,7 +198,7 @@ struct FeedState {
     std::mutex mu;
     Slot slots[kSlots]; int next = 0;
     std::vector<DeckTickDev> last; uint32_t last_spt = 0;   // the last feed's ticks, for mx_deck_debug_last_feed
-    struct KlTick { KlTickDev t; uint32_t log_hop, overlap; };
+    typedef DeckKlTick KlTick;
     std::vector<KlTick> last_kl; uint32_t kl_searched = 0, kl_unsearched = 0;   // ... and its key-locked ticks and grains, for mx_deck_debug_last_keylock
 } feed_state;
 }  // namespace
@@ -247,7 +248,7 @@ void Deck::feed(Deck* const* decks, const uint32_t* nodes, size_t n, Graph& g, u
         if (sl.pending) { hip_check(hipSetDevice(sl.device), "hipSetDevice"); hip_check(hipEventSynchronize(sl.done), "hipEventSynchronize"); sl.pending = false; hip_check(hipSetDevice(g.device()), "hipSetDevice"); }
         size_t nk = 0, grain_cap = 0;   // key-locked decks, and room for their grain starts: ceil(spt / hop) a tick at the most
         for (size_t i = 0; i < n; ++i)
-            if (decks[i]->kl_on_) { ++nk; grain_cap += (size_t)n_ticks * (spt / decks[i]->kl_.hop + 1); }
+            if (decks[i]->keylock_.on) { ++nk; grain_cap += (size_t)n_ticks * (spt / decks[i]->keylock_.k.hop + 1); }
         const size_t head_bytes = (n * sizeof(DeckDev) + 15) & ~(size_t)15, plain_bytes = (head_bytes + n * (size_t)n_ticks * sizeof(DeckTickDev) + 15) & ~(size_t)15;
         const size_t bytes = nk ? plain_bytes + nk * sizeof(KlDeckDev) + nk * (size_t)n_ticks * sizeof(KlTickDev) + grain_cap * sizeof(KlGrainIn)
                                 : head_bytes + n * (size_t)n_ticks * sizeof(DeckTickDev);
@@ -277,14 +278,14 @@ void Deck::feed(Deck* const* decks, const uint32_t* nodes, size_t n, Graph& g, u
         size_t ip = 0, ik = 0, grain_at = 0;
         for (size_t i = 0; i < n; ++i) {
             Deck& d = *decks[i];
-            const bool kl = d.kl_on_;
+            const bool kl = d.keylock_.on;
             if (!kl) dd[ip] = DeckDev{(const uint32_t*)d.track_.p, outs[i], (int64_t)d.n_frames_};
             mx_deck_head h = d.head_;
             recs[i].resize(n_ticks);
             std::vector<const Event*> at(d.sched_.empty() ? 0 : n_ticks, nullptr);
             for (const Event& e : d.sched_) at[e.tick] = &e;
-            uint64_t clock = kl && d.last_lineage_ == g.lineage() ? d.kl_t_ : 0;   // (another graph restarts the grain clock; one that adopted the last one's state is not another)
-            const uint32_t hop = d.kl_.hop;
+            uint64_t clock = kl && d.keylock_.last_lineage == g.lineage() ? d.keylock_.t : 0;   // (another graph restarts the grain clock; one that adopted the last one's state is not another)
+            const uint32_t hop = d.keylock_.k.hop;
             uint32_t next = 2;                                           // rec[] index of the next grain to start
             for (uint32_t t = 0; t < n_ticks; ++t) {
                 const Event* e = at.empty() ? nullptr : at[t];
@@ -300,7 +301,7 @@ void Deck::feed(Deck* const* decks, const uint32_t* nodes, size_t n, Graph& g, u
                 KlTickDev& k = kt[ik * (size_t)n_ticks + t];
                 if (!(r.flags & MX_DECK_TICK_PLAY)) { k = KlTickDev{0, 0, 0, 0}; clock = 0; continue; }   // (a tick that is not playing restarts the grain clock)
                 const uint32_t m0 = (uint32_t)(clock & (hop - 1));
-                k = KlTickDev{m0, m0 ? next - 1 : next, (clock >> d.kl_log_hop_) == 0 ? 1u : 0u, 1u};
+                k = KlTickDev{m0, m0 ? next - 1 : next, (clock >> d.keylock_.log_hop) == 0 ? 1u : 0u, 1u};
                 for (uint64_t fr = (hop - m0) & (hop - 1); fr < spt; fr += hop) {   // the grain starts of this tick
                     int64_t a = deck_u(r.pos_q32, r.step_q32, r.dstep_q32, (int64_t)fr);
                     if (r.flags & MX_DECK_TICK_LOOPING) a = deck_fold(a, r.loop_in * kOne, r.loop_len * kOne);
@@ -313,9 +314,9 @@ void Deck::feed(Deck* const* decks, const uint32_t* nodes, size_t n, Graph& g, u
             }
             heads[i] = h;
             if (kl) {
-                kd[ik] = KlDeckDev{(const uint32_t*)d.track_.p, outs[i], (int64_t)d.n_frames_, d.kl_.pitch_q32, nullptr, (int64_t*)d.kl_state_.p,
+                kd[ik] = KlDeckDev{(const uint32_t*)d.track_.p, outs[i], (int64_t)d.n_frames_, d.keylock_.k.pitch_q32, nullptr, (int64_t*)d.keylock_.state.p,
                                    (const KlGrainIn*)((const char*)sl.dev.p + ((const char*)(kg + grain_at) - (const char*)sl.host)),
-                                   (uint32_t)grains[ik].size(), d.kl_log_hop_, d.kl_.overlap, d.kl_.radius, d.kl_bank_, 0u};
+                                   (uint32_t)grains[ik].size(), d.keylock_.log_hop, d.keylock_.k.overlap, d.keylock_.k.radius, d.keylock_.bank, 0u};
                 clocks[ik] = clock;
                 grain_at += grains[ik].size();
                 ++ik;
@@ -325,14 +326,14 @@ void Deck::feed(Deck* const* decks, const uint32_t* nodes, size_t n, Graph& g, u
         // record buffers may still be in use on the other graph's stream.
         for (size_t i = 0, k = 0; i < n; ++i) {
             Deck& d = *decks[i];
-            if (!d.kl_on_) continue;
-            if (d.last_graph_ && d.last_graph_ != &g) hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+            if (!d.keylock_.on) continue;
+            if (d.keylock_.last_graph && d.keylock_.last_graph != &g) hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
             const size_t need = (2 + grains[k].size()) * sizeof(KlRec);
-            if (d.kl_rec_.bytes < need) {
+            if (d.keylock_.rec.bytes < need) {
                 d.fetch_grains();            // the last feed's records, before their buffer goes
-                d.kl_rec_.free_(); d.kl_rec_.alloc(2 * need);
+                d.keylock_.rec.free_(); d.keylock_.rec.alloc(2 * need);
             }
-            kd[k++].rec = (KlRec*)d.kl_rec_.p;
+            kd[k++].rec = (KlRec*)d.keylock_.rec.p;
         }
         for (size_t i = 0; i < n; ++i)
             if (decks[i]->load_pending_) { hip_check(hipStreamWaitEvent(g.stream(), decks[i]->loaded_, 0), "hipStreamWaitEvent"); decks[i]->load_pending_ = false; }
@@ -347,271 +348,19 @@ void Deck::feed(Deck* const* decks, const uint32_t* nodes, size_t n, Graph& g, u
         feed_state.last_kl.clear(); feed_state.kl_searched = feed_state.kl_unsearched = 0;
         for (size_t i = 0, k = 0; i < n; ++i) {
             Deck& d = *decks[i];
-            d.head_ = heads[i]; d.ticks_ = std::move(recs[i]); d.sched_.clear(); d.last_graph_ = &g; d.last_lineage_ = g.lineage();
-            if (!d.kl_on_) { d.grains_.clear(); d.grains_fetched_ = true; continue; }
-            for (const mx_deck_grain& gr : grains[k]) ++((gr.flags & MX_DECK_GRAIN_FIRST) || !d.kl_.radius ? feed_state.kl_unsearched : feed_state.kl_searched);
-            for (uint32_t t = 0; t < n_ticks; ++t) feed_state.last_kl.push_back(FeedState::KlTick{kt[k * (size_t)n_ticks + t], d.kl_log_hop_, d.kl_.overlap});
-            d.kl_t_ = clocks[k]; d.grains_ = std::move(grains[k]); d.grains_fetched_ = d.grains_.empty();
+            d.head_ = heads[i]; d.ticks_ = std::move(recs[i]); d.sched_.clear(); d.keylock_.last_graph = &g; d.keylock_.last_lineage = g.lineage();
+            if (!d.keylock_.on) { d.keylock_.grains.clear(); d.keylock_.grains_fetched = true; continue; }
+            for (const mx_deck_grain& gr : grains[k]) ++((gr.flags & MX_DECK_GRAIN_FIRST) || !d.keylock_.k.radius ? feed_state.kl_unsearched : feed_state.kl_searched);
+            for (uint32_t t = 0; t < n_ticks; ++t) feed_state.last_kl.push_back(FeedState::KlTick{kt[k * (size_t)n_ticks + t], d.keylock_.log_hop, d.keylock_.k.overlap});
+            d.keylock_.t = clocks[k]; d.keylock_.grains = std::move(grains[k]); d.keylock_.grains_fetched = d.keylock_.grains.empty();
             ++k;
         }
     } catch (...) { drop(); throw; }
 }
 
-// ---- key-lock ----
-void deck_keylock_check(const mx_deck_keylock& k) {
-    auto pow2 = [](uint32_t v) { return v && !(v & (v - 1)); };
-    if (k.pitch_q32 < kOne / 4 || k.pitch_q32 > kMaxStep) throw Error(MX_ERR_INVALID, "deck key-lock: pitch_q32 outside 2^30 .. 4 * 2^32");
-    if (!pow2(k.hop) || k.hop < 256 || k.hop > 8192) throw Error(MX_ERR_INVALID, "deck key-lock: hop is not a power of two in 256 .. 8192");
-    if (!pow2(k.overlap) || k.overlap < 16 || k.overlap > std::min<uint32_t>(k.hop / 2, 1024)) throw Error(MX_ERR_INVALID, "deck key-lock: overlap is not a power of two in 16 .. min(hop / 2, 1024)");
-    if (k.radius > 1024) throw Error(MX_ERR_INVALID, "deck key-lock: radius above 1024");
-    if (k._pad) throw Error(MX_ERR_INVALID, "deck key-lock: _pad must be 0");
-}
-
-void deck_keylock_search(const int16_t* x, uint64_t n_frames, int64_t C, int64_t A, uint32_t overlap, uint32_t radius, int32_t& delta, uint32_t& dist) {
-    const int64_t far = (int64_t)1 << 40;
-    if (!x) throw Error(MX_ERR_INVALID, "deck key-lock search: interleaved is NULL");
-    if (n_frames < 1 || n_frames > kMaxFrames) throw Error(MX_ERR_INVALID, "deck key-lock search: n_frames outside 1 .. 2^30");
-    if (overlap < 1 || overlap > 1024 || radius > 1024) throw Error(MX_ERR_INVALID, "deck key-lock search: overlap outside 1 .. 1024 or radius above 1024");
-    if (C < -far || C > far || A < -far || A > far) throw Error(MX_ERR_INVALID, "deck key-lock search: |C| or |A| above 2^40 frames");
-    auto s = [&](int64_t f) -> int32_t { return f < 0 || f >= (int64_t)n_frames ? 0 : (int32_t)x[2 * f] + (int32_t)x[2 * f + 1]; };
-    bool have = false;
-    // scanned in the tie order itself -- 0, -1, +1, -2, +2, ... -- so that a strictly smaller D is the only thing that replaces the best so far
-    for (int64_t q = 0; q <= (int64_t)radius; ++q)
-        for (int sgn = -1; sgn <= 1; sgn += 2) {
-            if (q == 0 && sgn > 0) continue;
-            const int64_t dl = sgn * q;
-            uint32_t D = 0;
-            for (uint32_t i = 0; i < overlap; ++i) { const int32_t v = s(C + i) - s(A + dl + i); D += (uint32_t)(v < 0 ? -v : v); }
-            if (!have || D < dist) { have = true; dist = D; delta = (int32_t)dl; }
-        }
-}
-
-void Deck::set_keylock(const mx_deck_keylock* k) {
-    if (k) {
-        deck_keylock_check(*k);
-        if (!kl_state_.p) { hip_check(hipSetDevice(device_), "hipSetDevice"); kl_state_.alloc(2 * sizeof(int64_t)); }
-        kl_ = *k;
-        kl_bank_ = k->pitch_q32 <= kOne ? 0u : 3 * k->pitch_q32 <= 4 * kOne ? 1u : k->pitch_q32 <= 2 * kOne ? 2u : 3u;
-        kl_log_hop_ = 0;
-        while ((1u << kl_log_hop_) < k->hop) ++kl_log_hop_;
-    }
-    kl_on_ = k != nullptr;
-    kl_t_ = 0;
-}
-
-void Deck::fetch_grains() {
-    if (grains_fetched_) return;
-    hip_check(hipSetDevice(device_), "hipSetDevice");
-    hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
-    std::vector<KlRec> r(grains_.size());
-    hip_check(hipMemcpy(r.data(), (const KlRec*)kl_rec_.p + 2, r.size() * sizeof(KlRec), hipMemcpyDeviceToHost), "hipMemcpy(deck grains)");
-    for (size_t k = 0; k < r.size(); ++k) { grains_[k].g_q32 = r[k].g; grains_[k].delta = r[k].delta; grains_[k].dist = r[k].dist; }
-    grains_fetched_ = true;
-}
-
-void Deck::read_grains(uint32_t first, uint32_t n, mx_deck_grain* dst) {
-    if (first > grains_.size() || n > grains_.size() - first) throw Error(MX_ERR_INVALID, "deck: a window beyond the last feed's grains");
-    if (n && !dst) throw Error(MX_ERR_INVALID, "deck: dst is NULL");
-    if (!n) return;
-    fetch_grains();
-    std::memcpy(dst, grains_.data() + first, (size_t)n * sizeof(mx_deck_grain));
-}
-
-void Deck::debug_last_keylock(uint32_t out[4]) {
+DeckLastKeylock deck_last_keylock() {
     std::lock_guard<std::mutex> lock(feed_state.mu);
-    out[0] = feed_state.kl_searched; out[1] = feed_state.kl_unsearched; out[2] = out[3] = 0;
-    const uint32_t spt = feed_state.last_spt;
-    for (const FeedState::KlTick& k : feed_state.last_kl) {
-        if (!k.t.play) continue;
-        const uint32_t hop = 1u << k.log_hop;
-        for (uint32_t n0 = 0; n0 < spt; n0 += MX_DECK_CHUNK) {
-            const uint32_t a = k.t.m0 + n0, b = a + std::min<uint32_t>(MX_DECK_CHUNK, spt - n0) - 1;   // the chunk's clock, first and last lane
-            if ((a >> k.log_hop) != (b >> k.log_hop)) ++out[3];
-            bool fades = false;
-            for (uint32_t dj = a >> k.log_hop; dj <= (b >> k.log_hop); ++dj)   // per grain of the chunk, the smallest m is that of its first lane
-                if ((std::max(a, dj * hop) & (hop - 1)) < k.overlap && !(k.t.first0 && dj == 0)) fades = true;
-            if (fades) ++out[2];
-        }
-    }
-}
-
-// ---- analysis (the header's ANALYSIS) ----
-void deck_analysis_check(const mx_deck_analysis& a) {
-    if (a.column < 64 || a.column > 4096 || (a.column & (a.column - 1))) throw Error(MX_ERR_INVALID, "deck analysis: column is not a power of two in 64 .. 4096");
-    if (!(a.taps & 1u) || a.taps > 127) throw Error(MX_ERR_INVALID, "deck analysis: taps is not odd in 1 .. 127");
-    if (a.max_lag < 16 || a.max_lag > 1024) throw Error(MX_ERR_INVALID, "deck analysis: max_lag outside 16 .. 1024");
-    if (a._pad) throw Error(MX_ERR_INVALID, "deck analysis: _pad must be 0");
-    for (const int16_t* t : {a.lo, a.hi}) {
-        uint32_t sum = 0;
-        for (uint32_t k = 0; k < 127; ++k) {
-            if (k >= a.taps && t[k]) throw Error(MX_ERR_INVALID, std::string("deck analysis: ") + (t == a.lo ? "lo" : "hi") + " has a non-zero entry at index taps or above");
-            sum += (uint32_t)(t[k] < 0 ? -(int32_t)t[k] : (int32_t)t[k]);
-        }
-        if (sum > 32767) throw Error(MX_ERR_INVALID, std::string("deck analysis: the sum of |") + (t == a.lo ? "lo" : "hi") + "[k]| is above 32767");
-    }
-}
-
-uint64_t deck_column_count(uint64_t n_frames, uint32_t column) {
-    if (n_frames < 1 || n_frames > kMaxFrames) throw Error(MX_ERR_INVALID, "deck analysis: n_frames outside 1 .. 2^30");
-    if (column < 64 || column > 4096 || (column & (column - 1))) throw Error(MX_ERR_INVALID, "deck analysis: column is not a power of two in 64 .. 4096");
-    return (n_frames + column - 1) / column;
-}
-
-void deck_analysis_bands(double rate, double f_lo, double f_hi, uint32_t taps, mx_deck_analysis& a) {
-    if (!(std::isfinite(rate) && rate > 0.0)) throw Error(MX_ERR_INVALID, "deck analysis bands: rate is not finite and positive");
-    if (!(f_lo > 0.0 && f_lo < f_hi && f_hi < rate / 2.0)) throw Error(MX_ERR_INVALID, "deck analysis bands: the cutoffs are not 0 < f_lo < f_hi < rate / 2");
-    if (!(taps & 1u) || taps > 127) throw Error(MX_ERR_INVALID, "deck analysis bands: taps is not odd in 1 .. 127");
-    const double pi = 3.14159265358979323846;
-    const int K = (int)taps, D = (K - 1) / 2;
-    mx_deck_analysis out = a;
-    out.taps = taps;
-    const double cut[2] = {f_lo, f_hi};
-    int16_t* const tab[2] = {out.lo, out.hi};
-    for (int b = 0; b < 2; ++b) {
-        const double fc = 2.0 * cut[b] / rate;
-        double g[127], sum = 0.0;
-        for (int k = 0; k <= D; ++k) {   // the first half and the centre; the rest mirrors them
-            const double x = fc * (double)(k - D), w = 0.5 - 0.5 * std::cos(2.0 * pi * (double)(k + 1) / (double)(K + 1));
-            g[k] = g[K - 1 - k] = fc * (x == 0.0 ? 1.0 : std::sin(pi * x) / (pi * x)) * w;
-        }
-        for (int k = 0; k < K; ++k) sum += g[k];
-        long total = 0, c[127];
-        for (int k = 0; k < K; ++k) { c[k] = std::lround(16384.0 * g[k] / sum); total += c[k]; }
-        c[D] += 16384 - total;
-        long mag = 0;
-        for (int k = 0; k < K; ++k) mag += c[k] < 0 ? -c[k] : c[k];
-        if (mag > 32767) throw Error(MX_ERR_INVALID, "deck analysis bands: the sum of |c| is above 32767 at these cutoffs");
-        for (int k = 0; k < 127; ++k) tab[b][k] = k < K ? (int16_t)c[k] : (int16_t)0;
-    }
-    a = out;
-}
-
-void deck_columns_host(const int16_t* x, uint64_t n_frames, const mx_deck_analysis& a, uint64_t first, uint64_t n, mx_deck_column* cols, uint64_t* R) {
-    if (!x) throw Error(MX_ERR_INVALID, "deck columns: interleaved is NULL");
-    deck_analysis_check(a);
-    const uint64_t N = deck_column_count(n_frames, a.column);
-    if (first > N || n > N - first) throw Error(MX_ERR_INVALID, "deck columns: a window beyond the track's columns");
-    if (n && !cols) throw Error(MX_ERR_INVALID, "deck columns: cols is NULL");
-    if (R && (first != 0 || n != N)) throw Error(MX_ERR_INVALID, "deck columns: the autocorrelation needs all the columns, first = 0 and n = N");
-    const uint32_t C = a.column, K = a.taps, D = (K - 1) / 2;
-    auto s = [&](int64_t f) -> int32_t { return f < 0 || f >= (int64_t)n_frames ? 0 : (int32_t)x[2 * f] + (int32_t)x[2 * f + 1]; };
-    std::vector<int32_t> w((size_t)C + K - 1);
-    uint32_t before = 0;   // A[first - 1]
-    if (first) {
-        uint64_t e = 0;
-        for (uint64_t f = (first - 1) * C; f < first * C; ++f) { const int64_t v = s((int64_t)f); e += (uint64_t)(v * v); }
-        before = tempo_root(e);
-    }
-    for (uint64_t c = first; c < first + n; ++c) {
-        const uint64_t f0 = c * C;
-        const uint32_t cnt = (uint32_t)std::min<uint64_t>(C, n_frames - f0);
-        for (uint32_t i = 0; i < cnt + K - 1; ++i) w[i] = s((int64_t)f0 - (int64_t)D + (int64_t)i);
-        mx_deck_column r{INT32_MAX, INT32_MIN, {0u, 0u, 0u}, 0u, {0u, 0u, 0u}, 0u};
-        for (uint32_t i = 0; i < cnt; ++i) {
-            int32_t a1 = 0, a2 = 0;   // exact: |a| <= 65536 * 32767
-            for (uint32_t k = 0; k < K; ++k) { a1 += (int32_t)a.lo[k] * w[i + k]; a2 += (int32_t)a.hi[k] * w[i + k]; }
-            const int32_t sv = w[i + D], low = a1 >> 14, b = a2 >> 14, band[3] = {low, b - low, sv - b};
-            r.smin = std::min(r.smin, sv); r.smax = std::max(r.smax, sv);
-            for (int j = 0; j < 3; ++j) {
-                const uint64_t m = (uint64_t)(band[j] < 0 ? -(int64_t)band[j] : (int64_t)band[j]);
-                r.peak[j] = std::max(r.peak[j], (uint32_t)m);
-                r.energy[j] += m * m;
-            }
-            r.e += (uint64_t)((int64_t)sv * sv);
-        }
-        const uint32_t A = tempo_root(r.e);
-        r.onset = (A > before ? A - before : 0u) >> 6;
-        before = A;
-        cols[c - first] = r;
-    }
-    if (R)
-        for (uint64_t l = 0; l < a.max_lag; ++l) {
-            uint64_t acc = 0;
-            for (uint64_t c = 0; c + l < N; ++c) acc += (uint64_t)cols[c].onset * cols[c + l].onset;
-            R[l] = acc;
-        }
-}
-
-// (the library is built with -ffp-contract=off: the multiply and the add of i_k are two roundings, as the header says)
-void deck_beatgrid(const mx_deck_column* cols, uint64_t n_cols, const uint64_t* R, uint32_t max_lag, uint32_t column, double rate, double bpm_lo, double bpm_hi, mx_deck_grid& out) {
-    if (!R || (n_cols && !cols)) throw Error(MX_ERR_INVALID, "deck beat grid: NULL argument");
-    if (column < 64 || column > 4096 || (column & (column - 1)) || max_lag < 16 || max_lag > 1024)
-        throw Error(MX_ERR_INVALID, "deck beat grid: column is not a power of two in 64 .. 4096, or max_lag is outside 16 .. 1024");
-    if (!(std::isfinite(rate) && rate > 0.0 && std::isfinite(bpm_lo) && bpm_lo > 0.0 && std::isfinite(bpm_hi) && bpm_hi >= bpm_lo))
-        throw Error(MX_ERR_INVALID, "deck beat grid: rate, bpm_lo and bpm_hi must be finite and positive, bpm_lo <= bpm_hi");
-    out = mx_deck_grid{0.0, 0.0, 0.0, 0u, 0u, 0u};
-    uint32_t best = 0; double d = 0.0;
-    if (!tempo_lag([&](uint32_t l) { return (double)R[l]; }, max_lag, column, rate, bpm_lo, bpm_hi, best, d)) return;
-    const double P = (double)best + d;
-    if (!(P >= 1.0 && P <= (double)max_lag)) return;
-    const uint32_t phases = (uint32_t)std::ceil(P);
-    uint64_t best_sum = 0; uint32_t phi_best = 0;
-    for (uint32_t phi = 0; phi < phases; ++phi) {
-        uint64_t sum = 0;
-        for (uint64_t k = 0;; ++k) {
-            const double step = (double)k * P;
-            const double at = (double)phi + step;
-            const int64_t i = (int64_t)std::floor(at);
-            if (i >= (int64_t)n_cols) break;
-            sum += cols[i].onset;
-        }
-        if (phi == 0 || sum > best_sum) { best_sum = sum; phi_best = phi; }
-    }
-    out.bpm = 60.0 * rate / ((double)column * P); out.period_columns = P; out.confidence = (double)R[best] / (double)R[0];
-    out.first_beat_frame = (uint64_t)phi_best * column; out.lag = best; out.phase_column = phi_best;
-}
-
-namespace {
-std::mutex analysis_mu;
-uint32_t last_analysis[4] = {0u, 0u, 0u, 0u};   // mx_deck_debug_last_analysis
-}  // namespace
-
-void Deck::analyse(const mx_deck_analysis* a) {
-    if (a) deck_analysis_check(*a);
-    hip_check(hipSetDevice(device_), "hipSetDevice");
-    const uint64_t N = a ? deck_column_count(n_frames_, a->column) : 0;
-    const size_t need = a ? (size_t)N * sizeof(mx_deck_column) + (size_t)a->max_lag * sizeof(uint64_t) + (size_t)N * sizeof(uint32_t) : 0;
-    if (!a || an_.bytes < need) {
-        hip_check(hipStreamSynchronize(load_stream_), "hipStreamSynchronize");   // an analysis in flight still writes the buffer that goes
-        an_cols_ = 0; an_lag_ = 0;
-        an_.free_();
-        if (!a) return;
-        an_.alloc(need);   // (MX_ERR_NOMEM leaves the deck without an analysis)
-    }
-    an_cols_ = 0; an_lag_ = 0;
-    DeckAnalyseTaps taps{};
-    for (uint32_t k = 0; k < a->taps; ++k) { taps.lo[k] = a->lo[k]; taps.hi[k] = a->hi[k]; }
-    uint64_t* const R = (uint64_t*)((char*)an_.p + (size_t)N * sizeof(mx_deck_column));
-    uint32_t forms[4];
-    launch_deck_analyse((const uint32_t*)track_.p, n_frames_, a->column, a->taps, a->max_lag, taps, an_.p, (uint32_t*)(R + a->max_lag), R, N, forms, load_stream_);
-    hip_check(hipGetLastError(), "deck analyse launch");
-    an_cols_ = N; an_lag_ = a->max_lag;
-    std::lock_guard<std::mutex> lock(analysis_mu);
-    std::memcpy(last_analysis, forms, sizeof forms);
-}
-
-void Deck::read_columns(uint64_t first, uint64_t n, mx_deck_column* dst) {
-    if (!an_cols_) throw Error(MX_ERR_INVALID, "deck: no analysis");
-    if (first > an_cols_ || n > an_cols_ - first) throw Error(MX_ERR_INVALID, "deck: a window beyond the analysis' columns");
-    if (n && !dst) throw Error(MX_ERR_INVALID, "deck: dst is NULL");
-    if (!n) return;
-    hip_check(hipSetDevice(device_), "hipSetDevice");
-    hip_check(hipStreamSynchronize(load_stream_), "hipStreamSynchronize");
-    hip_check(hipMemcpy(dst, (const mx_deck_column*)an_.p + first, (size_t)n * sizeof(mx_deck_column), hipMemcpyDeviceToHost), "hipMemcpy(deck columns)");
-}
-
-void Deck::read_autocorr(uint64_t* R, uint32_t cap) {
-    if (!an_cols_) throw Error(MX_ERR_INVALID, "deck: no analysis");
-    if (cap < an_lag_) throw Error(MX_ERR_INVALID, "deck: cap is below the analysis' max_lag");
-    if (!R) throw Error(MX_ERR_INVALID, "deck: R is NULL");
-    hip_check(hipSetDevice(device_), "hipSetDevice");
-    hip_check(hipStreamSynchronize(load_stream_), "hipStreamSynchronize");
-    hip_check(hipMemcpy(R, (const char*)an_.p + (size_t)an_cols_ * sizeof(mx_deck_column), (size_t)an_lag_ * sizeof(uint64_t), hipMemcpyDeviceToHost), "hipMemcpy(deck autocorrelation)");
-}
-
-void Deck::debug_last_analysis(uint32_t out[4]) {
-    std::lock_guard<std::mutex> lock(analysis_mu);
-    std::memcpy(out, last_analysis, sizeof last_analysis);
+    return DeckLastKeylock{feed_state.last_kl, feed_state.last_spt, feed_state.kl_searched, feed_state.kl_unsearched};
 }
 
 void Deck::debug_last_feed(uint32_t out[6]) {

@@ -4,6 +4,9 @@
 #include <vector>
 
 #include "mx_common.hpp"
+#include "mx_deck_columns.hpp"
+#include "mx_deck_finegrid.hpp"
+#include "mx_deck_loudkey.hpp"
 
 namespace mx {
 
@@ -60,33 +63,30 @@ struct KlTickDev { uint32_t m0, gi0, first0, play; };
 // ---- host ----
 void deck_keylock_check(const mx_deck_keylock& k);                                   // throws Error(MX_ERR_INVALID) naming the rule
 void deck_keylock_search(const int16_t* interleaved, uint64_t n_frames, int64_t C, int64_t A, uint32_t overlap, uint32_t radius, int32_t& delta, uint32_t& dist);
-// analysis (the header's ANALYSIS; mx_k_deck_analyse.hip)
-void deck_analysis_check(const mx_deck_analysis& a);                                 // throws Error(MX_ERR_INVALID) naming the rule
-void deck_analysis_bands(double rate, double f_lo, double f_hi, uint32_t taps, mx_deck_analysis& a);
-uint64_t deck_column_count(uint64_t n_frames, uint32_t column);
-void deck_columns_host(const int16_t* interleaved, uint64_t n_frames, const mx_deck_analysis& a, uint64_t first, uint64_t n, mx_deck_column* cols, uint64_t* R_or_null);
-void deck_beatgrid(const mx_deck_column* cols, uint64_t n_cols, const uint64_t* R, uint32_t max_lag, uint32_t column, double rate, double bpm_lo, double bpm_hi, mx_deck_grid& out);
-// whole-track tonality and loudness (the header's KEY AND LOUDNESS; mx_k_deck_tonality.hip, mx_k_deck_loudness.hip)
-void deck_tonality_check(const mx_deck_tonality& t);                                 // throws Error(MX_ERR_INVALID) naming the rule
-uint64_t deck_tonality_count(uint64_t n_frames, const mx_deck_tonality& t);
-void deck_tonality_host(const int16_t* interleaved, uint64_t n_frames, const mx_deck_tonality& t, uint64_t first, uint64_t n, void* dst);
-void deck_loudness_check(const mx_deck_loudness& l);                                 // throws Error(MX_ERR_INVALID) naming the rule
-uint64_t deck_loudness_count(uint64_t n_frames, uint32_t block_frames);
-void deck_loudness_host(const int16_t* interleaved, uint64_t n_frames, const mx_deck_loudness& l, mx_loudness_tick* dst, uint64_t cap);
-// the fine beat grid and sync (the header's FINE GRID; mx_deck_finegrid.cpp, mx_k_deck_finegrid.hip)
-void deck_finegrid_check(const mx_deck_finegrid& s, uint64_t n_frames, bool with_track);   // throws Error(MX_ERR_INVALID) naming the rule; without a track: every rule but first_hop < N
-uint64_t deck_finegrid_count(uint64_t n_frames, uint32_t hop);
-void deck_finegrid_span(uint64_t centre_q16, uint64_t halfwidth_q16, uint32_t beat_limit, uint64_t n_hops, uint32_t hop, mx_deck_finegrid& out, uint32_t* clipped_or_null);
-uint64_t deck_finegrid_period(double period_columns, uint32_t column, uint32_t hop);
-void deck_finegrid_host(const int16_t* interleaved, uint64_t n_frames, const mx_deck_finegrid& s, mx_deck_comb* recs, uint32_t* w_or_null);
-void deck_finegrid_pick(const mx_deck_comb* recs, const mx_deck_finegrid& s, double rate, mx_deck_fine_pick& out);
-void deck_sync(const mx_deck_beats& leader, int64_t leader_pos, int64_t leader_step, const mx_deck_beats& follower, int64_t follower_pos, mx_deck_sync_result& out);
 void deck_check(const mx_deck_params& p, uint64_t n_frames);                         // throws Error(MX_ERR_INVALID) naming the rule
 void deck_plan(const mx_deck_head& in, const mx_deck_params* params, const int64_t* seek, uint32_t spt, uint64_t n_frames, mx_deck_tick& tick, mx_deck_head& out);
 int64_t deck_step(uint32_t track_rate, uint32_t graph_rate, double speed);
 const float* deck_tables_host();                                                       // MX_DECK_BANKS x DECK_BANK_FLOATS, computed once
 void deck_stream_retired(hipStream_t s);                                               // the stream is going away: the feed's staging slots last used on it let go of it
 
+// key-lock of one deck: the setting, the grain clock t (playing output frames since the last restart), and the graph of the last feed (another one restarts the clock)
+struct DeckKeylock {
+    bool on = false; mx_deck_keylock k{}; uint32_t bank = 0, log_hop = 0;
+    uint64_t t = 0;
+    const Graph* last_graph = nullptr;
+    uint64_t last_lineage = 0;          // Graph::lineage() of that feed: a graph that adopted the last one's state is the same graph to the grain clock
+    DevBuf state;                       // g of the last two grains, 2 x int64: written and read by the search kernel only
+    DevBuf rec;                         // KlRec x (2 + the grains of the last feed)
+    std::vector<mx_deck_grain> grains;  // the last feed's grain records; g / delta / dist are fetched from rec by read_grains
+    bool grains_fetched = true;
+};
+// the key-locked ticks and grain counts of the last feed as mx_deck_debug_last_keylock reads them: a copy, taken under the feed's lock (mx_deck.cpp)
+struct DeckKlTick { KlTickDev t; uint32_t log_hop, overlap; };
+struct DeckLastKeylock { std::vector<DeckKlTick> ticks; uint32_t spt = 0, searched = 0, unsearched = 0; };
+DeckLastKeylock deck_last_keylock();
+
+// The track, the transport state machine and the feed (mx_deck.cpp), key-lock (mx_deck_keylock.cpp), and the four whole-track analyses, each a member that holds
+// its own results and sees of the deck a DeckTrack and nothing else (mx_deck_analysis.hpp).
 class Deck {
 public:
     Deck(uint64_t n_frames, int device);
@@ -101,23 +101,9 @@ public:
     static void feed(Deck* const* decks, const uint32_t* nodes, size_t n, Graph& g, uint32_t n_ticks);
     static void debug_last_feed(uint32_t out[6]);
     void set_keylock(const mx_deck_keylock* k);                            // NULL: off.  Restarts the grain clock.
-    uint32_t grain_count() const { return (uint32_t)grains_.size(); }
+    uint32_t grain_count() const { return (uint32_t)keylock_.grains.size(); }
     void read_grains(uint32_t first, uint32_t n, mx_deck_grain* dst);      // waits for the device
     static void debug_last_keylock(uint32_t out[4]);
-    void analyse(const mx_deck_analysis* a);                               // NULL: frees the results.  Asynchronous on the load stream.
-    void read_columns(uint64_t first, uint64_t n, mx_deck_column* dst);    // waits for the analysis
-    void read_autocorr(uint64_t* R, uint32_t cap);                         // waits for the analysis
-    static void debug_last_analysis(uint32_t out[4]);
-    void analyse_tonality(const mx_deck_tonality* t);                      // NULL: frees the results.  Asynchronous on the load stream.
-    void read_tonality(uint64_t first, uint64_t n, void* dst, size_t cap_bytes);   // waits for the analysis
-    static void debug_last_tonality(uint32_t out[4]);
-    void analyse_loudness(const mx_deck_loudness* l);                      // NULL: frees the results.  Asynchronous on the load stream.
-    void read_loudness(uint64_t first, uint64_t n, mx_loudness_tick* dst);  // waits for the analysis
-    static void debug_last_loudness(uint32_t out[4]);
-    void analyse_finegrid(const mx_deck_finegrid* s);                      // NULL: frees the results.  Asynchronous on the load stream.
-    void read_finegrid(uint64_t first, uint64_t n, mx_deck_comb* dst);     // waits for the analysis
-    void read_fine_onsets(uint64_t first, uint64_t n, uint32_t* w);        // waits for the analysis
-    static void debug_last_finegrid(uint32_t out[4]);
 
 private:
     void fetch_grains();
@@ -125,30 +111,18 @@ private:
     uint64_t n_frames_; int device_;
     DevBuf track_;
     hipStream_t load_stream_ = nullptr; hipEvent_t loaded_ = nullptr; bool load_pending_ = false;
+    DeckTrack for_analyses_;            // the four fields above that an analysis reads, as the constructor left them
     mx_deck_head head_{};
     std::vector<Event> sched_;          // at most one per tick, in no order
     std::vector<mx_deck_tick> ticks_;   // the last feed's records
-    // key-lock: the setting, the grain clock t (playing output frames since the last restart), and the graph of the last feed (another one restarts the clock)
-    bool kl_on_ = false; mx_deck_keylock kl_{}; uint32_t kl_bank_ = 0, kl_log_hop_ = 0;
-    uint64_t kl_t_ = 0;
-    const Graph* last_graph_ = nullptr;
-    uint64_t last_lineage_ = 0;               // Graph::lineage() of that feed: a graph that adopted the last one's state is the same graph to the grain clock
-    DevBuf kl_state_;                   // g of the last two grains, 2 x int64: written and read by the search kernel only
-    DevBuf kl_rec_;                     // KlRec x (2 + the grains of the last feed)
-    std::vector<mx_deck_grain> grains_; // the last feed's grain records; g / delta / dist are fetched from kl_rec_ by read_grains
-    bool grains_fetched_ = true;
-    // analysis: one buffer -- columns (an_cols_ x 56 bytes), R (an_lag_ x 8), onsets (an_cols_ x 4) -- written on load_stream_ only; an_cols_ = 0: none
-    DevBuf an_;
-    uint64_t an_cols_ = 0; uint32_t an_lag_ = 0;
-    // whole-track tonality: one buffer -- ton_segs_ records of ton_rec_bytes_, then the decimated frames -- and the table set of ton_tab_for_ with its decimator taps ton_fir_ (kept while the settings
-    // that shape them stay); loudness: one buffer -- loud_blocks_ records, then the walk states.  All written on load_stream_ only; a count of 0: none
-    DevBuf ton_, ton_tab_;
-    uint64_t ton_segs_ = 0; size_t ton_rec_bytes_ = 0; mx_deck_tonality ton_tab_for_{}; int16_t ton_fir_[64] = {};
-    DevBuf loud_;
-    uint64_t loud_blocks_ = 0;
-    // fine grid: one buffer -- room for 8192 comb records, then w (fg_hops_ x 4 bytes) -- written on load_stream_ only; fg_periods_ = 0: none
-    DevBuf fg_;
-    uint32_t fg_periods_ = 0; uint64_t fg_hops_ = 0;
+    DeckKeylock keylock_;
+
+public:
+    // the whole-track analyses (mx_abi_deck.cpp calls them directly)
+    DeckColumns columns{for_analyses_};
+    DeckTonality tonality{for_analyses_};
+    DeckLoudness loudness{for_analyses_};
+    DeckFineGrid finegrid{for_analyses_};
 };
 
 }  // namespace mx

@@ -1,0 +1,26 @@
+// mx_deck_columns.hpp -- the deck's band columns, onsets and their autocorrelation (include/mixlab_gpu.h "ANALYSIS"; mx_k_deck_analyse.hip):
+// the host-only rule functions and the deck's first analysis (internal).
+#pragma once
+#include "mx_deck_analysis.hpp"
+
+namespace mx {
+
+void deck_analysis_check(const mx_deck_analysis& a);                                 // throws Error(MX_ERR_INVALID) naming the rule
+void deck_analysis_bands(double rate, double f_lo, double f_hi, uint32_t taps, mx_deck_analysis& a);
+uint64_t deck_column_count(uint64_t n_frames, uint32_t column);
+void deck_columns_host(const int16_t* interleaved, uint64_t n_frames, const mx_deck_analysis& a, uint64_t first, uint64_t n, mx_deck_column* cols, uint64_t* R_or_null);
+void deck_beatgrid(const mx_deck_column* cols, uint64_t n_cols, const uint64_t* R, uint32_t max_lag, uint32_t column, double rate, double bpm_lo, double bpm_hi, mx_deck_grid& out);
+
+// one buffer -- columns (count_ x 56 bytes), R (lag_ x 8), onsets (count_ x 4)
+class DeckColumns : public DeckTrackAnalysis {
+public:
+    explicit DeckColumns(const DeckTrack& deck);
+    void analyse(const mx_deck_analysis* a);                               // NULL: frees the results.  Asynchronous on the load stream.
+    void read_columns(uint64_t first, uint64_t n, mx_deck_column* dst);    // waits for the analysis
+    void read_autocorr(uint64_t* R, uint32_t cap);                         // waits for the analysis
+    static void debug_last(uint32_t out[4]);
+private:
+    uint32_t lag_ = 0;
+};
+
+}  // namespace mx

@@ -3,17 +3,14 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <mutex>
 #include <vector>
 
-#include "mx_deck.hpp"
 #include "mx_deck_finegrid.hpp"
 
 namespace mx {
 
 typedef __int128 i128;
 
-static const uint64_t kMaxFrames = (uint64_t)1 << 30;
 static const int64_t kMaxStep = (int64_t)4 << 32, kMaxPeriod = (int64_t)1 << 56, kMaxPos = (int64_t)1 << 62;
 
 static void hop_check(uint32_t hop) {
@@ -21,7 +18,7 @@ static void hop_check(uint32_t hop) {
 }
 
 uint64_t deck_finegrid_count(uint64_t n_frames, uint32_t hop) {
-    if (n_frames < 1 || n_frames > kMaxFrames) throw Error(MX_ERR_INVALID, "deck fine grid: n_frames outside 1 .. 2^30");
+    if (n_frames < 1 || n_frames > kDeckMaxFrames) throw Error(MX_ERR_INVALID, "deck fine grid: n_frames outside 1 .. 2^30");
     hop_check(hop);
     return (n_frames + hop - 1) / hop;
 }
@@ -142,61 +139,34 @@ void deck_sync(const mx_deck_beats& l, int64_t lpos, int64_t lstep, const mx_dec
 }
 
 // ---- the deck's fourth analysis ----
-namespace {
-std::mutex finegrid_mu;
-uint32_t last_finegrid[4] = {0u, 0u, 0u, 0u};   // mx_deck_debug_last_finegrid
-size_t rec_bytes(uint32_t n_periods) { return (size_t)n_periods * sizeof(mx_deck_comb); }
-}  // namespace
+static DeckLastForms last_finegrid;   // mx_deck_debug_last_finegrid
+static const size_t kRecRoom = (size_t)MX_DECK_FINEGRID_MAX_PERIODS * sizeof(mx_deck_comb);
 
-void Deck::analyse_finegrid(const mx_deck_finegrid* s) {
-    if (s) deck_finegrid_check(*s, n_frames_, true);
-    hip_check(hipSetDevice(device_), "hipSetDevice");
-    const uint64_t N = s ? deck_finegrid_count(n_frames_, s->hop) : 0;
-    const size_t need = s ? rec_bytes(MX_DECK_FINEGRID_MAX_PERIODS) + (size_t)N * sizeof(uint32_t) : 0;   // room for any n_periods: a second stage never grows the buffer
-    if (!s || fg_.bytes < need) {
-        hip_check(hipStreamSynchronize(load_stream_), "hipStreamSynchronize");   // an analysis in flight still writes the buffer that goes
-        fg_periods_ = 0; fg_hops_ = 0;
-        fg_.free_();
-        if (!s) return;
-        fg_.alloc(need);   // (MX_ERR_NOMEM leaves the deck without a fine grid)
-    }
-    fg_periods_ = 0; fg_hops_ = 0;
+DeckFineGrid::DeckFineGrid(const DeckTrack& deck) : DeckTrackAnalysis(deck, last_finegrid) {}
+
+void DeckFineGrid::analyse(const mx_deck_finegrid* s) {
+    if (s) deck_finegrid_check(*s, deck_.n_frames, true);
+    const uint64_t N = s ? deck_finegrid_count(deck_.n_frames, s->hop) : 0;
+    // need does not depend on n_periods: there is room for any, so a second stage never grows the buffer (nor waits for the first)
+    if (!prepare(kRecRoom + (size_t)N * sizeof(uint32_t), !s)) return;
     uint32_t log_hop = 0;
     while ((1u << log_hop) < s->hop) ++log_hop;
-    DkFineArgs a{(const uint32_t*)track_.p, (int64_t)n_frames_, log_hop, (uint32_t)N, s->n_periods, s->first_hop, s->period0_q16, s->dperiod_q16,
-                 (uint32_t)fg_trip(N, s->first_hop, s->period0_q16, s->max_beats), (uint32_t*)((char*)fg_.p + rec_bytes(MX_DECK_FINEGRID_MAX_PERIODS)), (mx_deck_comb*)fg_.p};
+    DkFineArgs a{deck_.track, (int64_t)deck_.n_frames, log_hop, (uint32_t)N, s->n_periods, s->first_hop, s->period0_q16, s->dperiod_q16,
+                 (uint32_t)fg_trip(N, s->first_hop, s->period0_q16, s->max_beats), (uint32_t*)((char*)buf_.p + kRecRoom), (mx_deck_comb*)buf_.p};
     uint32_t forms[4];
-    launch_deck_finegrid(a, forms, load_stream_);
-    hip_check(hipGetLastError(), "deck fine grid launch");
-    fg_periods_ = s->n_periods; fg_hops_ = N;
-    std::lock_guard<std::mutex> lock(finegrid_mu);
-    std::memcpy(last_finegrid, forms, sizeof forms);
+    launch_deck_finegrid(a, forms, deck_.load_stream);
+    hops_ = N;
+    launched("deck fine grid launch", s->n_periods, forms);
 }
 
-void Deck::read_finegrid(uint64_t first, uint64_t n, mx_deck_comb* dst) {
-    if (!fg_periods_) throw Error(MX_ERR_INVALID, "deck: no fine grid");
-    if (first > fg_periods_ || n > fg_periods_ - first) throw Error(MX_ERR_INVALID, "deck: a window beyond the fine grid's periods");
-    if (n && !dst) throw Error(MX_ERR_INVALID, "deck: dst is NULL");
-    if (!n) return;
-    hip_check(hipSetDevice(device_), "hipSetDevice");
-    hip_check(hipStreamSynchronize(load_stream_), "hipStreamSynchronize");
-    hip_check(hipMemcpy(dst, (const mx_deck_comb*)fg_.p + first, (size_t)n * sizeof(mx_deck_comb), hipMemcpyDeviceToHost), "hipMemcpy(deck fine grid)");
+void DeckFineGrid::read(uint64_t first, uint64_t n, mx_deck_comb* dst) {
+    read_window(first, n, dst, sizeof(mx_deck_comb), 0, count_, {"deck: no fine grid", "deck: a window beyond the fine grid's periods", "deck: dst is NULL", "hipMemcpy(deck fine grid)"});
 }
 
-void Deck::read_fine_onsets(uint64_t first, uint64_t n, uint32_t* w) {
-    if (!fg_periods_) throw Error(MX_ERR_INVALID, "deck: no fine grid");
-    if (first > fg_hops_ || n > fg_hops_ - first) throw Error(MX_ERR_INVALID, "deck: a window beyond the fine grid's hops");
-    if (n && !w) throw Error(MX_ERR_INVALID, "deck: w is NULL");
-    if (!n) return;
-    hip_check(hipSetDevice(device_), "hipSetDevice");
-    hip_check(hipStreamSynchronize(load_stream_), "hipStreamSynchronize");
-    hip_check(hipMemcpy(w, (const char*)fg_.p + rec_bytes(MX_DECK_FINEGRID_MAX_PERIODS) + (size_t)first * sizeof(uint32_t), (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost),
-              "hipMemcpy(deck fine onsets)");
+void DeckFineGrid::read_onsets(uint64_t first, uint64_t n, uint32_t* w) {
+    read_window(first, n, w, sizeof(uint32_t), kRecRoom, hops_, {"deck: no fine grid", "deck: a window beyond the fine grid's hops", "deck: w is NULL", "hipMemcpy(deck fine onsets)"});
 }
 
-void Deck::debug_last_finegrid(uint32_t out[4]) {
-    std::lock_guard<std::mutex> lock(finegrid_mu);
-    std::memcpy(out, last_finegrid, sizeof last_finegrid);
-}
+void DeckFineGrid::debug_last(uint32_t out[4]) { last_finegrid.get(out); }
 
 }  // namespace mx

@@ -1,11 +1,12 @@
 // mx_deck_finegrid.hpp -- the deck's fine beat grid (include/mixlab_gpu.h "FINE GRID"): the rules that the host function
-// (mx_deck_finegrid.cpp) and the kernels (mx_k_deck_finegrid.hip) both evaluate, stated once, and the launch (internal).
+// (mx_deck_finegrid.cpp) and the kernels (mx_k_deck_finegrid.hip) both evaluate, stated once, the launch, and the deck's fourth analysis (internal).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "mx_common.hpp"
+#include "mx_deck_analysis.hpp"
 #include "mx_dev.hpp"
 
 namespace mx {
@@ -44,5 +45,26 @@ struct DkFineArgs {
 };
 enum { DK_FINE_FORM_ONE_PASS = 0, DK_FINE_FORM_STRIDED = 1, DK_FINE_FORM_ONSET = 2, DK_FINE_FORM_TRIP = 3 };
 void launch_deck_finegrid(const DkFineArgs& a, uint32_t forms[4], hipStream_t s);
+
+// ---- host ----
+void deck_finegrid_check(const mx_deck_finegrid& s, uint64_t n_frames, bool with_track);   // throws Error(MX_ERR_INVALID) naming the rule; without a track: every rule but first_hop < N
+uint64_t deck_finegrid_count(uint64_t n_frames, uint32_t hop);
+void deck_finegrid_span(uint64_t centre_q16, uint64_t halfwidth_q16, uint32_t beat_limit, uint64_t n_hops, uint32_t hop, mx_deck_finegrid& out, uint32_t* clipped_or_null);
+uint64_t deck_finegrid_period(double period_columns, uint32_t column, uint32_t hop);
+void deck_finegrid_host(const int16_t* interleaved, uint64_t n_frames, const mx_deck_finegrid& s, mx_deck_comb* recs, uint32_t* w_or_null);
+void deck_finegrid_pick(const mx_deck_comb* recs, const mx_deck_finegrid& s, double rate, mx_deck_fine_pick& out);
+void deck_sync(const mx_deck_beats& leader, int64_t leader_pos, int64_t leader_step, const mx_deck_beats& follower, int64_t follower_pos, mx_deck_sync_result& out);
+
+// one buffer -- room for MX_DECK_FINEGRID_MAX_PERIODS comb records (count_ of them written), then w (hops_ x 4 bytes)
+class DeckFineGrid : public DeckTrackAnalysis {
+public:
+    explicit DeckFineGrid(const DeckTrack& deck);
+    void analyse(const mx_deck_finegrid* s);                               // NULL: frees the results.  Asynchronous on the load stream.
+    void read(uint64_t first, uint64_t n, mx_deck_comb* dst);              // waits for the analysis
+    void read_onsets(uint64_t first, uint64_t n, uint32_t* w);             // waits for the analysis
+    static void debug_last(uint32_t out[4]);
+private:
+    uint64_t hops_ = 0;
+};
 
 }  // namespace mx

@@ -4,17 +4,14 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <mutex>
 #include <vector>
 
-#include "mx_deck.hpp"
 #include "mx_deck_loudkey.hpp"
 
 namespace mx {
 
-static const uint64_t kMaxFrames = (uint64_t)1 << 30;
 static void frames_check(uint64_t n_frames, const char* what) {
-    if (n_frames < 1 || n_frames > kMaxFrames) throw Error(MX_ERR_INVALID, std::string(what) + ": n_frames outside 1 .. 2^30");
+    if (n_frames < 1 || n_frames > kDeckMaxFrames) throw Error(MX_ERR_INVALID, std::string(what) + ": n_frames outside 1 .. 2^30");
 }
 
 // ---- tonality ----
@@ -160,104 +157,72 @@ void deck_loudness_host(const int16_t* x, uint64_t n_frames, const mx_deck_loudn
 
 // ---- the deck's two analyses ----
 namespace {
-std::mutex loudkey_mu;
-uint32_t last_tonality[4] = {0u, 0u, 0u, 0u}, last_loudness[4] = {0u, 0u, 0u, 0u};   // mx_deck_debug_last_tonality / _loudness
+DeckLastForms last_tonality, last_loudness;   // mx_deck_debug_last_tonality / _loudness
 bool same_tables(const mx_deck_tonality& a, const mx_deck_tonality& b) {
     return a.rate == b.rate && a.decim == b.decim && a.octaves == b.octaves && a.f_lo_mhz == b.f_lo_mhz;
 }
 }  // namespace
 
-void Deck::analyse_tonality(const mx_deck_tonality* t) {
+DeckTonality::DeckTonality(const DeckTrack& deck) : DeckTrackAnalysis(deck, last_tonality) {}
+
+void DeckTonality::analyse(const mx_deck_tonality* t) {
     if (t) deck_tonality_check(*t);
-    hip_check(hipSetDevice(device_), "hipSetDevice");
-    const uint64_t n_seg = t ? deck_tonality_count(n_frames_, *t) : 0;
+    const uint64_t n_seg = t ? deck_tonality_count(deck_.n_frames, *t) : 0;
     const size_t rb = t ? tonality_record_bytes(t->octaves) : 0;
     const size_t rec_bytes = (size_t)n_seg * rb, need = t ? rec_bytes + (size_t)n_seg * t->segment_hops * t->hop_frames * sizeof(int16_t) : 0;   // (rb is a multiple of 8)
-    const bool new_tables = t && !(ton_tab_.p && same_tables(*t, ton_tab_for_));
-    if (!t || ton_.bytes < need || new_tables) {
-        hip_check(hipStreamSynchronize(load_stream_), "hipStreamSynchronize");   // an analysis in flight still uses the buffers that go
-        ton_segs_ = 0;
-        if (!t || ton_.bytes < need) ton_.free_();
-        if (!t) { ton_tab_.free_(); return; }
-        if (!ton_.p) ton_.alloc(need);   // (MX_ERR_NOMEM leaves the deck without this analysis)
+    const bool new_tables = t && !(tab_.p && same_tables(*t, tab_for_));
+    // the record buffer goes only when it is too small or on NULL; new tables alone make the wait, since an analysis in flight reads the old ones
+    if (!prepare(need, !t, new_tables)) {
+        tab_.free_();   // the tables go on NULL only
+        return;
     }
-    ton_segs_ = 0;
     DkFir fir;
     if (new_tables) {   // (the stream is idle: waited for above.  The tables cost the host more than the kernels cost the device: made once per setting)
         std::vector<uint32_t> tab;
         tonality_table_set(*t, fir, tab);
-        ton_tab_.free_();
-        ton_tab_.alloc(tab.size() * sizeof(uint32_t));
-        hip_check(hipMemcpy(ton_tab_.p, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice), "hipMemcpy(deck tonality tables)");
-        ton_tab_for_ = *t;
-        std::memcpy(ton_fir_, fir.c, sizeof ton_fir_);
+        tab_.free_();
+        tab_.alloc(tab.size() * sizeof(uint32_t));
+        hip_check(hipMemcpy(tab_.p, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice), "hipMemcpy(deck tonality tables)");
+        tab_for_ = *t;
+        std::memcpy(fir_, fir.c, sizeof fir_);
     }
-    std::memcpy(fir.c, ton_fir_, sizeof ton_fir_);
-    DkTonArgs a{(const uint32_t*)track_.p, (int64_t)n_frames_, t->decim, t->hop_frames, 12 * t->octaves, t->f_lo_mhz, t->segment_hops, n_seg,
-                (const uint32_t*)ton_tab_.p, (uint32_t*)ton_.p, (uint32_t)(rb / 4), (int16_t*)((char*)ton_.p + rec_bytes)};
+    std::memcpy(fir.c, fir_, sizeof fir_);
+    DkTonArgs a{deck_.track, (int64_t)deck_.n_frames, t->decim, t->hop_frames, 12 * t->octaves, t->f_lo_mhz, t->segment_hops, n_seg,
+                (const uint32_t*)tab_.p, (uint32_t*)buf_.p, (uint32_t)(rb / 4), (int16_t*)((char*)buf_.p + rec_bytes)};
     uint32_t forms[4];
-    launch_deck_tonality(a, fir, forms, load_stream_);
-    hip_check(hipGetLastError(), "deck tonality launch");
-    ton_segs_ = n_seg; ton_rec_bytes_ = rb;
-    std::lock_guard<std::mutex> lock(loudkey_mu);
-    std::memcpy(last_tonality, forms, sizeof forms);
+    launch_deck_tonality(a, fir, forms, deck_.load_stream);
+    rec_bytes_ = rb;
+    launched("deck tonality launch", n_seg, forms);
 }
 
-void Deck::read_tonality(uint64_t first, uint64_t n, void* dst, size_t cap_bytes) {
-    if (!ton_segs_) throw Error(MX_ERR_INVALID, "deck: no tonality analysis");
-    if (first > ton_segs_ || n > ton_segs_ - first) throw Error(MX_ERR_INVALID, "deck: a window beyond the tonality analysis' segments");
-    if (cap_bytes / ton_rec_bytes_ < n) throw Error(MX_ERR_INVALID, "deck: cap_bytes is below n records");
-    if (n && !dst) throw Error(MX_ERR_INVALID, "deck: dst is NULL");
-    if (!n) return;
-    hip_check(hipSetDevice(device_), "hipSetDevice");
-    hip_check(hipStreamSynchronize(load_stream_), "hipStreamSynchronize");
-    hip_check(hipMemcpy(dst, (const char*)ton_.p + (size_t)first * ton_rec_bytes_, (size_t)n * ton_rec_bytes_, hipMemcpyDeviceToHost), "hipMemcpy(deck tonality)");
+void DeckTonality::read(uint64_t first, uint64_t n, void* dst, size_t cap_bytes) {
+    read_window(first, n, dst, rec_bytes_, 0, count_,
+                {"deck: no tonality analysis", "deck: a window beyond the tonality analysis' segments", "deck: dst is NULL", "hipMemcpy(deck tonality)"}, cap_bytes);
 }
 
-void Deck::debug_last_tonality(uint32_t out[4]) {
-    std::lock_guard<std::mutex> lock(loudkey_mu);
-    std::memcpy(out, last_tonality, sizeof last_tonality);
-}
+void DeckTonality::debug_last(uint32_t out[4]) { last_tonality.get(out); }
 
-void Deck::analyse_loudness(const mx_deck_loudness* l) {
+DeckLoudness::DeckLoudness(const DeckTrack& deck) : DeckTrackAnalysis(deck, last_loudness) {}
+
+void DeckLoudness::analyse(const mx_deck_loudness* l) {
     if (l) deck_loudness_check(*l);
-    hip_check(hipSetDevice(device_), "hipSetDevice");
-    const uint64_t nb = l ? deck_loudness_count(n_frames_, l->block_frames) : 0;
-    const size_t need = (size_t)nb * (sizeof(LoudTick) + 2 * 4 * sizeof(double));
-    if (!l || loud_.bytes < need) {
-        hip_check(hipStreamSynchronize(load_stream_), "hipStreamSynchronize");   // an analysis in flight still writes the buffer that goes
-        loud_blocks_ = 0;
-        loud_.free_();
-        if (!l) return;
-        loud_.alloc(need);   // (MX_ERR_NOMEM leaves the deck without this analysis)
-    }
-    loud_blocks_ = 0;
+    const uint64_t nb = l ? deck_loudness_count(deck_.n_frames, l->block_frames) : 0;
+    if (!prepare((size_t)nb * (sizeof(LoudTick) + 2 * 4 * sizeof(double)), !l)) return;
     DkLoudTabs t;
     (void)loudness_tables(l->rate, l->block_frames, t.bq, t.carry, t.interp);
-    DkLoudArgs a{(const uint32_t*)track_.p, (int64_t)n_frames_, l->block_frames, l->momentary_blocks, l->short_blocks, (uint32_t)nb, (LoudTick*)loud_.p,
-                 (double*)((char*)loud_.p + (size_t)nb * sizeof(LoudTick))};
+    DkLoudArgs a{deck_.track, (int64_t)deck_.n_frames, l->block_frames, l->momentary_blocks, l->short_blocks, (uint32_t)nb, (LoudTick*)buf_.p,
+                 (double*)((char*)buf_.p + (size_t)nb * sizeof(LoudTick))};
     uint32_t forms[4];
-    launch_deck_loudness(a, t, forms, load_stream_);
-    hip_check(hipGetLastError(), "deck loudness launch");
-    loud_blocks_ = nb;
-    std::lock_guard<std::mutex> lock(loudkey_mu);
-    std::memcpy(last_loudness, forms, sizeof forms);
+    launch_deck_loudness(a, t, forms, deck_.load_stream);
+    launched("deck loudness launch", nb, forms);
 }
 
-void Deck::read_loudness(uint64_t first, uint64_t n, mx_loudness_tick* dst) {
+void DeckLoudness::read(uint64_t first, uint64_t n, mx_loudness_tick* dst) {
     static_assert(sizeof(mx_loudness_tick) == sizeof(LoudTick), "mx_loudness_tick is the kernels' record");
-    if (!loud_blocks_) throw Error(MX_ERR_INVALID, "deck: no loudness analysis");
-    if (first > loud_blocks_ || n > loud_blocks_ - first) throw Error(MX_ERR_INVALID, "deck: a window beyond the loudness analysis' blocks");
-    if (n && !dst) throw Error(MX_ERR_INVALID, "deck: dst is NULL");
-    if (!n) return;
-    hip_check(hipSetDevice(device_), "hipSetDevice");
-    hip_check(hipStreamSynchronize(load_stream_), "hipStreamSynchronize");
-    hip_check(hipMemcpy(dst, (const LoudTick*)loud_.p + first, (size_t)n * sizeof(LoudTick), hipMemcpyDeviceToHost), "hipMemcpy(deck loudness)");
+    read_window(first, n, dst, sizeof(LoudTick), 0, count_,
+                {"deck: no loudness analysis", "deck: a window beyond the loudness analysis' blocks", "deck: dst is NULL", "hipMemcpy(deck loudness)"});
 }
 
-void Deck::debug_last_loudness(uint32_t out[4]) {
-    std::lock_guard<std::mutex> lock(loudkey_mu);
-    std::memcpy(out, last_loudness, sizeof last_loudness);
-}
+void DeckLoudness::debug_last(uint32_t out[4]) { last_loudness.get(out); }
 
 }  // namespace mx

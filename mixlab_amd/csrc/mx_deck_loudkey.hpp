@@ -1,5 +1,6 @@
 // mx_deck_loudkey.hpp -- the deck's whole-track tonality and loudness (include/mixlab_gpu.h "KEY AND LOUDNESS"): the rules that the host
-// functions (mx_deck.cpp) and the kernels (mx_k_deck_tonality.hip, mx_k_deck_loudness.hip) both evaluate, stated once, and the launches (internal).
+// functions (mx_deck_loudkey.cpp) and the kernels (mx_k_deck_tonality.hip, mx_k_deck_loudness.hip) both evaluate, stated once, the launches, and the deck's two
+// analyses (internal).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -7,6 +8,7 @@
 #include <cstdint>
 
 #include "mx_common.hpp"
+#include "mx_deck_analysis.hpp"
 #include "mx_dev.hpp"
 
 namespace mx {
@@ -55,5 +57,36 @@ struct DkLoudArgs {
     double* walk;      // [channel][n_blocks][4]: Z_k, then S_k
 };
 void launch_deck_loudness(const DkLoudArgs& a, const DkLoudTabs& t, uint32_t forms[4], hipStream_t s);
+
+// ---- host ----
+void deck_tonality_check(const mx_deck_tonality& t);                                 // throws Error(MX_ERR_INVALID) naming the rule
+uint64_t deck_tonality_count(uint64_t n_frames, const mx_deck_tonality& t);
+void deck_tonality_host(const int16_t* interleaved, uint64_t n_frames, const mx_deck_tonality& t, uint64_t first, uint64_t n, void* dst);
+void deck_loudness_check(const mx_deck_loudness& l);                                 // throws Error(MX_ERR_INVALID) naming the rule
+uint64_t deck_loudness_count(uint64_t n_frames, uint32_t block_frames);
+void deck_loudness_host(const int16_t* interleaved, uint64_t n_frames, const mx_deck_loudness& l, mx_loudness_tick* dst, uint64_t cap);
+
+// one buffer -- count_ segment records of rec_bytes_, then the decimated frames -- and the table set of tab_for_ with its decimator taps fir_, kept while the settings
+// that shape them stay
+class DeckTonality : public DeckTrackAnalysis {
+public:
+    explicit DeckTonality(const DeckTrack& deck);
+    void analyse(const mx_deck_tonality* t);                               // NULL: frees the results.  Asynchronous on the load stream.
+    void read(uint64_t first, uint64_t n, void* dst, size_t cap_bytes);    // waits for the analysis
+    static void debug_last(uint32_t out[4]);
+private:
+    DevBuf tab_;
+    mx_deck_tonality tab_for_{}; int16_t fir_[64] = {};
+    size_t rec_bytes_ = 0;
+};
+
+// one buffer -- count_ block records, then the walk states
+class DeckLoudness : public DeckTrackAnalysis {
+public:
+    explicit DeckLoudness(const DeckTrack& deck);
+    void analyse(const mx_deck_loudness* l);                               // NULL: frees the results.  Asynchronous on the load stream.
+    void read(uint64_t first, uint64_t n, mx_loudness_tick* dst);          // waits for the analysis
+    static void debug_last(uint32_t out[4]);
+};
 
 }  // namespace mx

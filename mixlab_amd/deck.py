@@ -67,10 +67,15 @@ def deck_plan(head: DeckHead, spt: int, n_frames: int, p: DeckParams | None = No
     return tick, out
 
 
+def _debug_last(call, keys) -> dict:
+    """the counts one mx_deck_debug_last_* call reports, under the names given"""
+    out = (C.c_uint32 * len(keys))()
+    check(call(out))
+    return dict(zip(keys, (int(v) for v in out)))
+
+
 def debug_last_feed() -> dict:
-    out = (C.c_uint32 * 6)()
-    check(lib.mx_deck_debug_last_feed(out))
-    return dict(zip(("ticks_zero", "ticks_stream", "ticks_gather", "chunks_zero", "chunks_stream", "chunks_gather"), (int(v) for v in out)))
+    return _debug_last(lib.mx_deck_debug_last_feed, ("ticks_zero", "ticks_stream", "ticks_gather", "chunks_zero", "chunks_stream", "chunks_gather"))
 
 
 def keylock(pitch_q32=ONE, hop=1024, overlap=256, radius=512) -> DeckKeylock:
@@ -92,9 +97,7 @@ def keylock_search(interleaved_i16: np.ndarray, C_frame: int, A_frame: int, over
 
 
 def debug_last_keylock() -> dict:
-    out = (C.c_uint32 * 4)()
-    check(lib.mx_deck_debug_last_keylock(out))
-    return dict(zip(("grains_searched", "grains_unsearched", "chunks_fading", "chunks_straddling"), (int(v) for v in out)))
+    return _debug_last(lib.mx_deck_debug_last_keylock, ("grains_searched", "grains_unsearched", "chunks_fading", "chunks_straddling"))
 
 
 # mx_deck_column as a numpy record: 56 bytes, the header's layout
@@ -154,9 +157,7 @@ def beatgrid(cols: np.ndarray, R: np.ndarray, column: int, rate: float, bpm_lo: 
 
 
 def debug_last_analysis() -> dict:
-    out = (C.c_uint32 * 4)()
-    check(lib.mx_deck_debug_last_analysis(out))
-    return dict(zip(("wgs_several_columns", "wgs_tiled_column", "short_track", "wgs_one_column"), (int(v) for v in out)))
+    return _debug_last(lib.mx_deck_debug_last_analysis, ("wgs_several_columns", "wgs_tiled_column", "short_track", "wgs_one_column"))
 
 
 def tonality(rate=48000.0, decim=8, hop_frames=512, octaves=5, f_lo_mhz=65406, segment_hops=64) -> DeckTonality:
@@ -188,9 +189,7 @@ def tonality_host(interleaved_i16: np.ndarray, t: DeckTonality, first: int = 0, 
 
 
 def debug_last_tonality() -> dict:
-    out = (C.c_uint32 * 4)()
-    check(lib.mx_deck_debug_last_tonality(out))
-    return dict(zip(("wgs_decimate", "wgs_cq_full", "wgs_cq_part", "wgs_head"), (int(v) for v in out)))
+    return _debug_last(lib.mx_deck_debug_last_tonality, ("wgs_decimate", "wgs_cq_full", "wgs_cq_part", "wgs_head"))
 
 
 def loudness(rate=48000.0, block_frames=4800, momentary_blocks=4, short_blocks=30) -> DeckLoudness:
@@ -219,9 +218,7 @@ def loudness_host(interleaved_i16: np.ndarray, l: DeckLoudness) -> np.ndarray:
 
 
 def debug_last_loudness() -> dict:
-    out = (C.c_uint32 * 4)()
-    check(lib.mx_deck_debug_last_loudness(out))
-    return dict(zip(("wgs_peak", "wgs_walk", "scan_steps", "wgs_window"), (int(v) for v in out)))
+    return _debug_last(lib.mx_deck_debug_last_loudness, ("wgs_peak", "wgs_walk", "scan_steps", "wgs_window"))
 
 
 def loudness_gain(recs: np.ndarray, momentary_blocks: int = 4, hop_blocks: int = 1, target_lufs: float = -14.0, ceiling_dbtp: float = -1.0):
@@ -298,9 +295,7 @@ def deck_sync(leader: DeckBeats, leader_pos_q32: int, leader_step_q32: int, foll
 
 
 def debug_last_finegrid() -> dict:
-    out = (C.c_uint32 * 4)()
-    check(lib.mx_deck_debug_last_finegrid(out))
-    return dict(zip(("wgs_one_pass", "wgs_strided", "wgs_onset", "trip"), (int(v) for v in out)))
+    return _debug_last(lib.mx_deck_debug_last_finegrid, ("wgs_one_pass", "wgs_strided", "wgs_onset", "trip"))
 
 
 _NOT_GIVEN = object()   # Deck.analyse_finegrid: no settings argument at all, as against None
@@ -312,7 +307,11 @@ class Deck:
     def __init__(self, n_frames: int, device: int = -1):
         self._h = C.c_void_p()
         self.n_frames = int(n_frames)
-        self._finegrid = None   # (n_periods, N) of the last analyse_finegrid() that succeeded: the library has no call that tells them
+        # the counts of each analysis' last analyse*() that succeeded (the library has no call that tells them); None: no results
+        self._analysis = None    # (columns, max_lag)
+        self._tonality = None    # (segments, octaves)
+        self._loudness = None    # blocks
+        self._finegrid = None    # (n_periods, hops)
         check(lib.mx_deck_create(self.n_frames, device, C.byref(self._h)))
 
     def close(self):
@@ -363,27 +362,32 @@ class Deck:
         check(lib.mx_deck_read_grains(self._h, int(first), int(n), arr))
         return list(arr[:n])
 
+    def _analyse(self, call, attr: str, settings, counts) -> None:
+        """one analyse*() call and the counts remembered of it: settings of None free the results; refused settings (MX_ERR_INVALID) leave the deck what it
+        had; anything else (no memory) leaves it without this analysis"""
+        try:
+            check(call(self._h, C.byref(settings) if settings is not None else None))
+        except abi.MxError as e:
+            if e.code != abi.MX_ERR_INVALID:
+                setattr(self, attr, None)
+            raise
+        setattr(self, attr, counts(settings) if settings is not None else None)
+
     def analyse(self, a: DeckAnalysis | None = None, **kw):
         """analyse the whole track as loaded now, asynchronously on the deck's own stream; keywords are analysis_bands()'s; analyse(None) frees the results"""
         a = a if a is not None else (analysis_bands(**kw) if kw else None)
-        try:
-            check(lib.mx_deck_analyse(self._h, C.byref(a) if a is not None else None))
-        except abi.MxError as e:
-            if e.code != abi.MX_ERR_INVALID:   # refused settings: the deck keeps what it had; anything else (no memory) leaves it without an analysis
-                self._analysis = None
-            raise
-        self._analysis = (column_count(self.n_frames, a.column), a.max_lag) if a is not None else None
+        self._analyse(lib.mx_deck_analyse, "_analysis", a, lambda a: (column_count(self.n_frames, a.column), a.max_lag))
 
     def read_columns(self, first: int = 0, n: int | None = None) -> np.ndarray:
         """COLUMN_DTYPE[n] of the analysis; waits for it"""
-        n = (self._analysis[0] - first if getattr(self, "_analysis", None) else 0) if n is None else n
+        n = (self._analysis[0] - first if self._analysis else 0) if n is None else n
         cols = np.zeros(max(1, n), COLUMN_DTYPE)
         check(lib.mx_deck_read_columns(self._h, int(first), int(n), cols.ctypes.data_as(C.c_void_p)))
         return cols[:n]
 
     def read_autocorr(self, cap: int | None = None) -> np.ndarray:
         """R as uint64[max_lag] of the analysis; waits for it.  cap is the room offered to the library (by default max_lag): the library fills max_lag of it"""
-        lag = self._analysis[1] if getattr(self, "_analysis", None) else 0   # (the settings of the last analyse() that succeeded: the library has no call that tells them)
+        lag = self._analysis[1] if self._analysis else 0
         cap = lag if cap is None else cap
         R = np.zeros(max(1, cap), np.uint64)
         check(lib.mx_deck_read_autocorr(self._h, R.ctypes.data_as(C.c_void_p), int(cap)))
@@ -392,17 +396,11 @@ class Deck:
     def analyse_tonality(self, t: DeckTonality | None = None, **kw):
         """the whole track's constant-Q sums per segment, asynchronously on the deck's own stream; keywords are tonality()'s; analyse_tonality(None) frees them"""
         t = t if t is not None else (tonality(**kw) if kw else None)
-        try:
-            check(lib.mx_deck_analyse_tonality(self._h, C.byref(t) if t is not None else None))
-        except abi.MxError as e:
-            if e.code != abi.MX_ERR_INVALID:
-                self._tonality = None
-            raise
-        self._tonality = (tonality_count(self.n_frames, t), t.octaves) if t is not None else None
+        self._analyse(lib.mx_deck_analyse_tonality, "_tonality", t, lambda t: (tonality_count(self.n_frames, t), t.octaves))
 
     def read_tonality(self, first: int = 0, n: int | None = None) -> list:
         """segments [first, first + n) of the tonality analysis as abi.parse_tonality_records dicts; waits for it"""
-        segs, octaves = getattr(self, "_tonality", None) or (0, 2)
+        segs, octaves = self._tonality or (0, 2)
         n = segs - first if n is None else n
         rb = 32 + 96 * octaves
         raw = np.zeros(max(1, n) * rb, np.uint8)
@@ -417,17 +415,11 @@ class Deck:
     def analyse_loudness(self, l: DeckLoudness | None = None, **kw):
         """the whole track's loudness records per block, asynchronously on the deck's own stream; keywords are loudness()'s; analyse_loudness(None) frees them"""
         l = l if l is not None else (loudness(**kw) if kw else None)
-        try:
-            check(lib.mx_deck_analyse_loudness(self._h, C.byref(l) if l is not None else None))
-        except abi.MxError as e:
-            if e.code != abi.MX_ERR_INVALID:
-                self._loudness = None
-            raise
-        self._loudness = loudness_count(self.n_frames, l.block_frames) if l is not None else None
+        self._analyse(lib.mx_deck_analyse_loudness, "_loudness", l, lambda l: loudness_count(self.n_frames, l.block_frames))
 
     def read_loudness(self, first: int = 0, n: int | None = None) -> np.ndarray:
         """abi.LOUDNESS_TICK_DTYPE[n] of the loudness analysis; waits for it"""
-        n = ((getattr(self, "_loudness", None) or 0) - first) if n is None else n
+        n = ((self._loudness or 0) - first) if n is None else n
         out = np.zeros(max(1, n), abi.LOUDNESS_TICK_DTYPE)
         check(lib.mx_deck_read_loudness(self._h, int(first), int(n), out.ctypes.data_as(C.c_void_p)))
         return out[:n]
@@ -440,13 +432,7 @@ class Deck:
             raise TypeError("analyse_finegrid takes settings (None frees the result) or finegrid()'s keywords, one of the two")
         if s is _NOT_GIVEN:
             s = finegrid(**kw)
-        try:
-            check(lib.mx_deck_analyse_finegrid(self._h, C.byref(s) if s is not None else None))
-        except abi.MxError as e:
-            if e.code != abi.MX_ERR_INVALID:
-                self._finegrid = None
-            raise
-        self._finegrid = (s.n_periods, finegrid_count(self.n_frames, s.hop)) if s is not None else None
+        self._analyse(lib.mx_deck_analyse_finegrid, "_finegrid", s, lambda s: (s.n_periods, finegrid_count(self.n_frames, s.hop)))
 
     def read_finegrid(self, first: int = 0, n: int | None = None) -> np.ndarray:
         """abi.DECK_COMB_DTYPE[n] of the fine grid, one record per candidate period; waits for it"""

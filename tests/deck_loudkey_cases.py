@@ -116,9 +116,9 @@ def _ton_floats(case, tr, frames, mis):
     return x.astype(np.float32) / np.float32(32768.0)
 
 
-def ton_records(case, mis=None) -> list:
-    """the records as bytes, one per segment, from the taps' model"""
-    tr = track(case)
+def ton_records(case, mis=None, tr=None) -> list:
+    """the records as bytes, one per segment, from the taps' model; tr: another track of case.n_frames than the case's own"""
+    tr = track(case) if tr is None else tr
     F, n_seg = case.G * case.Hc * case.D, ton_segments(case)
     hop = case.Hc * case.D
     # every hop whose kernels can see a frame of the track: the FIR reaches 8 D - 1 frames back and the longest kernel 2047 decimated frames; behind that q, d, S and
@@ -178,8 +178,9 @@ def loud_forms(case) -> dict:
     return {"wgs_peak": -(-n * case.F // 1024), "wgs_walk": -(-n // 32), "scan_steps": n, "wgs_window": -(-n // 256)}
 
 
-def loud_records(case, mis=None) -> np.ndarray:
-    tr, n = track(case), loud_blocks(case)
+def loud_records(case, mis=None, tr=None) -> np.ndarray:
+    """... from the taps' model; tr: another track of case.n_frames than the case's own"""
+    tr, n = track(case) if tr is None else tr, loud_blocks(case)
     x = padded(tr, n * case.F).astype(np.float32) / np.float32(32767.0 if mis == "over_32767" else 32768.0)
     m = lm.LoudnessModel(2, case.rate, case.F, case.M, case.S)
     if mis in ("run_in_not_carried", "history_cut_at_m"):   # block by block (the model's records do not depend on the grouping), forgetting in between
