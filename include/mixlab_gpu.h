@@ -54,7 +54,9 @@ extern "C" {
                               *    mx_deck_read_loudness, mx_deck_loudness_host, mx_deck_debug_last_loudness, mx_deck_loudness_gain, mx_tonality_camelot;
                               *    mx_deck_finegrid, mx_deck_comb, mx_deck_beats, mx_deck_fine_pick, mx_deck_sync_result, mx_deck_finegrid_check, mx_deck_finegrid_count,
                               *    mx_deck_finegrid_span, mx_deck_analyse_finegrid, mx_deck_read_finegrid, mx_deck_read_fine_onsets, mx_deck_finegrid_host,
-                              *    mx_deck_finegrid_pick, mx_deck_finegrid_period, mx_deck_sync, mx_deck_debug_last_finegrid */
+                              *    mx_deck_finegrid_pick, mx_deck_finegrid_period, mx_deck_sync, mx_deck_debug_last_finegrid;
+                              *    mx_deck_echo, mx_deck_set_echo, mx_deck_schedule_echo, mx_deck_echo_check, mx_deck_echo_delay, mx_deck_echo_state, mx_deck_echo_plan,
+                              *    mx_deck_debug_last_echo */
 
 /* ---- status codes (0 ok, <0 error; cf. MIXLAB_IOCTX_ERROR / MIXLAB_IOCTX_PANIC) ---- */
 enum {
@@ -951,6 +953,67 @@ int mx_deck_read_grains(mx_deck* d, uint32_t first, uint32_t n, mx_deck_grain* d
  * mx_deck_debug_last_feed counts the plain decks of the feed only. */
 int mx_deck_debug_last_keylock(uint32_t out[4]);
 
+/* ---- ECHO: a beat-synced feedback delay behind the deck, with echo-out ----
+ * BUILD-SPECIFIED.  An optional pass of a deck, set by mx_deck_set_echo / mx_deck_schedule_echo: a recursive delay line per deck that runs in place on what the deck
+ * wrote into its SOURCE_STEREO node's port, by the plain deck's rule or by key-lock's -- the echo does not look at how those samples were made.  The head, the tick
+ * records and the grains are what they were.  A deck that never sets an echo is untouched in every respect, and a feed in which no deck has an echo launches nothing new.
+ *
+ * SETTINGS   mx_deck_echo: MX_DECK_ECHO_MIN_DELAY <= delay <= MX_DECK_ECHO_MAX_DELAY output frames (mx_deck_echo_delay turns a beat fraction into one); send, feedback,
+ *            wet and damp finite, |send| <= 1, |feedback| <= 1, |wet| <= 4, 0 <= damp <= 1; no flag bit other than MX_DECK_ECHO_PINGPONG.
+ * CLOCK      a deck with an echo counts EVERY output frame it is fed in t: playing ticks, ticks written as zeros (not playing), BEFORE / PAST ticks.  That is how a
+ *            stopped deck rings out.  The delay line r_c[s], one per channel c, holds what PER FRAME wrote at clock s.  t = 0 and an all-zero line (r_c[s] = 0 for
+ *            every s < 0) hold at the first tick that runs with an echo after creation or after a tick without one: off -> on starts clean.  Nothing else restarts
+ *            the clock or clears the line: not a seek, a load, a change of step or of PLAY, a change of settings (a change of delay included: the new delay reads the
+ *            line the old one wrote), mx_deck_set_keylock, a feed into another graph handle, nor a graph that adopted another's state.  All of this the host can compute.
+ * PER FRAME  x_c[t] is the f32 the deck wrote for channel c (0 = L, 1 = R) at the frame with clock t.  c' is the other channel under MX_DECK_ECHO_PINGPONG, else c.
+ *            D is the tick's delay, s = t - D.  Every multiply and add is a separate f64 operation, never fused, in this order:
+ *                a = (double)damp * 0.25;   b = 1.0 - (a + a)                                              (per setting)
+ *                f_c = b * (double)r_c'[s] + a * (double)r_c'[s - 1] + a * (double)r_c'[s + 1]             (left to right: ((b r) + (a r)) + (a r); with damp = 0, r_c'[s])
+ *                r_c[t] = (float)((double)send_n * (double)x_c[t] + (double)fb_n * f_c)
+ *                y_c[t] = (float)((double)x_c[t] + (double)wet_n * f_c)
+ *            y replaces x in the port.  Subnormal f32 values are kept, not flushed (numpy's casts are the model).  MX_FLAG_FP_CONTRACT does not apply.  s + 1 <= t - 255:
+ *            a frame never reads what it or a later frame writes.
+ * RAMPS      send, feedback and wet never jump inside the sound.  In the tick at which a setting takes effect (any mx_deck_set_echo / mx_deck_schedule_echo with
+ *            settings, also one that repeats them), frame n of the tick, n = 0 .. spt - 1, uses for each of the three
+ *                g_n = (float)((double)old + ((double)new - (double)old) * ((double)n / (double)spt))
+ *            with `old` the value of the tick before (0 in the first tick after off -> on); every other tick uses `new` as it stands.  delay, damp and the flag
+ *            switch at the tick's first frame.
+ * SCHEDULE   mx_deck_set_echo applies from tick 0 of the next feed, mx_deck_schedule_echo from the tick named; NULL settings turn the echo off from that tick.  The
+ *            rules are mx_deck_schedule's: a later call for the same tick replaces an earlier one, the feed clears the schedule, a feed that does not reach a
+ *            scheduled tick fails with MX_ERR_INVALID and drops the schedule (the deck's own too) -- the setting in force, the clock and the line stay.
+ * IT FOLLOWS that the result does not depend on how ticks are grouped into feeds; that with wet = 0 the port holds the deck's own samples; that with send = 0,
+ *            feedback = 1, damp = 0 the line recirculates bit for bit for ever (the freeze; f_c = r_c'[s] then as a number, a -0 may come back as +0); that without
+ *            PINGPONG the two channels never meet; and that a deck whose PLAY flag is cleared keeps sounding its tail (the echo-out).
+ * BLOCKS     (how the device runs it; mx_deck_echo_plan restates it.)  Frame t reads the line no later than t - D + 1, so the frames of a block [t0, t0 + B) are
+ *            independent of one another when t - D(t) + 1 < t0 for every frame of it; with one delay, B <= D - 1.  A deck's echo frames of a feed are cut greedily
+ *            into maximal such blocks, a tick without an echo always ending one; the cut holds across a tick that lowers the delay.
+ * Out of scope: delays under 256 frames (flanger, chorus), modulated or interpolated delay, a resonant sweep filter, reverb, the echo on ports other than a deck's
+ * source, more than two channels.
+ */
+#define MX_DECK_ECHO_PINGPONG 1u
+#define MX_DECK_ECHO_MIN_DELAY 256u
+#define MX_DECK_ECHO_MAX_DELAY 262144u      /* 5.4 s at 48 kHz */
+typedef struct { uint32_t delay; uint32_t flags; float send; float feedback; float wet; float damp; } mx_deck_echo;   /* 24 bytes */
+/* The echo with these settings from tick 0 of the NEXT feed on; NULL: off from that tick.  mx_deck_schedule_echo(d, 0, e).  The first call with settings allocates the
+ * deck's delay line (2^19 frames, 4 MB).  Settings that mx_deck_echo_check refuses: MX_ERR_INVALID, and the deck and its schedule keep what they had. */
+int mx_deck_set_echo(mx_deck* d, const mx_deck_echo* e);
+/* ... from tick `tick_in_feed` of the next feed on (SCHEDULE). */
+int mx_deck_schedule_echo(mx_deck* d, uint32_t tick_in_feed, const mx_deck_echo* e);
+/* Host only: the SETTINGS rules alone. */
+int mx_deck_echo_check(const mx_deck_echo* e);
+/* mx_deck_echo_delay (host only: the delay of num / den beats) is declared below mx_deck_sync, with the mx_deck_beats it reads. */
+/* After the last feed: the clock t, whether the echo is on (1 / 0), and the setting in force (the last one it had, when off; all zero before the first).  Host data: no
+ * synchronisation. */
+int mx_deck_echo_state(const mx_deck* d, uint64_t* t, uint32_t* on, mx_deck_echo* setting);
+/* Host only, pure: BLOCKS for a feed of n_ticks ticks of spt frames, delay[k] the delay of tick k or 0 for a tick without an echo: block j is blocks[2 j] (its first
+ * frame, counted from the feed's first) and blocks[2 j + 1] (its frames), for j < min(*n_blocks, cap); *n_blocks is the number of blocks whatever cap is.  spt outside
+ * 1 .. MX_DECK_MAX_SPT, a delay that is neither 0 nor within MIN .. MAX, a NULL pointer: MX_ERR_INVALID. */
+int mx_deck_echo_plan(uint32_t spt, const uint32_t* delay, uint32_t n_ticks, uint64_t* blocks, uint32_t cap, uint32_t* n_blocks);
+/* DEBUG: the decks with an echo in any tick of the last mx_deck_feed of this process: out[0] decks rendered in the one-block form (the deck's echo frames of the feed are
+ * a single block: a lane per frame, no barrier), out[1] decks in the sequential form (one workgroup walks the deck's blocks in order), out[2] the blocks those walked,
+ * out[3] those of them that cross a tick boundary.  All zero for a feed in which no deck has an echo. */
+int mx_deck_debug_last_echo(uint32_t out[4]);
+
 /* ---- ANALYSIS: the band waveform overview, the onset autocorrelation and the beat grid of a whole track, before it sounds ----
  * BUILD-SPECIFIED.  One pass over the track as it lies in device memory, on the deck's own load stream: what a host needs at load time -- the coloured overview
  * (low / mid / high per column), the tempo, and where the beats are.  Everything up to the read-out of the beat grid is integer arithmetic, so no order of accumulation
@@ -1182,6 +1245,10 @@ int mx_deck_finegrid_pick(const mx_deck_comb* recs, const mx_deck_finegrid* s, d
 /* Host only, pure, exact: SYNC. */
 int mx_deck_sync(const mx_deck_beats* leader, int64_t leader_pos_q32, int64_t leader_step_q32, const mx_deck_beats* follower, int64_t follower_pos_q32,
                  mx_deck_sync_result* out);
+/* Host only, pure, exact (ECHO above): *delay = the integer nearest to period_q32 * num / (|step_q32| * den), the output frames of num / den beats of `grid` at this
+ * step, in 128-bit integers with ties to even: 3/4 beat of 126.4 BPM at 48 kHz and unity is 17 089.  step, num or den 0, a grid without a positive period, a result
+ * outside MX_DECK_ECHO_MIN_DELAY .. MX_DECK_ECHO_MAX_DELAY, NULL: MX_ERR_INVALID. */
+int mx_deck_echo_delay(const mx_deck_beats* grid, int64_t step_q32, uint32_t num, uint32_t den, uint32_t* delay);
 /* DEBUG: what the last mx_deck_analyse_finegrid of this process launched: out[0] comb workgroups (one per candidate, MX_DECK_FINEGRID_LANES lanes) whose phases fit one
  * pass of the lanes, out[1] comb workgroups that looped over the phases in strides, out[2] onset workgroups (256 lanes; 256 hops of w each), out[3] the trip count of
  * the comb kernel's loop over k (the teeth of phase 0 at the smallest period, or max_beats).  Tests use it to know every form ran. */

@@ -473,6 +473,18 @@ _proto("mx_deck_finegrid_host", C.c_int, C.c_void_p, C.c_uint64, C.POINTER(DeckF
 _proto("mx_deck_finegrid_pick", C.c_int, C.c_void_p, C.POINTER(DeckFinegrid), C.c_double, C.POINTER(DeckFinePick))
 _proto("mx_deck_sync", C.c_int, C.POINTER(DeckBeats), C.c_int64, C.c_int64, C.POINTER(DeckBeats), C.c_int64, C.POINTER(DeckSyncResult))
 _proto("mx_deck_debug_last_finegrid", C.c_int, C.POINTER(C.c_uint32))
+# ... its beat echo (the header's ECHO): a feedback delay per deck behind the feed, scheduled per tick
+DECK_ECHO_PINGPONG = 1
+DECK_ECHO_MIN_DELAY, DECK_ECHO_MAX_DELAY = 256, 262144
+class DeckEcho(C.Structure):
+    _fields_ = [("delay", C.c_uint32), ("flags", C.c_uint32), ("send", C.c_float), ("feedback", C.c_float), ("wet", C.c_float), ("damp", C.c_float)]
+_proto("mx_deck_set_echo", C.c_int, C.c_void_p, C.POINTER(DeckEcho))
+_proto("mx_deck_schedule_echo", C.c_int, C.c_void_p, C.c_uint32, C.POINTER(DeckEcho))
+_proto("mx_deck_echo_check", C.c_int, C.POINTER(DeckEcho))
+_proto("mx_deck_echo_delay", C.c_int, C.POINTER(DeckBeats), C.c_int64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32))
+_proto("mx_deck_echo_state", C.c_int, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(DeckEcho))
+_proto("mx_deck_echo_plan", C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32))
+_proto("mx_deck_debug_last_echo", C.c_int, C.POINTER(C.c_uint32))
 _proto("mx_module_create", C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p))
 _proto("mx_module_create_ex", C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(GraphOpts), C.POINTER(C.c_void_p))
 _proto("mx_module_update", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)

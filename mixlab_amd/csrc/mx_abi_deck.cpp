@@ -87,6 +87,38 @@ int mx_deck_read_grains(mx_deck* d, uint32_t first, uint32_t n, mx_deck_grain* d
 int mx_deck_debug_last_keylock(uint32_t out[4]) {
     return guard([&] { REQUIRE(out, "out is NULL"); Deck::debug_last_keylock(out); });
 }
+int mx_deck_set_echo(mx_deck* d, const mx_deck_echo* e) {
+    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.echo.schedule(0, e); });
+}
+int mx_deck_schedule_echo(mx_deck* d, uint32_t tick_in_feed, const mx_deck_echo* e) {
+    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.echo.schedule(tick_in_feed, e); });
+}
+int mx_deck_echo_check(const mx_deck_echo* e) {
+    return guard([&] { REQUIRE(e, "settings are NULL"); mx::deck_echo_check(*e); });
+}
+int mx_deck_echo_state(const mx_deck* d, uint64_t* t, uint32_t* on, mx_deck_echo* setting) {
+    return guard([&] {
+        REQUIRE(d && t && on && setting, "NULL argument");
+        const mx::DeckEcho::State& s = d->d.echo.state();
+        *t = s.t; *on = s.on ? 1u : 0u; *setting = s.set;
+    });
+}
+int mx_deck_echo_plan(uint32_t spt, const uint32_t* delay, uint32_t n_ticks, uint64_t* blocks, uint32_t cap, uint32_t* n_blocks) {
+    return guard([&] {
+        REQUIRE(n_blocks && (delay || !n_ticks) && (blocks || !cap), "NULL argument");
+        REQUIRE(spt >= 1 && spt <= MX_DECK_MAX_SPT, "frames per tick outside 1 .. MX_DECK_MAX_SPT");
+        for (uint32_t k = 0; k < n_ticks; ++k)
+            REQUIRE(!delay[k] || (delay[k] >= MX_DECK_ECHO_MIN_DELAY && delay[k] <= MX_DECK_ECHO_MAX_DELAY), "a delay that is neither 0 nor in MX_DECK_ECHO_MIN_DELAY .. MX_DECK_ECHO_MAX_DELAY");
+        std::vector<mx::EchoBlock> cut;
+        mx::deck_echo_cut(spt, delay, n_ticks, cut);
+        REQUIRE(cut.size() <= 0xffffffffu, "more than 2^32 blocks");
+        *n_blocks = (uint32_t)cut.size();
+        for (size_t k = 0; k < cut.size() && k < cap; ++k) { blocks[2 * k] = cut[k].first; blocks[2 * k + 1] = cut[k].frames; }
+    });
+}
+int mx_deck_debug_last_echo(uint32_t out[4]) {
+    return guard([&] { REQUIRE(out, "out is NULL"); mx::deck_debug_last_echo(out); });
+}
 int mx_deck_analysis_check(const mx_deck_analysis* a) {
     return guard([&] { REQUIRE(a, "settings are NULL"); mx::deck_analysis_check(*a); });
 }
@@ -210,6 +242,9 @@ int mx_deck_finegrid_pick(const mx_deck_comb* recs, const mx_deck_finegrid* s, d
 int mx_deck_sync(const mx_deck_beats* leader, int64_t leader_pos_q32, int64_t leader_step_q32, const mx_deck_beats* follower, int64_t follower_pos_q32,
                  mx_deck_sync_result* out) {
     return guard([&] { REQUIRE(leader && follower && out, "NULL argument"); mx::deck_sync(*leader, leader_pos_q32, leader_step_q32, *follower, follower_pos_q32, *out); });
+}
+int mx_deck_echo_delay(const mx_deck_beats* grid, int64_t step_q32, uint32_t num, uint32_t den, uint32_t* delay) {
+    return guard([&] { REQUIRE(grid && delay, "NULL argument"); *delay = mx::deck_echo_delay(*grid, step_q32, num, den); });
 }
 int mx_deck_debug_last_finegrid(uint32_t out[4]) {
     return guard([&] { REQUIRE(out, "out is NULL"); mx::DeckFineGrid::debug_last(out); });

@@ -1,6 +1,7 @@
 // mx_deck.cpp -- the deck's host side: parameter rules, the per-tick state machine (mx_deck_plan), the coefficient tables, the track, and the feed that turns the
 // coming ticks of many decks into one descriptor block and one launch (include/mixlab_gpu.h "the deck").  Key-lock beside the feed is
-// mx_deck_keylock.cpp's, and each whole-track analysis has a file of its own (mx_deck_analysis.hpp).
+// mx_deck_keylock.cpp's, the echo behind it mx_deck_echo.cpp's (the feed asks each deck's DeckEcho for its ticks, uploads them with its own, launches, commits),
+// and each whole-track analysis has a file of its own (mx_deck_analysis.hpp).
 #include "mx_deck.hpp"
 
 #include <algorithm>
@@ -200,6 +201,7 @@ struct FeedState {
     std::vector<DeckTickDev> last; uint32_t last_spt = 0;   // the last feed's ticks, for mx_deck_debug_last_feed
     typedef DeckKlTick KlTick;
     std::vector<KlTick> last_kl; uint32_t kl_searched = 0, kl_unsearched = 0;   // ... and its key-locked ticks and grains, for mx_deck_debug_last_keylock
+    std::vector<std::vector<uint32_t>> last_echo;                                // ... and per deck with an echo the delays of its ticks, for mx_deck_debug_last_echo
 } feed_state;
 }  // namespace
 
@@ -217,7 +219,7 @@ void deck_stream_retired(hipStream_t s) {
 }
 
 void Deck::feed(Deck* const* decks, const uint32_t* nodes, size_t n, Graph& g, uint32_t n_ticks) {
-    auto drop = [&] { for (size_t i = 0; i < n; ++i) if (decks && decks[i]) decks[i]->sched_.clear(); };
+    auto drop = [&] { for (size_t i = 0; i < n; ++i) if (decks && decks[i]) { decks[i]->sched_.clear(); decks[i]->echo.drop_schedule(); } };
     try {
         if (!n) return;
         if (!decks || !nodes) throw Error(MX_ERR_INVALID, "deck feed: decks / nodes is NULL");
@@ -232,6 +234,9 @@ void Deck::feed(Deck* const* decks, const uint32_t* nodes, size_t n, Graph& g, u
             outs[i] = g.source_feed_ptr(nodes[i], (size_t)n_ticks * spt);
             for (const Event& e : decks[i]->sched_)
                 if (e.tick >= n_ticks) throw Error(MX_ERR_INVALID, "deck feed: deck " + std::to_string(i) + " has an event scheduled at tick " + std::to_string(e.tick) + ", beyond this feed");
+            uint32_t beyond = 0;
+            if (decks[i]->echo.scheduled_beyond(n_ticks, beyond))
+                throw Error(MX_ERR_INVALID, "deck feed: deck " + std::to_string(i) + " has an echo scheduled at tick " + std::to_string(beyond) + ", beyond this feed");
         }
         {
             std::vector<const Deck*> d(decks, decks + n); std::vector<uint32_t> nd(nodes, nodes + n);
@@ -241,6 +246,21 @@ void Deck::feed(Deck* const* decks, const uint32_t* nodes, size_t n, Graph& g, u
         }
         hip_check(hipSetDevice(g.device()), "hipSetDevice");
         const float* tables = deck_tables_device(g.device());
+        // the echo of every deck over the coming ticks (host state only): echoes[] names the decks with an echo in any tick, those of the one-block form first
+        struct EchoPlan { size_t deck; std::vector<EchoTickDev> ticks; std::vector<uint32_t> delays; bool one_block; };
+        std::vector<EchoPlan> echoes;
+        std::vector<DeckEcho::State> echo_after(n);
+        for (size_t i = 0; i < n; ++i) {
+            std::vector<EchoTickDev> et;
+            if (!decks[i]->echo.plan(n_ticks, (uint32_t)spt, et, echo_after[i])) continue;
+            std::vector<uint32_t> dl(n_ticks);
+            for (uint32_t t = 0; t < n_ticks; ++t) dl[t] = echo_delay_of(et[t]);
+            const bool one = deck_echo_one_block((uint32_t)spt, dl.data(), n_ticks);
+            echoes.push_back(EchoPlan{i, std::move(et), std::move(dl), one});
+        }
+        std::stable_partition(echoes.begin(), echoes.end(), [](const EchoPlan& e) { return e.one_block; });
+        const size_t ne = echoes.size(), ne_block = (size_t)std::count_if(echoes.begin(), echoes.end(), [](const EchoPlan& e) { return e.one_block; });
+        const size_t echo_bytes = ne * sizeof(EchoDeckDev) + ne * (size_t)n_ticks * sizeof(EchoTickDev);
 
         std::lock_guard<std::mutex> lock(feed_state.mu);
         Slot& sl = feed_state.slots[feed_state.next];
@@ -250,8 +270,9 @@ void Deck::feed(Deck* const* decks, const uint32_t* nodes, size_t n, Graph& g, u
         for (size_t i = 0; i < n; ++i)
             if (decks[i]->keylock_.on) { ++nk; grain_cap += (size_t)n_ticks * (spt / decks[i]->keylock_.k.hop + 1); }
         const size_t head_bytes = (n * sizeof(DeckDev) + 15) & ~(size_t)15, plain_bytes = (head_bytes + n * (size_t)n_ticks * sizeof(DeckTickDev) + 15) & ~(size_t)15;
-        const size_t bytes = nk ? plain_bytes + nk * sizeof(KlDeckDev) + nk * (size_t)n_ticks * sizeof(KlTickDev) + grain_cap * sizeof(KlGrainIn)
-                                : head_bytes + n * (size_t)n_ticks * sizeof(DeckTickDev);
+        const size_t feed_bytes = nk ? plain_bytes + nk * sizeof(KlDeckDev) + nk * (size_t)n_ticks * sizeof(KlTickDev) + grain_cap * sizeof(KlGrainIn)
+                                     : head_bytes + n * (size_t)n_ticks * sizeof(DeckTickDev);
+        const size_t bytes = ne ? ((feed_bytes + 15) & ~(size_t)15) + echo_bytes : feed_bytes;   // (the echo's descriptors lie behind what the two feed kernels read)
         if (sl.host_cap < bytes) {
             if (sl.host) (void)hipHostFree(sl.host);
             sl.host = nullptr; sl.host_cap = 0;
@@ -337,17 +358,33 @@ void Deck::feed(Deck* const* decks, const uint32_t* nodes, size_t n, Graph& g, u
         }
         for (size_t i = 0; i < n; ++i)
             if (decks[i]->load_pending_) { hip_check(hipStreamWaitEvent(g.stream(), decks[i]->loaded_, 0), "hipStreamWaitEvent"); decks[i]->load_pending_ = false; }
-        launch_upload(sl.dev.p, sl.host, nk ? (size_t)((const char*)(kg + grain_at) - (const char*)sl.host) : bytes, g.stream());
+        const size_t feed_used = nk ? (size_t)((const char*)(kg + grain_at) - (const char*)sl.host) : feed_bytes, echo_at = (feed_used + 15) & ~(size_t)15;
+        if (ne) {
+            EchoDeckDev* ed = (EchoDeckDev*)((char*)sl.host + echo_at);
+            EchoTickDev* et = (EchoTickDev*)(ed + ne);
+            for (size_t k = 0; k < ne; ++k) {
+                Deck& d = *decks[echoes[k].deck];
+                if (d.echo.last_graph && d.echo.last_graph != &g) hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");   // (its line may still be in use on the other graph's stream)
+                ed[k] = EchoDeckDev{(float2*)outs[echoes[k].deck], d.echo.line()};
+                std::copy(echoes[k].ticks.begin(), echoes[k].ticks.end(), et + k * (size_t)n_ticks);
+            }
+        }
+        launch_upload(sl.dev.p, sl.host, ne ? echo_at + echo_bytes : feed_used, g.stream());
         launch_deck_feed((const DeckDev*)sl.dev.p, (const DeckTickDev*)((const char*)sl.dev.p + head_bytes), tables, (uint32_t)ip, n_ticks, (uint32_t)spt, phase_varies, g.stream());
         launch_deck_keylock((const KlDeckDev*)((const char*)sl.dev.p + plain_bytes), (const KlTickDev*)((const char*)sl.dev.p + plain_bytes + nk * sizeof(KlDeckDev)), tables,
                             (uint32_t)nk, n_ticks, (uint32_t)spt, g.stream());
+        if (ne) launch_deck_echo((const EchoDeckDev*)((const char*)sl.dev.p + echo_at), (const EchoTickDev*)((const char*)sl.dev.p + echo_at + ne * sizeof(EchoDeckDev)),
+                                 (uint32_t)ne_block, (uint32_t)(ne - ne_block), n_ticks, (uint32_t)spt, g.stream());
         hip_check(hipGetLastError(), "deck feed launch");
         hip_check(hipEventRecord(sl.done, g.stream()), "hipEventRecord");
         sl.pending = true; sl.stream = g.stream();
         feed_state.last.assign(td, td + ip * (size_t)n_ticks); feed_state.last_spt = (uint32_t)spt;
         feed_state.last_kl.clear(); feed_state.kl_searched = feed_state.kl_unsearched = 0;
+        feed_state.last_echo.clear();
+        for (EchoPlan& e : echoes) { decks[e.deck]->echo.last_graph = &g; feed_state.last_echo.push_back(std::move(e.delays)); }
         for (size_t i = 0, k = 0; i < n; ++i) {
             Deck& d = *decks[i];
+            d.echo.commit(echo_after[i]);
             d.head_ = heads[i]; d.ticks_ = std::move(recs[i]); d.sched_.clear(); d.keylock_.last_graph = &g; d.keylock_.last_lineage = g.lineage();
             if (!d.keylock_.on) { d.keylock_.grains.clear(); d.keylock_.grains_fetched = true; continue; }
             for (const mx_deck_grain& gr : grains[k]) ++((gr.flags & MX_DECK_GRAIN_FIRST) || !d.keylock_.k.radius ? feed_state.kl_unsearched : feed_state.kl_searched);
@@ -361,6 +398,11 @@ void Deck::feed(Deck* const* decks, const uint32_t* nodes, size_t n, Graph& g, u
 DeckLastKeylock deck_last_keylock() {
     std::lock_guard<std::mutex> lock(feed_state.mu);
     return DeckLastKeylock{feed_state.last_kl, feed_state.last_spt, feed_state.kl_searched, feed_state.kl_unsearched};
+}
+
+DeckLastEcho deck_last_echo() {
+    std::lock_guard<std::mutex> lock(feed_state.mu);
+    return DeckLastEcho{feed_state.last_echo, feed_state.last_spt};
 }
 
 void Deck::debug_last_feed(uint32_t out[6]) {

@@ -19,6 +19,11 @@ The fine grid (the header's FINE GRID) turns that read-out into beats good to a 
     beats = deck.refine_grid(grid, 512, 44100.0).grid                     # first_q32, period_q32: beat n lies at first + n * period
     step, seek, _ = deck_sync(leader_beats, leader.state().pos_q32, leader.state().step_q32, beats, deck.state().pos_q32)
     deck.schedule(0, params(step_q32=step, flags=abi.DECK_PLAY), seek)    # the follower's beats now fall on the leader's, and stay there
+
+The echo (the header's ECHO) is a feedback delay behind the deck, timed in beats; stopping the deck under it is the echo-out:
+
+    deck.set_echo(delay=deck.echo_delay(beats, 3, 4), feedback=0.6)       # a 3/4-beat echo from the next feed on
+    deck.schedule(k, params(flags=0))                                     # PLAY cleared at tick k: the tail rings over the incoming track
 """
 from __future__ import annotations
 
@@ -27,7 +32,7 @@ import ctypes as C
 import numpy as np
 
 from . import abi
-from .abi import (DeckAnalysis, DeckBeats, DeckFinegrid, DeckFinePick, DeckGrain, DeckGrid, DeckHead, DeckKeylock, DeckLoudness, DeckParams, DeckSyncResult, DeckTick,
+from .abi import (DeckAnalysis, DeckBeats, DeckEcho, DeckFinegrid, DeckFinePick, DeckGrain, DeckGrid, DeckHead, DeckKeylock, DeckLoudness, DeckParams, DeckSyncResult, DeckTick,
                   DeckTonality, check, lib)
 
 ONE = 1 << 32   # unity step / one track frame in Q32.32
@@ -298,6 +303,37 @@ def debug_last_finegrid() -> dict:
     return _debug_last(lib.mx_deck_debug_last_finegrid, ("wgs_one_pass", "wgs_strided", "wgs_onset", "trip"))
 
 
+def echo(delay, send=1.0, feedback=0.5, wet=1.0, damp=0.0, pingpong=False) -> DeckEcho:
+    """echo settings (the header's ECHO): delay in output frames (echo_delay() turns a beat fraction into one), the three gains, the damping, ping-pong"""
+    return DeckEcho(int(delay), abi.DECK_ECHO_PINGPONG if pingpong else 0, float(send), float(feedback), float(wet), float(damp))
+
+
+def echo_check(e: DeckEcho) -> None:
+    """the echo setting rules alone (host only); raises MxError"""
+    check(lib.mx_deck_echo_check(C.byref(e)))
+
+
+def echo_delay(grid: DeckBeats, step_q32: int, num: int, den: int) -> int:
+    """the output frames of num / den beats of `grid` at this step, exactly, ties to even (mx_deck_echo_delay, host only, pure)"""
+    out = C.c_uint32()
+    check(lib.mx_deck_echo_delay(C.byref(grid), int(step_q32), int(num), int(den), C.byref(out)))
+    return out.value
+
+
+def echo_plan(spt: int, delays) -> list:
+    """the blocks the echo kernel cuts a feed into, as (first frame, frames) (mx_deck_echo_plan, host only, pure); delays: one per tick, 0 for a tick without an echo"""
+    d = np.ascontiguousarray(delays, dtype=np.uint32)
+    n = C.c_uint32()
+    check(lib.mx_deck_echo_plan(int(spt), d.ctypes.data_as(C.c_void_p) if d.size else None, d.size, None, 0, C.byref(n)))
+    out = np.zeros((max(1, n.value), 2), np.uint64)
+    check(lib.mx_deck_echo_plan(int(spt), d.ctypes.data_as(C.c_void_p) if d.size else None, d.size, out.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
+    return [(int(a), int(b)) for a, b in out[:n.value]]
+
+
+def debug_last_echo() -> dict:
+    return _debug_last(lib.mx_deck_debug_last_echo, ("decks_one_block", "decks_sequential", "blocks", "blocks_crossing"))
+
+
 _NOT_GIVEN = object()   # Deck.analyse_finegrid: no settings argument at all, as against None
 
 
@@ -361,6 +397,26 @@ class Deck:
         arr = (DeckGrain * max(1, n))()
         check(lib.mx_deck_read_grains(self._h, int(first), int(n), arr))
         return list(arr[:n])
+
+    def set_echo(self, e: DeckEcho | None = None, **kw):
+        """the echo from tick 0 of the next feed on; keywords are echo()'s; set_echo(None) with no keywords turns it off"""
+        e = e if e is not None else (echo(**kw) if kw else None)
+        check(lib.mx_deck_set_echo(self._h, C.byref(e) if e is not None else None))
+
+    def schedule_echo(self, tick_in_feed: int, e: DeckEcho | None = None, **kw):
+        """... from that tick of the next feed on (the echo-out lands on a beat inside a long feed); None with no keywords turns it off there"""
+        e = e if e is not None else (echo(**kw) if kw else None)
+        check(lib.mx_deck_schedule_echo(self._h, int(tick_in_feed), C.byref(e) if e is not None else None))
+
+    def echo_delay(self, grid: DeckBeats, num: int, den: int) -> int:
+        """the delay of num / den beats of `grid` at the step the head moves at now (after the last feed)"""
+        return echo_delay(grid, self.state().step_q32, num, den)
+
+    def echo_state(self):
+        """(clock t, on, DeckEcho in force) after the last feed; host data, no synchronisation"""
+        t, on, e = C.c_uint64(), C.c_uint32(), DeckEcho()
+        check(lib.mx_deck_echo_state(self._h, C.byref(t), C.byref(on), C.byref(e)))
+        return t.value, bool(on.value), e
 
     def _analyse(self, call, attr: str, settings, counts) -> None:
         """one analyse*() call and the counts remembered of it: settings of None free the results; refused settings (MX_ERR_INVALID) leave the deck what it
