@@ -56,7 +56,9 @@ extern "C" {
                               *    mx_deck_finegrid_span, mx_deck_analyse_finegrid, mx_deck_read_finegrid, mx_deck_read_fine_onsets, mx_deck_finegrid_host,
                               *    mx_deck_finegrid_pick, mx_deck_finegrid_period, mx_deck_sync, mx_deck_debug_last_finegrid;
                               *    mx_deck_echo, mx_deck_set_echo, mx_deck_schedule_echo, mx_deck_echo_check, mx_deck_echo_delay, mx_deck_echo_state, mx_deck_echo_plan,
-                              *    mx_deck_debug_last_echo */
+                              *    mx_deck_debug_last_echo;
+                              *    mx_deck_bars, mx_deck_beat, mx_deck_bar_pick, mx_deck_bars_check, mx_deck_bars_count, mx_deck_bars_tables, mx_deck_analyse_bars,
+                              *    mx_deck_read_bars, mx_deck_read_bar_folds, mx_deck_bars_host, mx_deck_bars_pick, mx_deck_grid_next, mx_deck_debug_last_bars */
 
 /* ---- status codes (0 ok, <0 error; cf. MIXLAB_IOCTX_ERROR / MIXLAB_IOCTX_PANIC) ---- */
 enum {
@@ -1042,7 +1044,7 @@ int mx_deck_debug_last_echo(uint32_t out[4]);
  *            w_k = 0.5 - 0.5 cos(2 pi (k + 1) / (K + 1)), evaluated in f64 for k <= D and mirrored; each tap the nearest integer of 16384 g_k / sum g; the centre tap then
  *            adjusted so that sum c = 16384 exactly: DC passes at gain 1, and a constant track has mid = high = 0 away from its ends.
  * Out of scope: gated-loudness (LUFS) auto-gain and whole-track key (the columns' e and peaks serve a plain gain; key can follow on the same pass); tempo that changes
- * within a track, downbeat / bar detection; analysis of a range instead of the whole track; more than two channels; any change to how a deck plays. */
+ * within a track; downbeat / bar detection (BARS below has it); analysis of a range instead of the whole track; more than two channels; any change to how a deck plays. */
 typedef struct { uint32_t column; uint32_t taps; uint32_t max_lag; uint32_t _pad; int16_t lo[127]; int16_t hi[127]; } mx_deck_analysis;
 typedef struct { int32_t smin, smax; uint32_t peak[3]; uint32_t onset; uint64_t energy[3]; uint64_t e; } mx_deck_column;
 typedef struct { double bpm, period_columns, confidence; uint64_t first_beat_frame; uint32_t lag, phase_column; } mx_deck_grid;
@@ -1208,7 +1210,7 @@ int mx_tonality_camelot(int key, uint32_t* number, uint32_t* minor);
  *                delta = b - c, then Pf added or subtracted until it lies in (-Pf / 2, Pf / 2],   seek = follower_pos + delta
  *            The host hands step and seek to mx_deck_schedule for that tick.  A period outside [1, 2^56], a position or first beat beyond 2^62 in magnitude: MX_ERR_INVALID.
  * Out of scope: a key-locked leader or follower (under KEY-LOCK the head still crosses the track as mx_deck_plan says, so the arithmetic holds for the head; what the
- * grains make audible of it is KEY-LOCK's business, and nothing here refuses such a deck); tempo that changes within a track; downbeats and bars; phases finer than a
+ * grains make audible of it is KEY-LOCK's business, and nothing here refuses such a deck); tempo that changes within a track; downbeats and bars (BARS below); phases finer than a
  * hop; a search over a range of the track other than "from first_hop on". */
 #define MX_DECK_FINEGRID_LANES 256u       /* phases one pass of a comb workgroup covers (a lane per phase); tests size their candidates around it */
 #define MX_DECK_FINEGRID_MAX_PERIODS 8192u
@@ -1253,6 +1255,85 @@ int mx_deck_echo_delay(const mx_deck_beats* grid, int64_t step_q32, uint32_t num
  * pass of the lanes, out[1] comb workgroups that looped over the phases in strides, out[2] onset workgroups (256 lanes; 256 hops of w each), out[3] the trip count of
  * the comb kernel's loop over k (the teeth of phase 0 at the smallest period, or max_beats).  Tests use it to know every form ran. */
 int mx_deck_debug_last_finegrid(uint32_t out[4]);
+
+/* ---- BARS: downbeats and phrase lines of a whole track from the novelty of its beats, on the device ----
+ * BUILD-SPECIFIED.  The fine grid knows every beat and nothing above a beat.  This section finds which beat is a bar's first and which bar a phrase's first, by the rule
+ * "arrangements change on bar lines, and most of all on phrase lines": per beat of a given grid a small band-energy vector, a checkerboard novelty over the beats'
+ * pairwise distances at a bar-sized and at a phrase-sized width, and both novelties folded by beat index modulo the bar and modulo the phrase.  A fifth analysis on the
+ * deck's own load stream with the ownership rules of the other four and independent of their results; integers throughout, so the records are fixed count for count.
+ * A deck that never calls it is untouched in every respect, and mx_deck_analyse*, mx_deck_sync and mx_deck_echo_delay are what they were.
+ *
+ * SETTINGS   mx_deck_bars: grid the beats (FINE GRID's mx_deck_beats), period_q32 in [2048 * 2^32, 2^17 * 2^32] -- a half-beat is then at least 1024 frames, and a
+ *            half-beat's band energy (band^2 <= 2^36 over at most 2^16 frames) stays below 2^53, tempo_root's domain -- and |first_q32| <= 2^62; lead 0 .. 4096
+ *            frames; taps K odd, 1 .. 127; beats_per_bar M 2 .. 8; bars_per_phrase Q 1 .. 16; w_bar and w_phrase 1 .. 64 beats; max_beats (0: all); lo[0 .. K) and
+ *            hi[0 .. K) under ANALYSIS' rules exactly (Q14, sum |c_k| <= 32767, entries at index K and above 0).  The struct has no hole and no padding field (552
+ *            bytes).  mx_deck_bars_tables copies taps, lo and hi from an mx_deck_analysis that mx_deck_analysis_bands filled.  mx_deck_bars_check enforces exactly
+ *            these rules for a track of n_frames (1 .. 2^30), and refuses a grid that places no whole beat in the track, and one whose n_beats (BEATS: after
+ *            max_beats has cut it) is above MX_DECK_BARS_MAX_BEATS: a longer track is analysed over its first max_beats beats.
+ * BEATS      f(j) = ((first_q32 + j * period_q32) >> 32) - lead  (in integers that do not overflow; arithmetic shift: floor).  n0 is the smallest integer j, negative
+ *            ones included, with f(j) >= 0.  Beat k >= 0 covers the frames [f(n0 + k), f(n0 + k + 1)).  n_beats is the number of k whose beat ends at or before
+ *            n_frames (whole beats only), then cut to max_beats when that is not 0.  mx_deck_bars_count returns n_beats and n0 (host only).  lead is there because
+ *            a grid line is the centre of a tooth: the burst's first frames lie up to 1.5 fine hops before it.
+ * FEATURES   s, low, mid, high are ANALYSIS' SIGNAL, frame for frame (s zero outside the track, so the filter's halo reads zeros there).  With a, c the beat's ends
+ *            and h = a + ((c - a) >> 1), the beat's vector is v[0 .. 3) = floor(sqrt(sum band^2)) over the frames of [a, h) for low, mid, high -- the exact integer
+ *            root, tempo_root -- and v[3 .. 6) the same over [h, c).  d(i, j) = sum over the six components of |v[i][c] - v[j][c]| (below 2^30).
+ * NOVELTY    for a width W and W <= k <= n_beats - W, with P = [k - W, k) and F = [k, k + W):
+ *                N_W[k] = 2 sum_{a in P, b in F} d(a, b) - sum_{a, a' in P} d(a, a') - sum_{b, b' in F} d(b, b')
+ *            the two last sums over ORDERED pairs (each unordered pair twice; d(a, a) = 0).  N_W[k] = 0 for every other k.  The type is int64 and |N| < 2^44.  N is
+ *            never negative: per component it is W^2 times the energy distance of the two halves' values, 2 W^2 times the integral of (F_P - F_F)^2 over their
+ *            empirical distribution functions.  FOLD's clamp therefore changes nothing on the records of an analysis; it stays in the rule for a host that folds
+ *            novelties of its own making.
+ *            The record of beat k, mx_deck_beat (48 bytes): v[6], first_frame = f(n0 + k), frames = the beat's length, n_bar = N at W = w_bar, n_phrase = N at
+ *            W = w_phrase.
+ * FOLD       H_bar[m] = sum over k = m (mod M) of max(n_bar[k], 0) for m < M; H_phrase[m] = sum over k = m (mod M Q) of max(n_phrase[k], 0) for m < M Q: the clamp
+ *            per beat, before the sum.  uint64, M + M Q words (136 at the most), H_bar first; in device memory they lie behind the room for the records.
+ * PICK       mx_deck_bars_pick, host only, pure and exact.  The bar phase mb is the smallest m of the largest H_bar; the phrase phase mp is, among the m = mb (mod M),
+ *            the smallest of the largest H_phrase.  mx_deck_bar_pick (72 bytes): bars = { first_q32 + (n0 + mb) * period_q32, M * period_q32 }; phrases the same
+ *            with mp and M Q (at most 2^56, mx_deck_sync's bound); bar_phase = mb, phrase_phase = mp; bar_best = H_bar[mb], bar_sum = sum of H_bar,
+ *            phrase_best = H_phrase[mp], phrase_sum = the sum of H_phrase over the m = mb (mod M).  Confidence is best / sum, left to the caller.  With
+ *            bar_sum = 0 everything is zero.  Bar-aligned sync is mx_deck_sync on two `bars` grids.
+ * NEXT LINE  mx_deck_grid_next, host only, pure and exact (128-bit integers): the smallest n with first_q32 + n * period_q32 >= pos_q32 -- n = ceil((pos - first) /
+ *            period) by floor division, negative positions and indices included -- and that line.  On a beat, bar or phrase grid: what a host needs to schedule an
+ *            echo-out or a loop on the coming line.  mx_deck_sync's range rules: a period outside [1, 2^56], a position or first beat beyond 2^62 in magnitude:
+ *            MX_ERR_INVALID (|n| then stays below 2^63 but for pos = 2^62, first = -2^62, period = 1, which is refused too).
+ * Out of scope: metre detection (M is given); tempo that changes within a track; section labels and thresholds on phrase lines; chroma in the vector; analysis of a
+ * range of the track; any change to sync itself. */
+#define MX_DECK_BARS_MAX_BEATS 16384u
+#define MX_DECK_BARS_MAX_FOLDS 136u     /* M + M Q at M = 8, Q = 16 */
+#define MX_DECK_BARS_BLOCK 4u           /* beats one novelty workgroup takes (a wave per beat); tests size their cases around it */
+typedef struct { mx_deck_beats grid; uint32_t lead; uint32_t taps; uint32_t beats_per_bar; uint32_t bars_per_phrase; uint32_t w_bar; uint32_t w_phrase; uint32_t max_beats;
+                 int16_t lo[127]; int16_t hi[127]; } mx_deck_bars;   /* 552 bytes */
+typedef struct { uint32_t v[6]; uint32_t first_frame; uint32_t frames; int64_t n_bar; int64_t n_phrase; } mx_deck_beat;   /* 48 bytes */
+typedef struct { mx_deck_beats bars; mx_deck_beats phrases; uint32_t bar_phase; uint32_t phrase_phase; uint64_t bar_best; uint64_t bar_sum; uint64_t phrase_best;
+                 uint64_t phrase_sum; } mx_deck_bar_pick;   /* 72 bytes */
+/* Host only: the SETTINGS rules alone for a track of n_frames; MX_ERR_INVALID names the rule in mx_last_error. */
+int mx_deck_bars_check(const mx_deck_bars* s, uint64_t n_frames);
+/* Host only: BEATS.  *n_beats and *n0 (either may be NULL) of settings the check accepts; otherwise MX_ERR_INVALID. */
+int mx_deck_bars_count(const mx_deck_bars* s, uint64_t n_frames, uint32_t* n_beats, int64_t* n0);
+/* Host only: copies taps, lo and hi of *a (which must pass mx_deck_analysis_check) into *s and leaves the rest of *s alone.  Otherwise MX_ERR_INVALID, *s untouched. */
+int mx_deck_bars_tables(const mx_deck_analysis* a, mx_deck_bars* s);
+/* Analyse the whole track as loaded now.  Asynchronous on the deck's own load stream, like mx_deck_analyse: ordered after earlier loads and before later ones, not
+ * ordered against feeds.  Device memory the deck owns: 16384 * 48 + 136 * 8 bytes whatever the settings, so no later call grows it; a later call replaces the result,
+ * NULL frees it; the result is a snapshot that a later load does not invalidate.  Settings the check refuses: MX_ERR_INVALID, and the deck keeps what it had.  Memory
+ * that cannot be had: MX_ERR_NOMEM, and the deck is left without this analysis. */
+int mx_deck_analyse_bars(mx_deck* d, const mx_deck_bars* s);
+/* Records [first, first + n) of the deck's bars analysis; waits for it, like mx_deck_read_columns.  No analysis, a window beyond n_beats, NULL: MX_ERR_INVALID. */
+int mx_deck_read_bars(mx_deck* d, uint64_t first, uint64_t n, mx_deck_beat* dst);
+/* H_bar[0 .. M) and then H_phrase[0 .. M Q) of the deck's bars analysis into H[0 .. cap); waits for it.  No analysis, cap below M + M Q, NULL: MX_ERR_INVALID. */
+int mx_deck_read_bar_folds(mx_deck* d, uint64_t* H, uint32_t cap);
+/* Host only, pure: BEATS, FEATURES, NOVELTY and FOLD in plain C++ over a track of n_frames interleaved stereo frames: n_beats records into recs and M + M Q words into
+ * H_or_null when it is not NULL -- how the rules are tested without a device, and the single-thread baseline of the device path.  Settings the check refuses, NULL:
+ * MX_ERR_INVALID. */
+int mx_deck_bars_host(const int16_t* interleaved, uint64_t n_frames, const mx_deck_bars* s, mx_deck_beat* recs, uint64_t* H_or_null);
+/* Host only, pure, exact: PICK from the M + M Q words H of settings s.  Every SETTINGS rule that needs no track is held (not the two about the beats a grid places);
+ * otherwise, or with NULL: MX_ERR_INVALID. */
+int mx_deck_bars_pick(const uint64_t* H, const mx_deck_bars* s, mx_deck_bar_pick* out);
+/* Host only, pure, exact: NEXT LINE.  index or line_q32 may be NULL. */
+int mx_deck_grid_next(const mx_deck_beats* grid, int64_t pos_q32, int64_t* index, int64_t* line_q32);
+/* DEBUG: what the last mx_deck_analyse_bars of this process launched: out[0] band-pass workgroups (one per half-beat, 256 lanes) whose half-beat fits one tile of 1024
+ * frames, out[1] those that walked several tiles, out[2] novelty workgroups (MX_DECK_BARS_BLOCK beats each, a wave per beat), out[3] the novelties (a beat at a width)
+ * that NOVELTY defines and a wave summed, the others being written as 0.  Tests use it to know every form ran. */
+int mx_deck_debug_last_bars(uint32_t out[4]);
 
 /* ---------------------------------------------------------------------------------------------- */
 /* pixel path: device-resident yuv420p frames, VideoMixer, scaler, colour                          */

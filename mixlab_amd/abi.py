@@ -485,6 +485,29 @@ _proto("mx_deck_echo_delay", C.c_int, C.POINTER(DeckBeats), C.c_int64, C.c_uint3
 _proto("mx_deck_echo_state", C.c_int, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(DeckEcho))
 _proto("mx_deck_echo_plan", C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32))
 _proto("mx_deck_debug_last_echo", C.c_int, C.POINTER(C.c_uint32))
+# ... its bars and phrases (the header's BARS): beat vectors, checkerboard novelty at two widths, and the folds the downbeat and the phrase line are picked from
+DECK_BARS_MAX_BEATS = 16384   # MX_DECK_BARS_MAX_BEATS
+DECK_BARS_MAX_FOLDS = 136     # MX_DECK_BARS_MAX_FOLDS
+DECK_BARS_BLOCK = 4           # MX_DECK_BARS_BLOCK: beats one novelty workgroup takes
+class DeckBars(C.Structure):
+    _fields_ = [("grid", DeckBeats), ("lead", C.c_uint32), ("taps", C.c_uint32), ("beats_per_bar", C.c_uint32), ("bars_per_phrase", C.c_uint32), ("w_bar", C.c_uint32),
+                ("w_phrase", C.c_uint32), ("max_beats", C.c_uint32), ("lo", C.c_int16 * DECK_ANALYSIS_MAX_TAPS), ("hi", C.c_int16 * DECK_ANALYSIS_MAX_TAPS)]
+class DeckBeat(C.Structure):
+    _fields_ = [("v", C.c_uint32 * 6), ("first_frame", C.c_uint32), ("frames", C.c_uint32), ("n_bar", C.c_int64), ("n_phrase", C.c_int64)]
+class DeckBarPick(C.Structure):
+    _fields_ = [("bars", DeckBeats), ("phrases", DeckBeats), ("bar_phase", C.c_uint32), ("phrase_phase", C.c_uint32), ("bar_best", C.c_uint64), ("bar_sum", C.c_uint64),
+                ("phrase_best", C.c_uint64), ("phrase_sum", C.c_uint64)]
+DECK_BEAT_DTYPE = np.dtype([("v", "<u4", (6,)), ("first_frame", "<u4"), ("frames", "<u4"), ("n_bar", "<i8"), ("n_phrase", "<i8")])   # mx_deck_beat as a numpy record: 48 bytes
+_proto("mx_deck_bars_check", C.c_int, C.POINTER(DeckBars), C.c_uint64)
+_proto("mx_deck_bars_count", C.c_int, C.POINTER(DeckBars), C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_int64))
+_proto("mx_deck_bars_tables", C.c_int, C.POINTER(DeckAnalysis), C.POINTER(DeckBars))
+_proto("mx_deck_analyse_bars", C.c_int, C.c_void_p, C.POINTER(DeckBars))
+_proto("mx_deck_read_bars", C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p)
+_proto("mx_deck_read_bar_folds", C.c_int, C.c_void_p, C.c_void_p, C.c_uint32)
+_proto("mx_deck_bars_host", C.c_int, C.c_void_p, C.c_uint64, C.POINTER(DeckBars), C.c_void_p, C.c_void_p)
+_proto("mx_deck_bars_pick", C.c_int, C.c_void_p, C.POINTER(DeckBars), C.POINTER(DeckBarPick))
+_proto("mx_deck_grid_next", C.c_int, C.POINTER(DeckBeats), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64))
+_proto("mx_deck_debug_last_bars", C.c_int, C.POINTER(C.c_uint32))
 _proto("mx_module_create", C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p))
 _proto("mx_module_create_ex", C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(GraphOpts), C.POINTER(C.c_void_p))
 _proto("mx_module_update", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)

@@ -249,5 +249,40 @@ int mx_deck_echo_delay(const mx_deck_beats* grid, int64_t step_q32, uint32_t num
 int mx_deck_debug_last_finegrid(uint32_t out[4]) {
     return guard([&] { REQUIRE(out, "out is NULL"); mx::DeckFineGrid::debug_last(out); });
 }
+int mx_deck_bars_check(const mx_deck_bars* s, uint64_t n_frames) {
+    return guard([&] { REQUIRE(s, "settings are NULL"); (void)mx::deck_bars_check(*s, n_frames, true); });
+}
+int mx_deck_bars_count(const mx_deck_bars* s, uint64_t n_frames, uint32_t* n_beats, int64_t* n0) {
+    return guard([&] {
+        REQUIRE(s, "settings are NULL");
+        const mx::BarsBeats b = mx::deck_bars_check(*s, n_frames, true);
+        if (n_beats) *n_beats = b.n_beats;
+        if (n0) *n0 = b.n0;
+    });
+}
+int mx_deck_bars_tables(const mx_deck_analysis* a, mx_deck_bars* s) {
+    return guard([&] { REQUIRE(a && s, "NULL argument"); mx::deck_bars_tables(*a, *s); });
+}
+int mx_deck_analyse_bars(mx_deck* d, const mx_deck_bars* s) {
+    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.bars.analyse(s); });
+}
+int mx_deck_read_bars(mx_deck* d, uint64_t first, uint64_t n, mx_deck_beat* dst) {
+    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.bars.read(first, n, dst); });
+}
+int mx_deck_read_bar_folds(mx_deck* d, uint64_t* H, uint32_t cap) {
+    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.bars.read_folds(H, cap); });
+}
+int mx_deck_bars_host(const int16_t* interleaved, uint64_t n_frames, const mx_deck_bars* s, mx_deck_beat* recs, uint64_t* H_or_null) {
+    return guard([&] { REQUIRE(s, "settings are NULL"); mx::deck_bars_host(interleaved, n_frames, *s, recs, H_or_null); });
+}
+int mx_deck_bars_pick(const uint64_t* H, const mx_deck_bars* s, mx_deck_bar_pick* out) {
+    return guard([&] { REQUIRE(s && out, "NULL argument"); mx::deck_bars_pick(H, *s, *out); });
+}
+int mx_deck_grid_next(const mx_deck_beats* grid, int64_t pos_q32, int64_t* index, int64_t* line_q32) {
+    return guard([&] { REQUIRE(grid, "grid is NULL"); mx::deck_grid_next(*grid, pos_q32, index, line_q32); });
+}
+int mx_deck_debug_last_bars(uint32_t out[4]) {
+    return guard([&] { REQUIRE(out, "out is NULL"); mx::DeckBars::debug_last(out); });
+}
 
 }  // extern "C"

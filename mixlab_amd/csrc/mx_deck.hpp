@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "mx_common.hpp"
+#include "mx_deck_bars.hpp"
 #include "mx_deck_columns.hpp"
 #include "mx_deck_echo.hpp"
 #include "mx_deck_finegrid.hpp"
@@ -87,7 +88,7 @@ struct DeckLastKeylock { std::vector<DeckKlTick> ticks; uint32_t spt = 0, search
 DeckLastKeylock deck_last_keylock();
 
 // The track, the transport state machine and the feed (mx_deck.cpp), key-lock (mx_deck_keylock.cpp), the echo (mx_deck_echo.hpp: a member with its own state, schedule
-// and delay line), and the four whole-track analyses, each a member that holds its own results and sees of the deck a DeckTrack and nothing else (mx_deck_analysis.hpp).
+// and delay line), and the five whole-track analyses, each a member that holds its own results and sees of the deck a DeckTrack and nothing else (mx_deck_analysis.hpp).
 class Deck {
 public:
     Deck(uint64_t n_frames, int device);
@@ -124,6 +125,7 @@ public:
     DeckTonality tonality{for_analyses_};
     DeckLoudness loudness{for_analyses_};
     DeckFineGrid finegrid{for_analyses_};
+    DeckBars bars{for_analyses_};
     // the beat echo behind the feed and key-lock (mx_abi_deck.cpp calls it directly; the feed plans, launches and commits it)
     DeckEcho echo{device_};
 };

@@ -24,6 +24,12 @@ The echo (the header's ECHO) is a feedback delay behind the deck, timed in beats
 
     deck.set_echo(delay=deck.echo_delay(beats, 3, 4), feedback=0.6)       # a 3/4-beat echo from the next feed on
     deck.schedule(k, params(flags=0))                                     # PLAY cleared at tick k: the tail rings over the incoming track
+
+Bars (the header's BARS) say which beat is a bar's first and which bar a phrase's first; the two grids go where a beat grid goes:
+
+    pick = deck.find_bars(beats, analysis_bands(rate=44100.0))            # pick.bars, pick.phrases: DeckBeats; pick.bar_best / pick.bar_sum the confidence
+    step, seek, _ = deck_sync(leader_pick.bars, leader.state().pos_q32, leader.state().step_q32, pick.bars, deck.state().pos_q32)   # "1" on "1"
+    _, line = grid_next(pick.phrases, deck.state().pos_q32)               # the coming phrase line, for an echo-out or a loop
 """
 from __future__ import annotations
 
@@ -32,7 +38,7 @@ import ctypes as C
 import numpy as np
 
 from . import abi
-from .abi import (DeckAnalysis, DeckBeats, DeckEcho, DeckFinegrid, DeckFinePick, DeckGrain, DeckGrid, DeckHead, DeckKeylock, DeckLoudness, DeckParams, DeckSyncResult, DeckTick,
+from .abi import (DeckAnalysis, DeckBarPick, DeckBars, DeckBeats, DeckEcho, DeckFinegrid, DeckFinePick, DeckGrain, DeckGrid, DeckHead, DeckKeylock, DeckLoudness, DeckParams, DeckSyncResult, DeckTick,
                   DeckTonality, check, lib)
 
 ONE = 1 << 32   # unity step / one track frame in Q32.32
@@ -334,6 +340,58 @@ def debug_last_echo() -> dict:
     return _debug_last(lib.mx_deck_debug_last_echo, ("decks_one_block", "decks_sequential", "blocks", "blocks_crossing"))
 
 
+def bars(grid: DeckBeats, tables: DeckAnalysis | None = None, lead=128, beats_per_bar=4, bars_per_phrase=4, w_bar=4, w_phrase=8, max_beats=0) -> DeckBars:
+    """bars settings (the header's BARS) on a beat grid; the tap tables are those of `tables` (mx_deck_bars_tables), a single unity tap without it"""
+    s = DeckBars()
+    s.grid = DeckBeats(int(grid.first_q32), int(grid.period_q32))
+    s.lead, s.beats_per_bar, s.bars_per_phrase, s.w_bar, s.w_phrase, s.max_beats = int(lead), int(beats_per_bar), int(bars_per_phrase), int(w_bar), int(w_phrase), int(max_beats)
+    check(lib.mx_deck_bars_tables(C.byref(tables if tables is not None else analysis()), C.byref(s)))
+    return s
+
+
+def bars_check(s: DeckBars, n_frames: int) -> None:
+    """the bars setting rules alone for a track of n_frames (host only); raises MxError"""
+    check(lib.mx_deck_bars_check(C.byref(s), int(n_frames)))
+
+
+def bars_count(s: DeckBars, n_frames: int):
+    """(n_beats, n0): the whole beats the grid places in the track, and the grid index of the first (mx_deck_bars_count, host only)"""
+    n, n0 = C.c_uint32(), C.c_int64()
+    check(lib.mx_deck_bars_count(C.byref(s), int(n_frames), C.byref(n), C.byref(n0)))
+    return n.value, n0.value
+
+
+def bars_host(interleaved_i16: np.ndarray, s: DeckBars):
+    """the bars rules in plain C++ on the host (pure): (abi.DECK_BEAT_DTYPE[n_beats], the folds as uint64[M + M Q])"""
+    x = np.ascontiguousarray(interleaved_i16, dtype=np.int16).reshape(-1)
+    n, _ = bars_count(s, x.size // 2)   # before a buffer is sized from the settings
+    recs = np.zeros(n, abi.DECK_BEAT_DTYPE)
+    H = np.zeros(s.beats_per_bar * (1 + s.bars_per_phrase), np.uint64)
+    check(lib.mx_deck_bars_host(x.ctypes.data_as(C.c_void_p), x.size // 2, C.byref(s), recs.ctypes.data_as(C.c_void_p), H.ctypes.data_as(C.c_void_p)))
+    return recs, H
+
+
+def bars_pick(folds: np.ndarray, s: DeckBars) -> DeckBarPick:
+    """the downbeat and the phrase line as two grids (mx_deck_bars_pick, host only, pure): .bars, .phrases, the two phases and the four sums"""
+    H = np.zeros(abi.DECK_BARS_MAX_FOLDS, np.uint64)   # room for any M + M Q, whatever the settings say
+    f = np.asarray(folds, dtype=np.uint64).reshape(-1)
+    H[:min(f.size, H.size)] = f[:H.size]
+    out = DeckBarPick()
+    check(lib.mx_deck_bars_pick(H.ctypes.data_as(C.c_void_p), C.byref(s), C.byref(out)))
+    return out
+
+
+def grid_next(grid: DeckBeats, pos_q32: int):
+    """(n, line): the first line of a beat, bar or phrase grid at or after pos_q32, and its index (mx_deck_grid_next, host only, pure)"""
+    n, line = C.c_int64(), C.c_int64()
+    check(lib.mx_deck_grid_next(C.byref(grid), int(pos_q32), C.byref(n), C.byref(line)))
+    return n.value, line.value
+
+
+def debug_last_bars() -> dict:
+    return _debug_last(lib.mx_deck_debug_last_bars, ("wgs_half_one_tile", "wgs_half_tiled", "wgs_novelty", "novelties_defined"))
+
+
 _NOT_GIVEN = object()   # Deck.analyse_finegrid: no settings argument at all, as against None
 
 
@@ -348,6 +406,7 @@ class Deck:
         self._tonality = None    # (segments, octaves)
         self._loudness = None    # blocks
         self._finegrid = None    # (n_periods, hops)
+        self._bars = None        # (n_beats, M + M Q)
         check(lib.mx_deck_create(self.n_frames, device, C.byref(self._h)))
 
     def close(self):
@@ -520,6 +579,35 @@ class Deck:
         two, _ = finegrid_span(one.period0_q16 + first.index * one.dperiod_q16, 4 * one.dperiod_q16, 0, n_hops, hop)
         self.analyse_finegrid(two)
         return finegrid_pick(self.read_finegrid(), two, rate)
+
+    def analyse_bars(self, s: DeckBars | None):
+        """beat vectors, novelties and folds of the whole track on the grid of the settings, asynchronously on the deck's own stream; analyse_bars(None) frees them"""
+        self._analyse(lib.mx_deck_analyse_bars, "_bars", s, lambda s: (bars_count(s, self.n_frames)[0], s.beats_per_bar * (1 + s.bars_per_phrase)))
+
+    def read_bars(self, first: int = 0, n: int | None = None) -> np.ndarray:
+        """abi.DECK_BEAT_DTYPE[n] of the bars analysis, one record per beat; waits for it"""
+        n = ((self._bars or (0, 0))[0] - first) if n is None else n
+        out = np.zeros(max(1, n), abi.DECK_BEAT_DTYPE)
+        check(lib.mx_deck_read_bars(self._h, int(first), int(n), out.ctypes.data_as(C.c_void_p)))
+        return out[:n]
+
+    def read_bar_folds(self, cap: int | None = None) -> np.ndarray:
+        """H_bar then H_phrase as uint64[M + M Q] of the bars analysis; waits for it.  cap is the room offered to the library (by default M + M Q)"""
+        words = (self._bars or (0, 0))[1]
+        cap = words if cap is None else cap
+        H = np.zeros(max(1, cap), np.uint64)
+        check(lib.mx_deck_read_bar_folds(self._h, H.ctypes.data_as(C.c_void_p), int(cap)))
+        return H[:words]
+
+    def find_bars(self, pick_or_grid, tables: DeckAnalysis | None = None, **kw) -> DeckBarPick:
+        """the downbeats and phrase lines of a beat grid (a DeckBeats, or refine_grid()'s pick): analyse_bars, the folds, bars_pick.  Keywords are bars()'s.  Waits for
+        the device once.  A grid without a period (a silent track's pick) gives the all-zero pick."""
+        grid = getattr(pick_or_grid, "grid", pick_or_grid)
+        if not grid.period_q32 > 0:
+            return DeckBarPick()
+        s = bars(grid, tables, **kw)
+        self.analyse_bars(s)
+        return bars_pick(self.read_bar_folds(), s)
 
     def state(self) -> DeckHead:
         h = DeckHead()
