@@ -58,7 +58,10 @@ extern "C" {
                               *    mx_deck_echo, mx_deck_set_echo, mx_deck_schedule_echo, mx_deck_echo_check, mx_deck_echo_delay, mx_deck_echo_state, mx_deck_echo_plan,
                               *    mx_deck_debug_last_echo;
                               *    mx_deck_bars, mx_deck_beat, mx_deck_bar_pick, mx_deck_bars_check, mx_deck_bars_count, mx_deck_bars_tables, mx_deck_analyse_bars,
-                              *    mx_deck_read_bars, mx_deck_read_bar_folds, mx_deck_bars_host, mx_deck_bars_pick, mx_deck_grid_next, mx_deck_debug_last_bars */
+                              *    mx_deck_read_bars, mx_deck_read_bar_folds, mx_deck_bars_host, mx_deck_bars_pick, mx_deck_grid_next, mx_deck_debug_last_bars;
+                              *    mx_deck_tempomap, mx_deck_tempo_segment, mx_deck_tempomap_check, mx_deck_tempomap_count, mx_deck_tempomap_span, mx_deck_tempomap_host,
+                              *    mx_deck_tempomap_path, mx_deck_tempomap_segments, mx_deck_tempomap_at, mx_deck_tempomap_step, mx_deck_analyse_tempomap,
+                              *    mx_deck_read_tempomap, mx_deck_read_tempomap_onsets, mx_deck_debug_last_tempomap */
 
 /* ---- status codes (0 ok, <0 error; cf. MIXLAB_IOCTX_ERROR / MIXLAB_IOCTX_PANIC) ---- */
 enum {
@@ -1210,7 +1213,7 @@ int mx_tonality_camelot(int key, uint32_t* number, uint32_t* minor);
  *                delta = b - c, then Pf added or subtracted until it lies in (-Pf / 2, Pf / 2],   seek = follower_pos + delta
  *            The host hands step and seek to mx_deck_schedule for that tick.  A period outside [1, 2^56], a position or first beat beyond 2^62 in magnitude: MX_ERR_INVALID.
  * Out of scope: a key-locked leader or follower (under KEY-LOCK the head still crosses the track as mx_deck_plan says, so the arithmetic holds for the head; what the
- * grains make audible of it is KEY-LOCK's business, and nothing here refuses such a deck); tempo that changes within a track; downbeats and bars (BARS below); phases finer than a
+ * grains make audible of it is KEY-LOCK's business, and nothing here refuses such a deck); tempo that changes within a track (TEMPO MAP below); downbeats and bars (BARS below); phases finer than a
  * hop; a search over a range of the track other than "from first_hop on". */
 #define MX_DECK_FINEGRID_LANES 256u       /* phases one pass of a comb workgroup covers (a lane per phase); tests size their candidates around it */
 #define MX_DECK_FINEGRID_MAX_PERIODS 8192u
@@ -1334,6 +1337,100 @@ int mx_deck_grid_next(const mx_deck_beats* grid, int64_t pos_q32, int64_t* index
  * frames, out[1] those that walked several tiles, out[2] novelty workgroups (MX_DECK_BARS_BLOCK beats each, a wave per beat), out[3] the novelties (a beat at a width)
  * that NOVELTY defines and a wave summed, the others being written as 0.  Tests use it to know every form ran. */
 int mx_deck_debug_last_bars(uint32_t out[4]);
+
+/* ---- TEMPO MAP: the beats of a track whose tempo drifts, by a comb search per window of the track on the device, and the arithmetic that follows the map ----
+ * BUILD-SPECIFIED.  FINE GRID fits one period and one phase to a whole track; a live drummer, a record cut before sequencers or a single tempo change leaves such a
+ * grid half a beat off at the track's ends.  This section runs FINE GRID's comb inside overlapping windows of the track, every candidate period at every integer phase
+ * in every window; the host then picks one candidate per window by a path that pays for tempo jumps, turns the picks into segments that each carry an ordinary
+ * mx_deck_beats, and looks the segment of a position up -- whose grid goes into mx_deck_sync, mx_deck_echo_delay and mx_deck_grid_next unchanged.  A sixth analysis on
+ * the deck's own load stream with the ownership rules of the other five and independent of their results (the fine grid's included); integers throughout, so the
+ * records are fixed count for count.  A deck that never calls it is untouched in every respect, and every other entry point is what it was.
+ *
+ * SETTINGS   mx_deck_tempomap (32 bytes): hop h and the candidate periods P_j = period0_q16 + j * dperiod_q16 under FINE GRID's rules (h a power of two, 16 .. 256;
+ *            every P_j in [4 * 65536, 32768 * 65536]; dperiod_q16 >= 1 unless n_periods is 1), with n_periods 1 .. MX_DECK_TEMPOMAP_MAX_PERIODS; window_hops W with
+ *            2 * ceil(P_max) <= W <= MX_DECK_TEMPOMAP_MAX_WINDOW (P_max the largest candidate, ceil(P) = (P + 65535) >> 16: every phase of every candidate has a
+ *            second tooth's room in a full window, and a window's w is at most 64 KB); stride_hops T with 1 <= T <= W; _pad 0.  For a track of n_frames
+ *            (1 .. 2^30), N = ceil(n_frames / h) and the window count is V = 1 when N <= W, else ceil((N - W) / T) + 1; V * n_periods <= 2^20.
+ *            mx_deck_tempomap_check enforces exactly these rules, in this order, and names the broken one; mx_deck_tempomap_count returns V.
+ * ONSETS     w[i], 0 <= i < N, is FINE GRID's tooth weight over the whole track, number for number.
+ * COMB       window v covers the hops [v T, E_v), E_v = min(v T + W, N); the last window ends at N and is never empty.  For candidate j and each integer phase phi,
+ *            0 <= phi < ceil(P_j):
+ *                S_v(j, phi) = sum over k = 0, 1, ... of w[i_k],    i_k = v T + phi + ((k * P_j) >> 16)
+ *            the sum stopping at the first k with i_k >= E_v.  Record (v, j), an mx_deck_comb at index v * n_periods + j: score the largest S, phase the smallest
+ *            phi that reaches it, beats the number of teeth that phase summed.  A phase whose first tooth lies at or beyond E_v (a last window shorter than
+ *            ceil(P_j)) has S = 0 and 0 teeth.  With W >= N there is one window, and its records are FINE GRID's at first_hop = 0, max_beats = 0, byte for byte.
+ *            A score is below 2^30 (w <= 2^18, at most W / 4 = 2^12 teeth).
+ * PATH       mx_deck_tempomap_path, host only, pure and exact: one candidate index per window.  With score[v][j] the records' scores,
+ *                D[0][j] = score[0][j],    D[v][j] = score[v][j] + max over i of (D[v - 1][i] - penalty * |j - i|),    ties to the smallest i;
+ *            the path ends at the largest D[V - 1][j], ties to the smallest j, and is read backwards from there.  penalty is at most 2^40 and every score at most
+ *            2^40 (otherwise MX_ERR_INVALID), so with V * n_periods <= 2^20 nothing leaves int64.  penalty 0 is the per-window pick: the largest score of each
+ *            window, then the smallest j.
+ * SEGMENTS   mx_deck_tempomap_segments, host only, pure and exact: one mx_deck_tempo_segment (40 bytes) per window from the records, the settings and a path.
+ *            Window v's own grid, with j the path's index and phase the record's: period_q32 = (P_j * h) << 16, first_q32 = ((v T + phase) * h + h / 2) << 32 --
+ *            PICK's, with the window's first hop for first_hop.  score is the record's, window is v.  A window whose chosen score is 0 is a breakdown: its flags
+ *            carry MX_DECK_TEMPO_EMPTY and its grid is that of the nearest earlier window that is not empty; empty windows before the first that is not take the
+ *            grid of that one; when every window is empty every grid is { 0, 0 }.  start_q32 of segment 0 is -2^62.  For v >= 1 it is the first line of segment
+ *            v's grid (the inherited one for an empty window) at or after the position m_v = ((v T + (W - T) / 2) * h) << 32 -- (W - T) / 2 rounded down: the
+ *            middle of the overlap with window v - 1 -- as mx_deck_grid_next finds it; with a grid of { 0, 0 } it is m_v itself.  The beats of the map are, per
+ *            segment v, the lines b of its grid with start_v <= b and b + period_v / 2 <= start_(v+1) (period / 2 rounded down; no upper bound in the last
+ *            segment): the half-period rule keeps a seam from holding two beats a hop apart.  Starts are not forced to ascend (with T far below a period two
+ *            neighbours' first lines may cross); LOOK-UP is defined so that this does not matter.
+ * LOOK-UP    mx_deck_tempomap_at, host only, pure: the segment of a position is the one with the LARGEST INDEX among those with start_q32 <= pos_q32; *grid is its
+ *            grid and *segment its index (either may be NULL).  The grid goes into mx_deck_sync, mx_deck_echo_delay and mx_deck_grid_next unchanged: asked again
+ *            tick by tick it is how a follower tracks a drifting leader.  n = 0, a position below segment 0's start or beyond 2^62, NULL segs: MX_ERR_INVALID.
+ * WARP       mx_deck_tempomap_step, host only, pure and exact (128-bit integers, ties to even, as mx_deck_sync): *step_q32 = round(period_q32 * 2^32 /
+ *            out_period_q32), the step at which this stretch of the track comes out with a beat every out_period_q32 / 2^32 output frames.  A grid period outside
+ *            [1, 2^56], out_period_q32 outside [1, 2^56], a result above 4 * 2^32, NULL: MX_ERR_INVALID.
+ * SPAN       mx_deck_tempomap_span, host only and pure: SPAN's arithmetic of FINE GRID with K = window_beats (1 .. 4096), the teeth of one window.  dperiod =
+ *            max(1, floor(32768 / K)); m = min(ceil(half-width / dperiod), 511), further cut on either side to what stays within [4 * 65536, 8192 * 65536] -- the
+ *            periods that leave room for a window under the cap -- with the centre c itself a candidate (a centre outside that range: MX_ERR_INVALID); W =
+ *            ceil(window_beats * P_max / 65536), raised to 2 * ceil(P_max), cut to MX_DECK_TEMPOMAP_MAX_WINDOW; T = max(1, floor(stride_beats * c / 65536)) cut to
+ *            W (stride_beats 1 .. 4096).  *clipped says whether m, W (by the cap) or T was cut.  The result is held against mx_deck_tempomap_check's rules for a
+ *            track of n_hops hops (1 .. 2^26), so a search too large for V * n_periods <= 2^20 is refused here.
+ * Out of scope: bars and phrases over a map (BARS takes one grid); key-locked decks (as under FINE GRID); phases finer than a hop; tempo changes faster than a window
+ * can follow; the path search on the device; any change to mx_deck_sync's arithmetic. */
+#define MX_DECK_TEMPOMAP_MAX_WINDOW 16384u    /* hops of one window: 64 KB of w, which a workgroup can hold in LDS */
+#define MX_DECK_TEMPOMAP_MAX_PERIODS 1024u
+#define MX_DECK_TEMPOMAP_MAX_RECORDS 1048576u /* V * n_periods */
+#define MX_DECK_TEMPOMAP_GROUP 8u             /* candidates of one window that one comb workgroup walks; tests size their cases around it */
+#define MX_DECK_TEMPOMAP_STAGED_MAX 10112u /* the longest window (min(W, N) hops) whose comb workgroups stage it in LDS: four such workgroups fit a CU */
+#define MX_DECK_TEMPO_EMPTY 1u                /* mx_deck_tempo_segment.flags: the window's chosen score is 0 and the grid is a neighbour's */
+typedef struct { uint32_t hop; uint32_t n_periods; uint64_t period0_q16; uint32_t dperiod_q16; uint32_t window_hops; uint32_t stride_hops; uint32_t _pad; } mx_deck_tempomap;   /* 32 bytes */
+typedef struct { int64_t start_q32; mx_deck_beats grid; uint64_t score; uint32_t window; uint32_t flags; } mx_deck_tempo_segment;   /* 40 bytes */
+/* Host only: the SETTINGS rules alone for a track of n_frames; MX_ERR_INVALID names the rule in mx_last_error. */
+int mx_deck_tempomap_check(const mx_deck_tempomap* s, uint64_t n_frames);
+/* Host only: *n_windows = V of settings the check accepts; otherwise MX_ERR_INVALID. */
+int mx_deck_tempomap_count(const mx_deck_tempomap* s, uint64_t n_frames, uint32_t* n_windows);
+/* Host only, pure: SPAN.  *s untouched on MX_ERR_INVALID; clipped may be NULL. */
+int mx_deck_tempomap_span(uint64_t centre_q16, uint64_t halfwidth_q16, uint32_t window_beats, uint32_t stride_beats, uint64_t n_hops, uint32_t hop, mx_deck_tempomap* s,
+                          uint32_t* clipped);
+/* Host only, pure: ONSETS and COMB in plain C++ over a track of n_frames interleaved stereo frames: V * n_periods records into recs, and w[0 .. N) into w_or_null when it
+ * is not NULL -- how the rules are tested without a device, and the single-thread baseline of the device path.  Settings the check refuses, NULL: MX_ERR_INVALID. */
+int mx_deck_tempomap_host(const int16_t* interleaved, uint64_t n_frames, const mx_deck_tempomap* s, mx_deck_comb* recs, uint32_t* w_or_null);
+/* Host only, pure, exact: PATH over n_windows * n_periods records (both at least 1, their product at most 2^20): n_windows indices into index. */
+int mx_deck_tempomap_path(const mx_deck_comb* recs, uint32_t n_windows, uint32_t n_periods, uint64_t penalty, uint32_t* index);
+/* Host only, pure, exact: SEGMENTS.  V = mx_deck_tempomap_count(s, n_frames) entries of index (each below n_periods) are read and V segments written. */
+int mx_deck_tempomap_segments(const mx_deck_comb* recs, const mx_deck_tempomap* s, uint64_t n_frames, const uint32_t* index, mx_deck_tempo_segment* segs);
+/* Host only, pure: LOOK-UP. */
+int mx_deck_tempomap_at(const mx_deck_tempo_segment* segs, uint32_t n, int64_t pos_q32, mx_deck_beats* grid, uint32_t* segment);
+/* Host only, pure, exact: WARP. */
+int mx_deck_tempomap_step(const mx_deck_beats* grid, int64_t out_period_q32, int64_t* step_q32);
+/* Score every candidate in every window over the whole track as loaded now.  Asynchronous on the deck's own load stream, like mx_deck_analyse: ordered after earlier
+ * loads and before later ones, not ordered against feeds.  Device memory the deck owns: V * n_periods * 16 + N * 4 bytes; a later call replaces the result (a buffer
+ * that must grow waits for the stream first, one that is large enough stays), NULL frees it; the result is a snapshot that a later load does not invalidate, and each
+ * call computes w afresh.  Settings the check refuses: MX_ERR_INVALID, and the deck keeps what it had.  Memory that cannot be had: MX_ERR_NOMEM, and the deck is left
+ * without a tempo map. */
+int mx_deck_analyse_tempomap(mx_deck* d, const mx_deck_tempomap* s);
+/* Records [first, first + n) of the deck's tempo map (record (v, j) at v * n_periods + j); waits for it, like mx_deck_read_columns.  No tempo map, a window beyond
+ * V * n_periods, NULL: MX_ERR_INVALID. */
+int mx_deck_read_tempomap(mx_deck* d, uint64_t first, uint64_t n, mx_deck_comb* dst);
+/* w[first .. first + n) of the deck's tempo map; waits for it.  No tempo map, a window beyond N, NULL: MX_ERR_INVALID. */
+int mx_deck_read_tempomap_onsets(mx_deck* d, uint64_t first, uint64_t n, uint32_t* w);
+/* DEBUG: what the last mx_deck_analyse_tempomap of this process launched: out[0] comb workgroups (256 lanes, one window and up to MX_DECK_TEMPOMAP_GROUP candidates
+ * each) that staged their window's w in LDS, out[1] comb workgroups that read w from memory, out[2] onset workgroups (FINE GRID's), out[3] the trip count of the comb
+ * kernel's loop over k (the teeth of phase 0 at the smallest period in a window of min(W, N) hops).  One analysis takes one form: the workgroups stage when n_periods is
+ * at least 2 and min(W, N) is at most MX_DECK_TEMPOMAP_STAGED_MAX, and read w from memory otherwise.  Tests use it to know every form ran. */
+int mx_deck_debug_last_tempomap(uint32_t out[4]);
 
 /* ---------------------------------------------------------------------------------------------- */
 /* pixel path: device-resident yuv420p frames, VideoMixer, scaler, colour                          */

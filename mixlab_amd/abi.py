@@ -508,6 +508,31 @@ _proto("mx_deck_bars_host", C.c_int, C.c_void_p, C.c_uint64, C.POINTER(DeckBars)
 _proto("mx_deck_bars_pick", C.c_int, C.c_void_p, C.POINTER(DeckBars), C.POINTER(DeckBarPick))
 _proto("mx_deck_grid_next", C.c_int, C.POINTER(DeckBeats), C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64))
 _proto("mx_deck_debug_last_bars", C.c_int, C.POINTER(C.c_uint32))
+# ... its tempo map (the header's TEMPO MAP): the comb search per window of the track, the path through the windows, segments, look-up and warp
+DECK_TEMPOMAP_MAX_WINDOW = 16384       # MX_DECK_TEMPOMAP_MAX_WINDOW
+DECK_TEMPOMAP_MAX_PERIODS = 1024       # MX_DECK_TEMPOMAP_MAX_PERIODS
+DECK_TEMPOMAP_MAX_RECORDS = 1 << 20    # MX_DECK_TEMPOMAP_MAX_RECORDS
+DECK_TEMPOMAP_GROUP = 8                # MX_DECK_TEMPOMAP_GROUP: candidates one comb workgroup walks
+DECK_TEMPOMAP_STAGED_MAX = 10112     # MX_DECK_TEMPOMAP_STAGED_MAX: the longest window a comb workgroup stages in LDS
+DECK_TEMPO_EMPTY = 1                   # MX_DECK_TEMPO_EMPTY
+class DeckTempomap(C.Structure):
+    _fields_ = [("hop", C.c_uint32), ("n_periods", C.c_uint32), ("period0_q16", C.c_uint64), ("dperiod_q16", C.c_uint32), ("window_hops", C.c_uint32),
+                ("stride_hops", C.c_uint32), ("_pad", C.c_uint32)]
+class DeckTempoSegment(C.Structure):
+    _fields_ = [("start_q32", C.c_int64), ("grid", DeckBeats), ("score", C.c_uint64), ("window", C.c_uint32), ("flags", C.c_uint32)]
+DECK_TEMPO_SEGMENT_DTYPE = np.dtype([("start_q32", "<i8"), ("first_q32", "<i8"), ("period_q32", "<i8"), ("score", "<u8"), ("window", "<u4"), ("flags", "<u4")])   # 40 bytes, the grid flat
+_proto("mx_deck_tempomap_check", C.c_int, C.POINTER(DeckTempomap), C.c_uint64)
+_proto("mx_deck_tempomap_count", C.c_int, C.POINTER(DeckTempomap), C.c_uint64, C.POINTER(C.c_uint32))
+_proto("mx_deck_tempomap_span", C.c_int, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(DeckTempomap), C.POINTER(C.c_uint32))
+_proto("mx_deck_tempomap_host", C.c_int, C.c_void_p, C.c_uint64, C.POINTER(DeckTempomap), C.c_void_p, C.c_void_p)
+_proto("mx_deck_tempomap_path", C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p)
+_proto("mx_deck_tempomap_segments", C.c_int, C.c_void_p, C.POINTER(DeckTempomap), C.c_uint64, C.c_void_p, C.c_void_p)
+_proto("mx_deck_tempomap_at", C.c_int, C.c_void_p, C.c_uint32, C.c_int64, C.POINTER(DeckBeats), C.POINTER(C.c_uint32))
+_proto("mx_deck_tempomap_step", C.c_int, C.POINTER(DeckBeats), C.c_int64, C.POINTER(C.c_int64))
+_proto("mx_deck_analyse_tempomap", C.c_int, C.c_void_p, C.POINTER(DeckTempomap))
+_proto("mx_deck_read_tempomap", C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p)
+_proto("mx_deck_read_tempomap_onsets", C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p)
+_proto("mx_deck_debug_last_tempomap", C.c_int, C.POINTER(C.c_uint32))
 _proto("mx_module_create", C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p))
 _proto("mx_module_create_ex", C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(GraphOpts), C.POINTER(C.c_void_p))
 _proto("mx_module_update", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)

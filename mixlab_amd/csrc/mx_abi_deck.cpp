@@ -284,5 +284,42 @@ int mx_deck_grid_next(const mx_deck_beats* grid, int64_t pos_q32, int64_t* index
 int mx_deck_debug_last_bars(uint32_t out[4]) {
     return guard([&] { REQUIRE(out, "out is NULL"); mx::DeckBars::debug_last(out); });
 }
+int mx_deck_tempomap_check(const mx_deck_tempomap* s, uint64_t n_frames) {
+    return guard([&] { REQUIRE(s, "settings are NULL"); (void)mx::deck_tempomap_check(*s, n_frames); });
+}
+int mx_deck_tempomap_count(const mx_deck_tempomap* s, uint64_t n_frames, uint32_t* n_windows) {
+    return guard([&] { REQUIRE(s && n_windows, "NULL argument"); *n_windows = mx::deck_tempomap_check(*s, n_frames); });
+}
+int mx_deck_tempomap_span(uint64_t centre_q16, uint64_t halfwidth_q16, uint32_t window_beats, uint32_t stride_beats, uint64_t n_hops, uint32_t hop, mx_deck_tempomap* s,
+                          uint32_t* clipped) {
+    return guard([&] { REQUIRE(s, "settings are NULL"); mx::deck_tempomap_span(centre_q16, halfwidth_q16, window_beats, stride_beats, n_hops, hop, *s, clipped); });
+}
+int mx_deck_tempomap_host(const int16_t* interleaved, uint64_t n_frames, const mx_deck_tempomap* s, mx_deck_comb* recs, uint32_t* w_or_null) {
+    return guard([&] { REQUIRE(s, "settings are NULL"); mx::deck_tempomap_host(interleaved, n_frames, *s, recs, w_or_null); });
+}
+int mx_deck_tempomap_path(const mx_deck_comb* recs, uint32_t n_windows, uint32_t n_periods, uint64_t penalty, uint32_t* index) {
+    return guard([&] { mx::deck_tempomap_path(recs, n_windows, n_periods, penalty, index); });
+}
+int mx_deck_tempomap_segments(const mx_deck_comb* recs, const mx_deck_tempomap* s, uint64_t n_frames, const uint32_t* index, mx_deck_tempo_segment* segs) {
+    return guard([&] { REQUIRE(s, "settings are NULL"); mx::deck_tempomap_segments(recs, *s, n_frames, index, segs); });
+}
+int mx_deck_tempomap_at(const mx_deck_tempo_segment* segs, uint32_t n, int64_t pos_q32, mx_deck_beats* grid, uint32_t* segment) {
+    return guard([&] { mx::deck_tempomap_at(segs, n, pos_q32, grid, segment); });
+}
+int mx_deck_tempomap_step(const mx_deck_beats* grid, int64_t out_period_q32, int64_t* step_q32) {
+    return guard([&] { REQUIRE(grid && step_q32, "NULL argument"); *step_q32 = mx::deck_tempomap_step(*grid, out_period_q32); });
+}
+int mx_deck_analyse_tempomap(mx_deck* d, const mx_deck_tempomap* s) {
+    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.tempomap.analyse(s); });
+}
+int mx_deck_read_tempomap(mx_deck* d, uint64_t first, uint64_t n, mx_deck_comb* dst) {
+    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.tempomap.read(first, n, dst); });
+}
+int mx_deck_read_tempomap_onsets(mx_deck* d, uint64_t first, uint64_t n, uint32_t* w) {
+    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.tempomap.read_onsets(first, n, w); });
+}
+int mx_deck_debug_last_tempomap(uint32_t out[4]) {
+    return guard([&] { REQUIRE(out, "out is NULL"); mx::DeckTempoMap::debug_last(out); });
+}
 
 }  // extern "C"

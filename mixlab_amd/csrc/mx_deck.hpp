@@ -9,6 +9,7 @@
 #include "mx_deck_echo.hpp"
 #include "mx_deck_finegrid.hpp"
 #include "mx_deck_loudkey.hpp"
+#include "mx_deck_tempomap.hpp"
 
 namespace mx {
 
@@ -88,7 +89,7 @@ struct DeckLastKeylock { std::vector<DeckKlTick> ticks; uint32_t spt = 0, search
 DeckLastKeylock deck_last_keylock();
 
 // The track, the transport state machine and the feed (mx_deck.cpp), key-lock (mx_deck_keylock.cpp), the echo (mx_deck_echo.hpp: a member with its own state, schedule
-// and delay line), and the five whole-track analyses, each a member that holds its own results and sees of the deck a DeckTrack and nothing else (mx_deck_analysis.hpp).
+// and delay line), and the six whole-track analyses, each a member that holds its own results and sees of the deck a DeckTrack and nothing else (mx_deck_analysis.hpp).
 class Deck {
 public:
     Deck(uint64_t n_frames, int device);
@@ -126,6 +127,7 @@ public:
     DeckLoudness loudness{for_analyses_};
     DeckFineGrid finegrid{for_analyses_};
     DeckBars bars{for_analyses_};
+    DeckTempoMap tempomap{for_analyses_};
     // the beat echo behind the feed and key-lock (mx_abi_deck.cpp calls it directly; the feed plans, launches and commits it)
     DeckEcho echo{device_};
 };

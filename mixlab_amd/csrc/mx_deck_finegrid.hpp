@@ -45,6 +45,8 @@ struct DkFineArgs {
 };
 enum { DK_FINE_FORM_ONE_PASS = 0, DK_FINE_FORM_STRIDED = 1, DK_FINE_FORM_ONSET = 2, DK_FINE_FORM_TRIP = 3 };
 void launch_deck_finegrid(const DkFineArgs& a, uint32_t forms[4], hipStream_t s);
+// w[0 .. N) alone (the tempo map's onsets are these); the onset workgroups it launched
+uint32_t launch_deck_fine_onsets(const uint32_t* track, int64_t n_frames, uint32_t log_hop, uint32_t N, uint32_t* w, hipStream_t s);
 
 // ---- host ----
 void deck_finegrid_check(const mx_deck_finegrid& s, uint64_t n_frames, bool with_track);   // throws Error(MX_ERR_INVALID) naming the rule; without a track: every rule but first_hop < N

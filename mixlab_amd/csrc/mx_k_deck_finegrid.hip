@@ -83,9 +83,14 @@ __global__ __launch_bounds__(FG_LANES) void k_fine_comb(const uint32_t* __restri
     }
 }
 
+uint32_t launch_deck_fine_onsets(const uint32_t* track, int64_t n_frames, uint32_t log_hop, uint32_t N, uint32_t* w, hipStream_t s) {
+    const uint32_t onset_wgs = (N + FG_TILE - 1u) / FG_TILE;   // (N <= 2^26: at most 2^18)
+    hipLaunchKernelGGL(k_fine_onsets, dim3(onset_wgs), dim3(256), 0, s, track, n_frames, log_hop, N, w);
+    return onset_wgs;
+}
+
 void launch_deck_finegrid(const DkFineArgs& a, uint32_t forms[4], hipStream_t s) {
-    const uint32_t onset_wgs = (a.N + FG_TILE - 1u) / FG_TILE;   // (N <= 2^26: at most 2^18)
-    hipLaunchKernelGGL(k_fine_onsets, dim3(onset_wgs), dim3(256), 0, s, a.track, a.n_frames, a.log_hop, a.N, a.w);
+    const uint32_t onset_wgs = launch_deck_fine_onsets(a.track, a.n_frames, a.log_hop, a.N, a.w, s);
     hipLaunchKernelGGL(k_fine_comb, dim3(a.n_periods), dim3(FG_LANES), 0, s, (const uint32_t*)a.w, a.N, a.first_hop, a.period0, a.dperiod, a.trip, a.rec);
     forms[DK_FINE_FORM_ONE_PASS] = forms[DK_FINE_FORM_STRIDED] = 0u;
     for (uint32_t j = 0; j < a.n_periods; ++j) ++forms[fg_phases(a.period0 + (uint64_t)j * a.dperiod) <= FG_LANES ? DK_FINE_FORM_ONE_PASS : DK_FINE_FORM_STRIDED];

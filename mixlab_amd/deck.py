@@ -30,6 +30,12 @@ Bars (the header's BARS) say which beat is a bar's first and which bar a phrase'
     pick = deck.find_bars(beats, analysis_bands(rate=44100.0))            # pick.bars, pick.phrases: DeckBeats; pick.bar_best / pick.bar_sum the confidence
     step, seek, _ = deck_sync(leader_pick.bars, leader.state().pos_q32, leader.state().step_q32, pick.bars, deck.state().pos_q32)   # "1" on "1"
     _, line = grid_next(pick.phrases, deck.state().pos_q32)               # the coming phrase line, for an echo-out or a loop
+
+The tempo map (the header's TEMPO MAP) follows a track whose tempo drifts: a grid per window of the track, looked up by position:
+
+    segs = deck.map_tempo(deck.refine_grid(grid, 512, 44100.0))           # abi.DECK_TEMPO_SEGMENT_DTYPE, one per window
+    beats, _ = tempomap_at(segs, deck.state().pos_q32)                    # the DeckBeats in force here: goes where a beat grid goes, asked again tick by tick
+    deck.schedule_warp(segs, out_period_q32, n_ticks, spt)                # before each feed: the drifting track comes out at one constant beat length
 """
 from __future__ import annotations
 
@@ -38,8 +44,8 @@ import ctypes as C
 import numpy as np
 
 from . import abi
-from .abi import (DeckAnalysis, DeckBarPick, DeckBars, DeckBeats, DeckEcho, DeckFinegrid, DeckFinePick, DeckGrain, DeckGrid, DeckHead, DeckKeylock, DeckLoudness, DeckParams, DeckSyncResult, DeckTick,
-                  DeckTonality, check, lib)
+from .abi import (DeckAnalysis, DeckBarPick, DeckBars, DeckBeats, DeckEcho, DeckFinegrid, DeckFinePick, DeckGrain, DeckGrid, DeckHead, DeckKeylock, DeckLoudness, DeckParams, DeckSyncResult, DeckTempomap,
+                  DeckTick, DeckTonality, check, lib)
 
 ONE = 1 << 32   # unity step / one track frame in Q32.32
 
@@ -392,6 +398,99 @@ def debug_last_bars() -> dict:
     return _debug_last(lib.mx_deck_debug_last_bars, ("wgs_half_one_tile", "wgs_half_tiled", "wgs_novelty", "novelties_defined"))
 
 
+def tempomap(hop=64, n_periods=1, period0_q16=4 << 16, dperiod_q16=0, window_hops=16, stride_hops=8) -> DeckTempomap:
+    """tempo map settings (the header's TEMPO MAP): candidate periods in hops of `hop` frames, Q16, searched in windows of window_hops every stride_hops"""
+    return DeckTempomap(int(hop), int(n_periods), int(period0_q16), int(dperiod_q16), int(window_hops), int(stride_hops), 0)
+
+
+def tempomap_check(s: DeckTempomap, n_frames: int) -> None:
+    """the tempo map setting rules alone for a track of n_frames (host only); raises MxError"""
+    check(lib.mx_deck_tempomap_check(C.byref(s), int(n_frames)))
+
+
+def tempomap_count(s: DeckTempomap, n_frames: int) -> int:
+    """V, the windows of a track of n_frames (host only)"""
+    n = C.c_uint32()
+    check(lib.mx_deck_tempomap_count(C.byref(s), int(n_frames), C.byref(n)))
+    return n.value
+
+
+def tempomap_span(centre_q16: int, halfwidth_q16: int, window_beats: int, stride_beats: int, n_hops: int, hop: int):
+    """the settings of a windowed search round a centre period (mx_deck_tempomap_span, host only, pure): (DeckTempomap, clipped)"""
+    s, clipped = DeckTempomap(), C.c_uint32()
+    check(lib.mx_deck_tempomap_span(int(centre_q16), int(halfwidth_q16), int(window_beats), int(stride_beats), int(n_hops), int(hop), C.byref(s), C.byref(clipped)))
+    return s, bool(clipped.value)
+
+
+def tempomap_host(interleaved_i16: np.ndarray, s: DeckTempomap, onsets: bool = False):
+    """the tempo map rules in plain C++ on the host (pure): abi.DECK_COMB_DTYPE[V, n_periods], and with onsets=True (records, w as uint32[N])"""
+    x = np.ascontiguousarray(interleaved_i16, dtype=np.int16).reshape(-1)
+    V = tempomap_count(s, x.size // 2)   # before a buffer is sized from the settings
+    recs = np.zeros((V, s.n_periods), abi.DECK_COMB_DTYPE)
+    w = np.zeros(finegrid_count(x.size // 2, s.hop), np.uint32) if onsets else None
+    check(lib.mx_deck_tempomap_host(x.ctypes.data_as(C.c_void_p), x.size // 2, C.byref(s), recs.ctypes.data_as(C.c_void_p), w.ctypes.data_as(C.c_void_p) if onsets else None))
+    return (recs, w) if onsets else recs
+
+
+def tempomap_path(recs: np.ndarray, penalty: int) -> np.ndarray:
+    """one candidate index per window, uint32[V], through records of shape [V, n_periods] (mx_deck_tempomap_path, host only, pure); penalty 0 is the per-window pick"""
+    r = np.ascontiguousarray(recs, dtype=abi.DECK_COMB_DTYPE)
+    if r.ndim != 2 or not r.size:
+        raise abi.MxError(abi.MX_ERR_INVALID, "recs must have the shape [windows, n_periods], neither 0")
+    if not 0 <= int(penalty) < 1 << 64:
+        raise abi.MxError(abi.MX_ERR_INVALID, "penalty outside uint64")
+    index = np.zeros(r.shape[0], np.uint32)
+    check(lib.mx_deck_tempomap_path(r.ctypes.data_as(C.c_void_p), r.shape[0], r.shape[1], int(penalty), index.ctypes.data_as(C.c_void_p)))
+    return index
+
+
+def tempomap_segments(recs: np.ndarray, s: DeckTempomap, n_frames: int, index: np.ndarray) -> np.ndarray:
+    """abi.DECK_TEMPO_SEGMENT_DTYPE[V]: the path's grids, starts and flags (mx_deck_tempomap_segments, host only, pure)"""
+    V = tempomap_count(s, n_frames)
+    r = np.ascontiguousarray(recs, dtype=abi.DECK_COMB_DTYPE).reshape(-1)
+    ix = np.ascontiguousarray(index, dtype=np.uint32).reshape(-1)
+    if r.size != V * s.n_periods or ix.size != V:
+        raise abi.MxError(abi.MX_ERR_INVALID, "recs / index do not have the settings' windows x n_periods / windows")
+    segs = np.zeros(V, abi.DECK_TEMPO_SEGMENT_DTYPE)
+    check(lib.mx_deck_tempomap_segments(r.ctypes.data_as(C.c_void_p), C.byref(s), int(n_frames), ix.ctypes.data_as(C.c_void_p), segs.ctypes.data_as(C.c_void_p)))
+    return segs
+
+
+def tempomap_at(segs: np.ndarray, pos_q32: int):
+    """(DeckBeats, segment): the grid in force at pos_q32 and its segment's index (mx_deck_tempomap_at, host only, pure)"""
+    g = np.ascontiguousarray(segs, dtype=abi.DECK_TEMPO_SEGMENT_DTYPE).reshape(-1)
+    grid, seg = DeckBeats(), C.c_uint32()
+    check(lib.mx_deck_tempomap_at(g.ctypes.data_as(C.c_void_p) if g.size else None, g.size, int(pos_q32), C.byref(grid), C.byref(seg)))
+    return grid, seg.value
+
+
+def tempomap_step(grid: DeckBeats, out_period_q32: int) -> int:
+    """the step at which the beats of `grid` come out out_period_q32 / 2^32 output frames apart (mx_deck_tempomap_step, host only, pure, exact)"""
+    step = C.c_int64()
+    check(lib.mx_deck_tempomap_step(C.byref(grid), int(out_period_q32), C.byref(step)))
+    return step.value
+
+
+def tempomap_beats(segs: np.ndarray, end_q32: int) -> list:
+    """[(position, segment)]: the beats of the map in [0, end_q32), in Python integers -- per segment the lines b of its grid with start <= b and b + period / 2 <= the
+    next segment's start (the header's SEGMENTS); a segment without a period has none"""
+    out = []
+    for v, g in enumerate(segs):
+        first, period = int(g["first_q32"]), int(g["period_q32"])
+        if period <= 0:
+            continue
+        b = first + -((first - max(int(g["start_q32"]), 0)) // period) * period     # mx_deck_grid_next
+        last = v + 1 == len(segs)
+        while b < end_q32 and (last or b + period // 2 <= int(segs[v + 1]["start_q32"])):
+            out.append((b, v))
+            b += period
+    return out
+
+
+def debug_last_tempomap() -> dict:
+    return _debug_last(lib.mx_deck_debug_last_tempomap, ("wgs_staged", "wgs_global", "wgs_onset", "trip"))
+
+
 _NOT_GIVEN = object()   # Deck.analyse_finegrid: no settings argument at all, as against None
 
 
@@ -407,6 +506,7 @@ class Deck:
         self._loudness = None    # blocks
         self._finegrid = None    # (n_periods, hops)
         self._bars = None        # (n_beats, M + M Q)
+        self._tempomap = None    # (windows * n_periods, hops)
         check(lib.mx_deck_create(self.n_frames, device, C.byref(self._h)))
 
     def close(self):
@@ -608,6 +708,61 @@ class Deck:
         s = bars(grid, tables, **kw)
         self.analyse_bars(s)
         return bars_pick(self.read_bar_folds(), s)
+
+    def analyse_tempomap(self, s: DeckTempomap | None):
+        """score every candidate period in every window of the track, asynchronously on the deck's own stream; analyse_tempomap(None) frees the result"""
+        self._analyse(lib.mx_deck_analyse_tempomap, "_tempomap", s, lambda s: (tempomap_count(s, self.n_frames) * s.n_periods, finegrid_count(self.n_frames, s.hop)))
+
+    def read_tempomap(self, first: int = 0, n: int | None = None) -> np.ndarray:
+        """abi.DECK_COMB_DTYPE[n] of the tempo map, record (v, j) at v * n_periods + j; waits for it"""
+        n = ((self._tempomap or (0, 0))[0] - first) if n is None else n
+        out = np.zeros(max(1, n), abi.DECK_COMB_DTYPE)
+        check(lib.mx_deck_read_tempomap(self._h, int(first), int(n), out.ctypes.data_as(C.c_void_p)))
+        return out[:n]
+
+    def read_tempomap_onsets(self, first: int = 0, n: int | None = None) -> np.ndarray:
+        """the tooth weights w as uint32[n] of the tempo map; waits for it"""
+        n = ((self._tempomap or (0, 0))[1] - first) if n is None else n
+        w = np.zeros(max(1, n), np.uint32)
+        check(lib.mx_deck_read_tempomap_onsets(self._h, int(first), int(n), w.ctypes.data_as(C.c_void_p)))
+        return w[:n]
+
+    def map_tempo(self, pick_or_grid, hop: int = 64, window_beats: int = 16, stride_beats: int = 8, width: float = 0.06, penalty: int | None = None) -> np.ndarray:
+        """the tempo map round a whole-track grid (a DeckBeats, or refine_grid()'s pick, found at this hop): span (+-width of the period), analyse_tempomap, read, path,
+        segments; abi.DECK_TEMPO_SEGMENT_DTYPE[V].  penalty None: floor(the sum of the windows' best scores / (V * n_periods)) -- crossing the whole search range
+        costs what one window scores.  Waits for the device once.  A grid without a period (a silent track's pick) gives no segments."""
+        grid = getattr(pick_or_grid, "grid", pick_or_grid)
+        if not grid.period_q32 > 0:
+            return np.zeros(0, abi.DECK_TEMPO_SEGMENT_DTYPE)
+        centre = (grid.period_q32 >> 16) // hop
+        s, _ = tempomap_span(centre, int(centre * width), window_beats, stride_beats, finegrid_count(self.n_frames, hop), hop)
+        self.analyse_tempomap(s)
+        recs = self.read_tempomap().reshape(-1, s.n_periods)
+        if penalty is None:
+            penalty = sum(int(v) for v in recs["score"].max(axis=1)) // recs.size
+        return tempomap_segments(recs, s, self.n_frames, tempomap_path(recs, penalty))
+
+    def schedule_warp(self, segs: np.ndarray, out_period_q32: int, n_ticks: int, spt: int, p: DeckParams | None = None, seek: int | None = None) -> list:
+        """before a feed of n_ticks ticks of spt frames: walk the head through them as mx_deck_plan says and schedule, at every tick whose head stands in a segment
+        that wants another step than the one in force, that segment's mx_deck_tempomap_step -- the rest of the parameters stay.  p and seek, when given, are what the
+        host would have handed to set() and seek() for tick 0 (the warp's own event there replaces them, so they go through here); p's step is the map's from the
+        start.  [(tick, segment, step)] of the step changes.  Nothing is remembered between calls: the head and its parameters say all there is."""
+        head, out = self.state(), []
+        for k in range(n_ticks):
+            base = p if k == 0 and p is not None else None
+            sk = seek if k == 0 else None
+            q = base if base is not None else head.params
+            grid, seg = tempomap_at(segs, sk if sk is not None else head.pos_q32)
+            new = base
+            if grid.period_q32 > 0:
+                step = tempomap_step(grid, out_period_q32)
+                if step != q.step_q32:
+                    new = DeckParams(step, q.slew_q32, q.loop_in, q.loop_out, q.flags, 0)
+                    out.append((k, seg, step))
+            if new is not None or sk is not None:
+                self.schedule(k, new, sk)
+            _, head = deck_plan(head, spt, self.n_frames, new, sk)
+        return out
 
     def state(self) -> DeckHead:
         h = DeckHead()
