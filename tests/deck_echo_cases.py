@@ -1,5 +1,5 @@
 """The echo's shared cases (tests/test_cpu_deck_echo.py, tests/test_gpu_deck_echo.py): a deck script (tests/deck_cases.py's vocabulary) and an echo script, tick by
-tick, at the two real tick lengths.  The smallest shapes at which the kernel can still go wrong: delays at the floor and one above it (blocks of 255 and 256 frames,
+tick, at the two real tick lengths and at the suite's two tiny ones (16 frames and one frame a tick).  The smallest shapes at which the kernel can still go wrong: delays at the floor and one above it (blocks of 255 and 256 frames,
 the ring index wrapping), delays around the tick length on both sides of the one-block threshold D > spt, blocks that straddle tick boundaries, a tick that
 lowers the delay under a running block, off and on inside a feed, and a tail that runs into f32 subnormals.
 
@@ -20,6 +20,7 @@ Feed = namedtuple("Feed", "n_ticks deck echo")
 Case = namedtuple("Case", "name spt n_frames feeds keylock identity", defaults=(None, False))
 
 LONG_SPT = 1 << 20       # MX_DECK_MAX_SPT: one tick carries the clock past the ring's 2^19 frames
+LONG_FEEDS = {16: 64, 1: 600}    # tick length -> the ticks of its cases' one feed, more than the other cases' graphs hold
 
 
 def track(case: Case) -> np.ndarray:
@@ -55,6 +56,14 @@ def _cases():
     out.append(Case("subnormal tail", 800, 300, tail))
     # the longest delay, the clock past 2^19 inside one tick: two feeds of one tick of 2^20 frames, all but the first 4097 frames silence
     out.append(Case("delay 262144, ring wrap", LONG_SPT, 4097, [Feed(1, [(0, dc.play(ONE), 0)], [(0, Echo(262144, 1.0, 0.5, 1.0, 0.3, PINGPONG))]), Feed(1, [], [])], None, True))
+    # the suite's tiny ticks: a block of D - 1 frames spans 16 or 17 ticks of 16 frames (echo_block_end across many tick boundaries, ending inside a tick or on its edge)
+    for D, kw in ((256, dict(feedback=0.6, damp=0.3)), (257, dict(feedback=-0.6, flags=PINGPONG))):
+        out.append(simple(f"delay {D}, 16 frames a tick", 16, Echo(D, **kw), n_ticks=LONG_FEEDS[16]))
+    # ... and 255 ticks of one frame, where the ramp weight n / spt is always 0: tick 300 changes the three gains alone and sounds the old ones whole; 256 -> 300 at tick 400 (the
+    # new delay reads the line the old one wrote), off at 500, on again at 520
+    out.append(Case("one frame a tick", 1, 4097, [Feed(LONG_FEEDS[1], [(0, dc.play(ONE), 0)],
+                                                       [(0, Echo(256, 1.0, 0.6, 1.0, 0.0)), (300, Echo(256, 0.5, -0.8, 2.0, 0.0)), (400, Echo(300, 0.5, -0.8, 2.0, 0.3)), (500, OFF),
+                                                        (520, Echo(256, 1.0, 0.5, 1.0, 0.0, PINGPONG))])]))
     return out
 
 

@@ -20,6 +20,9 @@ Echo = namedtuple("Echo", "delay send feedback wet damp flags", defaults=(1.0, 0
 OFF = "off"
 
 MISREADINGS = ("r_from_y", "ramp_n_plus_1", "ramp_f32", "delay_from_tick_start", "pingpong_crosses_x", "seek_restarts", "line_kept_off_on", "block_plus_one")
+# two more that only a feed of several ticks can show, switched on by the random deck sessions (tests/random_decks.py) alone: the ramp weight running over the whole
+# feed instead of the tick, and a feed of several blocks that reads the line as it stood before the feed (what it wrote itself reads as zero)
+FEED_MISREADINGS = ("ramp_over_feed", "walk_as_one_block")
 
 
 def check(e: Echo) -> str | None:
@@ -81,10 +84,12 @@ class EchoModel:
     """mx_deck_set_echo / mx_deck_schedule_echo and the echo pass of mx_deck_feed on the host"""
 
     def __init__(self, mis=()):
+        assert all(m in MISREADINGS + FEED_MISREADINGS for m in mis), mis
         self.mis = mis
         self.on, self.set, self.t = False, Echo(0, 0.0, 0.0, 0.0, 0.0, 0), 0
         self.hist = np.zeros((1 << 12, 2), np.float32)   # r[0 .. t)
         self.sched: dict[int, object] = {}
+        self.stale_from = None                           # walk_as_one_block: the clock from which the line reads as zero
 
     def schedule(self, tick: int, e):
         """e: an Echo, or OFF"""
@@ -98,6 +103,8 @@ class EchoModel:
         """r[s] as f64 (len, 2), zero for s < 0"""
         out = self.hist[np.clip(s, 0, None)].astype(np.float64)
         out[s < 0] = 0.0
+        if self.stale_from is not None:
+            out[s >= self.stale_from] = 0.0
         return out
 
     def run(self, x: np.ndarray, spt: int, seeks=()) -> np.ndarray:
@@ -110,13 +117,14 @@ class EchoModel:
         sched, self.sched = self.sched, {}
         # the misreading that lives in the block cut: the last frame of a block one frame too long reads its tap at s + 1 before the block's first frame wrote it
         stale = set()
+        on, st, delays = self.on, self.set, []
+        for k in range(n_ticks):
+            if k in sched:
+                on = sched[k] is not OFF
+                st = sched[k] if on else st
+            delays.append(st.delay if on else 0)
+        self.stale_from = self.t if "walk_as_one_block" in self.mis and len(cut(spt, delays)) > 1 else None
         if "block_plus_one" in self.mis:
-            on, st, delays = self.on, self.set, []
-            for k in range(n_ticks):
-                if k in sched:
-                    on = sched[k] is not OFF
-                    st = sched[k] if on else st
-                delays.append(st.delay if on else 0)
             for first, frames in cut(spt, delays, self.mis):
                 stale |= {g for g in range(max(first, first + frames - 2), first + frames) if g - delays[g // spt] + 1 >= first}
         for k in range(n_ticks):
@@ -131,6 +139,7 @@ class EchoModel:
                         old = (np.float32(0.0),) * 3
                         if "line_kept_off_on" not in self.mis:
                             self.t = 0
+                            self.stale_from = 0 if self.stale_from is not None else None
                     self.on, self.set, ramp = True, e, True
             if not self.on:
                 continue
@@ -165,7 +174,11 @@ class EchoModel:
                         xs = xs[:, ::-1]
                     else:
                         r0, rm, rp = r0[:, ::-1], rm[:, ::-1], rp[:, ::-1]
-                if ramp:
+                if ramp and "ramp_over_feed" in self.mis:
+                    w = (k * spt + n).astype(np.float64) / np.float64(n_ticks * spt)
+                    g = [(np.float64(o) + (np.float64(v) - np.float64(o)) * w).astype(np.float32) for o, v in zip(old, new)]
+                    send, fb, wet = (v.astype(np.float64)[:, None] for v in g)
+                elif ramp:
                     if "ramp_f32" in self.mis:
                         w = ((n + (1 if "ramp_n_plus_1" in self.mis else 0)).astype(np.float32) / np.float32(spt)).astype(np.float32)
                         g = [(o + ((v - o) * w).astype(np.float32)).astype(np.float32) for o, v in zip(old, new)]
@@ -182,4 +195,5 @@ class EchoModel:
                 y[k, n0:n1] = yy
                 n0 = n1
             self.t += spt
+        self.stale_from = None
         return y.reshape(-1)

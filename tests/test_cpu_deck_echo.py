@@ -320,6 +320,53 @@ def test_a_misreading_changes_a_compared_sample_of_the_case_named(tables, truth,
     assert changed, mis
 
 
+TINY = ("delay 256, 16 frames a tick", "delay 257, 16 frames a tick", "one frame a tick")
+
+
+@pytest.mark.parametrize("name", TINY)
+def test_the_tiny_tick_cases_are_heard_and_their_blocks_span_many_ticks(truth, name):
+    """after frame D more than half the frames differ from dry; a block of D - 1 frames spans 16 or 17 ticks of 16 frames, 255 of one"""
+    c = ec.BY_NAME[name]
+    assert c in ec.QUICK and ec.LONG_FEEDS[c.spt] == ec.flatten(c)[0]
+    (x,), ((y,), _st) = truth[name]
+    D = c.feeds[0].echo[0][1].delay
+    differ = np.any((bits(x) != bits(y)).reshape(-1, 2)[D:], axis=1)
+    assert 2 * int(differ.sum()) > differ.size, (int(differ.sum()), differ.size)
+    (delays,) = ec.delays_of(c)
+    spans = [(first + n - 1) // c.spt - first // c.spt + 1 for first, n in em.cut(c.spt, delays)]
+    assert spans[0] == -(-(D - 1) // c.spt) and max(spans) <= spans[0] + 1 + (299 - 255 if c.spt == 1 else 0), spans      # 16 ticks or 255, later ones a tick more
+
+
+def test_at_one_frame_a_tick_the_ramp_tick_sounds_the_old_gains_whole(tables, truth):
+    c = ec.BY_NAME["one frame a tick"]
+    (x,), ((y,), _st) = truth[c.name]
+    feed = c.feeds[0]
+    later = c._replace(feeds=[feed._replace(echo=[(t + 1 if t == 300 else t, e) for t, e in feed.echo])])       # the same gains a tick later
+    (z,), _ = ec.run_model(later, tables, xs=[x])
+    y, z = bits(y).reshape(-1, 2), bits(z).reshape(-1, 2)
+    assert np.array_equal(y[:301], z[:301]) and not np.array_equal(y[301], z[301])
+    # ... and the line too: frame 300 + 256 reads what tick 300 wrote with the old send and feedback
+    never = c._replace(feeds=[feed._replace(echo=[(t, e) for t, e in feed.echo if t not in (300, 400)])])
+    m_y, m_n = EchoModel(), EchoModel()
+    for m, case in ((m_y, c), (m_n, never)):
+        for t, e in case.feeds[0].echo:
+            if t < 400:
+                m.schedule(t, e)
+        m.run(x[:2 * 400], 1)
+    assert np.array_equal(bits(m_y.hist[:301]), bits(m_n.hist[:301])) and not np.array_equal(bits(m_y.hist[301]), bits(m_n.hist[301]))
+
+
+def test_the_tiny_tick_cases_tell_the_model_from_the_misreadings_a_tick_of_their_length_can_show(tables, truth):
+    """at one frame a tick the two roundings of the ramp weight agree (the weight is 0), nothing seeks, and what a frame past 256 writes into the line -- where a
+    feedback taken from y, or a block a frame too long, would show -- is first read at tick 557, with the echo off; every other misreading changes a sample.
+    The damped case of 16 frames a tick shows those two; it has one setting without ping-pong from tick 0 on, ramped from 0 with weights n / 16 that both roundings hold exactly."""
+    for name, blind in (("one frame a tick", {"ramp_f32", "seek_restarts", "r_from_y", "block_plus_one"}), ("delay 256, 16 frames a tick", {"ramp_f32", "seek_restarts", "line_kept_off_on", "delay_from_tick_start", "pingpong_crosses_x"})):
+        c = ec.BY_NAME[name]
+        xs, (want, _st) = truth[name]
+        caught = {mis for mis in em.MISREADINGS if np.any(bits(np.concatenate(ec.run_model(c, tables, mis=(mis,), xs=xs)[0])) != bits(np.concatenate(want)))}
+        assert caught == set(em.MISREADINGS) - blind, (name, sorted(set(em.MISREADINGS) - caught))
+
+
 def test_the_cases_reach_both_forms_and_a_block_across_a_tick_boundary():
     one = seq = crossing = 0
     for c in ec.CASES:     # as given and tick by tick, the two groupings the device suite plays

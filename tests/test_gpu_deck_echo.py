@@ -2,7 +2,11 @@
 against the Python model (tests/deck_echo_model.py) applied to what DeckModel / KeylockModel say the deck wrote, over the shared cases (tests/deck_echo_cases.py):
 every delay of the list in one feed of 12 ticks (the sequential form, blocks across tick boundaries) and tick by tick (the one-block form where D > spt), the
 schedule inside a feed under three groupings, the echo-out plain, key-locked and looped, the subnormal tail, the ring wrap at the longest delay, several decks in one
-feed, and the refusals, which leave deck and echo where they stood."""
+feed, the refusals, which leave deck and echo where they stood, the suite's tiny ticks (16 frames and one frame), and what the header's CLOCK paragraph says does
+not restart the clock or clear the line: a feed into another graph handle, of the same tick length or another, a graph that adopted the last one's state, a load and
+mx_deck_set_keylock."""
+import copy
+
 import numpy as np
 import pytest
 
@@ -10,6 +14,7 @@ import deck_cases as dc
 import deck_echo_cases as ec
 import deck_echo_model as em
 from deck_echo_model import OFF, PINGPONG, Echo
+from deck_keylock_model import Keylock, KeylockModel
 from deck_model import ONE
 from mixlab_amd import abi, deck
 from mixlab_amd.workspace import Workspace
@@ -41,7 +46,7 @@ def graph_for(spt: int):
             mix = ws.mixer([(0.0, 1.0, False)] * N_SRC)
             for k, s in enumerate(srcs):
                 ws.connect(s, 0, mix, k)
-            _graphs[spt] = (ws.build(max_ticks_per_run=MAX_TICKS), srcs, [0])
+            _graphs[spt] = (ws.build(max_ticks_per_run=max(MAX_TICKS, ec.LONG_FEEDS.get(spt, 0))), srcs, [0])
     return _graphs[spt]
 
 
@@ -145,7 +150,9 @@ ONE_BLOCK = [c for c in ec.CASES if c.spt != ec.LONG_SPT and min(d for ds in ec.
 def test_tick_by_tick_every_feed_takes_the_one_block_form_and_equals_the_model(case, tables):
     total = ec.flatten(case)[0]
     _p, _s, counts = check_case(case, tables, [1] * total)
-    assert counts["decks_one_block"] == total and counts["decks_sequential"] == 0
+    # a tick with the echo off launches none: the one case whose echo is off for a while, ticks 500 .. 519 of 600, has 20 feeds fewer
+    assert counts["decks_one_block"] == (total - 20 if case.name == "one frame a tick" else total) and counts["decks_sequential"] == 0
+    assert counts["decks_one_block"] == sum(1 for (d,) in ec.delays_of(case, [1] * total) if d)
 
 
 def test_the_list_of_one_block_cases_holds_the_delays_just_above_the_threshold():
@@ -154,11 +161,12 @@ def test_the_list_of_one_block_cases_holds_the_delays_just_above_the_threshold()
     assert "delay 441, 441 frames a tick" not in names and "delay 800, 800 frames a tick" not in names     # D = spt is two blocks: spt - 1 frames and one
 
 
-@pytest.mark.parametrize("name", ("schedules inside a feed", "delay 256, 441 frames a tick", "delay 801, 800 frames a tick"))
+@pytest.mark.parametrize("name", ("schedules inside a feed", "delay 256, 441 frames a tick", "delay 801, 800 frames a tick", "delay 257, 16 frames a tick", "one frame a tick"))
 def test_any_grouping_of_ticks_into_feeds_gives_the_same_ports_and_echo_state(name, tables):
     case = ec.BY_NAME[name]
-    (ref,), (ref_state,), _ = check_case(case, tables)                       # one feed of 12
-    for split in ([1] * 12, [5, 7]):
+    total = ec.flatten(case)[0]
+    (ref,), (ref_state,), _ = check_case(case, tables)                       # one feed of 12, 64 or 600
+    for split in ([1] * total, [5, total - 5]):
         ports, states, _ = check_case(case, tables, split)
         assert_bits(np.concatenate(ports), ref, f"{name}: {split}")
         assert states[-1] == ref_state
@@ -285,3 +293,101 @@ def test_a_feed_in_which_the_echo_is_off_in_every_tick_launches_no_echo(tables):
     t, on, e = state_tuple(d)
     assert (t, on, e[0]) == (800, False, 802)
     d.close()
+
+
+# ---- "nothing else restarts the clock or clears the line": one deck and one EchoModel carried across every feed ----
+class Carried:
+    """an echoing deck with its models.  feed() plays n ticks into whatever graph, holds the port and the echo state to the models, and shows that the line
+    mattered: the same feed over a line of zeros would have given other samples"""
+
+    def __init__(self, tables, name, n_frames=12000):
+        tr = dc.track("echo " + name, n_frames)
+        self.d, self.m, self.e, self.at = deck.Deck(n_frames), KeylockModel(tr.copy(), tables), em.EchoModel(), {}
+        self.d.load(tr)
+
+    def play(self, p, seek=None):
+        self.d.schedule(0, c_params(p), seek)
+        self.m.schedule(0, p, seek)
+
+    def feed(self, g, src, spt, n, label, ringing=True):
+        deck.feed([self.d], [src], g, n)
+        at = self.at.get(id(g), 0)
+        g.run_ticks(at, n)
+        self.at[id(g)] = at + n
+        x = self.m.feed(n, spt)[0]
+        cleared = copy.deepcopy(self.e)
+        cleared.hist[:] = 0
+        want = self.e.run(x, spt)
+        assert_bits(g.read_output(src, 0, n, True), want, label)
+        assert state_tuple(self.d) == model_state(self.e.state()), label
+        assert not ringing or not np.array_equal(want.view(np.uint32), cleared.run(x, spt).view(np.uint32)), f"{label}: the line is not heard"
+        return x, want
+
+
+def lone_graph(spt, like=None):
+    """(Workspace, graph, node) of one stereo source feeding nothing; like: the Workspace to build once more"""
+    ws = like or Workspace(*dc.rate_of(spt))
+    src = 0 if like else ws.source_stereo()
+    return ws, ws.build(max_ticks_per_run=MAX_TICKS), src
+
+
+def ringing_deck(tables, name, g, src, spt):
+    c = Carried(tables, name)
+    c.play(dc.play(ONE), 0)
+    e = Echo(900, 1.0, 0.7, 1.0, 0.3, PINGPONG)
+    c.d.set_echo(c_echo(e))
+    c.e.schedule(0, e)
+    c.feed(g, src, spt, 3, f"{name}: the first feed", ringing=False)
+    return c
+
+
+def test_a_feed_into_another_graph_handle_neither_restarts_the_clock_nor_clears_the_line(tables):
+    """A, then B of the same tick length with the deck stopped -- what B's port holds is the line A wrote --, then A again"""
+    (_wa, ga, sa), (_wb, gb, sb) = lone_graph(800), lone_graph(800)
+    c = ringing_deck(tables, "two graphs", ga, sa, 800)
+    c.play(dc.play(ONE, on=False))
+    x, y = c.feed(gb, sb, 800, 2, "into B")
+    assert not x.any() and y.any()
+    c.play(dc.play(ONE))
+    c.feed(ga, sa, 800, 3, "into A again")
+    assert state_tuple(c.d)[0] == 8 * 800
+    c.d.close(); ga.close(); gb.close()
+
+
+def test_a_graph_of_another_tick_length_takes_the_deck_with_clock_and_line_as_they_stand(tables):
+    (_wa, ga, sa), (_wb, gb, sb) = lone_graph(800), lone_graph(441)
+    c = ringing_deck(tables, "two tick lengths", ga, sa, 800)
+    c.feed(gb, sb, 441, 5, "into 441 frames a tick")          # D = 900 covers two ticks of 441: a walk of blocks where A's ticks were one block each
+    assert state_tuple(c.d)[0] == 3 * 800 + 5 * 441
+    c.feed(ga, sa, 800, 2, "back into 800 frames a tick")
+    assert state_tuple(c.d)[0] == 5 * 800 + 5 * 441
+    c.d.close(); ga.close(); gb.close()
+
+
+def test_a_graph_that_adopted_the_state_of_the_one_last_fed_goes_on_with_clock_and_line(tables):
+    ws, ga, src = lone_graph(800)
+    c = ringing_deck(tables, "adopted", ga, src, 800)
+    _ws, gb, _src = lone_graph(800, like=ws)
+    gb.adopt_state(ga, [0])
+    c.at[id(gb)] = c.at[id(ga)]
+    c.feed(gb, src, 800, 4, "into the graph built anew")
+    assert state_tuple(c.d)[0] == 7 * 800
+    c.d.close(); ga.close(); gb.close()
+
+
+def test_a_load_and_set_keylock_on_and_off_between_feeds_leave_clock_and_line(tables):
+    _ws, g, src = lone_graph(800)
+    c = ringing_deck(tables, "load and key-lock", g, src, 800)
+    piece = dc.track("echo load and key-lock, loaded", 3000)             # over the frames the head plays next (it stands at 2400)
+    c.d.load(piece, 2000)
+    c.m.load(2000, piece)
+    c.feed(g, src, 800, 2, "after the load")
+    kl = Keylock(ONE, 256, 64, 5)
+    c.d.set_keylock(deck.keylock(*kl))
+    c.m.set_keylock(kl)
+    c.feed(g, src, 800, 2, "key-lock on")
+    c.d.set_keylock(None)
+    c.m.set_keylock(None)
+    c.feed(g, src, 800, 2, "key-lock off")
+    assert state_tuple(c.d)[0] == 9 * 800
+    c.d.close(); g.close()
