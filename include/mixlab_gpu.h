@@ -57,6 +57,8 @@ extern "C" {
                               *    mx_deck_finegrid_pick, mx_deck_finegrid_period, mx_deck_sync, mx_deck_debug_last_finegrid;
                               *    mx_deck_echo, mx_deck_set_echo, mx_deck_schedule_echo, mx_deck_echo_check, mx_deck_echo_delay, mx_deck_echo_state, mx_deck_echo_plan,
                               *    mx_deck_debug_last_echo;
+                              *    mx_deck_filter, mx_deck_filter_carry, mx_deck_set_filter, mx_deck_schedule_filter, mx_deck_filter_check, mx_deck_filter_state,
+                              *    mx_deck_read_filter_state, mx_deck_filter_design, mx_deck_filter_knob, mx_deck_filter_host, mx_deck_debug_last_filter;
                               *    mx_deck_bars, mx_deck_beat, mx_deck_bar_pick, mx_deck_bars_check, mx_deck_bars_count, mx_deck_bars_tables, mx_deck_analyse_bars,
                               *    mx_deck_read_bars, mx_deck_read_bar_folds, mx_deck_bars_host, mx_deck_bars_pick, mx_deck_grid_next, mx_deck_debug_last_bars;
                               *    mx_deck_tempomap, mx_deck_tempo_segment, mx_deck_tempomap_check, mx_deck_tempomap_count, mx_deck_tempomap_span, mx_deck_tempomap_host,
@@ -992,7 +994,7 @@ int mx_deck_debug_last_keylock(uint32_t out[4]);
  * BLOCKS     (how the device runs it; mx_deck_echo_plan restates it.)  Frame t reads the line no later than t - D + 1, so the frames of a block [t0, t0 + B) are
  *            independent of one another when t - D(t) + 1 < t0 for every frame of it; with one delay, B <= D - 1.  A deck's echo frames of a feed are cut greedily
  *            into maximal such blocks, a tick without an echo always ending one; the cut holds across a tick that lowers the delay.
- * Out of scope: delays under 256 frames (flanger, chorus), modulated or interpolated delay, a resonant sweep filter, reverb, the echo on ports other than a deck's
+ * Out of scope: delays under 256 frames (flanger, chorus), modulated or interpolated delay, reverb, the echo on ports other than a deck's
  * source, more than two channels.
  */
 #define MX_DECK_ECHO_PINGPONG 1u
@@ -1018,6 +1020,95 @@ int mx_deck_echo_plan(uint32_t spt, const uint32_t* delay, uint32_t n_ticks, uin
  * a single block: a lane per frame, no barrier), out[1] decks in the sequential form (one workgroup walks the deck's blocks in order), out[2] the blocks those walked,
  * out[3] those of them that cross a tick boundary.  All zero for a feed in which no deck has an echo. */
 int mx_deck_debug_last_echo(uint32_t out[4]);
+
+/* ---- FILTER: a resonant sweep filter behind the deck, ahead of the echo ----
+ * BUILD-SPECIFIED.  An optional pass of a deck, set by mx_deck_set_filter / mx_deck_schedule_filter: the one-knob filter of a transition, a trapezoidal
+ * (topology-preserving) state-variable filter of second order whose one core gives low-pass, high-pass, band-pass and notch, and which stays stable while its
+ * coefficients move -- a sweep is nothing but moving coefficients.  It runs in place on what the deck wrote into its SOURCE_STEREO node's port, by the plain deck's
+ * rule or by key-lock's, and the echo behind it (ECHO above) reads the filtered samples: the order is feed / key-lock -> filter -> echo, so an echo-out under a
+ * closing low-pass sends the filtered sound down the line, and the tail already in the line is not filtered again.  The head, the tick records and the grains are
+ * what they were.  A deck that never sets a filter is untouched in every respect, and a feed in which no deck has a filter launches nothing new and uploads no
+ * further byte.
+ *
+ * SETTINGS   mx_deck_filter: kind one of MX_DECK_FILTER_LP / HP / BP / NOTCH; g = tan(pi fc / rate) with MX_DECK_FILTER_MIN_G (2^-12) <= g <= MX_DECK_FILTER_MAX_G
+ *            (16); k = 1 / Q with MX_DECK_FILTER_MIN_K (0.05) <= k <= MX_DECK_FILTER_MAX_K (2); 0 <= wet <= 1; all three finite; flags and _pad 0.  The bounds are
+ *            compared as f32 (0.05 is the f32 nearest to it).  mx_deck_filter_design turns a cutoff and a Q into g and k, mx_deck_filter_knob a DJ knob into both.
+ * STATE      four f64 values per deck, s1 and s2 of L, then s1 and s2 of R, in device memory the deck owns (32 bytes, allocated at the first setting).  All four
+ *            are zero at the first tick that runs with a filter after creation or after a tick without one: off -> on starts clean.  Nothing else clears them: not
+ *            a seek, a load, a change of PLAY, of step or of settings (a change of kind included), mx_deck_set_keylock, an echo setting, a feed into another graph
+ *            handle, nor a graph that adopted another's state.  The filter runs on EVERY frame the deck is fed while it is on: playing ticks, ticks written as
+ *            zeros (not playing), BEFORE / PAST ticks.  That is how a stopped deck's resonance rings out.
+ * PER FRAME  the tick has spt frames.  For frame n of the tick, n = 0 .. spt - 1, and channel c, x = (double) of the f32 the deck wrote.  Every multiply, add and
+ *            divide is a separate f64 operation, never fused, in exactly this order and association:
+ *                w  = (double)n / (double)spt                                          (ramp ticks only, see RAMPS)
+ *                gn = g_old + (g_new - g_old) * w                                      (f64 throughout, g_old and g_new the f32 settings widened; a tick
+ *                kn = k_old + (k_new - k_old) * w                                       without a ramp: gn = (double)g_new, kn = (double)k_new,
+ *                wn = wet_old + (wet_new - wet_old) * w                                 wn = (double)wet_new)
+ *                d  = 1.0 + gn * (gn + kn);   a1 = 1.0 / d;   a2 = gn * a1;   a3 = gn * a2
+ *                v3 = x - s2
+ *                v1 = a1 * s1 + a2 * v3
+ *                v2 = s2 + (a2 * s1 + a3 * v3)
+ *                s1 = (v1 + v1) - s1;   s2 = (v2 + v2) - s2
+ *                f  = LP: v2    BP: v1    HP: (x - kn * v1) - v2    NOTCH: x - kn * v1
+ *                y  = (float)(x + wn * (f - x))
+ *            y replaces x in the port; s1 and s2 are the channel's own.  Subnormal f32 values are kept, not flushed (numpy's casts are the model), and the f64
+ *            division is the correctly rounded one.  MX_FLAG_FP_CONTRACT does not apply.
+ * RAMPS      g, k and wet never jump inside the sound.  In the tick at which a setting takes effect (any mx_deck_set_filter / mx_deck_schedule_filter with settings,
+ *            also one that repeats them), the three go from the values of the tick before (`old`) to the new ones by the formulas above; in the first tick after
+ *            off -> on, g_old = g_new, k_old = k_new and wet_old = 0: a fade-in at the target cutoff, not a sweep from nowhere.  Every other tick uses the new
+ *            values as they stand.  kind switches at the tick's first frame.  Turning the filter off is a hard switch at a tick's first frame; a host that wants a
+ *            smooth exit schedules wet = 0 one tick earlier.  (In a tick of one frame w is always 0: the tick sounds the old values whole.)
+ * SCHEDULE   mx_deck_set_filter applies from tick 0 of the next feed, mx_deck_schedule_filter from the tick named; NULL settings turn the filter off from that
+ *            tick.  The rules are mx_deck_schedule_echo's: a later call for the same tick replaces an earlier one, the feed clears the schedule, a feed that does
+ *            not reach a scheduled tick fails with MX_ERR_INVALID and drops the schedules (the deck's own and the echo's too) -- the setting in force and the state
+ *            stay.  Settings that mx_deck_filter_check refuses leave everything as it was.
+ * IT FOLLOWS that the result does not depend on how ticks are grouped into feeds; that with wet = 0 the port holds the deck's own samples as numbers (y =
+ *            (float)(x + 0 * (f - x)): a -0 may come back as +0) while the state moves on all the same; that the two channels never meet; that the kind can change
+ *            without touching the state (s1 and s2 do not depend on it); and that a deck whose PLAY flag is cleared keeps ringing.
+ * Out of scope: a time-parallel, not bit-exact form of the recurrence; filters of other orders; drive or saturation; the filter on ports other than a deck's source;
+ * more than two channels; per-frame automation finer than the per-tick ramp.
+ */
+#define MX_DECK_FILTER_LP 0u
+#define MX_DECK_FILTER_HP 1u
+#define MX_DECK_FILTER_BP 2u
+#define MX_DECK_FILTER_NOTCH 3u
+#define MX_DECK_FILTER_MIN_G 0.000244140625f   /* 2^-12: 3.7 Hz at 48 kHz */
+#define MX_DECK_FILTER_MAX_G 16.0f             /* 0.48 of the rate */
+#define MX_DECK_FILTER_MIN_K 0.05f             /* Q = 20 */
+#define MX_DECK_FILTER_MAX_K 2.0f              /* Q = 1 / 2: two real poles at the same place */
+typedef struct { uint32_t kind; uint32_t flags; float g; float k; float wet; uint32_t _pad; } mx_deck_filter;   /* 24 bytes */
+/* What mx_deck_filter_host carries from one call to the next: the four state values (STATE's order), the last setting, whether the filter was on (1 / 0); _pad 0.
+ * All zero is a deck that never had a filter. */
+typedef struct { double s[4]; mx_deck_filter last; uint32_t on; uint32_t _pad; } mx_deck_filter_carry;   /* 64 bytes */
+/* The filter with these settings from tick 0 of the NEXT feed on; NULL: off from that tick.  mx_deck_schedule_filter(d, 0, f).  The first call with settings allocates
+ * the deck's state (32 bytes).  Settings that mx_deck_filter_check refuses: MX_ERR_INVALID, and the deck and its schedule keep what they had. */
+int mx_deck_set_filter(mx_deck* d, const mx_deck_filter* f);
+/* ... from tick `tick_in_feed` of the next feed on (SCHEDULE). */
+int mx_deck_schedule_filter(mx_deck* d, uint32_t tick_in_feed, const mx_deck_filter* f);
+/* Host only: the SETTINGS rules alone. */
+int mx_deck_filter_check(const mx_deck_filter* f);
+/* After the last feed: whether the filter is on (1 / 0) and the setting in force (the last one it had, when off; all zero before the first).  Host data: no
+ * synchronisation. */
+int mx_deck_filter_state(const mx_deck* d, uint32_t* on, mx_deck_filter* setting);
+/* Waits for the feed's kernels, then: the four state values as they stand after the last feed, in STATE's order -- or all zeros when the filter is off or was never on. */
+int mx_deck_read_filter_state(mx_deck* d, double s[4]);
+/* Host only: *out = { kind, 0, (float)tan(pi cutoff_hz / rate), (float)(1 / q), (float)wet, 0 }.  Uses libm: specified to 1 f32 ulp, not to the bit -- the bit-exact
+ * path starts at mx_deck_filter.  An argument that is not finite, rate or q not positive, a cutoff outside (0, rate / 2), or a result that mx_deck_filter_check
+ * refuses: MX_ERR_INVALID, *out untouched. */
+int mx_deck_filter_design(uint32_t kind, double cutoff_hz, double q, double rate, double wet, mx_deck_filter* out);
+/* Host only: the DJ mapping of one knob in -1 .. 1, on mx_deck_filter_design.  |knob| < 1/64: *on = 0, *out untouched (the dead zone: no filter).  knob in [-1, 0):
+ * *on = 1, a low-pass at 20000 (80 / 20000)^|knob| Hz; knob in (0, 1]: *on = 1, a high-pass at 20 (8000 / 20)^knob Hz; the cutoff no higher than 0.45 rate; wet 1.
+ * A knob outside -1 .. 1 or not finite, and what mx_deck_filter_design refuses: MX_ERR_INVALID. */
+int mx_deck_filter_knob(double knob, double rate, double q, mx_deck_filter* out, uint32_t* on);
+/* Host only, pure: PER FRAME and RAMPS in plain C++ over the caller's frames[n_ticks * spt * 2] (L R interleaved), in place.  settings[k] is the setting in force in
+ * tick k, NULL for a tick without a filter; every tick with a setting counts as one at which that setting takes effect (a setting that repeats the last ramps from
+ * equal values, which is the constant tick bit for bit).  *carry goes in as the last call left it (all zero at first) and comes out as this call leaves it; its s[] is
+ * zero when the last tick had no filter.  spt outside 1 .. MX_DECK_MAX_SPT, a setting or carried block the check refuses, NULL: MX_ERR_INVALID, nothing written. */
+int mx_deck_filter_host(float* frames, uint32_t spt, uint32_t n_ticks, const mx_deck_filter* const* settings, mx_deck_filter_carry* carry);
+/* DEBUG: the decks with a filter in any tick of the last mx_deck_feed of this process: out[0] those decks, out[1] their ticks with a ramp, out[2] their ticks with a
+ * filter and no ramp, out[3] the 64-frame super-blocks their waves walked (ceil(n_ticks spt / 64) per deck: the walk covers the feed).  All zero for a feed in which
+ * no deck has a filter. */
+int mx_deck_debug_last_filter(uint32_t out[4]);
 
 /* ---- ANALYSIS: the band waveform overview, the onset autocorrelation and the beat grid of a whole track, before it sounds ----
  * BUILD-SPECIFIED.  One pass over the track as it lies in device memory, on the deck's own load stream: what a host needs at load time -- the coloured overview

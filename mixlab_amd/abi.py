@@ -485,6 +485,23 @@ _proto("mx_deck_echo_delay", C.c_int, C.POINTER(DeckBeats), C.c_int64, C.c_uint3
 _proto("mx_deck_echo_state", C.c_int, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(DeckEcho))
 _proto("mx_deck_echo_plan", C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32))
 _proto("mx_deck_debug_last_echo", C.c_int, C.POINTER(C.c_uint32))
+# ... its sweep filter (the header's FILTER): a resonant state-variable filter per deck between the feed and the echo, scheduled per tick
+DECK_FILTER_LP, DECK_FILTER_HP, DECK_FILTER_BP, DECK_FILTER_NOTCH = 0, 1, 2, 3
+DECK_FILTER_MIN_G, DECK_FILTER_MAX_G = 2.0 ** -12, 16.0
+DECK_FILTER_MIN_K, DECK_FILTER_MAX_K = 0.05000000074505806, 2.0   # (0.05 as an f32)
+class DeckFilter(C.Structure):
+    _fields_ = [("kind", C.c_uint32), ("flags", C.c_uint32), ("g", C.c_float), ("k", C.c_float), ("wet", C.c_float), ("_pad", C.c_uint32)]
+class DeckFilterCarry(C.Structure):
+    _fields_ = [("s", C.c_double * 4), ("last", DeckFilter), ("on", C.c_uint32), ("_pad", C.c_uint32)]
+_proto("mx_deck_set_filter", C.c_int, C.c_void_p, C.POINTER(DeckFilter))
+_proto("mx_deck_schedule_filter", C.c_int, C.c_void_p, C.c_uint32, C.POINTER(DeckFilter))
+_proto("mx_deck_filter_check", C.c_int, C.POINTER(DeckFilter))
+_proto("mx_deck_filter_state", C.c_int, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(DeckFilter))
+_proto("mx_deck_read_filter_state", C.c_int, C.c_void_p, C.POINTER(C.c_double))
+_proto("mx_deck_filter_design", C.c_int, C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(DeckFilter))
+_proto("mx_deck_filter_knob", C.c_int, C.c_double, C.c_double, C.c_double, C.POINTER(DeckFilter), C.POINTER(C.c_uint32))
+_proto("mx_deck_filter_host", C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(DeckFilterCarry))
+_proto("mx_deck_debug_last_filter", C.c_int, C.POINTER(C.c_uint32))
 # ... its bars and phrases (the header's BARS): beat vectors, checkerboard novelty at two widths, and the folds the downbeat and the phrase line are picked from
 DECK_BARS_MAX_BEATS = 16384   # MX_DECK_BARS_MAX_BEATS
 DECK_BARS_MAX_FOLDS = 136     # MX_DECK_BARS_MAX_FOLDS

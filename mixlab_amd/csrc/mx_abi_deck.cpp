@@ -119,6 +119,40 @@ int mx_deck_echo_plan(uint32_t spt, const uint32_t* delay, uint32_t n_ticks, uin
 int mx_deck_debug_last_echo(uint32_t out[4]) {
     return guard([&] { REQUIRE(out, "out is NULL"); mx::deck_debug_last_echo(out); });
 }
+int mx_deck_set_filter(mx_deck* d, const mx_deck_filter* f) {
+    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.filter.schedule(0, f); });
+}
+int mx_deck_schedule_filter(mx_deck* d, uint32_t tick_in_feed, const mx_deck_filter* f) {
+    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.filter.schedule(tick_in_feed, f); });
+}
+int mx_deck_filter_check(const mx_deck_filter* f) {
+    return guard([&] { REQUIRE(f, "settings are NULL"); mx::deck_filter_check(*f); });
+}
+int mx_deck_filter_state(const mx_deck* d, uint32_t* on, mx_deck_filter* setting) {
+    return guard([&] {
+        REQUIRE(d && on && setting, "NULL argument");
+        const mx::DeckFilter::State& s = d->d.filter.state();
+        *on = s.on ? 1u : 0u; *setting = s.set;
+    });
+}
+int mx_deck_read_filter_state(mx_deck* d, double s[4]) {
+    return guard([&] { REQUIRE(d && s, "NULL argument"); d->d.filter.read_state(s); });
+}
+int mx_deck_filter_design(uint32_t kind, double cutoff_hz, double q, double rate, double wet, mx_deck_filter* out) {
+    return guard([&] { REQUIRE(out, "out is NULL"); mx::deck_filter_design(kind, cutoff_hz, q, rate, wet, *out); });
+}
+int mx_deck_filter_knob(double knob, double rate, double q, mx_deck_filter* out, uint32_t* on) {
+    return guard([&] { REQUIRE(out && on, "NULL argument"); mx::deck_filter_knob(knob, rate, q, *out, *on); });
+}
+int mx_deck_filter_host(float* frames, uint32_t spt, uint32_t n_ticks, const mx_deck_filter* const* settings, mx_deck_filter_carry* carry) {
+    return guard([&] {
+        REQUIRE(carry && (!n_ticks || (frames && settings)), "NULL argument");
+        mx::deck_filter_host(frames, spt, n_ticks, settings, *carry);
+    });
+}
+int mx_deck_debug_last_filter(uint32_t out[4]) {
+    return guard([&] { REQUIRE(out, "out is NULL"); const mx::DeckLastFilter last = mx::deck_last_filter(); for (int k = 0; k < 4; ++k) out[k] = last.out[k]; });
+}
 int mx_deck_analysis_check(const mx_deck_analysis* a) {
     return guard([&] { REQUIRE(a, "settings are NULL"); mx::deck_analysis_check(*a); });
 }

@@ -1,7 +1,7 @@
 // mx_deck.cpp -- the deck's host side: parameter rules, the per-tick state machine (mx_deck_plan), the coefficient tables, the track, and the feed that turns the
 // coming ticks of many decks into one descriptor block and one launch (include/mixlab_gpu.h "the deck").  Key-lock beside the feed is
 // mx_deck_keylock.cpp's, the echo behind it mx_deck_echo.cpp's (the feed asks each deck's DeckEcho for its ticks, uploads them with its own, launches, commits),
-// and each whole-track analysis has a file of its own (mx_deck_analysis.hpp).
+// the sweep filter between the two mx_deck_filter.cpp's (DeckFilter, the same protocol), and each whole-track analysis has a file of its own (mx_deck_analysis.hpp).
 #include "mx_deck.hpp"
 
 #include <algorithm>
@@ -202,6 +202,7 @@ struct FeedState {
     typedef DeckKlTick KlTick;
     std::vector<KlTick> last_kl; uint32_t kl_searched = 0, kl_unsearched = 0;   // ... and its key-locked ticks and grains, for mx_deck_debug_last_keylock
     std::vector<std::vector<uint32_t>> last_echo;                                // ... and per deck with an echo the delays of its ticks, for mx_deck_debug_last_echo
+    DeckLastFilter last_filter;                                                  // ... and the filter's four counters, for mx_deck_debug_last_filter
 } feed_state;
 }  // namespace
 
@@ -219,7 +220,7 @@ void deck_stream_retired(hipStream_t s) {
 }
 
 void Deck::feed(Deck* const* decks, const uint32_t* nodes, size_t n, Graph& g, uint32_t n_ticks) {
-    auto drop = [&] { for (size_t i = 0; i < n; ++i) if (decks && decks[i]) { decks[i]->sched_.clear(); decks[i]->echo.drop_schedule(); } };
+    auto drop = [&] { for (size_t i = 0; i < n; ++i) if (decks && decks[i]) { decks[i]->sched_.clear(); decks[i]->echo.drop_schedule(); decks[i]->filter.drop_schedule(); } };
     try {
         if (!n) return;
         if (!decks || !nodes) throw Error(MX_ERR_INVALID, "deck feed: decks / nodes is NULL");
@@ -237,6 +238,8 @@ void Deck::feed(Deck* const* decks, const uint32_t* nodes, size_t n, Graph& g, u
             uint32_t beyond = 0;
             if (decks[i]->echo.scheduled_beyond(n_ticks, beyond))
                 throw Error(MX_ERR_INVALID, "deck feed: deck " + std::to_string(i) + " has an echo scheduled at tick " + std::to_string(beyond) + ", beyond this feed");
+            if (decks[i]->filter.scheduled_beyond(n_ticks, beyond))
+                throw Error(MX_ERR_INVALID, "deck feed: deck " + std::to_string(i) + " has a filter scheduled at tick " + std::to_string(beyond) + ", beyond this feed");
         }
         {
             std::vector<const Deck*> d(decks, decks + n); std::vector<uint32_t> nd(nodes, nodes + n);
@@ -261,6 +264,15 @@ void Deck::feed(Deck* const* decks, const uint32_t* nodes, size_t n, Graph& g, u
         std::stable_partition(echoes.begin(), echoes.end(), [](const EchoPlan& e) { return e.one_block; });
         const size_t ne = echoes.size(), ne_block = (size_t)std::count_if(echoes.begin(), echoes.end(), [](const EchoPlan& e) { return e.one_block; });
         const size_t echo_bytes = ne * sizeof(EchoDeckDev) + ne * (size_t)n_ticks * sizeof(EchoTickDev);
+        // ... and the sweep filter's, the same way: filters[] names the decks with a filter in any tick
+        struct FilterPlan { size_t deck; std::vector<FilterTickDev> ticks; };
+        std::vector<FilterPlan> filters;
+        std::vector<DeckFilter::State> filter_after(n);
+        for (size_t i = 0; i < n; ++i) {
+            std::vector<FilterTickDev> ft;
+            if (decks[i]->filter.plan(n_ticks, ft, filter_after[i])) filters.push_back(FilterPlan{i, std::move(ft)});
+        }
+        const size_t nf = filters.size(), filter_bytes = nf * sizeof(FilterDeckDev) + nf * (size_t)n_ticks * sizeof(FilterTickDev);
 
         std::lock_guard<std::mutex> lock(feed_state.mu);
         Slot& sl = feed_state.slots[feed_state.next];
@@ -272,7 +284,8 @@ void Deck::feed(Deck* const* decks, const uint32_t* nodes, size_t n, Graph& g, u
         const size_t head_bytes = (n * sizeof(DeckDev) + 15) & ~(size_t)15, plain_bytes = (head_bytes + n * (size_t)n_ticks * sizeof(DeckTickDev) + 15) & ~(size_t)15;
         const size_t feed_bytes = nk ? plain_bytes + nk * sizeof(KlDeckDev) + nk * (size_t)n_ticks * sizeof(KlTickDev) + grain_cap * sizeof(KlGrainIn)
                                      : head_bytes + n * (size_t)n_ticks * sizeof(DeckTickDev);
-        const size_t bytes = ne ? ((feed_bytes + 15) & ~(size_t)15) + echo_bytes : feed_bytes;   // (the echo's descriptors lie behind what the two feed kernels read)
+        const size_t with_echo = ne ? ((feed_bytes + 15) & ~(size_t)15) + echo_bytes : feed_bytes;   // (the echo's descriptors lie behind what the two feed kernels read)
+        const size_t bytes = nf ? ((with_echo + 15) & ~(size_t)15) + filter_bytes : with_echo;        // (... and the filter's behind the echo's)
         if (sl.host_cap < bytes) {
             if (sl.host) (void)hipHostFree(sl.host);
             sl.host = nullptr; sl.host_cap = 0;
@@ -369,10 +382,23 @@ void Deck::feed(Deck* const* decks, const uint32_t* nodes, size_t n, Graph& g, u
                 std::copy(echoes[k].ticks.begin(), echoes[k].ticks.end(), et + k * (size_t)n_ticks);
             }
         }
-        launch_upload(sl.dev.p, sl.host, ne ? echo_at + echo_bytes : feed_used, g.stream());
+        const size_t echo_used = ne ? echo_at + echo_bytes : feed_used, filter_at = (echo_used + 15) & ~(size_t)15;
+        if (nf) {
+            FilterDeckDev* fd = (FilterDeckDev*)((char*)sl.host + filter_at);
+            FilterTickDev* ft = (FilterTickDev*)(fd + nf);
+            for (size_t k = 0; k < nf; ++k) {
+                Deck& d = *decks[filters[k].deck];
+                if (d.filter.last_graph && d.filter.last_graph != &g) hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");   // (its state may still be in use on the other graph's stream)
+                fd[k] = FilterDeckDev{(float2*)outs[filters[k].deck], d.filter.dev_state()};
+                std::copy(filters[k].ticks.begin(), filters[k].ticks.end(), ft + k * (size_t)n_ticks);
+            }
+        }
+        launch_upload(sl.dev.p, sl.host, nf ? filter_at + filter_bytes : echo_used, g.stream());
         launch_deck_feed((const DeckDev*)sl.dev.p, (const DeckTickDev*)((const char*)sl.dev.p + head_bytes), tables, (uint32_t)ip, n_ticks, (uint32_t)spt, phase_varies, g.stream());
         launch_deck_keylock((const KlDeckDev*)((const char*)sl.dev.p + plain_bytes), (const KlTickDev*)((const char*)sl.dev.p + plain_bytes + nk * sizeof(KlDeckDev)), tables,
                             (uint32_t)nk, n_ticks, (uint32_t)spt, g.stream());
+        if (nf) launch_deck_filter((const FilterDeckDev*)((const char*)sl.dev.p + filter_at), (const FilterTickDev*)((const char*)sl.dev.p + filter_at + nf * sizeof(FilterDeckDev)),
+                                   (uint32_t)nf, n_ticks, (uint32_t)spt, g.stream());
         if (ne) launch_deck_echo((const EchoDeckDev*)((const char*)sl.dev.p + echo_at), (const EchoTickDev*)((const char*)sl.dev.p + echo_at + ne * sizeof(EchoDeckDev)),
                                  (uint32_t)ne_block, (uint32_t)(ne - ne_block), n_ticks, (uint32_t)spt, g.stream());
         hip_check(hipGetLastError(), "deck feed launch");
@@ -382,9 +408,18 @@ void Deck::feed(Deck* const* decks, const uint32_t* nodes, size_t n, Graph& g, u
         feed_state.last_kl.clear(); feed_state.kl_searched = feed_state.kl_unsearched = 0;
         feed_state.last_echo.clear();
         for (EchoPlan& e : echoes) { decks[e.deck]->echo.last_graph = &g; feed_state.last_echo.push_back(std::move(e.delays)); }
+        // mx_deck_debug_last_filter: decks with a filter, their ticks with and without a ramp, the super-blocks the kernel walked (every one of the feed, per deck)
+        feed_state.last_filter = DeckLastFilter{};
+        for (const FilterPlan& f : filters) {
+            decks[f.deck]->filter.last_graph = &g;
+            ++feed_state.last_filter.out[0];
+            for (const FilterTickDev& t : f.ticks) if (t.flags & FILTER_TICK_ON) ++feed_state.last_filter.out[(t.flags & FILTER_TICK_RAMP) ? 1 : 2];
+            feed_state.last_filter.out[3] += (uint32_t)(((uint64_t)n_ticks * spt + FILTER_BLOCK - 1) / FILTER_BLOCK);
+        }
         for (size_t i = 0, k = 0; i < n; ++i) {
             Deck& d = *decks[i];
             d.echo.commit(echo_after[i]);
+            d.filter.commit(filter_after[i]);
             d.head_ = heads[i]; d.ticks_ = std::move(recs[i]); d.sched_.clear(); d.keylock_.last_graph = &g; d.keylock_.last_lineage = g.lineage();
             if (!d.keylock_.on) { d.keylock_.grains.clear(); d.keylock_.grains_fetched = true; continue; }
             for (const mx_deck_grain& gr : grains[k]) ++((gr.flags & MX_DECK_GRAIN_FIRST) || !d.keylock_.k.radius ? feed_state.kl_unsearched : feed_state.kl_searched);
@@ -403,6 +438,11 @@ DeckLastKeylock deck_last_keylock() {
 DeckLastEcho deck_last_echo() {
     std::lock_guard<std::mutex> lock(feed_state.mu);
     return DeckLastEcho{feed_state.last_echo, feed_state.last_spt};
+}
+
+DeckLastFilter deck_last_filter() {
+    std::lock_guard<std::mutex> lock(feed_state.mu);
+    return feed_state.last_filter;
 }
 
 void Deck::debug_last_feed(uint32_t out[6]) {

@@ -7,6 +7,7 @@
 #include "mx_deck_bars.hpp"
 #include "mx_deck_columns.hpp"
 #include "mx_deck_echo.hpp"
+#include "mx_deck_filter.hpp"
 #include "mx_deck_finegrid.hpp"
 #include "mx_deck_loudkey.hpp"
 #include "mx_deck_tempomap.hpp"
@@ -88,8 +89,8 @@ struct DeckKlTick { KlTickDev t; uint32_t log_hop, overlap; };
 struct DeckLastKeylock { std::vector<DeckKlTick> ticks; uint32_t spt = 0, searched = 0, unsearched = 0; };
 DeckLastKeylock deck_last_keylock();
 
-// The track, the transport state machine and the feed (mx_deck.cpp), key-lock (mx_deck_keylock.cpp), the echo (mx_deck_echo.hpp: a member with its own state, schedule
-// and delay line), and the six whole-track analyses, each a member that holds its own results and sees of the deck a DeckTrack and nothing else (mx_deck_analysis.hpp).
+// The track, the transport state machine and the feed (mx_deck.cpp), key-lock (mx_deck_keylock.cpp), the sweep filter and the echo
+// (mx_deck_filter.hpp, mx_deck_echo.hpp: members with their own setting, schedule and device memory -- four state values, a delay line), and the six whole-track analyses, each a member that holds its own results and sees of the deck a DeckTrack and nothing else (mx_deck_analysis.hpp).
 class Deck {
 public:
     Deck(uint64_t n_frames, int device);
@@ -130,6 +131,8 @@ public:
     DeckTempoMap tempomap{for_analyses_};
     // the beat echo behind the feed and key-lock (mx_abi_deck.cpp calls it directly; the feed plans, launches and commits it)
     DeckEcho echo{device_};
+    // the sweep filter between them and the echo (the same protocol: plan, launch, commit)
+    DeckFilter filter{device_};
 };
 
 }  // namespace mx

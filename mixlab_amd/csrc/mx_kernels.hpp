@@ -362,7 +362,11 @@ void launch_deck_feed(const DeckDev* decks, const DeckTickDev* ticks, const floa
 // the key-locked decks of a feed (mx_deck.hpp, mx_k_deck_keylock.hip): the grain search, one workgroup per deck, then the render over n decks x n_ticks ticks x chunks
 struct KlDeckDev; struct KlTickDev;
 void launch_deck_keylock(const KlDeckDev* decks, const KlTickDev* ticks, const float* tables, uint32_t n, uint32_t n_ticks, uint32_t spt, hipStream_t s);
-// the echo of the decks of a feed that have one (mx_deck_echo.hpp, mx_k_deck_echo.hip), in place on their ports behind the two launches above: the first n_block decks
+// the sweep filter of the decks of a feed that have one (mx_deck_filter.hpp, mx_k_deck_filter.hip), in place on their ports behind the two launches above and ahead of
+// the echo: one wave per deck; ticks: n_ticks per deck
+struct FilterDeckDev; struct FilterTickDev;
+void launch_deck_filter(const FilterDeckDev* decks, const FilterTickDev* ticks, uint32_t n_decks, uint32_t n_ticks, uint32_t spt, hipStream_t s);
+// the echo of the decks of a feed that have one (mx_deck_echo.hpp, mx_k_deck_echo.hip), in place on their ports behind the launches above: the first n_block decks
 // in the one-block form (decks x ticks x chunks workgroups), the n_walk decks behind them in the sequential form (a workgroup per deck); ticks: n_ticks per deck
 struct EchoDeckDev; struct EchoTickDev;
 void launch_deck_echo(const EchoDeckDev* decks, const EchoTickDev* ticks, uint32_t n_block, uint32_t n_walk, uint32_t n_ticks, uint32_t spt, hipStream_t s);

@@ -25,6 +25,11 @@ The echo (the header's ECHO) is a feedback delay behind the deck, timed in beats
     deck.set_echo(delay=deck.echo_delay(beats, 3, 4), feedback=0.6)       # a 3/4-beat echo from the next feed on
     deck.schedule(k, params(flags=0))                                     # PLAY cleared at tick k: the tail rings over the incoming track
 
+The sweep filter (the header's FILTER) is the one-knob resonant filter of a transition, ahead of the echo; a sweep is one setting a tick, each ramping from the last:
+
+    deck.set_filter(filter_knob(-0.5, 48000.0))                           # a low-pass half closed, faded in over the next feed's first tick; None (the dead zone) turns it off
+    deck.schedule_filter(k, kind=abi.DECK_FILTER_HP, g=0.02, k=0.5)       # ... or by the numbers, from tick k on
+
 Bars (the header's BARS) say which beat is a bar's first and which bar a phrase's first; the two grids go where a beat grid goes:
 
     pick = deck.find_bars(beats, analysis_bands(rate=44100.0))            # pick.bars, pick.phrases: DeckBeats; pick.bar_best / pick.bar_sum the confidence
@@ -44,7 +49,7 @@ import ctypes as C
 import numpy as np
 
 from . import abi
-from .abi import (DeckAnalysis, DeckBarPick, DeckBars, DeckBeats, DeckEcho, DeckFinegrid, DeckFinePick, DeckGrain, DeckGrid, DeckHead, DeckKeylock, DeckLoudness, DeckParams, DeckSyncResult, DeckTempomap,
+from .abi import (DeckAnalysis, DeckBarPick, DeckBars, DeckBeats, DeckEcho, DeckFilter, DeckFinegrid, DeckFinePick, DeckGrain, DeckGrid, DeckHead, DeckKeylock, DeckLoudness, DeckParams, DeckSyncResult, DeckTempomap,
                   DeckTick, DeckTonality, check, lib)
 
 ONE = 1 << 32   # unity step / one track frame in Q32.32
@@ -346,6 +351,46 @@ def debug_last_echo() -> dict:
     return _debug_last(lib.mx_deck_debug_last_echo, ("decks_one_block", "decks_sequential", "blocks", "blocks_crossing"))
 
 
+def filt(kind=abi.DECK_FILTER_LP, g=1.0, k=1.0, wet=1.0) -> DeckFilter:
+    """sweep filter settings (the header's FILTER): the response, g = tan(pi fc / rate), k = 1 / Q, the wet mix; filter_design() and filter_knob() start from Hz"""
+    return DeckFilter(int(kind), 0, float(g), float(k), float(wet), 0)
+
+
+def filter_check(f: DeckFilter) -> None:
+    """the filter setting rules alone (host only); raises MxError"""
+    check(lib.mx_deck_filter_check(C.byref(f)))
+
+
+def filter_design(kind: int, cutoff_hz: float, q: float, rate: float, wet: float = 1.0) -> DeckFilter:
+    """the settings of a cutoff and a Q at this rate (mx_deck_filter_design, host only; libm, good to 1 f32 ulp)"""
+    out = DeckFilter()
+    check(lib.mx_deck_filter_design(int(kind), float(cutoff_hz), float(q), float(rate), float(wet), C.byref(out)))
+    return out
+
+
+def filter_knob(knob: float, rate: float, q: float = 2.0) -> DeckFilter | None:
+    """the DJ mapping of one knob in -1 .. 1 (mx_deck_filter_knob, host only): None in the dead zone, a low-pass closing to the left, a high-pass opening to the right"""
+    out, on = DeckFilter(), C.c_uint32()
+    check(lib.mx_deck_filter_knob(float(knob), float(rate), float(q), C.byref(out), C.byref(on)))
+    return out if on.value else None
+
+
+def filter_host(frames: np.ndarray, spt: int, settings, carry: abi.DeckFilterCarry | None = None):
+    """(float32 frames after the filter, the carried block) of mx_deck_filter_host (host only, pure): frames float32 [n_ticks * spt * 2], settings one DeckFilter or
+    None per tick, carry what the last call returned (None: a deck that never had a filter)"""
+    out = np.ascontiguousarray(frames, np.float32).reshape(-1).copy()
+    n_ticks = len(settings)
+    assert out.size == n_ticks * int(spt) * 2
+    carry = abi.DeckFilterCarry.from_buffer_copy(carry) if carry is not None else abi.DeckFilterCarry()
+    ptrs = (C.POINTER(DeckFilter) * max(1, n_ticks))(*[C.pointer(f) if f is not None else None for f in settings])
+    check(lib.mx_deck_filter_host(out.ctypes.data_as(C.c_void_p) if out.size else None, int(spt), n_ticks, C.cast(ptrs, C.c_void_p) if n_ticks else None, C.byref(carry)))
+    return out, carry
+
+
+def debug_last_filter() -> dict:
+    return _debug_last(lib.mx_deck_debug_last_filter, ("decks", "ticks_ramp", "ticks_constant", "blocks"))
+
+
 def bars(grid: DeckBeats, tables: DeckAnalysis | None = None, lead=128, beats_per_bar=4, bars_per_phrase=4, w_bar=4, w_phrase=8, max_beats=0) -> DeckBars:
     """bars settings (the header's BARS) on a beat grid; the tap tables are those of `tables` (mx_deck_bars_tables), a single unity tap without it"""
     s = DeckBars()
@@ -576,6 +621,28 @@ class Deck:
         t, on, e = C.c_uint64(), C.c_uint32(), DeckEcho()
         check(lib.mx_deck_echo_state(self._h, C.byref(t), C.byref(on), C.byref(e)))
         return t.value, bool(on.value), e
+
+    def set_filter(self, f: DeckFilter | None = None, **kw):
+        """the sweep filter from tick 0 of the next feed on; keywords are filt()'s; set_filter(None) with no keywords turns it off"""
+        f = f if f is not None else (filt(**kw) if kw else None)
+        check(lib.mx_deck_set_filter(self._h, C.byref(f) if f is not None else None))
+
+    def schedule_filter(self, tick_in_feed: int, f: DeckFilter | None = None, **kw):
+        """... from that tick of the next feed on (a sweep is one setting a tick: each ramps from the last); None with no keywords turns it off there"""
+        f = f if f is not None else (filt(**kw) if kw else None)
+        check(lib.mx_deck_schedule_filter(self._h, int(tick_in_feed), C.byref(f) if f is not None else None))
+
+    def filter_state(self):
+        """(on, DeckFilter in force) after the last feed; host data, no synchronisation"""
+        on, f = C.c_uint32(), DeckFilter()
+        check(lib.mx_deck_filter_state(self._h, C.byref(on), C.byref(f)))
+        return bool(on.value), f
+
+    def read_filter_state(self) -> np.ndarray:
+        """float64 [4]: s1 s2 of L, s1 s2 of R after the last feed (waits for the device); zeros when the filter is off or was never on"""
+        s = (C.c_double * 4)()
+        check(lib.mx_deck_read_filter_state(self._h, s))
+        return np.array(s[:], np.float64)
 
     def _analyse(self, call, attr: str, settings, counts) -> None:
         """one analyse*() call and the counts remembered of it: settings of None free the results; refused settings (MX_ERR_INVALID) leave the deck what it
