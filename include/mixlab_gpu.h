@@ -59,6 +59,8 @@ extern "C" {
                               *    mx_deck_debug_last_echo;
                               *    mx_deck_filter, mx_deck_filter_carry, mx_deck_set_filter, mx_deck_schedule_filter, mx_deck_filter_check, mx_deck_filter_state,
                               *    mx_deck_read_filter_state, mx_deck_filter_design, mx_deck_filter_knob, mx_deck_filter_host, mx_deck_debug_last_filter;
+                              *    mx_deck_reverb, mx_deck_reverb_carry, mx_deck_set_reverb, mx_deck_schedule_reverb, mx_deck_reverb_check, mx_deck_reverb_state,
+                              *    mx_deck_read_reverb_lines, mx_deck_reverb_plan, mx_deck_reverb_host, mx_deck_reverb_design, mx_deck_debug_last_reverb;
                               *    mx_deck_bars, mx_deck_beat, mx_deck_bar_pick, mx_deck_bars_check, mx_deck_bars_count, mx_deck_bars_tables, mx_deck_analyse_bars,
                               *    mx_deck_read_bars, mx_deck_read_bar_folds, mx_deck_bars_host, mx_deck_bars_pick, mx_deck_grid_next, mx_deck_debug_last_bars;
                               *    mx_deck_tempomap, mx_deck_tempo_segment, mx_deck_tempomap_check, mx_deck_tempomap_count, mx_deck_tempomap_span, mx_deck_tempomap_host,
@@ -994,8 +996,8 @@ int mx_deck_debug_last_keylock(uint32_t out[4]);
  * BLOCKS     (how the device runs it; mx_deck_echo_plan restates it.)  Frame t reads the line no later than t - D + 1, so the frames of a block [t0, t0 + B) are
  *            independent of one another when t - D(t) + 1 < t0 for every frame of it; with one delay, B <= D - 1.  A deck's echo frames of a feed are cut greedily
  *            into maximal such blocks, a tick without an echo always ending one; the cut holds across a tick that lowers the delay.
- * Out of scope: delays under 256 frames (flanger, chorus), modulated or interpolated delay, reverb, the echo on ports other than a deck's
- * source, more than two channels.
+ * Out of scope: delays under 256 frames (flanger, chorus), modulated or interpolated delay, the echo on ports other than a deck's
+ * source, more than two channels.  (The reverb is REVERB below: a pass of its own behind the echo.)
  */
 #define MX_DECK_ECHO_PINGPONG 1u
 #define MX_DECK_ECHO_MIN_DELAY 256u
@@ -1109,6 +1111,118 @@ int mx_deck_filter_host(float* frames, uint32_t spt, uint32_t n_ticks, const mx_
  * filter and no ramp, out[3] the 64-frame super-blocks their waves walked (ceil(n_ticks spt / 64) per deck: the walk covers the feed).  All zero for a feed in which
  * no deck has a filter. */
 int mx_deck_debug_last_filter(uint32_t out[4]);
+
+/* ---- REVERB: a feedback delay network behind the deck, the filter and the echo, with reverb-out ----
+ * BUILD-SPECIFIED.  An optional pass of a deck, set by mx_deck_set_reverb / mx_deck_schedule_reverb: the wash of a transition.  Two series allpass diffusers per
+ * channel feed a tank of eight delay lines mixed by an orthogonal (Hadamard) matrix.  It runs LAST, in place on what the deck, the filter and the echo left in the
+ * deck's SOURCE_STEREO node's port: feed / key-lock -> filter -> echo -> reverb, so echo repeats are reverberated.  The head, the tick records and the grains are
+ * what they were.  A deck that never sets a reverb is untouched in every respect, and a feed in which no deck has a reverb launches nothing new and uploads no
+ * further byte.
+ *
+ * SETTINGS   mx_deck_reverb: delay[i], i = 0 .. 7, the tank line delays in output frames, MX_DECK_REVERB_MIN_DELAY (128) <= delay[i] <= MX_DECK_REVERB_MAX_DELAY
+ *            (12000); diff[j], j = 0 .. 3, the diffuser delays, MX_DECK_REVERB_MIN_DIFF (64) <= diff[j] <= MX_DECK_REVERB_MAX_DIFF (2000): diff[0] then diff[1]
+ *            serve L in series, diff[2] then diff[3] serve R.  All floats finite; |gain[i]| <= 1, |send| <= 1, |dry| <= 1, |wet| <= 4, 0 <= damp <= 1,
+ *            0 <= diffusion <= 0.75 (compared as f32); flags 0.  mx_deck_reverb_design turns a size and a decay time into one.
+ * MEMORY     per deck, allocated at the first setting: eight tank rings r_i of MX_DECK_REVERB_TANK_RING (16384) f32 and four diffuser rings q_j of
+ *            MX_DECK_REVERB_DIFF_RING (4096) f32, one ring a line, one after another (MX_DECK_REVERB_LINE_FLOATS = 147456 f32, 576 KB): ring i of the tank starts
+ *            at float i * 16384, ring j of the diffusers at float 8 * 16384 + j * 4096.  The value of clock s lies in slot s & (ring - 1).  A read at a clock below
+ *            0 is zero, whatever the slot holds: off -> on needs no clearing.  The longest block (BLOCKS) plus the longest delay plus one stays under the ring,
+ *            2000 + 12000 + 1 < 16384 and 2000 + 2000 < 4096, so no frame of a block overwrites a slot another frame of that block still reads.
+ * CLOCK      the echo's rule.  A deck with a reverb counts EVERY output frame it is fed in t: playing ticks, ticks written as zeros (not playing), BEFORE / PAST
+ *            ticks.  That is how a stopped deck rings out.  t = 0 and all-zero lines (every read below clock 0) hold at the first tick that runs with a reverb
+ *            after creation or after a tick without one: off -> on starts clean.  Nothing else restarts the clock or clears the lines: not a seek, a load, a change
+ *            of step or of PLAY, a change of settings (delays included: the new delay reads what the old one wrote), mx_deck_set_keylock, a filter or echo
+ *            setting, a feed into another graph handle, nor a graph that adopted another's state.  All of this the host can compute.
+ * PER FRAME  x_c is the f32 in the port for channel c (0 = L, 1 = R) at the frame with clock t: what the deck, the filter and the echo left there.  send_n, dry_n,
+ *            wet_n, gain_n[i] are the frame's ramped values (RAMPS), each an f32 widened.  Every multiply, add and subtract is a separate f64 operation, never
+ *            fused, in this order:
+ *             1. a = (double)damp * 0.25;   b = 1.0 - (a + a);   gd = (double)diffusion                                   (per setting)
+ *             2. u = send_n * x_c
+ *             3. for j = 2c, then 2c + 1, with p = (double)q_j[t - diff_j]:
+ *                    v = u - gd * p;   q_j[t] = (float)v;   w = (double)(float)v;   u = p + gd * w
+ *                after both, e_c = u.  The rounded w is used, not v: the allpass is allpass with respect to what the line holds.
+ *             4. for i = 0 .. 7, s = t - delay_i:
+ *                    f_i = b * (double)r_i[s] + a * (double)r_i[s - 1] + a * (double)r_i[s + 1]         (left to right: ((b r) + (a r)) + (a r))
+ *                    g_i = gain_n[i] * f_i
+ *             5. h = g; three stages at distances d = 1, 2, 4: for every i with bit d clear, (h_i, h_{i+d}) <- (h_i + h_{i+d}, h_i - h_{i+d}), both from the
+ *                stage's inputs.  Then m_i = h_i * C, C = 0x1.6a09e667f3bcdp-2 (the f64 nearest 0.5 sqrt(0.5)).
+ *             6. r_i[t] = (float)(m_i + e_{i & 1})                                                        (even lines take L, odd lines R)
+ *             7. o_0 = ((f_0 - f_2) + (f_4 - f_6)) * 0.5;   o_1 = ((f_1 - f_3) + (f_5 - f_7)) * 0.5
+ *                y_c = (float)(dry_n * x_c + wet_n * o_c)
+ *            y replaces x in the port.  Subnormal f32 values are kept, not flushed (numpy's casts are the model).  MX_FLAG_FP_CONTRACT does not apply.  A frame
+ *            reads r_i no later than clock t - 127 and q_j no later than t - 64: never what it or a later frame writes.
+ * RAMPS      send, dry, wet and the eight gains never jump inside the sound.  In the tick at which a setting takes effect (any mx_deck_set_reverb /
+ *            mx_deck_schedule_reverb with settings, also one that repeats them), frame n of the tick, n = 0 .. spt - 1, uses for each of the eleven
+ *                g_n = (float)((double)old + ((double)new - (double)old) * ((double)n / (double)spt))
+ *            with `old` the value of the tick before; every other tick uses `new` as it stands.  In the first tick after off -> on `old` is 0 for ALL eleven,
+ *            dry included: that tick fades the dry signal in from silence too (a host that wants the dry signal untouched at the switch-on sets the reverb a
+ *            tick early with send = 0, or keeps dry at 1 by switching on under a tick of silence).  delay, diff, damp and diffusion switch at the tick's first
+ *            frame.  Turning the reverb off is a hard switch at a tick's first frame.  (In a tick of one frame the weight is always 0: the tick sounds the old
+ *            values whole.)
+ * SCHEDULE   mx_deck_set_reverb applies from tick 0 of the next feed, mx_deck_schedule_reverb from the tick named; NULL settings turn the reverb off from that
+ *            tick.  The rules are mx_deck_schedule_echo's: a later call for the same tick replaces an earlier one, the feed clears the schedule, a feed that does
+ *            not reach a scheduled tick fails with MX_ERR_INVALID and drops the schedules (the deck's own, the filter's and the echo's too) -- the setting in
+ *            force, the clock and the lines stay.  Settings that mx_deck_reverb_check refuses leave everything as it was.
+ * BLOCKS     (how the device runs it; mx_deck_reverb_plan restates it.)  The reach of a tick is R = min(min_i delay_i - 1, min_j diff_j), 64 <= R <= 2000: frame
+ *            t reads no line later than clock t - R.  The frames of a block [t0, t0 + B) are independent of one another when t - R(t) < t0 for every frame of it;
+ *            with one setting, B <= R.  A deck's reverb frames of a feed are cut greedily into maximal such blocks, a tick without a reverb always ending one;
+ *            the cut holds across a tick that lowers the reach.
+ * IT FOLLOWS that the result does not depend on how ticks are grouped into feeds; that with wet = 0 and dry = 1 the port holds the deck's samples as numbers
+ *            ((float)(1 * x + 0 * o): a -0 may come back as +0) while the lines move on; that with all gain = 0 and diffusion = 0 the wet signal is a four-tap
+ *            delay of the sent input that can be written down from the port alone: a diffuser with diffusion = 0 is a pure delay of diff_j frames, so with
+ *            u_c[t] = (double)(float)(send_t' * x_c[t']) at t' = t - diff_2c - diff_2c+1 (zero for t' < 0) and damp = 0,
+ *            o_0[t] = 0.5 ((u_0[t - D0] - u_0[t - D2]) + (u_0[t - D4] - u_0[t - D6])), and likewise o_1 with the odd delays; and that a deck whose PLAY flag is
+ *            cleared keeps sounding its tail (the reverb-out).
+ * Out of scope: pre-delay; modulated or interpolated lines; a one-pole damping (it would serialise the block); a bit-exact freeze (orthogonal mixing in floating
+ * point holds energy only within rounding); the reverb on ports other than a deck's source; more than two channels.
+ */
+#define MX_DECK_REVERB_MIN_DELAY 128u
+#define MX_DECK_REVERB_MAX_DELAY 12000u     /* 250 ms at 48 kHz */
+#define MX_DECK_REVERB_MIN_DIFF 64u
+#define MX_DECK_REVERB_MAX_DIFF 2000u
+#define MX_DECK_REVERB_TANK_RING 16384u
+#define MX_DECK_REVERB_DIFF_RING 4096u
+#define MX_DECK_REVERB_LINE_FLOATS 147456u  /* 8 x 16384 + 4 x 4096 */
+typedef struct { uint32_t delay[8]; uint32_t diff[4]; float gain[8]; float send; float dry; float wet; float damp; float diffusion; uint32_t flags; } mx_deck_reverb;   /* 104 bytes */
+/* What mx_deck_reverb_host carries from one call to the next beside the caller's lines: the clock t, the last setting, whether the reverb was on (1 / 0); _pad 0.
+ * All zero is a deck that never had a reverb. */
+typedef struct { uint64_t t; mx_deck_reverb last; uint32_t on; uint32_t _pad; } mx_deck_reverb_carry;   /* 120 bytes */
+/* The reverb with these settings from tick 0 of the NEXT feed on; NULL: off from that tick.  mx_deck_schedule_reverb(d, 0, r).  The first call with settings allocates
+ * the deck's lines (MEMORY, 576 KB).  Settings that mx_deck_reverb_check refuses: MX_ERR_INVALID, and the deck and its schedule keep what they had. */
+int mx_deck_set_reverb(mx_deck* d, const mx_deck_reverb* r);
+/* ... from tick `tick_in_feed` of the next feed on (SCHEDULE). */
+int mx_deck_schedule_reverb(mx_deck* d, uint32_t tick_in_feed, const mx_deck_reverb* r);
+/* Host only: the SETTINGS rules alone. */
+int mx_deck_reverb_check(const mx_deck_reverb* r);
+/* After the last feed: the clock t, whether the reverb is on (1 / 0), and the setting in force (the last one it had, when off; all zero before the first).  Host data:
+ * no synchronisation. */
+int mx_deck_reverb_state(const mx_deck* d, uint64_t* t, uint32_t* on, mx_deck_reverb* setting);
+/* Waits for the feed's kernels, then: the raw rings into dst[MX_DECK_REVERB_LINE_FLOATS], tank then diffusers (MEMORY's layout).  Only the slots of the clocks in
+ * [max(0, t - ring), t) are specified; all zeros for a deck that never had a setting. */
+int mx_deck_read_reverb_lines(mx_deck* d, float* dst);
+/* Host only, pure: BLOCKS for a feed of n_ticks ticks of spt frames, settings[k] the setting in force in tick k or NULL for a tick without a reverb: block j is
+ * blocks[2 j] (its first frame, counted from the feed's first) and blocks[2 j + 1] (its frames), for j < min(*n_blocks, cap); *n_blocks is the number of blocks
+ * whatever cap is.  spt outside 1 .. MX_DECK_MAX_SPT, a setting the check refuses, a NULL pointer: MX_ERR_INVALID. */
+int mx_deck_reverb_plan(uint32_t spt, const mx_deck_reverb* const* settings, uint32_t n_ticks, uint64_t* blocks, uint32_t cap, uint32_t* n_blocks);
+/* Host only, pure: PER FRAME, RAMPS and CLOCK in plain C++ over the caller's frames[n_ticks * spt * 2] (L R interleaved), in place, and the caller's
+ * lines[MX_DECK_REVERB_LINE_FLOATS] (MEMORY's layout; any content at first).  settings[k] is the setting in force in tick k, NULL for a tick without a reverb; every
+ * tick with a setting counts as one at which that setting takes effect (a setting that repeats the last ramps from equal values, which is the constant tick bit for
+ * bit).  *carry goes in as the last call left it (all zero at first) and comes out as this call leaves it.  spt outside 1 .. MX_DECK_MAX_SPT, a setting or carried
+ * block the check refuses, NULL: MX_ERR_INVALID, nothing written. */
+int mx_deck_reverb_host(float* frames, uint32_t spt, uint32_t n_ticks, const mx_deck_reverb* const* settings, float* lines, mx_deck_reverb_carry* carry);
+/* Host only: knobs into a setting.  size in 0.25 .. 4 scales the room, t60_seconds > 0 is the time the tank takes to fall by 60 dB, rate > 0 the graph's rate; all
+ * finite.  With P(x) the smallest prime >= x and the f64 expressions evaluated left to right as written:
+ *   tank     delay[i] = P(floor(base[i] * size * rate / 48000.0 + 0.5)), base = {1087, 1283, 1447, 1663, 1871, 2053, 2281, 2477}, for i = 0 .. 7 in turn; while the
+ *            prime equals a delay already given to a lower i, the next prime above it is taken
+ *   diffuser diff[j] = P(floor(dbase[j] * rate / 48000.0 + 0.5)), dbase = {229, 613, 241, 587}
+ *   gain[i] = (float)pow(10.0, -3.0 * (double)delay[i] / (rate * t60_seconds))        (libm: specified to 1 f32 ulp, not to the bit; the integers are exact)
+ *   send, dry, wet, damp, diffusion as given, rounded to f32; flags 0.
+ * An argument that is not finite, size outside 0.25 .. 4, rate or t60_seconds not positive, a delay out of range or a result that mx_deck_reverb_check refuses:
+ * MX_ERR_INVALID, *out untouched. */
+int mx_deck_reverb_design(double rate, double size, double t60_seconds, double damp, double diffusion, double send, double dry, double wet, mx_deck_reverb* out);
+/* DEBUG: the decks with a reverb in any tick of the last mx_deck_feed of this process: out[0] those decks, out[1] the blocks their workgroups walked, out[2] those of
+ * them that cross a tick boundary, out[3] the frames of the largest block.  All zero for a feed in which no deck has a reverb. */
+int mx_deck_debug_last_reverb(uint32_t out[4]);
 
 /* ---- ANALYSIS: the band waveform overview, the onset autocorrelation and the beat grid of a whole track, before it sounds ----
  * BUILD-SPECIFIED.  One pass over the track as it lies in device memory, on the deck's own load stream: what a host needs at load time -- the coloured overview

@@ -502,6 +502,25 @@ _proto("mx_deck_filter_design", C.c_int, C.c_uint32, C.c_double, C.c_double, C.c
 _proto("mx_deck_filter_knob", C.c_int, C.c_double, C.c_double, C.c_double, C.POINTER(DeckFilter), C.POINTER(C.c_uint32))
 _proto("mx_deck_filter_host", C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(DeckFilterCarry))
 _proto("mx_deck_debug_last_filter", C.c_int, C.POINTER(C.c_uint32))
+# ... its reverb (the header's REVERB): a feedback delay network per deck behind the echo, scheduled per tick
+DECK_REVERB_MIN_DELAY, DECK_REVERB_MAX_DELAY = 128, 12000
+DECK_REVERB_MIN_DIFF, DECK_REVERB_MAX_DIFF = 64, 2000
+DECK_REVERB_TANK_RING, DECK_REVERB_DIFF_RING = 16384, 4096
+DECK_REVERB_LINE_FLOATS = 8 * 16384 + 4 * 4096
+class DeckReverb(C.Structure):
+    _fields_ = [("delay", C.c_uint32 * 8), ("diff", C.c_uint32 * 4), ("gain", C.c_float * 8), ("send", C.c_float), ("dry", C.c_float), ("wet", C.c_float),
+                ("damp", C.c_float), ("diffusion", C.c_float), ("flags", C.c_uint32)]
+class DeckReverbCarry(C.Structure):
+    _fields_ = [("t", C.c_uint64), ("last", DeckReverb), ("on", C.c_uint32), ("_pad", C.c_uint32)]
+_proto("mx_deck_set_reverb", C.c_int, C.c_void_p, C.POINTER(DeckReverb))
+_proto("mx_deck_schedule_reverb", C.c_int, C.c_void_p, C.c_uint32, C.POINTER(DeckReverb))
+_proto("mx_deck_reverb_check", C.c_int, C.POINTER(DeckReverb))
+_proto("mx_deck_reverb_state", C.c_int, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(DeckReverb))
+_proto("mx_deck_read_reverb_lines", C.c_int, C.c_void_p, C.c_void_p)
+_proto("mx_deck_reverb_plan", C.c_int, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32))
+_proto("mx_deck_reverb_host", C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(DeckReverbCarry))
+_proto("mx_deck_reverb_design", C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(DeckReverb))
+_proto("mx_deck_debug_last_reverb", C.c_int, C.POINTER(C.c_uint32))
 # ... its bars and phrases (the header's BARS): beat vectors, checkerboard novelty at two widths, and the folds the downbeat and the phrase line are picked from
 DECK_BARS_MAX_BEATS = 16384   # MX_DECK_BARS_MAX_BEATS
 DECK_BARS_MAX_FOLDS = 136     # MX_DECK_BARS_MAX_FOLDS

@@ -150,6 +150,50 @@ int mx_deck_filter_host(float* frames, uint32_t spt, uint32_t n_ticks, const mx_
         mx::deck_filter_host(frames, spt, n_ticks, settings, *carry);
     });
 }
+int mx_deck_set_reverb(mx_deck* d, const mx_deck_reverb* r) {
+    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.reverb.schedule(0, r); });
+}
+int mx_deck_schedule_reverb(mx_deck* d, uint32_t tick_in_feed, const mx_deck_reverb* r) {
+    return guard([&] { REQUIRE(d, "deck is NULL"); d->d.reverb.schedule(tick_in_feed, r); });
+}
+int mx_deck_reverb_check(const mx_deck_reverb* r) {
+    return guard([&] { REQUIRE(r, "settings are NULL"); mx::deck_reverb_check(*r); });
+}
+int mx_deck_reverb_state(const mx_deck* d, uint64_t* t, uint32_t* on, mx_deck_reverb* setting) {
+    return guard([&] {
+        REQUIRE(d && t && on && setting, "NULL argument");
+        const mx::DeckReverb::State& s = d->d.reverb.state();
+        *t = s.t; *on = s.on ? 1u : 0u; *setting = s.set;
+    });
+}
+int mx_deck_read_reverb_lines(mx_deck* d, float* dst) {
+    return guard([&] { REQUIRE(d && dst, "NULL argument"); d->d.reverb.read_lines(dst); });
+}
+int mx_deck_reverb_plan(uint32_t spt, const mx_deck_reverb* const* settings, uint32_t n_ticks, uint64_t* blocks, uint32_t cap, uint32_t* n_blocks) {
+    return guard([&] {
+        REQUIRE(n_blocks && (!n_ticks || settings) && (!cap || blocks), "NULL argument");
+        REQUIRE(spt >= 1 && spt <= MX_DECK_MAX_SPT, "frames per tick outside 1 .. MX_DECK_MAX_SPT");
+        std::vector<uint32_t> reach(n_ticks, 0u);
+        for (uint32_t k = 0; k < n_ticks; ++k) if (settings[k]) { mx::deck_reverb_check(*settings[k]); reach[k] = mx::reverb_reach(*settings[k]); }
+        std::vector<mx::ReverbBlock> cut;
+        mx::deck_reverb_cut(spt, reach.data(), n_ticks, cut);
+        REQUIRE(cut.size() <= 0xffffffffu, "more than 2^32 blocks");
+        for (size_t j = 0; j < cut.size() && j < cap; ++j) { blocks[2 * j] = cut[j].first; blocks[2 * j + 1] = cut[j].frames; }
+        *n_blocks = (uint32_t)cut.size();
+    });
+}
+int mx_deck_reverb_host(float* frames, uint32_t spt, uint32_t n_ticks, const mx_deck_reverb* const* settings, float* lines, mx_deck_reverb_carry* carry) {
+    return guard([&] {
+        REQUIRE(carry && lines && (!n_ticks || (frames && settings)), "NULL argument");
+        mx::deck_reverb_host(frames, spt, n_ticks, settings, lines, *carry);
+    });
+}
+int mx_deck_reverb_design(double rate, double size, double t60_seconds, double damp, double diffusion, double send, double dry, double wet, mx_deck_reverb* out) {
+    return guard([&] { REQUIRE(out, "out is NULL"); mx::deck_reverb_design(rate, size, t60_seconds, damp, diffusion, send, dry, wet, *out); });
+}
+int mx_deck_debug_last_reverb(uint32_t out[4]) {
+    return guard([&] { REQUIRE(out, "out is NULL"); mx::deck_debug_last_reverb(out); });
+}
 int mx_deck_debug_last_filter(uint32_t out[4]) {
     return guard([&] { REQUIRE(out, "out is NULL"); const mx::DeckLastFilter last = mx::deck_last_filter(); for (int k = 0; k < 4; ++k) out[k] = last.out[k]; });
 }

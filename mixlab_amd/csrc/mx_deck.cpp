@@ -1,7 +1,7 @@
 // mx_deck.cpp -- the deck's host side: parameter rules, the per-tick state machine (mx_deck_plan), the coefficient tables, the track, and the feed that turns the
 // coming ticks of many decks into one descriptor block and one launch (include/mixlab_gpu.h "the deck").  Key-lock beside the feed is
 // mx_deck_keylock.cpp's, the echo behind it mx_deck_echo.cpp's (the feed asks each deck's DeckEcho for its ticks, uploads them with its own, launches, commits),
-// the sweep filter between the two mx_deck_filter.cpp's (DeckFilter, the same protocol), and each whole-track analysis has a file of its own (mx_deck_analysis.hpp).
+// the sweep filter between the two mx_deck_filter.cpp's (DeckFilter, the same protocol), the reverb behind the echo mx_deck_reverb.cpp's (DeckReverb), and each whole-track analysis has a file of its own (mx_deck_analysis.hpp).
 #include "mx_deck.hpp"
 
 #include <algorithm>
@@ -203,6 +203,7 @@ struct FeedState {
     std::vector<KlTick> last_kl; uint32_t kl_searched = 0, kl_unsearched = 0;   // ... and its key-locked ticks and grains, for mx_deck_debug_last_keylock
     std::vector<std::vector<uint32_t>> last_echo;                                // ... and per deck with an echo the delays of its ticks, for mx_deck_debug_last_echo
     DeckLastFilter last_filter;                                                  // ... and the filter's four counters, for mx_deck_debug_last_filter
+    std::vector<std::vector<uint32_t>> last_reverb;                              // ... and per deck with a reverb the reaches of its ticks, for mx_deck_debug_last_reverb
 } feed_state;
 }  // namespace
 
@@ -220,7 +221,7 @@ void deck_stream_retired(hipStream_t s) {
 }
 
 void Deck::feed(Deck* const* decks, const uint32_t* nodes, size_t n, Graph& g, uint32_t n_ticks) {
-    auto drop = [&] { for (size_t i = 0; i < n; ++i) if (decks && decks[i]) { decks[i]->sched_.clear(); decks[i]->echo.drop_schedule(); decks[i]->filter.drop_schedule(); } };
+    auto drop = [&] { for (size_t i = 0; i < n; ++i) if (decks && decks[i]) { decks[i]->sched_.clear(); decks[i]->echo.drop_schedule(); decks[i]->filter.drop_schedule(); decks[i]->reverb.drop_schedule(); } };
     try {
         if (!n) return;
         if (!decks || !nodes) throw Error(MX_ERR_INVALID, "deck feed: decks / nodes is NULL");
@@ -240,6 +241,8 @@ void Deck::feed(Deck* const* decks, const uint32_t* nodes, size_t n, Graph& g, u
                 throw Error(MX_ERR_INVALID, "deck feed: deck " + std::to_string(i) + " has an echo scheduled at tick " + std::to_string(beyond) + ", beyond this feed");
             if (decks[i]->filter.scheduled_beyond(n_ticks, beyond))
                 throw Error(MX_ERR_INVALID, "deck feed: deck " + std::to_string(i) + " has a filter scheduled at tick " + std::to_string(beyond) + ", beyond this feed");
+            if (decks[i]->reverb.scheduled_beyond(n_ticks, beyond))
+                throw Error(MX_ERR_INVALID, "deck feed: deck " + std::to_string(i) + " has a reverb scheduled at tick " + std::to_string(beyond) + ", beyond this feed");
         }
         {
             std::vector<const Deck*> d(decks, decks + n); std::vector<uint32_t> nd(nodes, nodes + n);
@@ -273,6 +276,15 @@ void Deck::feed(Deck* const* decks, const uint32_t* nodes, size_t n, Graph& g, u
             if (decks[i]->filter.plan(n_ticks, ft, filter_after[i])) filters.push_back(FilterPlan{i, std::move(ft)});
         }
         const size_t nf = filters.size(), filter_bytes = nf * sizeof(FilterDeckDev) + nf * (size_t)n_ticks * sizeof(FilterTickDev);
+        // ... and the reverb's: reverbs[] names the decks with a reverb in any tick
+        struct ReverbPlan { size_t deck; std::vector<ReverbTickDev> ticks; };
+        std::vector<ReverbPlan> reverbs;
+        std::vector<DeckReverb::State> reverb_after(n);
+        for (size_t i = 0; i < n; ++i) {
+            std::vector<ReverbTickDev> rt;
+            if (decks[i]->reverb.plan(n_ticks, (uint32_t)spt, rt, reverb_after[i])) reverbs.push_back(ReverbPlan{i, std::move(rt)});
+        }
+        const size_t nr = reverbs.size(), reverb_bytes = nr * sizeof(ReverbDeckDev) + nr * (size_t)n_ticks * sizeof(ReverbTickDev);
 
         std::lock_guard<std::mutex> lock(feed_state.mu);
         Slot& sl = feed_state.slots[feed_state.next];
@@ -285,7 +297,8 @@ void Deck::feed(Deck* const* decks, const uint32_t* nodes, size_t n, Graph& g, u
         const size_t feed_bytes = nk ? plain_bytes + nk * sizeof(KlDeckDev) + nk * (size_t)n_ticks * sizeof(KlTickDev) + grain_cap * sizeof(KlGrainIn)
                                      : head_bytes + n * (size_t)n_ticks * sizeof(DeckTickDev);
         const size_t with_echo = ne ? ((feed_bytes + 15) & ~(size_t)15) + echo_bytes : feed_bytes;   // (the echo's descriptors lie behind what the two feed kernels read)
-        const size_t bytes = nf ? ((with_echo + 15) & ~(size_t)15) + filter_bytes : with_echo;        // (... and the filter's behind the echo's)
+        const size_t with_filter = nf ? ((with_echo + 15) & ~(size_t)15) + filter_bytes : with_echo;  // (... and the filter's behind the echo's)
+        const size_t bytes = nr ? ((with_filter + 15) & ~(size_t)15) + reverb_bytes : with_filter;    // (... and the reverb's behind the filter's)
         if (sl.host_cap < bytes) {
             if (sl.host) (void)hipHostFree(sl.host);
             sl.host = nullptr; sl.host_cap = 0;
@@ -393,7 +406,18 @@ void Deck::feed(Deck* const* decks, const uint32_t* nodes, size_t n, Graph& g, u
                 std::copy(filters[k].ticks.begin(), filters[k].ticks.end(), ft + k * (size_t)n_ticks);
             }
         }
-        launch_upload(sl.dev.p, sl.host, nf ? filter_at + filter_bytes : echo_used, g.stream());
+        const size_t filter_used = nf ? filter_at + filter_bytes : echo_used, reverb_at = (filter_used + 15) & ~(size_t)15;
+        if (nr) {
+            ReverbDeckDev* rd = (ReverbDeckDev*)((char*)sl.host + reverb_at);
+            ReverbTickDev* rt = (ReverbTickDev*)(rd + nr);
+            for (size_t k = 0; k < nr; ++k) {
+                Deck& d = *decks[reverbs[k].deck];
+                if (d.reverb.last_graph && d.reverb.last_graph != &g) hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");   // (its lines may still be in use on the other graph's stream)
+                rd[k] = ReverbDeckDev{(float2*)outs[reverbs[k].deck], d.reverb.lines()};
+                std::copy(reverbs[k].ticks.begin(), reverbs[k].ticks.end(), rt + k * (size_t)n_ticks);
+            }
+        }
+        launch_upload(sl.dev.p, sl.host, nr ? reverb_at + reverb_bytes : filter_used, g.stream());
         launch_deck_feed((const DeckDev*)sl.dev.p, (const DeckTickDev*)((const char*)sl.dev.p + head_bytes), tables, (uint32_t)ip, n_ticks, (uint32_t)spt, phase_varies, g.stream());
         launch_deck_keylock((const KlDeckDev*)((const char*)sl.dev.p + plain_bytes), (const KlTickDev*)((const char*)sl.dev.p + plain_bytes + nk * sizeof(KlDeckDev)), tables,
                             (uint32_t)nk, n_ticks, (uint32_t)spt, g.stream());
@@ -401,6 +425,8 @@ void Deck::feed(Deck* const* decks, const uint32_t* nodes, size_t n, Graph& g, u
                                    (uint32_t)nf, n_ticks, (uint32_t)spt, g.stream());
         if (ne) launch_deck_echo((const EchoDeckDev*)((const char*)sl.dev.p + echo_at), (const EchoTickDev*)((const char*)sl.dev.p + echo_at + ne * sizeof(EchoDeckDev)),
                                  (uint32_t)ne_block, (uint32_t)(ne - ne_block), n_ticks, (uint32_t)spt, g.stream());
+        if (nr) launch_deck_reverb((const ReverbDeckDev*)((const char*)sl.dev.p + reverb_at), (const ReverbTickDev*)((const char*)sl.dev.p + reverb_at + nr * sizeof(ReverbDeckDev)),
+                                   (uint32_t)nr, n_ticks, (uint32_t)spt, g.stream());
         hip_check(hipGetLastError(), "deck feed launch");
         hip_check(hipEventRecord(sl.done, g.stream()), "hipEventRecord");
         sl.pending = true; sl.stream = g.stream();
@@ -416,10 +442,19 @@ void Deck::feed(Deck* const* decks, const uint32_t* nodes, size_t n, Graph& g, u
             for (const FilterTickDev& t : f.ticks) if (t.flags & FILTER_TICK_ON) ++feed_state.last_filter.out[(t.flags & FILTER_TICK_RAMP) ? 1 : 2];
             feed_state.last_filter.out[3] += (uint32_t)(((uint64_t)n_ticks * spt + FILTER_BLOCK - 1) / FILTER_BLOCK);
         }
+        // mx_deck_debug_last_reverb: per deck with a reverb the reaches of its ticks
+        feed_state.last_reverb.clear();
+        for (const ReverbPlan& r : reverbs) {
+            decks[r.deck]->reverb.last_graph = &g;
+            std::vector<uint32_t> reach(n_ticks);
+            for (uint32_t t = 0; t < n_ticks; ++t) reach[t] = reverb_reach_of(r.ticks[t]);
+            feed_state.last_reverb.push_back(std::move(reach));
+        }
         for (size_t i = 0, k = 0; i < n; ++i) {
             Deck& d = *decks[i];
             d.echo.commit(echo_after[i]);
             d.filter.commit(filter_after[i]);
+            d.reverb.commit(reverb_after[i]);
             d.head_ = heads[i]; d.ticks_ = std::move(recs[i]); d.sched_.clear(); d.keylock_.last_graph = &g; d.keylock_.last_lineage = g.lineage();
             if (!d.keylock_.on) { d.keylock_.grains.clear(); d.keylock_.grains_fetched = true; continue; }
             for (const mx_deck_grain& gr : grains[k]) ++((gr.flags & MX_DECK_GRAIN_FIRST) || !d.keylock_.k.radius ? feed_state.kl_unsearched : feed_state.kl_searched);
@@ -438,6 +473,11 @@ DeckLastKeylock deck_last_keylock() {
 DeckLastEcho deck_last_echo() {
     std::lock_guard<std::mutex> lock(feed_state.mu);
     return DeckLastEcho{feed_state.last_echo, feed_state.last_spt};
+}
+
+DeckLastReverb deck_last_reverb() {
+    std::lock_guard<std::mutex> lock(feed_state.mu);
+    return DeckLastReverb{feed_state.last_reverb, feed_state.last_spt};
 }
 
 DeckLastFilter deck_last_filter() {

@@ -10,6 +10,7 @@
 #include "mx_deck_filter.hpp"
 #include "mx_deck_finegrid.hpp"
 #include "mx_deck_loudkey.hpp"
+#include "mx_deck_reverb.hpp"
 #include "mx_deck_tempomap.hpp"
 
 namespace mx {
@@ -89,8 +90,8 @@ struct DeckKlTick { KlTickDev t; uint32_t log_hop, overlap; };
 struct DeckLastKeylock { std::vector<DeckKlTick> ticks; uint32_t spt = 0, searched = 0, unsearched = 0; };
 DeckLastKeylock deck_last_keylock();
 
-// The track, the transport state machine and the feed (mx_deck.cpp), key-lock (mx_deck_keylock.cpp), the sweep filter and the echo
-// (mx_deck_filter.hpp, mx_deck_echo.hpp: members with their own setting, schedule and device memory -- four state values, a delay line), and the six whole-track analyses, each a member that holds its own results and sees of the deck a DeckTrack and nothing else (mx_deck_analysis.hpp).
+// The track, the transport state machine and the feed (mx_deck.cpp), key-lock (mx_deck_keylock.cpp), the sweep filter, the echo and the reverb
+// (mx_deck_filter.hpp, mx_deck_echo.hpp, mx_deck_reverb.hpp: members with their own setting, schedule and device memory -- four state values, a delay line, twelve rings), and the six whole-track analyses, each a member that holds its own results and sees of the deck a DeckTrack and nothing else (mx_deck_analysis.hpp).
 class Deck {
 public:
     Deck(uint64_t n_frames, int device);
@@ -133,6 +134,8 @@ public:
     DeckEcho echo{device_};
     // the sweep filter between them and the echo (the same protocol: plan, launch, commit)
     DeckFilter filter{device_};
+    // the reverb behind the echo, last of the passes (the same protocol)
+    DeckReverb reverb{device_};
 };
 
 }  // namespace mx

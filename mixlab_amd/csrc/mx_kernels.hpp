@@ -370,6 +370,10 @@ void launch_deck_filter(const FilterDeckDev* decks, const FilterTickDev* ticks, 
 // in the one-block form (decks x ticks x chunks workgroups), the n_walk decks behind them in the sequential form (a workgroup per deck); ticks: n_ticks per deck
 struct EchoDeckDev; struct EchoTickDev;
 void launch_deck_echo(const EchoDeckDev* decks, const EchoTickDev* ticks, uint32_t n_block, uint32_t n_walk, uint32_t n_ticks, uint32_t spt, hipStream_t s);
+// the reverb of the decks of a feed that have one (mx_deck_reverb.hpp, mx_k_deck_reverb.hip), in place on their ports behind all the launches above: a workgroup per
+// deck walks its blocks; ticks: n_ticks per deck
+struct ReverbDeckDev; struct ReverbTickDev;
+void launch_deck_reverb(const ReverbDeckDev* decks, const ReverbTickDev* ticks, uint32_t n_decks, uint32_t n_ticks, uint32_t spt, hipStream_t s);
 // the analysis of a deck's track (mx_deck_columns.hpp, mx_k_deck_analyse.hip): columns -> cols (n_cols x 56 bytes), their onsets -> cols and `onsets`, the autocorrelation -> R
 // (max_lag words, zeroed here first); all on stream s.  The tap tables widened to int32 and padded with zeros travel as a kernel argument.  forms[DECK_AN_*]: what was
 // launched (mx_deck_debug_last_analysis).  Settings the check passes, n_cols = ceil(n_frames / column).

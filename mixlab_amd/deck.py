@@ -30,6 +30,11 @@ The sweep filter (the header's FILTER) is the one-knob resonant filter of a tran
     deck.set_filter(filter_knob(-0.5, 48000.0))                           # a low-pass half closed, faded in over the next feed's first tick; None (the dead zone) turns it off
     deck.schedule_filter(k, kind=abi.DECK_FILTER_HP, g=0.02, k=0.5)       # ... or by the numbers, from tick k on
 
+The reverb (the header's REVERB) is a feedback delay network behind the echo, last of the deck's passes; stopping the deck under it is the reverb-out:
+
+    deck.set_reverb(reverb_design(48000.0, size=1.0, t60_seconds=2.5, wet=1.0))   # the wash, faded in over the next feed's first tick
+    deck.schedule(k, params(flags=0))                                     # PLAY cleared at tick k: the tail rings over the incoming track
+
 Bars (the header's BARS) say which beat is a bar's first and which bar a phrase's first; the two grids go where a beat grid goes:
 
     pick = deck.find_bars(beats, analysis_bands(rate=44100.0))            # pick.bars, pick.phrases: DeckBeats; pick.bar_best / pick.bar_sum the confidence
@@ -49,7 +54,7 @@ import ctypes as C
 import numpy as np
 
 from . import abi
-from .abi import (DeckAnalysis, DeckBarPick, DeckBars, DeckBeats, DeckEcho, DeckFilter, DeckFinegrid, DeckFinePick, DeckGrain, DeckGrid, DeckHead, DeckKeylock, DeckLoudness, DeckParams, DeckSyncResult, DeckTempomap,
+from .abi import (DeckAnalysis, DeckBarPick, DeckBars, DeckBeats, DeckEcho, DeckFilter, DeckFinegrid, DeckFinePick, DeckGrain, DeckGrid, DeckHead, DeckKeylock, DeckLoudness, DeckParams, DeckReverb, DeckSyncResult, DeckTempomap,
                   DeckTick, DeckTonality, check, lib)
 
 ONE = 1 << 32   # unity step / one track frame in Q32.32
@@ -391,6 +396,57 @@ def debug_last_filter() -> dict:
     return _debug_last(lib.mx_deck_debug_last_filter, ("decks", "ticks_ramp", "ticks_constant", "blocks"))
 
 
+def reverb(delay, diff, gain, send=1.0, dry=1.0, wet=0.5, damp=0.0, diffusion=0.5) -> DeckReverb:
+    """reverb settings (the header's REVERB) by the numbers: eight tank delays, four diffuser delays, eight gains; reverb_design() starts from a size and a decay time"""
+    return DeckReverb((C.c_uint32 * 8)(*[int(v) for v in delay]), (C.c_uint32 * 4)(*[int(v) for v in diff]), (C.c_float * 8)(*[float(v) for v in gain]),
+                      float(send), float(dry), float(wet), float(damp), float(diffusion), 0)
+
+
+def reverb_check(r: DeckReverb) -> None:
+    """the reverb setting rules alone (host only); raises MxError"""
+    check(lib.mx_deck_reverb_check(C.byref(r)))
+
+
+def reverb_design(rate: float, size: float = 1.0, t60_seconds: float = 2.0, damp: float = 0.3, diffusion: float = 0.5, send: float = 1.0, dry: float = 1.0,
+                  wet: float = 0.5) -> DeckReverb:
+    """the setting of a room size (0.25 .. 4) and a decay time at this rate (mx_deck_reverb_design, host only): prime delays, exact; gains good to 1 f32 ulp"""
+    out = DeckReverb()
+    check(lib.mx_deck_reverb_design(float(rate), float(size), float(t60_seconds), float(damp), float(diffusion), float(send), float(dry), float(wet), C.byref(out)))
+    return out
+
+
+def _reverb_ptrs(settings):
+    return (C.POINTER(DeckReverb) * max(1, len(settings)))(*[C.pointer(r) if r is not None else None for r in settings])
+
+
+def reverb_plan(spt: int, settings) -> list:
+    """the blocks the reverb kernel cuts a feed into, as (first frame, frames) (mx_deck_reverb_plan, host only, pure); settings: one DeckReverb or None per tick"""
+    ptrs, n_ticks, n = _reverb_ptrs(settings), len(settings), C.c_uint32()
+    check(lib.mx_deck_reverb_plan(int(spt), C.cast(ptrs, C.c_void_p) if n_ticks else None, n_ticks, None, 0, C.byref(n)))
+    out = np.zeros((max(1, n.value), 2), np.uint64)
+    check(lib.mx_deck_reverb_plan(int(spt), C.cast(ptrs, C.c_void_p) if n_ticks else None, n_ticks, out.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
+    return [(int(a), int(b)) for a, b in out[:n.value]]
+
+
+def reverb_host(frames: np.ndarray, spt: int, settings, lines: np.ndarray | None = None, carry: abi.DeckReverbCarry | None = None):
+    """(float32 frames after the reverb, the lines, the carried block) of mx_deck_reverb_host (host only, pure): frames float32 [n_ticks * spt * 2], settings one
+    DeckReverb or None per tick, lines and carry what the last call returned (None: a deck that never had a reverb)"""
+    out = np.ascontiguousarray(frames, np.float32).reshape(-1).copy()
+    n_ticks = len(settings)
+    assert out.size == n_ticks * int(spt) * 2
+    lines = np.ascontiguousarray(lines, np.float32).copy() if lines is not None else np.zeros(abi.DECK_REVERB_LINE_FLOATS, np.float32)
+    assert lines.size == abi.DECK_REVERB_LINE_FLOATS
+    carry = abi.DeckReverbCarry.from_buffer_copy(carry) if carry is not None else abi.DeckReverbCarry()
+    ptrs = _reverb_ptrs(settings)
+    check(lib.mx_deck_reverb_host(out.ctypes.data_as(C.c_void_p) if out.size else None, int(spt), n_ticks, C.cast(ptrs, C.c_void_p) if n_ticks else None,
+                                  lines.ctypes.data_as(C.c_void_p), C.byref(carry)))
+    return out, lines, carry
+
+
+def debug_last_reverb() -> dict:
+    return _debug_last(lib.mx_deck_debug_last_reverb, ("decks", "blocks", "blocks_crossing", "largest_block"))
+
+
 def bars(grid: DeckBeats, tables: DeckAnalysis | None = None, lead=128, beats_per_bar=4, bars_per_phrase=4, w_bar=4, w_phrase=8, max_beats=0) -> DeckBars:
     """bars settings (the header's BARS) on a beat grid; the tap tables are those of `tables` (mx_deck_bars_tables), a single unity tap without it"""
     s = DeckBars()
@@ -643,6 +699,29 @@ class Deck:
         s = (C.c_double * 4)()
         check(lib.mx_deck_read_filter_state(self._h, s))
         return np.array(s[:], np.float64)
+
+    def set_reverb(self, r: DeckReverb | None = None, **kw):
+        """the reverb from tick 0 of the next feed on; keywords are reverb()'s; set_reverb(None) with no keywords turns it off"""
+        r = r if r is not None else (reverb(**kw) if kw else None)
+        check(lib.mx_deck_set_reverb(self._h, C.byref(r) if r is not None else None))
+
+    def schedule_reverb(self, tick_in_feed: int, r: DeckReverb | None = None, **kw):
+        """... from that tick of the next feed on (the reverb-out: send the deck into the tail, then clear PLAY); None with no keywords turns it off there"""
+        r = r if r is not None else (reverb(**kw) if kw else None)
+        check(lib.mx_deck_schedule_reverb(self._h, int(tick_in_feed), C.byref(r) if r is not None else None))
+
+    def reverb_state(self):
+        """(clock t, on, DeckReverb in force) after the last feed; host data, no synchronisation"""
+        t, on, r = C.c_uint64(), C.c_uint32(), DeckReverb()
+        check(lib.mx_deck_reverb_state(self._h, C.byref(t), C.byref(on), C.byref(r)))
+        return t.value, bool(on.value), r
+
+    def read_reverb_lines(self) -> np.ndarray:
+        """float32 [DECK_REVERB_LINE_FLOATS]: the raw rings after the last feed, tank then diffusers (waits for the device); only the slots of the clocks in
+        [max(0, t - ring), t) are specified"""
+        out = np.zeros(abi.DECK_REVERB_LINE_FLOATS, np.float32)
+        check(lib.mx_deck_read_reverb_lines(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
 
     def _analyse(self, call, attr: str, settings, counts) -> None:
         """one analyse*() call and the counts remembered of it: settings of None free the results; refused settings (MX_ERR_INVALID) leave the deck what it
