@@ -65,7 +65,9 @@ extern "C" {
                               *    mx_deck_read_bars, mx_deck_read_bar_folds, mx_deck_bars_host, mx_deck_bars_pick, mx_deck_grid_next, mx_deck_debug_last_bars;
                               *    mx_deck_tempomap, mx_deck_tempo_segment, mx_deck_tempomap_check, mx_deck_tempomap_count, mx_deck_tempomap_span, mx_deck_tempomap_host,
                               *    mx_deck_tempomap_path, mx_deck_tempomap_segments, mx_deck_tempomap_at, mx_deck_tempomap_step, mx_deck_analyse_tempomap,
-                              *    mx_deck_read_tempomap, mx_deck_read_tempomap_onsets, mx_deck_debug_last_tempomap */
+                              *    mx_deck_read_tempomap, mx_deck_read_tempomap_onsets, mx_deck_debug_last_tempomap;
+                              *    mx_wave_colour, mx_wave_grid, mx_wave_marker, mx_wave_range, mx_deck_waveform, mx_deck_waveform_check, mx_deck_waveform_view,
+                              *    mx_deck_render_waveform, mx_deck_waveform_host, mx_deck_debug_last_waveform */
 
 /* ---- status codes (0 ok, <0 error; cf. MIXLAB_IOCTX_ERROR / MIXLAB_IOCTX_PANIC) ---- */
 enum {
@@ -1636,6 +1638,84 @@ int mx_deck_read_tempomap_onsets(mx_deck* d, uint64_t first, uint64_t n, uint32_
  * kernel's loop over k (the teeth of phase 0 at the smallest period in a window of min(W, N) hops).  One analysis takes one form: the workgroups stage when n_periods is
  * at least 2 and min(W, N) is at most MX_DECK_TEMPOMAP_STAGED_MAX, and read w from memory otherwise.  Tests use it to know every form ran. */
 int mx_deck_debug_last_tempomap(uint32_t out[4]);
+
+/* ---- WAVEFORM: the band overview of ANALYSIS rendered to a picture on the device, with beat lines, markers and ranges ----
+ * BUILD-SPECIFIED.  mx_deck_render_waveform reads the deck's column records where they lie and writes, in ONE launch, an ordinary opaque yuv420p mx_dframe: the
+ * scrolling waveform or the whole-track overview of a deck, ready for mx_video_multiview, mx_video_place, a VideoMixer or mx_graph_set_video_source.  No record is read
+ * back and no picture uploaded.  All quantities are integers.  It is deck-side work like the analyses: no module kind, nothing in a graph; a deck that never calls it
+ * is untouched in every respect.
+ *
+ * SETTINGS   mx_deck_waveform (1416 bytes): w, h even, 2 <= w <= 8192, 4 <= h <= 4320; |first_frame| <= 2^30; frames_per_px (fpp) 1 .. 2^20 with w * fpp <= 2^30;
+ *            style MX_WAVE_BANDS or MX_WAVE_ENVELOPE; every gain_q16 0 .. 2^20; n_grids <= 16, n_markers <= 32, n_ranges <= 8.  Grid: period_q32 in [2^32, 2^56],
+ *            |first_q32| <= 2^61, from_q32 <= to_q32, inset <= h / 2.  Marker: width 1 .. 16.  Range: from_frame <= to_frame.  Every _pad is 0 (the struct's, every
+ *            colour's that is looked at, every range's).  Entries at index n_* and above are not looked at.  mx_deck_waveform_check enforces exactly these rules, in
+ *            this order -- the struct's scalars, its five colours, then the grids, the markers and the ranges in entry order -- and names the broken one.
+ * COLUMN     C and N the column size and count of the analysis, half = h / 2.  Pixel column x covers the frames [F0, F1) = [first_frame + x fpp, first_frame +
+ *            (x + 1) fpp) and the analysis columns c0 = max(0, F0 >> log2 C) .. c1 = min(N - 1, (F1 - 1) >> log2 C), the shifts arithmetic (floor).  c0 > c1: the
+ *            pixel column is OUTSIDE the track.  Otherwise P_b = max peak[b], SMAX = max smax, SMIN = min smin over those columns; the short last column of a track
+ *            counts as a column (so a pixel column whose F0 lies in [n_frames, N C) is inside).
+ * HEIGHTS    BANDS: H_b = min(half, (P_b * gain_q16[b] * half) >> 32) in uint64 (at most 2^31 * 2^20 * 2^12).  With d(y) = half - 1 - y for y < half and y - half
+ *            otherwise -- rows half - 1 and half both have d = 0 -- band b covers the pixel when d < H_b.  ENVELOPE: UP = min(half, (max(SMAX, 0) * gain_q16[0] *
+ *            half) >> 32), DOWN the same from max(-SMIN, 0); the rows [half - UP, half + DOWN) are covered, in colour band[0].
+ * LAYERS     bottom to top, each luma pixel ending with one (Y, U, V): (1) bg; (2) each range in entry order whose [from_frame, to_frame) meets [F0, F1) (an empty
+ *            range meets nothing): its colour as the background; (3) inside the track, `line` on the rows with d = 0; (4) the bands low, mid, high in that order,
+ *            high on top -- or the envelope; outside the track neither; (5) each grid in entry order: rows [inset, h - inset) of every pixel column that holds one
+ *            of its lines; (6) each marker in entry order, full height: the pixel columns [xm - width / 2, xm - width / 2 + width) cut to [0, w), xm = floor((frame -
+ *            first_frame) / fpp) -- floor division, not C's truncation -- and width / 2 rounded down.  Grids and markers are drawn outside the track too.
+ * GRID LINE  n_frames the deck's track length.  F0' and F1' are F0 and F1 clamped to [0, n_frames] FIRST: with that clamp, |first_q32| <= 2^61 and period_q32 <=
+ *            2^56, no Q32 quantity below leaves int64 -- which is what those range rules buy.  A = max(F0' << 32, from_q32), B = min(F1' << 32, to_q32).  The pixel
+ *            column holds a line of the grid when A < B and first_q32 + ceil((A - first_q32) / period_q32) * period_q32 < B, the ceil mathematical for either sign:
+ *            the lines are first + k period for every integer k inside [from, to).  A beat exactly on a pixel's left edge belongs to that pixel, one on its right
+ *            edge to the next; a pixel column wholly before frame 0 or at or beyond n_frames holds no line.
+ * PLANES     luma is the pixel's Y.  Chroma sample (cx, cy) is (the sum of the four pixels' U + 2) >> 2, likewise V: a one-pixel line tints its chroma sample by a
+ *            quarter, or a half where it spans both rows, and does not vanish at odd x.  *out is a NEW opaque yuv420p frame of w x h carrying one reference; every
+ *            byte of its three planes, stride padding included, is written exactly once, and the padding holds what mx_video_multiview leaves in its canvas', which
+ *            is what mx_dframe_create leaves: Y 0, chroma 0x80.
+ * ORDER      the launch goes on `stream` (NULL: the library's default video stream) and waits ON THE DEVICE for the analysis it reads, through an event recorded
+ *            behind that analysis on the load stream: a render never waits for the host and never queues behind a later track upload.  The frame is valid on
+ *            `stream` on return, like mx_video_multiview's.  A later mx_deck_analyse -- one that rewrites the records in place, regrows them or frees them -- is
+ *            ordered behind the deck's last render through a second event, on the device where the buffer stays and by the load stream's own wait where it goes.
+ * Out of scope: dimming the played part; text; anti-aliased lines; zoom finer than the analysis' columns (analyse at C = 64 for detail); rendering from PCM; a graph tap
+ * that re-renders per tick (call this once per video frame and hand the frame to the graph as a source); more than 16 grid entries -- tempo-map segments -- a picture. */
+#define MX_WAVE_BANDS 0u
+#define MX_WAVE_ENVELOPE 1u
+#define MX_WAVE_MAX_GRIDS 16u
+#define MX_WAVE_MAX_MARKERS 32u
+#define MX_WAVE_MAX_RANGES 8u
+#define MX_WAVE_STRIP 64u                     /* pixel columns one workgroup renders over the full height; tests size their cases around it */
+typedef struct { uint8_t y, u, v, _pad; } mx_wave_colour;
+typedef struct { mx_deck_beats grid; int64_t from_q32, to_q32; mx_wave_colour colour; uint32_t inset; } mx_wave_grid;   /* 40 bytes: lines at first + k period inside [from, to) */
+typedef struct { int64_t frame; uint32_t width; mx_wave_colour colour; } mx_wave_marker;                                /* 16 bytes: cue, loop point, playhead */
+typedef struct { int64_t from_frame, to_frame; mx_wave_colour colour; uint32_t _pad; } mx_wave_range;                   /* 24 bytes: loop region, section */
+typedef struct {
+    uint32_t w, h;                 /* even; 2 <= w <= 8192, 4 <= h <= 4320 */
+    int64_t  first_frame;          /* track frame at the left edge of pixel 0; may be negative; |first_frame| <= 2^30 */
+    uint32_t frames_per_px;        /* 1 .. 2^20, and w * frames_per_px <= 2^30 */
+    uint32_t style;                /* MX_WAVE_BANDS | MX_WAVE_ENVELOPE */
+    uint32_t gain_q16[3];          /* per band (ENVELOPE uses [0]); 0 .. 2^20 */
+    mx_wave_colour bg, line, band[3];
+    uint32_t n_grids, n_markers, n_ranges;
+    uint32_t _pad;
+    mx_wave_grid grid[MX_WAVE_MAX_GRIDS]; mx_wave_marker marker[MX_WAVE_MAX_MARKERS]; mx_wave_range range[MX_WAVE_MAX_RANGES];
+} mx_deck_waveform;                /* 1416 bytes: first_frame 8, frames_per_px 16, gain_q16 24, bg 36, n_grids 56, grid 72, marker 712, range 1224 */
+/* Host only: the SETTINGS rules alone; MX_ERR_INVALID names the rule in mx_last_error. */
+int mx_deck_waveform_check(const mx_deck_waveform* p);
+/* Host only: *first_frame = (pos_q32 >> 32) - playhead_x * frames_per_px (arithmetic shift), the first_frame that puts the playing position in pixel column playhead_x.
+ * frames_per_px outside 1 .. 2^20, playhead_x above 8191, a result beyond +-2^30, NULL: MX_ERR_INVALID. */
+int mx_deck_waveform_view(int64_t pos_q32, uint32_t frames_per_px, uint32_t playhead_x, int64_t* first_frame);
+/* Render the deck's current column analysis under *p into a new frame, asynchronous on `stream` (ORDER).  Refusals, in this order: a deck without a column analysis
+ * MX_ERR_INVALID; settings the check refuses MX_ERR_INVALID; memory MX_ERR_NOMEM.  In each case *out is untouched and the deck stands as it was. */
+struct mx_dframe;   /* the pixel path's device frame, below */
+int mx_deck_render_waveform(mx_deck* d, const mx_deck_waveform* p, struct mx_dframe** out, void* stream);
+/* Host only, pure: the same picture in plain C++ from n_cols records of an analysis at `column` of a track of n_frames (n_cols = ceil(n_frames / column), otherwise
+ * MX_ERR_INVALID): the visible area alone -- w bytes of each of h rows at y, w / 2 bytes of each of h / 2 rows at u and v; bytes beyond it are not touched.  Strides
+ * below the visible width, settings the check refuses, a column or n_frames ANALYSIS refuses, NULL: MX_ERR_INVALID.  How the rules are tested without a device. */
+int mx_deck_waveform_host(const mx_deck_column* cols, uint64_t n_cols, uint32_t column, uint64_t n_frames, const mx_deck_waveform* p,
+                          uint8_t* y, int32_t y_stride, uint8_t* u, uint8_t* v, int32_t c_stride);
+/* DEBUG: what the last mx_deck_render_waveform of this process launched, in strips of MX_WAVE_STRIP pixel columns (a workgroup each): out[0] strips whose pixel columns
+ * each held at most one record (and at least one of them one), out[1] strips that reduced several records in some pixel column, out[2] strips wholly outside the track,
+ * out[3] the largest number of records one strip read.  Tests use it to know every form ran. */
+int mx_deck_debug_last_waveform(uint32_t out[4]);
 
 /* ---------------------------------------------------------------------------------------------- */
 /* pixel path: device-resident yuv420p frames, VideoMixer, scaler, colour                          */

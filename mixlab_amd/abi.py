@@ -569,6 +569,27 @@ _proto("mx_deck_analyse_tempomap", C.c_int, C.c_void_p, C.POINTER(DeckTempomap))
 _proto("mx_deck_read_tempomap", C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p)
 _proto("mx_deck_read_tempomap_onsets", C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p)
 _proto("mx_deck_debug_last_tempomap", C.c_int, C.POINTER(C.c_uint32))
+# ... its waveform picture (the header's WAVEFORM): the columns rendered to a yuv420p frame on the device, with beat lines, markers and ranges
+WAVE_BANDS, WAVE_ENVELOPE = 0, 1       # MX_WAVE_BANDS, MX_WAVE_ENVELOPE
+WAVE_MAX_GRIDS, WAVE_MAX_MARKERS, WAVE_MAX_RANGES = 16, 32, 8
+WAVE_STRIP = 64                        # MX_WAVE_STRIP: pixel columns one workgroup renders
+class WaveColour(C.Structure):
+    _fields_ = [("y", C.c_uint8), ("u", C.c_uint8), ("v", C.c_uint8), ("_pad", C.c_uint8)]
+class WaveGrid(C.Structure):
+    _fields_ = [("grid", DeckBeats), ("from_q32", C.c_int64), ("to_q32", C.c_int64), ("colour", WaveColour), ("inset", C.c_uint32)]
+class WaveMarker(C.Structure):
+    _fields_ = [("frame", C.c_int64), ("width", C.c_uint32), ("colour", WaveColour)]
+class WaveRange(C.Structure):
+    _fields_ = [("from_frame", C.c_int64), ("to_frame", C.c_int64), ("colour", WaveColour), ("_pad", C.c_uint32)]
+class DeckWaveform(C.Structure):
+    _fields_ = [("w", C.c_uint32), ("h", C.c_uint32), ("first_frame", C.c_int64), ("frames_per_px", C.c_uint32), ("style", C.c_uint32), ("gain_q16", C.c_uint32 * 3),
+                ("bg", WaveColour), ("line", WaveColour), ("band", WaveColour * 3), ("n_grids", C.c_uint32), ("n_markers", C.c_uint32), ("n_ranges", C.c_uint32),
+                ("_pad", C.c_uint32), ("grid", WaveGrid * WAVE_MAX_GRIDS), ("marker", WaveMarker * WAVE_MAX_MARKERS), ("range", WaveRange * WAVE_MAX_RANGES)]
+_proto("mx_deck_waveform_check", C.c_int, C.POINTER(DeckWaveform))
+_proto("mx_deck_waveform_view", C.c_int, C.c_int64, C.c_uint32, C.c_uint32, C.POINTER(C.c_int64))
+_proto("mx_deck_render_waveform", C.c_int, C.c_void_p, C.POINTER(DeckWaveform), C.POINTER(C.c_void_p), C.c_void_p)
+_proto("mx_deck_waveform_host", C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.POINTER(DeckWaveform), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32)
+_proto("mx_deck_debug_last_waveform", C.c_int, C.POINTER(C.c_uint32))
 _proto("mx_module_create", C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p))
 _proto("mx_module_create_ex", C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(GraphOpts), C.POINTER(C.c_void_p))
 _proto("mx_module_update", C.c_int, C.c_void_p, C.c_void_p, C.c_size_t)

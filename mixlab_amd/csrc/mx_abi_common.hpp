@@ -12,6 +12,7 @@
 
 struct mx_graph { std::unique_ptr<mx::Graph> g; };
 
+namespace mx { hipStream_t abi_video_stream(void* stream); }   // mx_abi_video.cpp: a pixel call's stream (NULL: the library's default video stream), its deferred scaler work flushed
 void mx_set_last_error(const std::string& s);   // mx_abi.cpp: the one writer of the thread-local behind mx_last_error
 
 template <class F>

@@ -8,7 +8,9 @@
 #include <vector>
 
 #include "mx_deck.hpp"
+#include "mx_deck_waveform.hpp"
 #include "mx_engine.hpp"
+#include "mx_video.hpp"
 #include "mx_abi_common.hpp"
 
 using mx::Deck;
@@ -398,6 +400,26 @@ int mx_deck_read_tempomap_onsets(mx_deck* d, uint64_t first, uint64_t n, uint32_
 }
 int mx_deck_debug_last_tempomap(uint32_t out[4]) {
     return guard([&] { REQUIRE(out, "out is NULL"); mx::DeckTempoMap::debug_last(out); });
+}
+int mx_deck_waveform_check(const mx_deck_waveform* p) {
+    return guard([&] { REQUIRE(p, "settings are NULL"); mx::deck_waveform_check(*p); });
+}
+int mx_deck_waveform_view(int64_t pos_q32, uint32_t frames_per_px, uint32_t playhead_x, int64_t* first_frame) {
+    return guard([&] { REQUIRE(first_frame, "first_frame is NULL"); *first_frame = mx::deck_waveform_view(pos_q32, frames_per_px, playhead_x); });
+}
+int mx_deck_render_waveform(mx_deck* d, const mx_deck_waveform* p, mx_dframe** out, void* stream) {
+    return guard([&] {
+        REQUIRE(d && p && out, "NULL argument");
+        mx::DFrame* f = d->d.columns.render_waveform(*p, mx::abi_video_stream(stream));   // (*out is written only once the launch is on the stream)
+        *out = reinterpret_cast<mx_dframe*>(f);
+    });
+}
+int mx_deck_waveform_host(const mx_deck_column* cols, uint64_t n_cols, uint32_t column, uint64_t n_frames, const mx_deck_waveform* p,
+                          uint8_t* y, int32_t y_stride, uint8_t* u, uint8_t* v, int32_t c_stride) {
+    return guard([&] { REQUIRE(p, "settings are NULL"); mx::deck_waveform_host(cols, n_cols, column, n_frames, *p, y, y_stride, u, v, c_stride); });
+}
+int mx_deck_debug_last_waveform(uint32_t out[4]) {
+    return guard([&] { REQUIRE(out, "out is NULL"); mx::deck_debug_last_waveform(out); });
 }
 
 }  // extern "C"

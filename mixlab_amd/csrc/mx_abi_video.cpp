@@ -34,6 +34,7 @@ static hipStream_t S(void* stream) {
     mx::flush_scales(s);   // every stateless entry point starts from a stream with no deferred scaler work
     return s;
 }
+namespace mx { hipStream_t abi_video_stream(void* stream) { return S(stream); } }
 
 extern "C" {
 

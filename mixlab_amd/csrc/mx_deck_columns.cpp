@@ -142,10 +142,20 @@ static DeckLastForms last_columns;   // mx_deck_debug_last_analysis
 
 DeckColumns::DeckColumns(const DeckTrack& deck) : DeckTrackAnalysis(deck, last_columns) {}
 
+DeckColumns::~DeckColumns() {   // (the deck has waited for the device by now)
+    if (analysed_) (void)hipEventDestroy(analysed_);
+    if (rendered_) (void)hipEventDestroy(rendered_);
+}
+
 void DeckColumns::analyse(const mx_deck_analysis* a) {
     if (a) deck_analysis_check(*a);
     const uint64_t N = a ? deck_column_count(deck_.n_frames, a->column) : 0;
     const size_t need = a ? (size_t)N * sizeof(mx_deck_column) + (size_t)a->max_lag * sizeof(uint64_t) + (size_t)N * sizeof(uint32_t) : 0;
+    hip_check(hipSetDevice(deck_.device), "hipSetDevice");
+    if (a && !analysed_) hip_check(hipEventCreateWithFlags(&analysed_, hipEventDisableTiming), "hipEventCreate");
+    // a render in flight on another stream still reads the records: the load stream waits for it on the device, so the rewrite in place is ordered behind it, and so
+    // is prepare()'s host wait for the load stream where the buffer goes
+    if (rendered_) hip_check(hipStreamWaitEvent(deck_.load_stream, rendered_, 0), "hipStreamWaitEvent(deck waveform)");
     if (!prepare(need, !a)) return;
     DeckAnalyseTaps taps{};
     for (uint32_t k = 0; k < a->taps; ++k) { taps.lo[k] = a->lo[k]; taps.hi[k] = a->hi[k]; }
@@ -153,7 +163,9 @@ void DeckColumns::analyse(const mx_deck_analysis* a) {
     uint32_t forms[4];
     launch_deck_analyse(deck_.track, deck_.n_frames, a->column, a->taps, a->max_lag, taps, buf_.p, (uint32_t*)(R + a->max_lag), R, N, forms, deck_.load_stream);
     lag_ = a->max_lag;
+    column_ = a->column;
     launched("deck analyse launch", N, forms);
+    hip_check(hipEventRecord(analysed_, deck_.load_stream), "hipEventRecord");   // what a render waits for, on the device
 }
 
 void DeckColumns::read_columns(uint64_t first, uint64_t n, mx_deck_column* dst) {

@@ -5,6 +5,8 @@
 
 namespace mx {
 
+struct DFrame;
+
 void deck_analysis_check(const mx_deck_analysis& a);                                 // throws Error(MX_ERR_INVALID) naming the rule
 void deck_analysis_bands(double rate, double f_lo, double f_hi, uint32_t taps, mx_deck_analysis& a);
 uint64_t deck_column_count(uint64_t n_frames, uint32_t column);
@@ -15,12 +17,19 @@ void deck_beatgrid(const mx_deck_column* cols, uint64_t n_cols, const uint64_t* 
 class DeckColumns : public DeckTrackAnalysis {
 public:
     explicit DeckColumns(const DeckTrack& deck);
+    ~DeckColumns();
     void analyse(const mx_deck_analysis* a);                               // NULL: frees the results.  Asynchronous on the load stream.
     void read_columns(uint64_t first, uint64_t n, mx_deck_column* dst);    // waits for the analysis
     void read_autocorr(uint64_t* R, uint32_t cap);                         // waits for the analysis
     static void debug_last(uint32_t out[4]);
+    // The waveform picture of the records (mx_deck_waveform.cpp; include/mixlab_gpu.h "WAVEFORM"): a new frame with one reference, launched on s behind analysed_,
+    // with no host wait.  rendered_ follows the last render on its stream: analyse() makes the load stream wait for it before the records are rewritten or go.
+    DFrame* render_waveform(const mx_deck_waveform& p, hipStream_t s);
 private:
     uint32_t lag_ = 0;
+    uint32_t column_ = 0;
+    hipEvent_t analysed_ = nullptr;   // behind the last analysis on the load stream (created by the first analysis)
+    hipEvent_t rendered_ = nullptr;   // behind the last render on its stream (created by the first render)
 };
 
 }  // namespace mx

@@ -381,5 +381,9 @@ struct DeckAnalyseTaps { int32_t lo[128], hi[128]; };
 enum { DECK_AN_SEVERAL = 0, DECK_AN_TILED = 1, DECK_AN_SHORT = 2, DECK_AN_ONE = 3 };
 void launch_deck_analyse(const uint32_t* track, uint64_t n_frames, uint32_t column, uint32_t K, uint32_t max_lag, const DeckAnalyseTaps& taps, void* cols, uint32_t* onsets,
                          uint64_t* R, uint64_t n_cols, uint32_t forms[4], hipStream_t s);
+// the waveform picture of a deck's columns (mx_deck_waveform.hpp, mx_k_deck_waveform.hip): ceil(w / 64) workgroups, each a strip of 64 pixel columns over the full height
+// of the three planes; every byte of a.plane[0 .. 3) is written once.  Settings the check passes; a.stride_y = 64 * ceil(w / 64), a.stride_c = a multiple of 64 >= w / 2.
+struct WaveArgs;
+void launch_deck_waveform(const WaveArgs& a, hipStream_t s);
 
 }  // namespace mx

@@ -46,6 +46,13 @@ The tempo map (the header's TEMPO MAP) follows a track whose tempo drifts: a gri
     segs = deck.map_tempo(deck.refine_grid(grid, 512, 44100.0))           # abi.DECK_TEMPO_SEGMENT_DTYPE, one per window
     beats, _ = tempomap_at(segs, deck.state().pos_q32)                    # the DeckBeats in force here: goes where a beat grid goes, asked again tick by tick
     deck.schedule_warp(segs, out_period_q32, n_ticks, spt)                # before each feed: the drifting track comes out at one constant beat length
+
+The waveform (the header's WAVEFORM) turns the analysis' columns into a picture on the device, once per video frame -- no record is read back, no picture uploaded:
+
+    first = waveform_view(deck.state().pos_q32, 100, 480)                 # the playing position under pixel column 480 at 100 frames a pixel
+    p = waveform(1920, 128, first, 100, gain_q16=(6, 12, 24), grids=[wave_grid(beats, (90, 128, 128)), wave_grid(pick.bars, (235, 128, 128))],
+                 markers=[wave_marker(deck.state().pos_q32 >> 32, (255, 128, 128), width=2)], ranges=[wave_range(loop_in, loop_out, (60, 110, 140))])
+    frame = deck.render_waveform(p)                                       # a video.DFrame: into multiview(), place(), a VideoMixer or a graph's video source
 """
 from __future__ import annotations
 
@@ -55,7 +62,7 @@ import numpy as np
 
 from . import abi
 from .abi import (DeckAnalysis, DeckBarPick, DeckBars, DeckBeats, DeckEcho, DeckFilter, DeckFinegrid, DeckFinePick, DeckGrain, DeckGrid, DeckHead, DeckKeylock, DeckLoudness, DeckParams, DeckReverb, DeckSyncResult, DeckTempomap,
-                  DeckTick, DeckTonality, check, lib)
+                  DeckTick, DeckTonality, DeckWaveform, WaveColour, WaveGrid, WaveMarker, WaveRange, check, lib)
 
 ONE = 1 << 32   # unity step / one track frame in Q32.32
 
@@ -592,6 +599,89 @@ def debug_last_tempomap() -> dict:
     return _debug_last(lib.mx_deck_debug_last_tempomap, ("wgs_staged", "wgs_global", "wgs_onset", "trip"))
 
 
+def _colour(c) -> WaveColour:
+    return c if isinstance(c, WaveColour) else WaveColour(int(c[0]), int(c[1]), int(c[2]), 0)
+
+
+def wave_grid(grid, colour, from_q32: int = -(1 << 62), to_q32: int = 1 << 62, inset: int = 0, which: str = "bars") -> WaveGrid:
+    """one grid entry of a waveform from a DeckBeats, a DeckFinePick (its grid) or a DeckBarPick (its bars, or its phrases with which="phrases")"""
+    if isinstance(grid, DeckFinePick):
+        grid = grid.grid
+    elif isinstance(grid, DeckBarPick):
+        grid = grid.phrases if which == "phrases" else grid.bars
+    return WaveGrid(DeckBeats(int(grid.first_q32), int(grid.period_q32)), int(from_q32), int(to_q32), _colour(colour), int(inset))
+
+
+def wave_grids_tempomap(segs: np.ndarray, colour, inset: int = 0, end_q32: int = 1 << 62) -> list:
+    """one grid entry per tempo-map segment that places beats (tempomap_segments' records), each over [its start, the next one's start); a picture takes 16"""
+    out = []
+    for v in range(len(segs)):
+        if int(segs[v]["period_q32"]) <= 0:
+            continue
+        start = max(int(segs[v]["start_q32"]), -(1 << 62))
+        stop = int(segs[v + 1]["start_q32"]) if v + 1 < len(segs) else int(end_q32)
+        if start < stop:
+            out.append(WaveGrid(DeckBeats(int(segs[v]["first_q32"]), int(segs[v]["period_q32"])), start, stop, _colour(colour), int(inset)))
+    return out
+
+
+def wave_marker(frame: int, colour, width: int = 1) -> WaveMarker:
+    return WaveMarker(int(frame), int(width), _colour(colour))
+
+
+def wave_range(from_frame: int, to_frame: int, colour) -> WaveRange:
+    return WaveRange(int(from_frame), int(to_frame), _colour(colour), 0)
+
+
+def waveform(w: int, h: int, first_frame: int, frames_per_px: int, style: int = abi.WAVE_BANDS, gain_q16=(1 << 16, 1 << 16, 1 << 16), bg=(16, 128, 128),
+             line=(64, 128, 128), band=((81, 90, 240), (145, 54, 34), (210, 146, 16)), grids=(), markers=(), ranges=()) -> DeckWaveform:
+    """waveform settings (the header's WAVEFORM); colours are (Y, U, V); grids / markers / ranges from wave_grid(), wave_marker(), wave_range()"""
+    if len(grids) > abi.WAVE_MAX_GRIDS or len(markers) > abi.WAVE_MAX_MARKERS or len(ranges) > abi.WAVE_MAX_RANGES:
+        raise ValueError("a waveform takes 16 grids, 32 markers and 8 ranges at the most")
+    p = DeckWaveform()
+    p.w, p.h, p.first_frame, p.frames_per_px, p.style = int(w), int(h), int(first_frame), int(frames_per_px), int(style)
+    for b in range(3):
+        p.gain_q16[b] = int(gain_q16[b])
+        p.band[b] = _colour(band[b])
+    p.bg, p.line = _colour(bg), _colour(line)
+    p.n_grids, p.n_markers, p.n_ranges = len(grids), len(markers), len(ranges)
+    for k, g in enumerate(grids):
+        p.grid[k] = g
+    for k, m in enumerate(markers):
+        p.marker[k] = m
+    for k, r in enumerate(ranges):
+        p.range[k] = r
+    return p
+
+
+def waveform_check(p: DeckWaveform) -> None:
+    """the waveform setting rules alone (host only); raises MxError"""
+    check(lib.mx_deck_waveform_check(C.byref(p)))
+
+
+def waveform_view(pos_q32: int, frames_per_px: int, playhead_x: int) -> int:
+    """the first_frame that puts the position pos_q32 in pixel column playhead_x (mx_deck_waveform_view, host only)"""
+    f = C.c_int64()
+    check(lib.mx_deck_waveform_view(int(pos_q32), int(frames_per_px), int(playhead_x), C.byref(f)))
+    return f.value
+
+
+def waveform_host(cols: np.ndarray, column: int, n_frames: int, p: DeckWaveform, y_stride: int | None = None, c_stride: int | None = None, fill: int = 0):
+    """the picture in plain C++ on the host (pure): (y, u, v) uint8 arrays of h x y_stride, h / 2 x c_stride and again, pre-filled with `fill`; the picture is
+    their first w (w / 2) columns, and the rest is left alone"""
+    cols = np.ascontiguousarray(cols, dtype=COLUMN_DTYPE)
+    ys, cs = int(p.w if y_stride is None else y_stride), int(p.w // 2 if c_stride is None else c_stride)
+    y = np.full((p.h, max(1, ys)), fill, np.uint8)
+    u, v = np.full((p.h // 2, max(1, cs)), fill, np.uint8), np.full((p.h // 2, max(1, cs)), fill, np.uint8)
+    check(lib.mx_deck_waveform_host(cols.ctypes.data_as(C.c_void_p) if cols.size else None, cols.size, int(column), int(n_frames), C.byref(p),
+                                    y.ctypes.data_as(C.c_void_p), ys, u.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p), cs))
+    return y, u, v
+
+
+def debug_last_waveform() -> dict:
+    return _debug_last(lib.mx_deck_debug_last_waveform, ("strips_single", "strips_several", "strips_outside", "max_records"))
+
+
 _NOT_GIVEN = object()   # Deck.analyse_finegrid: no settings argument at all, as against None
 
 
@@ -753,6 +843,14 @@ class Deck:
         R = np.zeros(max(1, cap), np.uint64)
         check(lib.mx_deck_read_autocorr(self._h, R.ctypes.data_as(C.c_void_p), int(cap)))
         return R[:lag]
+
+    def render_waveform(self, p: DeckWaveform, stream=None):
+        """the analysis' columns as a picture under p (waveform()): a new opaque yuv420p video.DFrame, asynchronous on `stream` (None: the library's video
+        stream), ordered behind the analysis on the device; no analysis, or settings the check refuses: MxError, the deck as it was"""
+        from . import video
+        h = C.c_void_p()
+        check(lib.mx_deck_render_waveform(self._h, C.byref(p), C.byref(h), stream))
+        return video.DFrame(handle=h.value, stream=stream)
 
     def analyse_tonality(self, t: DeckTonality | None = None, **kw):
         """the whole track's constant-Q sums per segment, asynchronously on the deck's own stream; keywords are tonality()'s; analyse_tonality(None) frees them"""

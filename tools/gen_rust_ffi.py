@@ -143,6 +143,8 @@ class Header:
             self.opaque.append(m.group(2))
             self.order.append(("opaque", m.group(2)))
             return
+        if re.match(r"^struct\s+\w+$", s):   # a forward declaration of a handle whose typedef follows further down: nothing to emit
+            return
         m = re.match(r"^((?:const\s+)?\w+\s*\**)\s*(mx_\w+)\s*\((.*)\)$", s)
         if m:
             params = []
